@@ -2,7 +2,7 @@
 """Benchmark of the MI355X ray-cast/shade path: Mray/s (primary + shadow + secondary rays) at
 1920x1080, SAMPLES=64 (BASELINE.json `metric`).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload big-scene] [--traversal flat|kd|hier]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload big-scene] [--traversal flat|kd|hier] [--full] [--dump-outputs DIR]
 
 A "step" is one full frame of the workload, inputs resident in HBM (scene uploaded once, background
 rows on the device) when the timed region starts. With N > 1 (launched by torch.distributed.run, one
@@ -16,7 +16,12 @@ which scatters them into the row-major image: fixed total work, so `scaling` is 
               `--backend gloo` on CPU tensors for tests) - the cross-check of the node path.
 Rank 0 prints one JSON line.
 
-The line also carries
+A plain run sets up, warms up, times the K steps and prints the headline (`value`, `ms_per_step`, the ray counts of a frame).
+  --dump-outputs DIR  after the timed steps, the image the last step assembled on GPU 0, as DIR/image.npy (float32, rows x
+              columns x RGB, 0..255); an image of more than 64 MB as float32 is written as a fixed sample of its pixels
+              (DIR/image_sample.npy and the pixel indices, DIR/image_sample_pixels.npy).
+  --full      everything else the benchmark measures, after the timed steps: the line then also carries
+
   roofline     : the kernel is bound by VALU issue, not by HBM or MFMA: `frac` = the time the vector ALUs need
                  for SURVEY 8(d)'s algorithmic operations of one launch (f64 operations and the instructions the shipped
                  tree step issues, one slot each, at 39.3 T slots/s) over the kernel's launch duration measured live with
@@ -26,7 +31,10 @@ The line also carries
                  beside the bytes the frame needs, so that wasted traffic shows;
   secondary    : big-soup and the mirror scene at the metric's size (N = 1 default run);
   cpu_baseline : the CPU oracle (a C restatement of the reference, kind "port") timed on this box's
-                 host cores on a bounded sample of the same workload: median of 3, pixel loop only.
+                 host cores on a bounded sample of the same workload: median of 3, pixel loop only;
+  config       : two frames in flight, the host-buffer path, the warm preparation, the default semantics (N = 1),
+                 the frames one at a time and the per-rank kernel times (N > 1 through pt_node).
+  --no-extras / --no-cpu-baseline leave parts of that out.
 """
 import argparse
 import json
@@ -194,6 +202,24 @@ def row_background(h):
     return np.ascontiguousarray(np.array([0.2, 0.4, 0.6])[None, :] * (1.0 - v)[:, None] + np.array([0.0, 0.0, 1.0])[None, :] * v[:, None])
 
 
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(out_dir, img):
+    """--dump-outputs: the image of the last timed step (rows x columns x RGB, uint8) as float32. An image larger than DUMP_LIMIT_BYTES as
+    float32 is written as a fixed sample of its pixels (seed 0, in row-major order) beside their row-major indices, the two files within the limit."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    if img.size * 4 <= DUMP_LIMIT_BYTES:
+        np.save(os.path.join(out_dir, "image.npy"), img.astype(np.float32))
+        return
+    pixels = img.reshape(-1, img.shape[-1])
+    k = (DUMP_LIMIT_BYTES - 4096) // (pixels.shape[1] * 4 + 8)  # float32 colour + float64 index per pixel; 4096 B for the two headers
+    idx = np.sort(np.random.default_rng(0).choice(len(pixels), size=k, replace=False))
+    np.save(os.path.join(out_dir, "image_sample.npy"), pixels[idx].astype(np.float32))
+    np.save(os.path.join(out_dir, "image_sample_pixels.npy"), idx.astype(np.float64))
+
+
 def secondary_workload(host, H, lib, name, device, copy_gbps):
     """big-soup (1.25 M baked triangles: the one input beyond the caches) and the mirror scene (reflection recursion) at the
     metric's size, 1920x1080 SAMPLES=64, flat_scene semantics, kernel time from HIP events."""
@@ -251,8 +277,10 @@ def main():
     ap.add_argument("--via", default="node", choices=["node", "torch"], help="N > 1: the product's pt_node_* on rank 0 (default), or torch.distributed's gather with one process per GPU")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"], help="--via torch: the collective's backend")
     ap.add_argument("--same-device", action="store_true", help="testing on a 1-GPU box: every rank uses GPU 0")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="profiling: only the headline kernel (no host-buffer pass, no default-semantics pass)")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also the roofline (with its copy-bandwidth run), the extra passes and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write the image of the last step to DIR/image.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: no CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="--full, profiling: only the headline kernel (no host-buffer pass, no default-semantics pass)")
     ap.add_argument("--check", action="store_true", help="compare rank 0's assembled image with a single-GPU render")
     ap.add_argument("--overlap", action="store_true", help="N = 1 measurements: the timed frames two at a time on the context's two streams (the next frame's wavefronts start "
                     "in the places this frame's tail frees); kernel times of overlapped launches cover each other, so `roofline` is not to be read from such a line")
@@ -261,6 +289,8 @@ def main():
     ap.add_argument("--share", type=int, default=1, help="testing: render only one rank's tiles of an N-rank partition (no gather)")
     ap.add_argument("--share-rank", type=int, default=0, help="testing: which rank's tiles --share renders")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # Plain `python bench.py --gpus N`: this process becomes a launcher. It has not touched the GPU (no
@@ -370,7 +400,13 @@ def main():
                 kernel_ms, _ = state["frames"](args.steps, not args.no_pipeline)
             dist.barrier()
             elapsed = time.perf_counter() - t0
-            if rank == 0:  # untimed: the same frames one at a time, for what the host adds to a frame that nothing overlaps
+            if rank == 0 and args.dump_outputs:  # every frame is closed: the image on GPU 0 is the last one's
+                pp = H.PtRenderParams(w, h, H.PtRect(0, 0, w - 1, h - 1), s, 0, H.SAMPLE_RNG, 1, 0, world, 0)
+                img = np.zeros((h, w, 3), dtype=np.uint8)
+                if lib.pt_node_download_image(state["node"], C.byref(pp), img.ctypes.data_as(H._u8p)) != 0:
+                    raise RuntimeError("pt_node_download_image: " + lib.pt_node_last_error(state["node"]).decode())
+                dump_outputs(args.dump_outputs, img)
+            if rank == 0 and args.full:  # untimed: the same frames one at a time, for what the host adds to a frame that nothing overlaps
                 t1 = time.perf_counter()
                 lat_kernel, lat_host = state["frames"](max(args.steps, 3), False)
                 state["latency"] = ((time.perf_counter() - t1) * 1e3 / max(args.steps, 3), lat_kernel, lat_host)
@@ -521,6 +557,7 @@ def main():
     kernel_ms = []
     last = None
     overlapped = args.overlap and not use_dist
+    last_image = d_full  # the buffer the last timed frame is assembled in
     if overlapped:
         d_alt = C.c_void_p()
         check(lib.pt_device_alloc(ctx, w * h * 3, C.byref(d_alt)), "pt_device_alloc")
@@ -529,7 +566,8 @@ def main():
         t0 = time.perf_counter()
         for k in range(args.steps):
             slot = int(lib.pt_context_next_slot(ctx))
-            check(lib.pt_render_device(ctx, C.byref(cam), d_bg, C.byref(pp2), 0, d_full if slot == 0 else d_alt, C.c_void_p(lib.pt_context_stream(ctx, slot))), "pt_render_device")
+            last_image = d_full if slot == 0 else d_alt
+            check(lib.pt_render_device(ctx, C.byref(cam), d_bg, C.byref(pp2), 0, last_image, C.c_void_p(lib.pt_context_stream(ctx, slot))), "pt_render_device")
             if k > 0:
                 check(lib.pt_render_finish(ctx, C.byref(st2)), "pt_render_finish")
                 kernel_ms.append(st2.kernel_ms)
@@ -549,6 +587,12 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
+    if args.dump_outputs and rank == 0:
+        check(lib.pt_synchronize(ctx), "pt_synchronize")
+        img = np.zeros((h, w, 3), dtype=np.uint8)
+        check(lib.pt_copy_from_device(ctx, img.ctypes.data_as(C.c_void_p), last_image, img.nbytes), "pt_copy_from_device")
+        dump_outputs(args.dump_outputs, img)
+
     ok = None
     if args.check and rank == 0:
         img = np.zeros((h, w, 3), dtype=np.uint8)
@@ -558,12 +602,6 @@ def main():
         ok = bool(np.array_equal(img, one))
 
     if rank == 0:
-        mean_kernel_s = float(np.mean(kernel_ms)) * 1e-3
-        own_pixels = compact_bytes // 3 if use_dist else w * h
-        mine_bytes = algorithmic_bytes(counts, n_lights, own_pixels, args.traversal)
-        at_config_size = (w, h, s) == WORKLOADS[args.workload][2:] and args.share == 1
-        copy_gbps = C.c_double(0.0)
-        check(lib.pt_measure_copy_bandwidth(ctx, 1 << 30, 5, C.byref(copy_gbps)), "pt_measure_copy_bandwidth")  # this box's copy bandwidth, beside the 8 TB/s of the data sheet
         prep = renderer.prepare_ms()
         out = headline(args, example, w, h, s, world, rays_frame, elapsed, total)
         out["config"]["collective"] = ({"via": "torch.distributed gather, one process per GPU" + (f" (fell back from pt_node: {node_note})" if node_note else ""),
@@ -571,11 +609,18 @@ def main():
                                         "per_frame": "one gather of %d B per rank" % compact_bytes} if use_dist else None)
         # what a drop-in pays before the first pixel (the reference converts the scene inside every render call, render.rs:115-126)
         out["config"]["prepare_ms"] = dict(prep, scene_script=(t_prep1 - t_prep0) * 1e3, renderer_total=(t_prep2 - t_prep1) * 1e3)
-        out["roofline"] = roofline_block(f"{args.workload}/{args.traversal}/gpus{world}", at_config_size, last, mine_bytes, mean_kernel_s, float(copy_gbps.value),
-                                         counts, total, rays_frame, n_lights, args.traversal, needed_hbm_bytes(export, own_pixels, (s + 7) // 8))
         if ok is not None:
             out["config"]["assembled_image_equals_single_gpu_render"] = ok
-        if world == 1 and not args.no_extras:
+        if args.full:
+            mean_kernel_s = float(np.mean(kernel_ms)) * 1e-3
+            own_pixels = compact_bytes // 3 if use_dist else w * h
+            mine_bytes = algorithmic_bytes(counts, n_lights, own_pixels, args.traversal)
+            at_config_size = (w, h, s) == WORKLOADS[args.workload][2:] and args.share == 1
+            copy_gbps = C.c_double(0.0)
+            check(lib.pt_measure_copy_bandwidth(ctx, 1 << 30, 5, C.byref(copy_gbps)), "pt_measure_copy_bandwidth")  # this box's copy bandwidth, beside the 8 TB/s of the data sheet
+            out["roofline"] = roofline_block(f"{args.workload}/{args.traversal}/gpus{world}", at_config_size, last, mine_bytes, mean_kernel_s, float(copy_gbps.value),
+                                             counts, total, rays_frame, n_lights, args.traversal, needed_hbm_bytes(export, own_pixels, (s + 7) // 8))
+        if args.full and world == 1 and not args.no_extras:
             # Two frames in flight on the context's two streams (ABI 8, pt_context_stream): the next frame's wavefronts start where this frame's tail frees
             # places. Reported beside `value`, never as it: `value` keeps one frame at a time, so that the kernel time under the roofline stays one launch's own.
             d_alt = C.c_void_p()
@@ -596,13 +641,13 @@ def main():
             out["config"]["two_frames_in_flight"] = {"ms_per_frame": ms_o, "Mray_per_s": rays_frame / ms_o / 1e3, "frames": nfr,
                                                      "note": "pt_render_device on pt_context_stream(ctx, k & 1), the older frame closed after the newer one is queued"}
             lib.pt_device_free(ctx, d_alt)
-        if world == 1 and not args.no_extras:
+        if args.full and world == 1 and not args.no_extras:
             # the same frame through pt_render (host buffers in and out: background upload, image
             # round trip over PCIe): reported for reference, never used as `value`
             img = np.zeros((h, w, 3), dtype=np.uint8)
             _, _, hst = renderer.render(scene.camera, w, h, bg, samples=s, seed=0, sample_mode=H.SAMPLE_RNG, into=img, want_linear=False)
             out["config"]["host_buffer_path"] = {"ms_per_frame": hst["total_ms"], "Mray_per_s": rays_frame / hst["total_ms"] / 1e3}
-        if world == 1 and not args.no_extras:
+        if args.full and world == 1 and not args.no_extras:
             # The same preparation once more in this process ("warm": HIP is initialised, the library's code objects are loaded, the allocator has its pools) and the
             # first frame of that renderer: what a caller of Image::render pays on every call AFTER its first (the reference converts its scene inside every
             # render call, render.rs:115-126); `prepare_ms` above is the process's first, cold.
@@ -614,17 +659,17 @@ def main():
             tw2 = time.perf_counter()
             out["config"]["prepare_ms_warm"] = dict(again.prepare_ms(), renderer_total=(tw1 - tw0) * 1e3, first_frame_host_buffers_ms=(tw2 - tw1) * 1e3, its_kernel_ms=wst["kernel_ms"])
             again.close()
-        if world == 1 and args.traversal == "flat" and args.share == 1 and not args.no_extras:
+        if args.full and world == 1 and args.traversal == "flat" and args.share == 1 and not args.no_extras:
             # `value` is measured in the flat_scene semantics north_star prescribes. The crate's DEFAULT feature set is the
             # hierarchical traversal, which is not image-equivalent to it on every scene and costs more: the same
             # frame in those semantics, measured here so that the disclosure travels with the number (never used as `value`)
             hier = timed_frame(host, H, scene, H.TRAVERSE_HIER, device, w, h, s, bg)
             hier.pop("counters"); hier.pop("prepare_ms")
             out["config"]["default_semantics"] = dict(hier, traversal="hier (the crate built without features, scene.rs:80-120)")
-        if world == 1 and args.workload == "big-scene" and at_config_size and not args.no_extras:
+        if args.full and world == 1 and args.workload == "big-scene" and at_config_size and not args.no_extras:
             # the workloads where memory / ray incoherence matter, timed by the same run at the metric's size
             out["secondary"] = [secondary_workload(host, H, lib, name, device, float(copy_gbps.value)) for name in ("big-soup", "mirror")]
-        if not args.no_cpu_baseline and world == 1 and not example.startswith("synthetic:"):
+        if args.full and not args.no_cpu_baseline and world == 1 and not example.startswith("synthetic:"):
             out["cpu_baseline"] = cpu_baseline(example, n, w, h, args.traversal)
     else:
         out = None
@@ -702,6 +747,8 @@ def node_report(args, H, host, lib, state, world, w, h, s, example, elapsed, ker
         one.render(scene.camera, w, h, bg, samples=s, seed=0, sample_mode=H.SAMPLE_RNG, into=ref, want_linear=False)
         one.close()
         out["config"]["assembled_image_equals_single_gpu_render"] = bool(np.array_equal(img, ref))
+    if not args.full:
+        return out
     # the roofline of the slowest rank's kernel: the counters are the node's totals, a rank's share is 1 / ranks of them
     share = {k: v / ranks if isinstance(v, (int, float)) and k not in ("kernel_ms", "total_ms", "kernel_mode", "kernel_variant") else v for k, v in counts.items()}
     # The kernel time of a rank is taken from the frames rendered ONE AT A TIME (the untimed pass after the timed one): with two frames open a frame's

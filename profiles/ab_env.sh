@@ -4,7 +4,7 @@
 BARGS=$1; shift
 for e in "$@"; do
   for i in 1 2; do
-    env $e python bench.py --no-cpu-baseline $BARGS 2>&1 | tail -1 | python -c "
+    env $e python bench.py --full --no-cpu-baseline $BARGS 2>&1 | tail -1 | python -c "
 import sys,json
 d=json.loads(sys.stdin.read())
 r=d['roofline']['per_ray']

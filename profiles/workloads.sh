@@ -1,7 +1,7 @@
 #!/bin/bash
 # Throughput of the headline workloads with the current build (no CPU baseline). usage: bash profiles/workloads.sh [extra bench args]
 run() {
-python3 bench.py --no-cpu-baseline --steps 3 --warmup 1 "$@" 2>&1 | tail -1 | python3 -c "
+python3 bench.py --full --no-cpu-baseline --steps 3 --warmup 1 "$@" 2>&1 | tail -1 | python3 -c "
 import sys,json
 d=json.loads(sys.stdin.read()); r=d['roofline']['per_ray']
 print('%-44s %9.1f Mray/s %9.2f ms/frame (kernel %8.2f)  rays/frame %.3g  nodes/ray %.1f prim/ray %.2f tri/ray %.2f' % ('$*', d['value'], d['ms_per_step'], d['roofline']['kernel_ms'], d['config']['rays_per_frame'], r['inner_nodes'], r['primitive_tests'], r['triangle_tests']))"

@@ -86,3 +86,21 @@ def test_survey_accounting(bench):
     assert f64 == 90 * 50 + 50 * 30 + 126 * 5 + 9 * (60 + 129) and f32 == 36 * 400 and flops == f64 + 48 * 400
     f64k, f32k, flopsk = bench.algorithmic_ops(st, 3, "kd")
     assert f64k == f64 + 9 * 400 and f32k == 0 and flopsk == f64k
+
+
+def test_dump_outputs_writes_float32_within_the_limit(bench, tmp_path, monkeypatch):
+    import numpy as np
+    img = np.random.default_rng(5).integers(0, 256, size=(48, 64, 3), dtype=np.uint8)
+    bench.dump_outputs(str(tmp_path / "whole"), img)
+    got = np.load(tmp_path / "whole" / "image.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, img.astype(np.float32))
+    # past the limit: a fixed sample of the pixels and their row-major indices, both files within it, the same sample on every run
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 4096 + 20 * 200)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), img)
+        assert not (tmp_path / d / "image.npy").exists()
+        assert sum(os.path.getsize(tmp_path / d / f) for f in os.listdir(tmp_path / d)) <= bench.DUMP_LIMIT_BYTES
+    px, idx = np.load(tmp_path / "a" / "image_sample.npy"), np.load(tmp_path / "a" / "image_sample_pixels.npy")
+    assert px.dtype == np.float32 and idx.dtype == np.float64 and px.shape == (200, 3) and idx.shape == (200,)
+    assert np.array_equal(px, img.reshape(-1, 3)[idx.astype(np.int64)].astype(np.float32)) and np.all(np.diff(idx) > 0)
+    assert np.array_equal(px, np.load(tmp_path / "b" / "image_sample.npy")) and np.array_equal(idx, np.load(tmp_path / "b" / "image_sample_pixels.npy"))

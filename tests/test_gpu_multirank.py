@@ -422,36 +422,42 @@ def test_host_renderer_on_a_node(host, H, monkeypatch):
     assert np.array_equal(a, b)
 
 
-def _bench_line(*args):
-    """bench.py as the driver starts it (a subprocess; with --gpus N > 1 it spawns its own rank processes), the JSON line parsed."""
+def _bench_line(*args, full=True):
+    """bench.py as the driver starts it (a subprocess; with --gpus N > 1 it spawns its own rank processes), the JSON line parsed.
+    full: with --full (the roofline and the per-rank figures these tests read; --no-extras --no-cpu-baseline leave the rest out)."""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--no-cpu-baseline", "--no-extras", "--steps", "2", "--warmup", "1", *args],
+    extra = ["--full", "--no-cpu-baseline", "--no-extras"] if full else []
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), *extra, "--steps", "2", "--warmup", "1", *args],
                        capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     return json.loads(r.stdout.strip().splitlines()[-1])
 
 
-def test_bench_two_ranks_go_through_pt_node():
+def test_bench_two_ranks_go_through_pt_node(tmp_path):
     """`bench.py --gpus 2` times the product's own multi-GPU path: rank 0 drives pt_node_render_resident, the JSON line says which
     communicator carried the frame. Two ranks on one GPU here (device-to-device copies instead of RCCL: RCCL needs distinct GPUs)."""
-    d = _bench_line("--gpus", "2", "--same-device", "--workload", "primitives", "--check")
+    d = _bench_line("--gpus", "2", "--same-device", "--workload", "primitives", "--check", "--dump-outputs", str(tmp_path))
     c = d["config"]["collective"]
     assert d["n_gpus"] == 2 and c["via"].startswith("pt_node_render_resident") and c["ranks_in_group"] == 2 and c["devices"] == [0, 0]
     assert c["uses_rccl"] is False and c["rank_processes"] == 2
     assert d["config"]["assembled_image_equals_single_gpu_render"] is True
     assert d["value"] > 0 and d["roofline"]["bound"] == "valu" and 0 < d["roofline"]["frac"] < 1.5
     assert d["config"]["rays"]["primary"] == 800 * 600
+    img = np.load(tmp_path / "image.npy")  # the image --check compared, downloaded from GPU 0
+    assert img.dtype == np.float32 and img.shape == (600, 800, 3) and img.max() > 0
 
 
-def test_bench_two_ranks_via_torch_cross_check():
+def test_bench_two_ranks_via_torch_cross_check(tmp_path):
     """The same partition with one process per GPU and torch.distributed's gather (gloo here: two ranks share the GPU)."""
-    d = _bench_line("--gpus", "2", "--same-device", "--via", "torch", "--backend", "gloo", "--workload", "primitives", "--check")
+    d = _bench_line("--gpus", "2", "--same-device", "--via", "torch", "--backend", "gloo", "--workload", "primitives", "--check", "--dump-outputs", str(tmp_path))
     c = d["config"]["collective"]
     assert c["via"].startswith("torch.distributed") and c["ranks_in_group"] == 2
     assert d["config"]["assembled_image_equals_single_gpu_render"] is True
+    img = np.load(tmp_path / "image.npy")
+    assert img.dtype == np.float32 and img.shape == (600, 800, 3) and img.max() > 0
 
 
 def test_bench_single_gpu_line_carries_the_contract_fields():
@@ -462,3 +468,21 @@ def test_bench_single_gpu_line_carries_the_contract_fields():
     assert r["bound"] == "valu" and r["unit"].startswith("T lane-ops/s") and r["frac"] == pytest.approx(r["achieved"] / r["peak"])
     assert "pt_render_simple_kernel<1, false, false, 4, false>" in r["kernel"], "macho-cows: plain meshes, nothing reflective, untextured: 4 waves"
     assert r["hbm"]["needed_bytes"] > 0 and d["config"]["collective"] is None
+
+
+def test_bench_plain_line_is_the_headline_and_dumps_the_last_image(H, host, tmp_path):
+    """A run without --full: the headline fields only (no roofline, no extra passes), and --dump-outputs writes the image the timed steps
+    assembled - the same pixels as one render of the frame through the host path."""
+    d = _bench_line("--workload", "primitives", "--dump-outputs", str(tmp_path), full=False)
+    for k in ("metric", "value", "unit", "ms_per_step", "higher_is_better", "dtype"):
+        assert k in d, k
+    assert d["steps"] == 2 and d["value"] > 0 and d["ms_per_step"] > 0 and d["config"]["rays"]["primary"] == 800 * 600
+    assert "roofline" not in d and "cpu_baseline" not in d and "secondary" not in d and "default_semantics" not in d["config"]
+    img = np.load(tmp_path / "image.npy")
+    assert img.dtype == np.float32 and img.shape == (600, 800, 3)
+    sc = host.Scene.example("primitives-simple")
+    r = host.Renderer(sc, H.TRAVERSE_FLAT, kd_depth=10, device=0)
+    from bench import row_background
+    ref, _, _ = r.render(sc.camera, 800, 600, row_background(600), samples=1, seed=0, sample_mode=H.SAMPLE_RNG, want_linear=False)
+    r.close()
+    assert np.array_equal(img, ref.astype(np.float32))

@@ -1,7 +1,8 @@
 """The Rust shim (shim/: build.rs, src/hip_ffi.rs, src/hip_pack.rs, overlay/*.rs.append, apply.py) cannot be compiled
 here (no rustc / cargo). What CAN be checked:
 
-  CPU  shim/apply.py overlays a copy of the reference checkout without touching anything but the places it names, and
+  CPU  shim/apply.py overlays a copy of a checkout of the crate (a stand-in the test writes) without touching anything
+       but the places it names, and
        the structs of shim/src/hip_ffi.rs match include/portrayer_hip.h field for field;
   GPU  tests/shim_replay.c - the shim's call sequence and array layouts in plain C (triangle-list meshes, materials by
        first use, breadth-first nodes, the scene-graph arrays of an instanced subtree) - renders through
@@ -16,7 +17,34 @@ import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
-REFERENCE = "/root/reference"
+
+# A stand-in for a checkout of the crate: just the files shim/apply.py opens, with the shapes it relies on (a [package] table,
+# the signature of ImageSliceMut::render up to the opening brace of its body). Not compiled; the overlay's text is what is checked.
+STAND_IN_CRATE = {
+    "Cargo.toml": '[package]\nname = "portrayer"\nversion = "0.0.0"\nedition = "2018"\n\n[dependencies]\n',
+    "src/lib.rs": "pub mod bounding_box;\npub mod camera;\npub mod render;\npub mod texture;\n",
+    "src/render.rs": ("pub struct ImageSliceMut<'a> {\n    image: &'a mut Image,\n}\n\n"
+                      "impl<'a> ImageSliceMut<'a> {\n"
+                      "    pub fn render<R: Reporter, T: TextureSource>(\n"
+                      "        &mut self,\n        scene: &HierScene,\n        camera: CameraSettings,\n        background: T,\n    ) {\n"
+                      "        let _ = (scene, camera, background);\n    }\n}\n"),
+    "src/primitive/mesh.rs": "pub struct Mesh;\n",
+    "src/kdtree/kdmesh.rs": "pub struct KDMesh;\n",
+    "src/kdtree/node.rs": "pub enum KDTreeNode {}\n",
+    "src/bounding_box.rs": "pub struct BoundingBox;\n",
+    "src/camera.rs": "pub struct CameraSettings;\n",
+    "src/texture.rs": "pub trait TextureSource {}\n",
+    "target/release/stale.rlib": "build output\n",
+}
+
+
+def stand_in_crate(root):
+    for rel, text in STAND_IN_CRATE.items():
+        p = os.path.join(root, rel)
+        os.makedirs(os.path.dirname(p), exist_ok=True)
+        with open(p, "w") as fh:
+            fh.write(text)
+    return str(root)
 
 
 @pytest.mark.parametrize("c_name,rust_name", [("pt_scene", "PtScene"), ("pt_kdtree", "PtKdTree"), ("pt_camera", "PtCamera"), ("pt_rect", "PtRect"),
@@ -45,19 +73,20 @@ def test_hip_ffi_functions_exist_in_the_header():
     assert int(re.search(r"PT_ABI_VERSION: c_int = (\d+)", ffi).group(1)) == int(re.search(r"#define PT_ABI_VERSION (\d+)", header).group(1))
 
 
-@pytest.mark.skipif(not os.path.isdir(REFERENCE), reason="the reference checkout only exists in the build container")
 def test_apply_overlays_a_reference_checkout(tmp_path):
+    src = stand_in_crate(tmp_path / "portrayer")
     dst = str(tmp_path / "portrayer-hip")
-    subprocess.run([sys.executable, os.path.join(ROOT, "shim", "apply.py"), REFERENCE, dst], check=True)
+    subprocess.run([sys.executable, os.path.join(ROOT, "shim", "apply.py"), src, dst], check=True)
+    assert not os.path.exists(os.path.join(dst, "target")), "build output is not copied"
     render = open(os.path.join(dst, "src", "render.rs")).read()
-    ref_render = open(os.path.join(REFERENCE, "src", "render.rs")).read()
+    ref_render = open(os.path.join(src, "src", "render.rs")).read()
     # exactly one delegation inserted, everything else of the reference's file intact, our impl appended
     inserted = '        #[cfg(feature = "hip")]\n        { return self.render_hip::<R, T>(scene, camera, background); }\n'
     assert render.count(inserted) == 1
     assert render.replace(inserted, "").startswith(ref_render)
     assert "fn render_hip<" in render[len(ref_render):]
     for f in ("src/primitive/mesh.rs", "src/kdtree/kdmesh.rs", "src/kdtree/node.rs", "src/bounding_box.rs", "src/camera.rs", "src/texture.rs"):
-        new, old = open(os.path.join(dst, f)).read(), open(os.path.join(REFERENCE, f)).read()
+        new, old = open(os.path.join(dst, f)).read(), open(os.path.join(src, f)).read()
         assert new.startswith(old) and "hip_" in new[len(old):], f
     assert "mod hip_pack;" in open(os.path.join(dst, "src", "lib.rs")).read()
     cargo = open(os.path.join(dst, "Cargo.toml")).read()
