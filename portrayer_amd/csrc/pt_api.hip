@@ -1215,7 +1215,14 @@ static int pt_render_common(pt_context* c, PtRenderArgs& a, bool stats, hipStrea
     const int stack_spill_entries = std::max(a.scene.stack_cap - a.stack_lds_cap + wave_rows, 0);
     const size_t stack_column = (size_t)std::max(stack_spill_entries, a.scene.stack_cap);  // everything a lane's own stack can reach (pt_trace_wave gives the lanes fewer LDS rows in the k-d semantics)
     if ((rc = pt_reserve(c, sl.stack_spill, (size_t)a.n_lanes * stack_column * 4))) return rc;  // (the k-d walk's saved bounds needed columns behind this until round 5)
-    if ((rc = pt_reserve(c, sl.misc, 256 + sizeof(PtCounters) + PT_FINE_QUEUES * PT_QUEUE_STRIDE * 4))) return rc;
+    // The occluder table of the mesh-free walks' shadow rays (pt_trace_packet): one word per (own 8x8 tile, light), behind the work
+    // queues, zeroed with them before every launch - what it remembers comes from the frame being rendered, never from an earlier one.
+    // PORTRAYER_SHADOW_CACHE=0 leaves it out (A/B runs); so does a table of more than 4 MB (many lights: zeroing it would cost more).
+    const size_t misc_head = 256 + sizeof(PtCounters) + PT_FINE_QUEUES * PT_QUEUE_STRIDE * 4;
+    size_t occ_bytes = (size_t)(a.n_slots / 64) * a.scene.n_lights * 4;
+    if (!(a.scene.mode == PT_MODE_FLAT_NOMESH || a.scene.mode == PT_MODE_HIER_NOMESH) || occ_bytes > ((size_t)4 << 20)) occ_bytes = 0;
+    if (const char* e = getenv("PORTRAYER_SHADOW_CACHE")) if (atoi(e) <= 0) occ_bytes = 0;
+    if ((rc = pt_reserve(c, sl.misc, misc_head + occ_bytes))) return rc;
     if ((rc = pt_reserve(c, sl.accum, (size_t)a.n_slots * a.n_chunks * 3 * sizeof(double)))) return rc;
     a.accum = (double*)sl.accum.p;
     a.spill = (double*)sl.spill.p;
@@ -1224,10 +1231,12 @@ static int pt_render_common(pt_context* c, PtRenderArgs& a, bool stats, hipStrea
     a.overflow_flag = (unsigned int*)sl.misc.p + 1;
     a.counters = (PtCounters*)((char*)sl.misc.p + 256);
     a.work_queues = (unsigned int*)((char*)sl.misc.p + 256 + sizeof(PtCounters));
+    a.occluders = occ_bytes ? (uint32_t*)((char*)sl.misc.p + misc_head) : nullptr;
+    a.occ_row = std::max<uint32_t>(a.div_tiles_x.d / std::max<uint32_t>(a.tile_ranks, 1u), 1u);
     c->last_mode = (uint32_t)a.scene.mode;
     c->last_variant = (a.four_waves ? (uint32_t)a.four_waves : 3u) | ((a.run_variant == PT_RUN_LINE3 || a.run_variant == PT_RUN_LINE4 || a.run_variant == PT_RUN_LINE5 || a.run_variant == PT_RUN_CHAIN) ? 0u : PT_KERNEL_INTERPRETER) | (a.run_variant == PT_RUN_CHAIN ? PT_KERNEL_CHAIN : 0u) |
                       ((a.run_variant == PT_RUN_INTERP_PARK || a.run_variant == PT_RUN_INTERP_FORK) ? PT_KERNEL_PARK : 0u) | (a.run_variant == PT_RUN_INTERP_FORK ? PT_KERNEL_FORK : 0u) | (stats ? PT_KERNEL_COUNTING : 0u) | (tex ? PT_KERNEL_TEXTURED : 0u);
-    PT_HIP(c, hipMemsetAsync(sl.misc.p, 0, 256 + sizeof(PtCounters) + PT_FINE_QUEUES * PT_QUEUE_STRIDE * 4, stream));
+    PT_HIP(c, hipMemsetAsync(sl.misc.p, 0, misc_head + occ_bytes, stream));
     sl.mode = c->last_mode; sl.variant = c->last_variant; sl.counted = stats;
     PT_HIP(c, hipEventRecord(sl.ev0, stream));
     if (a.n_items) {

@@ -103,7 +103,8 @@ PT_HD PtKdLayout pt_kd_layout(const PtRenderArgs& a) {
 
 // One ray kind for the whole wavefront: `tracing` lanes carry `ray`; result in `hit` (untouched for the other lanes).
 template <int MODE, bool STATS>
-PT_HD void pt_trace_wave(const PtRenderArgs& a, const PtRay& ray, bool tracing, bool any, PtHit& hit, const PtStackSpill& stk, uint32_t* lds, PtCounters* cnt) {
+PT_HD void pt_trace_wave(const PtRenderArgs& a, const PtRay& ray, bool tracing, bool any, PtHit& hit, const PtStackSpill& stk, uint32_t* lds, PtCounters* cnt,
+                         PtOccRef occ = PtOccRef{nullptr, 0u, 0u}) {
 #ifdef PT_CYCLES  // profiles/cycles.sh: wave cycles inside the walks -> diag[0], calls -> diag[1]
     const unsigned long long cyc_t0 = __builtin_readcyclecounter();
     struct CycEnd { unsigned long long t0; PtCounters* c; __device__ ~CycEnd() { if (STATS && (threadIdx.x & 63u) == 0) { c->diag[0] += __builtin_readcyclecounter() - t0; c->diag[1]++; } } } cyc_end{cyc_t0, cnt};
@@ -121,7 +122,7 @@ PT_HD void pt_trace_wave(const PtRenderArgs& a, const PtRay& ray, bool tracing, 
     // stack of its own, else the part behind the lanes' rows (KDMesh trees are walked per lane, pt_kdmesh_hit).
     if (MODE == PT_MODE_FLAT_NOMESH || MODE == PT_MODE_HIER_NOMESH) {
         const int words = a.stack_lds_cap * 64;
-        pt_trace_packet<STATS, MODE == PT_MODE_HIER_NOMESH>(a.scene, ray, tracing, any, hit, lds + (size_t)wave * words, words, a.overflow_flag, cnt);
+        pt_trace_packet<STATS, MODE == PT_MODE_HIER_NOMESH>(a.scene, ray, tracing, any, hit, lds + (size_t)wave * words, words, a.overflow_flag, cnt, occ);
     } else if (MODE == PT_MODE_FLAT || MODE == PT_MODE_HIER_MESH) {
         const int words = a.stack_lds_cap * 64;
         pt_trace_packet_mesh<STATS, false, MODE == PT_MODE_HIER_MESH>(a.scene, ray, tracing, any, hit, lds + (size_t)wave * words, words, stk, a.overflow_flag, cnt);
@@ -339,7 +340,19 @@ __global__ void __launch_bounds__(PT_BLOCK, WAVES) pt_render_simple_kernel(PtRen
                 PtHit sh;
                 sh.t = INFINITY; sh.node = PT_NO_HIT; sh.sub = 0;
                 PT_SEC_END(6);
-                pt_trace_wave<MODE, STATS>(a, sray, shaded, true, sh, stk, pt_lds, &cnt);  // material.rs:174-179 only asks whether anything is in the way
+                // the occluder table's entry of this item's tile for this light (pt_trace_packet): mesh-free scenes, primary hits only
+                PtOccRef occ{nullptr, 0u, li};
+#ifdef PT_OCCLUDER_STATS
+                constexpr bool OCC = !CHAIN && (MODE == PT_MODE_FLAT_NOMESH || MODE == PT_MODE_HIER_NOMESH);
+#else
+                constexpr bool OCC = !STATS && !CHAIN && (MODE == PT_MODE_FLAT_NOMESH || MODE == PT_MODE_HIER_NOMESH);
+#endif
+                if (OCC && a.occluders) {
+                    const uint32_t tile_local = pt_fastdiv(w >> (a.k_log2 + a.c_log2), a.div_groups);
+                    occ.entry = a.occluders + (size_t)tile_local * sc.n_lights + li;
+                    occ.back = tile_local >= a.occ_row ? a.occ_row * sc.n_lights : 0u;
+                }
+                pt_trace_wave<MODE, STATS>(a, sray, shaded, true, sh, stk, pt_lds, &cnt, occ);  // material.rs:174-179 only asks whether anything is in the way
                 PT_SEC_SKIP();
                 if (shaded && sh.node == PT_NO_HIT) {
                     double lc[2], lf[4];  // colour.xy, colour.z + falloff

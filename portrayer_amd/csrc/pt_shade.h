@@ -169,6 +169,8 @@ struct PtRenderArgs {
     uint32_t fine_queues;            // 0: batches from work_counter. N > 0: one item at a time from N interleaved queues (work_queues), see pt_render_kernel
     unsigned int* work_queues;       // N counters, PT_QUEUE_STRIDE words apart
     uint32_t item_stride;            // hand-out position q -> item (q * item_stride) mod n_items; 1 = in image order
+    uint32_t* occluders;             // mesh-free scenes: the frame's occluder table, own tiles x lights (pt_trace_packet), zeroed with the work queues; nullptr: none
+    uint32_t occ_row;                // own tiles per row of the slice (>= 1): the tile above is this many entries x lights back
     PtCounters* counters;
 };
 

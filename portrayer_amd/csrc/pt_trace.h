@@ -1536,14 +1536,16 @@ PT_HD void pt_descend_mesh(const PtBvhNode* bvh, const PtRayPk& q, float tm, uns
     }
 }
 
-// wstack: the wavefront's own stack in LDS, `wwords` 32-bit words, linear.
+// wstack: the wavefront's own stack in LDS, `wwords` 32-bit words, linear. `live` = false: the lane's (shadow) ray is answered
+// already - its `best` is kept and it takes no part in the walk, while everything wave-wide (octant, identity levels) still follows
+// `has_ray`, as if it did (pt_trace_packet's occluder test).
 template <bool STATS, bool HIER>
-PT_HD void pt_trace_packet(const PtSceneView& sc, const PtRay& ray, bool has_ray, bool any, PtHit& best, uint32_t* wstack, int wwords,
-                           unsigned int* overflow, PtCounters* cnt) {
-    if (has_ray) { best.t = INFINITY; best.node = PT_NO_HIT; best.sub = 0; }
+PT_HD void pt_trace_packet_walk(const PtSceneView& sc, const PtRay& ray, bool has_ray, bool any, PtHit& best, uint32_t* wstack, int wwords,
+                                unsigned int* overflow, PtCounters* cnt, bool live = true) {
+    if (has_ray && live) { best.t = INFINITY; best.node = PT_NO_HIT; best.sub = 0; }
     if (sc.n_nodes == 0 || sc.tlas_root == PT_REF_EMPTY) return;
     const unsigned long long self = 1ull << PT_LANE_ID();
-    bool alive = has_ray;               // the lane still wants candidates (a shadow ray stops at its first hit)
+    bool alive = has_ray && live;       // the lane still wants candidates (a shadow ray stops at its first hit)
     unsigned long long amask = PT_BALLOT(alive);  // the same as a wave-uniform mask: the slab test's results are masks, never per-lane booleans
     unsigned long long in = ~0ull;      // wave-uniform: lanes whose rays reach the current node's box
     int oct;
@@ -1619,6 +1621,76 @@ PT_HD void pt_trace_packet(const PtSceneView& sc, const PtRay& ray, bool has_ray
         }
 #endif
     }
+}
+
+// The frame's occluder table (pt_render_simple_kernel): per (8x8 tile, light) the node that last blocked a shadow ray of the tile
+// toward the light, as node + 1 (0: none yet). `entry` = the wavefront's own entry, `back` = how many words before it the fallback
+// entry lies (the tile above; 0: none), `light` = the light's index (the -DPT_OCCLUDER_STATS counts). entry == nullptr: no table.
+struct PtOccRef {
+    uint32_t* entry;
+    uint32_t back, light;
+};
+
+// Shadow rays (any = true) test the tile's last occluder for their light first: where it blocks every lane, the walk is skipped.
+// Exact by construction: a shadow ray only asks whether ANY node is hit in [EPSILON, INF) - an OR over nodes, whatever their order -
+// and the cached test is the walk's own leaf test (same function, same range - `best` is still empty -, same local ray, the same
+// wave-wide identity_ok). Lanes it does not block walk as before; the walk may test that node again for them, which changes nothing.
+// The counting build walks as before (its node counts are compared with the oracle's); -DPT_OCCLUDER_STATS makes it count, per
+// light, what the test would have saved (diag[], see below) without changing the walk.
+template <bool STATS, bool HIER>
+PT_HD void pt_trace_packet(const PtSceneView& sc, const PtRay& ray, bool has_ray, bool any, PtHit& best, uint32_t* wstack, int wwords,
+                           unsigned int* overflow, PtCounters* cnt, PtOccRef occ = PtOccRef{nullptr, 0u, 0u}) {
+#if defined(__HIP_DEVICE_COMPILE__)
+#ifdef PT_OCCLUDER_STATS
+    constexpr bool COUNT_OCC = STATS;
+#else
+    constexpr bool COUNT_OCC = false;
+#endif
+    if ((STATS && !COUNT_OCC) || !any || occ.entry == nullptr) {
+        pt_trace_packet_walk<STATS, HIER>(sc, ray, has_ray, any, best, wstack, wwords, overflow, cnt);
+        return;
+    }
+    uint32_t* const entry = (uint32_t*)pt_uniform_ptr(occ.entry);
+    const uint32_t own = PT_UNIFORM_U32(entry[0]);
+    const uint32_t up = occ.back ? PT_UNIFORM_U32(entry[-(long)occ.back]) : 0u;
+    const uint32_t cand = own ? own : up;
+    const unsigned long long rays = PT_BALLOT(has_ray);
+    bool blocked = false;
+    if (has_ray) { best.t = INFINITY; best.node = PT_NO_HIT; best.sub = 0; }
+    if (cand != 0u && has_ray) {
+        const bool identity_ok = HIER && pt_ray_identity_safe(ray, has_ray);  // (wave-uniform, as in the walk: over every lane that carries a ray)
+        PtHit probe = best;
+        blocked = pt_test_node_uniform<false, HIER>(sc, cand - 1u, ray, identity_ok, probe, cnt);
+        if (!STATS && blocked) best = probe;
+    }
+    const unsigned long long blocked_mask = PT_BALLOT(blocked);
+    const uint32_t first = (uint32_t)__ffsll((long long)__ballot(1)) - 1u;
+    if (!STATS && blocked_mask != 0ull && blocked_mask == rays) {  // the whole wavefront in the shadow of one node: no walk
+        if (own != cand && PT_LANE_ID() == first) entry[0] = cand;
+        return;
+    }
+    if (STATS) pt_trace_packet_walk<STATS, HIER>(sc, ray, has_ray, any, best, wstack, wwords, overflow, cnt);
+    else pt_trace_packet_walk<STATS, HIER>(sc, ray, has_ray, any, best, wstack, wwords, overflow, cnt, !blocked);
+    // the entry: the node that blocked the lowest blocked lane; a walk in which nothing was in the way clears it (lit regions stop testing)
+    const unsigned long long hit_mask = PT_BALLOT(has_ray && best.node != PT_NO_HIT);
+    const uint32_t now = hit_mask ? (uint32_t)__builtin_amdgcn_readlane((int)best.node, (int)(__ffsll((long long)hit_mask) - 1)) + 1u : 0u;
+#ifdef PT_OCC_KEEP_ON_MISS  // (A/B only: a walk in which nothing was in the way leaves the entry as it was)
+    if (rays && now != 0u && now != own && PT_LANE_ID() == first) entry[0] = now;
+#else
+    if (rays && now != own && PT_LANE_ID() == first) entry[0] = now;
+#endif
+    if (COUNT_OCC && rays && occ.light < 3u && PT_LANE_ID() == first) {
+        // diag[2 l]: walks toward light l (low half), of them with a lane in the shadow (high half); diag[2 l + 1]: walks with EVERY lane in
+        // the shadow (low), of them those the candidate alone would have ended (high); diag[6]: walks with a candidate (low; high: from the
+        // own tile), diag[7]: walks in which the candidate blocked a lane (low)
+        cnt->diag[2 * occ.light] += 1ull | (hit_mask ? 1ull << 32 : 0ull);
+        if (hit_mask == rays) cnt->diag[2 * occ.light + 1] += 1ull | (blocked_mask == rays ? 1ull << 32 : 0ull);
+        if (cand) cnt->diag[6] += 1ull | (own ? 1ull << 32 : 0ull);
+        if (blocked_mask) cnt->diag[7]++;
+    }
+#else
+    pt_trace_packet_walk<STATS, HIER>(sc, ray, has_ray, any, best, wstack, wwords, overflow, cnt);
+#endif
 }
 
 // A wave-uniform pointer pinned to a scalar register pair (see pt_args_again: what is read through the re-read argument block would

@@ -1,0 +1,29 @@
+#!/usr/bin/env python3
+"""What the shadow rays' occluder table saves, from a counting build made beforehand with
+  make variant NAME=occstats EXTRA_HIPFLAGS=-DPT_OCCLUDER_STATS
+on big-scene 1920x1080x64: per light the shadow walks, those with a lane in the shadow, those with every lane in the shadow, and of
+the last how many the table's candidate alone would have ended. The counting walk itself is unchanged.
+usage (GPU box, repo root): python3 profiles/occluder_stats.py build/variants/occstats flat|hier"""
+import os, shutil, sys, tempfile, json
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+tmp = tempfile.mkdtemp()
+shutil.copytree(os.path.join(ROOT, "portrayer_amd"), os.path.join(tmp, "portrayer_amd"), ignore=shutil.ignore_patterns("csrc", "host"))
+shutil.copy(os.path.join(sys.argv[1], "libportrayer_hip.so"), os.path.join(tmp, "portrayer_amd", "libportrayer_hip.so"))
+sys.path.insert(0, tmp)
+sys.path.insert(1, os.path.join(ROOT, "tests"))
+from portrayer_amd import _hip as H, host
+from scene_dsl import ASSETS, default_background
+mode = sys.argv[2]
+sc = host.Scene.example("big-scene", assets=ASSETS)
+r = host.Renderer(sc, H.TRAVERSE_HIER if mode == "hier" else H.TRAVERSE_FLAT)
+w, h = 1920, 1080
+_, _, st = r.render(sc.camera, w, h, default_background(w, h), samples=64, seed=0, sample_mode=H.SAMPLE_RNG, stats=True, want_linear=False)
+r.close()
+d = st["diag"]
+lo = lambda x: x & 0xFFFFFFFF
+hi = lambda x: x >> 32
+out = {"mode": mode, "shadow_rays": st["shadow"], "n_inner": st["n_inner"], "primary": st["primary"], "lights": []}
+for l in range(3):
+    out["lights"].append({"walks": lo(d[2 * l]), "some_lane_occluded": hi(d[2 * l]), "all_occluded": lo(d[2 * l + 1]), "candidate_ends": hi(d[2 * l + 1])})
+out["walks_with_candidate"] = lo(d[6]); out["candidate_from_own_tile"] = hi(d[6]); out["candidate_blocked_a_lane"] = d[7]
+print("OCCSTATS " + json.dumps(out), flush=True)
