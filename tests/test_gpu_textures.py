@@ -118,6 +118,37 @@ def test_random_textured_scene_matches_oracle(oracle, host, H, seed, mode):
     assert_ulp(linear, ref.linear, 0)
 
 
+@pytest.mark.parametrize("seed", [0, 1])
+def test_four_wave_chain_kernel_of_hierarchical_textured_mesh_scenes_matches_oracle(oracle, host, H, monkeypatch, seed):
+    """PORTRAYER_CHAIN_WAVES=4 on a textured scene with Mesh instances and an opaque mirror in the hierarchical semantics: the chain
+    kernels pt_render_simple_kernel<8, *, true, 4, true>, whose blocks .LBB5_51 (counting) and .LBB13_796 (plain) the build repairs
+    (tools/check_exec_prologue.py). Both exact against the oracle."""
+    for k in ("PORTRAYER_PARK", "PORTRAYER_CHAIN", "PORTRAYER_NO_TEX"):  # this test picks the kernels itself (tests/test_gpu_switch_matrix.py)
+        monkeypatch.delenv(k, raising=False)
+    monkeypatch.setenv("PORTRAYER_CHAIN_WAVES", "4")
+    scene, cam = textured_scene(seed)
+    w, h = 160, 110
+    bg = default_background(w, h)
+    r = host.Renderer(host_glue.host_scene(scene), H.TRAVERSE_HIER)
+    kw = dict(samples=2, seed=seed, sample_mode=H.SAMPLE_RNG)
+    rgb, linear, st = r.render(host_glue.cam10(cam), w, h, bg, stats=False, **kw)
+    counted, counted_linear, stc = r.render(host_glue.cam10(cam), w, h, bg, stats=True, **kw)
+    r.close()
+    want = H.KERNEL_CHAIN | H.KERNEL_TEXTURED | 4
+    assert st["kernel_mode"] == stc["kernel_mode"] == 8
+    assert st["kernel_variant"] & (want | H.KERNEL_COUNTING | H.KERNEL_WAVES_MASK | H.KERNEL_INTERPRETER) == want
+    assert stc["kernel_variant"] & (want | H.KERNEL_COUNTING | H.KERNEL_WAVES_MASK | H.KERNEL_INTERPRETER) == want | H.KERNEL_COUNTING
+    ref = oracle.render(scene, cam, w, h, samples=2, seed=seed, jitter=oracle.JITTER_RNG, mode=oracle.MODE_HIER)
+    for k in ("primary", "shadow", "reflect", "refract", "hits"):
+        assert stc[k] == ref.stats[k], k
+    assert ref.stats["reflect"] > 0
+    texel_edge_proof(ref)
+    for img, lin in [(rgb, linear), (counted, counted_linear)]:
+        bad = (img != ref.rgb).any(axis=2)
+        assert bad.sum() == 0, f"{bad.sum()} pixels differ, first at {np.argwhere(bad)[:3]}"
+        assert_ulp(lin, ref.linear, 0)
+
+
 def test_texture_on_primitive_without_uv_is_rejected(host, H):
     """material.rs:133 / :141: 'Texture mapping is not supported for this primitive!' (a panic in the reference)."""
     tex = Texture(np.zeros((4, 4, 3), dtype=np.uint8))
