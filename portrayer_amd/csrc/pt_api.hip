@@ -211,6 +211,14 @@ __global__ void pt_untile_kernel(PtRenderArgs a, uint32_t slots_per_rank, const 
     d[0] = s[0]; d[1] = s[1]; d[2] = s[2];
 }
 
+// PORTRAYER_OCC_SEED (tests only, pt_render_common): the occluder table filled with hints the test chooses instead of zeros - every entry
+// `all` + 1, or entry i = hash(seed, i) mod (n_nodes + 1) (0: none). The table's test is exact whatever an entry holds (pt_trace_packet).
+__global__ void __launch_bounds__(256) pt_occ_seed_kernel(uint32_t* __restrict__ occ, uint32_t n, int hashed, uint64_t seed, uint32_t all, uint32_t n_nodes) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    occ[i] = hashed ? (uint32_t)(pt_rng_key(seed, i) % ((uint64_t)n_nodes + 1u)) : all + 1u;
+}
+
 // ------------------------------------------------------------------------------------------------
 // Context
 // ------------------------------------------------------------------------------------------------
@@ -1222,6 +1230,23 @@ static int pt_render_common(pt_context* c, PtRenderArgs& a, bool stats, hipStrea
     size_t occ_bytes = (size_t)(a.n_slots / 64) * a.scene.n_lights * 4;
     if (!(a.scene.mode == PT_MODE_FLAT_NOMESH || a.scene.mode == PT_MODE_HIER_NOMESH) || occ_bytes > ((size_t)4 << 20)) occ_bytes = 0;
     if (const char* e = getenv("PORTRAYER_SHADOW_CACHE")) if (atoi(e) <= 0) occ_bytes = 0;
+    // PORTRAYER_OCC_SEED=all:K | <seed> (tests only): the table starts with hints the test chose (pt_occ_seed_kernel), not with zeros
+    bool occ_seed = false, occ_hashed = false;
+    uint64_t occ_seed_value = 0;
+    uint32_t occ_all = 0;
+    if (const char* e = getenv("PORTRAYER_OCC_SEED"); e && *e && occ_bytes) {
+        char* end = nullptr;
+        if (strncmp(e, "all:", 4) == 0) {
+            const unsigned long long k = strtoull(e + 4, &end, 10);
+            if (end == e + 4 || *end || k >= a.scene.n_nodes) return pt_fail(c, PT_ERR_ARGUMENT, std::string("PORTRAYER_OCC_SEED=") + e + ": K must be a node index below " + std::to_string(a.scene.n_nodes));
+            occ_all = (uint32_t)k;
+        } else {
+            occ_seed_value = strtoull(e, &end, 10);
+            if (end == e || *end) return pt_fail(c, PT_ERR_ARGUMENT, std::string("PORTRAYER_OCC_SEED=") + e + ": expected all:<node> or a decimal seed");
+            occ_hashed = true;
+        }
+        occ_seed = true;
+    }
     if ((rc = pt_reserve(c, sl.misc, misc_head + occ_bytes))) return rc;
     if ((rc = pt_reserve(c, sl.accum, (size_t)a.n_slots * a.n_chunks * 3 * sizeof(double)))) return rc;
     a.accum = (double*)sl.accum.p;
@@ -1237,6 +1262,12 @@ static int pt_render_common(pt_context* c, PtRenderArgs& a, bool stats, hipStrea
     c->last_variant = (a.four_waves ? (uint32_t)a.four_waves : 3u) | ((a.run_variant == PT_RUN_LINE3 || a.run_variant == PT_RUN_LINE4 || a.run_variant == PT_RUN_LINE5 || a.run_variant == PT_RUN_CHAIN) ? 0u : PT_KERNEL_INTERPRETER) | (a.run_variant == PT_RUN_CHAIN ? PT_KERNEL_CHAIN : 0u) |
                       ((a.run_variant == PT_RUN_INTERP_PARK || a.run_variant == PT_RUN_INTERP_FORK) ? PT_KERNEL_PARK : 0u) | (a.run_variant == PT_RUN_INTERP_FORK ? PT_KERNEL_FORK : 0u) | (stats ? PT_KERNEL_COUNTING : 0u) | (tex ? PT_KERNEL_TEXTURED : 0u);
     PT_HIP(c, hipMemsetAsync(sl.misc.p, 0, misc_head + occ_bytes, stream));
+    if (occ_seed) {
+        const uint32_t n_occ = (uint32_t)(occ_bytes / 4);
+        hipLaunchKernelGGL(pt_occ_seed_kernel, dim3((n_occ + 255) / 256), dim3(256), 0, stream, a.occluders, n_occ, occ_hashed ? 1 : 0, occ_seed_value, occ_all, a.scene.n_nodes);
+        PT_HIP(c, hipGetLastError());
+        if (getenv("PORTRAYER_VERBOSE")) fprintf(stderr, "[pt_render] occluder table: %u entries seeded (PORTRAYER_OCC_SEED=%s)\n", n_occ, getenv("PORTRAYER_OCC_SEED"));
+    }
     sl.mode = c->last_mode; sl.variant = c->last_variant; sl.counted = stats;
     PT_HIP(c, hipEventRecord(sl.ev0, stream));
     if (a.n_items) {

@@ -29,8 +29,9 @@ def host():
     return host
 
 
-def render_partition(H, host, renderer, scene, w, h, rect, ranks, samples, bg):
-    """Every rank's compact buffer rendered on this GPU, concatenated rank-major, untiled on the device."""
+def render_partition(H, host, renderer, scene, w, h, rect, ranks, samples, bg, stats=True):
+    """Every rank's compact buffer rendered on this GPU, concatenated rank-major, untiled on the device (stats=False: by the plain
+    instantiation, whose ray counts are not kept - rays comes back 0)."""
     lib, ctx = H.lib(), renderer.context
     cam = host.camera(scene.camera, w, h)
 
@@ -49,7 +50,7 @@ def render_partition(H, host, renderer, scene, w, h, rect, ranks, samples, bg):
     check(lib.pt_copy_to_device(ctx, d_full, start.ctypes.data_as(C.c_void_p), start.nbytes), "copy")
     rays = 0
     for r in range(ranks):
-        p = H.PtRenderParams(w, h, H.PtRect(*rect), samples, 3, H.SAMPLE_RNG, 1, r, ranks, 1)
+        p = H.PtRenderParams(w, h, H.PtRect(*rect), samples, 3, H.SAMPLE_RNG, 1, r, ranks, 1 if stats else 0)
         st = H.PtStats()
         check(lib.pt_render_device(ctx, C.byref(cam), d_bg, C.byref(p), 1, C.c_void_p(d_gath.value + r * per), None), "pt_render_device")
         check(lib.pt_render_finish(ctx, C.byref(st)), "pt_render_finish")
@@ -245,7 +246,7 @@ def test_node_frames_in_a_pipeline(H, monkeypatch, ranks, threads):
     lib.pt_node_destroy(node)
 
 
-@pytest.mark.parametrize("scene_name,traverse", [("macho-cows", "flat"), ("entering-the-mirror-dimension", "kd"), ("transmission-refraction", "flat")])
+@pytest.mark.parametrize("scene_name,traverse", [("macho-cows", "flat"), ("entering-the-mirror-dimension", "kd"), ("transmission-refraction", "flat"), ("lit33-plain", "flat")])
 @pytest.mark.parametrize("two", ["0", "1"])
 def test_two_frames_in_flight_on_two_streams_of_one_context(H, monkeypatch, scene_name, traverse, two):
     """ABI 8: the two renders a context may have in flight own their work buffers (chunk sums, recursion frames, stack columns, counters, work queues) and
@@ -255,7 +256,13 @@ def test_two_frames_in_flight_on_two_streams_of_one_context(H, monkeypatch, scen
     import device_glue
     from example_scenes import EXAMPLES, TEXTURED_EXAMPLES
     from scene_dsl import Camera
-    scene, cam0 = (TEXTURED_EXAMPLES if scene_name in TEXTURED_EXAMPLES else EXAMPLES)[scene_name]()[:2]
+    from scene_dsl import linearise
+    from test_gpu_lights import lit_scene
+    if scene_name == "lit33-plain":  # 33 lights, nothing reflective: the straight-line kernel with recursion-frame buffers (needs_spill)
+        scene, cam0 = lit_scene(33, "plain")
+    else:
+        scene, cam0 = (TEXTURED_EXAMPLES if scene_name in TEXTURED_EXAMPLES else EXAMPLES)[scene_name]()[:2]
+    needs_spill = len(scene.lights) > 32 or any(m.reflectivity > 0.0 for m in linearise(scene).materials)
     tr = H.TRAVERSE_KD if traverse == "kd" else H.TRAVERSE_FLAT
     if two == "1":  # two streams forced for every scene: the recursion frames of two launches must not meet either
         monkeypatch.setenv("PORTRAYER_TWO_STREAMS", "1")
@@ -274,9 +281,11 @@ def test_two_frames_in_flight_on_two_streams_of_one_context(H, monkeypatch, scen
     d_img = [C.c_void_p(), C.c_void_p()]
     for d in d_img:
         assert lib.pt_device_alloc(c, w * h * 3, C.byref(d)) == 0
-    # two streams where the scene's kernels keep no recursion frames in HBM, one for both slots where they do (csrc/pt_api.hip: pt_context_stream)
+    # two streams where the scene's kernels keep no recursion frames in HBM, one for both slots where they do (csrc/pt_api.hip: pt_context_stream;
+    # needs_spill: something reflective, or more than PT_LIGHT_ROUND lights)
     assert lib.pt_context_stream(c, 0) and lib.pt_context_stream(c, 1)
-    assert (lib.pt_context_stream(c, 0) != lib.pt_context_stream(c, 1)) == (scene_name == "macho-cows" or two == "1")
+    assert (lib.pt_context_stream(c, 0) != lib.pt_context_stream(c, 1)) == (not needs_spill or two == "1")
+    assert needs_spill == (scene_name != "macho-cows")
     got, slots = [], []
     st = H.PtStats()
 
