@@ -234,6 +234,34 @@ int pt_render_finish(pt_context *ctx, pt_stats *stats);
 void *pt_context_stream(pt_context *ctx, int slot);
 int pt_context_next_slot(const pt_context *ctx);
 
+/* ---- Primary visibility: what is under each pixel. ONE primary ray per pixel of the slice - Camera::ray_at(x + offset[0], y + offset[1]),
+ * camera.rs:48-84; (0.5, 0.5) is the pixel centre PT_SAMPLE_CENTRE uses -, its nearest hit over [EPSILON, inf) in the traversal the scene was
+ * uploaded with, no shading, no lights, no secondary rays, no random numbers. Every buffer is OPTIONAL (NULL = not wanted, and nothing is computed
+ * for it), a full image, row-major; pixels outside the slice are left untouched. Every value carries the bits the render path computes on its way to
+ * the pixel's colour:
+ *   depth     width x height      f64  ray parameter t of the nearest hit (ray.rs:87-99)                          miss: +inf
+ *   position  width x height x 3  f64  world-space hit point (flat_scene.rs:85-95 / scene.rs:100-112)             miss: 0, 0, 0
+ *   normal    width x height x 3  f64  world-space normal, normalised (material.rs:123-125), BEFORE a normal map   miss: 0, 0, 0
+ *   node      width x height      i32  flattened node index (breadth-first, as in pt_scene)                       miss: -1
+ *   sub       width x height      i32  MESH / KDMESH: index of the triangle inside its mesh; else 0               miss: -1
+ *   material  width x height      i32  the node's material index: pt_scene.material[node], as uploaded             miss: -1
+ * Errors: PT_ERR_ARGUMENT (NULL context / camera / params, all six buffers NULL, a non-finite offset), PT_ERR_NO_SCENE, PT_ERR_SLICE - all before
+ * the first HIP call - and PT_ERR_TRAVERSAL as for a render. The pass has work buffers of its own: renders in flight on the context's two slots
+ * are not disturbed, and trees of any depth a render accepts are walked (the stack continues in HBM). */
+typedef struct {
+    uint32_t width, height;     /* Image::width / height                                                 */
+    pt_rect slice;              /* pixels to trace; an inverted slice traces nothing (render.rs:60-65)    */
+    double offset[2];           /* sample position inside the pixel, x then y                            */
+} pt_aov_params;
+typedef struct { double *depth; double *position; double *normal; int32_t *node; int32_t *sub; int32_t *material; } pt_aov_buffers;
+/* Host buffers, synchronous. kernel_ms (optional): device time of the kernel (HIP events). */
+int pt_aov(pt_context *ctx, const pt_camera *camera, const pt_aov_params *params, const pt_aov_buffers *host_out, double *kernel_ms);
+/* The same into DEVICE memory, queued on `hip_stream` (a hipStream_t, or NULL for the default stream) without synchronising the host.
+ * pt_aov_finish waits for that pass and returns what it found (PT_ERR_TRAVERSAL, else PT_OK) and, optionally, its kernel time; one pass
+ * may be in flight per context: a second pt_aov_device / pt_aov before pt_aov_finish is refused with PT_ERR_ARGUMENT. */
+int pt_aov_device(pt_context *ctx, const pt_camera *camera, const pt_aov_params *params, const pt_aov_buffers *device_out, void *hip_stream);
+int pt_aov_finish(pt_context *ctx, double *kernel_ms);
+
 /* Bytes of one rank's compact tile buffer for a slice split over tile_ranks ranks (equal for all ranks). */
 uint64_t pt_compact_bytes(const pt_render_params *params);
 /* Scatters the gathered compact buffers (rank-major) into a row-major image on the device. */

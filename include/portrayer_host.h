@@ -108,6 +108,12 @@ int ph_renderer_prepare_ms(ph_renderer *r, double out[5]);
 int ph_renderer_render(ph_renderer *r, const double camera[10], const pt_render_params *params, const double *background,
                        uint8_t *rgb, double *linear, pt_stats *stats);
 
+/* What is under each pixel (see pt_aov): one primary ray per pixel of params->slice through the camera a render of that size would use,
+ * host buffers out, each optional. A renderer spread over a node runs the pass on rank 0's context.
+ * `node` indexes the flattened nodes (ph_scene_flatten's order); `material` indexes the renderer's material table, which lists the scene's materials in the
+ * order the flattened nodes first use them: the numbering of ph_scene_flatten's `material` array, NOT that of ph_scene_export's `materials`. */
+int ph_renderer_aov(ph_renderer *r, const double camera[10], const pt_aov_params *params, const pt_aov_buffers *out, double *kernel_ms);
+
 /* Image::new + Image::render + Image::save with the crate's defaults (env SAMPLES, KD_DEPTH) on an
  * example scene: exercises the whole C++ API the way the reference's main() does. */
 int ph_example_render_to_png(const char *name, const char *assets_dir, int n, uint32_t width, uint32_t height, const char *png_path);

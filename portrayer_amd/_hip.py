@@ -76,6 +76,18 @@ class PtRenderParams(C.Structure):
                 ("collect_stats", C.c_int32)]
 
 
+class PtAovParams(C.Structure):
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("slice", PtRect), ("offset", C.c_double * 2)]
+
+
+class PtAovBuffers(C.Structure):
+    _fields_ = [("depth", _dp), ("position", _dp), ("normal", _dp), ("node", _ip), ("sub", _ip), ("material", _ip)]
+
+
+# pt_aov's outputs in the order of pt_aov_buffers: name -> (numpy dtype, components per pixel)
+AOV_BUFFERS = {"depth": (np.float64, 1), "position": (np.float64, 3), "normal": (np.float64, 3), "node": (np.int32, 1), "sub": (np.int32, 1), "material": (np.int32, 1)}
+
+
 class PtStats(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("primary", "shadow", "reflect", "refract", "depth11_skipped", "hits", "n_inner", "n_leaf",
                                           "n_analytic", "n_tri", "n_bbox", "kd_plane_miss", "stack_overflow")] + \
@@ -94,7 +106,8 @@ EXPORTS = ["pt_abi_version", "pt_device_count", "pt_context_create", "pt_context
            "pt_device_free", "pt_copy_to_device", "pt_copy_from_device", "pt_synchronize", "pt_measure_copy_bandwidth", "pt_test_cast_rays",
            "pt_test_math", "pt_test_work_items", "pt_node_create", "pt_node_destroy", "pt_node_last_error", "pt_node_ranks", "pt_node_uses_rccl", "pt_node_context",
            "pt_node_scene_upload", "pt_node_render", "pt_node_upload_background", "pt_node_render_resident", "pt_node_download_image",
-           "pt_node_device", "pt_node_frame_begin", "pt_node_frame_end", "pt_node_frames_in_flight", "pt_node_last_frame_host_ms", "pt_node_last_frame_rank_kernel_ms", "pt_test_pow_host", "pt_test_libm_host"]
+           "pt_node_device", "pt_node_frame_begin", "pt_node_frame_end", "pt_node_frames_in_flight", "pt_node_last_frame_host_ms", "pt_node_last_frame_rank_kernel_ms", "pt_test_pow_host", "pt_test_libm_host",
+           "pt_aov", "pt_aov_device", "pt_aov_finish"]
 
 
 def header_functions():
@@ -201,6 +214,12 @@ def lib() -> C.CDLL:
         l.pt_test_pow_host.argtypes = [C.c_uint64, _dp, _dp, _dp, _dp]
         l.pt_test_libm_host.restype = C.c_int
         l.pt_test_libm_host.argtypes = [C.c_int, C.c_uint64, _dp, _dp, _dp]
+        l.pt_aov.restype = C.c_int
+        l.pt_aov.argtypes = [C.c_void_p, C.POINTER(PtCamera), C.POINTER(PtAovParams), C.POINTER(PtAovBuffers), _dp]
+        l.pt_aov_device.restype = C.c_int
+        l.pt_aov_device.argtypes = [C.c_void_p, C.POINTER(PtCamera), C.POINTER(PtAovParams), C.POINTER(PtAovBuffers), C.c_void_p]
+        l.pt_aov_finish.restype = C.c_int
+        l.pt_aov_finish.argtypes = [C.c_void_p, _dp]
         _lib = l
     return _lib
 

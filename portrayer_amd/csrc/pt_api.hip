@@ -5,6 +5,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <string>
@@ -14,6 +15,7 @@
 #include "../../include/portrayer_hip.h"
 #include "pt_build.h"
 #include "pt_bvh.h"
+#include "pt_aov_inst.h"
 #include "pt_render_inst.h"
 #include "pt_shade.h"
 
@@ -271,6 +273,17 @@ struct pt_context {
     int slot_next = 0;     // the slot the next launch takes
     int slot_oldest = 0;   // the oldest launch not yet closed (== slot_next: none, unless every slot is pending)
     uint32_t last_mode = 0, last_variant = 0;
+    // The primary-visibility pass (pt_aov / pt_aov_device) owns its work buffers, so that the two render slots stay as they are whatever is in flight on them:
+    // the lanes' HBM stack columns, overflow flag + work queues, the device copies of the host-buffer path's six outputs, events and one pinned page.
+    struct Aov {
+        PtBuf stack_spill, misc, out[6];
+        hipEvent_t ev0 = nullptr, ev1 = nullptr, copy_done = nullptr;
+        unsigned char* host = nullptr;  // pinned: the first two words of misc (the second is the overflow flag)
+        bool pending = false;           // a pt_aov_device not yet closed by pt_aov_finish
+        hipStream_t stream = nullptr;   // of the last pass queued
+        bool queued = false;            // ... something of it may still be in flight (pt_aov_wait)
+        bool closed = false;            // ... and all of it was queued: copy_done is recorded behind it
+    } aov;
 };
 #define PT_SLOT_BYTES (256 + sizeof(PtCounters))
 
@@ -337,6 +350,12 @@ extern "C" void pt_context_destroy(pt_context* c) {
     PtBuf* bufs[] = {&c->inv, &c->fwd, &c->nrm, &c->info, &c->tri_v, &c->tri_e, &c->tri_leaf, &c->tri_n, &c->meshes, &c->materials, &c->lights,
                      &c->bvh, &c->bvh4, &c->bvh_items, &c->kd, &c->kd_items, &c->mat_maps, &c->uv_trans, &c->tex, &c->tex_rgb, &c->srgb_lut, &c->tri_uv, &c->texview, &c->mkd, &c->mkd_items, &c->slot[0].spill, &c->slot[0].stack_spill, &c->slot[0].accum, &c->slot[0].misc, &c->slot[1].spill, &c->slot[1].stack_spill, &c->slot[1].accum, &c->slot[1].misc, &c->bg, &c->rgb, &c->linear, &c->misc, &c->node_box, &c->kd_box, &c->mkd_box, &c->mkd_item_box, &c->kd_ref, &c->g_inv, &c->g_fwd, &c->g_nrm, &c->chain_off, &c->chain, &c->dfs_rank, &c->hier_rec, &c->own_inv};
     for (PtBuf* b : bufs) if (b->p) hipFree(b->p);
+    if (c->aov.queued) { if (c->aov.closed) hipEventSynchronize(c->aov.copy_done); else hipStreamSynchronize(c->aov.stream); }  // (pt_aov_wait)
+    for (PtBuf* b : {&c->aov.stack_spill, &c->aov.misc, &c->aov.out[0], &c->aov.out[1], &c->aov.out[2], &c->aov.out[3], &c->aov.out[4], &c->aov.out[5]}) if (b->p) hipFree(b->p);
+    if (c->aov.ev0) hipEventDestroy(c->aov.ev0);
+    if (c->aov.ev1) hipEventDestroy(c->aov.ev1);
+    if (c->aov.copy_done) hipEventDestroy(c->aov.copy_done);
+    if (c->aov.host) hipHostFree(c->aov.host);
     static_assert(pt_context::PT_SLOTS == 2, "the buffer list above names both slots");
     for (auto& sl : c->slot) {
         if (sl.stream) { hipStreamSynchronize(sl.stream); hipStreamDestroy(sl.stream); }
@@ -1124,6 +1143,27 @@ extern "C" int pt_test_work_items(const pt_render_params* p, uint32_t* sample_co
     return PT_OK;
 }
 
+// How a launch's traversal stacks are split between LDS and HBM - one place for the render kernels and the primary-visibility pass (pt_aov_common), whose
+// kernels lay their LDS out with the same code (pt_trace_wave: pt_wave_rows, pt_kd_layout).
+// pt_stack_lds_cap: entries per lane kept in LDS = what `block_budget` bytes of LDS per block leave beside `frame_bytes` of other per-block data (1 KB a row), at most the
+// scene's whole stack. The k-d walk keeps no saved bounds in HBM (round 5): its wavefront rows must hold the stack and, where the stack's slack is too small for it, the two
+// rows of the path table (pt_kd_layout, PtKdSav) - also under PORTRAYER_LDS_STACK=1 (experiments / tests of the overflow path), which then only shrinks the LANES' stacks.
+static int pt_stack_lds_cap(const PtSceneView& sc, size_t block_budget, size_t frame_bytes, bool kd_sem) {
+    int lds_cap = block_budget > frame_bytes ? (int)((block_budget - frame_bytes) / (PT_BLOCK * 4)) : 0;
+    lds_cap = std::max(lds_cap, 2);
+    if (const char* e = getenv("PORTRAYER_LDS_STACK")) lds_cap = std::max(1, atoi(e));
+    int cap = std::min(lds_cap, sc.stack_cap);
+    if (kd_sem) cap = std::max(cap, (sc.stack_cap + 63) / 64 + 2);
+    return cap;
+}
+// pt_stack_column: entries of a lane's HBM stack column (PtStackSpill::gbase). + wave_rows: the wavefront's own stack takes LDS rows from the lanes' stacks (pt_wave_rows,
+// pt_render_simple.h): eight, or what a deep tree needs; and at least everything a lane's own stack can reach (pt_trace_wave gives the lanes fewer LDS rows in the k-d semantics).
+static size_t pt_stack_column(const PtSceneView& sc, int stack_lds_cap) {
+    const int wave_rows = std::min(std::max(8, (sc.stack_cap + 63) / 64), std::max(stack_lds_cap, 8));  // (pt_wave_rows: at most this many)
+    const int stack_spill_entries = std::max(sc.stack_cap - stack_lds_cap + wave_rows, 0);
+    return (size_t)std::max(stack_spill_entries, sc.stack_cap);
+}
+
 static int pt_render_common(pt_context* c, PtRenderArgs& a, bool stats, hipStream_t stream, int slot_index = -1) {
     // LDS per block = traversal stack (as much of it as leaves room for three blocks per CU) + the shaded hit's frame (+ a parked one);
     // deeper stack entries live in HBM (PtStackSpill).
@@ -1179,13 +1219,7 @@ static int pt_render_common(pt_context* c, PtRenderArgs& a, bool stats, hipStrea
     size_t block_budget = a.four_waves >= 6 ? 26 * 1024 : (a.four_waves == 5 ? 31 * 1024 : (a.four_waves ? 39 * 1024 : 52 * 1024));  // 3 x 52 KB, 4 x 39 KB, 5 x 31 KB or 6 x 26 KB of the CU's 160 KB
     if (const char* e = getenv("PORTRAYER_LDS_BUDGET_KB")) block_budget = (size_t)std::max(16, std::min(160, atoi(e))) * 1024;  // experiment: 80 = two blocks per CU
     const size_t frame_bytes = (size_t)(PT_LDS_FRAME_F64 + a.park_slots * PT_PARK_F64) * PT_BLOCK * 8;
-    int lds_cap = block_budget > frame_bytes ? (int)((block_budget - frame_bytes) / (PT_BLOCK * 4)) : 0;
-    lds_cap = std::max(lds_cap, 2);
-    if (const char* e = getenv("PORTRAYER_LDS_STACK")) lds_cap = std::max(1, atoi(e));  // experiments / tests of the overflow path
-    a.stack_lds_cap = std::min(lds_cap, a.scene.stack_cap);
-    // the k-d walk keeps no saved bounds in HBM any more (round 5): its wavefront rows must hold the stack and, where the stack's slack is too small for it, the
-    // two rows of the path table (pt_kd_layout, PtKdSav) - also under PORTRAYER_LDS_STACK=1, which then only shrinks the LANES' stacks
-    if (kd_sem) a.stack_lds_cap = std::max(a.stack_lds_cap, (a.scene.stack_cap + 63) / 64 + 2);
+    a.stack_lds_cap = pt_stack_lds_cap(a.scene, block_budget, frame_bytes, kd_sem);
     a.grid_share = 1;  // (a share of the resident blocks per launch was tried for ranks that share a GPU, round 5 c23: their kernels do not run side by side - 35.5 -> 14.3 Gray/s)
     uint32_t grid = 0;
     PT_HIP(c, pt_dispatch(a, stats, c->n_cu, stream, &grid, false));
@@ -1218,10 +1252,7 @@ static int pt_render_common(pt_context* c, PtRenderArgs& a, bool stats, hipStrea
     pt_context::Slot& sl = c->slot[slot_index];  // the launch's work buffers are its slot's: another frame may be in flight on the other slot's
     const size_t spill_bytes = c->needs_spill ? (size_t)a.n_lanes * PT_SPILL_DEPTHS * PT_SPILL_STRIDE * sizeof(double) : 16;
     if ((rc = pt_reserve(c, sl.spill, spill_bytes))) return rc;
-    // + wave_rows: the wavefront's own stack takes LDS rows from the lanes' stacks (pt_wave_rows, pt_render_simple.h): eight, or what a deep tree needs
-    const int wave_rows = std::min(std::max(8, (a.scene.stack_cap + 63) / 64), std::max(a.stack_lds_cap, 8));  // (pt_wave_rows: at most this many)
-    const int stack_spill_entries = std::max(a.scene.stack_cap - a.stack_lds_cap + wave_rows, 0);
-    const size_t stack_column = (size_t)std::max(stack_spill_entries, a.scene.stack_cap);  // everything a lane's own stack can reach (pt_trace_wave gives the lanes fewer LDS rows in the k-d semantics)
+    const size_t stack_column = pt_stack_column(a.scene, a.stack_lds_cap);
     if ((rc = pt_reserve(c, sl.stack_spill, (size_t)a.n_lanes * stack_column * 4))) return rc;  // (the k-d walk's saved bounds needed columns behind this until round 5)
     // The occluder table of the mesh-free walks' shadow rays (pt_trace_packet): one word per (own 8x8 tile, light), behind the work
     // queues, zeroed with them before every launch - what it remembers comes from the frame being rendered, never from an earlier one.
@@ -1431,6 +1462,161 @@ extern "C" int pt_untile_host(const pt_render_params* p, const uint8_t* gathered
         }
     }
     return PT_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Primary visibility (pt_aov.h)
+// ------------------------------------------------------------------------------------------------
+static hipError_t pt_aov_dispatch(const PtAovArgs& a, int n_cu, hipStream_t stream, uint32_t* grid, bool launch) {
+    switch (a.r.scene.mode) {
+    case PT_MODE_KD: return pt_aov_launch_mode_2(a, n_cu, stream, grid, launch);
+    case PT_MODE_FLAT_NOMESH: return pt_aov_launch_mode_3(a, n_cu, stream, grid, launch);
+    case PT_MODE_FLAT_KDMESH: return pt_aov_launch_mode_4(a, n_cu, stream, grid, launch);
+    case PT_MODE_HIER: return pt_aov_launch_mode_5(a, n_cu, stream, grid, launch);
+    case PT_MODE_HIER_NOMESH: return pt_aov_launch_mode_6(a, n_cu, stream, grid, launch);
+    case PT_MODE_KD_NOMESH: return pt_aov_launch_mode_7(a, n_cu, stream, grid, launch);
+    case PT_MODE_HIER_MESH: return pt_aov_launch_mode_8(a, n_cu, stream, grid, launch);
+    case PT_MODE_KD_MESH: return pt_aov_launch_mode_9(a, n_cu, stream, grid, launch);
+    default: return pt_aov_launch_mode_1(a, n_cu, stream, grid, launch);
+    }
+}
+
+// Everything that can be refused without a HIP call, in the order the header gives.
+static int pt_aov_check(pt_context* c, const pt_camera* cam, const pt_aov_params* p, const pt_aov_buffers* out) {
+    if (!c || !cam || !p) return PT_ERR_ARGUMENT;
+    if (!out || !(out->depth || out->position || out->normal || out->node || out->sub || out->material))
+        return pt_fail(c, PT_ERR_ARGUMENT, "pt_aov: no output buffer asked for");
+    if (!std::isfinite(p->offset[0]) || !std::isfinite(p->offset[1])) return pt_fail(c, PT_ERR_ARGUMENT, "pt_aov: offset must be finite");
+    if (!c->have_scene) return pt_fail(c, PT_ERR_NO_SCENE, "no scene uploaded");
+    if (p->width == 0 || p->height == 0) return pt_fail(c, PT_ERR_ARGUMENT, "width and height must be positive");
+    if (p->slice.x0 >= p->width || p->slice.x1 >= p->width || p->slice.y0 >= p->height || p->slice.y1 >= p->height)
+        return pt_fail(c, PT_ERR_SLICE, "slice corner outside the image (render.rs:79-90)");
+    if (c->aov.pending) return pt_fail(c, PT_ERR_ARGUMENT, "a pt_aov_device pass is in flight: pt_aov_finish first");
+    return PT_OK;
+}
+
+// Queues the pass on `stream`: work counter + overflow flag zeroed, the kernel between the pass's two events, the flag copied to the pinned page behind it.
+// `out` holds DEVICE pointers. The LDS stack area is sized like a render's (pt_render_common) for the waves per SIMD the instantiation is compiled for, less
+// the hit frame a render keeps there; deeper entries of a lane's stack go to its HBM column.
+static int pt_aov_common(pt_context* c, const pt_camera* cam, const pt_aov_params* p, const pt_aov_buffers& out, hipStream_t stream) {
+    pt_context::Aov& v = c->aov;
+    if (!v.ev0) {
+        PT_HIP(c, hipEventCreate(&v.ev0));
+        PT_HIP(c, hipEventCreate(&v.ev1));
+        PT_HIP(c, hipEventCreateWithFlags(&v.copy_done, hipEventDisableTiming));
+        PT_HIP(c, hipHostMalloc((void**)&v.host, 256, hipHostMallocDefault));
+    }
+    pt_render_params rp;
+    memset(&rp, 0, sizeof rp);
+    rp.width = p->width; rp.height = p->height; rp.slice = p->slice;
+    rp.samples = 1; rp.sample_mode = PT_SAMPLE_CENTRE; rp.tile_rank = 0; rp.tile_ranks = 1;
+    PtAovArgs a;
+    pt_fill_args(c, cam, &rp, &a.r);  // samples = 1: one work item per 8x8 tile of the slice
+    a.off_x = p->offset[0]; a.off_y = p->offset[1];
+    a.depth = out.depth; a.position = out.position; a.normal = out.normal; a.node = out.node; a.sub = out.sub; a.material = out.material;
+    const int mode = a.r.scene.mode;
+    const bool kd_sem = mode == PT_MODE_KD || mode == PT_MODE_KD_NOMESH || mode == PT_MODE_KD_MESH;
+    const size_t block_budget = pt_aov_waves(mode) == 3 ? 52 * 1024 : 39 * 1024;  // 3 x 52 KB or 4 x 39 KB of the CU's 160 KB, as for a render; no hit frame beside the stacks
+    a.r.stack_lds_cap = pt_stack_lds_cap(a.r.scene, block_budget, 0, kd_sem);
+    a.r.grid_share = 1;
+    uint32_t grid = 0;
+    PT_HIP(c, pt_aov_dispatch(a, c->n_cu, stream, &grid, false));
+    a.r.n_lanes = grid * PT_BLOCK;
+    const size_t stack_column = pt_stack_column(a.r.scene, a.r.stack_lds_cap);
+    int rc;
+    const size_t aov_misc_bytes = 256 + PT_FINE_QUEUES * PT_QUEUE_STRIDE * 4;  // the overflow flag (word 1, where a render has it), the work queues
+    if ((rc = pt_reserve(c, v.stack_spill, (size_t)a.r.n_lanes * stack_column * 4)) || (rc = pt_reserve(c, v.misc, aov_misc_bytes))) return rc;
+    a.r.stack_spill = (uint32_t*)v.stack_spill.p;
+    a.r.overflow_flag = (unsigned int*)v.misc.p + 1;
+    a.r.work_queues = (unsigned int*)((char*)v.misc.p + 256);
+    a.r.fine_queues = 16;  // as a render of this size (pt_render_common)
+    v.stream = stream; v.queued = true; v.closed = false;  // from here on something of the pass may be in flight on `stream`, whatever fails below
+    PT_HIP(c, hipMemsetAsync(v.misc.p, 0, aov_misc_bytes, stream));
+    PT_HIP(c, hipEventRecord(v.ev0, stream));
+    if (a.r.n_items) PT_HIP(c, pt_aov_dispatch(a, c->n_cu, stream, &grid, true));
+    PT_HIP(c, hipEventRecord(v.ev1, stream));
+    PT_HIP(c, hipMemcpyAsync(v.host, v.misc.p, 8, hipMemcpyDeviceToHost, stream));
+    PT_HIP(c, hipEventRecord(v.copy_done, stream));
+    v.closed = true;
+    return PT_OK;
+}
+
+// Waits for whatever the last pt_aov_common queued: the event behind its last copy, or - where queuing failed half way - its stream.
+static int pt_aov_wait(pt_context* c) {
+    pt_context::Aov& v = c->aov;
+    if (!v.queued) return PT_OK;
+    v.queued = false;
+    if (v.closed) PT_HIP(c, hipEventSynchronize(v.copy_done));
+    else PT_HIP(c, hipStreamSynchronize(v.stream));
+    return PT_OK;
+}
+
+// After the pass's copy_done: the kernel time and what the overflow flag says (as pt_collect_stats reads a render's).
+static int pt_aov_close(pt_context* c, double* kernel_ms) {
+    unsigned int head[2];
+    memcpy(head, c->aov.host, sizeof head);
+    if (kernel_ms) {
+        float ms = 0.f;
+        PT_HIP(c, hipEventElapsedTime(&ms, c->aov.ev0, c->aov.ev1));
+        *kernel_ms = ms;
+    }
+    if (head[1] & 4u) return pt_fail(c, PT_ERR_TRAVERSAL, "a tree walk did not end (watchdog): results invalid");
+    if (head[1]) return pt_fail(c, PT_ERR_TRAVERSAL, "traversal stack overflow");
+    return PT_OK;
+}
+
+extern "C" int pt_aov(pt_context* c, const pt_camera* cam, const pt_aov_params* p, const pt_aov_buffers* host_out, double* kernel_ms) {
+    int rc = pt_aov_check(c, cam, p, host_out);
+    if (rc) return rc;
+    PT_HIP(c, hipSetDevice(c->device));
+    const size_t px = (size_t)p->width * p->height;
+    void* host[6] = {host_out->depth, host_out->position, host_out->normal, host_out->node, host_out->sub, host_out->material};
+    const size_t elem[6] = {8, 24, 24, 4, 4, 4};  // bytes per pixel
+    void* dev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    for (int k = 0; k < 6; k++) {
+        if (!host[k]) continue;
+        if ((rc = pt_reserve(c, c->aov.out[k], px * elem[k]))) return rc;
+        dev[k] = c->aov.out[k].p;
+    }
+    pt_aov_buffers d_out;
+    d_out.depth = (double*)dev[0]; d_out.position = (double*)dev[1]; d_out.normal = (double*)dev[2];
+    d_out.node = (int32_t*)dev[3]; d_out.sub = (int32_t*)dev[4]; d_out.material = (int32_t*)dev[5];
+    rc = pt_aov_common(c, cam, p, d_out, nullptr);
+    const int rc_wait = pt_aov_wait(c);
+    if (rc || (rc = rc_wait)) return rc;
+    // Only the slice's rectangle comes back (the kernel wrote nothing else, and the device copies hold nothing else of value): picking one pixel of a
+    // 1920x1080 frame moves 68 bytes, and pixels outside the slice keep the caller's bytes because they are never touched.
+    if (p->slice.x1 >= p->slice.x0 && p->slice.y1 >= p->slice.y0) {
+        const size_t cols = (size_t)p->slice.x1 - p->slice.x0 + 1, rows = (size_t)p->slice.y1 - p->slice.y0 + 1;
+        for (int k = 0; k < 6; k++) {
+            if (!host[k]) continue;
+            const size_t pitch = (size_t)p->width * elem[k], first = ((size_t)p->slice.y0 * p->width + p->slice.x0) * elem[k];
+            PT_HIP(c, hipMemcpy2D((char*)host[k] + first, pitch, (const char*)dev[k] + first, pitch, cols * elem[k], rows, hipMemcpyDeviceToHost));
+        }
+    }
+    return pt_aov_close(c, kernel_ms);
+}
+
+extern "C" int pt_aov_device(pt_context* c, const pt_camera* cam, const pt_aov_params* p, const pt_aov_buffers* device_out, void* hip_stream) {
+    int rc = pt_aov_check(c, cam, p, device_out);
+    if (rc) return rc;
+    PT_HIP(c, hipSetDevice(c->device));
+    if ((rc = pt_aov_common(c, cam, p, *device_out, (hipStream_t)hip_stream))) {
+        pt_aov_wait(c);  // what was queued before the failure must not outlive the call: the next pass may reallocate the buffers under it
+        return rc;
+    }
+    c->aov.pending = true;
+    return PT_OK;
+}
+
+extern "C" int pt_aov_finish(pt_context* c, double* kernel_ms) {
+    if (!c) return PT_ERR_ARGUMENT;
+    if (!c->aov.pending) return pt_fail(c, PT_ERR_ARGUMENT, "no pt_aov_device pass in flight");
+    PT_HIP(c, hipSetDevice(c->device));
+    c->aov.pending = false;
+    int rc = pt_aov_wait(c);
+    if (rc) return rc;
+    return pt_aov_close(c, kernel_ms);
 }
 
 // ------------------------------------------------------------------------------------------------

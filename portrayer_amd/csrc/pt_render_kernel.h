@@ -304,8 +304,9 @@ __global__ void __launch_bounds__(PT_BLOCK, PT_VAR_WAVES(VAR)) pt_render_kernel(
 // KERNEL is a non-type template parameter: every kernel instantiation gets its own `state` (templated on the kernel's TYPE - void(*)(PtRenderArgs)
 // for all of them - one array was shared by all kernels of a translation unit, and a kernel inherited the occupancy and the raised LDS limit of
 // whichever kernel with the same LDS size had been launched first: ADVICE r03).
-template <auto KERNEL>
-static hipError_t pt_launch_kernel(size_t lds, const PtRenderArgs& a, int n_cu, hipStream_t stream, uint32_t* grid_out, bool launch) {
+// ARGS: the kernel's argument block (PtRenderArgs; PtAovArgs for the primary-visibility pass); n_items / grid_share: PtRenderArgs' fields of that name.
+template <auto KERNEL, class ARGS>
+static hipError_t pt_launch_kernel_args(size_t lds, const ARGS& a, uint32_t n_items, uint32_t grid_share, int n_cu, hipStream_t stream, uint32_t* grid_out, bool launch) {
     constexpr auto kernel = KERNEL;
     struct PerDevice { size_t lds_allowed = 64 * 1024; size_t occ_lds = ~(size_t)0; int per_cu = 0; };
     static PerDevice state[PT_MAX_DEVICES];  // one per kernel instantiation and device
@@ -332,14 +333,18 @@ static hipError_t pt_launch_kernel(size_t lds, const PtRenderArgs& a, int n_cu, 
     }
     per_cu = st.per_cu;
     }
-    uint32_t want = (a.n_items + (PT_BLOCK / 64) - 1) / (PT_BLOCK / 64);
+    uint32_t want = (n_items + (PT_BLOCK / 64) - 1) / (PT_BLOCK / 64);
     if (const char* env = getenv("PORTRAYER_BLOCKS_PER_CU")) per_cu = std::max(1, std::min(per_cu, atoi(env)));  // experiment: fewer resident lanes
-    const uint32_t resident = std::max<uint32_t>((uint32_t)(n_cu * per_cu) / std::max<uint32_t>(a.grid_share, 1u), 1u);  // (grid_share: contexts launching side by side on one GPU)
+    const uint32_t resident = std::max<uint32_t>((uint32_t)(n_cu * per_cu) / std::max<uint32_t>(grid_share, 1u), 1u);  // (grid_share: contexts launching side by side on one GPU)
     uint32_t grid = std::min<uint32_t>(std::max<uint32_t>(want, 1u), resident);
     *grid_out = grid;
     if (!launch) return hipSuccess;
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(PT_BLOCK), lds, stream, a);
     return hipGetLastError();
+}
+template <auto KERNEL>
+static hipError_t pt_launch_kernel(size_t lds, const PtRenderArgs& a, int n_cu, hipStream_t stream, uint32_t* grid_out, bool launch) {
+    return pt_launch_kernel_args<KERNEL>(lds, a, a.n_items, a.grid_share, n_cu, stream, grid_out, launch);
 }
 
 // Which kernel runs (`variant`, chosen in pt_render_common):

@@ -19,7 +19,7 @@ _dp, _ip, _up, _u64p, _u8p = H._dp, H._ip, H._up, H._u64p, H._u8p
 
 EXPORTS = ["ph_last_error", "ph_scene_create", "ph_example_scene", "ph_scene_destroy", "ph_scene_counts", "ph_scene_export", "ph_scene_export_textures",
            "ph_scene_flatten", "ph_scene_kdtree", "ph_camera", "ph_obj_load", "ph_renderer_create", "ph_renderer_destroy",
-           "ph_renderer_context", "ph_renderer_ranks", "ph_renderer_node", "ph_renderer_prepare_ms", "ph_renderer_render", "ph_example_render_to_png", "ph_png_read", "ph_png_write", "ph_image_read", "ph_scene_graph"]
+           "ph_renderer_context", "ph_renderer_ranks", "ph_renderer_node", "ph_renderer_prepare_ms", "ph_renderer_render", "ph_renderer_aov", "ph_example_render_to_png", "ph_png_read", "ph_png_write", "ph_image_read", "ph_scene_graph"]
 
 
 class PortrayerHostError(RuntimeError):
@@ -76,6 +76,8 @@ def lib() -> C.CDLL:
         l.ph_renderer_prepare_ms.restype = C.c_int; l.ph_renderer_prepare_ms.argtypes = [vp, _dp]
         l.ph_renderer_render.restype = C.c_int
         l.ph_renderer_render.argtypes = [vp, _dp, C.POINTER(H.PtRenderParams), _dp, _u8p, _dp, C.POINTER(H.PtStats)]
+        l.ph_renderer_aov.restype = C.c_int
+        l.ph_renderer_aov.argtypes = [vp, _dp, C.POINTER(H.PtAovParams), C.POINTER(H.PtAovBuffers), _dp]
         l.ph_scene_export_textures.restype = C.c_int
         l.ph_scene_export_textures.argtypes = [vp, _u64p, _ip, _ip, _dp, _up, _u64p, _u8p, _dp, _u8p, _dp, _u8p]
         l.ph_example_render_to_png.restype = C.c_int
@@ -286,3 +288,31 @@ class Renderer:
         c = np.ascontiguousarray(cam10, dtype=np.float64)
         _check(lib().ph_renderer_render(self._h, _p(c, _dp), C.byref(p), _p(bg, _dp), _p(rgb, _u8p), _p(linear, _dp), C.byref(st)), "ph_renderer_render")
         return rgb, linear, st.as_dict()
+
+    def aov(self, cam10, width: int, height: int, rect=None, offset=(0.5, 0.5), want=("depth", "position", "normal", "node", "sub", "material"),
+            into: Optional[dict] = None) -> dict:
+        """What is under each pixel (pt_aov): one primary ray per pixel of `rect` at (x + offset[0], y + offset[1]). Returns the arrays named in
+        `want` - (H, W) or (H, W, 3); depth +inf, ids -1, point and normal 0 where nothing is hit - and `kernel_ms`. Buffers not in `want` are not
+        computed. Pixels outside `rect` are not written: they keep what `into` (a dict of arrays of the right shape and dtype) holds there; without `into` the
+        arrays start zero-filled (so outside `rect` depth is 0.0 and the ids are 0, not the miss values). `material` indexes the Renderer's material table: the
+        numbering of Scene.flatten()["material"], materials in the order the flattened nodes first use them (not the order of Scene.export()["materials"])."""
+        want = tuple(want)
+        unknown = [n for n in want if n not in H.AOV_BUFFERS]
+        if unknown or not want:
+            raise ValueError("want must name some of %s, got %r" % (", ".join(H.AOV_BUFFERS), want))
+        x0, y0, x1, y1 = rect if rect is not None else (0, 0, width - 1, height - 1)
+        p = H.PtAovParams(width, height, H.PtRect(x0, y0, x1, y1), (C.c_double * 2)(float(offset[0]), float(offset[1])))
+        out, b = {}, H.PtAovBuffers()
+        for name in want:
+            dtype, comps = H.AOV_BUFFERS[name]
+            shape = (height, width) if comps == 1 else (height, width, comps)
+            a = into[name] if into is not None and name in into else np.zeros(shape, dtype=dtype)
+            if a.shape != shape or a.dtype != dtype or not a.flags.c_contiguous:
+                raise ValueError("into[%r] must be a C-contiguous %s array of shape %r" % (name, np.dtype(dtype).name, shape))
+            out[name] = a
+            setattr(b, name, _p(a, _dp if dtype is np.float64 else _ip))
+        ms = C.c_double(0.0)
+        c = np.ascontiguousarray(cam10, dtype=np.float64)
+        _check(lib().ph_renderer_aov(self._h, _p(c, _dp), C.byref(p), C.byref(b), C.byref(ms)), "ph_renderer_aov")
+        out["kernel_ms"] = ms.value
+        return out

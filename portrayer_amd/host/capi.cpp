@@ -521,6 +521,16 @@ extern "C" int ph_renderer_render(ph_renderer* r, const double camera[10], const
     });
 }
 
+extern "C" int ph_renderer_aov(ph_renderer* r, const double camera[10], const pt_aov_params* p, const pt_aov_buffers* out, double* kernel_ms) {
+    if (!r || !camera || !p || !out) return bad("null argument");
+    return guarded([&]() -> int {
+        pt_camera pc = detail::Camera(camera_from(camera), (double)p->width, (double)p->height).to_abi();  // the camera a render of this size gets
+        int rc = pt_aov(r->r->context(), &pc, p, out, kernel_ms);  // (a renderer spread over a node: rank 0's context, the whole slice)
+        if (rc != PT_OK) { g_error = pt_last_error(r->r->context()); return rc == PT_ERR_SLICE ? PH_ERR_PANIC : PH_ERR_RUNTIME; }
+        return PH_OK;
+    });
+}
+
 extern "C" int ph_example_render_to_png(const char* name, const char* assets_dir, int n, uint32_t width, uint32_t height, const char* png_path) {
     if (!name || !png_path) return bad("null argument");
     return guarded([&]() -> int {

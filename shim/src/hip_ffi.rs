@@ -76,6 +76,11 @@ pub struct PtRenderParams {
     pub sample_mode: i32, pub background_rows: i32, pub tile_rank: u32, pub tile_ranks: u32, pub collect_stats: i32,
 }
 
+#[repr(C)] pub struct PtAovParams { pub width: u32, pub height: u32, pub slice: PtRect, pub offset: [f64; 2] }   // pt_aov_params: offset (0.5, 0.5) = the pixel centre
+#[repr(C)]
+pub struct PtAovBuffers {                  // pt_aov_buffers: each optional (null = not wanted), full image, row-major
+    pub depth: *mut f64, pub position: *mut f64, pub normal: *mut f64, pub node: *mut i32, pub sub: *mut i32, pub material: *mut i32,
+}
 #[repr(C)] #[derive(Default)]
 pub struct PtStats {
     pub primary: u64, pub shadow: u64, pub reflect: u64, pub refract: u64, pub depth11_skipped: u64, pub hits: u64,
@@ -97,6 +102,11 @@ extern "C" {
     pub fn pt_render_device(ctx: *mut PtContext, camera: *const PtCamera, d_background: *const f64, params: *const PtRenderParams,
                             compact: c_int, d_rgb: *mut c_void, hip_stream: *mut c_void) -> c_int;
     pub fn pt_render_finish(ctx: *mut PtContext, stats: *mut PtStats) -> c_int;
+    // what is under each pixel: one primary ray per pixel of the slice, no shading (depth, position, normal, node / triangle / material ids)
+    pub fn pt_aov(ctx: *mut PtContext, camera: *const PtCamera, params: *const PtAovParams, host_out: *const PtAovBuffers, kernel_ms: *mut f64) -> c_int;
+    pub fn pt_aov_device(ctx: *mut PtContext, camera: *const PtCamera, params: *const PtAovParams, device_out: *const PtAovBuffers,
+                         hip_stream: *mut c_void) -> c_int;
+    pub fn pt_aov_finish(ctx: *mut PtContext, kernel_ms: *mut f64) -> c_int;
     pub fn pt_context_stream(ctx: *mut PtContext, slot: c_int) -> *mut c_void;
     pub fn pt_context_next_slot(ctx: *const PtContext) -> c_int;
     // one render call over the GPUs of a node (one context per GPU, one RCCL gather)

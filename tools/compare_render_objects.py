@@ -1,0 +1,51 @@
+#!/usr/bin/env python3
+"""Are the render kernels of two builds the same machine code?
+
+    python3 tools/compare_render_objects.py <dir of the other build's objects> [<dir of this build's objects>]
+
+Extracts the gfx950 code object from pt_render_m1.o .. pt_render_m9.o of both directories (llvm-objdump --offloading, as
+tests/test_kernel_resources.py does) and compares them byte for byte. A change that claims to leave the render path alone
+(a new pass beside it, host code) runs this against a build of its parent commit: identical code objects mean identical
+behaviour and speed of every render kernel, without a GPU. Exit status 0: all nine identical; 1: some differ (named)."""
+import filecmp
+import os
+import shutil
+import subprocess
+import sys
+import tempfile
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+LLVM = os.environ.get("LLVM_BIN", "/opt/rocm/lib/llvm/bin")
+
+
+def code_object(obj: str, tmp: str) -> str:
+    """Path of the gfx950 code object extracted from the host object `obj` (into a directory of its own under tmp)."""
+    d = tempfile.mkdtemp(dir=tmp)
+    shutil.copy(obj, os.path.join(d, "k.o"))
+    subprocess.run([os.path.join(LLVM, "llvm-objdump"), "--offloading", "k.o"], cwd=d, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, check=False)
+    cos = [f for f in os.listdir(d) if "gfx950" in f]
+    if not cos:
+        raise SystemExit("no gfx950 code object in %s" % obj)
+    return os.path.join(d, cos[0])
+
+
+def main(argv):
+    if len(argv) < 2:
+        raise SystemExit(__doc__)
+    other = argv[1]
+    mine = argv[2] if len(argv) > 2 else os.path.join(ROOT, "portrayer_amd", "csrc")
+    differ = []
+    with tempfile.TemporaryDirectory() as tmp:
+        for m in range(1, 10):
+            name = "pt_render_m%d.o" % m
+            a, b = code_object(os.path.join(other, name), tmp), code_object(os.path.join(mine, name), tmp)
+            same = filecmp.cmp(a, b, shallow=False)
+            print("%-18s %9d bytes  %s" % (name, os.path.getsize(b), "identical" if same else "DIFFERENT"))
+            if not same:
+                differ.append(name)
+    print("render code objects: %s" % ("all nine byte-identical" if not differ else "differ: " + ", ".join(differ)))
+    return 1 if differ else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main(sys.argv))
