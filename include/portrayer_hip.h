@@ -262,6 +262,47 @@ int pt_aov(pt_context *ctx, const pt_camera *camera, const pt_aov_params *params
 int pt_aov_device(pt_context *ctx, const pt_camera *camera, const pt_aov_params *params, const pt_aov_buffers *device_out, void *hip_stream);
 int pt_aov_finish(pt_context *ctx, double *kernel_ms);
 
+/* ---- Ray queries: rays the CALLER supplies (the crate's public Ray / RayCast::ray_cast, ray.rs, kdmesh.rs:99-166) - picking from a point other than
+ * the eye, visibility between points, ambient-occlusion and light-map baking, range sensors, cameras the crate does not have. `origins` and
+ * `directions` are n x 3 f64 in world space; a direction is used as given, NOT normalised, and t is the ray parameter along it. Per ray, in the
+ * traversal the scene was uploaded with:
+ *   any_hit = 0   the nearest hit over [EPSILON, inf). Every buffer is OPTIONAL (NULL = not wanted, and nothing is computed for it), n entries, indexed
+ *                 like the input; t / position / normal / node / sub / material mean exactly what depth / position / normal / node / sub / material
+ *                 mean in pt_aov, miss values included (+inf; 0, 0, 0; -1), and carry the same bits. occluded (u8) = node >= 0.
+ *   any_hit = 1   is anything in the way over [EPSILON, inf) (the shadow rays' question, material.rs:171-179): occluded = 1 or 0. ONLY `occluded` may be
+ *                 asked for - which occluder a walk meets first depends on how rays are scheduled, so it is not part of the contract.
+ * The range is [EPSILON, inf) as everywhere in this code base: a bounded segment (t_max) would change the walks the render kernels share and is not offered;
+ * callers compare t with their own bound (any_hit = 0).
+ * Rays that are NOT TRACED report a miss (occluded = 0), occupy no lane of the walk and change no other ray's result: a ray with a non-finite component,
+ * with an all-zero direction, or with a component of origin or direction beyond 1e18 in magnitude. The last rule keeps the f32 constants of the walks'
+ * conservative box test finite and their error margins valid (the reciprocal of a direction component and its product with the origin stay inside the f32
+ * range; 1e18 is also the bound pt_scene_upload puts on box coordinates). Direction components BELOW 1e-18 in magnitude need no such rule: the box test
+ * then ignores that axis, which stays conservative, and the exact f64 primitive tests decide.
+ * reorder: 0 = 64 consecutive rays share a wavefront, whose one tree walk pays for the union of their paths; 1 = the device first sorts the rays by
+ *   (direction octant, Morton code of the origin inside the scene tree's root box; radix sort) and wavefronts take 64 consecutive rays of THAT order. Results are
+ *   bit-identical either way and are written at the caller's index; kernel_ms covers keying, sort and cast. Coherent batches (camera rays in pixel order,
+ *   anything already grouped) gain nothing and pay the sort, about 16 bytes of extra traffic per ray per radix pass; it is meant for large batches in
+ *   no useful order (ambient-occlusion and bounce rays). From which batch size and degree of disorder on it wins has not been measured yet: this is
+ *   the byte count of profiles/rays/notes.md section 2, whose measure.py is the script to settle it with.
+ * Errors, before the first HIP call: PT_ERR_ARGUMENT (NULL context / params / origins / directions; no buffer asked for; n > PT_RAYS_MAX; any_hit or
+ * reorder other than 0 or 1; any_hit = 1 with a buffer other than `occluded`), PT_ERR_NO_SCENE. n = 0 is PT_OK: nothing is launched or written. During the
+ * pass: PT_ERR_TRAVERSAL as for a render; trees of any depth a render accepts are walked (the stack continues in HBM). The pass has work buffers of its own:
+ * renders in flight on the context's two slots and a pt_aov_device pass are not disturbed. */
+#define PT_RAYS_MAX 0x40000000ull   /* rays per call (2^30) */
+typedef struct {
+    uint64_t n;        /* rays                                                                        */
+    int32_t any_hit;   /* 0: nearest hit; 1: occlusion query                                          */
+    int32_t reorder;   /* 0: caller's order; 1: the device groups like rays first (see above)         */
+} pt_rays_params;
+typedef struct { double *t; double *position; double *normal; int32_t *node; int32_t *sub; int32_t *material; uint8_t *occluded; } pt_rays_buffers;
+/* Host buffers, synchronous: uploads the rays, copies back the buffers asked for. kernel_ms (optional): device time of the pass (HIP events). */
+int pt_rays(pt_context *ctx, const pt_rays_params *params, const double *origins, const double *directions, const pt_rays_buffers *host_out, double *kernel_ms);
+/* The same with rays and results in DEVICE memory, queued on `hip_stream` (a hipStream_t, or NULL for the default stream) without synchronising the
+ * host. pt_rays_finish waits for that pass and returns what it found (PT_ERR_TRAVERSAL, else PT_OK) and, optionally, its device time; one pass may be
+ * in flight per context: a second pt_rays_device / pt_rays before pt_rays_finish is refused with PT_ERR_ARGUMENT. (n = 0 queues nothing and is not in flight.) */
+int pt_rays_device(pt_context *ctx, const pt_rays_params *params, const double *d_origins, const double *d_directions, const pt_rays_buffers *device_out, void *hip_stream);
+int pt_rays_finish(pt_context *ctx, double *kernel_ms);
+
 /* Bytes of one rank's compact tile buffer for a slice split over tile_ranks ranks (equal for all ranks). */
 uint64_t pt_compact_bytes(const pt_render_params *params);
 /* Scatters the gathered compact buffers (rank-major) into a row-major image on the device. */

@@ -114,6 +114,10 @@ int ph_renderer_render(ph_renderer *r, const double camera[10], const pt_render_
  * order the flattened nodes first use them: the numbering of ph_scene_flatten's `material` array, NOT that of ph_scene_export's `materials`. */
 int ph_renderer_aov(ph_renderer *r, const double camera[10], const pt_aov_params *params, const pt_aov_buffers *out, double *kernel_ms);
 
+/* Rays of the caller's own (see pt_rays): n x 3 f64 origins and directions in world space, host buffers out, each optional; any_hit = 1 answers `occluded`
+ * only. A renderer spread over a node runs the pass on rank 0's context. `node` and `material` are numbered as for ph_renderer_aov. */
+int ph_renderer_rays(ph_renderer *r, const pt_rays_params *params, const double *origins, const double *directions, const pt_rays_buffers *out, double *kernel_ms);
+
 /* Image::new + Image::render + Image::save with the crate's defaults (env SAMPLES, KD_DEPTH) on an
  * example scene: exercises the whole C++ API the way the reference's main() does. */
 int ph_example_render_to_png(const char *name, const char *assets_dir, int n, uint32_t width, uint32_t height, const char *png_path);

@@ -88,6 +88,20 @@ class PtAovBuffers(C.Structure):
 AOV_BUFFERS = {"depth": (np.float64, 1), "position": (np.float64, 3), "normal": (np.float64, 3), "node": (np.int32, 1), "sub": (np.int32, 1), "material": (np.int32, 1)}
 
 
+class PtRaysParams(C.Structure):
+    _fields_ = [("n", C.c_uint64), ("any_hit", C.c_int32), ("reorder", C.c_int32)]
+
+
+class PtRaysBuffers(C.Structure):
+    _fields_ = [("t", _dp), ("position", _dp), ("normal", _dp), ("node", _ip), ("sub", _ip), ("material", _ip), ("occluded", _u8p)]
+
+
+# pt_rays' outputs in the order of pt_rays_buffers: name -> (numpy dtype, components per ray)
+RAYS_BUFFERS = {"t": (np.float64, 1), "position": (np.float64, 3), "normal": (np.float64, 3), "node": (np.int32, 1), "sub": (np.int32, 1), "material": (np.int32, 1),
+                "occluded": (np.uint8, 1)}
+RAYS_MAX = 1 << 30  # PT_RAYS_MAX
+
+
 class PtStats(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("primary", "shadow", "reflect", "refract", "depth11_skipped", "hits", "n_inner", "n_leaf",
                                           "n_analytic", "n_tri", "n_bbox", "kd_plane_miss", "stack_overflow")] + \
@@ -107,7 +121,7 @@ EXPORTS = ["pt_abi_version", "pt_device_count", "pt_context_create", "pt_context
            "pt_test_math", "pt_test_work_items", "pt_node_create", "pt_node_destroy", "pt_node_last_error", "pt_node_ranks", "pt_node_uses_rccl", "pt_node_context",
            "pt_node_scene_upload", "pt_node_render", "pt_node_upload_background", "pt_node_render_resident", "pt_node_download_image",
            "pt_node_device", "pt_node_frame_begin", "pt_node_frame_end", "pt_node_frames_in_flight", "pt_node_last_frame_host_ms", "pt_node_last_frame_rank_kernel_ms", "pt_test_pow_host", "pt_test_libm_host",
-           "pt_aov", "pt_aov_device", "pt_aov_finish"]
+           "pt_aov", "pt_aov_device", "pt_aov_finish", "pt_rays", "pt_rays_device", "pt_rays_finish"]
 
 
 def header_functions():
@@ -220,6 +234,12 @@ def lib() -> C.CDLL:
         l.pt_aov_device.argtypes = [C.c_void_p, C.POINTER(PtCamera), C.POINTER(PtAovParams), C.POINTER(PtAovBuffers), C.c_void_p]
         l.pt_aov_finish.restype = C.c_int
         l.pt_aov_finish.argtypes = [C.c_void_p, _dp]
+        l.pt_rays.restype = C.c_int
+        l.pt_rays.argtypes = [C.c_void_p, C.POINTER(PtRaysParams), _dp, _dp, C.POINTER(PtRaysBuffers), _dp]
+        l.pt_rays_device.restype = C.c_int
+        l.pt_rays_device.argtypes = [C.c_void_p, C.POINTER(PtRaysParams), C.c_void_p, C.c_void_p, C.POINTER(PtRaysBuffers), C.c_void_p]
+        l.pt_rays_finish.restype = C.c_int
+        l.pt_rays_finish.argtypes = [C.c_void_p, _dp]
         _lib = l
     return _lib
 

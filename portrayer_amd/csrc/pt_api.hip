@@ -16,6 +16,7 @@
 #include "pt_build.h"
 #include "pt_bvh.h"
 #include "pt_aov_inst.h"
+#include "pt_rays_inst.h"
 #include "pt_render_inst.h"
 #include "pt_shade.h"
 
@@ -284,6 +285,17 @@ struct pt_context {
         bool queued = false;            // ... something of it may still be in flight (pt_aov_wait)
         bool closed = false;            // ... and all of it was queued: copy_done is recorded behind it
     } aov;
+    // The ray-query pass (pt_rays / pt_rays_device) likewise, apart from both: stack columns, overflow flag + work queues, events and a pinned page; the device
+    // copies of the host-buffer path's two inputs and seven outputs; and what reorder = 1 sorts with (keys and ray indices before and after, the sort's scratch).
+    struct Rays {
+        PtBuf stack_spill, misc, in[2], out[7], keys[2], vals[2], sort_tmp;
+        hipEvent_t ev0 = nullptr, ev1 = nullptr, copy_done = nullptr;
+        unsigned char* host = nullptr;
+        bool pending = false;           // a pt_rays_device not yet closed by pt_rays_finish
+        hipStream_t stream = nullptr;
+        bool queued = false, closed = false;  // as in Aov
+    } rays;
+    double root_lo[3] = {0.0, 0.0, 0.0}, root_hi[3] = {0.0, 0.0, 0.0};  // the scene tree's root box: union of the flattened nodes' world boxes (reorder = 1 quantises origins inside it)
 };
 #define PT_SLOT_BYTES (256 + sizeof(PtCounters))
 
@@ -356,6 +368,16 @@ extern "C" void pt_context_destroy(pt_context* c) {
     if (c->aov.ev1) hipEventDestroy(c->aov.ev1);
     if (c->aov.copy_done) hipEventDestroy(c->aov.copy_done);
     if (c->aov.host) hipHostFree(c->aov.host);
+    {
+        pt_context::Rays& y = c->rays;
+        if (y.queued) { if (y.closed) hipEventSynchronize(y.copy_done); else hipStreamSynchronize(y.stream); }  // (pt_rays_wait)
+        PtBuf* rb[] = {&y.stack_spill, &y.misc, &y.in[0], &y.in[1], &y.out[0], &y.out[1], &y.out[2], &y.out[3], &y.out[4], &y.out[5], &y.out[6], &y.keys[0], &y.keys[1], &y.vals[0], &y.vals[1], &y.sort_tmp};
+        for (PtBuf* b : rb) if (b->p) hipFree(b->p);
+        if (y.ev0) hipEventDestroy(y.ev0);
+        if (y.ev1) hipEventDestroy(y.ev1);
+        if (y.copy_done) hipEventDestroy(y.copy_done);
+        if (y.host) hipHostFree(y.host);
+    }
     static_assert(pt_context::PT_SLOTS == 2, "the buffer list above names both slots");
     for (auto& sl : c->slot) {
         if (sl.stream) { hipStreamSynchronize(sl.stream); hipStreamDestroy(sl.stream); }
@@ -693,6 +715,9 @@ extern "C" int pt_scene_upload(pt_context* c, const pt_scene* s, int traverse, c
         if (!boxed) pt_transform_box(M, lo, hi, &nb);
         pt_pad_box(&nb, 1e-9);
     }
+    for (int k = 0; k < 3; k++) { c->root_lo[k] = INFINITY; c->root_hi[k] = -INFINITY; }
+    for (uint32_t i = 0; i < n; i++)
+        for (int k = 0; k < 3; k++) { c->root_lo[k] = std::min(c->root_lo[k], node_box[i].lo[k]); c->root_hi[k] = std::max(c->root_hi[k], node_box[i].hi[k]); }
     int tlas_leaf = 1;  // primitive tests (f64, ~200 instructions) cost far more than a node visit: measured best on big-scene
     if (const char* e = getenv("PORTRAYER_TLAS_LEAF")) tlas_leaf = std::max(1, atoi(e));
     const bool tlas_direct = tlas_leaf == 1 && n < (1u << 28);
@@ -1617,6 +1642,166 @@ extern "C" int pt_aov_finish(pt_context* c, double* kernel_ms) {
     int rc = pt_aov_wait(c);
     if (rc) return rc;
     return pt_aov_close(c, kernel_ms);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Ray queries (pt_rays.h)
+// ------------------------------------------------------------------------------------------------
+static hipError_t pt_rays_dispatch(const PtRaysArgs& a, int n_cu, hipStream_t stream, uint32_t* grid, bool launch) {
+    switch (a.r.scene.mode) {
+    case PT_MODE_KD: return pt_rays_launch_mode_2(a, n_cu, stream, grid, launch);
+    case PT_MODE_FLAT_NOMESH: return pt_rays_launch_mode_3(a, n_cu, stream, grid, launch);
+    case PT_MODE_FLAT_KDMESH: return pt_rays_launch_mode_4(a, n_cu, stream, grid, launch);
+    case PT_MODE_HIER: return pt_rays_launch_mode_5(a, n_cu, stream, grid, launch);
+    case PT_MODE_HIER_NOMESH: return pt_rays_launch_mode_6(a, n_cu, stream, grid, launch);
+    case PT_MODE_KD_NOMESH: return pt_rays_launch_mode_7(a, n_cu, stream, grid, launch);
+    case PT_MODE_HIER_MESH: return pt_rays_launch_mode_8(a, n_cu, stream, grid, launch);
+    case PT_MODE_KD_MESH: return pt_rays_launch_mode_9(a, n_cu, stream, grid, launch);
+    default: return pt_rays_launch_mode_1(a, n_cu, stream, grid, launch);
+    }
+}
+
+// Everything that can be refused without a HIP call, in the order the header gives. (pt_fail takes a NULL context.)
+static int pt_rays_check(pt_context* c, const pt_rays_params* p, const double* origins, const double* directions, const pt_rays_buffers* out) {
+    if (!c || !p || !origins || !directions) return pt_fail(c, PT_ERR_ARGUMENT, "pt_rays: NULL context, params, origins or directions");
+    if (!out || !(out->t || out->position || out->normal || out->node || out->sub || out->material || out->occluded))
+        return pt_fail(c, PT_ERR_ARGUMENT, "pt_rays: no output buffer asked for");
+    if (p->n > PT_RAYS_MAX) return pt_fail(c, PT_ERR_ARGUMENT, "pt_rays: more than PT_RAYS_MAX rays in one call");
+    if ((p->any_hit != 0 && p->any_hit != 1) || (p->reorder != 0 && p->reorder != 1)) return pt_fail(c, PT_ERR_ARGUMENT, "pt_rays: any_hit and reorder are 0 or 1");
+    if (p->any_hit && (out->t || out->position || out->normal || out->node || out->sub || out->material))
+        return pt_fail(c, PT_ERR_ARGUMENT, "pt_rays: an occlusion query (any_hit = 1) answers `occluded` only");
+    if (!c->have_scene) return pt_fail(c, PT_ERR_NO_SCENE, "no scene uploaded");
+    if (c->rays.pending) return pt_fail(c, PT_ERR_ARGUMENT, "a pt_rays_device pass is in flight: pt_rays_finish first");
+    return PT_OK;
+}
+
+// Queues the pass on `stream`: queues + overflow flag zeroed; between the pass's two events the keying and the sort (reorder = 1) and the cast kernel; the flag
+// copied to the pinned page behind them. Every pointer is a DEVICE pointer. The LDS stack area is sized as for the primary-visibility pass (pt_aov_common).
+static int pt_rays_common(pt_context* c, const pt_rays_params* p, const double* d_origins, const double* d_directions, const pt_rays_buffers& out, hipStream_t stream) {
+    pt_context::Rays& v = c->rays;
+    if (!v.ev0) {
+        PT_HIP(c, hipEventCreate(&v.ev0));
+        PT_HIP(c, hipEventCreate(&v.ev1));
+        PT_HIP(c, hipEventCreateWithFlags(&v.copy_done, hipEventDisableTiming));
+        PT_HIP(c, hipHostMalloc((void**)&v.host, 256, hipHostMallocDefault));
+    }
+    PtRaysArgs a;
+    memset(&a, 0, sizeof a);
+    a.r.scene = c->view;
+    a.r.n_items = (uint32_t)((p->n + 63u) / 64u);  // (n <= PT_RAYS_MAX = 2^30)
+    a.n = p->n; a.origins = d_origins; a.directions = d_directions; a.any = p->any_hit;
+    a.t = out.t; a.position = out.position; a.normal = out.normal; a.node = out.node; a.sub = out.sub; a.material = out.material; a.occluded = out.occluded;
+    const int mode = a.r.scene.mode;
+    const bool kd_sem = mode == PT_MODE_KD || mode == PT_MODE_KD_NOMESH || mode == PT_MODE_KD_MESH;
+    const size_t block_budget = pt_rays_waves(mode) == 3 ? 52 * 1024 : 39 * 1024;  // 3 x 52 KB or 4 x 39 KB of the CU's 160 KB
+    a.r.stack_lds_cap = pt_stack_lds_cap(a.r.scene, block_budget, 0, kd_sem);
+    a.r.grid_share = 1;
+    uint32_t grid = 0;
+    PT_HIP(c, pt_rays_dispatch(a, c->n_cu, stream, &grid, false));
+    a.r.n_lanes = grid * PT_BLOCK;
+    const size_t stack_column = pt_stack_column(a.r.scene, a.r.stack_lds_cap);
+    int rc;
+    const size_t misc_bytes = 256 + PT_FINE_QUEUES * PT_QUEUE_STRIDE * 4;  // the overflow flag (word 1, where a render has it), the work queues
+    if ((rc = pt_reserve(c, v.stack_spill, (size_t)a.r.n_lanes * stack_column * 4)) || (rc = pt_reserve(c, v.misc, misc_bytes))) return rc;
+    size_t sort_bytes = 0;
+    if (p->reorder) {
+        PT_HIP(c, pt_rays_sort_bytes(p->n, &sort_bytes));
+        if ((rc = pt_reserve(c, v.keys[0], p->n * 8)) || (rc = pt_reserve(c, v.keys[1], p->n * 8)) || (rc = pt_reserve(c, v.vals[0], p->n * 4)) ||
+            (rc = pt_reserve(c, v.vals[1], p->n * 4)) || (rc = pt_reserve(c, v.sort_tmp, sort_bytes)))
+            return rc;
+        a.perm = (const uint32_t*)v.vals[1].p;
+    }
+    a.r.stack_spill = (uint32_t*)v.stack_spill.p;
+    a.r.overflow_flag = (unsigned int*)v.misc.p + 1;
+    a.r.work_queues = (unsigned int*)((char*)v.misc.p + 256);
+    a.r.fine_queues = 16;  // as the primary-visibility pass
+    v.stream = stream; v.queued = true; v.closed = false;  // from here on something of the pass may be in flight on `stream`, whatever fails below
+    PT_HIP(c, hipMemsetAsync(v.misc.p, 0, misc_bytes, stream));
+    PT_HIP(c, hipEventRecord(v.ev0, stream));
+    if (p->reorder)
+        PT_HIP(c, pt_rays_sort(p->n, d_origins, d_directions, c->root_lo, c->root_hi, (unsigned long long*)v.keys[0].p, (unsigned long long*)v.keys[1].p, (uint32_t*)v.vals[0].p,
+                               (uint32_t*)v.vals[1].p, v.sort_tmp.p, sort_bytes, stream));
+    PT_HIP(c, pt_rays_dispatch(a, c->n_cu, stream, &grid, true));
+    PT_HIP(c, hipEventRecord(v.ev1, stream));
+    PT_HIP(c, hipMemcpyAsync(v.host, v.misc.p, 8, hipMemcpyDeviceToHost, stream));
+    PT_HIP(c, hipEventRecord(v.copy_done, stream));
+    v.closed = true;
+    return PT_OK;
+}
+
+// Waits for whatever the last pt_rays_common queued: the event behind its last copy, or - where queuing failed half way - its stream.
+static int pt_rays_wait(pt_context* c) {
+    pt_context::Rays& v = c->rays;
+    if (!v.queued) return PT_OK;
+    v.queued = false;
+    if (v.closed) PT_HIP(c, hipEventSynchronize(v.copy_done));
+    else PT_HIP(c, hipStreamSynchronize(v.stream));
+    return PT_OK;
+}
+
+static int pt_rays_close(pt_context* c, double* kernel_ms) {
+    unsigned int head[2];
+    memcpy(head, c->rays.host, sizeof head);
+    if (kernel_ms) {
+        float ms = 0.f;
+        PT_HIP(c, hipEventElapsedTime(&ms, c->rays.ev0, c->rays.ev1));
+        *kernel_ms = ms;
+    }
+    if (head[1] & 4u) return pt_fail(c, PT_ERR_TRAVERSAL, "a tree walk did not end (watchdog): results invalid");
+    if (head[1]) return pt_fail(c, PT_ERR_TRAVERSAL, "traversal stack overflow");
+    return PT_OK;
+}
+
+extern "C" int pt_rays(pt_context* c, const pt_rays_params* p, const double* origins, const double* directions, const pt_rays_buffers* host_out, double* kernel_ms) {
+    int rc = pt_rays_check(c, p, origins, directions, host_out);
+    if (rc) return rc;
+    if (kernel_ms) *kernel_ms = 0.0;
+    if (p->n == 0) return PT_OK;
+    PT_HIP(c, hipSetDevice(c->device));
+    const size_t n = (size_t)p->n;
+    void* host[7] = {host_out->t, host_out->position, host_out->normal, host_out->node, host_out->sub, host_out->material, host_out->occluded};
+    const size_t elem[7] = {8, 24, 24, 4, 4, 4, 1};  // bytes per ray
+    void* dev[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    if ((rc = pt_reserve(c, c->rays.in[0], n * 24)) || (rc = pt_reserve(c, c->rays.in[1], n * 24))) return rc;
+    for (int k = 0; k < 7; k++) {
+        if (!host[k]) continue;
+        if ((rc = pt_reserve(c, c->rays.out[k], n * elem[k]))) return rc;
+        dev[k] = c->rays.out[k].p;
+    }
+    PT_HIP(c, hipMemcpy(c->rays.in[0].p, origins, n * 24, hipMemcpyHostToDevice));
+    PT_HIP(c, hipMemcpy(c->rays.in[1].p, directions, n * 24, hipMemcpyHostToDevice));
+    pt_rays_buffers d_out;
+    d_out.t = (double*)dev[0]; d_out.position = (double*)dev[1]; d_out.normal = (double*)dev[2];
+    d_out.node = (int32_t*)dev[3]; d_out.sub = (int32_t*)dev[4]; d_out.material = (int32_t*)dev[5]; d_out.occluded = (uint8_t*)dev[6];
+    rc = pt_rays_common(c, p, (const double*)c->rays.in[0].p, (const double*)c->rays.in[1].p, d_out, nullptr);
+    const int rc_wait = pt_rays_wait(c);
+    if (rc || (rc = rc_wait)) return rc;
+    for (int k = 0; k < 7; k++)
+        if (host[k]) PT_HIP(c, hipMemcpy(host[k], dev[k], n * elem[k], hipMemcpyDeviceToHost));
+    return pt_rays_close(c, kernel_ms);
+}
+
+extern "C" int pt_rays_device(pt_context* c, const pt_rays_params* p, const double* d_origins, const double* d_directions, const pt_rays_buffers* device_out, void* hip_stream) {
+    int rc = pt_rays_check(c, p, d_origins, d_directions, device_out);
+    if (rc) return rc;
+    if (p->n == 0) return PT_OK;  // nothing queued, nothing to finish
+    PT_HIP(c, hipSetDevice(c->device));
+    if ((rc = pt_rays_common(c, p, d_origins, d_directions, *device_out, (hipStream_t)hip_stream))) {
+        pt_rays_wait(c);  // what was queued before the failure must not outlive the call: the next pass may reallocate the buffers under it
+        return rc;
+    }
+    c->rays.pending = true;
+    return PT_OK;
+}
+
+extern "C" int pt_rays_finish(pt_context* c, double* kernel_ms) {
+    if (!c) return PT_ERR_ARGUMENT;
+    if (!c->rays.pending) return pt_fail(c, PT_ERR_ARGUMENT, "no pt_rays_device pass in flight");
+    PT_HIP(c, hipSetDevice(c->device));
+    c->rays.pending = false;
+    int rc = pt_rays_wait(c);
+    if (rc) return rc;
+    return pt_rays_close(c, kernel_ms);
 }
 
 // ------------------------------------------------------------------------------------------------

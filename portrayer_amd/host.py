@@ -19,7 +19,7 @@ _dp, _ip, _up, _u64p, _u8p = H._dp, H._ip, H._up, H._u64p, H._u8p
 
 EXPORTS = ["ph_last_error", "ph_scene_create", "ph_example_scene", "ph_scene_destroy", "ph_scene_counts", "ph_scene_export", "ph_scene_export_textures",
            "ph_scene_flatten", "ph_scene_kdtree", "ph_camera", "ph_obj_load", "ph_renderer_create", "ph_renderer_destroy",
-           "ph_renderer_context", "ph_renderer_ranks", "ph_renderer_node", "ph_renderer_prepare_ms", "ph_renderer_render", "ph_renderer_aov", "ph_example_render_to_png", "ph_png_read", "ph_png_write", "ph_image_read", "ph_scene_graph"]
+           "ph_renderer_context", "ph_renderer_ranks", "ph_renderer_node", "ph_renderer_prepare_ms", "ph_renderer_render", "ph_renderer_aov", "ph_renderer_rays", "ph_example_render_to_png", "ph_png_read", "ph_png_write", "ph_image_read", "ph_scene_graph"]
 
 
 class PortrayerHostError(RuntimeError):
@@ -78,6 +78,8 @@ def lib() -> C.CDLL:
         l.ph_renderer_render.argtypes = [vp, _dp, C.POINTER(H.PtRenderParams), _dp, _u8p, _dp, C.POINTER(H.PtStats)]
         l.ph_renderer_aov.restype = C.c_int
         l.ph_renderer_aov.argtypes = [vp, _dp, C.POINTER(H.PtAovParams), C.POINTER(H.PtAovBuffers), _dp]
+        l.ph_renderer_rays.restype = C.c_int
+        l.ph_renderer_rays.argtypes = [vp, C.POINTER(H.PtRaysParams), _dp, _dp, C.POINTER(H.PtRaysBuffers), _dp]
         l.ph_scene_export_textures.restype = C.c_int
         l.ph_scene_export_textures.argtypes = [vp, _u64p, _ip, _ip, _dp, _up, _u64p, _u8p, _dp, _u8p, _dp, _u8p]
         l.ph_example_render_to_png.restype = C.c_int
@@ -314,5 +316,41 @@ class Renderer:
         ms = C.c_double(0.0)
         c = np.ascontiguousarray(cam10, dtype=np.float64)
         _check(lib().ph_renderer_aov(self._h, _p(c, _dp), C.byref(p), C.byref(b), C.byref(ms)), "ph_renderer_aov")
+        out["kernel_ms"] = ms.value
+        return out
+
+    def rays(self, origins, directions, any_hit: bool = False, reorder: bool = False, want=None, into: Optional[dict] = None) -> dict:
+        """Rays of the caller's own (pt_rays): `origins` and `directions` are (n, 3) float64 in world space, directions used as given (t is the ray parameter).
+        Returns the arrays named in `want` - (n,) or (n, 3); t +inf, ids -1, point and normal 0, occluded 0 where nothing is hit - and `kernel_ms`.
+        `want=None` is every buffer. any_hit=True asks only whether anything is in the way: `want` must then be ("occluded",), which is also what None means there. reorder=True lets the
+        device group like rays before tracing; the results are the same bits. `into`: a dict of C-contiguous arrays of the right shape and dtype to write into.
+        Rays with a non-finite component, an all-zero direction or a component beyond 1e18 are not traced and report a miss. `material` is numbered as in aov()."""
+        want = (("occluded",) if any_hit else tuple(H.RAYS_BUFFERS)) if want is None else tuple(want)
+        unknown = [n for n in want if n not in H.RAYS_BUFFERS]
+        if unknown or not want:
+            raise ValueError("want must name some of %s, got %r" % (", ".join(H.RAYS_BUFFERS), want))
+        if any_hit and want != ("occluded",):
+            raise ValueError("any_hit=True answers only 'occluded', got want=%r" % (want,))
+        o, d = np.asarray(origins), np.asarray(directions)
+        if o.ndim != 2 or o.shape[1] != 3 or o.shape != d.shape:
+            raise ValueError("origins and directions must both be (n, 3), got %r and %r" % (o.shape, d.shape))
+        if o.dtype != np.float64 or d.dtype != np.float64:
+            raise ValueError("origins and directions must be float64, got %s and %s" % (o.dtype, d.dtype))
+        n = o.shape[0]
+        if n > H.RAYS_MAX:
+            raise ValueError("at most %d rays per call" % H.RAYS_MAX)
+        o, d = np.ascontiguousarray(o), np.ascontiguousarray(d)
+        out, b = {}, H.PtRaysBuffers()
+        for name in want:
+            dtype, comps = H.RAYS_BUFFERS[name]
+            shape = (n,) if comps == 1 else (n, comps)
+            a = into[name] if into is not None and name in into else np.zeros(shape, dtype=dtype)
+            if a.shape != shape or a.dtype != dtype or not a.flags.c_contiguous:
+                raise ValueError("into[%r] must be a C-contiguous %s array of shape %r" % (name, np.dtype(dtype).name, shape))
+            out[name] = a
+            setattr(b, name, _p(a, _dp if dtype is np.float64 else (_u8p if dtype is np.uint8 else _ip)))
+        p = H.PtRaysParams(n, 1 if any_hit else 0, 1 if reorder else 0)
+        ms = C.c_double(0.0)
+        _check(lib().ph_renderer_rays(self._h, C.byref(p), _p(o, _dp), _p(d, _dp), C.byref(b), C.byref(ms)), "ph_renderer_rays")
         out["kernel_ms"] = ms.value
         return out

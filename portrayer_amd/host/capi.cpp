@@ -531,6 +531,15 @@ extern "C" int ph_renderer_aov(ph_renderer* r, const double camera[10], const pt
     });
 }
 
+extern "C" int ph_renderer_rays(ph_renderer* r, const pt_rays_params* p, const double* origins, const double* directions, const pt_rays_buffers* out, double* kernel_ms) {
+    if (!r || !p || !out) return bad("null argument");
+    if (p->n && (!origins || !directions)) return bad("null argument");
+    return guarded([&]() -> int {
+        r->r->rays(*p, origins, directions, *out, kernel_ms);  // (a renderer spread over a node: rank 0's context, every ray)
+        return PH_OK;
+    });
+}
+
 extern "C" int ph_example_render_to_png(const char* name, const char* assets_dir, int n, uint32_t width, uint32_t height, const char* png_path) {
     if (!name || !png_path) return bad("null argument");
     return guarded([&]() -> int {

@@ -84,6 +84,8 @@ class Renderer {
     void render(const camera::CameraSettings& cam, uint32_t width, uint32_t height, const double* background, bool background_rows,
                 pt_rect slice, uint32_t samples, uint64_t seed, int sample_mode, bool collect_stats, uint8_t* rgb, double* linear,
                 pt_stats* stats);
+    // Rays of the caller's own (pt_rays): host buffers in and out; throws std::runtime_error with the library's message on any error.
+    void rays(const pt_rays_params& params, const double* origins, const double* directions, const pt_rays_buffers& out, double* kernel_ms);
     pt_context* context() const { return ctx_; }  // rank 0's context when the scene is on a node
     pt_node* node() const { return node_; }
     const FlatScene& flat() const { return flat_; }

@@ -773,6 +773,10 @@ void Renderer::render(const camera::CameraSettings& cam, uint32_t width, uint32_
     check(ctx_, pt_render(ctx_, &pc, background, &p, rgb, linear, stats), "pt_render");
 }
 
+void Renderer::rays(const pt_rays_params& params, const double* origins, const double* directions, const pt_rays_buffers& out, double* kernel_ms) {
+    check(ctx_, pt_rays(ctx_, &params, origins, directions, &out, kernel_ms), "pt_rays");
+}
+
 // ------------------------------------------------------------------------------------------------
 // PNG (8-bit RGB / RGBA / grey, non-interlaced)
 // ------------------------------------------------------------------------------------------------

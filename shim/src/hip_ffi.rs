@@ -81,6 +81,11 @@ pub struct PtRenderParams {
 pub struct PtAovBuffers {                  // pt_aov_buffers: each optional (null = not wanted), full image, row-major
     pub depth: *mut f64, pub position: *mut f64, pub normal: *mut f64, pub node: *mut i32, pub sub: *mut i32, pub material: *mut i32,
 }
+#[repr(C)] pub struct PtRaysParams { pub n: u64, pub any_hit: i32, pub reorder: i32 }   // pt_rays_params: any_hit 1 = occlusion query, reorder 1 = the device groups like rays first
+#[repr(C)]
+pub struct PtRaysBuffers {                 // pt_rays_buffers: each optional (null = not wanted), n entries, indexed like the rays
+    pub t: *mut f64, pub position: *mut f64, pub normal: *mut f64, pub node: *mut i32, pub sub: *mut i32, pub material: *mut i32, pub occluded: *mut u8,
+}
 #[repr(C)] #[derive(Default)]
 pub struct PtStats {
     pub primary: u64, pub shadow: u64, pub reflect: u64, pub refract: u64, pub depth11_skipped: u64, pub hits: u64,
@@ -107,6 +112,12 @@ extern "C" {
     pub fn pt_aov_device(ctx: *mut PtContext, camera: *const PtCamera, params: *const PtAovParams, device_out: *const PtAovBuffers,
                          hip_stream: *mut c_void) -> c_int;
     pub fn pt_aov_finish(ctx: *mut PtContext, kernel_ms: *mut f64) -> c_int;
+    // rays of the caller's own: nearest hit (t, position, normal, ids) or occlusion per ray; n x 3 f64 origins and directions in world space
+    pub fn pt_rays(ctx: *mut PtContext, params: *const PtRaysParams, origins: *const f64, directions: *const f64, host_out: *const PtRaysBuffers,
+                   kernel_ms: *mut f64) -> c_int;
+    pub fn pt_rays_device(ctx: *mut PtContext, params: *const PtRaysParams, d_origins: *const f64, d_directions: *const f64, device_out: *const PtRaysBuffers,
+                          hip_stream: *mut c_void) -> c_int;
+    pub fn pt_rays_finish(ctx: *mut PtContext, kernel_ms: *mut f64) -> c_int;
     pub fn pt_context_stream(ctx: *mut PtContext, slot: c_int) -> *mut c_void;
     pub fn pt_context_next_slot(ctx: *const PtContext) -> c_int;
     // one render call over the GPUs of a node (one context per GPU, one RCCL gather)
