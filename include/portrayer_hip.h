@@ -303,6 +303,40 @@ int pt_rays(pt_context *ctx, const pt_rays_params *params, const double *origins
 int pt_rays_device(pt_context *ctx, const pt_rays_params *params, const double *d_origins, const double *d_directions, const pt_rays_buffers *device_out, void *hip_stream);
 int pt_rays_finish(pt_context *ctx, double *kernel_ms);
 
+/* ---- Radiance: rays the CALLER supplies, SHADED (the crate's public Ray::color(scene, background, 0), ray.rs:139-148) - cameras the crate does not have
+ * (fisheye, panoramic, orthographic, thin lens), light probes and environment captures from a point inside the scene, one more gathered bounce for a baker
+ * that casts its own rays, samplers that choose which samples to trace. Rays as in pt_rays: n x 3 f64 origins and directions in world space, a direction used
+ * as given, NOT normalised. rgb[i] (n x 3 f64) carries the bits of Ray::color for ray i against ITS background colour, in the traversal the scene was uploaded
+ * with: everything pt_render shades - Blinn-Phong with shadow rays, area lights, glossy reflection, reflection and refraction to depth 10, textures and normal
+ * maps - as one linear sample: no mean, no gamma, no clamp. Accumulation is the caller's.
+ *   background: 3 doubles (background_per_ray = 0), or n x 3 indexed like the rays (1).
+ *   random draws (area lights, glossy reflection) of ray i come from the counter-based generator's stream (seed, stream_base + i, sample), draws 2, 3, ...: the
+ *     numbering a render uses behind its two jitter draws. With stream_base = 0 and the rays a full image's pixel centres in pixel order the result is pt_render's
+ *     `linear` at samples = 1, PT_SAMPLE_CENTRE and the same seed (background per pixel passed per ray); sample = s gives sample s of that pixel.
+ *   The stream belongs to the ray's INDEX, not to where it runs: results are bit-identical with reorder 0 and 1 (as in pt_rays), and a sub-batch [k, k + m)
+ *     submitted with stream_base = k equals that slice of the whole batch.
+ *   Rays that are NOT TRACED (pt_rays' rule: a non-finite component, an all-zero direction, a component beyond 1e18) report their background colour and disturb
+ *     no other ray.
+ * Errors, before the first HIP call: PT_ERR_ARGUMENT (NULL context / params / origins / directions / background / rgb; n > PT_RAYS_MAX; reorder or
+ * background_per_ray other than 0 or 1), PT_ERR_NO_SCENE. n = 0 is PT_OK: nothing is launched or written. During the pass: PT_ERR_TRAVERSAL as for a render.
+ * The pass has work buffers of its own (stack columns, recursion frames, queues, sort keys): renders in flight on the context's two slots, a pt_aov_device
+ * pass and a pt_rays_device pass are not disturbed. kernel_ms covers keying and sort (reorder = 1) and the shading kernel. */
+typedef struct {
+    uint64_t n;                  /* rays, <= PT_RAYS_MAX                                                        */
+    int32_t  reorder;            /* as pt_rays_params.reorder                                                   */
+    int32_t  background_per_ray; /* 0: background is 3 doubles; 1: n x 3, indexed like the rays                 */
+    uint64_t seed;               /* key of the counter-based generator, as pt_render_params.seed                */
+    uint64_t stream_base;        /* ray i draws from stream (seed, stream_base + i, sample), draws 2, 3, ...    */
+    uint32_t sample;
+} pt_radiance_params;
+/* Host buffers, synchronous: uploads rays and background, copies rgb back. kernel_ms (optional): device time of the pass (HIP events). */
+int pt_radiance(pt_context *ctx, const pt_radiance_params *params, const double *origins, const double *directions, const double *background, double *rgb, double *kernel_ms);
+/* The same with every array in DEVICE memory, queued on `hip_stream` (a hipStream_t, or NULL for the default stream) without synchronising the host.
+ * pt_radiance_finish waits for that pass and returns what it found (PT_ERR_TRAVERSAL, else PT_OK) and, optionally, its device time; one pass may be in flight
+ * per context: a second pt_radiance_device / pt_radiance before pt_radiance_finish is refused with PT_ERR_ARGUMENT. (n = 0 queues nothing and is not in flight.) */
+int pt_radiance_device(pt_context *ctx, const pt_radiance_params *params, const double *d_origins, const double *d_directions, const double *d_background, double *d_rgb, void *hip_stream);
+int pt_radiance_finish(pt_context *ctx, double *kernel_ms);
+
 /* Bytes of one rank's compact tile buffer for a slice split over tile_ranks ranks (equal for all ranks). */
 uint64_t pt_compact_bytes(const pt_render_params *params);
 /* Scatters the gathered compact buffers (rank-major) into a row-major image on the device. */

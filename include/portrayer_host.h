@@ -118,6 +118,11 @@ int ph_renderer_aov(ph_renderer *r, const double camera[10], const pt_aov_params
  * only. A renderer spread over a node runs the pass on rank 0's context. `node` and `material` are numbered as for ph_renderer_aov. */
 int ph_renderer_rays(ph_renderer *r, const pt_rays_params *params, const double *origins, const double *directions, const pt_rays_buffers *out, double *kernel_ms);
 
+/* Radiance along rays of the caller's own (see pt_radiance): n x 3 f64 origins and directions in world space, `background` 3 doubles or n x 3
+ * (params->background_per_ray), rgb n x 3 f64 out: one linear sample of Ray::color per ray. A renderer spread over a node runs the pass on rank 0's context. */
+int ph_renderer_radiance(ph_renderer *r, const pt_radiance_params *params, const double *origins, const double *directions, const double *background, double *rgb,
+                         double *kernel_ms);
+
 /* Image::new + Image::render + Image::save with the crate's defaults (env SAMPLES, KD_DEPTH) on an
  * example scene: exercises the whole C++ API the way the reference's main() does. */
 int ph_example_render_to_png(const char *name, const char *assets_dir, int n, uint32_t width, uint32_t height, const char *png_path);

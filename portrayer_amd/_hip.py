@@ -102,6 +102,10 @@ RAYS_BUFFERS = {"t": (np.float64, 1), "position": (np.float64, 3), "normal": (np
 RAYS_MAX = 1 << 30  # PT_RAYS_MAX
 
 
+class PtRadianceParams(C.Structure):
+    _fields_ = [("n", C.c_uint64), ("reorder", C.c_int32), ("background_per_ray", C.c_int32), ("seed", C.c_uint64), ("stream_base", C.c_uint64), ("sample", C.c_uint32)]
+
+
 class PtStats(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("primary", "shadow", "reflect", "refract", "depth11_skipped", "hits", "n_inner", "n_leaf",
                                           "n_analytic", "n_tri", "n_bbox", "kd_plane_miss", "stack_overflow")] + \
@@ -121,7 +125,8 @@ EXPORTS = ["pt_abi_version", "pt_device_count", "pt_context_create", "pt_context
            "pt_test_math", "pt_test_work_items", "pt_node_create", "pt_node_destroy", "pt_node_last_error", "pt_node_ranks", "pt_node_uses_rccl", "pt_node_context",
            "pt_node_scene_upload", "pt_node_render", "pt_node_upload_background", "pt_node_render_resident", "pt_node_download_image",
            "pt_node_device", "pt_node_frame_begin", "pt_node_frame_end", "pt_node_frames_in_flight", "pt_node_last_frame_host_ms", "pt_node_last_frame_rank_kernel_ms", "pt_test_pow_host", "pt_test_libm_host",
-           "pt_aov", "pt_aov_device", "pt_aov_finish", "pt_rays", "pt_rays_device", "pt_rays_finish"]
+           "pt_aov", "pt_aov_device", "pt_aov_finish", "pt_rays", "pt_rays_device", "pt_rays_finish",
+           "pt_radiance", "pt_radiance_device", "pt_radiance_finish"]
 
 
 def header_functions():
@@ -240,6 +245,12 @@ def lib() -> C.CDLL:
         l.pt_rays_device.argtypes = [C.c_void_p, C.POINTER(PtRaysParams), C.c_void_p, C.c_void_p, C.POINTER(PtRaysBuffers), C.c_void_p]
         l.pt_rays_finish.restype = C.c_int
         l.pt_rays_finish.argtypes = [C.c_void_p, _dp]
+        l.pt_radiance.restype = C.c_int
+        l.pt_radiance.argtypes = [C.c_void_p, C.POINTER(PtRadianceParams), _dp, _dp, _dp, _dp, _dp]
+        l.pt_radiance_device.restype = C.c_int
+        l.pt_radiance_device.argtypes = [C.c_void_p, C.POINTER(PtRadianceParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        l.pt_radiance_finish.restype = C.c_int
+        l.pt_radiance_finish.argtypes = [C.c_void_p, _dp]
         _lib = l
     return _lib
 

@@ -17,6 +17,7 @@
 #include "pt_bvh.h"
 #include "pt_aov_inst.h"
 #include "pt_rays_inst.h"
+#include "pt_radiance_inst.h"
 #include "pt_render_inst.h"
 #include "pt_shade.h"
 
@@ -295,6 +296,16 @@ struct pt_context {
         hipStream_t stream = nullptr;
         bool queued = false, closed = false;  // as in Aov
     } rays;
+    // The radiance pass (pt_radiance / pt_radiance_device) likewise, apart from all three: stack columns, the lanes' recursion-frame lines, overflow flag + work
+    // queues, events and a pinned page; the device copies of the host-buffer path's three inputs and its output; what reorder = 1 sorts with.
+    struct Radiance {
+        PtBuf stack_spill, spill, misc, in[3], out, keys[2], vals[2], sort_tmp;
+        hipEvent_t ev0 = nullptr, ev1 = nullptr, copy_done = nullptr;
+        unsigned char* host = nullptr;
+        bool pending = false;           // a pt_radiance_device not yet closed by pt_radiance_finish
+        hipStream_t stream = nullptr;
+        bool queued = false, closed = false;  // as in Aov
+    } radiance;
     double root_lo[3] = {0.0, 0.0, 0.0}, root_hi[3] = {0.0, 0.0, 0.0};  // the scene tree's root box: union of the flattened nodes' world boxes (reorder = 1 quantises origins inside it)
 };
 #define PT_SLOT_BYTES (256 + sizeof(PtCounters))
@@ -372,6 +383,16 @@ extern "C" void pt_context_destroy(pt_context* c) {
         pt_context::Rays& y = c->rays;
         if (y.queued) { if (y.closed) hipEventSynchronize(y.copy_done); else hipStreamSynchronize(y.stream); }  // (pt_rays_wait)
         PtBuf* rb[] = {&y.stack_spill, &y.misc, &y.in[0], &y.in[1], &y.out[0], &y.out[1], &y.out[2], &y.out[3], &y.out[4], &y.out[5], &y.out[6], &y.keys[0], &y.keys[1], &y.vals[0], &y.vals[1], &y.sort_tmp};
+        for (PtBuf* b : rb) if (b->p) hipFree(b->p);
+        if (y.ev0) hipEventDestroy(y.ev0);
+        if (y.ev1) hipEventDestroy(y.ev1);
+        if (y.copy_done) hipEventDestroy(y.copy_done);
+        if (y.host) hipHostFree(y.host);
+    }
+    {
+        pt_context::Radiance& y = c->radiance;
+        if (y.queued) { if (y.closed) hipEventSynchronize(y.copy_done); else hipStreamSynchronize(y.stream); }  // (pt_radiance_wait)
+        PtBuf* rb[] = {&y.stack_spill, &y.spill, &y.misc, &y.in[0], &y.in[1], &y.in[2], &y.out, &y.keys[0], &y.keys[1], &y.vals[0], &y.vals[1], &y.sort_tmp};
         for (PtBuf* b : rb) if (b->p) hipFree(b->p);
         if (y.ev0) hipEventDestroy(y.ev0);
         if (y.ev1) hipEventDestroy(y.ev1);
@@ -1802,6 +1823,161 @@ extern "C" int pt_rays_finish(pt_context* c, double* kernel_ms) {
     int rc = pt_rays_wait(c);
     if (rc) return rc;
     return pt_rays_close(c, kernel_ms);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Radiance along the caller's rays (pt_radiance.h)
+// ------------------------------------------------------------------------------------------------
+static hipError_t pt_radiance_dispatch(const PtRadianceArgs& a, bool tex, bool park, int n_cu, hipStream_t stream, uint32_t* grid, bool launch) {
+    switch (a.r.scene.mode) {
+    case PT_MODE_KD: return pt_radiance_launch_mode_2(a, tex, park, n_cu, stream, grid, launch);
+    case PT_MODE_FLAT_NOMESH: return pt_radiance_launch_mode_3(a, tex, park, n_cu, stream, grid, launch);
+    case PT_MODE_FLAT_KDMESH: return pt_radiance_launch_mode_4(a, tex, park, n_cu, stream, grid, launch);
+    case PT_MODE_HIER: return pt_radiance_launch_mode_5(a, tex, park, n_cu, stream, grid, launch);
+    case PT_MODE_HIER_NOMESH: return pt_radiance_launch_mode_6(a, tex, park, n_cu, stream, grid, launch);
+    case PT_MODE_KD_NOMESH: return pt_radiance_launch_mode_7(a, tex, park, n_cu, stream, grid, launch);
+    case PT_MODE_HIER_MESH: return pt_radiance_launch_mode_8(a, tex, park, n_cu, stream, grid, launch);
+    case PT_MODE_KD_MESH: return pt_radiance_launch_mode_9(a, tex, park, n_cu, stream, grid, launch);
+    default: return pt_radiance_launch_mode_1(a, tex, park, n_cu, stream, grid, launch);
+    }
+}
+
+// Everything that can be refused without a HIP call, in the order the header gives. (pt_fail takes a NULL context.)
+static int pt_radiance_check(pt_context* c, const pt_radiance_params* p, const double* origins, const double* directions, const double* background, const double* rgb) {
+    if (!c || !p || !origins || !directions || !background || !rgb) return pt_fail(c, PT_ERR_ARGUMENT, "pt_radiance: NULL context, params, origins, directions, background or rgb");
+    if (p->n > PT_RAYS_MAX) return pt_fail(c, PT_ERR_ARGUMENT, "pt_radiance: more than PT_RAYS_MAX rays in one call");
+    if ((p->reorder != 0 && p->reorder != 1) || (p->background_per_ray != 0 && p->background_per_ray != 1))
+        return pt_fail(c, PT_ERR_ARGUMENT, "pt_radiance: reorder and background_per_ray are 0 or 1");
+    if (!c->have_scene) return pt_fail(c, PT_ERR_NO_SCENE, "no scene uploaded");
+    if (c->radiance.pending) return pt_fail(c, PT_ERR_ARGUMENT, "a pt_radiance_device pass is in flight: pt_radiance_finish first");
+    return PT_OK;
+}
+
+// Queues the pass on `stream`: queues + overflow flag zeroed; between the pass's two events the keying and the sort (reorder = 1) and the shading kernel; the flag
+// copied to the pinned page behind them. Every pointer is a DEVICE pointer. LDS per block as a render's interpreter kernel has it (pt_render_common): three blocks
+// per CU, the stack area beside the hit frame and - scenes whose hits spawn rays - one parked frame per lane.
+static int pt_radiance_common(pt_context* c, const pt_radiance_params* p, const double* d_origins, const double* d_directions, const double* d_background, double* d_rgb, hipStream_t stream) {
+    pt_context::Radiance& v = c->radiance;
+    if (!v.ev0) {
+        PT_HIP(c, hipEventCreate(&v.ev0));
+        PT_HIP(c, hipEventCreate(&v.ev1));
+        PT_HIP(c, hipEventCreateWithFlags(&v.copy_done, hipEventDisableTiming));
+        PT_HIP(c, hipHostMalloc((void**)&v.host, 256, hipHostMallocDefault));
+    }
+    PtRadianceArgs a;
+    memset(&a, 0, sizeof a);  // (no occluder table, no counters, no work counter: null)
+    a.r.scene = c->view;
+    a.r.seed = p->seed;
+    a.r.n_items = (uint32_t)((p->n + 63u) / 64u);  // (n <= PT_RAYS_MAX = 2^30)
+    a.n = p->n; a.origins = d_origins; a.directions = d_directions; a.background = d_background; a.bg_stride = p->background_per_ray ? 3u : 0u;
+    a.sample = p->sample; a.stream_base = p->stream_base; a.rgb = d_rgb;
+    const int mode = a.r.scene.mode;
+    const bool kd_sem = mode == PT_MODE_KD || mode == PT_MODE_KD_NOMESH || mode == PT_MODE_KD_MESH;
+    const bool tex = a.r.scene.mat_maps != nullptr;
+    bool park = c->spawns;  // scenes whose hits spawn rays: the youngest parked frame of a lane in LDS, as a render has it
+    if (const char* e = getenv("PORTRAYER_PARK")) park = park && atoi(e) > 0;  // 0: every parked frame in HBM (tests, measurements), as for a render
+    a.r.park_slots = park ? 1 : 0;
+    const size_t frame_bytes = (size_t)(PT_LDS_FRAME_F64 + a.r.park_slots * PT_PARK_F64) * PT_BLOCK * 8;
+    a.r.stack_lds_cap = pt_stack_lds_cap(a.r.scene, 52 * 1024, frame_bytes, kd_sem);  // 3 x 52 KB of the CU's 160 KB (pt_radiance_waves)
+    a.r.grid_share = 1;
+    uint32_t grid = 0;
+    PT_HIP(c, pt_radiance_dispatch(a, tex, park, c->n_cu, stream, &grid, false));
+    a.r.n_lanes = grid * PT_BLOCK;
+    const size_t stack_column = pt_stack_column(a.r.scene, a.r.stack_lds_cap);
+    const size_t spill_bytes = c->needs_spill ? (size_t)a.r.n_lanes * PT_SPILL_DEPTHS * PT_SPILL_STRIDE * sizeof(double) : 16;
+    int rc;
+    const size_t misc_bytes = 256 + PT_FINE_QUEUES * PT_QUEUE_STRIDE * 4;  // the overflow flag (word 1, where a render has it), the work queues
+    if ((rc = pt_reserve(c, v.stack_spill, (size_t)a.r.n_lanes * stack_column * 4)) || (rc = pt_reserve(c, v.spill, spill_bytes)) || (rc = pt_reserve(c, v.misc, misc_bytes))) return rc;
+    size_t sort_bytes = 0;
+    if (p->reorder) {
+        PT_HIP(c, pt_rays_sort_bytes(p->n, &sort_bytes));
+        if ((rc = pt_reserve(c, v.keys[0], p->n * 8)) || (rc = pt_reserve(c, v.keys[1], p->n * 8)) || (rc = pt_reserve(c, v.vals[0], p->n * 4)) ||
+            (rc = pt_reserve(c, v.vals[1], p->n * 4)) || (rc = pt_reserve(c, v.sort_tmp, sort_bytes)))
+            return rc;
+        a.perm = (const uint32_t*)v.vals[1].p;
+    }
+    a.r.stack_spill = (uint32_t*)v.stack_spill.p;
+    a.r.spill = (double*)v.spill.p;
+    a.r.overflow_flag = (unsigned int*)v.misc.p + 1;
+    a.r.work_queues = (unsigned int*)((char*)v.misc.p + 256);
+    a.r.fine_queues = 16;  // one item at a time, as every pass whose items differ in cost by orders of magnitude
+    v.stream = stream; v.queued = true; v.closed = false;  // from here on something of the pass may be in flight on `stream`, whatever fails below
+    PT_HIP(c, hipMemsetAsync(v.misc.p, 0, misc_bytes, stream));
+    PT_HIP(c, hipEventRecord(v.ev0, stream));
+    if (p->reorder)
+        PT_HIP(c, pt_rays_sort(p->n, d_origins, d_directions, c->root_lo, c->root_hi, (unsigned long long*)v.keys[0].p, (unsigned long long*)v.keys[1].p, (uint32_t*)v.vals[0].p,
+                               (uint32_t*)v.vals[1].p, v.sort_tmp.p, sort_bytes, stream));
+    PT_HIP(c, pt_radiance_dispatch(a, tex, park, c->n_cu, stream, &grid, true));
+    PT_HIP(c, hipEventRecord(v.ev1, stream));
+    PT_HIP(c, hipMemcpyAsync(v.host, v.misc.p, 8, hipMemcpyDeviceToHost, stream));
+    PT_HIP(c, hipEventRecord(v.copy_done, stream));
+    v.closed = true;
+    return PT_OK;
+}
+
+// Waits for whatever the last pt_radiance_common queued: the event behind its last copy, or - where queuing failed half way - its stream.
+static int pt_radiance_wait(pt_context* c) {
+    pt_context::Radiance& v = c->radiance;
+    if (!v.queued) return PT_OK;
+    v.queued = false;
+    if (v.closed) PT_HIP(c, hipEventSynchronize(v.copy_done));
+    else PT_HIP(c, hipStreamSynchronize(v.stream));
+    return PT_OK;
+}
+
+static int pt_radiance_close(pt_context* c, double* kernel_ms) {
+    unsigned int head[2];
+    memcpy(head, c->radiance.host, sizeof head);
+    if (kernel_ms) {
+        float ms = 0.f;
+        PT_HIP(c, hipEventElapsedTime(&ms, c->radiance.ev0, c->radiance.ev1));
+        *kernel_ms = ms;
+    }
+    if (head[1] & 4u) return pt_fail(c, PT_ERR_TRAVERSAL, "a tree walk did not end (watchdog): results invalid");
+    if (head[1]) return pt_fail(c, PT_ERR_TRAVERSAL, "traversal stack overflow");
+    return PT_OK;
+}
+
+extern "C" int pt_radiance(pt_context* c, const pt_radiance_params* p, const double* origins, const double* directions, const double* background, double* rgb, double* kernel_ms) {
+    int rc = pt_radiance_check(c, p, origins, directions, background, rgb);
+    if (rc) return rc;
+    if (kernel_ms) *kernel_ms = 0.0;
+    if (p->n == 0) return PT_OK;
+    PT_HIP(c, hipSetDevice(c->device));
+    pt_context::Radiance& v = c->radiance;
+    const size_t n = (size_t)p->n, bg_bytes = p->background_per_ray ? n * 24 : 24;
+    if ((rc = pt_reserve(c, v.in[0], n * 24)) || (rc = pt_reserve(c, v.in[1], n * 24)) || (rc = pt_reserve(c, v.in[2], bg_bytes)) || (rc = pt_reserve(c, v.out, n * 24))) return rc;
+    PT_HIP(c, hipMemcpy(v.in[0].p, origins, n * 24, hipMemcpyHostToDevice));
+    PT_HIP(c, hipMemcpy(v.in[1].p, directions, n * 24, hipMemcpyHostToDevice));
+    PT_HIP(c, hipMemcpy(v.in[2].p, background, bg_bytes, hipMemcpyHostToDevice));
+    rc = pt_radiance_common(c, p, (const double*)v.in[0].p, (const double*)v.in[1].p, (const double*)v.in[2].p, (double*)v.out.p, nullptr);
+    const int rc_wait = pt_radiance_wait(c);
+    if (rc || (rc = rc_wait)) return rc;
+    PT_HIP(c, hipMemcpy(rgb, v.out.p, n * 24, hipMemcpyDeviceToHost));
+    return pt_radiance_close(c, kernel_ms);
+}
+
+extern "C" int pt_radiance_device(pt_context* c, const pt_radiance_params* p, const double* d_origins, const double* d_directions, const double* d_background, double* d_rgb, void* hip_stream) {
+    int rc = pt_radiance_check(c, p, d_origins, d_directions, d_background, d_rgb);
+    if (rc) return rc;
+    if (p->n == 0) return PT_OK;  // nothing queued, nothing to finish
+    PT_HIP(c, hipSetDevice(c->device));
+    if ((rc = pt_radiance_common(c, p, d_origins, d_directions, d_background, d_rgb, (hipStream_t)hip_stream))) {
+        pt_radiance_wait(c);  // what was queued before the failure must not outlive the call: the next pass may reallocate the buffers under it
+        return rc;
+    }
+    c->radiance.pending = true;
+    return PT_OK;
+}
+
+extern "C" int pt_radiance_finish(pt_context* c, double* kernel_ms) {
+    if (!c) return PT_ERR_ARGUMENT;
+    if (!c->radiance.pending) return pt_fail(c, PT_ERR_ARGUMENT, "no pt_radiance_device pass in flight");
+    PT_HIP(c, hipSetDevice(c->device));
+    c->radiance.pending = false;
+    int rc = pt_radiance_wait(c);
+    if (rc) return rc;
+    return pt_radiance_close(c, kernel_ms);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -19,7 +19,7 @@ _dp, _ip, _up, _u64p, _u8p = H._dp, H._ip, H._up, H._u64p, H._u8p
 
 EXPORTS = ["ph_last_error", "ph_scene_create", "ph_example_scene", "ph_scene_destroy", "ph_scene_counts", "ph_scene_export", "ph_scene_export_textures",
            "ph_scene_flatten", "ph_scene_kdtree", "ph_camera", "ph_obj_load", "ph_renderer_create", "ph_renderer_destroy",
-           "ph_renderer_context", "ph_renderer_ranks", "ph_renderer_node", "ph_renderer_prepare_ms", "ph_renderer_render", "ph_renderer_aov", "ph_renderer_rays", "ph_example_render_to_png", "ph_png_read", "ph_png_write", "ph_image_read", "ph_scene_graph"]
+           "ph_renderer_context", "ph_renderer_ranks", "ph_renderer_node", "ph_renderer_prepare_ms", "ph_renderer_render", "ph_renderer_aov", "ph_renderer_rays", "ph_renderer_radiance", "ph_example_render_to_png", "ph_png_read", "ph_png_write", "ph_image_read", "ph_scene_graph"]
 
 
 class PortrayerHostError(RuntimeError):
@@ -80,6 +80,8 @@ def lib() -> C.CDLL:
         l.ph_renderer_aov.argtypes = [vp, _dp, C.POINTER(H.PtAovParams), C.POINTER(H.PtAovBuffers), _dp]
         l.ph_renderer_rays.restype = C.c_int
         l.ph_renderer_rays.argtypes = [vp, C.POINTER(H.PtRaysParams), _dp, _dp, C.POINTER(H.PtRaysBuffers), _dp]
+        l.ph_renderer_radiance.restype = C.c_int
+        l.ph_renderer_radiance.argtypes = [vp, C.POINTER(H.PtRadianceParams), _dp, _dp, _dp, _dp, _dp]
         l.ph_scene_export_textures.restype = C.c_int
         l.ph_scene_export_textures.argtypes = [vp, _u64p, _ip, _ip, _dp, _up, _u64p, _u8p, _dp, _u8p, _dp, _u8p]
         l.ph_example_render_to_png.restype = C.c_int
@@ -354,3 +356,38 @@ class Renderer:
         _check(lib().ph_renderer_rays(self._h, C.byref(p), _p(o, _dp), _p(d, _dp), C.byref(b), C.byref(ms)), "ph_renderer_rays")
         out["kernel_ms"] = ms.value
         return out
+
+    def radiance(self, origins, directions, background=(0.0, 0.0, 0.0), seed: int = 0, sample: int = 0, stream_base: int = 0, reorder: bool = False,
+                 into: Optional[np.ndarray] = None) -> dict:
+        """Radiance along rays of the caller's own (pt_radiance): `origins` and `directions` are (n, 3) float64 in world space, directions used as given.
+        Returns {"rgb": (n, 3) float64, "kernel_ms": float}: per ray one linear sample of what render() shades (shadow rays, area lights, glossy reflection,
+        reflection and refraction, textures), no mean, no gamma, no clamp. `background` is one colour (3,) or one per ray (n, 3). Ray i draws its random
+        numbers from the stream (seed, stream_base + i, sample): the result depends on neither the order of the batch (reorder=True lets the device group like
+        rays first; same bits) nor on how it is cut (a slice [k, k + m) with stream_base=k gives that slice of the whole). With the pixel-centre rays of a
+        full image in pixel order it equals render()'s `linear` at samples=1, SAMPLE_CENTRE and the same seed. Rays with a non-finite component, an all-zero
+        direction or a component beyond 1e18 are not traced and report their background colour. `into`: a C-contiguous (n, 3) float64 array to write into."""
+        o, d = np.asarray(origins), np.asarray(directions)
+        if o.ndim != 2 or o.shape[1] != 3 or o.shape != d.shape:
+            raise ValueError("origins and directions must both be (n, 3), got %r and %r" % (o.shape, d.shape))
+        if o.dtype != np.float64 or d.dtype != np.float64:
+            raise ValueError("origins and directions must be float64, got %s and %s" % (o.dtype, d.dtype))
+        n = o.shape[0]
+        if n > H.RAYS_MAX:
+            raise ValueError("at most %d rays per call" % H.RAYS_MAX)
+        bg = np.ascontiguousarray(background, dtype=np.float64)
+        if bg.shape != (3,) and bg.shape != (n, 3):
+            raise ValueError("background must be (3,) or (n, 3) = %r, got %r" % ((n, 3), bg.shape))
+        per_ray = 1 if bg.ndim == 2 else 0
+        for name, v, top in (("seed", seed, 1 << 64), ("stream_base", stream_base, 1 << 64), ("sample", sample, 1 << 32)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) < top:
+                raise ValueError("%s must be an integer in [0, 2^%d), got %r" % (name, top.bit_length() - 1, v))
+        if not isinstance(reorder, (bool, np.bool_)) and not (isinstance(reorder, (int, np.integer)) and int(reorder) in (0, 1)):
+            raise ValueError("reorder is a flag (False or True), got %r" % (reorder,))
+        rgb = into if into is not None else np.zeros((n, 3), dtype=np.float64)
+        if not isinstance(rgb, np.ndarray) or rgb.shape != (n, 3) or rgb.dtype != np.float64 or not rgb.flags.c_contiguous:
+            raise ValueError("into must be a C-contiguous float64 array of shape %r" % ((n, 3),))
+        o, d = np.ascontiguousarray(o), np.ascontiguousarray(d)
+        p = H.PtRadianceParams(n, 1 if reorder else 0, per_ray, int(seed), int(stream_base), int(sample))
+        ms = C.c_double(0.0)
+        _check(lib().ph_renderer_radiance(self._h, C.byref(p), _p(o, _dp), _p(d, _dp), _p(bg, _dp), _p(rgb, _dp), C.byref(ms)), "ph_renderer_radiance")
+        return {"rgb": rgb, "kernel_ms": ms.value}

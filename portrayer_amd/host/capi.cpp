@@ -540,6 +540,19 @@ extern "C" int ph_renderer_rays(ph_renderer* r, const pt_rays_params* p, const d
     });
 }
 
+extern "C" int ph_renderer_radiance(ph_renderer* r, const pt_radiance_params* p, const double* origins, const double* directions, const double* background, double* rgb,
+                                    double* kernel_ms) {
+    if (!r || !p || !background) return bad("null argument");
+    if (p->n && (!origins || !directions || !rgb)) return bad("null argument");
+    if ((p->reorder != 0 && p->reorder != 1) || (p->background_per_ray != 0 && p->background_per_ray != 1)) return bad("reorder and background_per_ray are 0 or 1");
+    if (p->n > PT_RAYS_MAX) return bad("more than PT_RAYS_MAX rays in one call");
+    if (p->n == 0) { if (kernel_ms) *kernel_ms = 0.0; return PH_OK; }  // nothing to shade, nothing written (the flags are checked all the same, as pt_radiance does)
+    return guarded([&]() -> int {
+        r->r->radiance(*p, origins, directions, background, rgb, kernel_ms);  // (a renderer spread over a node: rank 0's context, every ray)
+        return PH_OK;
+    });
+}
+
 extern "C" int ph_example_render_to_png(const char* name, const char* assets_dir, int n, uint32_t width, uint32_t height, const char* png_path) {
     if (!name || !png_path) return bad("null argument");
     return guarded([&]() -> int {

@@ -86,6 +86,8 @@ class Renderer {
                 pt_stats* stats);
     // Rays of the caller's own (pt_rays): host buffers in and out; throws std::runtime_error with the library's message on any error.
     void rays(const pt_rays_params& params, const double* origins, const double* directions, const pt_rays_buffers& out, double* kernel_ms);
+    // Radiance along rays of the caller's own (pt_radiance): host buffers in and out; throws likewise.
+    void radiance(const pt_radiance_params& params, const double* origins, const double* directions, const double* background, double* rgb, double* kernel_ms);
     pt_context* context() const { return ctx_; }  // rank 0's context when the scene is on a node
     pt_node* node() const { return node_; }
     const FlatScene& flat() const { return flat_; }

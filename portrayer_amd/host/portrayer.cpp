@@ -777,6 +777,10 @@ void Renderer::rays(const pt_rays_params& params, const double* origins, const d
     check(ctx_, pt_rays(ctx_, &params, origins, directions, &out, kernel_ms), "pt_rays");
 }
 
+void Renderer::radiance(const pt_radiance_params& params, const double* origins, const double* directions, const double* background, double* rgb, double* kernel_ms) {
+    check(ctx_, pt_radiance(ctx_, &params, origins, directions, background, rgb, kernel_ms), "pt_radiance");
+}
+
 // ------------------------------------------------------------------------------------------------
 // PNG (8-bit RGB / RGBA / grey, non-interlaced)
 // ------------------------------------------------------------------------------------------------

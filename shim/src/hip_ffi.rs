@@ -83,6 +83,10 @@ pub struct PtAovBuffers {                  // pt_aov_buffers: each optional (nul
 }
 #[repr(C)] pub struct PtRaysParams { pub n: u64, pub any_hit: i32, pub reorder: i32 }   // pt_rays_params: any_hit 1 = occlusion query, reorder 1 = the device groups like rays first
 #[repr(C)]
+pub struct PtRadianceParams {              // pt_radiance_params: ray i draws from the generator's stream (seed, stream_base + i, sample), draws 2, 3, ...
+    pub n: u64, pub reorder: i32, pub background_per_ray: i32, pub seed: u64, pub stream_base: u64, pub sample: u32,
+}
+#[repr(C)]
 pub struct PtRaysBuffers {                 // pt_rays_buffers: each optional (null = not wanted), n entries, indexed like the rays
     pub t: *mut f64, pub position: *mut f64, pub normal: *mut f64, pub node: *mut i32, pub sub: *mut i32, pub material: *mut i32, pub occluded: *mut u8,
 }
@@ -118,6 +122,12 @@ extern "C" {
     pub fn pt_rays_device(ctx: *mut PtContext, params: *const PtRaysParams, d_origins: *const f64, d_directions: *const f64, device_out: *const PtRaysBuffers,
                           hip_stream: *mut c_void) -> c_int;
     pub fn pt_rays_finish(ctx: *mut PtContext, kernel_ms: *mut f64) -> c_int;
+    // radiance along rays of the caller's own (Ray::color as a batch): background 3 f64 or n x 3 (background_per_ray), rgb n x 3 f64, one linear sample per ray
+    pub fn pt_radiance(ctx: *mut PtContext, params: *const PtRadianceParams, origins: *const f64, directions: *const f64, background: *const f64, rgb: *mut f64,
+                       kernel_ms: *mut f64) -> c_int;
+    pub fn pt_radiance_device(ctx: *mut PtContext, params: *const PtRadianceParams, d_origins: *const f64, d_directions: *const f64, d_background: *const f64,
+                              d_rgb: *mut f64, hip_stream: *mut c_void) -> c_int;
+    pub fn pt_radiance_finish(ctx: *mut PtContext, kernel_ms: *mut f64) -> c_int;
     pub fn pt_context_stream(ctx: *mut PtContext, slot: c_int) -> *mut c_void;
     pub fn pt_context_next_slot(ctx: *const PtContext) -> c_int;
     // one render call over the GPUs of a node (one context per GPU, one RCCL gather)
