@@ -210,6 +210,29 @@ const char *pt_last_error(const pt_context *ctx);
  * `kd` must be non-NULL for PT_TRAVERSE_KD. Replaces any scene uploaded before. */
 int pt_scene_upload(pt_context *ctx, const pt_scene *scene, int traverse, const pt_kdtree *kd);
 
+/* Moves the resident scene: the scene stays as uploaded except for the node matrices (and, in PT_TRAVERSE_HIER, the graph nodes'), the lights and
+ * the ambient light, which are replaced by the ones given here. After PT_OK every entry point answers as if pt_scene_upload had been called with the
+ * original pt_scene carrying these arrays - the same bits in pixels, linear means, aov / rays / radiance results and the ray counters primary, shadow,
+ * reflect, refract, hits, depth11_skipped (tree-visit counters may differ) - in the traversal the scene was uploaded with; in PT_TRAVERSE_KD the new
+ * k-d tree is part of the call (`kd`, NULL otherwise). Primitive types and data, materials, meshes and their trees, KDMesh trees, textures, node paths
+ * and dfs_rank stay resident and untouched: no triangle, tree-item or texture data is copied; only the scene-level tree is rebuilt (on the host or on
+ * the device: PORTRAYER_BUILD, as for mesh trees). The call is synchronous.
+ * Errors, all before the first write (the resident scene stays usable): PT_ERR_ARGUMENT (NULL context / motion / matrix arrays; n_nodes, n_graph_nodes
+ * or - with lights - n_lights other than the uploaded scene's; PT_TRAVERSE_HIER without graph_*; PT_TRAVERSE_KD without `kd`, `kd` in another traversal,
+ * an inconsistent k-d tree; "a render is in flight": a pt_render_device, pt_aov_device, pt_rays_device or pt_radiance_device not yet closed by its
+ * _finish), PT_ERR_NO_SCENE. PT_ERR_SCENE as for an upload (tree too deep for the traversal stack, the k-d limits): after it the context has NO scene,
+ * as after a refused pt_scene_upload. */
+typedef struct {
+    uint32_t n_nodes;                 /* must equal the uploaded scene's */
+    const double *trans, *invtrans, *normal_trans;          /* n_nodes x 16 each, as in pt_scene */
+    uint32_t n_graph_nodes;           /* PT_TRAVERSE_HIER: must equal the uploaded scene's; else 0 */
+    const double *graph_trans, *graph_invtrans, *graph_normal_trans;
+    uint32_t n_lights;                /* with lights != NULL: must equal the uploaded scene's */
+    const double *lights;             /* n_lights x 15, or NULL: lights stay as they are */
+    const double *ambient;            /* 3 doubles, or NULL */
+} pt_scene_motion;
+int pt_scene_update(pt_context *ctx, const pt_scene_motion *motion, const pt_kdtree *kd);
+
 /* Renders with host buffers. background: per pt_render_params.background_rows. rgb: height x width
  * x 3 bytes, only pixels of the slice that belong to this tile rank are written. linear (optional):
  * height x width x 3 doubles, the sample mean before gamma (render.rs:45). */
@@ -363,6 +386,8 @@ int pt_node_ranks(const pt_node *node);
 int pt_node_uses_rccl(const pt_node *node);          /* 1: the gather is RCCL; 0: ranks share a device, copies */
 pt_context *pt_node_context(pt_node *node, int rank);
 int pt_node_scene_upload(pt_node *node, const pt_scene *scene, int traverse, const pt_kdtree *kd);
+/* pt_scene_update on every rank; refused with PT_ERR_ARGUMENT while frames are open (pt_node_frame_begin without its pt_node_frame_end) */
+int pt_node_scene_update(pt_node *node, const pt_scene_motion *motion, const pt_kdtree *kd);
 /* Like pt_render (host buffers; params->tile_rank / tile_ranks must be 0 / 1: the node partitions the tiles itself).
  * stats: counters summed over the ranks, kernel_ms of the slowest rank, total_ms of the whole call. */
 int pt_node_render(pt_node *node, const pt_camera *camera, const double *background, const pt_render_params *params,
@@ -404,6 +429,11 @@ int pt_measure_copy_bandwidth(pt_context *ctx, uint64_t bytes, int iters, double
 /* Self-test entry points for the parity tests: run device arithmetic on explicit inputs. */
 int pt_test_cast_rays(pt_context *ctx, uint64_t n, const double *origins, const double *directions, int any_hit,
                       double *out_t, int32_t *out_node, int32_t *out_sub);
+/* tests: bytes of device memory the context's scene buffers hold (pt_scene_update must not make it grow) */
+uint64_t pt_test_scene_bytes(const pt_context *ctx);
+/* tests: out[0] the walks' stack_cap, out[1] who built the scene-level tree last (0 pt_scene_upload, 1 pt_scene_update on the host, 2 on the device),
+ * out[2] the device build's clustering rounds, out[3] bytes of the tree buffers (bvh, bvh4, bvh_items) */
+int pt_test_scene_info(const pt_context *ctx, uint64_t out[4]);
 int pt_test_math(pt_context *ctx, int op, uint64_t n, const double *a, const double *b, double *out);
 /* (ABI 6) No GPU, no context: x[i]^y[i] by the HOST build of the kernels' pow (csrc/pt_pow.h) in `port` and by this machine's
  * libm in `libm` - the pin of the restated glibc algorithm against the library the reference calls. */

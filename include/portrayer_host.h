@@ -118,6 +118,15 @@ int ph_renderer_aov(ph_renderer *r, const double camera[10], const pt_aov_params
  * only. A renderer spread over a node runs the pass on rank 0's context. `node` and `material` are numbered as for ph_renderer_aov. */
 int ph_renderer_rays(ph_renderer *r, const pt_rays_params *params, const double *origins, const double *directions, const pt_rays_buffers *out, double *kernel_ms);
 
+/* The resident scene moved (pt_scene_update): `scene` must have the structure of the one the renderer was created from - ph_scene_same_structure - and may
+ * differ in transforms, lights' values and ambient light; PH_ERR_ARGUMENT names the first difference otherwise and the renderer keeps its scene. Only node
+ * matrices, lights and (k-d traversal) the rebuilt reference k-d tree go to the device: meshes, their trees and textures stay where they are. A renderer
+ * spread over a node updates every rank. */
+int ph_renderer_update(ph_renderer *r, const ph_scene *scene);
+/* 1 if `b` is `a` moved (same flattened nodes in the same order: primitive kinds, meshes / triangles, shading, materials, paths through the graph; as many
+ * lights), 0 if not, with the first difference in `why` (n bytes, optional), or a negative PH_ERR_* code. Needs no GPU. */
+int ph_scene_same_structure(const ph_scene *a, const ph_scene *b, char *why, size_t n);
+
 /* Radiance along rays of the caller's own (see pt_radiance): n x 3 f64 origins and directions in world space, `background` 3 doubles or n x 3
  * (params->background_per_ray), rgb n x 3 f64 out: one linear sample of Ray::color per ray. A renderer spread over a node runs the pass on rank 0's context. */
 int ph_renderer_radiance(ph_renderer *r, const pt_radiance_params *params, const double *origins, const double *directions, const double *background, double *rgb,

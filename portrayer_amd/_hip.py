@@ -88,6 +88,13 @@ class PtAovBuffers(C.Structure):
 AOV_BUFFERS = {"depth": (np.float64, 1), "position": (np.float64, 3), "normal": (np.float64, 3), "node": (np.int32, 1), "sub": (np.int32, 1), "material": (np.int32, 1)}
 
 
+class PtSceneMotion(C.Structure):
+    """pt_scene_motion: the resident scene's new node matrices (graph matrices in PT_TRAVERSE_HIER), lights and ambient light for pt_scene_update."""
+    _fields_ = [("n_nodes", C.c_uint32), ("trans", _dp), ("invtrans", _dp), ("normal_trans", _dp),
+                ("n_graph_nodes", C.c_uint32), ("graph_trans", _dp), ("graph_invtrans", _dp), ("graph_normal_trans", _dp),
+                ("n_lights", C.c_uint32), ("lights", _dp), ("ambient", _dp)]
+
+
 class PtRaysParams(C.Structure):
     _fields_ = [("n", C.c_uint64), ("any_hit", C.c_int32), ("reorder", C.c_int32)]
 
@@ -126,7 +133,7 @@ EXPORTS = ["pt_abi_version", "pt_device_count", "pt_context_create", "pt_context
            "pt_node_scene_upload", "pt_node_render", "pt_node_upload_background", "pt_node_render_resident", "pt_node_download_image",
            "pt_node_device", "pt_node_frame_begin", "pt_node_frame_end", "pt_node_frames_in_flight", "pt_node_last_frame_host_ms", "pt_node_last_frame_rank_kernel_ms", "pt_test_pow_host", "pt_test_libm_host",
            "pt_aov", "pt_aov_device", "pt_aov_finish", "pt_rays", "pt_rays_device", "pt_rays_finish",
-           "pt_radiance", "pt_radiance_device", "pt_radiance_finish"]
+           "pt_radiance", "pt_radiance_device", "pt_radiance_finish", "pt_scene_update", "pt_node_scene_update", "pt_test_scene_bytes", "pt_test_scene_info"]
 
 
 def header_functions():
@@ -159,6 +166,14 @@ def lib() -> C.CDLL:
         l.pt_last_error.argtypes = [C.c_void_p]
         l.pt_scene_upload.restype = C.c_int
         l.pt_scene_upload.argtypes = [C.c_void_p, C.POINTER(PtScene), C.c_int, C.POINTER(PtKdTree)]
+        l.pt_scene_update.restype = C.c_int
+        l.pt_scene_update.argtypes = [C.c_void_p, C.POINTER(PtSceneMotion), C.POINTER(PtKdTree)]
+        l.pt_node_scene_update.restype = C.c_int
+        l.pt_node_scene_update.argtypes = [C.c_void_p, C.POINTER(PtSceneMotion), C.POINTER(PtKdTree)]
+        l.pt_test_scene_bytes.restype = C.c_uint64
+        l.pt_test_scene_bytes.argtypes = [C.c_void_p]
+        l.pt_test_scene_info.restype = C.c_int
+        l.pt_test_scene_info.argtypes = [C.c_void_p, C.POINTER(C.c_uint64 * 4)]
         l.pt_render.restype = C.c_int
         l.pt_render.argtypes = [C.c_void_p, C.POINTER(PtCamera), _dp, C.POINTER(PtRenderParams), _u8p, _dp, C.POINTER(PtStats)]
         l.pt_render_device.restype = C.c_int
@@ -289,6 +304,9 @@ class Context:
 
     def upload(self, scene: PtScene, traverse: int, kd: Optional[PtKdTree] = None):
         self.check(lib().pt_scene_upload(self._h, C.byref(scene), traverse, C.byref(kd) if kd is not None else None), "pt_scene_upload")
+
+    def update(self, motion: "PtSceneMotion", kd: Optional[PtKdTree] = None):
+        self.check(lib().pt_scene_update(self._h, C.byref(motion), C.byref(kd) if kd is not None else None), "pt_scene_update")
 
     def render(self, cam: PtCamera, background: np.ndarray, params: PtRenderParams, rgb: np.ndarray, linear: Optional[np.ndarray] = None) -> dict:
         st = PtStats()

@@ -107,10 +107,11 @@ __global__ void __launch_bounds__(256) pt_tri_leaf_kernel(const uint32_t* __rest
     o[9] = c.d;
 }
 
+// [first, end): the nodes this launch converts (pt_scene_upload: all n of them; pt_scene_update: the scene-level tree's alone).
 __global__ void __launch_bounds__(256) pt_collapse4_kernel(const PtBvhNode* __restrict__ bvh2, PtBvh4Node* __restrict__ bvh4, uint32_t n, int by_area_mode,
-                                                            uint32_t scene_first, uint32_t scene_end) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
+                                                            uint32_t scene_first, uint32_t scene_end, uint32_t first, uint32_t end) {
+    const uint32_t i = first + blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= end || i >= n) return;
     // by_area_mode 0: never, 1: mesh trees only (nodes outside [scene_first, scene_end)), 2: every tree
     const bool by_area = by_area_mode == 2 || (by_area_mode == 1 && (i < scene_first || i >= scene_end));
     const PtBvhNode a = bvh2[i];
@@ -306,6 +307,26 @@ struct pt_context {
         hipStream_t stream = nullptr;
         bool queued = false, closed = false;  // as in Aov
     } radiance;
+    // What pt_scene_update needs of the uploaded scene besides the device buffers: everything a flattened node's world box is made of apart from its
+    // matrix, the node paths (identity bits of hier_rec, own_inv), where the scene-level tree sits in bvh / bvh4 (bvh_items with PORTRAYER_TLAS_LEAF != 1),
+    // and the figures stack_cap and forkable are derived from.
+    struct Resident {
+        int traverse = 0;
+        uint32_t n_nodes = 0, n_graph = 0, n_lights = 0;
+        std::vector<uint32_t> info;            // 4 words per flattened node, as uploaded
+        std::vector<PtBuildBox> mesh_box;      // per mesh: the padded model box
+        std::vector<PtBuildBox> tri_box;       // per stand-alone triangle: the padded model box
+        size_t mesh_tris = 0;                  // stand-alone triangle t is triangle mesh_tris + t
+        std::vector<uint32_t> chain_off, chain;
+        size_t tlas_first = 0, tlas_cap = 0;   // the scene-level tree's nodes: bvh[tlas_first, tlas_first + tlas_cap), tlas_cap = n_nodes - 1
+        size_t tlas_items = 0;                 // ... and its n_nodes leaf items in bvh_items (none when the leaves are direct)
+        size_t tree_nodes = 0;                 // nodes in bvh / bvh4 altogether
+        int tlas_leaf = 1, collapse_mode = 1;
+        int below = 0;                         // stack_cap: the deepest walk under a scene leaf
+        int last_builder = 0, last_rounds = 0; // tests: who built the scene-level tree last (0 the upload, 1 an update on the host, 2 on the device) and in how many clustering rounds
+        bool mat_draws = false, dielectric = false;  // forkable: what the materials say
+    } res;
+    PtBuf mesh_box_dev;  // the per-mesh boxes again, 6 f64 each, for the device build of the scene-level tree
     double root_lo[3] = {0.0, 0.0, 0.0}, root_hi[3] = {0.0, 0.0, 0.0};  // the scene tree's root box: union of the flattened nodes' world boxes (reorder = 1 quantises origins inside it)
 };
 #define PT_SLOT_BYTES (256 + sizeof(PtCounters))
@@ -371,7 +392,7 @@ extern "C" void pt_context_destroy(pt_context* c) {
     if (!c) return;
     hipSetDevice(c->device);
     PtBuf* bufs[] = {&c->inv, &c->fwd, &c->nrm, &c->info, &c->tri_v, &c->tri_e, &c->tri_leaf, &c->tri_n, &c->meshes, &c->materials, &c->lights,
-                     &c->bvh, &c->bvh4, &c->bvh_items, &c->kd, &c->kd_items, &c->mat_maps, &c->uv_trans, &c->tex, &c->tex_rgb, &c->srgb_lut, &c->tri_uv, &c->texview, &c->mkd, &c->mkd_items, &c->slot[0].spill, &c->slot[0].stack_spill, &c->slot[0].accum, &c->slot[0].misc, &c->slot[1].spill, &c->slot[1].stack_spill, &c->slot[1].accum, &c->slot[1].misc, &c->bg, &c->rgb, &c->linear, &c->misc, &c->node_box, &c->kd_box, &c->mkd_box, &c->mkd_item_box, &c->kd_ref, &c->g_inv, &c->g_fwd, &c->g_nrm, &c->chain_off, &c->chain, &c->dfs_rank, &c->hier_rec, &c->own_inv};
+                     &c->bvh, &c->bvh4, &c->bvh_items, &c->kd, &c->kd_items, &c->mat_maps, &c->uv_trans, &c->tex, &c->tex_rgb, &c->srgb_lut, &c->tri_uv, &c->texview, &c->mkd, &c->mkd_items, &c->slot[0].spill, &c->slot[0].stack_spill, &c->slot[0].accum, &c->slot[0].misc, &c->slot[1].spill, &c->slot[1].stack_spill, &c->slot[1].accum, &c->slot[1].misc, &c->bg, &c->rgb, &c->linear, &c->misc, &c->node_box, &c->kd_box, &c->mkd_box, &c->mkd_item_box, &c->kd_ref, &c->g_inv, &c->g_fwd, &c->g_nrm, &c->chain_off, &c->chain, &c->dfs_rank, &c->hier_rec, &c->own_inv, &c->mesh_box_dev};
     for (PtBuf* b : bufs) if (b->p) hipFree(b->p);
     if (c->aov.queued) { if (c->aov.closed) hipEventSynchronize(c->aov.copy_done); else hipStreamSynchronize(c->aov.stream); }  // (pt_aov_wait)
     for (PtBuf* b : {&c->aov.stack_spill, &c->aov.misc, &c->aov.out[0], &c->aov.out[1], &c->aov.out[2], &c->aov.out[3], &c->aov.out[4], &c->aov.out[5]}) if (b->p) hipFree(b->p);
@@ -446,6 +467,264 @@ static void pt_pad_box(PtBuildBox* b, double rel) {
         double pad = rel * std::max(b->hi[k] - b->lo[k], mag) + 1e-300;
         b->lo[k] -= pad; b->hi[k] += pad;
     }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Steps of pt_scene_upload that pt_scene_update repeats for a moved scene: both call these, so a host-computed part of an updated
+// scene is what an upload of the same scene computes.
+// ------------------------------------------------------------------------------------------------
+static void pt_pack_node_matrices(uint32_t n, const double* trans, const double* invtrans, const double* normal_trans, std::vector<double>& inv,
+                                  std::vector<double>& fwd, std::vector<double>& nrm) {
+    inv.resize(12 * (size_t)n); fwd.resize(12 * (size_t)n); nrm.resize(9 * (size_t)n);
+    for (uint32_t i = 0; i < n; i++) {
+        for (int r = 0; r < 12; r++) { inv[12 * (size_t)i + r] = invtrans[16 * (size_t)i + r]; fwd[12 * (size_t)i + r] = trans[16 * (size_t)i + r]; }
+        for (int r = 0; r < 3; r++) for (int k = 0; k < 3; k++) nrm[9 * (size_t)i + 3 * r + k] = normal_trans[16 * (size_t)i + 4 * r + k];
+    }
+}
+
+struct PtGraphArrays {
+    std::vector<double> g_inv, g_fwd, g_nrm, own_inv;
+    std::vector<uint32_t> hier_rec;
+};
+// PT_TRAVERSE_HIER: the graph nodes' matrices and, per flattened node, its path record and its own level's inverse. chain_off / chain are checked by the caller.
+static void pt_pack_graph(uint32_t n, uint32_t g, const double* graph_trans, const double* graph_invtrans, const double* graph_normal_trans,
+                          const std::vector<uint32_t>& chain_off, const std::vector<uint32_t>& chain, PtGraphArrays& out) {
+    std::vector<double>&g_inv = out.g_inv, &g_fwd = out.g_fwd, &g_nrm = out.g_nrm, &own_inv = out.own_inv;
+    std::vector<uint32_t>& hier_rec = out.hier_rec;
+    g_inv.resize(12 * (size_t)g); g_fwd.resize(12 * (size_t)g); g_nrm.resize(9 * (size_t)g);
+    for (uint32_t i = 0; i < g; i++) {
+        for (int r = 0; r < 12; r++) { g_inv[12 * (size_t)i + r] = graph_invtrans[16 * (size_t)i + r]; g_fwd[12 * (size_t)i + r] = graph_trans[16 * (size_t)i + r]; }
+        for (int r = 0; r < 3; r++) for (int k = 0; k < 3; k++) g_nrm[9 * (size_t)i + 3 * r + k] = graph_normal_trans[16 * (size_t)i + 4 * r + k];
+    }
+    // One record per flattened node for the walks (pt_node_local_ray_uniform): its path in one scalar fetch instead of three dependent
+    // ones, and which of its levels are the identity (a group without a transform, like every reference scene's root): multiplying a
+    // ray by such a level changes no bit unless a component is -0 or not finite, which the walk rules out once per ray.
+    auto identity = [&](uint32_t gi) {
+        for (int r = 0; r < 3; r++)
+            for (int k = 0; k < 4; k++) {
+                const double want = r == k ? 1.0 : 0.0;  // (== : a zero of either sign passes)
+                if (g_inv[12 * (size_t)gi + 4 * r + k] != want || g_fwd[12 * (size_t)gi + 4 * r + k] != want) return false;
+                if (k < 3 && g_nrm[9 * (size_t)gi + 3 * r + k] != want) return false;
+            }
+        return true;
+    };
+    std::vector<uint8_t> g_ident(g);
+    for (uint32_t i = 0; i < g; i++) g_ident[i] = identity(i) ? 1 : 0;
+    hier_rec.assign(8 * (size_t)n, 0u);
+    own_inv.assign(12 * (size_t)n, 0.0);
+    for (uint32_t i = 0; i < n; i++) {
+        const uint32_t len = chain_off[i + 1] - chain_off[i];
+        uint32_t* rec = &hier_rec[8 * (size_t)i];
+        for (int r = 0; r < 12; r++) own_inv[12 * (size_t)i + r] = g_inv[12 * (size_t)chain[chain_off[i + 1] - 1] + r];  // the node's own level: the last of its path
+        if (len > 7) { rec[0] = 255u; continue; }
+        rec[0] = len;
+        for (uint32_t k = 0; k < len; k++) {
+            const uint32_t gi = chain[chain_off[i] + k];
+            rec[1 + k] = gi;
+            if (g_ident[gi]) rec[0] |= 1u << (8 + k);
+        }
+    }
+}
+
+// the padded model box of a stand-alone triangle (9 f64)
+static void pt_triangle_model_box(const double* v, PtBuildBox* b) {
+    double ext = 1e-30;
+    for (int k = 0; k < 3; k++) {
+        b->lo[k] = std::min(v[k], std::min(v[3 + k], v[6 + k])); b->hi[k] = std::max(v[k], std::max(v[3 + k], v[6 + k]));
+        ext = std::max(ext, b->hi[k] - b->lo[k]);
+    }
+    for (int k = 0; k < 3; k++) { b->lo[k] -= 1e-6 * ext; b->hi[k] += 1e-6 * ext; }
+}
+
+// Conservative world-space boxes of the flattened nodes and their union, the scene tree's root box (c->root_lo / root_hi): every hit the
+// primitive tests can accept lies inside its box (cube.rs:25 / plane.rs:31 accept points up to 1e-5 outside the unit shape; all shapes are
+// padded by 1e-4 model units). Spheres, cylinders and cones get their exact boxes under the affine transform instead of the box of their
+// transformed unit cube. `info`: 4 words per node (type, data, ..); pt_node_box_kernel (pt_build.hip) is the device's copy of the formulas.
+static void pt_node_world_boxes(uint32_t n, const double* trans, const uint32_t* info, const std::vector<PtBuildBox>& mesh_box,
+                                const std::vector<PtBuildBox>& tri_box, size_t mesh_tris, std::vector<PtBuildBox>& node_box, double root_lo[3], double root_hi[3]) {
+    node_box.resize(n);
+    for (uint32_t i = 0; i < n; i++) {
+        const int t = (int)info[4 * (size_t)i];
+        const uint32_t data = info[4 * (size_t)i + 1];
+        const double* M = &trans[16 * (size_t)i];
+        PtBuildBox& nb = node_box[i];
+        auto disc = [&](double yc, double radius, PtBuildBox* b) {  // disc of `radius` in the model xz-plane at height yc
+            for (int r = 0; r < 3; r++) {
+                double c = M[4 * r + 1] * yc + M[4 * r + 3];
+                double e = radius * std::sqrt(M[4 * r] * M[4 * r] + M[4 * r + 2] * M[4 * r + 2]);
+                b->lo[r] = std::min(b->lo[r], c - e); b->hi[r] = std::max(b->hi[r], c + e);
+            }
+        };
+        double lo[3], hi[3];
+        bool boxed = false;
+        switch (t) {
+        case PT_PRIM_SPHERE:
+            for (int r = 0; r < 3; r++) {
+                double e = 1.0001 * std::sqrt(M[4 * r] * M[4 * r] + M[4 * r + 1] * M[4 * r + 1] + M[4 * r + 2] * M[4 * r + 2]);
+                nb.lo[r] = M[4 * r + 3] - e; nb.hi[r] = M[4 * r + 3] + e;
+            }
+            boxed = true; break;
+        case PT_PRIM_CYLINDER: nb = pt_bvh_detail::empty_box(); disc(0.5001, 0.5001, &nb); disc(-0.5001, 0.5001, &nb); boxed = true; break;
+        case PT_PRIM_CONE: nb = pt_bvh_detail::empty_box(); disc(0.5001, 1e-4, &nb); disc(-0.5001, 0.5001, &nb); boxed = true; break;
+        case PT_PRIM_PLANE: lo[0] = lo[2] = -0.5001; hi[0] = hi[2] = 0.5001; lo[1] = -1e-4; hi[1] = 1e-4; break;
+        case PT_PRIM_MESH: case PT_PRIM_KDMESH: for (int k = 0; k < 3; k++) { lo[k] = mesh_box[data].lo[k]; hi[k] = mesh_box[data].hi[k]; } break;
+        case PT_PRIM_TRIANGLE: for (int k = 0; k < 3; k++) { lo[k] = tri_box[data - mesh_tris].lo[k]; hi[k] = tri_box[data - mesh_tris].hi[k]; } break;
+        default: lo[0] = lo[1] = lo[2] = -0.5001; hi[0] = hi[1] = hi[2] = 0.5001; break;  // cube
+        }
+        if (!boxed) pt_transform_box(M, lo, hi, &nb);
+        pt_pad_box(&nb, 1e-9);
+    }
+    for (int k = 0; k < 3; k++) { root_lo[k] = INFINITY; root_hi[k] = -INFINITY; }
+    for (uint32_t i = 0; i < n; i++)
+        for (int k = 0; k < 3; k++) { root_lo[k] = std::min(root_lo[k], node_box[i].lo[k]); root_hi[k] = std::max(root_hi[k], node_box[i].hi[k]); }
+}
+
+// The scene-level tree on the host: binned SAH over the nodes' world boxes (pt_bvh.h), built from index 0 and then moved to where it lives in the
+// context's arrays: its nodes from `node_base` on in bvh, its leaf items (none when the leaves are direct) from `item_base` on in bvh_items.
+static PtBvhRef pt_build_scene_tree(const std::vector<PtBuildBox>& node_box, int tlas_leaf, bool direct, size_t node_base, size_t item_base,
+                                    std::vector<PtBvhNode>& nodes, std::vector<uint32_t>& items) {
+    nodes.clear(); items.clear();
+    PtBvhRef root = pt_bvh_build(node_box.data(), nullptr, node_box.size(), tlas_leaf, nodes, items, direct);
+    auto moved = [&](uint32_t ref) -> uint32_t {
+        if (ref == PT_REF_EMPTY) return ref;
+        if (!(ref & PT_REF_LEAF)) return ref + (uint32_t)node_base;
+        if (direct) return ref;
+        return PT_REF_LEAF | (((((ref & ~PT_REF_LEAF) >> 3) + (uint32_t)item_base) << 3) | (ref & 7u));
+    };
+    for (PtBvhNode& nd : nodes) { nd.child0 = moved(nd.child0); nd.child1 = moved(nd.child1); }
+    root.child = moved(root.child);
+    return root;
+}
+
+// The reference's k-d tree over the flattened nodes (PT_TRAVERSE_KD) as the walks read it, with the conservative f32 boxes the culls use.
+struct PtKdArrays {
+    std::vector<PtKdNode> kdn;
+    std::vector<uint32_t> kdi, kd_ref32;
+    std::vector<float> node_box32, kd_box32;
+    double kd_extent = 0.0;
+    int kd_depth = 0, kd_levels = 0;
+};
+static int pt_pack_kd(pt_context* c, const pt_kdtree* kd, uint32_t n, const std::vector<PtBuildBox>& node_box, PtKdArrays& out) {
+    std::vector<PtKdNode>& kdn = out.kdn;
+    std::vector<uint32_t>&kdi = out.kdi, &kd_ref32 = out.kd_ref32;
+    std::vector<float>&node_box32 = out.node_box32, &kd_box32 = out.kd_box32;
+    int& kd_levels = out.kd_levels;  // split levels on the deepest path of the tree (root = level 0)
+    if (kd->n_nodes == 0 || !kd->axis || !kd->plane || !kd->front || !kd->back || !kd->first || !kd->count || (kd->n_items && !kd->leaf_items))
+        return pt_fail(c, PT_ERR_ARGUMENT, "incomplete k-d tree");
+    kdn.resize(kd->n_nodes);
+    for (uint32_t i = 0; i < kd->n_nodes; i++) {
+        PtKdNode& k = kdn[i];
+        k.axis = kd->axis[i]; k.plane = kd->plane[i]; k.front = kd->front[i]; k.back = kd->back[i];
+        k.first = kd->first[i]; k.count = kd->count[i]; k.pad = 0; k.pad2[0] = k.pad2[1] = 0.0f; for (int r = 0; r < 6; r++) k.box[r] = 0.0f;
+        if (k.axis >= 0) {
+            if (k.axis > 2 || k.front < 0 || k.back < 0 || (uint32_t)k.front >= kd->n_nodes || (uint32_t)k.back >= kd->n_nodes)
+                return pt_fail(c, PT_ERR_ARGUMENT, "k-d child out of range");
+        } else if (k.first < 0 || k.count < 0 || (uint32_t)(k.first + k.count) > kd->n_items) {
+            return pt_fail(c, PT_ERR_ARGUMENT, "k-d leaf range out of bounds");
+        }
+    }
+    kdi.resize(kd->n_items);
+    for (uint32_t i = 0; i < kd->n_items; i++) {
+        if (kd->leaf_items[i] < 0 || (uint32_t)kd->leaf_items[i] >= n) return pt_fail(c, PT_ERR_ARGUMENT, "k-d leaf item out of range");
+        kdi[i] = (uint32_t)kd->leaf_items[i];
+    }
+    double dx = kd->root_max[0] - kd->root_min[0], dy = kd->root_max[1] - kd->root_min[1], dz = kd->root_max[2] - kd->root_min[2];
+    out.kd_extent = (dx * dx + dy * dy) + dz * dz;  // bounding_box.rs:95-99 magnitude_squared
+    out.kd_depth = kd->max_depth < 0 ? 0 : kd->max_depth;
+    node_box32.resize(6 * kdi.size());  // in leaf-item order: the walk reads a leaf's boxes one after the other
+    for (size_t j = 0; j < kdi.size(); j++)
+        for (int k = 0; k < 3; k++) {
+            node_box32[6 * j + k] = pt_bvh_detail::round_down(node_box[kdi[j]].lo[k]);
+            node_box32[6 * j + 3 + k] = pt_bvh_detail::round_up(node_box[kdi[j]].hi[k]);
+        }
+    // the wave-uniform k-d walk (pt_trace_packet_kd) reads a leaf reference and its cull box in ONE scalar fetch: 32 bytes {node, 0, box}
+    kd_ref32.resize(8 * kdi.size());
+    for (size_t j = 0; j < kdi.size(); j++) {
+        kd_ref32[8 * j] = kdi[j]; kd_ref32[8 * j + 1] = 0u;
+        memcpy(&kd_ref32[8 * j + 2], &node_box32[6 * j], 6 * sizeof(float));
+    }
+    {
+        std::vector<std::pair<uint32_t, int>> todo;
+        std::vector<uint8_t> seen(kdn.size(), 0);
+        if (!kdn.empty()) todo.push_back({0u, 0});
+        while (!todo.empty()) {
+            auto [i, lev] = todo.back(); todo.pop_back();
+            if (seen[i]) return pt_fail(c, PT_ERR_ARGUMENT, "k-d tree is not a tree");
+            seen[i] = 1;
+            if (kdn[i].axis < 0) continue;
+            kd_levels = std::max(kd_levels, lev + 1);
+            todo.push_back({(uint32_t)kdn[i].front, lev + 1}); todo.push_back({(uint32_t)kdn[i].back, lev + 1});
+        }
+    }
+    if (kd_levels > PT_KD_WAVE_LEVELS)  // two bits of per-lane state per level in one 64-bit word (pt_trace_packet_kd); a tree that deep has > 2^32 leaves unless it is a degenerate chain
+        return pt_fail(c, PT_ERR_SCENE, "k-d tree deeper than 32 levels (the limit of the k-d walk: include/portrayer_hip.h, pt_kdtree)");
+    // what the walk's packed words can address: a stack entry is (node << 5) | level, a node is fetched at byte offset node << 6, a leaf reference at (first + i) << 5
+    if (kdn.size() >= ((size_t)1 << 26)) return pt_fail(c, PT_ERR_SCENE, "k-d tree of 2^26 nodes or more");
+    if (kd_ref32.size() / 8 >= ((size_t)1 << 27)) return pt_fail(c, PT_ERR_SCENE, "k-d tree with 2^27 leaf references or more");
+    // children follow their parents in the linearised tree (pre-order): one backward sweep
+    kd_box32.assign(6 * kdn.size(), 0.0f);
+    for (size_t i = kdn.size(); i-- > 0;) {
+        float* b = &kd_box32[6 * i];
+        const PtKdNode& k = kdn[i];
+        for (int r = 0; r < 3; r++) { b[r] = (float)PT_BOX_LIMIT; b[3 + r] = -(float)PT_BOX_LIMIT; }  // empty
+        if (k.axis < 0) {
+            for (int32_t j = 0; j < k.count; j++)
+                for (int r = 0; r < 3; r++) {
+                    b[r] = std::min(b[r], node_box32[6 * (size_t)(k.first + j) + r]);
+                    b[3 + r] = std::max(b[3 + r], node_box32[6 * (size_t)(k.first + j) + 3 + r]);
+                }
+        } else if ((size_t)k.front > i && (size_t)k.back > i) {
+            for (int r = 0; r < 3; r++) {
+                b[r] = std::min(kd_box32[6 * (size_t)k.front + r], kd_box32[6 * (size_t)k.back + r]);
+                b[3 + r] = std::max(kd_box32[6 * (size_t)k.front + 3 + r], kd_box32[6 * (size_t)k.back + 3 + r]);
+            }
+        } else {  // not in pre-order: no culling at this node
+            for (int r = 0; r < 3; r++) { b[r] = -(float)PT_BOX_LIMIT; b[3 + r] = (float)PT_BOX_LIMIT; }
+        }
+    }
+    for (size_t i = 0; i < kdn.size(); i++) for (int r = 0; r < 6; r++) kdn[i].box[r] = kd_box32[6 * i + r];
+    return PT_OK;
+}
+// ... into the context's buffers and the view (k.kdn empty: another traversal)
+static int pt_upload_kd(pt_context* c, const PtKdArrays& k, bool kd_mode) {
+    int rc;
+    if ((rc = pt_upload(c, c->node_box, k.node_box32)) || (rc = pt_upload(c, c->kd_box, k.kd_box32)) || (rc = pt_upload(c, c->kd, k.kdn)) ||
+        (rc = pt_upload(c, c->kd_items, k.kdi)) || (rc = pt_upload(c, c->kd_ref, k.kd_ref32)))
+        return rc;
+    PtSceneView& v = c->view;
+    v.kd = (const PtKdNode*)c->kd.p; v.kd_items = (const uint32_t*)c->kd_items.p;
+    v.kd_extent = k.kd_extent;
+    v.kd_ref = (const uint32_t*)c->kd_ref.p; v.kd_levels = k.kd_levels;
+    v.node_box = kd_mode && !k.kdi.empty() ? (const float*)c->node_box.p : nullptr;
+    v.kd_box = kd_mode ? (const float*)c->kd_box.p : nullptr;
+    if (getenv("PORTRAYER_KD_NO_CULL")) v.kd_box = v.node_box = nullptr;  // experiment: the reference's walk as it is
+    if (const char* e = getenv("PORTRAYER_KD_CULL")) { const int m = atoi(e); if (!(m & 1)) v.kd_box = nullptr; if (!(m & 2)) v.node_box = nullptr; }  // experiment: bit 0 tree nodes, bit 1 leaf references
+    return PT_OK;
+}
+
+// fork / join of refracted subtrees (pt_shade.h) needs a recursion that draws no random numbers and a dielectric material to be of use
+static void pt_set_light_flags(pt_context* c, const double* lights, uint32_t n_lights) {
+    bool draws = c->res.mat_draws;
+    for (uint32_t l = 0; l < n_lights; l++) {
+        const double* L = &lights[15 * (size_t)l];
+        const bool empty = (L[9] == 0.0 && L[10] == 0.0 && L[11] == 0.0) || (L[12] == 0.0 && L[13] == 0.0 && L[14] == 0.0);  // light.rs:51-53
+        if (!empty) draws = true;
+    }
+    c->forkable = c->spawns && c->res.dielectric && !draws && n_lights <= PT_LIGHT_ROUND;
+    c->one_ray = c->spawns && !c->res.dielectric;
+}
+
+// The walks' stack: a level of the four-child walk pushes up to three pending children; it covers two levels of the two-child tree in the plain
+// collapse and at least one when nodes are opened by area. `tlas_depth`: of the scene-level tree (two-child form); `kd_depth`: of the k-d tree
+// the scene is walked with NOW (PT_TRAVERSE_KD; it changes when nodes move).
+static int pt_set_stack_cap(pt_context* c, int tlas_depth, int kd_depth) {
+    const int collapse_mode = c->res.collapse_mode;
+    auto wide = [&](int depth2) { return collapse_mode ? 3 * depth2 : 3 * ((depth2 + 1) / 2); };
+    int cap = c->res.traverse == PT_TRAVERSE_KD ? 3 * (kd_depth + 1) + c->res.below + 2 : wide(tlas_depth) + c->res.below + 4;
+    c->view.stack_cap = std::max(cap, 8);
+    if (const char* e = getenv("PORTRAYER_STACK_CAP")) c->view.stack_cap = std::max(1, atoi(e));  // tests: force PT_ERR_TRAVERSAL
+    if (c->view.stack_cap > 4096) return pt_fail(c, PT_ERR_SCENE, "tree too deep for the traversal stack");
+    return PT_OK;
 }
 
 extern "C" int pt_scene_upload(pt_context* c, const pt_scene* s, int traverse, const pt_kdtree* kd) {
@@ -638,18 +917,12 @@ extern "C" int pt_scene_upload(pt_context* c, const pt_scene* s, int traverse, c
         }
 
     // ---- nodes
-    std::vector<double> inv(12 * (size_t)n), fwd(12 * (size_t)n), nrm(9 * (size_t)n);
+    std::vector<double> inv, fwd, nrm;
     std::vector<uint32_t> info(4 * (size_t)n);
-    std::vector<double> g_inv, g_fwd, g_nrm;
-    std::vector<uint32_t> chain_off, chain, dfs_rank, hier_rec;
-    std::vector<double> own_inv;
+    PtGraphArrays graph;
+    std::vector<uint32_t> chain_off, chain, dfs_rank;
     if (traverse == PT_TRAVERSE_HIER && n) {
         const uint32_t g = s->n_graph_nodes;
-        g_inv.resize(12 * (size_t)g); g_fwd.resize(12 * (size_t)g); g_nrm.resize(9 * (size_t)g);
-        for (uint32_t i = 0; i < g; i++) {
-            for (int r = 0; r < 12; r++) { g_inv[12 * (size_t)i + r] = s->graph_invtrans[16 * (size_t)i + r]; g_fwd[12 * (size_t)i + r] = s->graph_trans[16 * (size_t)i + r]; }
-            for (int r = 0; r < 3; r++) for (int k = 0; k < 3; k++) g_nrm[9 * (size_t)i + 3 * r + k] = s->graph_normal_trans[16 * (size_t)i + 4 * r + k];
-        }
         chain_off.assign(s->node_chain_off, s->node_chain_off + n + 1);
         if (chain_off[0] != 0) return pt_fail(c, PT_ERR_ARGUMENT, "node_chain_off must start at 0");
         for (uint32_t i = 0; i < n; i++)
@@ -657,184 +930,43 @@ extern "C" int pt_scene_upload(pt_context* c, const pt_scene* s, int traverse, c
         chain.assign(s->node_chain, s->node_chain + chain_off[n]);
         for (uint32_t id : chain) if (id >= g) return pt_fail(c, PT_ERR_ARGUMENT, "node_chain names a graph node out of range");
         dfs_rank.assign(s->node_dfs_rank, s->node_dfs_rank + n);
-        // One record per flattened node for the walks (pt_node_local_ray_uniform): its path in one scalar fetch instead of three dependent
-        // ones, and which of its levels are the identity (a group without a transform, like every reference scene's root): multiplying a
-        // ray by such a level changes no bit unless a component is -0 or not finite, which the walk rules out once per ray.
-        auto identity = [&](uint32_t gi) {
-            for (int r = 0; r < 3; r++)
-                for (int k = 0; k < 4; k++) {
-                    const double want = r == k ? 1.0 : 0.0;  // (== : a zero of either sign passes)
-                    if (g_inv[12 * (size_t)gi + 4 * r + k] != want || g_fwd[12 * (size_t)gi + 4 * r + k] != want) return false;
-                    if (k < 3 && g_nrm[9 * (size_t)gi + 3 * r + k] != want) return false;
-                }
-            return true;
-        };
-        std::vector<uint8_t> g_ident(g);
-        for (uint32_t i = 0; i < g; i++) g_ident[i] = identity(i) ? 1 : 0;
-        hier_rec.assign(8 * (size_t)n, 0u);
-        own_inv.assign(12 * (size_t)n, 0.0);
-        for (uint32_t i = 0; i < n; i++) {
-            const uint32_t len = chain_off[i + 1] - chain_off[i];
-            uint32_t* rec = &hier_rec[8 * (size_t)i];
-            for (int r = 0; r < 12; r++) own_inv[12 * (size_t)i + r] = g_inv[12 * (size_t)chain[chain_off[i + 1] - 1] + r];  // the node's own level: the last of its path
-            if (len > 7) { rec[0] = 255u; continue; }
-            rec[0] = len;
-            for (uint32_t k = 0; k < len; k++) {
-                const uint32_t gi = chain[chain_off[i] + k];
-                rec[1 + k] = gi;
-                if (g_ident[gi]) rec[0] |= 1u << (8 + k);
-            }
-        }
+        pt_pack_graph(n, g, s->graph_trans, s->graph_invtrans, s->graph_normal_trans, chain_off, chain, graph);
     }
-    std::vector<PtBuildBox> node_box(n);
+    pt_pack_node_matrices(n, s->trans, s->invtrans, s->normal_trans, inv, fwd, nrm);
+    std::vector<PtBuildBox> tri_box(s->n_triangles);
+    for (uint32_t t = 0; t < s->n_triangles; t++) pt_triangle_model_box(&tri_v[9 * (mesh_tris + t)], &tri_box[t]);
     for (uint32_t i = 0; i < n; i++) {
-        for (int r = 0; r < 12; r++) { inv[12 * (size_t)i + r] = s->invtrans[16 * (size_t)i + r]; fwd[12 * (size_t)i + r] = s->trans[16 * (size_t)i + r]; }
-        for (int r = 0; r < 3; r++) for (int k = 0; k < 3; k++) nrm[9 * (size_t)i + 3 * r + k] = s->normal_trans[16 * (size_t)i + 4 * r + k];
         int t = s->prim_type[i];
         uint32_t data = (uint32_t)s->prim_data[i];
         if (t == PT_PRIM_TRIANGLE) data = (uint32_t)(mesh_tris + data);
         info[4 * (size_t)i] = (uint32_t)t; info[4 * (size_t)i + 1] = data;
         info[4 * (size_t)i + 2] = (uint32_t)s->prim_flags[i]; info[4 * (size_t)i + 3] = (uint32_t)s->material[i];
-        // Conservative world-space box: every hit the primitive tests can accept lies inside it
-        // (cube.rs:25 / plane.rs:31 accept points up to 1e-5 outside the unit shape; all shapes are
-        // padded by 1e-4 model units). Spheres, cylinders and cones get their exact boxes under the
-        // affine transform instead of the box of their transformed unit cube.
-        const double* M = &s->trans[16 * (size_t)i];
-        PtBuildBox& nb = node_box[i];
-        auto disc = [&](double yc, double radius, PtBuildBox* b) {  // disc of `radius` in the model xz-plane at height yc
-            for (int r = 0; r < 3; r++) {
-                double c = M[4 * r + 1] * yc + M[4 * r + 3];
-                double e = radius * std::sqrt(M[4 * r] * M[4 * r] + M[4 * r + 2] * M[4 * r + 2]);
-                b->lo[r] = std::min(b->lo[r], c - e); b->hi[r] = std::max(b->hi[r], c + e);
-            }
-        };
-        double lo[3], hi[3];
-        bool boxed = false;
-        switch (t) {
-        case PT_PRIM_SPHERE:
-            for (int r = 0; r < 3; r++) {
-                double e = 1.0001 * std::sqrt(M[4 * r] * M[4 * r] + M[4 * r + 1] * M[4 * r + 1] + M[4 * r + 2] * M[4 * r + 2]);
-                nb.lo[r] = M[4 * r + 3] - e; nb.hi[r] = M[4 * r + 3] + e;
-            }
-            boxed = true; break;
-        case PT_PRIM_CYLINDER: nb = pt_bvh_detail::empty_box(); disc(0.5001, 0.5001, &nb); disc(-0.5001, 0.5001, &nb); boxed = true; break;
-        case PT_PRIM_CONE: nb = pt_bvh_detail::empty_box(); disc(0.5001, 1e-4, &nb); disc(-0.5001, 0.5001, &nb); boxed = true; break;
-        case PT_PRIM_PLANE: lo[0] = lo[2] = -0.5001; hi[0] = hi[2] = 0.5001; lo[1] = -1e-4; hi[1] = 1e-4; break;
-        case PT_PRIM_MESH: case PT_PRIM_KDMESH: for (int k = 0; k < 3; k++) { lo[k] = mesh_box[data].lo[k]; hi[k] = mesh_box[data].hi[k]; } break;
-        case PT_PRIM_TRIANGLE: {
-            const double* v = &tri_v[9 * (size_t)data];
-            double ext = 1e-30;
-            for (int k = 0; k < 3; k++) {
-                lo[k] = std::min(v[k], std::min(v[3 + k], v[6 + k])); hi[k] = std::max(v[k], std::max(v[3 + k], v[6 + k]));
-                ext = std::max(ext, hi[k] - lo[k]);
-            }
-            for (int k = 0; k < 3; k++) { lo[k] -= 1e-6 * ext; hi[k] += 1e-6 * ext; }
-            break;
-        }
-        default: lo[0] = lo[1] = lo[2] = -0.5001; hi[0] = hi[1] = hi[2] = 0.5001; break;  // cube
-        }
-        if (!boxed) pt_transform_box(M, lo, hi, &nb);
-        pt_pad_box(&nb, 1e-9);
     }
-    for (int k = 0; k < 3; k++) { c->root_lo[k] = INFINITY; c->root_hi[k] = -INFINITY; }
-    for (uint32_t i = 0; i < n; i++)
-        for (int k = 0; k < 3; k++) { c->root_lo[k] = std::min(c->root_lo[k], node_box[i].lo[k]); c->root_hi[k] = std::max(c->root_hi[k], node_box[i].hi[k]); }
+    std::vector<PtBuildBox> node_box;
+    pt_node_world_boxes(n, s->trans, info.data(), mesh_box, tri_box, mesh_tris, node_box, c->root_lo, c->root_hi);
     int tlas_leaf = 1;  // primitive tests (f64, ~200 instructions) cost far more than a node visit: measured best on big-scene
     if (const char* e = getenv("PORTRAYER_TLAS_LEAF")) tlas_leaf = std::max(1, atoi(e));
     const bool tlas_direct = tlas_leaf == 1 && n < (1u << 28);
-    const size_t tlas_first = bvh.size();
-    PtBvhRef tlas = pt_bvh_build(node_box.data(), nullptr, n, tlas_leaf, bvh, items, tlas_direct);
+    // the scene-level tree keeps room for the n - 1 nodes any tree over n leaves can have: pt_scene_update builds its trees into the same place
+    const size_t tlas_first = bvh.size(), tlas_items = items.size(), tlas_cap = n ? n - 1 : 0;
+    PtBvhRef tlas;
+    {
+        std::vector<PtBvhNode> tl_nodes;
+        std::vector<uint32_t> tl_items;
+        tlas = pt_build_scene_tree(node_box, tlas_leaf, tlas_direct, tlas_first, tlas_items, tl_nodes, tl_items);
+        bvh.insert(bvh.end(), tl_nodes.begin(), tl_nodes.end());
+        items.insert(items.end(), tl_items.begin(), tl_items.end());
+        PtBvhNode unused;
+        memset(&unused, 0, sizeof unused);
+        unused.child0 = unused.child1 = PT_REF_EMPTY;
+        bvh.resize(tlas_first + tlas_cap, unused);
+    }
     const size_t tlas_end = bvh.size();
 
     // ---- k-d tree (reference structure, KD mode)
-    std::vector<PtKdNode> kdn;
-    std::vector<uint32_t> kdi;
-    double kd_extent = 0.0;
-    int kd_depth = 0;
-    if (traverse == PT_TRAVERSE_KD) {
-        if (kd->n_nodes == 0 || !kd->axis || !kd->plane || !kd->front || !kd->back || !kd->first || !kd->count || (kd->n_items && !kd->leaf_items))
-            return pt_fail(c, PT_ERR_ARGUMENT, "incomplete k-d tree");
-        kdn.resize(kd->n_nodes);
-        for (uint32_t i = 0; i < kd->n_nodes; i++) {
-            PtKdNode& k = kdn[i];
-            k.axis = kd->axis[i]; k.plane = kd->plane[i]; k.front = kd->front[i]; k.back = kd->back[i];
-            k.first = kd->first[i]; k.count = kd->count[i]; k.pad = 0; k.pad2[0] = k.pad2[1] = 0.0f; for (int r = 0; r < 6; r++) k.box[r] = 0.0f;
-            if (k.axis >= 0) {
-                if (k.axis > 2 || k.front < 0 || k.back < 0 || (uint32_t)k.front >= kd->n_nodes || (uint32_t)k.back >= kd->n_nodes)
-                    return pt_fail(c, PT_ERR_ARGUMENT, "k-d child out of range");
-            } else if (k.first < 0 || k.count < 0 || (uint32_t)(k.first + k.count) > kd->n_items) {
-                return pt_fail(c, PT_ERR_ARGUMENT, "k-d leaf range out of bounds");
-            }
-        }
-        kdi.resize(kd->n_items);
-        for (uint32_t i = 0; i < kd->n_items; i++) {
-            if (kd->leaf_items[i] < 0 || (uint32_t)kd->leaf_items[i] >= n) return pt_fail(c, PT_ERR_ARGUMENT, "k-d leaf item out of range");
-            kdi[i] = (uint32_t)kd->leaf_items[i];
-        }
-        double dx = kd->root_max[0] - kd->root_min[0], dy = kd->root_max[1] - kd->root_min[1], dz = kd->root_max[2] - kd->root_min[2];
-        kd_extent = (dx * dx + dy * dy) + dz * dz;  // bounding_box.rs:95-99 magnitude_squared
-        kd_depth = kd->max_depth < 0 ? 0 : kd->max_depth;
-    }
-
+    PtKdArrays kda;
     int rc;
-    std::vector<float> node_box32;
-    if (traverse == PT_TRAVERSE_KD) {
-        node_box32.resize(6 * kdi.size());  // in leaf-item order: the walk reads a leaf's boxes one after the other
-        for (size_t j = 0; j < kdi.size(); j++)
-            for (int k = 0; k < 3; k++) {
-                node_box32[6 * j + k] = pt_bvh_detail::round_down(node_box[kdi[j]].lo[k]);
-                node_box32[6 * j + 3 + k] = pt_bvh_detail::round_up(node_box[kdi[j]].hi[k]);
-            }
-    }
-    // the wave-uniform k-d walk (pt_trace_packet_kd) reads a leaf reference and its cull box in ONE scalar fetch: 32 bytes {node, 0, box}
-    std::vector<uint32_t> kd_ref32;
-    int kd_levels = 0;  // split levels on the deepest path of the tree (root = level 0)
-    if (traverse == PT_TRAVERSE_KD) {
-        kd_ref32.resize(8 * kdi.size());
-        for (size_t j = 0; j < kdi.size(); j++) {
-            kd_ref32[8 * j] = kdi[j]; kd_ref32[8 * j + 1] = 0u;
-            memcpy(&kd_ref32[8 * j + 2], &node_box32[6 * j], 6 * sizeof(float));
-        }
-        std::vector<std::pair<uint32_t, int>> todo;
-        std::vector<uint8_t> seen(kdn.size(), 0);
-        if (!kdn.empty()) todo.push_back({0u, 0});
-        while (!todo.empty()) {
-            auto [i, lev] = todo.back(); todo.pop_back();
-            if (seen[i]) return pt_fail(c, PT_ERR_ARGUMENT, "k-d tree is not a tree");
-            seen[i] = 1;
-            if (kdn[i].axis < 0) continue;
-            kd_levels = std::max(kd_levels, lev + 1);
-            todo.push_back({(uint32_t)kdn[i].front, lev + 1}); todo.push_back({(uint32_t)kdn[i].back, lev + 1});
-        }
-    }
-    if (kd_levels > PT_KD_WAVE_LEVELS)  // two bits of per-lane state per level in one 64-bit word (pt_trace_packet_kd); a tree that deep has > 2^32 leaves unless it is a degenerate chain
-        return pt_fail(c, PT_ERR_SCENE, "k-d tree deeper than 32 levels (the limit of the k-d walk: include/portrayer_hip.h, pt_kdtree)");
-    // what the walk's packed words can address: a stack entry is (node << 5) | level, a node is fetched at byte offset node << 6, a leaf reference at (first + i) << 5
-    if (kdn.size() >= ((size_t)1 << 26)) return pt_fail(c, PT_ERR_SCENE, "k-d tree of 2^26 nodes or more");
-    if (kd_ref32.size() / 8 >= ((size_t)1 << 27)) return pt_fail(c, PT_ERR_SCENE, "k-d tree with 2^27 leaf references or more");
-    std::vector<float> kd_box32;
-    if (traverse == PT_TRAVERSE_KD) {  // children follow their parents in the linearised tree (pre-order): one backward sweep
-        kd_box32.assign(6 * kdn.size(), 0.0f);
-        for (size_t i = kdn.size(); i-- > 0;) {
-            float* b = &kd_box32[6 * i];
-            const PtKdNode& k = kdn[i];
-            for (int r = 0; r < 3; r++) { b[r] = (float)PT_BOX_LIMIT; b[3 + r] = -(float)PT_BOX_LIMIT; }  // empty
-            if (k.axis < 0) {
-                for (int32_t j = 0; j < k.count; j++)
-                    for (int r = 0; r < 3; r++) {
-                        b[r] = std::min(b[r], node_box32[6 * (size_t)(k.first + j) + r]);
-                        b[3 + r] = std::max(b[3 + r], node_box32[6 * (size_t)(k.first + j) + 3 + r]);
-                    }
-            } else if ((size_t)k.front > i && (size_t)k.back > i) {
-                for (int r = 0; r < 3; r++) {
-                    b[r] = std::min(kd_box32[6 * (size_t)k.front + r], kd_box32[6 * (size_t)k.back + r]);
-                    b[3 + r] = std::max(kd_box32[6 * (size_t)k.front + 3 + r], kd_box32[6 * (size_t)k.back + 3 + r]);
-                }
-            } else {  // not in pre-order: no culling at this node
-                for (int r = 0; r < 3; r++) { b[r] = -(float)PT_BOX_LIMIT; b[3 + r] = (float)PT_BOX_LIMIT; }
-            }
-        }
-    }
+    if (traverse == PT_TRAVERSE_KD && (rc = pt_pack_kd(c, kd, n, node_box, kda))) return rc;
     lap("scene tree");
     if ((rc = pt_upload(c, c->tri_v, tri_v))) return rc;
     {   // the edge form of every triangle (pt_triangle_hit_e): corner a, a - b, a - c
@@ -848,6 +980,7 @@ extern "C" int pt_scene_upload(pt_context* c, const pt_scene* s, int traverse, c
         }
         if ((rc = pt_upload(c, c->tri_e, tri_e))) return rc;
     }
+    size_t tree_nodes = 0;
     {   // tree arrays: the host-built part first, then room for the device-built mesh trees
         size_t n_nodes = bvh.size(), n_items = items.size();
         for (const DeviceMesh& dm : device_meshes) { n_nodes += PT_DEVICE_TREE_NODES(dm.count); n_items += PT_DEVICE_TREE_ITEMS(dm.count, blas_leaf); }
@@ -874,10 +1007,11 @@ extern "C" int pt_scene_upload(pt_context* c, const pt_scene* s, int traverse, c
         if (const char* e = getenv("PORTRAYER_COLLAPSE")) collapse_mode = strcmp(e, "plain") == 0 ? 0 : (strcmp(e, "area") == 0 ? 2 : 1);
         if ((rc = pt_reserve(c, c->bvh4, std::max<size_t>(n_nodes, 1) * sizeof(PtBvh4Node)))) return rc;
         if (n_nodes) {
-            hipLaunchKernelGGL(pt_collapse4_kernel, dim3((unsigned)((n_nodes + 255) / 256)), dim3(256), 0, nullptr, (const PtBvhNode*)c->bvh.p, (PtBvh4Node*)c->bvh4.p, (uint32_t)n_nodes, collapse_mode, (uint32_t)tlas_first, (uint32_t)tlas_end);
+            hipLaunchKernelGGL(pt_collapse4_kernel, dim3((unsigned)((n_nodes + 255) / 256)), dim3(256), 0, nullptr, (const PtBvhNode*)c->bvh.p, (PtBvh4Node*)c->bvh4.p, (uint32_t)n_nodes, collapse_mode, (uint32_t)tlas_first, (uint32_t)tlas_end, 0u, (uint32_t)n_nodes);
             PT_HIP(c, hipGetLastError());
             PT_HIP(c, hipDeviceSynchronize());
         }
+        tree_nodes = n_nodes;
         lap("four-child form");
         if ((rc = pt_reserve(c, c->tri_leaf, std::max<size_t>(n_items, 1) * 80))) return rc;
         if (n_items && total_tris) {
@@ -888,16 +1022,14 @@ extern "C" int pt_scene_upload(pt_context* c, const pt_scene* s, int traverse, c
         }
         lap("triangle records in leaf order");
     }
-    for (size_t i = 0; i < kdn.size() && !kd_box32.empty(); i++) for (int r = 0; r < 6; r++) kdn[i].box[r] = kd_box32[6 * i + r];
     for (size_t i = 0; i < mkd.size() && !mkd_box.empty(); i++) for (int r = 0; r < 6; r++) mkd[i].box[r] = mkd_box[6 * i + r];
-    if ((rc = pt_upload(c, c->g_inv, g_inv)) || (rc = pt_upload(c, c->g_fwd, g_fwd)) || (rc = pt_upload(c, c->g_nrm, g_nrm)) ||
+    if ((rc = pt_upload(c, c->g_inv, graph.g_inv)) || (rc = pt_upload(c, c->g_fwd, graph.g_fwd)) || (rc = pt_upload(c, c->g_nrm, graph.g_nrm)) ||
         (rc = pt_upload(c, c->chain_off, chain_off)) || (rc = pt_upload(c, c->chain, chain)) || (rc = pt_upload(c, c->dfs_rank, dfs_rank)) ||
-        (rc = pt_upload(c, c->hier_rec, hier_rec)) || (rc = pt_upload(c, c->own_inv, own_inv)))
+        (rc = pt_upload(c, c->hier_rec, graph.hier_rec)) || (rc = pt_upload(c, c->own_inv, graph.own_inv)))
         return rc;
     if ((rc = pt_upload(c, c->inv, inv)) || (rc = pt_upload(c, c->fwd, fwd)) || (rc = pt_upload(c, c->nrm, nrm)) ||
         (rc = pt_upload(c, c->info, info)) || (rc = pt_upload(c, c->tri_n, tri_n)) ||
-        (rc = pt_upload(c, c->meshes, meshes)) || (rc = pt_upload(c, c->node_box, node_box32)) || (rc = pt_upload(c, c->kd_box, kd_box32)) ||
-        (rc = pt_upload(c, c->kd, kdn)) || (rc = pt_upload(c, c->kd_items, kdi)) || (rc = pt_upload(c, c->kd_ref, kd_ref32)) || (rc = pt_upload(c, c->mkd, mkd)) ||
+        (rc = pt_upload(c, c->meshes, meshes)) || (rc = pt_upload(c, c->mkd, mkd)) ||
         (rc = pt_upload(c, c->mkd_items, mkd_items)) || (rc = pt_upload(c, c->mkd_box, mkd_box)) || (rc = pt_upload(c, c->mkd_item_box, mkd_item_box)))
         return rc;
     std::vector<double> mats(s->materials, s->materials + 10 * (size_t)s->n_materials);
@@ -934,19 +1066,14 @@ extern "C" int pt_scene_upload(pt_context* c, const pt_scene* s, int traverse, c
         c->five_waves_mesh = !c->spawns && plain_meshes && instanced_tris >= 65536 && traverse == PT_TRAVERSE_HIER;
     }
     std::vector<double> lights(s->lights, s->lights + 15 * (size_t)s->n_lights);
-    {   // fork / join of refracted subtrees (pt_shade.h) needs a recursion that draws no random numbers and a dielectric material to be of use
+    {   // what the materials say about the recursion; the lights have their say in pt_set_light_flags
         bool draws = false, dielectric = false;
         for (uint32_t m = 0; m < s->n_materials; m++) {
             if (mats[10 * (size_t)m + 7] > 0.0 && mats[10 * (size_t)m + 8] > 0.0) draws = true;   // glossy reflection (material.rs:221-239)
             if (mats[10 * (size_t)m + 7] > 0.0 && mats[10 * (size_t)m + 9] > 0.0) dielectric = true;
         }
-        for (uint32_t l = 0; l < s->n_lights; l++) {
-            const double* L = &lights[15 * (size_t)l];
-            const bool empty = (L[9] == 0.0 && L[10] == 0.0 && L[11] == 0.0) || (L[12] == 0.0 && L[13] == 0.0 && L[14] == 0.0);  // light.rs:51-53
-            if (!empty) draws = true;
-        }
-        c->forkable = c->spawns && dielectric && !draws && s->n_lights <= PT_LIGHT_ROUND;
-        c->one_ray = c->spawns && !dielectric;
+        c->res.mat_draws = draws; c->res.dielectric = dielectric;
+        pt_set_light_flags(c, lights.data(), s->n_lights);
     }
     if ((rc = pt_upload(c, c->materials, mats)) || (rc = pt_upload(c, c->lights, lights))) return rc;
 
@@ -1024,13 +1151,7 @@ extern "C" int pt_scene_upload(pt_context* c, const pt_scene* s, int traverse, c
     // mirror scene +0.6 %; PORTRAYER_MESH_OCT=0 walks every triangle tree with the per-lane form again)
     v.mesh_oct = 1u;
     if (const char* e = getenv("PORTRAYER_MESH_OCT")) v.mesh_oct = atoi(e) > 0 ? 1u : 0u;
-    v.kd = (const PtKdNode*)c->kd.p; v.kd_items = (const uint32_t*)c->kd_items.p;
-    v.kd_extent = kd_extent;
-    v.kd_ref = (const uint32_t*)c->kd_ref.p; v.kd_levels = kd_levels;
-    v.node_box = traverse == PT_TRAVERSE_KD && !kdi.empty() ? (const float*)c->node_box.p : nullptr;
-    v.kd_box = traverse == PT_TRAVERSE_KD ? (const float*)c->kd_box.p : nullptr;
-    if (getenv("PORTRAYER_KD_NO_CULL")) v.kd_box = v.node_box = nullptr;  // experiment: the reference's walk as it is
-    if (const char* e = getenv("PORTRAYER_KD_CULL")) { const int m = atoi(e); if (!(m & 1)) v.kd_box = nullptr; if (!(m & 2)) v.node_box = nullptr; }  // experiment: bit 0 tree nodes, bit 1 leaf references
+    if ((rc = pt_upload_kd(c, kda, traverse == PT_TRAVERSE_KD))) return rc;
     v.mkd = mkd.empty() ? nullptr : (const PtKdNode*)c->mkd.p; v.mkd_items = (const uint32_t*)c->mkd_items.p;  // (null without KDMesh trees: the k-d walk then keeps no LDS rows for lane stacks)
     v.mkd_box = mkd_box.empty() || getenv("PORTRAYER_KD_NO_CULL") ? nullptr : (const float*)c->mkd_box.p;
     v.mkd_item_box = v.mkd_box ? (const float*)c->mkd_item_box.p : nullptr;
@@ -1041,13 +1162,21 @@ extern "C" int pt_scene_upload(pt_context* c, const pt_scene* s, int traverse, c
         v.chain_off = (const uint32_t*)c->chain_off.p; v.chain = (const uint32_t*)c->chain.p; v.dfs_rank = (const uint32_t*)c->dfs_rank.p;
         v.hier_rec = (const uint32_t*)c->hier_rec.p; v.own_inv = (const double*)c->own_inv.p;
     }
-    // a level of the four-child walk pushes up to three pending children; it covers two levels of the two-child tree in the plain
-    // collapse and at least one when nodes are opened by area
-    auto wide = [&](int depth2) { return collapse_mode ? 3 * depth2 : 3 * ((depth2 + 1) / 2); };
-    int below = std::max(wide(max_blas_depth), 3 * (max_kdm_depth + 1));  // deepest walk under a scene leaf: a mesh tree or a KDMesh tree
-    int cap = traverse == PT_TRAVERSE_KD ? 3 * (kd_depth + 1) + below + 2 : wide(tlas.depth) + below + 4;
-    v.stack_cap = std::max(cap, 8);
-    if (const char* e = getenv("PORTRAYER_STACK_CAP")) v.stack_cap = std::max(1, atoi(e));  // tests: force PT_ERR_TRAVERSAL
+    {   // what pt_scene_update needs later (pt_context::Resident)
+        pt_context::Resident& r = c->res;
+        r.traverse = traverse; r.n_nodes = n; r.n_graph = traverse == PT_TRAVERSE_HIER && n ? s->n_graph_nodes : 0u; r.n_lights = s->n_lights;
+        r.mesh_tris = mesh_tris; r.tlas_first = tlas_first; r.tlas_cap = tlas_cap; r.tlas_items = tlas_items; r.tree_nodes = tree_nodes;
+        r.tlas_leaf = tlas_leaf; r.collapse_mode = collapse_mode;
+        r.last_builder = 0; r.last_rounds = 0;
+        auto wide = [&](int depth2) { return collapse_mode ? 3 * depth2 : 3 * ((depth2 + 1) / 2); };
+        r.below = std::max(wide(max_blas_depth), 3 * (max_kdm_depth + 1));  // deepest walk under a scene leaf: a mesh tree or a KDMesh tree
+        std::vector<double> mb(6 * mesh_box.size());
+        for (size_t m = 0; m < mesh_box.size(); m++) for (int k = 0; k < 3; k++) { mb[6 * m + k] = mesh_box[m].lo[k]; mb[6 * m + 3 + k] = mesh_box[m].hi[k]; }
+        if ((rc = pt_upload(c, c->mesh_box_dev, mb))) return rc;
+        r.info = std::move(info); r.mesh_box = std::move(mesh_box); r.tri_box = std::move(tri_box);
+        r.chain_off = std::move(chain_off); r.chain = std::move(chain);
+    }
+    const int cap_rc = pt_set_stack_cap(c, tlas.depth, kda.kd_depth);
     if (textured) {
         v.mat_maps = (const int32_t*)c->mat_maps.p; v.uv_trans = (const double*)c->uv_trans.p; v.tex = (const PtTexInfo*)c->tex.p;
         v.tex_rgb = (const uint8_t*)c->tex_rgb.p; v.srgb_lut = (const double*)c->srgb_lut.p; v.tri_uv = (const double*)c->tri_uv.p;
@@ -1058,8 +1187,127 @@ extern "C" int pt_scene_upload(pt_context* c, const pt_scene* s, int traverse, c
         v.texview = (const PtTexView*)c->texview.p;
     }
     lap("upload the rest");
-    if (v.stack_cap > 4096) return pt_fail(c, PT_ERR_SCENE, "tree too deep for the traversal stack");
+    if (cap_rc) return cap_rc;
     c->have_scene = true;
+    return PT_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Scene update: the resident scene with new node matrices, lights and ambient light. Everything under a flattened node lives in model space
+// (triangle records, mesh trees, KDMesh trees, textures) and stays where it is; what depends on the matrices is recomputed by the functions
+// pt_scene_upload uses (above), and the scene-level tree is rebuilt in the place the upload reserved for it - on the host (pt_bvh_build: the
+// upload's tree) or on the device (pt_device_build_scene_tree), by the rule mesh trees follow: PORTRAYER_BUILD = host | device | auto,
+// auto takes the device from PORTRAYER_BUILD_MIN nodes on (default 65536), device from 16 on; PORTRAYER_TLAS_LEAF != 1: always the host.
+// ------------------------------------------------------------------------------------------------
+extern "C" int pt_scene_update(pt_context* c, const pt_scene_motion* mo, const pt_kdtree* kd) {
+    if (!c || !mo) return PT_ERR_ARGUMENT;
+    if (!c->have_scene) return pt_fail(c, PT_ERR_NO_SCENE, "no scene uploaded");
+    pt_context::Resident& res = c->res;
+    const uint32_t n = res.n_nodes;
+    if (mo->n_nodes != n) return pt_fail(c, PT_ERR_ARGUMENT, "n_nodes differs from the uploaded scene's");
+    if (n && (!mo->trans || !mo->invtrans || !mo->normal_trans)) return pt_fail(c, PT_ERR_ARGUMENT, "null node array");
+    if (mo->n_graph_nodes != res.n_graph) return pt_fail(c, PT_ERR_ARGUMENT, "n_graph_nodes differs from the uploaded scene's (0 unless it was uploaded with PT_TRAVERSE_HIER)");
+    if (res.n_graph && (!mo->graph_trans || !mo->graph_invtrans || !mo->graph_normal_trans))
+        return pt_fail(c, PT_ERR_ARGUMENT, "PT_TRAVERSE_HIER needs the scene graph's matrices (graph_*)");
+    if (mo->lights && mo->n_lights != res.n_lights) return pt_fail(c, PT_ERR_ARGUMENT, "n_lights differs from the uploaded scene's");
+    if (res.traverse == PT_TRAVERSE_KD && !kd) return pt_fail(c, PT_ERR_ARGUMENT, "PT_TRAVERSE_KD needs the host-built k-d tree");
+    if (res.traverse != PT_TRAVERSE_KD && kd) return pt_fail(c, PT_ERR_ARGUMENT, "a k-d tree for a scene that was not uploaded with PT_TRAVERSE_KD");
+    // the copies and kernels below are not ordered against the context's non-blocking streams
+    bool in_flight = c->aov.pending || c->rays.pending || c->radiance.pending;
+    for (const auto& sl : c->slot) in_flight = in_flight || sl.pending;
+    if (in_flight) return pt_fail(c, PT_ERR_ARGUMENT, "a render is in flight: pt_render_finish / pt_aov_finish / pt_rays_finish / pt_radiance_finish first");
+
+    // ---- everything the host computes, before the first write
+    std::vector<double> inv, fwd, nrm;
+    PtGraphArrays graph;
+    pt_pack_node_matrices(n, mo->trans, mo->invtrans, mo->normal_trans, inv, fwd, nrm);
+    if (res.n_graph) pt_pack_graph(n, res.n_graph, mo->graph_trans, mo->graph_invtrans, mo->graph_normal_trans, res.chain_off, res.chain, graph);
+    std::vector<PtBuildBox> node_box;
+    double root_lo[3], root_hi[3];
+    pt_node_world_boxes(n, mo->trans, res.info.data(), res.mesh_box, res.tri_box, res.mesh_tris, node_box, root_lo, root_hi);
+    PtKdArrays kda;
+    int rc;
+    if (res.traverse == PT_TRAVERSE_KD && (rc = pt_pack_kd(c, kd, n, node_box, kda))) {
+        if (rc == PT_ERR_SCENE) c->have_scene = false;  // as after a refused upload
+        return rc;
+    }
+    int build_mode = 2;
+    size_t device_build_min = 65536;
+    if (const char* e = getenv("PORTRAYER_BUILD")) build_mode = !strcmp(e, "host") ? 0 : (!strcmp(e, "device") ? 1 : 2);
+    if (const char* e = getenv("PORTRAYER_BUILD_MIN")) device_build_min = (size_t)std::max(16, atoi(e));
+    const bool direct = res.tlas_leaf == 1 && n < (1u << 28);
+    const bool on_device = direct && ((build_mode == 1 && n >= 16) || (build_mode == 2 && n >= device_build_min));
+    std::vector<PtBvhNode> tl_nodes;
+    std::vector<uint32_t> tl_items;
+    PtBvhRef tlas;
+    tlas.child = PT_REF_EMPTY; tlas.depth = 0;
+    if (!on_device) {
+        tlas = pt_build_scene_tree(node_box, res.tlas_leaf, direct, res.tlas_first, res.tlas_items, tl_nodes, tl_items);
+        if (tl_nodes.size() > res.tlas_cap || tl_items.size() > (direct ? 0u : n)) return pt_fail(c, PT_ERR_DEVICE, "scene tree larger than its place");  // (a tree over n leaves has at most n - 1 nodes)
+        if ((rc = pt_set_stack_cap(c, tlas.depth, kda.kd_depth))) { c->have_scene = false; return rc; }
+    }
+
+    // ---- writes
+    PT_HIP(c, hipSetDevice(c->device));
+    PT_HIP(c, hipDeviceSynchronize());  // passes whose _finish has been called may still have copies queued
+    c->have_scene = false;              // until every write below has been made
+    if ((rc = pt_upload(c, c->inv, inv)) || (rc = pt_upload(c, c->fwd, fwd)) || (rc = pt_upload(c, c->nrm, nrm))) return rc;
+    if (res.n_graph && ((rc = pt_upload(c, c->g_inv, graph.g_inv)) || (rc = pt_upload(c, c->g_fwd, graph.g_fwd)) || (rc = pt_upload(c, c->g_nrm, graph.g_nrm)) ||
+                        (rc = pt_upload(c, c->hier_rec, graph.hier_rec)) || (rc = pt_upload(c, c->own_inv, graph.own_inv))))
+        return rc;
+    if (res.traverse == PT_TRAVERSE_KD && (rc = pt_upload_kd(c, kda, true))) return rc;
+    for (int k = 0; k < 3; k++) { c->root_lo[k] = root_lo[k]; c->root_hi[k] = root_hi[k]; }
+    PtSceneView& v = c->view;
+    if (mo->lights) {
+        std::vector<double> lights(mo->lights, mo->lights + 15 * (size_t)mo->n_lights);
+        if ((rc = pt_upload(c, c->lights, lights))) return rc;
+        pt_set_light_flags(c, lights.data(), mo->n_lights);
+    }
+    if (mo->ambient) for (int k = 0; k < 3; k++) v.ambient[k] = mo->ambient[k];
+    if (on_device) {
+        PtDeviceBuildResult built;
+        PT_HIP(c, pt_device_build_scene_tree(n, (const double*)c->fwd.p, (const uint32_t*)c->info.p, (const double*)c->mesh_box_dev.p, (const double*)c->tri_v.p,
+                                             root_lo, root_hi, (PtBvhNode*)c->bvh.p, (uint32_t)res.tlas_first, nullptr, &built));
+        tlas.child = built.root; tlas.depth = built.depth;
+        if (getenv("PORTRAYER_VERBOSE")) fprintf(stderr, "[pt_scene_update] device scene tree: %u nodes, %.2f ms, %d clustering rounds, depth %d\n", n, built.ms, built.rounds, built.depth);
+        res.last_builder = 2; res.last_rounds = built.rounds;
+        if ((rc = pt_set_stack_cap(c, tlas.depth, kda.kd_depth))) return rc;  // (have_scene stays false)
+    } else {
+        res.last_builder = 1; res.last_rounds = 0;
+        if (!tl_nodes.empty()) PT_HIP(c, hipMemcpy((PtBvhNode*)c->bvh.p + res.tlas_first, tl_nodes.data(), tl_nodes.size() * sizeof(PtBvhNode), hipMemcpyHostToDevice));
+        if (!tl_items.empty()) PT_HIP(c, hipMemcpy((uint32_t*)c->bvh_items.p + res.tlas_items, tl_items.data(), tl_items.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    }
+    if (res.tlas_cap) {  // the four-child form of the new tree alone, opened as the upload opened it
+        const uint32_t first = (uint32_t)res.tlas_first, end = (uint32_t)(res.tlas_first + res.tlas_cap);
+        hipLaunchKernelGGL(pt_collapse4_kernel, dim3((unsigned)((res.tlas_cap + 255) / 256)), dim3(256), 0, nullptr, (const PtBvhNode*)c->bvh.p, (PtBvh4Node*)c->bvh4.p,
+                           (uint32_t)res.tree_nodes, res.collapse_mode, first, end, first, end);
+        PT_HIP(c, hipGetLastError());
+    }
+    PT_HIP(c, hipDeviceSynchronize());
+    v.tlas_root = tlas.child;
+    c->have_scene = true;
+    return PT_OK;
+}
+
+// tests: the bytes of device memory the context's scene buffers hold (an update must not make it grow)
+extern "C" uint64_t pt_test_scene_bytes(const pt_context* c) {
+    if (!c) return 0;
+    const PtBuf* bufs[] = {&c->inv, &c->fwd, &c->nrm, &c->info, &c->tri_v, &c->tri_e, &c->tri_leaf, &c->tri_n, &c->meshes, &c->materials, &c->lights, &c->bvh, &c->bvh4,
+                           &c->bvh_items, &c->kd, &c->kd_items, &c->mat_maps, &c->uv_trans, &c->tex, &c->tex_rgb, &c->srgb_lut, &c->tri_uv, &c->texview, &c->mkd, &c->mkd_items,
+                           &c->node_box, &c->kd_box, &c->mkd_box, &c->mkd_item_box, &c->kd_ref, &c->g_inv, &c->g_fwd, &c->g_nrm, &c->chain_off, &c->chain, &c->dfs_rank,
+                           &c->hier_rec, &c->own_inv, &c->mesh_box_dev};
+    uint64_t total = 0;
+    for (const PtBuf* b : bufs) total += b->bytes;
+    return total;
+}
+
+// tests: out[0] = stack_cap, out[1] = who built the scene-level tree last (0 the upload, 1 an update on the host, 2 an update on the device),
+// out[2] = the device build's clustering rounds, out[3] = bytes of the tree buffers (bvh, bvh4, bvh_items)
+extern "C" int pt_test_scene_info(const pt_context* c, uint64_t out[4]) {
+    if (!c || !out) return PT_ERR_ARGUMENT;
+    if (!c->have_scene) return PT_ERR_NO_SCENE;
+    out[0] = (uint64_t)c->view.stack_cap; out[1] = (uint64_t)c->res.last_builder; out[2] = (uint64_t)c->res.last_rounds;
+    out[3] = c->bvh.bytes + c->bvh4.bytes + c->bvh_items.bytes;
     return PT_OK;
 }
 

@@ -34,3 +34,14 @@ struct PtDeviceBuildResult {
 hipError_t pt_device_build_mesh_tree(const double* d_tri_v, uint32_t tri_first, uint32_t n, const double lo[3], const double hi[3], double pad, int max_leaf,
                                      PtBvhNode* d_nodes, uint32_t node_base, uint32_t* d_items, uint32_t item_base, hipStream_t stream,
                                      PtDeviceBuildResult* out);
+
+// The scene-level tree of pt_scene_update, built on the device by the same clustering over the flattened nodes' world boxes: one thread per
+// node first writes its conservative f32 box from the resident `d_fwd` (12 f64 per node), `d_info` (4 words per node: type, data, flags,
+// material), `d_mesh_box` (6 f64 per mesh: the padded model box) and `d_tri_v` (stand-alone triangles) with pt_scene_upload's formulas, then
+// the boxes are sorted by the Morton codes of their centres inside `lo` / `hi` (the root box) and clustered. Leaves are DIRECT
+// (PT_REF_LEAF | node << 3, pt_bvh.h): nothing is written to an items array. Writes exactly n - 1 nodes at d_nodes[node_base ...]; n >= 2.
+// Like every tree here it only finds candidates: equal hits are resolved by node index (by dfs_rank in the hierarchical traversal) in the
+// walks, never by tree order, so a render does not depend on which builder made the tree. Like the mesh build it reads one word back per clustering round (the clusters left) and `out` at the end; it copies nothing else.
+hipError_t pt_device_build_scene_tree(uint32_t n, const double* d_fwd, const uint32_t* d_info, const double* d_mesh_box, const double* d_tri_v,
+                                      const double lo[3], const double hi[3], PtBvhNode* d_nodes, uint32_t node_base, hipStream_t stream,
+                                      PtDeviceBuildResult* out);

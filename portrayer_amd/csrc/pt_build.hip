@@ -20,6 +20,8 @@
 // 256, 1.90 without, against 2.74 for the host tree.)
 #include "pt_build.h"
 
+#include "../../include/portrayer_hip.h"
+
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -210,104 +212,299 @@ __global__ void __launch_bounds__(PT_BUILD_BLOCK) pt_ploc_depth(uint32_t n, cons
     if ((threadIdx.x & 63) == 0) atomicMax(depth, d);
 }
 
-struct Arena {
-    char* base = nullptr;
-    size_t used = 0, cap = 0;
-    template <class T> T* take(size_t count) {
-        used = (used + 255) & ~(size_t)255;
-        T* p = reinterpret_cast<T*>(base + used);
-        used += count * sizeof(T);
-        return p;
+}  // namespace
+
+// ------------------------------------------------------------------------------------------------
+// The same clustering over BOXES instead of triangles: the scene-level tree of pt_scene_update (pt_build.h).
+// Its leaves are the flattened nodes themselves, named by the leaf reference (PT_REF_LEAF | node << 3, "direct":
+// pt_bvh.h), so nothing goes into the items array and a node is never turned into a multi-item leaf. The triangle
+// path above is left as it is; pt_ploc_nearest, pt_ploc_compact and pt_ploc_depth serve both.
+// ------------------------------------------------------------------------------------------------
+namespace {
+
+// Conservative world box of every flattened node, with pt_scene_upload's formulas and paddings (pt_api.hip: pt_node_world_boxes): the exact box of
+// a sphere, the two discs of a cylinder / cone, the transformed padded model box otherwise, a relative pad of 1e-9 on the result; f64, then
+// rounded outward to f32. The device's f64 may differ from the host's in the last bits (sqrt, the order of min / max): the 1e-4 model-unit
+// padding of every shape dominates that by many orders of magnitude, so the boxes stay conservative and no bit equality with the host's is sought.
+__global__ void __launch_bounds__(PT_BUILD_BLOCK) pt_node_box_kernel(uint32_t n, const double* __restrict__ fwd, const uint32_t* __restrict__ info,
+                                                                    const double* __restrict__ mesh_box, const double* __restrict__ tri_v,
+                                                                    PtBox6* __restrict__ out) {
+    uint32_t i = blockIdx.x * PT_BUILD_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    double M[12];
+    for (int k = 0; k < 12; k++) M[k] = fwd[12 * (size_t)i + k];
+    const int t = (int)info[4 * (size_t)i];
+    const uint32_t data = info[4 * (size_t)i + 1];
+    double blo[3], bhi[3], lo[3], hi[3];
+    bool boxed = false;
+    if (t == PT_PRIM_SPHERE) {
+        for (int r = 0; r < 3; r++) {
+            double e = 1.0001 * sqrt(M[4 * r] * M[4 * r] + M[4 * r + 1] * M[4 * r + 1] + M[4 * r + 2] * M[4 * r + 2]);
+            blo[r] = M[4 * r + 3] - e; bhi[r] = M[4 * r + 3] + e;
+        }
+        boxed = true;
+    } else if (t == PT_PRIM_CYLINDER || t == PT_PRIM_CONE) {  // discs in the model xz-plane at y = +-0.5001
+        const double top = t == PT_PRIM_CONE ? 1e-4 : 0.5001;
+        for (int r = 0; r < 3; r++) {
+            double s = sqrt(M[4 * r] * M[4 * r] + M[4 * r + 2] * M[4 * r + 2]);
+            double c0 = M[4 * r + 1] * 0.5001 + M[4 * r + 3], e0 = top * s;
+            double c1 = M[4 * r + 1] * -0.5001 + M[4 * r + 3], e1 = 0.5001 * s;
+            blo[r] = fmin(fmin(INFINITY, c0 - e0), c1 - e1); bhi[r] = fmax(fmax(-INFINITY, c0 + e0), c1 + e1);
+        }
+        boxed = true;
+    } else if (t == PT_PRIM_PLANE) {
+        lo[0] = lo[2] = -0.5001; hi[0] = hi[2] = 0.5001; lo[1] = -1e-4; hi[1] = 1e-4;
+    } else if (t == PT_PRIM_MESH || t == PT_PRIM_KDMESH) {  // the mesh's padded model box
+        for (int k = 0; k < 3; k++) { lo[k] = mesh_box[6 * (size_t)data + k]; hi[k] = mesh_box[6 * (size_t)data + 3 + k]; }
+    } else if (t == PT_PRIM_TRIANGLE) {
+        const double* v = tri_v + 9 * (size_t)data;
+        double ext = 1e-30;
+        for (int k = 0; k < 3; k++) {
+            lo[k] = fmin(v[k], fmin(v[3 + k], v[6 + k])); hi[k] = fmax(v[k], fmax(v[3 + k], v[6 + k]));
+            ext = fmax(ext, hi[k] - lo[k]);
+        }
+        for (int k = 0; k < 3; k++) { lo[k] -= 1e-6 * ext; hi[k] += 1e-6 * ext; }
+    } else {  // cube
+        lo[0] = lo[1] = lo[2] = -0.5001; hi[0] = hi[1] = hi[2] = 0.5001;
     }
+    if (!boxed) {
+        for (int r = 0; r < 3; r++) { blo[r] = INFINITY; bhi[r] = -INFINITY; }
+        for (int c = 0; c < 8; c++) {
+            double x = (c & 4) ? hi[0] : lo[0], y = (c & 2) ? hi[1] : lo[1], z = (c & 1) ? hi[2] : lo[2];
+            for (int r = 0; r < 3; r++) {
+                double v = M[4 * r] * x + M[4 * r + 1] * y + M[4 * r + 2] * z + M[4 * r + 3];
+                blo[r] = fmin(blo[r], v); bhi[r] = fmax(bhi[r], v);
+            }
+        }
+    }
+    PtBox6 b;
+    for (int k = 0; k < 3; k++) {
+        double mag = fmax(fabs(blo[k]), fabs(bhi[k]));
+        double pad = 1e-9 * fmax(bhi[k] - blo[k], mag) + 1e-300;
+        b.v[k] = pt_box_lo(blo[k] - pad);
+        b.v[3 + k] = pt_box_hi(bhi[k] + pad);
+    }
+    out[i] = b;
+}
+
+// Morton code of every box centre inside the root box
+__global__ void __launch_bounds__(PT_BUILD_BLOCK) pt_ploc_prepare_boxes(const PtBox6* __restrict__ box, uint32_t n, double lx, double ly, double lz,
+                                                                       double ix, double iy, double iz, unsigned long long* __restrict__ keys,
+                                                                       uint32_t* __restrict__ vals) {
+    uint32_t t = blockIdx.x * PT_BUILD_BLOCK + threadIdx.x;
+    if (t >= n) return;
+    const PtBox6 b = box[t];
+    unsigned long long qx = pt_quantise21(0.5 * ((double)b.v[0] + (double)b.v[3]), lx, ix);
+    unsigned long long qy = pt_quantise21(0.5 * ((double)b.v[1] + (double)b.v[4]), ly, iy);
+    unsigned long long qz = pt_quantise21(0.5 * ((double)b.v[2] + (double)b.v[5]), lz, iz);
+    keys[t] = (pt_spread21(qx) << 2) | (pt_spread21(qy) << 1) | pt_spread21(qz);
+    vals[t] = t;
+}
+
+// the clusters of the first round: the boxes in Morton order; leaf_item[k] = the flattened node behind sorted place k
+__global__ void __launch_bounds__(PT_BUILD_BLOCK) pt_ploc_init_boxes(uint32_t n, const uint32_t* __restrict__ vals, const PtBox6* __restrict__ box,
+                                                                    uint32_t* __restrict__ leaf_item, uint32_t* __restrict__ cid, PtBox6* __restrict__ cbox) {
+    uint32_t k = blockIdx.x * PT_BUILD_BLOCK + threadIdx.x;
+    if (k >= n) return;
+    leaf_item[k] = vals[k];
+    cid[k] = k | PT_PLOC_LEAF;
+    cbox[k] = box[vals[k]];
+}
+
+struct PtPlocDirectOut {
+    PtBvhNode* nodes;           // d_nodes + node_base: n - 1 of them
+    const uint32_t* leaf_item;  // per sorted place: the item its leaf names
+    uint32_t* leaf_count;       // per node: 0 (pt_ploc_depth counts every node as an inner one)
+    uint32_t* node_parent;
+    uint32_t* leaf_parent;
+    uint32_t* counter;
+    uint32_t node_base;
 };
+
+__global__ void __launch_bounds__(PT_BUILD_BLOCK) pt_ploc_merge_direct(uint32_t m, const uint32_t* __restrict__ nearest, const uint32_t* __restrict__ cid,
+                                                                      const PtBox6* __restrict__ cbox, uint32_t* __restrict__ cid_out,
+                                                                      PtBox6* __restrict__ cbox_out, uint32_t* __restrict__ keep, PtPlocDirectOut o) {
+    uint32_t i = blockIdx.x * PT_BUILD_BLOCK + threadIdx.x;
+    if (i >= m) return;
+    uint32_t j = nearest[i];
+    bool mutual = j != i && nearest[j] == i;
+    if (!mutual) { cid_out[i] = cid[i]; cbox_out[i] = cbox[i]; keep[i] = 1u; return; }
+    if (i > j) { keep[i] = 0u; return; }
+    const uint32_t a = cid[i], b = cid[j];
+    const PtBox6 ba = cbox[i], bb = cbox[j];
+    const uint32_t node = atomicAdd(o.counter, 1u);
+    PtBvhNode nd;
+    for (int k = 0; k < 3; k++) { nd.lo[k][0] = ba.v[k]; nd.hi[k][0] = ba.v[3 + k]; nd.lo[k][1] = bb.v[k]; nd.hi[k][1] = bb.v[3 + k]; }
+    nd.child0 = (a & PT_PLOC_LEAF) ? (PT_REF_LEAF | (o.leaf_item[a & ~PT_PLOC_LEAF] << 3)) : o.node_base + a;
+    nd.child1 = (b & PT_PLOC_LEAF) ? (PT_REF_LEAF | (o.leaf_item[b & ~PT_PLOC_LEAF] << 3)) : o.node_base + b;
+    nd.pad[0] = nd.pad[1] = 0u;
+    o.nodes[node] = nd;
+    o.leaf_count[node] = 0u;
+    if (a & PT_PLOC_LEAF) o.leaf_parent[a & ~PT_PLOC_LEAF] = node; else o.node_parent[a] = node;
+    if (b & PT_PLOC_LEAF) o.leaf_parent[b & ~PT_PLOC_LEAF] = node; else o.node_parent[b] = node;
+    o.node_parent[node] = PT_PLOC_NONE;
+    PtBox6 u;
+    for (int k = 0; k < 3; k++) { u.v[k] = fminf(ba.v[k], bb.v[k]); u.v[3 + k] = fmaxf(ba.v[3 + k], bb.v[3 + k]); }
+    cid_out[i] = node;
+    cbox_out[i] = u;
+    keep[i] = 1u;
+}
 
 }  // namespace
 
-#define PT_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { if (arena.base) hipFree(arena.base); return e_; } } while (0)
+// ------------------------------------------------------------------------------------------------
+// The host side of a build, shared by both: temporaries, sort, the clustering rounds, depth, read-back. What differs - the kernels that key the
+// leaves (`prepare`), seed the first round's clusters from the sorted order (`init`) and merge (`merge`) - is passed in.
+// ------------------------------------------------------------------------------------------------
+namespace {
 
-hipError_t pt_device_build_mesh_tree(const double* d_tri_v, uint32_t tri_first, uint32_t n, const double lo[3], const double hi[3], double pad, int max_leaf,
-                                     PtBvhNode* d_nodes, uint32_t node_base, uint32_t* d_items, uint32_t item_base, hipStream_t stream,
-                                     PtDeviceBuildResult* out) {
-    Arena arena;
-    if (n < 2 || max_leaf < 1 || max_leaf > 8 || n <= (uint32_t)max_leaf) return hipErrorInvalidValue;
+struct PtPlocWork {  // every temporary of a build, in one allocation
+    unsigned long long *keys_in, *keys;
+    uint32_t *vals_in, *vals;
+    PtBox6* leaf_box;   // per leaf (triangle / scene node), in input order
+    PtBox6* cbox[3];    // clusters: current, merged (with gaps), next
+    uint32_t* cid[3];
+    uint32_t *nearest, *keep, *pos, *leaf_count, *node_parent, *leaf_parent, *leaf_item;
+    uint32_t* scalars;  // [0] next node, [1] clusters left, [2] depth
+};
+
+struct PtPlocHold {  // what a build must give back however it ends
+    char* base = nullptr;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    ~PtPlocHold() {
+        if (e0) hipEventDestroy(e0);
+        if (e1) hipEventDestroy(e1);
+        if (base) hipFree(base);
+    }
+};
+
+#define PT_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return e_; } while (0)
+
+template <class Prepare, class Init, class Merge>
+hipError_t pt_ploc_build(uint32_t n, hipStream_t stream, Prepare prepare, Init init, Merge merge, PtDeviceBuildResult* out, uint32_t* root) {
+    PtPlocHold hold;
     size_t sort_bytes = 0, scan_bytes = 0;
     PT_TRY(rocprim::radix_sort_pairs(nullptr, sort_bytes, (unsigned long long*)nullptr, (unsigned long long*)nullptr, (uint32_t*)nullptr,
                                      (uint32_t*)nullptr, (size_t)n, 0u, 63u, stream));
     PT_TRY(rocprim::exclusive_scan(nullptr, scan_bytes, (uint32_t*)nullptr, (uint32_t*)nullptr, 0u, (size_t)n, rocprim::plus<uint32_t>(), stream));
     const size_t tmp_bytes = std::max(sort_bytes, scan_bytes);
-    // one allocation for every temporary
-    size_t need = 8192 + tmp_bytes + (size_t)n * (8 + 8 + 4 + 4 + 24 + 3 * 24 + 3 * 4 + 4 + 4 + 4 + 4 + 4 + 4);
-    PT_TRY(hipMalloc((void**)&arena.base, need));
-    arena.cap = need;
-    auto* keys_in = arena.take<unsigned long long>(n);
-    auto* keys = arena.take<unsigned long long>(n);
-    auto* vals_in = arena.take<uint32_t>(n);
-    auto* vals = arena.take<uint32_t>(n);
-    auto* tri_box = arena.take<PtBox6>(n);
-    PtBox6* cbox[3] = {arena.take<PtBox6>(n), arena.take<PtBox6>(n), arena.take<PtBox6>(n)};  // current, merged (with gaps), next
-    uint32_t* cid[3] = {arena.take<uint32_t>(n), arena.take<uint32_t>(n), arena.take<uint32_t>(n)};
-    auto* nearest = arena.take<uint32_t>(n);
-    auto* keep = arena.take<uint32_t>(n);
-    auto* pos = arena.take<uint32_t>(n);
-    auto* leaf_count = arena.take<uint32_t>(n);
-    auto* node_parent = arena.take<uint32_t>(n);
-    auto* leaf_parent = arena.take<uint32_t>(n);
-    auto* scalars = arena.take<uint32_t>(4);  // [0] next node, [1] clusters left, [2] depth
-    void* tmp = arena.take<char>(tmp_bytes);
-    if (arena.used > arena.cap) { hipFree(arena.base); return hipErrorOutOfMemory; }
+    // one allocation for every temporary, freed before the call returns
+    const size_t need = 8192 + tmp_bytes + (size_t)n * (8 + 8 + 4 + 4 + 24 + 3 * 24 + 3 * 4 + 7 * 4);
+    PT_TRY(hipMalloc((void**)&hold.base, need));
+    size_t used = 0;
+    auto take = [&](size_t bytes) { used = (used + 255) & ~(size_t)255; char* p = hold.base + used; used += bytes; return (void*)p; };
+    PtPlocWork w;
+    w.keys_in = (unsigned long long*)take(8 * (size_t)n); w.keys = (unsigned long long*)take(8 * (size_t)n);
+    w.vals_in = (uint32_t*)take(4 * (size_t)n); w.vals = (uint32_t*)take(4 * (size_t)n);
+    w.leaf_box = (PtBox6*)take(sizeof(PtBox6) * (size_t)n);
+    for (int k = 0; k < 3; k++) w.cbox[k] = (PtBox6*)take(sizeof(PtBox6) * (size_t)n);
+    for (int k = 0; k < 3; k++) w.cid[k] = (uint32_t*)take(4 * (size_t)n);
+    uint32_t** per_leaf[] = {&w.nearest, &w.keep, &w.pos, &w.leaf_count, &w.node_parent, &w.leaf_parent, &w.leaf_item};
+    for (uint32_t** p : per_leaf) *p = (uint32_t*)take(4 * (size_t)n);
+    w.scalars = (uint32_t*)take(16);
+    void* tmp = take(tmp_bytes);
+    if (used > need) return hipErrorOutOfMemory;
 
     int radius = PT_PLOC_RADIUS;
     if (const char* e = getenv("PORTRAYER_PLOC_RADIUS")) radius = std::min(std::max(atoi(e), 1), 128);
 
-    hipEvent_t e0, e1;
-    PT_TRY(hipEventCreate(&e0));
-    PT_TRY(hipEventCreate(&e1));
-    PT_TRY(hipEventRecord(e0, stream));
-    double inv[3];
-    for (int k = 0; k < 3; k++) inv[k] = hi[k] > lo[k] ? 1.0 / (hi[k] - lo[k]) : 0.0;
+    PT_TRY(hipEventCreate(&hold.e0));
+    PT_TRY(hipEventCreate(&hold.e1));
+    PT_TRY(hipEventRecord(hold.e0, stream));
     auto blocks = [](uint32_t count) { return dim3((count + PT_BUILD_BLOCK - 1) / PT_BUILD_BLOCK); };
-    PT_TRY(hipMemsetAsync(scalars, 0, 16, stream));
-    hipLaunchKernelGGL(pt_ploc_prepare, blocks(n), dim3(PT_BUILD_BLOCK), 0, stream, d_tri_v, tri_first, n, lo[0], lo[1], lo[2], inv[0], inv[1], inv[2], pad,
-                       keys_in, vals_in, tri_box);
+    PT_TRY(hipMemsetAsync(w.scalars, 0, 16, stream));
+    prepare(w);
     PT_TRY(hipGetLastError());
-    PT_TRY(rocprim::radix_sort_pairs(tmp, sort_bytes, keys_in, keys, vals_in, vals, (size_t)n, 0u, 63u, stream));
-    hipLaunchKernelGGL(pt_ploc_init, blocks(n), dim3(PT_BUILD_BLOCK), 0, stream, n, vals, tri_box, tri_first, d_items + item_base, cid[0], cbox[0]);
+    PT_TRY(rocprim::radix_sort_pairs(tmp, sort_bytes, w.keys_in, w.keys, w.vals_in, w.vals, (size_t)n, 0u, 63u, stream));
+    init(w);
     PT_TRY(hipGetLastError());
 
-    PtPlocOut o;
-    o.nodes = d_nodes + node_base; o.items = d_items + item_base; o.leaf_count = leaf_count; o.node_parent = node_parent; o.leaf_parent = leaf_parent;
-    o.counter = scalars; o.node_base = node_base; o.item_base = item_base; o.n = n; o.max_leaf = max_leaf;
     uint32_t m = n;
     int rounds = 0;
     while (m > 1) {
-        if (++rounds > 4096) { hipFree(arena.base); return hipErrorLaunchFailure; }  // every round merges at least the closest pair
-        hipLaunchKernelGGL(pt_ploc_nearest, blocks(m), dim3(PT_BUILD_BLOCK), 0, stream, m, radius, cbox[0], nearest);
-        hipLaunchKernelGGL(pt_ploc_merge, blocks(m), dim3(PT_BUILD_BLOCK), 0, stream, m, nearest, cid[0], cbox[0], cid[1], cbox[1], keep, o);
+        if (++rounds > 4096) return hipErrorLaunchFailure;  // every round merges at least the closest pair
+        hipLaunchKernelGGL(pt_ploc_nearest, blocks(m), dim3(PT_BUILD_BLOCK), 0, stream, m, radius, w.cbox[0], w.nearest);
+        merge(w, m);
         PT_TRY(hipGetLastError());
-        PT_TRY(rocprim::exclusive_scan(tmp, scan_bytes, keep, pos, 0u, (size_t)m, rocprim::plus<uint32_t>(), stream));
-        hipLaunchKernelGGL(pt_ploc_compact, blocks(m), dim3(PT_BUILD_BLOCK), 0, stream, m, keep, pos, cid[1], cbox[1], cid[2], cbox[2], scalars + 1);
+        PT_TRY(rocprim::exclusive_scan(tmp, scan_bytes, w.keep, w.pos, 0u, (size_t)m, rocprim::plus<uint32_t>(), stream));
+        hipLaunchKernelGGL(pt_ploc_compact, blocks(m), dim3(PT_BUILD_BLOCK), 0, stream, m, w.keep, w.pos, w.cid[1], w.cbox[1], w.cid[2], w.cbox[2], w.scalars + 1);
         PT_TRY(hipGetLastError());
-        PT_TRY(hipMemcpyAsync(&m, scalars + 1, 4, hipMemcpyDeviceToHost, stream));
+        uint32_t left = m;
+        PT_TRY(hipMemcpyAsync(&left, w.scalars + 1, 4, hipMemcpyDeviceToHost, stream));
         PT_TRY(hipStreamSynchronize(stream));
-        std::swap(cid[0], cid[2]);
-        std::swap(cbox[0], cbox[2]);
+        if (left == 0 || left >= m) return hipErrorLaunchFailure;  // (keeps the next round's launches inside the arrays whatever the device answered)
+        m = left;
+        std::swap(w.cid[0], w.cid[2]);
+        std::swap(w.cbox[0], w.cbox[2]);
     }
-    hipLaunchKernelGGL(pt_ploc_depth, blocks(n), dim3(PT_BUILD_BLOCK), 0, stream, n, node_parent, leaf_parent, leaf_count, (int*)(scalars + 2));
+    hipLaunchKernelGGL(pt_ploc_depth, blocks(n), dim3(PT_BUILD_BLOCK), 0, stream, n, w.node_parent, w.leaf_parent, w.leaf_count, (int*)(w.scalars + 2));
     PT_TRY(hipGetLastError());
-    PT_TRY(hipEventRecord(e1, stream));
-    uint32_t h[3] = {0, 0, 0}, root = 0;
-    PT_TRY(hipMemcpyAsync(h, scalars, 12, hipMemcpyDeviceToHost, stream));
-    PT_TRY(hipMemcpyAsync(&root, cid[0], 4, hipMemcpyDeviceToHost, stream));
+    PT_TRY(hipEventRecord(hold.e1, stream));
+    uint32_t h[3] = {0, 0, 0};
+    *root = 0;
+    PT_TRY(hipMemcpyAsync(h, w.scalars, 12, hipMemcpyDeviceToHost, stream));
+    PT_TRY(hipMemcpyAsync(root, w.cid[0], 4, hipMemcpyDeviceToHost, stream));
     PT_TRY(hipStreamSynchronize(stream));
     float ms = 0.0f;
-    PT_TRY(hipEventElapsedTime(&ms, e0, e1));
-    hipEventDestroy(e0);
-    hipEventDestroy(e1);
-    hipFree(arena.base);
-    if (h[0] != n - 1 || (root & PT_PLOC_LEAF)) return hipErrorLaunchFailure;  // a binary tree over n leaves has n - 1 nodes
-    out->root = node_base + root;  // n > max_leaf: the root is never a leaf
+    PT_TRY(hipEventElapsedTime(&ms, hold.e0, hold.e1));
+    if (h[0] != n - 1 || (*root & PT_PLOC_LEAF) || *root >= n - 1) return hipErrorLaunchFailure;  // a binary tree over n leaves has n - 1 nodes
     out->depth = (int)h[2];
     out->ms = ms;
     out->rounds = rounds;
+    return hipSuccess;
+}
+
+}  // namespace
+
+hipError_t pt_device_build_mesh_tree(const double* d_tri_v, uint32_t tri_first, uint32_t n, const double lo[3], const double hi[3], double pad, int max_leaf,
+                                     PtBvhNode* d_nodes, uint32_t node_base, uint32_t* d_items, uint32_t item_base, hipStream_t stream,
+                                     PtDeviceBuildResult* out) {
+    if (n < 2 || max_leaf < 1 || max_leaf > 8 || n <= (uint32_t)max_leaf) return hipErrorInvalidValue;
+    double inv[3];
+    for (int k = 0; k < 3; k++) inv[k] = hi[k] > lo[k] ? 1.0 / (hi[k] - lo[k]) : 0.0;
+    const dim3 grid((n + PT_BUILD_BLOCK - 1) / PT_BUILD_BLOCK), block(PT_BUILD_BLOCK);
+    uint32_t root = 0;
+    hipError_t e = pt_ploc_build(
+        n, stream,
+        [&](PtPlocWork& w) {
+            hipLaunchKernelGGL(pt_ploc_prepare, grid, block, 0, stream, d_tri_v, tri_first, n, lo[0], lo[1], lo[2], inv[0], inv[1], inv[2], pad, w.keys_in, w.vals_in, w.leaf_box);
+        },
+        [&](PtPlocWork& w) { hipLaunchKernelGGL(pt_ploc_init, grid, block, 0, stream, n, w.vals, w.leaf_box, tri_first, d_items + item_base, w.cid[0], w.cbox[0]); },
+        [&](PtPlocWork& w, uint32_t m) {
+            PtPlocOut o;
+            o.nodes = d_nodes + node_base; o.items = d_items + item_base; o.leaf_count = w.leaf_count; o.node_parent = w.node_parent; o.leaf_parent = w.leaf_parent;
+            o.counter = w.scalars; o.node_base = node_base; o.item_base = item_base; o.n = n; o.max_leaf = max_leaf;
+            hipLaunchKernelGGL(pt_ploc_merge, dim3((m + PT_BUILD_BLOCK - 1) / PT_BUILD_BLOCK), block, 0, stream, m, w.nearest, w.cid[0], w.cbox[0], w.cid[1], w.cbox[1], w.keep, o);
+        },
+        out, &root);
+    if (e != hipSuccess) return e;
+    out->root = node_base + root;  // n > max_leaf: the root is never a leaf
+    return hipSuccess;
+}
+
+hipError_t pt_device_build_scene_tree(uint32_t n, const double* d_fwd, const uint32_t* d_info, const double* d_mesh_box, const double* d_tri_v,
+                                      const double lo[3], const double hi[3], PtBvhNode* d_nodes, uint32_t node_base, hipStream_t stream,
+                                      PtDeviceBuildResult* out) {
+    if (n < 2 || n >= (1u << 28)) return hipErrorInvalidValue;  // a direct leaf reference holds its node in 28 bits
+    double inv[3];
+    for (int k = 0; k < 3; k++) inv[k] = hi[k] > lo[k] ? 1.0 / (hi[k] - lo[k]) : 0.0;
+    const dim3 grid((n + PT_BUILD_BLOCK - 1) / PT_BUILD_BLOCK), block(PT_BUILD_BLOCK);
+    uint32_t root = 0;
+    hipError_t e = pt_ploc_build(
+        n, stream,
+        [&](PtPlocWork& w) {
+            hipLaunchKernelGGL(pt_node_box_kernel, grid, block, 0, stream, n, d_fwd, d_info, d_mesh_box, d_tri_v, w.leaf_box);
+            hipLaunchKernelGGL(pt_ploc_prepare_boxes, grid, block, 0, stream, w.leaf_box, n, lo[0], lo[1], lo[2], inv[0], inv[1], inv[2], w.keys_in, w.vals_in);
+        },
+        [&](PtPlocWork& w) { hipLaunchKernelGGL(pt_ploc_init_boxes, grid, block, 0, stream, n, w.vals, w.leaf_box, w.leaf_item, w.cid[0], w.cbox[0]); },
+        [&](PtPlocWork& w, uint32_t m) {
+            PtPlocDirectOut o;
+            o.nodes = d_nodes + node_base; o.leaf_item = w.leaf_item; o.leaf_count = w.leaf_count; o.node_parent = w.node_parent; o.leaf_parent = w.leaf_parent;
+            o.counter = w.scalars; o.node_base = node_base;
+            hipLaunchKernelGGL(pt_ploc_merge_direct, dim3((m + PT_BUILD_BLOCK - 1) / PT_BUILD_BLOCK), block, 0, stream, m, w.nearest, w.cid[0], w.cbox[0], w.cid[1], w.cbox[1], w.keep, o);
+        },
+        out, &root);
+    if (e != hipSuccess) return e;
+    out->root = node_base + root;
     return hipSuccess;
 }

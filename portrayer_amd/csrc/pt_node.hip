@@ -252,6 +252,22 @@ extern "C" int pt_node_scene_upload(pt_node* n, const pt_scene* scene, int trave
     return PT_OK;
 }
 
+extern "C" int pt_node_scene_update(pt_node* n, const pt_scene_motion* motion, const pt_kdtree* kd) {
+    if (!n || !motion) return PT_ERR_ARGUMENT;
+    if (!n->have_scene) return node_fail(n, PT_ERR_NO_SCENE, "no scene uploaded");
+    // as for an upload: the scene buffers are read by the renders of open frames
+    if (n->frame_begun != n->frame_ended) return node_fail(n, PT_ERR_ARGUMENT, "frames are in flight: pt_node_frame_end first");
+    for (size_t r = 0; r < n->ctx.size(); r++) {
+        int rc = pt_scene_update(n->ctx[r], motion, kd);
+        if (rc != PT_OK) {
+            // rank 0 refuses before its first write, so the node's scene is still whole; later ranks hold the same scene and refuse alike, unless the device failed
+            if (r > 0 || rc == PT_ERR_SCENE || rc == PT_ERR_DEVICE) n->have_scene = false;
+            return node_fail(n, rc, "rank " + std::to_string(r) + ": " + pt_last_error(n->ctx[r]));
+        }
+    }
+    return PT_OK;
+}
+
 extern "C" int pt_node_device(const pt_node* n, int rank) { return (n && rank >= 0 && (size_t)rank < n->devices.size()) ? n->devices[rank] : -1; }
 
 static int node_check_params(pt_node* n, const pt_render_params* params) {

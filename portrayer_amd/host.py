@@ -19,7 +19,7 @@ _dp, _ip, _up, _u64p, _u8p = H._dp, H._ip, H._up, H._u64p, H._u8p
 
 EXPORTS = ["ph_last_error", "ph_scene_create", "ph_example_scene", "ph_scene_destroy", "ph_scene_counts", "ph_scene_export", "ph_scene_export_textures",
            "ph_scene_flatten", "ph_scene_kdtree", "ph_camera", "ph_obj_load", "ph_renderer_create", "ph_renderer_destroy",
-           "ph_renderer_context", "ph_renderer_ranks", "ph_renderer_node", "ph_renderer_prepare_ms", "ph_renderer_render", "ph_renderer_aov", "ph_renderer_rays", "ph_renderer_radiance", "ph_example_render_to_png", "ph_png_read", "ph_png_write", "ph_image_read", "ph_scene_graph"]
+           "ph_renderer_context", "ph_renderer_ranks", "ph_renderer_node", "ph_renderer_prepare_ms", "ph_renderer_render", "ph_renderer_aov", "ph_renderer_rays", "ph_renderer_radiance", "ph_renderer_update", "ph_scene_same_structure", "ph_example_render_to_png", "ph_png_read", "ph_png_write", "ph_image_read", "ph_scene_graph"]
 
 
 class PortrayerHostError(RuntimeError):
@@ -82,6 +82,8 @@ def lib() -> C.CDLL:
         l.ph_renderer_rays.argtypes = [vp, C.POINTER(H.PtRaysParams), _dp, _dp, C.POINTER(H.PtRaysBuffers), _dp]
         l.ph_renderer_radiance.restype = C.c_int
         l.ph_renderer_radiance.argtypes = [vp, C.POINTER(H.PtRadianceParams), _dp, _dp, _dp, _dp, _dp]
+        l.ph_renderer_update.restype = C.c_int; l.ph_renderer_update.argtypes = [vp, vp]
+        l.ph_scene_same_structure.restype = C.c_int; l.ph_scene_same_structure.argtypes = [vp, vp, C.c_char_p, C.c_size_t]
         l.ph_scene_export_textures.restype = C.c_int
         l.ph_scene_export_textures.argtypes = [vp, _u64p, _ip, _ip, _dp, _up, _u64p, _u8p, _dp, _u8p, _dp, _u8p]
         l.ph_example_render_to_png.restype = C.c_int
@@ -104,6 +106,19 @@ def _check(rc: int, what: str):
 
 def _p(a, typ):
     return None if a is None else a.ctypes.data_as(typ)
+
+
+class SameStructure:
+    """Scene.same_structure()'s answer: truthy or not, with the first difference in `reason`."""
+
+    def __init__(self, same: bool, reason: str):
+        self.same, self.reason = same, reason
+
+    def __bool__(self):
+        return self.same
+
+    def __repr__(self):
+        return "SameStructure(%r, %r)" % (self.same, self.reason)
 
 
 class Scene:
@@ -196,6 +211,14 @@ class Scene:
                                                   _p(t["tri_texcoords"], _dp), _p(t["tri_has_texcoords"], _u8p)), "ph_scene_export_textures")
             a.update(t, n_textures=ntex)
         return a
+
+    def same_structure(self, other: "Scene"):
+        """Whether `other` is this scene moved - the same flattened nodes in the same order (primitive kinds, meshes / triangles, shading, materials, paths
+        through the graph) and as many lights; transforms, lights' values and ambient light may differ - which is what Renderer.update() accepts. Returns a
+        value that is true or false and carries the first difference as `.reason` ("" when true). Needs no GPU."""
+        why = C.create_string_buffer(512)
+        rc = _check(lib().ph_scene_same_structure(self._h, other._h, why, len(why)), "ph_scene_same_structure")
+        return SameStructure(rc == 1, why.value.decode())
 
     def flatten(self) -> dict:
         n = _check(lib().ph_scene_flatten(self._h, 0, None, None, None, None, None, None), "ph_scene_flatten")
@@ -292,6 +315,13 @@ class Renderer:
         c = np.ascontiguousarray(cam10, dtype=np.float64)
         _check(lib().ph_renderer_render(self._h, _p(c, _dp), C.byref(p), _p(bg, _dp), _p(rgb, _u8p), _p(linear, _dp), C.byref(st)), "ph_renderer_render")
         return rgb, linear, st.as_dict()
+
+    def update(self, scene: Scene):
+        """The resident scene moved (pt_scene_update): `scene` must be the renderer's scene with other transforms, lights' values or ambient light
+        (Scene.same_structure). Meshes, their trees and textures stay on the device; only the scene-level tree is rebuilt. Every later call answers as
+        a new Renderer on `scene` would, bit for bit."""
+        _check(lib().ph_renderer_update(self._h, scene._h), "ph_renderer_update")
+        self.scene = scene
 
     def aov(self, cam10, width: int, height: int, rect=None, offset=(0.5, 0.5), want=("depth", "position", "normal", "node", "sub", "material"),
             into: Optional[dict] = None) -> dict:

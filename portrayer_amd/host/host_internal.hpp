@@ -48,6 +48,12 @@ struct GraphPacking {  // the ABI-4 scene-graph arrays of pt_scene (include/port
 };
 GraphPacking pack_graph(const FlatScene& flat);
 
+// Whether `b` is `a` moved: the same flattened nodes in the same order - per node the primitive kind, the mesh / triangle (numbered by first
+// use, equal in content), the shading flag, the material (numbered by first use, equal in its ten values, maps and uv transform) and the
+// path through the graph (so graph nodes, chains and dfs_rank agree) - and as many lights. Transforms, light values and the ambient
+// light may differ. Returns "" or the first difference.
+std::string structure_difference(const FlatScene& a, const FlatScene& b);
+
 struct PartitionConfig {  // leaf.rs:55-67
     size_t target_max_nodes = 3;
     long target_max_merit = 3;
@@ -88,6 +94,10 @@ class Renderer {
     void rays(const pt_rays_params& params, const double* origins, const double* directions, const pt_rays_buffers& out, double* kernel_ms);
     // Radiance along rays of the caller's own (pt_radiance): host buffers in and out; throws likewise.
     void radiance(const pt_radiance_params& params, const double* origins, const double* directions, const double* background, double* rgb, double* kernel_ms);
+    // The resident scene moved (pt_scene_update): `scene` must have the structure of the one this renderer was made from (structure_difference; throws
+    // std::invalid_argument naming the first difference) and may differ in transforms, lights' values and ambient light. Nothing but the node matrices, the
+    // lights and - in k-d mode - the rebuilt reference k-d tree goes to the device. On an error the renderer keeps its scene, unless the library says it is gone.
+    void update(const scene::HierScene& scene);
     pt_context* context() const { return ctx_; }  // rank 0's context when the scene is on a node
     pt_node* node() const { return node_; }
     const FlatScene& flat() const { return flat_; }
@@ -99,6 +109,8 @@ class Renderer {
     pt_context* ctx_ = nullptr;
     pt_node* node_ = nullptr;  // PORTRAYER_GPUS > 1: the render is tile-partitioned over the node's GPUs (one RCCL gather)
     PrepareMs prep_;
+    render::Traversal traversal_ = render::Traversal::Flat;
+    int kd_depth_ = -1;
 };
 
 // PNG codec for Image::new / Image::save (render.rs:165-208; the reference uses the `image` crate)

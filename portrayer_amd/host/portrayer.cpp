@@ -372,6 +372,63 @@ GraphPacking pack_graph(const FlatScene& flat) {
     return g;
 }
 
+std::string structure_difference(const FlatScene& a, const FlatScene& b) {
+    if (a.root.size() != b.root.size()) return "the scenes have " + std::to_string(a.root.size()) + " and " + std::to_string(b.root.size()) + " flattened nodes";
+    auto same_v = [](Vec3 x, Vec3 y) { return x.x == y.x && x.y == y.y && x.z == y.z; };
+    auto same_image = [](const texture::RgbImageBuffer* x, const texture::RgbImageBuffer* y) {
+        if (!x || !y) return x == y;
+        return x == y || (x->width == y->width && x->height == y->height && x->rgb == y->rgb);
+    };
+    auto same_mesh = [&](const primitive::MeshData* x, const primitive::MeshData* y) {
+        if (x == y) return true;
+        if (x->positions().size() != y->positions().size() || x->triangles() != y->triangles() || x->normals().size() != y->normals().size() ||
+            x->tex_coords().size() != y->tex_coords().size())
+            return false;
+        for (size_t i = 0; i < x->positions().size(); i++) if (!same_v(x->positions()[i], y->positions()[i])) return false;
+        for (size_t i = 0; i < x->normals().size(); i++) if (!same_v(x->normals()[i], y->normals()[i])) return false;
+        for (size_t i = 0; i < x->tex_coords().size(); i++) if (x->tex_coords()[i].u != y->tex_coords()[i].u || x->tex_coords()[i].v != y->tex_coords()[i].v) return false;
+        return true;
+    };
+    auto same_material = [&](const material::Material* x, const material::Material* y) {
+        if (x == y) return true;
+        if (!x || !y) return false;
+        const double rx[10] = {x->diffuse.r, x->diffuse.g, x->diffuse.b, x->specular.r, x->specular.g, x->specular.b, x->shininess, x->reflectivity, x->glossy_side_length, x->refraction_index};
+        const double ry[10] = {y->diffuse.r, y->diffuse.g, y->diffuse.b, y->specular.r, y->specular.g, y->specular.b, y->shininess, y->reflectivity, y->glossy_side_length, y->refraction_index};
+        if (std::memcmp(rx, ry, sizeof rx) != 0 || std::memcmp(x->uv_trans.m, y->uv_trans.m, sizeof x->uv_trans.m) != 0) return false;
+        return same_image(x->texture ? &x->texture->image.buffer : nullptr, y->texture ? &y->texture->image.buffer : nullptr) &&
+               same_image(x->normals ? &x->normals->buffer : nullptr, y->normals ? &y->normals->buffer : nullptr);
+    };
+    // numbered by first use, as the Renderer numbers meshes, materials and graph nodes
+    std::map<const void*, size_t> mesh_a, mesh_b, mat_a, mat_b, graph_a, graph_b;
+    auto number = [](std::map<const void*, size_t>& m, const void* p) { return m.emplace(p, m.size()).first->second; };
+    static const char* const kinds[] = {"sphere", "triangle", "mesh", "KDMesh", "plane", "cube", "cylinder", "cone"};
+    for (size_t i = 0; i < a.root.size(); i++) {
+        const FlatSceneNode &x = a.root[i], &y = b.root[i];
+        const std::string at = "flattened node " + std::to_string(i) + ": ";
+        const auto &p = x.geometry.primitive, &q = y.geometry.primitive;
+        if (p.kind != q.kind) return at + "a " + kinds[(int)p.kind & 7] + " became a " + kinds[(int)q.kind & 7];
+        if (p.kind == primitive::Primitive::MeshK || p.kind == primitive::Primitive::KDMeshK) {
+            if (number(mesh_a, p.mesh.get()) != number(mesh_b, q.mesh.get()) || !same_mesh(p.mesh.get(), q.mesh.get())) return at + "another mesh";
+            if (p.shading != q.shading) return at + "another shading";
+        } else if (p.kind == primitive::Primitive::TriangleK) {
+            const auto &s = p.triangle, &t = q.triangle;
+            bool same = same_v(s.a, t.a) && same_v(s.b, t.b) && same_v(s.c, t.c) && s.normals.has_value() == t.normals.has_value() && s.tex_coords.has_value() == t.tex_coords.has_value();
+            for (int k = 0; same && k < 3; k++) {
+                if (s.normals && !same_v((*s.normals)[k], (*t.normals)[k])) same = false;
+                if (s.tex_coords && ((*s.tex_coords)[k].u != (*t.tex_coords)[k].u || (*s.tex_coords)[k].v != (*t.tex_coords)[k].v)) same = false;
+            }
+            if (!same) return at + "another triangle";
+        }
+        if (number(mat_a, x.geometry.material.get()) != number(mat_b, y.geometry.material.get()) || !same_material(x.geometry.material.get(), y.geometry.material.get()))
+            return at + "another material";
+        if (x.path != y.path || x.chain.size() != y.chain.size()) return at + "another path through the scene graph";
+        for (size_t k = 0; k < x.chain.size(); k++)
+            if (number(graph_a, x.chain[k]) != number(graph_b, y.chain[k])) return at + "another path through the scene graph";
+    }
+    if (a.lights.size() != b.lights.size()) return "the scenes have " + std::to_string(a.lights.size()) + " and " + std::to_string(b.lights.size()) + " lights";
+    return "";
+}
+
 namespace {
 struct InfinitePlane {  // infinite_plane.rs:16-35
     Vec3 normal, point;
@@ -510,9 +567,32 @@ static std::vector<int> node_devices(int device) {
     return devs;
 }
 
+// what the constructor and update() hand the library alike: the lights as 15 doubles each, the k-d tree as the ABI's view of `t` (which must outlive it)
+static std::vector<double> pack_lights(const std::vector<light::Light>& all) {
+    std::vector<double> lights;
+    for (const auto& l : all) {
+        const double row[15] = {l.position.x, l.position.y, l.position.z, l.color.r, l.color.g, l.color.b, l.falloff.c0, l.falloff.c1, l.falloff.c2,
+                                l.area.a.x, l.area.a.y, l.area.a.z, l.area.b.x, l.area.b.y, l.area.b.z};
+        lights.insert(lights.end(), row, row + 15);
+    }
+    return lights;
+}
+static pt_kdtree kd_abi(const KdTree& t) {
+    pt_kdtree kd;
+    std::memset(&kd, 0, sizeof kd);
+    kd.n_nodes = (uint32_t)t.axis.size();
+    kd.axis = t.axis.data(); kd.plane = t.plane.data(); kd.front = t.front.data(); kd.back = t.back.data();
+    kd.first = t.first.data(); kd.count = t.count.data();
+    kd.n_items = (uint32_t)t.items.size(); kd.leaf_items = t.items.data();
+    kd.root_min[0] = t.root_min.x; kd.root_min[1] = t.root_min.y; kd.root_min[2] = t.root_min.z;
+    kd.root_max[0] = t.root_max.x; kd.root_max[1] = t.root_max.y; kd.root_max[2] = t.root_max.z;
+    kd.max_depth = t.max_depth;
+    return kd;
+}
+
 static double ms_since(std::chrono::steady_clock::time_point t) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count(); }
 
-Renderer::Renderer(const scene::HierScene& hier, render::Traversal traversal, int kd_depth, int device) {
+Renderer::Renderer(const scene::HierScene& hier, render::Traversal traversal, int kd_depth, int device) : traversal_(traversal), kd_depth_(kd_depth) {
     auto t_flat = std::chrono::steady_clock::now();
     flat_ = FlatScene::from(hier);
     prep_.flatten = ms_since(t_flat);
@@ -637,12 +717,7 @@ Renderer::Renderer(const scene::HierScene& hier, render::Traversal traversal, in
             std::memcpy(&mesh_kd_bounds_inv[16 * mi], rb.invtrans.m, 128);
         }
     }
-    std::vector<double> lights;
-    for (const auto& l : flat_.lights) {
-        const double row[15] = {l.position.x, l.position.y, l.position.z, l.color.r, l.color.g, l.color.b, l.falloff.c0, l.falloff.c1, l.falloff.c2,
-                                l.area.a.x, l.area.a.y, l.area.a.z, l.area.b.x, l.area.b.y, l.area.b.z};
-        lights.insert(lights.end(), row, row + 15);
-    }
+    std::vector<double> lights = pack_lights(flat_.lights);
     pt_scene s;
     std::memset(&s, 0, sizeof s);
     s.n_nodes = (uint32_t)n;
@@ -712,15 +787,7 @@ Renderer::Renderer(const scene::HierScene& hier, render::Traversal traversal, in
             auto t_kd = std::chrono::steady_clock::now();
             KdTree t = kd_scene_tree(flat_, kd_depth < 0 ? 10 : (size_t)kd_depth);
             prep_.kd_build = ms_since(t_kd);
-            pt_kdtree kd;
-            std::memset(&kd, 0, sizeof kd);
-            kd.n_nodes = (uint32_t)t.axis.size();
-            kd.axis = t.axis.data(); kd.plane = t.plane.data(); kd.front = t.front.data(); kd.back = t.back.data();
-            kd.first = t.first.data(); kd.count = t.count.data();
-            kd.n_items = (uint32_t)t.items.size(); kd.leaf_items = t.items.data();
-            kd.root_min[0] = t.root_min.x; kd.root_min[1] = t.root_min.y; kd.root_min[2] = t.root_min.z;
-            kd.root_max[0] = t.root_max.x; kd.root_max[1] = t.root_max.y; kd.root_max[2] = t.root_max.z;
-            kd.max_depth = t.max_depth;
+            pt_kdtree kd = kd_abi(t);
             upload(PT_TRAVERSE_KD, &kd);
         } else if (traversal == render::Traversal::Hier) {
             // scene.rs:80-120: the hierarchy itself. Every SceneNode on a path gets an index; a flattened node's chain
@@ -771,6 +838,51 @@ void Renderer::render(const camera::CameraSettings& cam, uint32_t width, uint32_
         return;
     }
     check(ctx_, pt_render(ctx_, &pc, background, &p, rgb, linear, stats), "pt_render");
+}
+
+void Renderer::update(const scene::HierScene& hier) {
+    FlatScene moved = FlatScene::from(hier);
+    const std::string why = structure_difference(flat_, moved);
+    if (!why.empty()) throw std::invalid_argument("Renderer::update: the scene has another structure than the resident one: " + why);
+    const size_t n = moved.root.size();
+    std::vector<double> trans(16 * n), inv(16 * n), nrm(16 * n), lights;
+    for (size_t i = 0; i < n; i++) {
+        std::memcpy(&trans[16 * i], moved.root[i].trans.m, 128);
+        std::memcpy(&inv[16 * i], moved.root[i].invtrans.m, 128);
+        std::memcpy(&nrm[16 * i], moved.root[i].normal_trans.m, 128);
+    }
+    lights = pack_lights(moved.lights);
+    if (lights.empty()) lights.resize(15);  // (a pointer to give: lights = NULL means "keep the resident ones")
+    const double ambient[3] = {moved.ambient.r, moved.ambient.g, moved.ambient.b};
+    pt_scene_motion mo;
+    std::memset(&mo, 0, sizeof mo);
+    mo.n_nodes = (uint32_t)n;
+    mo.trans = trans.data(); mo.invtrans = inv.data(); mo.normal_trans = nrm.data();
+    mo.n_lights = (uint32_t)moved.lights.size(); mo.lights = lights.data(); mo.ambient = ambient;
+    GraphPacking gp;
+    KdTree t;
+    pt_kdtree kd;
+    std::memset(&kd, 0, sizeof kd);
+    if (traversal_ == render::Traversal::Hier && n) {
+        gp = pack_graph(moved);
+        mo.n_graph_nodes = gp.n_graph_nodes;
+        mo.graph_trans = gp.trans.data(); mo.graph_invtrans = gp.invtrans.data(); mo.graph_normal_trans = gp.normal_trans.data();
+    } else if (traversal_ == render::Traversal::KdTree) {
+        t = kd_scene_tree(moved, kd_depth_ < 0 ? 10 : (size_t)kd_depth_);
+        kd = kd_abi(t);
+    }
+    const pt_kdtree* kdp = traversal_ == render::Traversal::KdTree ? &kd : nullptr;
+    if (node_) {
+        int rc = pt_node_scene_update(node_, &mo, kdp);
+        if (rc != PT_OK) {
+            std::string msg = std::string("pt_node_scene_update failed (") + std::to_string(rc) + "): " + pt_node_last_error(node_);
+            if (rc == PT_ERR_SCENE) throw Panic(msg);
+            throw std::runtime_error(msg);
+        }
+    } else {
+        check(ctx_, pt_scene_update(ctx_, &mo, kdp), "pt_scene_update");
+    }
+    flat_ = std::move(moved);
 }
 
 void Renderer::rays(const pt_rays_params& params, const double* origins, const double* directions, const pt_rays_buffers& out, double* kernel_ms) {

@@ -67,6 +67,17 @@ pub struct PtKdTree {                      // pt_kdtree
     pub root_min: [f64; 3], pub root_max: [f64; 3], pub max_depth: i32,
 }
 
+#[repr(C)]
+pub struct PtSceneMotion {                 // pt_scene_motion: the resident scene's new matrices, lights and ambient light (pt_scene_update)
+    pub n_nodes: u32,
+    pub trans: *const f64, pub invtrans: *const f64, pub normal_trans: *const f64,
+    pub n_graph_nodes: u32,
+    pub graph_trans: *const f64, pub graph_invtrans: *const f64, pub graph_normal_trans: *const f64,
+    pub n_lights: u32,
+    pub lights: *const f64,
+    pub ambient: *const f64,
+}
+
 #[repr(C)] pub struct PtCamera { pub eye: [f64; 3], pub view_to_world: [f64; 16], pub fov_factor: f64, pub aspect_ratio: f64, pub width: f64, pub height: f64 }
 #[repr(C)] pub struct PtRect { pub x0: u32, pub y0: u32, pub x1: u32, pub y1: u32 }
 
@@ -106,6 +117,8 @@ extern "C" {
     pub fn pt_context_destroy(ctx: *mut PtContext);
     pub fn pt_last_error(ctx: *const PtContext) -> *const c_char;
     pub fn pt_scene_upload(ctx: *mut PtContext, scene: *const PtScene, traverse: c_int, kd: *const PtKdTree) -> c_int;
+    // move the resident scene: new node matrices, lights, ambient light; only the scene-level tree is rebuilt
+    pub fn pt_scene_update(ctx: *mut PtContext, motion: *const PtSceneMotion, kd: *const PtKdTree) -> c_int;
     pub fn pt_render(ctx: *mut PtContext, camera: *const PtCamera, background: *const f64, params: *const PtRenderParams,
                      rgb: *mut u8, linear: *mut f64, stats: *mut PtStats) -> c_int;
     pub fn pt_render_device(ctx: *mut PtContext, camera: *const PtCamera, d_background: *const f64, params: *const PtRenderParams,
@@ -135,6 +148,7 @@ extern "C" {
     pub fn pt_node_destroy(node: *mut PtNode);
     pub fn pt_node_last_error(node: *const PtNode) -> *const c_char;
     pub fn pt_node_scene_upload(node: *mut PtNode, scene: *const PtScene, traverse: c_int, kd: *const PtKdTree) -> c_int;
+    pub fn pt_node_scene_update(node: *mut PtNode, motion: *const PtSceneMotion, kd: *const PtKdTree) -> c_int;
     pub fn pt_node_render(node: *mut PtNode, camera: *const PtCamera, background: *const f64, params: *const PtRenderParams,
                           rgb: *mut u8, stats: *mut PtStats) -> c_int;
 }
