@@ -233,6 +233,34 @@ typedef struct {
 } pt_scene_motion;
 int pt_scene_update(pt_context *ctx, const pt_scene_motion *motion, const pt_kdtree *kd);
 
+/* Deforms resident meshes: new vertex positions (and normals) under the topology the mesh was uploaded with, then the pt_scene_update above (every instance's
+ * world box, the root box, the scene-level tree and - in PT_TRAVERSE_KD - `kd` depend on the mesh's new box; `motion` is required and may carry the matrices
+ * already resident). After PT_OK every entry point answers as if pt_scene_upload had been called with the original pt_scene carrying these positions, normals,
+ * mesh bounds and the motion's arrays: the same bits in pixels, linear means, aov / rays / radiance results (`sub` included), the ray counters primary, shadow,
+ * reflect, refract, hits, depth11_skipped and kernel_mode / kernel_variant (tree-visit counters may differ). Only the vertices cross to the device
+ * (n_vertices x 24 bytes, 48 with normals): triangle records are expanded there through the resident indices, and the mesh's tree - which keeps its place in the
+ * tree arrays - is REFITTED (rebuild = 0: same topology, every box recomputed bottom-up; a large deformation costs walk speed, never a result) or REBUILT by
+ * the device builder in place (rebuild = 1: only for a tree the device built at upload, PORTRAYER_BUILD). Indices, texture coordinates, textures, materials,
+ * node paths and the trees of meshes not named stay resident and untouched. The first deform of a context allocates what it needs (the indices on the device,
+ * a parent index and an arrival counter per tree node, a staging buffer for vertices); later deforms of the same meshes allocate nothing. Synchronous.
+ * n_deforms = 0 is a plain pt_scene_update.
+ * Errors, all before the first write (the resident scene stays usable): PT_ERR_ARGUMENT (NULL context / deforms / positions / bounds_invtrans / motion; a mesh
+ * index out of range or named twice; normals for a mesh uploaded without; a mesh with a KDMesh tree (mesh_kd_root >= 0: the reference's own structure, built
+ * by the host from the positions); rebuild = 1 for a tree the upload built on the host; a non-finite coordinate or a mesh box beyond +-1e18; everything
+ * pt_scene_update refuses about motion or kd, a pass in flight included), PT_ERR_NO_SCENE. PT_ERR_SCENE as for pt_scene_update: the context then has NO scene. */
+typedef struct {
+    uint32_t mesh;                  /* index into the uploaded scene's meshes                                   */
+    const double *positions;        /* n_vertices x 3, the vertex count the mesh was uploaded with               */
+    const double *normals;          /* n_vertices x 3, or NULL: the resident normals stay                        */
+    const double *bounds_invtrans;  /* 16 doubles: BoundingBox::invtrans of the NEW mesh AABB (as pt_scene.mesh_bounds_invtrans) */
+    int32_t rebuild;                /* 0: refit the resident tree; 1: rebuild it with the device builder, in place */
+} pt_mesh_deform;
+int pt_scene_deform(pt_context *ctx, uint32_t n_deforms, const pt_mesh_deform *deforms,
+                    const pt_scene_motion *motion, const pt_kdtree *kd);
+/* Whether pt_scene_deform accepts rebuild = 1 for this mesh of the resident scene: 1 (the device built its tree at upload, so its place has the worst-case
+ * size), 0 (the host built it: refit only), PT_ERR_ARGUMENT (NULL context, mesh index out of range), PT_ERR_NO_SCENE. Needs no device work. */
+int pt_scene_mesh_rebuildable(const pt_context *ctx, uint32_t mesh);
+
 /* Renders with host buffers. background: per pt_render_params.background_rows. rgb: height x width
  * x 3 bytes, only pixels of the slice that belong to this tile rank are written. linear (optional):
  * height x width x 3 doubles, the sample mean before gamma (render.rs:45). */
@@ -388,6 +416,9 @@ pt_context *pt_node_context(pt_node *node, int rank);
 int pt_node_scene_upload(pt_node *node, const pt_scene *scene, int traverse, const pt_kdtree *kd);
 /* pt_scene_update on every rank; refused with PT_ERR_ARGUMENT while frames are open (pt_node_frame_begin without its pt_node_frame_end) */
 int pt_node_scene_update(pt_node *node, const pt_scene_motion *motion, const pt_kdtree *kd);
+/* pt_scene_deform on every rank, refused alike while frames are open */
+int pt_node_scene_deform(pt_node *node, uint32_t n_deforms, const pt_mesh_deform *deforms,
+                         const pt_scene_motion *motion, const pt_kdtree *kd);
 /* Like pt_render (host buffers; params->tile_rank / tile_ranks must be 0 / 1: the node partitions the tiles itself).
  * stats: counters summed over the ranks, kernel_ms of the slowest rank, total_ms of the whole call. */
 int pt_node_render(pt_node *node, const pt_camera *camera, const double *background, const pt_render_params *params,

@@ -126,6 +126,15 @@ int ph_renderer_update(ph_renderer *r, const ph_scene *scene);
 /* 1 if `b` is `a` moved (same flattened nodes in the same order: primitive kinds, meshes / triangles, shading, materials, paths through the graph; as many
  * lights), 0 if not, with the first difference in `why` (n bytes, optional), or a negative PH_ERR_* code. Needs no GPU. */
 int ph_scene_same_structure(const ph_scene *a, const ph_scene *b, char *why, size_t n);
+/* Resident meshes deformed (pt_scene_deform): `scene` must have the topology of the one the renderer was created from - ph_scene_same_topology: the same
+ * structure, except that a mesh may differ in the values of its vertex positions and normals; PH_ERR_ARGUMENT names the first difference otherwise and the
+ * renderer keeps its scene. The meshes whose positions or normals differ in a bit are sent - vertices and bounds only; indices, texture coordinates and
+ * textures stay on the device - and their trees are refitted there; rebuild != 0 rebuilds the trees the device built at upload instead and refits the
+ * others. Transforms, lights and ambient light move as in ph_renderer_update. Meshes with KDMesh trees cannot be deformed (PH_ERR_RUNTIME). */
+int ph_renderer_deform(ph_renderer *r, const ph_scene *scene, int rebuild);
+/* As ph_scene_same_structure, for ph_renderer_deform: vertex count, triangles, texture coordinates and presence of normals of a mesh must be equal, the
+ * values of positions and normals may differ. */
+int ph_scene_same_topology(const ph_scene *a, const ph_scene *b, char *why, size_t n);
 
 /* Radiance along rays of the caller's own (see pt_radiance): n x 3 f64 origins and directions in world space, `background` 3 doubles or n x 3
  * (params->background_per_ray), rgb n x 3 f64 out: one linear sample of Ray::color per ray. A renderer spread over a node runs the pass on rank 0's context. */

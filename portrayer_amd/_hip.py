@@ -95,6 +95,11 @@ class PtSceneMotion(C.Structure):
                 ("n_lights", C.c_uint32), ("lights", _dp), ("ambient", _dp)]
 
 
+class PtMeshDeform(C.Structure):
+    """pt_mesh_deform: one resident mesh's new vertex positions (and normals), its new bounds, and whether its tree is refitted or rebuilt."""
+    _fields_ = [("mesh", C.c_uint32), ("positions", _dp), ("normals", _dp), ("bounds_invtrans", _dp), ("rebuild", C.c_int32)]
+
+
 class PtRaysParams(C.Structure):
     _fields_ = [("n", C.c_uint64), ("any_hit", C.c_int32), ("reorder", C.c_int32)]
 
@@ -133,7 +138,7 @@ EXPORTS = ["pt_abi_version", "pt_device_count", "pt_context_create", "pt_context
            "pt_node_scene_upload", "pt_node_render", "pt_node_upload_background", "pt_node_render_resident", "pt_node_download_image",
            "pt_node_device", "pt_node_frame_begin", "pt_node_frame_end", "pt_node_frames_in_flight", "pt_node_last_frame_host_ms", "pt_node_last_frame_rank_kernel_ms", "pt_test_pow_host", "pt_test_libm_host",
            "pt_aov", "pt_aov_device", "pt_aov_finish", "pt_rays", "pt_rays_device", "pt_rays_finish",
-           "pt_radiance", "pt_radiance_device", "pt_radiance_finish", "pt_scene_update", "pt_node_scene_update", "pt_test_scene_bytes", "pt_test_scene_info"]
+           "pt_radiance", "pt_radiance_device", "pt_radiance_finish", "pt_scene_update", "pt_node_scene_update", "pt_scene_deform", "pt_node_scene_deform", "pt_scene_mesh_rebuildable", "pt_test_scene_bytes", "pt_test_scene_info"]
 
 
 def header_functions():
@@ -170,6 +175,12 @@ def lib() -> C.CDLL:
         l.pt_scene_update.argtypes = [C.c_void_p, C.POINTER(PtSceneMotion), C.POINTER(PtKdTree)]
         l.pt_node_scene_update.restype = C.c_int
         l.pt_node_scene_update.argtypes = [C.c_void_p, C.POINTER(PtSceneMotion), C.POINTER(PtKdTree)]
+        l.pt_scene_deform.restype = C.c_int
+        l.pt_scene_deform.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(PtMeshDeform), C.POINTER(PtSceneMotion), C.POINTER(PtKdTree)]
+        l.pt_node_scene_deform.restype = C.c_int
+        l.pt_node_scene_deform.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(PtMeshDeform), C.POINTER(PtSceneMotion), C.POINTER(PtKdTree)]
+        l.pt_scene_mesh_rebuildable.restype = C.c_int
+        l.pt_scene_mesh_rebuildable.argtypes = [C.c_void_p, C.c_uint32]
         l.pt_test_scene_bytes.restype = C.c_uint64
         l.pt_test_scene_bytes.argtypes = [C.c_void_p]
         l.pt_test_scene_info.restype = C.c_int
@@ -307,6 +318,11 @@ class Context:
 
     def update(self, motion: "PtSceneMotion", kd: Optional[PtKdTree] = None):
         self.check(lib().pt_scene_update(self._h, C.byref(motion), C.byref(kd) if kd is not None else None), "pt_scene_update")
+
+    def deform(self, deforms, motion: "PtSceneMotion", kd: Optional[PtKdTree] = None):
+        """pt_scene_deform with a list of PtMeshDeform"""
+        arr = (PtMeshDeform * max(len(deforms), 1))(*deforms)
+        self.check(lib().pt_scene_deform(self._h, len(deforms), arr, C.byref(motion), C.byref(kd) if kd is not None else None), "pt_scene_deform")
 
     def render(self, cam: PtCamera, background: np.ndarray, params: PtRenderParams, rgb: np.ndarray, linear: Optional[np.ndarray] = None) -> dict:
         st = PtStats()

@@ -88,7 +88,9 @@ __global__ void __launch_bounds__(256) pt_copy1_kernel(const double2* __restrict
 // child at three entries). Mesh trees only: on scene-level trees the grandchildren form measured better (transmission-refraction
 // 3.32 against 3.72 node visits per ray). PORTRAYER_COLLAPSE=plain | mesh | area.
 // One thread per two-child node; entries of the array that no tree uses (the device build reserves n - 1 nodes per mesh
-// and may need fewer) hold garbage, are never referenced, and are only kept from reading out of bounds.
+// and may need fewer) are never referenced and are only kept from reading out of bounds. In a device-built tree's place they
+// hold 0xFF bytes, i.e. PT_REF_EMPTY children: pt_scene_upload and a rebuild by pt_scene_deform fill the place before the
+// builder runs, and pt_parent_kernel / pt_refit_kernel (pt_build.hip), which scan the whole place, rely on that - the memset is not redundant.
 // tri_leaf: the edge record of every triangle named by a slot of the items array, in slot order (80 bytes a slot: 9 f64 + the triangle's index), so
 // that a mesh leaf's triangles lie side by side and the wave-uniform walks fetch them without going through bvh_items first.
 __global__ void __launch_bounds__(256) pt_tri_leaf_kernel(const uint32_t* __restrict__ items, uint32_t n_items, const double* __restrict__ tri_e, uint32_t n_tris,
@@ -325,8 +327,26 @@ struct pt_context {
         int below = 0;                         // stack_cap: the deepest walk under a scene leaf
         int last_builder = 0, last_rounds = 0; // tests: who built the scene-level tree last (0 the upload, 1 an update on the host, 2 on the device) and in how many clustering rounds
         bool mat_draws = false, dielectric = false;  // forkable: what the materials say
+        // pt_scene_deform: where every mesh's tree sits in bvh / bvh4 (nodes) and bvh_items / tri_leaf (items), who built it and how deep it is; the
+        // meshes' indices as uploaded (they go to the device with the first deform) and the PtMeshInfo records (bbox_inv and blas_root change)
+        struct MeshPlace {
+            uint32_t node_first = 0, node_count = 0, item_first = 0, item_count = 0, n_verts = 0;
+            int depth = 0;                 // of the two-child tree
+            bool device_built = false;     // its place has the device builder's worst-case size: it can be rebuilt there
+            bool has_normals = false;
+            bool parents_valid = false;    // tree_parent holds this tree's parents (set by the first refit, cleared by a rebuild)
+        };
+        std::vector<MeshPlace> place;
+        std::vector<uint32_t> indices;
+        std::vector<PtMeshInfo> meshes;
+        bool indices_resident = false;     // mesh_idx holds `indices`
+        int blas_leaf = 2, max_kdm_depth = 0;
+        bool any_normals = false;          // tri_n holds a record per triangle (some node shades smoothly)
     } res;
     PtBuf mesh_box_dev;  // the per-mesh boxes again, 6 f64 each, for the device build of the scene-level tree
+    // pt_scene_deform, allocated by the first deform of the context: the meshes' indices, a parent index and an arrival counter per tree node (the refit),
+    // and the staging buffer the new vertices are copied to
+    PtBuf mesh_idx, tree_parent, tree_arrive, deform_stage;
     double root_lo[3] = {0.0, 0.0, 0.0}, root_hi[3] = {0.0, 0.0, 0.0};  // the scene tree's root box: union of the flattened nodes' world boxes (reorder = 1 quantises origins inside it)
 };
 #define PT_SLOT_BYTES (256 + sizeof(PtCounters))
@@ -392,7 +412,7 @@ extern "C" void pt_context_destroy(pt_context* c) {
     if (!c) return;
     hipSetDevice(c->device);
     PtBuf* bufs[] = {&c->inv, &c->fwd, &c->nrm, &c->info, &c->tri_v, &c->tri_e, &c->tri_leaf, &c->tri_n, &c->meshes, &c->materials, &c->lights,
-                     &c->bvh, &c->bvh4, &c->bvh_items, &c->kd, &c->kd_items, &c->mat_maps, &c->uv_trans, &c->tex, &c->tex_rgb, &c->srgb_lut, &c->tri_uv, &c->texview, &c->mkd, &c->mkd_items, &c->slot[0].spill, &c->slot[0].stack_spill, &c->slot[0].accum, &c->slot[0].misc, &c->slot[1].spill, &c->slot[1].stack_spill, &c->slot[1].accum, &c->slot[1].misc, &c->bg, &c->rgb, &c->linear, &c->misc, &c->node_box, &c->kd_box, &c->mkd_box, &c->mkd_item_box, &c->kd_ref, &c->g_inv, &c->g_fwd, &c->g_nrm, &c->chain_off, &c->chain, &c->dfs_rank, &c->hier_rec, &c->own_inv, &c->mesh_box_dev};
+                     &c->bvh, &c->bvh4, &c->bvh_items, &c->kd, &c->kd_items, &c->mat_maps, &c->uv_trans, &c->tex, &c->tex_rgb, &c->srgb_lut, &c->tri_uv, &c->texview, &c->mkd, &c->mkd_items, &c->slot[0].spill, &c->slot[0].stack_spill, &c->slot[0].accum, &c->slot[0].misc, &c->slot[1].spill, &c->slot[1].stack_spill, &c->slot[1].accum, &c->slot[1].misc, &c->bg, &c->rgb, &c->linear, &c->misc, &c->node_box, &c->kd_box, &c->mkd_box, &c->mkd_item_box, &c->kd_ref, &c->g_inv, &c->g_fwd, &c->g_nrm, &c->chain_off, &c->chain, &c->dfs_rank, &c->hier_rec, &c->own_inv, &c->mesh_box_dev, &c->mesh_idx, &c->tree_parent, &c->tree_arrive, &c->deform_stage};
     for (PtBuf* b : bufs) if (b->p) hipFree(b->p);
     if (c->aov.queued) { if (c->aov.closed) hipEventSynchronize(c->aov.copy_done); else hipStreamSynchronize(c->aov.stream); }  // (pt_aov_wait)
     for (PtBuf* b : {&c->aov.stack_spill, &c->aov.misc, &c->aov.out[0], &c->aov.out[1], &c->aov.out[2], &c->aov.out[3], &c->aov.out[4], &c->aov.out[5]}) if (b->p) hipFree(b->p);
@@ -524,6 +544,15 @@ static void pt_pack_graph(uint32_t n, uint32_t g, const double* graph_trans, con
             if (g_ident[gi]) rec[0] |= 1u << (8 + k);
         }
     }
+}
+
+// The box of a mesh's vertices and its largest extent (floored at 1e-30): triangle boxes are padded by 1e-7 ext, the mesh's own box by 1e-5 ext.
+// pt_scene_upload and pt_scene_deform both call this.
+static double pt_mesh_vertex_box(const double* pos, uint64_t n_verts, PtBuildBox* mb) {
+    *mb = pt_bvh_detail::empty_box();
+    for (uint64_t v = 0; v < n_verts; v++)
+        for (int k = 0; k < 3; k++) { mb->lo[k] = std::min(mb->lo[k], pos[3 * v + k]); mb->hi[k] = std::max(mb->hi[k], pos[3 * v + k]); }
+    return std::max(std::max(mb->hi[0] - mb->lo[0], mb->hi[1] - mb->lo[1]), std::max(mb->hi[2] - mb->lo[2], 1e-30));
 }
 
 // the padded model box of a stand-alone triangle (9 f64)
@@ -788,15 +817,14 @@ extern "C" int pt_scene_upload(pt_context* c, const pt_scene* s, int traverse, c
     if (const char* e = getenv("PORTRAYER_BUILD_MIN")) device_build_min = (size_t)std::max(16, atoi(e));
     struct DeviceMesh { uint32_t m, t0, count; double lo[3], hi[3], pad; };
     std::vector<DeviceMesh> device_meshes;
+    std::vector<pt_context::Resident::MeshPlace> place(s->n_meshes);
     for (uint32_t m = 0; m < s->n_meshes; m++) {
         uint64_t v0 = s->mesh_vert_off[m], v1 = s->mesh_vert_off[m + 1], t0 = s->mesh_tri_off[m], t1 = s->mesh_tri_off[m + 1];
         if (v1 <= v0) return pt_fail(c, PT_ERR_SCENE, "meshes must have at least one vertex (mesh.rs:71)");
         const double* pos = s->mesh_positions + 3 * v0;
         const double* nrm = (s->mesh_normals && s->mesh_has_normals && s->mesh_has_normals[m]) ? s->mesh_normals + 3 * v0 : nullptr;
-        PtBuildBox mb = pt_bvh_detail::empty_box();
-        for (uint64_t v = 0; v < v1 - v0; v++)
-            for (int k = 0; k < 3; k++) { mb.lo[k] = std::min(mb.lo[k], pos[3 * v + k]); mb.hi[k] = std::max(mb.hi[k], pos[3 * v + k]); }
-        double ext = std::max(std::max(mb.hi[0] - mb.lo[0], mb.hi[1] - mb.lo[1]), std::max(mb.hi[2] - mb.lo[2], 1e-30));
+        PtBuildBox mb;
+        const double ext = pt_mesh_vertex_box(pos, v1 - v0, &mb);
         const bool on_device = (build_mode == 1 && t1 - t0 >= 16) || (build_mode == 2 && t1 - t0 >= device_build_min);
         std::vector<PtBuildBox> boxes(on_device ? 0 : t1 - t0);
         std::vector<uint32_t> ids(on_device ? 0 : t1 - t0);
@@ -819,6 +847,9 @@ extern "C" int pt_scene_upload(pt_context* c, const pt_scene* s, int traverse, c
         }
         PtBvhRef ref;
         ref.child = PT_REF_EMPTY; ref.depth = 0;
+        pt_context::Resident::MeshPlace& pl = place[m];
+        pl.n_verts = (uint32_t)(v1 - v0); pl.has_normals = nrm != nullptr; pl.device_built = on_device;
+        pl.node_first = (uint32_t)bvh.size(); pl.item_first = (uint32_t)items.size();
         if (on_device) {  // built after the triangles are in HBM (below); the root is filled in then
             DeviceMesh dm;
             dm.m = m; dm.t0 = (uint32_t)t0; dm.count = (uint32_t)(t1 - t0);
@@ -827,6 +858,7 @@ extern "C" int pt_scene_upload(pt_context* c, const pt_scene* s, int traverse, c
             device_meshes.push_back(dm);
         } else {
             ref = pt_bvh_build(boxes.data(), ids.data(), boxes.size(), blas_leaf, bvh, items);
+            pl.node_count = (uint32_t)bvh.size() - pl.node_first; pl.item_count = (uint32_t)items.size() - pl.item_first; pl.depth = ref.depth;
         }
         max_blas_depth = std::max(max_blas_depth, ref.depth);
         PtMeshInfo& mi = meshes[m];
@@ -994,10 +1026,15 @@ extern "C" int pt_scene_upload(pt_context* c, const pt_scene* s, int traverse, c
         int rounds = 0;
         for (const DeviceMesh& dm : device_meshes) {
             PtDeviceBuildResult res;
+            pt_context::Resident::MeshPlace& pl = place[dm.m];
+            pl.node_first = node_base; pl.node_count = PT_DEVICE_TREE_NODES(dm.count); pl.item_first = item_base; pl.item_count = PT_DEVICE_TREE_ITEMS(dm.count, blas_leaf);
+            // entries of the place that the tree will not use name no children (pt_device_tree_parents reads the whole range)
+            PT_HIP(c, hipMemset((PtBvhNode*)c->bvh.p + node_base, 0xFF, (size_t)pl.node_count * sizeof(PtBvhNode)));
             PT_HIP(c, pt_device_build_mesh_tree((const double*)c->tri_v.p, dm.t0, dm.count, dm.lo, dm.hi, dm.pad, blas_leaf, (PtBvhNode*)c->bvh.p, node_base,
                                                 (uint32_t*)c->bvh_items.p, item_base, nullptr, &res));
             meshes[dm.m].blas_root = res.root;
             max_blas_depth = std::max(max_blas_depth, res.depth);
+            pl.depth = res.depth;
             node_base += PT_DEVICE_TREE_NODES(dm.count); item_base += PT_DEVICE_TREE_ITEMS(dm.count, blas_leaf);
             device_ms += res.ms; rounds += res.rounds;
         }
@@ -1174,6 +1211,8 @@ extern "C" int pt_scene_upload(pt_context* c, const pt_scene* s, int traverse, c
         for (size_t m = 0; m < mesh_box.size(); m++) for (int k = 0; k < 3; k++) { mb[6 * m + k] = mesh_box[m].lo[k]; mb[6 * m + 3 + k] = mesh_box[m].hi[k]; }
         if ((rc = pt_upload(c, c->mesh_box_dev, mb))) return rc;
         r.info = std::move(info); r.mesh_box = std::move(mesh_box); r.tri_box = std::move(tri_box);
+        r.place = std::move(place); r.meshes = meshes; r.blas_leaf = blas_leaf; r.max_kdm_depth = max_kdm_depth; r.any_normals = any_normals;
+        r.indices.assign(s->mesh_indices, s->mesh_indices + (mesh_tris ? 3 * mesh_tris : 0)); r.indices_resident = false;
         r.chain_off = std::move(chain_off); r.chain = std::move(chain);
     }
     const int cap_rc = pt_set_stack_cap(c, tlas.depth, kda.kd_depth);
@@ -1199,7 +1238,26 @@ extern "C" int pt_scene_upload(pt_context* c, const pt_scene* s, int traverse, c
 // upload's tree) or on the device (pt_device_build_scene_tree), by the rule mesh trees follow: PORTRAYER_BUILD = host | device | auto,
 // auto takes the device from PORTRAYER_BUILD_MIN nodes on (default 65536), device from 16 on; PORTRAYER_TLAS_LEAF != 1: always the host.
 // ------------------------------------------------------------------------------------------------
-extern "C" int pt_scene_update(pt_context* c, const pt_scene_motion* mo, const pt_kdtree* kd) {
+// What an update computes on the host before its first write (pt_update_prepare) and then writes (pt_update_commit). pt_scene_deform runs the same two
+// steps around its own writes, with the deformed meshes' new boxes.
+struct PtUpdatePlan {
+    std::vector<double> inv, fwd, nrm;
+    PtGraphArrays graph;
+    std::vector<PtBuildBox> node_box;
+    double root_lo[3], root_hi[3];
+    PtKdArrays kda;
+    bool direct = false, on_device = false;
+    std::vector<PtBvhNode> tl_nodes;
+    std::vector<uint32_t> tl_items;
+    PtBvhRef tlas;
+};
+
+// Every check of pt_scene_update and everything its host side computes. `mesh_box`: the meshes' padded model boxes the moved scene has (the resident ones,
+// or a deform's). Writes nothing to the device; PT_ERR_SCENE leaves the context without a scene, as after a refused upload.
+// On the host-build path it does set view.stack_cap (pt_set_stack_cap) from the mesh depths as they are BEFORE the call: for a deform with rebuild = 1
+// that is half a check - a mesh tree the rebuild makes deeper is only seen by pt_update_commit, which computes the cap again after the writes and then
+// ends with PT_ERR_SCENE and no scene, as the header says.
+static int pt_update_prepare(pt_context* c, const pt_scene_motion* mo, const pt_kdtree* kd, const std::vector<PtBuildBox>& mesh_box, PtUpdatePlan& p) {
     if (!c || !mo) return PT_ERR_ARGUMENT;
     if (!c->have_scene) return pt_fail(c, PT_ERR_NO_SCENE, "no scene uploaded");
     pt_context::Resident& res = c->res;
@@ -1218,16 +1276,11 @@ extern "C" int pt_scene_update(pt_context* c, const pt_scene_motion* mo, const p
     if (in_flight) return pt_fail(c, PT_ERR_ARGUMENT, "a render is in flight: pt_render_finish / pt_aov_finish / pt_rays_finish / pt_radiance_finish first");
 
     // ---- everything the host computes, before the first write
-    std::vector<double> inv, fwd, nrm;
-    PtGraphArrays graph;
-    pt_pack_node_matrices(n, mo->trans, mo->invtrans, mo->normal_trans, inv, fwd, nrm);
-    if (res.n_graph) pt_pack_graph(n, res.n_graph, mo->graph_trans, mo->graph_invtrans, mo->graph_normal_trans, res.chain_off, res.chain, graph);
-    std::vector<PtBuildBox> node_box;
-    double root_lo[3], root_hi[3];
-    pt_node_world_boxes(n, mo->trans, res.info.data(), res.mesh_box, res.tri_box, res.mesh_tris, node_box, root_lo, root_hi);
-    PtKdArrays kda;
+    pt_pack_node_matrices(n, mo->trans, mo->invtrans, mo->normal_trans, p.inv, p.fwd, p.nrm);
+    if (res.n_graph) pt_pack_graph(n, res.n_graph, mo->graph_trans, mo->graph_invtrans, mo->graph_normal_trans, res.chain_off, res.chain, p.graph);
+    pt_node_world_boxes(n, mo->trans, res.info.data(), mesh_box, res.tri_box, res.mesh_tris, p.node_box, p.root_lo, p.root_hi);
     int rc;
-    if (res.traverse == PT_TRAVERSE_KD && (rc = pt_pack_kd(c, kd, n, node_box, kda))) {
+    if (res.traverse == PT_TRAVERSE_KD && (rc = pt_pack_kd(c, kd, n, p.node_box, p.kda))) {
         if (rc == PT_ERR_SCENE) c->have_scene = false;  // as after a refused upload
         return rc;
     }
@@ -1235,28 +1288,31 @@ extern "C" int pt_scene_update(pt_context* c, const pt_scene_motion* mo, const p
     size_t device_build_min = 65536;
     if (const char* e = getenv("PORTRAYER_BUILD")) build_mode = !strcmp(e, "host") ? 0 : (!strcmp(e, "device") ? 1 : 2);
     if (const char* e = getenv("PORTRAYER_BUILD_MIN")) device_build_min = (size_t)std::max(16, atoi(e));
-    const bool direct = res.tlas_leaf == 1 && n < (1u << 28);
-    const bool on_device = direct && ((build_mode == 1 && n >= 16) || (build_mode == 2 && n >= device_build_min));
-    std::vector<PtBvhNode> tl_nodes;
-    std::vector<uint32_t> tl_items;
-    PtBvhRef tlas;
-    tlas.child = PT_REF_EMPTY; tlas.depth = 0;
-    if (!on_device) {
-        tlas = pt_build_scene_tree(node_box, res.tlas_leaf, direct, res.tlas_first, res.tlas_items, tl_nodes, tl_items);
-        if (tl_nodes.size() > res.tlas_cap || tl_items.size() > (direct ? 0u : n)) return pt_fail(c, PT_ERR_DEVICE, "scene tree larger than its place");  // (a tree over n leaves has at most n - 1 nodes)
-        if ((rc = pt_set_stack_cap(c, tlas.depth, kda.kd_depth))) { c->have_scene = false; return rc; }
+    p.direct = res.tlas_leaf == 1 && n < (1u << 28);
+    p.on_device = p.direct && ((build_mode == 1 && n >= 16) || (build_mode == 2 && n >= device_build_min));
+    p.tlas.child = PT_REF_EMPTY; p.tlas.depth = 0;
+    if (!p.on_device) {
+        p.tlas = pt_build_scene_tree(p.node_box, res.tlas_leaf, p.direct, res.tlas_first, res.tlas_items, p.tl_nodes, p.tl_items);
+        if (p.tl_nodes.size() > res.tlas_cap || p.tl_items.size() > (p.direct ? 0u : n)) return pt_fail(c, PT_ERR_DEVICE, "scene tree larger than its place");  // (a tree over n leaves has at most n - 1 nodes)
+        if ((rc = pt_set_stack_cap(c, p.tlas.depth, p.kda.kd_depth))) { c->have_scene = false; return rc; }
     }
+    return PT_OK;
+}
 
-    // ---- writes
+// ---- writes
+static int pt_update_commit(pt_context* c, const pt_scene_motion* mo, PtUpdatePlan& p) {
+    pt_context::Resident& res = c->res;
+    const uint32_t n = res.n_nodes;
+    int rc;
     PT_HIP(c, hipSetDevice(c->device));
     PT_HIP(c, hipDeviceSynchronize());  // passes whose _finish has been called may still have copies queued
     c->have_scene = false;              // until every write below has been made
-    if ((rc = pt_upload(c, c->inv, inv)) || (rc = pt_upload(c, c->fwd, fwd)) || (rc = pt_upload(c, c->nrm, nrm))) return rc;
-    if (res.n_graph && ((rc = pt_upload(c, c->g_inv, graph.g_inv)) || (rc = pt_upload(c, c->g_fwd, graph.g_fwd)) || (rc = pt_upload(c, c->g_nrm, graph.g_nrm)) ||
-                        (rc = pt_upload(c, c->hier_rec, graph.hier_rec)) || (rc = pt_upload(c, c->own_inv, graph.own_inv))))
+    if ((rc = pt_upload(c, c->inv, p.inv)) || (rc = pt_upload(c, c->fwd, p.fwd)) || (rc = pt_upload(c, c->nrm, p.nrm))) return rc;
+    if (res.n_graph && ((rc = pt_upload(c, c->g_inv, p.graph.g_inv)) || (rc = pt_upload(c, c->g_fwd, p.graph.g_fwd)) || (rc = pt_upload(c, c->g_nrm, p.graph.g_nrm)) ||
+                        (rc = pt_upload(c, c->hier_rec, p.graph.hier_rec)) || (rc = pt_upload(c, c->own_inv, p.graph.own_inv))))
         return rc;
-    if (res.traverse == PT_TRAVERSE_KD && (rc = pt_upload_kd(c, kda, true))) return rc;
-    for (int k = 0; k < 3; k++) { c->root_lo[k] = root_lo[k]; c->root_hi[k] = root_hi[k]; }
+    if (res.traverse == PT_TRAVERSE_KD && (rc = pt_upload_kd(c, p.kda, true))) return rc;
+    for (int k = 0; k < 3; k++) { c->root_lo[k] = p.root_lo[k]; c->root_hi[k] = p.root_hi[k]; }
     PtSceneView& v = c->view;
     if (mo->lights) {
         std::vector<double> lights(mo->lights, mo->lights + 15 * (size_t)mo->n_lights);
@@ -1264,19 +1320,21 @@ extern "C" int pt_scene_update(pt_context* c, const pt_scene_motion* mo, const p
         pt_set_light_flags(c, lights.data(), mo->n_lights);
     }
     if (mo->ambient) for (int k = 0; k < 3; k++) v.ambient[k] = mo->ambient[k];
-    if (on_device) {
+    PtBvhRef tlas = p.tlas;
+    if (p.on_device) {
         PtDeviceBuildResult built;
         PT_HIP(c, pt_device_build_scene_tree(n, (const double*)c->fwd.p, (const uint32_t*)c->info.p, (const double*)c->mesh_box_dev.p, (const double*)c->tri_v.p,
-                                             root_lo, root_hi, (PtBvhNode*)c->bvh.p, (uint32_t)res.tlas_first, nullptr, &built));
+                                             p.root_lo, p.root_hi, (PtBvhNode*)c->bvh.p, (uint32_t)res.tlas_first, nullptr, &built));
         tlas.child = built.root; tlas.depth = built.depth;
         if (getenv("PORTRAYER_VERBOSE")) fprintf(stderr, "[pt_scene_update] device scene tree: %u nodes, %.2f ms, %d clustering rounds, depth %d\n", n, built.ms, built.rounds, built.depth);
         res.last_builder = 2; res.last_rounds = built.rounds;
-        if ((rc = pt_set_stack_cap(c, tlas.depth, kda.kd_depth))) return rc;  // (have_scene stays false)
     } else {
         res.last_builder = 1; res.last_rounds = 0;
-        if (!tl_nodes.empty()) PT_HIP(c, hipMemcpy((PtBvhNode*)c->bvh.p + res.tlas_first, tl_nodes.data(), tl_nodes.size() * sizeof(PtBvhNode), hipMemcpyHostToDevice));
-        if (!tl_items.empty()) PT_HIP(c, hipMemcpy((uint32_t*)c->bvh_items.p + res.tlas_items, tl_items.data(), tl_items.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+        if (!p.tl_nodes.empty()) PT_HIP(c, hipMemcpy((PtBvhNode*)c->bvh.p + res.tlas_first, p.tl_nodes.data(), p.tl_nodes.size() * sizeof(PtBvhNode), hipMemcpyHostToDevice));
+        if (!p.tl_items.empty()) PT_HIP(c, hipMemcpy((uint32_t*)c->bvh_items.p + res.tlas_items, p.tl_items.data(), p.tl_items.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     }
+    // the stack of the trees as they are now: the scene-level tree just built and (pt_scene_deform) mesh trees a rebuild may have made deeper
+    if ((rc = pt_set_stack_cap(c, tlas.depth, p.kda.kd_depth))) return rc;  // (have_scene stays false)
     if (res.tlas_cap) {  // the four-child form of the new tree alone, opened as the upload opened it
         const uint32_t first = (uint32_t)res.tlas_first, end = (uint32_t)(res.tlas_first + res.tlas_cap);
         hipLaunchKernelGGL(pt_collapse4_kernel, dim3((unsigned)((res.tlas_cap + 255) / 256)), dim3(256), 0, nullptr, (const PtBvhNode*)c->bvh.p, (PtBvh4Node*)c->bvh4.p,
@@ -1289,13 +1347,146 @@ extern "C" int pt_scene_update(pt_context* c, const pt_scene_motion* mo, const p
     return PT_OK;
 }
 
+extern "C" int pt_scene_update(pt_context* c, const pt_scene_motion* mo, const pt_kdtree* kd) {
+    if (!c || !mo) return PT_ERR_ARGUMENT;
+    PtUpdatePlan plan;
+    int rc = pt_update_prepare(c, mo, kd, c->res.mesh_box, plan);
+    if (rc) return rc;
+    return pt_update_commit(c, mo, plan);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Scene deform: new vertices for resident meshes under the topology they were uploaded with, then the update above. Per mesh the host
+// computes the box (the upload's function) and copies the vertices; the device expands the triangle records through the resident indices
+// (pt_device_expand_mesh), refits the mesh's tree in place or rebuilds it there (pt_device_refit_mesh_tree / pt_device_build_mesh_tree) and re-derives
+// the four-child form and the leaf-order records for the mesh's node and item ranges alone.
+// ------------------------------------------------------------------------------------------------
+extern "C" int pt_scene_deform(pt_context* c, uint32_t n_deforms, const pt_mesh_deform* deforms, const pt_scene_motion* mo, const pt_kdtree* kd) {
+    if (!c || !mo || (n_deforms && !deforms)) return PT_ERR_ARGUMENT;
+    if (!c->have_scene) return pt_fail(c, PT_ERR_NO_SCENE, "no scene uploaded");
+    pt_context::Resident& res = c->res;
+    struct NewBox { PtBuildBox vertex, padded; double ext; };
+    std::vector<NewBox> nb(n_deforms);
+    std::vector<PtBuildBox> mesh_box = res.mesh_box;
+    {
+        std::vector<uint8_t> named(res.place.size(), 0);
+        for (uint32_t d = 0; d < n_deforms; d++) {
+            const pt_mesh_deform& df = deforms[d];
+            const std::string at = "deform " + std::to_string(d) + ": ";
+            if (!df.positions || !df.bounds_invtrans) return pt_fail(c, PT_ERR_ARGUMENT, at + "positions and bounds_invtrans are required");
+            if (df.mesh >= res.place.size()) return pt_fail(c, PT_ERR_ARGUMENT, at + "mesh index out of range");
+            if (named[df.mesh]) return pt_fail(c, PT_ERR_ARGUMENT, at + "the mesh is named twice");
+            named[df.mesh] = 1;
+            const pt_context::Resident::MeshPlace& pl = res.place[df.mesh];
+            if (df.normals && !pl.has_normals) return pt_fail(c, PT_ERR_ARGUMENT, at + "normals for a mesh that was uploaded without normals");
+            if (res.meshes[df.mesh].kd_root >= 0)
+                return pt_fail(c, PT_ERR_ARGUMENT, at + "the mesh has a KDMesh tree, which the host builds from the positions: upload the scene again");
+            if (df.rebuild != 0 && df.rebuild != 1) return pt_fail(c, PT_ERR_ARGUMENT, at + "rebuild must be 0 or 1");
+            if (df.rebuild && !pl.device_built)
+                return pt_fail(c, PT_ERR_ARGUMENT, at + "rebuild = 1 needs a tree the device built at upload (its place has the worst-case size); this one was built on the host");
+            nb[d].ext = pt_mesh_vertex_box(df.positions, pl.n_verts, &nb[d].vertex);
+            nb[d].padded = nb[d].vertex;
+            for (int k = 0; k < 3; k++) { nb[d].padded.lo[k] -= 1e-5 * nb[d].ext; nb[d].padded.hi[k] += 1e-5 * nb[d].ext; }
+            bool finite = true;
+            for (uint64_t v = 0; v < 3 * (uint64_t)pl.n_verts; v++) finite = finite && std::isfinite(df.positions[v]);
+            for (int k = 0; k < 3; k++) finite = finite && nb[d].padded.lo[k] >= -PT_BOX_LIMIT && nb[d].padded.hi[k] <= PT_BOX_LIMIT;
+            if (!finite) return pt_fail(c, PT_ERR_ARGUMENT, at + "a coordinate is not finite or the mesh's box reaches beyond +-1e18");
+            mesh_box[df.mesh] = nb[d].padded;
+        }
+    }
+    PtUpdatePlan plan;
+    int rc = pt_update_prepare(c, mo, kd, mesh_box, plan);
+    if (rc) return rc;
+    if (n_deforms == 0) return pt_update_commit(c, mo, plan);
+
+    // ---- writes
+    PT_HIP(c, hipSetDevice(c->device));
+    PT_HIP(c, hipDeviceSynchronize());
+    c->have_scene = false;  // until every write has been made (pt_update_commit sets it again)
+    const bool verbose = getenv("PORTRAYER_VERBOSE") != nullptr;
+    if (!res.indices_resident) {
+        if ((rc = pt_upload(c, c->mesh_idx, res.indices))) return rc;
+        res.indices_resident = true;
+    }
+    bool any_refit = false;
+    size_t stage_bytes = 0;
+    for (uint32_t d = 0; d < n_deforms; d++) {
+        any_refit = any_refit || !deforms[d].rebuild;
+        stage_bytes = std::max(stage_bytes, (size_t)res.place[deforms[d].mesh].n_verts * 24 * (deforms[d].normals ? 2 : 1));
+    }
+    if ((rc = pt_reserve(c, c->deform_stage, stage_bytes))) return rc;
+    if (any_refit && ((rc = pt_reserve(c, c->tree_parent, std::max<size_t>(res.tree_nodes, 1) * 4)) || (rc = pt_reserve(c, c->tree_arrive, std::max<size_t>(res.tree_nodes, 1) * 4)))) return rc;
+    const bool write_normals = res.any_normals;  // (tri_n is empty unless a node shades smoothly: the upload then drops the normals it is given, and so does this)
+    for (uint32_t d = 0; d < n_deforms; d++) {
+        const pt_mesh_deform& df = deforms[d];
+        pt_context::Resident::MeshPlace& pl = res.place[df.mesh];
+        PtMeshInfo& mi = res.meshes[df.mesh];
+        const size_t pos_bytes = (size_t)pl.n_verts * 24;
+        PT_HIP(c, hipMemcpy(c->deform_stage.p, df.positions, pos_bytes, hipMemcpyHostToDevice));
+        if (df.normals) PT_HIP(c, hipMemcpy((char*)c->deform_stage.p + pos_bytes, df.normals, pos_bytes, hipMemcpyHostToDevice));
+        const double* d_pos = (const double*)c->deform_stage.p;
+        const double* d_nrm = df.normals && write_normals ? (const double*)((const char*)c->deform_stage.p + pos_bytes) : nullptr;
+        PT_HIP(c, pt_device_expand_mesh((const uint32_t*)c->mesh_idx.p, mi.tri_first, mi.tri_count, d_pos, d_nrm, pl.n_verts, (double*)c->tri_v.p, (double*)c->tri_e.p,
+                                        d_nrm ? (double*)c->tri_n.p : nullptr, nullptr));
+        const double pad = 1e-7 * nb[d].ext;
+        if (df.rebuild) {
+            PtDeviceBuildResult built;
+            PT_HIP(c, hipMemsetAsync((PtBvhNode*)c->bvh.p + pl.node_first, 0xFF, (size_t)pl.node_count * sizeof(PtBvhNode), nullptr));
+            PT_HIP(c, pt_device_build_mesh_tree((const double*)c->tri_v.p, mi.tri_first, mi.tri_count, nb[d].vertex.lo, nb[d].vertex.hi, pad, res.blas_leaf, (PtBvhNode*)c->bvh.p,
+                                                pl.node_first, (uint32_t*)c->bvh_items.p, pl.item_first, nullptr, &built));
+            mi.blas_root = built.root; pl.depth = built.depth; pl.parents_valid = false;
+            if (verbose) fprintf(stderr, "[pt_scene_deform] mesh %u rebuilt: %u triangles, %.2f ms, %d clustering rounds, depth %d\n", df.mesh, mi.tri_count, built.ms, built.rounds, built.depth);
+        } else if (pl.node_count) {
+            if (!pl.parents_valid) {
+                PT_HIP(c, pt_device_tree_parents((const PtBvhNode*)c->bvh.p, pl.node_first, pl.node_count, (uint32_t*)c->tree_parent.p, nullptr));
+                pl.parents_valid = true;
+            }
+            PT_HIP(c, pt_device_refit_mesh_tree((PtBvhNode*)c->bvh.p, pl.node_first, pl.node_count, (const uint32_t*)c->bvh_items.p, pl.item_first, pl.item_count,
+                                                (const double*)c->tri_v.p, mi.tri_first, mi.tri_count, pad, (const uint32_t*)c->tree_parent.p, (uint32_t*)c->tree_arrive.p, nullptr));
+        }
+        // what the walks read, for the mesh's node and item ranges alone
+        if (pl.node_count) {
+            const uint32_t first = pl.node_first, end = pl.node_first + pl.node_count;
+            hipLaunchKernelGGL(pt_collapse4_kernel, dim3((pl.node_count + 255) / 256), dim3(256), 0, nullptr, (const PtBvhNode*)c->bvh.p, (PtBvh4Node*)c->bvh4.p,
+                               (uint32_t)res.tree_nodes, res.collapse_mode, (uint32_t)res.tlas_first, (uint32_t)(res.tlas_first + res.tlas_cap), first, end);
+            PT_HIP(c, hipGetLastError());
+        }
+        if (pl.item_count) {
+            hipLaunchKernelGGL(pt_tri_leaf_kernel, dim3((pl.item_count + 255) / 256), dim3(256), 0, nullptr, (const uint32_t*)c->bvh_items.p + pl.item_first, pl.item_count,
+                               (const double*)c->tri_e.p, (uint32_t)(res.mesh_tris + res.tri_box.size()), (double*)c->tri_leaf.p + 10 * (size_t)pl.item_first);
+            PT_HIP(c, hipGetLastError());
+        }
+        for (int r = 0; r < 12; r++) mi.bbox_inv[r] = df.bounds_invtrans[r];
+        res.mesh_box[df.mesh] = nb[d].padded;
+        PT_HIP(c, hipStreamSynchronize(nullptr));  // the staging buffer is the next mesh's
+    }
+    {   // the records the walks and the scene-level build read: PtMeshInfo (bbox_inv, blas_root), the padded boxes; the stack under a scene leaf
+        if ((rc = pt_upload(c, c->meshes, res.meshes))) return rc;
+        std::vector<double> mb(6 * res.mesh_box.size());
+        for (size_t m = 0; m < res.mesh_box.size(); m++) for (int k = 0; k < 3; k++) { mb[6 * m + k] = res.mesh_box[m].lo[k]; mb[6 * m + 3 + k] = res.mesh_box[m].hi[k]; }
+        if ((rc = pt_upload(c, c->mesh_box_dev, mb))) return rc;
+        int max_blas_depth = 0;
+        for (const auto& pl : res.place) max_blas_depth = std::max(max_blas_depth, pl.depth);
+        auto wide = [&](int depth2) { return res.collapse_mode ? 3 * depth2 : 3 * ((depth2 + 1) / 2); };
+        res.below = std::max(wide(max_blas_depth), 3 * (res.max_kdm_depth + 1));
+    }
+    return pt_update_commit(c, mo, plan);
+}
+
+extern "C" int pt_scene_mesh_rebuildable(const pt_context* c, uint32_t mesh) {
+    if (!c) return PT_ERR_ARGUMENT;
+    if (!c->have_scene) return PT_ERR_NO_SCENE;
+    if (mesh >= c->res.place.size()) return PT_ERR_ARGUMENT;
+    return c->res.place[mesh].device_built ? 1 : 0;
+}
+
 // tests: the bytes of device memory the context's scene buffers hold (an update must not make it grow)
 extern "C" uint64_t pt_test_scene_bytes(const pt_context* c) {
     if (!c) return 0;
     const PtBuf* bufs[] = {&c->inv, &c->fwd, &c->nrm, &c->info, &c->tri_v, &c->tri_e, &c->tri_leaf, &c->tri_n, &c->meshes, &c->materials, &c->lights, &c->bvh, &c->bvh4,
                            &c->bvh_items, &c->kd, &c->kd_items, &c->mat_maps, &c->uv_trans, &c->tex, &c->tex_rgb, &c->srgb_lut, &c->tri_uv, &c->texview, &c->mkd, &c->mkd_items,
                            &c->node_box, &c->kd_box, &c->mkd_box, &c->mkd_item_box, &c->kd_ref, &c->g_inv, &c->g_fwd, &c->g_nrm, &c->chain_off, &c->chain, &c->dfs_rank,
-                           &c->hier_rec, &c->own_inv, &c->mesh_box_dev};
+                           &c->hier_rec, &c->own_inv, &c->mesh_box_dev, &c->mesh_idx, &c->tree_parent, &c->tree_arrive, &c->deform_stage};
     uint64_t total = 0;
     for (const PtBuf* b : bufs) total += b->bytes;
     return total;

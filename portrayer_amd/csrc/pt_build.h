@@ -45,3 +45,25 @@ hipError_t pt_device_build_mesh_tree(const double* d_tri_v, uint32_t tri_first, 
 hipError_t pt_device_build_scene_tree(uint32_t n, const double* d_fwd, const uint32_t* d_info, const double* d_mesh_box, const double* d_tri_v,
                                       const double lo[3], const double hi[3], PtBvhNode* d_nodes, uint32_t node_base, hipStream_t stream,
                                       PtDeviceBuildResult* out);
+
+// ---- pt_scene_deform: new vertices under an unchanged topology -------------------------------------------------------------------
+// Expand: one thread per triangle t of [0, n_tris) gathers its three vertices through d_indices[3 (tri_first + t) ..] (indices local to the mesh, as
+// uploaded; one >= n_verts leaves its triangle untouched) from d_pos (n_verts x 3 f64) and writes record tri_first + t of d_tri_v (a, b, c), of d_tri_e
+// (a, a - b, a - c: plain f64 subtractions, the upload's bits) and - when d_nrm and d_tri_n are given - of d_tri_n.
+hipError_t pt_device_expand_mesh(const uint32_t* d_indices, uint32_t tri_first, uint32_t n_tris, const double* d_pos, const double* d_nrm, uint32_t n_verts,
+                                 double* d_tri_v, double* d_tri_e, double* d_tri_n, hipStream_t stream);
+
+// d_parent[i] for the two-child nodes [node_first, node_first + node_count) of one mesh tree: (parent << 1) | the parent's child slot, PT_TREE_NO_PARENT
+// for the root and for entries no node refers to. Entries of the range that the tree does not use must hold PT_REF_EMPTY children (pt_scene_upload and a
+// rebuild fill the range with 0xFF bytes before the device builder runs). Depends on the topology alone: computed once per tree, again after a rebuild.
+#define PT_TREE_NO_PARENT 0xFFFFFFFFu
+hipError_t pt_device_tree_parents(const PtBvhNode* d_nodes, uint32_t node_first, uint32_t node_count, uint32_t* d_parent, hipStream_t stream);
+
+// Refit: the tree keeps its topology, every box is recomputed bottom-up. One thread per node writes the boxes of the node's LEAF children from the
+// triangles their references name through d_items (padded by `pad`, rounded outward to f32 like pt_ploc_prepare and the host build), and carries the
+// union upward into the parent's lo[axis][slot] / hi[axis][slot]: a node is complete when two arrivals have been counted at it (d_arrive, zeroed by this
+// call for the range; a leaf child is an arrival of the node's own thread); the first to arrive exits, the second continues: no thread waits or spins.
+// A device-scope fence separates a box store from the counter increment. item / triangle / parent indices outside their ranges are skipped, not followed.
+hipError_t pt_device_refit_mesh_tree(PtBvhNode* d_nodes, uint32_t node_first, uint32_t node_count, const uint32_t* d_items, uint32_t item_first,
+                                     uint32_t item_count, const double* d_tri_v, uint32_t tri_first, uint32_t tri_count, double pad,
+                                     const uint32_t* d_parent, uint32_t* d_arrive, hipStream_t stream);

@@ -508,3 +508,162 @@ hipError_t pt_device_build_scene_tree(uint32_t n, const double* d_fwd, const uin
     out->root = node_base + root;
     return hipSuccess;
 }
+
+// ------------------------------------------------------------------------------------------------
+// pt_scene_deform (pt_build.h): triangle records from new vertices, and the refit of a mesh tree whose topology stays.
+// ------------------------------------------------------------------------------------------------
+namespace {
+
+__global__ void __launch_bounds__(PT_BUILD_BLOCK) pt_expand_kernel(const uint32_t* __restrict__ indices, uint32_t tri_first, uint32_t n_tris,
+                                                                  const double* __restrict__ pos, const double* __restrict__ nrm, uint32_t n_verts,
+                                                                  double* __restrict__ tri_v, double* __restrict__ tri_e, double* __restrict__ tri_n) {
+    const uint32_t t = blockIdx.x * PT_BUILD_BLOCK + threadIdx.x;
+    if (t >= n_tris) return;
+    const size_t g = (size_t)tri_first + t;
+    const uint32_t ia = indices[3 * g], ib = indices[3 * g + 1], ic = indices[3 * g + 2];
+    if (ia >= n_verts || ib >= n_verts || ic >= n_verts) return;  // (the upload refuses such a mesh)
+    double a[3], b[3], c[3];
+    for (int k = 0; k < 3; k++) { a[k] = pos[3 * (size_t)ia + k]; b[k] = pos[3 * (size_t)ib + k]; c[k] = pos[3 * (size_t)ic + k]; }
+    double* v = tri_v + 9 * g;
+    double* e = tri_e + 9 * g;
+    for (int k = 0; k < 3; k++) {
+        v[k] = a[k]; v[3 + k] = b[k]; v[6 + k] = c[k];
+        e[k] = a[k]; e[3 + k] = a[k] - b[k]; e[6 + k] = a[k] - c[k];
+    }
+    if (nrm && tri_n) {
+        double* n = tri_n + 9 * g;
+        for (int k = 0; k < 3; k++) { n[k] = nrm[3 * (size_t)ia + k]; n[3 + k] = nrm[3 * (size_t)ib + k]; n[6 + k] = nrm[3 * (size_t)ic + k]; }
+    }
+}
+
+__device__ __forceinline__ bool pt_ref_inner(uint32_t ref) { return ref != PT_REF_EMPTY && !(ref & PT_REF_LEAF); }
+
+__global__ void __launch_bounds__(PT_BUILD_BLOCK) pt_parent_clear_kernel(uint32_t node_count, uint32_t* __restrict__ parent) {
+    const uint32_t k = blockIdx.x * PT_BUILD_BLOCK + threadIdx.x;
+    if (k < node_count) parent[k] = PT_TREE_NO_PARENT;
+}
+
+// parent is indexed from the range's first node
+__global__ void __launch_bounds__(PT_BUILD_BLOCK) pt_parent_kernel(const PtBvhNode* __restrict__ nodes, uint32_t node_first, uint32_t node_count,
+                                                                  uint32_t* __restrict__ parent) {
+    const uint32_t k = blockIdx.x * PT_BUILD_BLOCK + threadIdx.x;
+    if (k >= node_count) return;
+    const uint32_t i = node_first + k;
+    const uint32_t child[2] = {nodes[i].child0, nodes[i].child1};
+    for (int s = 0; s < 2; s++) {
+        const uint32_t c = child[s];
+        if (!pt_ref_inner(c) || c < node_first || c - node_first >= node_count || c == i) continue;
+        parent[c - node_first] = (i << 1) | (uint32_t)s;
+    }
+}
+
+struct PtRefitArgs {
+    PtBvhNode* nodes;
+    const uint32_t* items;
+    const double* tri_v;
+    const uint32_t* parent;  // from the range's first node
+    uint32_t* arrive;        // likewise
+    uint32_t node_first, node_count, item_first, item_count, tri_first, tri_count;
+    double pad;
+};
+
+// the box of a leaf reference's triangles, padded and rounded outward; false: the reference names nothing inside the mesh's ranges
+__device__ __forceinline__ bool pt_refit_leaf_box(const PtRefitArgs& a, uint32_t ref, float lo[3], float hi[3]) {
+    const uint32_t first = (ref & ~PT_REF_LEAF) >> 3, count = (ref & 7u) + 1u;
+    if (first < a.item_first || first - a.item_first > a.item_count || count > a.item_count - (first - a.item_first)) return false;
+    double l[3] = {INFINITY, INFINITY, INFINITY}, h[3] = {-INFINITY, -INFINITY, -INFINITY};
+    bool any = false;
+    for (uint32_t j = 0; j < count; j++) {
+        const uint32_t t = a.items[first + j];
+        if (t < a.tri_first || t - a.tri_first >= a.tri_count) continue;
+        const double* v = a.tri_v + 9 * (size_t)t;
+        for (int k = 0; k < 3; k++) {
+            l[k] = fmin(l[k], fmin(fmin(v[k], v[3 + k]), v[6 + k]));
+            h[k] = fmax(h[k], fmax(fmax(v[k], v[3 + k]), v[6 + k]));
+        }
+        any = true;
+    }
+    if (!any) return false;
+    for (int k = 0; k < 3; k++) { lo[k] = pt_box_lo(l[k] - a.pad); hi[k] = pt_box_hi(h[k] + a.pad); }
+    return true;
+}
+
+__device__ __forceinline__ void pt_refit_store_box(PtBvhNode* nd, uint32_t slot, const float lo[3], const float hi[3]) {
+    for (int k = 0; k < 3; k++) { nd->lo[k][slot] = lo[k]; nd->hi[k][slot] = hi[k]; }
+}
+
+__device__ __forceinline__ float pt_refit_load(const float* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+__global__ void __launch_bounds__(PT_BUILD_BLOCK) pt_refit_kernel(PtRefitArgs a) {
+    const uint32_t k0 = blockIdx.x * PT_BUILD_BLOCK + threadIdx.x;
+    if (k0 >= a.node_count) return;
+    uint32_t k = k0;  // the node this thread stands at, from the range's first
+    PtBvhNode* nd = a.nodes + a.node_first + k;
+    const uint32_t child[2] = {nd->child0, nd->child1};
+    if (child[0] == PT_REF_EMPTY && child[1] == PT_REF_EMPTY) return;  // an entry of the range that the tree does not use
+    uint32_t arrivals = 0;
+    for (uint32_t s = 0; s < 2; s++) {
+        if (pt_ref_inner(child[s])) continue;
+        float lo[3], hi[3];
+        if (child[s] != PT_REF_EMPTY && pt_refit_leaf_box(a, child[s], lo, hi)) pt_refit_store_box(nd, s, lo, hi);
+        arrivals++;
+    }
+    if (arrivals == 0) return;  // both children are inner nodes: the second of them to finish carries on from here
+    // at most one pass per level of the tree: the loop ends at the root or where this thread is the first to arrive
+    for (uint32_t level = 0; level <= a.node_count; level++) {
+        if (arrivals < 2) {
+            __threadfence();  // the box stored above is visible device-wide before the arrival is counted
+            if (atomicAdd(a.arrive + k, 1u) == 0u) return;  // the first to arrive: whoever brings the other child continues
+            __threadfence();  // ... whose box is read below
+        }
+        const uint32_t p = a.parent[k];
+        if (p == PT_TREE_NO_PARENT) return;  // the root: its own box is the mesh's (PtMeshInfo::bbox_inv)
+        const uint32_t pi = p >> 1, slot = p & 1u;
+        if (pi < a.node_first || pi - a.node_first >= a.node_count) return;
+        const bool used[2] = {nd->child0 != PT_REF_EMPTY, nd->child1 != PT_REF_EMPTY};  // (the references never change)
+        float lo[3], hi[3];
+        for (int ax = 0; ax < 3; ax++) {
+            lo[ax] = PT_PLOC_LIMIT; hi[ax] = -PT_PLOC_LIMIT;
+            for (int s = 0; s < 2; s++)
+                if (used[s]) { lo[ax] = fminf(lo[ax], pt_refit_load(&nd->lo[ax][s])); hi[ax] = fmaxf(hi[ax], pt_refit_load(&nd->hi[ax][s])); }
+        }
+        k = pi - a.node_first;
+        nd = a.nodes + pi;
+        pt_refit_store_box(nd, slot, lo, hi);
+        arrivals = 1;
+    }
+}
+
+}  // namespace
+
+hipError_t pt_device_expand_mesh(const uint32_t* d_indices, uint32_t tri_first, uint32_t n_tris, const double* d_pos, const double* d_nrm, uint32_t n_verts,
+                                 double* d_tri_v, double* d_tri_e, double* d_tri_n, hipStream_t stream) {
+    if (n_tris == 0) return hipSuccess;
+    if (!d_indices || !d_pos || !d_tri_v || !d_tri_e) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(pt_expand_kernel, dim3((n_tris + PT_BUILD_BLOCK - 1) / PT_BUILD_BLOCK), dim3(PT_BUILD_BLOCK), 0, stream, d_indices, tri_first, n_tris, d_pos,
+                       d_nrm, n_verts, d_tri_v, d_tri_e, d_tri_n);
+    return hipGetLastError();
+}
+
+hipError_t pt_device_tree_parents(const PtBvhNode* d_nodes, uint32_t node_first, uint32_t node_count, uint32_t* d_parent, hipStream_t stream) {
+    if (node_count == 0) return hipSuccess;
+    if (!d_nodes || !d_parent || node_first >= (1u << 30) || node_count >= (1u << 30)) return hipErrorInvalidValue;
+    const dim3 grid((node_count + PT_BUILD_BLOCK - 1) / PT_BUILD_BLOCK), block(PT_BUILD_BLOCK);
+    hipLaunchKernelGGL(pt_parent_clear_kernel, grid, block, 0, stream, node_count, d_parent + node_first);
+    hipLaunchKernelGGL(pt_parent_kernel, grid, block, 0, stream, d_nodes, node_first, node_count, d_parent + node_first);
+    return hipGetLastError();
+}
+
+hipError_t pt_device_refit_mesh_tree(PtBvhNode* d_nodes, uint32_t node_first, uint32_t node_count, const uint32_t* d_items, uint32_t item_first,
+                                     uint32_t item_count, const double* d_tri_v, uint32_t tri_first, uint32_t tri_count, double pad,
+                                     const uint32_t* d_parent, uint32_t* d_arrive, hipStream_t stream) {
+    if (node_count == 0) return hipSuccess;
+    if (!d_nodes || !d_items || !d_tri_v || !d_parent || !d_arrive) return hipErrorInvalidValue;
+    PT_TRY(hipMemsetAsync(d_arrive + node_first, 0, 4 * (size_t)node_count, stream));
+    PtRefitArgs a;
+    a.nodes = d_nodes; a.items = d_items; a.tri_v = d_tri_v; a.parent = d_parent + node_first; a.arrive = d_arrive + node_first;
+    a.node_first = node_first; a.node_count = node_count; a.item_first = item_first; a.item_count = item_count; a.tri_first = tri_first; a.tri_count = tri_count;
+    a.pad = pad;
+    hipLaunchKernelGGL(pt_refit_kernel, dim3((node_count + PT_BUILD_BLOCK - 1) / PT_BUILD_BLOCK), dim3(PT_BUILD_BLOCK), 0, stream, a);
+    return hipGetLastError();
+}

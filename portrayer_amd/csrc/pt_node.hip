@@ -268,6 +268,20 @@ extern "C" int pt_node_scene_update(pt_node* n, const pt_scene_motion* motion, c
     return PT_OK;
 }
 
+extern "C" int pt_node_scene_deform(pt_node* n, uint32_t n_deforms, const pt_mesh_deform* deforms, const pt_scene_motion* motion, const pt_kdtree* kd) {
+    if (!n || !motion || (n_deforms && !deforms)) return PT_ERR_ARGUMENT;
+    if (!n->have_scene) return node_fail(n, PT_ERR_NO_SCENE, "no scene uploaded");
+    if (n->frame_begun != n->frame_ended) return node_fail(n, PT_ERR_ARGUMENT, "frames are in flight: pt_node_frame_end first");
+    for (size_t r = 0; r < n->ctx.size(); r++) {
+        int rc = pt_scene_deform(n->ctx[r], n_deforms, deforms, motion, kd);
+        if (rc != PT_OK) {
+            if (r > 0 || rc == PT_ERR_SCENE || rc == PT_ERR_DEVICE) n->have_scene = false;  // as in pt_node_scene_update
+            return node_fail(n, rc, "rank " + std::to_string(r) + ": " + pt_last_error(n->ctx[r]));
+        }
+    }
+    return PT_OK;
+}
+
 extern "C" int pt_node_device(const pt_node* n, int rank) { return (n && rank >= 0 && (size_t)rank < n->devices.size()) ? n->devices[rank] : -1; }
 
 static int node_check_params(pt_node* n, const pt_render_params* params) {

@@ -19,7 +19,7 @@ _dp, _ip, _up, _u64p, _u8p = H._dp, H._ip, H._up, H._u64p, H._u8p
 
 EXPORTS = ["ph_last_error", "ph_scene_create", "ph_example_scene", "ph_scene_destroy", "ph_scene_counts", "ph_scene_export", "ph_scene_export_textures",
            "ph_scene_flatten", "ph_scene_kdtree", "ph_camera", "ph_obj_load", "ph_renderer_create", "ph_renderer_destroy",
-           "ph_renderer_context", "ph_renderer_ranks", "ph_renderer_node", "ph_renderer_prepare_ms", "ph_renderer_render", "ph_renderer_aov", "ph_renderer_rays", "ph_renderer_radiance", "ph_renderer_update", "ph_scene_same_structure", "ph_example_render_to_png", "ph_png_read", "ph_png_write", "ph_image_read", "ph_scene_graph"]
+           "ph_renderer_context", "ph_renderer_ranks", "ph_renderer_node", "ph_renderer_prepare_ms", "ph_renderer_render", "ph_renderer_aov", "ph_renderer_rays", "ph_renderer_radiance", "ph_renderer_update", "ph_scene_same_structure", "ph_renderer_deform", "ph_scene_same_topology", "ph_example_render_to_png", "ph_png_read", "ph_png_write", "ph_image_read", "ph_scene_graph"]
 
 
 class PortrayerHostError(RuntimeError):
@@ -84,6 +84,8 @@ def lib() -> C.CDLL:
         l.ph_renderer_radiance.argtypes = [vp, C.POINTER(H.PtRadianceParams), _dp, _dp, _dp, _dp, _dp]
         l.ph_renderer_update.restype = C.c_int; l.ph_renderer_update.argtypes = [vp, vp]
         l.ph_scene_same_structure.restype = C.c_int; l.ph_scene_same_structure.argtypes = [vp, vp, C.c_char_p, C.c_size_t]
+        l.ph_renderer_deform.restype = C.c_int; l.ph_renderer_deform.argtypes = [vp, vp, C.c_int]
+        l.ph_scene_same_topology.restype = C.c_int; l.ph_scene_same_topology.argtypes = [vp, vp, C.c_char_p, C.c_size_t]
         l.ph_scene_export_textures.restype = C.c_int
         l.ph_scene_export_textures.argtypes = [vp, _u64p, _ip, _ip, _dp, _up, _u64p, _u8p, _dp, _u8p, _dp, _u8p]
         l.ph_example_render_to_png.restype = C.c_int
@@ -220,6 +222,14 @@ class Scene:
         rc = _check(lib().ph_scene_same_structure(self._h, other._h, why, len(why)), "ph_scene_same_structure")
         return SameStructure(rc == 1, why.value.decode())
 
+    def same_topology(self, other: "Scene"):
+        """Whether `other` is this scene moved and DEFORMED: same_structure(), except that a mesh may differ in the values of its vertex positions and
+        normals (vertex count, triangles, texture coordinates and the presence of normals must be equal) - which is what Renderer.deform() accepts.
+        Returns a value like same_structure()'s. Needs no GPU."""
+        why = C.create_string_buffer(512)
+        rc = _check(lib().ph_scene_same_topology(self._h, other._h, why, len(why)), "ph_scene_same_topology")
+        return SameStructure(rc == 1, why.value.decode())
+
     def flatten(self) -> dict:
         n = _check(lib().ph_scene_flatten(self._h, 0, None, None, None, None, None, None), "ph_scene_flatten")
         tr, inv, nrm = np.zeros((n, 16)), np.zeros((n, 16)), np.zeros((n, 16))
@@ -321,6 +331,14 @@ class Renderer:
         (Scene.same_structure). Meshes, their trees and textures stay on the device; only the scene-level tree is rebuilt. Every later call answers as
         a new Renderer on `scene` would, bit for bit."""
         _check(lib().ph_renderer_update(self._h, scene._h), "ph_renderer_update")
+        self.scene = scene
+
+    def deform(self, scene: Scene, rebuild: bool = False):
+        """Resident meshes deformed (pt_scene_deform; on several ranks pt_node_scene_deform): `scene` must be the renderer's scene with other vertex
+        positions / normals in its meshes and, as for update(), other transforms, lights' values or ambient light (Scene.same_topology). Only the vertices
+        of the meshes that changed go to the device, where their triangle records are expanded and their trees refitted - or, with rebuild=True, rebuilt
+        where the device built them at upload. Every later call answers as a new Renderer on `scene` would, bit for bit."""
+        _check(lib().ph_renderer_deform(self._h, scene._h, 1 if rebuild else 0), "ph_renderer_deform")
         self.scene = scene
 
     def aov(self, cam10, width: int, height: int, rect=None, offset=(0.5, 0.5), want=("depth", "position", "normal", "node", "sub", "material"),

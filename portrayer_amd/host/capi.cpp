@@ -531,6 +531,29 @@ extern "C" int ph_scene_same_structure(const ph_scene* a, const ph_scene* b, cha
     });
 }
 
+extern "C" int ph_scene_same_topology(const ph_scene* a, const ph_scene* b, char* why, size_t n) {
+    if (why && n) why[0] = 0;
+    if (!a || !b) return bad("null argument");
+    return guarded([&]() -> int {
+        const std::string diff = detail::structure_difference(detail::FlatScene::from(a->hier), detail::FlatScene::from(b->hier), true);
+        if (why && n) { std::strncpy(why, diff.c_str(), n - 1); why[n - 1] = 0; }
+        return diff.empty() ? 1 : 0;
+    });
+}
+
+extern "C" int ph_renderer_deform(ph_renderer* r, const ph_scene* s, int rebuild) {
+    if (!r || !s) return bad("null argument");
+    return guarded([&]() -> int {
+        try {
+            r->r->deform(s->hier, rebuild != 0);
+        } catch (const std::invalid_argument& e) {
+            g_error = e.what();
+            return PH_ERR_ARGUMENT;
+        }
+        return PH_OK;
+    });
+}
+
 extern "C" int ph_renderer_update(ph_renderer* r, const ph_scene* s) {
     if (!r || !s) return bad("null argument");
     return guarded([&]() -> int {

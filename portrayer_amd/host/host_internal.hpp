@@ -52,7 +52,9 @@ GraphPacking pack_graph(const FlatScene& flat);
 // use, equal in content), the shading flag, the material (numbered by first use, equal in its ten values, maps and uv transform) and the
 // path through the graph (so graph nodes, chains and dfs_rank agree) - and as many lights. Transforms, light values and the ambient
 // light may differ. Returns "" or the first difference.
-std::string structure_difference(const FlatScene& a, const FlatScene& b);
+// deformable = true asks for the same TOPOLOGY instead: a mesh may also differ in the values of its vertex positions and normals (vertex count, triangles,
+// texture coordinates and the presence of normals must still be equal) - what Renderer::deform accepts.
+std::string structure_difference(const FlatScene& a, const FlatScene& b, bool deformable = false);
 
 struct PartitionConfig {  // leaf.rs:55-67
     size_t target_max_nodes = 3;
@@ -98,6 +100,10 @@ class Renderer {
     // std::invalid_argument naming the first difference) and may differ in transforms, lights' values and ambient light. Nothing but the node matrices, the
     // lights and - in k-d mode - the rebuilt reference k-d tree goes to the device. On an error the renderer keeps its scene, unless the library says it is gone.
     void update(const scene::HierScene& scene);
+    // Resident meshes deformed (pt_scene_deform): `scene` must have the topology of the one this renderer was made from (structure_difference(.., true); throws
+    // std::invalid_argument naming the first difference). The meshes whose positions or normals differ in a bit are sent - vertices and bounds only - and their
+    // trees refitted on the device; rebuild = true rebuilds those the device built at upload instead (and refits the others). The motion is performed as by update().
+    void deform(const scene::HierScene& scene, bool rebuild = false);
     pt_context* context() const { return ctx_; }  // rank 0's context when the scene is on a node
     pt_node* node() const { return node_; }
     const FlatScene& flat() const { return flat_; }
@@ -111,6 +117,7 @@ class Renderer {
     PrepareMs prep_;
     render::Traversal traversal_ = render::Traversal::Flat;
     int kd_depth_ = -1;
+    void move(FlatScene&& moved, const std::vector<pt_mesh_deform>* deforms);
 };
 
 // PNG codec for Image::new / Image::save (render.rs:165-208; the reference uses the `image` crate)

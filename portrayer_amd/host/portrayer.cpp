@@ -372,7 +372,7 @@ GraphPacking pack_graph(const FlatScene& flat) {
     return g;
 }
 
-std::string structure_difference(const FlatScene& a, const FlatScene& b) {
+std::string structure_difference(const FlatScene& a, const FlatScene& b, bool deformable) {
     if (a.root.size() != b.root.size()) return "the scenes have " + std::to_string(a.root.size()) + " and " + std::to_string(b.root.size()) + " flattened nodes";
     auto same_v = [](Vec3 x, Vec3 y) { return x.x == y.x && x.y == y.y && x.z == y.z; };
     auto same_image = [](const texture::RgbImageBuffer* x, const texture::RgbImageBuffer* y) {
@@ -384,8 +384,8 @@ std::string structure_difference(const FlatScene& a, const FlatScene& b) {
         if (x->positions().size() != y->positions().size() || x->triangles() != y->triangles() || x->normals().size() != y->normals().size() ||
             x->tex_coords().size() != y->tex_coords().size())
             return false;
-        for (size_t i = 0; i < x->positions().size(); i++) if (!same_v(x->positions()[i], y->positions()[i])) return false;
-        for (size_t i = 0; i < x->normals().size(); i++) if (!same_v(x->normals()[i], y->normals()[i])) return false;
+        for (size_t i = 0; i < x->positions().size() && !deformable; i++) if (!same_v(x->positions()[i], y->positions()[i])) return false;
+        for (size_t i = 0; i < x->normals().size() && !deformable; i++) if (!same_v(x->normals()[i], y->normals()[i])) return false;
         for (size_t i = 0; i < x->tex_coords().size(); i++) if (x->tex_coords()[i].u != y->tex_coords()[i].u || x->tex_coords()[i].v != y->tex_coords()[i].v) return false;
         return true;
     };
@@ -590,6 +590,12 @@ static pt_kdtree kd_abi(const KdTree& t) {
     return kd;
 }
 
+// BoundingBox::invtrans of a mesh's AABB (mesh.rs:82): what the upload and a deform hand the library as the mesh's bounds
+static void append_mesh_bounds(const primitive::MeshData* m, std::vector<double>& out) {
+    BoundingBox bb = BoundingBox::create(m->bounds_min(), m->bounds_max());
+    const double* im = &bb.invtrans.m[0][0];
+    out.insert(out.end(), im, im + 16);
+}
 static double ms_since(std::chrono::steady_clock::time_point t) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count(); }
 
 Renderer::Renderer(const scene::HierScene& hier, render::Traversal traversal, int kd_depth, int device) : traversal_(traversal), kd_depth_(kd_depth) {
@@ -672,9 +678,7 @@ Renderer::Renderer(const scene::HierScene& hier, render::Traversal traversal, in
         for (const auto& t : m->triangles()) { indices.push_back(t[0]); indices.push_back(t[1]); indices.push_back(t[2]); }
         vert_off.push_back(vert_off.back() + m->positions().size());
         tri_off.push_back(tri_off.back() + m->triangles().size());
-        BoundingBox bb = BoundingBox::create(m->bounds_min(), m->bounds_max());  // mesh.rs:82
-        const double* im = &bb.invtrans.m[0][0];
-        mesh_bounds_inv.insert(mesh_bounds_inv.end(), im, im + 16);
+        append_mesh_bounds(m, mesh_bounds_inv);
     }
     // KDMesh::new (kdmesh.rs:37-58): a k-d tree over the triangles of every mesh a KDMesh primitive uses
     std::vector<int32_t> mesh_kd_root(meshes.size(), -1), mesh_kd_depth(meshes.size(), 0);
@@ -844,6 +848,58 @@ void Renderer::update(const scene::HierScene& hier) {
     FlatScene moved = FlatScene::from(hier);
     const std::string why = structure_difference(flat_, moved);
     if (!why.empty()) throw std::invalid_argument("Renderer::update: the scene has another structure than the resident one: " + why);
+    move(std::move(moved), nullptr);
+}
+
+void Renderer::deform(const scene::HierScene& hier, bool rebuild) {
+    FlatScene moved = FlatScene::from(hier);
+    const std::string why = structure_difference(flat_, moved, true);
+    if (!why.empty()) throw std::invalid_argument("Renderer::deform: the scene has another topology than the resident one: " + why);
+    // the meshes in the constructor's numbering (first use), resident and new side by side; those whose positions or normals differ in a bit are sent
+    std::map<const primitive::MeshData*, uint32_t> mesh_id;
+    std::vector<pt_mesh_deform> deforms;
+    std::vector<std::vector<double>> arrays;  // what the deforms point into
+    auto bits_differ = [](const std::vector<Vec3>& x, const std::vector<Vec3>& y) {
+        for (size_t i = 0; i < x.size(); i++) {
+            const double a[3] = {x[i].x, x[i].y, x[i].z}, b[3] = {y[i].x, y[i].y, y[i].z};
+            if (std::memcmp(a, b, sizeof a) != 0) return true;
+        }
+        return false;
+    };
+    auto flat3 = [](const std::vector<Vec3>& x) {
+        std::vector<double> out;
+        out.reserve(3 * x.size());
+        for (const Vec3& v : x) { out.push_back(v.x); out.push_back(v.y); out.push_back(v.z); }
+        return out;
+    };
+    for (size_t i = 0; i < moved.root.size(); i++) {
+        const auto &p = flat_.root[i].geometry.primitive, &q = moved.root[i].geometry.primitive;
+        if (p.kind != primitive::Primitive::MeshK && p.kind != primitive::Primitive::KDMeshK) continue;
+        if (!mesh_id.emplace(p.mesh.get(), (uint32_t)mesh_id.size()).second) continue;
+        const uint32_t m = (uint32_t)mesh_id.size() - 1;
+        const primitive::MeshData *was = p.mesh.get(), *now = q.mesh.get();
+        if (was == now || (!bits_differ(was->positions(), now->positions()) && !bits_differ(was->normals(), now->normals()))) continue;
+        pt_mesh_deform d;
+        std::memset(&d, 0, sizeof d);
+        d.mesh = m;
+        d.rebuild = rebuild && pt_scene_mesh_rebuildable(ctx_, m) == 1 ? 1 : 0;  // (every rank holds the same scene, built by the same rule: rank 0 answers for all)
+        const bool has_normals = now->normals().size() == now->positions().size();
+        arrays.push_back(flat3(now->positions()));
+        arrays.push_back(has_normals ? flat3(now->normals()) : std::vector<double>());
+        arrays.emplace_back();
+        append_mesh_bounds(now, arrays.back());
+        deforms.push_back(d);
+    }
+    for (size_t k = 0; k < deforms.size(); k++) {
+        deforms[k].positions = arrays[3 * k].data();
+        deforms[k].normals = arrays[3 * k + 1].empty() ? nullptr : arrays[3 * k + 1].data();
+        deforms[k].bounds_invtrans = arrays[3 * k + 2].data();
+    }
+    move(std::move(moved), &deforms);
+}
+
+// pt_scene_update (deforms == nullptr) or pt_scene_deform with the moved scene's matrices, lights and - in k-d mode - its rebuilt reference k-d tree
+void Renderer::move(FlatScene&& moved, const std::vector<pt_mesh_deform>* deforms) {
     const size_t n = moved.root.size();
     std::vector<double> trans(16 * n), inv(16 * n), nrm(16 * n), lights;
     for (size_t i = 0; i < n; i++) {
@@ -872,13 +928,18 @@ void Renderer::update(const scene::HierScene& hier) {
         kd = kd_abi(t);
     }
     const pt_kdtree* kdp = traversal_ == render::Traversal::KdTree ? &kd : nullptr;
+    const pt_mesh_deform dummy{};
+    const pt_mesh_deform* dp = deforms ? (deforms->empty() ? &dummy : deforms->data()) : nullptr;
+    const uint32_t nd = deforms ? (uint32_t)deforms->size() : 0u;
     if (node_) {
-        int rc = pt_node_scene_update(node_, &mo, kdp);
+        int rc = deforms ? pt_node_scene_deform(node_, nd, dp, &mo, kdp) : pt_node_scene_update(node_, &mo, kdp);
         if (rc != PT_OK) {
-            std::string msg = std::string("pt_node_scene_update failed (") + std::to_string(rc) + "): " + pt_node_last_error(node_);
+            std::string msg = std::string(deforms ? "pt_node_scene_deform" : "pt_node_scene_update") + " failed (" + std::to_string(rc) + "): " + pt_node_last_error(node_);
             if (rc == PT_ERR_SCENE) throw Panic(msg);
             throw std::runtime_error(msg);
         }
+    } else if (deforms) {
+        check(ctx_, pt_scene_deform(ctx_, nd, dp, &mo, kdp), "pt_scene_deform");
     } else {
         check(ctx_, pt_scene_update(ctx_, &mo, kdp), "pt_scene_update");
     }
