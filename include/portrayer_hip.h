@@ -261,6 +261,38 @@ int pt_scene_deform(pt_context *ctx, uint32_t n_deforms, const pt_mesh_deform *d
  * size), 0 (the host built it: refit only), PT_ERR_ARGUMENT (NULL context, mesh index out of range), PT_ERR_NO_SCENE. Needs no device work. */
 int pt_scene_mesh_rebuildable(const pt_context *ctx, uint32_t mesh);
 
+/* ---- The same deform with vertices that are already in DEVICE memory (a simulation, skinning or a torch tensor on the context's GPU): nothing per vertex
+ * crosses the bus or is touched by the host. Two calls, because bounds_invtrans and - in PT_TRAVERSE_KD - `kd` are host structures that depend on the mesh's
+ * new box: pt_vertex_bounds_device gives the caller the box, from which it makes BoundingBox::invtrans (and the k-d tree), then pt_scene_deform_device deforms.
+ *
+ * pt_vertex_bounds_device: the box of n_vertices x 3 f64 positions in device memory, by one reduction pass on the device. out[0..2] = min, out[3..5] = max per
+ * axis, with the bits the host loop of pt_scene_upload / pt_scene_deform leaves: where an extreme is a zero that occurs with both signs, the sign of the
+ * lowest-index vertex attaining it. *non_finite = how many of the 3 n coordinates are NaN or +-inf; they take no part in min / max. n_vertices = 0 or nothing
+ * finite: the empty box (min = +inf, max = -inf). Needs no scene. Synchronous, see "Ordering" below.
+ *
+ * pt_scene_deform_device: pt_scene_deform with d_positions / d_normals in device memory. After PT_OK the resident scene equals, in everything pt_scene_deform
+ * promises, the scene after pt_scene_deform with the same values read from host arrays. The library computes each mesh's box again itself (it never takes a
+ * caller's word for a conservative box) and the expand kernel reads the caller's buffers in place: no staging buffer is reserved.
+ * Ordering: both calls are synchronous and work on the default stream. They open with a hipDeviceSynchronize of the context's device, which is also what orders
+ *   them behind whatever stream produced the vertices: work queued on any stream of that device before the call is complete before the buffers are read. The
+ *   caller's buffers are free again when the call returns.
+ * Pointers: d_positions (and d_normals, if given) must be 8-byte aligned device memory of the context's device, as hipPointerGetAttributes reports it, and the
+ *   allocation (hipMemGetAddressRange) must reach n_vertices x 24 bytes beyond the pointer; a pointer into the middle of a larger allocation is fine. Pageable or
+ *   pinned host memory, managed memory and another device's memory are refused: no kernel is launched on a pointer that fails the check.
+ * Errors, all before the first write (the resident scene stays usable): PT_ERR_ARGUMENT (everything pt_scene_deform refuses, a pass in flight included; NULL
+ *   d_positions / bounds_invtrans / out / non_finite; a pointer that fails the check above; non_finite != 0 or a mesh box beyond +-1e18, in pt_scene_deform's
+ *   words; n_vertices >= 2^32), PT_ERR_NO_SCENE, PT_ERR_DEVICE. PT_ERR_SCENE as for pt_scene_update: the context then has NO scene. */
+int pt_vertex_bounds_device(pt_context *ctx, uint64_t n_vertices, const double *d_positions, double out[6], uint64_t *non_finite);
+typedef struct {
+    uint32_t mesh;                  /* index into the uploaded scene's meshes                                   */
+    const double *d_positions;      /* DEVICE, n_vertices x 3, the vertex count the mesh was uploaded with       */
+    const double *d_normals;        /* DEVICE, n_vertices x 3, or NULL: the resident normals stay                */
+    const double *bounds_invtrans;  /* HOST, 16 doubles, as in pt_mesh_deform                                    */
+    int32_t rebuild;                /* as in pt_mesh_deform                                                      */
+} pt_mesh_deform_device;
+int pt_scene_deform_device(pt_context *ctx, uint32_t n_deforms, const pt_mesh_deform_device *deforms,
+                           const pt_scene_motion *motion, const pt_kdtree *kd);
+
 /* Renders with host buffers. background: per pt_render_params.background_rows. rgb: height x width
  * x 3 bytes, only pixels of the slice that belong to this tile rank are written. linear (optional):
  * height x width x 3 doubles, the sample mean before gamma (render.rs:45). */
@@ -465,6 +497,9 @@ uint64_t pt_test_scene_bytes(const pt_context *ctx);
 /* tests: out[0] the walks' stack_cap, out[1] who built the scene-level tree last (0 pt_scene_upload, 1 pt_scene_update on the host, 2 on the device),
  * out[2] the device build's clustering rounds, out[3] bytes of the tree buffers (bvh, bvh4, bvh_items) */
 int pt_test_scene_info(const pt_context *ctx, uint64_t out[4]);
+/* tests: the shape of pt_vertex_bounds_device's reduction on this context's device: out[0] = vertices a block takes per step (its thread count), out[1] = the
+ * most blocks it launches. More than out[0] vertices use several blocks, more than out[0] x out[1] several grid strides. */
+int pt_test_vertex_box_shape(const pt_context *ctx, uint64_t out[2]);
 int pt_test_math(pt_context *ctx, int op, uint64_t n, const double *a, const double *b, double *out);
 /* (ABI 6) No GPU, no context: x[i]^y[i] by the HOST build of the kernels' pow (csrc/pt_pow.h) in `port` and by this machine's
  * libm in `libm` - the pin of the restated glibc algorithm against the library the reference calls. */

@@ -135,6 +135,20 @@ int ph_renderer_deform(ph_renderer *r, const ph_scene *scene, int rebuild);
 /* As ph_scene_same_structure, for ph_renderer_deform: vertex count, triangles, texture coordinates and presence of normals of a mesh must be equal, the
  * values of positions and normals may differ. */
 int ph_scene_same_topology(const ph_scene *a, const ph_scene *b, char *why, size_t n);
+/* Resident meshes deformed from vertices that are already in the memory of the renderer's device (pt_vertex_bounds_device + pt_scene_deform_device): per
+ * mesh its index in the renderer's numbering (the order in which the flattened nodes first use the meshes: ph_renderer_deform's), a device pointer to
+ * n_vertices x 3 doubles and optionally one to as many normals (NULL: the resident normals stay). `moved` may be NULL; otherwise it must have the structure of
+ * the resident scene (ph_scene_same_structure) and its transforms, lights and ambient light move as in ph_renderer_update. rebuild as in ph_renderer_deform.
+ * Nothing per vertex crosses the bus. The call is synchronous and ordered behind every stream of the device (see pt_scene_deform_device). A mesh deformed
+ * this way is remembered as posed on the device: a later ph_renderer_deform sends it whatever its comparison against the host's copy says.
+ * PH_ERR_ARGUMENT: the k-d traversal (its tree is built by the host from the meshes' bounds, which the host no longer has; the C ABI supports it with the
+ * caller's tree), a renderer with several ranks (each rank's device needs its own copy of the vertices), a mesh index out of range, another structure.
+ * PH_ERR_RUNTIME: what the library refuses (a pointer that is not device memory of that device, non-finite coordinates, ...). */
+typedef struct { uint32_t mesh; const double *d_positions; const double *d_normals; } ph_device_mesh;
+int ph_renderer_deform_device(ph_renderer *r, uint32_t n_meshes, const ph_device_mesh *meshes, int rebuild, const ph_scene *moved);
+/* Distinct meshes of the renderer's scene, and the vertex count of mesh `mesh` in the renderer's numbering (negative: PH_ERR_*). Need no GPU work. */
+int64_t ph_renderer_mesh_count(ph_renderer *r);
+int64_t ph_renderer_mesh_vertices(ph_renderer *r, uint32_t mesh);
 
 /* Radiance along rays of the caller's own (see pt_radiance): n x 3 f64 origins and directions in world space, `background` 3 doubles or n x 3
  * (params->background_per_ray), rgb n x 3 f64 out: one linear sample of Ray::color per ray. A renderer spread over a node runs the pass on rank 0's context. */

@@ -100,6 +100,11 @@ class PtMeshDeform(C.Structure):
     _fields_ = [("mesh", C.c_uint32), ("positions", _dp), ("normals", _dp), ("bounds_invtrans", _dp), ("rebuild", C.c_int32)]
 
 
+class PtMeshDeformDevice(C.Structure):
+    """pt_mesh_deform_device: pt_mesh_deform with the positions (and normals) in DEVICE memory; bounds_invtrans stays a host pointer."""
+    _fields_ = [("mesh", C.c_uint32), ("d_positions", C.c_void_p), ("d_normals", C.c_void_p), ("bounds_invtrans", _dp), ("rebuild", C.c_int32)]
+
+
 class PtRaysParams(C.Structure):
     _fields_ = [("n", C.c_uint64), ("any_hit", C.c_int32), ("reorder", C.c_int32)]
 
@@ -138,7 +143,8 @@ EXPORTS = ["pt_abi_version", "pt_device_count", "pt_context_create", "pt_context
            "pt_node_scene_upload", "pt_node_render", "pt_node_upload_background", "pt_node_render_resident", "pt_node_download_image",
            "pt_node_device", "pt_node_frame_begin", "pt_node_frame_end", "pt_node_frames_in_flight", "pt_node_last_frame_host_ms", "pt_node_last_frame_rank_kernel_ms", "pt_test_pow_host", "pt_test_libm_host",
            "pt_aov", "pt_aov_device", "pt_aov_finish", "pt_rays", "pt_rays_device", "pt_rays_finish",
-           "pt_radiance", "pt_radiance_device", "pt_radiance_finish", "pt_scene_update", "pt_node_scene_update", "pt_scene_deform", "pt_node_scene_deform", "pt_scene_mesh_rebuildable", "pt_test_scene_bytes", "pt_test_scene_info"]
+           "pt_radiance", "pt_radiance_device", "pt_radiance_finish", "pt_scene_update", "pt_node_scene_update", "pt_scene_deform", "pt_node_scene_deform", "pt_scene_mesh_rebuildable", "pt_test_scene_bytes", "pt_test_scene_info",
+           "pt_vertex_bounds_device", "pt_scene_deform_device", "pt_test_vertex_box_shape"]
 
 
 def header_functions():
@@ -181,6 +187,12 @@ def lib() -> C.CDLL:
         l.pt_node_scene_deform.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(PtMeshDeform), C.POINTER(PtSceneMotion), C.POINTER(PtKdTree)]
         l.pt_scene_mesh_rebuildable.restype = C.c_int
         l.pt_scene_mesh_rebuildable.argtypes = [C.c_void_p, C.c_uint32]
+        l.pt_vertex_bounds_device.restype = C.c_int
+        l.pt_vertex_bounds_device.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, _dp, _u64p]
+        l.pt_scene_deform_device.restype = C.c_int
+        l.pt_scene_deform_device.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(PtMeshDeformDevice), C.POINTER(PtSceneMotion), C.POINTER(PtKdTree)]
+        l.pt_test_vertex_box_shape.restype = C.c_int
+        l.pt_test_vertex_box_shape.argtypes = [C.c_void_p, C.POINTER(C.c_uint64 * 2)]
         l.pt_test_scene_bytes.restype = C.c_uint64
         l.pt_test_scene_bytes.argtypes = [C.c_void_p]
         l.pt_test_scene_info.restype = C.c_int
@@ -323,6 +335,18 @@ class Context:
         """pt_scene_deform with a list of PtMeshDeform"""
         arr = (PtMeshDeform * max(len(deforms), 1))(*deforms)
         self.check(lib().pt_scene_deform(self._h, len(deforms), arr, C.byref(motion), C.byref(kd) if kd is not None else None), "pt_scene_deform")
+
+    def deform_device(self, deforms, motion: "PtSceneMotion", kd: Optional[PtKdTree] = None):
+        """pt_scene_deform_device with a list of PtMeshDeformDevice (device pointers as integers, e.g. a torch tensor's data_ptr())"""
+        arr = (PtMeshDeformDevice * max(len(deforms), 1))(*deforms)
+        self.check(lib().pt_scene_deform_device(self._h, len(deforms), arr, C.byref(motion), C.byref(kd) if kd is not None else None), "pt_scene_deform_device")
+
+    def vertex_bounds_device(self, d_positions: int, n_vertices: int):
+        """pt_vertex_bounds_device: (box, non_finite) of n_vertices x 3 f64 at the device address d_positions; box = 6 doubles, min then max per axis"""
+        box = np.zeros(6)
+        bad = C.c_uint64(0)
+        self.check(lib().pt_vertex_bounds_device(self._h, n_vertices, C.c_void_p(d_positions), _p(box, _dp), C.byref(bad)), "pt_vertex_bounds_device")
+        return box, int(bad.value)
 
     def render(self, cam: PtCamera, background: np.ndarray, params: PtRenderParams, rgb: np.ndarray, linear: Optional[np.ndarray] = None) -> dict:
         st = PtStats()

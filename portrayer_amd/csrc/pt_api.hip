@@ -347,6 +347,7 @@ struct pt_context {
     // pt_scene_deform, allocated by the first deform of the context: the meshes' indices, a parent index and an arrival counter per tree node (the refit),
     // and the staging buffer the new vertices are copied to
     PtBuf mesh_idx, tree_parent, tree_arrive, deform_stage;
+    PtBuf vbox;  // pt_vertex_bounds_device / pt_scene_deform_device: the reduction's per-block partials (PtVboxPartial); a work buffer, not part of the scene
     double root_lo[3] = {0.0, 0.0, 0.0}, root_hi[3] = {0.0, 0.0, 0.0};  // the scene tree's root box: union of the flattened nodes' world boxes (reorder = 1 quantises origins inside it)
 };
 #define PT_SLOT_BYTES (256 + sizeof(PtCounters))
@@ -412,7 +413,7 @@ extern "C" void pt_context_destroy(pt_context* c) {
     if (!c) return;
     hipSetDevice(c->device);
     PtBuf* bufs[] = {&c->inv, &c->fwd, &c->nrm, &c->info, &c->tri_v, &c->tri_e, &c->tri_leaf, &c->tri_n, &c->meshes, &c->materials, &c->lights,
-                     &c->bvh, &c->bvh4, &c->bvh_items, &c->kd, &c->kd_items, &c->mat_maps, &c->uv_trans, &c->tex, &c->tex_rgb, &c->srgb_lut, &c->tri_uv, &c->texview, &c->mkd, &c->mkd_items, &c->slot[0].spill, &c->slot[0].stack_spill, &c->slot[0].accum, &c->slot[0].misc, &c->slot[1].spill, &c->slot[1].stack_spill, &c->slot[1].accum, &c->slot[1].misc, &c->bg, &c->rgb, &c->linear, &c->misc, &c->node_box, &c->kd_box, &c->mkd_box, &c->mkd_item_box, &c->kd_ref, &c->g_inv, &c->g_fwd, &c->g_nrm, &c->chain_off, &c->chain, &c->dfs_rank, &c->hier_rec, &c->own_inv, &c->mesh_box_dev, &c->mesh_idx, &c->tree_parent, &c->tree_arrive, &c->deform_stage};
+                     &c->bvh, &c->bvh4, &c->bvh_items, &c->kd, &c->kd_items, &c->mat_maps, &c->uv_trans, &c->tex, &c->tex_rgb, &c->srgb_lut, &c->tri_uv, &c->texview, &c->mkd, &c->mkd_items, &c->slot[0].spill, &c->slot[0].stack_spill, &c->slot[0].accum, &c->slot[0].misc, &c->slot[1].spill, &c->slot[1].stack_spill, &c->slot[1].accum, &c->slot[1].misc, &c->bg, &c->rgb, &c->linear, &c->misc, &c->node_box, &c->kd_box, &c->mkd_box, &c->mkd_item_box, &c->kd_ref, &c->g_inv, &c->g_fwd, &c->g_nrm, &c->chain_off, &c->chain, &c->dfs_rank, &c->hier_rec, &c->own_inv, &c->mesh_box_dev, &c->mesh_idx, &c->tree_parent, &c->tree_arrive, &c->deform_stage, &c->vbox};
     for (PtBuf* b : bufs) if (b->p) hipFree(b->p);
     if (c->aov.queued) { if (c->aov.closed) hipEventSynchronize(c->aov.copy_done); else hipStreamSynchronize(c->aov.stream); }  // (pt_aov_wait)
     for (PtBuf* b : {&c->aov.stack_spill, &c->aov.misc, &c->aov.out[0], &c->aov.out[1], &c->aov.out[2], &c->aov.out[3], &c->aov.out[4], &c->aov.out[5]}) if (b->p) hipFree(b->p);
@@ -548,11 +549,12 @@ static void pt_pack_graph(uint32_t n, uint32_t g, const double* graph_trans, con
 
 // The box of a mesh's vertices and its largest extent (floored at 1e-30): triangle boxes are padded by 1e-7 ext, the mesh's own box by 1e-5 ext.
 // pt_scene_upload and pt_scene_deform both call this.
+static double pt_box_extent(const PtBuildBox& b) { return std::max(std::max(b.hi[0] - b.lo[0], b.hi[1] - b.lo[1]), std::max(b.hi[2] - b.lo[2], 1e-30)); }
 static double pt_mesh_vertex_box(const double* pos, uint64_t n_verts, PtBuildBox* mb) {
     *mb = pt_bvh_detail::empty_box();
     for (uint64_t v = 0; v < n_verts; v++)
         for (int k = 0; k < 3; k++) { mb->lo[k] = std::min(mb->lo[k], pos[3 * v + k]); mb->hi[k] = std::max(mb->hi[k], pos[3 * v + k]); }
-    return std::max(std::max(mb->hi[0] - mb->lo[0], mb->hi[1] - mb->lo[1]), std::max(mb->hi[2] - mb->lo[2], 1e-30));
+    return pt_box_extent(*mb);
 }
 
 // the padded model box of a stand-alone triangle (9 f64)
@@ -1252,6 +1254,14 @@ struct PtUpdatePlan {
     PtBvhRef tlas;
 };
 
+// the copies and kernels of an update or a deform are not ordered against the context's non-blocking streams
+static int pt_refuse_in_flight(pt_context* c) {
+    bool in_flight = c->aov.pending || c->rays.pending || c->radiance.pending;
+    for (const auto& sl : c->slot) in_flight = in_flight || sl.pending;
+    if (in_flight) return pt_fail(c, PT_ERR_ARGUMENT, "a render is in flight: pt_render_finish / pt_aov_finish / pt_rays_finish / pt_radiance_finish first");
+    return PT_OK;
+}
+
 // Every check of pt_scene_update and everything its host side computes. `mesh_box`: the meshes' padded model boxes the moved scene has (the resident ones,
 // or a deform's). Writes nothing to the device; PT_ERR_SCENE leaves the context without a scene, as after a refused upload.
 // On the host-build path it does set view.stack_cap (pt_set_stack_cap) from the mesh depths as they are BEFORE the call: for a deform with rebuild = 1
@@ -1270,10 +1280,7 @@ static int pt_update_prepare(pt_context* c, const pt_scene_motion* mo, const pt_
     if (mo->lights && mo->n_lights != res.n_lights) return pt_fail(c, PT_ERR_ARGUMENT, "n_lights differs from the uploaded scene's");
     if (res.traverse == PT_TRAVERSE_KD && !kd) return pt_fail(c, PT_ERR_ARGUMENT, "PT_TRAVERSE_KD needs the host-built k-d tree");
     if (res.traverse != PT_TRAVERSE_KD && kd) return pt_fail(c, PT_ERR_ARGUMENT, "a k-d tree for a scene that was not uploaded with PT_TRAVERSE_KD");
-    // the copies and kernels below are not ordered against the context's non-blocking streams
-    bool in_flight = c->aov.pending || c->rays.pending || c->radiance.pending;
-    for (const auto& sl : c->slot) in_flight = in_flight || sl.pending;
-    if (in_flight) return pt_fail(c, PT_ERR_ARGUMENT, "a render is in flight: pt_render_finish / pt_aov_finish / pt_rays_finish / pt_radiance_finish first");
+    if (int rc = pt_refuse_in_flight(c)) return rc;
 
     // ---- everything the host computes, before the first write
     pt_pack_node_matrices(n, mo->trans, mo->invtrans, mo->normal_trans, p.inv, p.fwd, p.nrm);
@@ -1359,19 +1366,87 @@ extern "C" int pt_scene_update(pt_context* c, const pt_scene_motion* mo, const p
 // Scene deform: new vertices for resident meshes under the topology they were uploaded with, then the update above. Per mesh the host
 // computes the box (the upload's function) and copies the vertices; the device expands the triangle records through the resident indices
 // (pt_device_expand_mesh), refits the mesh's tree in place or rebuilds it there (pt_device_refit_mesh_tree / pt_device_build_mesh_tree) and re-derives
-// the four-child form and the leaf-order records for the mesh's node and item ranges alone.
+// the four-child form and the leaf-order records for the mesh's node and item ranges alone. With the vertices already in device memory
+// (pt_scene_deform_device) the box is a reduction on the device (pt_device_vertex_box) and the expand kernel reads the caller's buffer in place.
 // ------------------------------------------------------------------------------------------------
-extern "C" int pt_scene_deform(pt_context* c, uint32_t n_deforms, const pt_mesh_deform* deforms, const pt_scene_motion* mo, const pt_kdtree* kd) {
-    if (!c || !mo || (n_deforms && !deforms)) return PT_ERR_ARGUMENT;
+// One mesh of a deform, wherever its vertices are: pt_mesh_deform's fields with host pointers, pt_mesh_deform_device's with device pointers.
+struct PtDeformItem {
+    uint32_t mesh;
+    const double *positions, *normals, *bounds_invtrans;
+    int32_t rebuild;
+};
+
+// What keeps a caller's mistake from becoming a GPU fault: `p` must be 8-byte aligned device memory of the context's device whose allocation reaches `bytes`
+// beyond it. The context's device is current.
+static int pt_check_device_pointer(pt_context* c, const void* p, uint64_t bytes, const std::string& what) {
+    if ((uintptr_t)p & 7u) return pt_fail(c, PT_ERR_ARGUMENT, what + " is not 8-byte aligned");
+    hipPointerAttribute_t at;
+    memset(&at, 0, sizeof at);
+    if (hipPointerGetAttributes(&at, p) != hipSuccess) {
+        (void)hipGetLastError();  // (pageable host memory: the query itself fails, and leaves its error behind)
+        return pt_fail(c, PT_ERR_ARGUMENT, what + " is not device memory (hipPointerGetAttributes does not know the pointer)");
+    }
+    if (at.type != hipMemoryTypeDevice || at.isManaged)
+        return pt_fail(c, PT_ERR_ARGUMENT, what + " is not device memory (host, pinned or managed memory: copy it to the device, or use pt_scene_deform)");
+    if (at.device != c->device)
+        return pt_fail(c, PT_ERR_ARGUMENT, what + " is memory of device " + std::to_string(at.device) + ", the context is on device " + std::to_string(c->device));
+    hipDeviceptr_t base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess || !base) {
+        (void)hipGetLastError();
+        return pt_fail(c, PT_ERR_ARGUMENT, what + ": hipMemGetAddressRange does not know the pointer's allocation");
+    }
+    const uint64_t off = (uint64_t)((const char*)p - (const char*)base);
+    if ((const char*)p < (const char*)base || off > size || bytes > size - off)
+        return pt_fail(c, PT_ERR_ARGUMENT, what + ": the allocation ends " + std::to_string(size - std::min<uint64_t>(off, size)) + " bytes after the pointer, " + std::to_string(bytes) + " are needed (n_vertices x 24)");
+    return PT_OK;
+}
+
+// The box and the count of non-finite coordinates of n x 3 f64 in device memory (pt_device_vertex_box): the pointer has passed pt_check_device_pointer, the
+// context's device is current and synchronised. One copy brings the result back.
+static int pt_vertex_box_on_device(pt_context* c, uint64_t n, const double* d_pos, PtBuildBox* box, uint64_t* non_finite) {
+    int rc = pt_reserve(c, c->vbox, (size_t)pt_vertex_box_partials(c->n_cu) * sizeof(PtVboxPartial));
+    if (rc) return rc;
+    PT_HIP(c, pt_device_vertex_box(d_pos, n, c->n_cu, (PtVboxPartial*)c->vbox.p, nullptr));
+    PtVboxPartial got;
+    PT_HIP(c, hipMemcpy(&got, c->vbox.p, sizeof got, hipMemcpyDeviceToHost));
+    for (int k = 0; k < 3; k++) { box->lo[k] = got.v[k]; box->hi[k] = got.v[3 + k]; }
+    *non_finite = got.non_finite;
+    return PT_OK;
+}
+
+extern "C" int pt_vertex_bounds_device(pt_context* c, uint64_t n_vertices, const double* d_positions, double out[6], uint64_t* non_finite) {
+    if (!c) return PT_ERR_ARGUMENT;
+    if (!out || !non_finite) return pt_fail(c, PT_ERR_ARGUMENT, "out and non_finite are required");
+    if (n_vertices > 0xFFFFFFFFull) return pt_fail(c, PT_ERR_ARGUMENT, "n_vertices must be below 2^32");
+    PtBuildBox box = pt_bvh_detail::empty_box();
+    *non_finite = 0;
+    if (n_vertices) {
+        if (!d_positions) return pt_fail(c, PT_ERR_ARGUMENT, "d_positions is required");
+        PT_HIP(c, hipSetDevice(c->device));
+        int rc = pt_check_device_pointer(c, d_positions, n_vertices * 24, "d_positions");
+        if (rc) return rc;
+        PT_HIP(c, hipDeviceSynchronize());  // behind whatever stream produced the vertices
+        if ((rc = pt_vertex_box_on_device(c, n_vertices, d_positions, &box, non_finite))) return rc;
+    }
+    for (int k = 0; k < 3; k++) { out[k] = box.lo[k]; out[3 + k] = box.hi[k]; }
+    return PT_OK;
+}
+
+// pt_scene_deform and pt_scene_deform_device: the two differ in where a mesh's box comes from (the host loop / the device reduction behind the pointer check)
+// and in which pointer the expand kernel reads (the staging buffer the vertices are copied to / the caller's buffer in place).
+static int pt_deform_meshes(pt_context* c, const std::vector<PtDeformItem>& items, bool on_device, const pt_scene_motion* mo, const pt_kdtree* kd) {
     if (!c->have_scene) return pt_fail(c, PT_ERR_NO_SCENE, "no scene uploaded");
     pt_context::Resident& res = c->res;
+    const uint32_t n_deforms = (uint32_t)items.size();
     struct NewBox { PtBuildBox vertex, padded; double ext; };
     std::vector<NewBox> nb(n_deforms);
     std::vector<PtBuildBox> mesh_box = res.mesh_box;
     {
         std::vector<uint8_t> named(res.place.size(), 0);
+        bool synchronised = false;
         for (uint32_t d = 0; d < n_deforms; d++) {
-            const pt_mesh_deform& df = deforms[d];
+            const PtDeformItem& df = items[d];
             const std::string at = "deform " + std::to_string(d) + ": ";
             if (!df.positions || !df.bounds_invtrans) return pt_fail(c, PT_ERR_ARGUMENT, at + "positions and bounds_invtrans are required");
             if (df.mesh >= res.place.size()) return pt_fail(c, PT_ERR_ARGUMENT, at + "mesh index out of range");
@@ -1384,11 +1459,28 @@ extern "C" int pt_scene_deform(pt_context* c, uint32_t n_deforms, const pt_mesh_
             if (df.rebuild != 0 && df.rebuild != 1) return pt_fail(c, PT_ERR_ARGUMENT, at + "rebuild must be 0 or 1");
             if (df.rebuild && !pl.device_built)
                 return pt_fail(c, PT_ERR_ARGUMENT, at + "rebuild = 1 needs a tree the device built at upload (its place has the worst-case size); this one was built on the host");
-            nb[d].ext = pt_mesh_vertex_box(df.positions, pl.n_verts, &nb[d].vertex);
+            bool finite = true;
+            if (on_device) {
+                nb[d].vertex = pt_bvh_detail::empty_box();
+                if (pl.n_verts) {  // (nothing is launched on an empty mesh, and nothing of it is read)
+                    int rc = pt_refuse_in_flight(c);
+                    if (rc) return rc;
+                    PT_HIP(c, hipSetDevice(c->device));
+                    if ((rc = pt_check_device_pointer(c, df.positions, (uint64_t)pl.n_verts * 24, at + "d_positions"))) return rc;
+                    if (df.normals && (rc = pt_check_device_pointer(c, df.normals, (uint64_t)pl.n_verts * 24, at + "d_normals"))) return rc;
+                    if (!synchronised) PT_HIP(c, hipDeviceSynchronize());  // behind whatever stream produced the vertices
+                    synchronised = true;
+                    uint64_t non_finite = 0;
+                    if ((rc = pt_vertex_box_on_device(c, pl.n_verts, df.positions, &nb[d].vertex, &non_finite))) return rc;
+                    finite = non_finite == 0;
+                }
+                nb[d].ext = pt_box_extent(nb[d].vertex);
+            } else {
+                nb[d].ext = pt_mesh_vertex_box(df.positions, pl.n_verts, &nb[d].vertex);
+                for (uint64_t v = 0; v < 3 * (uint64_t)pl.n_verts; v++) finite = finite && std::isfinite(df.positions[v]);
+            }
             nb[d].padded = nb[d].vertex;
             for (int k = 0; k < 3; k++) { nb[d].padded.lo[k] -= 1e-5 * nb[d].ext; nb[d].padded.hi[k] += 1e-5 * nb[d].ext; }
-            bool finite = true;
-            for (uint64_t v = 0; v < 3 * (uint64_t)pl.n_verts; v++) finite = finite && std::isfinite(df.positions[v]);
             for (int k = 0; k < 3; k++) finite = finite && nb[d].padded.lo[k] >= -PT_BOX_LIMIT && nb[d].padded.hi[k] <= PT_BOX_LIMIT;
             if (!finite) return pt_fail(c, PT_ERR_ARGUMENT, at + "a coordinate is not finite or the mesh's box reaches beyond +-1e18");
             mesh_box[df.mesh] = nb[d].padded;
@@ -1411,21 +1503,24 @@ extern "C" int pt_scene_deform(pt_context* c, uint32_t n_deforms, const pt_mesh_
     bool any_refit = false;
     size_t stage_bytes = 0;
     for (uint32_t d = 0; d < n_deforms; d++) {
-        any_refit = any_refit || !deforms[d].rebuild;
-        stage_bytes = std::max(stage_bytes, (size_t)res.place[deforms[d].mesh].n_verts * 24 * (deforms[d].normals ? 2 : 1));
+        any_refit = any_refit || !items[d].rebuild;
+        stage_bytes = std::max(stage_bytes, (size_t)res.place[items[d].mesh].n_verts * 24 * (items[d].normals ? 2 : 1));
     }
-    if ((rc = pt_reserve(c, c->deform_stage, stage_bytes))) return rc;
+    if (!on_device && (rc = pt_reserve(c, c->deform_stage, stage_bytes))) return rc;  // (vertices in device memory are read where they are)
     if (any_refit && ((rc = pt_reserve(c, c->tree_parent, std::max<size_t>(res.tree_nodes, 1) * 4)) || (rc = pt_reserve(c, c->tree_arrive, std::max<size_t>(res.tree_nodes, 1) * 4)))) return rc;
     const bool write_normals = res.any_normals;  // (tri_n is empty unless a node shades smoothly: the upload then drops the normals it is given, and so does this)
     for (uint32_t d = 0; d < n_deforms; d++) {
-        const pt_mesh_deform& df = deforms[d];
+        const PtDeformItem& df = items[d];
         pt_context::Resident::MeshPlace& pl = res.place[df.mesh];
         PtMeshInfo& mi = res.meshes[df.mesh];
         const size_t pos_bytes = (size_t)pl.n_verts * 24;
-        PT_HIP(c, hipMemcpy(c->deform_stage.p, df.positions, pos_bytes, hipMemcpyHostToDevice));
-        if (df.normals) PT_HIP(c, hipMemcpy((char*)c->deform_stage.p + pos_bytes, df.normals, pos_bytes, hipMemcpyHostToDevice));
-        const double* d_pos = (const double*)c->deform_stage.p;
-        const double* d_nrm = df.normals && write_normals ? (const double*)((const char*)c->deform_stage.p + pos_bytes) : nullptr;
+        const double *d_pos = df.positions, *d_nrm = df.normals && write_normals ? df.normals : nullptr;
+        if (!on_device) {
+            PT_HIP(c, hipMemcpy(c->deform_stage.p, df.positions, pos_bytes, hipMemcpyHostToDevice));
+            if (df.normals) PT_HIP(c, hipMemcpy((char*)c->deform_stage.p + pos_bytes, df.normals, pos_bytes, hipMemcpyHostToDevice));
+            d_pos = (const double*)c->deform_stage.p;
+            if (d_nrm) d_nrm = (const double*)((const char*)c->deform_stage.p + pos_bytes);
+        }
         PT_HIP(c, pt_device_expand_mesh((const uint32_t*)c->mesh_idx.p, mi.tri_first, mi.tri_count, d_pos, d_nrm, pl.n_verts, (double*)c->tri_v.p, (double*)c->tri_e.p,
                                         d_nrm ? (double*)c->tri_n.p : nullptr, nullptr));
         const double pad = 1e-7 * nb[d].ext;
@@ -1473,6 +1568,20 @@ extern "C" int pt_scene_deform(pt_context* c, uint32_t n_deforms, const pt_mesh_
     return pt_update_commit(c, mo, plan);
 }
 
+extern "C" int pt_scene_deform(pt_context* c, uint32_t n_deforms, const pt_mesh_deform* deforms, const pt_scene_motion* mo, const pt_kdtree* kd) {
+    if (!c || !mo || (n_deforms && !deforms)) return PT_ERR_ARGUMENT;
+    std::vector<PtDeformItem> items(n_deforms);
+    for (uint32_t d = 0; d < n_deforms; d++) items[d] = PtDeformItem{deforms[d].mesh, deforms[d].positions, deforms[d].normals, deforms[d].bounds_invtrans, deforms[d].rebuild};
+    return pt_deform_meshes(c, items, false, mo, kd);
+}
+
+extern "C" int pt_scene_deform_device(pt_context* c, uint32_t n_deforms, const pt_mesh_deform_device* deforms, const pt_scene_motion* mo, const pt_kdtree* kd) {
+    if (!c || !mo || (n_deforms && !deforms)) return PT_ERR_ARGUMENT;
+    std::vector<PtDeformItem> items(n_deforms);
+    for (uint32_t d = 0; d < n_deforms; d++) items[d] = PtDeformItem{deforms[d].mesh, deforms[d].d_positions, deforms[d].d_normals, deforms[d].bounds_invtrans, deforms[d].rebuild};
+    return pt_deform_meshes(c, items, true, mo, kd);
+}
+
 extern "C" int pt_scene_mesh_rebuildable(const pt_context* c, uint32_t mesh) {
     if (!c) return PT_ERR_ARGUMENT;
     if (!c->have_scene) return PT_ERR_NO_SCENE;
@@ -1490,6 +1599,12 @@ extern "C" uint64_t pt_test_scene_bytes(const pt_context* c) {
     uint64_t total = 0;
     for (const PtBuf* b : bufs) total += b->bytes;
     return total;
+}
+
+extern "C" int pt_test_vertex_box_shape(const pt_context* c, uint64_t out[2]) {
+    if (!c || !out) return PT_ERR_ARGUMENT;
+    out[0] = PT_VBOX_BLOCK; out[1] = pt_vertex_box_partials(c->n_cu);
+    return PT_OK;
 }
 
 // tests: out[0] = stack_cap, out[1] = who built the scene-level tree last (0 the upload, 1 an update on the host, 2 an update on the device),

@@ -67,3 +67,22 @@ hipError_t pt_device_tree_parents(const PtBvhNode* d_nodes, uint32_t node_first,
 hipError_t pt_device_refit_mesh_tree(PtBvhNode* d_nodes, uint32_t node_first, uint32_t node_count, const uint32_t* d_items, uint32_t item_first,
                                      uint32_t item_count, const double* d_tri_v, uint32_t tri_first, uint32_t tri_count, double pad,
                                      const uint32_t* d_parent, uint32_t* d_arrive, hipStream_t stream);
+
+// ---- pt_vertex_bounds_device / pt_scene_deform_device: the box of vertices that are already in device memory -------------------------------
+// One pass over d_pos (n_verts x 3 f64, 8-byte aligned) read as a flat array, so that a wavefront's 64 lanes load 64 consecutive doubles: a block of
+// PT_VBOX_BLOCK threads takes PT_VBOX_BLOCK whole vertices per step (three loads per thread, one coordinate of each axis), the grid strides over those
+// steps. Every minimum / maximum is carried as (value, lowest vertex index attaining it) through the lanes of a wavefront (registers), the block's
+// wavefronts (LDS) and the blocks (one PtVboxPartial per block, plain stores, folded by a one-block launch of the same reduction): the six doubles carry
+// the bits pt_mesh_vertex_box's loop leaves - it keeps the first extreme it meets, which matters where the extreme is a zero that occurs with both signs.
+// NaN and +-inf coordinates take no part and are counted. n_verts = 0 or nothing finite: the empty box (lo = +inf, hi = -inf). No atomics.
+// The grid is min(steps, PT_VBOX_BLOCKS_PER_CU * n_cu) blocks; d_partials holds pt_vertex_box_partials(n_cu) records. Queued on `stream`: the result is at
+// d_partials[0] when the stream has drained.
+#define PT_VBOX_BLOCK 256
+#define PT_VBOX_BLOCKS_PER_CU 4
+struct PtVboxPartial {
+    double v[6];        // lo xyz, hi xyz
+    uint32_t at[6];     // the lowest vertex index attaining each (0xFFFFFFFF: none)
+    uint64_t non_finite;
+};
+inline uint32_t pt_vertex_box_partials(int n_cu) { return (uint32_t)PT_VBOX_BLOCKS_PER_CU * (uint32_t)(n_cu > 0 ? n_cu : 1); }
+hipError_t pt_device_vertex_box(const double* d_pos, uint64_t n_verts, int n_cu, PtVboxPartial* d_partials, hipStream_t stream);

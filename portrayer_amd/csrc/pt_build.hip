@@ -667,3 +667,125 @@ hipError_t pt_device_refit_mesh_tree(PtBvhNode* d_nodes, uint32_t node_first, ui
     hipLaunchKernelGGL(pt_refit_kernel, dim3((node_count + PT_BUILD_BLOCK - 1) / PT_BUILD_BLOCK), dim3(PT_BUILD_BLOCK), 0, stream, a);
     return hipGetLastError();
 }
+
+// ------------------------------------------------------------------------------------------------
+// pt_device_vertex_box (pt_build.h): the box of vertices that are already in device memory.
+// ------------------------------------------------------------------------------------------------
+namespace {
+
+struct PtVboxAcc {
+    double v[6];
+    uint32_t at[6];
+    unsigned long long bad;
+};
+
+__device__ __forceinline__ void pt_vbox_clear(PtVboxAcc& a) {
+#pragma unroll
+    for (int k = 0; k < 3; k++) { a.v[k] = INFINITY; a.v[3 + k] = -INFINITY; a.at[k] = a.at[3 + k] = 0xFFFFFFFFu; }
+    a.bad = 0ull;
+}
+
+// entry k of `a` against (v, at): the smaller (k < 3) or larger value stays, of two equal ones (+0.0 and -0.0 are the pair with different bits) the one
+// met first by a loop in ascending vertex order
+__device__ __forceinline__ void pt_vbox_take(PtVboxAcc& a, int k, double v, uint32_t at) {
+    const bool better = k < 3 ? v < a.v[k] : a.v[k] < v;
+    if (better || (v == a.v[k] && at < a.at[k])) { a.v[k] = v; a.at[k] = at; }
+}
+
+// the block's accumulators folded into *out: across the wavefront's 64 lanes in registers, then across the block's wavefronts through LDS
+__device__ __forceinline__ void pt_vbox_block_reduce(PtVboxAcc a, PtVboxPartial* out) {
+    __shared__ PtVboxPartial sh[PT_VBOX_BLOCK / 64];
+#pragma unroll
+    for (int step = 32; step >= 1; step >>= 1) {
+#pragma unroll
+        for (int k = 0; k < 6; k++) {
+            const double ov = __shfl_xor(a.v[k], step, 64);
+            const uint32_t oat = __shfl_xor(a.at[k], step, 64);
+            pt_vbox_take(a, k, ov, oat);
+        }
+        a.bad += __shfl_xor(a.bad, step, 64);
+    }
+    const uint32_t wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63u) == 0u) {
+#pragma unroll
+        for (int k = 0; k < 6; k++) { sh[wave].v[k] = a.v[k]; sh[wave].at[k] = a.at[k]; }
+        sh[wave].non_finite = a.bad;
+    }
+    __syncthreads();
+    if (threadIdx.x != 0u) return;
+    for (uint32_t w = 1; w < PT_VBOX_BLOCK / 64; w++) {
+#pragma unroll
+        for (int k = 0; k < 6; k++) pt_vbox_take(a, k, sh[w].v[k], sh[w].at[k]);
+        a.bad += sh[w].non_finite;
+    }
+#pragma unroll
+    for (int k = 0; k < 6; k++) { out->v[k] = a.v[k]; out->at[k] = a.at[k]; }
+    out->non_finite = a.bad;
+}
+
+__device__ __forceinline__ double pt_pick3(double x0, double x1, double x2, uint32_t s) { return s == 0u ? x0 : (s == 1u ? x1 : x2); }
+__device__ __forceinline__ uint32_t pt_pick3(uint32_t x0, uint32_t x1, uint32_t x2, uint32_t s) { return s == 0u ? x0 : (s == 1u ? x1 : x2); }
+
+// Step s covers vertices [s B, (s + 1) B), B = PT_VBOX_BLOCK: doubles [3 s B, 3 (s + 1) B) of the flat array, read as three rows of B consecutive doubles.
+// Element e = j B + thread of a step belongs to vertex s B + e / 3 and - B being 1 mod 3 - to axis (j + thread) % 3: a thread's row j always carries the
+// same axis, so it accumulates per row and sorts the rows into axes once, after the loop. Within a thread vertex indices only grow: `<` alone keeps the first.
+static_assert(PT_VBOX_BLOCK % 3 == 1 && PT_VBOX_BLOCK % 64 == 0, "the row-to-axis rule of pt_vbox_kernel");
+__global__ void __launch_bounds__(PT_VBOX_BLOCK) pt_vbox_kernel(const double* __restrict__ pos, unsigned long long n_verts, uint32_t n_steps,
+                                                                PtVboxPartial* __restrict__ partials) {
+    const uint32_t tid = threadIdx.x;
+    const unsigned long long n_flat = 3ull * n_verts;
+    double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    uint32_t lo_at[3] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu}, hi_at[3] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
+    unsigned long long bad = 0ull;
+    for (uint32_t s = blockIdx.x; s < n_steps; s += gridDim.x) {
+        const unsigned long long v0 = (unsigned long long)s * PT_VBOX_BLOCK;
+#pragma unroll
+        for (int j = 0; j < 3; j++) {
+            const uint32_t e = (uint32_t)j * PT_VBOX_BLOCK + tid;
+            const unsigned long long flat = 3ull * v0 + e;
+            if (flat >= n_flat) continue;
+            const double x = pos[flat];
+            const uint32_t at = (uint32_t)(v0 + e / 3u);
+            if (!(fabs(x) < INFINITY)) { bad++; continue; }  // NaN, +-inf
+            if (x < lo[j]) { lo[j] = x; lo_at[j] = at; }
+            if (hi[j] < x) { hi[j] = x; hi_at[j] = at; }
+        }
+    }
+    PtVboxAcc a;
+    const uint32_t r = tid % 3u;
+#pragma unroll
+    for (uint32_t k = 0; k < 3; k++) {
+        const uint32_t row = (k + 3u - r) % 3u;  // the row that carries axis k: (row + tid) % 3 == k
+        a.v[k] = pt_pick3(lo[0], lo[1], lo[2], row); a.at[k] = pt_pick3(lo_at[0], lo_at[1], lo_at[2], row);
+        a.v[3 + k] = pt_pick3(hi[0], hi[1], hi[2], row); a.at[3 + k] = pt_pick3(hi_at[0], hi_at[1], hi_at[2], row);
+    }
+    a.bad = bad;
+    pt_vbox_block_reduce(a, partials + blockIdx.x);
+}
+
+// one block: partials[0 .. n) folded into partials[0] (thread 0 alone reads and, behind the block's barrier, writes that record)
+__global__ void __launch_bounds__(PT_VBOX_BLOCK) pt_vbox_fold_kernel(PtVboxPartial* partials, uint32_t n) {
+    PtVboxAcc a;
+    pt_vbox_clear(a);
+    for (uint32_t p = threadIdx.x; p < n; p += PT_VBOX_BLOCK) {
+#pragma unroll
+        for (int k = 0; k < 6; k++) pt_vbox_take(a, k, partials[p].v[k], partials[p].at[k]);
+        a.bad += partials[p].non_finite;
+    }
+    pt_vbox_block_reduce(a, partials);
+}
+
+}  // namespace
+
+hipError_t pt_device_vertex_box(const double* d_pos, uint64_t n_verts, int n_cu, PtVboxPartial* d_partials, hipStream_t stream) {
+    if (!d_partials || (n_verts && !d_pos) || n_verts > 0xFFFFFFFFull) return hipErrorInvalidValue;
+    const uint64_t steps = std::max<uint64_t>(1, (n_verts + PT_VBOX_BLOCK - 1) / PT_VBOX_BLOCK);  // (n_verts = 0: one block that loads nothing writes the empty box)
+    const uint32_t blocks = (uint32_t)std::min<uint64_t>(steps, pt_vertex_box_partials(n_cu));
+    hipLaunchKernelGGL(pt_vbox_kernel, dim3(blocks), dim3(PT_VBOX_BLOCK), 0, stream, d_pos, (unsigned long long)n_verts, (uint32_t)steps, d_partials);
+    PT_TRY(hipGetLastError());
+    if (blocks > 1) {
+        hipLaunchKernelGGL(pt_vbox_fold_kernel, dim3(1), dim3(PT_VBOX_BLOCK), 0, stream, d_partials, blocks);
+        PT_TRY(hipGetLastError());
+    }
+    return hipSuccess;
+}

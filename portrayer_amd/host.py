@@ -19,7 +19,7 @@ _dp, _ip, _up, _u64p, _u8p = H._dp, H._ip, H._up, H._u64p, H._u8p
 
 EXPORTS = ["ph_last_error", "ph_scene_create", "ph_example_scene", "ph_scene_destroy", "ph_scene_counts", "ph_scene_export", "ph_scene_export_textures",
            "ph_scene_flatten", "ph_scene_kdtree", "ph_camera", "ph_obj_load", "ph_renderer_create", "ph_renderer_destroy",
-           "ph_renderer_context", "ph_renderer_ranks", "ph_renderer_node", "ph_renderer_prepare_ms", "ph_renderer_render", "ph_renderer_aov", "ph_renderer_rays", "ph_renderer_radiance", "ph_renderer_update", "ph_scene_same_structure", "ph_renderer_deform", "ph_scene_same_topology", "ph_example_render_to_png", "ph_png_read", "ph_png_write", "ph_image_read", "ph_scene_graph"]
+           "ph_renderer_context", "ph_renderer_ranks", "ph_renderer_node", "ph_renderer_prepare_ms", "ph_renderer_render", "ph_renderer_aov", "ph_renderer_rays", "ph_renderer_radiance", "ph_renderer_update", "ph_scene_same_structure", "ph_renderer_deform", "ph_scene_same_topology", "ph_renderer_deform_device", "ph_renderer_mesh_count", "ph_renderer_mesh_vertices", "ph_example_render_to_png", "ph_png_read", "ph_png_write", "ph_image_read", "ph_scene_graph"]
 
 
 class PortrayerHostError(RuntimeError):
@@ -28,6 +28,11 @@ class PortrayerHostError(RuntimeError):
 
 class PortrayerPanic(PortrayerHostError):
     """Raised where the reference would panic (e.g. ImageSliceMut::new, render.rs:79-90)."""
+
+
+class PhDeviceMesh(C.Structure):
+    """ph_device_mesh: one mesh of ph_renderer_deform_device, its vertices in device memory"""
+    _fields_ = [("mesh", C.c_uint32), ("d_positions", C.c_void_p), ("d_normals", C.c_void_p)]
 
 
 class PhSceneDesc(C.Structure):
@@ -85,6 +90,9 @@ def lib() -> C.CDLL:
         l.ph_renderer_update.restype = C.c_int; l.ph_renderer_update.argtypes = [vp, vp]
         l.ph_scene_same_structure.restype = C.c_int; l.ph_scene_same_structure.argtypes = [vp, vp, C.c_char_p, C.c_size_t]
         l.ph_renderer_deform.restype = C.c_int; l.ph_renderer_deform.argtypes = [vp, vp, C.c_int]
+        l.ph_renderer_deform_device.restype = C.c_int; l.ph_renderer_deform_device.argtypes = [vp, C.c_uint32, C.POINTER(PhDeviceMesh), C.c_int, vp]
+        l.ph_renderer_mesh_count.restype = C.c_int64; l.ph_renderer_mesh_count.argtypes = [vp]
+        l.ph_renderer_mesh_vertices.restype = C.c_int64; l.ph_renderer_mesh_vertices.argtypes = [vp, C.c_uint32]
         l.ph_scene_same_topology.restype = C.c_int; l.ph_scene_same_topology.argtypes = [vp, vp, C.c_char_p, C.c_size_t]
         l.ph_scene_export_textures.restype = C.c_int
         l.ph_scene_export_textures.argtypes = [vp, _u64p, _ip, _ip, _dp, _up, _u64p, _u8p, _dp, _u8p, _dp, _u8p]
@@ -274,12 +282,31 @@ def load_obj(path: str):
     return pos, (nrm if hn else None), idx
 
 
+def _device_tensor_pointer(t, shape, device: int, what: str) -> int:
+    """The device address of a torch tensor after checking that pt_scene_deform_device can read it as `shape` float64 values on HIP device `device`."""
+    import torch
+    if not isinstance(t, torch.Tensor):
+        raise ValueError("%s must be a torch tensor, got %s" % (what, type(t).__name__))
+    if t.dtype != torch.float64:
+        raise ValueError("%s must be float64, got %s" % (what, t.dtype))
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError("%s must have shape %r (the mesh's vertex count x 3), got %r" % (what, tuple(shape), tuple(t.shape)))
+    if not t.is_contiguous():
+        raise ValueError("%s must be contiguous" % what)
+    if t.device.type != "cuda":
+        raise ValueError("%s must be on the renderer's GPU (cuda:%d), got a tensor on %s: use deform() for host data" % (what, device, t.device))
+    if t.device.index != device:
+        raise ValueError("%s is on %s, the renderer is on cuda:%d" % (what, t.device, device))
+    return int(t.data_ptr())
+
+
 class Renderer:
     """A flattened scene resident on one MI355X (what render.rs:121-126 prepares, kept across renders)."""
 
     def __init__(self, scene: Scene, traverse: int = H.TRAVERSE_FLAT, kd_depth: int = 10, device: int = 0):
         self._h = C.c_void_p()
         self.scene = scene
+        self._device = device
         _check(lib().ph_renderer_create(scene._h, traverse, kd_depth, device, C.byref(self._h)), "ph_renderer_create")
 
     def close(self):
@@ -340,6 +367,46 @@ class Renderer:
         where the device built them at upload. Every later call answers as a new Renderer on `scene` would, bit for bit."""
         _check(lib().ph_renderer_deform(self._h, scene._h, 1 if rebuild else 0), "ph_renderer_deform")
         self.scene = scene
+
+    def mesh_count(self) -> int:
+        """Distinct meshes of the renderer's scene; deform_device() numbers them in the order the flattened nodes first use them."""
+        return int(_check(lib().ph_renderer_mesh_count(self._h), "ph_renderer_mesh_count"))
+
+    def mesh_vertices(self, m: int) -> int:
+        """Vertices of mesh `m` in the renderer's numbering."""
+        if isinstance(m, bool) or not isinstance(m, (int, np.integer)) or not 0 <= int(m) < self.mesh_count():
+            raise ValueError("mesh must be an index in [0, %d), got %r" % (self.mesh_count(), m))
+        return int(_check(lib().ph_renderer_mesh_vertices(self._h, int(m)), "ph_renderer_mesh_vertices"))
+
+    def deform_device(self, positions: dict, normals: Optional[dict] = None, rebuild: bool = False, moved: Optional[Scene] = None):
+        """Resident meshes deformed from vertices that are already on the renderer's GPU (pt_vertex_bounds_device + pt_scene_deform_device): `positions`
+        maps a mesh index (the renderer's numbering, see mesh_count()) to a torch tensor - float64, contiguous, of shape (mesh_vertices(m), 3), on the
+        renderer's device; `normals` optionally maps some of those indices to tensors of the same kind (meshes uploaded with normals only; without, the
+        resident normals stay). Anything else raises ValueError before a library call. Nothing per vertex crosses the bus: the mesh's box is a reduction on
+        the device and the triangle records are expanded from the tensor in place. `moved` (optional) is the renderer's scene with other transforms, lights'
+        values or ambient light, as for update(). The call is synchronous and waits for all work queued on the device before it reads the tensors, whichever
+        torch stream produced them; they are free again when it returns. Every later call answers as after deform() with the same numbers. A mesh deformed this
+        way is remembered as posed on the device: a later deform(scene) sends it again whatever the comparison with the host's copy says. Not available with
+        the k-d traversal or on a renderer of several ranks (PortrayerHostError says why)."""
+        normals = {} if normals is None else normals
+        if not isinstance(positions, dict) or not isinstance(normals, dict):
+            raise ValueError("positions and normals must be dicts {mesh index: tensor}")
+        extra = [m for m in normals if m not in positions]
+        if extra:
+            raise ValueError("normals for meshes without positions: %r" % (extra,))
+        n_meshes = self.mesh_count()
+        for m in positions:
+            if isinstance(m, bool) or not isinstance(m, (int, np.integer)) or not 0 <= int(m) < n_meshes:
+                raise ValueError("mesh must be an index in [0, %d), got %r" % (n_meshes, m))
+        arr = (PhDeviceMesh * max(len(positions), 1))()
+        for k, (m, pos) in enumerate(positions.items()):
+            shape = (self.mesh_vertices(int(m)), 3)
+            arr[k].mesh = int(m)
+            arr[k].d_positions = _device_tensor_pointer(pos, shape, self._device, "positions[%d]" % m)
+            arr[k].d_normals = _device_tensor_pointer(normals[m], shape, self._device, "normals[%d]" % m) if m in normals else None
+        _check(lib().ph_renderer_deform_device(self._h, len(positions), arr, 1 if rebuild else 0, moved._h if moved is not None else None), "ph_renderer_deform_device")
+        if moved is not None:
+            self.scene = moved
 
     def aov(self, cam10, width: int, height: int, rect=None, offset=(0.5, 0.5), want=("depth", "position", "normal", "node", "sub", "material"),
             into: Optional[dict] = None) -> dict:

@@ -554,6 +554,28 @@ extern "C" int ph_renderer_deform(ph_renderer* r, const ph_scene* s, int rebuild
     });
 }
 
+extern "C" int ph_renderer_deform_device(ph_renderer* r, uint32_t n_meshes, const ph_device_mesh* meshes, int rebuild, const ph_scene* moved) {
+    if (!r || (n_meshes && !meshes)) return bad("null argument");
+    return guarded([&]() -> int {
+        try {
+            std::vector<detail::Renderer::DeviceMesh> dm(n_meshes);
+            for (uint32_t k = 0; k < n_meshes; k++) dm[k] = detail::Renderer::DeviceMesh{meshes[k].mesh, meshes[k].d_positions, meshes[k].d_normals};
+            r->r->deform_device(dm, rebuild != 0, moved ? &moved->hier : nullptr);
+        } catch (const std::invalid_argument& e) {
+            g_error = e.what();
+            return PH_ERR_ARGUMENT;
+        }
+        return PH_OK;
+    });
+}
+
+extern "C" int64_t ph_renderer_mesh_count(ph_renderer* r) { return r ? (int64_t)r->r->mesh_count() : (int64_t)bad("null argument"); }
+extern "C" int64_t ph_renderer_mesh_vertices(ph_renderer* r, uint32_t mesh) {
+    if (!r) return bad("null argument");
+    const int64_t n = r->r->mesh_vertices(mesh);
+    return n < 0 ? (int64_t)bad("mesh index out of range") : n;
+}
+
 extern "C" int ph_renderer_update(ph_renderer* r, const ph_scene* s) {
     if (!r || !s) return bad("null argument");
     return guarded([&]() -> int {

@@ -104,6 +104,16 @@ class Renderer {
     // std::invalid_argument naming the first difference). The meshes whose positions or normals differ in a bit are sent - vertices and bounds only - and their
     // trees refitted on the device; rebuild = true rebuilds those the device built at upload instead (and refits the others). The motion is performed as by update().
     void deform(const scene::HierScene& scene, bool rebuild = false);
+    // Resident meshes deformed from vertices that are already in the memory of the renderer's device (pt_vertex_bounds_device + pt_scene_deform_device): per
+    // mesh its index in the renderer's numbering (first use by the flattened nodes, as deform() numbers them), a device pointer to n_vertices x 3 f64 positions
+    // and optionally one to as many normals. `moved` (optional) must have the structure of the resident scene; its matrices and lights ride along as in
+    // update(). Such a mesh is remembered as posed on the device: the host's MeshData no longer describes it, so a later deform(scene) sends it whatever its
+    // comparison says; update() keeps working (the boxes it needs are the library's resident ones). Throws std::invalid_argument for the k-d traversal (its
+    // tree is built by the host from the meshes' bounds) and for a renderer with several ranks (each rank's device needs its own copy of the vertices).
+    struct DeviceMesh { uint32_t mesh; const double* d_positions; const double* d_normals; };
+    void deform_device(const std::vector<DeviceMesh>& meshes, bool rebuild = false, const scene::HierScene* moved = nullptr);
+    size_t mesh_count() const;                 // distinct meshes, in the renderer's numbering
+    int64_t mesh_vertices(size_t m) const;     // vertices of mesh m, -1: no such mesh
     pt_context* context() const { return ctx_; }  // rank 0's context when the scene is on a node
     pt_node* node() const { return node_; }
     const FlatScene& flat() const { return flat_; }
@@ -117,7 +127,8 @@ class Renderer {
     PrepareMs prep_;
     render::Traversal traversal_ = render::Traversal::Flat;
     int kd_depth_ = -1;
-    void move(FlatScene&& moved, const std::vector<pt_mesh_deform>* deforms);
+    std::vector<uint8_t> posed_on_device_;  // per mesh: deformed by deform_device since flat_ last described it
+    void move(FlatScene&& moved, const std::vector<pt_mesh_deform>* deforms, const std::vector<pt_mesh_deform_device>* device_deforms = nullptr);
 };
 
 // PNG codec for Image::new / Image::save (render.rs:165-208; the reference uses the `image` crate)

@@ -591,10 +591,22 @@ static pt_kdtree kd_abi(const KdTree& t) {
 }
 
 // BoundingBox::invtrans of a mesh's AABB (mesh.rs:82): what the upload and a deform hand the library as the mesh's bounds
-static void append_mesh_bounds(const primitive::MeshData* m, std::vector<double>& out) {
-    BoundingBox bb = BoundingBox::create(m->bounds_min(), m->bounds_max());
+static void append_box_bounds(Vec3 lo, Vec3 hi, std::vector<double>& out) {
+    BoundingBox bb = BoundingBox::create(lo, hi);
     const double* im = &bb.invtrans.m[0][0];
     out.insert(out.end(), im, im + 16);
+}
+static void append_mesh_bounds(const primitive::MeshData* m, std::vector<double>& out) { append_box_bounds(m->bounds_min(), m->bounds_max(), out); }
+// the scene's distinct meshes in the Renderer's numbering: the order in which the flattened nodes first use them
+static std::vector<const primitive::MeshData*> meshes_of(const FlatScene& flat) {
+    std::map<const primitive::MeshData*, uint32_t> mesh_id;
+    std::vector<const primitive::MeshData*> out;
+    for (const FlatSceneNode& fn : flat.root) {
+        const auto& p = fn.geometry.primitive;
+        if (p.kind != primitive::Primitive::MeshK && p.kind != primitive::Primitive::KDMeshK) continue;
+        if (mesh_id.emplace(p.mesh.get(), (uint32_t)mesh_id.size()).second) out.push_back(p.mesh.get());
+    }
+    return out;
 }
 static double ms_since(std::chrono::steady_clock::time_point t) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count(); }
 
@@ -878,7 +890,9 @@ void Renderer::deform(const scene::HierScene& hier, bool rebuild) {
         if (!mesh_id.emplace(p.mesh.get(), (uint32_t)mesh_id.size()).second) continue;
         const uint32_t m = (uint32_t)mesh_id.size() - 1;
         const primitive::MeshData *was = p.mesh.get(), *now = q.mesh.get();
-        if (was == now || (!bits_differ(was->positions(), now->positions()) && !bits_differ(was->normals(), now->normals()))) continue;
+        // (a mesh posed on the device is sent whatever the comparison says: `was` no longer describes what is resident)
+        const bool posed = m < posed_on_device_.size() && posed_on_device_[m];
+        if (!posed && (was == now || (!bits_differ(was->positions(), now->positions()) && !bits_differ(was->normals(), now->normals())))) continue;
         pt_mesh_deform d;
         std::memset(&d, 0, sizeof d);
         d.mesh = m;
@@ -896,10 +910,55 @@ void Renderer::deform(const scene::HierScene& hier, bool rebuild) {
         deforms[k].bounds_invtrans = arrays[3 * k + 2].data();
     }
     move(std::move(moved), &deforms);
+    for (const pt_mesh_deform& d : deforms) if (d.mesh < posed_on_device_.size()) posed_on_device_[d.mesh] = 0;  // flat_ describes these meshes again
 }
 
-// pt_scene_update (deforms == nullptr) or pt_scene_deform with the moved scene's matrices, lights and - in k-d mode - its rebuilt reference k-d tree
-void Renderer::move(FlatScene&& moved, const std::vector<pt_mesh_deform>* deforms) {
+size_t Renderer::mesh_count() const { return meshes_of(flat_).size(); }
+
+int64_t Renderer::mesh_vertices(size_t m) const {
+    const auto meshes = meshes_of(flat_);
+    return m < meshes.size() ? (int64_t)meshes[m]->positions().size() : -1;
+}
+
+void Renderer::deform_device(const std::vector<DeviceMesh>& meshes, bool rebuild, const scene::HierScene* moved_scene) {
+    if (traversal_ == render::Traversal::KdTree)
+        throw std::invalid_argument("Renderer::deform_device: the k-d traversal's tree is built by the host from the meshes' bounds, which the host no longer has for a mesh posed on the device: "
+                                    "call pt_scene_deform_device with a k-d tree of your own, or use deform()");
+    if (node_)
+        throw std::invalid_argument("Renderer::deform_device: the renderer has several ranks, and each rank's device needs its own copy of the vertices: use deform(), or one renderer per device");
+    FlatScene moved = moved_scene ? FlatScene::from(*moved_scene) : flat_;
+    if (moved_scene) {
+        const std::string why = structure_difference(flat_, moved);
+        if (!why.empty()) throw std::invalid_argument("Renderer::deform_device: the moved scene has another structure than the resident one: " + why);
+    }
+    const auto resident = meshes_of(flat_);
+    std::vector<pt_mesh_deform_device> deforms;
+    std::vector<std::vector<double>> bounds;  // what the deforms point into
+    for (const DeviceMesh& dm : meshes) {
+        if (dm.mesh >= resident.size()) throw std::invalid_argument("Renderer::deform_device: mesh " + std::to_string(dm.mesh) + " of " + std::to_string(resident.size()));
+        if (!dm.d_positions) throw std::invalid_argument("Renderer::deform_device: mesh " + std::to_string(dm.mesh) + ": no positions");
+        double box[6];
+        uint64_t non_finite = 0;
+        check(ctx_, pt_vertex_bounds_device(ctx_, resident[dm.mesh]->positions().size(), dm.d_positions, box, &non_finite), "pt_vertex_bounds_device");
+        if (non_finite || !(box[0] <= box[3] && box[1] <= box[4] && box[2] <= box[5]))
+            throw std::runtime_error("Renderer::deform_device: mesh " + std::to_string(dm.mesh) + ": " + std::to_string(non_finite) + " coordinates are not finite, or the mesh has no vertices");
+        pt_mesh_deform_device d;
+        std::memset(&d, 0, sizeof d);
+        d.mesh = dm.mesh; d.d_positions = dm.d_positions; d.d_normals = dm.d_normals;
+        d.rebuild = rebuild && pt_scene_mesh_rebuildable(ctx_, dm.mesh) == 1 ? 1 : 0;
+        bounds.emplace_back();
+        append_box_bounds(Vec3(box[0], box[1], box[2]), Vec3(box[3], box[4], box[5]), bounds.back());  // (what the upload makes of MeshData's bounds)
+        deforms.push_back(d);
+    }
+    for (size_t k = 0; k < deforms.size(); k++) deforms[k].bounds_invtrans = bounds[k].data();
+    move(std::move(moved), nullptr, &deforms);
+    posed_on_device_.resize(resident.size(), 0);
+    for (const pt_mesh_deform_device& d : deforms) posed_on_device_[d.mesh] = 1;  // flat_'s MeshData no longer describes what is resident
+}
+
+// pt_scene_update (no deforms), pt_scene_deform or pt_scene_deform_device (one rank) with the moved scene's matrices, lights and - in k-d mode - its rebuilt
+// reference k-d tree
+void Renderer::move(FlatScene&& moved, const std::vector<pt_mesh_deform>* deforms, const std::vector<pt_mesh_deform_device>* device_deforms) {
     const size_t n = moved.root.size();
     std::vector<double> trans(16 * n), inv(16 * n), nrm(16 * n), lights;
     for (size_t i = 0; i < n; i++) {
@@ -931,7 +990,10 @@ void Renderer::move(FlatScene&& moved, const std::vector<pt_mesh_deform>* deform
     const pt_mesh_deform dummy{};
     const pt_mesh_deform* dp = deforms ? (deforms->empty() ? &dummy : deforms->data()) : nullptr;
     const uint32_t nd = deforms ? (uint32_t)deforms->size() : 0u;
-    if (node_) {
+    if (device_deforms) {
+        const pt_mesh_deform_device none{};
+        check(ctx_, pt_scene_deform_device(ctx_, (uint32_t)device_deforms->size(), device_deforms->empty() ? &none : device_deforms->data(), &mo, kdp), "pt_scene_deform_device");
+    } else if (node_) {
         int rc = deforms ? pt_node_scene_deform(node_, nd, dp, &mo, kdp) : pt_node_scene_update(node_, &mo, kdp);
         if (rc != PT_OK) {
             std::string msg = std::string(deforms ? "pt_node_scene_deform" : "pt_node_scene_update") + " failed (" + std::to_string(rc) + "): " + pt_node_last_error(node_);

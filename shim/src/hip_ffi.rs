@@ -78,6 +78,15 @@ pub struct PtSceneMotion {                 // pt_scene_motion: the resident scen
     pub ambient: *const f64,
 }
 
+#[repr(C)]
+pub struct PtMeshDeformDevice {            // pt_mesh_deform_device: a resident mesh's new vertices, already in device memory (pt_scene_deform_device)
+    pub mesh: u32,
+    pub d_positions: *const f64,           // DEVICE, n_vertices x 3
+    pub d_normals: *const f64,             // DEVICE, n_vertices x 3, or null
+    pub bounds_invtrans: *const f64,       // HOST, 16 doubles
+    pub rebuild: i32,
+}
+
 #[repr(C)] pub struct PtCamera { pub eye: [f64; 3], pub view_to_world: [f64; 16], pub fov_factor: f64, pub aspect_ratio: f64, pub width: f64, pub height: f64 }
 #[repr(C)] pub struct PtRect { pub x0: u32, pub y0: u32, pub x1: u32, pub y1: u32 }
 
@@ -119,6 +128,10 @@ extern "C" {
     pub fn pt_scene_upload(ctx: *mut PtContext, scene: *const PtScene, traverse: c_int, kd: *const PtKdTree) -> c_int;
     // move the resident scene: new node matrices, lights, ambient light; only the scene-level tree is rebuilt
     pub fn pt_scene_update(ctx: *mut PtContext, motion: *const PtSceneMotion, kd: *const PtKdTree) -> c_int;
+    // deform resident meshes from vertices in device memory: the box of such vertices (min xyz, max xyz; count of NaN / inf coordinates), then the deform
+    pub fn pt_vertex_bounds_device(ctx: *mut PtContext, n_vertices: u64, d_positions: *const f64, out: *mut f64, non_finite: *mut u64) -> c_int;
+    pub fn pt_scene_deform_device(ctx: *mut PtContext, n_deforms: u32, deforms: *const PtMeshDeformDevice, motion: *const PtSceneMotion,
+                                  kd: *const PtKdTree) -> c_int;
     pub fn pt_render(ctx: *mut PtContext, camera: *const PtCamera, background: *const f64, params: *const PtRenderParams,
                      rgb: *mut u8, linear: *mut f64, stats: *mut PtStats) -> c_int;
     pub fn pt_render_device(ctx: *mut PtContext, camera: *const PtCamera, d_background: *const f64, params: *const PtRenderParams,
