@@ -33,7 +33,8 @@ RENDER_MODES := 1 2 3 4 5 6 7 8 9
 HIP_OBJS := $(OBJDIR)/pt_api.o $(OBJDIR)/pt_build.o $(OBJDIR)/pt_node.o $(foreach m,$(RENDER_MODES),$(OBJDIR)/pt_render_m$(m).o) \
             $(foreach m,$(RENDER_MODES),$(OBJDIR)/pt_aov_m$(m).o) \
             $(OBJDIR)/pt_rays_sort.o $(foreach m,$(RENDER_MODES),$(OBJDIR)/pt_rays_m$(m).o) \
-            $(foreach m,$(RENDER_MODES),$(OBJDIR)/pt_radiance_m$(m).o)
+            $(foreach m,$(RENDER_MODES),$(OBJDIR)/pt_radiance_m$(m).o) \
+            $(foreach m,$(RENDER_MODES),$(OBJDIR)/pt_segments_m$(m).o)
 
 # Every HIP translation unit is built in four steps instead of one `hipcc -c`, so that the device code can be CHECKED and REPAIRED between
 # the compiler and the assembler (tools/check_exec_prologue.py; profiles/r05/notes.md section 1: the AMDGPU backend of this toolchain can put
@@ -68,6 +69,10 @@ $(OBJDIR)/pt_aov_m%.o: $(CSRC)/pt_aov_inst.hip $(HIP_HDRS) tools/check_exec_prol
 
 # the ray-query pass (pt_rays.h), likewise; its keying + sort step (pt_rays_sort.hip) is built by the %.o rule
 $(OBJDIR)/pt_rays_m%.o: $(CSRC)/pt_rays_inst.hip $(HIP_HDRS) tools/check_exec_prologue.py
+	$(call hip_four_steps,-DPT_INST_MODE=$*)
+
+# the bounded-segment ray queries (pt_segments.h): pt_rays_kernel with a t_max per ray, and the one unit whose walks start at that bound (PT_WALK_ENTRY_T)
+$(OBJDIR)/pt_segments_m%.o: $(CSRC)/pt_segments_inst.hip $(HIP_HDRS) tools/check_exec_prologue.py
 	$(call hip_four_steps,-DPT_INST_MODE=$*)
 
 # the radiance pass (pt_radiance.h): the interpreter over the caller's rays, <TEX, PARK> instantiations per mode

@@ -354,8 +354,7 @@ int pt_aov_finish(pt_context *ctx, double *kernel_ms);
  *                 mean in pt_aov, miss values included (+inf; 0, 0, 0; -1), and carry the same bits. occluded (u8) = node >= 0.
  *   any_hit = 1   is anything in the way over [EPSILON, inf) (the shadow rays' question, material.rs:171-179): occluded = 1 or 0. ONLY `occluded` may be
  *                 asked for - which occluder a walk meets first depends on how rays are scheduled, so it is not part of the contract.
- * The range is [EPSILON, inf) as everywhere in this code base: a bounded segment (t_max) would change the walks the render kernels share and is not offered;
- * callers compare t with their own bound (any_hit = 0).
+ * The range is [EPSILON, inf) as everywhere in this code base; pt_segments (below) is this pass over a bounded segment [EPSILON, t_max) per ray.
  * Rays that are NOT TRACED report a miss (occluded = 0), occupy no lane of the walk and change no other ray's result: a ray with a non-finite component,
  * with an all-zero direction, or with a component of origin or direction beyond 1e18 in magnitude. The last rule keeps the f32 constants of the walks'
  * conservative box test finite and their error margins valid (the reciprocal of a direction component and its product with the origin stay inside the f32
@@ -385,6 +384,33 @@ int pt_rays(pt_context *ctx, const pt_rays_params *params, const double *origins
  * in flight per context: a second pt_rays_device / pt_rays before pt_rays_finish is refused with PT_ERR_ARGUMENT. (n = 0 queues nothing and is not in flight.) */
 int pt_rays_device(pt_context *ctx, const pt_rays_params *params, const double *d_origins, const double *d_directions, const pt_rays_buffers *device_out, void *hip_stream);
 int pt_rays_finish(pt_context *ctx, double *kernel_ms);
+
+/* ---- Ray queries over bounded SEGMENTS: pt_rays with a t_max per ray (n f64, in units of the ray's direction, like t) - visibility between two points
+ * (direction = b - a, t_max = 1), ambient occlusion inside a closed room, range sensors. Per ray the result is that of pt_rays restricted to hits with
+ * EPSILON <= t < t_max, in every buffer:
+ *   any_hit = 0   the nearest hit if its t < t_max, else the miss values.
+ *   any_hit = 1   occluded = 1 iff such a hit exists.
+ * t_max = +inf gives pt_rays' bits exactly. A ray whose t_max is NaN or <= PT_EPSILON has an empty range: it is NOT TRACED - reports a miss, occupies no
+ * lane of the walk and changes no other ray's result - like the rays pt_rays does not trace, whose rules hold here too.
+ * In the flat_scene and hierarchical semantics this is the crate's ray_cast(&ray, &mut Range {start: EPSILON, end: t_max}): a primitive returns its smallest
+ * root in range, a mesh is entered whenever a triangle could still be hit inside the range (BoundingBox::test_hit, bounding_box.rs:104-116: also by a ray
+ * that starts inside the box whose far face lies beyond t_max), exact ties keep their winner. The walks start with the bound and prune with it: boxes beyond
+ * t_max are never entered, and an occlusion query ends at the first hit inside the range. Two exceptions, for the reason of the next paragraph - both are tests
+ * whose outcome for a hit just inside the bound depends on more than the exact comparison t < t_max, so that the crate's bounded cast would lose hits pt_rays
+ * reports: a KDMesh's own triangle k-d tree (kdmesh.rs; its classification of a split's sides reads the range's END - hits on a split plane within EPSILON of
+ * t_max) and a Mesh's box test (bounding_box.rs:104-116; the box's entry parameter is rounded differently from a triangle's t - triangles lying IN a face of the
+ * box, t_max an ulp behind them). While nothing is found yet both get the range an unbounded walk would give them, and the hit is kept iff t < t_max.
+ * In the k-d semantics the crate's own bounded range would enter the split classification (node.rs:121) and could differ in quirk cases; the contract here
+ * is BY DEFINITION the unbounded walk's result, filtered by t < t_max. The walk is therefore not pruned and runs as a nearest-hit walk for any_hit = 1 as
+ * well (an occlusion walk may stop at an occluder beyond t_max while a nearer one sits in another leaf): a bound saves no time in these semantics.
+ * params, buffers, reorder (pt_rays' sort, unchanged: the bound is not part of the key) and kernel_ms as in pt_rays. The pass IS a ray-query pass: it shares
+ * pt_rays' work buffers and its one pass in flight - pt_segments_device is closed by pt_rays_finish, and while a pt_rays_device or pt_segments_device pass
+ * is open a second one of either kind (or pt_rays / pt_segments) is PT_ERR_ARGUMENT.
+ * Errors, before the first HIP call: PT_ERR_ARGUMENT for a NULL t_max, and pt_rays' errors. n = 0 is PT_OK. */
+int pt_segments(pt_context *ctx, const pt_rays_params *params, const double *origins, const double *directions, const double *t_max, const pt_rays_buffers *host_out,
+                double *kernel_ms);
+int pt_segments_device(pt_context *ctx, const pt_rays_params *params, const double *d_origins, const double *d_directions, const double *d_t_max,
+                       const pt_rays_buffers *device_out, void *hip_stream);
 
 /* ---- Radiance: rays the CALLER supplies, SHADED (the crate's public Ray::color(scene, background, 0), ray.rs:139-148) - cameras the crate does not have
  * (fisheye, panoramic, orthographic, thin lens), light probes and environment captures from a point inside the scene, one more gathered bounce for a baker

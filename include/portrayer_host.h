@@ -117,6 +117,10 @@ int ph_renderer_aov(ph_renderer *r, const double camera[10], const pt_aov_params
 /* Rays of the caller's own (see pt_rays): n x 3 f64 origins and directions in world space, host buffers out, each optional; any_hit = 1 answers `occluded`
  * only. A renderer spread over a node runs the pass on rank 0's context. `node` and `material` are numbered as for ph_renderer_aov. */
 int ph_renderer_rays(ph_renderer *r, const pt_rays_params *params, const double *origins, const double *directions, const pt_rays_buffers *out, double *kernel_ms);
+/* The same over bounded segments (see pt_segments): t_max holds n f64, ray i answers for hits with EPSILON <= t < t_max[i]; a NaN or <= EPSILON bound is an
+ * empty range and reports a miss. */
+int ph_renderer_segments(ph_renderer *r, const pt_rays_params *params, const double *origins, const double *directions, const double *t_max, const pt_rays_buffers *out,
+                         double *kernel_ms);
 
 /* The resident scene moved (pt_scene_update): `scene` must have the structure of the one the renderer was created from - ph_scene_same_structure - and may
  * differ in transforms, lights' values and ambient light; PH_ERR_ARGUMENT names the first difference otherwise and the renderer keeps its scene. Only node

@@ -142,7 +142,7 @@ EXPORTS = ["pt_abi_version", "pt_device_count", "pt_context_create", "pt_context
            "pt_test_math", "pt_test_work_items", "pt_node_create", "pt_node_destroy", "pt_node_last_error", "pt_node_ranks", "pt_node_uses_rccl", "pt_node_context",
            "pt_node_scene_upload", "pt_node_render", "pt_node_upload_background", "pt_node_render_resident", "pt_node_download_image",
            "pt_node_device", "pt_node_frame_begin", "pt_node_frame_end", "pt_node_frames_in_flight", "pt_node_last_frame_host_ms", "pt_node_last_frame_rank_kernel_ms", "pt_test_pow_host", "pt_test_libm_host",
-           "pt_aov", "pt_aov_device", "pt_aov_finish", "pt_rays", "pt_rays_device", "pt_rays_finish",
+           "pt_aov", "pt_aov_device", "pt_aov_finish", "pt_rays", "pt_rays_device", "pt_rays_finish", "pt_segments", "pt_segments_device",
            "pt_radiance", "pt_radiance_device", "pt_radiance_finish", "pt_scene_update", "pt_node_scene_update", "pt_scene_deform", "pt_node_scene_deform", "pt_scene_mesh_rebuildable", "pt_test_scene_bytes", "pt_test_scene_info",
            "pt_vertex_bounds_device", "pt_scene_deform_device", "pt_test_vertex_box_shape"]
 
@@ -281,6 +281,10 @@ def lib() -> C.CDLL:
         l.pt_rays.argtypes = [C.c_void_p, C.POINTER(PtRaysParams), _dp, _dp, C.POINTER(PtRaysBuffers), _dp]
         l.pt_rays_device.restype = C.c_int
         l.pt_rays_device.argtypes = [C.c_void_p, C.POINTER(PtRaysParams), C.c_void_p, C.c_void_p, C.POINTER(PtRaysBuffers), C.c_void_p]
+        l.pt_segments.restype = C.c_int
+        l.pt_segments.argtypes = [C.c_void_p, C.POINTER(PtRaysParams), _dp, _dp, _dp, C.POINTER(PtRaysBuffers), _dp]
+        l.pt_segments_device.restype = C.c_int
+        l.pt_segments_device.argtypes = [C.c_void_p, C.POINTER(PtRaysParams), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(PtRaysBuffers), C.c_void_p]
         l.pt_rays_finish.restype = C.c_int
         l.pt_rays_finish.argtypes = [C.c_void_p, _dp]
         l.pt_radiance.restype = C.c_int

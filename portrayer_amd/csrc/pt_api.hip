@@ -17,6 +17,7 @@
 #include "pt_bvh.h"
 #include "pt_aov_inst.h"
 #include "pt_rays_inst.h"
+#include "pt_segments_inst.h"
 #include "pt_radiance_inst.h"
 #include "pt_render_inst.h"
 #include "pt_shade.h"
@@ -292,10 +293,10 @@ struct pt_context {
     // The ray-query pass (pt_rays / pt_rays_device) likewise, apart from both: stack columns, overflow flag + work queues, events and a pinned page; the device
     // copies of the host-buffer path's two inputs and seven outputs; and what reorder = 1 sorts with (keys and ray indices before and after, the sort's scratch).
     struct Rays {
-        PtBuf stack_spill, misc, in[2], out[7], keys[2], vals[2], sort_tmp;
+        PtBuf stack_spill, misc, in[2], in_t_max, out[7], keys[2], vals[2], sort_tmp;  // in_t_max: pt_segments' third input
         hipEvent_t ev0 = nullptr, ev1 = nullptr, copy_done = nullptr;
         unsigned char* host = nullptr;
-        bool pending = false;           // a pt_rays_device not yet closed by pt_rays_finish
+        bool pending = false;           // a pt_rays_device / pt_segments_device not yet closed by pt_rays_finish
         hipStream_t stream = nullptr;
         bool queued = false, closed = false;  // as in Aov
     } rays;
@@ -424,7 +425,7 @@ extern "C" void pt_context_destroy(pt_context* c) {
     {
         pt_context::Rays& y = c->rays;
         if (y.queued) { if (y.closed) hipEventSynchronize(y.copy_done); else hipStreamSynchronize(y.stream); }  // (pt_rays_wait)
-        PtBuf* rb[] = {&y.stack_spill, &y.misc, &y.in[0], &y.in[1], &y.out[0], &y.out[1], &y.out[2], &y.out[3], &y.out[4], &y.out[5], &y.out[6], &y.keys[0], &y.keys[1], &y.vals[0], &y.vals[1], &y.sort_tmp};
+        PtBuf* rb[] = {&y.stack_spill, &y.misc, &y.in[0], &y.in[1], &y.in_t_max, &y.out[0], &y.out[1], &y.out[2], &y.out[3], &y.out[4], &y.out[5], &y.out[6], &y.keys[0], &y.keys[1], &y.vals[0], &y.vals[1], &y.sort_tmp};
         for (PtBuf* b : rb) if (b->p) hipFree(b->p);
         if (y.ev0) hipEventDestroy(y.ev0);
         if (y.ev1) hipEventDestroy(y.ev1);
@@ -2236,6 +2237,21 @@ static hipError_t pt_rays_dispatch(const PtRaysArgs& a, int n_cu, hipStream_t st
     }
 }
 
+// The bounded-segment form of the pass (pt_segments.h): the same arguments and a bound per ray.
+static hipError_t pt_segments_dispatch(const PtSegmentsArgs& a, int n_cu, hipStream_t stream, uint32_t* grid, bool launch) {
+    switch (a.q.r.scene.mode) {
+    case PT_MODE_KD: return pt_segments_launch_mode_2(a, n_cu, stream, grid, launch);
+    case PT_MODE_FLAT_NOMESH: return pt_segments_launch_mode_3(a, n_cu, stream, grid, launch);
+    case PT_MODE_FLAT_KDMESH: return pt_segments_launch_mode_4(a, n_cu, stream, grid, launch);
+    case PT_MODE_HIER: return pt_segments_launch_mode_5(a, n_cu, stream, grid, launch);
+    case PT_MODE_HIER_NOMESH: return pt_segments_launch_mode_6(a, n_cu, stream, grid, launch);
+    case PT_MODE_KD_NOMESH: return pt_segments_launch_mode_7(a, n_cu, stream, grid, launch);
+    case PT_MODE_HIER_MESH: return pt_segments_launch_mode_8(a, n_cu, stream, grid, launch);
+    case PT_MODE_KD_MESH: return pt_segments_launch_mode_9(a, n_cu, stream, grid, launch);
+    default: return pt_segments_launch_mode_1(a, n_cu, stream, grid, launch);
+    }
+}
+
 // Everything that can be refused without a HIP call, in the order the header gives. (pt_fail takes a NULL context.)
 static int pt_rays_check(pt_context* c, const pt_rays_params* p, const double* origins, const double* directions, const pt_rays_buffers* out) {
     if (!c || !p || !origins || !directions) return pt_fail(c, PT_ERR_ARGUMENT, "pt_rays: NULL context, params, origins or directions");
@@ -2246,13 +2262,21 @@ static int pt_rays_check(pt_context* c, const pt_rays_params* p, const double* o
     if (p->any_hit && (out->t || out->position || out->normal || out->node || out->sub || out->material))
         return pt_fail(c, PT_ERR_ARGUMENT, "pt_rays: an occlusion query (any_hit = 1) answers `occluded` only");
     if (!c->have_scene) return pt_fail(c, PT_ERR_NO_SCENE, "no scene uploaded");
-    if (c->rays.pending) return pt_fail(c, PT_ERR_ARGUMENT, "a pt_rays_device pass is in flight: pt_rays_finish first");
+    if (c->rays.pending) return pt_fail(c, PT_ERR_ARGUMENT, "a pt_rays_device / pt_segments_device pass is in flight: pt_rays_finish first");
     return PT_OK;
+}
+
+// pt_segments': pt_rays' and the bound.
+static int pt_segments_check(pt_context* c, const pt_rays_params* p, const double* origins, const double* directions, const double* t_max, const pt_rays_buffers* out) {
+    if (!c || !p || !origins || !directions || !t_max) return pt_fail(c, PT_ERR_ARGUMENT, "pt_segments: NULL context, params, origins, directions or t_max");
+    return pt_rays_check(c, p, origins, directions, out);
 }
 
 // Queues the pass on `stream`: queues + overflow flag zeroed; between the pass's two events the keying and the sort (reorder = 1) and the cast kernel; the flag
 // copied to the pinned page behind them. Every pointer is a DEVICE pointer. The LDS stack area is sized as for the primary-visibility pass (pt_aov_common).
-static int pt_rays_common(pt_context* c, const pt_rays_params* p, const double* d_origins, const double* d_directions, const pt_rays_buffers& out, hipStream_t stream) {
+// d_t_max: null = pt_rays' kernel; else the bounded-segment kernel (pt_segments), which takes the same arguments and that array.
+static int pt_rays_common(pt_context* c, const pt_rays_params* p, const double* d_origins, const double* d_directions, const pt_rays_buffers& out, hipStream_t stream,
+                          const double* d_t_max = nullptr) {
     pt_context::Rays& v = c->rays;
     if (!v.ev0) {
         PT_HIP(c, hipEventCreate(&v.ev0));
@@ -2272,7 +2296,13 @@ static int pt_rays_common(pt_context* c, const pt_rays_params* p, const double* 
     a.r.stack_lds_cap = pt_stack_lds_cap(a.r.scene, block_budget, 0, kd_sem);
     a.r.grid_share = 1;
     uint32_t grid = 0;
-    PT_HIP(c, pt_rays_dispatch(a, c->n_cu, stream, &grid, false));
+    auto dispatch = [&](bool launch) -> hipError_t {  // (the segments kernel's argument block is built from `a` as it stands at the call)
+        if (!d_t_max) return pt_rays_dispatch(a, c->n_cu, stream, &grid, launch);
+        PtSegmentsArgs s;
+        s.q = a; s.t_max = d_t_max;
+        return pt_segments_dispatch(s, c->n_cu, stream, &grid, launch);
+    };
+    PT_HIP(c, dispatch(false));
     a.r.n_lanes = grid * PT_BLOCK;
     const size_t stack_column = pt_stack_column(a.r.scene, a.r.stack_lds_cap);
     int rc;
@@ -2296,7 +2326,7 @@ static int pt_rays_common(pt_context* c, const pt_rays_params* p, const double* 
     if (p->reorder)
         PT_HIP(c, pt_rays_sort(p->n, d_origins, d_directions, c->root_lo, c->root_hi, (unsigned long long*)v.keys[0].p, (unsigned long long*)v.keys[1].p, (uint32_t*)v.vals[0].p,
                                (uint32_t*)v.vals[1].p, v.sort_tmp.p, sort_bytes, stream));
-    PT_HIP(c, pt_rays_dispatch(a, c->n_cu, stream, &grid, true));
+    PT_HIP(c, dispatch(true));
     PT_HIP(c, hipEventRecord(v.ev1, stream));
     PT_HIP(c, hipMemcpyAsync(v.host, v.misc.p, 8, hipMemcpyDeviceToHost, stream));
     PT_HIP(c, hipEventRecord(v.copy_done, stream));
@@ -2327,9 +2357,8 @@ static int pt_rays_close(pt_context* c, double* kernel_ms) {
     return PT_OK;
 }
 
-extern "C" int pt_rays(pt_context* c, const pt_rays_params* p, const double* origins, const double* directions, const pt_rays_buffers* host_out, double* kernel_ms) {
-    int rc = pt_rays_check(c, p, origins, directions, host_out);
-    if (rc) return rc;
+// The host-buffer path of pt_rays (t_max null) and pt_segments: upload, pass, copy back.
+static int pt_rays_host(pt_context* c, const pt_rays_params* p, const double* origins, const double* directions, const double* t_max, const pt_rays_buffers* host_out, double* kernel_ms) {
     if (kernel_ms) *kernel_ms = 0.0;
     if (p->n == 0) return PT_OK;
     PT_HIP(c, hipSetDevice(c->device));
@@ -2337,7 +2366,9 @@ extern "C" int pt_rays(pt_context* c, const pt_rays_params* p, const double* ori
     void* host[7] = {host_out->t, host_out->position, host_out->normal, host_out->node, host_out->sub, host_out->material, host_out->occluded};
     const size_t elem[7] = {8, 24, 24, 4, 4, 4, 1};  // bytes per ray
     void* dev[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    int rc;
     if ((rc = pt_reserve(c, c->rays.in[0], n * 24)) || (rc = pt_reserve(c, c->rays.in[1], n * 24))) return rc;
+    if (t_max && (rc = pt_reserve(c, c->rays.in_t_max, n * 8))) return rc;
     for (int k = 0; k < 7; k++) {
         if (!host[k]) continue;
         if ((rc = pt_reserve(c, c->rays.out[k], n * elem[k]))) return rc;
@@ -2345,10 +2376,11 @@ extern "C" int pt_rays(pt_context* c, const pt_rays_params* p, const double* ori
     }
     PT_HIP(c, hipMemcpy(c->rays.in[0].p, origins, n * 24, hipMemcpyHostToDevice));
     PT_HIP(c, hipMemcpy(c->rays.in[1].p, directions, n * 24, hipMemcpyHostToDevice));
+    if (t_max) PT_HIP(c, hipMemcpy(c->rays.in_t_max.p, t_max, n * 8, hipMemcpyHostToDevice));
     pt_rays_buffers d_out;
     d_out.t = (double*)dev[0]; d_out.position = (double*)dev[1]; d_out.normal = (double*)dev[2];
     d_out.node = (int32_t*)dev[3]; d_out.sub = (int32_t*)dev[4]; d_out.material = (int32_t*)dev[5]; d_out.occluded = (uint8_t*)dev[6];
-    rc = pt_rays_common(c, p, (const double*)c->rays.in[0].p, (const double*)c->rays.in[1].p, d_out, nullptr);
+    rc = pt_rays_common(c, p, (const double*)c->rays.in[0].p, (const double*)c->rays.in[1].p, d_out, nullptr, t_max ? (const double*)c->rays.in_t_max.p : nullptr);
     const int rc_wait = pt_rays_wait(c);
     if (rc || (rc = rc_wait)) return rc;
     for (int k = 0; k < 7; k++)
@@ -2356,12 +2388,12 @@ extern "C" int pt_rays(pt_context* c, const pt_rays_params* p, const double* ori
     return pt_rays_close(c, kernel_ms);
 }
 
-extern "C" int pt_rays_device(pt_context* c, const pt_rays_params* p, const double* d_origins, const double* d_directions, const pt_rays_buffers* device_out, void* hip_stream) {
-    int rc = pt_rays_check(c, p, d_origins, d_directions, device_out);
-    if (rc) return rc;
+// ... and the device-buffer path of both.
+static int pt_rays_queue(pt_context* c, const pt_rays_params* p, const double* d_origins, const double* d_directions, const double* d_t_max, const pt_rays_buffers* device_out, void* hip_stream) {
     if (p->n == 0) return PT_OK;  // nothing queued, nothing to finish
     PT_HIP(c, hipSetDevice(c->device));
-    if ((rc = pt_rays_common(c, p, d_origins, d_directions, *device_out, (hipStream_t)hip_stream))) {
+    int rc;
+    if ((rc = pt_rays_common(c, p, d_origins, d_directions, *device_out, (hipStream_t)hip_stream, d_t_max))) {
         pt_rays_wait(c);  // what was queued before the failure must not outlive the call: the next pass may reallocate the buffers under it
         return rc;
     }
@@ -2369,9 +2401,33 @@ extern "C" int pt_rays_device(pt_context* c, const pt_rays_params* p, const doub
     return PT_OK;
 }
 
+extern "C" int pt_rays(pt_context* c, const pt_rays_params* p, const double* origins, const double* directions, const pt_rays_buffers* host_out, double* kernel_ms) {
+    int rc = pt_rays_check(c, p, origins, directions, host_out);
+    if (rc) return rc;
+    return pt_rays_host(c, p, origins, directions, nullptr, host_out, kernel_ms);
+}
+
+extern "C" int pt_rays_device(pt_context* c, const pt_rays_params* p, const double* d_origins, const double* d_directions, const pt_rays_buffers* device_out, void* hip_stream) {
+    int rc = pt_rays_check(c, p, d_origins, d_directions, device_out);
+    if (rc) return rc;
+    return pt_rays_queue(c, p, d_origins, d_directions, nullptr, device_out, hip_stream);
+}
+
+extern "C" int pt_segments(pt_context* c, const pt_rays_params* p, const double* origins, const double* directions, const double* t_max, const pt_rays_buffers* host_out, double* kernel_ms) {
+    int rc = pt_segments_check(c, p, origins, directions, t_max, host_out);
+    if (rc) return rc;
+    return pt_rays_host(c, p, origins, directions, t_max, host_out, kernel_ms);
+}
+
+extern "C" int pt_segments_device(pt_context* c, const pt_rays_params* p, const double* d_origins, const double* d_directions, const double* d_t_max, const pt_rays_buffers* device_out, void* hip_stream) {
+    int rc = pt_segments_check(c, p, d_origins, d_directions, d_t_max, device_out);
+    if (rc) return rc;
+    return pt_rays_queue(c, p, d_origins, d_directions, d_t_max, device_out, hip_stream);
+}
+
 extern "C" int pt_rays_finish(pt_context* c, double* kernel_ms) {
     if (!c) return PT_ERR_ARGUMENT;
-    if (!c->rays.pending) return pt_fail(c, PT_ERR_ARGUMENT, "no pt_rays_device pass in flight");
+    if (!c->rays.pending) return pt_fail(c, PT_ERR_ARGUMENT, "no pt_rays_device / pt_segments_device pass in flight");
     PT_HIP(c, hipSetDevice(c->device));
     c->rays.pending = false;
     int rc = pt_rays_wait(c);

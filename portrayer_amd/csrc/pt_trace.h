@@ -1272,6 +1272,36 @@ PT_HD void pt_slab_pk2_t(const pt_u32x16& v, const PtRayPk& q, float tm, unsigne
 // a lane's exclusive range end as the f32 the slab test compares with, rounded up (inf stays inf)
 PT_HD float pt_tmax32(double t) { float tm = (float)t; return tm + fabsf(tm) * 2.4e-7f; }
 
+// The bound a lane ENTERS the two wavefront walks of the flat_scene and hierarchical semantics with (pt_trace_packet_walk, pt_trace_packet_mesh): best.t, and
+// tm, its f32 image for the slab tests. Every pass but one starts a walk over [EPSILON, inf): these defaults, which expand to the text that stood here before
+// the seam. The bounded-segment pass (pt_segments_inst.hip) defines both BEFORE its includes so that its copy of the walks keeps the best.t the lane came in
+// with - its t_max - and prunes with it from the first box on; pt_cand_end / pt_cand_end_in then give every candidate [EPSILON, t_max). A macro and not a
+// template parameter, because editing the walks' templates reorders every render object's code.
+//
+// The third macro is the test of a KDMesh instance's own triangle k-d tree in pt_trace_packet_mesh. Its side classification reads the END of the range it is given
+// (pt_kdmesh_hit: `end - PT_EPSILON`, node.rs:121), so a walk handed a caller's bound can lose a hit just inside that bound which the walk over [EPSILON, inf)
+// finds. The bounded-segment pass promises the unbounded result, filtered - here as in the scene-level k-d semantics - and uses pt_kdmesh_hit_filtered instead.
+// The fourth is the range end of a Mesh instance's box test there (bounding_box.rs:104-116, a cube hit in [EPSILON, end)): the box's entry parameter and a
+// triangle's t are rounded differently, so where a triangle lies IN a face of its mesh's box a bound one ulp behind the triangle can lie in front of the box. The
+// bounded-segment pass tests the box over [EPSILON, inf) while the lane has found nothing; the triangles get the bound, whose comparison with their t is exact.
+#ifndef PT_WALK_ENTRY_T
+#define PT_WALK_ENTRY_T(best) INFINITY
+#define PT_WALK_ENTRY_TM(best) INFINITY
+#define PT_WALK_KDMESH_HIT(STATS, HIER, sc, mi, lr, best, node, lane_stk, t, tri, cnt) pt_kdmesh_hit<STATS>(sc, mi, lr, PT_EPSILON, pt_cand_end_in<HIER>(sc, best, node, 0), lane_stk, 0, t, tri, cnt)
+#define PT_WALK_MESH_BOX_END(HIER, sc, best, node) pt_cand_end_in<HIER>(sc, best, node, 0)
+#endif
+
+// pt_kdmesh_hit for a walk that was entered with a bound (best.t = t_max, best.node = PT_NO_HIT): as long as nothing is found, best.t is no hit and the mesh's tree
+// gets the range an unbounded walk would give it, [EPSILON, inf); its hit then counts iff it lies in front of the bound. Once something is found best.t is a hit
+// like any other.
+template <bool STATS, bool HIER, class Stack>
+PT_HD bool pt_kdmesh_hit_filtered(const PtSceneView& sc, const PtMeshInfo& m, const PtRay& lr, const PtHit& best, uint32_t node, const Stack& stk, double* t, uint32_t* tri,
+                                  PtCounters* cnt) {
+    const bool open = best.node == PT_NO_HIT;
+    if (!pt_kdmesh_hit<STATS>(sc, m, lr, PT_EPSILON, open ? (double)INFINITY : pt_cand_end_in<HIER>(sc, best, node, 0), stk, 0, t, tri, cnt)) return false;
+    return !open || *t < best.t;
+}
+
 // The scalar side of a step in one block: which children the wavefront enters (code 0: neither, 1: child 0 only, 2: child 1
 // only, 3: both), which one first (`near`: the one the majority of the lanes that reach a child enter first; with a single
 // child reached that is that child) and which one waits on the stack (`far`, meaningful for code 3).
@@ -1542,7 +1572,7 @@ PT_HD void pt_descend_mesh(const PtBvhNode* bvh, const PtRayPk& q, float tm, uns
 template <bool STATS, bool HIER>
 PT_HD void pt_trace_packet_walk(const PtSceneView& sc, const PtRay& ray, bool has_ray, bool any, PtHit& best, uint32_t* wstack, int wwords,
                                 unsigned int* overflow, PtCounters* cnt, bool live = true) {
-    if (has_ray && live) { best.t = INFINITY; best.node = PT_NO_HIT; best.sub = 0; }
+    if (has_ray && live) { best.t = PT_WALK_ENTRY_T(best); best.node = PT_NO_HIT; best.sub = 0; }
     if (sc.n_nodes == 0 || sc.tlas_root == PT_REF_EMPTY) return;
     const unsigned long long self = 1ull << PT_LANE_ID();
     bool alive = has_ray && live;       // the lane still wants candidates (a shadow ray stops at its first hit)
@@ -1551,7 +1581,7 @@ PT_HD void pt_trace_packet_walk(const PtSceneView& sc, const PtRay& ray, bool ha
     int oct;
     const PtRayPk q = pt_raypk(ray, has_ray, &oct);
     const bool identity_ok = HIER && pt_ray_identity_safe(ray, has_ray);  // (wave-uniform) levels of a path that are the identity may be skipped
-    float tm = INFINITY;                 // best.t as the f32 bound of the slab test, rounded up; follows best.t
+    float tm = PT_WALK_ENTRY_TM(best);                 // best.t as the f32 bound of the slab test, rounded up; follows best.t
     uint32_t cur = PT_UNIFORM_U32(sc.tlas_root);
     int sp = 0;                          // words on the stack
     constexpr int W = STATS ? 3 : 1;     // per entry: the node, and in the counting build the mask of the lanes that reach it
@@ -1773,7 +1803,7 @@ PT_HD int pt_walk_instance(const PtSceneView& sc, uint32_t inst, uint32_t root, 
 template <bool STATS, bool KDMESH, bool HIER, class LaneStack>
 PT_HD void pt_trace_packet_mesh(const PtSceneView& sc, const PtRay& ray, bool has_ray, bool any, PtHit& best, uint32_t* wstack, int wwords,
                                 const LaneStack& lane_stk, unsigned int* overflow, PtCounters* cnt) {
-    if (has_ray) { best.t = INFINITY; best.node = PT_NO_HIT; best.sub = 0; }
+    if (has_ray) { best.t = PT_WALK_ENTRY_T(best); best.node = PT_NO_HIT; best.sub = 0; }
     if (sc.n_nodes == 0 || sc.tlas_root == PT_REF_EMPTY) return;
     bool alive = has_ray;     // the lane still wants candidates
     bool part = has_ray;      // ... and takes part in the tree being walked (inside a mesh: its ray passed the mesh's box test)
@@ -1782,7 +1812,7 @@ PT_HD void pt_trace_packet_mesh(const PtSceneView& sc, const PtRay& ray, bool ha
     PtRayPk q = pt_raypk(ray);
     int oct = PT_OCT_MIXED;   // wave-uniform: the octant the participating lanes' rays share inside the mesh instance being walked, if they do (sc.mesh_oct)
     const bool identity_ok = HIER && pt_ray_identity_safe(ray, has_ray);  // (wave-uniform) levels of a path that are the identity may be skipped
-    float tm = INFINITY;      // best.t as the f32 bound of the slab test (t means the same in every space, ray.rs:130-135)
+    float tm = PT_WALK_ENTRY_TM(best);      // best.t as the f32 bound of the slab test (t means the same in every space, ray.rs:130-135)
     uint32_t inst = PT_NO_HIT;  // wave-uniform: flat node of the mesh instance being walked
     uint32_t cur = PT_UNIFORM_U32(sc.tlas_root);
     int sp = 0;
@@ -1881,7 +1911,7 @@ PT_HD void pt_trace_packet_mesh(const PtSceneView& sc, const PtRay& ray, bool ha
                         if (KDMESH && type == PT_KDMESH && (int32_t)head[3] >= 0) {  // the reference's own triangle tree (quirk Q3)
                             if (alive) {
                                 double t; uint32_t tri = 0;
-                                if (pt_kdmesh_hit<STATS>(sc, *mi, lr, PT_EPSILON, pt_cand_end_in<HIER>(sc, best, node, 0), lane_stk, 0, &t, &tri, cnt)) {
+                                if (PT_WALK_KDMESH_HIT(STATS, HIER, sc, *mi, lr, best, node, lane_stk, &t, &tri, cnt)) {
                                     best.t = t; best.node = node; best.sub = tri;
                                     tm = pt_tmax32(t);
                                     if (any) alive = false;
@@ -1893,7 +1923,7 @@ PT_HD void pt_trace_packet_mesh(const PtSceneView& sc, const PtRay& ray, bool ha
                         const uint32_t root = head[2];
                         if (STATS && alive) cnt->n_bbox++;
                         if (root == PT_REF_EMPTY) continue;
-                        const bool inside = alive && pt_bbox_test_hit(bi, lr, PT_EPSILON, pt_cand_end_in<HIER>(sc, best, node, 0));
+                        const bool inside = alive && pt_bbox_test_hit(bi, lr, PT_EPSILON, PT_WALK_MESH_BOX_END(HIER, sc, best, node));
                         const unsigned long long inside_mask = PT_BALLOT(inside);
                         if (!inside_mask) continue;
 #ifndef PT_MESH_MARKER_WALK

@@ -19,7 +19,7 @@ _dp, _ip, _up, _u64p, _u8p = H._dp, H._ip, H._up, H._u64p, H._u8p
 
 EXPORTS = ["ph_last_error", "ph_scene_create", "ph_example_scene", "ph_scene_destroy", "ph_scene_counts", "ph_scene_export", "ph_scene_export_textures",
            "ph_scene_flatten", "ph_scene_kdtree", "ph_camera", "ph_obj_load", "ph_renderer_create", "ph_renderer_destroy",
-           "ph_renderer_context", "ph_renderer_ranks", "ph_renderer_node", "ph_renderer_prepare_ms", "ph_renderer_render", "ph_renderer_aov", "ph_renderer_rays", "ph_renderer_radiance", "ph_renderer_update", "ph_scene_same_structure", "ph_renderer_deform", "ph_scene_same_topology", "ph_renderer_deform_device", "ph_renderer_mesh_count", "ph_renderer_mesh_vertices", "ph_example_render_to_png", "ph_png_read", "ph_png_write", "ph_image_read", "ph_scene_graph"]
+           "ph_renderer_context", "ph_renderer_ranks", "ph_renderer_node", "ph_renderer_prepare_ms", "ph_renderer_render", "ph_renderer_aov", "ph_renderer_rays", "ph_renderer_segments", "ph_renderer_radiance", "ph_renderer_update", "ph_scene_same_structure", "ph_renderer_deform", "ph_scene_same_topology", "ph_renderer_deform_device", "ph_renderer_mesh_count", "ph_renderer_mesh_vertices", "ph_example_render_to_png", "ph_png_read", "ph_png_write", "ph_image_read", "ph_scene_graph"]
 
 
 class PortrayerHostError(RuntimeError):
@@ -85,6 +85,8 @@ def lib() -> C.CDLL:
         l.ph_renderer_aov.argtypes = [vp, _dp, C.POINTER(H.PtAovParams), C.POINTER(H.PtAovBuffers), _dp]
         l.ph_renderer_rays.restype = C.c_int
         l.ph_renderer_rays.argtypes = [vp, C.POINTER(H.PtRaysParams), _dp, _dp, C.POINTER(H.PtRaysBuffers), _dp]
+        l.ph_renderer_segments.restype = C.c_int
+        l.ph_renderer_segments.argtypes = [vp, C.POINTER(H.PtRaysParams), _dp, _dp, _dp, C.POINTER(H.PtRaysBuffers), _dp]
         l.ph_renderer_radiance.restype = C.c_int
         l.ph_renderer_radiance.argtypes = [vp, C.POINTER(H.PtRadianceParams), _dp, _dp, _dp, _dp, _dp]
         l.ph_renderer_update.restype = C.c_int; l.ph_renderer_update.argtypes = [vp, vp]
@@ -436,12 +438,14 @@ class Renderer:
         out["kernel_ms"] = ms.value
         return out
 
-    def rays(self, origins, directions, any_hit: bool = False, reorder: bool = False, want=None, into: Optional[dict] = None) -> dict:
+    def rays(self, origins, directions, any_hit: bool = False, reorder: bool = False, want=None, into: Optional[dict] = None, t_max=None) -> dict:
         """Rays of the caller's own (pt_rays): `origins` and `directions` are (n, 3) float64 in world space, directions used as given (t is the ray parameter).
         Returns the arrays named in `want` - (n,) or (n, 3); t +inf, ids -1, point and normal 0, occluded 0 where nothing is hit - and `kernel_ms`.
         `want=None` is every buffer. any_hit=True asks only whether anything is in the way: `want` must then be ("occluded",), which is also what None means there. reorder=True lets the
         device group like rays before tracing; the results are the same bits. `into`: a dict of C-contiguous arrays of the right shape and dtype to write into.
-        Rays with a non-finite component, an all-zero direction or a component beyond 1e18 are not traced and report a miss. `material` is numbered as in aov()."""
+        Rays with a non-finite component, an all-zero direction or a component beyond 1e18 are not traced and report a miss. `material` is numbered as in aov().
+        `t_max` (pt_segments): a scalar or an (n,) float64 array, in units of the direction like t; ray i then answers for the segment [EPSILON, t_max[i]) only -
+        the nearest hit inside it, or with any_hit whether there is one - and a bound that is NaN or <= EPSILON reports a miss. None is the unbounded pass."""
         want = (("occluded",) if any_hit else tuple(H.RAYS_BUFFERS)) if want is None else tuple(want)
         unknown = [n for n in want if n not in H.RAYS_BUFFERS]
         if unknown or not want:
@@ -457,6 +461,13 @@ class Renderer:
         if n > H.RAYS_MAX:
             raise ValueError("at most %d rays per call" % H.RAYS_MAX)
         o, d = np.ascontiguousarray(o), np.ascontiguousarray(d)
+        if t_max is not None:
+            tm = np.asarray(t_max)
+            if tm.ndim == 0:
+                tm = np.full(n, float(tm), dtype=np.float64)
+            if tm.shape != (n,) or tm.dtype != np.float64:
+                raise ValueError("t_max must be a scalar or an (n,) float64 array, got %s %r" % (tm.dtype, tm.shape))
+            tm = np.ascontiguousarray(tm)
         out, b = {}, H.PtRaysBuffers()
         for name in want:
             dtype, comps = H.RAYS_BUFFERS[name]
@@ -468,7 +479,10 @@ class Renderer:
             setattr(b, name, _p(a, _dp if dtype is np.float64 else (_u8p if dtype is np.uint8 else _ip)))
         p = H.PtRaysParams(n, 1 if any_hit else 0, 1 if reorder else 0)
         ms = C.c_double(0.0)
-        _check(lib().ph_renderer_rays(self._h, C.byref(p), _p(o, _dp), _p(d, _dp), C.byref(b), C.byref(ms)), "ph_renderer_rays")
+        if t_max is None:
+            _check(lib().ph_renderer_rays(self._h, C.byref(p), _p(o, _dp), _p(d, _dp), C.byref(b), C.byref(ms)), "ph_renderer_rays")
+        else:
+            _check(lib().ph_renderer_segments(self._h, C.byref(p), _p(o, _dp), _p(d, _dp), _p(tm, _dp), C.byref(b), C.byref(ms)), "ph_renderer_segments")
         out["kernel_ms"] = ms.value
         return out
 

@@ -608,6 +608,16 @@ extern "C" int ph_renderer_rays(ph_renderer* r, const pt_rays_params* p, const d
     });
 }
 
+extern "C" int ph_renderer_segments(ph_renderer* r, const pt_rays_params* p, const double* origins, const double* directions, const double* t_max, const pt_rays_buffers* out,
+                                    double* kernel_ms) {
+    if (!r || !p || !out) return bad("null argument");
+    if (p->n && (!origins || !directions || !t_max)) return bad("null argument");
+    return guarded([&]() -> int {
+        r->r->segments(*p, origins, directions, t_max, *out, kernel_ms);  // (a renderer spread over a node: rank 0's context, every ray)
+        return PH_OK;
+    });
+}
+
 extern "C" int ph_renderer_radiance(ph_renderer* r, const pt_radiance_params* p, const double* origins, const double* directions, const double* background, double* rgb,
                                     double* kernel_ms) {
     if (!r || !p || !background) return bad("null argument");

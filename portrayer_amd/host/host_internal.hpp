@@ -94,6 +94,8 @@ class Renderer {
                 pt_stats* stats);
     // Rays of the caller's own (pt_rays): host buffers in and out; throws std::runtime_error with the library's message on any error.
     void rays(const pt_rays_params& params, const double* origins, const double* directions, const pt_rays_buffers& out, double* kernel_ms);
+    // The same over bounded segments (pt_segments): t_max holds n bounds; throws likewise.
+    void segments(const pt_rays_params& params, const double* origins, const double* directions, const double* t_max, const pt_rays_buffers& out, double* kernel_ms);
     // Radiance along rays of the caller's own (pt_radiance): host buffers in and out; throws likewise.
     void radiance(const pt_radiance_params& params, const double* origins, const double* directions, const double* background, double* rgb, double* kernel_ms);
     // The resident scene moved (pt_scene_update): `scene` must have the structure of the one this renderer was made from (structure_difference; throws

@@ -1012,6 +1012,10 @@ void Renderer::rays(const pt_rays_params& params, const double* origins, const d
     check(ctx_, pt_rays(ctx_, &params, origins, directions, &out, kernel_ms), "pt_rays");
 }
 
+void Renderer::segments(const pt_rays_params& params, const double* origins, const double* directions, const double* t_max, const pt_rays_buffers& out, double* kernel_ms) {
+    check(ctx_, pt_segments(ctx_, &params, origins, directions, t_max, &out, kernel_ms), "pt_segments");
+}
+
 void Renderer::radiance(const pt_radiance_params& params, const double* origins, const double* directions, const double* background, double* rgb, double* kernel_ms) {
     check(ctx_, pt_radiance(ctx_, &params, origins, directions, background, rgb, kernel_ms), "pt_radiance");
 }

@@ -148,6 +148,12 @@ extern "C" {
     pub fn pt_rays_device(ctx: *mut PtContext, params: *const PtRaysParams, d_origins: *const f64, d_directions: *const f64, device_out: *const PtRaysBuffers,
                           hip_stream: *mut c_void) -> c_int;
     pub fn pt_rays_finish(ctx: *mut PtContext, kernel_ms: *mut f64) -> c_int;
+    // the same over bounded segments: t_max holds n f64 (units of the direction, like t); ray i answers for hits with EPSILON <= t < t_max[i], a NaN or
+    // <= EPSILON bound reports a miss. Shares pt_rays' pass: pt_segments_device is closed by pt_rays_finish, one pass of either kind in flight per context.
+    pub fn pt_segments(ctx: *mut PtContext, params: *const PtRaysParams, origins: *const f64, directions: *const f64, t_max: *const f64,
+                       host_out: *const PtRaysBuffers, kernel_ms: *mut f64) -> c_int;
+    pub fn pt_segments_device(ctx: *mut PtContext, params: *const PtRaysParams, d_origins: *const f64, d_directions: *const f64, d_t_max: *const f64,
+                              device_out: *const PtRaysBuffers, hip_stream: *mut c_void) -> c_int;
     // radiance along rays of the caller's own (Ray::color as a batch): background 3 f64 or n x 3 (background_per_ray), rgb n x 3 f64, one linear sample per ray
     pub fn pt_radiance(ctx: *mut PtContext, params: *const PtRadianceParams, origins: *const f64, directions: *const f64, background: *const f64, rgb: *mut f64,
                        kernel_ms: *mut f64) -> c_int;
