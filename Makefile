@@ -101,10 +101,24 @@ verify:
 verify-mi:
 	for m in $(RENDER_MODES); do $(HIPCC) $(HIPFLAGS) --offload-device-only -mllvm -verify-machineinstrs -DPT_INST_MODE=$$m -c $(CSRC)/pt_render_inst.hip -o /dev/null || exit 1; done
 
+# `make sanitize-raypk`: the host code of pt_api.hip (the slab-test hook pt_test_raypk and everything beside it) under AddressSanitizer + UBSan, driven by
+# tools/raypk_sanitize.cpp as a program of its own on the CPU. Only the HOST side is instrumented (-Xarch_host); the object is built through the same four
+# steps as every other one, the remaining objects are the library's. The program launches nothing.
+comma := ,
+SANITIZE := -fsanitize=address$(comma)undefined
+build/sanitize/pt_api.o: $(CSRC)/pt_api.hip $(HIP_HDRS) tools/check_exec_prologue.py
+	@mkdir -p build/sanitize
+	$(call hip_four_steps,-Xarch_host $(SANITIZE) -Xarch_host -fno-omit-frame-pointer)
+sanitize-raypk: build/sanitize/pt_api.o $(HIP_OBJS)
+	$(LLVM_BIN)/clang++ -O1 -g -std=c++17 $(SANITIZE) -fno-omit-frame-pointer -c tools/raypk_sanitize.cpp -o build/sanitize/raypk_sanitize.o
+	$(HIPCC) --offload-arch=$(ARCH) -Xarch_host $(SANITIZE) build/sanitize/raypk_sanitize.o build/sanitize/pt_api.o $(filter-out $(OBJDIR)/pt_api.o,$(HIP_OBJS)) -o build/sanitize/raypk_sanitize -ldl
+	build/sanitize/raypk_sanitize
+
 clean:
 	rm -f portrayer_amd/*.so $(CSRC)/*.o
 	rm -rf build/asm
 	rm -rf build/variants
+	rm -rf build/sanitize
 	rm -rf examples/bin
 	$(MAKE) -C oracle clean
-.PHONY: all oracle clean hipobjs variant verify verify-mi
+.PHONY: all oracle clean hipobjs variant verify verify-mi sanitize-raypk

@@ -538,6 +538,12 @@ int pt_test_libm_host(int op, uint64_t n, const double *a, const double *b, doub
  * items and {pixels, chunks, samples} per wavefront. */
 int pt_test_work_items(const pt_render_params *params, uint32_t *sample_count, uint64_t *sample_index_sum, uint32_t *chunk_length_sum,
                        uint64_t *n_items, uint32_t *lane_pixels_chunks_samples);
+/* Host-side run (no GPU, no context) of the tree walks' single-precision slab test. Pair i: the ray origins[3i..], directions[3i..] over [0, t_max[i]]
+ * against the box box_lo[3i..], box_hi[3i..]. body 0: the ray constants as the kernels are built, 1: their form with f64 products, 2: their f32 form.
+ * Out per pair: the interval the per-lane form computed (t_near, t_far) and verdict - bit 0 the per-lane form accepts the box, bit 1 the wavefront
+ * form for mixed signs does, bit 2 the wavefront form for the ray's own octant does, bit 3 the two children of a wavefront form disagree. */
+int pt_test_raypk(uint64_t n, int body, const double *origins, const double *directions, const double *t_max, const float *box_lo, const float *box_hi,
+                  int32_t *verdict, float *t_near, float *t_far);
 
 #ifdef __cplusplus
 }

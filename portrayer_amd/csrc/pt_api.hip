@@ -1744,6 +1744,67 @@ extern "C" int pt_test_work_items(const pt_render_params* p, uint32_t* sample_co
     return PT_OK;
 }
 
+// Host-side run (no GPU involved) of the walks' f32 slab test: pair i is ray i (origins / directions: 3 doubles each, range [0, t_max[i]]) against box i
+// (box_lo / box_hi: 3 floats each). body 0: the constants the kernels are built with (pt_raypk), 1: the f64-product body, 2: the f32 body.
+// Out per pair: t_near / t_far = the interval of the per-lane form (pt_slab_seg_pk's expressions: entering clamped at 0, leaving at the rounded t_max) and
+// verdict, bit 0: pt_slab_seg_pk accepts, bit 1: pt_slab_pk2<PT_OCT_MIXED> accepts (the box as both children), bit 2: pt_slab_pk2 under the ray's own octant
+// accepts (a ray with a switched-off axis has no octant: bit 2 repeats bit 1), bit 3: the two children of either form disagree. Tests check that a box the
+// exact ray meets is never rejected.
+extern "C" int pt_test_raypk(uint64_t n, int body, const double* origins, const double* directions, const double* t_max, const float* box_lo, const float* box_hi,
+                             int32_t* verdict, float* t_near, float* t_far) {
+    if (!origins || !directions || !t_max || !box_lo || !box_hi || !verdict || !t_near || !t_far || body < 0 || body > 2) return PT_ERR_ARGUMENT;
+    for (uint64_t i = 0; i < n; i++) {
+        PtRay r;
+        r.o = pt_v3(origins[3 * i], origins[3 * i + 1], origins[3 * i + 2]);
+        r.d = pt_v3(directions[3 * i], directions[3 * i + 1], directions[3 * i + 2]);
+        PtRayPk q;
+        int s[3];
+        if (body == 0) {  // (what pt_raypk(r) does)
+            s[0] = pt_raypk_axis(r.o.x, r.d.x, &q.a[0], &q.b[0]); s[1] = pt_raypk_axis(r.o.y, r.d.y, &q.a[1], &q.b[1]); s[2] = pt_raypk_axis(r.o.z, r.d.z, &q.a[2], &q.b[2]);
+        } else if (body == 1) {
+            s[0] = pt_raypk_axis_f64(r.o.x, r.d.x, &q.a[0], &q.b[0]); s[1] = pt_raypk_axis_f64(r.o.y, r.d.y, &q.a[1], &q.b[1]); s[2] = pt_raypk_axis_f64(r.o.z, r.d.z, &q.a[2], &q.b[2]);
+        } else {
+            s[0] = pt_raypk_axis_f32(r.o.x, r.d.x, &q.a[0], &q.b[0]); s[1] = pt_raypk_axis_f32(r.o.y, r.d.y, &q.a[1], &q.b[1]); s[2] = pt_raypk_axis_f32(r.o.z, r.d.z, &q.a[2], &q.b[2]);
+        }
+        const float* lo = box_lo + 3 * i;
+        const float* hi = box_hi + 3 * i;
+        const float tm = pt_tmax32(t_max[i]);
+        const float ax = __builtin_fmaf(lo[0], q.a[0].x, q.a[0].y), bx = __builtin_fmaf(hi[0], q.b[0].x, q.b[0].y);
+        const float ay = __builtin_fmaf(lo[1], q.a[1].x, q.a[1].y), by = __builtin_fmaf(hi[1], q.b[1].x, q.b[1].y);
+        const float az = __builtin_fmaf(lo[2], q.a[2].x, q.a[2].y), bz = __builtin_fmaf(hi[2], q.b[2].x, q.b[2].y);
+        t_near[i] = fmaxf(fmaxf(fminf(ax, bx), fminf(ay, by)), fmaxf(fminf(az, bz), 0.0f));
+        t_far[i] = fminf(fminf(fmaxf(ax, bx), fmaxf(ay, by)), fminf(fmaxf(az, bz), tm));
+        int v = pt_slab_seg_pk(lo, hi, q, 0.0f, tm) ? 1 : 0;
+        pt_u32x16 rec;
+        for (int k = 0; k < 16; k++) rec[k] = 0u;
+        for (int k = 0; k < 3; k++) {
+            uint32_t l, h;
+            memcpy(&l, lo + k, 4); memcpy(&h, hi + k, 4);
+            rec[2 * k] = rec[2 * k + 1] = l; rec[6 + 2 * k] = rec[6 + 2 * k + 1] = h;
+        }
+        unsigned long long m0 = 0, m1 = 0, first = 0, o0 = 0, o1 = 0;
+        pt_slab_pk2<PT_OCT_MIXED>(rec, q, tm, &m0, &m1, &first);
+        o0 = m0; o1 = m1;
+        if (s[0] && s[1] && s[2]) {
+            switch ((s[0] == 2 ? 1 : 0) | (s[1] == 2 ? 2 : 0) | (s[2] == 2 ? 4 : 0)) {
+                case 0: pt_slab_pk2<0>(rec, q, tm, &o0, &o1, &first); break;
+                case 1: pt_slab_pk2<1>(rec, q, tm, &o0, &o1, &first); break;
+                case 2: pt_slab_pk2<2>(rec, q, tm, &o0, &o1, &first); break;
+                case 3: pt_slab_pk2<3>(rec, q, tm, &o0, &o1, &first); break;
+                case 4: pt_slab_pk2<4>(rec, q, tm, &o0, &o1, &first); break;
+                case 5: pt_slab_pk2<5>(rec, q, tm, &o0, &o1, &first); break;
+                case 6: pt_slab_pk2<6>(rec, q, tm, &o0, &o1, &first); break;
+                default: pt_slab_pk2<7>(rec, q, tm, &o0, &o1, &first); break;
+            }
+        }
+        if (m0) v |= 2;
+        if (o0) v |= 4;
+        if ((m0 != 0) != (m1 != 0) || (o0 != 0) != (o1 != 0)) v |= 8;
+        verdict[i] = v;
+    }
+    return PT_OK;
+}
+
 // How a launch's traversal stacks are split between LDS and HBM - one place for the render kernels and the primary-visibility pass (pt_aov_common), whose
 // kernels lay their LDS out with the same code (pt_trace_wave: pt_wave_rows, pt_kd_layout).
 // pt_stack_lds_cap: entries per lane kept in LDS = what `block_budget` bytes of LDS per block leave beside `frame_bytes` of other per-block data (1 KB a row), at most the

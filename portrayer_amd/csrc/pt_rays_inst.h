@@ -27,7 +27,7 @@ struct PtRaysArgs {
 // Which rays are traced. Every component finite, the direction not all zero, and every component at most 1e18 in magnitude: that is the bound
 // pt_scene_upload guarantees for box coordinates and the one under which every product of the f32 slab constants (pt_raypk_axis, pt_ray32_axis:
 // |1 / d| <= 1e18 or the axis is switched off; origin x reciprocal <= 1e36) stays finite, and a reciprocal of at least 1e-18 keeps the constants'
-// relative margins meaningful (a product that falls below the normal range is covered by their absolute 1e-37). A direction component BELOW 1e-18
+// relative margins meaningful (a product that falls below the normal range is covered by their absolute terms). A direction component BELOW 1e-18
 // needs no rule: its axis is switched off, which accepts every box.
 PT_HD bool pt_rays_traced(const PtRay& r) {
     const double lim = 1e18;

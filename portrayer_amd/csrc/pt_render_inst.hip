@@ -17,6 +17,12 @@
 #define PT_MAPS_BEFORE
 #define PT_LANE_MAPS_INLINE
 #endif
+// The hierarchical kernels of scenes with KDMesh trees (mode 5, PT_MODE_HIER) keep the walks' ray constants with f64 products (pt_trace.h: pt_raypk_axis_f64). With the f32 body
+// this toolchain's register allocator leaves a spill store of a register pair nothing has written in pt_render_kernel<5, true, true, 3>, which LLVM's machine
+// verifier refuses (`make verify-mi`: "Using an undefined physical register"); every other mode's object passes it with the f32 body.
+#if defined(PT_INST_MODE) && PT_INST_MODE == 5 && !defined(PT_RAYPK_F64)
+#define PT_RAYPK_F64
+#endif
 #include "pt_render_kernel.h"
 #include "pt_render_inst.h"
 

@@ -165,8 +165,49 @@ PT_HD float pt_rcp_f32(float x) {
     return 1.0f / x;
 #endif
 }
+// The constants of one axis, all in f32 (the f64 origin is converted once; -DPT_RAYPK_F64 restores the body that multiplied it in f64).
+// With u = 2^-24 (half an ulp), T = (P - o) / d the exact parameter of a plane P (an f32, |P| <= 1e18), and every subnormal result
+// allowed to be rounded OR flushed (absolute error <= 2^-126 either way; host and device differ there):
+//     i0 = rcp((float)d)             = (1 / d)(1 + e),  |e| < 2^-22.4     (the conversion u, v_rcp_f32 one ulp = 2u; the host's division u).
+//                                      Kept only for |i0| <= 1e18, i.e. |d| >= 1e-18: (float)d is normal.
+//     lo = fma(|i0|, -2^-21, i0),  hi = fma(|i0|, 2^-21, i0)     one rounding each: lo = i0 -+ |i0| 2^-21 (1 + u'), so for d > 0
+//                                      lo <= (1 / d)(1 + 2^-22.4)(1 - 2^-21)(1 + u) < (1 / d)(1 - 2^-22.1) and hi > (1 / d)(1 + 2^-22.1); for d < 0 the
+//                                      same with the magnitudes exchanged: lo is i_f, hi is i_n. lo goes with the LOWER planes (A), hi with
+//                                      the UPPER ones (B) whatever the sign - what the selects of the f64 body worked out.
+//     of = (float)o                  = o (1 + d1) + h1,  |d1| <= u, |h1| <= 2^-126
+//     w  = fma(|fl(of i0)|, 2.4e-7, 2e-20)    >= (|o i0| (1 - u)^2 4.02u + 2e-20 - 2^-126 (|i0| + 1) 2.4e-7)(1 - u)
+//     c_n = fma(-of, i_n, -w),  c_f = fma(-of, i_f, +w)     ONE rounding each (the product is not rounded on its own), so
+//         c_n <= -o i_n + |o i_n| u + 2^-126 |i_n|          (what converting o cost)
+//                      + (|o i_n| (1 + u) + 2^-126 |i_n| + w) u + 2^-126        (the fma's rounding)   - w
+//             <= -o i_n + |o i_n| (2u + u^2) + 2^-126 (|i_n| + 1)(1 + u) - w (1 - u)   <=   -o i_n
+//       because |i_n| <= |i0| <= |i_f| <= |i0| (1 + 2^-21 + 2u) makes the relative part of w at least 4u |o i_n| (1 - 2^-20) - against 2u + u^2
+//       needed, for i_f as well - and its constant part 2e-20 (1 - u) - 3e-45 > 1.18e-20 (1 + 3u) >= 2^-126 (1e18 (1 + 2^-20) + 1)(1 + u). c_f >= -o i_f
+//       likewise. A subnormal product or sum (either factor tiny) is inside the same constant.
+// Entering: fma(P, i_n, c_n) is at most (P - o) i_n before its rounding, which has the sign of T and for T > 0 is at most T (1 - 2^-22.1): the
+// rounding (1 + u) cannot lift it above T, and below 2^-126 the constant part of w (at least 0.8e-20 of it is left over) keeps it negative; for
+// T <= 0 it stays <= 0 (clamped to 0 or t0 anyway). Leaving: fma(P, i_f, c_f) >= T (1 + 2^-22.1)(1 - u) >= T for T >= 0, by the same argument.
+// A switched-off axis takes i0 = +0 and w = +inf through the same expressions: lo = hi = +0, c = fma(-of, 0, -+inf) = -+inf - A = (0, -inf), B = (0, +inf), as
+// the f64 body's early return gives them - for a finite (float)o. Where it overflows (|o| >= FLT_MAX) the product is inf x 0 and both c are NaN, which v_max / v_min
+// drop as well: the axis is still off, by another route than before.
+// All of this for finite o with |o i0| below FLT_MAX; beyond it c_n / c_f become infinities or NaNs of the harmless kind, as they did with the f64
+// product (an entering -inf, a leaving +inf; v_max / v_min drop a NaN operand).
 // returns 0: axis switched off, 1: positive direction, 2: negative direction
-PT_HD int pt_raypk_axis(double o, double d, pt_f32x2* a, pt_f32x2* b) {
+PT_HD int pt_raypk_axis_f32(double o, double d, pt_f32x2* a, pt_f32x2* b) {
+    const float r = pt_rcp_f32((float)d);
+    const bool on = fabsf(r) <= 1e18f;  // (false for a NaN as well)
+    const float i0 = on ? r : 0.0f;
+    const float of = (float)o;
+    const float k = 4.76837158203125e-7f;  // 2^-21
+    const float lo = __builtin_fmaf(fabsf(i0), -k, i0), hi = __builtin_fmaf(fabsf(i0), k, i0);
+    const float w = __builtin_fmaf(fabsf(of * i0), 2.4e-7f, 2e-20f);
+    const float sw = __builtin_copysignf(on ? w : INFINITY, i0);  // d > 0: A enters (c_n = .. - w), B leaves (c_f = .. + w); d < 0: the other way round
+    a->x = lo; a->y = __builtin_fmaf(-of, lo, -sw);
+    b->x = hi; b->y = __builtin_fmaf(-of, hi, sw);
+    return on ? (r < 0.0f ? 2 : 1) : 0;
+}
+// the constants as they were computed before, the products with the origin in f64 (derivation: the same with the conversion's u and the margin's own
+// rounding in place of the two terms above, 1e-37 for the one subnormal result): -DPT_RAYPK_F64 for an A/B, and what pt_test_raypk compares with
+PT_HD int pt_raypk_axis_f64(double o, double d, pt_f32x2* a, pt_f32x2* b) {
     const float i0 = pt_rcp_f32((float)d);
     if (!(fabsf(i0) <= 1e18f)) {
         a->x = 0.0f; a->y = -INFINITY; b->x = 0.0f; b->y = INFINITY;
@@ -181,6 +222,13 @@ PT_HD int pt_raypk_axis(double o, double d, pt_f32x2* a, pt_f32x2* b) {
     a->x = neg ? fi : in; a->y = neg ? cf : cn;
     b->x = neg ? in : fi; b->y = neg ? cn : cf;
     return neg ? 2 : 1;
+}
+PT_HD int pt_raypk_axis(double o, double d, pt_f32x2* a, pt_f32x2* b) {
+#ifdef PT_RAYPK_F64
+    return pt_raypk_axis_f64(o, d, a, b);
+#else
+    return pt_raypk_axis_f32(o, d, a, b);
+#endif
 }
 PT_HD PtRayPk pt_raypk(const PtRay& r) {  // without the wavefront's view: for walks that always take the per-lane form
     PtRayPk q;
@@ -1064,12 +1112,12 @@ PT_HD PtRay pt_node_local_ray_uniform(const PtSceneView& sc, uint32_t node, cons
 // the parameter fma(P, i, c) ~ (P - o) / d; min / max of the two planes' values are the entering / leaving parameters. The
 // constants are rounded so that every error makes the overlap LONGER (the walk may only err towards testing more candidates):
 //     i0  = rcp((float)d)                        relative error < 2^-22.4 (conversion 2^-24, v_rcp_f32 one ulp)
-//     i_n = i0 (1 - 2^-21),  i_f = i0 (1 + 2^-21)    so |i_n| < |1 / d| < |i_f| by at least 2^-23 relative, whatever i0's error
-//     c_n = fl(-o i_n) - margin,  c_f = fl(-o i_f) + margin   (the product in f64 from the f64 origin; margin = 2^-22 relative
-//                                                              + 1e-37: more than the conversion's rounding)
-// Entering: fma(P, i_n, c_n) = (P - o) i_n - m before its one rounding; for a positive parameter T = (P - o) / d that is at most
-// T (1 - 2^-23), which the fma's rounding (2^-24) cannot lift above T; a negative one stays negative (it is clamped to 0 anyway).
-// Leaving: fma(P, i_f, c_f) >= T (1 + 2^-23) (1 - 2^-24) >= T for T >= 0; a box with T < 0 lies behind the ray and may be rejected.
+//     i_n = i0 (1 - 2^-21),  i_f = i0 (1 + 2^-21)    so |i_n| < |1 / d| < |i_f| by at least 2^-22.1 relative, whatever i0's error
+//     c_n = fl(-o i_n - w),  c_f = fl(-o i_f + w)    (one fma each from the origin in f32; w = 2.4e-7 relative + 2e-20: more than the
+//                                                     origin's conversion and the fma's own rounding - the derivation is with pt_raypk_axis)
+// Entering: fma(P, i_n, c_n) <= (P - o) i_n before its one rounding; for a positive parameter T = (P - o) / d that is at most
+// T (1 - 2^-22.1), which the fma's rounding (2^-24) cannot lift above T; a negative one stays negative (it is clamped to 0 anyway).
+// Leaving: fma(P, i_f, c_f) >= T (1 + 2^-22.1) (1 - 2^-24) >= T for T >= 0; a box with T < 0 lies behind the ray and may be rejected.
 // For a box the ray really passes (entering <= leaving, leaving >= 0) the two values come out in that order, so min / max pick
 // them correctly; for any other box a wrong order can only turn a rejection into a visit or keep it a rejection.
 // An axis the ray is parallel to (|i0| > 1e18 or NaN - which also keeps every product below FLT_MAX for |coordinates| <= 1e18) is
