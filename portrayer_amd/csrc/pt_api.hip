@@ -227,6 +227,21 @@ __global__ void __launch_bounds__(256) pt_occ_seed_kernel(uint32_t* __restrict__
     occ[i] = hashed ? (uint32_t)(pt_rng_key(seed, i) % ((uint64_t)n_nodes + 1u)) : all + 1u;
 }
 
+// The launch's eye table (PtRenderArgs::eye_tab), one thread per flattened node: the node's `inv` record with its translation column replaced by the camera's eye
+// in the node's space - pt_xform_point, the function a lane of the render kernel calls on the same operands (pt_ray_to_local), compiled with the same flags, so
+// every entry carries the bits a lane would compute. The primary stage of the mesh-free flat_scene straight-line kernels reads it through the scalar cache
+// (pt_test_node_uniform, pt_hit_model). Filled in front of every launch: nothing of it outlives one (the camera moves from frame to frame, so may the nodes).
+__global__ void __launch_bounds__(256) pt_eye_table_kernel(const double* __restrict__ inv, double* __restrict__ tab, uint32_t n_nodes, double ex, double ey, double ez) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_nodes) return;
+    const double* m = inv + 12 * (size_t)i;
+    double* o = tab + 12 * (size_t)i;
+    const PtVec3 e = pt_xform_point(m, pt_v3(ex, ey, ez));
+    o[0] = m[0]; o[1] = m[1]; o[2] = m[2]; o[3] = e.x;
+    o[4] = m[4]; o[5] = m[5]; o[6] = m[6]; o[7] = e.y;
+    o[8] = m[8]; o[9] = m[9]; o[10] = m[10]; o[11] = e.z;
+}
+
 // ------------------------------------------------------------------------------------------------
 // Context
 // ------------------------------------------------------------------------------------------------
@@ -266,6 +281,7 @@ struct pt_context {
     // profiles/r05/notes.md section 2) - and the next frame's wavefronts take the places they free instead of waiting for the last one.
     struct Slot {
         PtBuf spill, stack_spill, accum, misc;     // misc: work counter + overflow flag (8 B), PtCounters at +256, the work queues behind them
+        PtBuf eye_tab;                             // the launch's eye table (pt_eye_table_kernel): n_nodes x 96 bytes, the slot's own - the other slot's frame has another camera
         hipStream_t stream = nullptr;              // pt_context_stream(ctx, slot): non-blocking, created with the context
         hipEvent_t ev0 = nullptr, ev1 = nullptr;   // around the kernels (pt_stats.kernel_ms)
         hipEvent_t copy_done = nullptr;            // behind the copy into `host`
@@ -414,7 +430,7 @@ extern "C" void pt_context_destroy(pt_context* c) {
     if (!c) return;
     hipSetDevice(c->device);
     PtBuf* bufs[] = {&c->inv, &c->fwd, &c->nrm, &c->info, &c->tri_v, &c->tri_e, &c->tri_leaf, &c->tri_n, &c->meshes, &c->materials, &c->lights,
-                     &c->bvh, &c->bvh4, &c->bvh_items, &c->kd, &c->kd_items, &c->mat_maps, &c->uv_trans, &c->tex, &c->tex_rgb, &c->srgb_lut, &c->tri_uv, &c->texview, &c->mkd, &c->mkd_items, &c->slot[0].spill, &c->slot[0].stack_spill, &c->slot[0].accum, &c->slot[0].misc, &c->slot[1].spill, &c->slot[1].stack_spill, &c->slot[1].accum, &c->slot[1].misc, &c->bg, &c->rgb, &c->linear, &c->misc, &c->node_box, &c->kd_box, &c->mkd_box, &c->mkd_item_box, &c->kd_ref, &c->g_inv, &c->g_fwd, &c->g_nrm, &c->chain_off, &c->chain, &c->dfs_rank, &c->hier_rec, &c->own_inv, &c->mesh_box_dev, &c->mesh_idx, &c->tree_parent, &c->tree_arrive, &c->deform_stage, &c->vbox};
+                     &c->bvh, &c->bvh4, &c->bvh_items, &c->kd, &c->kd_items, &c->mat_maps, &c->uv_trans, &c->tex, &c->tex_rgb, &c->srgb_lut, &c->tri_uv, &c->texview, &c->mkd, &c->mkd_items, &c->slot[0].spill, &c->slot[0].stack_spill, &c->slot[0].accum, &c->slot[0].misc, &c->slot[1].spill, &c->slot[1].stack_spill, &c->slot[1].accum, &c->slot[1].misc, &c->slot[0].eye_tab, &c->slot[1].eye_tab, &c->bg, &c->rgb, &c->linear, &c->misc, &c->node_box, &c->kd_box, &c->mkd_box, &c->mkd_item_box, &c->kd_ref, &c->g_inv, &c->g_fwd, &c->g_nrm, &c->chain_off, &c->chain, &c->dfs_rank, &c->hier_rec, &c->own_inv, &c->mesh_box_dev, &c->mesh_idx, &c->tree_parent, &c->tree_arrive, &c->deform_stage, &c->vbox};
     for (PtBuf* b : bufs) if (b->p) hipFree(b->p);
     if (c->aov.queued) { if (c->aov.closed) hipEventSynchronize(c->aov.copy_done); else hipStreamSynchronize(c->aov.stream); }  // (pt_aov_wait)
     for (PtBuf* b : {&c->aov.stack_spill, &c->aov.misc, &c->aov.out[0], &c->aov.out[1], &c->aov.out[2], &c->aov.out[3], &c->aov.out[4], &c->aov.out[5]}) if (b->p) hipFree(b->p);
@@ -1943,6 +1959,18 @@ static int pt_render_common(pt_context* c, PtRenderArgs& a, bool stats, hipStrea
     if ((rc = pt_reserve(c, sl.misc, misc_head + occ_bytes))) return rc;
     if ((rc = pt_reserve(c, sl.accum, (size_t)a.n_slots * a.n_chunks * 3 * sizeof(double)))) return rc;
     a.accum = (double*)sl.accum.p;
+    // The eye table of the mesh-free flat_scene semantics (pt_render_simple.h: EYE_TABLE): every launch in that mode gets one, whichever kernel runs - the counting,
+    // chain and interpreter kernels do not read it, and a launch's choice of kernel must never leave a kernel that does without
+#ifndef PT_NO_EYE_TABLE
+    const bool eye_table = a.scene.mode == PT_MODE_FLAT_NOMESH && a.scene.n_nodes > 0;
+#else
+    const bool eye_table = false;
+#endif
+    a.eye_tab = nullptr;
+    if (eye_table) {
+        if ((rc = pt_reserve(c, sl.eye_tab, (size_t)a.scene.n_nodes * 12 * sizeof(double)))) return rc;
+        a.eye_tab = (const double*)sl.eye_tab.p;
+    }
     a.spill = (double*)sl.spill.p;
     a.stack_spill = (uint32_t*)sl.stack_spill.p;
     a.work_counter = (unsigned int*)sl.misc.p;
@@ -1964,6 +1992,11 @@ static int pt_render_common(pt_context* c, PtRenderArgs& a, bool stats, hipStrea
     sl.mode = c->last_mode; sl.variant = c->last_variant; sl.counted = stats;
     PT_HIP(c, hipEventRecord(sl.ev0, stream));
     if (a.n_items) {
+        if (eye_table) {  // (behind ev0: pt_stats.kernel_ms pays for it)
+            hipLaunchKernelGGL(pt_eye_table_kernel, dim3((a.scene.n_nodes + 255) / 256), dim3(256), 0, stream, a.scene.inv, (double*)sl.eye_tab.p, (uint32_t)a.scene.n_nodes,
+                               a.cam.eye[0], a.cam.eye[1], a.cam.eye[2]);
+            PT_HIP(c, hipGetLastError());
+        }
         PT_HIP(c, pt_dispatch(a, stats, c->n_cu, stream, &grid, true));
         hipLaunchKernelGGL(pt_finish_kernel, dim3((a.n_slots + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, stream, a);
         PT_HIP(c, hipGetLastError());

@@ -102,7 +102,8 @@ PT_HD PtKdLayout pt_kd_layout(const PtRenderArgs& a) {
 }
 
 // One ray kind for the whole wavefront: `tracing` lanes carry `ray`; result in `hit` (untouched for the other lanes).
-template <int MODE, bool STATS>
+// EYE (PT_MODE_FLAT_NOMESH only): the rays are primary rays; the walk's leaf tests take the local origin from the launch's eye table (a.eye_tab, pt_test_node_uniform).
+template <int MODE, bool STATS, bool EYE = false>
 PT_HD void pt_trace_wave(const PtRenderArgs& a, const PtRay& ray, bool tracing, bool any, PtHit& hit, const PtStackSpill& stk, uint32_t* lds, PtCounters* cnt,
                          PtOccRef occ = PtOccRef{nullptr, 0u, 0u}) {
 #ifdef PT_CYCLES  // profiles/cycles.sh: wave cycles inside the walks -> diag[0], calls -> diag[1]
@@ -122,7 +123,8 @@ PT_HD void pt_trace_wave(const PtRenderArgs& a, const PtRay& ray, bool tracing, 
     // stack of its own, else the part behind the lanes' rows (KDMesh trees are walked per lane, pt_kdmesh_hit).
     if (MODE == PT_MODE_FLAT_NOMESH || MODE == PT_MODE_HIER_NOMESH) {
         const int words = a.stack_lds_cap * 64;
-        pt_trace_packet<STATS, MODE == PT_MODE_HIER_NOMESH>(a.scene, ray, tracing, any, hit, lds + (size_t)wave * words, words, a.overflow_flag, cnt, occ);
+        constexpr bool EYE_WALK = EYE && MODE == PT_MODE_FLAT_NOMESH;
+        pt_trace_packet<STATS, MODE == PT_MODE_HIER_NOMESH, EYE_WALK>(a.scene, ray, tracing, any, hit, lds + (size_t)wave * words, words, a.overflow_flag, cnt, occ, EYE_WALK ? a.eye_tab : nullptr);
     } else if (MODE == PT_MODE_FLAT || MODE == PT_MODE_HIER_MESH) {
         const int words = a.stack_lds_cap * 64;
         pt_trace_packet_mesh<STATS, false, MODE == PT_MODE_HIER_MESH>(a.scene, ray, tracing, any, hit, lds + (size_t)wave * words, words, stk, a.overflow_flag, cnt);
@@ -179,6 +181,24 @@ PT_HD uint32_t* pt_fork_queue(const PtRenderArgs& a, uint32_t* lds) {
 template <int MODE, bool STATS, bool TEX, int WAVES, bool CHAIN = false>
 __global__ void __launch_bounds__(PT_BLOCK, WAVES) pt_render_simple_kernel(PtRenderArgs a0) {
     constexpr bool HIER = MODE == PT_MODE_HIER || MODE == PT_MODE_HIER_NOMESH || MODE == PT_MODE_HIER_MESH;
+    // The primary stage of the mesh-free flat_scene kernel reads the camera's eye in each node's space from the launch's eye table (PtRenderArgs::eye_tab: filled once
+    // per launch, pt_eye_table_kernel) instead of transforming it in every lane for every leaf test and once more for the surface. The counting and the chain
+    // instantiations keep the per-lane transform; -DPT_NO_EYE_TABLE: every instantiation does, and no table is filled (A/B).
+#if defined(PT_NO_EYE_TABLE)
+    constexpr bool EYE_TABLE = false;
+#else
+    constexpr bool EYE_TABLE = MODE == PT_MODE_FLAT_NOMESH && !CHAIN && !STATS;
+#endif
+    // The surface of a hit from records fetched once per wavefront and node (pt_hit_surface_uniform_flat): the mesh-free flat_scene kernel of scenes without
+    // reflection or maps. The counting instantiations keep the per-lane form (-DPT_UNIFORM_HIT_STATS: they take this one and count its passes);
+    // -DPT_NO_UNIFORM_HIT: the per-lane form everywhere (A/B).
+#if defined(PT_NO_UNIFORM_HIT)
+    constexpr bool UNIFORM_HIT = false;
+#elif defined(PT_UNIFORM_HIT_STATS)
+    constexpr bool UNIFORM_HIT = MODE == PT_MODE_FLAT_NOMESH && !TEX && !CHAIN;
+#else
+    constexpr bool UNIFORM_HIT = MODE == PT_MODE_FLAT_NOMESH && !TEX && !CHAIN && !STATS;
+#endif
     extern __shared__ uint32_t pt_lds[];
     const PtRenderArgs& a = a0;
     const uint32_t lane_global = blockIdx.x * PT_BLOCK + threadIdx.x;
@@ -278,7 +298,7 @@ __global__ void __launch_bounds__(PT_BLOCK, WAVES) pt_render_simple_kernel(PtRen
         PtHit hit;
         hit.t = INFINITY; hit.node = PT_NO_HIT; hit.sub = 0;
         PT_SEC_END(3);
-        pt_trace_wave<MODE, STATS>(a, ray, live, false, hit, stk, pt_lds, &cnt);
+        pt_trace_wave<MODE, STATS, EYE_TABLE>(a, ray, live, false, hit, stk, pt_lds, &cnt);  // (EYE_TABLE is never CHAIN: this is the depth-0 walk, the only one)
         PT_SEC_SKIP();
 
         // ---- ray.rs:139-148: the background where nothing was hit, else Material::hit_color (material.rs:91-243)
@@ -291,10 +311,44 @@ __global__ void __launch_bounds__(PT_BLOCK, WAVES) pt_render_simple_kernel(PtRen
             PtRay sray;  // o = the hit point for every light; d = the direction to the light being tested
             sray.o = sray.d = pt_v3(0.0, 0.0, 0.0);
             PtVec3 color = pt_v3(0.0, 0.0, 0.0);
+            PtVec3 N = pt_v3(0.0, 0.0, 0.0);
+            bool surfaced = false;  // this lane's surface came from the wave-uniform form
+            if (UNIFORM_HIT) {
+                // One pass per DISTINCT node among the shaded lanes' hits (one pass unless the pixel's samples straddle a silhouette): the node of the first lane
+                // still pending, the lanes that share it, its records as scalar operands (pt_hit_surface_uniform_flat). Triangles stay pending for the per-lane form.
+                unsigned long long pending = PT_BALLOT(shaded);
+                [[maybe_unused]] unsigned passes = 0;
+                while (pending) {
+                    const uint32_t node = (uint32_t)__builtin_amdgcn_readlane((int)hit.node, __builtin_ctzll(pending));
+                    const bool here = shaded && hit.node == node;
+                    pending &= ~PT_BALLOT(here);
+                    const pt_u32x4 info = pt_sload4(sc.info + 4 * (size_t)node);
+                    if (info[0] == PT_TRIANGLE || info[0] == PT_MESH || info[0] == PT_KDMESH) continue;
+                    passes++;
+                    if (here) {
+                        pt_hit_surface_uniform_flat<EYE_TABLE>(sc, node, info[0], ray, hit, &sray.o, &N, a.eye_tab);
+                        mat = info[3];
+                        surfaced = true;
+                    }
+                }
+#ifdef PT_UNIFORM_HIT_STATS  // diag[0] items with a shaded lane, diag[1] those whose lanes all took ONE pass of the loop, diag[2] passes, diag[3] items with lanes left to the per-lane form
+                if (STATS && lane == 0) { cnt.diag[0]++; cnt.diag[2] += passes; }
+                { const bool left = PT_BALLOT(shaded && !surfaced) != 0ull; if (STATS && lane == 0) { if (passes == 1 && !left) cnt.diag[1]++; if (left) cnt.diag[3]++; } }
+#endif
+            }
             if (shaded) {
                 if (STATS) cnt.hits++;
-                PtVec3 N;
-                pt_hit_surface<TEX, HIER>(sc, ray, hit, &sray.o, &N, &mat, &ftag);
+                if (!surfaced) {
+                    if (EYE_TABLE && UNIFORM_HIT) {
+                        // what the loop above left: stand-alone triangles. Their local origin is transformed per lane from the eye re-read from the argument block (a scalar
+                        // operand) - with the table gathered per lane here as well the headline instantiation spills 33 registers instead of 25
+                        PtRay pr;
+                        pr.o = pt_v3(a.cam.eye[0], a.cam.eye[1], a.cam.eye[2]); pr.d = ray.d;
+                        pt_hit_surface<TEX, HIER>(sc, pr, hit, &sray.o, &N, &mat, &ftag);
+                    } else {
+                        pt_hit_surface<TEX, HIER, false, false, EYE_TABLE>(sc, ray, hit, &sray.o, &N, &mat, &ftag, a.eye_tab);
+                    }
+                }
                 fr.set_l3(PT_L_N, N);
                 fr.set_l3(PT_L_D, ray.d);
                 const double* m = sc.materials + 10 * (size_t)mat;

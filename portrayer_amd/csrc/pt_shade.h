@@ -172,6 +172,8 @@ struct PtRenderArgs {
     uint32_t* occluders;             // mesh-free scenes: the frame's occluder table, own tiles x lights (pt_trace_packet), zeroed with the work queues; nullptr: none
     uint32_t occ_row;                // own tiles per row of the slice (>= 1): the tile above is this many entries x lights back
     PtCounters* counters;
+    const double* eye_tab;           // the launch's eye table (pt_eye_table_kernel, pt_api.hip): per flattened node its `inv` record with the translation column replaced by the camera's
+                                     // eye in the node's space; nullptr: none (a scene without nodes, -DPT_NO_EYE_TABLE). Read by the mesh-free flat_scene straight-line kernels' primary stage.
 };
 
 struct PtLane {
@@ -578,11 +580,22 @@ PT_HD bool pt_identity_safe(PtVec3 v) {
 }
 
 // The hit in the node's model space: its point p and raw normal n, the ray there, the node's type and material.
-template <bool HIER>
-PT_HD void pt_hit_model(const PtSceneView& sc, const PtRay& ray, const PtHit& hit, uint32_t* type_out, uint32_t* mat_out, PtRay* local_out, PtVec3* p_out, PtVec3* n_out) {
+// EYE (flat_scene semantics, primary rays only): the ray's origin is the camera's eye, whose image in the node's space waits in the launch's eye table
+// (PtRenderArgs::eye_tab) - the same expression evaluated once per node and launch, so the same bits; ray.o is not read.
+template <bool HIER, bool EYE = false>
+PT_HD void pt_hit_model(const PtSceneView& sc, const PtRay& ray, const PtHit& hit, uint32_t* type_out, uint32_t* mat_out, PtRay* local_out, PtVec3* p_out, PtVec3* n_out,
+                        const double* eye_tab = nullptr) {
+    static_assert(!(EYE && HIER), "the eye table holds composed inverses: flat_scene semantics only");
     const uint32_t* info = sc.info + 4 * (size_t)hit.node;
     uint32_t type = info[0], flags = info[2];
-    PtRay local = pt_node_local_ray<HIER>(sc, hit.node, ray);
+    PtRay local;
+    if (EYE) {
+        const double* m = eye_tab + 12 * (size_t)hit.node;
+        local.o = pt_v3(m[3], m[7], m[11]);
+        local.d = pt_xform_dir(m, 4, ray.d);
+    } else {
+        local = pt_node_local_ray<HIER>(sc, hit.node, ray);
+    }
     PtVec3 p, n;
     if (type == PT_TRIANGLE || type == PT_MESH || type == PT_KDMESH) {
         const double* v = sc.tri_v + 9 * (size_t)hit.sub;
@@ -610,12 +623,14 @@ PT_HD void pt_hit_model(const PtSceneView& sc, const PtRay& ray, const PtHit& hi
 // are spilled around it and not around every pass: profiles/r04/notes.md section 6). Returns true when the material has a map.
 // SKIP_IDENT: identity levels of a hierarchical path are skipped on the way up (the interpreter kernel: +2 % on the dielectric scenes; the straight-line kernels are
 // as fast or faster applying every level, c51).
-template <bool TEX, bool HIER, bool MAPS_LATER = false, bool SKIP_IDENT = false>
-PT_HD bool pt_hit_surface(const PtSceneView& sc, const PtRay& ray, const PtHit& hit, PtVec3* P_out, PtVec3* N_out, uint32_t* mat_out, uint32_t* ftag_out) {
+// EYE: the hit of a primary ray, its local origin from the launch's eye table (pt_hit_model).
+template <bool TEX, bool HIER, bool MAPS_LATER = false, bool SKIP_IDENT = false, bool EYE = false>
+PT_HD bool pt_hit_surface(const PtSceneView& sc, const PtRay& ray, const PtHit& hit, PtVec3* P_out, PtVec3* N_out, uint32_t* mat_out, uint32_t* ftag_out,
+                          const double* eye_tab = nullptr) {
     uint32_t type, mat;
     PtRay local;
     PtVec3 p, n;
-    pt_hit_model<HIER>(sc, ray, hit, &type, &mat, &local, &p, &n);
+    pt_hit_model<HIER, EYE>(sc, ray, hit, &type, &mat, &local, &p, &n, eye_tab);
     PT_FENCE;
     PtVec3 P, Nw;
     if (HIER) {  // scene.rs:100-101, :111-112: every level on the way up applies its own trans / normal_trans
@@ -657,6 +672,52 @@ PT_HD bool pt_hit_surface(const PtSceneView& sc, const PtRay& ray, const PtHit& 
     }
     *P_out = P; *N_out = N; *mat_out = mat; *ftag_out = ftag;
     return later;
+}
+
+// 9 doubles (a 3x3 matrix: the 72-byte records of nrm) at a wave-uniform address through the scalar cache - 64 + 8 bytes, so nothing behind the array's last record is read
+PT_HD void pt_sload_mat9(const double* p, double m[9]) {
+    pt_u32x16 a;
+    typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+    u32x2 b;
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("s_load_dwordx16 %0, %2, 0x0\n\ts_load_dwordx2 %1, %2, 0x40\n\ts_waitcnt lgkmcnt(0)" : "=&s"(a), "=&s"(b) : "s"(pt_uniform_ptr(p)) : "memory");
+#else
+    a = *reinterpret_cast<const pt_u32x16*>(p);
+    b = *reinterpret_cast<const u32x2*>(reinterpret_cast<const char*>(p) + 64);
+#endif
+#pragma unroll
+    for (int k = 0; k < 8; k++) m[k] = pt_f64_of(a[2 * k], a[2 * k + 1]);
+    m[8] = pt_f64_of(b[0], b[1]);
+}
+
+// pt_hit_surface of the flat_scene semantics for the lanes whose hit is on the WAVE-UNIFORM analytic node `node` of type `type` (its info record is the caller's,
+// one s_load_dwordx4): the node's inverse, forward and normal matrices come through the scalar cache - three fetches for the wavefront instead of 33 doubles
+// gathered per lane from what is nearly always one address (a wavefront of the straight-line kernels is the 64 samples of one pixel) - and are scalar operands
+// of the same functions in the same order, so the same bits; the switch over the type becomes scalar branches. Not for PT_TRIANGLE / PT_MESH / PT_KDMESH hits
+// (hit.sub names a triangle per lane) and not for mapped materials: those take pt_hit_surface. EYE: a primary ray's hit - the record comes from the launch's
+// eye table, whose fourth column is the local origin (pt_hit_model).
+template <bool EYE = false>
+PT_HD void pt_hit_surface_uniform_flat(const PtSceneView& sc, uint32_t node, uint32_t type, const PtRay& ray, const PtHit& hit, PtVec3* P_out, PtVec3* N_out,
+                                       const double* eye_tab = nullptr) {
+    double m[12];
+    PtRay local;
+    if (EYE) {
+        pt_sload_mat12(eye_tab + 12 * (size_t)node, m);
+        local.o = pt_v3(m[3], m[7], m[11]);
+        local.d = pt_xform_dir(m, 4, ray.d);
+    } else {
+        pt_sload_mat12(sc.inv + 12 * (size_t)node, m);
+        local = pt_ray_to_local(m, ray);
+    }
+    PtVec3 p, n;
+    pt_prim_surface(type, hit.sub, local, hit.t, &p, &n);
+    PT_FENCE;
+    pt_sload_mat12(sc.fwd + 12 * (size_t)node, m);
+    const PtVec3 P = pt_xform_point(m, p);
+    double nm[9];
+    pt_sload_mat9(sc.nrm + 9 * (size_t)node, nm);
+    const PtVec3 Nw = pt_xform_dir(nm, 3, n);
+    *P_out = P; *N_out = pt_normalized(Nw);  // material.rs:123-125
 }
 
 // material.rs:179-210 for one light that is not occluded: (diffuse + specular) / attenuation. lcol = the light's colour,

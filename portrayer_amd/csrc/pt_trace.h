@@ -1400,14 +1400,19 @@ PT_HD pt_u32x16 pt_sload_node(const void* base, uint32_t index) {
 }
 
 // One flattened node against every participating lane's ray; `node` is wave-uniform.
-template <bool STATS, bool HIER>
-PT_HD bool pt_test_node_uniform(const PtSceneView& sc, uint32_t node, const PtRay& ray, bool identity_ok, PtHit& best, PtCounters* cnt) {
+// EYE (flat_scene semantics, primary rays): every lane's origin is the camera's eye, the same in every lane, item and wavefront of the launch. The same two
+// scalar loads then read the node's record of the launch's eye table `eye_tab` (pt_eye_table_kernel, pt_api.hip) instead of sc.inv: the inverse with its
+// translation column replaced by pt_xform_point(inverse, eye) - the local origin, bit for bit what every lane worked out per leaf test (9 f64 products and 9 sums
+// on six vector registers that no longer live through the walk); ray.o is not read. The direction is transformed as before.
+template <bool STATS, bool HIER, bool EYE = false>
+PT_HD bool pt_test_node_uniform(const PtSceneView& sc, uint32_t node, const PtRay& ray, bool identity_ok, PtHit& best, PtCounters* cnt, const double* eye_tab = nullptr) {
+    static_assert(!(EYE && HIER), "the eye table holds composed inverses: flat_scene semantics only");
     // the node's record in one round trip through the scalar cache: {type, data, flags, material} and rows 0..2 of its inverse
     pt_u32x4 info;
     pt_u32x16 a;  // doubles 0..7 of the 3x4 inverse
     pt_u32x8 b;   // doubles 8..11
     const void* info_ptr = sc.info + 4 * (size_t)node;
-    const void* rec = sc.inv + 12 * (size_t)node;
+    const void* rec = (EYE ? eye_tab : sc.inv) + 12 * (size_t)node;
 #if defined(__HIP_DEVICE_COMPILE__)
     pt_u32x8 hrec;  // HIER: the node's path record
     if (HIER) {  // ... the node's path record (hier_rec) and the inverse of its OWN level instead of a composed inverse
@@ -1437,6 +1442,7 @@ PT_HD bool pt_test_node_uniform(const PtSceneView& sc, uint32_t node, const PtRa
 #pragma unroll
         for (int k = 0; k < 4; k++) m[8 + k] = pt_f64_of(b[2 * k], b[2 * k + 1]);
         if (HIER) local = pt_node_local_ray_rec_own(sc, node, hrec, m, ray, identity_ok);
+        else if (EYE) { local.o = pt_v3(m[3], m[7], m[11]); local.d = pt_xform_dir(m, 4, ray.d); }
         else local = pt_ray_to_local(m, ray);
     }
     if (STATS) cnt->n_analytic++;
@@ -1616,10 +1622,11 @@ PT_HD void pt_descend_mesh(const PtBvhNode* bvh, const PtRayPk& q, float tm, uns
 
 // wstack: the wavefront's own stack in LDS, `wwords` 32-bit words, linear. `live` = false: the lane's (shadow) ray is answered
 // already - its `best` is kept and it takes no part in the walk, while everything wave-wide (octant, identity levels) still follows
-// `has_ray`, as if it did (pt_trace_packet's occluder test).
-template <bool STATS, bool HIER>
+// `has_ray`, as if it did (pt_trace_packet's occluder test). EYE: a walk of primary rays whose leaf tests take the local origin from `eye_tab`
+// (pt_test_node_uniform); ray.o is read for the slab test's constants at the top and not after.
+template <bool STATS, bool HIER, bool EYE = false>
 PT_HD void pt_trace_packet_walk(const PtSceneView& sc, const PtRay& ray, bool has_ray, bool any, PtHit& best, uint32_t* wstack, int wwords,
-                                unsigned int* overflow, PtCounters* cnt, bool live = true) {
+                                unsigned int* overflow, PtCounters* cnt, bool live = true, const double* eye_tab = nullptr) {
     if (has_ray && live) { best.t = PT_WALK_ENTRY_T(best); best.node = PT_NO_HIT; best.sub = 0; }
     if (sc.n_nodes == 0 || sc.tlas_root == PT_REF_EMPTY) return;
     const unsigned long long self = 1ull << PT_LANE_ID();
@@ -1672,7 +1679,7 @@ PT_HD void pt_trace_packet_walk(const PtSceneView& sc, const PtRay& ray, bool ha
             const uint32_t node = sc.tlas_direct ? first : PT_UNIFORM_U32(sc.bvh_items[first + i]);
             if (alive && (!STATS || (in & self))) {
                 if (STATS) cnt->n_leaf++;
-                if (pt_test_node_uniform<STATS, HIER>(sc, node, ray, identity_ok, best, cnt)) {
+                if (pt_test_node_uniform<STATS, HIER, EYE>(sc, node, ray, identity_ok, best, cnt, eye_tab)) {
                     tm = pt_tmax32(best.t);
                     if (any) alive = false;
                 }
@@ -1715,9 +1722,14 @@ struct PtOccRef {
 // wave-wide identity_ok). Lanes it does not block walk as before; the walk may test that node again for them, which changes nothing.
 // The counting build walks as before (its node counts are compared with the oracle's); -DPT_OCCLUDER_STATS makes it count, per
 // light, what the test would have saved (diag[], see below) without changing the walk.
-template <bool STATS, bool HIER>
+// EYE: primary rays (nearest hit, no table entry) whose walk reads the launch's eye table (pt_trace_packet_walk).
+template <bool STATS, bool HIER, bool EYE = false>
 PT_HD void pt_trace_packet(const PtSceneView& sc, const PtRay& ray, bool has_ray, bool any, PtHit& best, uint32_t* wstack, int wwords,
-                           unsigned int* overflow, PtCounters* cnt, PtOccRef occ = PtOccRef{nullptr, 0u, 0u}) {
+                           unsigned int* overflow, PtCounters* cnt, PtOccRef occ = PtOccRef{nullptr, 0u, 0u}, const double* eye_tab = nullptr) {
+    if (EYE) {
+        pt_trace_packet_walk<STATS, HIER, EYE>(sc, ray, has_ray, false, best, wstack, wwords, overflow, cnt, true, eye_tab);
+        return;
+    }
 #if defined(__HIP_DEVICE_COMPILE__)
 #ifdef PT_OCCLUDER_STATS
     constexpr bool COUNT_OCC = STATS;
