@@ -34,7 +34,8 @@ HIP_OBJS := $(OBJDIR)/pt_api.o $(OBJDIR)/pt_build.o $(OBJDIR)/pt_node.o $(foreac
             $(foreach m,$(RENDER_MODES),$(OBJDIR)/pt_aov_m$(m).o) \
             $(OBJDIR)/pt_rays_sort.o $(foreach m,$(RENDER_MODES),$(OBJDIR)/pt_rays_m$(m).o) \
             $(foreach m,$(RENDER_MODES),$(OBJDIR)/pt_radiance_m$(m).o) \
-            $(foreach m,$(RENDER_MODES),$(OBJDIR)/pt_segments_m$(m).o)
+            $(foreach m,$(RENDER_MODES),$(OBJDIR)/pt_segments_m$(m).o) \
+            $(OBJDIR)/pt_film.o $(foreach m,$(RENDER_MODES),$(OBJDIR)/pt_film_m$(m).o)
 
 # Every HIP translation unit is built in four steps instead of one `hipcc -c`, so that the device code can be CHECKED and REPAIRED between
 # the compiler and the assembler (tools/check_exec_prologue.py; profiles/r05/notes.md section 1: the AMDGPU backend of this toolchain can put
@@ -77,6 +78,11 @@ $(OBJDIR)/pt_segments_m%.o: $(CSRC)/pt_segments_inst.hip $(HIP_HDRS) tools/check
 
 # the radiance pass (pt_radiance.h): the interpreter over the caller's rays, <TEX, PARK> instantiations per mode
 $(OBJDIR)/pt_radiance_m%.o: $(CSRC)/pt_radiance_inst.hip $(HIP_HDRS) tools/check_exec_prologue.py
+	$(call hip_four_steps,-DPT_INST_MODE=$*)
+
+# the film's sampling kernel (pt_film.h): the same interpreter with the camera as its source, <TEX, PARK> instantiations per mode; its fold and resolve
+# kernels (pt_film.hip) are built by the %.o rule
+$(OBJDIR)/pt_film_m%.o: $(CSRC)/pt_film_inst.hip $(HIP_HDRS) tools/check_exec_prologue.py
 	$(call hip_four_steps,-DPT_INST_MODE=$*)
 
 $(HIPLIB): $(HIP_OBJS)

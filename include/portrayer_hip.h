@@ -446,6 +446,45 @@ int pt_radiance(pt_context *ctx, const pt_radiance_params *params, const double 
 int pt_radiance_device(pt_context *ctx, const pt_radiance_params *params, const double *d_origins, const double *d_directions, const double *d_background, double *d_rgb, void *hip_stream);
 int pt_radiance_finish(pt_context *ctx, double *kernel_ms);
 
+/* ---- Film: a width x height accumulator in DEVICE memory that belongs to a context - a preview that sharpens, a render that can stop when it is good enough,
+ * more samples where the image is noisy. Per pixel: `total` (3 f64, the sum of its complete 8-sample chunks), `partial` (3 f64, the sum of the open chunk) and
+ * `count` (u32, samples taken so far): 52 bytes, nothing per sample.
+ *   pt_film_add gives every pixel p of `slice` the samples count[p] .. count[p] + samples - 1, each taken exactly as pt_render takes that sample of that pixel
+ *     (PT_SAMPLE_RNG: jitter from draws 0 and 1, x before y; PT_SAMPLE_CENTRE: (0.5, 0.5); the background at the integer pixel; draws 2, 3, ... along the
+ *     recursion), and folds them in ascending order into total / partial the way a render's chunk sums associate.
+ *   pt_film_resolve writes, for every pixel with count > 0, what pt_render writes with samples = count[p]: the mean as `linear` (width x height x 3 f64) and
+ *     gamma, clamp, u8 as `rgb` (width x height x 3). Pixels with count == 0 are left untouched, as pt_render leaves pixels outside its slice.
+ * PROMISE: if every pt_film_add to a film used the same camera, background, seed and sample mode and the resident scene did not change, rgb and linear at p
+ * carry the bits of pt_render(samples = count[p]) - however the samples were split over calls and slices, in all three traversals. Mixing cameras or seeds
+ * is not an error: the film adds what it is given; pt_film_reset zeroes the counts. A film needs no scene except to add, and survives pt_scene_upload.
+ * The film is not a faster pt_render: its kernel is the per-lane interpreter whatever the scene (DESIGN 4.12 has the measurements).
+ * Errors, before the first HIP call and with the film unchanged: PT_ERR_ARGUMENT (NULL context, film, camera, background, params or out; a film of another
+ * context; width or height 0, or 2^31 pixels or more; a bad sample_mode; background_rows other than 0 or 1; samples == 0; a pixel's count that would pass 2^31;
+ * a radiance or film pass in flight; both resolve buffers NULL), PT_ERR_SLICE as for a render, PT_ERR_NO_SCENE (add only). An inverted slice adds nothing and
+ * is PT_OK. During the pass: PT_ERR_TRAVERSAL as for a render (the film then holds invalid samples: reset it). */
+typedef struct pt_film pt_film;
+typedef struct {
+    pt_rect slice;              /* pixels that get samples                                                        */
+    uint32_t samples;           /* per pixel of the slice, > 0                                                    */
+    uint64_t seed;              /* as pt_render_params.seed                                                       */
+    int32_t sample_mode;        /* PT_SAMPLE_*                                                                    */
+    int32_t background_rows;    /* 1: background is height x 3; 0: height x width x 3 (the FILM's width, height)  */
+} pt_film_params;
+int pt_film_create(pt_context *ctx, uint32_t width, uint32_t height, pt_film **out);
+int pt_film_destroy(pt_context *ctx, pt_film *film);   /* films still alive die with the context */
+int pt_film_reset(pt_context *ctx, pt_film *film);
+/* Host background, synchronous. kernel_ms (optional): device time of the sampling launches and their folds (HIP events). */
+int pt_film_add(pt_context *ctx, pt_film *film, const pt_camera *camera, const double *background, const pt_film_params *params, double *kernel_ms);
+/* The same with the background in DEVICE memory, queued on `hip_stream` without synchronising the host. A film pass IS a radiance pass for bookkeeping (as
+ * pt_segments is a rays pass): it uses the radiance pass's work buffers and its one pass in flight, is closed by pt_radiance_finish, is refused while a
+ * radiance or film pass is open, and counts as a render in flight for pt_scene_update / pt_scene_deform. (An inverted slice queues nothing.) */
+int pt_film_add_device(pt_context *ctx, pt_film *film, const pt_camera *camera, const double *d_background, const pt_film_params *params, void *hip_stream);
+/* Host buffers, either may be NULL but not both; synchronous. */
+int pt_film_resolve(pt_context *ctx, pt_film *film, uint8_t *rgb, double *linear);
+/* Device buffers, queued on `hip_stream` (behind a pt_film_add_device on the same stream it sees that pass's samples). */
+int pt_film_resolve_device(pt_context *ctx, pt_film *film, void *d_rgb, double *d_linear, void *hip_stream);
+int pt_film_counts(pt_context *ctx, pt_film *film, uint32_t *counts);   /* host, width x height */
+
 /* Bytes of one rank's compact tile buffer for a slice split over tile_ranks ranks (equal for all ranks). */
 uint64_t pt_compact_bytes(const pt_render_params *params);
 /* Scatters the gathered compact buffers (rank-major) into a row-major image on the device. */
@@ -544,6 +583,9 @@ int pt_test_work_items(const pt_render_params *params, uint32_t *sample_count, u
  * form for mixed signs does, bit 2 the wavefront form for the ray's own octant does, bit 3 the two children of a wavefront form disagree. */
 int pt_test_raypk(uint64_t n, int body, const double *origins, const double *directions, const double *t_max, const float *box_lo, const float *box_hi,
                   int32_t *verdict, float *t_near, float *t_far);
+/* Host-side run (no GPU, no context) of the film's running sum: `samples` (n x 3) given to one pixel in n_cuts consecutive adds of cuts[k] samples each
+ * (their sum must be n), through the functions the film's fold and resolve kernels call. out_sum: what resolve divides by n. */
+int pt_test_film_fold_host(uint32_t n, const double *samples, const uint32_t *cuts, uint32_t n_cuts, double out_sum[3]);
 
 #ifdef __cplusplus
 }

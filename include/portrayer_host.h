@@ -159,6 +159,18 @@ int64_t ph_renderer_mesh_vertices(ph_renderer *r, uint32_t mesh);
 int ph_renderer_radiance(ph_renderer *r, const pt_radiance_params *params, const double *origins, const double *directions, const double *background, double *rgb,
                          double *kernel_ms);
 
+/* A film of the renderer (see pt_film_create ... pt_film_counts): samples accumulate in device memory, add after add, and ph_renderer_film_resolve gives at
+ * every pixel the bits of a render with that pixel's count of samples. `camera` as for ph_renderer_render: the camera a render of the film's size gets. The
+ * background is height x width x 3 doubles, or height x 3 with params->background_rows. A renderer spread over several ranks (PORTRAYER_GPUS) refuses to
+ * create a film (PH_ERR_ARGUMENT): a film lives on one device. PH_ERR_PANIC: a slice corner outside the film; PH_ERR_RUNTIME: what the library refuses. */
+typedef struct ph_film ph_film;
+int ph_renderer_film_create(ph_renderer *r, uint32_t width, uint32_t height, ph_film **out);
+int ph_renderer_film_destroy(ph_renderer *r, ph_film *film);   /* before the renderer; films still alive die with it */
+int ph_renderer_film_reset(ph_renderer *r, ph_film *film);
+int ph_renderer_film_add(ph_renderer *r, ph_film *film, const double camera[10], const double *background, const pt_film_params *params, double *kernel_ms);
+int ph_renderer_film_resolve(ph_renderer *r, ph_film *film, uint8_t *rgb, double *linear);   /* either may be NULL, not both */
+int ph_renderer_film_counts(ph_renderer *r, ph_film *film, uint32_t *counts);
+
 /* Image::new + Image::render + Image::save with the crate's defaults (env SAMPLES, KD_DEPTH) on an
  * example scene: exercises the whole C++ API the way the reference's main() does. */
 int ph_example_render_to_png(const char *name, const char *assets_dir, int n, uint32_t width, uint32_t height, const char *png_path);

@@ -123,6 +123,11 @@ class PtRadianceParams(C.Structure):
     _fields_ = [("n", C.c_uint64), ("reorder", C.c_int32), ("background_per_ray", C.c_int32), ("seed", C.c_uint64), ("stream_base", C.c_uint64), ("sample", C.c_uint32)]
 
 
+class PtFilmParams(C.Structure):
+    """pt_film_params: one add to a film - the slice that gets samples, how many per pixel, and the render's seed, sample mode and background shape."""
+    _fields_ = [("slice", PtRect), ("samples", C.c_uint32), ("seed", C.c_uint64), ("sample_mode", C.c_int32), ("background_rows", C.c_int32)]
+
+
 class PtStats(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("primary", "shadow", "reflect", "refract", "depth11_skipped", "hits", "n_inner", "n_leaf",
                                           "n_analytic", "n_tri", "n_bbox", "kd_plane_miss", "stack_overflow")] + \
@@ -144,7 +149,9 @@ EXPORTS = ["pt_abi_version", "pt_device_count", "pt_context_create", "pt_context
            "pt_node_device", "pt_node_frame_begin", "pt_node_frame_end", "pt_node_frames_in_flight", "pt_node_last_frame_host_ms", "pt_node_last_frame_rank_kernel_ms", "pt_test_pow_host", "pt_test_libm_host",
            "pt_aov", "pt_aov_device", "pt_aov_finish", "pt_rays", "pt_rays_device", "pt_rays_finish", "pt_segments", "pt_segments_device",
            "pt_radiance", "pt_radiance_device", "pt_radiance_finish", "pt_scene_update", "pt_node_scene_update", "pt_scene_deform", "pt_node_scene_deform", "pt_scene_mesh_rebuildable", "pt_test_scene_bytes", "pt_test_scene_info",
-           "pt_vertex_bounds_device", "pt_scene_deform_device", "pt_test_vertex_box_shape", "pt_test_raypk"]
+           "pt_vertex_bounds_device", "pt_scene_deform_device", "pt_test_vertex_box_shape", "pt_test_raypk",
+           "pt_film_create", "pt_film_destroy", "pt_film_reset", "pt_film_add", "pt_film_add_device", "pt_film_resolve", "pt_film_resolve_device", "pt_film_counts",
+           "pt_test_film_fold_host"]
 
 
 def header_functions():
@@ -295,6 +302,23 @@ def lib() -> C.CDLL:
         l.pt_radiance_device.argtypes = [C.c_void_p, C.POINTER(PtRadianceParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         l.pt_radiance_finish.restype = C.c_int
         l.pt_radiance_finish.argtypes = [C.c_void_p, _dp]
+        l.pt_film_create.restype = C.c_int
+        l.pt_film_create.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]
+        for name in ("pt_film_destroy", "pt_film_reset"):
+            getattr(l, name).restype = C.c_int
+            getattr(l, name).argtypes = [C.c_void_p, C.c_void_p]
+        l.pt_film_add.restype = C.c_int
+        l.pt_film_add.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(PtCamera), _dp, C.POINTER(PtFilmParams), _dp]
+        l.pt_film_add_device.restype = C.c_int
+        l.pt_film_add_device.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(PtCamera), C.c_void_p, C.POINTER(PtFilmParams), C.c_void_p]
+        l.pt_film_resolve.restype = C.c_int
+        l.pt_film_resolve.argtypes = [C.c_void_p, C.c_void_p, _u8p, _dp]
+        l.pt_film_resolve_device.restype = C.c_int
+        l.pt_film_resolve_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        l.pt_film_counts.restype = C.c_int
+        l.pt_film_counts.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]
+        l.pt_test_film_fold_host.restype = C.c_int
+        l.pt_test_film_fold_host.argtypes = [C.c_uint32, _dp, C.POINTER(C.c_uint32), C.c_uint32, _dp]
         _lib = l
     return _lib
 

@@ -19,6 +19,7 @@
 #include "pt_rays_inst.h"
 #include "pt_segments_inst.h"
 #include "pt_radiance_inst.h"
+#include "pt_film_inst.h"
 #include "pt_render_inst.h"
 #include "pt_shade.h"
 
@@ -250,6 +251,7 @@ struct PtBuf {
     size_t bytes = 0;
 };
 
+struct pt_film;
 struct pt_context {
     int device = 0;
     int n_cu = 0;
@@ -326,6 +328,10 @@ struct pt_context {
         hipStream_t stream = nullptr;
         bool queued = false, closed = false;  // as in Aov
     } radiance;
+    // Films (pt_film_create): each owns its device state; a film pass is a radiance pass for bookkeeping (pt_film_add_device), film_open names the film of the
+    // one in flight. Films still alive die with the context.
+    std::vector<pt_film*> films;
+    pt_film* film_open = nullptr;
     // What pt_scene_update needs of the uploaded scene besides the device buffers: everything a flattened node's world box is made of apart from its
     // matrix, the node paths (identity bits of hier_rec, own_inv), where the scene-level tree sits in bvh / bvh4 (bvh_items with PORTRAYER_TLAS_LEAF != 1),
     // and the figures stack_cap and forkable are derived from.
@@ -368,6 +374,20 @@ struct pt_context {
     double root_lo[3] = {0.0, 0.0, 0.0}, root_hi[3] = {0.0, 0.0, 0.0};  // the scene tree's root box: union of the flattened nodes' world boxes (reorder = 1 quantises origins inside it)
 };
 #define PT_SLOT_BYTES (256 + sizeof(PtCounters))
+
+// A film (include/portrayer_hip.h): per pixel the sum of its complete chunks, the sum of its open chunk and its count, row-major; the staging buffer the
+// sampling kernel writes a launch's samples to (sized for the largest slice seen); device copies for the host-buffer paths; and the counts again on the host,
+// so that an add that would take a pixel past 2^31 samples is refused before any HIP call.
+struct pt_film {
+    pt_context* ctx = nullptr;
+    uint32_t width = 0, height = 0;
+    PtBuf total, partial, count, staging, bg, out_rgb, out_linear;
+    std::vector<uint32_t> counts;
+};
+static void pt_film_free(pt_film* f) {
+    for (PtBuf* b : {&f->total, &f->partial, &f->count, &f->staging, &f->bg, &f->out_rgb, &f->out_linear}) if (b->p) hipFree(b->p);
+    delete f;
+}
 
 static int pt_fail(pt_context* c, int code, const std::string& msg) {
     if (c) c->err = msg;
@@ -458,6 +478,8 @@ extern "C" void pt_context_destroy(pt_context* c) {
         if (y.copy_done) hipEventDestroy(y.copy_done);
         if (y.host) hipHostFree(y.host);
     }
+    for (pt_film* f : c->films) pt_film_free(f);  // (behind the radiance pass's wait above: nothing of a film pass is in flight any more)
+    c->films.clear();
     static_assert(pt_context::PT_SLOTS == 2, "the buffer list above names both slots");
     for (auto& sl : c->slot) {
         if (sl.stream) { hipStreamSynchronize(sl.stream); hipStreamDestroy(sl.stream); }
@@ -2679,9 +2701,250 @@ extern "C" int pt_radiance_finish(pt_context* c, double* kernel_ms) {
     if (!c->radiance.pending) return pt_fail(c, PT_ERR_ARGUMENT, "no pt_radiance_device pass in flight");
     PT_HIP(c, hipSetDevice(c->device));
     c->radiance.pending = false;
+    c->film_open = nullptr;
     int rc = pt_radiance_wait(c);
     if (rc) return rc;
     return pt_radiance_close(c, kernel_ms);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Film: samples accumulate on the device (pt_film.h, pt_film.hip)
+// ------------------------------------------------------------------------------------------------
+static hipError_t pt_film_dispatch(const PtFilmArgs& a, bool tex, bool park, int n_cu, hipStream_t stream, uint32_t* grid, bool launch) {
+    switch (a.r.scene.mode) {
+    case PT_MODE_KD: return pt_film_launch_mode_2(a, tex, park, n_cu, stream, grid, launch);
+    case PT_MODE_FLAT_NOMESH: return pt_film_launch_mode_3(a, tex, park, n_cu, stream, grid, launch);
+    case PT_MODE_FLAT_KDMESH: return pt_film_launch_mode_4(a, tex, park, n_cu, stream, grid, launch);
+    case PT_MODE_HIER: return pt_film_launch_mode_5(a, tex, park, n_cu, stream, grid, launch);
+    case PT_MODE_HIER_NOMESH: return pt_film_launch_mode_6(a, tex, park, n_cu, stream, grid, launch);
+    case PT_MODE_KD_NOMESH: return pt_film_launch_mode_7(a, tex, park, n_cu, stream, grid, launch);
+    case PT_MODE_HIER_MESH: return pt_film_launch_mode_8(a, tex, park, n_cu, stream, grid, launch);
+    case PT_MODE_KD_MESH: return pt_film_launch_mode_9(a, tex, park, n_cu, stream, grid, launch);
+    default: return pt_film_launch_mode_1(a, tex, park, n_cu, stream, grid, launch);
+    }
+}
+
+#define PT_FILM_COUNT_MAX 0x80000000u  // a pixel holds at most 2^31 samples: count + a launch's lane offset never wraps
+
+// The context's own film, and no pass of its own in flight (`busy`: calls that read or write its state from the host). The handle is looked up, not
+// dereferenced: a film of another context, or one already destroyed, is refused like a NULL.
+static int pt_film_handle(pt_context* c, pt_film* f, bool busy, const char* who) {
+    if (!c) return PT_ERR_ARGUMENT;
+    if (!f || std::find(c->films.begin(), c->films.end(), f) == c->films.end()) return pt_fail(c, PT_ERR_ARGUMENT, std::string(who) + ": NULL film, or not a film of this context");
+    if (busy && c->radiance.pending && c->film_open == f) return pt_fail(c, PT_ERR_ARGUMENT, std::string(who) + ": a pt_film_add_device pass of this film is in flight: pt_radiance_finish first");
+    return PT_OK;
+}
+
+extern "C" int pt_film_create(pt_context* c, uint32_t width, uint32_t height, pt_film** out) {
+    if (out) *out = nullptr;
+    if (!c || !out) return pt_fail(c, PT_ERR_ARGUMENT, "pt_film_create: NULL context or out");
+    if (width == 0 || height == 0 || (uint64_t)width * height >= 0x80000000ull) return pt_fail(c, PT_ERR_ARGUMENT, "pt_film_create: width and height must be positive, below 2^31 pixels");
+    PT_HIP(c, hipSetDevice(c->device));
+    pt_film* f = new pt_film();
+    f->ctx = c; f->width = width; f->height = height;
+    const size_t n = (size_t)width * height;
+    int rc;
+    if ((rc = pt_reserve(c, f->total, n * 24)) || (rc = pt_reserve(c, f->partial, n * 24)) || (rc = pt_reserve(c, f->count, n * 4))) { pt_film_free(f); return rc; }
+    if (hipMemset(f->total.p, 0, n * 24) != hipSuccess || hipMemset(f->partial.p, 0, n * 24) != hipSuccess || hipMemset(f->count.p, 0, n * 4) != hipSuccess ||
+        hipDeviceSynchronize() != hipSuccess) {
+        pt_film_free(f);
+        return pt_fail(c, PT_ERR_DEVICE, "pt_film_create: clearing the film failed");
+    }
+    f->counts.assign(n, 0u);
+    c->films.push_back(f);
+    *out = f;
+    return PT_OK;
+}
+
+extern "C" int pt_film_destroy(pt_context* c, pt_film* f) {
+    int rc = pt_film_handle(c, f, true, "pt_film_destroy");
+    if (rc) return rc;
+    PT_HIP(c, hipSetDevice(c->device));
+    c->films.erase(std::find(c->films.begin(), c->films.end(), f));
+    pt_film_free(f);  // (hipFree waits for whatever still reads the buffers)
+    return PT_OK;
+}
+
+// The counts to zero: total and partial need no clearing, the first sample of a pixel is assigned (pt_film_fold).
+extern "C" int pt_film_reset(pt_context* c, pt_film* f) {
+    int rc = pt_film_handle(c, f, true, "pt_film_reset");
+    if (rc) return rc;
+    PT_HIP(c, hipSetDevice(c->device));
+    PT_HIP(c, hipMemset(f->count.p, 0, f->counts.size() * 4));
+    PT_HIP(c, hipDeviceSynchronize());
+    std::fill(f->counts.begin(), f->counts.end(), 0u);
+    return PT_OK;
+}
+
+// Everything that can be refused without a HIP call, in the order the header gives.
+static int pt_film_add_check(pt_context* c, pt_film* f, const pt_camera* cam, const double* background, const pt_film_params* p) {
+    if (!c || !f || !cam || !background || !p) return pt_fail(c, PT_ERR_ARGUMENT, "pt_film_add: NULL context, film, camera, background or params");
+    int rc = pt_film_handle(c, f, false, "pt_film_add");
+    if (rc) return rc;
+    if (p->sample_mode != PT_SAMPLE_CENTRE && p->sample_mode != PT_SAMPLE_RNG) return pt_fail(c, PT_ERR_ARGUMENT, "pt_film_add: bad sample_mode");
+    if (p->background_rows != 0 && p->background_rows != 1) return pt_fail(c, PT_ERR_ARGUMENT, "pt_film_add: background_rows is 0 or 1");
+    if (p->samples == 0) return pt_fail(c, PT_ERR_ARGUMENT, "pt_film_add: samples must be positive");
+    if (p->slice.x0 >= f->width || p->slice.x1 >= f->width || p->slice.y0 >= f->height || p->slice.y1 >= f->height)
+        return pt_fail(c, PT_ERR_SLICE, "slice corner outside the image (render.rs:79-90)");
+    if (!c->have_scene) return pt_fail(c, PT_ERR_NO_SCENE, "no scene uploaded");
+    if (c->radiance.pending) return pt_fail(c, PT_ERR_ARGUMENT, "a pt_radiance_device / pt_film_add_device pass is in flight: pt_radiance_finish first");
+    if (p->samples > PT_FILM_COUNT_MAX) return pt_fail(c, PT_ERR_ARGUMENT, "pt_film_add: a pixel's count would pass 2^31");
+    for (uint32_t y = p->slice.y0; y <= p->slice.y1 && p->slice.x0 <= p->slice.x1; y++) {
+        const uint32_t* row = f->counts.data() + (size_t)y * f->width;
+        for (uint32_t x = p->slice.x0; x <= p->slice.x1; x++)
+            if (row[x] > PT_FILM_COUNT_MAX - p->samples) return pt_fail(c, PT_ERR_ARGUMENT, "pt_film_add: a pixel's count would pass 2^31");
+    }
+    return PT_OK;
+}
+static bool pt_film_slice_empty(const pt_film_params* p) { return p->slice.x1 < p->slice.x0 || p->slice.y1 < p->slice.y0; }  // render.rs:60-65: an inverted slice renders nothing
+
+// Queues the add on `stream` as a radiance pass (its work buffers, events and pinned page): queues + overflow flag zeroed; between the pass's two events, per
+// at most `lw` samples, the sampling kernel and its fold (the queues zeroed again in between); the flag copied to the pinned page behind them. d_background is
+// a DEVICE pointer. LDS per block as the radiance pass has it.
+static int pt_film_add_common(pt_context* c, pt_film* f, const pt_camera* cam, const double* d_background, const pt_film_params* p, hipStream_t stream) {
+    pt_context::Radiance& v = c->radiance;
+    if (!v.ev0) {
+        PT_HIP(c, hipEventCreate(&v.ev0));
+        PT_HIP(c, hipEventCreate(&v.ev1));
+        PT_HIP(c, hipEventCreateWithFlags(&v.copy_done, hipEventDisableTiming));
+        PT_HIP(c, hipHostMalloc((void**)&v.host, 256, hipHostMallocDefault));
+    }
+    pt_render_params rp;
+    memset(&rp, 0, sizeof rp);
+    rp.width = f->width; rp.height = f->height; rp.slice = p->slice;
+    rp.samples = 1; rp.seed = p->seed; rp.sample_mode = p->sample_mode; rp.background_rows = p->background_rows; rp.tile_rank = 0; rp.tile_ranks = 1;
+    PtFilmArgs a;
+    memset(&a, 0, sizeof a);  // (no occluder table, no counters, no work counter: null)
+    pt_fill_args(c, cam, &rp, &a.r);  // the camera, the slice and its pixel slots; the work items are the film's own (below)
+    a.r.background = d_background;
+    uint32_t lw = PT_FILM_LW;
+    if (const char* e = getenv("PORTRAYER_FILM_LW")) { const int w = atoi(e); if (w == 8 || w == 64) lw = (uint32_t)w; }  // measurements (profiles/film)
+    a.lw = lw;
+    a.count = (const uint32_t*)f->count.p;
+    const int mode = a.r.scene.mode;
+    const bool kd_sem = mode == PT_MODE_KD || mode == PT_MODE_KD_NOMESH || mode == PT_MODE_KD_MESH;
+    const bool tex = a.r.scene.mat_maps != nullptr;
+    bool park = c->spawns;  // as the radiance pass and a render
+    if (const char* e = getenv("PORTRAYER_PARK")) park = park && atoi(e) > 0;
+    a.r.park_slots = park ? 1 : 0;
+    const size_t frame_bytes = (size_t)(PT_LDS_FRAME_F64 + a.r.park_slots * PT_PARK_F64) * PT_BLOCK * 8;
+    a.r.stack_lds_cap = pt_stack_lds_cap(a.r.scene, 52 * 1024, frame_bytes, kd_sem);  // 3 x 52 KB of the CU's 160 KB (pt_film_waves)
+    a.r.grid_share = 1;
+    const uint32_t tiles = a.r.n_slots / 64u;
+    // the buffers are sized for the add's largest launch (its first: min(samples, lw) samples per pixel); the later ones use a prefix of the same lanes
+    auto set_launch = [&](uint32_t m) {
+        a.launch_samples = m;
+        for (a.k_log2 = 0; (1u << a.k_log2) < m; a.k_log2++) { }
+        a.r.n_items = tiles << a.k_log2;  // (tiles < 2^25, K <= 64)
+    };
+    set_launch(std::min(p->samples, lw));
+    uint32_t grid = 0;
+    PT_HIP(c, pt_film_dispatch(a, tex, park, c->n_cu, stream, &grid, false));
+    a.r.n_lanes = grid * PT_BLOCK;
+    const size_t stack_column = pt_stack_column(a.r.scene, a.r.stack_lds_cap);
+    const size_t spill_bytes = c->needs_spill ? (size_t)a.r.n_lanes * PT_SPILL_DEPTHS * PT_SPILL_STRIDE * sizeof(double) : 16;
+    int rc;
+    const size_t misc_bytes = 256 + PT_FINE_QUEUES * PT_QUEUE_STRIDE * 4;  // the overflow flag (word 1, where a render has it), the work queues
+    if ((rc = pt_reserve(c, v.stack_spill, (size_t)a.r.n_lanes * stack_column * 4)) || (rc = pt_reserve(c, v.spill, spill_bytes)) || (rc = pt_reserve(c, v.misc, misc_bytes)) ||
+        (rc = pt_reserve(c, f->staging, (size_t)a.r.n_slots * lw * 24)))
+        return rc;
+    a.staging = (double*)f->staging.p;
+    a.r.stack_spill = (uint32_t*)v.stack_spill.p;
+    a.r.spill = (double*)v.spill.p;
+    a.r.overflow_flag = (unsigned int*)v.misc.p + 1;
+    a.r.work_queues = (unsigned int*)((char*)v.misc.p + 256);
+    a.r.fine_queues = 16;
+    v.stream = stream; v.queued = true; v.closed = false;  // from here on something of the pass may be in flight on `stream`, whatever fails below
+    PT_HIP(c, hipMemsetAsync(v.misc.p, 0, misc_bytes, stream));
+    PT_HIP(c, hipEventRecord(v.ev0, stream));
+    for (uint32_t left = p->samples, first = 1; left > 0; first = 0) {
+        const uint32_t m = std::min(left, lw);
+        set_launch(m);
+        if (!first) PT_HIP(c, hipMemsetAsync((char*)v.misc.p + 256, 0, misc_bytes - 256, stream));  // the queues again; the overflow flag stays
+        uint32_t g = 0;
+        PT_HIP(c, pt_film_dispatch(a, tex, park, c->n_cu, stream, &g, true));  // (g <= grid: no more items than the launch the buffers were sized for)
+        PT_HIP(c, pt_film_fold_launch(a, (double*)f->total.p, (double*)f->partial.p, (uint32_t*)f->count.p, stream));
+        left -= m;
+    }
+    PT_HIP(c, hipEventRecord(v.ev1, stream));
+    PT_HIP(c, hipMemcpyAsync(v.host, v.misc.p, 8, hipMemcpyDeviceToHost, stream));
+    PT_HIP(c, hipEventRecord(v.copy_done, stream));
+    v.closed = true;
+    for (uint32_t y = p->slice.y0; y <= p->slice.y1; y++) {  // the host's copy of the counts
+        uint32_t* row = f->counts.data() + (size_t)y * f->width;
+        for (uint32_t x = p->slice.x0; x <= p->slice.x1; x++) row[x] += p->samples;
+    }
+    return PT_OK;
+}
+
+extern "C" int pt_film_add(pt_context* c, pt_film* f, const pt_camera* cam, const double* background, const pt_film_params* p, double* kernel_ms) {
+    int rc = pt_film_add_check(c, f, cam, background, p);
+    if (rc) return rc;
+    if (kernel_ms) *kernel_ms = 0.0;
+    if (pt_film_slice_empty(p)) return PT_OK;
+    PT_HIP(c, hipSetDevice(c->device));
+    const size_t bg_bytes = (p->background_rows ? (size_t)f->height : (size_t)f->height * f->width) * 24;
+    if ((rc = pt_reserve(c, f->bg, bg_bytes))) return rc;
+    PT_HIP(c, hipMemcpy(f->bg.p, background, bg_bytes, hipMemcpyHostToDevice));
+    rc = pt_film_add_common(c, f, cam, (const double*)f->bg.p, p, nullptr);
+    const int rc_wait = pt_radiance_wait(c);
+    if (rc || (rc = rc_wait)) return rc;
+    return pt_radiance_close(c, kernel_ms);
+}
+
+extern "C" int pt_film_add_device(pt_context* c, pt_film* f, const pt_camera* cam, const double* d_background, const pt_film_params* p, void* hip_stream) {
+    int rc = pt_film_add_check(c, f, cam, d_background, p);
+    if (rc) return rc;
+    if (pt_film_slice_empty(p)) return PT_OK;  // nothing queued, nothing to finish
+    PT_HIP(c, hipSetDevice(c->device));
+    if ((rc = pt_film_add_common(c, f, cam, d_background, p, (hipStream_t)hip_stream))) {
+        pt_radiance_wait(c);  // what was queued before the failure must not outlive the call
+        return rc;
+    }
+    c->radiance.pending = true;
+    c->film_open = f;
+    return PT_OK;
+}
+
+extern "C" int pt_film_resolve_device(pt_context* c, pt_film* f, void* d_rgb, double* d_linear, void* hip_stream) {
+    if (!c || !f || (!d_rgb && !d_linear)) return pt_fail(c, PT_ERR_ARGUMENT, "pt_film_resolve_device: NULL context or film, or neither rgb nor linear");
+    int rc = pt_film_handle(c, f, false, "pt_film_resolve_device");
+    if (rc) return rc;
+    PT_HIP(c, hipSetDevice(c->device));
+    PT_HIP(c, pt_film_resolve_launch(f->width, f->height, (const double*)f->total.p, (const double*)f->partial.p, (const uint32_t*)f->count.p, (uint8_t*)d_rgb, d_linear, (hipStream_t)hip_stream));
+    return PT_OK;
+}
+
+extern "C" int pt_film_resolve(pt_context* c, pt_film* f, uint8_t* rgb, double* linear) {
+    if (!c || !f || (!rgb && !linear)) return pt_fail(c, PT_ERR_ARGUMENT, "pt_film_resolve: NULL context or film, or neither rgb nor linear");
+    int rc = pt_film_handle(c, f, true, "pt_film_resolve");
+    if (rc) return rc;
+    PT_HIP(c, hipSetDevice(c->device));
+    const size_t n = f->counts.size();
+    // pixels without samples keep the caller's bytes: where there are any, the caller's buffers go to the device first
+    const bool holes = std::find(f->counts.begin(), f->counts.end(), 0u) != f->counts.end();
+    if (rgb) {
+        if ((rc = pt_reserve(c, f->out_rgb, n * 3))) return rc;
+        if (holes) PT_HIP(c, hipMemcpy(f->out_rgb.p, rgb, n * 3, hipMemcpyHostToDevice));
+    }
+    if (linear) {
+        if ((rc = pt_reserve(c, f->out_linear, n * 24))) return rc;
+        if (holes) PT_HIP(c, hipMemcpy(f->out_linear.p, linear, n * 24, hipMemcpyHostToDevice));
+    }
+    PT_HIP(c, pt_film_resolve_launch(f->width, f->height, (const double*)f->total.p, (const double*)f->partial.p, (const uint32_t*)f->count.p, rgb ? (uint8_t*)f->out_rgb.p : nullptr,
+                                     linear ? (double*)f->out_linear.p : nullptr, nullptr));
+    if (rgb) PT_HIP(c, hipMemcpy(rgb, f->out_rgb.p, n * 3, hipMemcpyDeviceToHost));
+    if (linear) PT_HIP(c, hipMemcpy(linear, f->out_linear.p, n * 24, hipMemcpyDeviceToHost));
+    return PT_OK;
+}
+
+extern "C" int pt_film_counts(pt_context* c, pt_film* f, uint32_t* counts) {
+    if (!c || !f || !counts) return pt_fail(c, PT_ERR_ARGUMENT, "pt_film_counts: NULL context, film or counts");
+    int rc = pt_film_handle(c, f, true, "pt_film_counts");
+    if (rc) return rc;
+    PT_HIP(c, hipSetDevice(c->device));
+    PT_HIP(c, hipMemcpy(counts, f->count.p, f->counts.size() * 4, hipMemcpyDeviceToHost));  // the DEVICE's counts: what the kernels see
+    return PT_OK;
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -19,7 +19,7 @@ _dp, _ip, _up, _u64p, _u8p = H._dp, H._ip, H._up, H._u64p, H._u8p
 
 EXPORTS = ["ph_last_error", "ph_scene_create", "ph_example_scene", "ph_scene_destroy", "ph_scene_counts", "ph_scene_export", "ph_scene_export_textures",
            "ph_scene_flatten", "ph_scene_kdtree", "ph_camera", "ph_obj_load", "ph_renderer_create", "ph_renderer_destroy",
-           "ph_renderer_context", "ph_renderer_ranks", "ph_renderer_node", "ph_renderer_prepare_ms", "ph_renderer_render", "ph_renderer_aov", "ph_renderer_rays", "ph_renderer_segments", "ph_renderer_radiance", "ph_renderer_update", "ph_scene_same_structure", "ph_renderer_deform", "ph_scene_same_topology", "ph_renderer_deform_device", "ph_renderer_mesh_count", "ph_renderer_mesh_vertices", "ph_example_render_to_png", "ph_png_read", "ph_png_write", "ph_image_read", "ph_scene_graph"]
+           "ph_renderer_context", "ph_renderer_ranks", "ph_renderer_node", "ph_renderer_prepare_ms", "ph_renderer_render", "ph_renderer_aov", "ph_renderer_rays", "ph_renderer_segments", "ph_renderer_radiance", "ph_renderer_film_create", "ph_renderer_film_destroy", "ph_renderer_film_reset", "ph_renderer_film_add", "ph_renderer_film_resolve", "ph_renderer_film_counts", "ph_renderer_update", "ph_scene_same_structure", "ph_renderer_deform", "ph_scene_same_topology", "ph_renderer_deform_device", "ph_renderer_mesh_count", "ph_renderer_mesh_vertices", "ph_example_render_to_png", "ph_png_read", "ph_png_write", "ph_image_read", "ph_scene_graph"]
 
 
 class PortrayerHostError(RuntimeError):
@@ -89,6 +89,12 @@ def lib() -> C.CDLL:
         l.ph_renderer_segments.argtypes = [vp, C.POINTER(H.PtRaysParams), _dp, _dp, _dp, C.POINTER(H.PtRaysBuffers), _dp]
         l.ph_renderer_radiance.restype = C.c_int
         l.ph_renderer_radiance.argtypes = [vp, C.POINTER(H.PtRadianceParams), _dp, _dp, _dp, _dp, _dp]
+        l.ph_renderer_film_create.restype = C.c_int; l.ph_renderer_film_create.argtypes = [vp, C.c_uint32, C.c_uint32, C.POINTER(vp)]
+        l.ph_renderer_film_destroy.restype = C.c_int; l.ph_renderer_film_destroy.argtypes = [vp, vp]
+        l.ph_renderer_film_reset.restype = C.c_int; l.ph_renderer_film_reset.argtypes = [vp, vp]
+        l.ph_renderer_film_add.restype = C.c_int; l.ph_renderer_film_add.argtypes = [vp, vp, _dp, _dp, C.POINTER(H.PtFilmParams), _dp]
+        l.ph_renderer_film_resolve.restype = C.c_int; l.ph_renderer_film_resolve.argtypes = [vp, vp, _u8p, _dp]
+        l.ph_renderer_film_counts.restype = C.c_int; l.ph_renderer_film_counts.argtypes = [vp, vp, _up]
         l.ph_renderer_update.restype = C.c_int; l.ph_renderer_update.argtypes = [vp, vp]
         l.ph_scene_same_structure.restype = C.c_int; l.ph_scene_same_structure.argtypes = [vp, vp, C.c_char_p, C.c_size_t]
         l.ph_renderer_deform.restype = C.c_int; l.ph_renderer_deform.argtypes = [vp, vp, C.c_int]
@@ -302,6 +308,74 @@ def _device_tensor_pointer(t, shape, device: int, what: str) -> int:
     return int(t.data_ptr())
 
 
+class Film:
+    """A width x height accumulator in the renderer's device memory (pt_film_*): add() gives pixels their next samples, resolve() gives at every pixel the
+    bits of Renderer.render(samples = that pixel's count) - provided every add used the same camera, background, seed and sample mode and the scene did not
+    change in between. Made by Renderer.film(); close it before its renderer."""
+
+    def __init__(self, renderer: "Renderer", width: int, height: int):
+        for name, v in (("width", width), ("height", height)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 < int(v) < 1 << 32:
+                raise ValueError("%s must be a positive integer, got %r" % (name, v))
+        self._h = C.c_void_p()
+        self._r = renderer
+        self.width, self.height = int(width), int(height)
+        _check(lib().ph_renderer_film_create(renderer._h, self.width, self.height, C.byref(self._h)), "ph_renderer_film_create")
+
+    def close(self):
+        if self._h and self._r._h:
+            lib().ph_renderer_film_destroy(self._r._h, self._h)
+        self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def add(self, cam10, background, samples: int = 1, seed: int = 0, sample_mode: int = H.SAMPLE_CENTRE, rect=None) -> float:
+        """`samples` more samples for every pixel of `rect` (x0, y0, x1, y1 inclusive; default: the whole film), each taken as render() takes that sample of
+        that pixel. `background` is (H, 3) or (H, W, 3) as for render(). Returns the device time in ms."""
+        bg = np.ascontiguousarray(background, dtype=np.float64)
+        rows = 1 if bg.shape == (self.height, 3) else 0
+        if not rows and bg.shape != (self.height, self.width, 3):
+            raise ValueError("background must be (H, 3) or (H, W, 3)")
+        if isinstance(samples, bool) or not isinstance(samples, (int, np.integer)) or not 0 < int(samples) <= 1 << 31:
+            raise ValueError("samples must be an integer in [1, 2^31], got %r" % (samples,))
+        if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 1 << 64:
+            raise ValueError("seed must be an integer in [0, 2^64), got %r" % (seed,))
+        x0, y0, x1, y1 = rect if rect is not None else (0, 0, self.width - 1, self.height - 1)
+        p = H.PtFilmParams(H.PtRect(x0, y0, x1, y1), int(samples), int(seed), sample_mode, rows)
+        c = np.ascontiguousarray(cam10, dtype=np.float64)
+        ms = C.c_double(0.0)
+        _check(lib().ph_renderer_film_add(self._r._h, self._h, _p(c, _dp), _p(bg, _dp), C.byref(p), C.byref(ms)), "ph_renderer_film_add")
+        return ms.value
+
+    def resolve(self, want_linear: bool = True, into: Optional[np.ndarray] = None, linear_into: Optional[np.ndarray] = None):
+        """(rgb, linear): (H, W, 3) uint8 and (H, W, 3) float64 (None without want_linear). Pixels that have no sample yet keep what `into` / `linear_into`
+        hold (zeros when the arrays are made here)."""
+        rgb = into if into is not None else np.zeros((self.height, self.width, 3), dtype=np.uint8)
+        if not isinstance(rgb, np.ndarray) or rgb.shape != (self.height, self.width, 3) or rgb.dtype != np.uint8 or not rgb.flags.c_contiguous:
+            raise ValueError("into must be a C-contiguous uint8 array of shape %r" % ((self.height, self.width, 3),))
+        linear = None
+        if want_linear or linear_into is not None:
+            linear = linear_into if linear_into is not None else np.zeros((self.height, self.width, 3), dtype=np.float64)
+            if not isinstance(linear, np.ndarray) or linear.shape != (self.height, self.width, 3) or linear.dtype != np.float64 or not linear.flags.c_contiguous:
+                raise ValueError("linear_into must be a C-contiguous float64 array of shape %r" % ((self.height, self.width, 3),))
+        _check(lib().ph_renderer_film_resolve(self._r._h, self._h, _p(rgb, _u8p), _p(linear, _dp)), "ph_renderer_film_resolve")
+        return rgb, linear
+
+    def counts(self) -> np.ndarray:
+        """(H, W) uint32: samples every pixel holds."""
+        out = np.zeros((self.height, self.width), dtype=np.uint32)
+        _check(lib().ph_renderer_film_counts(self._r._h, self._h, _p(out, _up)), "ph_renderer_film_counts")
+        return out
+
+    def reset(self):
+        """Every count back to zero: the next add starts at sample 0."""
+        _check(lib().ph_renderer_film_reset(self._r._h, self._h), "ph_renderer_film_reset")
+
+
 class Renderer:
     """A flattened scene resident on one MI355X (what render.rs:121-126 prepares, kept across renders)."""
 
@@ -354,6 +428,10 @@ class Renderer:
         c = np.ascontiguousarray(cam10, dtype=np.float64)
         _check(lib().ph_renderer_render(self._h, _p(c, _dp), C.byref(p), _p(bg, _dp), _p(rgb, _u8p), _p(linear, _dp), C.byref(st)), "ph_renderer_render")
         return rgb, linear, st.as_dict()
+
+    def film(self, width: int, height: int) -> Film:
+        """A film of this renderer (pt_film_create): samples accumulate on the device, add after add; see Film."""
+        return Film(self, width, height)
 
     def update(self, scene: Scene):
         """The resident scene moved (pt_scene_update): `scene` must be the renderer's scene with other transforms, lights' values or ambient light

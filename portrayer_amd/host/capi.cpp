@@ -631,6 +631,64 @@ extern "C" int ph_renderer_radiance(ph_renderer* r, const pt_radiance_params* p,
     });
 }
 
+// A film of the renderer's context (pt_film_*). The handle remembers the film's size: the camera of an add is the one a render of that size gets.
+struct ph_film {
+    pt_film* f = nullptr;
+    uint32_t width = 0, height = 0;
+};
+static int film_rc(ph_renderer* r, int rc) {
+    if (rc == PT_OK) return PH_OK;
+    g_error = pt_last_error(r->r->context());
+    return rc == PT_ERR_SLICE ? PH_ERR_PANIC : PH_ERR_RUNTIME;
+}
+
+extern "C" int ph_renderer_film_create(ph_renderer* r, uint32_t width, uint32_t height, ph_film** out) {
+    if (!r || !out) return bad("null argument");
+    *out = nullptr;
+    if (width == 0 || height == 0) return bad("a film's width and height must be positive");
+    if (r->r->node()) return bad("a film lives on one device: this renderer is spread over several ranks (PORTRAYER_GPUS); create it with one");
+    return guarded([&]() -> int {
+        auto f = std::make_unique<ph_film>();
+        f->width = width; f->height = height;
+        int rc = film_rc(r, pt_film_create(r->r->context(), width, height, &f->f));
+        if (rc != PH_OK) return rc;
+        *out = f.release();
+        return PH_OK;
+    });
+}
+
+extern "C" int ph_renderer_film_destroy(ph_renderer* r, ph_film* film) {
+    if (!r || !film) return bad("null argument");
+    return guarded([&]() -> int {
+        int rc = film_rc(r, pt_film_destroy(r->r->context(), film->f));
+        if (rc == PH_OK) delete film;
+        return rc;
+    });
+}
+
+extern "C" int ph_renderer_film_reset(ph_renderer* r, ph_film* film) {
+    if (!r || !film) return bad("null argument");
+    return guarded([&]() -> int { return film_rc(r, pt_film_reset(r->r->context(), film->f)); });
+}
+
+extern "C" int ph_renderer_film_add(ph_renderer* r, ph_film* film, const double camera[10], const double* background, const pt_film_params* p, double* kernel_ms) {
+    if (!r || !film || !camera || !background || !p) return bad("null argument");
+    return guarded([&]() -> int {
+        pt_camera pc = detail::Camera(camera_from(camera), (double)film->width, (double)film->height).to_abi();  // the camera a render of this size gets
+        return film_rc(r, pt_film_add(r->r->context(), film->f, &pc, background, p, kernel_ms));
+    });
+}
+
+extern "C" int ph_renderer_film_resolve(ph_renderer* r, ph_film* film, uint8_t* rgb, double* linear) {
+    if (!r || !film || (!rgb && !linear)) return bad("null argument");
+    return guarded([&]() -> int { return film_rc(r, pt_film_resolve(r->r->context(), film->f, rgb, linear)); });
+}
+
+extern "C" int ph_renderer_film_counts(ph_renderer* r, ph_film* film, uint32_t* counts) {
+    if (!r || !film || !counts) return bad("null argument");
+    return guarded([&]() -> int { return film_rc(r, pt_film_counts(r->r->context(), film->f, counts)); });
+}
+
 extern "C" int ph_example_render_to_png(const char* name, const char* assets_dir, int n, uint32_t width, uint32_t height, const char* png_path) {
     if (!name || !png_path) return bad("null argument");
     return guarded([&]() -> int {

@@ -6,6 +6,7 @@ use std::os::raw::{c_char, c_int, c_void};
 
 #[repr(C)] pub struct PtContext { _private: [u8; 0] }
 #[repr(C)] pub struct PtNode { _private: [u8; 0] }
+#[repr(C)] pub struct PtFilm { _private: [u8; 0] }
 
 pub const PT_ABI_VERSION: c_int = 8;
 
@@ -107,6 +108,10 @@ pub struct PtRadianceParams {              // pt_radiance_params: ray i draws fr
     pub n: u64, pub reorder: i32, pub background_per_ray: i32, pub seed: u64, pub stream_base: u64, pub sample: u32,
 }
 #[repr(C)]
+pub struct PtFilmParams {                  // pt_film_params: one add to a film - `samples` more samples for every pixel of `slice`, taken as pt_render takes them
+    pub slice: PtRect, pub samples: u32, pub seed: u64, pub sample_mode: i32, pub background_rows: i32,
+}
+#[repr(C)]
 pub struct PtRaysBuffers {                 // pt_rays_buffers: each optional (null = not wanted), n entries, indexed like the rays
     pub t: *mut f64, pub position: *mut f64, pub normal: *mut f64, pub node: *mut i32, pub sub: *mut i32, pub material: *mut i32, pub occluded: *mut u8,
 }
@@ -160,6 +165,17 @@ extern "C" {
     pub fn pt_radiance_device(ctx: *mut PtContext, params: *const PtRadianceParams, d_origins: *const f64, d_directions: *const f64, d_background: *const f64,
                               d_rgb: *mut f64, hip_stream: *mut c_void) -> c_int;
     pub fn pt_radiance_finish(ctx: *mut PtContext, kernel_ms: *mut f64) -> c_int;
+    // a film: samples accumulate in device memory, add after add; pt_film_add_device is closed by pt_radiance_finish
+    pub fn pt_film_create(ctx: *mut PtContext, width: u32, height: u32, out: *mut *mut PtFilm) -> c_int;
+    pub fn pt_film_destroy(ctx: *mut PtContext, film: *mut PtFilm) -> c_int;
+    pub fn pt_film_reset(ctx: *mut PtContext, film: *mut PtFilm) -> c_int;
+    pub fn pt_film_add(ctx: *mut PtContext, film: *mut PtFilm, camera: *const PtCamera, background: *const f64, params: *const PtFilmParams,
+                       kernel_ms: *mut f64) -> c_int;
+    pub fn pt_film_add_device(ctx: *mut PtContext, film: *mut PtFilm, camera: *const PtCamera, d_background: *const f64, params: *const PtFilmParams,
+                              hip_stream: *mut c_void) -> c_int;
+    pub fn pt_film_resolve(ctx: *mut PtContext, film: *mut PtFilm, rgb: *mut u8, linear: *mut f64) -> c_int;
+    pub fn pt_film_resolve_device(ctx: *mut PtContext, film: *mut PtFilm, d_rgb: *mut c_void, d_linear: *mut f64, hip_stream: *mut c_void) -> c_int;
+    pub fn pt_film_counts(ctx: *mut PtContext, film: *mut PtFilm, counts: *mut u32) -> c_int;
     pub fn pt_context_stream(ctx: *mut PtContext, slot: c_int) -> *mut c_void;
     pub fn pt_context_next_slot(ctx: *const PtContext) -> c_int;
     // one render call over the GPUs of a node (one context per GPU, one RCCL gather)

@@ -4,8 +4,8 @@
     python3 tools/compare_render_objects.py <dir of the other build's objects> [<dir of this build's objects>]
 
 Extracts the gfx950 code object from pt_render_m1.o .. pt_render_m9.o of both directories (llvm-objdump --offloading, as
-tests/test_kernel_resources.py does) and compares them byte for byte; likewise the primary-visibility pass's (pt_aov_m*.o) and the ray-query pass's
-(pt_rays_m*.o), where the other build has them. A change that claims to leave the render path alone
+tests/test_kernel_resources.py does) and compares them byte for byte; likewise the primary-visibility pass's (pt_aov_m*.o), the ray-query passes'
+(pt_rays_m*.o, pt_segments_m*.o) and the radiance pass's (pt_radiance_m*.o), where the other build has them. A change that claims to leave the render path alone
 (a new pass beside it, host code) runs this against a build of its parent commit: identical code objects mean identical
 behaviour and speed of every render kernel, without a GPU. Exit status 0: all identical; 1: some differ (named)."""
 import filecmp
@@ -37,7 +37,7 @@ def main(argv):
     mine = argv[2] if len(argv) > 2 else os.path.join(ROOT, "portrayer_amd", "csrc")
     differ, compared = [], 0
     with tempfile.TemporaryDirectory() as tmp:
-        for prefix in ("pt_render", "pt_aov", "pt_rays"):
+        for prefix in ("pt_render", "pt_aov", "pt_rays", "pt_segments", "pt_radiance"):
             for m in range(1, 10):
                 name = "%s_m%d.o" % (prefix, m)
                 if prefix != "pt_render" and not os.path.exists(os.path.join(other, name)):
@@ -48,7 +48,7 @@ def main(argv):
                 compared += 1
                 if not same:
                     differ.append(name)
-    print("render, aov and rays code objects: %s" % ("all %d byte-identical" % compared if not differ else "differ: " + ", ".join(differ)))
+    print("render, aov, rays, segments and radiance code objects: %s" % ("all %d byte-identical" % compared if not differ else "differ: " + ", ".join(differ)))
     return 1 if differ else 0
 
 
