@@ -35,7 +35,8 @@ HIP_OBJS := $(OBJDIR)/pt_api.o $(OBJDIR)/pt_build.o $(OBJDIR)/pt_node.o $(foreac
             $(OBJDIR)/pt_rays_sort.o $(foreach m,$(RENDER_MODES),$(OBJDIR)/pt_rays_m$(m).o) \
             $(foreach m,$(RENDER_MODES),$(OBJDIR)/pt_radiance_m$(m).o) \
             $(foreach m,$(RENDER_MODES),$(OBJDIR)/pt_segments_m$(m).o) \
-            $(OBJDIR)/pt_film.o $(foreach m,$(RENDER_MODES),$(OBJDIR)/pt_film_m$(m).o)
+            $(OBJDIR)/pt_film.o $(foreach m,$(RENDER_MODES),$(OBJDIR)/pt_film_m$(m).o) \
+            $(OBJDIR)/pt_film_map.o $(foreach m,$(RENDER_MODES),$(OBJDIR)/pt_film_map_m$(m).o)
 
 # Every HIP translation unit is built in four steps instead of one `hipcc -c`, so that the device code can be CHECKED and REPAIRED between
 # the compiler and the assembler (tools/check_exec_prologue.py; profiles/r05/notes.md section 1: the AMDGPU backend of this toolchain can put
@@ -84,6 +85,15 @@ $(OBJDIR)/pt_radiance_m%.o: $(CSRC)/pt_radiance_inst.hip $(HIP_HDRS) tools/check
 # kernels (pt_film.hip) are built by the %.o rule
 $(OBJDIR)/pt_film_m%.o: $(CSRC)/pt_film_inst.hip $(HIP_HDRS) tools/check_exec_prologue.py
 	$(call hip_four_steps,-DPT_INST_MODE=$*)
+
+# the film's per-pixel budget (pt_film_map.h): the sampling kernel over a list of samples, <TEX, PARK> instantiations per mode; its plan, fold, error and
+# budget kernels are pt_film_map.hip. Both as static rules: the names also match the pattern pt_film_m%.o above, which must not build them.
+$(foreach m,$(RENDER_MODES),$(OBJDIR)/pt_film_map_m$(m).o): $(OBJDIR)/pt_film_map_m%.o: $(CSRC)/pt_film_map_inst.hip $(HIP_HDRS) tools/check_exec_prologue.py
+	$(call hip_four_steps,-DPT_INST_MODE=$*)
+$(OBJDIR)/pt_film_map.o: $(CSRC)/pt_film_map.hip $(HIP_HDRS) tools/check_exec_prologue.py
+	$(call hip_four_steps,)
+# (... and nothing makes the sources: make's built-in "a program from its object" would look for pt_film_map.hip.o, which pt_film_m%.o matches too)
+$(CSRC)/pt_film_map.hip $(CSRC)/pt_film_map_inst.hip $(CSRC)/pt_film_map.h $(CSRC)/pt_film_map_inst.h: ;
 
 $(HIPLIB): $(HIP_OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared $^ -o $@ -ldl

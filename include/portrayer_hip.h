@@ -483,7 +483,49 @@ int pt_film_add_device(pt_context *ctx, pt_film *film, const pt_camera *camera, 
 int pt_film_resolve(pt_context *ctx, pt_film *film, uint8_t *rgb, double *linear);
 /* Device buffers, queued on `hip_stream` (behind a pt_film_add_device on the same stream it sees that pass's samples). */
 int pt_film_resolve_device(pt_context *ctx, pt_film *film, void *d_rgb, double *d_linear, void *hip_stream);
-int pt_film_counts(pt_context *ctx, pt_film *film, uint32_t *counts);   /* host, width x height */
+int pt_film_counts(pt_context *ctx, pt_film *film, uint32_t *counts);   /* host, width x height: the DEVICE's counts; the host's copy is set to them */
+
+/* ---- Film, adaptive: a sample budget per pixel, a noise estimate, and the budget a refine pass gives.
+ *   pt_film_add_map gives pixel p of `slice` its next m[p] = min(budget[p], max_samples) samples, each taken and folded exactly as pt_film_add does it: the
+ *     PROMISE above is unchanged after any mix of pt_film_add and pt_film_add_map. `budget` is width x height u32, row-major like pt_film_counts; only the
+ *     slice is read. The samples of a launch are laid out one per lane, whatever their pixels want: no lane idles beside a pixel that wanted more.
+ *     max_samples is 1 .. PT_FILM_MAP_MAX; the number of launches follows from it (a device map is not known to the host). A map of zeros is PT_OK and changes
+ *     nothing. Bookkeeping and refusals are pt_film_add(_device)'s: one radiance / film pass in flight, closed by pt_radiance_finish; a pixel's count may not
+ *     pass 2^31 - for a host map by its own m[p], for a device map by max_samples, by which the HOST's copy of the counts is then raised over the slice: an
+ *     upper bound, which pt_film_counts brings back to the device's values. Also refused (PT_ERR_ARGUMENT): a slice of 2^29 pixel slots (8x8 tiles x 64) or more.
+ *   pt_film_create_moments makes a film that keeps one more f64 per pixel (60 bytes instead of 52): q, the running sum of y * y, y = (v.x + v.y) + v.z of
+ *     every sample v, in plain ascending order (the first sample is assigned: pt_film_reset clears nothing more). Every add to such a film keeps it.
+ *   pt_film_error writes width x height f64, the standard error of the mean of y in linear units, in exactly this order of IEEE operations:
+ *     n = count[p]; n < 2: +inf; S = the pixel's sum as resolve divides it; mean = S / n; my = (mean.x + mean.y) + mean.z;
+ *     var = (q - (n * my) * my) / (n - 1), a var that is not > 0 becomes 0; err = sqrt(var / n). PT_ERR_ARGUMENT on a film without moments.
+ *   pt_film_budget_device writes width x height u32: 0 outside `slice`; inside, with c = count[p] and e = the error above:
+ *     c < min_count: min(min_count - c, step); else c < max_count and e > threshold: min(step, max_count - c); else 0.
+ *     d_summary (2 x u64, zeroed by the call on the stream): the pixels with a budget, and the sum of the budgets. Needs a film with moments; step is
+ *     1 .. PT_FILM_MAP_MAX, min_count <= max_count <= 2^31. Queued on `hip_stream`; refused while a pass of the film is open. */
+#define PT_FILM_MAP_MAX 4096u
+typedef struct {
+    pt_rect slice;              /* pixels that may get samples                                                    */
+    uint32_t max_samples;       /* no pixel gets more in this call, 1 .. PT_FILM_MAP_MAX                          */
+    uint64_t seed;              /* as pt_render_params.seed                                                       */
+    int32_t sample_mode;        /* PT_SAMPLE_*                                                                    */
+    int32_t background_rows;    /* as pt_film_params.background_rows                                              */
+} pt_film_map_params;
+typedef struct {
+    pt_rect slice;              /* pixels that may get a budget                                                   */
+    double threshold;           /* refine where the error is above it                                             */
+    uint32_t min_count;         /* every pixel of the slice is brought to this count first                        */
+    uint32_t max_count;         /* ... and none beyond this one                                                   */
+    uint32_t step;              /* most samples one pass gives a pixel                                            */
+} pt_film_refine_params;
+int pt_film_create_moments(pt_context *ctx, uint32_t width, uint32_t height, pt_film **out);
+/* Host map and background, synchronous; the host's copy of the counts is updated exactly. kernel_ms as for pt_film_add. */
+int pt_film_add_map(pt_context *ctx, pt_film *film, const pt_camera *camera, const double *background, const pt_film_map_params *params, const uint32_t *budget, double *kernel_ms);
+/* Map and background in DEVICE memory, queued on `hip_stream`; closed by pt_radiance_finish like pt_film_add_device. The map is read by the kernels of the
+ * pass: it must stay unchanged until the pass is finished. */
+int pt_film_add_map_device(pt_context *ctx, pt_film *film, const pt_camera *camera, const double *d_background, const pt_film_map_params *params, const uint32_t *d_budget, void *hip_stream);
+int pt_film_error(pt_context *ctx, pt_film *film, double *err);   /* host, width x height; synchronous */
+int pt_film_error_device(pt_context *ctx, pt_film *film, double *d_err, void *hip_stream);
+int pt_film_budget_device(pt_context *ctx, pt_film *film, const pt_film_refine_params *params, uint32_t *d_budget, uint64_t *d_summary, void *hip_stream);
 
 /* Bytes of one rank's compact tile buffer for a slice split over tile_ranks ranks (equal for all ranks). */
 uint64_t pt_compact_bytes(const pt_render_params *params);
@@ -586,6 +628,17 @@ int pt_test_raypk(uint64_t n, int body, const double *origins, const double *dir
 /* Host-side run (no GPU, no context) of the film's running sum: `samples` (n x 3) given to one pixel in n_cuts consecutive adds of cuts[k] samples each
  * (their sum must be n), through the functions the film's fold and resolve kernels call. out_sum: what resolve divides by n. */
 int pt_test_film_fold_host(uint32_t n, const double *samples, const uint32_t *cuts, uint32_t n_cuts, double out_sum[3]);
+/* The same for a film with moments, through the functions pt_film_fold_map_kernel and pt_film_error_kernel call: out_q the pixel's second moment, out_err what
+ * pt_film_error writes for it. n = 0 (then samples, cuts may be NULL): the untouched pixel, out_err = +inf. */
+int pt_test_film_moments_host(uint32_t n, const double *samples, const uint32_t *cuts, uint32_t n_cuts, double out_sum[3], double *out_q, double *out_err);
+/* Host-side run (no GPU, no context) of the plan of launch round `round` of pt_film_add_map over `slice` of a width x height film: the list the sampling
+ * kernel walks, one entry per sample, (pixel slot << 3) | j in ascending (slot, j) order; pixel slots are the slice's 8x8 tiles, row-major, rows of a tile.
+ * *n_out: the list's length (also where it exceeds `cap`, the room in `list`). */
+int pt_test_film_plan_host(uint32_t width, uint32_t height, const pt_rect *slice, const uint32_t *budget, uint32_t max_samples, uint32_t round, uint32_t *list, uint32_t cap,
+                           uint32_t *n_out);
+/* The same list by the plan KERNELS of `ctx`'s device (host `budget` in, list copied back; nothing is sampled, no scene or film needed). */
+int pt_test_film_plan(pt_context *ctx, uint32_t width, uint32_t height, const pt_rect *slice, const uint32_t *budget, uint32_t max_samples, uint32_t round, uint32_t *list, uint32_t cap,
+                      uint32_t *n_out);
 
 #ifdef __cplusplus
 }

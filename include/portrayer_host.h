@@ -170,6 +170,17 @@ int ph_renderer_film_reset(ph_renderer *r, ph_film *film);
 int ph_renderer_film_add(ph_renderer *r, ph_film *film, const double camera[10], const double *background, const pt_film_params *params, double *kernel_ms);
 int ph_renderer_film_resolve(ph_renderer *r, ph_film *film, uint8_t *rgb, double *linear);   /* either may be NULL, not both */
 int ph_renderer_film_counts(ph_renderer *r, ph_film *film, uint32_t *counts);
+/* The adaptive film (pt_film_create_moments, pt_film_add_map, pt_film_error, pt_film_budget_device): a film that also keeps the second moment of its samples;
+ * an add with a budget per pixel (`budget`: width x height u32, only params->slice is read); the standard error of every pixel's mean (width x height f64,
+ * +inf below 2 samples); and the closed loop - budget on the device, add what it asks for, until no pixel of refine->slice is below min_count or above the
+ * threshold (and below max_count), or max_passes have run. `sampling` gives refine its seed, sample_mode and background_rows (its slice and max_samples are
+ * ignored: refine->slice, refine->step). out[3]: passes run, samples added, pixels that still wanted samples at the end. kernel_ms (optional): device time
+ * of the adds. */
+int ph_renderer_film_create_moments(ph_renderer *r, uint32_t width, uint32_t height, ph_film **out);
+int ph_renderer_film_add_map(ph_renderer *r, ph_film *film, const double camera[10], const double *background, const pt_film_map_params *params, const uint32_t *budget, double *kernel_ms);
+int ph_renderer_film_error(ph_renderer *r, ph_film *film, double *err);
+int ph_renderer_film_refine(ph_renderer *r, ph_film *film, const double camera[10], const double *background, const pt_film_map_params *sampling, const pt_film_refine_params *refine,
+                            uint32_t max_passes, uint64_t out[3], double *kernel_ms);
 
 /* Image::new + Image::render + Image::save with the crate's defaults (env SAMPLES, KD_DEPTH) on an
  * example scene: exercises the whole C++ API the way the reference's main() does. */

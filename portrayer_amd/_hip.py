@@ -128,6 +128,19 @@ class PtFilmParams(C.Structure):
     _fields_ = [("slice", PtRect), ("samples", C.c_uint32), ("seed", C.c_uint64), ("sample_mode", C.c_int32), ("background_rows", C.c_int32)]
 
 
+FILM_MAP_MAX = 4096  # PT_FILM_MAP_MAX
+
+
+class PtFilmMapParams(C.Structure):
+    """pt_film_map_params: one add with a budget per pixel - the slice, the most any pixel gets, and the render's seed, sample mode and background shape."""
+    _fields_ = [("slice", PtRect), ("max_samples", C.c_uint32), ("seed", C.c_uint64), ("sample_mode", C.c_int32), ("background_rows", C.c_int32)]
+
+
+class PtFilmRefineParams(C.Structure):
+    """pt_film_refine_params: what a refine pass gives a pixel - up to `step` samples while it is below min_count, or below max_count with an error above the threshold."""
+    _fields_ = [("slice", PtRect), ("threshold", C.c_double), ("min_count", C.c_uint32), ("max_count", C.c_uint32), ("step", C.c_uint32)]
+
+
 class PtStats(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("primary", "shadow", "reflect", "refract", "depth11_skipped", "hits", "n_inner", "n_leaf",
                                           "n_analytic", "n_tri", "n_bbox", "kd_plane_miss", "stack_overflow")] + \
@@ -151,7 +164,9 @@ EXPORTS = ["pt_abi_version", "pt_device_count", "pt_context_create", "pt_context
            "pt_radiance", "pt_radiance_device", "pt_radiance_finish", "pt_scene_update", "pt_node_scene_update", "pt_scene_deform", "pt_node_scene_deform", "pt_scene_mesh_rebuildable", "pt_test_scene_bytes", "pt_test_scene_info",
            "pt_vertex_bounds_device", "pt_scene_deform_device", "pt_test_vertex_box_shape", "pt_test_raypk",
            "pt_film_create", "pt_film_destroy", "pt_film_reset", "pt_film_add", "pt_film_add_device", "pt_film_resolve", "pt_film_resolve_device", "pt_film_counts",
-           "pt_test_film_fold_host"]
+           "pt_test_film_fold_host",
+           "pt_film_create_moments", "pt_film_add_map", "pt_film_add_map_device", "pt_film_error", "pt_film_error_device", "pt_film_budget_device",
+           "pt_test_film_moments_host", "pt_test_film_plan_host", "pt_test_film_plan"]
 
 
 def header_functions():
@@ -319,6 +334,25 @@ def lib() -> C.CDLL:
         l.pt_film_counts.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]
         l.pt_test_film_fold_host.restype = C.c_int
         l.pt_test_film_fold_host.argtypes = [C.c_uint32, _dp, C.POINTER(C.c_uint32), C.c_uint32, _dp]
+        _u32p = C.POINTER(C.c_uint32)
+        l.pt_film_create_moments.restype = C.c_int
+        l.pt_film_create_moments.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]
+        l.pt_film_add_map.restype = C.c_int
+        l.pt_film_add_map.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(PtCamera), _dp, C.POINTER(PtFilmMapParams), _u32p, _dp]
+        l.pt_film_add_map_device.restype = C.c_int
+        l.pt_film_add_map_device.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(PtCamera), C.c_void_p, C.POINTER(PtFilmMapParams), C.c_void_p, C.c_void_p]
+        l.pt_film_error.restype = C.c_int
+        l.pt_film_error.argtypes = [C.c_void_p, C.c_void_p, _dp]
+        l.pt_film_error_device.restype = C.c_int
+        l.pt_film_error_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        l.pt_film_budget_device.restype = C.c_int
+        l.pt_film_budget_device.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(PtFilmRefineParams), C.c_void_p, C.c_void_p, C.c_void_p]
+        l.pt_test_film_moments_host.restype = C.c_int
+        l.pt_test_film_moments_host.argtypes = [C.c_uint32, _dp, _u32p, C.c_uint32, _dp, _dp, _dp]
+        l.pt_test_film_plan_host.restype = C.c_int
+        l.pt_test_film_plan_host.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(PtRect), _u32p, C.c_uint32, C.c_uint32, _u32p, C.c_uint32, _u32p]
+        l.pt_test_film_plan.restype = C.c_int
+        l.pt_test_film_plan.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(PtRect), _u32p, C.c_uint32, C.c_uint32, _u32p, C.c_uint32, _u32p]
         _lib = l
     return _lib
 

@@ -20,6 +20,7 @@
 #include "pt_segments_inst.h"
 #include "pt_radiance_inst.h"
 #include "pt_film_inst.h"
+#include "pt_film_map_inst.h"
 #include "pt_render_inst.h"
 #include "pt_shade.h"
 
@@ -382,10 +383,14 @@ struct pt_film {
     pt_context* ctx = nullptr;
     uint32_t width = 0, height = 0;
     PtBuf total, partial, count, staging, bg, out_rgb, out_linear;
+    // pt_film_create_moments: the second moment per pixel. pt_film_add_map: the host map's device copy, the list of a launch round (its length in the
+    // word in front of it), the plan's block sums. pt_film_error: the host path's device buffer.
+    PtBuf q, budget, list, plan_work, out_err;
+    bool moments = false;
     std::vector<uint32_t> counts;
 };
 static void pt_film_free(pt_film* f) {
-    for (PtBuf* b : {&f->total, &f->partial, &f->count, &f->staging, &f->bg, &f->out_rgb, &f->out_linear}) if (b->p) hipFree(b->p);
+    for (PtBuf* b : {&f->total, &f->partial, &f->count, &f->staging, &f->bg, &f->out_rgb, &f->out_linear, &f->q, &f->budget, &f->list, &f->plan_work, &f->out_err}) if (b->p) hipFree(b->p);
     delete f;
 }
 
@@ -2735,7 +2740,7 @@ static int pt_film_handle(pt_context* c, pt_film* f, bool busy, const char* who)
     return PT_OK;
 }
 
-extern "C" int pt_film_create(pt_context* c, uint32_t width, uint32_t height, pt_film** out) {
+static int pt_film_create_common(pt_context* c, uint32_t width, uint32_t height, pt_film** out, bool moments) {
     if (out) *out = nullptr;
     if (!c || !out) return pt_fail(c, PT_ERR_ARGUMENT, "pt_film_create: NULL context or out");
     if (width == 0 || height == 0 || (uint64_t)width * height >= 0x80000000ull) return pt_fail(c, PT_ERR_ARGUMENT, "pt_film_create: width and height must be positive, below 2^31 pixels");
@@ -2744,8 +2749,12 @@ extern "C" int pt_film_create(pt_context* c, uint32_t width, uint32_t height, pt
     f->ctx = c; f->width = width; f->height = height;
     const size_t n = (size_t)width * height;
     int rc;
-    if ((rc = pt_reserve(c, f->total, n * 24)) || (rc = pt_reserve(c, f->partial, n * 24)) || (rc = pt_reserve(c, f->count, n * 4))) { pt_film_free(f); return rc; }
-    if (hipMemset(f->total.p, 0, n * 24) != hipSuccess || hipMemset(f->partial.p, 0, n * 24) != hipSuccess || hipMemset(f->count.p, 0, n * 4) != hipSuccess ||
+    f->moments = moments;
+    if ((rc = pt_reserve(c, f->total, n * 24)) || (rc = pt_reserve(c, f->partial, n * 24)) || (rc = pt_reserve(c, f->count, n * 4)) || (moments && (rc = pt_reserve(c, f->q, n * 8)))) {
+        pt_film_free(f);
+        return rc;
+    }
+    if ((moments && hipMemset(f->q.p, 0, n * 8) != hipSuccess) || hipMemset(f->total.p, 0, n * 24) != hipSuccess || hipMemset(f->partial.p, 0, n * 24) != hipSuccess || hipMemset(f->count.p, 0, n * 4) != hipSuccess ||
         hipDeviceSynchronize() != hipSuccess) {
         pt_film_free(f);
         return pt_fail(c, PT_ERR_DEVICE, "pt_film_create: clearing the film failed");
@@ -2755,6 +2764,8 @@ extern "C" int pt_film_create(pt_context* c, uint32_t width, uint32_t height, pt
     *out = f;
     return PT_OK;
 }
+extern "C" int pt_film_create(pt_context* c, uint32_t width, uint32_t height, pt_film** out) { return pt_film_create_common(c, width, height, out, false); }
+extern "C" int pt_film_create_moments(pt_context* c, uint32_t width, uint32_t height, pt_film** out) { return pt_film_create_common(c, width, height, out, true); }
 
 extern "C" int pt_film_destroy(pt_context* c, pt_film* f) {
     int rc = pt_film_handle(c, f, true, "pt_film_destroy");
@@ -2800,8 +2811,10 @@ static bool pt_film_slice_empty(const pt_film_params* p) { return p->slice.x1 < 
 
 // Queues the add on `stream` as a radiance pass (its work buffers, events and pinned page): queues + overflow flag zeroed; between the pass's two events, per
 // at most `lw` samples, the sampling kernel and its fold (the queues zeroed again in between); the flag copied to the pinned page behind them. d_background is
-// a DEVICE pointer. LDS per block as the radiance pass has it.
-static int pt_film_add_common(pt_context* c, pt_film* f, const pt_camera* cam, const double* d_background, const pt_film_params* p, hipStream_t stream) {
+// a DEVICE pointer. LDS per block as the radiance pass has it. In three steps, shared with pt_film_add_map: the argument block ...
+struct PtFilmPass { bool tex, park; size_t misc_bytes; };
+static int pt_film_pass_args(pt_context* c, pt_film* f, const pt_camera* cam, const double* d_background, const pt_rect& slice, uint64_t seed, int32_t sample_mode, int32_t background_rows, uint32_t lw,
+                             PtFilmArgs& a, PtFilmPass& ps) {
     pt_context::Radiance& v = c->radiance;
     if (!v.ev0) {
         PT_HIP(c, hipEventCreate(&v.ev0));
@@ -2811,25 +2824,66 @@ static int pt_film_add_common(pt_context* c, pt_film* f, const pt_camera* cam, c
     }
     pt_render_params rp;
     memset(&rp, 0, sizeof rp);
-    rp.width = f->width; rp.height = f->height; rp.slice = p->slice;
-    rp.samples = 1; rp.seed = p->seed; rp.sample_mode = p->sample_mode; rp.background_rows = p->background_rows; rp.tile_rank = 0; rp.tile_ranks = 1;
-    PtFilmArgs a;
+    rp.width = f->width; rp.height = f->height; rp.slice = slice;
+    rp.samples = 1; rp.seed = seed; rp.sample_mode = sample_mode; rp.background_rows = background_rows; rp.tile_rank = 0; rp.tile_ranks = 1;
     memset(&a, 0, sizeof a);  // (no occluder table, no counters, no work counter: null)
-    pt_fill_args(c, cam, &rp, &a.r);  // the camera, the slice and its pixel slots; the work items are the film's own (below)
+    pt_fill_args(c, cam, &rp, &a.r);  // the camera, the slice and its pixel slots; the work items are the film's own (the callers')
     a.r.background = d_background;
-    uint32_t lw = PT_FILM_LW;
-    if (const char* e = getenv("PORTRAYER_FILM_LW")) { const int w = atoi(e); if (w == 8 || w == 64) lw = (uint32_t)w; }  // measurements (profiles/film)
     a.lw = lw;
     a.count = (const uint32_t*)f->count.p;
     const int mode = a.r.scene.mode;
     const bool kd_sem = mode == PT_MODE_KD || mode == PT_MODE_KD_NOMESH || mode == PT_MODE_KD_MESH;
-    const bool tex = a.r.scene.mat_maps != nullptr;
-    bool park = c->spawns;  // as the radiance pass and a render
-    if (const char* e = getenv("PORTRAYER_PARK")) park = park && atoi(e) > 0;
-    a.r.park_slots = park ? 1 : 0;
+    ps.tex = a.r.scene.mat_maps != nullptr;
+    ps.park = c->spawns;  // as the radiance pass and a render
+    if (const char* e = getenv("PORTRAYER_PARK")) ps.park = ps.park && atoi(e) > 0;
+    a.r.park_slots = ps.park ? 1 : 0;
     const size_t frame_bytes = (size_t)(PT_LDS_FRAME_F64 + a.r.park_slots * PT_PARK_F64) * PT_BLOCK * 8;
     a.r.stack_lds_cap = pt_stack_lds_cap(a.r.scene, 52 * 1024, frame_bytes, kd_sem);  // 3 x 52 KB of the CU's 160 KB (pt_film_waves)
     a.r.grid_share = 1;
+    ps.misc_bytes = 256 + PT_FINE_QUEUES * PT_QUEUE_STRIDE * 4;  // the overflow flag (word 1, where a render has it), the work queues
+    return PT_OK;
+}
+// ... the buffers for the pass's largest launch (`grid` blocks), the queues and the flag zeroed and the first event on `stream` ...
+static int pt_film_pass_open(pt_context* c, pt_film* f, PtFilmArgs& a, const PtFilmPass& ps, uint32_t grid, hipStream_t stream) {
+    pt_context::Radiance& v = c->radiance;
+    a.r.n_lanes = grid * PT_BLOCK;
+    const size_t stack_column = pt_stack_column(a.r.scene, a.r.stack_lds_cap);
+    const size_t spill_bytes = c->needs_spill ? (size_t)a.r.n_lanes * PT_SPILL_DEPTHS * PT_SPILL_STRIDE * sizeof(double) : 16;
+    int rc;
+    if ((rc = pt_reserve(c, v.stack_spill, (size_t)a.r.n_lanes * stack_column * 4)) || (rc = pt_reserve(c, v.spill, spill_bytes)) || (rc = pt_reserve(c, v.misc, ps.misc_bytes)) ||
+        (rc = pt_reserve(c, f->staging, (size_t)a.r.n_slots * a.lw * 24)))
+        return rc;
+    a.staging = (double*)f->staging.p;
+    a.r.stack_spill = (uint32_t*)v.stack_spill.p;
+    a.r.spill = (double*)v.spill.p;
+    a.r.overflow_flag = (unsigned int*)v.misc.p + 1;
+    a.r.work_queues = (unsigned int*)((char*)v.misc.p + 256);
+    a.r.fine_queues = 16;
+    v.stream = stream; v.queued = true; v.closed = false;  // from here on something of the pass may be in flight on `stream`, whatever fails below
+    PT_HIP(c, hipMemsetAsync(v.misc.p, 0, ps.misc_bytes, stream));
+    PT_HIP(c, hipEventRecord(v.ev0, stream));
+    return PT_OK;
+}
+// ... and, behind the launches, the second event and the flag's copy.
+static int pt_film_pass_close(pt_context* c, hipStream_t stream) {
+    pt_context::Radiance& v = c->radiance;
+    PT_HIP(c, hipEventRecord(v.ev1, stream));
+    PT_HIP(c, hipMemcpyAsync(v.host, v.misc.p, 8, hipMemcpyDeviceToHost, stream));
+    PT_HIP(c, hipEventRecord(v.copy_done, stream));
+    v.closed = true;
+    return PT_OK;
+}
+
+static int pt_film_add_common(pt_context* c, pt_film* f, const pt_camera* cam, const double* d_background, const pt_film_params* p, hipStream_t stream) {
+    pt_context::Radiance& v = c->radiance;
+    uint32_t lw = PT_FILM_LW;
+    if (const char* e = getenv("PORTRAYER_FILM_LW")) { const int w = atoi(e); if (w == 8 || w == 64) lw = (uint32_t)w; }  // measurements (profiles/film)
+    if (f->moments) lw = PT_FILM_LW;  // (the fold that keeps q takes at most PT_FILM_LW samples per launch: pt_film_map_round)
+    PtFilmArgs a;
+    PtFilmPass ps;
+    int rc = pt_film_pass_args(c, f, cam, d_background, p->slice, p->seed, p->sample_mode, p->background_rows, lw, a, ps);
+    if (rc) return rc;
+    const bool tex = ps.tex, park = ps.park;
     const uint32_t tiles = a.r.n_slots / 64u;
     // the buffers are sized for the add's largest launch (its first: min(samples, lw) samples per pixel); the later ones use a prefix of the same lanes
     auto set_launch = [&](uint32_t m) {
@@ -2840,36 +2894,20 @@ static int pt_film_add_common(pt_context* c, pt_film* f, const pt_camera* cam, c
     set_launch(std::min(p->samples, lw));
     uint32_t grid = 0;
     PT_HIP(c, pt_film_dispatch(a, tex, park, c->n_cu, stream, &grid, false));
-    a.r.n_lanes = grid * PT_BLOCK;
-    const size_t stack_column = pt_stack_column(a.r.scene, a.r.stack_lds_cap);
-    const size_t spill_bytes = c->needs_spill ? (size_t)a.r.n_lanes * PT_SPILL_DEPTHS * PT_SPILL_STRIDE * sizeof(double) : 16;
-    int rc;
-    const size_t misc_bytes = 256 + PT_FINE_QUEUES * PT_QUEUE_STRIDE * 4;  // the overflow flag (word 1, where a render has it), the work queues
-    if ((rc = pt_reserve(c, v.stack_spill, (size_t)a.r.n_lanes * stack_column * 4)) || (rc = pt_reserve(c, v.spill, spill_bytes)) || (rc = pt_reserve(c, v.misc, misc_bytes)) ||
-        (rc = pt_reserve(c, f->staging, (size_t)a.r.n_slots * lw * 24)))
-        return rc;
-    a.staging = (double*)f->staging.p;
-    a.r.stack_spill = (uint32_t*)v.stack_spill.p;
-    a.r.spill = (double*)v.spill.p;
-    a.r.overflow_flag = (unsigned int*)v.misc.p + 1;
-    a.r.work_queues = (unsigned int*)((char*)v.misc.p + 256);
-    a.r.fine_queues = 16;
-    v.stream = stream; v.queued = true; v.closed = false;  // from here on something of the pass may be in flight on `stream`, whatever fails below
-    PT_HIP(c, hipMemsetAsync(v.misc.p, 0, misc_bytes, stream));
-    PT_HIP(c, hipEventRecord(v.ev0, stream));
+    if ((rc = pt_film_pass_open(c, f, a, ps, grid, stream))) return rc;
     for (uint32_t left = p->samples, first = 1; left > 0; first = 0) {
         const uint32_t m = std::min(left, lw);
         set_launch(m);
-        if (!first) PT_HIP(c, hipMemsetAsync((char*)v.misc.p + 256, 0, misc_bytes - 256, stream));  // the queues again; the overflow flag stays
+        if (!first) PT_HIP(c, hipMemsetAsync((char*)v.misc.p + 256, 0, ps.misc_bytes - 256, stream));  // the queues again; the overflow flag stays
         uint32_t g = 0;
         PT_HIP(c, pt_film_dispatch(a, tex, park, c->n_cu, stream, &g, true));  // (g <= grid: no more items than the launch the buffers were sized for)
-        PT_HIP(c, pt_film_fold_launch(a, (double*)f->total.p, (double*)f->partial.p, (uint32_t*)f->count.p, stream));
+        if (f->moments)  // the fold that keeps q as well: a uniform "map" of m, round 0 (pt_film_map.hip)
+            PT_HIP(c, pt_film_fold_map_launch(a, nullptr, m, 0u, (double*)f->total.p, (double*)f->partial.p, (uint32_t*)f->count.p, (double*)f->q.p, stream));
+        else
+            PT_HIP(c, pt_film_fold_launch(a, (double*)f->total.p, (double*)f->partial.p, (uint32_t*)f->count.p, stream));
         left -= m;
     }
-    PT_HIP(c, hipEventRecord(v.ev1, stream));
-    PT_HIP(c, hipMemcpyAsync(v.host, v.misc.p, 8, hipMemcpyDeviceToHost, stream));
-    PT_HIP(c, hipEventRecord(v.copy_done, stream));
-    v.closed = true;
+    if ((rc = pt_film_pass_close(c, stream))) return rc;
     for (uint32_t y = p->slice.y0; y <= p->slice.y1; y++) {  // the host's copy of the counts
         uint32_t* row = f->counts.data() + (size_t)y * f->width;
         for (uint32_t x = p->slice.x0; x <= p->slice.x1; x++) row[x] += p->samples;
@@ -2944,6 +2982,208 @@ extern "C" int pt_film_counts(pt_context* c, pt_film* f, uint32_t* counts) {
     if (rc) return rc;
     PT_HIP(c, hipSetDevice(c->device));
     PT_HIP(c, hipMemcpy(counts, f->count.p, f->counts.size() * 4, hipMemcpyDeviceToHost));  // the DEVICE's counts: what the kernels see
+    std::copy(counts, counts + f->counts.size(), f->counts.begin());  // (behind a device map the host's copy was an upper bound: pt_film_add_map_device)
+    return PT_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Film, adaptive: a budget per pixel, a noise estimate, the budget of a refine pass (pt_film_map.h, pt_film_map.hip)
+// ------------------------------------------------------------------------------------------------
+static hipError_t pt_film_map_dispatch(const PtFilmMapArgs& a, bool tex, bool park, int n_cu, hipStream_t stream, uint32_t* grid, bool launch) {
+    switch (a.f.r.scene.mode) {
+    case PT_MODE_KD: return pt_film_map_launch_mode_2(a, tex, park, n_cu, stream, grid, launch);
+    case PT_MODE_FLAT_NOMESH: return pt_film_map_launch_mode_3(a, tex, park, n_cu, stream, grid, launch);
+    case PT_MODE_FLAT_KDMESH: return pt_film_map_launch_mode_4(a, tex, park, n_cu, stream, grid, launch);
+    case PT_MODE_HIER: return pt_film_map_launch_mode_5(a, tex, park, n_cu, stream, grid, launch);
+    case PT_MODE_HIER_NOMESH: return pt_film_map_launch_mode_6(a, tex, park, n_cu, stream, grid, launch);
+    case PT_MODE_KD_NOMESH: return pt_film_map_launch_mode_7(a, tex, park, n_cu, stream, grid, launch);
+    case PT_MODE_HIER_MESH: return pt_film_map_launch_mode_8(a, tex, park, n_cu, stream, grid, launch);
+    case PT_MODE_KD_MESH: return pt_film_map_launch_mode_9(a, tex, park, n_cu, stream, grid, launch);
+    default: return pt_film_map_launch_mode_1(a, tex, park, n_cu, stream, grid, launch);
+    }
+}
+
+static uint64_t pt_film_slice_slots(const pt_rect& s) { return (uint64_t)((s.x1 - s.x0 + 8u) / 8u) * ((s.y1 - s.y0 + 8u) / 8u) * 64u; }  // 8x8 tiles over the rectangle (pt_slot_to_pixel)
+
+// Everything that can be refused without a HIP call. host_budget: the map where the host can read it (then a pixel's bound is its own m), else NULL.
+// *most: the most any pixel of the slice gets (max_samples for a device map).
+static int pt_film_add_map_check(pt_context* c, pt_film* f, const pt_camera* cam, const double* background, const pt_film_map_params* p, const uint32_t* budget, const uint32_t* host_budget,
+                                 uint32_t* most) {
+    if (!c || !f || !cam || !background || !p || !budget) return pt_fail(c, PT_ERR_ARGUMENT, "pt_film_add_map: NULL context, film, camera, background, params or budget");
+    int rc = pt_film_handle(c, f, false, "pt_film_add_map");
+    if (rc) return rc;
+    if (p->sample_mode != PT_SAMPLE_CENTRE && p->sample_mode != PT_SAMPLE_RNG) return pt_fail(c, PT_ERR_ARGUMENT, "pt_film_add_map: bad sample_mode");
+    if (p->background_rows != 0 && p->background_rows != 1) return pt_fail(c, PT_ERR_ARGUMENT, "pt_film_add_map: background_rows is 0 or 1");
+    if (p->max_samples == 0 || p->max_samples > PT_FILM_MAP_MAX) return pt_fail(c, PT_ERR_ARGUMENT, "pt_film_add_map: max_samples is 1 .. PT_FILM_MAP_MAX");
+    if (p->slice.x0 >= f->width || p->slice.x1 >= f->width || p->slice.y0 >= f->height || p->slice.y1 >= f->height)
+        return pt_fail(c, PT_ERR_SLICE, "slice corner outside the image (render.rs:79-90)");
+    if (!c->have_scene) return pt_fail(c, PT_ERR_NO_SCENE, "no scene uploaded");
+    if (c->radiance.pending) return pt_fail(c, PT_ERR_ARGUMENT, "a pt_radiance_device / pt_film_add_device pass is in flight: pt_radiance_finish first");
+    *most = 0;
+    if (p->slice.x1 < p->slice.x0 || p->slice.y1 < p->slice.y0) return PT_OK;
+    if (pt_film_slice_slots(p->slice) >= PT_FILM_MAP_SLOTS_MAX) return pt_fail(c, PT_ERR_ARGUMENT, "pt_film_add_map: a slice of 2^29 pixel slots or more (an entry of the list is one u32)");
+    for (uint32_t y = p->slice.y0; y <= p->slice.y1; y++) {
+        const uint32_t* row = f->counts.data() + (size_t)y * f->width;
+        const uint32_t* brow = host_budget ? host_budget + (size_t)y * f->width : nullptr;
+        for (uint32_t x = p->slice.x0; x <= p->slice.x1; x++) {
+            const uint32_t m = brow ? std::min(brow[x], p->max_samples) : p->max_samples;
+            if (row[x] > PT_FILM_COUNT_MAX - m) return pt_fail(c, PT_ERR_ARGUMENT, "pt_film_add_map: a pixel's count would pass 2^31");
+            *most = std::max(*most, m);
+        }
+    }
+    return PT_OK;
+}
+
+// Queues the pass like pt_film_add_common; per launch round r < ceil(most / PT_FILM_LW): the plan (list + its length), the queues zeroed, the sampling kernel
+// over the list, the fold. The grid and the buffers are sized from the host's upper bound of round 0: every slot taking min(most, PT_FILM_LW).
+static int pt_film_add_map_common(pt_context* c, pt_film* f, const pt_camera* cam, const double* d_background, const pt_film_map_params* p, const uint32_t* d_budget, uint32_t most,
+                                  hipStream_t stream) {
+    pt_context::Radiance& v = c->radiance;
+    PtFilmMapArgs a;
+    memset(&a, 0, sizeof a);
+    PtFilmPass ps;
+    int rc = pt_film_pass_args(c, f, cam, d_background, p->slice, p->seed, p->sample_mode, p->background_rows, PT_FILM_LW, a.f, ps);
+    if (rc) return rc;
+    const uint32_t n_slots = a.f.r.n_slots;  // (< 2^29: n_slots * PT_FILM_LW fits a u32)
+    auto bound = [&](uint32_t round) { return (uint32_t)(((uint64_t)n_slots * std::min<uint32_t>(most - round * PT_FILM_LW, PT_FILM_LW) + 63u) / 64u); };
+    a.f.r.n_items = bound(0);
+    a.f.launch_samples = PT_FILM_LW;
+    uint32_t grid = 0;
+    PT_HIP(c, pt_film_map_dispatch(a, ps.tex, ps.park, c->n_cu, stream, &grid, false));
+    if ((rc = pt_reserve(c, f->list, 16 + (size_t)n_slots * PT_FILM_LW * 4)) || (rc = pt_reserve(c, f->plan_work, pt_film_plan_words(n_slots) * 4))) return rc;
+    uint32_t* n_list = (uint32_t*)f->list.p;
+    uint32_t* list = (uint32_t*)((char*)f->list.p + 16);
+    a.list = list;
+    a.n_list = n_list;
+    if ((rc = pt_film_pass_open(c, f, a.f, ps, grid, stream))) return rc;
+    const uint32_t rounds = (most + PT_FILM_LW - 1u) / PT_FILM_LW;
+    for (uint32_t round = 0; round < rounds; round++) {
+        PT_HIP(c, pt_film_plan_launch(a.f.r, d_budget, p->max_samples, round, (uint32_t*)f->plan_work.p, list, n_list, stream));
+        if (round) PT_HIP(c, hipMemsetAsync((char*)v.misc.p + 256, 0, ps.misc_bytes - 256, stream));  // the queues again; the overflow flag stays
+        a.f.r.n_items = bound(round);
+        uint32_t g = 0;
+        PT_HIP(c, pt_film_map_dispatch(a, ps.tex, ps.park, c->n_cu, stream, &g, true));  // (g <= grid: no more items than the launch the buffers were sized for)
+        PT_HIP(c, pt_film_fold_map_launch(a.f, d_budget, p->max_samples, round, (double*)f->total.p, (double*)f->partial.p, (uint32_t*)f->count.p, f->moments ? (double*)f->q.p : nullptr, stream));
+    }
+    return pt_film_pass_close(c, stream);
+}
+
+extern "C" int pt_film_add_map(pt_context* c, pt_film* f, const pt_camera* cam, const double* background, const pt_film_map_params* p, const uint32_t* budget, double* kernel_ms) {
+    uint32_t most = 0;
+    int rc = pt_film_add_map_check(c, f, cam, background, p, budget, budget, &most);
+    if (rc) return rc;
+    if (kernel_ms) *kernel_ms = 0.0;
+    if (most == 0) return PT_OK;  // an inverted slice, or a map of zeros over it: nothing queued, nothing changed
+    PT_HIP(c, hipSetDevice(c->device));
+    const size_t bg_bytes = (p->background_rows ? (size_t)f->height : (size_t)f->height * f->width) * 24;
+    if ((rc = pt_reserve(c, f->bg, bg_bytes)) || (rc = pt_reserve(c, f->budget, f->counts.size() * 4))) return rc;
+    PT_HIP(c, hipMemcpy(f->bg.p, background, bg_bytes, hipMemcpyHostToDevice));
+    PT_HIP(c, hipMemcpy(f->budget.p, budget, f->counts.size() * 4, hipMemcpyHostToDevice));
+    rc = pt_film_add_map_common(c, f, cam, (const double*)f->bg.p, p, (const uint32_t*)f->budget.p, most, nullptr);
+    const int rc_wait = pt_radiance_wait(c);
+    if (rc || (rc = rc_wait)) return rc;
+    for (uint32_t y = p->slice.y0; y <= p->slice.y1; y++) {  // the host's copy of the counts, exactly
+        uint32_t* row = f->counts.data() + (size_t)y * f->width;
+        const uint32_t* brow = budget + (size_t)y * f->width;
+        for (uint32_t x = p->slice.x0; x <= p->slice.x1; x++) row[x] += std::min(brow[x], p->max_samples);
+    }
+    return pt_radiance_close(c, kernel_ms);
+}
+
+extern "C" int pt_film_add_map_device(pt_context* c, pt_film* f, const pt_camera* cam, const double* d_background, const pt_film_map_params* p, const uint32_t* d_budget, void* hip_stream) {
+    uint32_t most = 0;
+    int rc = pt_film_add_map_check(c, f, cam, d_background, p, d_budget, nullptr, &most);
+    if (rc) return rc;
+    if (most == 0) return PT_OK;  // an inverted slice: nothing queued, nothing to finish
+    PT_HIP(c, hipSetDevice(c->device));
+    if ((rc = pt_film_add_map_common(c, f, cam, d_background, p, d_budget, most, (hipStream_t)hip_stream))) {
+        pt_radiance_wait(c);  // what was queued before the failure must not outlive the call
+        return rc;
+    }
+    for (uint32_t y = p->slice.y0; y <= p->slice.y1; y++) {  // the host's copy of the counts: an upper bound, until pt_film_counts
+        uint32_t* row = f->counts.data() + (size_t)y * f->width;
+        for (uint32_t x = p->slice.x0; x <= p->slice.x1; x++) row[x] += p->max_samples;
+    }
+    c->radiance.pending = true;
+    c->film_open = f;
+    return PT_OK;
+}
+
+extern "C" int pt_film_error_device(pt_context* c, pt_film* f, double* d_err, void* hip_stream) {
+    if (!c || !f || !d_err) return pt_fail(c, PT_ERR_ARGUMENT, "pt_film_error_device: NULL context, film or err");
+    int rc = pt_film_handle(c, f, false, "pt_film_error_device");
+    if (rc) return rc;
+    if (!f->moments) return pt_fail(c, PT_ERR_ARGUMENT, "pt_film_error: the film keeps no second moment (pt_film_create_moments)");
+    PT_HIP(c, hipSetDevice(c->device));
+    PT_HIP(c, pt_film_error_launch(f->width, f->height, (const double*)f->total.p, (const double*)f->partial.p, (const uint32_t*)f->count.p, (const double*)f->q.p, d_err, (hipStream_t)hip_stream));
+    return PT_OK;
+}
+
+extern "C" int pt_film_error(pt_context* c, pt_film* f, double* err) {
+    if (!c || !f || !err) return pt_fail(c, PT_ERR_ARGUMENT, "pt_film_error: NULL context, film or err");
+    int rc = pt_film_handle(c, f, true, "pt_film_error");
+    if (rc) return rc;
+    if (!f->moments) return pt_fail(c, PT_ERR_ARGUMENT, "pt_film_error: the film keeps no second moment (pt_film_create_moments)");
+    PT_HIP(c, hipSetDevice(c->device));
+    const size_t n = f->counts.size();
+    if ((rc = pt_reserve(c, f->out_err, n * 8))) return rc;
+    PT_HIP(c, pt_film_error_launch(f->width, f->height, (const double*)f->total.p, (const double*)f->partial.p, (const uint32_t*)f->count.p, (const double*)f->q.p, (double*)f->out_err.p, nullptr));
+    PT_HIP(c, hipMemcpy(err, f->out_err.p, n * 8, hipMemcpyDeviceToHost));
+    return PT_OK;
+}
+
+extern "C" int pt_film_budget_device(pt_context* c, pt_film* f, const pt_film_refine_params* p, uint32_t* d_budget, uint64_t* d_summary, void* hip_stream) {
+    if (!c || !f || !p || !d_budget || !d_summary) return pt_fail(c, PT_ERR_ARGUMENT, "pt_film_budget_device: NULL context, film, params, budget or summary");
+    int rc = pt_film_handle(c, f, true, "pt_film_budget_device");
+    if (rc) return rc;
+    if (!f->moments) return pt_fail(c, PT_ERR_ARGUMENT, "pt_film_budget_device: the film keeps no second moment (pt_film_create_moments)");
+    if (p->step == 0 || p->step > PT_FILM_MAP_MAX) return pt_fail(c, PT_ERR_ARGUMENT, "pt_film_budget_device: step is 1 .. PT_FILM_MAP_MAX");
+    if (p->min_count > p->max_count || p->max_count > PT_FILM_COUNT_MAX) return pt_fail(c, PT_ERR_ARGUMENT, "pt_film_budget_device: min_count <= max_count <= 2^31");
+    if (p->threshold != p->threshold) return pt_fail(c, PT_ERR_ARGUMENT, "pt_film_budget_device: the threshold is not a number");
+    if (p->slice.x0 >= f->width || p->slice.x1 >= f->width || p->slice.y0 >= f->height || p->slice.y1 >= f->height)
+        return pt_fail(c, PT_ERR_SLICE, "slice corner outside the image (render.rs:79-90)");
+    PT_HIP(c, hipSetDevice(c->device));
+    PtRenderArgs r;
+    memset(&r, 0, sizeof r);
+    r.width = f->width; r.height = f->height;
+    r.x0 = p->slice.x0; r.y0 = p->slice.y0; r.x1 = p->slice.x1; r.y1 = p->slice.y1;  // (an inverted slice holds no pixel: zeros everywhere)
+    PT_HIP(c, hipMemsetAsync(d_summary, 0, 16, (hipStream_t)hip_stream));
+    PT_HIP(c, pt_film_budget_launch(r, p->threshold, p->min_count, p->max_count, p->step, (const double*)f->total.p, (const double*)f->partial.p, (const uint32_t*)f->count.p, (const double*)f->q.p,
+                                    d_budget, (unsigned long long*)d_summary, (hipStream_t)hip_stream));
+    return PT_OK;
+}
+
+// The plan kernels alone (tests): the list of one launch round, copied back.
+extern "C" int pt_test_film_plan(pt_context* c, uint32_t width, uint32_t height, const pt_rect* slice, const uint32_t* budget, uint32_t max_samples, uint32_t round, uint32_t* list, uint32_t cap,
+                                 uint32_t* n_out) {
+    if (!c || !slice || !budget || !n_out || (!list && cap) || width == 0 || height == 0 || (uint64_t)width * height >= 0x80000000ull || max_samples == 0 || max_samples > PT_FILM_MAP_MAX ||
+        round >= (PT_FILM_MAP_MAX + PT_FILM_LW - 1) / PT_FILM_LW)
+        return pt_fail(c, PT_ERR_ARGUMENT, "pt_test_film_plan: bad argument");
+    if (slice->x0 > slice->x1 || slice->y0 > slice->y1 || slice->x1 >= width || slice->y1 >= height) return pt_fail(c, PT_ERR_SLICE, "pt_test_film_plan: bad slice");
+    if (pt_film_slice_slots(*slice) >= PT_FILM_MAP_SLOTS_MAX) return pt_fail(c, PT_ERR_ARGUMENT, "pt_test_film_plan: a slice of 2^29 pixel slots or more");
+    PT_HIP(c, hipSetDevice(c->device));
+    PtRenderArgs r;
+    memset(&r, 0, sizeof r);
+    r.width = width; r.height = height;
+    r.x0 = slice->x0; r.y0 = slice->y0; r.x1 = slice->x1; r.y1 = slice->y1;
+    r.tile_rank = 0; r.tile_ranks = 1;
+    r.n_slots = (uint32_t)pt_film_slice_slots(*slice);
+    const size_t n_pixels = (size_t)width * height;
+    PtBuf d_budget, d_list, d_work;
+    int rc;
+    if ((rc = pt_reserve(c, d_budget, n_pixels * 4)) || (rc = pt_reserve(c, d_list, 16 + (size_t)r.n_slots * PT_FILM_LW * 4)) || (rc = pt_reserve(c, d_work, pt_film_plan_words(r.n_slots) * 4))) {
+        for (PtBuf* b : {&d_budget, &d_list, &d_work}) if (b->p) hipFree(b->p);
+        return rc;
+    }
+    uint32_t n = 0;
+    hipError_t e = hipMemcpy(d_budget.p, budget, n_pixels * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = pt_film_plan_launch(r, (const uint32_t*)d_budget.p, max_samples, round, (uint32_t*)d_work.p, (uint32_t*)((char*)d_list.p + 16), (uint32_t*)d_list.p, nullptr);
+    if (e == hipSuccess) e = hipMemcpy(&n, d_list.p, 4, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && n > r.n_slots * (uint32_t)PT_FILM_LW) n = r.n_slots * (uint32_t)PT_FILM_LW;  // (never: the list's room)
+    if (e == hipSuccess && std::min(n, cap)) e = hipMemcpy(list, (char*)d_list.p + 16, (size_t)std::min(n, cap) * 4, hipMemcpyDeviceToHost);
+    for (PtBuf* b : {&d_budget, &d_list, &d_work}) if (b->p) hipFree(b->p);
+    if (e != hipSuccess) return pt_fail(c, PT_ERR_DEVICE, std::string("pt_test_film_plan: ") + hipGetErrorString(e));
+    *n_out = n;
     return PT_OK;
 }
 

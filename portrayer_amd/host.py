@@ -19,7 +19,7 @@ _dp, _ip, _up, _u64p, _u8p = H._dp, H._ip, H._up, H._u64p, H._u8p
 
 EXPORTS = ["ph_last_error", "ph_scene_create", "ph_example_scene", "ph_scene_destroy", "ph_scene_counts", "ph_scene_export", "ph_scene_export_textures",
            "ph_scene_flatten", "ph_scene_kdtree", "ph_camera", "ph_obj_load", "ph_renderer_create", "ph_renderer_destroy",
-           "ph_renderer_context", "ph_renderer_ranks", "ph_renderer_node", "ph_renderer_prepare_ms", "ph_renderer_render", "ph_renderer_aov", "ph_renderer_rays", "ph_renderer_segments", "ph_renderer_radiance", "ph_renderer_film_create", "ph_renderer_film_destroy", "ph_renderer_film_reset", "ph_renderer_film_add", "ph_renderer_film_resolve", "ph_renderer_film_counts", "ph_renderer_update", "ph_scene_same_structure", "ph_renderer_deform", "ph_scene_same_topology", "ph_renderer_deform_device", "ph_renderer_mesh_count", "ph_renderer_mesh_vertices", "ph_example_render_to_png", "ph_png_read", "ph_png_write", "ph_image_read", "ph_scene_graph"]
+           "ph_renderer_context", "ph_renderer_ranks", "ph_renderer_node", "ph_renderer_prepare_ms", "ph_renderer_render", "ph_renderer_aov", "ph_renderer_rays", "ph_renderer_segments", "ph_renderer_radiance", "ph_renderer_film_create", "ph_renderer_film_destroy", "ph_renderer_film_reset", "ph_renderer_film_add", "ph_renderer_film_resolve", "ph_renderer_film_counts", "ph_renderer_film_create_moments", "ph_renderer_film_add_map", "ph_renderer_film_error", "ph_renderer_film_refine", "ph_renderer_update", "ph_scene_same_structure", "ph_renderer_deform", "ph_scene_same_topology", "ph_renderer_deform_device", "ph_renderer_mesh_count", "ph_renderer_mesh_vertices", "ph_example_render_to_png", "ph_png_read", "ph_png_write", "ph_image_read", "ph_scene_graph"]
 
 
 class PortrayerHostError(RuntimeError):
@@ -95,6 +95,11 @@ def lib() -> C.CDLL:
         l.ph_renderer_film_add.restype = C.c_int; l.ph_renderer_film_add.argtypes = [vp, vp, _dp, _dp, C.POINTER(H.PtFilmParams), _dp]
         l.ph_renderer_film_resolve.restype = C.c_int; l.ph_renderer_film_resolve.argtypes = [vp, vp, _u8p, _dp]
         l.ph_renderer_film_counts.restype = C.c_int; l.ph_renderer_film_counts.argtypes = [vp, vp, _up]
+        l.ph_renderer_film_create_moments.restype = C.c_int; l.ph_renderer_film_create_moments.argtypes = [vp, C.c_uint32, C.c_uint32, C.POINTER(vp)]
+        l.ph_renderer_film_add_map.restype = C.c_int; l.ph_renderer_film_add_map.argtypes = [vp, vp, _dp, _dp, C.POINTER(H.PtFilmMapParams), _up, _dp]
+        l.ph_renderer_film_error.restype = C.c_int; l.ph_renderer_film_error.argtypes = [vp, vp, _dp]
+        l.ph_renderer_film_refine.restype = C.c_int
+        l.ph_renderer_film_refine.argtypes = [vp, vp, _dp, _dp, C.POINTER(H.PtFilmMapParams), C.POINTER(H.PtFilmRefineParams), C.c_uint32, _u64p, _dp]
         l.ph_renderer_update.restype = C.c_int; l.ph_renderer_update.argtypes = [vp, vp]
         l.ph_scene_same_structure.restype = C.c_int; l.ph_scene_same_structure.argtypes = [vp, vp, C.c_char_p, C.c_size_t]
         l.ph_renderer_deform.restype = C.c_int; l.ph_renderer_deform.argtypes = [vp, vp, C.c_int]
@@ -313,14 +318,18 @@ class Film:
     bits of Renderer.render(samples = that pixel's count) - provided every add used the same camera, background, seed and sample mode and the scene did not
     change in between. Made by Renderer.film(); close it before its renderer."""
 
-    def __init__(self, renderer: "Renderer", width: int, height: int):
+    def __init__(self, renderer: "Renderer", width: int, height: int, moments: bool = False):
         for name, v in (("width", width), ("height", height)):
             if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 < int(v) < 1 << 32:
                 raise ValueError("%s must be a positive integer, got %r" % (name, v))
         self._h = C.c_void_p()
         self._r = renderer
         self.width, self.height = int(width), int(height)
-        _check(lib().ph_renderer_film_create(renderer._h, self.width, self.height, C.byref(self._h)), "ph_renderer_film_create")
+        self.moments = bool(moments)
+        if self.moments:
+            _check(lib().ph_renderer_film_create_moments(renderer._h, self.width, self.height, C.byref(self._h)), "ph_renderer_film_create_moments")
+        else:
+            _check(lib().ph_renderer_film_create(renderer._h, self.width, self.height, C.byref(self._h)), "ph_renderer_film_create")
 
     def close(self):
         if self._h and self._r._h:
@@ -350,6 +359,73 @@ class Film:
         ms = C.c_double(0.0)
         _check(lib().ph_renderer_film_add(self._r._h, self._h, _p(c, _dp), _p(bg, _dp), C.byref(p), C.byref(ms)), "ph_renderer_film_add")
         return ms.value
+
+    def _background(self, background):
+        bg = np.ascontiguousarray(background, dtype=np.float64)
+        rows = 1 if bg.shape == (self.height, 3) else 0
+        if not rows and bg.shape != (self.height, self.width, 3):
+            raise ValueError("background must be (H, 3) or (H, W, 3)")
+        return bg, rows
+
+    @staticmethod
+    def _integer(name, v, lo, hi):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
+            raise ValueError("%s must be an integer in [%d, %d], got %r" % (name, lo, hi, v))
+        return int(v)
+
+    def add_map(self, cam10, background, budget, seed: int = 0, sample_mode: int = H.SAMPLE_CENTRE, rect=None, max_samples: Optional[int] = None) -> float:
+        """Pixel p of `rect` gets its next min(budget[p], max_samples) samples, each taken as add() takes it: `budget` is an (H, W) uint32 array, of which only
+        `rect` is read; max_samples (default: the largest budget inside rect, at most 4096) bounds what any pixel gets. A budget of zeros adds nothing.
+        Returns the device time in ms."""
+        bg, rows = self._background(background)
+        if not isinstance(budget, np.ndarray) or budget.dtype != np.uint32 or budget.shape != (self.height, self.width):
+            raise ValueError("budget must be a uint32 array of shape %r" % ((self.height, self.width),))
+        b = np.ascontiguousarray(budget)
+        seed = self._integer("seed", seed, 0, (1 << 64) - 1)
+        x0, y0, x1, y1 = rect if rect is not None else (0, 0, self.width - 1, self.height - 1)
+        if max_samples is None:
+            inside = b[y0:y1 + 1, x0:x1 + 1] if 0 <= x0 <= x1 < self.width and 0 <= y0 <= y1 < self.height else b[:0]
+            max_samples = min(max(int(inside.max()) if inside.size else 1, 1), H.FILM_MAP_MAX)
+        max_samples = self._integer("max_samples", max_samples, 1, H.FILM_MAP_MAX)
+        p = H.PtFilmMapParams(H.PtRect(x0, y0, x1, y1), max_samples, seed, sample_mode, rows)
+        c = np.ascontiguousarray(cam10, dtype=np.float64)
+        ms = C.c_double(0.0)
+        _check(lib().ph_renderer_film_add_map(self._r._h, self._h, _p(c, _dp), _p(bg, _dp), C.byref(p), _p(b, _up), C.byref(ms)), "ph_renderer_film_add_map")
+        return ms.value
+
+    def error(self, into: Optional[np.ndarray] = None) -> np.ndarray:
+        """(H, W) float64: the standard error of every pixel's mean (of r + g + b, linear units); +inf where a pixel has fewer than 2 samples. Needs a film
+        made with moments=True."""
+        if not self.moments:
+            raise ValueError("error() needs a film that keeps moments: Renderer.film(w, h, moments=True)")
+        err = into if into is not None else np.zeros((self.height, self.width), dtype=np.float64)
+        if not isinstance(err, np.ndarray) or err.shape != (self.height, self.width) or err.dtype != np.float64 or not err.flags.c_contiguous:
+            raise ValueError("into must be a C-contiguous float64 array of shape %r" % ((self.height, self.width),))
+        _check(lib().ph_renderer_film_error(self._r._h, self._h, _p(err, _dp)), "ph_renderer_film_error")
+        return err
+
+    def refine(self, cam10, background, threshold: float, min_count: int = 8, max_count: int = 64, step: int = 8, max_passes: int = 64, seed: int = 0,
+               sample_mode: int = H.SAMPLE_CENTRE, rect=None) -> dict:
+        """The closed loop on the device: every pixel of `rect` is brought to min_count samples, then pixels whose error() is above `threshold` get up to
+        `step` more per pass until they fall below it or reach max_count, or max_passes have run. Returns {"passes", "samples", "pixels_left", "kernel_ms"}."""
+        if not self.moments:
+            raise ValueError("refine() needs a film that keeps moments: Renderer.film(w, h, moments=True)")
+        bg, rows = self._background(background)
+        if isinstance(threshold, bool) or not isinstance(threshold, (int, float, np.integer, np.floating)) or threshold != threshold:
+            raise ValueError("threshold must be a number, got %r" % (threshold,))
+        step = self._integer("step", step, 1, H.FILM_MAP_MAX)
+        max_count = self._integer("max_count", max_count, 0, 1 << 31)
+        min_count = self._integer("min_count", min_count, 0, max_count)
+        max_passes = self._integer("max_passes", max_passes, 0, (1 << 32) - 1)
+        seed = self._integer("seed", seed, 0, (1 << 64) - 1)
+        x0, y0, x1, y1 = rect if rect is not None else (0, 0, self.width - 1, self.height - 1)
+        sp = H.PtFilmMapParams(H.PtRect(x0, y0, x1, y1), step, seed, sample_mode, rows)
+        rp = H.PtFilmRefineParams(H.PtRect(x0, y0, x1, y1), float(threshold), min_count, max_count, step)
+        c = np.ascontiguousarray(cam10, dtype=np.float64)
+        out = np.zeros(3, dtype=np.uint64)
+        ms = C.c_double(0.0)
+        _check(lib().ph_renderer_film_refine(self._r._h, self._h, _p(c, _dp), _p(bg, _dp), C.byref(sp), C.byref(rp), max_passes, _p(out, _u64p), C.byref(ms)), "ph_renderer_film_refine")
+        return {"passes": int(out[0]), "samples": int(out[1]), "pixels_left": int(out[2]), "kernel_ms": ms.value}
 
     def resolve(self, want_linear: bool = True, into: Optional[np.ndarray] = None, linear_into: Optional[np.ndarray] = None):
         """(rgb, linear): (H, W, 3) uint8 and (H, W, 3) float64 (None without want_linear). Pixels that have no sample yet keep what `into` / `linear_into`
@@ -429,9 +505,10 @@ class Renderer:
         _check(lib().ph_renderer_render(self._h, _p(c, _dp), C.byref(p), _p(bg, _dp), _p(rgb, _u8p), _p(linear, _dp), C.byref(st)), "ph_renderer_render")
         return rgb, linear, st.as_dict()
 
-    def film(self, width: int, height: int) -> Film:
-        """A film of this renderer (pt_film_create): samples accumulate on the device, add after add; see Film."""
-        return Film(self, width, height)
+    def film(self, width: int, height: int, moments: bool = False) -> Film:
+        """A film of this renderer (pt_film_create): samples accumulate on the device, add after add; see Film. moments=True (pt_film_create_moments): the
+        film also keeps what error() and refine() need."""
+        return Film(self, width, height, moments)
 
     def update(self, scene: Scene):
         """The resident scene moved (pt_scene_update): `scene` must be the renderer's scene with other transforms, lights' values or ambient light

@@ -689,6 +689,82 @@ extern "C" int ph_renderer_film_counts(ph_renderer* r, ph_film* film, uint32_t* 
     return guarded([&]() -> int { return film_rc(r, pt_film_counts(r->r->context(), film->f, counts)); });
 }
 
+extern "C" int ph_renderer_film_create_moments(ph_renderer* r, uint32_t width, uint32_t height, ph_film** out) {
+    if (!r || !out) return bad("null argument");
+    *out = nullptr;
+    if (width == 0 || height == 0) return bad("a film's width and height must be positive");
+    if (r->r->node()) return bad("a film lives on one device: this renderer is spread over several ranks (PORTRAYER_GPUS); create it with one");
+    return guarded([&]() -> int {
+        auto f = std::make_unique<ph_film>();
+        f->width = width; f->height = height;
+        int rc = film_rc(r, pt_film_create_moments(r->r->context(), width, height, &f->f));
+        if (rc != PH_OK) return rc;
+        *out = f.release();
+        return PH_OK;
+    });
+}
+
+extern "C" int ph_renderer_film_add_map(ph_renderer* r, ph_film* film, const double camera[10], const double* background, const pt_film_map_params* p, const uint32_t* budget, double* kernel_ms) {
+    if (!r || !film || !camera || !background || !p || !budget) return bad("null argument");
+    return guarded([&]() -> int {
+        pt_camera pc = detail::Camera(camera_from(camera), (double)film->width, (double)film->height).to_abi();  // the camera a render of this size gets
+        return film_rc(r, pt_film_add_map(r->r->context(), film->f, &pc, background, p, budget, kernel_ms));
+    });
+}
+
+extern "C" int ph_renderer_film_error(ph_renderer* r, ph_film* film, double* err) {
+    if (!r || !film || !err) return bad("null argument");
+    return guarded([&]() -> int { return film_rc(r, pt_film_error(r->r->context(), film->f, err)); });
+}
+
+// The closed loop: budget on the device, its two-word summary to the host, a device map's add, until no pixel wants more or max_passes have run. The map
+// never leaves the device.
+extern "C" int ph_renderer_film_refine(ph_renderer* r, ph_film* film, const double camera[10], const double* background, const pt_film_map_params* sampling, const pt_film_refine_params* refine,
+                                       uint32_t max_passes, uint64_t out[3], double* kernel_ms) {
+    if (!r || !film || !camera || !background || !sampling || !refine || !out) return bad("null argument");
+    if (sampling->background_rows != 0 && sampling->background_rows != 1) return bad("background_rows is 0 or 1");
+    return guarded([&]() -> int {
+        pt_context* c = r->r->context();
+        pt_camera pc = detail::Camera(camera_from(camera), (double)film->width, (double)film->height).to_abi();
+        const size_t n = (size_t)film->width * film->height;
+        const size_t bg_bytes = (sampling->background_rows ? (size_t)film->height : n) * 24;
+        void *d_bg = nullptr, *d_budget = nullptr, *d_summary = nullptr;
+        auto release = [&]() { for (void* d : {d_bg, d_budget, d_summary}) if (d) pt_device_free(c, d); };
+        int rc;
+        if ((rc = pt_device_alloc(c, bg_bytes, &d_bg)) || (rc = pt_device_alloc(c, n * 4, &d_budget)) || (rc = pt_device_alloc(c, 16, &d_summary)) ||
+            (rc = pt_copy_to_device(c, d_bg, background, bg_bytes))) {
+            rc = film_rc(r, rc);
+            release();
+            return rc;
+        }
+        pt_film_map_params mp = *sampling;
+        mp.slice = refine->slice;
+        mp.max_samples = refine->step;
+        uint64_t passes = 0, samples = 0, summary[2] = {0, 0};
+        double ms_all = 0.0;
+        for (;;) {
+            if ((rc = pt_film_budget_device(c, film->f, refine, (uint32_t*)d_budget, (uint64_t*)d_summary, nullptr)) || (rc = pt_copy_from_device(c, summary, d_summary, 16))) break;
+            if (summary[0] == 0 || passes == max_passes) break;
+            double ms = 0.0;
+            if ((rc = pt_film_add_map_device(c, film->f, &pc, (const double*)d_bg, &mp, (const uint32_t*)d_budget, nullptr))) break;
+            if ((rc = pt_radiance_finish(c, &ms))) break;
+            ms_all += ms;
+            passes++;
+            samples += summary[1];
+        }
+        if (rc == PT_OK && passes) {  // the library's host copy of the counts was raised by `step` per pass: back to the device's values
+            std::vector<uint32_t> counts(n);
+            rc = pt_film_counts(c, film->f, counts.data());
+        }
+        rc = film_rc(r, rc);
+        release();
+        if (rc != PH_OK) return rc;
+        out[0] = passes; out[1] = samples; out[2] = summary[0];
+        if (kernel_ms) *kernel_ms = ms_all;
+        return PH_OK;
+    });
+}
+
 extern "C" int ph_example_render_to_png(const char* name, const char* assets_dir, int n, uint32_t width, uint32_t height, const char* png_path) {
     if (!name || !png_path) return bad("null argument");
     return guarded([&]() -> int {

@@ -112,6 +112,14 @@ pub struct PtFilmParams {                  // pt_film_params: one add to a film 
     pub slice: PtRect, pub samples: u32, pub seed: u64, pub sample_mode: i32, pub background_rows: i32,
 }
 #[repr(C)]
+pub struct PtFilmMapParams {               // pt_film_map_params: one add with a budget per pixel - pixel p of `slice` gets its next min(budget[p], max_samples) samples
+    pub slice: PtRect, pub max_samples: u32, pub seed: u64, pub sample_mode: i32, pub background_rows: i32,
+}
+#[repr(C)]
+pub struct PtFilmRefineParams {            // pt_film_refine_params: the budget of a refine pass - up to `step` below min_count, or below max_count with an error above the threshold
+    pub slice: PtRect, pub threshold: f64, pub min_count: u32, pub max_count: u32, pub step: u32,
+}
+#[repr(C)]
 pub struct PtRaysBuffers {                 // pt_rays_buffers: each optional (null = not wanted), n entries, indexed like the rays
     pub t: *mut f64, pub position: *mut f64, pub normal: *mut f64, pub node: *mut i32, pub sub: *mut i32, pub material: *mut i32, pub occluded: *mut u8,
 }
@@ -176,6 +184,17 @@ extern "C" {
     pub fn pt_film_resolve(ctx: *mut PtContext, film: *mut PtFilm, rgb: *mut u8, linear: *mut f64) -> c_int;
     pub fn pt_film_resolve_device(ctx: *mut PtContext, film: *mut PtFilm, d_rgb: *mut c_void, d_linear: *mut f64, hip_stream: *mut c_void) -> c_int;
     pub fn pt_film_counts(ctx: *mut PtContext, film: *mut PtFilm, counts: *mut u32) -> c_int;
+    // the adaptive film: a film that also keeps a second moment (60 bytes per pixel), an add with a budget per pixel (host or device map), the standard
+    // error of every pixel's mean, and the budget a refine pass gives with its two-word summary; pt_film_add_map_device is closed by pt_radiance_finish
+    pub fn pt_film_create_moments(ctx: *mut PtContext, width: u32, height: u32, out: *mut *mut PtFilm) -> c_int;
+    pub fn pt_film_add_map(ctx: *mut PtContext, film: *mut PtFilm, camera: *const PtCamera, background: *const f64, params: *const PtFilmMapParams,
+                           budget: *const u32, kernel_ms: *mut f64) -> c_int;
+    pub fn pt_film_add_map_device(ctx: *mut PtContext, film: *mut PtFilm, camera: *const PtCamera, d_background: *const f64, params: *const PtFilmMapParams,
+                                  d_budget: *const u32, hip_stream: *mut c_void) -> c_int;
+    pub fn pt_film_error(ctx: *mut PtContext, film: *mut PtFilm, err: *mut f64) -> c_int;
+    pub fn pt_film_error_device(ctx: *mut PtContext, film: *mut PtFilm, d_err: *mut f64, hip_stream: *mut c_void) -> c_int;
+    pub fn pt_film_budget_device(ctx: *mut PtContext, film: *mut PtFilm, params: *const PtFilmRefineParams, d_budget: *mut u32, d_summary: *mut u64,
+                                 hip_stream: *mut c_void) -> c_int;
     pub fn pt_context_stream(ctx: *mut PtContext, slot: c_int) -> *mut c_void;
     pub fn pt_context_next_slot(ctx: *const PtContext) -> c_int;
     // one render call over the GPUs of a node (one context per GPU, one RCCL gather)

@@ -5,7 +5,8 @@
 
 Extracts the gfx950 code object from pt_render_m1.o .. pt_render_m9.o of both directories (llvm-objdump --offloading, as
 tests/test_kernel_resources.py does) and compares them byte for byte; likewise the primary-visibility pass's (pt_aov_m*.o), the ray-query passes'
-(pt_rays_m*.o, pt_segments_m*.o) and the radiance pass's (pt_radiance_m*.o), where the other build has them. A change that claims to leave the render path alone
+(pt_rays_m*.o, pt_segments_m*.o), the radiance pass's (pt_radiance_m*.o), the film's (pt_film_m*.o, pt_film.o) and the single objects' (pt_api.o, pt_build.o,
+pt_rays_sort.o), where the other build has them. A change that claims to leave the render path alone
 (a new pass beside it, host code) runs this against a build of its parent commit: identical code objects mean identical
 behaviour and speed of every render kernel, without a GPU. Exit status 0: all identical; 1: some differ (named)."""
 import filecmp
@@ -48,7 +49,18 @@ def main(argv):
                 compared += 1
                 if not same:
                     differ.append(name)
-    print("render, aov, rays, segments and radiance code objects: %s" % ("all %d byte-identical" % compared if not differ else "differ: " + ", ".join(differ)))
+        # the film's objects (pt_film_m*.o and its fold / resolve kernels) and the single objects, where the other build has them
+        singles = ["pt_film_m%d.o" % m for m in range(1, 10)] + ["pt_film.o", "pt_api.o", "pt_build.o", "pt_rays_sort.o"]  # (pt_node.o holds no device code)
+        for name in singles:
+            if not os.path.exists(os.path.join(other, name)):
+                continue
+            a, b = code_object(os.path.join(other, name), tmp), code_object(os.path.join(mine, name), tmp)
+            same = filecmp.cmp(a, b, shallow=False)
+            print("%-18s %9d bytes  %s" % (name, os.path.getsize(b), "identical" if same else "DIFFERENT"))
+            compared += 1
+            if not same:
+                differ.append(name)
+    print("render, aov, rays, segments, radiance, film and single code objects: %s" % ("all %d byte-identical" % compared if not differ else "differ: " + ", ".join(differ)))
     return 1 if differ else 0
 
 
