@@ -36,7 +36,8 @@ HIP_OBJS := $(OBJDIR)/pt_api.o $(OBJDIR)/pt_build.o $(OBJDIR)/pt_node.o $(foreac
             $(foreach m,$(RENDER_MODES),$(OBJDIR)/pt_radiance_m$(m).o) \
             $(foreach m,$(RENDER_MODES),$(OBJDIR)/pt_segments_m$(m).o) \
             $(OBJDIR)/pt_film.o $(foreach m,$(RENDER_MODES),$(OBJDIR)/pt_film_m$(m).o) \
-            $(OBJDIR)/pt_film_map.o $(foreach m,$(RENDER_MODES),$(OBJDIR)/pt_film_map_m$(m).o)
+            $(OBJDIR)/pt_film_map.o $(foreach m,$(RENDER_MODES),$(OBJDIR)/pt_film_map_m$(m).o) \
+            $(OBJDIR)/pt_denoise.o
 
 # Every HIP translation unit is built in four steps instead of one `hipcc -c`, so that the device code can be CHECKED and REPAIRED between
 # the compiler and the assembler (tools/check_exec_prologue.py; profiles/r05/notes.md section 1: the AMDGPU backend of this toolchain can put

@@ -527,6 +527,50 @@ int pt_film_error(pt_context *ctx, pt_film *film, double *err);   /* host, width
 int pt_film_error_device(pt_context *ctx, pt_film *film, double *d_err, void *hip_stream);
 int pt_film_budget_device(pt_context *ctx, pt_film *film, const pt_film_refine_params *params, uint32_t *d_budget, uint64_t *d_summary, void *hip_stream);
 
+/* ---- Film, denoised: a second, explicitly LOSSY way to read a film (resolve keeps its promise; the film's state is not written). An edge-avoiding a-trous
+ * wavelet filter over the resolved mean, steered by primary-visibility buffers (`guides`, laid out as pt_aov writes them) and by the film's own noise
+ * estimate. The filter has no counterpart in the reference: it is DEFINED as the following sequence of correctly rounded IEEE f64 operations (+ - * /,
+ * comparisons; no exp, no libm - the weights are clamped rationals so that a restatement can match in its bits), and the kernels, pt_test_denoise_host and
+ * a numpy restatement agree in every bit. portrayer_amd/csrc/pt_denoise.h holds these steps as functions; DESIGN 4.14 has the text.
+ *   level 0, per pixel with count > 0: c = pt_film_sum / count (resolve's linear); v = e * e, e = pt_film_error's value, where count >= 2; at count 1
+ *     v = my * my, my = (c.x + c.y) + c.z; on a film without moments v = 0, accepted with sigma_color == 0 only.
+ *   level l (0 <= l < iterations), step s = 1 << l, H = {1/16, 1/4, 3/8, 1/4, 1/16}: for every centre p with count > 0, cs = (+0, +0, +0), vs = ws = +0; the
+ *     taps q = p + s (i, j), j = -2 .. 2 outer, i = -2 .. 2 inner; a tap outside the film or with count[q] == 0 is skipped; then
+ *       1. skip if (node[p] < 0) != (node[q] < 0); with PT_DENOISE_SAME_NODE skip if node[p] != node[q];
+ *       2. w = H[j + 2] * H[i + 2];
+ *       3. on a hit, normal_power_log2 >= 0: a = (n_p.x n_q.x + n_p.y n_q.y) + n_p.z n_q.z; a = a > 0 ? a : 0; normal_power_log2 times a = a * a; w = w * a;
+ *       4. on a hit, sigma_plane > 0: e = pos_q - pos_p; d = (n_p.x e.x + n_p.y e.y) + n_p.z e.z; t = 1 - (d * d) * kp; w = w * (t > 0 ? t * t : 0);
+ *          kp = 1.0 / (sigma_plane * sigma_plane);
+ *       5. sigma_color > 0: y = (c.x + c.y) + c.z; dy = y_p - y_q; t = 1 - (dy * dy) / (kc * (v_p + v_q) + 1e-12); w = w * (t > 0 ? t * t : 0);
+ *          kc = sigma_color * sigma_color;
+ *       6. skip unless w > 0 (also a NaN weight from non-finite guides);
+ *       7. cs = cs + c_q * w per channel; vs = vs + (w * w) * v_q; ws = ws + w.
+ *     c' = cs / ws, v' = vs / (ws * ws); with ws == 0 (a degenerate guide at p itself) c' = c_p, v' = v_p.
+ *   after the last level, each optional: linear = c (width x height x 3 f64), variance = v (width x height f64), rgb = resolve's finishing of c (gamma, clamp,
+ *     u8). Pixels with count == 0 are neither centres nor taps and keep what the output buffers hold.
+ * MEMORY: a level reads (c, v) and writes the next level's: two work buffers of 32 bytes per pixel that BELONG TO THE FILM - allocated by its first denoise,
+ * kept for later ones, freed with the film.
+ * Guides: `node` always; `normal` with normal_power_log2 >= 0 or sigma_plane > 0; `position` with sigma_plane > 0. No scene is needed.
+ * Errors, with nothing written: PT_ERR_ARGUMENT (NULL context, film, params or guides; a film of another context; iterations outside 1 .. 8; unknown flags;
+ * a negative or non-finite sigma; normal_power_log2 outside -1 .. 7; a required guide NULL; all three outputs NULL; sigma_color > 0 on a film without
+ * moments; a pass of this film in flight; in the device form a guide or an output that is not 8-byte aligned device memory of the context's device reaching
+ * far enough). All but the last come before the first HIP call.
+ * PORTRAYER_DENOISE_TILE=0|1 (read per call) selects the direct or the LDS-tiled form of the level kernel; both compute the same bits. */
+#define PT_DENOISE_SAME_NODE 1u
+typedef struct {
+    int32_t iterations;         /* 1 .. 8: filter levels, level l with step 1 << l                                */
+    uint32_t flags;             /* PT_DENOISE_SAME_NODE: taps on another node get weight 0                        */
+    double sigma_color;         /* >= 0: colour tolerance in standard errors; 0 = no colour weight               */
+    double sigma_plane;         /* >= 0: plane-distance tolerance in world units; 0 = off                        */
+    int32_t normal_power_log2;  /* -1 .. 7: the clamped normal dot raised to 2^k; -1 = off                        */
+} pt_denoise_params;
+typedef struct { const double *position; const double *normal; const int32_t *node; } pt_denoise_guides;
+/* Guides and outputs in DEVICE memory, queued on `hip_stream` without synchronising the host (behind a finished add on the same stream it sees its samples). */
+int pt_film_denoise_device(pt_context *ctx, pt_film *film, const pt_denoise_params *params, const pt_denoise_guides *d_guides, void *d_rgb, double *d_linear, double *d_variance,
+                           void *hip_stream);
+/* Host buffers, synchronous. */
+int pt_film_denoise(pt_context *ctx, pt_film *film, const pt_denoise_params *params, const pt_denoise_guides *host_guides, uint8_t *rgb, double *linear, double *variance);
+
 /* Bytes of one rank's compact tile buffer for a slice split over tile_ranks ranks (equal for all ranks). */
 uint64_t pt_compact_bytes(const pt_render_params *params);
 /* Scatters the gathered compact buffers (rank-major) into a row-major image on the device. */
@@ -639,6 +683,11 @@ int pt_test_film_plan_host(uint32_t width, uint32_t height, const pt_rect *slice
 /* The same list by the plan KERNELS of `ctx`'s device (host `budget` in, list copied back; nothing is sampled, no scene or film needed). */
 int pt_test_film_plan(pt_context *ctx, uint32_t width, uint32_t height, const pt_rect *slice, const uint32_t *budget, uint32_t max_samples, uint32_t round, uint32_t *list, uint32_t cap,
                       uint32_t *n_out);
+/* Host-side run (no GPU, no context) of pt_film_denoise's levels through the functions its kernels call, from a level-0 input the caller supplies: `linear`
+ * (width x height x 3), `variance` (width x height; NULL = zeros, with sigma_color == 0 only), `counts` and the guides, all host memory. out_linear and
+ * out_variance are each optional (not both NULL); pixels with count == 0 are left untouched. */
+int pt_test_denoise_host(uint32_t width, uint32_t height, const pt_denoise_params *params, const double *linear, const double *variance, const uint32_t *counts,
+                         const pt_denoise_guides *guides, double *out_linear, double *out_variance);
 
 #ifdef __cplusplus
 }

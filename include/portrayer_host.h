@@ -181,6 +181,12 @@ int ph_renderer_film_add_map(ph_renderer *r, ph_film *film, const double camera[
 int ph_renderer_film_error(ph_renderer *r, ph_film *film, double *err);
 int ph_renderer_film_refine(ph_renderer *r, ph_film *film, const double camera[10], const double *background, const pt_film_map_params *sampling, const pt_film_refine_params *refine,
                             uint32_t max_passes, uint64_t out[3], double *kernel_ms);
+/* The film, denoised (pt_film_denoise: an a-trous filter over the resolved mean; lossy, the film's state is not written). With `guides` (host arrays laid out as
+ * pt_aov writes them) this is the library's host path and `camera` may be NULL. With guides == NULL the guides are what is under each pixel centre for `camera`:
+ * a primary-visibility pass into device buffers kept with the film handle, then the filter, on the device throughout; only the outputs asked for are copied out.
+ * rgb (width x height x 3 u8), linear (x 3 f64) and variance (f64) are each optional, not all NULL; pixels without samples keep what they hold. */
+int ph_renderer_film_denoise(ph_renderer *r, ph_film *film, const double camera[10], const pt_denoise_params *params, const pt_denoise_guides *guides, uint8_t *rgb, double *linear,
+                             double *variance);
 
 /* Image::new + Image::render + Image::save with the crate's defaults (env SAMPLES, KD_DEPTH) on an
  * example scene: exercises the whole C++ API the way the reference's main() does. */

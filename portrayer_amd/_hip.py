@@ -141,6 +141,19 @@ class PtFilmRefineParams(C.Structure):
     _fields_ = [("slice", PtRect), ("threshold", C.c_double), ("min_count", C.c_uint32), ("max_count", C.c_uint32), ("step", C.c_uint32)]
 
 
+DENOISE_SAME_NODE = 1  # PT_DENOISE_SAME_NODE
+
+
+class PtDenoiseParams(C.Structure):
+    """pt_denoise_params: the levels of the a-trous filter and its three edge-stopping weights (0 / -1 switch one off)."""
+    _fields_ = [("iterations", C.c_int32), ("flags", C.c_uint32), ("sigma_color", C.c_double), ("sigma_plane", C.c_double), ("normal_power_log2", C.c_int32)]
+
+
+class PtDenoiseGuides(C.Structure):
+    """pt_denoise_guides: full images laid out as pt_aov writes them - position and normal (H, W, 3) f64, node (H, W) i32; host or device pointers."""
+    _fields_ = [("position", C.c_void_p), ("normal", C.c_void_p), ("node", C.c_void_p)]
+
+
 class PtStats(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("primary", "shadow", "reflect", "refract", "depth11_skipped", "hits", "n_inner", "n_leaf",
                                           "n_analytic", "n_tri", "n_bbox", "kd_plane_miss", "stack_overflow")] + \
@@ -166,7 +179,8 @@ EXPORTS = ["pt_abi_version", "pt_device_count", "pt_context_create", "pt_context
            "pt_film_create", "pt_film_destroy", "pt_film_reset", "pt_film_add", "pt_film_add_device", "pt_film_resolve", "pt_film_resolve_device", "pt_film_counts",
            "pt_test_film_fold_host",
            "pt_film_create_moments", "pt_film_add_map", "pt_film_add_map_device", "pt_film_error", "pt_film_error_device", "pt_film_budget_device",
-           "pt_test_film_moments_host", "pt_test_film_plan_host", "pt_test_film_plan"]
+           "pt_test_film_moments_host", "pt_test_film_plan_host", "pt_test_film_plan",
+           "pt_film_denoise", "pt_film_denoise_device", "pt_test_denoise_host"]
 
 
 def header_functions():
@@ -351,6 +365,12 @@ def lib() -> C.CDLL:
         l.pt_test_film_moments_host.argtypes = [C.c_uint32, _dp, _u32p, C.c_uint32, _dp, _dp, _dp]
         l.pt_test_film_plan_host.restype = C.c_int
         l.pt_test_film_plan_host.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(PtRect), _u32p, C.c_uint32, C.c_uint32, _u32p, C.c_uint32, _u32p]
+        l.pt_film_denoise.restype = C.c_int
+        l.pt_film_denoise.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(PtDenoiseParams), C.POINTER(PtDenoiseGuides), _u8p, _dp, _dp]
+        l.pt_film_denoise_device.restype = C.c_int
+        l.pt_film_denoise_device.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(PtDenoiseParams), C.POINTER(PtDenoiseGuides), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        l.pt_test_denoise_host.restype = C.c_int
+        l.pt_test_denoise_host.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(PtDenoiseParams), _dp, _dp, _u32p, C.POINTER(PtDenoiseGuides), _dp, _dp]
         l.pt_test_film_plan.restype = C.c_int
         l.pt_test_film_plan.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(PtRect), _u32p, C.c_uint32, C.c_uint32, _u32p, C.c_uint32, _u32p]
         _lib = l

@@ -21,6 +21,7 @@
 #include "pt_radiance_inst.h"
 #include "pt_film_inst.h"
 #include "pt_film_map_inst.h"
+#include "pt_denoise.h"
 #include "pt_render_inst.h"
 #include "pt_shade.h"
 
@@ -386,11 +387,15 @@ struct pt_film {
     // pt_film_create_moments: the second moment per pixel. pt_film_add_map: the host map's device copy, the list of a launch round (its length in the
     // word in front of it), the plan's block sums. pt_film_error: the host path's device buffer.
     PtBuf q, budget, list, plan_work, out_err;
+    // pt_film_denoise: the two work buffers of its levels (32 bytes per pixel each, allocated by the first denoise); the host path's device copies of the
+    // guides and of the variance it returns.
+    PtBuf dn_work[2], dn_position, dn_normal, dn_node, out_var;
     bool moments = false;
     std::vector<uint32_t> counts;
 };
 static void pt_film_free(pt_film* f) {
-    for (PtBuf* b : {&f->total, &f->partial, &f->count, &f->staging, &f->bg, &f->out_rgb, &f->out_linear, &f->q, &f->budget, &f->list, &f->plan_work, &f->out_err}) if (b->p) hipFree(b->p);
+    for (PtBuf* b : {&f->total, &f->partial, &f->count, &f->staging, &f->bg, &f->out_rgb, &f->out_linear, &f->q, &f->budget, &f->list, &f->plan_work, &f->out_err,
+                     &f->dn_work[0], &f->dn_work[1], &f->dn_position, &f->dn_normal, &f->dn_node, &f->out_var}) if (b->p) hipFree(b->p);
     delete f;
 }
 
@@ -3150,6 +3155,105 @@ extern "C" int pt_film_budget_device(pt_context* c, pt_film* f, const pt_film_re
     PT_HIP(c, hipMemsetAsync(d_summary, 0, 16, (hipStream_t)hip_stream));
     PT_HIP(c, pt_film_budget_launch(r, p->threshold, p->min_count, p->max_count, p->step, (const double*)f->total.p, (const double*)f->partial.p, (const uint32_t*)f->count.p, (const double*)f->q.p,
                                     d_budget, (unsigned long long*)d_summary, (hipStream_t)hip_stream));
+    return PT_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Film, denoised: the a-trous filter over the resolved mean (pt_denoise.h, pt_denoise.hip)
+// ------------------------------------------------------------------------------------------------
+// Everything that can be refused without a HIP call, in the order the header gives. Bookkeeping is pt_film_resolve_device's, and the call is refused while a
+// pass of the film is open.
+static int pt_film_denoise_check(pt_context* c, pt_film* f, const pt_denoise_params* p, const pt_denoise_guides* g, const void* rgb, const void* linear, const void* variance, const char* who) {
+    if (!c || !f || !p || !g) return pt_fail(c, PT_ERR_ARGUMENT, std::string(who) + ": NULL context, film, params or guides");
+    int rc = pt_film_handle(c, f, true, who);
+    if (rc) return rc;
+    if (const char* why = pt_denoise_check(p, g)) return pt_fail(c, PT_ERR_ARGUMENT, std::string(who) + ": " + why);
+    if (!rgb && !linear && !variance) return pt_fail(c, PT_ERR_ARGUMENT, std::string(who) + ": none of rgb, linear and variance");
+    if (!f->moments && p->sigma_color > 0.0) return pt_fail(c, PT_ERR_ARGUMENT, std::string(who) + ": the film keeps no second moment (pt_film_create_moments): sigma_color must be 0");
+    return PT_OK;
+}
+
+// The kernels of one denoise, queued on `stream`: seed, a level kernel per iteration between the film's two work buffers, finish. The context's device is current.
+static int pt_film_denoise_queue(pt_context* c, pt_film* f, const pt_denoise_params* p, const pt_denoise_guides& g, uint8_t* d_rgb, double* d_linear, double* d_variance, hipStream_t stream) {
+    const size_t n = f->counts.size();
+    int rc;
+    if ((rc = pt_reserve(c, f->dn_work[0], n * 32)) || (rc = pt_reserve(c, f->dn_work[1], n * 32))) return rc;
+    bool tiled = true;  // the LDS-tiled form, the faster one at 5 levels by more than three spreads (profiles/denoise/notes.md), unless the switch says otherwise
+    if (const char* e = getenv("PORTRAYER_DENOISE_TILE")) tiled = atoi(e) > 0;
+    const uint32_t* count = (const uint32_t*)f->count.p;
+    PT_HIP(c, pt_denoise_seed_launch(f->width, f->height, (const double*)f->total.p, (const double*)f->partial.p, count, f->moments ? (const double*)f->q.p : nullptr, (double*)f->dn_work[0].p, stream));
+    PtDenoiseLevelArgs a;
+    a.k = pt_denoise_const(*p);
+    a.width = f->width; a.height = f->height;
+    a.count = count;
+    a.position = g.position; a.normal = g.normal; a.node = g.node;
+    int cur = 0;
+    for (int l = 0; l < p->iterations; l++, cur ^= 1) {
+        a.step = 1u << l;
+        a.in = (const double*)f->dn_work[cur].p;
+        a.out = (double*)f->dn_work[cur ^ 1].p;
+        PT_HIP(c, pt_denoise_level_launch(a, tiled, stream));
+    }
+    PT_HIP(c, pt_denoise_finish_launch(f->width, f->height, (const double*)f->dn_work[cur].p, count, d_rgb, d_linear, d_variance, stream));
+    return PT_OK;
+}
+
+extern "C" int pt_film_denoise_device(pt_context* c, pt_film* f, const pt_denoise_params* p, const pt_denoise_guides* d_guides, void* d_rgb, double* d_linear, double* d_variance,
+                                      void* hip_stream) {
+    int rc = pt_film_denoise_check(c, f, p, d_guides, d_rgb, d_linear, d_variance, "pt_film_denoise_device");
+    if (rc) return rc;
+    PT_HIP(c, hipSetDevice(c->device));
+    const uint64_t n = f->counts.size();
+    const bool want_n = p->normal_power_log2 >= 0 || p->sigma_plane > 0.0, want_pos = p->sigma_plane > 0.0;
+    pt_denoise_guides g = {want_pos ? d_guides->position : nullptr, want_n ? d_guides->normal : nullptr, d_guides->node};  // (a guide no weight reads is not looked at)
+    if ((rc = pt_check_device_pointer(c, g.node, n * 4, "pt_film_denoise_device: the node guide"))) return rc;
+    if (g.normal && (rc = pt_check_device_pointer(c, g.normal, n * 24, "pt_film_denoise_device: the normal guide"))) return rc;
+    if (g.position && (rc = pt_check_device_pointer(c, g.position, n * 24, "pt_film_denoise_device: the position guide"))) return rc;
+    if (d_rgb && (rc = pt_check_device_pointer(c, d_rgb, n * 3, "pt_film_denoise_device: rgb"))) return rc;
+    if (d_linear && (rc = pt_check_device_pointer(c, d_linear, n * 24, "pt_film_denoise_device: linear"))) return rc;
+    if (d_variance && (rc = pt_check_device_pointer(c, d_variance, n * 8, "pt_film_denoise_device: variance"))) return rc;
+    return pt_film_denoise_queue(c, f, p, g, (uint8_t*)d_rgb, d_linear, d_variance, (hipStream_t)hip_stream);
+}
+
+extern "C" int pt_film_denoise(pt_context* c, pt_film* f, const pt_denoise_params* p, const pt_denoise_guides* host_guides, uint8_t* rgb, double* linear, double* variance) {
+    int rc = pt_film_denoise_check(c, f, p, host_guides, rgb, linear, variance, "pt_film_denoise");
+    if (rc) return rc;
+    PT_HIP(c, hipSetDevice(c->device));
+    const size_t n = f->counts.size();
+    const bool want_n = p->normal_power_log2 >= 0 || p->sigma_plane > 0.0, want_pos = p->sigma_plane > 0.0;
+    pt_denoise_guides g = {nullptr, nullptr, nullptr};
+    if ((rc = pt_reserve(c, f->dn_node, n * 4))) return rc;
+    PT_HIP(c, hipMemcpy(f->dn_node.p, host_guides->node, n * 4, hipMemcpyHostToDevice));
+    g.node = (const int32_t*)f->dn_node.p;
+    if (want_n) {
+        if ((rc = pt_reserve(c, f->dn_normal, n * 24))) return rc;
+        PT_HIP(c, hipMemcpy(f->dn_normal.p, host_guides->normal, n * 24, hipMemcpyHostToDevice));
+        g.normal = (const double*)f->dn_normal.p;
+    }
+    if (want_pos) {
+        if ((rc = pt_reserve(c, f->dn_position, n * 24))) return rc;
+        PT_HIP(c, hipMemcpy(f->dn_position.p, host_guides->position, n * 24, hipMemcpyHostToDevice));
+        g.position = (const double*)f->dn_position.p;
+    }
+    // pixels without samples keep the caller's bytes: where there are any, the caller's buffers go to the device first (pt_film_resolve)
+    PT_HIP(c, hipMemcpy(f->counts.data(), f->count.p, n * 4, hipMemcpyDeviceToHost));  // (behind a device map the host's copy is an upper bound)
+    const bool holes = std::find(f->counts.begin(), f->counts.end(), 0u) != f->counts.end();
+    if (rgb) {
+        if ((rc = pt_reserve(c, f->out_rgb, n * 3))) return rc;
+        if (holes) PT_HIP(c, hipMemcpy(f->out_rgb.p, rgb, n * 3, hipMemcpyHostToDevice));
+    }
+    if (linear) {
+        if ((rc = pt_reserve(c, f->out_linear, n * 24))) return rc;
+        if (holes) PT_HIP(c, hipMemcpy(f->out_linear.p, linear, n * 24, hipMemcpyHostToDevice));
+    }
+    if (variance) {
+        if ((rc = pt_reserve(c, f->out_var, n * 8))) return rc;
+        if (holes) PT_HIP(c, hipMemcpy(f->out_var.p, variance, n * 8, hipMemcpyHostToDevice));
+    }
+    if ((rc = pt_film_denoise_queue(c, f, p, g, rgb ? (uint8_t*)f->out_rgb.p : nullptr, linear ? (double*)f->out_linear.p : nullptr, variance ? (double*)f->out_var.p : nullptr, nullptr))) return rc;
+    if (rgb) PT_HIP(c, hipMemcpy(rgb, f->out_rgb.p, n * 3, hipMemcpyDeviceToHost));
+    if (linear) PT_HIP(c, hipMemcpy(linear, f->out_linear.p, n * 24, hipMemcpyDeviceToHost));
+    if (variance) PT_HIP(c, hipMemcpy(variance, f->out_var.p, n * 8, hipMemcpyDeviceToHost));
     return PT_OK;
 }
 

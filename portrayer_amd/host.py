@@ -19,7 +19,7 @@ _dp, _ip, _up, _u64p, _u8p = H._dp, H._ip, H._up, H._u64p, H._u8p
 
 EXPORTS = ["ph_last_error", "ph_scene_create", "ph_example_scene", "ph_scene_destroy", "ph_scene_counts", "ph_scene_export", "ph_scene_export_textures",
            "ph_scene_flatten", "ph_scene_kdtree", "ph_camera", "ph_obj_load", "ph_renderer_create", "ph_renderer_destroy",
-           "ph_renderer_context", "ph_renderer_ranks", "ph_renderer_node", "ph_renderer_prepare_ms", "ph_renderer_render", "ph_renderer_aov", "ph_renderer_rays", "ph_renderer_segments", "ph_renderer_radiance", "ph_renderer_film_create", "ph_renderer_film_destroy", "ph_renderer_film_reset", "ph_renderer_film_add", "ph_renderer_film_resolve", "ph_renderer_film_counts", "ph_renderer_film_create_moments", "ph_renderer_film_add_map", "ph_renderer_film_error", "ph_renderer_film_refine", "ph_renderer_update", "ph_scene_same_structure", "ph_renderer_deform", "ph_scene_same_topology", "ph_renderer_deform_device", "ph_renderer_mesh_count", "ph_renderer_mesh_vertices", "ph_example_render_to_png", "ph_png_read", "ph_png_write", "ph_image_read", "ph_scene_graph"]
+           "ph_renderer_context", "ph_renderer_ranks", "ph_renderer_node", "ph_renderer_prepare_ms", "ph_renderer_render", "ph_renderer_aov", "ph_renderer_rays", "ph_renderer_segments", "ph_renderer_radiance", "ph_renderer_film_create", "ph_renderer_film_destroy", "ph_renderer_film_reset", "ph_renderer_film_add", "ph_renderer_film_resolve", "ph_renderer_film_counts", "ph_renderer_film_create_moments", "ph_renderer_film_add_map", "ph_renderer_film_error", "ph_renderer_film_refine", "ph_renderer_film_denoise", "ph_renderer_update", "ph_scene_same_structure", "ph_renderer_deform", "ph_scene_same_topology", "ph_renderer_deform_device", "ph_renderer_mesh_count", "ph_renderer_mesh_vertices", "ph_example_render_to_png", "ph_png_read", "ph_png_write", "ph_image_read", "ph_scene_graph"]
 
 
 class PortrayerHostError(RuntimeError):
@@ -100,6 +100,8 @@ def lib() -> C.CDLL:
         l.ph_renderer_film_error.restype = C.c_int; l.ph_renderer_film_error.argtypes = [vp, vp, _dp]
         l.ph_renderer_film_refine.restype = C.c_int
         l.ph_renderer_film_refine.argtypes = [vp, vp, _dp, _dp, C.POINTER(H.PtFilmMapParams), C.POINTER(H.PtFilmRefineParams), C.c_uint32, _u64p, _dp]
+        l.ph_renderer_film_denoise.restype = C.c_int
+        l.ph_renderer_film_denoise.argtypes = [vp, vp, _dp, C.POINTER(H.PtDenoiseParams), C.POINTER(H.PtDenoiseGuides), _u8p, _dp, _dp]
         l.ph_renderer_update.restype = C.c_int; l.ph_renderer_update.argtypes = [vp, vp]
         l.ph_scene_same_structure.restype = C.c_int; l.ph_scene_same_structure.argtypes = [vp, vp, C.c_char_p, C.c_size_t]
         l.ph_renderer_deform.restype = C.c_int; l.ph_renderer_deform.argtypes = [vp, vp, C.c_int]
@@ -440,6 +442,63 @@ class Film:
                 raise ValueError("linear_into must be a C-contiguous float64 array of shape %r" % ((self.height, self.width, 3),))
         _check(lib().ph_renderer_film_resolve(self._r._h, self._h, _p(rgb, _u8p), _p(linear, _dp)), "ph_renderer_film_resolve")
         return rgb, linear
+
+    def denoise(self, cam10, iterations: int = 5, sigma_color: float = 2.0, sigma_plane: float = 0.0, normal_power: Optional[int] = 32, same_node: bool = False,
+                want_variance: bool = False, guides: Optional[dict] = None, into: Optional[np.ndarray] = None, linear_into: Optional[np.ndarray] = None,
+                variance_into: Optional[np.ndarray] = None):
+        """(rgb, linear[, variance]): the film's mean after `iterations` levels of an edge-avoiding a-trous filter (pt_film_denoise) - a lossy read, the film
+        itself is not changed and resolve() keeps its promise. The filter is steered by what is under each pixel for camera `cam10` (a primary-visibility
+        pass on the device) - or by the caller's `guides`, a dict of "node" (H, W) int32, "normal" and "position" (H, W, 3) float64 as Renderer.aov() returns
+        them, of which only what the weights read is needed - and by the film's noise estimate: sigma_color is the colour tolerance in standard errors (0: off;
+        a film without moments takes 0 only), sigma_plane the plane-distance tolerance in world units (0: off), normal_power the power of two from 1 to 128
+        the clamped dot of the normals is raised to (None: off), same_node=True keeps every tap on the centre's node. variance is (H, W) float64, the filtered
+        variance of r + g + b. Pixels without samples keep what `into` / `linear_into` / `variance_into` hold (zeros when the arrays are made here)."""
+        iterations = self._integer("iterations", iterations, 1, 8)
+        sig = []
+        for name, v in (("sigma_color", sigma_color), ("sigma_plane", sigma_plane)):
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not 0.0 <= float(v) < float("inf"):
+                raise ValueError("%s must be a finite number >= 0, got %r" % (name, v))
+            sig.append(float(v))
+        if normal_power is None:
+            npl2 = -1
+        else:
+            if isinstance(normal_power, bool) or not isinstance(normal_power, (int, np.integer)) or int(normal_power) not in (1, 2, 4, 8, 16, 32, 64, 128):
+                raise ValueError("normal_power must be a power of two from 1 to 128 or None, got %r" % (normal_power,))
+            npl2 = int(normal_power).bit_length() - 1
+        if sig[0] > 0.0 and not self.moments:
+            raise ValueError("sigma_color > 0 needs a film that keeps moments: Renderer.film(w, h, moments=True)")
+        shape3, shape1 = (self.height, self.width, 3), (self.height, self.width)
+        g = None
+        if guides is not None:
+            if not isinstance(guides, dict):
+                raise ValueError("guides must be a dict with 'node' and, where the weights read them, 'normal' and 'position'")
+            needed = ["node"] + (["normal"] if npl2 >= 0 or sig[1] > 0.0 else []) + (["position"] if sig[1] > 0.0 else [])
+            g, keep = H.PtDenoiseGuides(), []
+            for name in needed:
+                a = guides.get(name)
+                dtype, shape = (np.int32, shape1) if name == "node" else (np.float64, shape3)
+                if not isinstance(a, np.ndarray) or a.dtype != dtype or a.shape != shape:
+                    raise ValueError("guides[%r] must be a %s array of shape %r" % (name, np.dtype(dtype).name, shape))
+                a = np.ascontiguousarray(a)
+                keep.append(a)
+                setattr(g, name, a.ctypes.data)
+        out = []
+        for name, a, dtype, shape, wanted in (("into", into, np.uint8, shape3, True), ("linear_into", linear_into, np.float64, shape3, True),
+                                              ("variance_into", variance_into, np.float64, shape1, want_variance or variance_into is not None)):
+            if not wanted:
+                out.append(None)
+                continue
+            a = a if a is not None else np.zeros(shape, dtype=dtype)
+            if not isinstance(a, np.ndarray) or a.shape != shape or a.dtype != dtype or not a.flags.c_contiguous:
+                raise ValueError("%s must be a C-contiguous %s array of shape %r" % (name, np.dtype(dtype).name, shape))
+            out.append(a)
+        c = None if cam10 is None else np.ascontiguousarray(cam10, dtype=np.float64)
+        if g is None and (c is None or c.shape != (10,)):
+            raise ValueError("cam10 must hold the camera's 10 numbers unless guides are given")
+        p = H.PtDenoiseParams(iterations, H.DENOISE_SAME_NODE if same_node else 0, sig[0], sig[1], npl2)
+        _check(lib().ph_renderer_film_denoise(self._r._h, self._h, _p(c, _dp), C.byref(p), C.byref(g) if g is not None else None, _p(out[0], _u8p), _p(out[1], _dp), _p(out[2], _dp)),
+               "ph_renderer_film_denoise")
+        return (out[0], out[1], out[2]) if out[2] is not None else (out[0], out[1])
 
     def counts(self) -> np.ndarray:
         """(H, W) uint32: samples every pixel holds."""

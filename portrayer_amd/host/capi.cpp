@@ -635,6 +635,9 @@ extern "C" int ph_renderer_radiance(ph_renderer* r, const pt_radiance_params* p,
 struct ph_film {
     pt_film* f = nullptr;
     uint32_t width = 0, height = 0;
+    // ph_renderer_film_denoise: the guides its aov pass writes (position, normal, node) and the device copies of its three outputs, allocated on first use
+    void* d_guide[3] = {nullptr, nullptr, nullptr};
+    void* d_out[3] = {nullptr, nullptr, nullptr};
 };
 static int film_rc(ph_renderer* r, int rc) {
     if (rc == PT_OK) return PH_OK;
@@ -661,7 +664,9 @@ extern "C" int ph_renderer_film_destroy(ph_renderer* r, ph_film* film) {
     if (!r || !film) return bad("null argument");
     return guarded([&]() -> int {
         int rc = film_rc(r, pt_film_destroy(r->r->context(), film->f));
-        if (rc == PH_OK) delete film;
+        if (rc != PH_OK) return rc;
+        for (void* d : {film->d_guide[0], film->d_guide[1], film->d_guide[2], film->d_out[0], film->d_out[1], film->d_out[2]}) if (d) pt_device_free(r->r->context(), d);
+        delete film;
         return rc;
     });
 }
@@ -761,6 +766,48 @@ extern "C" int ph_renderer_film_refine(ph_renderer* r, ph_film* film, const doub
         if (rc != PH_OK) return rc;
         out[0] = passes; out[1] = samples; out[2] = summary[0];
         if (kernel_ms) *kernel_ms = ms_all;
+        return PH_OK;
+    });
+}
+
+// The film, denoised (pt_film_denoise): with the caller's guides the library's host path; without, the guides come from a primary-visibility pass at the pixel
+// centres for `camera` and never leave the device - pt_aov_device into buffers kept with the handle, pt_aov_finish, pt_film_denoise_device, the outputs copied out.
+extern "C" int ph_renderer_film_denoise(ph_renderer* r, ph_film* film, const double camera[10], const pt_denoise_params* p, const pt_denoise_guides* guides, uint8_t* rgb, double* linear,
+                                        double* variance) {
+    if (!r || !film || !p || (!guides && !camera) || (!rgb && !linear && !variance)) return bad("null argument");
+    return guarded([&]() -> int {
+        pt_context* c = r->r->context();
+        if (guides) return film_rc(r, pt_film_denoise(c, film->f, p, guides, rgb, linear, variance));
+        const size_t n = (size_t)film->width * film->height;
+        const bool want_n = p->normal_power_log2 >= 0 || p->sigma_plane > 0.0, want_pos = p->sigma_plane > 0.0;
+        const size_t guide_bytes[3] = {n * 24, n * 24, n * 4}, out_bytes[3] = {n * 3, n * 24, n * 8};
+        const bool guide_wanted[3] = {want_pos, want_n, true};
+        void* host_out[3] = {rgb, linear, variance};
+        int rc = PT_OK;
+        for (int k = 0; k < 3 && rc == PT_OK; k++) {
+            if (guide_wanted[k] && !film->d_guide[k]) rc = pt_device_alloc(c, guide_bytes[k], &film->d_guide[k]);
+            if (rc == PT_OK && host_out[k] && !film->d_out[k]) rc = pt_device_alloc(c, out_bytes[k], &film->d_out[k]);
+        }
+        if (rc != PT_OK) return film_rc(r, rc);
+        // pixels without samples keep the caller's bytes: where there are any, the caller's buffers go to the device first
+        std::vector<uint32_t> counts(n);
+        if ((rc = pt_film_counts(c, film->f, counts.data()))) return film_rc(r, rc);
+        if (std::find(counts.begin(), counts.end(), 0u) != counts.end())
+            for (int k = 0; k < 3; k++)
+                if (host_out[k] && (rc = pt_copy_to_device(c, film->d_out[k], host_out[k], out_bytes[k]))) return film_rc(r, rc);
+        pt_camera pc = detail::Camera(camera_from(camera), (double)film->width, (double)film->height).to_abi();  // the camera a render of this size gets
+        pt_aov_params ap;
+        ap.width = film->width; ap.height = film->height;
+        ap.slice.x0 = 0; ap.slice.y0 = 0; ap.slice.x1 = film->width - 1; ap.slice.y1 = film->height - 1;
+        ap.offset[0] = 0.5; ap.offset[1] = 0.5;
+        pt_aov_buffers ab = {nullptr, want_pos ? (double*)film->d_guide[0] : nullptr, want_n ? (double*)film->d_guide[1] : nullptr, (int32_t*)film->d_guide[2], nullptr, nullptr};
+        if ((rc = pt_aov_device(c, &pc, &ap, &ab, nullptr))) return film_rc(r, rc);
+        if ((rc = pt_aov_finish(c, nullptr))) return film_rc(r, rc);
+        pt_denoise_guides dg = {ab.position, ab.normal, ab.node};
+        if ((rc = pt_film_denoise_device(c, film->f, p, &dg, rgb ? film->d_out[0] : nullptr, linear ? (double*)film->d_out[1] : nullptr, variance ? (double*)film->d_out[2] : nullptr, nullptr)))
+            return film_rc(r, rc);
+        for (int k = 0; k < 3; k++)
+            if (host_out[k] && (rc = pt_copy_from_device(c, host_out[k], film->d_out[k], out_bytes[k]))) return film_rc(r, rc);
         return PH_OK;
     });
 }

@@ -120,6 +120,14 @@ pub struct PtFilmRefineParams {            // pt_film_refine_params: the budget 
     pub slice: PtRect, pub threshold: f64, pub min_count: u32, pub max_count: u32, pub step: u32,
 }
 #[repr(C)]
+pub struct PtDenoiseParams {               // pt_denoise_params: the levels of pt_film_denoise's a-trous filter and its edge-stopping weights (0 / -1 = off); flags: PT_DENOISE_SAME_NODE = 1
+    pub iterations: i32, pub flags: u32, pub sigma_color: f64, pub sigma_plane: f64, pub normal_power_log2: i32,
+}
+#[repr(C)]
+pub struct PtDenoiseGuides {               // pt_denoise_guides: full images as pt_aov writes them; node always, normal / position where a weight reads them
+    pub position: *const f64, pub normal: *const f64, pub node: *const i32,
+}
+#[repr(C)]
 pub struct PtRaysBuffers {                 // pt_rays_buffers: each optional (null = not wanted), n entries, indexed like the rays
     pub t: *mut f64, pub position: *mut f64, pub normal: *mut f64, pub node: *mut i32, pub sub: *mut i32, pub material: *mut i32, pub occluded: *mut u8,
 }
@@ -195,6 +203,11 @@ extern "C" {
     pub fn pt_film_error_device(ctx: *mut PtContext, film: *mut PtFilm, d_err: *mut f64, hip_stream: *mut c_void) -> c_int;
     pub fn pt_film_budget_device(ctx: *mut PtContext, film: *mut PtFilm, params: *const PtFilmRefineParams, d_budget: *mut u32, d_summary: *mut u64,
                                  hip_stream: *mut c_void) -> c_int;
+    // the film, denoised: an a-trous filter over the resolved mean, guided by aov buffers and the film's noise estimate; lossy, the film is not written
+    pub fn pt_film_denoise(ctx: *mut PtContext, film: *mut PtFilm, params: *const PtDenoiseParams, host_guides: *const PtDenoiseGuides, rgb: *mut u8, linear: *mut f64,
+                           variance: *mut f64) -> c_int;
+    pub fn pt_film_denoise_device(ctx: *mut PtContext, film: *mut PtFilm, params: *const PtDenoiseParams, d_guides: *const PtDenoiseGuides, d_rgb: *mut c_void,
+                                  d_linear: *mut f64, d_variance: *mut f64, hip_stream: *mut c_void) -> c_int;
     pub fn pt_context_stream(ctx: *mut PtContext, slot: c_int) -> *mut c_void;
     pub fn pt_context_next_slot(ctx: *const PtContext) -> c_int;
     // one render call over the GPUs of a node (one context per GPU, one RCCL gather)
