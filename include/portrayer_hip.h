@@ -669,6 +669,10 @@ int pt_test_work_items(const pt_render_params *params, uint32_t *sample_count, u
  * form for mixed signs does, bit 2 the wavefront form for the ray's own octant does, bit 3 the two children of a wavefront form disagree. */
 int pt_test_raypk(uint64_t n, int body, const double *origins, const double *directions, const double *t_max, const float *box_lo, const float *box_hi,
                   int32_t *verdict, float *t_near, float *t_far);
+/* Host-side run (no GPU, no context) of the shadow rays' certain-occlusion test. Case i: a node of primitive `type` (the PT_* tags of the scene export: 0 sphere,
+ * 5 cube have a ball; every other type is never certain) with rows 0..2 of its forward and inverse matrices in fwd[12i..] and inv[12i..], a shaded point P[3i..] and a light position L[3i..].
+ * out_certain[i]: the single-precision test says the shadow ray certainly ends in the node; out_exact_hit[i]: the exact test of that node for that ray says so. */
+int pt_test_certain_shadow(uint64_t n, int type, const double *fwd, const double *inv, const double *P, const double *L, int32_t *out_certain, int32_t *out_exact_hit);
 /* Host-side run (no GPU, no context) of the film's running sum: `samples` (n x 3) given to one pixel in n_cuts consecutive adds of cuts[k] samples each
  * (their sum must be n), through the functions the film's fold and resolve kernels call. out_sum: what resolve divides by n. */
 int pt_test_film_fold_host(uint32_t n, const double *samples, const uint32_t *cuts, uint32_t n_cuts, double out_sum[3]);

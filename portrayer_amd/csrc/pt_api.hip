@@ -245,6 +245,16 @@ __global__ void __launch_bounds__(256) pt_eye_table_kernel(const double* __restr
     o[8] = m[8]; o[9] = m[9]; o[10] = m[10]; o[11] = e.z;
 }
 
+// The launch's certain-shadow table (behind the eye table, PtRenderArgs::eye_tab), one thread per flattened node: a ball inside the node's primitive as four floats (pt_certain_ball,
+// pt_certain.h). Filled in front of every launch that has an occluder table, like the eye table: pt_scene_update and pt_scene_deform move nodes between launches,
+// and two frames in flight have a slot each.
+__global__ void __launch_bounds__(256) pt_certain_table_kernel(const uint32_t* __restrict__ info, const double* __restrict__ fwd, const double* __restrict__ inv, float* __restrict__ tab,
+                                                               uint32_t n_nodes) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_nodes) return;
+    pt_certain_ball(info[4 * (size_t)i], fwd + 12 * (size_t)i, inv + 12 * (size_t)i, tab + 4 * (size_t)i);
+}
+
 // ------------------------------------------------------------------------------------------------
 // Context
 // ------------------------------------------------------------------------------------------------
@@ -285,7 +295,8 @@ struct pt_context {
     // profiles/r05/notes.md section 2) - and the next frame's wavefronts take the places they free instead of waiting for the last one.
     struct Slot {
         PtBuf spill, stack_spill, accum, misc;     // misc: work counter + overflow flag (8 B), PtCounters at +256, the work queues behind them
-        PtBuf eye_tab;                             // the launch's eye table (pt_eye_table_kernel): n_nodes x 96 bytes, the slot's own - the other slot's frame has another camera
+        PtBuf eye_tab;                             // the launch's eye table (pt_eye_table_kernel): n_nodes x 96 bytes, the slot's own - the other slot's frame has another camera;
+                                                   // behind it the launch's certain-shadow table (pt_certain_table_kernel): n_nodes x 16 bytes
         hipStream_t stream = nullptr;              // pt_context_stream(ctx, slot): non-blocking, created with the context
         hipEvent_t ev0 = nullptr, ev1 = nullptr;   // around the kernels (pt_stats.kernel_ms)
         hipEvent_t copy_done = nullptr;            // behind the copy into `host`
@@ -1853,6 +1864,29 @@ extern "C" int pt_test_raypk(uint64_t n, int body, const double* origins, const 
     return PT_OK;
 }
 
+// Host-side run (no GPU involved) of the certain-shadow test (pt_certain.h): case i is a node of `type` with the records fwd[12 i ..], inv[12 i ..] (rows 0..2 of its two
+// matrices), a shaded point P[3 i ..] and a light position L[3 i ..]. out_certain[i]: the table routine gave the node a ball and the lane test, on the floats the kernel would
+// hold, says "certainly hit"; out_exact_hit[i]: the reference's own test of that node for the shadow ray {P, (L - P) / |L - P|} over [EPSILON, INF) (pt_ray_to_local,
+// pt_unit_prim_hit). Tests check that certain never comes without exact_hit.
+extern "C" int pt_test_certain_shadow(uint64_t n, int type, const double* fwd, const double* inv, const double* P, const double* L, int32_t* out_certain, int32_t* out_exact_hit) {
+    if (!fwd || !inv || !P || !L || !out_certain || !out_exact_hit || type < 0 || type > 7) return PT_ERR_ARGUMENT;
+    for (uint64_t i = 0; i < n; i++) {
+        float ball[4];
+        pt_certain_ball((uint32_t)type, fwd + 12 * i, inv + 12 * i, ball);
+        const PtVec3 p = pt_v3(P[3 * i], P[3 * i + 1], P[3 * i + 2]), l = pt_v3(L[3 * i], L[3 * i + 1], L[3 * i + 2]);
+        out_certain[i] = ball[3] > 0.0f && pt_certain_lane(ball, (float)p.x, (float)p.y, (float)p.z, (float)l.x, (float)l.y, (float)l.z) ? 1 : 0;
+        PtRay r;
+        r.o = p;
+        const PtVec3 hit_to_light = l - p;
+        r.d = hit_to_light / pt_length(hit_to_light);
+        const PtRay local = pt_ray_to_local(inv + 12 * i, r);
+        double t;
+        uint32_t part = 0;
+        out_exact_hit[i] = pt_unit_prim_hit((uint32_t)type, local, PT_EPSILON, INFINITY, &t, &part) ? 1 : 0;
+    }
+    return PT_OK;
+}
+
 // How a launch's traversal stacks are split between LDS and HBM - one place for the render kernels and the primary-visibility pass (pt_aov_common), whose
 // kernels lay their LDS out with the same code (pt_trace_wave: pt_wave_rows, pt_kd_layout).
 // pt_stack_lds_cap: entries per lane kept in LDS = what `block_budget` bytes of LDS per block leave beside `frame_bytes` of other per-block data (1 KB a row), at most the
@@ -1998,9 +2032,15 @@ static int pt_render_common(pt_context* c, PtRenderArgs& a, bool stats, hipStrea
 #else
     const bool eye_table = false;
 #endif
+    // The certain-shadow table (pt_render_simple.h: CERTAIN) behind it: the flat_scene launches that have an occluder table, whichever kernel runs
+#ifndef PT_NO_CERTAIN_SHADOW
+    const bool certain_table = a.scene.mode == PT_MODE_FLAT_NOMESH && a.scene.n_nodes > 0 && occ_bytes != 0;
+#else
+    const bool certain_table = false;
+#endif
     a.eye_tab = nullptr;
-    if (eye_table) {
-        if ((rc = pt_reserve(c, sl.eye_tab, (size_t)a.scene.n_nodes * 12 * sizeof(double)))) return rc;
+    if (eye_table || certain_table) {
+        if ((rc = pt_reserve(c, sl.eye_tab, (size_t)a.scene.n_nodes * (12 * sizeof(double) + 4 * sizeof(float))))) return rc;
         a.eye_tab = (const double*)sl.eye_tab.p;
     }
     a.spill = (double*)sl.spill.p;
@@ -2027,6 +2067,11 @@ static int pt_render_common(pt_context* c, PtRenderArgs& a, bool stats, hipStrea
         if (eye_table) {  // (behind ev0: pt_stats.kernel_ms pays for it)
             hipLaunchKernelGGL(pt_eye_table_kernel, dim3((a.scene.n_nodes + 255) / 256), dim3(256), 0, stream, a.scene.inv, (double*)sl.eye_tab.p, (uint32_t)a.scene.n_nodes,
                                a.cam.eye[0], a.cam.eye[1], a.cam.eye[2]);
+            PT_HIP(c, hipGetLastError());
+        }
+        if (certain_table) {
+            hipLaunchKernelGGL(pt_certain_table_kernel, dim3((a.scene.n_nodes + 255) / 256), dim3(256), 0, stream, a.scene.info, a.scene.fwd, a.scene.inv, (float*)((double*)sl.eye_tab.p + 12 * (size_t)a.scene.n_nodes),
+                               (uint32_t)a.scene.n_nodes);
             PT_HIP(c, hipGetLastError());
         }
         PT_HIP(c, pt_dispatch(a, stats, c->n_cu, stream, &grid, true));

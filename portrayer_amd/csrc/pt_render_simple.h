@@ -18,6 +18,13 @@
 
 #include "pt_shade.h"
 
+// The certain-shadow test (pt_certain.h) exists in the mesh-free flat_scene kernels only. Objects compiled for another mode (-DPT_INST_MODE) keep a light's set-up as
+// it was, line for line, and so does every object under -DPT_NO_CERTAIN_SHADOW: the two forms compute the same, but the compiler allocates registers differently
+// for them (the chain kernel of scenes with meshes lost 1.8 % to the new form alone).
+#if !defined(PT_NO_CERTAIN_SHADOW) && (!defined(PT_INST_MODE) || PT_INST_MODE == 3)
+#define PT_CERTAIN_SHADOW_FORM 1
+#endif
+
 // doubles at a wave-uniform address through the scalar cache (N = 2 or 4)
 template <int N>
 PT_HD void pt_sload_f64(const double* p, double* out) {
@@ -369,6 +376,7 @@ __global__ void __launch_bounds__(PT_BLOCK, WAVES) pt_render_simple_kernel(PtRen
                 PtVec3 lpos = pt_v3(lp[0], lp[1], lp[2]);
                 const PtVec3 aa = pt_v3(la[0], la[1], lb[0]), ab = pt_v3(lb[1], lb[2], lb[3]);
                 const bool area = !((aa.x == 0.0 && aa.y == 0.0 && aa.z == 0.0) || (ab.x == 0.0 && ab.y == 0.0 && ab.z == 0.0));  // light.rs:51-53 (wave-uniform)
+#if !defined(PT_CERTAIN_SHADOW_FORM)  // a light's set-up as it was before the certain-shadow test, line for line
                 double light_dist = 0.0;
                 if (shaded) {
                     if (area) {  // light.rs:62-70, :87-90
@@ -406,6 +414,97 @@ __global__ void __launch_bounds__(PT_BLOCK, WAVES) pt_render_simple_kernel(PtRen
                     occ.entry = a.occluders + (size_t)tile_local * sc.n_lights + li;
                     occ.back = tile_local >= a.occ_row ? a.occ_row * sc.n_lights : 0u;
                 }
+#else
+                double light_dist = 0.0;
+                if (shaded && area) {  // light.rs:62-70, :87-90
+                    PtItemLane it;
+                    uint32_t x2, y2;
+                    pt_item_lane_fast(a, w, lane, &it, &x2, &y2);
+                    const uint64_t key = pt_rng_key(a.seed, (uint64_t)y * a.width + x);
+                    const uint32_t d0 = CHAIN ? draw : udraw;
+                    double a_coord = 2.0 * pt_rng_draw(key, it.sample, d0) - 1.0;
+                    double b_coord = 2.0 * pt_rng_draw(key, it.sample, d0 + 1) - 1.0;
+                    lpos = lpos + (aa * a_coord + ab * b_coord);
+                    if (CHAIN) draw += 2;
+                }
+                if (area) udraw += 2;
+                // the occluder table's entry of this item's tile for this light (pt_trace_packet): mesh-free scenes, primary hits only
+                PtOccRef occ{nullptr, 0u, li};
+#ifdef PT_OCCLUDER_STATS
+                constexpr bool OCC = !CHAIN && (MODE == PT_MODE_FLAT_NOMESH || MODE == PT_MODE_HIER_NOMESH);
+#else
+                constexpr bool OCC = !STATS && !CHAIN && (MODE == PT_MODE_FLAT_NOMESH || MODE == PT_MODE_HIER_NOMESH);
+#endif
+                if (OCC && a.occluders) {
+                    const uint32_t tile_local = pt_fastdiv(w >> (a.k_log2 + a.c_log2), a.div_groups);
+                    occ.entry = a.occluders + (size_t)tile_local * sc.n_lights + li;
+                    occ.back = tile_local >= a.occ_row ? a.occ_row * sc.n_lights : 0u;
+                }
+                // Where the candidate's inscribed ball (the launch's table, pt_certain.h) settles every shaded lane - the exact ray certainly ends in that node - the
+                // light contributes nothing to this item: no direction, no length, no probe, no walk. The entry is written as the probe would have written it.
+                // Flat_scene semantics only: the hierarchical one has no composed forward record resident to place the balls with. -DPT_NO_CERTAIN_SHADOW: the
+                // code as it was, and no table. The counting build of -DPT_OCCLUDER_STATS=2 evaluates the test and hands the outcome to pt_trace_packet's counts,
+                // nothing else.
+                constexpr bool CERTAIN = OCC && MODE == PT_MODE_FLAT_NOMESH;
+                [[maybe_unused]] PtOccHint hint{0u, 0u, 0u, 0u};
+                if (CERTAIN && occ.entry) {  // (a launch of this mode that has an occluder table has the certain-shadow table: pt_render_common)
+                    const float* const certain_tab = (const float*)(a.eye_tab + 12 * (size_t)sc.n_nodes);
+                    const uint32_t* const entry = (const uint32_t*)pt_uniform_ptr(occ.entry);
+                    hint.own = PT_UNIFORM_U32(entry[0]);
+                    hint.up = occ.back ? PT_UNIFORM_U32(entry[-(long)occ.back]) : 0u;
+                    hint.loaded = 1u;
+                    const uint32_t cand = hint.own ? hint.own : hint.up;
+                    if (cand != 0u) {
+                        const pt_u32x4 rec = pt_sload4(certain_tab + 4 * (size_t)(cand - 1u));
+                        float ball[4];
+#pragma unroll
+                        for (int k = 0; k < 4; k++) ball[k] = __builtin_bit_cast(float, (uint32_t)rec[k]);
+                        if (ball[3] > 0.0f) {
+                            const float pf[3] = {pt_f32_here(sray.o.x), pt_f32_here(sray.o.y), pt_f32_here(sray.o.z)};
+                            const float lx = (float)lpos.x, ly = (float)lpos.y, lz = (float)lpos.z;
+                            const bool c1 = shaded && pt_certain_lane(ball, pf[0], pf[1], pf[2], lx, ly, lz);
+                            const unsigned long long want = PT_BALLOT(shaded), got = PT_BALLOT(c1);
+                            bool settled = want != 0ull && got == want;  // (a wavefront without a shaded lane writes no entry, like the probe)
+                            if (settled) {
+                                hint.certain = 3u;
+                                if (!STATS && hint.own != cand && lane == (unsigned)(__ffsll((long long)__ballot(1)) - 1)) occ.entry[0] = cand;
+                            }
+#if PT_OCCLUDER_STATS + 0 == 2  // (the ball of the tile above for the lanes `own`'s leaves open: counted only - 6 % more walks than the first ball settles, profiles/r09/notes.md - and not built)
+                            else if (hint.own != 0u && hint.up != 0u && hint.up != hint.own) {
+                                const pt_u32x4 rec2 = pt_sload4(certain_tab + 4 * (size_t)(hint.up - 1u));
+                                float ball2[4];
+#pragma unroll
+                                for (int k = 0; k < 4; k++) ball2[k] = __builtin_bit_cast(float, (uint32_t)rec2[k]);
+                                if (ball2[3] > 0.0f) {
+                                    const bool c2 = shaded && !c1 && pt_certain_lane(ball2, pf[0], pf[1], pf[2], lx, ly, lz);
+                                    settled = want != 0ull && (got | PT_BALLOT(c2)) == want;
+                                    if (settled) hint.certain = 2u;
+                                }
+                            }
+#endif
+                            if (!STATS && settled) { PT_SEC_END(6); continue; }  // (PT_CYCLES builds count STATS instantiations only, which never get here)
+                        }
+                    }
+                }
+                if (shaded) {
+                    PtVec3 hit_to_light = lpos - sray.o;
+                    light_dist = pt_length(hit_to_light);
+                    sray.d = hit_to_light / light_dist;
+#ifndef PT_NO_LDS_COLOR
+                    fr.l(PT_L_TAG) = light_dist;
+#endif
+                    if (STATS) cnt.shadow++;
+                }
+                PtHit sh;
+                sh.t = INFINITY; sh.node = PT_NO_HIT; sh.sub = 0;
+                PT_SEC_END(6);
+#endif
+#if defined(PT_CERTAIN_SHADOW_FORM) && !defined(PT_CYCLES) && !defined(PT_ABLATE) && !defined(PT_NO_PACKET)
+                if (CERTAIN && occ.entry) {  // the table's test with the entries read above (what pt_trace_wave does for this mode, and pt_trace_packet behind it)
+                    const int words = a.stack_lds_cap * 64;
+                    pt_trace_packet_occ<STATS, false>(sc, sray, shaded, sh, pt_lds + (size_t)(threadIdx.x >> 6) * words, words, a.overflow_flag, &cnt, occ, hint);
+                } else
+#endif
                 pt_trace_wave<MODE, STATS>(a, sray, shaded, true, sh, stk, pt_lds, &cnt, occ);  // material.rs:174-179 only asks whether anything is in the way
                 PT_SEC_SKIP();
                 if (shaded && sh.node == PT_NO_HIT) {

@@ -174,6 +174,9 @@ struct PtRenderArgs {
     PtCounters* counters;
     const double* eye_tab;           // the launch's eye table (pt_eye_table_kernel, pt_api.hip): per flattened node its `inv` record with the translation column replaced by the camera's
                                      // eye in the node's space; nullptr: none (a scene without nodes, -DPT_NO_EYE_TABLE). Read by the mesh-free flat_scene straight-line kernels' primary stage.
+                                     // Behind its n_nodes x 12 doubles, in the launches that have an occluder table: the certain-shadow table (pt_certain_table_kernel; pt_certain.h), per node four
+                                     // floats {centre, squared radius} of a ball inside the primitive (radius 0: none), read in front of a light's shadow-ray set-up. (Not a pointer of its own: the
+                                     // argument block is the head of every other pass's arguments, and growing it shifts their fields - the film's and the radiance pass's kernels allocate differently.)
 };
 
 struct PtLane {

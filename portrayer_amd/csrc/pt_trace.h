@@ -16,6 +16,7 @@
 #pragma once
 
 #include "pt_prims.h"
+#include "pt_certain.h"
 #include "pt_scene_view.h"
 
 #define PT_NO_HIT 0xFFFFFFFFu
@@ -1716,33 +1717,31 @@ struct PtOccRef {
     uint32_t back, light;
 };
 
+// What the caller has read of the table already (the certain-shadow test in front of a light's set-up, pt_render_simple_kernel): `loaded` != 0: the two entries
+// (`own`, `up`). `certain` (the -DPT_OCCLUDER_STATS=2 counts only): bit 0 every shaded lane is certain by the candidate's ball, bit 1 by the two entries' balls together.
+struct PtOccHint {
+    uint32_t loaded, own, up, certain;
+};
+
 // Shadow rays (any = true) test the tile's last occluder for their light first: where it blocks every lane, the walk is skipped.
 // Exact by construction: a shadow ray only asks whether ANY node is hit in [EPSILON, INF) - an OR over nodes, whatever their order -
 // and the cached test is the walk's own leaf test (same function, same range - `best` is still empty -, same local ray, the same
 // wave-wide identity_ok). Lanes it does not block walk as before; the walk may test that node again for them, which changes nothing.
-// The counting build walks as before (its node counts are compared with the oracle's); -DPT_OCCLUDER_STATS makes it count, per
-// light, what the test would have saved (diag[], see below) without changing the walk.
-// EYE: primary rays (nearest hit, no table entry) whose walk reads the launch's eye table (pt_trace_packet_walk).
-template <bool STATS, bool HIER, bool EYE = false>
-PT_HD void pt_trace_packet(const PtSceneView& sc, const PtRay& ray, bool has_ray, bool any, PtHit& best, uint32_t* wstack, int wwords,
-                           unsigned int* overflow, PtCounters* cnt, PtOccRef occ = PtOccRef{nullptr, 0u, 0u}, const double* eye_tab = nullptr) {
-    if (EYE) {
-        pt_trace_packet_walk<STATS, HIER, EYE>(sc, ray, has_ray, false, best, wstack, wwords, overflow, cnt, true, eye_tab);
-        return;
-    }
+// -DPT_OCCLUDER_STATS makes the counting build count, per light, what the test would have saved (diag[], see below) without changing the walk.
+// (occ.entry != nullptr; STATS only with -DPT_OCCLUDER_STATS - pt_trace_packet sees to both.)
+template <bool STATS, bool HIER>
+PT_HD void pt_trace_packet_occ(const PtSceneView& sc, const PtRay& ray, bool has_ray, PtHit& best, uint32_t* wstack, int wwords,
+                               unsigned int* overflow, PtCounters* cnt, PtOccRef occ, PtOccHint hint) {
+    constexpr bool any = true;
 #if defined(__HIP_DEVICE_COMPILE__)
 #ifdef PT_OCCLUDER_STATS
     constexpr bool COUNT_OCC = STATS;
 #else
     constexpr bool COUNT_OCC = false;
 #endif
-    if ((STATS && !COUNT_OCC) || !any || occ.entry == nullptr) {
-        pt_trace_packet_walk<STATS, HIER>(sc, ray, has_ray, any, best, wstack, wwords, overflow, cnt);
-        return;
-    }
     uint32_t* const entry = (uint32_t*)pt_uniform_ptr(occ.entry);
-    const uint32_t own = PT_UNIFORM_U32(entry[0]);
-    const uint32_t up = occ.back ? PT_UNIFORM_U32(entry[-(long)occ.back]) : 0u;
+    const uint32_t own = hint.loaded ? hint.own : PT_UNIFORM_U32(entry[0]);
+    const uint32_t up = hint.loaded ? hint.up : (occ.back ? PT_UNIFORM_U32(entry[-(long)occ.back]) : 0u);
     const uint32_t cand = own ? own : up;
     const unsigned long long rays = PT_BALLOT(has_ray);
     bool blocked = false;
@@ -1775,9 +1774,40 @@ PT_HD void pt_trace_packet(const PtSceneView& sc, const PtRay& ray, bool has_ray
         // own tile), diag[7]: walks in which the candidate blocked a lane (low)
         cnt->diag[2 * occ.light] += 1ull | (hit_mask ? 1ull << 32 : 0ull);
         if (hit_mask == rays) cnt->diag[2 * occ.light + 1] += 1ull | (blocked_mask == rays ? 1ull << 32 : 0ull);
+#if PT_OCCLUDER_STATS + 0 == 2  // diag[6]: per light (21 bits each) the walks the candidate alone ends in which its ball settles every lane; diag[7]: the fully blocked walks the two entries' balls settle
+        if (hit_mask == rays && blocked_mask == rays && (hint.certain & 1u)) cnt->diag[6] += 1ull << (21 * occ.light);
+        if (hit_mask == rays && (hint.certain & 2u)) cnt->diag[7] += 1ull << (21 * occ.light);
+#else
         if (cand) cnt->diag[6] += 1ull | (own ? 1ull << 32 : 0ull);
         if (blocked_mask) cnt->diag[7]++;
+#endif
     }
+#else
+    pt_trace_packet_walk<STATS, HIER>(sc, ray, has_ray, any, best, wstack, wwords, overflow, cnt);
+#endif
+}
+
+// The mesh-free walks' entry: shadow rays of a launch with an occluder table go through the table's test (pt_trace_packet_occ). The counting build walks as before
+// (its node counts are compared with the oracle's) unless -DPT_OCCLUDER_STATS.
+// EYE: primary rays (nearest hit, no table entry) whose walk reads the launch's eye table (pt_trace_packet_walk).
+template <bool STATS, bool HIER, bool EYE = false>
+PT_HD void pt_trace_packet(const PtSceneView& sc, const PtRay& ray, bool has_ray, bool any, PtHit& best, uint32_t* wstack, int wwords,
+                           unsigned int* overflow, PtCounters* cnt, PtOccRef occ = PtOccRef{nullptr, 0u, 0u}, const double* eye_tab = nullptr) {
+    if (EYE) {
+        pt_trace_packet_walk<STATS, HIER, EYE>(sc, ray, has_ray, false, best, wstack, wwords, overflow, cnt, true, eye_tab);
+        return;
+    }
+#if defined(__HIP_DEVICE_COMPILE__)
+#ifdef PT_OCCLUDER_STATS
+    constexpr bool COUNT_OCC = STATS;
+#else
+    constexpr bool COUNT_OCC = false;
+#endif
+    if ((STATS && !COUNT_OCC) || !any || occ.entry == nullptr) {
+        pt_trace_packet_walk<STATS, HIER>(sc, ray, has_ray, any, best, wstack, wwords, overflow, cnt);
+        return;
+    }
+    pt_trace_packet_occ<STATS, HIER>(sc, ray, has_ray, best, wstack, wwords, overflow, cnt, occ, PtOccHint{0u, 0u, 0u, 0u});
 #else
     pt_trace_packet_walk<STATS, HIER>(sc, ray, has_ray, any, best, wstack, wwords, overflow, cnt);
 #endif

@@ -3,7 +3,13 @@
   make variant NAME=occstats EXTRA_HIPFLAGS=-DPT_OCCLUDER_STATS
 on big-scene 1920x1080x64: per light the shadow walks, those with a lane in the shadow, those with every lane in the shadow, and of
 the last how many the table's candidate alone would have ended. The counting walk itself is unchanged.
-usage (GPU box, repo root): python3 profiles/occluder_stats.py build/variants/occstats flat|hier"""
+usage (GPU box, repo root): python3 profiles/occluder_stats.py build/variants/occstats flat|hier
+
+With a third argument `certain` the build is one of
+  make variant NAME=occstats2 EXTRA_HIPFLAGS=-DPT_OCCLUDER_STATS=2
+whose diag[6] and diag[7] count instead, per light in 21 bits each (so fewer than 2,097,152 walks per light: checked), what the certain-shadow test (pt_certain.h)
+would settle: of the walks the candidate alone ends, those in which its inscribed ball settles every shaded lane; and of ALL fully blocked walks, those the balls
+of the tile's own entry and of the tile above settle together. The counting walk is unchanged there as well (flat only: the hierarchical semantics has no table)."""
 import os, shutil, sys, tempfile, json
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 tmp = tempfile.mkdtemp()
@@ -25,5 +31,11 @@ hi = lambda x: x >> 32
 out = {"mode": mode, "shadow_rays": st["shadow"], "n_inner": st["n_inner"], "primary": st["primary"], "lights": []}
 for l in range(3):
     out["lights"].append({"walks": lo(d[2 * l]), "some_lane_occluded": hi(d[2 * l]), "all_occluded": lo(d[2 * l + 1]), "candidate_ends": hi(d[2 * l + 1])})
-out["walks_with_candidate"] = lo(d[6]); out["candidate_from_own_tile"] = hi(d[6]); out["candidate_blocked_a_lane"] = d[7]
+if len(sys.argv) > 3 and sys.argv[3] == "certain":
+    for l in range(3):
+        assert out["lights"][l]["walks"] < (1 << 21), "a 21-bit field would overflow"
+        out["lights"][l]["candidate_ends_and_its_ball_settles"] = (d[6] >> (21 * l)) & 0x1FFFFF
+        out["lights"][l]["all_occluded_and_two_balls_settle"] = (d[7] >> (21 * l)) & 0x1FFFFF
+else:
+    out["walks_with_candidate"] = lo(d[6]); out["candidate_from_own_tile"] = hi(d[6]); out["candidate_blocked_a_lane"] = d[7]
 print("OCCSTATS " + json.dumps(out), flush=True)
