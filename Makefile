@@ -63,38 +63,21 @@ endef
 $(OBJDIR)/%.o: $(CSRC)/%.hip $(HIP_HDRS) tools/check_exec_prologue.py
 	$(call hip_four_steps,)
 
-$(OBJDIR)/pt_render_m%.o: $(CSRC)/pt_render_inst.hip $(HIP_HDRS) tools/check_exec_prologue.py
-	$(call hip_four_steps,-DPT_INST_MODE=$*)
-
-# the primary-visibility pass (pt_aov.h), instantiated per traversal mode like the render kernel
-$(OBJDIR)/pt_aov_m%.o: $(CSRC)/pt_aov_inst.hip $(HIP_HDRS) tools/check_exec_prologue.py
-	$(call hip_four_steps,-DPT_INST_MODE=$*)
-
-# the ray-query pass (pt_rays.h), likewise; its keying + sort step (pt_rays_sort.hip) is built by the %.o rule
-$(OBJDIR)/pt_rays_m%.o: $(CSRC)/pt_rays_inst.hip $(HIP_HDRS) tools/check_exec_prologue.py
-	$(call hip_four_steps,-DPT_INST_MODE=$*)
-
-# the bounded-segment ray queries (pt_segments.h): pt_rays_kernel with a t_max per ray, and the one unit whose walks start at that bound (PT_WALK_ENTRY_T)
-$(OBJDIR)/pt_segments_m%.o: $(CSRC)/pt_segments_inst.hip $(HIP_HDRS) tools/check_exec_prologue.py
-	$(call hip_four_steps,-DPT_INST_MODE=$*)
-
-# the radiance pass (pt_radiance.h): the interpreter over the caller's rays, <TEX, PARK> instantiations per mode
-$(OBJDIR)/pt_radiance_m%.o: $(CSRC)/pt_radiance_inst.hip $(HIP_HDRS) tools/check_exec_prologue.py
-	$(call hip_four_steps,-DPT_INST_MODE=$*)
-
-# the film's sampling kernel (pt_film.h): the same interpreter with the camera as its source, <TEX, PARK> instantiations per mode; its fold and resolve
-# kernels (pt_film.hip) are built by the %.o rule
-$(OBJDIR)/pt_film_m%.o: $(CSRC)/pt_film_inst.hip $(HIP_HDRS) tools/check_exec_prologue.py
-	$(call hip_four_steps,-DPT_INST_MODE=$*)
-
-# the film's per-pixel budget (pt_film_map.h): the sampling kernel over a list of samples, <TEX, PARK> instantiations per mode; its plan, fold, error and
-# budget kernels are pt_film_map.hip. Both as static rules: the names also match the pattern pt_film_m%.o above, which must not build them.
-$(foreach m,$(RENDER_MODES),$(OBJDIR)/pt_film_map_m$(m).o): $(OBJDIR)/pt_film_map_m%.o: $(CSRC)/pt_film_map_inst.hip $(HIP_HDRS) tools/check_exec_prologue.py
-	$(call hip_four_steps,-DPT_INST_MODE=$*)
-$(OBJDIR)/pt_film_map.o: $(CSRC)/pt_film_map.hip $(HIP_HDRS) tools/check_exec_prologue.py
-	$(call hip_four_steps,)
-# (... and nothing makes the sources: make's built-in "a program from its object" would look for pt_film_map.hip.o, which pt_film_m%.o matches too)
-$(CSRC)/pt_film_map.hip $(CSRC)/pt_film_map_inst.hip $(CSRC)/pt_film_map.h $(CSRC)/pt_film_map_inst.h: ;
+# The kernels instantiated per traversal mode - one source, nine objects per pass: pt_<pass>_m<mode>.o from pt_<pass>_inst.hip with -DPT_INST_MODE=<mode>.
+#   render    the render kernel (pt_render_kernel.h)
+#   aov       the primary-visibility pass (pt_aov.h)
+#   rays      the ray-query pass (pt_rays.h); its keying + sort step (pt_rays_sort.hip) is built by the %.o rule
+#   segments  the bounded-segment ray queries (pt_segments.h): pt_rays_kernel with a t_max per ray, and the one unit whose walks start at that bound (PT_WALK_ENTRY_T)
+#   radiance  the radiance pass (pt_radiance.h): the interpreter over the caller's rays, <TEX, PARK> instantiations per mode
+#   film      the film's sampling kernel (pt_film.h): the same interpreter with the camera as its source; its fold and resolve kernels (pt_film.hip): the %.o rule
+#   film_map  the film's per-pixel budget (pt_film_map.h): the sampling kernel over a list of samples; its plan, fold, error and budget kernels (pt_film_map.hip): the %.o rule
+# Static pattern rules, each over its own nine objects: as a plain pattern, pt_film_m%.o would match pt_film_map.o and pt_film_map_m1.o too.
+PASSES := render aov rays segments radiance film film_map
+define mode_rule
+$(foreach m,$(RENDER_MODES),$(OBJDIR)/pt_$(1)_m$(m).o): $(OBJDIR)/pt_$(1)_m%.o: $(CSRC)/pt_$(1)_inst.hip $(HIP_HDRS) tools/check_exec_prologue.py
+	$$(call hip_four_steps,-DPT_INST_MODE=$$*)
+endef
+$(foreach p,$(PASSES),$(eval $(call mode_rule,$(p))))
 
 $(HIPLIB): $(HIP_OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared $^ -o $@ -ldl

@@ -4,6 +4,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include "pt_mode_launch.h"
 #include "pt_shade.h"
 
 struct PtAovArgs {
@@ -17,17 +18,8 @@ struct PtAovArgs {
     int32_t* material;
 };
 
-// Waves per SIMD the instantiation of a mode is compiled for (pt_aov_kernel's launch bounds) - and so how much LDS a block may take for its stacks (pt_aov_common):
+// Waves per SIMD the instantiation of a mode is compiled for (pt_aov_kernel's launch bounds) - and so how much LDS a block may take for its stacks (pt_walk_sizing):
 // the modes that carry the per-lane KDMesh walker need its registers, as in a render.
 constexpr int pt_aov_waves(int mode) { return (mode == PT_MODE_KD || mode == PT_MODE_FLAT_KDMESH || mode == PT_MODE_HIER) ? 3 : 4; }
 
-#define PT_DECLARE_AOV_LAUNCHER(n) hipError_t pt_aov_launch_mode_##n(const PtAovArgs& a, int n_cu, hipStream_t stream, uint32_t* grid, bool launch)
-PT_DECLARE_AOV_LAUNCHER(1);  // PT_MODE_FLAT
-PT_DECLARE_AOV_LAUNCHER(2);  // PT_MODE_KD
-PT_DECLARE_AOV_LAUNCHER(3);  // PT_MODE_FLAT_NOMESH
-PT_DECLARE_AOV_LAUNCHER(4);  // PT_MODE_FLAT_KDMESH
-PT_DECLARE_AOV_LAUNCHER(5);  // PT_MODE_HIER
-PT_DECLARE_AOV_LAUNCHER(6);  // PT_MODE_HIER_NOMESH
-PT_DECLARE_AOV_LAUNCHER(7);  // PT_MODE_KD_NOMESH
-PT_DECLARE_AOV_LAUNCHER(8);  // PT_MODE_HIER_MESH
-PT_DECLARE_AOV_LAUNCHER(9);  // PT_MODE_KD_MESH
+PT_DECLARE_MODE_LAUNCHERS(pt_aov_launch_mode_, const PtAovArgs& a, int n_cu, hipStream_t stream, uint32_t* grid, bool launch);

@@ -258,9 +258,34 @@ __global__ void __launch_bounds__(256) pt_certain_table_kernel(const uint32_t* _
 // ------------------------------------------------------------------------------------------------
 // Context
 // ------------------------------------------------------------------------------------------------
+// A device buffer (pt_reserve). It dies with its owner - the context, a film, a function's scope - whose device is current wherever one is destroyed.
 struct PtBuf {
     void* p = nullptr;
     size_t bytes = 0;
+    PtBuf() = default;
+    PtBuf(const PtBuf&) = delete;
+    PtBuf& operator=(const PtBuf&) = delete;
+    ~PtBuf() { if (p) hipFree(p); }
+};
+
+// What a device pass beside the render owns whatever its kind (primary visibility, ray queries, radiance and the film's passes; the pt_pass_* functions below),
+// so that the two render slots stay as they are whatever is in flight on them, and every pass whatever is in flight on another.
+struct PtPass {
+    PtBuf stack_spill;                         // the lanes' HBM stack columns
+    PtBuf spill;                               // the lanes' recursion-frame lines (the radiance pass and the film's only)
+    PtBuf misc;                                // the overflow flag (word 1, where a render has it) and, from +256 on, the work queues
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;   // around the kernels (kernel_ms)
+    hipEvent_t copy_done = nullptr;            // behind the copy into `host`
+    unsigned char* host = nullptr;             // pinned: the first two words of misc (the second is the overflow flag)
+    hipStream_t stream = nullptr;              // of the last pass queued
+    bool pending = false;                      // a _device call not yet closed by its _finish
+    bool queued = false;                       // something of the last pass queued may still be in flight (pt_pass_wait)
+    bool closed = false;                       // ... and all of it was queued: copy_done is recorded behind it
+};
+// What reorder = 1 of the ray passes sorts with: keys and ray indices before and after, the sort's scratch (pt_ray_sort_reserve, pt_ray_sort_queue).
+struct PtRaySort {
+    PtBuf keys[2], vals[2], tmp;
+    size_t tmp_bytes = 0;
 };
 
 struct pt_film;
@@ -310,37 +335,27 @@ struct pt_context {
     int slot_next = 0;     // the slot the next launch takes
     int slot_oldest = 0;   // the oldest launch not yet closed (== slot_next: none, unless every slot is pending)
     uint32_t last_mode = 0, last_variant = 0;
-    // The primary-visibility pass (pt_aov / pt_aov_device) owns its work buffers, so that the two render slots stay as they are whatever is in flight on them:
-    // the lanes' HBM stack columns, overflow flag + work queues, the device copies of the host-buffer path's six outputs, events and one pinned page.
+    // The three passes beside the render, each with a PtPass of its own: all three may be in flight at once, with two renders. Beside it, what is the kind's.
+    // The primary-visibility pass (pt_aov / pt_aov_device ... pt_aov_finish): the device copies of the host-buffer path's six outputs.
     struct Aov {
-        PtBuf stack_spill, misc, out[6];
-        hipEvent_t ev0 = nullptr, ev1 = nullptr, copy_done = nullptr;
-        unsigned char* host = nullptr;  // pinned: the first two words of misc (the second is the overflow flag)
-        bool pending = false;           // a pt_aov_device not yet closed by pt_aov_finish
-        hipStream_t stream = nullptr;   // of the last pass queued
-        bool queued = false;            // ... something of it may still be in flight (pt_aov_wait)
-        bool closed = false;            // ... and all of it was queued: copy_done is recorded behind it
+        PtPass pass;
+        PtBuf out[6];
     } aov;
-    // The ray-query pass (pt_rays / pt_rays_device) likewise, apart from both: stack columns, overflow flag + work queues, events and a pinned page; the device
-    // copies of the host-buffer path's two inputs and seven outputs; and what reorder = 1 sorts with (keys and ray indices before and after, the sort's scratch).
+    // The ray-query pass (pt_rays / pt_segments, their _device forms ... pt_rays_finish): the device copies of the host-buffer path's inputs (in_t_max: pt_segments'
+    // third) and seven outputs.
     struct Rays {
-        PtBuf stack_spill, misc, in[2], in_t_max, out[7], keys[2], vals[2], sort_tmp;  // in_t_max: pt_segments' third input
-        hipEvent_t ev0 = nullptr, ev1 = nullptr, copy_done = nullptr;
-        unsigned char* host = nullptr;
-        bool pending = false;           // a pt_rays_device / pt_segments_device not yet closed by pt_rays_finish
-        hipStream_t stream = nullptr;
-        bool queued = false, closed = false;  // as in Aov
+        PtPass pass;
+        PtBuf in[2], in_t_max, out[7];
+        PtRaySort sort;
     } rays;
-    // The radiance pass (pt_radiance / pt_radiance_device) likewise, apart from all three: stack columns, the lanes' recursion-frame lines, overflow flag + work
-    // queues, events and a pinned page; the device copies of the host-buffer path's three inputs and its output; what reorder = 1 sorts with.
+    // The radiance pass (pt_radiance / pt_radiance_device ... pt_radiance_finish), which a film's passes share: the device copies of the host-buffer path's three
+    // inputs and its output.
     struct Radiance {
-        PtBuf stack_spill, spill, misc, in[3], out, keys[2], vals[2], sort_tmp;
-        hipEvent_t ev0 = nullptr, ev1 = nullptr, copy_done = nullptr;
-        unsigned char* host = nullptr;
-        bool pending = false;           // a pt_radiance_device not yet closed by pt_radiance_finish
-        hipStream_t stream = nullptr;
-        bool queued = false, closed = false;  // as in Aov
+        PtPass pass;
+        PtBuf in[3], out;
+        PtRaySort sort;
     } radiance;
+    PtPass* const passes[3] = {&aov.pass, &rays.pass, &radiance.pass};
     // Films (pt_film_create): each owns its device state; a film pass is a radiance pass for bookkeeping (pt_film_add_device), film_open names the film of the
     // one in flight. Films still alive die with the context.
     std::vector<pt_film*> films;
@@ -404,12 +419,6 @@ struct pt_film {
     bool moments = false;
     std::vector<uint32_t> counts;
 };
-static void pt_film_free(pt_film* f) {
-    for (PtBuf* b : {&f->total, &f->partial, &f->count, &f->staging, &f->bg, &f->out_rgb, &f->out_linear, &f->q, &f->budget, &f->list, &f->plan_work, &f->out_err,
-                     &f->dn_work[0], &f->dn_work[1], &f->dn_position, &f->dn_normal, &f->dn_node, &f->out_var}) if (b->p) hipFree(b->p);
-    delete f;
-}
-
 static int pt_fail(pt_context* c, int code, const std::string& msg) {
     if (c) c->err = msg;
     return code;
@@ -434,6 +443,107 @@ static int pt_upload(pt_context* c, PtBuf& b, const std::vector<T>& v) {
     if (rc) return rc;
     if (!v.empty()) PT_HIP(c, hipMemcpy(b.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
     return PT_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// The life of a device pass (PtPass), the same for every kind. Queueing: prepare, [the kind's argument block and sizing dispatch], open, [its sort and kernels],
+// seal. On the pass's stream that is: all of misc zeroed, ev0, the sort and the kernels, ev1, the overflow flag's copy to the pinned page, copy_done.
+// Closing: wait, result. The entry points: pt_pass_device_tail ... pt_pass_finish, or pt_pass_settle ... pt_pass_result within one call (host buffers).
+// ------------------------------------------------------------------------------------------------
+#define PT_PASS_MISC_BYTES (256 + PT_FINE_QUEUES * PT_QUEUE_STRIDE * 4)
+static size_t pt_stack_column(const PtSceneView& sc, int stack_lds_cap);
+
+// The events and the pinned page, made by the pass's first use: a context that never runs the pass never pays for them.
+static int pt_pass_prepare(pt_context* c, PtPass& v) {
+    if (v.ev0) return PT_OK;
+    PT_HIP(c, hipEventCreate(&v.ev0));
+    PT_HIP(c, hipEventCreate(&v.ev1));
+    PT_HIP(c, hipEventCreateWithFlags(&v.copy_done, hipEventDisableTiming));
+    PT_HIP(c, hipHostMalloc((void**)&v.host, 256, hipHostMallocDefault));
+    return PT_OK;
+}
+
+// The work buffers for a launch of `grid` blocks (the sizing dispatch's figure, with r.stack_lds_cap set) and `r` pointed into them; then misc zeroed and the first
+// event on `stream`. frames: the kernels keep recursion frames (the interpreter's). The items come one at a time from 16 interleaved queues, as a render of this
+// size has them (pt_render_common).
+static int pt_pass_open(pt_context* c, PtPass& v, PtRenderArgs& r, uint32_t grid, bool frames, hipStream_t stream) {
+    r.n_lanes = grid * PT_BLOCK;
+    int rc;
+    if ((rc = pt_reserve(c, v.stack_spill, (size_t)r.n_lanes * pt_stack_column(r.scene, r.stack_lds_cap) * 4))) return rc;
+    if (frames && (rc = pt_reserve(c, v.spill, c->needs_spill ? (size_t)r.n_lanes * PT_SPILL_DEPTHS * PT_SPILL_STRIDE * sizeof(double) : 16))) return rc;
+    if ((rc = pt_reserve(c, v.misc, PT_PASS_MISC_BYTES))) return rc;
+    r.stack_spill = (uint32_t*)v.stack_spill.p;
+    if (frames) r.spill = (double*)v.spill.p;
+    r.overflow_flag = (unsigned int*)v.misc.p + 1;
+    r.work_queues = (unsigned int*)((char*)v.misc.p + 256);
+    r.fine_queues = 16;
+    v.stream = stream; v.queued = true; v.closed = false;  // from here on something of the pass may be in flight on `stream`, whatever fails below
+    PT_HIP(c, hipMemsetAsync(v.misc.p, 0, PT_PASS_MISC_BYTES, stream));
+    PT_HIP(c, hipEventRecord(v.ev0, stream));
+    return PT_OK;
+}
+
+// Behind the kernels: the second event, and the overflow flag on its way to the pinned page.
+static int pt_pass_seal(pt_context* c, PtPass& v) {
+    PT_HIP(c, hipEventRecord(v.ev1, v.stream));
+    PT_HIP(c, hipMemcpyAsync(v.host, v.misc.p, 8, hipMemcpyDeviceToHost, v.stream));
+    PT_HIP(c, hipEventRecord(v.copy_done, v.stream));
+    v.closed = true;
+    return PT_OK;
+}
+
+// Waits for whatever the last queueing left in flight: the event behind its last copy, or - where queueing failed half way - its stream.
+static int pt_pass_wait(pt_context* c, PtPass& v) {
+    if (!v.queued) return PT_OK;
+    v.queued = false;
+    if (v.closed) PT_HIP(c, hipEventSynchronize(v.copy_done));
+    else PT_HIP(c, hipStreamSynchronize(v.stream));
+    return PT_OK;
+}
+
+// After the pass's copy_done: the kernel time and what the overflow flag says (as pt_collect_stats reads a render's).
+static int pt_pass_result(pt_context* c, PtPass& v, double* kernel_ms) {
+    unsigned int head[2];
+    memcpy(head, v.host, sizeof head);
+    if (kernel_ms) {
+        float ms = 0.f;
+        PT_HIP(c, hipEventElapsedTime(&ms, v.ev0, v.ev1));
+        *kernel_ms = ms;
+    }
+    if (head[1] & 4u) return pt_fail(c, PT_ERR_TRAVERSAL, "a tree walk did not end (watchdog): results invalid");
+    if (head[1]) return pt_fail(c, PT_ERR_TRAVERSAL, "traversal stack overflow");
+    return PT_OK;
+}
+
+// The end of a _device entry point; rc: what queueing returned. What was queued before a failure must not outlive the call: the next pass may reallocate the
+// buffers under it.
+static int pt_pass_device_tail(pt_context* c, PtPass& v, int rc) {
+    if (rc) { pt_pass_wait(c, v); return rc; }
+    v.pending = true;
+    return PT_OK;
+}
+// ... and the middle of a host-buffer one, in front of its copies back: it waits whether or not queueing failed, and the queueing error comes first.
+static int pt_pass_settle(pt_context* c, PtPass& v, int rc) {
+    const int rc_wait = pt_pass_wait(c, v);
+    return rc ? rc : rc_wait;
+}
+
+// A _finish entry point (c is not NULL); none: what it says when no _device call of the pass is open.
+static int pt_pass_finish(pt_context* c, PtPass& v, const char* none, double* kernel_ms) {
+    if (!v.pending) return pt_fail(c, PT_ERR_ARGUMENT, none);
+    PT_HIP(c, hipSetDevice(c->device));
+    v.pending = false;
+    int rc = pt_pass_wait(c, v);
+    if (rc) return rc;
+    return pt_pass_result(c, v, kernel_ms);
+}
+
+// pt_context_destroy, behind the pass's wait: what is not a PtBuf.
+static void pt_pass_release(PtPass& v) {
+    if (v.ev0) hipEventDestroy(v.ev0);
+    if (v.ev1) hipEventDestroy(v.ev1);
+    if (v.copy_done) hipEventDestroy(v.copy_done);
+    if (v.host) hipHostFree(v.host);
 }
 
 extern "C" int pt_abi_version(void) { return PT_ABI_VERSION; }
@@ -470,46 +580,22 @@ extern "C" int pt_context_create(int device, pt_context** out) {
 extern "C" void pt_context_destroy(pt_context* c) {
     if (!c) return;
     hipSetDevice(c->device);
-    PtBuf* bufs[] = {&c->inv, &c->fwd, &c->nrm, &c->info, &c->tri_v, &c->tri_e, &c->tri_leaf, &c->tri_n, &c->meshes, &c->materials, &c->lights,
-                     &c->bvh, &c->bvh4, &c->bvh_items, &c->kd, &c->kd_items, &c->mat_maps, &c->uv_trans, &c->tex, &c->tex_rgb, &c->srgb_lut, &c->tri_uv, &c->texview, &c->mkd, &c->mkd_items, &c->slot[0].spill, &c->slot[0].stack_spill, &c->slot[0].accum, &c->slot[0].misc, &c->slot[1].spill, &c->slot[1].stack_spill, &c->slot[1].accum, &c->slot[1].misc, &c->slot[0].eye_tab, &c->slot[1].eye_tab, &c->bg, &c->rgb, &c->linear, &c->misc, &c->node_box, &c->kd_box, &c->mkd_box, &c->mkd_item_box, &c->kd_ref, &c->g_inv, &c->g_fwd, &c->g_nrm, &c->chain_off, &c->chain, &c->dfs_rank, &c->hier_rec, &c->own_inv, &c->mesh_box_dev, &c->mesh_idx, &c->tree_parent, &c->tree_arrive, &c->deform_stage, &c->vbox};
-    for (PtBuf* b : bufs) if (b->p) hipFree(b->p);
-    if (c->aov.queued) { if (c->aov.closed) hipEventSynchronize(c->aov.copy_done); else hipStreamSynchronize(c->aov.stream); }  // (pt_aov_wait)
-    for (PtBuf* b : {&c->aov.stack_spill, &c->aov.misc, &c->aov.out[0], &c->aov.out[1], &c->aov.out[2], &c->aov.out[3], &c->aov.out[4], &c->aov.out[5]}) if (b->p) hipFree(b->p);
-    if (c->aov.ev0) hipEventDestroy(c->aov.ev0);
-    if (c->aov.ev1) hipEventDestroy(c->aov.ev1);
-    if (c->aov.copy_done) hipEventDestroy(c->aov.copy_done);
-    if (c->aov.host) hipHostFree(c->aov.host);
-    {
-        pt_context::Rays& y = c->rays;
-        if (y.queued) { if (y.closed) hipEventSynchronize(y.copy_done); else hipStreamSynchronize(y.stream); }  // (pt_rays_wait)
-        PtBuf* rb[] = {&y.stack_spill, &y.misc, &y.in[0], &y.in[1], &y.in_t_max, &y.out[0], &y.out[1], &y.out[2], &y.out[3], &y.out[4], &y.out[5], &y.out[6], &y.keys[0], &y.keys[1], &y.vals[0], &y.vals[1], &y.sort_tmp};
-        for (PtBuf* b : rb) if (b->p) hipFree(b->p);
-        if (y.ev0) hipEventDestroy(y.ev0);
-        if (y.ev1) hipEventDestroy(y.ev1);
-        if (y.copy_done) hipEventDestroy(y.copy_done);
-        if (y.host) hipHostFree(y.host);
-    }
-    {
-        pt_context::Radiance& y = c->radiance;
-        if (y.queued) { if (y.closed) hipEventSynchronize(y.copy_done); else hipStreamSynchronize(y.stream); }  // (pt_radiance_wait)
-        PtBuf* rb[] = {&y.stack_spill, &y.spill, &y.misc, &y.in[0], &y.in[1], &y.in[2], &y.out, &y.keys[0], &y.keys[1], &y.vals[0], &y.vals[1], &y.sort_tmp};
-        for (PtBuf* b : rb) if (b->p) hipFree(b->p);
-        if (y.ev0) hipEventDestroy(y.ev0);
-        if (y.ev1) hipEventDestroy(y.ev1);
-        if (y.copy_done) hipEventDestroy(y.copy_done);
-        if (y.host) hipHostFree(y.host);
-    }
-    for (pt_film* f : c->films) pt_film_free(f);  // (behind the radiance pass's wait above: nothing of a film pass is in flight any more)
-    c->films.clear();
-    static_assert(pt_context::PT_SLOTS == 2, "the buffer list above names both slots");
+    // Whatever a pass or a render still has in flight may read any buffer of the context: all of it is waited for before anything is freed.
+    for (PtPass* v : c->passes) pt_pass_wait(c, *v);
     for (auto& sl : c->slot) {
-        if (sl.stream) { hipStreamSynchronize(sl.stream); hipStreamDestroy(sl.stream); }
+        if (sl.pending) hipEventSynchronize(sl.copy_done);
+        if (sl.stream) hipStreamSynchronize(sl.stream);
+    }
+    for (pt_film* f : c->films) delete f;
+    for (PtPass* v : c->passes) pt_pass_release(*v);
+    for (auto& sl : c->slot) {
+        if (sl.stream) hipStreamDestroy(sl.stream);
         if (sl.ev0) hipEventDestroy(sl.ev0);
         if (sl.ev1) hipEventDestroy(sl.ev1);
         if (sl.copy_done) hipEventDestroy(sl.copy_done);
         if (sl.host) hipHostFree(sl.host);
     }
-    delete c;
+    delete c;  // (with every PtBuf it holds)
 }
 
 extern "C" const char* pt_last_error(const pt_context* c) { return c ? c->err.c_str() : "no context"; }
@@ -1316,7 +1402,8 @@ struct PtUpdatePlan {
 
 // the copies and kernels of an update or a deform are not ordered against the context's non-blocking streams
 static int pt_refuse_in_flight(pt_context* c) {
-    bool in_flight = c->aov.pending || c->rays.pending || c->radiance.pending;
+    bool in_flight = false;
+    for (const PtPass* v : c->passes) in_flight = in_flight || v->pending;
     for (const auto& sl : c->slot) in_flight = in_flight || sl.pending;
     if (in_flight) return pt_fail(c, PT_ERR_ARGUMENT, "a render is in flight: pt_render_finish / pt_aov_finish / pt_rays_finish / pt_radiance_finish first");
     return PT_OK;
@@ -1712,17 +1799,7 @@ static int pt_check_params(pt_context* c, const pt_camera* cam, const pt_render_
 // a.run_variant (PT_RUN_*, pt_render_kernel.h) selects the kernel.
 static hipError_t pt_dispatch(const PtRenderArgs& a, bool stats, int n_cu, hipStream_t stream, uint32_t* grid, bool launch) {
     const bool tex = a.scene.mat_maps != nullptr;
-    switch (a.scene.mode) {
-    case PT_MODE_KD: return pt_launch_mode_2(a, a.run_variant, stats, tex, n_cu, stream, grid, launch);
-    case PT_MODE_FLAT_NOMESH: return pt_launch_mode_3(a, a.run_variant, stats, tex, n_cu, stream, grid, launch);
-    case PT_MODE_FLAT_KDMESH: return pt_launch_mode_4(a, a.run_variant, stats, tex, n_cu, stream, grid, launch);
-    case PT_MODE_HIER: return pt_launch_mode_5(a, a.run_variant, stats, tex, n_cu, stream, grid, launch);
-    case PT_MODE_HIER_NOMESH: return pt_launch_mode_6(a, a.run_variant, stats, tex, n_cu, stream, grid, launch);
-    case PT_MODE_KD_NOMESH: return pt_launch_mode_7(a, a.run_variant, stats, tex, n_cu, stream, grid, launch);
-    case PT_MODE_HIER_MESH: return pt_launch_mode_8(a, a.run_variant, stats, tex, n_cu, stream, grid, launch);
-    case PT_MODE_KD_MESH: return pt_launch_mode_9(a, a.run_variant, stats, tex, n_cu, stream, grid, launch);
-    default: return pt_launch_mode_1(a, a.run_variant, stats, tex, n_cu, stream, grid, launch);
-    }
+    PT_MODE_LAUNCH(pt_launch_mode_, a.scene.mode, a, a.run_variant, stats, tex, n_cu, stream, grid, launch)
 }
 
 // The part of the kernel arguments that follows from the render parameters alone: the slice, the rank's tiles, how a wavefront's
@@ -1887,17 +1964,18 @@ extern "C" int pt_test_certain_shadow(uint64_t n, int type, const double* fwd, c
     return PT_OK;
 }
 
-// How a launch's traversal stacks are split between LDS and HBM - one place for the render kernels and the primary-visibility pass (pt_aov_common), whose
+// How a launch's traversal stacks are split between LDS and HBM - one place for the render kernels and every pass beside them, whose
 // kernels lay their LDS out with the same code (pt_trace_wave: pt_wave_rows, pt_kd_layout).
 // pt_stack_lds_cap: entries per lane kept in LDS = what `block_budget` bytes of LDS per block leave beside `frame_bytes` of other per-block data (1 KB a row), at most the
 // scene's whole stack. The k-d walk keeps no saved bounds in HBM (round 5): its wavefront rows must hold the stack and, where the stack's slack is too small for it, the two
 // rows of the path table (pt_kd_layout, PtKdSav) - also under PORTRAYER_LDS_STACK=1 (experiments / tests of the overflow path), which then only shrinks the LANES' stacks.
-static int pt_stack_lds_cap(const PtSceneView& sc, size_t block_budget, size_t frame_bytes, bool kd_sem) {
+static bool pt_kd_semantics(int mode) { return mode == PT_MODE_KD || mode == PT_MODE_KD_NOMESH || mode == PT_MODE_KD_MESH; }
+static int pt_stack_lds_cap(const PtSceneView& sc, size_t block_budget, size_t frame_bytes) {
     int lds_cap = block_budget > frame_bytes ? (int)((block_budget - frame_bytes) / (PT_BLOCK * 4)) : 0;
     lds_cap = std::max(lds_cap, 2);
     if (const char* e = getenv("PORTRAYER_LDS_STACK")) lds_cap = std::max(1, atoi(e));
     int cap = std::min(lds_cap, sc.stack_cap);
-    if (kd_sem) cap = std::max(cap, (sc.stack_cap + 63) / 64 + 2);
+    if (pt_kd_semantics(sc.mode)) cap = std::max(cap, (sc.stack_cap + 63) / 64 + 2);
     return cap;
 }
 // pt_stack_column: entries of a lane's HBM stack column (PtStackSpill::gbase). + wave_rows: the wavefront's own stack takes LDS rows from the lanes' stacks (pt_wave_rows,
@@ -1906,6 +1984,27 @@ static size_t pt_stack_column(const PtSceneView& sc, int stack_lds_cap) {
     const int wave_rows = std::min(std::max(8, (sc.stack_cap + 63) / 64), std::max(stack_lds_cap, 8));  // (pt_wave_rows: at most this many)
     const int stack_spill_entries = std::max(sc.stack_cap - stack_lds_cap + wave_rows, 0);
     return (size_t)std::max(stack_spill_entries, sc.stack_cap);
+}
+
+// What a pass's sizing dispatch reads of the host-side fields. The passes that only walk (primary visibility, ray queries): the LDS stack area is sized like a
+// render's for the waves per SIMD the mode's instantiation is compiled for, with no hit frame beside the stacks.
+static void pt_walk_sizing(PtRenderArgs& r, int waves) {
+    r.stack_lds_cap = pt_stack_lds_cap(r.scene, waves == 3 ? 52 * 1024 : 39 * 1024, 0);  // 3 x 52 KB or 4 x 39 KB of the CU's 160 KB
+    r.grid_share = 1;
+}
+// The interpreter passes (radiance, the film's): LDS per block as a render's interpreter kernel has it - three blocks per CU, the stack area beside the hit
+// frame and, in scenes whose hits spawn rays, the youngest parked frame of every lane. Returns which <TEX, PARK> instantiation runs.
+struct PtInterp { bool tex, park; };
+static PtInterp pt_interp_sizing(const pt_context* c, PtRenderArgs& r) {
+    PtInterp k;
+    k.tex = r.scene.mat_maps != nullptr;
+    k.park = c->spawns;
+    if (const char* e = getenv("PORTRAYER_PARK")) k.park = k.park && atoi(e) > 0;  // 0: every parked frame in HBM (tests, measurements), as for a render
+    r.park_slots = k.park ? 1 : 0;
+    const size_t frame_bytes = (size_t)(PT_LDS_FRAME_F64 + r.park_slots * PT_PARK_F64) * PT_BLOCK * 8;
+    r.stack_lds_cap = pt_stack_lds_cap(r.scene, 52 * 1024, frame_bytes);  // 3 x 52 KB of the CU's 160 KB (pt_radiance_waves, pt_film_waves)
+    r.grid_share = 1;
+    return k;
 }
 
 static int pt_render_common(pt_context* c, PtRenderArgs& a, bool stats, hipStream_t stream, int slot_index = -1) {
@@ -1919,7 +2018,7 @@ static int pt_render_common(pt_context* c, PtRenderArgs& a, bool stats, hipStrea
     if (!c->spawns) a.park_slots = 0;
     // Scenes whose hits spawn rays need the interpreter kernel (3 waves per SIMD); the others run the straight-line kernel at 3 or
     // 4 waves per SIMD. PORTRAYER_INTERP=1 (builds with -DPT_KEEP_INTERP): the interpreter on those too, for A/B runs.
-    const bool kd_sem = a.scene.mode == PT_MODE_KD || a.scene.mode == PT_MODE_KD_NOMESH || a.scene.mode == PT_MODE_KD_MESH;
+    const bool kd_sem = pt_kd_semantics(a.scene.mode);
     a.four_waves = (!c->spawns && (c->four_waves || (c->four_waves_untextured && !tex) || c->four_waves_hier)) ? (c->five_waves ? PT_LINE_TOP_WAVES : ((c->five_waves_mesh && !tex) ? PT_MESH_TOP_WAVES : 4)) : 0;
     if (const char* e = getenv("PORTRAYER_WAVES")) {
         const int wv = atoi(e);
@@ -1963,7 +2062,7 @@ static int pt_render_common(pt_context* c, PtRenderArgs& a, bool stats, hipStrea
     size_t block_budget = a.four_waves >= 6 ? 26 * 1024 : (a.four_waves == 5 ? 31 * 1024 : (a.four_waves ? 39 * 1024 : 52 * 1024));  // 3 x 52 KB, 4 x 39 KB, 5 x 31 KB or 6 x 26 KB of the CU's 160 KB
     if (const char* e = getenv("PORTRAYER_LDS_BUDGET_KB")) block_budget = (size_t)std::max(16, std::min(160, atoi(e))) * 1024;  // experiment: 80 = two blocks per CU
     const size_t frame_bytes = (size_t)(PT_LDS_FRAME_F64 + a.park_slots * PT_PARK_F64) * PT_BLOCK * 8;
-    a.stack_lds_cap = pt_stack_lds_cap(a.scene, block_budget, frame_bytes, kd_sem);
+    a.stack_lds_cap = pt_stack_lds_cap(a.scene, block_budget, frame_bytes);
     a.grid_share = 1;  // (a share of the resident blocks per launch was tried for ranks that share a GPU, round 5 c23: their kernels do not run side by side - 35.5 -> 14.3 Gray/s)
     uint32_t grid = 0;
     PT_HIP(c, pt_dispatch(a, stats, c->n_cu, stream, &grid, false));
@@ -2240,17 +2339,7 @@ extern "C" int pt_untile_host(const pt_render_params* p, const uint8_t* gathered
 // Primary visibility (pt_aov.h)
 // ------------------------------------------------------------------------------------------------
 static hipError_t pt_aov_dispatch(const PtAovArgs& a, int n_cu, hipStream_t stream, uint32_t* grid, bool launch) {
-    switch (a.r.scene.mode) {
-    case PT_MODE_KD: return pt_aov_launch_mode_2(a, n_cu, stream, grid, launch);
-    case PT_MODE_FLAT_NOMESH: return pt_aov_launch_mode_3(a, n_cu, stream, grid, launch);
-    case PT_MODE_FLAT_KDMESH: return pt_aov_launch_mode_4(a, n_cu, stream, grid, launch);
-    case PT_MODE_HIER: return pt_aov_launch_mode_5(a, n_cu, stream, grid, launch);
-    case PT_MODE_HIER_NOMESH: return pt_aov_launch_mode_6(a, n_cu, stream, grid, launch);
-    case PT_MODE_KD_NOMESH: return pt_aov_launch_mode_7(a, n_cu, stream, grid, launch);
-    case PT_MODE_HIER_MESH: return pt_aov_launch_mode_8(a, n_cu, stream, grid, launch);
-    case PT_MODE_KD_MESH: return pt_aov_launch_mode_9(a, n_cu, stream, grid, launch);
-    default: return pt_aov_launch_mode_1(a, n_cu, stream, grid, launch);
-    }
+    PT_MODE_LAUNCH(pt_aov_launch_mode_, a.r.scene.mode, a, n_cu, stream, grid, launch)
 }
 
 // Everything that can be refused without a HIP call, in the order the header gives.
@@ -2263,21 +2352,16 @@ static int pt_aov_check(pt_context* c, const pt_camera* cam, const pt_aov_params
     if (p->width == 0 || p->height == 0) return pt_fail(c, PT_ERR_ARGUMENT, "width and height must be positive");
     if (p->slice.x0 >= p->width || p->slice.x1 >= p->width || p->slice.y0 >= p->height || p->slice.y1 >= p->height)
         return pt_fail(c, PT_ERR_SLICE, "slice corner outside the image (render.rs:79-90)");
-    if (c->aov.pending) return pt_fail(c, PT_ERR_ARGUMENT, "a pt_aov_device pass is in flight: pt_aov_finish first");
+    if (c->aov.pass.pending) return pt_fail(c, PT_ERR_ARGUMENT, "a pt_aov_device pass is in flight: pt_aov_finish first");
     return PT_OK;
 }
 
-// Queues the pass on `stream`: work counter + overflow flag zeroed, the kernel between the pass's two events, the flag copied to the pinned page behind it.
-// `out` holds DEVICE pointers. The LDS stack area is sized like a render's (pt_render_common) for the waves per SIMD the instantiation is compiled for, less
-// the hit frame a render keeps there; deeper entries of a lane's stack go to its HBM column.
+// Queues the pass on `stream` (pt_pass_open ... pt_pass_seal): the kernel between the pass's two events, launched only where the slice holds a tile.
+// `out` holds DEVICE pointers. Deeper entries of a lane's stack than its LDS area holds (pt_walk_sizing) go to its HBM column.
 static int pt_aov_common(pt_context* c, const pt_camera* cam, const pt_aov_params* p, const pt_aov_buffers& out, hipStream_t stream) {
-    pt_context::Aov& v = c->aov;
-    if (!v.ev0) {
-        PT_HIP(c, hipEventCreate(&v.ev0));
-        PT_HIP(c, hipEventCreate(&v.ev1));
-        PT_HIP(c, hipEventCreateWithFlags(&v.copy_done, hipEventDisableTiming));
-        PT_HIP(c, hipHostMalloc((void**)&v.host, 256, hipHostMallocDefault));
-    }
+    PtPass& v = c->aov.pass;
+    int rc = pt_pass_prepare(c, v);
+    if (rc) return rc;
     pt_render_params rp;
     memset(&rp, 0, sizeof rp);
     rp.width = p->width; rp.height = p->height; rp.slice = p->slice;
@@ -2286,55 +2370,12 @@ static int pt_aov_common(pt_context* c, const pt_camera* cam, const pt_aov_param
     pt_fill_args(c, cam, &rp, &a.r);  // samples = 1: one work item per 8x8 tile of the slice
     a.off_x = p->offset[0]; a.off_y = p->offset[1];
     a.depth = out.depth; a.position = out.position; a.normal = out.normal; a.node = out.node; a.sub = out.sub; a.material = out.material;
-    const int mode = a.r.scene.mode;
-    const bool kd_sem = mode == PT_MODE_KD || mode == PT_MODE_KD_NOMESH || mode == PT_MODE_KD_MESH;
-    const size_t block_budget = pt_aov_waves(mode) == 3 ? 52 * 1024 : 39 * 1024;  // 3 x 52 KB or 4 x 39 KB of the CU's 160 KB, as for a render; no hit frame beside the stacks
-    a.r.stack_lds_cap = pt_stack_lds_cap(a.r.scene, block_budget, 0, kd_sem);
-    a.r.grid_share = 1;
+    pt_walk_sizing(a.r, pt_aov_waves(a.r.scene.mode));
     uint32_t grid = 0;
     PT_HIP(c, pt_aov_dispatch(a, c->n_cu, stream, &grid, false));
-    a.r.n_lanes = grid * PT_BLOCK;
-    const size_t stack_column = pt_stack_column(a.r.scene, a.r.stack_lds_cap);
-    int rc;
-    const size_t aov_misc_bytes = 256 + PT_FINE_QUEUES * PT_QUEUE_STRIDE * 4;  // the overflow flag (word 1, where a render has it), the work queues
-    if ((rc = pt_reserve(c, v.stack_spill, (size_t)a.r.n_lanes * stack_column * 4)) || (rc = pt_reserve(c, v.misc, aov_misc_bytes))) return rc;
-    a.r.stack_spill = (uint32_t*)v.stack_spill.p;
-    a.r.overflow_flag = (unsigned int*)v.misc.p + 1;
-    a.r.work_queues = (unsigned int*)((char*)v.misc.p + 256);
-    a.r.fine_queues = 16;  // as a render of this size (pt_render_common)
-    v.stream = stream; v.queued = true; v.closed = false;  // from here on something of the pass may be in flight on `stream`, whatever fails below
-    PT_HIP(c, hipMemsetAsync(v.misc.p, 0, aov_misc_bytes, stream));
-    PT_HIP(c, hipEventRecord(v.ev0, stream));
+    if ((rc = pt_pass_open(c, v, a.r, grid, false, stream))) return rc;
     if (a.r.n_items) PT_HIP(c, pt_aov_dispatch(a, c->n_cu, stream, &grid, true));
-    PT_HIP(c, hipEventRecord(v.ev1, stream));
-    PT_HIP(c, hipMemcpyAsync(v.host, v.misc.p, 8, hipMemcpyDeviceToHost, stream));
-    PT_HIP(c, hipEventRecord(v.copy_done, stream));
-    v.closed = true;
-    return PT_OK;
-}
-
-// Waits for whatever the last pt_aov_common queued: the event behind its last copy, or - where queuing failed half way - its stream.
-static int pt_aov_wait(pt_context* c) {
-    pt_context::Aov& v = c->aov;
-    if (!v.queued) return PT_OK;
-    v.queued = false;
-    if (v.closed) PT_HIP(c, hipEventSynchronize(v.copy_done));
-    else PT_HIP(c, hipStreamSynchronize(v.stream));
-    return PT_OK;
-}
-
-// After the pass's copy_done: the kernel time and what the overflow flag says (as pt_collect_stats reads a render's).
-static int pt_aov_close(pt_context* c, double* kernel_ms) {
-    unsigned int head[2];
-    memcpy(head, c->aov.host, sizeof head);
-    if (kernel_ms) {
-        float ms = 0.f;
-        PT_HIP(c, hipEventElapsedTime(&ms, c->aov.ev0, c->aov.ev1));
-        *kernel_ms = ms;
-    }
-    if (head[1] & 4u) return pt_fail(c, PT_ERR_TRAVERSAL, "a tree walk did not end (watchdog): results invalid");
-    if (head[1]) return pt_fail(c, PT_ERR_TRAVERSAL, "traversal stack overflow");
-    return PT_OK;
+    return pt_pass_seal(c, v);
 }
 
 extern "C" int pt_aov(pt_context* c, const pt_camera* cam, const pt_aov_params* p, const pt_aov_buffers* host_out, double* kernel_ms) {
@@ -2353,9 +2394,7 @@ extern "C" int pt_aov(pt_context* c, const pt_camera* cam, const pt_aov_params* 
     pt_aov_buffers d_out;
     d_out.depth = (double*)dev[0]; d_out.position = (double*)dev[1]; d_out.normal = (double*)dev[2];
     d_out.node = (int32_t*)dev[3]; d_out.sub = (int32_t*)dev[4]; d_out.material = (int32_t*)dev[5];
-    rc = pt_aov_common(c, cam, p, d_out, nullptr);
-    const int rc_wait = pt_aov_wait(c);
-    if (rc || (rc = rc_wait)) return rc;
+    if ((rc = pt_pass_settle(c, c->aov.pass, pt_aov_common(c, cam, p, d_out, nullptr)))) return rc;
     // Only the slice's rectangle comes back (the kernel wrote nothing else, and the device copies hold nothing else of value): picking one pixel of a
     // 1920x1080 frame moves 68 bytes, and pixels outside the slice keep the caller's bytes because they are never touched.
     if (p->slice.x1 >= p->slice.x0 && p->slice.y1 >= p->slice.y0) {
@@ -2366,61 +2405,31 @@ extern "C" int pt_aov(pt_context* c, const pt_camera* cam, const pt_aov_params* 
             PT_HIP(c, hipMemcpy2D((char*)host[k] + first, pitch, (const char*)dev[k] + first, pitch, cols * elem[k], rows, hipMemcpyDeviceToHost));
         }
     }
-    return pt_aov_close(c, kernel_ms);
+    return pt_pass_result(c, c->aov.pass, kernel_ms);
 }
 
 extern "C" int pt_aov_device(pt_context* c, const pt_camera* cam, const pt_aov_params* p, const pt_aov_buffers* device_out, void* hip_stream) {
     int rc = pt_aov_check(c, cam, p, device_out);
     if (rc) return rc;
     PT_HIP(c, hipSetDevice(c->device));
-    if ((rc = pt_aov_common(c, cam, p, *device_out, (hipStream_t)hip_stream))) {
-        pt_aov_wait(c);  // what was queued before the failure must not outlive the call: the next pass may reallocate the buffers under it
-        return rc;
-    }
-    c->aov.pending = true;
-    return PT_OK;
+    return pt_pass_device_tail(c, c->aov.pass, pt_aov_common(c, cam, p, *device_out, (hipStream_t)hip_stream));
 }
 
 extern "C" int pt_aov_finish(pt_context* c, double* kernel_ms) {
     if (!c) return PT_ERR_ARGUMENT;
-    if (!c->aov.pending) return pt_fail(c, PT_ERR_ARGUMENT, "no pt_aov_device pass in flight");
-    PT_HIP(c, hipSetDevice(c->device));
-    c->aov.pending = false;
-    int rc = pt_aov_wait(c);
-    if (rc) return rc;
-    return pt_aov_close(c, kernel_ms);
+    return pt_pass_finish(c, c->aov.pass, "no pt_aov_device pass in flight", kernel_ms);
 }
 
 // ------------------------------------------------------------------------------------------------
 // Ray queries (pt_rays.h)
 // ------------------------------------------------------------------------------------------------
 static hipError_t pt_rays_dispatch(const PtRaysArgs& a, int n_cu, hipStream_t stream, uint32_t* grid, bool launch) {
-    switch (a.r.scene.mode) {
-    case PT_MODE_KD: return pt_rays_launch_mode_2(a, n_cu, stream, grid, launch);
-    case PT_MODE_FLAT_NOMESH: return pt_rays_launch_mode_3(a, n_cu, stream, grid, launch);
-    case PT_MODE_FLAT_KDMESH: return pt_rays_launch_mode_4(a, n_cu, stream, grid, launch);
-    case PT_MODE_HIER: return pt_rays_launch_mode_5(a, n_cu, stream, grid, launch);
-    case PT_MODE_HIER_NOMESH: return pt_rays_launch_mode_6(a, n_cu, stream, grid, launch);
-    case PT_MODE_KD_NOMESH: return pt_rays_launch_mode_7(a, n_cu, stream, grid, launch);
-    case PT_MODE_HIER_MESH: return pt_rays_launch_mode_8(a, n_cu, stream, grid, launch);
-    case PT_MODE_KD_MESH: return pt_rays_launch_mode_9(a, n_cu, stream, grid, launch);
-    default: return pt_rays_launch_mode_1(a, n_cu, stream, grid, launch);
-    }
+    PT_MODE_LAUNCH(pt_rays_launch_mode_, a.r.scene.mode, a, n_cu, stream, grid, launch)
 }
 
 // The bounded-segment form of the pass (pt_segments.h): the same arguments and a bound per ray.
 static hipError_t pt_segments_dispatch(const PtSegmentsArgs& a, int n_cu, hipStream_t stream, uint32_t* grid, bool launch) {
-    switch (a.q.r.scene.mode) {
-    case PT_MODE_KD: return pt_segments_launch_mode_2(a, n_cu, stream, grid, launch);
-    case PT_MODE_FLAT_NOMESH: return pt_segments_launch_mode_3(a, n_cu, stream, grid, launch);
-    case PT_MODE_FLAT_KDMESH: return pt_segments_launch_mode_4(a, n_cu, stream, grid, launch);
-    case PT_MODE_HIER: return pt_segments_launch_mode_5(a, n_cu, stream, grid, launch);
-    case PT_MODE_HIER_NOMESH: return pt_segments_launch_mode_6(a, n_cu, stream, grid, launch);
-    case PT_MODE_KD_NOMESH: return pt_segments_launch_mode_7(a, n_cu, stream, grid, launch);
-    case PT_MODE_HIER_MESH: return pt_segments_launch_mode_8(a, n_cu, stream, grid, launch);
-    case PT_MODE_KD_MESH: return pt_segments_launch_mode_9(a, n_cu, stream, grid, launch);
-    default: return pt_segments_launch_mode_1(a, n_cu, stream, grid, launch);
-    }
+    PT_MODE_LAUNCH(pt_segments_launch_mode_, a.q.r.scene.mode, a, n_cu, stream, grid, launch)
 }
 
 // Everything that can be refused without a HIP call, in the order the header gives. (pt_fail takes a NULL context.)
@@ -2433,7 +2442,7 @@ static int pt_rays_check(pt_context* c, const pt_rays_params* p, const double* o
     if (p->any_hit && (out->t || out->position || out->normal || out->node || out->sub || out->material))
         return pt_fail(c, PT_ERR_ARGUMENT, "pt_rays: an occlusion query (any_hit = 1) answers `occluded` only");
     if (!c->have_scene) return pt_fail(c, PT_ERR_NO_SCENE, "no scene uploaded");
-    if (c->rays.pending) return pt_fail(c, PT_ERR_ARGUMENT, "a pt_rays_device / pt_segments_device pass is in flight: pt_rays_finish first");
+    if (c->rays.pass.pending) return pt_fail(c, PT_ERR_ARGUMENT, "a pt_rays_device / pt_segments_device pass is in flight: pt_rays_finish first");
     return PT_OK;
 }
 
@@ -2443,29 +2452,38 @@ static int pt_segments_check(pt_context* c, const pt_rays_params* p, const doubl
     return pt_rays_check(c, p, origins, directions, out);
 }
 
-// Queues the pass on `stream`: queues + overflow flag zeroed; between the pass's two events the keying and the sort (reorder = 1) and the cast kernel; the flag
-// copied to the pinned page behind them. Every pointer is a DEVICE pointer. The LDS stack area is sized as for the primary-visibility pass (pt_aov_common).
+// reorder = 1: the buffers for n rays, and *perm (slot -> ray index) pointed at where the sort will leave it ...
+static int pt_ray_sort_reserve(pt_context* c, PtRaySort& s, uint64_t n, const uint32_t** perm) {
+    PT_HIP(c, pt_rays_sort_bytes(n, &s.tmp_bytes));
+    int rc;
+    if ((rc = pt_reserve(c, s.keys[0], n * 8)) || (rc = pt_reserve(c, s.keys[1], n * 8)) || (rc = pt_reserve(c, s.vals[0], n * 4)) || (rc = pt_reserve(c, s.vals[1], n * 4)) ||
+        (rc = pt_reserve(c, s.tmp, s.tmp_bytes)))
+        return rc;
+    *perm = (const uint32_t*)s.vals[1].p;
+    return PT_OK;
+}
+// ... and the keying and the sort on `stream`, behind the pass's first event.
+static int pt_ray_sort_queue(pt_context* c, PtRaySort& s, uint64_t n, const double* d_origins, const double* d_directions, hipStream_t stream) {
+    PT_HIP(c, pt_rays_sort(n, d_origins, d_directions, c->root_lo, c->root_hi, (unsigned long long*)s.keys[0].p, (unsigned long long*)s.keys[1].p, (uint32_t*)s.vals[0].p,
+                           (uint32_t*)s.vals[1].p, s.tmp.p, s.tmp_bytes, stream));
+    return PT_OK;
+}
+
+// Queues the pass on `stream` (pt_pass_open ... pt_pass_seal): between the pass's two events the keying and the sort (reorder = 1) and the cast kernel.
+// Every pointer is a DEVICE pointer. The LDS stack area is sized as for the primary-visibility pass (pt_walk_sizing).
 // d_t_max: null = pt_rays' kernel; else the bounded-segment kernel (pt_segments), which takes the same arguments and that array.
 static int pt_rays_common(pt_context* c, const pt_rays_params* p, const double* d_origins, const double* d_directions, const pt_rays_buffers& out, hipStream_t stream,
                           const double* d_t_max = nullptr) {
-    pt_context::Rays& v = c->rays;
-    if (!v.ev0) {
-        PT_HIP(c, hipEventCreate(&v.ev0));
-        PT_HIP(c, hipEventCreate(&v.ev1));
-        PT_HIP(c, hipEventCreateWithFlags(&v.copy_done, hipEventDisableTiming));
-        PT_HIP(c, hipHostMalloc((void**)&v.host, 256, hipHostMallocDefault));
-    }
+    PtPass& v = c->rays.pass;
+    int rc = pt_pass_prepare(c, v);
+    if (rc) return rc;
     PtRaysArgs a;
     memset(&a, 0, sizeof a);
     a.r.scene = c->view;
     a.r.n_items = (uint32_t)((p->n + 63u) / 64u);  // (n <= PT_RAYS_MAX = 2^30)
     a.n = p->n; a.origins = d_origins; a.directions = d_directions; a.any = p->any_hit;
     a.t = out.t; a.position = out.position; a.normal = out.normal; a.node = out.node; a.sub = out.sub; a.material = out.material; a.occluded = out.occluded;
-    const int mode = a.r.scene.mode;
-    const bool kd_sem = mode == PT_MODE_KD || mode == PT_MODE_KD_NOMESH || mode == PT_MODE_KD_MESH;
-    const size_t block_budget = pt_rays_waves(mode) == 3 ? 52 * 1024 : 39 * 1024;  // 3 x 52 KB or 4 x 39 KB of the CU's 160 KB
-    a.r.stack_lds_cap = pt_stack_lds_cap(a.r.scene, block_budget, 0, kd_sem);
-    a.r.grid_share = 1;
+    pt_walk_sizing(a.r, pt_rays_waves(a.r.scene.mode));
     uint32_t grid = 0;
     auto dispatch = [&](bool launch) -> hipError_t {  // (the segments kernel's argument block is built from `a` as it stands at the call)
         if (!d_t_max) return pt_rays_dispatch(a, c->n_cu, stream, &grid, launch);
@@ -2474,58 +2492,11 @@ static int pt_rays_common(pt_context* c, const pt_rays_params* p, const double* 
         return pt_segments_dispatch(s, c->n_cu, stream, &grid, launch);
     };
     PT_HIP(c, dispatch(false));
-    a.r.n_lanes = grid * PT_BLOCK;
-    const size_t stack_column = pt_stack_column(a.r.scene, a.r.stack_lds_cap);
-    int rc;
-    const size_t misc_bytes = 256 + PT_FINE_QUEUES * PT_QUEUE_STRIDE * 4;  // the overflow flag (word 1, where a render has it), the work queues
-    if ((rc = pt_reserve(c, v.stack_spill, (size_t)a.r.n_lanes * stack_column * 4)) || (rc = pt_reserve(c, v.misc, misc_bytes))) return rc;
-    size_t sort_bytes = 0;
-    if (p->reorder) {
-        PT_HIP(c, pt_rays_sort_bytes(p->n, &sort_bytes));
-        if ((rc = pt_reserve(c, v.keys[0], p->n * 8)) || (rc = pt_reserve(c, v.keys[1], p->n * 8)) || (rc = pt_reserve(c, v.vals[0], p->n * 4)) ||
-            (rc = pt_reserve(c, v.vals[1], p->n * 4)) || (rc = pt_reserve(c, v.sort_tmp, sort_bytes)))
-            return rc;
-        a.perm = (const uint32_t*)v.vals[1].p;
-    }
-    a.r.stack_spill = (uint32_t*)v.stack_spill.p;
-    a.r.overflow_flag = (unsigned int*)v.misc.p + 1;
-    a.r.work_queues = (unsigned int*)((char*)v.misc.p + 256);
-    a.r.fine_queues = 16;  // as the primary-visibility pass
-    v.stream = stream; v.queued = true; v.closed = false;  // from here on something of the pass may be in flight on `stream`, whatever fails below
-    PT_HIP(c, hipMemsetAsync(v.misc.p, 0, misc_bytes, stream));
-    PT_HIP(c, hipEventRecord(v.ev0, stream));
-    if (p->reorder)
-        PT_HIP(c, pt_rays_sort(p->n, d_origins, d_directions, c->root_lo, c->root_hi, (unsigned long long*)v.keys[0].p, (unsigned long long*)v.keys[1].p, (uint32_t*)v.vals[0].p,
-                               (uint32_t*)v.vals[1].p, v.sort_tmp.p, sort_bytes, stream));
+    if (p->reorder && (rc = pt_ray_sort_reserve(c, c->rays.sort, p->n, &a.perm))) return rc;
+    if ((rc = pt_pass_open(c, v, a.r, grid, false, stream))) return rc;
+    if (p->reorder && (rc = pt_ray_sort_queue(c, c->rays.sort, p->n, d_origins, d_directions, stream))) return rc;
     PT_HIP(c, dispatch(true));
-    PT_HIP(c, hipEventRecord(v.ev1, stream));
-    PT_HIP(c, hipMemcpyAsync(v.host, v.misc.p, 8, hipMemcpyDeviceToHost, stream));
-    PT_HIP(c, hipEventRecord(v.copy_done, stream));
-    v.closed = true;
-    return PT_OK;
-}
-
-// Waits for whatever the last pt_rays_common queued: the event behind its last copy, or - where queuing failed half way - its stream.
-static int pt_rays_wait(pt_context* c) {
-    pt_context::Rays& v = c->rays;
-    if (!v.queued) return PT_OK;
-    v.queued = false;
-    if (v.closed) PT_HIP(c, hipEventSynchronize(v.copy_done));
-    else PT_HIP(c, hipStreamSynchronize(v.stream));
-    return PT_OK;
-}
-
-static int pt_rays_close(pt_context* c, double* kernel_ms) {
-    unsigned int head[2];
-    memcpy(head, c->rays.host, sizeof head);
-    if (kernel_ms) {
-        float ms = 0.f;
-        PT_HIP(c, hipEventElapsedTime(&ms, c->rays.ev0, c->rays.ev1));
-        *kernel_ms = ms;
-    }
-    if (head[1] & 4u) return pt_fail(c, PT_ERR_TRAVERSAL, "a tree walk did not end (watchdog): results invalid");
-    if (head[1]) return pt_fail(c, PT_ERR_TRAVERSAL, "traversal stack overflow");
-    return PT_OK;
+    return pt_pass_seal(c, v);
 }
 
 // The host-buffer path of pt_rays (t_max null) and pt_segments: upload, pass, copy back.
@@ -2552,24 +2523,17 @@ static int pt_rays_host(pt_context* c, const pt_rays_params* p, const double* or
     d_out.t = (double*)dev[0]; d_out.position = (double*)dev[1]; d_out.normal = (double*)dev[2];
     d_out.node = (int32_t*)dev[3]; d_out.sub = (int32_t*)dev[4]; d_out.material = (int32_t*)dev[5]; d_out.occluded = (uint8_t*)dev[6];
     rc = pt_rays_common(c, p, (const double*)c->rays.in[0].p, (const double*)c->rays.in[1].p, d_out, nullptr, t_max ? (const double*)c->rays.in_t_max.p : nullptr);
-    const int rc_wait = pt_rays_wait(c);
-    if (rc || (rc = rc_wait)) return rc;
+    if ((rc = pt_pass_settle(c, c->rays.pass, rc))) return rc;
     for (int k = 0; k < 7; k++)
         if (host[k]) PT_HIP(c, hipMemcpy(host[k], dev[k], n * elem[k], hipMemcpyDeviceToHost));
-    return pt_rays_close(c, kernel_ms);
+    return pt_pass_result(c, c->rays.pass, kernel_ms);
 }
 
 // ... and the device-buffer path of both.
 static int pt_rays_queue(pt_context* c, const pt_rays_params* p, const double* d_origins, const double* d_directions, const double* d_t_max, const pt_rays_buffers* device_out, void* hip_stream) {
     if (p->n == 0) return PT_OK;  // nothing queued, nothing to finish
     PT_HIP(c, hipSetDevice(c->device));
-    int rc;
-    if ((rc = pt_rays_common(c, p, d_origins, d_directions, *device_out, (hipStream_t)hip_stream, d_t_max))) {
-        pt_rays_wait(c);  // what was queued before the failure must not outlive the call: the next pass may reallocate the buffers under it
-        return rc;
-    }
-    c->rays.pending = true;
-    return PT_OK;
+    return pt_pass_device_tail(c, c->rays.pass, pt_rays_common(c, p, d_origins, d_directions, *device_out, (hipStream_t)hip_stream, d_t_max));
 }
 
 extern "C" int pt_rays(pt_context* c, const pt_rays_params* p, const double* origins, const double* directions, const pt_rays_buffers* host_out, double* kernel_ms) {
@@ -2598,29 +2562,14 @@ extern "C" int pt_segments_device(pt_context* c, const pt_rays_params* p, const 
 
 extern "C" int pt_rays_finish(pt_context* c, double* kernel_ms) {
     if (!c) return PT_ERR_ARGUMENT;
-    if (!c->rays.pending) return pt_fail(c, PT_ERR_ARGUMENT, "no pt_rays_device / pt_segments_device pass in flight");
-    PT_HIP(c, hipSetDevice(c->device));
-    c->rays.pending = false;
-    int rc = pt_rays_wait(c);
-    if (rc) return rc;
-    return pt_rays_close(c, kernel_ms);
+    return pt_pass_finish(c, c->rays.pass, "no pt_rays_device / pt_segments_device pass in flight", kernel_ms);
 }
 
 // ------------------------------------------------------------------------------------------------
 // Radiance along the caller's rays (pt_radiance.h)
 // ------------------------------------------------------------------------------------------------
 static hipError_t pt_radiance_dispatch(const PtRadianceArgs& a, bool tex, bool park, int n_cu, hipStream_t stream, uint32_t* grid, bool launch) {
-    switch (a.r.scene.mode) {
-    case PT_MODE_KD: return pt_radiance_launch_mode_2(a, tex, park, n_cu, stream, grid, launch);
-    case PT_MODE_FLAT_NOMESH: return pt_radiance_launch_mode_3(a, tex, park, n_cu, stream, grid, launch);
-    case PT_MODE_FLAT_KDMESH: return pt_radiance_launch_mode_4(a, tex, park, n_cu, stream, grid, launch);
-    case PT_MODE_HIER: return pt_radiance_launch_mode_5(a, tex, park, n_cu, stream, grid, launch);
-    case PT_MODE_HIER_NOMESH: return pt_radiance_launch_mode_6(a, tex, park, n_cu, stream, grid, launch);
-    case PT_MODE_KD_NOMESH: return pt_radiance_launch_mode_7(a, tex, park, n_cu, stream, grid, launch);
-    case PT_MODE_HIER_MESH: return pt_radiance_launch_mode_8(a, tex, park, n_cu, stream, grid, launch);
-    case PT_MODE_KD_MESH: return pt_radiance_launch_mode_9(a, tex, park, n_cu, stream, grid, launch);
-    default: return pt_radiance_launch_mode_1(a, tex, park, n_cu, stream, grid, launch);
-    }
+    PT_MODE_LAUNCH(pt_radiance_launch_mode_, a.r.scene.mode, a, tex, park, n_cu, stream, grid, launch)
 }
 
 // Everything that can be refused without a HIP call, in the order the header gives. (pt_fail takes a NULL context.)
@@ -2630,21 +2579,16 @@ static int pt_radiance_check(pt_context* c, const pt_radiance_params* p, const d
     if ((p->reorder != 0 && p->reorder != 1) || (p->background_per_ray != 0 && p->background_per_ray != 1))
         return pt_fail(c, PT_ERR_ARGUMENT, "pt_radiance: reorder and background_per_ray are 0 or 1");
     if (!c->have_scene) return pt_fail(c, PT_ERR_NO_SCENE, "no scene uploaded");
-    if (c->radiance.pending) return pt_fail(c, PT_ERR_ARGUMENT, "a pt_radiance_device pass is in flight: pt_radiance_finish first");
+    if (c->radiance.pass.pending) return pt_fail(c, PT_ERR_ARGUMENT, "a pt_radiance_device pass is in flight: pt_radiance_finish first");
     return PT_OK;
 }
 
-// Queues the pass on `stream`: queues + overflow flag zeroed; between the pass's two events the keying and the sort (reorder = 1) and the shading kernel; the flag
-// copied to the pinned page behind them. Every pointer is a DEVICE pointer. LDS per block as a render's interpreter kernel has it (pt_render_common): three blocks
-// per CU, the stack area beside the hit frame and - scenes whose hits spawn rays - one parked frame per lane.
+// Queues the pass on `stream` (pt_pass_open ... pt_pass_seal): between the pass's two events the keying and the sort (reorder = 1) and the shading kernel.
+// Every pointer is a DEVICE pointer. LDS per block as a render's interpreter kernel has it (pt_interp_sizing).
 static int pt_radiance_common(pt_context* c, const pt_radiance_params* p, const double* d_origins, const double* d_directions, const double* d_background, double* d_rgb, hipStream_t stream) {
-    pt_context::Radiance& v = c->radiance;
-    if (!v.ev0) {
-        PT_HIP(c, hipEventCreate(&v.ev0));
-        PT_HIP(c, hipEventCreate(&v.ev1));
-        PT_HIP(c, hipEventCreateWithFlags(&v.copy_done, hipEventDisableTiming));
-        PT_HIP(c, hipHostMalloc((void**)&v.host, 256, hipHostMallocDefault));
-    }
+    PtPass& v = c->radiance.pass;
+    int rc = pt_pass_prepare(c, v);
+    if (rc) return rc;
     PtRadianceArgs a;
     memset(&a, 0, sizeof a);  // (no occluder table, no counters, no work counter: null)
     a.r.scene = c->view;
@@ -2652,71 +2596,14 @@ static int pt_radiance_common(pt_context* c, const pt_radiance_params* p, const 
     a.r.n_items = (uint32_t)((p->n + 63u) / 64u);  // (n <= PT_RAYS_MAX = 2^30)
     a.n = p->n; a.origins = d_origins; a.directions = d_directions; a.background = d_background; a.bg_stride = p->background_per_ray ? 3u : 0u;
     a.sample = p->sample; a.stream_base = p->stream_base; a.rgb = d_rgb;
-    const int mode = a.r.scene.mode;
-    const bool kd_sem = mode == PT_MODE_KD || mode == PT_MODE_KD_NOMESH || mode == PT_MODE_KD_MESH;
-    const bool tex = a.r.scene.mat_maps != nullptr;
-    bool park = c->spawns;  // scenes whose hits spawn rays: the youngest parked frame of a lane in LDS, as a render has it
-    if (const char* e = getenv("PORTRAYER_PARK")) park = park && atoi(e) > 0;  // 0: every parked frame in HBM (tests, measurements), as for a render
-    a.r.park_slots = park ? 1 : 0;
-    const size_t frame_bytes = (size_t)(PT_LDS_FRAME_F64 + a.r.park_slots * PT_PARK_F64) * PT_BLOCK * 8;
-    a.r.stack_lds_cap = pt_stack_lds_cap(a.r.scene, 52 * 1024, frame_bytes, kd_sem);  // 3 x 52 KB of the CU's 160 KB (pt_radiance_waves)
-    a.r.grid_share = 1;
+    const PtInterp k = pt_interp_sizing(c, a.r);
     uint32_t grid = 0;
-    PT_HIP(c, pt_radiance_dispatch(a, tex, park, c->n_cu, stream, &grid, false));
-    a.r.n_lanes = grid * PT_BLOCK;
-    const size_t stack_column = pt_stack_column(a.r.scene, a.r.stack_lds_cap);
-    const size_t spill_bytes = c->needs_spill ? (size_t)a.r.n_lanes * PT_SPILL_DEPTHS * PT_SPILL_STRIDE * sizeof(double) : 16;
-    int rc;
-    const size_t misc_bytes = 256 + PT_FINE_QUEUES * PT_QUEUE_STRIDE * 4;  // the overflow flag (word 1, where a render has it), the work queues
-    if ((rc = pt_reserve(c, v.stack_spill, (size_t)a.r.n_lanes * stack_column * 4)) || (rc = pt_reserve(c, v.spill, spill_bytes)) || (rc = pt_reserve(c, v.misc, misc_bytes))) return rc;
-    size_t sort_bytes = 0;
-    if (p->reorder) {
-        PT_HIP(c, pt_rays_sort_bytes(p->n, &sort_bytes));
-        if ((rc = pt_reserve(c, v.keys[0], p->n * 8)) || (rc = pt_reserve(c, v.keys[1], p->n * 8)) || (rc = pt_reserve(c, v.vals[0], p->n * 4)) ||
-            (rc = pt_reserve(c, v.vals[1], p->n * 4)) || (rc = pt_reserve(c, v.sort_tmp, sort_bytes)))
-            return rc;
-        a.perm = (const uint32_t*)v.vals[1].p;
-    }
-    a.r.stack_spill = (uint32_t*)v.stack_spill.p;
-    a.r.spill = (double*)v.spill.p;
-    a.r.overflow_flag = (unsigned int*)v.misc.p + 1;
-    a.r.work_queues = (unsigned int*)((char*)v.misc.p + 256);
-    a.r.fine_queues = 16;  // one item at a time, as every pass whose items differ in cost by orders of magnitude
-    v.stream = stream; v.queued = true; v.closed = false;  // from here on something of the pass may be in flight on `stream`, whatever fails below
-    PT_HIP(c, hipMemsetAsync(v.misc.p, 0, misc_bytes, stream));
-    PT_HIP(c, hipEventRecord(v.ev0, stream));
-    if (p->reorder)
-        PT_HIP(c, pt_rays_sort(p->n, d_origins, d_directions, c->root_lo, c->root_hi, (unsigned long long*)v.keys[0].p, (unsigned long long*)v.keys[1].p, (uint32_t*)v.vals[0].p,
-                               (uint32_t*)v.vals[1].p, v.sort_tmp.p, sort_bytes, stream));
-    PT_HIP(c, pt_radiance_dispatch(a, tex, park, c->n_cu, stream, &grid, true));
-    PT_HIP(c, hipEventRecord(v.ev1, stream));
-    PT_HIP(c, hipMemcpyAsync(v.host, v.misc.p, 8, hipMemcpyDeviceToHost, stream));
-    PT_HIP(c, hipEventRecord(v.copy_done, stream));
-    v.closed = true;
-    return PT_OK;
-}
-
-// Waits for whatever the last pt_radiance_common queued: the event behind its last copy, or - where queuing failed half way - its stream.
-static int pt_radiance_wait(pt_context* c) {
-    pt_context::Radiance& v = c->radiance;
-    if (!v.queued) return PT_OK;
-    v.queued = false;
-    if (v.closed) PT_HIP(c, hipEventSynchronize(v.copy_done));
-    else PT_HIP(c, hipStreamSynchronize(v.stream));
-    return PT_OK;
-}
-
-static int pt_radiance_close(pt_context* c, double* kernel_ms) {
-    unsigned int head[2];
-    memcpy(head, c->radiance.host, sizeof head);
-    if (kernel_ms) {
-        float ms = 0.f;
-        PT_HIP(c, hipEventElapsedTime(&ms, c->radiance.ev0, c->radiance.ev1));
-        *kernel_ms = ms;
-    }
-    if (head[1] & 4u) return pt_fail(c, PT_ERR_TRAVERSAL, "a tree walk did not end (watchdog): results invalid");
-    if (head[1]) return pt_fail(c, PT_ERR_TRAVERSAL, "traversal stack overflow");
-    return PT_OK;
+    PT_HIP(c, pt_radiance_dispatch(a, k.tex, k.park, c->n_cu, stream, &grid, false));
+    if (p->reorder && (rc = pt_ray_sort_reserve(c, c->radiance.sort, p->n, &a.perm))) return rc;
+    if ((rc = pt_pass_open(c, v, a.r, grid, true, stream))) return rc;
+    if (p->reorder && (rc = pt_ray_sort_queue(c, c->radiance.sort, p->n, d_origins, d_directions, stream))) return rc;
+    PT_HIP(c, pt_radiance_dispatch(a, k.tex, k.park, c->n_cu, stream, &grid, true));
+    return pt_pass_seal(c, v);
 }
 
 extern "C" int pt_radiance(pt_context* c, const pt_radiance_params* p, const double* origins, const double* directions, const double* background, double* rgb, double* kernel_ms) {
@@ -2732,10 +2619,9 @@ extern "C" int pt_radiance(pt_context* c, const pt_radiance_params* p, const dou
     PT_HIP(c, hipMemcpy(v.in[1].p, directions, n * 24, hipMemcpyHostToDevice));
     PT_HIP(c, hipMemcpy(v.in[2].p, background, bg_bytes, hipMemcpyHostToDevice));
     rc = pt_radiance_common(c, p, (const double*)v.in[0].p, (const double*)v.in[1].p, (const double*)v.in[2].p, (double*)v.out.p, nullptr);
-    const int rc_wait = pt_radiance_wait(c);
-    if (rc || (rc = rc_wait)) return rc;
+    if ((rc = pt_pass_settle(c, v.pass, rc))) return rc;
     PT_HIP(c, hipMemcpy(rgb, v.out.p, n * 24, hipMemcpyDeviceToHost));
-    return pt_radiance_close(c, kernel_ms);
+    return pt_pass_result(c, v.pass, kernel_ms);
 }
 
 extern "C" int pt_radiance_device(pt_context* c, const pt_radiance_params* p, const double* d_origins, const double* d_directions, const double* d_background, double* d_rgb, void* hip_stream) {
@@ -2743,40 +2629,21 @@ extern "C" int pt_radiance_device(pt_context* c, const pt_radiance_params* p, co
     if (rc) return rc;
     if (p->n == 0) return PT_OK;  // nothing queued, nothing to finish
     PT_HIP(c, hipSetDevice(c->device));
-    if ((rc = pt_radiance_common(c, p, d_origins, d_directions, d_background, d_rgb, (hipStream_t)hip_stream))) {
-        pt_radiance_wait(c);  // what was queued before the failure must not outlive the call: the next pass may reallocate the buffers under it
-        return rc;
-    }
-    c->radiance.pending = true;
-    return PT_OK;
+    return pt_pass_device_tail(c, c->radiance.pass, pt_radiance_common(c, p, d_origins, d_directions, d_background, d_rgb, (hipStream_t)hip_stream));
 }
 
 extern "C" int pt_radiance_finish(pt_context* c, double* kernel_ms) {
     if (!c) return PT_ERR_ARGUMENT;
-    if (!c->radiance.pending) return pt_fail(c, PT_ERR_ARGUMENT, "no pt_radiance_device pass in flight");
-    PT_HIP(c, hipSetDevice(c->device));
-    c->radiance.pending = false;
-    c->film_open = nullptr;
-    int rc = pt_radiance_wait(c);
-    if (rc) return rc;
-    return pt_radiance_close(c, kernel_ms);
+    const int rc = pt_pass_finish(c, c->radiance.pass, "no pt_radiance_device pass in flight", kernel_ms);
+    if (!c->radiance.pass.pending) c->film_open = nullptr;  // (a film's pass is closed here too)
+    return rc;
 }
 
 // ------------------------------------------------------------------------------------------------
 // Film: samples accumulate on the device (pt_film.h, pt_film.hip)
 // ------------------------------------------------------------------------------------------------
 static hipError_t pt_film_dispatch(const PtFilmArgs& a, bool tex, bool park, int n_cu, hipStream_t stream, uint32_t* grid, bool launch) {
-    switch (a.r.scene.mode) {
-    case PT_MODE_KD: return pt_film_launch_mode_2(a, tex, park, n_cu, stream, grid, launch);
-    case PT_MODE_FLAT_NOMESH: return pt_film_launch_mode_3(a, tex, park, n_cu, stream, grid, launch);
-    case PT_MODE_FLAT_KDMESH: return pt_film_launch_mode_4(a, tex, park, n_cu, stream, grid, launch);
-    case PT_MODE_HIER: return pt_film_launch_mode_5(a, tex, park, n_cu, stream, grid, launch);
-    case PT_MODE_HIER_NOMESH: return pt_film_launch_mode_6(a, tex, park, n_cu, stream, grid, launch);
-    case PT_MODE_KD_NOMESH: return pt_film_launch_mode_7(a, tex, park, n_cu, stream, grid, launch);
-    case PT_MODE_HIER_MESH: return pt_film_launch_mode_8(a, tex, park, n_cu, stream, grid, launch);
-    case PT_MODE_KD_MESH: return pt_film_launch_mode_9(a, tex, park, n_cu, stream, grid, launch);
-    default: return pt_film_launch_mode_1(a, tex, park, n_cu, stream, grid, launch);
-    }
+    PT_MODE_LAUNCH(pt_film_launch_mode_, a.r.scene.mode, a, tex, park, n_cu, stream, grid, launch)
 }
 
 #define PT_FILM_COUNT_MAX 0x80000000u  // a pixel holds at most 2^31 samples: count + a launch's lane offset never wraps
@@ -2786,7 +2653,7 @@ static hipError_t pt_film_dispatch(const PtFilmArgs& a, bool tex, bool park, int
 static int pt_film_handle(pt_context* c, pt_film* f, bool busy, const char* who) {
     if (!c) return PT_ERR_ARGUMENT;
     if (!f || std::find(c->films.begin(), c->films.end(), f) == c->films.end()) return pt_fail(c, PT_ERR_ARGUMENT, std::string(who) + ": NULL film, or not a film of this context");
-    if (busy && c->radiance.pending && c->film_open == f) return pt_fail(c, PT_ERR_ARGUMENT, std::string(who) + ": a pt_film_add_device pass of this film is in flight: pt_radiance_finish first");
+    if (busy && c->radiance.pass.pending && c->film_open == f) return pt_fail(c, PT_ERR_ARGUMENT, std::string(who) + ": a pt_film_add_device pass of this film is in flight: pt_radiance_finish first");
     return PT_OK;
 }
 
@@ -2801,12 +2668,12 @@ static int pt_film_create_common(pt_context* c, uint32_t width, uint32_t height,
     int rc;
     f->moments = moments;
     if ((rc = pt_reserve(c, f->total, n * 24)) || (rc = pt_reserve(c, f->partial, n * 24)) || (rc = pt_reserve(c, f->count, n * 4)) || (moments && (rc = pt_reserve(c, f->q, n * 8)))) {
-        pt_film_free(f);
+        delete f;
         return rc;
     }
     if ((moments && hipMemset(f->q.p, 0, n * 8) != hipSuccess) || hipMemset(f->total.p, 0, n * 24) != hipSuccess || hipMemset(f->partial.p, 0, n * 24) != hipSuccess || hipMemset(f->count.p, 0, n * 4) != hipSuccess ||
         hipDeviceSynchronize() != hipSuccess) {
-        pt_film_free(f);
+        delete f;
         return pt_fail(c, PT_ERR_DEVICE, "pt_film_create: clearing the film failed");
     }
     f->counts.assign(n, 0u);
@@ -2822,7 +2689,7 @@ extern "C" int pt_film_destroy(pt_context* c, pt_film* f) {
     if (rc) return rc;
     PT_HIP(c, hipSetDevice(c->device));
     c->films.erase(std::find(c->films.begin(), c->films.end(), f));
-    pt_film_free(f);  // (hipFree waits for whatever still reads the buffers)
+    delete f;  // (hipFree waits for whatever still reads the buffers)
     return PT_OK;
 }
 
@@ -2848,7 +2715,7 @@ static int pt_film_add_check(pt_context* c, pt_film* f, const pt_camera* cam, co
     if (p->slice.x0 >= f->width || p->slice.x1 >= f->width || p->slice.y0 >= f->height || p->slice.y1 >= f->height)
         return pt_fail(c, PT_ERR_SLICE, "slice corner outside the image (render.rs:79-90)");
     if (!c->have_scene) return pt_fail(c, PT_ERR_NO_SCENE, "no scene uploaded");
-    if (c->radiance.pending) return pt_fail(c, PT_ERR_ARGUMENT, "a pt_radiance_device / pt_film_add_device pass is in flight: pt_radiance_finish first");
+    if (c->radiance.pass.pending) return pt_fail(c, PT_ERR_ARGUMENT, "a pt_radiance_device / pt_film_add_device pass is in flight: pt_radiance_finish first");
     if (p->samples > PT_FILM_COUNT_MAX) return pt_fail(c, PT_ERR_ARGUMENT, "pt_film_add: a pixel's count would pass 2^31");
     for (uint32_t y = p->slice.y0; y <= p->slice.y1 && p->slice.x0 <= p->slice.x1; y++) {
         const uint32_t* row = f->counts.data() + (size_t)y * f->width;
@@ -2859,19 +2726,13 @@ static int pt_film_add_check(pt_context* c, pt_film* f, const pt_camera* cam, co
 }
 static bool pt_film_slice_empty(const pt_film_params* p) { return p->slice.x1 < p->slice.x0 || p->slice.y1 < p->slice.y0; }  // render.rs:60-65: an inverted slice renders nothing
 
-// Queues the add on `stream` as a radiance pass (its work buffers, events and pinned page): queues + overflow flag zeroed; between the pass's two events, per
-// at most `lw` samples, the sampling kernel and its fold (the queues zeroed again in between); the flag copied to the pinned page behind them. d_background is
-// a DEVICE pointer. LDS per block as the radiance pass has it. In three steps, shared with pt_film_add_map: the argument block ...
-struct PtFilmPass { bool tex, park; size_t misc_bytes; };
+// Queues the add on `stream` as a radiance pass (its PtPass: pt_pass_open ... pt_pass_seal): between the pass's two events, per at most `lw` samples, the
+// sampling kernel and its fold (the queues zeroed again in between; the overflow flag stays). d_background is a DEVICE pointer. LDS per block as the radiance
+// pass has it. The argument block is shared with pt_film_add_map:
 static int pt_film_pass_args(pt_context* c, pt_film* f, const pt_camera* cam, const double* d_background, const pt_rect& slice, uint64_t seed, int32_t sample_mode, int32_t background_rows, uint32_t lw,
-                             PtFilmArgs& a, PtFilmPass& ps) {
-    pt_context::Radiance& v = c->radiance;
-    if (!v.ev0) {
-        PT_HIP(c, hipEventCreate(&v.ev0));
-        PT_HIP(c, hipEventCreate(&v.ev1));
-        PT_HIP(c, hipEventCreateWithFlags(&v.copy_done, hipEventDisableTiming));
-        PT_HIP(c, hipHostMalloc((void**)&v.host, 256, hipHostMallocDefault));
-    }
+                             PtFilmArgs& a, PtInterp& k) {
+    int rc = pt_pass_prepare(c, c->radiance.pass);
+    if (rc) return rc;
     pt_render_params rp;
     memset(&rp, 0, sizeof rp);
     rp.width = f->width; rp.height = f->height; rp.slice = slice;
@@ -2881,59 +2742,19 @@ static int pt_film_pass_args(pt_context* c, pt_film* f, const pt_camera* cam, co
     a.r.background = d_background;
     a.lw = lw;
     a.count = (const uint32_t*)f->count.p;
-    const int mode = a.r.scene.mode;
-    const bool kd_sem = mode == PT_MODE_KD || mode == PT_MODE_KD_NOMESH || mode == PT_MODE_KD_MESH;
-    ps.tex = a.r.scene.mat_maps != nullptr;
-    ps.park = c->spawns;  // as the radiance pass and a render
-    if (const char* e = getenv("PORTRAYER_PARK")) ps.park = ps.park && atoi(e) > 0;
-    a.r.park_slots = ps.park ? 1 : 0;
-    const size_t frame_bytes = (size_t)(PT_LDS_FRAME_F64 + a.r.park_slots * PT_PARK_F64) * PT_BLOCK * 8;
-    a.r.stack_lds_cap = pt_stack_lds_cap(a.r.scene, 52 * 1024, frame_bytes, kd_sem);  // 3 x 52 KB of the CU's 160 KB (pt_film_waves)
-    a.r.grid_share = 1;
-    ps.misc_bytes = 256 + PT_FINE_QUEUES * PT_QUEUE_STRIDE * 4;  // the overflow flag (word 1, where a render has it), the work queues
-    return PT_OK;
-}
-// ... the buffers for the pass's largest launch (`grid` blocks), the queues and the flag zeroed and the first event on `stream` ...
-static int pt_film_pass_open(pt_context* c, pt_film* f, PtFilmArgs& a, const PtFilmPass& ps, uint32_t grid, hipStream_t stream) {
-    pt_context::Radiance& v = c->radiance;
-    a.r.n_lanes = grid * PT_BLOCK;
-    const size_t stack_column = pt_stack_column(a.r.scene, a.r.stack_lds_cap);
-    const size_t spill_bytes = c->needs_spill ? (size_t)a.r.n_lanes * PT_SPILL_DEPTHS * PT_SPILL_STRIDE * sizeof(double) : 16;
-    int rc;
-    if ((rc = pt_reserve(c, v.stack_spill, (size_t)a.r.n_lanes * stack_column * 4)) || (rc = pt_reserve(c, v.spill, spill_bytes)) || (rc = pt_reserve(c, v.misc, ps.misc_bytes)) ||
-        (rc = pt_reserve(c, f->staging, (size_t)a.r.n_slots * a.lw * 24)))
-        return rc;
-    a.staging = (double*)f->staging.p;
-    a.r.stack_spill = (uint32_t*)v.stack_spill.p;
-    a.r.spill = (double*)v.spill.p;
-    a.r.overflow_flag = (unsigned int*)v.misc.p + 1;
-    a.r.work_queues = (unsigned int*)((char*)v.misc.p + 256);
-    a.r.fine_queues = 16;
-    v.stream = stream; v.queued = true; v.closed = false;  // from here on something of the pass may be in flight on `stream`, whatever fails below
-    PT_HIP(c, hipMemsetAsync(v.misc.p, 0, ps.misc_bytes, stream));
-    PT_HIP(c, hipEventRecord(v.ev0, stream));
-    return PT_OK;
-}
-// ... and, behind the launches, the second event and the flag's copy.
-static int pt_film_pass_close(pt_context* c, hipStream_t stream) {
-    pt_context::Radiance& v = c->radiance;
-    PT_HIP(c, hipEventRecord(v.ev1, stream));
-    PT_HIP(c, hipMemcpyAsync(v.host, v.misc.p, 8, hipMemcpyDeviceToHost, stream));
-    PT_HIP(c, hipEventRecord(v.copy_done, stream));
-    v.closed = true;
+    k = pt_interp_sizing(c, a.r);
     return PT_OK;
 }
 
 static int pt_film_add_common(pt_context* c, pt_film* f, const pt_camera* cam, const double* d_background, const pt_film_params* p, hipStream_t stream) {
-    pt_context::Radiance& v = c->radiance;
+    PtPass& v = c->radiance.pass;
     uint32_t lw = PT_FILM_LW;
     if (const char* e = getenv("PORTRAYER_FILM_LW")) { const int w = atoi(e); if (w == 8 || w == 64) lw = (uint32_t)w; }  // measurements (profiles/film)
     if (f->moments) lw = PT_FILM_LW;  // (the fold that keeps q takes at most PT_FILM_LW samples per launch: pt_film_map_round)
     PtFilmArgs a;
-    PtFilmPass ps;
-    int rc = pt_film_pass_args(c, f, cam, d_background, p->slice, p->seed, p->sample_mode, p->background_rows, lw, a, ps);
+    PtInterp k;
+    int rc = pt_film_pass_args(c, f, cam, d_background, p->slice, p->seed, p->sample_mode, p->background_rows, lw, a, k);
     if (rc) return rc;
-    const bool tex = ps.tex, park = ps.park;
     const uint32_t tiles = a.r.n_slots / 64u;
     // the buffers are sized for the add's largest launch (its first: min(samples, lw) samples per pixel); the later ones use a prefix of the same lanes
     auto set_launch = [&](uint32_t m) {
@@ -2943,21 +2764,23 @@ static int pt_film_add_common(pt_context* c, pt_film* f, const pt_camera* cam, c
     };
     set_launch(std::min(p->samples, lw));
     uint32_t grid = 0;
-    PT_HIP(c, pt_film_dispatch(a, tex, park, c->n_cu, stream, &grid, false));
-    if ((rc = pt_film_pass_open(c, f, a, ps, grid, stream))) return rc;
+    PT_HIP(c, pt_film_dispatch(a, k.tex, k.park, c->n_cu, stream, &grid, false));
+    if ((rc = pt_reserve(c, f->staging, (size_t)a.r.n_slots * a.lw * 24))) return rc;
+    a.staging = (double*)f->staging.p;
+    if ((rc = pt_pass_open(c, v, a.r, grid, true, stream))) return rc;
     for (uint32_t left = p->samples, first = 1; left > 0; first = 0) {
         const uint32_t m = std::min(left, lw);
         set_launch(m);
-        if (!first) PT_HIP(c, hipMemsetAsync((char*)v.misc.p + 256, 0, ps.misc_bytes - 256, stream));  // the queues again; the overflow flag stays
+        if (!first) PT_HIP(c, hipMemsetAsync((char*)v.misc.p + 256, 0, PT_PASS_MISC_BYTES - 256, stream));  // the queues again; the overflow flag stays
         uint32_t g = 0;
-        PT_HIP(c, pt_film_dispatch(a, tex, park, c->n_cu, stream, &g, true));  // (g <= grid: no more items than the launch the buffers were sized for)
+        PT_HIP(c, pt_film_dispatch(a, k.tex, k.park, c->n_cu, stream, &g, true));  // (g <= grid: no more items than the launch the buffers were sized for)
         if (f->moments)  // the fold that keeps q as well: a uniform "map" of m, round 0 (pt_film_map.hip)
             PT_HIP(c, pt_film_fold_map_launch(a, nullptr, m, 0u, (double*)f->total.p, (double*)f->partial.p, (uint32_t*)f->count.p, (double*)f->q.p, stream));
         else
             PT_HIP(c, pt_film_fold_launch(a, (double*)f->total.p, (double*)f->partial.p, (uint32_t*)f->count.p, stream));
         left -= m;
     }
-    if ((rc = pt_film_pass_close(c, stream))) return rc;
+    if ((rc = pt_pass_seal(c, v))) return rc;
     for (uint32_t y = p->slice.y0; y <= p->slice.y1; y++) {  // the host's copy of the counts
         uint32_t* row = f->counts.data() + (size_t)y * f->width;
         for (uint32_t x = p->slice.x0; x <= p->slice.x1; x++) row[x] += p->samples;
@@ -2974,10 +2797,8 @@ extern "C" int pt_film_add(pt_context* c, pt_film* f, const pt_camera* cam, cons
     const size_t bg_bytes = (p->background_rows ? (size_t)f->height : (size_t)f->height * f->width) * 24;
     if ((rc = pt_reserve(c, f->bg, bg_bytes))) return rc;
     PT_HIP(c, hipMemcpy(f->bg.p, background, bg_bytes, hipMemcpyHostToDevice));
-    rc = pt_film_add_common(c, f, cam, (const double*)f->bg.p, p, nullptr);
-    const int rc_wait = pt_radiance_wait(c);
-    if (rc || (rc = rc_wait)) return rc;
-    return pt_radiance_close(c, kernel_ms);
+    if ((rc = pt_pass_settle(c, c->radiance.pass, pt_film_add_common(c, f, cam, (const double*)f->bg.p, p, nullptr)))) return rc;
+    return pt_pass_result(c, c->radiance.pass, kernel_ms);
 }
 
 extern "C" int pt_film_add_device(pt_context* c, pt_film* f, const pt_camera* cam, const double* d_background, const pt_film_params* p, void* hip_stream) {
@@ -2985,11 +2806,7 @@ extern "C" int pt_film_add_device(pt_context* c, pt_film* f, const pt_camera* ca
     if (rc) return rc;
     if (pt_film_slice_empty(p)) return PT_OK;  // nothing queued, nothing to finish
     PT_HIP(c, hipSetDevice(c->device));
-    if ((rc = pt_film_add_common(c, f, cam, d_background, p, (hipStream_t)hip_stream))) {
-        pt_radiance_wait(c);  // what was queued before the failure must not outlive the call
-        return rc;
-    }
-    c->radiance.pending = true;
+    if ((rc = pt_pass_device_tail(c, c->radiance.pass, pt_film_add_common(c, f, cam, d_background, p, (hipStream_t)hip_stream)))) return rc;
     c->film_open = f;
     return PT_OK;
 }
@@ -3040,17 +2857,7 @@ extern "C" int pt_film_counts(pt_context* c, pt_film* f, uint32_t* counts) {
 // Film, adaptive: a budget per pixel, a noise estimate, the budget of a refine pass (pt_film_map.h, pt_film_map.hip)
 // ------------------------------------------------------------------------------------------------
 static hipError_t pt_film_map_dispatch(const PtFilmMapArgs& a, bool tex, bool park, int n_cu, hipStream_t stream, uint32_t* grid, bool launch) {
-    switch (a.f.r.scene.mode) {
-    case PT_MODE_KD: return pt_film_map_launch_mode_2(a, tex, park, n_cu, stream, grid, launch);
-    case PT_MODE_FLAT_NOMESH: return pt_film_map_launch_mode_3(a, tex, park, n_cu, stream, grid, launch);
-    case PT_MODE_FLAT_KDMESH: return pt_film_map_launch_mode_4(a, tex, park, n_cu, stream, grid, launch);
-    case PT_MODE_HIER: return pt_film_map_launch_mode_5(a, tex, park, n_cu, stream, grid, launch);
-    case PT_MODE_HIER_NOMESH: return pt_film_map_launch_mode_6(a, tex, park, n_cu, stream, grid, launch);
-    case PT_MODE_KD_NOMESH: return pt_film_map_launch_mode_7(a, tex, park, n_cu, stream, grid, launch);
-    case PT_MODE_HIER_MESH: return pt_film_map_launch_mode_8(a, tex, park, n_cu, stream, grid, launch);
-    case PT_MODE_KD_MESH: return pt_film_map_launch_mode_9(a, tex, park, n_cu, stream, grid, launch);
-    default: return pt_film_map_launch_mode_1(a, tex, park, n_cu, stream, grid, launch);
-    }
+    PT_MODE_LAUNCH(pt_film_map_launch_mode_, a.f.r.scene.mode, a, tex, park, n_cu, stream, grid, launch)
 }
 
 static uint64_t pt_film_slice_slots(const pt_rect& s) { return (uint64_t)((s.x1 - s.x0 + 8u) / 8u) * ((s.y1 - s.y0 + 8u) / 8u) * 64u; }  // 8x8 tiles over the rectangle (pt_slot_to_pixel)
@@ -3068,7 +2875,7 @@ static int pt_film_add_map_check(pt_context* c, pt_film* f, const pt_camera* cam
     if (p->slice.x0 >= f->width || p->slice.x1 >= f->width || p->slice.y0 >= f->height || p->slice.y1 >= f->height)
         return pt_fail(c, PT_ERR_SLICE, "slice corner outside the image (render.rs:79-90)");
     if (!c->have_scene) return pt_fail(c, PT_ERR_NO_SCENE, "no scene uploaded");
-    if (c->radiance.pending) return pt_fail(c, PT_ERR_ARGUMENT, "a pt_radiance_device / pt_film_add_device pass is in flight: pt_radiance_finish first");
+    if (c->radiance.pass.pending) return pt_fail(c, PT_ERR_ARGUMENT, "a pt_radiance_device / pt_film_add_device pass is in flight: pt_radiance_finish first");
     *most = 0;
     if (p->slice.x1 < p->slice.x0 || p->slice.y1 < p->slice.y0) return PT_OK;
     if (pt_film_slice_slots(p->slice) >= PT_FILM_MAP_SLOTS_MAX) return pt_fail(c, PT_ERR_ARGUMENT, "pt_film_add_map: a slice of 2^29 pixel slots or more (an entry of the list is one u32)");
@@ -3088,34 +2895,36 @@ static int pt_film_add_map_check(pt_context* c, pt_film* f, const pt_camera* cam
 // over the list, the fold. The grid and the buffers are sized from the host's upper bound of round 0: every slot taking min(most, PT_FILM_LW).
 static int pt_film_add_map_common(pt_context* c, pt_film* f, const pt_camera* cam, const double* d_background, const pt_film_map_params* p, const uint32_t* d_budget, uint32_t most,
                                   hipStream_t stream) {
-    pt_context::Radiance& v = c->radiance;
+    PtPass& v = c->radiance.pass;
     PtFilmMapArgs a;
     memset(&a, 0, sizeof a);
-    PtFilmPass ps;
-    int rc = pt_film_pass_args(c, f, cam, d_background, p->slice, p->seed, p->sample_mode, p->background_rows, PT_FILM_LW, a.f, ps);
+    PtInterp k;
+    int rc = pt_film_pass_args(c, f, cam, d_background, p->slice, p->seed, p->sample_mode, p->background_rows, PT_FILM_LW, a.f, k);
     if (rc) return rc;
     const uint32_t n_slots = a.f.r.n_slots;  // (< 2^29: n_slots * PT_FILM_LW fits a u32)
     auto bound = [&](uint32_t round) { return (uint32_t)(((uint64_t)n_slots * std::min<uint32_t>(most - round * PT_FILM_LW, PT_FILM_LW) + 63u) / 64u); };
     a.f.r.n_items = bound(0);
     a.f.launch_samples = PT_FILM_LW;
     uint32_t grid = 0;
-    PT_HIP(c, pt_film_map_dispatch(a, ps.tex, ps.park, c->n_cu, stream, &grid, false));
+    PT_HIP(c, pt_film_map_dispatch(a, k.tex, k.park, c->n_cu, stream, &grid, false));
     if ((rc = pt_reserve(c, f->list, 16 + (size_t)n_slots * PT_FILM_LW * 4)) || (rc = pt_reserve(c, f->plan_work, pt_film_plan_words(n_slots) * 4))) return rc;
     uint32_t* n_list = (uint32_t*)f->list.p;
     uint32_t* list = (uint32_t*)((char*)f->list.p + 16);
     a.list = list;
     a.n_list = n_list;
-    if ((rc = pt_film_pass_open(c, f, a.f, ps, grid, stream))) return rc;
+    if ((rc = pt_reserve(c, f->staging, (size_t)n_slots * PT_FILM_LW * 24))) return rc;
+    a.f.staging = (double*)f->staging.p;
+    if ((rc = pt_pass_open(c, v, a.f.r, grid, true, stream))) return rc;
     const uint32_t rounds = (most + PT_FILM_LW - 1u) / PT_FILM_LW;
     for (uint32_t round = 0; round < rounds; round++) {
         PT_HIP(c, pt_film_plan_launch(a.f.r, d_budget, p->max_samples, round, (uint32_t*)f->plan_work.p, list, n_list, stream));
-        if (round) PT_HIP(c, hipMemsetAsync((char*)v.misc.p + 256, 0, ps.misc_bytes - 256, stream));  // the queues again; the overflow flag stays
+        if (round) PT_HIP(c, hipMemsetAsync((char*)v.misc.p + 256, 0, PT_PASS_MISC_BYTES - 256, stream));  // the queues again; the overflow flag stays
         a.f.r.n_items = bound(round);
         uint32_t g = 0;
-        PT_HIP(c, pt_film_map_dispatch(a, ps.tex, ps.park, c->n_cu, stream, &g, true));  // (g <= grid: no more items than the launch the buffers were sized for)
+        PT_HIP(c, pt_film_map_dispatch(a, k.tex, k.park, c->n_cu, stream, &g, true));  // (g <= grid: no more items than the launch the buffers were sized for)
         PT_HIP(c, pt_film_fold_map_launch(a.f, d_budget, p->max_samples, round, (double*)f->total.p, (double*)f->partial.p, (uint32_t*)f->count.p, f->moments ? (double*)f->q.p : nullptr, stream));
     }
-    return pt_film_pass_close(c, stream);
+    return pt_pass_seal(c, v);
 }
 
 extern "C" int pt_film_add_map(pt_context* c, pt_film* f, const pt_camera* cam, const double* background, const pt_film_map_params* p, const uint32_t* budget, double* kernel_ms) {
@@ -3129,15 +2938,13 @@ extern "C" int pt_film_add_map(pt_context* c, pt_film* f, const pt_camera* cam, 
     if ((rc = pt_reserve(c, f->bg, bg_bytes)) || (rc = pt_reserve(c, f->budget, f->counts.size() * 4))) return rc;
     PT_HIP(c, hipMemcpy(f->bg.p, background, bg_bytes, hipMemcpyHostToDevice));
     PT_HIP(c, hipMemcpy(f->budget.p, budget, f->counts.size() * 4, hipMemcpyHostToDevice));
-    rc = pt_film_add_map_common(c, f, cam, (const double*)f->bg.p, p, (const uint32_t*)f->budget.p, most, nullptr);
-    const int rc_wait = pt_radiance_wait(c);
-    if (rc || (rc = rc_wait)) return rc;
+    if ((rc = pt_pass_settle(c, c->radiance.pass, pt_film_add_map_common(c, f, cam, (const double*)f->bg.p, p, (const uint32_t*)f->budget.p, most, nullptr)))) return rc;
     for (uint32_t y = p->slice.y0; y <= p->slice.y1; y++) {  // the host's copy of the counts, exactly
         uint32_t* row = f->counts.data() + (size_t)y * f->width;
         const uint32_t* brow = budget + (size_t)y * f->width;
         for (uint32_t x = p->slice.x0; x <= p->slice.x1; x++) row[x] += std::min(brow[x], p->max_samples);
     }
-    return pt_radiance_close(c, kernel_ms);
+    return pt_pass_result(c, c->radiance.pass, kernel_ms);
 }
 
 extern "C" int pt_film_add_map_device(pt_context* c, pt_film* f, const pt_camera* cam, const double* d_background, const pt_film_map_params* p, const uint32_t* d_budget, void* hip_stream) {
@@ -3146,15 +2953,11 @@ extern "C" int pt_film_add_map_device(pt_context* c, pt_film* f, const pt_camera
     if (rc) return rc;
     if (most == 0) return PT_OK;  // an inverted slice: nothing queued, nothing to finish
     PT_HIP(c, hipSetDevice(c->device));
-    if ((rc = pt_film_add_map_common(c, f, cam, d_background, p, d_budget, most, (hipStream_t)hip_stream))) {
-        pt_radiance_wait(c);  // what was queued before the failure must not outlive the call
-        return rc;
-    }
+    if ((rc = pt_pass_device_tail(c, c->radiance.pass, pt_film_add_map_common(c, f, cam, d_background, p, d_budget, most, (hipStream_t)hip_stream)))) return rc;
     for (uint32_t y = p->slice.y0; y <= p->slice.y1; y++) {  // the host's copy of the counts: an upper bound, until pt_film_counts
         uint32_t* row = f->counts.data() + (size_t)y * f->width;
         for (uint32_t x = p->slice.x0; x <= p->slice.x1; x++) row[x] += p->max_samples;
     }
-    c->radiance.pending = true;
     c->film_open = f;
     return PT_OK;
 }
@@ -3320,17 +3123,13 @@ extern "C" int pt_test_film_plan(pt_context* c, uint32_t width, uint32_t height,
     const size_t n_pixels = (size_t)width * height;
     PtBuf d_budget, d_list, d_work;
     int rc;
-    if ((rc = pt_reserve(c, d_budget, n_pixels * 4)) || (rc = pt_reserve(c, d_list, 16 + (size_t)r.n_slots * PT_FILM_LW * 4)) || (rc = pt_reserve(c, d_work, pt_film_plan_words(r.n_slots) * 4))) {
-        for (PtBuf* b : {&d_budget, &d_list, &d_work}) if (b->p) hipFree(b->p);
-        return rc;
-    }
+    if ((rc = pt_reserve(c, d_budget, n_pixels * 4)) || (rc = pt_reserve(c, d_list, 16 + (size_t)r.n_slots * PT_FILM_LW * 4)) || (rc = pt_reserve(c, d_work, pt_film_plan_words(r.n_slots) * 4))) return rc;
     uint32_t n = 0;
     hipError_t e = hipMemcpy(d_budget.p, budget, n_pixels * 4, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = pt_film_plan_launch(r, (const uint32_t*)d_budget.p, max_samples, round, (uint32_t*)d_work.p, (uint32_t*)((char*)d_list.p + 16), (uint32_t*)d_list.p, nullptr);
     if (e == hipSuccess) e = hipMemcpy(&n, d_list.p, 4, hipMemcpyDeviceToHost);
     if (e == hipSuccess && n > r.n_slots * (uint32_t)PT_FILM_LW) n = r.n_slots * (uint32_t)PT_FILM_LW;  // (never: the list's room)
     if (e == hipSuccess && std::min(n, cap)) e = hipMemcpy(list, (char*)d_list.p + 16, (size_t)std::min(n, cap) * 4, hipMemcpyDeviceToHost);
-    for (PtBuf* b : {&d_budget, &d_list, &d_work}) if (b->p) hipFree(b->p);
     if (e != hipSuccess) return pt_fail(c, PT_ERR_DEVICE, std::string("pt_test_film_plan: ") + hipGetErrorString(e));
     *n_out = n;
     return PT_OK;

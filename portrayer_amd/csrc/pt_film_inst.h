@@ -61,16 +61,7 @@ PT_HD PtVec3 pt_film_sum(PtVec3 total, PtVec3 partial, uint32_t count) {
 constexpr int pt_film_waves(int /*mode*/) { return 3; }  // the interpreter's three (pt_radiance_waves)
 
 // tex, park: as for the radiance pass
-#define PT_DECLARE_FILM_LAUNCHER(n) hipError_t pt_film_launch_mode_##n(const PtFilmArgs& a, bool tex, bool park, int n_cu, hipStream_t stream, uint32_t* grid, bool launch)
-PT_DECLARE_FILM_LAUNCHER(1);  // PT_MODE_FLAT
-PT_DECLARE_FILM_LAUNCHER(2);  // PT_MODE_KD
-PT_DECLARE_FILM_LAUNCHER(3);  // PT_MODE_FLAT_NOMESH
-PT_DECLARE_FILM_LAUNCHER(4);  // PT_MODE_FLAT_KDMESH
-PT_DECLARE_FILM_LAUNCHER(5);  // PT_MODE_HIER
-PT_DECLARE_FILM_LAUNCHER(6);  // PT_MODE_HIER_NOMESH
-PT_DECLARE_FILM_LAUNCHER(7);  // PT_MODE_KD_NOMESH
-PT_DECLARE_FILM_LAUNCHER(8);  // PT_MODE_HIER_MESH
-PT_DECLARE_FILM_LAUNCHER(9);  // PT_MODE_KD_MESH
+PT_DECLARE_MODE_LAUNCHERS(pt_film_launch_mode_, const PtFilmArgs& a, bool tex, bool park, int n_cu, hipStream_t stream, uint32_t* grid, bool launch);
 
 // pt_film.hip. Both take the slice / image through PtRenderArgs' fields (width, height, x0 .. y1, n_slots) and queue one kernel on `stream`.
 // fold: one thread per pixel slot of the slice; the slot's launch_samples staged samples folded into total / partial in ascending order, count += launch_samples.

@@ -55,16 +55,7 @@ PT_HD double pt_film_error_of(PtVec3 total, PtVec3 partial, double q, uint32_t n
     return sqrt(var / dn);
 }
 
-#define PT_DECLARE_FILM_MAP_LAUNCHER(n) hipError_t pt_film_map_launch_mode_##n(const PtFilmMapArgs& a, bool tex, bool park, int n_cu, hipStream_t stream, uint32_t* grid, bool launch)
-PT_DECLARE_FILM_MAP_LAUNCHER(1);  // PT_MODE_FLAT
-PT_DECLARE_FILM_MAP_LAUNCHER(2);  // PT_MODE_KD
-PT_DECLARE_FILM_MAP_LAUNCHER(3);  // PT_MODE_FLAT_NOMESH
-PT_DECLARE_FILM_MAP_LAUNCHER(4);  // PT_MODE_FLAT_KDMESH
-PT_DECLARE_FILM_MAP_LAUNCHER(5);  // PT_MODE_HIER
-PT_DECLARE_FILM_MAP_LAUNCHER(6);  // PT_MODE_HIER_NOMESH
-PT_DECLARE_FILM_MAP_LAUNCHER(7);  // PT_MODE_KD_NOMESH
-PT_DECLARE_FILM_MAP_LAUNCHER(8);  // PT_MODE_HIER_MESH
-PT_DECLARE_FILM_MAP_LAUNCHER(9);  // PT_MODE_KD_MESH
+PT_DECLARE_MODE_LAUNCHERS(pt_film_map_launch_mode_, const PtFilmMapArgs& a, bool tex, bool park, int n_cu, hipStream_t stream, uint32_t* grid, bool launch);
 
 // pt_film_map.hip. All take the slice / image through PtRenderArgs' fields (width, height, x0 .. y1, n_slots) and queue their kernels on `stream`.
 // Words of work space the plan of a slice of n_slots needs (the block sums of every level of the scan).

@@ -45,13 +45,4 @@ struct PtRaySource {
 constexpr int pt_radiance_waves(int /*mode*/) { return 3; }
 
 // tex: the scene has texture or normal maps (TEX instantiation); park: its hits spawn rays (PARK = 1: the youngest parked recursion frame stays in LDS)
-#define PT_DECLARE_RADIANCE_LAUNCHER(n) hipError_t pt_radiance_launch_mode_##n(const PtRadianceArgs& a, bool tex, bool park, int n_cu, hipStream_t stream, uint32_t* grid, bool launch)
-PT_DECLARE_RADIANCE_LAUNCHER(1);  // PT_MODE_FLAT
-PT_DECLARE_RADIANCE_LAUNCHER(2);  // PT_MODE_KD
-PT_DECLARE_RADIANCE_LAUNCHER(3);  // PT_MODE_FLAT_NOMESH
-PT_DECLARE_RADIANCE_LAUNCHER(4);  // PT_MODE_FLAT_KDMESH
-PT_DECLARE_RADIANCE_LAUNCHER(5);  // PT_MODE_HIER
-PT_DECLARE_RADIANCE_LAUNCHER(6);  // PT_MODE_HIER_NOMESH
-PT_DECLARE_RADIANCE_LAUNCHER(7);  // PT_MODE_KD_NOMESH
-PT_DECLARE_RADIANCE_LAUNCHER(8);  // PT_MODE_HIER_MESH
-PT_DECLARE_RADIANCE_LAUNCHER(9);  // PT_MODE_KD_MESH
+PT_DECLARE_MODE_LAUNCHERS(pt_radiance_launch_mode_, const PtRadianceArgs& a, bool tex, bool park, int n_cu, hipStream_t stream, uint32_t* grid, bool launch);

@@ -6,6 +6,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include "pt_mode_launch.h"
 #include "pt_shade.h"
 
 struct PtRaysArgs {
@@ -39,16 +40,7 @@ PT_HD bool pt_rays_traced(const PtRay& r) {
 // the per-lane KDMesh walker need its registers.
 constexpr int pt_rays_waves(int mode) { return (mode == PT_MODE_KD || mode == PT_MODE_FLAT_KDMESH || mode == PT_MODE_HIER) ? 3 : 4; }
 
-#define PT_DECLARE_RAYS_LAUNCHER(n) hipError_t pt_rays_launch_mode_##n(const PtRaysArgs& a, int n_cu, hipStream_t stream, uint32_t* grid, bool launch)
-PT_DECLARE_RAYS_LAUNCHER(1);  // PT_MODE_FLAT
-PT_DECLARE_RAYS_LAUNCHER(2);  // PT_MODE_KD
-PT_DECLARE_RAYS_LAUNCHER(3);  // PT_MODE_FLAT_NOMESH
-PT_DECLARE_RAYS_LAUNCHER(4);  // PT_MODE_FLAT_KDMESH
-PT_DECLARE_RAYS_LAUNCHER(5);  // PT_MODE_HIER
-PT_DECLARE_RAYS_LAUNCHER(6);  // PT_MODE_HIER_NOMESH
-PT_DECLARE_RAYS_LAUNCHER(7);  // PT_MODE_KD_NOMESH
-PT_DECLARE_RAYS_LAUNCHER(8);  // PT_MODE_HIER_MESH
-PT_DECLARE_RAYS_LAUNCHER(9);  // PT_MODE_KD_MESH
+PT_DECLARE_MODE_LAUNCHERS(pt_rays_launch_mode_, const PtRaysArgs& a, int n_cu, hipStream_t stream, uint32_t* grid, bool launch);
 
 // reorder = 1 (pt_rays_sort.hip). Key of a ray, most significant first: bit 63 set = not traced (sorts last); bits 62..60 the direction's sign bits
 // (z, y, x: set where the component is below zero); bits 59..0 the Morton code of the origin, 20 bits per axis, quantised inside

@@ -15,13 +15,4 @@ PT_HD bool pt_segments_traced(const PtRay& r, double t_max) { return pt_rays_tra
 // Waves per SIMD (pt_segments_kernel's launch bounds): the walks and the surface code are pt_rays_kernel's, so is the choice.
 constexpr int pt_segments_waves(int mode) { return pt_rays_waves(mode); }
 
-#define PT_DECLARE_SEGMENTS_LAUNCHER(n) hipError_t pt_segments_launch_mode_##n(const PtSegmentsArgs& a, int n_cu, hipStream_t stream, uint32_t* grid, bool launch)
-PT_DECLARE_SEGMENTS_LAUNCHER(1);  // PT_MODE_FLAT
-PT_DECLARE_SEGMENTS_LAUNCHER(2);  // PT_MODE_KD
-PT_DECLARE_SEGMENTS_LAUNCHER(3);  // PT_MODE_FLAT_NOMESH
-PT_DECLARE_SEGMENTS_LAUNCHER(4);  // PT_MODE_FLAT_KDMESH
-PT_DECLARE_SEGMENTS_LAUNCHER(5);  // PT_MODE_HIER
-PT_DECLARE_SEGMENTS_LAUNCHER(6);  // PT_MODE_HIER_NOMESH
-PT_DECLARE_SEGMENTS_LAUNCHER(7);  // PT_MODE_KD_NOMESH
-PT_DECLARE_SEGMENTS_LAUNCHER(8);  // PT_MODE_HIER_MESH
-PT_DECLARE_SEGMENTS_LAUNCHER(9);  // PT_MODE_KD_MESH
+PT_DECLARE_MODE_LAUNCHERS(pt_segments_launch_mode_, const PtSegmentsArgs& a, int n_cu, hipStream_t stream, uint32_t* grid, bool launch);

@@ -54,11 +54,24 @@ def design_table():
     return {(int(m), int(t), int(p)): (int(v), int(s), int(b)) for m, t, p, v, s, b in rows}
 
 
+def function_body(text, signature):
+    """The function of pt_api.hip that starts with `signature`, up to its closing brace in column 0."""
+    start = text.index(signature)
+    return text[start:text.index("\n}\n", start)]
+
+
 def test_the_wave_count_is_the_one_the_source_states():
     src = open(os.path.join(CSRC, "pt_film_inst.h")).read()
     assert re.search(r"constexpr int pt_film_waves\(int /\*mode\*/\) \{ return 3; \}", src), "pt_film_waves changed: update WAVES and BUDGET here knowingly"
+    # the LDS budget stands once, in the sizing the interpreter passes share; the film's argument block calls it, and both of its queueing functions build that block
     api = open(os.path.join(CSRC, "pt_api.hip")).read()
-    assert re.search(r"pt_stack_lds_cap\(a\.r\.scene, 52 \* 1024, frame_bytes, kd_sem\);\s*// 3 x 52 KB of the CU's 160 KB \(pt_film_waves\)", api), "the film sizes its LDS for three blocks per CU"
+    sizing = function_body(api, "static PtInterp pt_interp_sizing(")
+    assert re.search(r"r\.stack_lds_cap = pt_stack_lds_cap\(r\.scene, 52 \* 1024, frame_bytes\);\s*// 3 x 52 KB of the CU's 160 KB \(pt_radiance_waves, pt_film_waves\)", sizing), \
+        "the film sizes its LDS for three blocks per CU"
+    assert "pt_kd_semantics(sc.mode)" in function_body(api, "static int pt_stack_lds_cap(const PtSceneView& sc, size_t block_budget, size_t frame_bytes)")
+    assert "k = pt_interp_sizing(c, a.r)" in function_body(api, "static int pt_film_pass_args(")
+    for queue in ("static int pt_film_add_common(", "static int pt_film_add_map_common("):
+        assert "pt_film_pass_args(c, f, cam, d_background, " in function_body(api, queue), queue
 
 
 @pytest.mark.parametrize("mode", [1, 2, 3, 4, 5, 6, 7, 8, 9])

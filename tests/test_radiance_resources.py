@@ -53,11 +53,21 @@ def design_table():
     return {(int(m), int(t), int(p)): (int(v), int(s), int(b)) for m, t, p, v, s, b in rows}
 
 
+def function_body(text, signature):
+    """The function of pt_api.hip that starts with `signature`, up to its closing brace in column 0."""
+    start = text.index(signature)
+    return text[start:text.index("\n}\n", start)]
+
+
 def test_the_wave_count_is_the_one_the_source_states():
     src = open(os.path.join(CSRC, "pt_radiance_inst.h")).read()
     assert re.search(r"constexpr int pt_radiance_waves\(int /\*mode\*/\) \{ return 3; \}", src), "pt_radiance_waves changed: update WAVES and BUDGET here knowingly"
+    # the LDS budget stands once, in the sizing the interpreter passes share, and the pass's queueing function calls it
     api = open(os.path.join(CSRC, "pt_api.hip")).read()
-    assert re.search(r"pt_stack_lds_cap\(a\.r\.scene, 52 \* 1024, frame_bytes, kd_sem\);\s*// 3 x 52 KB", api), "the pass sizes its LDS for three blocks per CU"
+    sizing = function_body(api, "static PtInterp pt_interp_sizing(")
+    assert re.search(r"r\.stack_lds_cap = pt_stack_lds_cap\(r\.scene, 52 \* 1024, frame_bytes\);\s*// 3 x 52 KB", sizing), "the pass sizes its LDS for three blocks per CU"
+    assert "pt_kd_semantics(sc.mode)" in function_body(api, "static int pt_stack_lds_cap(const PtSceneView& sc, size_t block_budget, size_t frame_bytes)")
+    assert "pt_interp_sizing(c, a.r)" in function_body(api, "static int pt_radiance_common("), "pt_radiance_common sizes its LDS with pt_interp_sizing"
 
 
 @pytest.mark.parametrize("mode", [1, 2, 3, 4, 5, 6, 7, 8, 9])
