@@ -26,7 +26,7 @@ examples/bin/%: examples/%.cpp portrayer_amd/libportrayer_host.so
 	$(CXX) $(CXXFLAGS) -fPIE -DPORTRAYER_EXAMPLE_MAIN $< -o $@ -Lportrayer_amd -lportrayer_host -lportrayer_hip -Wl,-rpath,'$$ORIGIN/../../portrayer_amd'
 
 # Device objects: the C ABI + small kernels, the device-side tree build, and the render kernel instantiated per
-# traversal mode (one source, six objects) - compiled side by side under make -j.
+# traversal mode (one source, nine objects) - compiled side by side under make -j.
 OBJDIR ?= $(CSRC)
 HIPLIB ?= portrayer_amd/libportrayer_hip.so
 RENDER_MODES := 1 2 3 4 5 6 7 8 9
@@ -101,6 +101,28 @@ verify:
 verify-mi:
 	for m in $(RENDER_MODES); do $(HIPCC) $(HIPFLAGS) --offload-device-only -mllvm -verify-machineinstrs -DPT_INST_MODE=$$m -c $(CSRC)/pt_render_inst.hip -o /dev/null || exit 1; done
 
+# The switches a build may set (EXTRA_HIPFLAGS, `make variant`); this list is the one place that says which exist. Instrumentation that a driver script
+# under profiles/ builds - PT_DIAG (diag.sh), PT_CYCLES (cycles.sh), PT_TIMELINE (timeline.sh), PT_OCCLUDER_STATS (occluder_stats.py), PT_ABLATE
+# (light_slope.py) - and the off switches of shipped optimisations whose gain hangs on this toolchain's register allocation and is measured again after a
+# ROCm update (DESIGN.md names each as its A/B). PT_MIN_WAVES=<n> (profiles/ab.sh) takes a value of the user's and is not listed.
+# `make -j8 switches` compiles each switch alone, device-only, to /dev/null (the pattern of verify-mi, the same HIPFLAGS) for the render modes whose object
+# it changes - MODES_<switch>, all nine where nothing says so: a switch that stops compiling is noticed. Not part of `all`, and no test runs it.
+SWITCHES := PT_DIAG PT_CYCLES PT_TIMELINE PT_OCCLUDER_STATS=1 PT_OCCLUDER_STATS=2 PT_ABLATE=1 PT_ABLATE=2 PT_ABLATE=3 PT_ABLATE=5 PT_ABLATE=6 \
+            PT_NO_UNIFORM_HIT PT_NO_EYE_TABLE PT_NO_CERTAIN_SHADOW PT_POW_OCML
+MODES_PT_OCCLUDER_STATS := 3 6
+MODES_PT_NO_UNIFORM_HIT := 3
+MODES_PT_NO_EYE_TABLE := 3
+MODES_PT_NO_CERTAIN_SHADOW := 3
+switch_modes = $(or $(MODES_$(firstword $(subst =, ,$(1)))),$(RENDER_MODES))
+switch_target = switch-$(subst =,.,$(1))-m$(2)
+define switch_rule
+$(call switch_target,$(1),$(2)):
+	$$(HIPCC) $$(HIPFLAGS) --offload-device-only -D$(1) -DPT_INST_MODE=$(2) -c $$(CSRC)/pt_render_inst.hip -o /dev/null
+endef
+SWITCH_TARGETS := $(foreach s,$(SWITCHES),$(foreach m,$(call switch_modes,$(s)),$(call switch_target,$(s),$(m))))
+$(foreach s,$(SWITCHES),$(foreach m,$(call switch_modes,$(s)),$(eval $(call switch_rule,$(s),$(m)))))
+switches: $(SWITCH_TARGETS)
+
 # `make sanitize-raypk`: the host code of pt_api.hip (the slab-test hook pt_test_raypk and everything beside it) under AddressSanitizer + UBSan, driven by
 # tools/raypk_sanitize.cpp as a program of its own on the CPU. Only the HOST side is instrumented (-Xarch_host); the object is built through the same four
 # steps as every other one, the remaining objects are the library's. The program launches nothing.
@@ -121,4 +143,4 @@ clean:
 	rm -rf build/sanitize
 	rm -rf examples/bin
 	$(MAKE) -C oracle clean
-.PHONY: all oracle clean hipobjs variant verify verify-mi sanitize-raypk
+.PHONY: all oracle clean hipobjs variant verify verify-mi sanitize-raypk switches $(SWITCH_TARGETS)

@@ -61,7 +61,7 @@ __global__ void pt_math_kernel(int op, uint64_t n, const double* a, const double
     case 4: r = atan2(a[i], b[i]); break;   // sphere.rs:57-58 (texture coordinates)
     case 5: r = acos(a[i]); break;          // sphere.rs:59
     case 6: r = pow(a[i], b[i]); break;     // the device library's pow, for comparison
-    case 7:  // the k-d walk's short division (pt_trace.h: pt_div_fast) where its exponent test admits the operands, NaN where it does not
+    case 7:  // the k-d walk's short division (pt_walk_kd.h: pt_div_fast) where its exponent test admits the operands, NaN where it does not
         r = (pt_div_exp_ok(a[i]) && pt_div_exp_ok(b[i])) ? pt_div_fast(a[i], b[i], pt_rcp_refined(b[i])) : __builtin_nan("");
         break;
     default: r = 0.0; break;
@@ -180,10 +180,6 @@ __global__ void __launch_bounds__(256) pt_collapse4_kernel(const PtBvhNode* __re
 // its seven neighbours' loads next to it, and the pixel's first thread adds the eight values in ascending order (the summation contract: a
 // fixed left-to-right association) - leaves the sums in LDS, and then finishes ONE pixel per thread (the three pows with every lane busy).
 __global__ void __launch_bounds__(PT_BLOCK) pt_finish_kernel(PtRenderArgs a) {
-#ifdef PT_ACCUM_CHUNK_MAJOR
-    uint32_t p = blockIdx.x * PT_BLOCK + threadIdx.x;
-    if (p < a.n_slots) pt_finish_pixel(a, p, pt_pixel_sum(a, p));
-#else
     __shared__ double sums[3 * PT_BLOCK];
     const uint32_t base = blockIdx.x * PT_BLOCK, j = threadIdx.x & 7u;
     for (uint32_t pass = 0; pass < 8u; pass++) {
@@ -205,7 +201,6 @@ __global__ void __launch_bounds__(PT_BLOCK) pt_finish_kernel(PtRenderArgs a) {
     __syncthreads();
     const uint32_t p = base + threadIdx.x;
     if (p < a.n_slots) pt_finish_pixel(a, p, pt_v3(sums[3 * threadIdx.x], sums[3 * threadIdx.x + 1], sums[3 * threadIdx.x + 2]));
-#endif
 }
 
 // compact (rank-major, tile-major) -> row-major image
@@ -2017,7 +2012,7 @@ static int pt_render_common(pt_context* c, PtRenderArgs& a, bool stats, hipStrea
     if (const char* e = getenv("PORTRAYER_PARK")) a.park_slots = atoi(e) > 0 ? 1 : 0;  // 0: every parked frame in HBM (tests, measurements)
     if (!c->spawns) a.park_slots = 0;
     // Scenes whose hits spawn rays need the interpreter kernel (3 waves per SIMD); the others run the straight-line kernel at 3 or
-    // 4 waves per SIMD. PORTRAYER_INTERP=1 (builds with -DPT_KEEP_INTERP): the interpreter on those too, for A/B runs.
+    // 4 waves per SIMD.
     const bool kd_sem = pt_kd_semantics(a.scene.mode);
     a.four_waves = (!c->spawns && (c->four_waves || (c->four_waves_untextured && !tex) || c->four_waves_hier)) ? (c->five_waves ? PT_LINE_TOP_WAVES : ((c->five_waves_mesh && !tex) ? PT_MESH_TOP_WAVES : 4)) : 0;
     if (const char* e = getenv("PORTRAYER_WAVES")) {
@@ -2046,7 +2041,6 @@ static int pt_render_common(pt_context* c, PtRenderArgs& a, bool stats, hipStrea
     bool chain = c->one_ray;
     if (const char* e = getenv("PORTRAYER_CHAIN")) chain = chain && atoi(e) > 0;  // 0: the interpreter kernel also for scenes whose recursion is a chain (A/B runs, tests)
     if (c->spawns) a.run_variant = (chain && a.park_slots) ? PT_RUN_CHAIN : (a.park_slots ? (fork ? PT_RUN_INTERP_FORK : PT_RUN_INTERP_PARK) : PT_RUN_INTERP);
-    else if (pt_interpreter_forced()) a.run_variant = a.four_waves ? PT_RUN_INTERP4 : PT_RUN_INTERP;
     else a.run_variant = a.four_waves >= 5 ? PT_RUN_LINE5 : (a.four_waves ? PT_RUN_LINE4 : PT_RUN_LINE3);  // (LINE5: the densest instantiation the mode has)
     if (a.run_variant == PT_RUN_CHAIN) {
         a.park_slots = 0;  // no frame in LDS: the parked colours go straight to the lane's HBM lines

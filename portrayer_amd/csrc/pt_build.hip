@@ -33,9 +33,7 @@
 #define PT_PLOC_LEAF 0x80000000u
 #define PT_PLOC_NONE 0xFFFFFFFFu
 #define PT_PLOC_LIMIT 1e18f  // pt_bvh.h PT_BOX_LIMIT: box coordinates stay finite and within +-1e18
-#ifndef PT_PLOC_RADIUS
 #define PT_PLOC_RADIUS 16
-#endif
 
 namespace {
 

@@ -1,5 +1,5 @@
 // The render kernel (render.rs:127-150 and everything below it) and its launcher. Included by
-// pt_render_inst.hip, which is compiled once per traversal mode (seven objects built side by side).
+// pt_render_inst.hip, which is compiled once per traversal mode (nine objects built side by side).
 //
 // Kernel design (CDNA4: 64-wide wavefronts, 256 CUs in 8 XCDs, 160 KB LDS per CU, no matrix cores involved -
 // there is no dense contraction on this path):
@@ -11,7 +11,7 @@
 //    (or a compact window of a few), which is what keeps its lanes in step inside the walk (profiles/r02/notes.md).
 //  * one traversal loop per wavefront for all ray kinds: pt_lane_advance() turns whatever the lane traced
 //    last into its next ray, so secondary rays re-enter the same loop instead of recursing.
-//  * in the flat_scene and hierarchical semantics the trees are walked ONCE PER WAVEFRONT (pt_trace.h: pt_trace_packet,
+//  * in the flat_scene and hierarchical semantics the trees are walked ONCE PER WAVEFRONT (pt_walk_wave.h: pt_trace_packet,
 //    pt_trace_packet_mesh): node index and stack are scalars, nodes and leaf records come through the scalar cache; the
 //    k-d tree semantics keep a walk per lane.
 //  * LDS: the traversal stack (the wavefront's, or one column per lane, overflowing to HBM beyond the LDS part), per lane the
@@ -31,16 +31,13 @@
 // VAR (template parameter), chosen per scene in pt_scene_upload:
 //   0  hits never spawn rays; 3 waves per SIMD (168 VGPRs). The code and lane state for parked recursion frames are compiled out.
 //   1  scenes with reflective materials: the youngest parked recursion frame of a lane stays in LDS (PARK); 3 waves per SIMD.
-//   2  like 0 with 4 waves per SIMD (128 VGPRs): with the wave-uniform walk the traversal needs few registers of its own, and
-//      traversal-heavy scenes gain from the fourth wave (big-scene 19.1 -> 20.8 Gray/s, big-soup 6.9 -> 7.4) where shading-heavy
-//      and reflective ones lose (cows -8 %, mirror -7 %, transmission-refraction -21 %; profiles/r02/notes.md).
+//   3  1 + fork / join of refracted subtrees.
+//   (2 was 0 at 4 waves per SIMD, what round 2 timed - profiles/r02/notes.md; the straight-line kernel of pt_render_simple.h took its place.)
 #ifndef PT_MIN_WAVES
 #define PT_MIN_WAVES 0  // experiments: -DPT_MIN_WAVES=2 / 3 / 4 for every instantiation
 #endif
-#ifndef PT_INTERP_WAVES
-#define PT_INTERP_WAVES 3  // experiments: -DPT_INTERP_WAVES=2 compiles the interpreter kernels (VAR 0, 1, 3) for 2 waves per SIMD (256 VGPRs)
-#endif
-#define PT_VAR_WAVES(VAR) (PT_MIN_WAVES ? PT_MIN_WAVES : ((VAR) == 2 ? 4 : PT_INTERP_WAVES))  // VAR 3 = VAR 1 + fork / join of refracted subtrees
+#define PT_INTERP_WAVES 3  // the interpreter kernels (VAR 0, 1, 3): compiled for 3 waves per SIMD (168 VGPRs)
+#define PT_VAR_WAVES(VAR) (PT_MIN_WAVES ? PT_MIN_WAVES : PT_INTERP_WAVES)
 
 __device__ __forceinline__ void pt_flush_counters(PtCounters* dst, const PtCounters& c) {
     const unsigned long long* s = reinterpret_cast<const unsigned long long*>(&c);
@@ -151,14 +148,12 @@ __global__ void __launch_bounds__(PT_BLOCK, PT_VAR_WAVES(VAR)) pt_render_kernel(
 #ifdef PT_CYCLES
             const unsigned long long cyc_a = __builtin_readcyclecounter();
 #endif
-#ifndef PT_NO_ARGS_AGAIN
             // what the interpreter and this pass's walk need of the arguments is fetched now, not kept from the top of the kernel on (pt_render_simple.h).
             // (Round 4 kept this out of <PT_MODE_KD, true, *, 0>, which rendered wrongly with it. Round 5 found why - the compiler's vector register
             // allocator had put a spill store of `best.t` in front of the s_or_b64 exec that re-converges the block, so the lanes that sat out a leaf lost
             // their nearest hit: profiles/r05/notes.md section 1 - and the build now checks and repairs every kernel's assembly for it
             // (tools/check_exec_prologue.py), so no instantiation is special any more.)
             const PtRenderArgs& a = pt_args_again(a0);
-#endif
             constexpr bool HIER = MODE == PT_MODE_HIER || MODE == PT_MODE_HIER_NOMESH || MODE == PT_MODE_HIER_MESH;
             uint32_t pre = 0;
 #ifdef PT_MAPS_BEFORE
@@ -353,8 +348,6 @@ static hipError_t pt_launch_kernel(size_t lds, const PtRenderArgs& a, int n_cu, 
 //   PT_RUN_INTERP_FORK                   PT_RUN_INTERP_PARK + fork / join: idle lanes take the refracted subtrees busy lanes offer (pt_shade.h)
 //   PT_RUN_LINE3 / PT_RUN_LINE4 / _LINE5 the straight-line kernel of pt_render_simple.h (hits spawn nothing), 3 / 4 / 5 waves per SIMD
 //   PT_RUN_CHAIN                         the straight-line kernel with a loop over the depth: scenes whose reflective materials are all opaque (3 waves)
-//   PT_RUN_INTERP4                       -DPT_KEEP_INTERP builds only: the interpreter at 4 waves per SIMD on a scene without reflective
-//                                        materials (what round 2 timed), for A/B runs against the straight-line kernel
 template <int MODE, bool STATS, bool TEX>
 static hipError_t pt_launch_variant(const PtRenderArgs& a, int variant, bool kd_mode, int n_cu, hipStream_t stream, uint32_t* grid_out, bool launch) {
     const size_t lds = pt_render_lds_bytes(a.stack_lds_cap, TEX, (variant == PT_RUN_INTERP_PARK || variant == PT_RUN_INTERP_FORK) ? 1 : 0);
@@ -362,11 +355,6 @@ static hipError_t pt_launch_variant(const PtRenderArgs& a, int variant, bool kd_
     case PT_RUN_INTERP_PARK: return pt_launch_kernel<&pt_render_kernel<MODE, STATS, TEX, 1>>(lds, a, n_cu, stream, grid_out, launch);
     case PT_RUN_INTERP_FORK: return pt_launch_kernel<&pt_render_kernel<MODE, STATS, TEX, 3>>(lds, a, n_cu, stream, grid_out, launch);
     case PT_RUN_INTERP: return pt_launch_kernel<&pt_render_kernel<MODE, STATS, TEX, 0>>(lds, a, n_cu, stream, grid_out, launch);
-#ifdef PT_KEEP_INTERP
-    case PT_RUN_INTERP4:
-        if constexpr (MODE != PT_MODE_KD && MODE != PT_MODE_KD_NOMESH && MODE != PT_MODE_KD_MESH) return pt_launch_kernel<&pt_render_kernel<MODE, STATS, TEX, 2>>(lds, a, n_cu, stream, grid_out, launch);
-        return pt_launch_kernel<&pt_render_kernel<MODE, STATS, TEX, 0>>(lds, a, n_cu, stream, grid_out, launch);
-#endif
     case PT_RUN_CHAIN:
         if constexpr (MODE != PT_MODE_KD)
             if (a.four_waves == 4) return pt_launch_kernel<&pt_render_simple_kernel<MODE, STATS, TEX, 4, true>>(lds, a, n_cu, stream, grid_out, launch);

@@ -92,7 +92,7 @@ PT_HD PtKdLayout pt_kd_layout(const PtRenderArgs& a) {
         l.wrows = cap < l.srows + 2 ? cap : l.srows + 2;
         l.lane_rows = cap - l.wrows;
     }
-    // the levels that get no slot are recomputed from the path table (PtKdSav, pt_trace.h): 3 words per such level, in the slack behind the wavefront's stack
+    // the levels that get no slot are recomputed from the path table (PtKdSav, pt_walk_kd.h): 3 words per such level, in the slack behind the wavefront's stack
     // (its rows hold srows x 64 words, the walks need scene.stack_cap of them) or, where that is too small, in two rows taken from the level slots
     int lv = (l.wrows - l.srows) / 2;
     lv = lv < 0 ? 0 : (lv > a.scene.kd_levels ? a.scene.kd_levels : lv);
@@ -125,7 +125,6 @@ PT_HD void pt_trace_wave(const PtRenderArgs& a, const PtRay& ray, bool tracing, 
 #else
     const uint32_t wave = 0;
 #endif
-#ifndef PT_NO_PACKET
     // The wavefront's stack is a linear region of the block's LDS stack area: all of the wavefront's share where no lane needs a
     // stack of its own, else the part behind the lanes' rows (KDMesh trees are walked per lane, pt_kdmesh_hit).
     if (MODE == PT_MODE_FLAT_NOMESH || MODE == PT_MODE_HIER_NOMESH) {
@@ -155,9 +154,6 @@ PT_HD void pt_trace_wave(const PtRenderArgs& a, const PtRay& ray, bool tracing, 
         if (kl.path_word < stack_words) stack_words = kl.path_word;  // (the path table sits in the slack of the stack's rows: the stack ends where it begins)
         pt_trace_packet_kd<STATS, MODE == PT_MODE_KD || MODE == PT_MODE_KD_MESH, MODE == PT_MODE_KD>(a.scene, ray, tracing, any, hit, wbase, stack_words, sav, lane_stk, a.overflow_flag, cnt);
     }
-#else
-    if (tracing) pt_trace<MODE, STATS>(a.scene, ray, any, hit, stk, cnt);
-#endif
 }
 
 // The first words of the wavefront's own traversal stack (free between walks): the queue through which offered rays find takers
@@ -197,12 +193,10 @@ __global__ void __launch_bounds__(PT_BLOCK, WAVES) pt_render_simple_kernel(PtRen
     constexpr bool EYE_TABLE = MODE == PT_MODE_FLAT_NOMESH && !CHAIN && !STATS;
 #endif
     // The surface of a hit from records fetched once per wavefront and node (pt_hit_surface_uniform_flat): the mesh-free flat_scene kernel of scenes without
-    // reflection or maps. The counting instantiations keep the per-lane form (-DPT_UNIFORM_HIT_STATS: they take this one and count its passes);
+    // reflection or maps. The counting instantiations keep the per-lane form;
     // -DPT_NO_UNIFORM_HIT: the per-lane form everywhere (A/B).
 #if defined(PT_NO_UNIFORM_HIT)
     constexpr bool UNIFORM_HIT = false;
-#elif defined(PT_UNIFORM_HIT_STATS)
-    constexpr bool UNIFORM_HIT = MODE == PT_MODE_FLAT_NOMESH && !TEX && !CHAIN;
 #else
     constexpr bool UNIFORM_HIT = MODE == PT_MODE_FLAT_NOMESH && !TEX && !CHAIN && !STATS;
 #endif
@@ -210,7 +204,7 @@ __global__ void __launch_bounds__(PT_BLOCK, WAVES) pt_render_simple_kernel(PtRen
     const PtRenderArgs& a = a0;
     const uint32_t lane_global = blockIdx.x * PT_BLOCK + threadIdx.x;
     const unsigned lane = threadIdx.x & 63u;
-    [[maybe_unused]] const PtSceneView& sc = a.scene;  // (shadowed per item by the re-read arguments' view unless -DPT_NO_ARGS_AGAIN)
+    [[maybe_unused]] const PtSceneView& sc = a.scene;  // (shadowed per item by the re-read arguments' view)
     PtStackSpill stk;
     stk.base = pt_lds + threadIdx.x;
     stk.cap = a.stack_lds_cap;
@@ -274,11 +268,10 @@ __global__ void __launch_bounds__(PT_BLOCK, WAVES) pt_render_simple_kernel(PtRen
 #define PT_SEC_SKIP() do { } while (0)
 #define PT_SEC_END(k) do { } while (0)
 #endif
-#ifndef PT_NO_ARGS_AGAIN  // (shadows the kernel's own view of its arguments for the rest of the item. The k-d semantics of mesh-free scenes are as fast without
+        // (shadows the kernel's own view of its arguments for the rest of the item. The k-d semantics of mesh-free scenes are as fast without
         // - 30.5 against 30.7 ms on big-scene, c22 / c50 -; with mesh instances they gain like the others: mirror 8.7 -> 9.6 Gray/s, macho-cows 6.7 -> 7.2, c50)
         const PtRenderArgs& a = pt_args_again(a0);
         const PtSceneView& sc = a.scene;
-#endif
         // ---- the primary ray of this lane's sample (render.rs:36-41, camera.rs:48-84)
         uint32_t x, y;
         bool mine;
@@ -338,10 +331,6 @@ __global__ void __launch_bounds__(PT_BLOCK, WAVES) pt_render_simple_kernel(PtRen
                         surfaced = true;
                     }
                 }
-#ifdef PT_UNIFORM_HIT_STATS  // diag[0] items with a shaded lane, diag[1] those whose lanes all took ONE pass of the loop, diag[2] passes, diag[3] items with lanes left to the per-lane form
-                if (STATS && lane == 0) { cnt.diag[0]++; cnt.diag[2] += passes; }
-                { const bool left = PT_BALLOT(shaded && !surfaced) != 0ull; if (STATS && lane == 0) { if (passes == 1 && !left) cnt.diag[1]++; if (left) cnt.diag[3]++; } }
-#endif
             }
             if (shaded) {
                 if (STATS) cnt.hits++;
@@ -362,9 +351,8 @@ __global__ void __launch_bounds__(PT_BLOCK, WAVES) pt_render_simple_kernel(PtRen
                 PtVec3 kd = pt_v3(m[0], m[1], m[2]);
                 if (TEX && (ftag & PT_FS_TEXEL)) kd = pt_v3(sc.srgb_lut[ftag & 255u], sc.srgb_lut[(ftag >> 8) & 255u], sc.srgb_lut[(ftag >> 16) & 255u]);
                 color = pt_v3(sc.ambient[0], sc.ambient[1], sc.ambient[2]) * kd;  // material.rs:148
-#ifndef PT_NO_LDS_COLOR  // the colour so far and the distance to the light wait in the lane's LDS column (slots of P and the tag, unused here) while the shadow ray is walked: eight registers the walks need more
+                // the colour so far and the distance to the light wait in the lane's LDS column (slots of P and the tag, unused here) while the shadow ray is walked: eight registers the walks need more
                 fr.set_l3(PT_L_P, color);
-#endif
             }
             PT_SEC_END(4);
             for (uint32_t li = 0; li < sc.n_lights; li++) {  // material.rs:149-210, one light after the other
@@ -393,9 +381,7 @@ __global__ void __launch_bounds__(PT_BLOCK, WAVES) pt_render_simple_kernel(PtRen
                     PtVec3 hit_to_light = lpos - sray.o;
                     light_dist = pt_length(hit_to_light);
                     sray.d = hit_to_light / light_dist;
-#ifndef PT_NO_LDS_COLOR
                     fr.l(PT_L_TAG) = light_dist;
-#endif
                     if (STATS) cnt.shadow++;
                 }
                 if (area) udraw += 2;
@@ -490,16 +476,14 @@ __global__ void __launch_bounds__(PT_BLOCK, WAVES) pt_render_simple_kernel(PtRen
                     PtVec3 hit_to_light = lpos - sray.o;
                     light_dist = pt_length(hit_to_light);
                     sray.d = hit_to_light / light_dist;
-#ifndef PT_NO_LDS_COLOR
                     fr.l(PT_L_TAG) = light_dist;
-#endif
                     if (STATS) cnt.shadow++;
                 }
                 PtHit sh;
                 sh.t = INFINITY; sh.node = PT_NO_HIT; sh.sub = 0;
                 PT_SEC_END(6);
 #endif
-#if defined(PT_CERTAIN_SHADOW_FORM) && !defined(PT_CYCLES) && !defined(PT_ABLATE) && !defined(PT_NO_PACKET)
+#if defined(PT_CERTAIN_SHADOW_FORM) && !defined(PT_CYCLES) && !defined(PT_ABLATE)
                 if (CERTAIN && occ.entry) {  // the table's test with the entries read above (what pt_trace_wave does for this mode, and pt_trace_packet behind it)
                     const int words = a.stack_lds_cap * 64;
                     pt_trace_packet_occ<STATS, false>(sc, sray, shaded, sh, pt_lds + (size_t)(threadIdx.x >> 6) * words, words, a.overflow_flag, &cnt, occ, hint);
@@ -514,18 +498,12 @@ __global__ void __launch_bounds__(PT_BLOCK, WAVES) pt_render_simple_kernel(PtRen
                     const double* m = sc.materials + 10 * (size_t)mat;
                     PtVec3 kd = pt_v3(m[0], m[1], m[2]), ks = pt_v3(m[3], m[4], m[5]);
                     if (TEX && (ftag & PT_FS_TEXEL)) kd = pt_v3(sc.srgb_lut[ftag & 255u], sc.srgb_lut[(ftag >> 8) & 255u], sc.srgb_lut[(ftag >> 16) & 255u]);
-#ifndef PT_NO_LDS_COLOR
                     fr.set_l3(PT_L_P, fr.l3(PT_L_P) + pt_light_term(pt_v3(lc[0], lc[1], lf[0]), pt_v3(lf[1], lf[2], lf[3]), sray.d, fr.l(PT_L_TAG), fr.l3(PT_L_N), fr.l3(PT_L_D), kd, ks, m[6]));
-#else
-                    color = color + pt_light_term(pt_v3(lc[0], lc[1], lf[0]), pt_v3(lf[1], lf[2], lf[3]), sray.d, light_dist, fr.l3(PT_L_N), fr.l3(PT_L_D), kd, ks, m[6]);
-#endif
                 }
                 PT_SEC_END(7);
             }
             if (shaded) {
-#ifndef PT_NO_LDS_COLOR
                 color = fr.l3(PT_L_P);
-#endif
                 const double* m = sc.materials + 10 * (size_t)mat;
                 const double reflectivity = m[7], glossy = m[8];
                 if (!CHAIN || !(reflectivity > 0.0)) {  // material.rs:216: nothing is reflected
@@ -577,21 +555,13 @@ __global__ void __launch_bounds__(PT_BLOCK, WAVES) pt_render_simple_kernel(PtRen
             const bool mine2 = pt_item_lane_fast(a, w, lane, &it, &x2, &y2);
             if (mine2 && it.first) {
                 PtVec3 sum = fr.l3(PT_L_VALUE);
-#ifdef PT_UNBOUNDED_CHUNK_LOOP  // (A/B only)
-                for (uint32_t k = 1; k < it.count; k++) {
-#else
                 for (uint32_t k = 1; k < it.count && k < PT_SAMPLE_CHUNK; k++) {  // (bounded by a constant as well: a corrupted count must not spin - profiles/r04/notes.md)
-#endif
                     const double* o = fr.lds + k;
                     sum = sum + pt_v3(o[(PT_L_VALUE + 0) * PT_FRAME_STRIDE], o[(PT_L_VALUE + 1) * PT_FRAME_STRIDE], o[(PT_L_VALUE + 2) * PT_FRAME_STRIDE]);
                 }
                 // pixel-major: where a wavefront is one pixel (SAMPLES = 64) the eight chunk-first lanes' 24-byte stores fill one 192-byte run instead of eight
                 // lines 1,536 bytes apart (round 3: 0.97 GB HBM-side per big-scene frame for 0.45 GB of payload, the write granularity's doing)
-#ifdef PT_ACCUM_CHUNK_MAJOR  // (A/B only: round 3's layout)
-                double* o = a.accum + 3 * ((size_t)(it.slot >> 6) * a.n_chunks * 64 + (size_t)it.chunk * 64 + (it.slot & 63u));
-#else
                 double* o = a.accum + 3 * ((size_t)it.slot * a.n_chunks + it.chunk);
-#endif
                 o[0] = sum.x; o[1] = sum.y; o[2] = sum.z;
             }
         }

@@ -28,10 +28,10 @@ enum { PT_MODE_FLAT = 1, PT_MODE_KD = 2, PT_MODE_FLAT_NOMESH = 3, PT_MODE_FLAT_K
 // Boxes are f32, rounded OUTWARD at build time: the tree only decides which candidates are tested
 // (every accepted hit is produced by the f64 reference arithmetic of the primitive tests), so its
 // own arithmetic may be single precision as long as it never rejects a box the f64 ray touches
-// (pt_slab32 in pt_trace.h carries the error bounds).
+// (pt_slab32 in pt_walk_lane.h carries the error bounds).
 struct PtBvhNode {
     float lo[3][2], hi[3][2];  // [axis][child]: the two children's planes of one axis side by side, so that a wave-uniform walk
-                               // feeds one packed f32 fma with the pair straight from scalar registers (pt_trace.h: pt_slab_pk2)
+                               // feeds one packed f32 fma with the pair straight from scalar registers (pt_walk_wave.h: pt_slab_pk2)
     uint32_t child0, child1;
     uint32_t pad[2];
 };  // 64 bytes = one s_load_dwordx16 / four 16-byte loads
@@ -74,7 +74,7 @@ struct PtMeshInfo {
 };
 
 static_assert(offsetof(PtMeshInfo, tri_first) == 96 && offsetof(PtMeshInfo, blas_root) == 104 && offsetof(PtMeshInfo, kd_root) == 108,
-              "pt_sload_mat12_x4 (pt_trace.h) reads {tri_first, tri_count, blas_root, kd_root} as the 16 bytes behind bbox_inv");
+              "pt_sload_mat12_x4 (pt_walk_wave.h) reads {tri_first, tri_count, blas_root, kd_root} as the 16 bytes behind bbox_inv");
 
 struct PtTexInfo {  // one RgbImageBuffer (texture.rs:74-76) inside tex_rgb
     uint64_t offset;
@@ -125,7 +125,7 @@ struct PtSceneView {
     const uint32_t* chain;      // graph node indices, root first
     const uint32_t* dfs_rank;   // per flattened node: depth-first order, a node before its children (who wins equal hits)
     const uint32_t* hier_rec;   // per flattened node 8 words: levels on its path (bits 0-7; 255 = more than 7: use chain_off / chain) | bit 8 + k set where
-                                // level k's three matrices are the identity; then the graph node indices of levels 0..6, root first (pt_trace.h)
+                                // level k's three matrices are the identity; then the graph node indices of levels 0..6, root first (pt_walk_wave.h)
     const float* kd_box;     // KD mode: non-null = PtKdNode::box is valid and the walk culls with it (the array itself is a copy kept for tools); else null
     const float* node_box;   // KD mode: per kd_items entry, that node's padded world box as 6 f32 rounded outward (leaf pre-cull in pt_trace_kd); else null
     double kd_extent;  // bounding_box.rs:95-99: squared diagonal of the root bounds

@@ -9,7 +9,7 @@
 // ends at the first hit inside the range. Whatever the walk reports is therefore in range; a miss leaves hit.node = PT_NO_HIT. Two tests are the exception,
 // because their outcome for a hit just inside the bound depends on more than the exact comparison t < t_max: a KDMesh instance's own triangle k-d tree (its side
 // classification reads the range's end, pt_kdmesh_hit) and a Mesh instance's box test (the box's entry parameter is rounded differently from a triangle's t). While
-// the lane has found nothing both get [EPSILON, inf), and a KDMesh's hit is kept iff t < t_max (PT_WALK_KDMESH_HIT, PT_WALK_MESH_BOX_END in pt_trace.h) - the
+// the lane has found nothing both get [EPSILON, inf), and a KDMesh's hit is kept iff t < t_max (PT_WALK_KDMESH_HIT, PT_WALK_MESH_BOX_END in pt_walk_wave.h) - the
 // unbounded result, filtered, as in the k-d semantics below.
 // k-d semantics: by definition the UNBOUNDED walk's result, filtered (the crate's own bounded range would enter the split classification, node.rs:121). The
 // walk (pt_trace_packet_kd, untouched) resets the bound itself and runs as a nearest-hit walk also for any = true - an occlusion walk may stop at an occluder
@@ -17,7 +17,7 @@
 #pragma once
 
 #ifndef PT_WALK_ENTRY_T
-#error "pt_segments.h: define PT_WALK_ENTRY_T / PT_WALK_ENTRY_TM first (pt_segments_inst.hip) - with the defaults of pt_trace.h the walks would ignore t_max"
+#error "pt_segments.h: define PT_WALK_ENTRY_T / PT_WALK_ENTRY_TM first (pt_segments_inst.hip) - with the defaults of pt_walk_wave.h the walks would ignore t_max"
 #endif
 
 #include "pt_render_kernel.h"

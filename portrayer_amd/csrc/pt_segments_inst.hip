@@ -1,7 +1,7 @@
 // One traversal mode's instantiation of pt_segments_kernel (pt_segments.h) and its launcher. Compiled once per mode, -DPT_INST_MODE=1..9
 // (Makefile: pt_segments_m<mode>.o), beside the ray-query pass's objects and through the same check / repair of the assembly.
 //
-// The one translation unit in which the wavefront walks of the flat_scene and hierarchical semantics do NOT start at infinity (pt_trace.h, PT_WALK_ENTRY_T):
+// The one translation unit in which the wavefront walks of the flat_scene and hierarchical semantics do NOT start at infinity (pt_walk_wave.h, PT_WALK_ENTRY_T):
 // a lane enters with best.t = its t_max, and the slab tests prune with that bound's f32 image from the first box on; a KDMesh instance's own tree is walked over
 // the unbounded range and its hit filtered (PT_WALK_KDMESH_HIT), and a Mesh instance's box is tested over the unbounded range (PT_WALK_MESH_BOX_END), both while
 // the lane has found nothing: the two tests whose outcome for a hit just inside the bound depends on more than the exact comparison t < t_max.

@@ -39,7 +39,6 @@
 #include "pt_trace.h"
 
 #define PT_MAX_DEPTH 10  // material.rs:12
-#define PT_SPILL_SLOTS 11
 #define PT_SPILL_STRIDE 16  // doubles per parked frame: one 128-byte line, so that a push or pop of one lane touches one line
 #define PT_SPILL_DEPTHS (PT_MAX_DEPTH + 1)  // frames at depth 0..9 can have a child in flight; depth 10 only parks a colour between rounds of > 32 lights
 #define PT_PARK_F64 12                // a parked frame: the PT_H_* slots 0..11
@@ -48,12 +47,10 @@
 // sample index), then the chunk sums sequentially (ascending chunk index). This is the build's
 // summation contract (the reference's rayon reduce has no fixed association, render.rs:36-43); it
 // lets a chunk's samples run side by side in the lanes of one wavefront.
-#ifndef PT_SAMPLE_CHUNK
 #define PT_SAMPLE_CHUNK 8
-#endif
 // A compiler-only fence: stops hipcc from hoisting the loads of one interpreter state above the
 // stores of the previous one (register pressure), costs no instruction.
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(PT_NO_STATE_FENCE)
+#if defined(__HIP_DEVICE_COMPILE__)
 #define PT_FENCE asm volatile("" ::: "memory")
 #else
 #define PT_FENCE
@@ -66,9 +63,7 @@
 #endif
 #define PT_QUEUE_STRIDE 32  // words between two queue counters: one 128-byte line each
 #define PT_FINE_QUEUES 64
-#ifndef PT_WORK_BATCH_MAX
 #define PT_WORK_BATCH_MAX 8  // most work items (64 lanes each) a wavefront takes from the global counter at a time (PtRenderArgs::batch_max): 32 -> 8 costs big-scene 0.4 % and gives the 1.25 M-triangle scenes 4-7 % (profiles/r02/notes.md)
-#endif
 
 enum { PT_JITTER_CENTRE = 0, PT_JITTER_RNG = 1 };
 enum { PT_ST_NEW_SAMPLE = 0, PT_ST_CLOSEST_DONE = 1, PT_ST_LIGHT = 2, PT_ST_SHADOW_DONE = 3, PT_ST_SHADE = 4, PT_ST_DONE = 5, PT_ST_WAIT_FORK = 6 };
@@ -93,16 +88,6 @@ enum { PT_H_MAIL = 12, PT_H_MAIL_TICKET = 15, PT_RESULT_DEPTH = PT_MAX_DEPTH };
 #define PT_FS_TEXEL 0x80000000u  // hit frame: bits 0..23 are the texel's R, G, B bytes; the diffuse colour is srgb_lut[] of them (texture.rs:162-168)
 #define PT_LIGHT_ROUND 32  // shadow-ray results are kept as one bit per light, 32 lights at a time
 
-// true when PORTRAYER_INTERP=1 asks for the interpreter kernel where the straight-line kernel would run (builds with -DPT_KEEP_INTERP only)
-inline bool pt_interpreter_forced() {
-#ifdef PT_KEEP_INTERP
-    const char* e = getenv("PORTRAYER_INTERP");
-    return e && atoi(e) > 0;
-#else
-    return false;
-#endif
-}
-
 // Division of a wave-uniform index by a launch constant without a divider: q = (n * magic) >> shift, exact for every n < 2^31
 // (magic = ceil(2^shift / d), shift = 31 + ceil(log2 d): the error of magic / 2^shift is below 2^-31 / d ... n e < 2^shift).
 // The scalar unit has multiply-high and shifts but no division: hipcc turns `w / n_groups` into a float reciprocal on the VECTOR
@@ -119,17 +104,13 @@ inline PtFastDiv pt_fastdiv_make(uint32_t d) {
     return f;
 }
 
-enum { PT_RUN_INTERP = 0, PT_RUN_INTERP_PARK = 1, PT_RUN_LINE4 = 2, PT_RUN_LINE3 = 3, PT_RUN_INTERP4 = 4, PT_RUN_INTERP_FORK = 5, PT_RUN_LINE5 = 6, PT_RUN_CHAIN = 7 };  // PtRenderArgs::run_variant, explained in pt_render_kernel.h
+enum { PT_RUN_INTERP = 0, PT_RUN_INTERP_PARK = 1, PT_RUN_LINE4 = 2, PT_RUN_LINE3 = 3, PT_RUN_INTERP_FORK = 5, PT_RUN_LINE5 = 6, PT_RUN_CHAIN = 7 };  // PtRenderArgs::run_variant, explained in pt_render_kernel.h
 
-#ifndef PT_LINE_TOP_WAVES
 // Waves per SIMD of the mesh-free straight-line kernels' densest instantiation (flat_scene / hierarchical semantics): 6 since round 4 (80 registers, 26 KB of
 // LDS a block; big-scene +3.1 %, hierarchical +2.3 %, 3840x2160x256 +3.3 %: profiles/r04/notes.md section 5 - round 3 measured the same gain and could not ship
-// it because that build hung: section 2). -DPT_LINE_TOP_WAVES=5 builds round 3's.
+// it because that build hung: section 2). Round 3's value was 5.
 #define PT_LINE_TOP_WAVES 6
-#endif
-#ifndef PT_MESH_TOP_WAVES
 #define PT_MESH_TOP_WAVES 5   // ... and of scenes of very many triangles in plain Mesh instances (6 measured: profiles/r04/notes.md section 7)
-#endif
 struct PtRenderArgs {
     PtSceneView scene;
     PtCamera cam;
@@ -323,22 +304,8 @@ PT_HD uint32_t pt_lane_sample(const PtRenderArgs& a, uint32_t item) {
     return it.sample;
 }
 
-// -DPT_XY_ON_DEMAND: the pixel coordinates too (experiment; see profiles/r02/notes.md)
-PT_HD void pt_lane_xy(const PtRenderArgs& a, uint32_t item, uint32_t* x, uint32_t* y) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    asm volatile("" : "+s"(item));
-    const uint32_t lane = threadIdx.x & 63u;
-#else
-    const uint32_t lane = 0;
-#endif
-    PtItemLane it;
-    pt_item_lane_fast(a, item, lane, &it, x, y);
-}
-#ifdef PT_XY_ON_DEMAND
-#define PT_LANE_XY(a, L, X, Y) uint32_t X, Y; pt_lane_xy(a, (L).item, &X, &Y)
-#else
+// (the pixel coordinates stay in the lane's state: worked out on demand like the sample index they cost big-scene 3 %, profiles/r02/notes.md)
 #define PT_LANE_XY(a, L, X, Y) const uint32_t X = (L).x, Y = (L).y
-#endif
 
 PT_HD PtVec3 pt_background(const PtRenderArgs& a, uint32_t x, uint32_t y) {  // render.rs:31-34
     const double* b = a.background_rows ? a.background + 3 * (size_t)y : a.background + 3 * ((size_t)y * a.width + x);
@@ -366,11 +333,7 @@ PT_HD PtRay pt_camera_ray(const PtCamera& c, double x, double y) {  // camera.rs
 #else
 #define PT_POW_IMPL(x, y) pt_pow_glibc(x, y)
 #endif
-#ifdef PT_POW_INLINE
-PT_HD double pt_pow(double x, double y) { return PT_POW_IMPL(x, y); }
-#else
 PT_NOINLINE double pt_pow(double x, double y) { return PT_POW_IMPL(x, y); }
-#endif
 
 PT_HD uint8_t pt_to_u8(double c) {  // render.rs:143-147: `as u8` saturates, NaN -> 0
     double v = c * 255.0;
@@ -398,15 +361,9 @@ PT_HD bool pt_refracted_direction(PtVec3 ray_dir, PtVec3 normal, double eta, PtV
 
 // A pixel's chunk sums added up in ascending order (the summation contract). p = pixel slot.
 PT_HD PtVec3 pt_pixel_sum(const PtRenderArgs& a, uint32_t p) {
-#ifdef PT_ACCUM_CHUNK_MAJOR
-    const double* acc = a.accum + 3 * ((size_t)(p >> 6) * a.n_chunks * 64 + (p & 63));
-    PtVec3 sum = pt_v3(acc[0], acc[1], acc[2]);
-    for (uint32_t k = 1; k < a.n_chunks; k++) sum = sum + pt_v3(acc[192 * (size_t)k], acc[192 * (size_t)k + 1], acc[192 * (size_t)k + 2]);
-#else
     const double* acc = a.accum + 3 * (size_t)p * a.n_chunks;  // the pixel's chunk sums, side by side
     PtVec3 sum = pt_v3(acc[0], acc[1], acc[2]);
     for (uint32_t k = 1; k < a.n_chunks; k++) sum = sum + pt_v3(acc[3 * (size_t)k], acc[3 * (size_t)k + 1], acc[3 * (size_t)k + 2]);
-#endif
     return sum;
 }
 // One pixel's sum -> mean, gamma, clamp, u8 (render.rs:45-50, :143-147). p = pixel slot.
@@ -756,11 +713,7 @@ PT_HD PtVec3 pt_light_term(PtVec3 lcol, PtVec3 falloff, PtVec3 light_dir, double
 
 // Runs the lane's interpreter until it needs a ray traced (L.has_ray) or its sample is finished
 // (L.stage == PT_ST_DONE, colour in the lane's LDS column). `hit` is the result of the ray the lane traced last.
-#ifdef PT_ADVANCE_NOINLINE  // measured slower at every occupancy (profiles/r01/notes.md)
-#define PT_ADVANCE_ATTR PT_NOINLINE
-#else
-#define PT_ADVANCE_ATTR PT_HD
-#endif
+#define PT_ADVANCE_ATTR PT_HD  // (in line: out of line it measured slower at every occupancy, profiles/r01/notes.md)
 // TEX = false compiles the texture / normal-map path out (scenes without mapped materials).
 PT_HD uint64_t pt_fork_ticket(uint32_t nonce, uint32_t seq, int32_t depth) { return ((uint64_t)(nonce & 0xFFFFFFu) << 40) | ((uint64_t)(seq & 0xFFFFFFu) << 8) | (uint64_t)(depth & 0xFF) | (1ull << 39); }
 PT_HD uint64_t pt_mail_load(const double* slot) {

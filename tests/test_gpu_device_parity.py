@@ -33,7 +33,7 @@ def test_device_arithmetic_is_ieee(ctx):
 
 def test_short_division_of_the_kd_walk_is_the_hardware_division(ctx):
     """Every straddled split of the k-d walk divides by the same direction component: pt_div_fast() finishes a division in three
-    instructions from a reciprocal refined once per ray (pt_trace.h). It must be `/` bit for bit wherever its exponent test admits the
+    instructions from a reciprocal refined once per ray (pt_walk_kd.h). It must be `/` bit for bit wherever its exponent test admits the
     operands (biased exponents in [640, 1407]); everything else - zeros, denormals, infinities, NaNs, huge and tiny values - must be
     refused (NaN marker here; the walk then takes the real division). Random mantissas over the whole window, its edges, exact
     quotients, powers of two, operands one ulp apart."""

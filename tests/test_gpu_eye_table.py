@@ -1,4 +1,4 @@
-"""The eye table of the mesh-free flat_scene straight-line kernels (pt_api.hip: pt_eye_table_kernel; pt_trace.h: pt_test_node_uniform<EYE>; pt_shade.h:
+"""The eye table of the mesh-free flat_scene straight-line kernels (pt_api.hip: pt_eye_table_kernel; pt_walk_wave.h: pt_test_node_uniform<EYE>; pt_shade.h:
 pt_hit_model<EYE>): the camera's eye in every node's space is worked out once per launch and read through the scalar cache by the primary walk's leaf tests
 and by the surface of a primary hit, instead of being transformed in every lane. The same function on the same operands, so every image and every f64 mean
 must stay what the oracle computes, bit for bit:

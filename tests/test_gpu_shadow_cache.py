@@ -1,4 +1,4 @@
-"""The occluder table of the mesh-free walks' shadow rays (pt_trace.h: pt_trace_packet): a shadow ray tests the node that
+"""The occluder table of the mesh-free walks' shadow rays (pt_walk_wave.h: pt_trace_packet): a shadow ray tests the node that
 last blocked a ray of its tile toward the same light before it walks the tree. Its answer is an OR over nodes, so the images must not
 change: the plain instantiations with the table (the default) and without it (PORTRAYER_SHADOW_CACHE=0) against each other at the
 benchmark's size, and against the oracle at small sizes - big-scene, area lights (a light position per lane) and a scene in which

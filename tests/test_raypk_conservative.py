@@ -1,4 +1,4 @@
-"""The tree walks' f32 slab test may only err towards visiting more boxes (pt_trace.h: pt_raypk_axis, pt_slab_pk2, pt_slab_seg_pk).
+"""The tree walks' f32 slab test may only err towards visiting more boxes (pt_walk_lane.h: pt_raypk_axis, pt_slab_seg_pk; pt_walk_wave.h: pt_slab_pk2).
 Through the host build of that code (pt_test_raypk: no GPU) 2.3 million ray / box pairs with a fixed seed: whenever the exact f64 ray
 meets the f32 box within [0, t_max], every form of the test must accept the box.
 
