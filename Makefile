@@ -102,14 +102,16 @@ verify-mi:
 	for m in $(RENDER_MODES); do $(HIPCC) $(HIPFLAGS) --offload-device-only -mllvm -verify-machineinstrs -DPT_INST_MODE=$$m -c $(CSRC)/pt_render_inst.hip -o /dev/null || exit 1; done
 
 # The switches a build may set (EXTRA_HIPFLAGS, `make variant`); this list is the one place that says which exist. Instrumentation that a driver script
-# under profiles/ builds - PT_DIAG (diag.sh), PT_CYCLES (cycles.sh), PT_TIMELINE (timeline.sh), PT_OCCLUDER_STATS (occluder_stats.py), PT_ABLATE
+# under profiles/ builds - PT_DIAG (diag.sh), PT_CYCLES (cycles.sh), PT_TIMELINE (timeline.sh), PT_OCCLUDER_STATS (occluder_stats.py), PT_PIXEL_LIST_STATS (pixel_list_stats.py), PT_ABLATE
 # (light_slope.py) - and the off switches of shipped optimisations whose gain hangs on this toolchain's register allocation and is measured again after a
 # ROCm update (DESIGN.md names each as its A/B). PT_MIN_WAVES=<n> (profiles/ab.sh) takes a value of the user's and is not listed.
 # `make -j8 switches` compiles each switch alone, device-only, to /dev/null (the pattern of verify-mi, the same HIPFLAGS) for the render modes whose object
 # it changes - MODES_<switch>, all nine where nothing says so: a switch that stops compiling is noticed. Not part of `all`, and no test runs it.
 SWITCHES := PT_DIAG PT_CYCLES PT_TIMELINE PT_OCCLUDER_STATS=1 PT_OCCLUDER_STATS=2 PT_ABLATE=1 PT_ABLATE=2 PT_ABLATE=3 PT_ABLATE=5 PT_ABLATE=6 \
-            PT_NO_UNIFORM_HIT PT_NO_EYE_TABLE PT_NO_CERTAIN_SHADOW PT_POW_OCML
+            PT_NO_UNIFORM_HIT PT_NO_EYE_TABLE PT_NO_CERTAIN_SHADOW PT_NO_PIXEL_LISTS PT_PIXEL_LIST_STATS PT_POW_OCML
 MODES_PT_OCCLUDER_STATS := 3 6
+MODES_PT_NO_PIXEL_LISTS := 3
+MODES_PT_PIXEL_LIST_STATS := 3
 MODES_PT_NO_UNIFORM_HIT := 3
 MODES_PT_NO_EYE_TABLE := 3
 MODES_PT_NO_CERTAIN_SHADOW := 3

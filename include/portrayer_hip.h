@@ -673,6 +673,16 @@ int pt_test_raypk(uint64_t n, int body, const double *origins, const double *dir
  * 5 cube have a ball; every other type is never certain) with rows 0..2 of its forward and inverse matrices in fwd[12i..] and inv[12i..], a shaded point P[3i..] and a light position L[3i..].
  * out_certain[i]: the single-precision test says the shadow ray certainly ends in the node; out_exact_hit[i]: the exact test of that node for that ray says so. */
 int pt_test_certain_shadow(uint64_t n, int type, const double *fwd, const double *inv, const double *P, const double *L, int32_t *out_certain, int32_t *out_exact_hit);
+/* Host-side run (no GPU, no context) of the beam test behind the primary rays' per-pixel candidate lists, beside the tree walk's own slab test. Case i: a camera
+ * (cameras[19i..]: eye, rows 0..2 of view_to_world, fov_factor, aspect_ratio, width, height), a pixel (pixels[2i..]: x, y), a sample position inside it
+ * (jitters[2i..], each in [0, 1)) and a box (box_lo[3i..], box_hi[3i..]). accept[i]: some ray through the pixel may reach the box, as the list kernel decides it;
+ * bound[i]: the lower bound on every such ray's entry parameter it stores (0 where it rejects); walk[i]: the walk's slab test of the box for the sample's ray, no bound
+ * on t - bit 0 the wavefront form for mixed signs accepts, bit 1 the form for the ray's own octant does; rays (may be NULL): the sample's ray, origin and direction. */
+int pt_test_pixel_beam(uint64_t n, const double *cameras, const uint32_t *pixels, const double *jitters, const float *box_lo, const float *box_hi,
+                       int32_t *accept, float *bound, int32_t *walk, double *rays);
+/* What the last launch of the context left in its per-pixel candidate lists (tests; that launch must be closed). out has 11 entries: [0] the records - 0 where the launch
+ * had no lists -, [1] the background ones (empty, nothing left out), [2] those cut at the cap, [3] those marked "take the walk", [4 + n] those with n entries, n = 0 .. 6. */
+int pt_test_pixel_list_summary(pt_context *ctx, uint64_t *out);
 /* Host-side run (no GPU, no context) of the film's running sum: `samples` (n x 3) given to one pixel in n_cuts consecutive adds of cuts[k] samples each
  * (their sum must be n), through the functions the film's fold and resolve kernels call. out_sum: what resolve divides by n. */
 int pt_test_film_fold_host(uint32_t n, const double *samples, const uint32_t *cuts, uint32_t n_cuts, double out_sum[3]);

@@ -24,6 +24,7 @@
 #include "pt_denoise.h"
 #include "pt_render_inst.h"
 #include "pt_shade.h"
+#include "pt_pixel_list.h"
 
 // ------------------------------------------------------------------------------------------------
 // Kernels
@@ -250,6 +251,75 @@ __global__ void __launch_bounds__(256) pt_certain_table_kernel(const uint32_t* _
     pt_certain_ball(info[4 * (size_t)i], fwd + 12 * (size_t)i, inv + 12 * (size_t)i, tab + 4 * (size_t)i);
 }
 
+// The launch's per-pixel candidate lists (pt_pixel_list.h), behind the eye table and the certain-shadow table: a wavefront per 8x8 tile of the launch's own tiles, a lane
+// per pixel slot - pixels of partial tiles outside the slice get a record like any other. The 64 beams of a tile reach nearly the same nodes, so ONE walk of sc.bvh
+// serves them: a node is entered when any lane's beam reaches its box (a lane whose beam missed the box above tests the children all the same: a leaf too many in a list
+// changes nothing), the pending nodes are one list per wavefront in LDS, and a child that is a leaf goes straight into the lists of the lanes that reach it - every item of
+// it with the leaf box's bound. A lane's list is its LDS column, kept sorted (pt_pl_insert). A stack that runs full marks the tile's 64 records "take the walk".
+// cap (PORTRAYER_PIXEL_LIST_CAP, tests only): entries a list may hold, <= PT_PL_K.
+#define PT_PL_BLOCK 256
+#define PT_PL_STACK 64
+__global__ void __launch_bounds__(PT_PL_BLOCK) pt_pixel_list_kernel(PtRenderArgs a, uint32_t* __restrict__ table, uint32_t cap) {
+    __shared__ uint32_t s_list[PT_PL_BLOCK / 64][PT_PL_K][64];
+    __shared__ uint32_t s_stack[PT_PL_BLOCK / 64][PT_PL_STACK];
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    const uint32_t tile_local = blockIdx.x * (PT_PL_BLOCK / 64) + wave;
+    if (tile_local >= a.n_slots / 64u) return;  // (wave-uniform)
+    const PtSceneView& sc = a.scene;
+    const uint32_t slot = tile_local * 64u + lane;
+    uint32_t x, y;
+    pt_slot_to_pixel(a, slot, &x, &y);
+    const PtBeam beam = pt_beam_setup(a.cam, (double)x, (double)y);
+    uint32_t* const list = &s_list[wave][0][lane];
+    uint32_t* const stack = s_stack[wave];
+    uint32_t count = 0, tail = PT_PL_INF_BITS;
+    if (cap > PT_PL_K) cap = PT_PL_K;  // (the host refuses a larger one; a list's LDS column has PT_PL_K rows)
+    bool overflowed = false;
+    int sp = 0;
+    auto add_leaf = [&](uint32_t ref, bool reached, float bound) {  // ref: a leaf reference (wave-uniform)
+        const uint32_t first = (ref & ~PT_REF_LEAF) >> 3, n = (ref & 7u) + 1u;
+        for (uint32_t i = 0; i < n; i++) {
+            const uint32_t node = sc.tlas_direct ? first : sc.bvh_items[first + i];
+            if (reached) pt_pl_insert(list, 64u, cap, &count, &tail, pt_pl_entry(bound, node));
+        }
+    };
+    const uint32_t root = sc.tlas_root;
+    if (sc.n_nodes != 0 && root != PT_REF_EMPTY) {
+        if (root & PT_REF_LEAF) add_leaf(root, true, 0.0f);  // (the walk tests a root leaf without a box test)
+        else { stack[0] = root; sp = 1; }
+    }
+    while (sp > 0) {
+        // (lane 0's pushes of the step before, seen by the whole wavefront: same wavefront, program order and a fence suffice)
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        const uint32_t cur = (uint32_t)__builtin_amdgcn_readfirstlane((int)stack[sp - 1]);
+        sp--;
+        const pt_u32x16 nd = pt_sload_node(sc.bvh, cur);  // (PtBvhNode as 16 words in scalar registers, as the render kernel's walk fetches it: lo[axis][child], hi[axis][child], the children)
+#pragma unroll
+        for (int ch = 0; ch < 2; ch++) {
+            const uint32_t ref = nd[12 + ch];
+            if (ref == PT_REF_EMPTY) continue;
+            float lo[3], hi[3], bound = 0.0f;
+#pragma unroll
+            for (int k = 0; k < 3; k++) { lo[k] = pt_f32_of(nd[2 * k + ch]); hi[k] = pt_f32_of(nd[6 + 2 * k + ch]); }
+            const bool reached = pt_beam_box(beam, lo, hi, &bound);
+            if (!__any(reached)) continue;
+            if (ref & PT_REF_LEAF) add_leaf(ref, reached, bound);
+            else if (sp < PT_PL_STACK) { if (lane == 0) stack[sp] = ref; sp++; }
+            else overflowed = true;
+        }
+    }
+    uint32_t* rec = table + (size_t)slot * PT_PL_WORDS;
+    uint32_t wds[PT_PL_WORDS];
+    wds[0] = overflowed ? PT_PL_WALK : count;
+    wds[1] = tail;
+#pragma unroll
+    for (uint32_t k = 0; k < PT_PL_K; k++) wds[2 + k] = k < count ? list[k * 64u] : 0u;
+#pragma unroll
+    for (uint32_t k = 0; k < PT_PL_WORDS; k += 4) reinterpret_cast<uint4*>(rec)[k / 4] = make_uint4(wds[k], wds[k + 1], wds[k + 2], wds[k + 3]);
+}
+
 // ------------------------------------------------------------------------------------------------
 // Context
 // ------------------------------------------------------------------------------------------------
@@ -330,6 +400,9 @@ struct pt_context {
     int slot_next = 0;     // the slot the next launch takes
     int slot_oldest = 0;   // the oldest launch not yet closed (== slot_next: none, unless every slot is pending)
     uint32_t last_mode = 0, last_variant = 0;
+    int pl_slot = -1;          // pt_test_pixel_list_summary: the slot whose eye_tab buffer holds the last launch's pixel lists (-1: that launch had none) ...
+    uint32_t pl_slots = 0;     // ... its pixel slots ...
+    size_t pl_off = 0;         // ... and where its records start in the buffer
     // The three passes beside the render, each with a PtPass of its own: all three may be in flight at once, with two renders. Beside it, what is the kind's.
     // The primary-visibility pass (pt_aov / pt_aov_device ... pt_aov_finish): the device copies of the host-buffer path's six outputs.
     struct Aov {
@@ -1936,6 +2009,86 @@ extern "C" int pt_test_raypk(uint64_t n, int body, const double* origins, const 
     return PT_OK;
 }
 
+// What the last launch of the context left in its pixel lists (tests; the launch must have been closed - pt_render, or pt_render_finish): out[0] the records (0: that
+// launch had no lists - PORTRAYER_PIXEL_LISTS=0, several pixels per wavefront, another mode or kernel), out[1] those that are background (empty, infinite tail), out[2]
+// those cut at the cap (finite tail), out[3] those marked "take the walk", out[4 + n] those with n entries, n = 0 .. PT_PL_K (5 + PT_PL_K words in all). The records are copied back and counted here.
+extern "C" int pt_test_pixel_list_summary(pt_context* c, uint64_t* out) {
+    if (!c || !out) return PT_ERR_ARGUMENT;
+    for (uint32_t k = 0; k < 5u + PT_PL_K; k++) out[k] = 0;
+    if (c->pl_slot < 0 || c->pl_slots == 0) return PT_OK;
+    PT_HIP(c, hipSetDevice(c->device));
+    PT_HIP(c, hipDeviceSynchronize());
+    std::vector<uint32_t> rec((size_t)c->pl_slots * PT_PL_WORDS);
+    const pt_context::Slot& sl = c->slot[c->pl_slot];
+    if (sl.eye_tab.bytes < c->pl_off + rec.size() * 4) return pt_fail(c, PT_ERR_ARGUMENT, "the slot's buffer no longer holds that launch's lists");
+    PT_HIP(c, hipMemcpy(rec.data(), (const char*)sl.eye_tab.p + c->pl_off, rec.size() * 4, hipMemcpyDeviceToHost));
+    out[0] = c->pl_slots;
+    for (uint32_t i = 0; i < c->pl_slots; i++) {
+        const uint32_t head = rec[(size_t)i * PT_PL_WORDS], tail = rec[(size_t)i * PT_PL_WORDS + 1];
+        if (head & PT_PL_WALK) { out[3]++; continue; }
+        const uint32_t n = head & 255u;
+        if (n > PT_PL_K) return pt_fail(c, PT_ERR_TRAVERSAL, "a pixel list longer than its record");
+        if (n == 0 && tail == PT_PL_INF_BITS) out[1]++;
+        if (tail != PT_PL_INF_BITS) out[2]++;
+        out[4 + n]++;
+    }
+    return PT_OK;
+}
+
+// Host-side run (no GPU involved) of the pixel lists' beam test (pt_pixel_list.h) beside the walk's own slab test: case i is a camera (cameras[19 i ..]: eye, rows 0..2 of
+// view_to_world, fov_factor, aspect, width, height - PtCamera's fields in order), a pixel (pixels[2 i ..]: x, y), a sample of it (jitters[2 i ..] in [0, 1): the ray of
+// pt_camera_ray(x + jx, y + jy)) and a box (3 floats each). Out per case: accept = pt_beam_box's verdict for the pixel's beam, bound = the bound it stores (0 where it
+// rejects), walk = what the walk does with the box for that sample's ray and no bound on t (pt_raypk's constants): bit 0 pt_slab_pk2<PT_OCT_MIXED> accepts, bit 1 the form of
+// the ray's own octant accepts (a ray with a switched-off axis has none: bit 1 repeats bit 0); rays (optional, 6 doubles per case): that ray's origin and direction.
+// Tests check that walk != 0 never comes with accept == 0, and that bound never exceeds the exact entry parameter.
+extern "C" int pt_test_pixel_beam(uint64_t n, const double* cameras, const uint32_t* pixels, const double* jitters, const float* box_lo, const float* box_hi,
+                                  int32_t* accept, float* bound, int32_t* walk, double* rays) {
+    if (!cameras || !pixels || !jitters || !box_lo || !box_hi || !accept || !bound || !walk) return PT_ERR_ARGUMENT;
+    for (uint64_t i = 0; i < n; i++) {
+        PtCamera cam;
+        const double* cp = cameras + 19 * i;
+        for (int k = 0; k < 3; k++) cam.eye[k] = cp[k];
+        for (int k = 0; k < 12; k++) cam.view_to_world[k] = cp[3 + k];
+        cam.fov_factor = cp[15]; cam.aspect = cp[16]; cam.width = cp[17]; cam.height = cp[18];
+        const uint32_t x = pixels[2 * i], y = pixels[2 * i + 1];
+        const float* lo = box_lo + 3 * i;
+        const float* hi = box_hi + 3 * i;
+        const PtBeam beam = pt_beam_setup(cam, (double)x, (double)y);
+        float b = 0.0f;
+        accept[i] = pt_beam_box(beam, lo, hi, &b) ? 1 : 0;
+        bound[i] = accept[i] ? b : 0.0f;
+        const PtRay r = pt_camera_ray(cam, (double)x + jitters[2 * i], (double)y + jitters[2 * i + 1]);
+        if (rays) { rays[6 * i] = r.o.x; rays[6 * i + 1] = r.o.y; rays[6 * i + 2] = r.o.z; rays[6 * i + 3] = r.d.x; rays[6 * i + 4] = r.d.y; rays[6 * i + 5] = r.d.z; }
+        PtRayPk q;
+        int s[3];
+        s[0] = pt_raypk_axis(r.o.x, r.d.x, &q.a[0], &q.b[0]); s[1] = pt_raypk_axis(r.o.y, r.d.y, &q.a[1], &q.b[1]); s[2] = pt_raypk_axis(r.o.z, r.d.z, &q.a[2], &q.b[2]);
+        pt_u32x16 rec;
+        for (int k = 0; k < 16; k++) rec[k] = 0u;
+        for (int k = 0; k < 3; k++) {
+            uint32_t l, h;
+            memcpy(&l, lo + k, 4); memcpy(&h, hi + k, 4);
+            rec[2 * k] = rec[2 * k + 1] = l; rec[6 + 2 * k] = rec[6 + 2 * k + 1] = h;
+        }
+        unsigned long long m0 = 0, m1 = 0, first = 0, o0 = 0, o1 = 0;
+        pt_slab_pk2<PT_OCT_MIXED>(rec, q, INFINITY, &m0, &m1, &first);
+        o0 = m0; o1 = m1;
+        if (s[0] && s[1] && s[2]) {
+            switch ((s[0] == 2 ? 1 : 0) | (s[1] == 2 ? 2 : 0) | (s[2] == 2 ? 4 : 0)) {
+                case 0: pt_slab_pk2<0>(rec, q, INFINITY, &o0, &o1, &first); break;
+                case 1: pt_slab_pk2<1>(rec, q, INFINITY, &o0, &o1, &first); break;
+                case 2: pt_slab_pk2<2>(rec, q, INFINITY, &o0, &o1, &first); break;
+                case 3: pt_slab_pk2<3>(rec, q, INFINITY, &o0, &o1, &first); break;
+                case 4: pt_slab_pk2<4>(rec, q, INFINITY, &o0, &o1, &first); break;
+                case 5: pt_slab_pk2<5>(rec, q, INFINITY, &o0, &o1, &first); break;
+                case 6: pt_slab_pk2<6>(rec, q, INFINITY, &o0, &o1, &first); break;
+                default: pt_slab_pk2<7>(rec, q, INFINITY, &o0, &o1, &first); break;
+            }
+        }
+        walk[i] = (m0 ? 1 : 0) | (o0 ? 2 : 0);
+    }
+    return PT_OK;
+}
+
 // Host-side run (no GPU involved) of the certain-shadow test (pt_certain.h): case i is a node of `type` with the records fwd[12 i ..], inv[12 i ..] (rows 0..2 of its two
 // matrices), a shaded point P[3 i ..] and a light position L[3 i ..]. out_certain[i]: the table routine gave the node a ball and the lane test, on the floats the kernel would
 // hold, says "certainly hit"; out_exact_hit[i]: the reference's own test of that node for the shadow ray {P, (L - P) / |L - P|} over [EPSILON, INF) (pt_ray_to_local,
@@ -2131,9 +2284,35 @@ static int pt_render_common(pt_context* c, PtRenderArgs& a, bool stats, hipStrea
 #else
     const bool certain_table = false;
 #endif
+    // The per-pixel candidate lists (pt_pixel_list.h; pt_render_simple.h: PIXEL_LISTS) behind both: the launches whose kernel reads them - the plain straight-line kernels of
+    // this mode where a wavefront is one pixel - and scenes whose node indices fit an entry's 16 bits. Their 64-byte header is written in every launch that has an eye table
+    // (0: no lists). PORTRAYER_PIXEL_LISTS=0: none (the walk's image from the same library); PORTRAYER_PIXEL_LIST_CAP=k (tests only): a list holds k entries at most, so that
+    // small scenes reach the tail bound and the fall-back. -DPT_NO_PIXEL_LISTS: no header, no lists, the kernels as they were (A/B).
+#ifndef PT_NO_PIXEL_LISTS
+    const bool list_header = eye_table;
+#ifdef PT_PIXEL_LIST_STATS  // the counting build evaluates the lists beside its walk (pt_render_simple.h): it gets them too
+    const bool list_reader = true;
+#else
+    const bool list_reader = !stats;
+#endif
+    bool pixel_lists = eye_table && list_reader && (a.run_variant == PT_RUN_LINE3 || a.run_variant == PT_RUN_LINE4 || a.run_variant == PT_RUN_LINE5) && a.k_log2 + a.c_log2 == 6u &&
+                       a.scene.n_nodes <= PT_PL_MAX_NODES && a.n_slots != 0;
+    if (const char* e = getenv("PORTRAYER_PIXEL_LISTS")) if (atoi(e) <= 0) pixel_lists = false;
+    uint32_t list_cap = PT_PL_K;
+    if (const char* e = getenv("PORTRAYER_PIXEL_LIST_CAP"); e && *e) {
+        char* end = nullptr;
+        const unsigned long long k = strtoull(e, &end, 10);
+        if (end == e || *end || k > PT_PL_K) return pt_fail(c, PT_ERR_ARGUMENT, std::string("PORTRAYER_PIXEL_LIST_CAP=") + e + ": expected 0 .. " + std::to_string(PT_PL_K));
+        list_cap = (uint32_t)k;
+    }
+#else
+    const bool list_header = false, pixel_lists = false;
+    const uint32_t list_cap = 0;
+#endif
+    const size_t list_off = pt_pl_header_offset((uint32_t)a.scene.n_nodes);
     a.eye_tab = nullptr;
     if (eye_table || certain_table) {
-        if ((rc = pt_reserve(c, sl.eye_tab, (size_t)a.scene.n_nodes * (12 * sizeof(double) + 4 * sizeof(float))))) return rc;
+        if ((rc = pt_reserve(c, sl.eye_tab, list_header ? list_off + pt_pl_bytes(pixel_lists ? a.n_slots : 0u) : (size_t)a.scene.n_nodes * (12 * sizeof(double) + 4 * sizeof(float))))) return rc;
         a.eye_tab = (const double*)sl.eye_tab.p;
     }
     a.spill = (double*)sl.spill.p;
@@ -2167,6 +2346,16 @@ static int pt_render_common(pt_context* c, PtRenderArgs& a, bool stats, hipStrea
                                (uint32_t)a.scene.n_nodes);
             PT_HIP(c, hipGetLastError());
         }
+        if (list_header) {  // behind the eye table's fill, on the launch's stream: the header, then the slot's records
+            uint32_t* const header = (uint32_t*)((char*)sl.eye_tab.p + list_off);
+            PT_HIP(c, hipMemsetD32Async((hipDeviceptr_t)header, pixel_lists ? 1 : 0, 16, stream));
+            if (pixel_lists) {
+                const uint32_t tiles = a.n_slots / 64u;
+                hipLaunchKernelGGL(pt_pixel_list_kernel, dim3((tiles + PT_PL_BLOCK / 64 - 1) / (PT_PL_BLOCK / 64)), dim3(PT_PL_BLOCK), 0, stream, a, header + 16, list_cap);
+                PT_HIP(c, hipGetLastError());
+            }
+        }
+        c->pl_slot = pixel_lists ? slot_index : -1; c->pl_slots = a.n_slots; c->pl_off = list_off + 64;
         PT_HIP(c, pt_dispatch(a, stats, c->n_cu, stream, &grid, true));
         hipLaunchKernelGGL(pt_finish_kernel, dim3((a.n_slots + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, stream, a);
         PT_HIP(c, hipGetLastError());

@@ -25,6 +25,66 @@
 #define PT_CERTAIN_SHADOW_FORM 1
 #endif
 
+// The per-pixel candidate lists of the primary stage (pt_pixel_list.h) exist where the eye table does: the plain mesh-free flat_scene kernels. Every other mode's object
+// keeps its text, and so does every object under -DPT_NO_PIXEL_LISTS (A/B: the kernels as they were, and the host fills no lists).
+#if !defined(PT_NO_PIXEL_LISTS) && !defined(PT_NO_EYE_TABLE) && (!defined(PT_INST_MODE) || PT_INST_MODE == 3)
+#define PT_PIXEL_LIST_FORM 1
+#include "pt_pixel_list.h"
+// one or two words at a wave-uniform address through the scalar cache
+typedef uint32_t pt_u32x2 __attribute__((ext_vector_type(2)));
+PT_HD uint32_t pt_sload1(const void* p) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    uint32_t v;
+    asm volatile("s_load_dword %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(v) : "s"(pt_uniform_ptr(p)) : "memory");
+    return v;
+#else
+    return *static_cast<const uint32_t*>(p);
+#endif
+}
+PT_HD pt_u32x2 pt_sload2(const void* p) {
+    pt_u32x2 v;
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("s_load_dwordx2 %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(v) : "s"(pt_uniform_ptr(p)) : "memory");
+#else
+    v = *static_cast<const pt_u32x2*>(p);
+#endif
+    return v;
+}
+// The record of work item w's pixel (pt_pixel_list.h), where the launch has lists and a wavefront is one pixel: its head - entry count or PT_PL_WALK - and tail bound through
+// the scalar cache; the entries are fetched one by one where they are tested (pt_pl_eval). nullptr, *head = PT_PL_WALK: no list, the walk. Shared by the plain kernel and the
+// counting build of -DPT_PIXEL_LIST_STATS, so that both read the same record the same way.
+PT_HD const uint32_t* pt_pl_fetch(const PtRenderArgs& a, uint32_t n_nodes, uint32_t w, uint32_t* head, uint32_t* tail) {
+    *head = PT_PL_WALK; *tail = 0u;
+    if (!a.eye_tab || a.k_log2 + a.c_log2 != 6u) return nullptr;
+    const uint32_t* const header = (const uint32_t*)((const char*)a.eye_tab + pt_pl_header_offset(n_nodes));
+    if (pt_sload1(header) == 0u) return nullptr;
+    const uint32_t slot = (pt_fastdiv(w >> 6, a.div_groups) << 6) | pt_tile_order_to_slot(w & 63u);  // (pt_item_lane_fast's, from the wave-uniform part alone)
+    const uint32_t* const rec = header + 16 + (size_t)slot * PT_PL_WORDS;
+    const pt_u32x2 h = pt_sload2(rec);
+    *head = h[0]; *tail = h[1];
+    return rec;
+}
+// The walk's own leaf test (same function, same range through pt_cand_end_in, same eye table) on the record's entries instead of the walk: the nearest candidate, the lowest
+// index on ties, whatever the order. The entries come in ascending bound: one whose bound lies strictly above every live lane's hit ends the list - neither it nor anything
+// behind it, the left-out tail included, can hold a hit at or in front of those. Returns true where the tail does not settle every live lane: the item takes the walk, from
+// scratch. head: not PT_PL_WALK. *tests (may be null): the leaf tests this lane ran.
+PT_HD bool pt_pl_eval(const PtSceneView& sc, const uint32_t* rec, uint32_t head, uint32_t tail, const PtRay& ray, bool live, PtHit& hit, PtCounters* cnt, const double* eye_tab,
+                      unsigned long long* tests) {
+    bool settled = false;
+    const uint32_t n = head & 255u;
+    for (uint32_t i = 0; i < n && !settled; i++) {
+        const uint32_t e = pt_sload1(rec + 2 + i);
+        if (PT_BALLOT(live && !((double)pt_pl_entry_bound(e) > hit.t)) == 0ull) settled = true;
+        else if (live) {
+            pt_test_node_uniform<false, false, true>(sc, pt_pl_entry_node(e), ray, false, hit, cnt, eye_tab);
+            if (tests) (*tests)++;
+        }
+    }
+    if (settled || tail == PT_PL_INF_BITS) return false;
+    return PT_BALLOT(live && !((double)pt_f32_of(tail) > hit.t)) != 0ull;
+}
+#endif
+
 // doubles at a wave-uniform address through the scalar cache (N = 2 or 4)
 template <int N>
 PT_HD void pt_sload_f64(const double* p, double* out) {
@@ -277,10 +337,21 @@ __global__ void __launch_bounds__(PT_BLOCK, WAVES) pt_render_simple_kernel(PtRen
         bool mine;
         PtRay ray;
         ray.o = ray.d = pt_v3(0.0, 0.0, 0.0);
+#if defined(PT_PIXEL_LIST_FORM)
+        // The pixel's candidate list (pt_pl_fetch). pl_head = PT_PL_WALK: no list, today's walk.
+        constexpr bool PIXEL_LISTS = EYE_TABLE;
+        const uint32_t* pl_rec = nullptr;
+        uint32_t pl_head = PT_PL_WALK, pl_tail = 0u;
+        if constexpr (PIXEL_LISTS) pl_rec = pt_pl_fetch(a, sc.n_nodes, w, &pl_head, &pl_tail);
+        // no leaf is reached by any ray through the pixel: background for every sample, without jitter draws, camera ray or walk
+        const bool pl_background = PIXEL_LISTS && pl_head == 0u && pl_tail == PT_PL_INF_BITS;
+#else
+        constexpr bool pl_background = false;
+#endif
         {
             PtItemLane it;
             mine = pt_item_lane_fast(a, w, lane, &it, &x, &y);
-            if (mine) {
+            if (mine && !pl_background) {
                 double jx = 0.5, jy = 0.5;
                 if (a.jitter_mode == PT_JITTER_RNG) {  // render.rs:38-39: x drawn before y
                     const uint64_t key = pt_rng_key(a.seed, (uint64_t)y * a.width + x);
@@ -298,7 +369,48 @@ __global__ void __launch_bounds__(PT_BLOCK, WAVES) pt_render_simple_kernel(PtRen
         PtHit hit;
         hit.t = INFINITY; hit.node = PT_NO_HIT; hit.sub = 0;
         PT_SEC_END(3);
+#if defined(PT_PIXEL_LIST_STATS) && defined(PT_PIXEL_LIST_FORM)
+        const unsigned long long pl_na0 = cnt.n_analytic;
+#endif
+#if defined(PT_PIXEL_LIST_FORM)
+        // the list instead of the walk (pt_pl_eval); the walk where there is no list, or where the list's tail leaves a lane open
+        bool pl_walk = true;
+        if constexpr (PIXEL_LISTS) {
+            if (!(pl_head & PT_PL_WALK)) pl_walk = pl_background ? false : pt_pl_eval(sc, pl_rec, pl_head, pl_tail, ray, live, hit, &cnt, a.eye_tab, nullptr);
+        }
+        if (pl_walk)
+#endif
         pt_trace_wave<MODE, STATS, EYE_TABLE>(a, ray, live, false, hit, stk, pt_lds, &cnt);  // (EYE_TABLE is never CHAIN: this is the depth-0 walk, the only one)
+#if defined(PT_PIXEL_LIST_STATS) && defined(PT_PIXEL_LIST_FORM)
+        // -DPT_PIXEL_LIST_STATS (profiles/pixel_list_stats.py): the counting build evaluates the pixel's list BESIDE its unchanged walk - the plain build's procedure on a
+        // hit record of its own - and counts, in 21-bit fields (fewer than 2,097,152 items: the script checks): diag[0] items with a record | of them background (empty
+        // list, infinite tail) | marked "take the walk"; diag[1] items whose list was cut at the cap (finite tail) | items that would fall back to the walk | items in
+        // which some lane's list result differs from the walk's (must be 0); diag[2] leaf tests by list and diag[3] by the primary walk, per lane; diag[4..7] the
+        // histogram of list lengths, three bins a word: 0 .. 8, 9-10, 11-13, 14.
+        // (PIXEL_LISTS is EYE_TABLE, false in a counting instantiation: this is the counting twin of the instantiations that have it - mesh-free flat_scene, no chain)
+        if constexpr (STATS && MODE == PT_MODE_FLAT_NOMESH && !CHAIN) {
+            {
+                uint32_t head0, tail;
+                const uint32_t* const rec = pt_pl_fetch(a, sc.n_nodes, w, &head0, &tail);
+                if (rec) {
+                    const uint32_t n = head0 & 255u;
+                    const bool marked = (head0 & PT_PL_WALK) != 0u;
+                    PtHit h2;
+                    h2.t = INFINITY; h2.node = PT_NO_HIT; h2.sub = 0;
+                    const bool walk2 = marked || pt_pl_eval(sc, rec, head0, tail, ray, live, h2, &cnt, a.eye_tab, &cnt.diag[2]);
+                    const bool differs = live && !walk2 && (h2.node != hit.node || (h2.node != PT_NO_HIT && (h2.sub != hit.sub || h2.t != hit.t)));
+                    const bool any_differs = PT_BALLOT(differs) != 0ull;
+                    cnt.diag[3] += cnt.n_analytic - pl_na0;
+                    if (lane == 0) {
+                        cnt.diag[0] += 1ull | ((!marked && n == 0u && tail == PT_PL_INF_BITS) ? 1ull << 21 : 0ull) | (marked ? 1ull << 42 : 0ull);
+                        cnt.diag[1] += ((!marked && tail != PT_PL_INF_BITS) ? 1ull : 0ull) | ((walk2 && !marked) ? 1ull << 21 : 0ull) | (any_differs ? 1ull << 42 : 0ull);
+                        const uint32_t bin = marked ? 11u : (n <= 8u ? n : (n <= 10u ? 9u : (n <= 13u ? 10u : 11u)));
+                        if (!marked) cnt.diag[4 + bin / 3u] += 1ull << (21u * (bin % 3u));
+                    }
+                }
+            }
+        }
+#endif
         PT_SEC_SKIP();
 
         // ---- ray.rs:139-148: the background where nothing was hit, else Material::hit_color (material.rs:91-243)

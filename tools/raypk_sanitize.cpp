@@ -40,5 +40,31 @@ int main() {
     if (pt_test_raypk(1, 3, o.data(), d.data(), tm.data(), lo.data(), hi.data(), verdict.data(), tn.data(), tf.data()) == 0) { std::printf("body 3 was not refused\n"); return 1; }
     if (pt_test_raypk(0, 0, o.data(), d.data(), tm.data(), lo.data(), hi.data(), verdict.data(), tn.data(), tf.data()) != 0) { std::printf("n = 0 failed\n"); return 1; }
     std::printf("raypk_sanitize ok: %llu pairs x 3 bodies, %llu accepted\n", (unsigned long long)n, (unsigned long long)accepted);
+
+    // The pixel lists' beam test (pt_test_pixel_beam) on the same boxes: cameras at random and degenerate ones (zero and non-finite fields, a zero-sized image),
+    // pixels inside and far outside the image, jitters at the ends of [0, 1).
+    std::vector<double> cams(19 * n), jit(2 * n), rays(6 * n);
+    std::vector<uint32_t> pix(2 * n);
+    std::vector<int32_t> accept(n), walk(n);
+    std::vector<float> bound(n);
+    const double odd[] = {0.0, -0.0, 1e-310, 1e300, -1e300, std::numeric_limits<double>::infinity(), std::numeric_limits<double>::quiet_NaN()};
+    for (uint64_t i = 0; i < n; i++) {
+        double* c = &cams[19 * i];
+        for (int k = 0; k < 15; k++) c[k] = u(rng) * (k < 3 ? std::pow(10.0, e(rng)) : 1.0);
+        for (int k = 0; k < 3; k++) c[3 + 4 * k + 3] = c[k];
+        c[15] = 0.05 + std::fabs(u(rng)) * 2.0; c[17] = (double)(1 + rng() % 2000); c[18] = (double)(1 + rng() % 1200); c[16] = c[17] / c[18];
+        if (rng() % 9 == 0) c[rng() % 19] = odd[rng() % 7];
+        pix[2 * i] = (rng() % 13 == 0) ? (uint32_t)rng() : (uint32_t)(rng() % 2000);
+        pix[2 * i + 1] = (rng() % 13 == 0) ? (uint32_t)rng() : (uint32_t)(rng() % 1200);
+        for (int k = 0; k < 2; k++) jit[2 * i + k] = (rng() % 5 == 0) ? 0.0 : ((rng() % 5 == 0) ? 1.0 - 0x1p-53 : 0.5 + 0.5 * u(rng) * (1.0 - 0x1p-53));
+    }
+    int rc = pt_test_pixel_beam(n, cams.data(), pix.data(), jit.data(), lo.data(), hi.data(), accept.data(), bound.data(), walk.data(), rays.data());
+    if (rc != 0) { std::printf("pt_test_pixel_beam returned %d\n", rc); return 1; }
+    uint64_t listed = 0, walked = 0;
+    for (uint64_t i = 0; i < n; i++) { listed += (uint64_t)accept[i]; walked += walk[i] != 0; if (accept[i] && !(bound[i] >= 0.0f)) { std::printf("case %llu: a bound that is no number\n", (unsigned long long)i); return 1; } }
+    if (pt_test_pixel_beam(n, cams.data(), pix.data(), jit.data(), lo.data(), hi.data(), accept.data(), bound.data(), walk.data(), nullptr) != 0) { std::printf("rays = NULL failed\n"); return 1; }
+    if (pt_test_pixel_beam(1, nullptr, pix.data(), jit.data(), lo.data(), hi.data(), accept.data(), bound.data(), walk.data(), nullptr) == 0) { std::printf("cameras = NULL was not refused\n"); return 1; }
+    if (pt_test_pixel_beam(0, cams.data(), pix.data(), jit.data(), lo.data(), hi.data(), accept.data(), bound.data(), walk.data(), nullptr) != 0) { std::printf("n = 0 failed\n"); return 1; }
+    std::printf("pixel beam ok: %llu cases, %llu listed, %llu accepted by the walk\n", (unsigned long long)n, (unsigned long long)listed, (unsigned long long)walked);
     return 0;
 }
