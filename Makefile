@@ -32,12 +32,13 @@ HIPLIB ?= portrayer_amd/libportrayer_hip.so
 RENDER_MODES := 1 2 3 4 5 6 7 8 9
 HIP_OBJS := $(OBJDIR)/pt_api.o $(OBJDIR)/pt_build.o $(OBJDIR)/pt_node.o $(foreach m,$(RENDER_MODES),$(OBJDIR)/pt_render_m$(m).o) \
             $(foreach m,$(RENDER_MODES),$(OBJDIR)/pt_aov_m$(m).o) \
+            $(foreach m,$(RENDER_MODES),$(OBJDIR)/pt_guides_m$(m).o) \
             $(OBJDIR)/pt_rays_sort.o $(foreach m,$(RENDER_MODES),$(OBJDIR)/pt_rays_m$(m).o) \
             $(foreach m,$(RENDER_MODES),$(OBJDIR)/pt_radiance_m$(m).o) \
             $(foreach m,$(RENDER_MODES),$(OBJDIR)/pt_segments_m$(m).o) \
             $(OBJDIR)/pt_film.o $(foreach m,$(RENDER_MODES),$(OBJDIR)/pt_film_m$(m).o) \
             $(OBJDIR)/pt_film_map.o $(foreach m,$(RENDER_MODES),$(OBJDIR)/pt_film_map_m$(m).o) \
-            $(OBJDIR)/pt_denoise.o
+            $(OBJDIR)/pt_denoise.o $(OBJDIR)/pt_denoise_albedo.o
 
 # Every HIP translation unit is built in four steps instead of one `hipcc -c`, so that the device code can be CHECKED and REPAIRED between
 # the compiler and the assembler (tools/check_exec_prologue.py; profiles/r05/notes.md section 1: the AMDGPU backend of this toolchain can put
@@ -66,13 +67,14 @@ $(OBJDIR)/%.o: $(CSRC)/%.hip $(HIP_HDRS) tools/check_exec_prologue.py
 # The kernels instantiated per traversal mode - one source, nine objects per pass: pt_<pass>_m<mode>.o from pt_<pass>_inst.hip with -DPT_INST_MODE=<mode>.
 #   render    the render kernel (pt_render_kernel.h)
 #   aov       the primary-visibility pass (pt_aov.h)
+#   guides    the guides pass (pt_guides.h): the primary-visibility pass with the albedo, <TEX> instantiations per mode
 #   rays      the ray-query pass (pt_rays.h); its keying + sort step (pt_rays_sort.hip) is built by the %.o rule
 #   segments  the bounded-segment ray queries (pt_segments.h): pt_rays_kernel with a t_max per ray, and the one unit whose walks start at that bound (PT_WALK_ENTRY_T)
 #   radiance  the radiance pass (pt_radiance.h): the interpreter over the caller's rays, <TEX, PARK> instantiations per mode
 #   film      the film's sampling kernel (pt_film.h): the same interpreter with the camera as its source; its fold and resolve kernels (pt_film.hip): the %.o rule
 #   film_map  the film's per-pixel budget (pt_film_map.h): the sampling kernel over a list of samples; its plan, fold, error and budget kernels (pt_film_map.hip): the %.o rule
 # Static pattern rules, each over its own nine objects: as a plain pattern, pt_film_m%.o would match pt_film_map.o and pt_film_map_m1.o too.
-PASSES := render aov rays segments radiance film film_map
+PASSES := render aov guides rays segments radiance film film_map
 define mode_rule
 $(foreach m,$(RENDER_MODES),$(OBJDIR)/pt_$(1)_m$(m).o): $(OBJDIR)/pt_$(1)_m%.o: $(CSRC)/pt_$(1)_inst.hip $(HIP_HDRS) tools/check_exec_prologue.py
 	$$(call hip_four_steps,-DPT_INST_MODE=$$*)

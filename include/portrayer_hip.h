@@ -345,6 +345,24 @@ int pt_aov(pt_context *ctx, const pt_camera *camera, const pt_aov_params *params
 int pt_aov_device(pt_context *ctx, const pt_camera *camera, const pt_aov_params *params, const pt_aov_buffers *device_out, void *hip_stream);
 int pt_aov_finish(pt_context *ctx, double *kernel_ms);
 
+/* ---- Guides: what a denoiser needs of each pixel, in ONE trace. The pass is pt_aov's - the same pt_aov_params, the same primary ray at
+ * (x + offset[0], y + offset[1]), the same nearest hit over [EPSILON, inf), no shading, no lights, no secondary rays, no random numbers - with the diffuse
+ * colour under the pixel beside three of pt_aov's buffers. Every buffer is OPTIONAL (NULL = not wanted), a full image, row-major; pixels outside the slice
+ * are left untouched.
+ *   albedo    width x height x 3  f64  diffuse_color of material.rs:137-143 at the primary hit, in the bits the render path uses: the material's diffuse,
+ *                                      or, where the material has a texture, the three srgb_lut entries of the hit's texel (fetched at uv_trans * uv).
+ *                                      It is the FIRST hit's colour, whatever the material (a mirror's or a glass's own diffuse).  miss: +0, +0, +0
+ *   position, normal, node             as in pt_aov, the same bits and miss values (normal: BEFORE a normal map)
+ * Errors: pt_aov's, with "all four buffers NULL" in place of "all six" - all before the first HIP call - and PT_ERR_TRAVERSAL as for a render.
+ * The pass runs on pt_aov's pass object and shares its work buffers: a guides pass and an aov pass exclude each other, ONE of the two in flight per
+ * context (the second is refused with PT_ERR_ARGUMENT), and pt_guides_finish and pt_aov_finish are the same function - either closes whichever is open. */
+typedef struct { double *albedo; double *position; double *normal; int32_t *node; } pt_guides_buffers;
+/* Host buffers, synchronous; only the slice's rectangle is copied back. kernel_ms (optional): device time of the kernel (HIP events). */
+int pt_guides(pt_context *ctx, const pt_camera *camera, const pt_aov_params *params, const pt_guides_buffers *host_out, double *kernel_ms);
+/* The same into DEVICE memory, queued on `hip_stream` without synchronising the host; pt_guides_finish waits for it, as pt_aov_finish does. */
+int pt_guides_device(pt_context *ctx, const pt_camera *camera, const pt_aov_params *params, const pt_guides_buffers *device_out, void *hip_stream);
+int pt_guides_finish(pt_context *ctx, double *kernel_ms);
+
 /* ---- Ray queries: rays the CALLER supplies (the crate's public Ray / RayCast::ray_cast, ray.rs, kdmesh.rs:99-166) - picking from a point other than
  * the eye, visibility between points, ambient-occlusion and light-map baking, range sensors, cameras the crate does not have. `origins` and
  * `directions` are n x 3 f64 in world space; a direction is used as given, NOT normalised, and t is the ray parameter along it. Per ray, in the
@@ -571,6 +589,21 @@ int pt_film_denoise_device(pt_context *ctx, pt_film *film, const pt_denoise_para
 /* Host buffers, synchronous. */
 int pt_film_denoise(pt_context *ctx, pt_film *film, const pt_denoise_params *params, const pt_denoise_guides *host_guides, uint8_t *rgb, double *linear, double *variance);
 
+/* ---- The same filter on DEMODULATED colour: `albedo` (width x height x 3 f64, as pt_guides writes it) is divided out of level 0's colour and
+ * multiplied back after the last level, so that texture detail the guide knows of is not blurred. Parameters, guides, levels, bookkeeping, refusals and
+ * outputs are pt_film_denoise's; a NULL albedo is PT_ERR_ARGUMENT, and in the device form the albedo is checked like the guides. The steps, as functions of
+ * portrayer_amd/csrc/pt_denoise.h, with EPS = PT_DENOISE_ALBEDO_EPS = 0.0078125 (2^-7):
+ *   per pixel with count > 0: on a hit (node >= 0), per channel a of the albedo: m = (a >= 0.0 && a < inf) ? a + EPS : 1.0 (a NaN, negative or infinite
+ *     channel is not demodulated); on a miss m = (1, 1, 1); mm = ((m.x + m.y) + m.z) / 3.0;
+ *   after the level-0 seed: c.x = c.x / m.x, likewise y and z; v = v / (mm * mm) (the film keeps ONE variance, that of the channel sum: exact for grey
+ *     albedos, an approximation otherwise);
+ *   the levels of pt_film_denoise, unchanged;
+ *   after the last level: c.x = c.x * m.x, likewise y and z; v = v * (mm * mm), with the pixel's own m; then linear, variance and rgb as above. */
+int pt_film_denoise_albedo_device(pt_context *ctx, pt_film *film, const pt_denoise_params *params, const pt_denoise_guides *d_guides, const double *d_albedo, void *d_rgb, double *d_linear,
+                                  double *d_variance, void *hip_stream);
+int pt_film_denoise_albedo(pt_context *ctx, pt_film *film, const pt_denoise_params *params, const pt_denoise_guides *host_guides, const double *albedo, uint8_t *rgb, double *linear,
+                           double *variance);
+
 /* Bytes of one rank's compact tile buffer for a slice split over tile_ranks ranks (equal for all ranks). */
 uint64_t pt_compact_bytes(const pt_render_params *params);
 /* Scatters the gathered compact buffers (rank-major) into a row-major image on the device. */
@@ -702,6 +735,9 @@ int pt_test_film_plan(pt_context *ctx, uint32_t width, uint32_t height, const pt
  * out_variance are each optional (not both NULL); pixels with count == 0 are left untouched. */
 int pt_test_denoise_host(uint32_t width, uint32_t height, const pt_denoise_params *params, const double *linear, const double *variance, const uint32_t *counts,
                          const pt_denoise_guides *guides, double *out_linear, double *out_variance);
+/* The same for pt_film_denoise_albedo: the division after the level-0 input, pt_test_denoise_host's levels, the products after the last level. */
+int pt_test_denoise_albedo_host(uint32_t width, uint32_t height, const pt_denoise_params *params, const double *linear, const double *variance, const uint32_t *counts,
+                                const pt_denoise_guides *guides, const double *albedo, double *out_linear, double *out_variance);
 
 #ifdef __cplusplus
 }

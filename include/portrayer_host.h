@@ -114,6 +114,10 @@ int ph_renderer_render(ph_renderer *r, const double camera[10], const pt_render_
  * order the flattened nodes first use them: the numbering of ph_scene_flatten's `material` array, NOT that of ph_scene_export's `materials`. */
 int ph_renderer_aov(ph_renderer *r, const double camera[10], const pt_aov_params *params, const pt_aov_buffers *out, double *kernel_ms);
 
+/* What a denoiser needs of each pixel (see pt_guides): the same pass with the diffuse colour under the pixel (`albedo`) beside position, normal and node,
+ * in one trace; host buffers out, each optional. The camera, the slice and `node` are ph_renderer_aov's. */
+int ph_renderer_guides(ph_renderer *r, const double camera[10], const pt_aov_params *params, const pt_guides_buffers *out, double *kernel_ms);
+
 /* Rays of the caller's own (see pt_rays): n x 3 f64 origins and directions in world space, host buffers out, each optional; any_hit = 1 answers `occluded`
  * only. A renderer spread over a node runs the pass on rank 0's context. `node` and `material` are numbered as for ph_renderer_aov. */
 int ph_renderer_rays(ph_renderer *r, const pt_rays_params *params, const double *origins, const double *directions, const pt_rays_buffers *out, double *kernel_ms);
@@ -187,6 +191,11 @@ int ph_renderer_film_refine(ph_renderer *r, ph_film *film, const double camera[1
  * rgb (width x height x 3 u8), linear (x 3 f64) and variance (f64) are each optional, not all NULL; pixels without samples keep what they hold. */
 int ph_renderer_film_denoise(ph_renderer *r, ph_film *film, const double camera[10], const pt_denoise_params *params, const pt_denoise_guides *guides, uint8_t *rgb, double *linear,
                              double *variance);
+/* The same on demodulated colour (pt_film_denoise_albedo). With `guides` AND `albedo` (host arrays as pt_guides writes them; one without the other is refused)
+ * it is the library's host path. With both NULL, ONE guides pass for `camera` writes albedo, guides and node into device buffers kept with the film handle,
+ * then pt_film_denoise_albedo_device; only the outputs asked for are copied out. */
+int ph_renderer_film_denoise_albedo(ph_renderer *r, ph_film *film, const double camera[10], const pt_denoise_params *params, const pt_denoise_guides *guides, const double *albedo,
+                                    uint8_t *rgb, double *linear, double *variance);
 
 /* Image::new + Image::render + Image::save with the crate's defaults (env SAMPLES, KD_DEPTH) on an
  * example scene: exercises the whole C++ API the way the reference's main() does. */

@@ -88,6 +88,15 @@ class PtAovBuffers(C.Structure):
 AOV_BUFFERS = {"depth": (np.float64, 1), "position": (np.float64, 3), "normal": (np.float64, 3), "node": (np.int32, 1), "sub": (np.int32, 1), "material": (np.int32, 1)}
 
 
+class PtGuidesBuffers(C.Structure):
+    """pt_guides_buffers: the guides pass's outputs - albedo, position and normal (H, W, 3) f64, node (H, W) i32; each optional."""
+    _fields_ = [("albedo", _dp), ("position", _dp), ("normal", _dp), ("node", _ip)]
+
+
+# pt_guides' outputs in the order of pt_guides_buffers: name -> (numpy dtype, components per pixel)
+GUIDES_BUFFERS = {"albedo": (np.float64, 3), "position": (np.float64, 3), "normal": (np.float64, 3), "node": (np.int32, 1)}
+
+
 class PtSceneMotion(C.Structure):
     """pt_scene_motion: the resident scene's new node matrices (graph matrices in PT_TRAVERSE_HIER), lights and ambient light for pt_scene_update."""
     _fields_ = [("n_nodes", C.c_uint32), ("trans", _dp), ("invtrans", _dp), ("normal_trans", _dp),
@@ -142,6 +151,7 @@ class PtFilmRefineParams(C.Structure):
 
 
 DENOISE_SAME_NODE = 1  # PT_DENOISE_SAME_NODE
+DENOISE_ALBEDO_EPS = 0.0078125  # PT_DENOISE_ALBEDO_EPS
 
 
 class PtDenoiseParams(C.Structure):
@@ -180,7 +190,8 @@ EXPORTS = ["pt_abi_version", "pt_device_count", "pt_context_create", "pt_context
            "pt_test_film_fold_host",
            "pt_film_create_moments", "pt_film_add_map", "pt_film_add_map_device", "pt_film_error", "pt_film_error_device", "pt_film_budget_device",
            "pt_test_film_moments_host", "pt_test_film_plan_host", "pt_test_film_plan",
-           "pt_film_denoise", "pt_film_denoise_device", "pt_test_denoise_host"]
+           "pt_film_denoise", "pt_film_denoise_device", "pt_test_denoise_host",
+           "pt_guides", "pt_guides_device", "pt_guides_finish", "pt_film_denoise_albedo", "pt_film_denoise_albedo_device", "pt_test_denoise_albedo_host"]
 
 
 def header_functions():
@@ -321,6 +332,12 @@ def lib() -> C.CDLL:
         l.pt_aov_device.argtypes = [C.c_void_p, C.POINTER(PtCamera), C.POINTER(PtAovParams), C.POINTER(PtAovBuffers), C.c_void_p]
         l.pt_aov_finish.restype = C.c_int
         l.pt_aov_finish.argtypes = [C.c_void_p, _dp]
+        l.pt_guides.restype = C.c_int
+        l.pt_guides.argtypes = [C.c_void_p, C.POINTER(PtCamera), C.POINTER(PtAovParams), C.POINTER(PtGuidesBuffers), _dp]
+        l.pt_guides_device.restype = C.c_int
+        l.pt_guides_device.argtypes = [C.c_void_p, C.POINTER(PtCamera), C.POINTER(PtAovParams), C.POINTER(PtGuidesBuffers), C.c_void_p]
+        l.pt_guides_finish.restype = C.c_int
+        l.pt_guides_finish.argtypes = [C.c_void_p, _dp]
         l.pt_rays.restype = C.c_int
         l.pt_rays.argtypes = [C.c_void_p, C.POINTER(PtRaysParams), _dp, _dp, C.POINTER(PtRaysBuffers), _dp]
         l.pt_rays_device.restype = C.c_int
@@ -377,6 +394,12 @@ def lib() -> C.CDLL:
         l.pt_film_denoise_device.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(PtDenoiseParams), C.POINTER(PtDenoiseGuides), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         l.pt_test_denoise_host.restype = C.c_int
         l.pt_test_denoise_host.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(PtDenoiseParams), _dp, _dp, _u32p, C.POINTER(PtDenoiseGuides), _dp, _dp]
+        l.pt_film_denoise_albedo.restype = C.c_int
+        l.pt_film_denoise_albedo.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(PtDenoiseParams), C.POINTER(PtDenoiseGuides), _dp, _u8p, _dp, _dp]
+        l.pt_film_denoise_albedo_device.restype = C.c_int
+        l.pt_film_denoise_albedo_device.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(PtDenoiseParams), C.POINTER(PtDenoiseGuides), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        l.pt_test_denoise_albedo_host.restype = C.c_int
+        l.pt_test_denoise_albedo_host.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(PtDenoiseParams), _dp, _dp, _u32p, C.POINTER(PtDenoiseGuides), _dp, _dp, _dp]
         l.pt_test_film_plan.restype = C.c_int
         l.pt_test_film_plan.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(PtRect), _u32p, C.c_uint32, C.c_uint32, _u32p, C.c_uint32, _u32p]
         _lib = l

@@ -16,6 +16,7 @@
 #include "pt_build.h"
 #include "pt_bvh.h"
 #include "pt_aov_inst.h"
+#include "pt_guides_inst.h"
 #include "pt_rays_inst.h"
 #include "pt_segments_inst.h"
 #include "pt_radiance_inst.h"
@@ -405,9 +406,13 @@ struct pt_context {
     size_t pl_off = 0;         // ... and where its records start in the buffer
     // The three passes beside the render, each with a PtPass of its own: all three may be in flight at once, with two renders. Beside it, what is the kind's.
     // The primary-visibility pass (pt_aov / pt_aov_device ... pt_aov_finish): the device copies of the host-buffer path's six outputs.
+    // The guides pass (pt_guides ...) runs on the SAME pass - one of the two in flight, one set of stack columns - and its host-buffer path takes position, normal and
+    // node from out[1 .. 3] and the albedo from a buffer of its own.
     struct Aov {
         PtPass pass;
         PtBuf out[6];
+        PtBuf albedo;
+        bool guides = false;  // the pass in flight (pass.pending) is a pt_guides_device one: which words a refusal uses
     } aov;
     // The ray-query pass (pt_rays / pt_segments, their _device forms ... pt_rays_finish): the device copies of the host-buffer path's inputs (in_t_max: pt_segments'
     // third) and seven outputs.
@@ -483,7 +488,7 @@ struct pt_film {
     PtBuf q, budget, list, plan_work, out_err;
     // pt_film_denoise: the two work buffers of its levels (32 bytes per pixel each, allocated by the first denoise); the host path's device copies of the
     // guides and of the variance it returns.
-    PtBuf dn_work[2], dn_position, dn_normal, dn_node, out_var;
+    PtBuf dn_work[2], dn_position, dn_normal, dn_node, dn_albedo, out_var;  // (dn_albedo: pt_film_denoise_albedo's guide)
     bool moments = false;
     std::vector<uint32_t> counts;
 };
@@ -2525,6 +2530,11 @@ static hipError_t pt_aov_dispatch(const PtAovArgs& a, int n_cu, hipStream_t stre
     PT_MODE_LAUNCH(pt_aov_launch_mode_, a.r.scene.mode, a, n_cu, stream, grid, launch)
 }
 
+// What refuses a second pass on the pass object pt_aov and pt_guides share: the open one's kind and the call that closes it.
+static const char* pt_aov_open_words(const pt_context* c) {
+    return c->aov.guides ? "a pt_guides_device pass is in flight: pt_guides_finish first" : "a pt_aov_device pass is in flight: pt_aov_finish first";
+}
+
 // Everything that can be refused without a HIP call, in the order the header gives.
 static int pt_aov_check(pt_context* c, const pt_camera* cam, const pt_aov_params* p, const pt_aov_buffers* out) {
     if (!c || !cam || !p) return PT_ERR_ARGUMENT;
@@ -2535,7 +2545,7 @@ static int pt_aov_check(pt_context* c, const pt_camera* cam, const pt_aov_params
     if (p->width == 0 || p->height == 0) return pt_fail(c, PT_ERR_ARGUMENT, "width and height must be positive");
     if (p->slice.x0 >= p->width || p->slice.x1 >= p->width || p->slice.y0 >= p->height || p->slice.y1 >= p->height)
         return pt_fail(c, PT_ERR_SLICE, "slice corner outside the image (render.rs:79-90)");
-    if (c->aov.pass.pending) return pt_fail(c, PT_ERR_ARGUMENT, "a pt_aov_device pass is in flight: pt_aov_finish first");
+    if (c->aov.pass.pending) return pt_fail(c, PT_ERR_ARGUMENT, pt_aov_open_words(c));
     return PT_OK;
 }
 
@@ -2595,13 +2605,96 @@ extern "C" int pt_aov_device(pt_context* c, const pt_camera* cam, const pt_aov_p
     int rc = pt_aov_check(c, cam, p, device_out);
     if (rc) return rc;
     PT_HIP(c, hipSetDevice(c->device));
+    c->aov.guides = false;
     return pt_pass_device_tail(c, c->aov.pass, pt_aov_common(c, cam, p, *device_out, (hipStream_t)hip_stream));
 }
 
 extern "C" int pt_aov_finish(pt_context* c, double* kernel_ms) {
     if (!c) return PT_ERR_ARGUMENT;
-    return pt_pass_finish(c, c->aov.pass, "no pt_aov_device pass in flight", kernel_ms);
+    return pt_pass_finish(c, c->aov.pass, "no pt_aov_device pass in flight", kernel_ms);  // (also what pt_guides_finish says: the same function)
 }
+
+// ------------------------------------------------------------------------------------------------
+// Guides (pt_guides.h): the primary-visibility pass with the albedo, on that pass's PtPass
+// ------------------------------------------------------------------------------------------------
+static hipError_t pt_guides_dispatch(const PtGuidesArgs& a, bool tex, int n_cu, hipStream_t stream, uint32_t* grid, bool launch) {
+    PT_MODE_LAUNCH(pt_guides_launch_mode_, a.r.scene.mode, a, tex, n_cu, stream, grid, launch)
+}
+
+// Everything that can be refused without a HIP call: pt_aov_check's list, in its order.
+static int pt_guides_check(pt_context* c, const pt_camera* cam, const pt_aov_params* p, const pt_guides_buffers* out) {
+    if (!c || !cam || !p) return PT_ERR_ARGUMENT;
+    if (!out || !(out->albedo || out->position || out->normal || out->node)) return pt_fail(c, PT_ERR_ARGUMENT, "pt_guides: no output buffer asked for");
+    if (!std::isfinite(p->offset[0]) || !std::isfinite(p->offset[1])) return pt_fail(c, PT_ERR_ARGUMENT, "pt_guides: offset must be finite");
+    if (!c->have_scene) return pt_fail(c, PT_ERR_NO_SCENE, "no scene uploaded");
+    if (p->width == 0 || p->height == 0) return pt_fail(c, PT_ERR_ARGUMENT, "width and height must be positive");
+    if (p->slice.x0 >= p->width || p->slice.x1 >= p->width || p->slice.y0 >= p->height || p->slice.y1 >= p->height)
+        return pt_fail(c, PT_ERR_SLICE, "slice corner outside the image (render.rs:79-90)");
+    if (c->aov.pass.pending) return pt_fail(c, PT_ERR_ARGUMENT, pt_aov_open_words(c));
+    return PT_OK;
+}
+
+// Queues the pass on `stream`, as pt_aov_common does and on its PtPass. `out` holds DEVICE pointers. A scene with material maps launches the TEX instantiation.
+static int pt_guides_common(pt_context* c, const pt_camera* cam, const pt_aov_params* p, const pt_guides_buffers& out, hipStream_t stream) {
+    PtPass& v = c->aov.pass;
+    int rc = pt_pass_prepare(c, v);
+    if (rc) return rc;
+    pt_render_params rp;
+    memset(&rp, 0, sizeof rp);
+    rp.width = p->width; rp.height = p->height; rp.slice = p->slice;
+    rp.samples = 1; rp.sample_mode = PT_SAMPLE_CENTRE; rp.tile_rank = 0; rp.tile_ranks = 1;
+    PtGuidesArgs a;
+    pt_fill_args(c, cam, &rp, &a.r);  // samples = 1: one work item per 8x8 tile of the slice
+    a.off_x = p->offset[0]; a.off_y = p->offset[1];
+    a.albedo = out.albedo; a.position = out.position; a.normal = out.normal; a.node = out.node;
+    pt_walk_sizing(a.r, pt_aov_waves(a.r.scene.mode));
+    const bool tex = a.r.scene.mat_maps != nullptr;
+    uint32_t grid = 0;
+    PT_HIP(c, pt_guides_dispatch(a, tex, c->n_cu, stream, &grid, false));
+    if ((rc = pt_pass_open(c, v, a.r, grid, false, stream))) return rc;
+    if (a.r.n_items) PT_HIP(c, pt_guides_dispatch(a, tex, c->n_cu, stream, &grid, true));
+    return pt_pass_seal(c, v);
+}
+
+extern "C" int pt_guides(pt_context* c, const pt_camera* cam, const pt_aov_params* p, const pt_guides_buffers* host_out, double* kernel_ms) {
+    int rc = pt_guides_check(c, cam, p, host_out);
+    if (rc) return rc;
+    PT_HIP(c, hipSetDevice(c->device));
+    const size_t px = (size_t)p->width * p->height;
+    void* host[4] = {host_out->albedo, host_out->position, host_out->normal, host_out->node};
+    PtBuf* buf[4] = {&c->aov.albedo, &c->aov.out[1], &c->aov.out[2], &c->aov.out[3]};
+    const size_t elem[4] = {24, 24, 24, 4};  // bytes per pixel
+    void* dev[4] = {nullptr, nullptr, nullptr, nullptr};
+    for (int k = 0; k < 4; k++) {
+        if (!host[k]) continue;
+        if ((rc = pt_reserve(c, *buf[k], px * elem[k]))) return rc;
+        dev[k] = buf[k]->p;
+    }
+    pt_guides_buffers d_out;
+    d_out.albedo = (double*)dev[0]; d_out.position = (double*)dev[1]; d_out.normal = (double*)dev[2]; d_out.node = (int32_t*)dev[3];
+    if ((rc = pt_pass_settle(c, c->aov.pass, pt_guides_common(c, cam, p, d_out, nullptr)))) return rc;
+    // only the slice's rectangle comes back, as in pt_aov: pixels outside it keep the caller's bytes
+    if (p->slice.x1 >= p->slice.x0 && p->slice.y1 >= p->slice.y0) {
+        const size_t cols = (size_t)p->slice.x1 - p->slice.x0 + 1, rows = (size_t)p->slice.y1 - p->slice.y0 + 1;
+        for (int k = 0; k < 4; k++) {
+            if (!host[k]) continue;
+            const size_t pitch = (size_t)p->width * elem[k], first = ((size_t)p->slice.y0 * p->width + p->slice.x0) * elem[k];
+            PT_HIP(c, hipMemcpy2D((char*)host[k] + first, pitch, (const char*)dev[k] + first, pitch, cols * elem[k], rows, hipMemcpyDeviceToHost));
+        }
+    }
+    return pt_pass_result(c, c->aov.pass, kernel_ms);
+}
+
+extern "C" int pt_guides_device(pt_context* c, const pt_camera* cam, const pt_aov_params* p, const pt_guides_buffers* device_out, void* hip_stream) {
+    int rc = pt_guides_check(c, cam, p, device_out);
+    if (rc) return rc;
+    PT_HIP(c, hipSetDevice(c->device));
+    c->aov.guides = true;
+    return pt_pass_device_tail(c, c->aov.pass, pt_guides_common(c, cam, p, *device_out, (hipStream_t)hip_stream));
+}
+
+// The pass is pt_aov's: one function closes either.
+extern "C" int pt_guides_finish(pt_context* c, double* kernel_ms) { return pt_aov_finish(c, kernel_ms); }
 
 // ------------------------------------------------------------------------------------------------
 // Ray queries (pt_rays.h)
@@ -3205,14 +3298,18 @@ static int pt_film_denoise_check(pt_context* c, pt_film* f, const pt_denoise_par
 }
 
 // The kernels of one denoise, queued on `stream`: seed, a level kernel per iteration between the film's two work buffers, finish. The context's device is current.
-static int pt_film_denoise_queue(pt_context* c, pt_film* f, const pt_denoise_params* p, const pt_denoise_guides& g, uint8_t* d_rgb, double* d_linear, double* d_variance, hipStream_t stream) {
+// With an albedo (pt_film_denoise_albedo*) the seed and the finish are pt_denoise_albedo.hip's, the levels the same.
+static int pt_film_denoise_queue(pt_context* c, pt_film* f, const pt_denoise_params* p, const pt_denoise_guides& g, const double* d_albedo, uint8_t* d_rgb, double* d_linear, double* d_variance,
+                                 hipStream_t stream) {
     const size_t n = f->counts.size();
     int rc;
     if ((rc = pt_reserve(c, f->dn_work[0], n * 32)) || (rc = pt_reserve(c, f->dn_work[1], n * 32))) return rc;
     bool tiled = true;  // the LDS-tiled form, the faster one at 5 levels by more than three spreads (profiles/denoise/notes.md), unless the switch says otherwise
     if (const char* e = getenv("PORTRAYER_DENOISE_TILE")) tiled = atoi(e) > 0;
     const uint32_t* count = (const uint32_t*)f->count.p;
-    PT_HIP(c, pt_denoise_seed_launch(f->width, f->height, (const double*)f->total.p, (const double*)f->partial.p, count, f->moments ? (const double*)f->q.p : nullptr, (double*)f->dn_work[0].p, stream));
+    const double* q = f->moments ? (const double*)f->q.p : nullptr;
+    if (d_albedo) PT_HIP(c, pt_denoise_albedo_seed_launch(f->width, f->height, (const double*)f->total.p, (const double*)f->partial.p, count, q, g.node, d_albedo, (double*)f->dn_work[0].p, stream));
+    else PT_HIP(c, pt_denoise_seed_launch(f->width, f->height, (const double*)f->total.p, (const double*)f->partial.p, count, q, (double*)f->dn_work[0].p, stream));
     PtDenoiseLevelArgs a;
     a.k = pt_denoise_const(*p);
     a.width = f->width; a.height = f->height;
@@ -3225,30 +3322,47 @@ static int pt_film_denoise_queue(pt_context* c, pt_film* f, const pt_denoise_par
         a.out = (double*)f->dn_work[cur ^ 1].p;
         PT_HIP(c, pt_denoise_level_launch(a, tiled, stream));
     }
-    PT_HIP(c, pt_denoise_finish_launch(f->width, f->height, (const double*)f->dn_work[cur].p, count, d_rgb, d_linear, d_variance, stream));
+    if (d_albedo) PT_HIP(c, pt_denoise_albedo_finish_launch(f->width, f->height, (const double*)f->dn_work[cur].p, count, g.node, d_albedo, d_rgb, d_linear, d_variance, stream));
+    else PT_HIP(c, pt_denoise_finish_launch(f->width, f->height, (const double*)f->dn_work[cur].p, count, d_rgb, d_linear, d_variance, stream));
     return PT_OK;
 }
 
-extern "C" int pt_film_denoise_device(pt_context* c, pt_film* f, const pt_denoise_params* p, const pt_denoise_guides* d_guides, void* d_rgb, double* d_linear, double* d_variance,
-                                      void* hip_stream) {
-    int rc = pt_film_denoise_check(c, f, p, d_guides, d_rgb, d_linear, d_variance, "pt_film_denoise_device");
+// The device form of both denoises: `who` names the entry point, `albedo` says whether it is the demodulated one (d_albedo is then required).
+static int pt_film_denoise_device_any(pt_context* c, pt_film* f, const pt_denoise_params* p, const pt_denoise_guides* d_guides, bool albedo, const double* d_albedo, void* d_rgb, double* d_linear,
+                                      double* d_variance, void* hip_stream, const std::string& who) {
+    int rc = pt_film_denoise_check(c, f, p, d_guides, d_rgb, d_linear, d_variance, who.c_str());
     if (rc) return rc;
+    if (albedo && !d_albedo) return pt_fail(c, PT_ERR_ARGUMENT, who + ": NULL albedo");
     PT_HIP(c, hipSetDevice(c->device));
     const uint64_t n = f->counts.size();
     const bool want_n = p->normal_power_log2 >= 0 || p->sigma_plane > 0.0, want_pos = p->sigma_plane > 0.0;
     pt_denoise_guides g = {want_pos ? d_guides->position : nullptr, want_n ? d_guides->normal : nullptr, d_guides->node};  // (a guide no weight reads is not looked at)
-    if ((rc = pt_check_device_pointer(c, g.node, n * 4, "pt_film_denoise_device: the node guide"))) return rc;
-    if (g.normal && (rc = pt_check_device_pointer(c, g.normal, n * 24, "pt_film_denoise_device: the normal guide"))) return rc;
-    if (g.position && (rc = pt_check_device_pointer(c, g.position, n * 24, "pt_film_denoise_device: the position guide"))) return rc;
-    if (d_rgb && (rc = pt_check_device_pointer(c, d_rgb, n * 3, "pt_film_denoise_device: rgb"))) return rc;
-    if (d_linear && (rc = pt_check_device_pointer(c, d_linear, n * 24, "pt_film_denoise_device: linear"))) return rc;
-    if (d_variance && (rc = pt_check_device_pointer(c, d_variance, n * 8, "pt_film_denoise_device: variance"))) return rc;
-    return pt_film_denoise_queue(c, f, p, g, (uint8_t*)d_rgb, d_linear, d_variance, (hipStream_t)hip_stream);
+    if ((rc = pt_check_device_pointer(c, g.node, n * 4, who + ": the node guide"))) return rc;
+    if (g.normal && (rc = pt_check_device_pointer(c, g.normal, n * 24, who + ": the normal guide"))) return rc;
+    if (g.position && (rc = pt_check_device_pointer(c, g.position, n * 24, who + ": the position guide"))) return rc;
+    if (d_rgb && (rc = pt_check_device_pointer(c, d_rgb, n * 3, who + ": rgb"))) return rc;
+    if (d_linear && (rc = pt_check_device_pointer(c, d_linear, n * 24, who + ": linear"))) return rc;
+    if (d_variance && (rc = pt_check_device_pointer(c, d_variance, n * 8, who + ": variance"))) return rc;
+    if (albedo && (rc = pt_check_device_pointer(c, d_albedo, n * 24, who + ": the albedo"))) return rc;
+    return pt_film_denoise_queue(c, f, p, g, albedo ? d_albedo : nullptr, (uint8_t*)d_rgb, d_linear, d_variance, (hipStream_t)hip_stream);
 }
 
-extern "C" int pt_film_denoise(pt_context* c, pt_film* f, const pt_denoise_params* p, const pt_denoise_guides* host_guides, uint8_t* rgb, double* linear, double* variance) {
-    int rc = pt_film_denoise_check(c, f, p, host_guides, rgb, linear, variance, "pt_film_denoise");
+extern "C" int pt_film_denoise_device(pt_context* c, pt_film* f, const pt_denoise_params* p, const pt_denoise_guides* d_guides, void* d_rgb, double* d_linear, double* d_variance,
+                                      void* hip_stream) {
+    return pt_film_denoise_device_any(c, f, p, d_guides, false, nullptr, d_rgb, d_linear, d_variance, hip_stream, "pt_film_denoise_device");
+}
+
+extern "C" int pt_film_denoise_albedo_device(pt_context* c, pt_film* f, const pt_denoise_params* p, const pt_denoise_guides* d_guides, const double* d_albedo, void* d_rgb, double* d_linear,
+                                             double* d_variance, void* hip_stream) {
+    return pt_film_denoise_device_any(c, f, p, d_guides, true, d_albedo, d_rgb, d_linear, d_variance, hip_stream, "pt_film_denoise_albedo_device");
+}
+
+// The host-buffer form of both denoises, as pt_film_denoise_device_any is the device form's.
+static int pt_film_denoise_host_any(pt_context* c, pt_film* f, const pt_denoise_params* p, const pt_denoise_guides* host_guides, bool albedo, const double* host_albedo, uint8_t* rgb, double* linear,
+                                    double* variance, const std::string& who) {
+    int rc = pt_film_denoise_check(c, f, p, host_guides, rgb, linear, variance, who.c_str());
     if (rc) return rc;
+    if (albedo && !host_albedo) return pt_fail(c, PT_ERR_ARGUMENT, who + ": NULL albedo");
     PT_HIP(c, hipSetDevice(c->device));
     const size_t n = f->counts.size();
     const bool want_n = p->normal_power_log2 >= 0 || p->sigma_plane > 0.0, want_pos = p->sigma_plane > 0.0;
@@ -3266,6 +3380,12 @@ extern "C" int pt_film_denoise(pt_context* c, pt_film* f, const pt_denoise_param
         PT_HIP(c, hipMemcpy(f->dn_position.p, host_guides->position, n * 24, hipMemcpyHostToDevice));
         g.position = (const double*)f->dn_position.p;
     }
+    const double* d_albedo = nullptr;
+    if (albedo) {
+        if ((rc = pt_reserve(c, f->dn_albedo, n * 24))) return rc;
+        PT_HIP(c, hipMemcpy(f->dn_albedo.p, host_albedo, n * 24, hipMemcpyHostToDevice));
+        d_albedo = (const double*)f->dn_albedo.p;
+    }
     // pixels without samples keep the caller's bytes: where there are any, the caller's buffers go to the device first (pt_film_resolve)
     PT_HIP(c, hipMemcpy(f->counts.data(), f->count.p, n * 4, hipMemcpyDeviceToHost));  // (behind a device map the host's copy is an upper bound)
     const bool holes = std::find(f->counts.begin(), f->counts.end(), 0u) != f->counts.end();
@@ -3281,11 +3401,20 @@ extern "C" int pt_film_denoise(pt_context* c, pt_film* f, const pt_denoise_param
         if ((rc = pt_reserve(c, f->out_var, n * 8))) return rc;
         if (holes) PT_HIP(c, hipMemcpy(f->out_var.p, variance, n * 8, hipMemcpyHostToDevice));
     }
-    if ((rc = pt_film_denoise_queue(c, f, p, g, rgb ? (uint8_t*)f->out_rgb.p : nullptr, linear ? (double*)f->out_linear.p : nullptr, variance ? (double*)f->out_var.p : nullptr, nullptr))) return rc;
+    if ((rc = pt_film_denoise_queue(c, f, p, g, d_albedo, rgb ? (uint8_t*)f->out_rgb.p : nullptr, linear ? (double*)f->out_linear.p : nullptr, variance ? (double*)f->out_var.p : nullptr, nullptr))) return rc;
     if (rgb) PT_HIP(c, hipMemcpy(rgb, f->out_rgb.p, n * 3, hipMemcpyDeviceToHost));
     if (linear) PT_HIP(c, hipMemcpy(linear, f->out_linear.p, n * 24, hipMemcpyDeviceToHost));
     if (variance) PT_HIP(c, hipMemcpy(variance, f->out_var.p, n * 8, hipMemcpyDeviceToHost));
     return PT_OK;
+}
+
+extern "C" int pt_film_denoise(pt_context* c, pt_film* f, const pt_denoise_params* p, const pt_denoise_guides* host_guides, uint8_t* rgb, double* linear, double* variance) {
+    return pt_film_denoise_host_any(c, f, p, host_guides, false, nullptr, rgb, linear, variance, "pt_film_denoise");
+}
+
+extern "C" int pt_film_denoise_albedo(pt_context* c, pt_film* f, const pt_denoise_params* p, const pt_denoise_guides* host_guides, const double* albedo, uint8_t* rgb, double* linear,
+                                      double* variance) {
+    return pt_film_denoise_host_any(c, f, p, host_guides, true, albedo, rgb, linear, variance, "pt_film_denoise_albedo");
 }
 
 // The plan kernels alone (tests): the list of one launch round, copied back.

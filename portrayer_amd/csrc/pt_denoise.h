@@ -116,6 +116,36 @@ PT_HD void pt_denoise_level_out(const PtDenoiseAcc& a, PtVec3 cp, double vp, PtV
     *v = a.vs / (a.ws * a.ws);
 }
 
+// Albedo demodulation (pt_film_denoise_albedo*): level 0's colour is divided by the diffuse colour under the pixel before the levels smooth it and
+// multiplied by it again after the last one, so that texture detail the guides know of is not blurred. The levels themselves are the ones above, unchanged.
+#define PT_DENOISE_ALBEDO_EPS 0.0078125  // 2^-7, exact: a black albedo divides by this
+
+// The modulation of one channel of a hit pixel's albedo guide: a NaN, negative or infinite channel is not demodulated (and makes no NaN).
+PT_HD double pt_denoise_modulation_of(double a) { return (a >= 0.0 && a < INFINITY) ? a + PT_DENOISE_ALBEDO_EPS : 1.0; }
+// The modulation of a pixel with count > 0: its albedo's where the node guide says hit, (1, 1, 1) on a miss.
+PT_HD PtVec3 pt_denoise_modulation(int32_t node, PtVec3 albedo) {
+    if (node < 0) return pt_v3(1.0, 1.0, 1.0);
+    return pt_v3(pt_denoise_modulation_of(albedo.x), pt_denoise_modulation_of(albedo.y), pt_denoise_modulation_of(albedo.z));
+}
+// The film keeps ONE variance, that of the channel sum: it is scaled by the square of the mean modulation - exact for grey albedos, an approximation otherwise.
+PT_HD double pt_denoise_mean_modulation(PtVec3 m) { return ((m.x + m.y) + m.z) / 3.0; }
+// After the level-0 seed ...
+PT_HD void pt_denoise_demodulate(PtVec3 m, PtVec3* c, double* v) {
+    const double mm = pt_denoise_mean_modulation(m);
+    c->x = c->x / m.x;
+    c->y = c->y / m.y;
+    c->z = c->z / m.z;
+    *v = *v / (mm * mm);
+}
+// ... and after the last level, with the pixel's own m.
+PT_HD void pt_denoise_remodulate(PtVec3 m, PtVec3* c, double* v) {
+    const double mm = pt_denoise_mean_modulation(m);
+    c->x = c->x * m.x;
+    c->y = c->y * m.y;
+    c->z = c->z * m.z;
+    *v = *v * (mm * mm);
+}
+
 // The tiled form's geometry (pt_denoise.hip): a block owns PT_DN_TILE x PT_DN_TILE pixels of one residue class modulo the step and stages a
 // (PT_DN_TILE + 4)^2 neighbourhood of it, every component as an f64 array of its own.
 #define PT_DN_TILE 16
@@ -146,3 +176,8 @@ hipError_t pt_denoise_seed_launch(uint32_t width, uint32_t height, const double*
 hipError_t pt_denoise_level_launch(const PtDenoiseLevelArgs& a, bool tiled, hipStream_t stream);
 // finish: the last level's (c, v) to the caller's buffers, each optional; rgb is resolve's finishing of c. Pixels with count == 0 are not written.
 hipError_t pt_denoise_finish_launch(uint32_t width, uint32_t height, const double* work, const uint32_t* count, uint8_t* rgb, double* linear, double* variance, hipStream_t stream);
+// pt_denoise_albedo.hip: the seed with the division by the modulation fused in, the finish with the products; node and albedo are the caller's guides.
+hipError_t pt_denoise_albedo_seed_launch(uint32_t width, uint32_t height, const double* total, const double* partial, const uint32_t* count, const double* q, const int32_t* node,
+                                         const double* albedo, double* work, hipStream_t stream);
+hipError_t pt_denoise_albedo_finish_launch(uint32_t width, uint32_t height, const double* work, const uint32_t* count, const int32_t* node, const double* albedo, uint8_t* rgb, double* linear,
+                                           double* variance, hipStream_t stream);

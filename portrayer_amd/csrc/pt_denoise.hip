@@ -10,8 +10,7 @@
 
 #include "../../include/portrayer_hip.h"
 #include "pt_denoise.h"
-#include "pt_film_map_inst.h"
-#include "pt_shade.h"
+#include "pt_denoise_pixel.h"
 
 // One thread per pixel of the image. Pixels without samples are neither centres nor taps: their record is never read, so none is written.
 __global__ void __launch_bounds__(256) pt_denoise_seed_kernel(uint32_t n_pixels, const double* __restrict__ total, const double* __restrict__ partial, const uint32_t* __restrict__ count,
@@ -146,19 +145,7 @@ __global__ void __launch_bounds__(256) pt_denoise_finish_kernel(uint32_t n_pixel
     if (p >= n_pixels) return;
     if (count[p] == 0u) return;
     const double* cv = work + 4 * (size_t)p;
-    const PtVec3 color = pt_v3(cv[0], cv[1], cv[2]);
-    if (linear) { double* o = linear + 3 * (size_t)p; o[0] = color.x; o[1] = color.y; o[2] = color.z; }
-    if (variance) variance[p] = cv[3];
-    if (!rgb) return;
-    const double g = 1.0 / PT_GAMMA;
-    double ch[3] = {pt_pow(color.x, g), pt_pow(color.y, g), pt_pow(color.z, g)};
-    uint8_t* o = rgb + 3 * (size_t)p;
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-        double v = ch[k];
-        v = v < 0.0 ? 0.0 : (v > 1.0 ? 1.0 : v);
-        o[k] = pt_to_u8(v);
-    }
+    pt_denoise_finish_pixel(p, pt_v3(cv[0], cv[1], cv[2]), cv + 3, rgb, linear, variance);
 }
 
 hipError_t pt_denoise_seed_launch(uint32_t width, uint32_t height, const double* total, const double* partial, const uint32_t* count, const double* q, double* work, hipStream_t stream) {

@@ -19,7 +19,7 @@ _dp, _ip, _up, _u64p, _u8p = H._dp, H._ip, H._up, H._u64p, H._u8p
 
 EXPORTS = ["ph_last_error", "ph_scene_create", "ph_example_scene", "ph_scene_destroy", "ph_scene_counts", "ph_scene_export", "ph_scene_export_textures",
            "ph_scene_flatten", "ph_scene_kdtree", "ph_camera", "ph_obj_load", "ph_renderer_create", "ph_renderer_destroy",
-           "ph_renderer_context", "ph_renderer_ranks", "ph_renderer_node", "ph_renderer_prepare_ms", "ph_renderer_render", "ph_renderer_aov", "ph_renderer_rays", "ph_renderer_segments", "ph_renderer_radiance", "ph_renderer_film_create", "ph_renderer_film_destroy", "ph_renderer_film_reset", "ph_renderer_film_add", "ph_renderer_film_resolve", "ph_renderer_film_counts", "ph_renderer_film_create_moments", "ph_renderer_film_add_map", "ph_renderer_film_error", "ph_renderer_film_refine", "ph_renderer_film_denoise", "ph_renderer_update", "ph_scene_same_structure", "ph_renderer_deform", "ph_scene_same_topology", "ph_renderer_deform_device", "ph_renderer_mesh_count", "ph_renderer_mesh_vertices", "ph_example_render_to_png", "ph_png_read", "ph_png_write", "ph_image_read", "ph_scene_graph"]
+           "ph_renderer_context", "ph_renderer_ranks", "ph_renderer_node", "ph_renderer_prepare_ms", "ph_renderer_render", "ph_renderer_aov", "ph_renderer_rays", "ph_renderer_segments", "ph_renderer_radiance", "ph_renderer_film_create", "ph_renderer_film_destroy", "ph_renderer_film_reset", "ph_renderer_film_add", "ph_renderer_film_resolve", "ph_renderer_film_counts", "ph_renderer_film_create_moments", "ph_renderer_film_add_map", "ph_renderer_film_error", "ph_renderer_film_refine", "ph_renderer_film_denoise", "ph_renderer_guides", "ph_renderer_film_denoise_albedo", "ph_renderer_update", "ph_scene_same_structure", "ph_renderer_deform", "ph_scene_same_topology", "ph_renderer_deform_device", "ph_renderer_mesh_count", "ph_renderer_mesh_vertices", "ph_example_render_to_png", "ph_png_read", "ph_png_write", "ph_image_read", "ph_scene_graph"]
 
 
 class PortrayerHostError(RuntimeError):
@@ -83,6 +83,8 @@ def lib() -> C.CDLL:
         l.ph_renderer_render.argtypes = [vp, _dp, C.POINTER(H.PtRenderParams), _dp, _u8p, _dp, C.POINTER(H.PtStats)]
         l.ph_renderer_aov.restype = C.c_int
         l.ph_renderer_aov.argtypes = [vp, _dp, C.POINTER(H.PtAovParams), C.POINTER(H.PtAovBuffers), _dp]
+        l.ph_renderer_guides.restype = C.c_int
+        l.ph_renderer_guides.argtypes = [vp, _dp, C.POINTER(H.PtAovParams), C.POINTER(H.PtGuidesBuffers), _dp]
         l.ph_renderer_rays.restype = C.c_int
         l.ph_renderer_rays.argtypes = [vp, C.POINTER(H.PtRaysParams), _dp, _dp, C.POINTER(H.PtRaysBuffers), _dp]
         l.ph_renderer_segments.restype = C.c_int
@@ -102,6 +104,8 @@ def lib() -> C.CDLL:
         l.ph_renderer_film_refine.argtypes = [vp, vp, _dp, _dp, C.POINTER(H.PtFilmMapParams), C.POINTER(H.PtFilmRefineParams), C.c_uint32, _u64p, _dp]
         l.ph_renderer_film_denoise.restype = C.c_int
         l.ph_renderer_film_denoise.argtypes = [vp, vp, _dp, C.POINTER(H.PtDenoiseParams), C.POINTER(H.PtDenoiseGuides), _u8p, _dp, _dp]
+        l.ph_renderer_film_denoise_albedo.restype = C.c_int
+        l.ph_renderer_film_denoise_albedo.argtypes = [vp, vp, _dp, C.POINTER(H.PtDenoiseParams), C.POINTER(H.PtDenoiseGuides), _dp, _u8p, _dp, _dp]
         l.ph_renderer_update.restype = C.c_int; l.ph_renderer_update.argtypes = [vp, vp]
         l.ph_scene_same_structure.restype = C.c_int; l.ph_scene_same_structure.argtypes = [vp, vp, C.c_char_p, C.c_size_t]
         l.ph_renderer_deform.restype = C.c_int; l.ph_renderer_deform.argtypes = [vp, vp, C.c_int]
@@ -445,14 +449,17 @@ class Film:
 
     def denoise(self, cam10, iterations: int = 5, sigma_color: float = 2.0, sigma_plane: float = 0.0, normal_power: Optional[int] = 32, same_node: bool = False,
                 want_variance: bool = False, guides: Optional[dict] = None, into: Optional[np.ndarray] = None, linear_into: Optional[np.ndarray] = None,
-                variance_into: Optional[np.ndarray] = None):
+                variance_into: Optional[np.ndarray] = None, albedo=False):
         """(rgb, linear[, variance]): the film's mean after `iterations` levels of an edge-avoiding a-trous filter (pt_film_denoise) - a lossy read, the film
         itself is not changed and resolve() keeps its promise. The filter is steered by what is under each pixel for camera `cam10` (a primary-visibility
         pass on the device) - or by the caller's `guides`, a dict of "node" (H, W) int32, "normal" and "position" (H, W, 3) float64 as Renderer.aov() returns
         them, of which only what the weights read is needed - and by the film's noise estimate: sigma_color is the colour tolerance in standard errors (0: off;
         a film without moments takes 0 only), sigma_plane the plane-distance tolerance in world units (0: off), normal_power the power of two from 1 to 128
         the clamped dot of the normals is raised to (None: off), same_node=True keeps every tap on the centre's node. variance is (H, W) float64, the filtered
-        variance of r + g + b. Pixels without samples keep what `into` / `linear_into` / `variance_into` hold (zeros when the arrays are made here)."""
+        variance of r + g + b. Pixels without samples keep what `into` / `linear_into` / `variance_into` hold (zeros when the arrays are made here).
+        albedo=True filters DEMODULATED colour (pt_film_denoise_albedo): the diffuse colour under each pixel, from one guides pass on the device that also writes
+        the guides, is divided out before the levels and multiplied back after them, so texture detail is not blurred. An (H, W, 3) float64 array is the caller's
+        albedo, as Renderer.guides() returns it, and needs `guides`. False is the plain filter."""
         iterations = self._integer("iterations", iterations, 1, 8)
         sig = []
         for name, v in (("sigma_color", sigma_color), ("sigma_plane", sigma_plane)):
@@ -468,6 +475,15 @@ class Film:
         if sig[0] > 0.0 and not self.moments:
             raise ValueError("sigma_color > 0 needs a film that keeps moments: Renderer.film(w, h, moments=True)")
         shape3, shape1 = (self.height, self.width, 3), (self.height, self.width)
+        alb = None
+        if not isinstance(albedo, (bool, np.bool_)):
+            if not isinstance(albedo, np.ndarray) or albedo.dtype != np.float64 or albedo.shape != shape3:
+                raise ValueError("albedo must be True, False or a float64 array of shape %r" % (shape3,))
+            if guides is None:
+                raise ValueError("an albedo array needs guides=: the caller's albedo comes with the caller's guides")
+            alb = np.ascontiguousarray(albedo)
+        elif albedo and guides is not None:
+            raise ValueError("albedo=True runs the guides pass on the device: with guides= pass the albedo array too")
         g = None
         if guides is not None:
             if not isinstance(guides, dict):
@@ -496,8 +512,12 @@ class Film:
         if g is None and (c is None or c.shape != (10,)):
             raise ValueError("cam10 must hold the camera's 10 numbers unless guides are given")
         p = H.PtDenoiseParams(iterations, H.DENOISE_SAME_NODE if same_node else 0, sig[0], sig[1], npl2)
-        _check(lib().ph_renderer_film_denoise(self._r._h, self._h, _p(c, _dp), C.byref(p), C.byref(g) if g is not None else None, _p(out[0], _u8p), _p(out[1], _dp), _p(out[2], _dp)),
-               "ph_renderer_film_denoise")
+        if alb is not None or (isinstance(albedo, (bool, np.bool_)) and albedo):
+            _check(lib().ph_renderer_film_denoise_albedo(self._r._h, self._h, _p(c, _dp), C.byref(p), C.byref(g) if g is not None else None, _p(alb, _dp), _p(out[0], _u8p), _p(out[1], _dp),
+                                                         _p(out[2], _dp)), "ph_renderer_film_denoise_albedo")
+        else:
+            _check(lib().ph_renderer_film_denoise(self._r._h, self._h, _p(c, _dp), C.byref(p), C.byref(g) if g is not None else None, _p(out[0], _u8p), _p(out[1], _dp), _p(out[2], _dp)),
+                   "ph_renderer_film_denoise")
         return (out[0], out[1], out[2]) if out[2] is not None else (out[0], out[1])
 
     def counts(self) -> np.ndarray:
@@ -649,6 +669,31 @@ class Renderer:
         ms = C.c_double(0.0)
         c = np.ascontiguousarray(cam10, dtype=np.float64)
         _check(lib().ph_renderer_aov(self._h, _p(c, _dp), C.byref(p), C.byref(b), C.byref(ms)), "ph_renderer_aov")
+        out["kernel_ms"] = ms.value
+        return out
+
+    def guides(self, cam10, width: int, height: int, rect=None, offset=(0.5, 0.5), want=("albedo", "position", "normal", "node"), into: Optional[dict] = None) -> dict:
+        """What a denoiser needs of each pixel (pt_guides), in one trace: aov()'s `position`, `normal` and `node` - the same bits - and `albedo`, (H, W, 3) float64,
+        the diffuse colour at the primary hit (the material's, or its texture's texel as the render path reads it; 0 where nothing is hit). `rect`, `offset`,
+        `want` and `into` work as in aov(); returns the arrays named in `want` and `kernel_ms`."""
+        want = tuple(want)
+        unknown = [n for n in want if n not in H.GUIDES_BUFFERS]
+        if unknown or not want:
+            raise ValueError("want must name some of %s, got %r" % (", ".join(H.GUIDES_BUFFERS), want))
+        x0, y0, x1, y1 = rect if rect is not None else (0, 0, width - 1, height - 1)
+        p = H.PtAovParams(width, height, H.PtRect(x0, y0, x1, y1), (C.c_double * 2)(float(offset[0]), float(offset[1])))
+        out, b = {}, H.PtGuidesBuffers()
+        for name in want:
+            dtype, comps = H.GUIDES_BUFFERS[name]
+            shape = (height, width) if comps == 1 else (height, width, comps)
+            a = into[name] if into is not None and name in into else np.zeros(shape, dtype=dtype)
+            if not isinstance(a, np.ndarray) or a.shape != shape or a.dtype != dtype or not a.flags.c_contiguous:
+                raise ValueError("into[%r] must be a C-contiguous %s array of shape %r" % (name, np.dtype(dtype).name, shape))
+            out[name] = a
+            setattr(b, name, _p(a, _dp if dtype is np.float64 else _ip))
+        ms = C.c_double(0.0)
+        c = np.ascontiguousarray(cam10, dtype=np.float64)
+        _check(lib().ph_renderer_guides(self._h, _p(c, _dp), C.byref(p), C.byref(b), C.byref(ms)), "ph_renderer_guides")
         out["kernel_ms"] = ms.value
         return out
 

@@ -599,6 +599,16 @@ extern "C" int ph_renderer_aov(ph_renderer* r, const double camera[10], const pt
     });
 }
 
+extern "C" int ph_renderer_guides(ph_renderer* r, const double camera[10], const pt_aov_params* p, const pt_guides_buffers* out, double* kernel_ms) {
+    if (!r || !camera || !p || !out) return bad("null argument");
+    return guarded([&]() -> int {
+        pt_camera pc = detail::Camera(camera_from(camera), (double)p->width, (double)p->height).to_abi();  // the camera a render of this size gets
+        int rc = pt_guides(r->r->context(), &pc, p, out, kernel_ms);  // (a renderer spread over a node: rank 0's context, the whole slice)
+        if (rc != PT_OK) { g_error = pt_last_error(r->r->context()); return rc == PT_ERR_SLICE ? PH_ERR_PANIC : PH_ERR_RUNTIME; }
+        return PH_OK;
+    });
+}
+
 extern "C" int ph_renderer_rays(ph_renderer* r, const pt_rays_params* p, const double* origins, const double* directions, const pt_rays_buffers* out, double* kernel_ms) {
     if (!r || !p || !out) return bad("null argument");
     if (p->n && (!origins || !directions)) return bad("null argument");
@@ -638,6 +648,7 @@ struct ph_film {
     // ph_renderer_film_denoise: the guides its aov pass writes (position, normal, node) and the device copies of its three outputs, allocated on first use
     void* d_guide[3] = {nullptr, nullptr, nullptr};
     void* d_out[3] = {nullptr, nullptr, nullptr};
+    void* d_albedo = nullptr;  // ph_renderer_film_denoise_albedo: the albedo its guides pass writes
 };
 static int film_rc(ph_renderer* r, int rc) {
     if (rc == PT_OK) return PH_OK;
@@ -665,7 +676,7 @@ extern "C" int ph_renderer_film_destroy(ph_renderer* r, ph_film* film) {
     return guarded([&]() -> int {
         int rc = film_rc(r, pt_film_destroy(r->r->context(), film->f));
         if (rc != PH_OK) return rc;
-        for (void* d : {film->d_guide[0], film->d_guide[1], film->d_guide[2], film->d_out[0], film->d_out[1], film->d_out[2]}) if (d) pt_device_free(r->r->context(), d);
+        for (void* d : {film->d_guide[0], film->d_guide[1], film->d_guide[2], film->d_out[0], film->d_out[1], film->d_out[2], film->d_albedo}) if (d) pt_device_free(r->r->context(), d);
         delete film;
         return rc;
     });
@@ -772,12 +783,15 @@ extern "C" int ph_renderer_film_refine(ph_renderer* r, ph_film* film, const doub
 
 // The film, denoised (pt_film_denoise): with the caller's guides the library's host path; without, the guides come from a primary-visibility pass at the pixel
 // centres for `camera` and never leave the device - pt_aov_device into buffers kept with the handle, pt_aov_finish, pt_film_denoise_device, the outputs copied out.
-extern "C" int ph_renderer_film_denoise(ph_renderer* r, ph_film* film, const double camera[10], const pt_denoise_params* p, const pt_denoise_guides* guides, uint8_t* rgb, double* linear,
-                                        double* variance) {
+// demodulated (ph_renderer_film_denoise_albedo, pt_film_denoise_albedo): the caller's guides come with the caller's albedo; without them ONE guides pass
+// (pt_guides_device) writes the albedo beside the guides in the same trace, and pt_film_denoise_albedo_device takes the place of pt_film_denoise_device.
+static int film_denoise(ph_renderer* r, ph_film* film, const double camera[10], const pt_denoise_params* p, const pt_denoise_guides* guides, bool demodulated, const double* albedo, uint8_t* rgb,
+                        double* linear, double* variance) {
     if (!r || !film || !p || (!guides && !camera) || (!rgb && !linear && !variance)) return bad("null argument");
+    if (demodulated && (guides != nullptr) != (albedo != nullptr)) return bad("the caller's guides and the caller's albedo come together");
     return guarded([&]() -> int {
         pt_context* c = r->r->context();
-        if (guides) return film_rc(r, pt_film_denoise(c, film->f, p, guides, rgb, linear, variance));
+        if (guides) return film_rc(r, demodulated ? pt_film_denoise_albedo(c, film->f, p, guides, albedo, rgb, linear, variance) : pt_film_denoise(c, film->f, p, guides, rgb, linear, variance));
         const size_t n = (size_t)film->width * film->height;
         const bool want_n = p->normal_power_log2 >= 0 || p->sigma_plane > 0.0, want_pos = p->sigma_plane > 0.0;
         const size_t guide_bytes[3] = {n * 24, n * 24, n * 4}, out_bytes[3] = {n * 3, n * 24, n * 8};
@@ -788,6 +802,7 @@ extern "C" int ph_renderer_film_denoise(ph_renderer* r, ph_film* film, const dou
             if (guide_wanted[k] && !film->d_guide[k]) rc = pt_device_alloc(c, guide_bytes[k], &film->d_guide[k]);
             if (rc == PT_OK && host_out[k] && !film->d_out[k]) rc = pt_device_alloc(c, out_bytes[k], &film->d_out[k]);
         }
+        if (rc == PT_OK && demodulated && !film->d_albedo) rc = pt_device_alloc(c, n * 24, &film->d_albedo);
         if (rc != PT_OK) return film_rc(r, rc);
         // pixels without samples keep the caller's bytes: where there are any, the caller's buffers go to the device first
         std::vector<uint32_t> counts(n);
@@ -800,16 +815,34 @@ extern "C" int ph_renderer_film_denoise(ph_renderer* r, ph_film* film, const dou
         ap.width = film->width; ap.height = film->height;
         ap.slice.x0 = 0; ap.slice.y0 = 0; ap.slice.x1 = film->width - 1; ap.slice.y1 = film->height - 1;
         ap.offset[0] = 0.5; ap.offset[1] = 0.5;
-        pt_aov_buffers ab = {nullptr, want_pos ? (double*)film->d_guide[0] : nullptr, want_n ? (double*)film->d_guide[1] : nullptr, (int32_t*)film->d_guide[2], nullptr, nullptr};
-        if ((rc = pt_aov_device(c, &pc, &ap, &ab, nullptr))) return film_rc(r, rc);
-        if ((rc = pt_aov_finish(c, nullptr))) return film_rc(r, rc);
-        pt_denoise_guides dg = {ab.position, ab.normal, ab.node};
-        if ((rc = pt_film_denoise_device(c, film->f, p, &dg, rgb ? film->d_out[0] : nullptr, linear ? (double*)film->d_out[1] : nullptr, variance ? (double*)film->d_out[2] : nullptr, nullptr)))
-            return film_rc(r, rc);
+        pt_denoise_guides dg = {want_pos ? (double*)film->d_guide[0] : nullptr, want_n ? (double*)film->d_guide[1] : nullptr, (int32_t*)film->d_guide[2]};
+        void* d_rgb = rgb ? film->d_out[0] : nullptr;
+        double *d_linear = linear ? (double*)film->d_out[1] : nullptr, *d_variance = variance ? (double*)film->d_out[2] : nullptr;
+        if (demodulated) {
+            pt_guides_buffers gb = {(double*)film->d_albedo, (double*)dg.position, (double*)dg.normal, (int32_t*)dg.node};
+            if ((rc = pt_guides_device(c, &pc, &ap, &gb, nullptr))) return film_rc(r, rc);
+            if ((rc = pt_guides_finish(c, nullptr))) return film_rc(r, rc);
+            if ((rc = pt_film_denoise_albedo_device(c, film->f, p, &dg, gb.albedo, d_rgb, d_linear, d_variance, nullptr))) return film_rc(r, rc);
+        } else {
+            pt_aov_buffers ab = {nullptr, (double*)dg.position, (double*)dg.normal, (int32_t*)dg.node, nullptr, nullptr};
+            if ((rc = pt_aov_device(c, &pc, &ap, &ab, nullptr))) return film_rc(r, rc);
+            if ((rc = pt_aov_finish(c, nullptr))) return film_rc(r, rc);
+            if ((rc = pt_film_denoise_device(c, film->f, p, &dg, d_rgb, d_linear, d_variance, nullptr))) return film_rc(r, rc);
+        }
         for (int k = 0; k < 3; k++)
             if (host_out[k] && (rc = pt_copy_from_device(c, host_out[k], film->d_out[k], out_bytes[k]))) return film_rc(r, rc);
         return PH_OK;
     });
+}
+
+extern "C" int ph_renderer_film_denoise(ph_renderer* r, ph_film* film, const double camera[10], const pt_denoise_params* p, const pt_denoise_guides* guides, uint8_t* rgb, double* linear,
+                                        double* variance) {
+    return film_denoise(r, film, camera, p, guides, false, nullptr, rgb, linear, variance);
+}
+
+extern "C" int ph_renderer_film_denoise_albedo(ph_renderer* r, ph_film* film, const double camera[10], const pt_denoise_params* p, const pt_denoise_guides* guides, const double* albedo,
+                                               uint8_t* rgb, double* linear, double* variance) {
+    return film_denoise(r, film, camera, p, guides, true, albedo, rgb, linear, variance);
 }
 
 extern "C" int ph_example_render_to_png(const char* name, const char* assets_dir, int n, uint32_t width, uint32_t height, const char* png_path) {

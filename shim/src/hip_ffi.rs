@@ -102,6 +102,10 @@ pub struct PtRenderParams {
 pub struct PtAovBuffers {                  // pt_aov_buffers: each optional (null = not wanted), full image, row-major
     pub depth: *mut f64, pub position: *mut f64, pub normal: *mut f64, pub node: *mut i32, pub sub: *mut i32, pub material: *mut i32,
 }
+#[repr(C)]
+pub struct PtGuidesBuffers {               // pt_guides_buffers: each optional (null = not wanted), full image, row-major; albedo width x height x 3 f64, the rest as in pt_aov_buffers
+    pub albedo: *mut f64, pub position: *mut f64, pub normal: *mut f64, pub node: *mut i32,
+}
 #[repr(C)] pub struct PtRaysParams { pub n: u64, pub any_hit: i32, pub reorder: i32 }   // pt_rays_params: any_hit 1 = occlusion query, reorder 1 = the device groups like rays first
 #[repr(C)]
 pub struct PtRadianceParams {              // pt_radiance_params: ray i draws from the generator's stream (seed, stream_base + i, sample), draws 2, 3, ...
@@ -163,6 +167,12 @@ extern "C" {
     pub fn pt_aov_device(ctx: *mut PtContext, camera: *const PtCamera, params: *const PtAovParams, device_out: *const PtAovBuffers,
                          hip_stream: *mut c_void) -> c_int;
     pub fn pt_aov_finish(ctx: *mut PtContext, kernel_ms: *mut f64) -> c_int;
+    // what a denoiser needs of each pixel, in one trace: pt_aov's pass with the diffuse colour under the pixel (albedo) beside position, normal and node.
+    // Shares pt_aov's pass: one pass of either kind in flight per context, and pt_guides_finish is pt_aov_finish
+    pub fn pt_guides(ctx: *mut PtContext, camera: *const PtCamera, params: *const PtAovParams, host_out: *const PtGuidesBuffers, kernel_ms: *mut f64) -> c_int;
+    pub fn pt_guides_device(ctx: *mut PtContext, camera: *const PtCamera, params: *const PtAovParams, device_out: *const PtGuidesBuffers,
+                            hip_stream: *mut c_void) -> c_int;
+    pub fn pt_guides_finish(ctx: *mut PtContext, kernel_ms: *mut f64) -> c_int;
     // rays of the caller's own: nearest hit (t, position, normal, ids) or occlusion per ray; n x 3 f64 origins and directions in world space
     pub fn pt_rays(ctx: *mut PtContext, params: *const PtRaysParams, origins: *const f64, directions: *const f64, host_out: *const PtRaysBuffers,
                    kernel_ms: *mut f64) -> c_int;
@@ -208,6 +218,11 @@ extern "C" {
                            variance: *mut f64) -> c_int;
     pub fn pt_film_denoise_device(ctx: *mut PtContext, film: *mut PtFilm, params: *const PtDenoiseParams, d_guides: *const PtDenoiseGuides, d_rgb: *mut c_void,
                                   d_linear: *mut f64, d_variance: *mut f64, hip_stream: *mut c_void) -> c_int;
+    // the same filter on demodulated colour: albedo (width x height x 3 f64, as pt_guides writes it) is divided out before the levels and multiplied back after
+    pub fn pt_film_denoise_albedo(ctx: *mut PtContext, film: *mut PtFilm, params: *const PtDenoiseParams, host_guides: *const PtDenoiseGuides, albedo: *const f64,
+                                  rgb: *mut u8, linear: *mut f64, variance: *mut f64) -> c_int;
+    pub fn pt_film_denoise_albedo_device(ctx: *mut PtContext, film: *mut PtFilm, params: *const PtDenoiseParams, d_guides: *const PtDenoiseGuides, d_albedo: *const f64,
+                                         d_rgb: *mut c_void, d_linear: *mut f64, d_variance: *mut f64, hip_stream: *mut c_void) -> c_int;
     pub fn pt_context_stream(ctx: *mut PtContext, slot: c_int) -> *mut c_void;
     pub fn pt_context_next_slot(ctx: *const PtContext) -> c_int;
     // one render call over the GPUs of a node (one context per GPU, one RCCL gather)
