@@ -382,8 +382,9 @@ int pt_guides_finish(pt_context *ctx, double *kernel_ms);
  *   (direction octant, Morton code of the origin inside the scene tree's root box; radix sort) and wavefronts take 64 consecutive rays of THAT order. Results are
  *   bit-identical either way and are written at the caller's index; kernel_ms covers keying, sort and cast. Coherent batches (camera rays in pixel order,
  *   anything already grouped) gain nothing and pay the sort, about 16 bytes of extra traffic per ray per radix pass; it is meant for large batches in
- *   no useful order (ambient-occlusion and bounce rays). From which batch size and degree of disorder on it wins has not been measured yet: this is
- *   the byte count of profiles/rays/notes.md section 2, whose measure.py is the script to settle it with.
+ *   no useful order (bounce rays). From which batch size and degree of disorder on it wins has not been measured yet: this is
+ *   the byte count of profiles/rays/notes.md section 2, whose measure.py is the script to settle it with. Measured since (profiles/ao/notes.md): ambient-occlusion
+ *   rays with a point's rays next to each other, points in pixel order, are NOT such a batch - at 33 M rays reorder = 1 is 1.3 to 4.1 x slower there.
  * Errors, before the first HIP call: PT_ERR_ARGUMENT (NULL context / params / origins / directions; no buffer asked for; n > PT_RAYS_MAX; any_hit or
  * reorder other than 0 or 1; any_hit = 1 with a buffer other than `occluded`), PT_ERR_NO_SCENE. n = 0 is PT_OK: nothing is launched or written. During the
  * pass: PT_ERR_TRAVERSAL as for a render; trees of any depth a render accepts are walked (the stack continues in HBM). The pass has work buffers of its own:
@@ -429,6 +430,60 @@ int pt_segments(pt_context *ctx, const pt_rays_params *params, const double *ori
                 double *kernel_ms);
 int pt_segments_device(pt_context *ctx, const pt_rays_params *params, const double *d_origins, const double *d_directions, const double *d_t_max,
                        const pt_rays_buffers *device_out, void *hip_stream);
+
+/* ---- Ambient occlusion: how much of the hemisphere above a point is blocked within `radius`. The caller gives POINTS - n positions and n normals, n x 3 f64 in
+ * world space, what pt_aov writes per pixel or a baker's texel centres - and the device makes each point's `samples` rays in registers, walks them as occlusion
+ * queries over [EPSILON, radius) and counts. No ray is ever in memory: 48 bytes per point in, at most 29 out.
+ * The rays are a CONTRACT, a fixed sequence of correctly rounded f64 operations (portrayer_amd/csrc/pt_ao.h states it; pt_test_ao_rays_host replays it on the
+ * host). Point i has the stream index q = first_index + i, and in this order:
+ *   1. valid      all six components finite and at most 1e18 in magnitude (pt_rays' rule) and the normal not (0, 0, 0). An INVALID point traces nothing, occupies
+ *                 no lane of a walk and reports occluded = 0, valid = 0, bent = (0, 0, 0) - so pt_aov's miss pixels are invalid points.
+ *   2. face eye   with PT_AO_FACE_EYE: v = P - eye per component; if dot(N, v) > 0 then N = -N. (dot: (x x' + y y') + z z', as everywhere.)
+ *   3. normalise  n = N / sqrt(dot(N, N)), a component-wise division.
+ *   4. rotation   j = (uint32)(rng(seed, q, pass, draw 0) * 256.0), the render's counter-based generator; (c, s) = PT_AO_ROT[j] = (cos, sin) of 2 pi (j + 0.5) / 256.
+ *   5. local      for k = 0 .. samples - 1 with (x, y, z) = PT_AO_DIRS[k]: lx = c x - s y, ly = s x + c y, lz = z. PT_AO_DIRS: 64 cosine-weighted directions
+ *                 about +z, every power-of-two prefix stratified (pt_ao_tables.h; tools/gen_ao_tables.py).
+ *   6. frame      sg = copysign(1, n.z); a = -1 / (sg + n.z); b = (n.x n.y) a; T = (1 + ((sg n.x) n.x) a, sg b, -(sg n.x)); B = (b, sg + (n.y n.y) a, -n.y).
+ *   7. direction  d = (T lx + B ly) + n lz per component, not renormalised.
+ *   8. origin     o = P + n bias.
+ *   9. occlusion  occ_k = what pt_segments with any_hit = 1 answers for (o, d, t_max = radius) in the scene's traversal - that definition taken over whole, with
+ *                 its exceptions for the k-d semantics, KDMesh trees and mesh boxes, and its rule for rays that are not traced. radius = +inf is pt_rays.
+ * Outputs per point, each OPTIONAL (NULL = not wanted), at least one:
+ *   occluded  n      u32  the sum of occ_k
+ *   valid     n      u8   step 1
+ *   bent      n x 3  f64  starting from (0, 0, 0), the sum of d_k over the k with occ_k = 0 in ascending k, left to right, not normalised
+ * The bits do not depend on how a batch is cut - a slice [k, k + m) submitted with first_index + k equals that slice of the whole - nor on the work layout the
+ * kernel runs in (PORTRAYER_AO_LAYOUT=point|sample picks it at the launch). Another `pass` draws another rotation: a caller sums passes for more than
+ * 64 rays per point.
+ * The pass IS a ray-query pass: it shares pt_rays' work buffers and its one pass in flight - pt_ao_device is closed by pt_ao_finish, which is pt_rays_finish, and
+ * while a pt_rays_device / pt_segments_device / pt_ao_device pass is open a second one of any kind is PT_ERR_ARGUMENT.
+ * Errors, before the first HIP call: PT_ERR_ARGUMENT (a NULL context / params / positions / normals / buffers; no buffer asked for; n > PT_AO_MAX; samples not a
+ * power of two <= 64; radius NaN or <= PT_EPSILON; bias negative or not finite; flags other than PT_AO_FACE_EYE; PT_AO_FACE_EYE with a non-finite eye),
+ * PT_ERR_NO_SCENE. n = 0 is PT_OK: nothing is launched or written. During the pass: PT_ERR_TRAVERSAL as for a render. */
+#define PT_AO_FACE_EYE 1u                 /* pt_ao_params.flags: turn each normal towards `eye` first (step 2) */
+#define PT_AO_MAX (PT_RAYS_MAX / 64)      /* points per call (2^24): PT_RAYS_MAX rays at 64 samples            */
+typedef struct {
+    uint64_t n;             /* points, <= PT_AO_MAX                                          */
+    uint32_t samples;       /* rays per point: 1, 2, 4, 8, 16, 32 or 64                      */
+    uint32_t pass;          /* which rotation a point draws                                  */
+    uint64_t seed;
+    uint64_t first_index;   /* stream index of point 0                                       */
+    double radius;          /* > EPSILON; +inf allowed                                       */
+    double bias;            /* finite, >= 0: the origin is lifted by bias along the normal   */
+    uint32_t flags;         /* 0 or PT_AO_FACE_EYE                                           */
+    double eye[3];          /* read with PT_AO_FACE_EYE only                                 */
+} pt_ao_params;
+typedef struct { uint32_t *occluded; uint8_t *valid; double *bent; } pt_ao_buffers;
+/* Host buffers, synchronous: uploads the points, copies back the buffers asked for. kernel_ms (optional): device time of the pass (HIP events). */
+int pt_ao(pt_context *ctx, const pt_ao_params *params, const double *positions, const double *normals, const pt_ao_buffers *host_out, double *kernel_ms);
+/* The same with points and results in DEVICE memory, queued on `hip_stream` (a hipStream_t, or NULL for the default stream) without synchronising the host -
+ * behind a pt_aov_device on the same stream it reads that pass's position and normal, and nothing per pixel crosses the bus but the results. */
+int pt_ao_device(pt_context *ctx, const pt_ao_params *params, const double *d_positions, const double *d_normals, const pt_ao_buffers *device_out, void *hip_stream);
+int pt_ao_finish(pt_context *ctx, double *kernel_ms);
+/* Test hooks, no context and no GPU. pt_test_ao_rays_host: steps 1 to 8 on the host, by the functions the kernel compiles: origins and directions n x samples x 3
+ * (point-major; zeros for an invalid point), valid n. Checks params as pt_ao does (PT_ERR_ARGUMENT). pt_test_ao_tables: the library's PT_AO_DIRS (192) and PT_AO_ROT (512). */
+int pt_test_ao_rays_host(uint64_t n, const pt_ao_params *params, const double *positions, const double *normals, double *origins, double *directions, uint8_t *valid);
+int pt_test_ao_tables(double *dirs, double *rot);
 
 /* ---- Radiance: rays the CALLER supplies, SHADED (the crate's public Ray::color(scene, background, 0), ray.rs:139-148) - cameras the crate does not have
  * (fisheye, panoramic, orthographic, thin lens), light probes and environment captures from a point inside the scene, one more gathered bounce for a baker

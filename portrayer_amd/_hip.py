@@ -128,6 +128,25 @@ RAYS_BUFFERS = {"t": (np.float64, 1), "position": (np.float64, 3), "normal": (np
 RAYS_MAX = 1 << 30  # PT_RAYS_MAX
 
 
+class PtAoParams(C.Structure):
+    """pt_ao_params: the points of one ambient-occlusion call and what fixes their rays - samples per point, which rotation (pass, seed, first_index), radius, bias,
+    and with AO_FACE_EYE the eye every normal is first turned towards."""
+    _fields_ = [("n", C.c_uint64), ("samples", C.c_uint32), ("pass_index", C.c_uint32), ("seed", C.c_uint64), ("first_index", C.c_uint64), ("radius", C.c_double),
+                ("bias", C.c_double), ("flags", C.c_uint32), ("eye", C.c_double * 3)]
+
+
+class PtAoBuffers(C.Structure):
+    """pt_ao_buffers: occluded (n,) u32, valid (n,) u8, bent (n, 3) f64; each optional."""
+    _fields_ = [("occluded", _up), ("valid", _u8p), ("bent", _dp)]
+
+
+# pt_ao's outputs in the order of pt_ao_buffers: name -> (numpy dtype, components per point)
+AO_BUFFERS = {"occluded": (np.uint32, 1), "valid": (np.uint8, 1), "bent": (np.float64, 3)}
+AO_FACE_EYE = 1  # PT_AO_FACE_EYE
+AO_MAX = RAYS_MAX // 64  # PT_AO_MAX
+AO_SAMPLES = (1, 2, 4, 8, 16, 32, 64)
+
+
 class PtRadianceParams(C.Structure):
     _fields_ = [("n", C.c_uint64), ("reorder", C.c_int32), ("background_per_ray", C.c_int32), ("seed", C.c_uint64), ("stream_base", C.c_uint64), ("sample", C.c_uint32)]
 
@@ -191,7 +210,8 @@ EXPORTS = ["pt_abi_version", "pt_device_count", "pt_context_create", "pt_context
            "pt_film_create_moments", "pt_film_add_map", "pt_film_add_map_device", "pt_film_error", "pt_film_error_device", "pt_film_budget_device",
            "pt_test_film_moments_host", "pt_test_film_plan_host", "pt_test_film_plan",
            "pt_film_denoise", "pt_film_denoise_device", "pt_test_denoise_host",
-           "pt_guides", "pt_guides_device", "pt_guides_finish", "pt_film_denoise_albedo", "pt_film_denoise_albedo_device", "pt_test_denoise_albedo_host"]
+           "pt_guides", "pt_guides_device", "pt_guides_finish", "pt_film_denoise_albedo", "pt_film_denoise_albedo_device", "pt_test_denoise_albedo_host",
+           "pt_ao", "pt_ao_device", "pt_ao_finish", "pt_test_ao_rays_host", "pt_test_ao_tables"]
 
 
 def header_functions():
@@ -348,6 +368,16 @@ def lib() -> C.CDLL:
         l.pt_segments_device.argtypes = [C.c_void_p, C.POINTER(PtRaysParams), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(PtRaysBuffers), C.c_void_p]
         l.pt_rays_finish.restype = C.c_int
         l.pt_rays_finish.argtypes = [C.c_void_p, _dp]
+        l.pt_ao.restype = C.c_int
+        l.pt_ao.argtypes = [C.c_void_p, C.POINTER(PtAoParams), _dp, _dp, C.POINTER(PtAoBuffers), _dp]
+        l.pt_ao_device.restype = C.c_int
+        l.pt_ao_device.argtypes = [C.c_void_p, C.POINTER(PtAoParams), C.c_void_p, C.c_void_p, C.POINTER(PtAoBuffers), C.c_void_p]
+        l.pt_ao_finish.restype = C.c_int
+        l.pt_ao_finish.argtypes = [C.c_void_p, _dp]
+        l.pt_test_ao_rays_host.restype = C.c_int
+        l.pt_test_ao_rays_host.argtypes = [C.c_uint64, C.POINTER(PtAoParams), _dp, _dp, _dp, _dp, _u8p]
+        l.pt_test_ao_tables.restype = C.c_int
+        l.pt_test_ao_tables.argtypes = [_dp, _dp]
         l.pt_radiance.restype = C.c_int
         l.pt_radiance.argtypes = [C.c_void_p, C.POINTER(PtRadianceParams), _dp, _dp, _dp, _dp, _dp]
         l.pt_radiance_device.restype = C.c_int

@@ -19,6 +19,7 @@
 #include "pt_guides_inst.h"
 #include "pt_rays_inst.h"
 #include "pt_segments_inst.h"
+#include "pt_ao_inst.h"
 #include "pt_radiance_inst.h"
 #include "pt_film_inst.h"
 #include "pt_film_map_inst.h"
@@ -2839,6 +2840,145 @@ extern "C" int pt_segments_device(pt_context* c, const pt_rays_params* p, const 
 extern "C" int pt_rays_finish(pt_context* c, double* kernel_ms) {
     if (!c) return PT_ERR_ARGUMENT;
     return pt_pass_finish(c, c->rays.pass, "no pt_rays_device / pt_segments_device pass in flight", kernel_ms);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Ambient occlusion (pt_ao.h: the contract; pt_ao_inst.hip: the kernel): a ray-query pass, on that pass's PtPass
+// ------------------------------------------------------------------------------------------------
+static hipError_t pt_ao_dispatch(const PtAoArgs& a, int layout, int n_cu, hipStream_t stream, uint32_t* grid, bool launch) {
+    PT_MODE_LAUNCH(pt_ao_launch_mode_, a.r.scene.mode, a, layout, n_cu, stream, grid, launch)
+}
+
+// What pt_ao refuses of a parameter block, in the order the header gives; null: nothing. (Also pt_test_ao_rays_host's check.)
+static const char* pt_ao_params_error(const pt_ao_params* p) {
+    if (p->n > PT_AO_MAX) return "pt_ao: more than PT_AO_MAX points in one call";
+    if (p->samples == 0 || p->samples > 64 || (p->samples & (p->samples - 1)) != 0) return "pt_ao: samples must be a power of two, 1 .. 64";
+    if (!(p->radius > PT_EPSILON)) return "pt_ao: radius must be greater than EPSILON (+inf is allowed)";
+    if (!std::isfinite(p->bias) || p->bias < 0.0) return "pt_ao: bias must be finite and not negative";
+    if (p->flags & ~PT_AO_FACE_EYE) return "pt_ao: unknown flags";
+    if ((p->flags & PT_AO_FACE_EYE) && !(std::isfinite(p->eye[0]) && std::isfinite(p->eye[1]) && std::isfinite(p->eye[2]))) return "pt_ao: PT_AO_FACE_EYE needs a finite eye";
+    return nullptr;
+}
+
+static PtAoSet pt_ao_set(const pt_ao_params* p) {
+    PtAoSet s;
+    s.seed = p->seed; s.first_index = p->first_index; s.pass = p->pass; s.flags = p->flags; s.bias = p->bias;
+    s.eye = (p->flags & PT_AO_FACE_EYE) ? pt_v3(p->eye[0], p->eye[1], p->eye[2]) : pt_v3(0.0, 0.0, 0.0);
+    return s;
+}
+
+// Everything that can be refused without a HIP call, in the order the header gives. (pt_fail takes a NULL context.)
+static int pt_ao_check(pt_context* c, const pt_ao_params* p, const double* positions, const double* normals, const pt_ao_buffers* out) {
+    if (!c || !p || !positions || !normals || !out) return pt_fail(c, PT_ERR_ARGUMENT, "pt_ao: NULL context, params, positions, normals or buffers");
+    if (!(out->occluded || out->valid || out->bent)) return pt_fail(c, PT_ERR_ARGUMENT, "pt_ao: no output buffer asked for");
+    if (const char* why = pt_ao_params_error(p)) return pt_fail(c, PT_ERR_ARGUMENT, why);
+    if (!c->have_scene) return pt_fail(c, PT_ERR_NO_SCENE, "no scene uploaded");
+    // (the ray queries' words, whichever of the three kinds is open: the pass object is theirs, and pt_rays_finish closes all of them)
+    if (c->rays.pass.pending) return pt_fail(c, PT_ERR_ARGUMENT, "a pt_rays_device / pt_segments_device pass is in flight: pt_rays_finish first");
+    return PT_OK;
+}
+
+// The work layout of a launch: PORTRAYER_AO_LAYOUT=point|sample, else the one that measured faster.
+static int pt_ao_layout() {
+    if (const char* e = getenv("PORTRAYER_AO_LAYOUT")) {
+        if (!strcmp(e, "point")) return PT_AO_POINT_MAJOR;
+        if (!strcmp(e, "sample")) return PT_AO_SAMPLE_MAJOR;
+    }
+    return PT_AO_POINT_MAJOR;
+}
+
+// Queues the pass on `stream` (pt_pass_open ... pt_pass_seal), as pt_rays_common does and on its PtPass. Every pointer is a DEVICE pointer; n > 0. The LDS stack
+// area is sized as for the ray queries, less the point-major layout's column of directions.
+static int pt_ao_common(pt_context* c, const pt_ao_params* p, const double* d_positions, const double* d_normals, const pt_ao_buffers& out, hipStream_t stream) {
+    PtPass& v = c->rays.pass;
+    int rc = pt_pass_prepare(c, v);
+    if (rc) return rc;
+    const int layout = pt_ao_layout();
+    PtAoArgs a;
+    memset(&a, 0, sizeof a);
+    a.r.scene = c->view;
+    a.n = p->n; a.positions = d_positions; a.normals = d_normals;
+    a.set = pt_ao_set(p);
+    a.samples = p->samples;
+    while ((1u << a.log2_samples) < p->samples) a.log2_samples++;
+    a.radius = p->radius;
+    a.occluded = out.occluded; a.valid = out.valid; a.bent = out.bent;
+    const uint64_t per_item = layout == PT_AO_POINT_MAJOR ? 64u >> a.log2_samples : 64u;  // points of a wavefront
+    a.r.n_items = (uint32_t)((p->n + per_item - 1) / per_item);                          // (n <= PT_AO_MAX = 2^24: at most 2^24 items)
+    a.r.stack_lds_cap = pt_stack_lds_cap(a.r.scene, pt_ao_waves(a.r.scene.mode) == 3 ? 52 * 1024 : 39 * 1024, pt_ao_frame_bytes(layout));  // (pt_walk_sizing's budgets)
+    a.r.grid_share = 1;
+    uint32_t grid = 0;
+    PT_HIP(c, pt_ao_dispatch(a, layout, c->n_cu, stream, &grid, false));
+    if ((rc = pt_pass_open(c, v, a.r, grid, false, stream))) return rc;
+    PT_HIP(c, pt_ao_dispatch(a, layout, c->n_cu, stream, &grid, true));
+    return pt_pass_seal(c, v);
+}
+
+extern "C" int pt_ao(pt_context* c, const pt_ao_params* p, const double* positions, const double* normals, const pt_ao_buffers* host_out, double* kernel_ms) {
+    int rc = pt_ao_check(c, p, positions, normals, host_out);
+    if (rc) return rc;
+    if (kernel_ms) *kernel_ms = 0.0;
+    if (p->n == 0) return PT_OK;
+    PT_HIP(c, hipSetDevice(c->device));
+    const size_t n = (size_t)p->n;
+    // the ray-query pass's device copies: positions and normals where it keeps origins and directions, the results in three of its output buffers
+    void* host[3] = {host_out->occluded, host_out->valid, host_out->bent};
+    PtBuf* buf[3] = {&c->rays.out[3], &c->rays.out[6], &c->rays.out[1]};
+    const size_t elem[3] = {4, 1, 24};  // bytes per point
+    void* dev[3] = {nullptr, nullptr, nullptr};
+    if ((rc = pt_reserve(c, c->rays.in[0], n * 24)) || (rc = pt_reserve(c, c->rays.in[1], n * 24))) return rc;
+    for (int k = 0; k < 3; k++) {
+        if (!host[k]) continue;
+        if ((rc = pt_reserve(c, *buf[k], n * elem[k]))) return rc;
+        dev[k] = buf[k]->p;
+    }
+    PT_HIP(c, hipMemcpy(c->rays.in[0].p, positions, n * 24, hipMemcpyHostToDevice));
+    PT_HIP(c, hipMemcpy(c->rays.in[1].p, normals, n * 24, hipMemcpyHostToDevice));
+    pt_ao_buffers d_out;
+    d_out.occluded = (uint32_t*)dev[0]; d_out.valid = (uint8_t*)dev[1]; d_out.bent = (double*)dev[2];
+    rc = pt_ao_common(c, p, (const double*)c->rays.in[0].p, (const double*)c->rays.in[1].p, d_out, nullptr);
+    if ((rc = pt_pass_settle(c, c->rays.pass, rc))) return rc;
+    for (int k = 0; k < 3; k++)
+        if (host[k]) PT_HIP(c, hipMemcpy(host[k], dev[k], n * elem[k], hipMemcpyDeviceToHost));
+    return pt_pass_result(c, c->rays.pass, kernel_ms);
+}
+
+extern "C" int pt_ao_device(pt_context* c, const pt_ao_params* p, const double* d_positions, const double* d_normals, const pt_ao_buffers* device_out, void* hip_stream) {
+    int rc = pt_ao_check(c, p, d_positions, d_normals, device_out);
+    if (rc) return rc;
+    if (p->n == 0) return PT_OK;  // nothing queued, nothing to finish
+    PT_HIP(c, hipSetDevice(c->device));
+    return pt_pass_device_tail(c, c->rays.pass, pt_ao_common(c, p, d_positions, d_normals, *device_out, (hipStream_t)hip_stream));
+}
+
+// The pass is the ray queries': one function closes any of them.
+extern "C" int pt_ao_finish(pt_context* c, double* kernel_ms) { return pt_rays_finish(c, kernel_ms); }
+
+// Steps 1 to 8 of the contract on the host: pt_ao_valid and pt_ao_ray as this translation unit's host pass compiles them (-ffp-contract=off).
+extern "C" int pt_test_ao_rays_host(uint64_t n, const pt_ao_params* p, const double* positions, const double* normals, double* origins, double* directions, uint8_t* valid) {
+    if (!p || !positions || !normals || !origins || !directions || !valid) return PT_ERR_ARGUMENT;
+    if (pt_ao_params_error(p)) return PT_ERR_ARGUMENT;
+    const PtAoSet set = pt_ao_set(p);
+    for (uint64_t i = 0; i < n; i++) {
+        const PtVec3 P = pt_v3(positions[3 * i], positions[3 * i + 1], positions[3 * i + 2]), N = pt_v3(normals[3 * i], normals[3 * i + 1], normals[3 * i + 2]);
+        valid[i] = pt_ao_valid(P, N) ? 1 : 0;
+        for (uint32_t k = 0; k < p->samples; k++) {
+            PtVec3 o = pt_v3(0.0, 0.0, 0.0), d = o;
+            if (valid[i]) pt_ao_ray(set, P, N, p->first_index + i, k, &o, &d);
+            double* oo = origins + 3 * (i * p->samples + k);
+            double* dd = directions + 3 * (i * p->samples + k);
+            oo[0] = o.x; oo[1] = o.y; oo[2] = o.z;
+            dd[0] = d.x; dd[1] = d.y; dd[2] = d.z;
+        }
+    }
+    return PT_OK;
+}
+
+extern "C" int pt_test_ao_tables(double* dirs, double* rot) {
+    if (!dirs || !rot) return PT_ERR_ARGUMENT;
+    memcpy(dirs, PT_AO_DIRS, sizeof PT_AO_DIRS);
+    memcpy(rot, PT_AO_ROT, sizeof PT_AO_ROT);
+    return PT_OK;
 }
 
 // ------------------------------------------------------------------------------------------------

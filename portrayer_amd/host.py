@@ -19,7 +19,7 @@ _dp, _ip, _up, _u64p, _u8p = H._dp, H._ip, H._up, H._u64p, H._u8p
 
 EXPORTS = ["ph_last_error", "ph_scene_create", "ph_example_scene", "ph_scene_destroy", "ph_scene_counts", "ph_scene_export", "ph_scene_export_textures",
            "ph_scene_flatten", "ph_scene_kdtree", "ph_camera", "ph_obj_load", "ph_renderer_create", "ph_renderer_destroy",
-           "ph_renderer_context", "ph_renderer_ranks", "ph_renderer_node", "ph_renderer_prepare_ms", "ph_renderer_render", "ph_renderer_aov", "ph_renderer_rays", "ph_renderer_segments", "ph_renderer_radiance", "ph_renderer_film_create", "ph_renderer_film_destroy", "ph_renderer_film_reset", "ph_renderer_film_add", "ph_renderer_film_resolve", "ph_renderer_film_counts", "ph_renderer_film_create_moments", "ph_renderer_film_add_map", "ph_renderer_film_error", "ph_renderer_film_refine", "ph_renderer_film_denoise", "ph_renderer_guides", "ph_renderer_film_denoise_albedo", "ph_renderer_update", "ph_scene_same_structure", "ph_renderer_deform", "ph_scene_same_topology", "ph_renderer_deform_device", "ph_renderer_mesh_count", "ph_renderer_mesh_vertices", "ph_example_render_to_png", "ph_png_read", "ph_png_write", "ph_image_read", "ph_scene_graph"]
+           "ph_renderer_context", "ph_renderer_ranks", "ph_renderer_node", "ph_renderer_prepare_ms", "ph_renderer_render", "ph_renderer_aov", "ph_renderer_rays", "ph_renderer_segments", "ph_renderer_ao", "ph_renderer_ao_camera", "ph_renderer_radiance", "ph_renderer_film_create", "ph_renderer_film_destroy", "ph_renderer_film_reset", "ph_renderer_film_add", "ph_renderer_film_resolve", "ph_renderer_film_counts", "ph_renderer_film_create_moments", "ph_renderer_film_add_map", "ph_renderer_film_error", "ph_renderer_film_refine", "ph_renderer_film_denoise", "ph_renderer_guides", "ph_renderer_film_denoise_albedo", "ph_renderer_update", "ph_scene_same_structure", "ph_renderer_deform", "ph_scene_same_topology", "ph_renderer_deform_device", "ph_renderer_mesh_count", "ph_renderer_mesh_vertices", "ph_example_render_to_png", "ph_png_read", "ph_png_write", "ph_image_read", "ph_scene_graph"]
 
 
 class PortrayerHostError(RuntimeError):
@@ -89,6 +89,10 @@ def lib() -> C.CDLL:
         l.ph_renderer_rays.argtypes = [vp, C.POINTER(H.PtRaysParams), _dp, _dp, C.POINTER(H.PtRaysBuffers), _dp]
         l.ph_renderer_segments.restype = C.c_int
         l.ph_renderer_segments.argtypes = [vp, C.POINTER(H.PtRaysParams), _dp, _dp, _dp, C.POINTER(H.PtRaysBuffers), _dp]
+        l.ph_renderer_ao.restype = C.c_int
+        l.ph_renderer_ao.argtypes = [vp, C.POINTER(H.PtAoParams), _dp, _dp, C.POINTER(H.PtAoBuffers), _dp]
+        l.ph_renderer_ao_camera.restype = C.c_int
+        l.ph_renderer_ao_camera.argtypes = [vp, _dp, C.c_uint32, C.c_uint32, C.POINTER(H.PtAoParams), C.POINTER(H.PtAoBuffers), _dp]
         l.ph_renderer_radiance.restype = C.c_int
         l.ph_renderer_radiance.argtypes = [vp, C.POINTER(H.PtRadianceParams), _dp, _dp, _dp, _dp, _dp]
         l.ph_renderer_film_create.restype = C.c_int; l.ph_renderer_film_create.argtypes = [vp, C.c_uint32, C.c_uint32, C.POINTER(vp)]
@@ -744,6 +748,95 @@ class Renderer:
             _check(lib().ph_renderer_segments(self._h, C.byref(p), _p(o, _dp), _p(d, _dp), _p(tm, _dp), C.byref(b), C.byref(ms)), "ph_renderer_segments")
         out["kernel_ms"] = ms.value
         return out
+
+    @staticmethod
+    def _ao_params(n, samples, radius, bias, seed, pass_index, first_index, eye):
+        """ao()'s and ao_camera()'s argument checks, and the pt_ao_params they describe"""
+        if isinstance(samples, bool) or not isinstance(samples, (int, np.integer)) or int(samples) not in H.AO_SAMPLES:
+            raise ValueError("samples must be one of %r, got %r" % (H.AO_SAMPLES, samples))
+        for name, v, top in (("seed", seed, 1 << 64), ("first_index", first_index, 1 << 64), ("pass_index", pass_index, 1 << 32)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) < top:
+                raise ValueError("%s must be an integer in [0, 2^%d), got %r" % (name, top.bit_length() - 1, v))
+        for name, v in (("radius", radius), ("bias", bias)):
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+                raise ValueError("%s must be a number, got %r" % (name, v))
+        if not float(radius) > 1e-5:  # PT_EPSILON; false for NaN
+            raise ValueError("radius must be greater than EPSILON = 1e-5 (inf is allowed), got %r" % (radius,))
+        if not np.isfinite(float(bias)) or float(bias) < 0.0:
+            raise ValueError("bias must be finite and not negative, got %r" % (bias,))
+        if n > H.AO_MAX:
+            raise ValueError("at most %d points per call" % H.AO_MAX)
+        flags, e = 0, np.zeros(3)
+        if eye is not None:
+            e = np.asarray(eye, dtype=np.float64)
+            if e.shape != (3,) or not np.all(np.isfinite(e)):
+                raise ValueError("eye must be three finite numbers, got %r" % (eye,))
+            flags = H.AO_FACE_EYE
+        return H.PtAoParams(n, int(samples), int(pass_index), int(seed), int(first_index), float(radius), float(bias), flags, (C.c_double * 3)(*e))
+
+    @staticmethod
+    def _ao_buffers(want, into, shape):
+        want = tuple(want)
+        unknown = [n for n in want if n not in H.AO_BUFFERS]
+        if unknown or not want:
+            raise ValueError("want must name some of %s, got %r" % (", ".join(H.AO_BUFFERS), want))
+        out, b = {}, H.PtAoBuffers()
+        for name in want:
+            dtype, comps = H.AO_BUFFERS[name]
+            full = shape if comps == 1 else shape + (comps,)
+            a = into[name] if into is not None and name in into else np.zeros(full, dtype=dtype)
+            if not isinstance(a, np.ndarray) or a.shape != full or a.dtype != dtype or not a.flags.c_contiguous:
+                raise ValueError("into[%r] must be a C-contiguous %s array of shape %r" % (name, np.dtype(dtype).name, full))
+            out[name] = a
+            setattr(b, name, _p(a, {np.uint32: _up, np.uint8: _u8p, np.float64: _dp}[dtype]))
+        return out, b
+
+    @staticmethod
+    def _ao_result(out, samples, ms):
+        if "occluded" in out:
+            out["visibility"] = 1.0 - out["occluded"].astype(np.float64) / float(samples)  # (1.0 at invalid points: they count no occluder)
+        out["kernel_ms"] = ms.value
+        return out
+
+    def ao(self, points, normals, samples: int = 16, radius: float = float("inf"), bias: float = 0.0, seed: int = 0, pass_index: int = 0, first_index: int = 0,
+           eye=None, want=("occluded",), into: Optional[dict] = None) -> dict:
+        """Ambient occlusion at points of the caller's own (pt_ao): `points` and `normals` are (n, 3) float64 in world space - aov()'s position and normal, a
+        baker's texel centres. The device makes `samples` (1, 2, 4 .. 64) cosine-weighted rays per point about its normal, in registers, and counts those that
+        meet something within `radius` (in world units; inf: anywhere); the origin is lifted by `bias` along the normal. `eye` (three numbers) first turns every
+        normal towards that point. Returns the arrays named in `want` - `occluded` (n,) uint32, `valid` (n,) uint8, `bent` (n, 3) float64: the sum of the
+        unoccluded directions, not normalised - with `visibility` = 1 - occluded / samples (float64, computed here) where `occluded` was asked for, and
+        `kernel_ms`. A point with a non-finite component, one beyond 1e18 or a zero normal is invalid: occluded 0, valid 0, bent 0, visibility 1. Point i draws
+        its rotation from the stream (seed, first_index + i, pass_index): a slice [k, k + m) with first_index=k gives that slice of the whole, and another
+        pass_index gives other rays to sum. `into`: a dict of C-contiguous arrays of the right shape and dtype to write into."""
+        P, N = np.asarray(points), np.asarray(normals)
+        if P.ndim != 2 or P.shape[1] != 3 or P.shape != N.shape:
+            raise ValueError("points and normals must both be (n, 3), got %r and %r" % (P.shape, N.shape))
+        if P.dtype != np.float64 or N.dtype != np.float64:
+            raise ValueError("points and normals must be float64, got %s and %s" % (P.dtype, N.dtype))
+        n = P.shape[0]
+        p = self._ao_params(n, samples, radius, bias, seed, pass_index, first_index, eye)
+        out, b = self._ao_buffers(want, into, (n,))
+        P, N = np.ascontiguousarray(P), np.ascontiguousarray(N)
+        ms = C.c_double(0.0)
+        _check(lib().ph_renderer_ao(self._h, C.byref(p), _p(P, _dp), _p(N, _dp), C.byref(b), C.byref(ms)), "ph_renderer_ao")
+        return self._ao_result(out, samples, ms)
+
+    def ao_camera(self, cam10, width: int, height: int, samples: int = 16, radius: float = float("inf"), bias: float = 0.0, seed: int = 0, pass_index: int = 0,
+                  want=("occluded",), into: Optional[dict] = None) -> dict:
+        """Ambient occlusion under every pixel (pt_aov_device then pt_ao_device on the device): the points are what aov() finds at the pixel centres, the normals
+        turned towards the camera's eye, pixel (x, y) the stream index y * width + x - the bits of ao(aov's position, aov's normal, eye=the eye). Nothing per
+        pixel crosses the bus but the results: arrays of shape (H, W) - `bent` (H, W, 3) - as in ao(); pixels that see nothing are invalid points."""
+        for name, v in (("width", width), ("height", height)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or int(v) < 1:
+                raise ValueError("%s must be a positive integer, got %r" % (name, v))
+        p = self._ao_params(int(width) * int(height), samples, radius, bias, seed, pass_index, 0, None)
+        out, b = self._ao_buffers(want, into, (int(height), int(width)))
+        c = np.ascontiguousarray(cam10, dtype=np.float64)
+        if c.shape != (10,):
+            raise ValueError("cam10 must hold 10 numbers, got shape %r" % (c.shape,))
+        ms = C.c_double(0.0)
+        _check(lib().ph_renderer_ao_camera(self._h, _p(c, _dp), int(width), int(height), C.byref(p), C.byref(b), C.byref(ms)), "ph_renderer_ao_camera")
+        return self._ao_result(out, samples, ms)
 
     def radiance(self, origins, directions, background=(0.0, 0.0, 0.0), seed: int = 0, sample: int = 0, stream_base: int = 0, reorder: bool = False,
                  into: Optional[np.ndarray] = None) -> dict:

@@ -15,6 +15,15 @@ struct ph_scene {
 };
 struct ph_renderer {
     std::unique_ptr<detail::Renderer> r;
+    // ph_renderer_ao_camera: position and normal of its primary-visibility pass and the device copies of its three outputs, for ao_points pixels; allocated on
+    // first use, grown with the image, freed with the renderer (before its context goes)
+    void* d_ao[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    uint64_t ao_points = 0;
+    void ao_release() {
+        for (void*& p : d_ao) { if (p) pt_device_free(r->context(), p); p = nullptr; }
+        ao_points = 0;
+    }
+    ~ph_renderer() { if (r) ao_release(); }
 };
 
 static thread_local std::string g_error;
@@ -624,6 +633,63 @@ extern "C" int ph_renderer_segments(ph_renderer* r, const pt_rays_params* p, con
     if (p->n && (!origins || !directions || !t_max)) return bad("null argument");
     return guarded([&]() -> int {
         r->r->segments(*p, origins, directions, t_max, *out, kernel_ms);  // (a renderer spread over a node: rank 0's context, every ray)
+        return PH_OK;
+    });
+}
+
+// Ambient occlusion at points of the caller's own (pt_ao): host buffers in and out.
+extern "C" int ph_renderer_ao(ph_renderer* r, const pt_ao_params* p, const double* positions, const double* normals, const pt_ao_buffers* out, double* kernel_ms) {
+    if (!r || !p || !out) return bad("null argument");
+    if (p->n && (!positions || !normals)) return bad("null argument");
+    if (p->n == 0) { if (kernel_ms) *kernel_ms = 0.0; return PH_OK; }
+    return guarded([&]() -> int {
+        int rc = pt_ao(r->r->context(), p, positions, normals, out, kernel_ms);  // (a renderer spread over a node: rank 0's context, every point)
+        if (rc != PT_OK) { g_error = pt_last_error(r->r->context()); return rc == PT_ERR_ARGUMENT ? PH_ERR_ARGUMENT : PH_ERR_RUNTIME; }
+        return PH_OK;
+    });
+}
+
+// Ambient occlusion under every pixel of a width x height image: pt_aov_device writes position and normal at the pixel centres into device memory kept with the
+// renderer, pt_ao_device behind it on the same stream reads them with PT_AO_FACE_EYE and the camera's eye - point q = y * width + x, so params->n, flags, eye
+// and first_index are set here - and only the results asked for cross the bus.
+extern "C" int ph_renderer_ao_camera(ph_renderer* r, const double camera[10], uint32_t width, uint32_t height, const pt_ao_params* p, const pt_ao_buffers* out, double* kernel_ms) {
+    if (!r || !camera || !p || !out) return bad("null argument");
+    if (width == 0 || height == 0) return bad("width and height must be positive");
+    if ((uint64_t)width * height > PT_AO_MAX) return bad("more than PT_AO_MAX pixels");
+    if (!(out->occluded || out->valid || out->bent)) return bad("no output buffer asked for");
+    return guarded([&]() -> int {
+        pt_context* c = r->r->context();
+        auto fail = [&](int rc) { g_error = pt_last_error(c); return rc == PT_ERR_ARGUMENT ? PH_ERR_ARGUMENT : PH_ERR_RUNTIME; };
+        const uint64_t n = (uint64_t)width * height;
+        const size_t bytes[5] = {n * 24, n * 24, n * 4, n * 1, n * 24};
+        void* host_out[3] = {out->occluded, out->valid, out->bent};
+        int rc = PT_OK;
+        if (r->ao_points < n) {
+            r->ao_release();
+            for (int k = 0; k < 5 && rc == PT_OK; k++) rc = pt_device_alloc(c, bytes[k], &r->d_ao[k]);
+            if (rc != PT_OK) { const int shown = fail(rc); r->ao_release(); return shown; }
+            r->ao_points = n;
+        }
+        pt_camera pc = detail::Camera(camera_from(camera), (double)width, (double)height).to_abi();  // the camera a render of this size gets
+        pt_aov_params ap;
+        ap.width = width; ap.height = height;
+        ap.slice.x0 = 0; ap.slice.y0 = 0; ap.slice.x1 = width - 1; ap.slice.y1 = height - 1;
+        ap.offset[0] = 0.5; ap.offset[1] = 0.5;
+        pt_ao_params q = *p;
+        q.n = n; q.first_index = 0; q.flags = PT_AO_FACE_EYE;
+        for (int k = 0; k < 3; k++) q.eye[k] = pc.eye[k];
+        pt_aov_buffers ab = {nullptr, (double*)r->d_ao[0], (double*)r->d_ao[1], nullptr, nullptr, nullptr};
+        pt_ao_buffers db = {out->occluded ? (uint32_t*)r->d_ao[2] : nullptr, out->valid ? (uint8_t*)r->d_ao[3] : nullptr, out->bent ? (double*)r->d_ao[4] : nullptr};
+        if ((rc = pt_aov_device(c, &pc, &ap, &ab, nullptr))) return fail(rc);
+        rc = pt_ao_device(c, &q, (const double*)r->d_ao[0], (const double*)r->d_ao[1], &db, nullptr);  // the same (default) stream: behind the aov pass
+        if (rc) { const int shown = fail(rc); pt_aov_finish(c, nullptr); return shown; }
+        const int rc_aov = pt_aov_finish(c, nullptr);
+        if (rc_aov) g_error = pt_last_error(c);
+        rc = pt_ao_finish(c, kernel_ms);
+        if (rc_aov) return PH_ERR_RUNTIME;
+        if (rc) return fail(rc);
+        for (int k = 0; k < 3; k++)
+            if (host_out[k] && (rc = pt_copy_from_device(c, host_out[k], r->d_ao[2 + k], bytes[2 + k]))) return fail(rc);
         return PH_OK;
     });
 }

@@ -106,6 +106,16 @@ pub struct PtAovBuffers {                  // pt_aov_buffers: each optional (nul
 pub struct PtGuidesBuffers {               // pt_guides_buffers: each optional (null = not wanted), full image, row-major; albedo width x height x 3 f64, the rest as in pt_aov_buffers
     pub albedo: *mut f64, pub position: *mut f64, pub normal: *mut f64, pub node: *mut i32,
 }
+#[repr(C)]
+pub struct PtAoParams {                    // pt_ao_params: n points; samples 1, 2, 4 .. 64 rays each; point i draws its rotation from the stream (seed, first_index + i, pass)
+    pub n: u64, pub samples: u32, pub pass: u32, pub seed: u64, pub first_index: u64,
+    pub radius: f64, pub bias: f64, pub flags: u32, pub eye: [f64; 3],
+}
+#[repr(C)]
+pub struct PtAoBuffers {                   // pt_ao_buffers: each optional (null = not wanted), n entries; occluded = rays that met something, bent n x 3 = sum of the others' directions
+    pub occluded: *mut u32, pub valid: *mut u8, pub bent: *mut f64,
+}
+pub const PT_AO_FACE_EYE: u32 = 1;         // PtAoParams.flags: turn each normal towards `eye` first
 #[repr(C)] pub struct PtRaysParams { pub n: u64, pub any_hit: i32, pub reorder: i32 }   // pt_rays_params: any_hit 1 = occlusion query, reorder 1 = the device groups like rays first
 #[repr(C)]
 pub struct PtRadianceParams {              // pt_radiance_params: ray i draws from the generator's stream (seed, stream_base + i, sample), draws 2, 3, ...
@@ -185,6 +195,14 @@ extern "C" {
                        host_out: *const PtRaysBuffers, kernel_ms: *mut f64) -> c_int;
     pub fn pt_segments_device(ctx: *mut PtContext, params: *const PtRaysParams, d_origins: *const f64, d_directions: *const f64, d_t_max: *const f64,
                               device_out: *const PtRaysBuffers, hip_stream: *mut c_void) -> c_int;
+    // ambient occlusion at points of the caller's own: n x 3 f64 positions and normals in world space; the device makes each point's rays in registers (a fixed
+    // sequence of f64 operations, pt_ao.h), walks them over [EPSILON, radius) and counts. Shares pt_rays' pass: pt_ao_device is closed by pt_ao_finish, which is
+    // pt_rays_finish; queued behind pt_aov_device on the same stream it reads that pass's position and normal where they are
+    pub fn pt_ao(ctx: *mut PtContext, params: *const PtAoParams, positions: *const f64, normals: *const f64, host_out: *const PtAoBuffers,
+                 kernel_ms: *mut f64) -> c_int;
+    pub fn pt_ao_device(ctx: *mut PtContext, params: *const PtAoParams, d_positions: *const f64, d_normals: *const f64, device_out: *const PtAoBuffers,
+                        hip_stream: *mut c_void) -> c_int;
+    pub fn pt_ao_finish(ctx: *mut PtContext, kernel_ms: *mut f64) -> c_int;
     // radiance along rays of the caller's own (Ray::color as a batch): background 3 f64 or n x 3 (background_per_ray), rgb n x 3 f64, one linear sample per ray
     pub fn pt_radiance(ctx: *mut PtContext, params: *const PtRadianceParams, origins: *const f64, directions: *const f64, background: *const f64, rgb: *mut f64,
                        kernel_ms: *mut f64) -> c_int;
