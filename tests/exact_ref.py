@@ -459,6 +459,7 @@ class ExactScene:
     def __init__(self, scene, flat_trans, prim_type=None):
         def build(n):
             return _Node(list(n.ops), None if n.geometry is None else _Geometry(n.geometry[0]), [build(c) for c in n.children])
+        self.scene = scene   # its materials, lights and ambient colour are read by exact_shade
         self.root = build(scene.root)
         self.flat = []
         queue = deque([self.root])
