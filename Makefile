@@ -37,6 +37,7 @@ HIP_OBJS := $(OBJDIR)/pt_api.o $(OBJDIR)/pt_build.o $(OBJDIR)/pt_node.o $(foreac
             $(foreach m,$(RENDER_MODES),$(OBJDIR)/pt_radiance_m$(m).o) \
             $(foreach m,$(RENDER_MODES),$(OBJDIR)/pt_segments_m$(m).o) \
             $(foreach m,$(RENDER_MODES),$(OBJDIR)/pt_ao_m$(m).o) \
+            $(foreach m,$(RENDER_MODES),$(OBJDIR)/pt_gather_m$(m).o) \
             $(OBJDIR)/pt_film.o $(foreach m,$(RENDER_MODES),$(OBJDIR)/pt_film_m$(m).o) \
             $(OBJDIR)/pt_film_map.o $(foreach m,$(RENDER_MODES),$(OBJDIR)/pt_film_map_m$(m).o) \
             $(OBJDIR)/pt_denoise.o $(OBJDIR)/pt_denoise_albedo.o
@@ -73,10 +74,11 @@ $(OBJDIR)/%.o: $(CSRC)/%.hip $(HIP_HDRS) tools/check_exec_prologue.py
 #   segments  the bounded-segment ray queries (pt_segments.h): pt_rays_kernel with a t_max per ray, and the one unit whose walks start at that bound (PT_WALK_ENTRY_T)
 #   ao        the ambient-occlusion pass (pt_ao_inst.hip): a point's rays made in registers (pt_ao.h), pt_segments' walks, both work layouts per mode
 #   radiance  the radiance pass (pt_radiance.h): the interpreter over the caller's rays, <TEX, PARK> instantiations per mode
+#   gather    the gather pass (pt_gather.h): the same interpreter over the ambient-occlusion contract's rays, made in registers (pt_ao.h), summed per point; <TEX, PARK> per mode
 #   film      the film's sampling kernel (pt_film.h): the same interpreter with the camera as its source; its fold and resolve kernels (pt_film.hip): the %.o rule
 #   film_map  the film's per-pixel budget (pt_film_map.h): the sampling kernel over a list of samples; its plan, fold, error and budget kernels (pt_film_map.hip): the %.o rule
 # Static pattern rules, each over its own nine objects: as a plain pattern, pt_film_m%.o would match pt_film_map.o and pt_film_map_m1.o too.
-PASSES := render aov guides rays segments ao radiance film film_map
+PASSES := render aov guides rays segments ao radiance gather film film_map
 define mode_rule
 $(foreach m,$(RENDER_MODES),$(OBJDIR)/pt_$(1)_m$(m).o): $(OBJDIR)/pt_$(1)_m%.o: $(CSRC)/pt_$(1)_inst.hip $(HIP_HDRS) tools/check_exec_prologue.py
 	$$(call hip_four_steps,-DPT_INST_MODE=$$*)

@@ -519,6 +519,53 @@ int pt_radiance(pt_context *ctx, const pt_radiance_params *params, const double 
 int pt_radiance_device(pt_context *ctx, const pt_radiance_params *params, const double *d_origins, const double *d_directions, const double *d_background, double *d_rgb, void *hip_stream);
 int pt_radiance_finish(pt_context *ctx, double *kernel_ms);
 
+/* ---- Gather: the light that arrives at a point from the hemisphere above it - sky and one bounce of everything pt_render shades - as the SUM of `samples`
+ * shaded radiance samples along the ambient-occlusion pass's rays. pt_ao can only count what a point's rays meet, pt_radiance shades rays the caller has to make
+ * and ship (48 bytes per ray up, 24 down); this pass joins them on the device: POINTS in - n positions and n normals, n x 3 f64 in world space, what pt_aov
+ * writes per pixel or a baker's texel centres - and per point one sum out. No ray and no per-ray colour is ever in memory: 48 bytes per point in, at most 25 out.
+ * The result is defined, to the bit, by the two contracts that exist. Point i has the stream index q = first_index + i, S = samples, and in this order:
+ *   1. - 8.       pt_ao's steps 1 to 8, unchanged and computed by the same functions (portrayer_amd/csrc/pt_ao.h; pt_test_ao_rays_host replays them): valid, face
+ *                 eye, normalise, rotation from rng(seed, q, pass, draw 0), local direction from PT_AO_DIRS[k] and PT_AO_ROT[j], frame, direction d_k, origin
+ *                 o_k = P + n bias. There is no radius: a gather ray is unbounded, as a radiance ray is.
+ *   9. radiance   rgb_k = what pt_radiance answers for the ray (o_k, d_k) with `background` (3 doubles, the sky: what a ray that leaves the scene brings back), the
+ *                 generator's stream (seed, q * S + k, sample = pass), draws 2, 3, ... - that definition taken over whole: textures and normal maps, area lights,
+ *                 glossy draws, reflection and refraction to depth 10, and its rule that a ray which is NOT TRACED (a component beyond 1e18 or not finite - a
+ *                 huge bias can do that to an origin) reports the background. q * S + k is a 64-bit product, reduced modulo 2^64 only.
+ * Outputs per point, each OPTIONAL (NULL = not wanted), at least one:
+ *   sum    n x 3  f64  starting from (0, 0, 0), rgb_k added per channel in ascending k, left to right. The mean is sum / S; the directions are cosine-weighted, so
+ *                      the irradiance estimate is pi x the mean.
+ *   valid  n      u8   step 1
+ * An INVALID point traces nothing, occupies no lane of a walk and reports sum = (0, 0, 0), valid = 0 - so pt_aov's miss pixels are invalid points.
+ * Consequences: the bits do not depend on how a batch is cut - a slice [k, k + m) submitted with first_index + k equals that slice of the whole - nor on which
+ * rays share a wavefront; and the pass equals pt_radiance on pt_test_ao_rays_host's rays (same seed, pass, first_index, bias, flags, eye; any radius), flattened
+ * point-major, with stream_base = first_index * S and sample = pass, summed in that order. Another `pass` gives other rays and other draws: a caller sums passes.
+ * The pass runs on the RADIANCE pass object and its work buffers, as a film's add does: pt_gather_device is closed by pt_gather_finish, which is
+ * pt_radiance_finish, and while a pt_radiance_device / pt_film_add_device / pt_film_add_map_device / pt_gather_device pass is open a second one of any kind
+ * is PT_ERR_ARGUMENT. Renders on the context's two slots, a pt_aov_device pass and a pt_rays_device pass are not disturbed.
+ * Errors, before the first HIP call: PT_ERR_ARGUMENT (a NULL context / params / positions / normals / background / buffers; no buffer asked for; n > PT_AO_MAX;
+ * samples not a power of two <= 64; bias negative or not finite; flags other than PT_AO_FACE_EYE; PT_AO_FACE_EYE with a non-finite eye), PT_ERR_NO_SCENE.
+ * n = 0 is PT_OK: nothing is launched or written. During the pass: PT_ERR_TRAVERSAL as for a render. */
+typedef struct {
+    uint64_t n;             /* points, <= PT_AO_MAX                                          */
+    uint32_t samples;       /* rays per point: 1, 2, 4, 8, 16, 32 or 64                      */
+    uint32_t pass;          /* which rotation a point draws, and the `sample` of its streams */
+    uint64_t seed;
+    uint64_t first_index;   /* stream index of point 0                                       */
+    double bias;            /* finite, >= 0: the origin is lifted by bias along the normal   */
+    uint32_t flags;         /* 0 or PT_AO_FACE_EYE                                           */
+    double eye[3];          /* read with PT_AO_FACE_EYE only                                 */
+} pt_gather_params;
+typedef struct { double *sum; uint8_t *valid; } pt_gather_buffers;
+/* Host buffers, synchronous: uploads the points, copies back the buffers asked for. kernel_ms (optional): device time of the pass (HIP events). */
+int pt_gather(pt_context *ctx, const pt_gather_params *params, const double *positions, const double *normals, const double *background,
+              const pt_gather_buffers *host_out, double *kernel_ms);
+/* The same with points and results in DEVICE memory, queued on `hip_stream` (a hipStream_t, or NULL for the default stream) without synchronising the host -
+ * behind a pt_aov_device on the same stream it reads that pass's position and normal, and nothing per pixel crosses the bus but the results. `background` stays
+ * a HOST pointer to 3 doubles: it is read during the call and travels in the kernel's argument block. */
+int pt_gather_device(pt_context *ctx, const pt_gather_params *params, const double *d_positions, const double *d_normals, const double *background,
+                     const pt_gather_buffers *device_out, void *hip_stream);
+int pt_gather_finish(pt_context *ctx, double *kernel_ms);
+
 /* ---- Film: a width x height accumulator in DEVICE memory that belongs to a context - a preview that sharpens, a render that can stop when it is good enough,
  * more samples where the image is noisy. Per pixel: `total` (3 f64, the sum of its complete 8-sample chunks), `partial` (3 f64, the sum of the open chunk) and
  * `count` (u32, samples taken so far): 52 bytes, nothing per sample.

@@ -168,6 +168,19 @@ int ph_renderer_ao(ph_renderer *r, const pt_ao_params *params, const double *pos
 int ph_renderer_ao_camera(ph_renderer *r, const double camera[10], uint32_t width, uint32_t height, const pt_ao_params *params, const pt_ao_buffers *out,
                           double *kernel_ms);
 
+/* Gathered radiance at points of the caller's own (see pt_gather): n x 3 f64 positions and normals in world space, `background` 3 doubles, host buffers out,
+ * each optional: per point the sum of `samples` shaded samples along the ambient-occlusion pass's rays. A renderer spread over a node runs the pass on rank 0's
+ * context. n = 0 is PH_OK. */
+int ph_renderer_gather(ph_renderer *r, const pt_gather_params *params, const double *positions, const double *normals, const double *background,
+                       const pt_gather_buffers *out, double *kernel_ms);
+/* Gathered radiance under every pixel of a width x height image, through the camera a render of that size would use, built like ph_renderer_ao_camera: a
+ * primary-visibility pass at the pixel centres writes position and normal into device memory kept with the renderer, and pt_gather_device reads them there on
+ * the same stream with PT_AO_FACE_EYE and the camera's eye; point q = y * width + x. Of `params` samples, pass, seed and bias are read (n, first_index, flags
+ * and eye are set here). Host buffers out, width x height entries each, each optional: nothing per pixel crosses the bus but the results. kernel_ms: the gather
+ * pass's. */
+int ph_renderer_gather_camera(ph_renderer *r, const double camera[10], uint32_t width, uint32_t height, const pt_gather_params *params, const double *background,
+                              const pt_gather_buffers *out, double *kernel_ms);
+
 /* Radiance along rays of the caller's own (see pt_radiance): n x 3 f64 origins and directions in world space, `background` 3 doubles or n x 3
  * (params->background_per_ray), rgb n x 3 f64 out: one linear sample of Ray::color per ray. A renderer spread over a node runs the pass on rank 0's context. */
 int ph_renderer_radiance(ph_renderer *r, const pt_radiance_params *params, const double *origins, const double *directions, const double *background, double *rgb,

@@ -147,6 +147,22 @@ AO_MAX = RAYS_MAX // 64  # PT_AO_MAX
 AO_SAMPLES = (1, 2, 4, 8, 16, 32, 64)
 
 
+class PtGatherParams(C.Structure):
+    """pt_gather_params: the points of one gather call and what fixes their rays and draws - samples per point, pass, seed, first_index, bias, and with
+    AO_FACE_EYE the eye every normal is first turned towards. pt_ao_params without the radius: a gather ray is unbounded."""
+    _fields_ = [("n", C.c_uint64), ("samples", C.c_uint32), ("pass_index", C.c_uint32), ("seed", C.c_uint64), ("first_index", C.c_uint64), ("bias", C.c_double),
+                ("flags", C.c_uint32), ("eye", C.c_double * 3)]
+
+
+class PtGatherBuffers(C.Structure):
+    """pt_gather_buffers: sum (n, 3) f64, valid (n,) u8; each optional."""
+    _fields_ = [("sum", _dp), ("valid", _u8p)]
+
+
+# pt_gather's outputs in the order of pt_gather_buffers: name -> (numpy dtype, components per point)
+GATHER_BUFFERS = {"sum": (np.float64, 3), "valid": (np.uint8, 1)}
+
+
 class PtRadianceParams(C.Structure):
     _fields_ = [("n", C.c_uint64), ("reorder", C.c_int32), ("background_per_ray", C.c_int32), ("seed", C.c_uint64), ("stream_base", C.c_uint64), ("sample", C.c_uint32)]
 
@@ -211,7 +227,8 @@ EXPORTS = ["pt_abi_version", "pt_device_count", "pt_context_create", "pt_context
            "pt_test_film_moments_host", "pt_test_film_plan_host", "pt_test_film_plan",
            "pt_film_denoise", "pt_film_denoise_device", "pt_test_denoise_host",
            "pt_guides", "pt_guides_device", "pt_guides_finish", "pt_film_denoise_albedo", "pt_film_denoise_albedo_device", "pt_test_denoise_albedo_host",
-           "pt_ao", "pt_ao_device", "pt_ao_finish", "pt_test_ao_rays_host", "pt_test_ao_tables"]
+           "pt_ao", "pt_ao_device", "pt_ao_finish", "pt_test_ao_rays_host", "pt_test_ao_tables",
+           "pt_gather", "pt_gather_device", "pt_gather_finish"]
 
 
 def header_functions():
@@ -378,6 +395,12 @@ def lib() -> C.CDLL:
         l.pt_test_ao_rays_host.argtypes = [C.c_uint64, C.POINTER(PtAoParams), _dp, _dp, _dp, _dp, _u8p]
         l.pt_test_ao_tables.restype = C.c_int
         l.pt_test_ao_tables.argtypes = [_dp, _dp]
+        l.pt_gather.restype = C.c_int
+        l.pt_gather.argtypes = [C.c_void_p, C.POINTER(PtGatherParams), _dp, _dp, _dp, C.POINTER(PtGatherBuffers), _dp]
+        l.pt_gather_device.restype = C.c_int
+        l.pt_gather_device.argtypes = [C.c_void_p, C.POINTER(PtGatherParams), C.c_void_p, C.c_void_p, _dp, C.POINTER(PtGatherBuffers), C.c_void_p]
+        l.pt_gather_finish.restype = C.c_int
+        l.pt_gather_finish.argtypes = [C.c_void_p, _dp]
         l.pt_radiance.restype = C.c_int
         l.pt_radiance.argtypes = [C.c_void_p, C.POINTER(PtRadianceParams), _dp, _dp, _dp, _dp, _dp]
         l.pt_radiance_device.restype = C.c_int

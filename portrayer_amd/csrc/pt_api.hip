@@ -21,6 +21,7 @@
 #include "pt_segments_inst.h"
 #include "pt_ao_inst.h"
 #include "pt_radiance_inst.h"
+#include "pt_gather_inst.h"
 #include "pt_film_inst.h"
 #include "pt_film_map_inst.h"
 #include "pt_denoise.h"
@@ -3054,6 +3055,95 @@ extern "C" int pt_radiance_finish(pt_context* c, double* kernel_ms) {
     if (!c->radiance.pass.pending) c->film_open = nullptr;  // (a film's pass is closed here too)
     return rc;
 }
+
+// ------------------------------------------------------------------------------------------------
+// Gather (pt_gather.h): the ambient-occlusion contract's rays, shaded and summed per point; a radiance pass for bookkeeping, on that pass's PtPass
+// ------------------------------------------------------------------------------------------------
+static hipError_t pt_gather_dispatch(const PtGatherArgs& a, bool tex, bool park, int n_cu, hipStream_t stream, uint32_t* grid, bool launch) {
+    PT_MODE_LAUNCH(pt_gather_launch_mode_, a.r.scene.mode, a, tex, park, n_cu, stream, grid, launch)
+}
+
+// Everything that can be refused without a HIP call, in the order the header gives. (pt_fail takes a NULL context.)
+static int pt_gather_check(pt_context* c, const pt_gather_params* p, const double* positions, const double* normals, const double* background, const pt_gather_buffers* out) {
+    if (!c || !p || !positions || !normals || !background || !out)
+        return pt_fail(c, PT_ERR_ARGUMENT, "pt_gather: NULL context, params, positions, normals, background or buffers");
+    if (!(out->sum || out->valid)) return pt_fail(c, PT_ERR_ARGUMENT, "pt_gather: no output buffer asked for");
+    if (p->n > PT_AO_MAX) return pt_fail(c, PT_ERR_ARGUMENT, "pt_gather: more than PT_AO_MAX points in one call");
+    if (p->samples == 0 || p->samples > 64 || (p->samples & (p->samples - 1)) != 0) return pt_fail(c, PT_ERR_ARGUMENT, "pt_gather: samples must be a power of two, 1 .. 64");
+    if (!std::isfinite(p->bias) || p->bias < 0.0) return pt_fail(c, PT_ERR_ARGUMENT, "pt_gather: bias must be finite and not negative");
+    if (p->flags & ~PT_AO_FACE_EYE) return pt_fail(c, PT_ERR_ARGUMENT, "pt_gather: unknown flags");
+    if ((p->flags & PT_AO_FACE_EYE) && !(std::isfinite(p->eye[0]) && std::isfinite(p->eye[1]) && std::isfinite(p->eye[2])))
+        return pt_fail(c, PT_ERR_ARGUMENT, "pt_gather: PT_AO_FACE_EYE needs a finite eye");
+    if (!c->have_scene) return pt_fail(c, PT_ERR_NO_SCENE, "no scene uploaded");
+    if (c->radiance.pass.pending) return pt_fail(c, PT_ERR_ARGUMENT, "a pt_radiance_device / pt_film_add_device / pt_gather_device pass is in flight: pt_radiance_finish first");
+    return PT_OK;
+}
+
+// Queues the pass on `stream` (pt_pass_open ... pt_pass_seal) as pt_radiance_common does and on its PtPass. The point and result pointers are DEVICE pointers,
+// `background` is the caller's HOST colour, copied into the argument block; n > 0. LDS per block as a render's interpreter kernel has it (pt_interp_sizing).
+static int pt_gather_common(pt_context* c, const pt_gather_params* p, const double* d_positions, const double* d_normals, const double* background, const pt_gather_buffers& out,
+                            hipStream_t stream) {
+    PtPass& v = c->radiance.pass;
+    int rc = pt_pass_prepare(c, v);
+    if (rc) return rc;
+    PtGatherArgs a;
+    memset(&a, 0, sizeof a);  // (no occluder table, no counters, no work counter: null)
+    a.r.scene = c->view;
+    a.r.seed = p->seed;
+    a.n = p->n; a.positions = d_positions; a.normals = d_normals;
+    // what steps 1 to 8 read (pt_ao_set: the eye only with PT_AO_FACE_EYE)
+    a.set.seed = p->seed; a.set.first_index = p->first_index; a.set.pass = p->pass; a.set.flags = p->flags; a.set.bias = p->bias;
+    a.set.eye = (p->flags & PT_AO_FACE_EYE) ? pt_v3(p->eye[0], p->eye[1], p->eye[2]) : pt_v3(0.0, 0.0, 0.0);
+    a.samples = p->samples;
+    while ((1u << a.log2_samples) < p->samples) a.log2_samples++;
+    for (int k = 0; k < 3; k++) a.background[k] = background[k];
+    a.sum = out.sum; a.valid = out.valid;
+    const uint64_t per_item = 64u >> a.log2_samples;              // points of a wavefront
+    a.r.n_items = (uint32_t)((p->n + per_item - 1) / per_item);  // (n <= PT_AO_MAX = 2^24: at most 2^24 items)
+    const PtInterp k = pt_interp_sizing(c, a.r);
+    uint32_t grid = 0;
+    PT_HIP(c, pt_gather_dispatch(a, k.tex, k.park, c->n_cu, stream, &grid, false));
+    if ((rc = pt_pass_open(c, v, a.r, grid, true, stream))) return rc;
+    PT_HIP(c, pt_gather_dispatch(a, k.tex, k.park, c->n_cu, stream, &grid, true));
+    return pt_pass_seal(c, v);
+}
+
+extern "C" int pt_gather(pt_context* c, const pt_gather_params* p, const double* positions, const double* normals, const double* background, const pt_gather_buffers* host_out,
+                         double* kernel_ms) {
+    int rc = pt_gather_check(c, p, positions, normals, background, host_out);
+    if (rc) return rc;
+    if (kernel_ms) *kernel_ms = 0.0;
+    if (p->n == 0) return PT_OK;
+    PT_HIP(c, hipSetDevice(c->device));
+    pt_context::Radiance& v = c->radiance;
+    const size_t n = (size_t)p->n;
+    // the radiance pass's device copies: positions and normals where it keeps origins and directions, the sums in its output, the flags where its background goes
+    if ((rc = pt_reserve(c, v.in[0], n * 24)) || (rc = pt_reserve(c, v.in[1], n * 24))) return rc;
+    if (host_out->sum && (rc = pt_reserve(c, v.out, n * 24))) return rc;
+    if (host_out->valid && (rc = pt_reserve(c, v.in[2], n))) return rc;
+    PT_HIP(c, hipMemcpy(v.in[0].p, positions, n * 24, hipMemcpyHostToDevice));
+    PT_HIP(c, hipMemcpy(v.in[1].p, normals, n * 24, hipMemcpyHostToDevice));
+    pt_gather_buffers d_out;
+    d_out.sum = host_out->sum ? (double*)v.out.p : nullptr;
+    d_out.valid = host_out->valid ? (uint8_t*)v.in[2].p : nullptr;
+    rc = pt_gather_common(c, p, (const double*)v.in[0].p, (const double*)v.in[1].p, background, d_out, nullptr);
+    if ((rc = pt_pass_settle(c, v.pass, rc))) return rc;
+    if (host_out->sum) PT_HIP(c, hipMemcpy(host_out->sum, d_out.sum, n * 24, hipMemcpyDeviceToHost));
+    if (host_out->valid) PT_HIP(c, hipMemcpy(host_out->valid, d_out.valid, n, hipMemcpyDeviceToHost));
+    return pt_pass_result(c, v.pass, kernel_ms);
+}
+
+extern "C" int pt_gather_device(pt_context* c, const pt_gather_params* p, const double* d_positions, const double* d_normals, const double* background,
+                                const pt_gather_buffers* device_out, void* hip_stream) {
+    int rc = pt_gather_check(c, p, d_positions, d_normals, background, device_out);
+    if (rc) return rc;
+    if (p->n == 0) return PT_OK;  // nothing queued, nothing to finish
+    PT_HIP(c, hipSetDevice(c->device));
+    return pt_pass_device_tail(c, c->radiance.pass, pt_gather_common(c, p, d_positions, d_normals, background, *device_out, (hipStream_t)hip_stream));
+}
+
+// The pass is the radiance pass's: one function closes either.
+extern "C" int pt_gather_finish(pt_context* c, double* kernel_ms) { return pt_radiance_finish(c, kernel_ms); }
 
 // ------------------------------------------------------------------------------------------------
 // Film: samples accumulate on the device (pt_film.h, pt_film.hip)

@@ -19,7 +19,7 @@ _dp, _ip, _up, _u64p, _u8p = H._dp, H._ip, H._up, H._u64p, H._u8p
 
 EXPORTS = ["ph_last_error", "ph_scene_create", "ph_example_scene", "ph_scene_destroy", "ph_scene_counts", "ph_scene_export", "ph_scene_export_textures",
            "ph_scene_flatten", "ph_scene_kdtree", "ph_camera", "ph_obj_load", "ph_renderer_create", "ph_renderer_destroy",
-           "ph_renderer_context", "ph_renderer_ranks", "ph_renderer_node", "ph_renderer_prepare_ms", "ph_renderer_render", "ph_renderer_aov", "ph_renderer_rays", "ph_renderer_segments", "ph_renderer_ao", "ph_renderer_ao_camera", "ph_renderer_radiance", "ph_renderer_film_create", "ph_renderer_film_destroy", "ph_renderer_film_reset", "ph_renderer_film_add", "ph_renderer_film_resolve", "ph_renderer_film_counts", "ph_renderer_film_create_moments", "ph_renderer_film_add_map", "ph_renderer_film_error", "ph_renderer_film_refine", "ph_renderer_film_denoise", "ph_renderer_guides", "ph_renderer_film_denoise_albedo", "ph_renderer_update", "ph_scene_same_structure", "ph_renderer_deform", "ph_scene_same_topology", "ph_renderer_deform_device", "ph_renderer_mesh_count", "ph_renderer_mesh_vertices", "ph_example_render_to_png", "ph_png_read", "ph_png_write", "ph_image_read", "ph_scene_graph"]
+           "ph_renderer_context", "ph_renderer_ranks", "ph_renderer_node", "ph_renderer_prepare_ms", "ph_renderer_render", "ph_renderer_aov", "ph_renderer_rays", "ph_renderer_segments", "ph_renderer_ao", "ph_renderer_ao_camera", "ph_renderer_gather", "ph_renderer_gather_camera", "ph_renderer_radiance", "ph_renderer_film_create", "ph_renderer_film_destroy", "ph_renderer_film_reset", "ph_renderer_film_add", "ph_renderer_film_resolve", "ph_renderer_film_counts", "ph_renderer_film_create_moments", "ph_renderer_film_add_map", "ph_renderer_film_error", "ph_renderer_film_refine", "ph_renderer_film_denoise", "ph_renderer_guides", "ph_renderer_film_denoise_albedo", "ph_renderer_update", "ph_scene_same_structure", "ph_renderer_deform", "ph_scene_same_topology", "ph_renderer_deform_device", "ph_renderer_mesh_count", "ph_renderer_mesh_vertices", "ph_example_render_to_png", "ph_png_read", "ph_png_write", "ph_image_read", "ph_scene_graph"]
 
 
 class PortrayerHostError(RuntimeError):
@@ -93,6 +93,10 @@ def lib() -> C.CDLL:
         l.ph_renderer_ao.argtypes = [vp, C.POINTER(H.PtAoParams), _dp, _dp, C.POINTER(H.PtAoBuffers), _dp]
         l.ph_renderer_ao_camera.restype = C.c_int
         l.ph_renderer_ao_camera.argtypes = [vp, _dp, C.c_uint32, C.c_uint32, C.POINTER(H.PtAoParams), C.POINTER(H.PtAoBuffers), _dp]
+        l.ph_renderer_gather.restype = C.c_int
+        l.ph_renderer_gather.argtypes = [vp, C.POINTER(H.PtGatherParams), _dp, _dp, _dp, C.POINTER(H.PtGatherBuffers), _dp]
+        l.ph_renderer_gather_camera.restype = C.c_int
+        l.ph_renderer_gather_camera.argtypes = [vp, _dp, C.c_uint32, C.c_uint32, C.POINTER(H.PtGatherParams), _dp, C.POINTER(H.PtGatherBuffers), _dp]
         l.ph_renderer_radiance.restype = C.c_int
         l.ph_renderer_radiance.argtypes = [vp, C.POINTER(H.PtRadianceParams), _dp, _dp, _dp, _dp, _dp]
         l.ph_renderer_film_create.restype = C.c_int; l.ph_renderer_film_create.argtypes = [vp, C.c_uint32, C.c_uint32, C.POINTER(vp)]
@@ -837,6 +841,81 @@ class Renderer:
         ms = C.c_double(0.0)
         _check(lib().ph_renderer_ao_camera(self._h, _p(c, _dp), int(width), int(height), C.byref(p), C.byref(b), C.byref(ms)), "ph_renderer_ao_camera")
         return self._ao_result(out, samples, ms)
+
+    @staticmethod
+    def _gather_params(n, background, samples, bias, seed, pass_index, first_index, eye):
+        """gather()'s and gather_camera()'s argument checks: the pt_gather_params they describe and the background as three doubles"""
+        a = Renderer._ao_params(n, samples, float("inf"), bias, seed, pass_index, first_index, eye)  # (the same checks; a gather ray has no radius)
+        bg = np.ascontiguousarray(background, dtype=np.float64)
+        if bg.shape != (3,):
+            raise ValueError("background must be 3 numbers, got shape %r" % (bg.shape,))
+        return H.PtGatherParams(a.n, a.samples, a.pass_index, a.seed, a.first_index, a.bias, a.flags, a.eye), bg
+
+    @staticmethod
+    def _gather_buffers(want, into, shape):
+        want = tuple(want)
+        unknown = [n for n in want if n not in H.GATHER_BUFFERS]
+        if unknown or not want:
+            raise ValueError("want must name some of %s, got %r" % (", ".join(H.GATHER_BUFFERS), want))
+        out, b = {}, H.PtGatherBuffers()
+        for name in want:
+            dtype, comps = H.GATHER_BUFFERS[name]
+            full = shape if comps == 1 else shape + (comps,)
+            a = into[name] if into is not None and name in into else np.zeros(full, dtype=dtype)
+            if not isinstance(a, np.ndarray) or a.shape != full or a.dtype != dtype or not a.flags.c_contiguous:
+                raise ValueError("into[%r] must be a C-contiguous %s array of shape %r" % (name, np.dtype(dtype).name, full))
+            out[name] = a
+            setattr(b, name, _p(a, {np.uint8: _u8p, np.float64: _dp}[dtype]))
+        return out, b
+
+    @staticmethod
+    def _gather_result(out, samples, ms):
+        if "sum" in out:
+            out["mean"] = out["sum"] / float(samples)  # (zeros at invalid points)
+        out["kernel_ms"] = ms.value
+        return out
+
+    def gather(self, points, normals, background=(0.0, 0.0, 0.0), samples: int = 16, bias: float = 0.0, seed: int = 0, pass_index: int = 0, first_index: int = 0,
+               eye=None, want=("sum",), into: Optional[dict] = None) -> dict:
+        """Gathered radiance at points of the caller's own (pt_gather): `points` and `normals` are (n, 3) float64 in world space - aov()'s position and normal, a
+        baker's texel centres. The device makes ao()'s `samples` (1, 2, 4 .. 64) cosine-weighted rays per point about its normal, in registers, shades each as
+        radiance() would - everything render() shades, `background` (three numbers, the sky) for a ray that leaves the scene - and sums them per point; no ray and
+        no per-ray colour is ever in memory. The origin is lifted by `bias` along the normal; `eye` (three numbers) first turns every normal towards that point.
+        Returns the arrays named in `want` - `sum` (n, 3) float64: the samples added in order, `valid` (n,) uint8 - with `mean` = sum / samples (computed here)
+        where `sum` was asked for, and `kernel_ms`. The directions are cosine-weighted, so the irradiance estimate at a point is pi x mean. A point with a
+        non-finite component, one beyond 1e18 or a zero normal is invalid: sum 0, valid 0. The bits are those of radiance() on ao()'s rays, flattened point-major,
+        with stream_base = first_index * samples and sample = pass_index, summed in order: a slice [k, k + m) with first_index=k gives that slice of the whole, and
+        another pass_index gives other rays and draws to sum. `into`: a dict of C-contiguous arrays of the right shape and dtype to write into."""
+        P, N = np.asarray(points), np.asarray(normals)
+        if P.ndim != 2 or P.shape[1] != 3 or P.shape != N.shape:
+            raise ValueError("points and normals must both be (n, 3), got %r and %r" % (P.shape, N.shape))
+        if P.dtype != np.float64 or N.dtype != np.float64:
+            raise ValueError("points and normals must be float64, got %s and %s" % (P.dtype, N.dtype))
+        n = P.shape[0]
+        p, bg = self._gather_params(n, background, samples, bias, seed, pass_index, first_index, eye)
+        out, b = self._gather_buffers(want, into, (n,))
+        P, N = np.ascontiguousarray(P), np.ascontiguousarray(N)
+        ms = C.c_double(0.0)
+        _check(lib().ph_renderer_gather(self._h, C.byref(p), _p(P, _dp), _p(N, _dp), _p(bg, _dp), C.byref(b), C.byref(ms)), "ph_renderer_gather")
+        return self._gather_result(out, samples, ms)
+
+    def gather_camera(self, cam10, width: int, height: int, background=(0.0, 0.0, 0.0), samples: int = 16, bias: float = 0.0, seed: int = 0, pass_index: int = 0,
+                      want=("sum",), into: Optional[dict] = None) -> dict:
+        """Gathered radiance under every pixel (pt_aov_device then pt_gather_device on the device): the points are what aov() finds at the pixel centres, the
+        normals turned towards the camera's eye, pixel (x, y) the stream index y * width + x - the bits of gather(aov's position, aov's normal, eye=the eye).
+        Nothing per pixel crosses the bus but the results: `sum` and `mean` (H, W, 3), `valid` (H, W), as in gather(); the irradiance estimate is pi x mean;
+        pixels that see nothing are invalid points."""
+        for name, v in (("width", width), ("height", height)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or int(v) < 1:
+                raise ValueError("%s must be a positive integer, got %r" % (name, v))
+        p, bg = self._gather_params(int(width) * int(height), background, samples, bias, seed, pass_index, 0, None)
+        out, b = self._gather_buffers(want, into, (int(height), int(width)))
+        c = np.ascontiguousarray(cam10, dtype=np.float64)
+        if c.shape != (10,):
+            raise ValueError("cam10 must hold 10 numbers, got shape %r" % (c.shape,))
+        ms = C.c_double(0.0)
+        _check(lib().ph_renderer_gather_camera(self._h, _p(c, _dp), int(width), int(height), C.byref(p), _p(bg, _dp), C.byref(b), C.byref(ms)), "ph_renderer_gather_camera")
+        return self._gather_result(out, samples, ms)
 
     def radiance(self, origins, directions, background=(0.0, 0.0, 0.0), seed: int = 0, sample: int = 0, stream_base: int = 0, reorder: bool = False,
                  into: Optional[np.ndarray] = None) -> dict:

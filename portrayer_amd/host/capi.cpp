@@ -16,7 +16,7 @@ struct ph_scene {
 struct ph_renderer {
     std::unique_ptr<detail::Renderer> r;
     // ph_renderer_ao_camera: position and normal of its primary-visibility pass and the device copies of its three outputs, for ao_points pixels; allocated on
-    // first use, grown with the image, freed with the renderer (before its context goes)
+    // first use, grown with the image, freed with the renderer (before its context goes). ph_renderer_gather_camera uses the same five (its sums in the fifth)
     void* d_ao[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     uint64_t ao_points = 0;
     void ao_release() {
@@ -690,6 +690,64 @@ extern "C" int ph_renderer_ao_camera(ph_renderer* r, const double camera[10], ui
         if (rc) return fail(rc);
         for (int k = 0; k < 3; k++)
             if (host_out[k] && (rc = pt_copy_from_device(c, host_out[k], r->d_ao[2 + k], bytes[2 + k]))) return fail(rc);
+        return PH_OK;
+    });
+}
+
+// Gathered radiance at points of the caller's own (pt_gather): host buffers in and out.
+extern "C" int ph_renderer_gather(ph_renderer* r, const pt_gather_params* p, const double* positions, const double* normals, const double* background,
+                                  const pt_gather_buffers* out, double* kernel_ms) {
+    if (!r || !p || !background || !out) return bad("null argument");
+    if (p->n && (!positions || !normals)) return bad("null argument");
+    if (p->n == 0) { if (kernel_ms) *kernel_ms = 0.0; return PH_OK; }
+    return guarded([&]() -> int {
+        int rc = pt_gather(r->r->context(), p, positions, normals, background, out, kernel_ms);  // (a renderer spread over a node: rank 0's context, every point)
+        if (rc != PT_OK) { g_error = pt_last_error(r->r->context()); return rc == PT_ERR_ARGUMENT ? PH_ERR_ARGUMENT : PH_ERR_RUNTIME; }
+        return PH_OK;
+    });
+}
+
+// Gathered radiance under every pixel of a width x height image, built like ph_renderer_ao_camera and on its device scratch (position, normal; the sums where that
+// pass keeps its bent normals, the flags where it keeps its own): pt_aov_device at the pixel centres, pt_gather_device behind it on the same stream with
+// PT_AO_FACE_EYE and the camera's eye - point q = y * width + x, so params->n, flags, eye and first_index are set here - and only the results cross the bus.
+extern "C" int ph_renderer_gather_camera(ph_renderer* r, const double camera[10], uint32_t width, uint32_t height, const pt_gather_params* p, const double* background,
+                                         const pt_gather_buffers* out, double* kernel_ms) {
+    if (!r || !camera || !p || !background || !out) return bad("null argument");
+    if (width == 0 || height == 0) return bad("width and height must be positive");
+    if ((uint64_t)width * height > PT_AO_MAX) return bad("more than PT_AO_MAX pixels");
+    if (!(out->sum || out->valid)) return bad("no output buffer asked for");
+    return guarded([&]() -> int {
+        pt_context* c = r->r->context();
+        auto fail = [&](int rc) { g_error = pt_last_error(c); return rc == PT_ERR_ARGUMENT ? PH_ERR_ARGUMENT : PH_ERR_RUNTIME; };
+        const uint64_t n = (uint64_t)width * height;
+        const size_t bytes[5] = {n * 24, n * 24, n * 4, n * 1, n * 24};  // (ph_renderer_ao_camera's five)
+        int rc = PT_OK;
+        if (r->ao_points < n) {
+            r->ao_release();
+            for (int k = 0; k < 5 && rc == PT_OK; k++) rc = pt_device_alloc(c, bytes[k], &r->d_ao[k]);
+            if (rc != PT_OK) { const int shown = fail(rc); r->ao_release(); return shown; }
+            r->ao_points = n;
+        }
+        pt_camera pc = detail::Camera(camera_from(camera), (double)width, (double)height).to_abi();  // the camera a render of this size gets
+        pt_aov_params ap;
+        ap.width = width; ap.height = height;
+        ap.slice.x0 = 0; ap.slice.y0 = 0; ap.slice.x1 = width - 1; ap.slice.y1 = height - 1;
+        ap.offset[0] = 0.5; ap.offset[1] = 0.5;
+        pt_gather_params q = *p;
+        q.n = n; q.first_index = 0; q.flags = PT_AO_FACE_EYE;
+        for (int k = 0; k < 3; k++) q.eye[k] = pc.eye[k];
+        pt_aov_buffers ab = {nullptr, (double*)r->d_ao[0], (double*)r->d_ao[1], nullptr, nullptr, nullptr};
+        pt_gather_buffers db = {out->sum ? (double*)r->d_ao[4] : nullptr, out->valid ? (uint8_t*)r->d_ao[3] : nullptr};
+        if ((rc = pt_aov_device(c, &pc, &ap, &ab, nullptr))) return fail(rc);
+        rc = pt_gather_device(c, &q, (const double*)r->d_ao[0], (const double*)r->d_ao[1], background, &db, nullptr);  // the same (default) stream: behind the aov pass
+        if (rc) { const int shown = fail(rc); pt_aov_finish(c, nullptr); return shown; }
+        const int rc_aov = pt_aov_finish(c, nullptr);
+        if (rc_aov) g_error = pt_last_error(c);
+        rc = pt_gather_finish(c, kernel_ms);
+        if (rc_aov) return PH_ERR_RUNTIME;
+        if (rc) return fail(rc);
+        if (out->sum && (rc = pt_copy_from_device(c, out->sum, r->d_ao[4], bytes[4]))) return fail(rc);
+        if (out->valid && (rc = pt_copy_from_device(c, out->valid, r->d_ao[3], bytes[3]))) return fail(rc);
         return PH_OK;
     });
 }

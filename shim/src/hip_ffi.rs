@@ -116,6 +116,15 @@ pub struct PtAoBuffers {                   // pt_ao_buffers: each optional (null
     pub occluded: *mut u32, pub valid: *mut u8, pub bent: *mut f64,
 }
 pub const PT_AO_FACE_EYE: u32 = 1;         // PtAoParams.flags: turn each normal towards `eye` first
+#[repr(C)]
+pub struct PtGatherParams {                // pt_gather_params: pt_ao_params without the radius; ray k of point i draws from the stream (seed, (first_index + i) * samples + k, pass)
+    pub n: u64, pub samples: u32, pub pass: u32, pub seed: u64, pub first_index: u64,
+    pub bias: f64, pub flags: u32, pub eye: [f64; 3],
+}
+#[repr(C)]
+pub struct PtGatherBuffers {               // pt_gather_buffers: each optional (null = not wanted), n entries; sum n x 3 = a point's shaded samples added in order
+    pub sum: *mut f64, pub valid: *mut u8,
+}
 #[repr(C)] pub struct PtRaysParams { pub n: u64, pub any_hit: i32, pub reorder: i32 }   // pt_rays_params: any_hit 1 = occlusion query, reorder 1 = the device groups like rays first
 #[repr(C)]
 pub struct PtRadianceParams {              // pt_radiance_params: ray i draws from the generator's stream (seed, stream_base + i, sample), draws 2, 3, ...
@@ -209,6 +218,14 @@ extern "C" {
     pub fn pt_radiance_device(ctx: *mut PtContext, params: *const PtRadianceParams, d_origins: *const f64, d_directions: *const f64, d_background: *const f64,
                               d_rgb: *mut f64, hip_stream: *mut c_void) -> c_int;
     pub fn pt_radiance_finish(ctx: *mut PtContext, kernel_ms: *mut f64) -> c_int;
+    // gathered radiance at points of the caller's own: per point the sum of `samples` shaded samples (what pt_radiance answers) along pt_ao's rays, made in
+    // registers; background 3 f64 on the HOST in both forms. A radiance pass for bookkeeping: pt_gather_device is closed by pt_gather_finish, which is
+    // pt_radiance_finish; queued behind pt_aov_device on the same stream it reads that pass's position and normal where they are
+    pub fn pt_gather(ctx: *mut PtContext, params: *const PtGatherParams, positions: *const f64, normals: *const f64, background: *const f64,
+                     host_out: *const PtGatherBuffers, kernel_ms: *mut f64) -> c_int;
+    pub fn pt_gather_device(ctx: *mut PtContext, params: *const PtGatherParams, d_positions: *const f64, d_normals: *const f64, background: *const f64,
+                            device_out: *const PtGatherBuffers, hip_stream: *mut c_void) -> c_int;
+    pub fn pt_gather_finish(ctx: *mut PtContext, kernel_ms: *mut f64) -> c_int;
     // a film: samples accumulate in device memory, add after add; pt_film_add_device is closed by pt_radiance_finish
     pub fn pt_film_create(ctx: *mut PtContext, width: u32, height: u32, out: *mut *mut PtFilm) -> c_int;
     pub fn pt_film_destroy(ctx: *mut PtContext, film: *mut PtFilm) -> c_int;
