@@ -25,12 +25,12 @@ examples/bin/%: examples/%.cpp portrayer_amd/libportrayer_host.so
 	@mkdir -p examples/bin
 	$(CXX) $(CXXFLAGS) -fPIE -DPORTRAYER_EXAMPLE_MAIN $< -o $@ -Lportrayer_amd -lportrayer_host -lportrayer_hip -Wl,-rpath,'$$ORIGIN/../../portrayer_amd'
 
-# Device objects: the C ABI + small kernels, the device-side tree build, and the render kernel instantiated per
+# Device objects: the C ABI + small kernels (pt_api: context, render, passes; pt_scene: upload, update, deform), the device-side tree build, and the render kernel instantiated per
 # traversal mode (one source, nine objects) - compiled side by side under make -j.
 OBJDIR ?= $(CSRC)
 HIPLIB ?= portrayer_amd/libportrayer_hip.so
 RENDER_MODES := 1 2 3 4 5 6 7 8 9
-HIP_OBJS := $(OBJDIR)/pt_api.o $(OBJDIR)/pt_build.o $(OBJDIR)/pt_node.o $(foreach m,$(RENDER_MODES),$(OBJDIR)/pt_render_m$(m).o) \
+HIP_OBJS := $(OBJDIR)/pt_api.o $(OBJDIR)/pt_scene.o $(OBJDIR)/pt_build.o $(OBJDIR)/pt_node.o $(foreach m,$(RENDER_MODES),$(OBJDIR)/pt_render_m$(m).o) \
             $(foreach m,$(RENDER_MODES),$(OBJDIR)/pt_aov_m$(m).o) \
             $(foreach m,$(RENDER_MODES),$(OBJDIR)/pt_guides_m$(m).o) \
             $(OBJDIR)/pt_rays_sort.o $(foreach m,$(RENDER_MODES),$(OBJDIR)/pt_rays_m$(m).o) \

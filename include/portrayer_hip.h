@@ -798,6 +798,24 @@ int pt_test_libm_host(int op, uint64_t n, const double *a, const double *b, doub
  * items and {pixels, chunks, samples} per wavefront. */
 int pt_test_work_items(const pt_render_params *params, uint32_t *sample_count, uint64_t *sample_index_sum, uint32_t *chunk_length_sum,
                        uint64_t *n_items, uint32_t *lane_pixels_chunks_samples);
+/* What an uploaded scene says that the choice of its render kernel depends on (the context keeps one per scene; pt_scene_update refreshes n_lights and
+ * area_light): what the scene IS, not what follows from it. */
+typedef struct pt_scene_traits {
+    int32_t traverse;            /* PT_TRAVERSE_*                                                            */
+    uint32_t n_nodes, n_lights;  /* flattened nodes, lights                                                  */
+    int32_t has_meshes;          /* the scene has meshes (Mesh or KDMesh) ...                                */
+    int32_t has_kdmesh;          /* ... and some of them carry a KDMesh tree                                 */
+    int32_t reflective;          /* some material is reflective (material.rs:216: its hits spawn rays)       */
+    int32_t reflective_opaque;   /* every reflective material is opaque (no index of refraction)             */
+    int32_t glossy;              /* some reflective material is glossy (material.rs:221-239: it draws random numbers) */
+    int32_t area_light;          /* some light is an area light (light.rs:51-53: it draws random numbers)    */
+    int32_t pad;
+    uint64_t instanced_tris;     /* triangles over all Mesh / KDMesh nodes, a mesh counted once per instance */
+} pt_scene_traits;
+/* Host-side (no GPU, no context): the kernel a render of a scene with these traits launches under the environment's PORTRAYER_* switches, as pt_stats reports
+ * it - *kernel_mode (PT_KERNEL_MODE_*) and *kernel_variant (PT_KERNEL_*, without PT_KERNEL_COUNTING). mode: the scene's PT_KERNEL_MODE_*, or a negative
+ * number for the one that follows from the traits; textured: some material of the scene has a texture or a normal map. */
+int pt_test_kernel_choice(const pt_scene_traits *traits, int mode, int textured, uint32_t *kernel_mode, uint32_t *kernel_variant);
 /* Host-side run (no GPU, no context) of the tree walks' single-precision slab test. Pair i: the ray origins[3i..], directions[3i..] over [0, t_max[i]]
  * against the box box_lo[3i..], box_hi[3i..]. body 0: the ray constants as the kernels are built, 1: their form with f64 products, 2: their f32 form.
  * Out per pair: the interval the per-lane form computed (t_near, t_far) and verdict - bit 0 the per-lane form accepts the box, bit 1 the wavefront

@@ -228,7 +228,7 @@ EXPORTS = ["pt_abi_version", "pt_device_count", "pt_context_create", "pt_context
            "pt_film_denoise", "pt_film_denoise_device", "pt_test_denoise_host",
            "pt_guides", "pt_guides_device", "pt_guides_finish", "pt_film_denoise_albedo", "pt_film_denoise_albedo_device", "pt_test_denoise_albedo_host",
            "pt_ao", "pt_ao_device", "pt_ao_finish", "pt_test_ao_rays_host", "pt_test_ao_tables",
-           "pt_gather", "pt_gather_device", "pt_gather_finish"]
+           "pt_gather", "pt_gather_device", "pt_gather_finish", "pt_test_kernel_choice"]
 
 
 def header_functions():

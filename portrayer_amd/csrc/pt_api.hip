@@ -1,20 +1,10 @@
-// The C ABI declared in include/portrayer_hip.h: context, scene upload (tree builds), render calls, and the
-// small kernels around the render kernel (finishing pass, untile, explicit-ray casts for the parity tests).
+// The C ABI declared in include/portrayer_hip.h: the context's life cycle, render calls and the passes beside the render, and the
+// small kernels around the render kernel (finishing pass, untile, explicit-ray casts for the parity tests). The scene - upload (tree builds), update,
+// deform - is in pt_scene.hip; the context both units share in pt_context.h.
 // The render kernel itself is in pt_render_kernel.h, instantiated per traversal mode by pt_render_inst.hip.
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
-#include <chrono>
-#include <cmath>
-#include <cstdio>
-#include <cstring>
-#include <string>
 #include <type_traits>
-#include <vector>
 
-#include "../../include/portrayer_hip.h"
-#include "pt_build.h"
-#include "pt_bvh.h"
+#include "pt_context.h"
 #include "pt_aov_inst.h"
 #include "pt_guides_inst.h"
 #include "pt_rays_inst.h"
@@ -88,94 +78,6 @@ __global__ void __launch_bounds__(256) pt_copy_kernel(const double2* __restrict_
 __global__ void __launch_bounds__(256) pt_copy1_kernel(const double2* __restrict__ src, double2* __restrict__ dst, size_t n) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) dst[i] = src[i];
-}
-
-// Two-child tree -> four-child tree (PtBvh4Node, pt_scene_view.h). Node i starts with its two children and, while it has
-// fewer than four, replaces the inner child with the largest surface area by that child's two children (the child a ray is
-// most likely to enter is the one worth opening; taking over both children's children regardless leaves a node with a leaf
-// child at three entries). Mesh trees only: on scene-level trees the grandchildren form measured better (transmission-refraction
-// 3.32 against 3.72 node visits per ray). PORTRAYER_COLLAPSE=plain | mesh | area.
-// One thread per two-child node; entries of the array that no tree uses (the device build reserves n - 1 nodes per mesh
-// and may need fewer) are never referenced and are only kept from reading out of bounds. In a device-built tree's place they
-// hold 0xFF bytes, i.e. PT_REF_EMPTY children: pt_scene_upload and a rebuild by pt_scene_deform fill the place before the
-// builder runs, and pt_parent_kernel / pt_refit_kernel (pt_build.hip), which scan the whole place, rely on that - the memset is not redundant.
-// tri_leaf: the edge record of every triangle named by a slot of the items array, in slot order (80 bytes a slot: 9 f64 + the triangle's index), so
-// that a mesh leaf's triangles lie side by side and the wave-uniform walks fetch them without going through bvh_items first.
-__global__ void __launch_bounds__(256) pt_tri_leaf_kernel(const uint32_t* __restrict__ items, uint32_t n_items, const double* __restrict__ tri_e, uint32_t n_tris,
-                                                         double* __restrict__ out) {
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    if (i >= n_items) return;
-    const uint32_t t = items[i];
-    double* o = out + 10 * (size_t)i;
-    if (t < n_tris) {
-        const double* e = tri_e + 9 * (size_t)t;
-        for (int k = 0; k < 9; k++) o[k] = e[k];
-    } else {
-        for (int k = 0; k < 9; k++) o[k] = 0.0;
-    }
-    union { double d; uint32_t u[2]; } c; c.u[0] = t; c.u[1] = 0u;
-    o[9] = c.d;
-}
-
-// [first, end): the nodes this launch converts (pt_scene_upload: all n of them; pt_scene_update: the scene-level tree's alone).
-__global__ void __launch_bounds__(256) pt_collapse4_kernel(const PtBvhNode* __restrict__ bvh2, PtBvh4Node* __restrict__ bvh4, uint32_t n, int by_area_mode,
-                                                            uint32_t scene_first, uint32_t scene_end, uint32_t first, uint32_t end) {
-    const uint32_t i = first + blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= end || i >= n) return;
-    // by_area_mode 0: never, 1: mesh trees only (nodes outside [scene_first, scene_end)), 2: every tree
-    const bool by_area = by_area_mode == 2 || (by_area_mode == 1 && (i < scene_first || i >= scene_end));
-    const PtBvhNode a = bvh2[i];
-    float lo[4][3], hi[4][3];
-    uint32_t child[4];
-    int k = 0;
-    auto put = [&](const PtBvhNode& nd, int which) {
-        pt_node_get_box(nd, which, lo[k], hi[k]);
-        child[k] = which ? nd.child1 : nd.child0;
-        k++;
-    };
-    auto inner = [&](uint32_t c) { return c != PT_REF_EMPTY && !(c & PT_REF_LEAF) && c < n; };
-    if (by_area) {
-        if (a.child0 != PT_REF_EMPTY) put(a, 0);
-        if (a.child1 != PT_REF_EMPTY) put(a, 1);
-        while (k < 4) {
-            int best = -1;
-            float best_area = -1.0f;
-            for (int j = 0; j < k; j++) {
-                if (!inner(child[j])) continue;
-                const float dx = hi[j][0] - lo[j][0], dy = hi[j][1] - lo[j][1], dz = hi[j][2] - lo[j][2];
-                const float area = dx * dy + dy * dz + dz * dx;
-                if (!(area <= best_area)) { best = j; best_area = area; }  // also takes a NaN / infinite area rather than nothing
-            }
-            if (best < 0) break;
-            const PtBvhNode c = bvh2[child[best]];
-            const int n_kids = (c.child0 != PT_REF_EMPTY) + (c.child1 != PT_REF_EMPTY);
-            if (n_kids == 0) { child[best] = child[k - 1]; for (int ax = 0; ax < 3; ax++) { lo[best][ax] = lo[k - 1][ax]; hi[best][ax] = hi[k - 1][ax]; } k--; continue; }
-            // the first child takes the opened entry's place, the second goes to the end
-            const int first = c.child0 != PT_REF_EMPTY ? 0 : 1;
-            pt_node_get_box(c, first, lo[best], hi[best]);
-            child[best] = first ? c.child1 : c.child0;
-            if (n_kids == 2) put(c, 1);
-        }
-    } else {
-        auto expand = [&](const PtBvhNode& nd, int which) {
-            const uint32_t c0 = which ? nd.child1 : nd.child0;
-            if (c0 == PT_REF_EMPTY) return;
-            if (!inner(c0)) { put(nd, which); return; }
-            const PtBvhNode c = bvh2[c0];
-            if (c.child0 != PT_REF_EMPTY) put(c, 0);
-            if (c.child1 != PT_REF_EMPTY) put(c, 1);
-        };
-        expand(a, 0);
-        expand(a, 1);
-    }
-    PtBvh4Node o;
-    for (int j = 0; j < 4; j++) {
-        const bool used = j < k;
-        for (int ax = 0; ax < 3; ax++) { o.lo[ax][j] = used ? lo[j][ax] : (float)PT_BOX_LIMIT; o.hi[ax][j] = used ? hi[j][ax] : -(float)PT_BOX_LIMIT; }
-        o.child[j] = used ? child[j] : PT_REF_EMPTY;
-    }
-    o.pad[0] = o.pad[1] = o.pad[2] = o.pad[3] = 0u;
-    bvh4[i] = o;
 }
 
 // Second pass of a render: chunk sums -> pixels, a block of PT_BLOCK threads per PT_BLOCK pixel slots. The chunk sums are pixel-major (the
@@ -324,203 +226,6 @@ __global__ void __launch_bounds__(PT_PL_BLOCK) pt_pixel_list_kernel(PtRenderArgs
 }
 
 // ------------------------------------------------------------------------------------------------
-// Context
-// ------------------------------------------------------------------------------------------------
-// A device buffer (pt_reserve). It dies with its owner - the context, a film, a function's scope - whose device is current wherever one is destroyed.
-struct PtBuf {
-    void* p = nullptr;
-    size_t bytes = 0;
-    PtBuf() = default;
-    PtBuf(const PtBuf&) = delete;
-    PtBuf& operator=(const PtBuf&) = delete;
-    ~PtBuf() { if (p) hipFree(p); }
-};
-
-// What a device pass beside the render owns whatever its kind (primary visibility, ray queries, radiance and the film's passes; the pt_pass_* functions below),
-// so that the two render slots stay as they are whatever is in flight on them, and every pass whatever is in flight on another.
-struct PtPass {
-    PtBuf stack_spill;                         // the lanes' HBM stack columns
-    PtBuf spill;                               // the lanes' recursion-frame lines (the radiance pass and the film's only)
-    PtBuf misc;                                // the overflow flag (word 1, where a render has it) and, from +256 on, the work queues
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;   // around the kernels (kernel_ms)
-    hipEvent_t copy_done = nullptr;            // behind the copy into `host`
-    unsigned char* host = nullptr;             // pinned: the first two words of misc (the second is the overflow flag)
-    hipStream_t stream = nullptr;              // of the last pass queued
-    bool pending = false;                      // a _device call not yet closed by its _finish
-    bool queued = false;                       // something of the last pass queued may still be in flight (pt_pass_wait)
-    bool closed = false;                       // ... and all of it was queued: copy_done is recorded behind it
-};
-// What reorder = 1 of the ray passes sorts with: keys and ray indices before and after, the sort's scratch (pt_ray_sort_reserve, pt_ray_sort_queue).
-struct PtRaySort {
-    PtBuf keys[2], vals[2], tmp;
-    size_t tmp_bytes = 0;
-};
-
-struct pt_film;
-struct pt_context {
-    int device = 0;
-    int n_cu = 0;
-    std::string err;
-    PtBuf inv, fwd, nrm, info, tri_v, tri_e, tri_leaf, tri_n, meshes, materials, lights, bvh, bvh4, bvh_items, kd, kd_items;
-    PtBuf mat_maps, uv_trans, tex, tex_rgb, srgb_lut, tri_uv, texview, mkd, mkd_items;
-    PtBuf node_box, kd_box, mkd_box, mkd_item_box, kd_ref;
-    PtBuf g_inv, g_fwd, g_nrm, chain_off, chain, dfs_rank, hier_rec, own_inv;  // PT_TRAVERSE_HIER: the scene graph
-    PtBuf bg, rgb, linear, misc;  // (pt_render's host-buffer path; misc: pt_test_cast_rays' overflow flag)
-    bool needs_spill = false;  // some material is reflective (recursion frames) or the scene has more than 32 lights
-    bool spawns = false;       // some material is reflective: hits spawn rays, so the cost of a pixel varies by orders of magnitude
-    bool one_ray = false;      // ... and every reflective material is opaque (no index of refraction): a hit spawns at most one ray, the recursion is a chain
-    bool forkable = false;     // ... and no hit draws random numbers after the jitter (no area light, no glossy material): refracted subtrees may be walked by other lanes
-    uint32_t launch_seq = 0;   // PtRenderArgs::launch_nonce
-    bool four_waves_untextured = false;  // ... or, while the scene has no texture maps: any scene with plain Mesh instances
-    bool four_waves_hier = false;        // ... or any scene without KDMesh trees in the hierarchical semantics
-    bool four_waves = false;   // traversal-heavy scene without reflective materials, flat_scene / hierarchical semantics: a kernel compiled for more than 3 waves per SIMD
-    bool five_waves = false;   // ... mesh-free: 5 waves per SIMD (96 registers)
-    bool five_waves_mesh = false;  // ... very many triangles in plain Mesh instances, untextured: 5 waves too
-    PtSceneView view;
-    bool have_scene = false;
-    // Up to PT_SLOTS renders of one context may be in flight on a stream (pt_render_device ... pt_render_finish, oldest first): a frame's
-    // events and the page of pinned host memory its overflow flag and counters are copied to - asynchronously, right behind its kernels -
-    // belong to its slot, so closing a frame is an event wait and a read of host memory: no blocking copy, and the next frame may already
-    // be queued behind it (pt_node: frame k + 1 renders while frame k is gathered).
-    // Round 5: a slot also owns the launch's WORK buffers (chunk sums, recursion frames, stack overflow columns, work counters / queues / statistics) and a
-    // stream of its own (pt_context_stream), so that two frames may be in flight on two queues at once: the render kernels are persistent - a launch's
-    // wavefronts retire one by one over the duration of its longest work items (the TAIL: 0.13 ms of a 1.3 ms share of the headline frame, 11 %;
-    // profiles/r05/notes.md section 2) - and the next frame's wavefronts take the places they free instead of waiting for the last one.
-    struct Slot {
-        PtBuf spill, stack_spill, accum, misc;     // misc: work counter + overflow flag (8 B), PtCounters at +256, the work queues behind them
-        PtBuf eye_tab;                             // the launch's eye table (pt_eye_table_kernel): n_nodes x 96 bytes, the slot's own - the other slot's frame has another camera;
-                                                   // behind it the launch's certain-shadow table (pt_certain_table_kernel): n_nodes x 16 bytes
-        hipStream_t stream = nullptr;              // pt_context_stream(ctx, slot): non-blocking, created with the context
-        hipEvent_t ev0 = nullptr, ev1 = nullptr;   // around the kernels (pt_stats.kernel_ms)
-        hipEvent_t copy_done = nullptr;            // behind the copy into `host`
-        unsigned char* host = nullptr;   // pinned: [0, 8) work counter + overflow flag, [256, 256 + sizeof(PtCounters)) the counters
-        bool pending = false, counted = false;
-        uint32_t mode = 0, variant = 0;  // pt_stats.kernel_mode / kernel_variant of the launch
-        std::chrono::steady_clock::time_point t_start;
-    };
-    static constexpr int PT_SLOTS = 2;
-    Slot slot[PT_SLOTS];
-    int slot_next = 0;     // the slot the next launch takes
-    int slot_oldest = 0;   // the oldest launch not yet closed (== slot_next: none, unless every slot is pending)
-    uint32_t last_mode = 0, last_variant = 0;
-    int pl_slot = -1;          // pt_test_pixel_list_summary: the slot whose eye_tab buffer holds the last launch's pixel lists (-1: that launch had none) ...
-    uint32_t pl_slots = 0;     // ... its pixel slots ...
-    size_t pl_off = 0;         // ... and where its records start in the buffer
-    // The three passes beside the render, each with a PtPass of its own: all three may be in flight at once, with two renders. Beside it, what is the kind's.
-    // The primary-visibility pass (pt_aov / pt_aov_device ... pt_aov_finish): the device copies of the host-buffer path's six outputs.
-    // The guides pass (pt_guides ...) runs on the SAME pass - one of the two in flight, one set of stack columns - and its host-buffer path takes position, normal and
-    // node from out[1 .. 3] and the albedo from a buffer of its own.
-    struct Aov {
-        PtPass pass;
-        PtBuf out[6];
-        PtBuf albedo;
-        bool guides = false;  // the pass in flight (pass.pending) is a pt_guides_device one: which words a refusal uses
-    } aov;
-    // The ray-query pass (pt_rays / pt_segments, their _device forms ... pt_rays_finish): the device copies of the host-buffer path's inputs (in_t_max: pt_segments'
-    // third) and seven outputs.
-    struct Rays {
-        PtPass pass;
-        PtBuf in[2], in_t_max, out[7];
-        PtRaySort sort;
-    } rays;
-    // The radiance pass (pt_radiance / pt_radiance_device ... pt_radiance_finish), which a film's passes share: the device copies of the host-buffer path's three
-    // inputs and its output.
-    struct Radiance {
-        PtPass pass;
-        PtBuf in[3], out;
-        PtRaySort sort;
-    } radiance;
-    PtPass* const passes[3] = {&aov.pass, &rays.pass, &radiance.pass};
-    // Films (pt_film_create): each owns its device state; a film pass is a radiance pass for bookkeeping (pt_film_add_device), film_open names the film of the
-    // one in flight. Films still alive die with the context.
-    std::vector<pt_film*> films;
-    pt_film* film_open = nullptr;
-    // What pt_scene_update needs of the uploaded scene besides the device buffers: everything a flattened node's world box is made of apart from its
-    // matrix, the node paths (identity bits of hier_rec, own_inv), where the scene-level tree sits in bvh / bvh4 (bvh_items with PORTRAYER_TLAS_LEAF != 1),
-    // and the figures stack_cap and forkable are derived from.
-    struct Resident {
-        int traverse = 0;
-        uint32_t n_nodes = 0, n_graph = 0, n_lights = 0;
-        std::vector<uint32_t> info;            // 4 words per flattened node, as uploaded
-        std::vector<PtBuildBox> mesh_box;      // per mesh: the padded model box
-        std::vector<PtBuildBox> tri_box;       // per stand-alone triangle: the padded model box
-        size_t mesh_tris = 0;                  // stand-alone triangle t is triangle mesh_tris + t
-        std::vector<uint32_t> chain_off, chain;
-        size_t tlas_first = 0, tlas_cap = 0;   // the scene-level tree's nodes: bvh[tlas_first, tlas_first + tlas_cap), tlas_cap = n_nodes - 1
-        size_t tlas_items = 0;                 // ... and its n_nodes leaf items in bvh_items (none when the leaves are direct)
-        size_t tree_nodes = 0;                 // nodes in bvh / bvh4 altogether
-        int tlas_leaf = 1, collapse_mode = 1;
-        int below = 0;                         // stack_cap: the deepest walk under a scene leaf
-        int last_builder = 0, last_rounds = 0; // tests: who built the scene-level tree last (0 the upload, 1 an update on the host, 2 on the device) and in how many clustering rounds
-        bool mat_draws = false, dielectric = false;  // forkable: what the materials say
-        // pt_scene_deform: where every mesh's tree sits in bvh / bvh4 (nodes) and bvh_items / tri_leaf (items), who built it and how deep it is; the
-        // meshes' indices as uploaded (they go to the device with the first deform) and the PtMeshInfo records (bbox_inv and blas_root change)
-        struct MeshPlace {
-            uint32_t node_first = 0, node_count = 0, item_first = 0, item_count = 0, n_verts = 0;
-            int depth = 0;                 // of the two-child tree
-            bool device_built = false;     // its place has the device builder's worst-case size: it can be rebuilt there
-            bool has_normals = false;
-            bool parents_valid = false;    // tree_parent holds this tree's parents (set by the first refit, cleared by a rebuild)
-        };
-        std::vector<MeshPlace> place;
-        std::vector<uint32_t> indices;
-        std::vector<PtMeshInfo> meshes;
-        bool indices_resident = false;     // mesh_idx holds `indices`
-        int blas_leaf = 2, max_kdm_depth = 0;
-        bool any_normals = false;          // tri_n holds a record per triangle (some node shades smoothly)
-    } res;
-    PtBuf mesh_box_dev;  // the per-mesh boxes again, 6 f64 each, for the device build of the scene-level tree
-    // pt_scene_deform, allocated by the first deform of the context: the meshes' indices, a parent index and an arrival counter per tree node (the refit),
-    // and the staging buffer the new vertices are copied to
-    PtBuf mesh_idx, tree_parent, tree_arrive, deform_stage;
-    PtBuf vbox;  // pt_vertex_bounds_device / pt_scene_deform_device: the reduction's per-block partials (PtVboxPartial); a work buffer, not part of the scene
-    double root_lo[3] = {0.0, 0.0, 0.0}, root_hi[3] = {0.0, 0.0, 0.0};  // the scene tree's root box: union of the flattened nodes' world boxes (reorder = 1 quantises origins inside it)
-};
-#define PT_SLOT_BYTES (256 + sizeof(PtCounters))
-
-// A film (include/portrayer_hip.h): per pixel the sum of its complete chunks, the sum of its open chunk and its count, row-major; the staging buffer the
-// sampling kernel writes a launch's samples to (sized for the largest slice seen); device copies for the host-buffer paths; and the counts again on the host,
-// so that an add that would take a pixel past 2^31 samples is refused before any HIP call.
-struct pt_film {
-    pt_context* ctx = nullptr;
-    uint32_t width = 0, height = 0;
-    PtBuf total, partial, count, staging, bg, out_rgb, out_linear;
-    // pt_film_create_moments: the second moment per pixel. pt_film_add_map: the host map's device copy, the list of a launch round (its length in the
-    // word in front of it), the plan's block sums. pt_film_error: the host path's device buffer.
-    PtBuf q, budget, list, plan_work, out_err;
-    // pt_film_denoise: the two work buffers of its levels (32 bytes per pixel each, allocated by the first denoise); the host path's device copies of the
-    // guides and of the variance it returns.
-    PtBuf dn_work[2], dn_position, dn_normal, dn_node, dn_albedo, out_var;  // (dn_albedo: pt_film_denoise_albedo's guide)
-    bool moments = false;
-    std::vector<uint32_t> counts;
-};
-static int pt_fail(pt_context* c, int code, const std::string& msg) {
-    if (c) c->err = msg;
-    return code;
-}
-#define PT_HIP(c, call)                                                                                   \
-    do {                                                                                                  \
-        hipError_t e_ = (call);                                                                           \
-        if (e_ != hipSuccess) return pt_fail(c, PT_ERR_DEVICE, std::string(#call) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
-static int pt_reserve(pt_context* c, PtBuf& b, size_t bytes) {
-    if (bytes == 0) bytes = 16;
-    if (b.bytes >= bytes) return PT_OK;
-    if (b.p) { PT_HIP(c, hipFree(b.p)); b.p = nullptr; b.bytes = 0; }
-    PT_HIP(c, hipMalloc(&b.p, bytes));
-    b.bytes = bytes;
-    return PT_OK;
-}
-template <class T>
-static int pt_upload(pt_context* c, PtBuf& b, const std::vector<T>& v) {
-    int rc = pt_reserve(c, b, v.size() * sizeof(T));
-    if (rc) return rc;
-    if (!v.empty()) PT_HIP(c, hipMemcpy(b.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-    return PT_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
 // The life of a device pass (PtPass), the same for every kind. Queueing: prepare, [the kind's argument block and sizing dispatch], open, [its sort and kernels],
 // seal. On the pass's stream that is: all of misc zeroed, ev0, the sort and the kernels, ev1, the overflow flag's copy to the pinned page, copy_done.
 // Closing: wait, result. The entry points: pt_pass_device_tail ... pt_pass_finish, or pt_pass_settle ... pt_pass_result within one call (host buffers).
@@ -545,7 +250,7 @@ static int pt_pass_open(pt_context* c, PtPass& v, PtRenderArgs& r, uint32_t grid
     r.n_lanes = grid * PT_BLOCK;
     int rc;
     if ((rc = pt_reserve(c, v.stack_spill, (size_t)r.n_lanes * pt_stack_column(r.scene, r.stack_lds_cap) * 4))) return rc;
-    if (frames && (rc = pt_reserve(c, v.spill, c->needs_spill ? (size_t)r.n_lanes * PT_SPILL_DEPTHS * PT_SPILL_STRIDE * sizeof(double) : 16))) return rc;
+    if (frames && (rc = pt_reserve(c, v.spill, pt_needs_spill(c->traits) ? (size_t)r.n_lanes * PT_SPILL_DEPTHS * PT_SPILL_STRIDE * sizeof(double) : 16))) return rc;
     if ((rc = pt_reserve(c, v.misc, PT_PASS_MISC_BYTES))) return rc;
     r.stack_spill = (uint32_t*)v.stack_spill.p;
     if (frames) r.spill = (double*)v.spill.p;
@@ -683,1161 +388,11 @@ extern "C" const char* pt_last_error(const pt_context* c) { return c ? c->err.c_
 // PORTRAYER_TWO_STREAMS=0 / 1 forces one / two.
 extern "C" void* pt_context_stream(pt_context* c, int slot) {
     if (!c) return nullptr;
-    bool two = !(c->have_scene && c->needs_spill);
+    bool two = !(c->have_scene && pt_needs_spill(c->traits));
     if (const char* e = getenv("PORTRAYER_TWO_STREAMS")) two = atoi(e) > 0;
     return (void*)c->slot[two ? (slot & 1) : 0].stream;
 }
 extern "C" int pt_context_next_slot(const pt_context* c) { return c ? c->slot_next : 0; }
-
-// ------------------------------------------------------------------------------------------------
-// Scene upload
-// ------------------------------------------------------------------------------------------------
-static void pt_transform_box(const double* m, const double lo[3], const double hi[3], PtBuildBox* out) {
-    *out = pt_bvh_detail::empty_box();
-    for (int ix = 0; ix < 2; ix++) for (int iy = 0; iy < 2; iy++) for (int iz = 0; iz < 2; iz++) {
-        double x = ix ? hi[0] : lo[0], y = iy ? hi[1] : lo[1], z = iz ? hi[2] : lo[2];
-        for (int r = 0; r < 3; r++) {
-            double v = m[4 * r] * x + m[4 * r + 1] * y + m[4 * r + 2] * z + m[4 * r + 3];
-            out->lo[r] = std::min(out->lo[r], v);
-            out->hi[r] = std::max(out->hi[r], v);
-        }
-    }
-}
-static void pt_pad_box(PtBuildBox* b, double rel) {
-    for (int k = 0; k < 3; k++) {
-        double mag = std::max(std::fabs(b->lo[k]), std::fabs(b->hi[k]));
-        double pad = rel * std::max(b->hi[k] - b->lo[k], mag) + 1e-300;
-        b->lo[k] -= pad; b->hi[k] += pad;
-    }
-}
-
-// ------------------------------------------------------------------------------------------------
-// Steps of pt_scene_upload that pt_scene_update repeats for a moved scene: both call these, so a host-computed part of an updated
-// scene is what an upload of the same scene computes.
-// ------------------------------------------------------------------------------------------------
-static void pt_pack_node_matrices(uint32_t n, const double* trans, const double* invtrans, const double* normal_trans, std::vector<double>& inv,
-                                  std::vector<double>& fwd, std::vector<double>& nrm) {
-    inv.resize(12 * (size_t)n); fwd.resize(12 * (size_t)n); nrm.resize(9 * (size_t)n);
-    for (uint32_t i = 0; i < n; i++) {
-        for (int r = 0; r < 12; r++) { inv[12 * (size_t)i + r] = invtrans[16 * (size_t)i + r]; fwd[12 * (size_t)i + r] = trans[16 * (size_t)i + r]; }
-        for (int r = 0; r < 3; r++) for (int k = 0; k < 3; k++) nrm[9 * (size_t)i + 3 * r + k] = normal_trans[16 * (size_t)i + 4 * r + k];
-    }
-}
-
-struct PtGraphArrays {
-    std::vector<double> g_inv, g_fwd, g_nrm, own_inv;
-    std::vector<uint32_t> hier_rec;
-};
-// PT_TRAVERSE_HIER: the graph nodes' matrices and, per flattened node, its path record and its own level's inverse. chain_off / chain are checked by the caller.
-static void pt_pack_graph(uint32_t n, uint32_t g, const double* graph_trans, const double* graph_invtrans, const double* graph_normal_trans,
-                          const std::vector<uint32_t>& chain_off, const std::vector<uint32_t>& chain, PtGraphArrays& out) {
-    std::vector<double>&g_inv = out.g_inv, &g_fwd = out.g_fwd, &g_nrm = out.g_nrm, &own_inv = out.own_inv;
-    std::vector<uint32_t>& hier_rec = out.hier_rec;
-    g_inv.resize(12 * (size_t)g); g_fwd.resize(12 * (size_t)g); g_nrm.resize(9 * (size_t)g);
-    for (uint32_t i = 0; i < g; i++) {
-        for (int r = 0; r < 12; r++) { g_inv[12 * (size_t)i + r] = graph_invtrans[16 * (size_t)i + r]; g_fwd[12 * (size_t)i + r] = graph_trans[16 * (size_t)i + r]; }
-        for (int r = 0; r < 3; r++) for (int k = 0; k < 3; k++) g_nrm[9 * (size_t)i + 3 * r + k] = graph_normal_trans[16 * (size_t)i + 4 * r + k];
-    }
-    // One record per flattened node for the walks (pt_node_local_ray_uniform): its path in one scalar fetch instead of three dependent
-    // ones, and which of its levels are the identity (a group without a transform, like every reference scene's root): multiplying a
-    // ray by such a level changes no bit unless a component is -0 or not finite, which the walk rules out once per ray.
-    auto identity = [&](uint32_t gi) {
-        for (int r = 0; r < 3; r++)
-            for (int k = 0; k < 4; k++) {
-                const double want = r == k ? 1.0 : 0.0;  // (== : a zero of either sign passes)
-                if (g_inv[12 * (size_t)gi + 4 * r + k] != want || g_fwd[12 * (size_t)gi + 4 * r + k] != want) return false;
-                if (k < 3 && g_nrm[9 * (size_t)gi + 3 * r + k] != want) return false;
-            }
-        return true;
-    };
-    std::vector<uint8_t> g_ident(g);
-    for (uint32_t i = 0; i < g; i++) g_ident[i] = identity(i) ? 1 : 0;
-    hier_rec.assign(8 * (size_t)n, 0u);
-    own_inv.assign(12 * (size_t)n, 0.0);
-    for (uint32_t i = 0; i < n; i++) {
-        const uint32_t len = chain_off[i + 1] - chain_off[i];
-        uint32_t* rec = &hier_rec[8 * (size_t)i];
-        for (int r = 0; r < 12; r++) own_inv[12 * (size_t)i + r] = g_inv[12 * (size_t)chain[chain_off[i + 1] - 1] + r];  // the node's own level: the last of its path
-        if (len > 7) { rec[0] = 255u; continue; }
-        rec[0] = len;
-        for (uint32_t k = 0; k < len; k++) {
-            const uint32_t gi = chain[chain_off[i] + k];
-            rec[1 + k] = gi;
-            if (g_ident[gi]) rec[0] |= 1u << (8 + k);
-        }
-    }
-}
-
-// The box of a mesh's vertices and its largest extent (floored at 1e-30): triangle boxes are padded by 1e-7 ext, the mesh's own box by 1e-5 ext.
-// pt_scene_upload and pt_scene_deform both call this.
-static double pt_box_extent(const PtBuildBox& b) { return std::max(std::max(b.hi[0] - b.lo[0], b.hi[1] - b.lo[1]), std::max(b.hi[2] - b.lo[2], 1e-30)); }
-static double pt_mesh_vertex_box(const double* pos, uint64_t n_verts, PtBuildBox* mb) {
-    *mb = pt_bvh_detail::empty_box();
-    for (uint64_t v = 0; v < n_verts; v++)
-        for (int k = 0; k < 3; k++) { mb->lo[k] = std::min(mb->lo[k], pos[3 * v + k]); mb->hi[k] = std::max(mb->hi[k], pos[3 * v + k]); }
-    return pt_box_extent(*mb);
-}
-
-// the padded model box of a stand-alone triangle (9 f64)
-static void pt_triangle_model_box(const double* v, PtBuildBox* b) {
-    double ext = 1e-30;
-    for (int k = 0; k < 3; k++) {
-        b->lo[k] = std::min(v[k], std::min(v[3 + k], v[6 + k])); b->hi[k] = std::max(v[k], std::max(v[3 + k], v[6 + k]));
-        ext = std::max(ext, b->hi[k] - b->lo[k]);
-    }
-    for (int k = 0; k < 3; k++) { b->lo[k] -= 1e-6 * ext; b->hi[k] += 1e-6 * ext; }
-}
-
-// Conservative world-space boxes of the flattened nodes and their union, the scene tree's root box (c->root_lo / root_hi): every hit the
-// primitive tests can accept lies inside its box (cube.rs:25 / plane.rs:31 accept points up to 1e-5 outside the unit shape; all shapes are
-// padded by 1e-4 model units). Spheres, cylinders and cones get their exact boxes under the affine transform instead of the box of their
-// transformed unit cube. `info`: 4 words per node (type, data, ..); pt_node_box_kernel (pt_build.hip) is the device's copy of the formulas.
-static void pt_node_world_boxes(uint32_t n, const double* trans, const uint32_t* info, const std::vector<PtBuildBox>& mesh_box,
-                                const std::vector<PtBuildBox>& tri_box, size_t mesh_tris, std::vector<PtBuildBox>& node_box, double root_lo[3], double root_hi[3]) {
-    node_box.resize(n);
-    for (uint32_t i = 0; i < n; i++) {
-        const int t = (int)info[4 * (size_t)i];
-        const uint32_t data = info[4 * (size_t)i + 1];
-        const double* M = &trans[16 * (size_t)i];
-        PtBuildBox& nb = node_box[i];
-        auto disc = [&](double yc, double radius, PtBuildBox* b) {  // disc of `radius` in the model xz-plane at height yc
-            for (int r = 0; r < 3; r++) {
-                double c = M[4 * r + 1] * yc + M[4 * r + 3];
-                double e = radius * std::sqrt(M[4 * r] * M[4 * r] + M[4 * r + 2] * M[4 * r + 2]);
-                b->lo[r] = std::min(b->lo[r], c - e); b->hi[r] = std::max(b->hi[r], c + e);
-            }
-        };
-        double lo[3], hi[3];
-        bool boxed = false;
-        switch (t) {
-        case PT_PRIM_SPHERE:
-            for (int r = 0; r < 3; r++) {
-                double e = 1.0001 * std::sqrt(M[4 * r] * M[4 * r] + M[4 * r + 1] * M[4 * r + 1] + M[4 * r + 2] * M[4 * r + 2]);
-                nb.lo[r] = M[4 * r + 3] - e; nb.hi[r] = M[4 * r + 3] + e;
-            }
-            boxed = true; break;
-        case PT_PRIM_CYLINDER: nb = pt_bvh_detail::empty_box(); disc(0.5001, 0.5001, &nb); disc(-0.5001, 0.5001, &nb); boxed = true; break;
-        case PT_PRIM_CONE: nb = pt_bvh_detail::empty_box(); disc(0.5001, 1e-4, &nb); disc(-0.5001, 0.5001, &nb); boxed = true; break;
-        case PT_PRIM_PLANE: lo[0] = lo[2] = -0.5001; hi[0] = hi[2] = 0.5001; lo[1] = -1e-4; hi[1] = 1e-4; break;
-        case PT_PRIM_MESH: case PT_PRIM_KDMESH: for (int k = 0; k < 3; k++) { lo[k] = mesh_box[data].lo[k]; hi[k] = mesh_box[data].hi[k]; } break;
-        case PT_PRIM_TRIANGLE: for (int k = 0; k < 3; k++) { lo[k] = tri_box[data - mesh_tris].lo[k]; hi[k] = tri_box[data - mesh_tris].hi[k]; } break;
-        default: lo[0] = lo[1] = lo[2] = -0.5001; hi[0] = hi[1] = hi[2] = 0.5001; break;  // cube
-        }
-        if (!boxed) pt_transform_box(M, lo, hi, &nb);
-        pt_pad_box(&nb, 1e-9);
-    }
-    for (int k = 0; k < 3; k++) { root_lo[k] = INFINITY; root_hi[k] = -INFINITY; }
-    for (uint32_t i = 0; i < n; i++)
-        for (int k = 0; k < 3; k++) { root_lo[k] = std::min(root_lo[k], node_box[i].lo[k]); root_hi[k] = std::max(root_hi[k], node_box[i].hi[k]); }
-}
-
-// The scene-level tree on the host: binned SAH over the nodes' world boxes (pt_bvh.h), built from index 0 and then moved to where it lives in the
-// context's arrays: its nodes from `node_base` on in bvh, its leaf items (none when the leaves are direct) from `item_base` on in bvh_items.
-static PtBvhRef pt_build_scene_tree(const std::vector<PtBuildBox>& node_box, int tlas_leaf, bool direct, size_t node_base, size_t item_base,
-                                    std::vector<PtBvhNode>& nodes, std::vector<uint32_t>& items) {
-    nodes.clear(); items.clear();
-    PtBvhRef root = pt_bvh_build(node_box.data(), nullptr, node_box.size(), tlas_leaf, nodes, items, direct);
-    auto moved = [&](uint32_t ref) -> uint32_t {
-        if (ref == PT_REF_EMPTY) return ref;
-        if (!(ref & PT_REF_LEAF)) return ref + (uint32_t)node_base;
-        if (direct) return ref;
-        return PT_REF_LEAF | (((((ref & ~PT_REF_LEAF) >> 3) + (uint32_t)item_base) << 3) | (ref & 7u));
-    };
-    for (PtBvhNode& nd : nodes) { nd.child0 = moved(nd.child0); nd.child1 = moved(nd.child1); }
-    root.child = moved(root.child);
-    return root;
-}
-
-// The reference's k-d tree over the flattened nodes (PT_TRAVERSE_KD) as the walks read it, with the conservative f32 boxes the culls use.
-struct PtKdArrays {
-    std::vector<PtKdNode> kdn;
-    std::vector<uint32_t> kdi, kd_ref32;
-    std::vector<float> node_box32, kd_box32;
-    double kd_extent = 0.0;
-    int kd_depth = 0, kd_levels = 0;
-};
-static int pt_pack_kd(pt_context* c, const pt_kdtree* kd, uint32_t n, const std::vector<PtBuildBox>& node_box, PtKdArrays& out) {
-    std::vector<PtKdNode>& kdn = out.kdn;
-    std::vector<uint32_t>&kdi = out.kdi, &kd_ref32 = out.kd_ref32;
-    std::vector<float>&node_box32 = out.node_box32, &kd_box32 = out.kd_box32;
-    int& kd_levels = out.kd_levels;  // split levels on the deepest path of the tree (root = level 0)
-    if (kd->n_nodes == 0 || !kd->axis || !kd->plane || !kd->front || !kd->back || !kd->first || !kd->count || (kd->n_items && !kd->leaf_items))
-        return pt_fail(c, PT_ERR_ARGUMENT, "incomplete k-d tree");
-    kdn.resize(kd->n_nodes);
-    for (uint32_t i = 0; i < kd->n_nodes; i++) {
-        PtKdNode& k = kdn[i];
-        k.axis = kd->axis[i]; k.plane = kd->plane[i]; k.front = kd->front[i]; k.back = kd->back[i];
-        k.first = kd->first[i]; k.count = kd->count[i]; k.pad = 0; k.pad2[0] = k.pad2[1] = 0.0f; for (int r = 0; r < 6; r++) k.box[r] = 0.0f;
-        if (k.axis >= 0) {
-            if (k.axis > 2 || k.front < 0 || k.back < 0 || (uint32_t)k.front >= kd->n_nodes || (uint32_t)k.back >= kd->n_nodes)
-                return pt_fail(c, PT_ERR_ARGUMENT, "k-d child out of range");
-        } else if (k.first < 0 || k.count < 0 || (uint32_t)(k.first + k.count) > kd->n_items) {
-            return pt_fail(c, PT_ERR_ARGUMENT, "k-d leaf range out of bounds");
-        }
-    }
-    kdi.resize(kd->n_items);
-    for (uint32_t i = 0; i < kd->n_items; i++) {
-        if (kd->leaf_items[i] < 0 || (uint32_t)kd->leaf_items[i] >= n) return pt_fail(c, PT_ERR_ARGUMENT, "k-d leaf item out of range");
-        kdi[i] = (uint32_t)kd->leaf_items[i];
-    }
-    double dx = kd->root_max[0] - kd->root_min[0], dy = kd->root_max[1] - kd->root_min[1], dz = kd->root_max[2] - kd->root_min[2];
-    out.kd_extent = (dx * dx + dy * dy) + dz * dz;  // bounding_box.rs:95-99 magnitude_squared
-    out.kd_depth = kd->max_depth < 0 ? 0 : kd->max_depth;
-    node_box32.resize(6 * kdi.size());  // in leaf-item order: the walk reads a leaf's boxes one after the other
-    for (size_t j = 0; j < kdi.size(); j++)
-        for (int k = 0; k < 3; k++) {
-            node_box32[6 * j + k] = pt_bvh_detail::round_down(node_box[kdi[j]].lo[k]);
-            node_box32[6 * j + 3 + k] = pt_bvh_detail::round_up(node_box[kdi[j]].hi[k]);
-        }
-    // the wave-uniform k-d walk (pt_trace_packet_kd) reads a leaf reference and its cull box in ONE scalar fetch: 32 bytes {node, 0, box}
-    kd_ref32.resize(8 * kdi.size());
-    for (size_t j = 0; j < kdi.size(); j++) {
-        kd_ref32[8 * j] = kdi[j]; kd_ref32[8 * j + 1] = 0u;
-        memcpy(&kd_ref32[8 * j + 2], &node_box32[6 * j], 6 * sizeof(float));
-    }
-    {
-        std::vector<std::pair<uint32_t, int>> todo;
-        std::vector<uint8_t> seen(kdn.size(), 0);
-        if (!kdn.empty()) todo.push_back({0u, 0});
-        while (!todo.empty()) {
-            auto [i, lev] = todo.back(); todo.pop_back();
-            if (seen[i]) return pt_fail(c, PT_ERR_ARGUMENT, "k-d tree is not a tree");
-            seen[i] = 1;
-            if (kdn[i].axis < 0) continue;
-            kd_levels = std::max(kd_levels, lev + 1);
-            todo.push_back({(uint32_t)kdn[i].front, lev + 1}); todo.push_back({(uint32_t)kdn[i].back, lev + 1});
-        }
-    }
-    if (kd_levels > PT_KD_WAVE_LEVELS)  // two bits of per-lane state per level in one 64-bit word (pt_trace_packet_kd); a tree that deep has > 2^32 leaves unless it is a degenerate chain
-        return pt_fail(c, PT_ERR_SCENE, "k-d tree deeper than 32 levels (the limit of the k-d walk: include/portrayer_hip.h, pt_kdtree)");
-    // what the walk's packed words can address: a stack entry is (node << 5) | level, a node is fetched at byte offset node << 6, a leaf reference at (first + i) << 5
-    if (kdn.size() >= ((size_t)1 << 26)) return pt_fail(c, PT_ERR_SCENE, "k-d tree of 2^26 nodes or more");
-    if (kd_ref32.size() / 8 >= ((size_t)1 << 27)) return pt_fail(c, PT_ERR_SCENE, "k-d tree with 2^27 leaf references or more");
-    // children follow their parents in the linearised tree (pre-order): one backward sweep
-    kd_box32.assign(6 * kdn.size(), 0.0f);
-    for (size_t i = kdn.size(); i-- > 0;) {
-        float* b = &kd_box32[6 * i];
-        const PtKdNode& k = kdn[i];
-        for (int r = 0; r < 3; r++) { b[r] = (float)PT_BOX_LIMIT; b[3 + r] = -(float)PT_BOX_LIMIT; }  // empty
-        if (k.axis < 0) {
-            for (int32_t j = 0; j < k.count; j++)
-                for (int r = 0; r < 3; r++) {
-                    b[r] = std::min(b[r], node_box32[6 * (size_t)(k.first + j) + r]);
-                    b[3 + r] = std::max(b[3 + r], node_box32[6 * (size_t)(k.first + j) + 3 + r]);
-                }
-        } else if ((size_t)k.front > i && (size_t)k.back > i) {
-            for (int r = 0; r < 3; r++) {
-                b[r] = std::min(kd_box32[6 * (size_t)k.front + r], kd_box32[6 * (size_t)k.back + r]);
-                b[3 + r] = std::max(kd_box32[6 * (size_t)k.front + 3 + r], kd_box32[6 * (size_t)k.back + 3 + r]);
-            }
-        } else {  // not in pre-order: no culling at this node
-            for (int r = 0; r < 3; r++) { b[r] = -(float)PT_BOX_LIMIT; b[3 + r] = (float)PT_BOX_LIMIT; }
-        }
-    }
-    for (size_t i = 0; i < kdn.size(); i++) for (int r = 0; r < 6; r++) kdn[i].box[r] = kd_box32[6 * i + r];
-    return PT_OK;
-}
-// ... into the context's buffers and the view (k.kdn empty: another traversal)
-static int pt_upload_kd(pt_context* c, const PtKdArrays& k, bool kd_mode) {
-    int rc;
-    if ((rc = pt_upload(c, c->node_box, k.node_box32)) || (rc = pt_upload(c, c->kd_box, k.kd_box32)) || (rc = pt_upload(c, c->kd, k.kdn)) ||
-        (rc = pt_upload(c, c->kd_items, k.kdi)) || (rc = pt_upload(c, c->kd_ref, k.kd_ref32)))
-        return rc;
-    PtSceneView& v = c->view;
-    v.kd = (const PtKdNode*)c->kd.p; v.kd_items = (const uint32_t*)c->kd_items.p;
-    v.kd_extent = k.kd_extent;
-    v.kd_ref = (const uint32_t*)c->kd_ref.p; v.kd_levels = k.kd_levels;
-    v.node_box = kd_mode && !k.kdi.empty() ? (const float*)c->node_box.p : nullptr;
-    v.kd_box = kd_mode ? (const float*)c->kd_box.p : nullptr;
-    if (getenv("PORTRAYER_KD_NO_CULL")) v.kd_box = v.node_box = nullptr;  // experiment: the reference's walk as it is
-    if (const char* e = getenv("PORTRAYER_KD_CULL")) { const int m = atoi(e); if (!(m & 1)) v.kd_box = nullptr; if (!(m & 2)) v.node_box = nullptr; }  // experiment: bit 0 tree nodes, bit 1 leaf references
-    return PT_OK;
-}
-
-// fork / join of refracted subtrees (pt_shade.h) needs a recursion that draws no random numbers and a dielectric material to be of use
-static void pt_set_light_flags(pt_context* c, const double* lights, uint32_t n_lights) {
-    bool draws = c->res.mat_draws;
-    for (uint32_t l = 0; l < n_lights; l++) {
-        const double* L = &lights[15 * (size_t)l];
-        const bool empty = (L[9] == 0.0 && L[10] == 0.0 && L[11] == 0.0) || (L[12] == 0.0 && L[13] == 0.0 && L[14] == 0.0);  // light.rs:51-53
-        if (!empty) draws = true;
-    }
-    c->forkable = c->spawns && c->res.dielectric && !draws && n_lights <= PT_LIGHT_ROUND;
-    c->one_ray = c->spawns && !c->res.dielectric;
-}
-
-// The walks' stack: a level of the four-child walk pushes up to three pending children; it covers two levels of the two-child tree in the plain
-// collapse and at least one when nodes are opened by area. `tlas_depth`: of the scene-level tree (two-child form); `kd_depth`: of the k-d tree
-// the scene is walked with NOW (PT_TRAVERSE_KD; it changes when nodes move).
-static int pt_set_stack_cap(pt_context* c, int tlas_depth, int kd_depth) {
-    const int collapse_mode = c->res.collapse_mode;
-    auto wide = [&](int depth2) { return collapse_mode ? 3 * depth2 : 3 * ((depth2 + 1) / 2); };
-    int cap = c->res.traverse == PT_TRAVERSE_KD ? 3 * (kd_depth + 1) + c->res.below + 2 : wide(tlas_depth) + c->res.below + 4;
-    c->view.stack_cap = std::max(cap, 8);
-    if (const char* e = getenv("PORTRAYER_STACK_CAP")) c->view.stack_cap = std::max(1, atoi(e));  // tests: force PT_ERR_TRAVERSAL
-    if (c->view.stack_cap > 4096) return pt_fail(c, PT_ERR_SCENE, "tree too deep for the traversal stack");
-    return PT_OK;
-}
-
-extern "C" int pt_scene_upload(pt_context* c, const pt_scene* s, int traverse, const pt_kdtree* kd) {
-    if (!c || !s) return PT_ERR_ARGUMENT;
-    if (traverse != PT_TRAVERSE_FLAT && traverse != PT_TRAVERSE_KD && traverse != PT_TRAVERSE_HIER)
-        return pt_fail(c, PT_ERR_ARGUMENT, "traverse must be PT_TRAVERSE_FLAT, PT_TRAVERSE_KD or PT_TRAVERSE_HIER");
-    if (traverse == PT_TRAVERSE_HIER && s->n_nodes &&
-        (!s->n_graph_nodes || !s->graph_trans || !s->graph_invtrans || !s->graph_normal_trans || !s->node_chain_off || !s->node_chain || !s->node_dfs_rank))
-        return pt_fail(c, PT_ERR_ARGUMENT, "PT_TRAVERSE_HIER needs the scene graph (graph_*, node_chain*, node_dfs_rank)");
-    if (traverse == PT_TRAVERSE_KD && !kd) return pt_fail(c, PT_ERR_ARGUMENT, "PT_TRAVERSE_KD needs the host-built k-d tree");
-    if (s->n_nodes && (!s->trans || !s->invtrans || !s->normal_trans || !s->prim_type || !s->prim_data || !s->prim_flags || !s->material))
-        return pt_fail(c, PT_ERR_ARGUMENT, "null node array");
-    PT_HIP(c, hipSetDevice(c->device));
-    c->have_scene = false;
-    const uint32_t n = s->n_nodes;
-    const bool verbose = getenv("PORTRAYER_VERBOSE") != nullptr;
-    auto t_begin = std::chrono::steady_clock::now();
-    auto lap = [&](const char* what) {
-        if (!verbose) return;
-        auto now = std::chrono::steady_clock::now();
-        fprintf(stderr, "[pt_scene_upload] %-28s %8.2f ms\n", what, std::chrono::duration<double, std::milli>(now - t_begin).count());
-        t_begin = now;
-    };
-
-    // ---- triangles: every mesh expanded to 72-byte vertex records, stand-alone triangles appended
-    std::vector<uint64_t> tri_first(s->n_meshes + 1, 0);
-    size_t mesh_tris = s->n_meshes ? (size_t)s->mesh_tri_off[s->n_meshes] : 0;
-    size_t total_tris = mesh_tris + s->n_triangles;
-    bool any_normals = false;
-    for (uint32_t i = 0; i < n; i++) {
-        int t = s->prim_type[i];
-        if (t < PT_PRIM_SPHERE || t > PT_PRIM_CONE) return pt_fail(c, PT_ERR_ARGUMENT, "unknown primitive type");
-        if (s->material[i] < 0 || (uint32_t)s->material[i] >= s->n_materials) return pt_fail(c, PT_ERR_ARGUMENT, "material index out of range");
-        if (t == PT_PRIM_MESH || t == PT_PRIM_KDMESH) {
-            if (s->prim_data[i] < 0 || (uint32_t)s->prim_data[i] >= s->n_meshes) return pt_fail(c, PT_ERR_ARGUMENT, "mesh index out of range");
-            if (s->prim_flags[i] & 1) {
-                if (!s->mesh_has_normals || !s->mesh_has_normals[s->prim_data[i]] || !s->mesh_normals)
-                    return pt_fail(c, PT_ERR_SCENE, "smooth shading needs a vertex normal per vertex (mesh.rs:135-138)");
-                any_normals = true;
-            }
-        } else if (t == PT_PRIM_TRIANGLE) {
-            if (s->prim_data[i] < 0 || (uint32_t)s->prim_data[i] >= s->n_triangles) return pt_fail(c, PT_ERR_ARGUMENT, "triangle index out of range");
-            if (s->prim_flags[i] & 1) { if (!s->tri_normals) return pt_fail(c, PT_ERR_SCENE, "triangle normals missing"); any_normals = true; }
-        }
-    }
-    std::vector<double> tri_v(total_tris * 9), tri_n(any_normals ? total_tris * 9 : 0);
-    std::vector<PtMeshInfo> meshes(s->n_meshes);
-    std::vector<PtBvhNode> bvh;
-    std::vector<uint32_t> items;
-    std::vector<PtBuildBox> mesh_box(s->n_meshes);
-    int max_blas_depth = 0;
-    int collapse_mode = 1;  // how two-child trees become four-child trees (pt_collapse4_kernel): 0 grandchildren, 1 mesh trees opened by area, 2 every tree by area
-    int blas_leaf = 2;  // triangles per mesh-tree leaf (measured: 2 beats 1, 3 and 4 by 2-5 % on cows / big-soup)
-    if (const char* e = getenv("PORTRAYER_BLAS_LEAF")) blas_leaf = std::min(std::max(1, atoi(e)), 8);
-    // Where a mesh's triangle tree is built: on the host (binned SAH, pt_bvh.h: the better tree) or on the
-    // device (Morton-order tree, pt_build.h: ~100x faster to build). PORTRAYER_BUILD = host | device | auto;
-    // auto takes the device for meshes of PORTRAYER_BUILD_MIN (default 65536) triangles or more.
-    int build_mode = 2;
-    size_t device_build_min = 65536;
-    if (const char* e = getenv("PORTRAYER_BUILD")) build_mode = !strcmp(e, "host") ? 0 : (!strcmp(e, "device") ? 1 : 2);
-    if (const char* e = getenv("PORTRAYER_BUILD_MIN")) device_build_min = (size_t)std::max(16, atoi(e));
-    struct DeviceMesh { uint32_t m, t0, count; double lo[3], hi[3], pad; };
-    std::vector<DeviceMesh> device_meshes;
-    std::vector<pt_context::Resident::MeshPlace> place(s->n_meshes);
-    for (uint32_t m = 0; m < s->n_meshes; m++) {
-        uint64_t v0 = s->mesh_vert_off[m], v1 = s->mesh_vert_off[m + 1], t0 = s->mesh_tri_off[m], t1 = s->mesh_tri_off[m + 1];
-        if (v1 <= v0) return pt_fail(c, PT_ERR_SCENE, "meshes must have at least one vertex (mesh.rs:71)");
-        const double* pos = s->mesh_positions + 3 * v0;
-        const double* nrm = (s->mesh_normals && s->mesh_has_normals && s->mesh_has_normals[m]) ? s->mesh_normals + 3 * v0 : nullptr;
-        PtBuildBox mb;
-        const double ext = pt_mesh_vertex_box(pos, v1 - v0, &mb);
-        const bool on_device = (build_mode == 1 && t1 - t0 >= 16) || (build_mode == 2 && t1 - t0 >= device_build_min);
-        std::vector<PtBuildBox> boxes(on_device ? 0 : t1 - t0);
-        std::vector<uint32_t> ids(on_device ? 0 : t1 - t0);
-        for (uint64_t t = t0; t < t1; t++) {
-            PtBuildBox b = pt_bvh_detail::empty_box();
-            for (int corner = 0; corner < 3; corner++) {
-                uint32_t vi = s->mesh_indices[3 * t + corner];
-                if (vi >= v1 - v0) return pt_fail(c, PT_ERR_ARGUMENT, "mesh index out of range");
-                for (int k = 0; k < 3; k++) {
-                    double x = pos[3 * (size_t)vi + k];
-                    tri_v[9 * t + 3 * corner + k] = x;
-                    if (any_normals) tri_n[9 * t + 3 * corner + k] = nrm ? nrm[3 * (size_t)vi + k] : 0.0;
-                    b.lo[k] = std::min(b.lo[k], x); b.hi[k] = std::max(b.hi[k], x);
-                }
-            }
-            if (on_device) continue;
-            for (int k = 0; k < 3; k++) { b.lo[k] -= 1e-7 * ext; b.hi[k] += 1e-7 * ext; }
-            boxes[t - t0] = b;
-            ids[t - t0] = (uint32_t)t;
-        }
-        PtBvhRef ref;
-        ref.child = PT_REF_EMPTY; ref.depth = 0;
-        pt_context::Resident::MeshPlace& pl = place[m];
-        pl.n_verts = (uint32_t)(v1 - v0); pl.has_normals = nrm != nullptr; pl.device_built = on_device;
-        pl.node_first = (uint32_t)bvh.size(); pl.item_first = (uint32_t)items.size();
-        if (on_device) {  // built after the triangles are in HBM (below); the root is filled in then
-            DeviceMesh dm;
-            dm.m = m; dm.t0 = (uint32_t)t0; dm.count = (uint32_t)(t1 - t0);
-            for (int k = 0; k < 3; k++) { dm.lo[k] = mb.lo[k]; dm.hi[k] = mb.hi[k]; }
-            dm.pad = 1e-7 * ext;
-            device_meshes.push_back(dm);
-        } else {
-            ref = pt_bvh_build(boxes.data(), ids.data(), boxes.size(), blas_leaf, bvh, items);
-            pl.node_count = (uint32_t)bvh.size() - pl.node_first; pl.item_count = (uint32_t)items.size() - pl.item_first; pl.depth = ref.depth;
-        }
-        max_blas_depth = std::max(max_blas_depth, ref.depth);
-        PtMeshInfo& mi = meshes[m];
-        for (int r = 0; r < 12; r++) mi.bbox_inv[r] = s->mesh_bounds_invtrans ? s->mesh_bounds_invtrans[16 * (size_t)m + r] : 0.0;
-        if (!s->mesh_bounds_invtrans) return pt_fail(c, PT_ERR_ARGUMENT, "mesh_bounds_invtrans missing");
-        mi.tri_first = (uint32_t)t0; mi.tri_count = (uint32_t)(t1 - t0);
-        mi.blas_root = ref.child; mi.kd_root = -1; mi.kd_extent = 0.0;
-        for (int r = 0; r < 12; r++) mi.kd_bbox_inv[r] = 0.0;
-        for (int k = 0; k < 3; k++) { mb.lo[k] -= 1e-5 * ext; mb.hi[k] += 1e-5 * ext; }
-        mesh_box[m] = mb;
-    }
-    lap("triangles + mesh trees");
-    // ---- KDMesh triangle trees (reference structure)
-    std::vector<PtKdNode> mkd;
-    std::vector<uint32_t> mkd_items;
-    std::vector<float> mkd_box, mkd_item_box;  // conservative f32 bounds per KDMesh tree node / per leaf reference (pt_kdmesh_hit's culls)
-    int max_kdm_depth = 0;
-    bool any_kdmesh = false;
-    if (s->mesh_kd_root && s->n_kdm_nodes) {
-        if (!s->kdm_axis || !s->kdm_plane || !s->kdm_front || !s->kdm_back || !s->kdm_first || !s->kdm_count || (s->n_kdm_items && !s->kdm_items) ||
-            !s->mesh_kd_bounds || !s->mesh_kd_bounds_invtrans)
-            return pt_fail(c, PT_ERR_ARGUMENT, "incomplete KDMesh tree arrays");
-        mkd.resize(s->n_kdm_nodes);
-        for (uint32_t i = 0; i < s->n_kdm_nodes; i++) {
-            PtKdNode& k = mkd[i];
-            k.axis = s->kdm_axis[i]; k.plane = s->kdm_plane[i]; k.front = s->kdm_front[i]; k.back = s->kdm_back[i];
-            k.first = s->kdm_first[i]; k.count = s->kdm_count[i]; k.pad = 0; k.pad2[0] = k.pad2[1] = 0.0f; for (int r = 0; r < 6; r++) k.box[r] = 0.0f;
-            if (k.axis >= 0) {
-                if (k.axis > 2 || k.front < 0 || k.back < 0 || (uint32_t)k.front >= s->n_kdm_nodes || (uint32_t)k.back >= s->n_kdm_nodes)
-                    return pt_fail(c, PT_ERR_ARGUMENT, "KDMesh tree child out of range");
-            } else if (k.first < 0 || k.count < 0 || (uint32_t)(k.first + k.count) > s->n_kdm_items) {
-                return pt_fail(c, PT_ERR_ARGUMENT, "KDMesh leaf range out of bounds");
-            }
-        }
-        mkd_items.assign(s->n_kdm_items, 0);
-        mkd_box.assign(6 * (size_t)s->n_kdm_nodes, 0.0f);
-        mkd_item_box.assign(6 * (size_t)s->n_kdm_items, 0.0f);
-        // leaf items are local triangle indices: make them global, mesh by mesh (a leaf belongs to the mesh whose tree reaches it)
-        std::vector<int32_t> owner(s->n_kdm_nodes, -1);
-        for (uint32_t m = 0; m < s->n_meshes; m++) {
-            int32_t root = s->mesh_kd_root[m];
-            if (root < 0) continue;
-            if ((uint32_t)root >= s->n_kdm_nodes) return pt_fail(c, PT_ERR_ARGUMENT, "KDMesh root out of range");
-            std::vector<int32_t> todo{root}, visited;
-            const double tri_pad = 1e-7 * std::max(std::max(mesh_box[m].hi[0] - mesh_box[m].lo[0], mesh_box[m].hi[1] - mesh_box[m].lo[1]),
-                                                   std::max(mesh_box[m].hi[2] - mesh_box[m].lo[2], 1e-30));
-            while (!todo.empty()) {
-                int32_t i = todo.back(); todo.pop_back();
-                if (owner[i] >= 0) return pt_fail(c, PT_ERR_ARGUMENT, "KDMesh trees must not share nodes");
-                owner[i] = (int32_t)m;
-                visited.push_back(i);
-                if (mkd[i].axis >= 0) { todo.push_back(mkd[i].front); todo.push_back(mkd[i].back); }
-                else for (int32_t k = 0; k < mkd[i].count; k++) {
-                    int32_t local = s->kdm_items[mkd[i].first + k];
-                    if (local < 0 || (uint64_t)local >= s->mesh_tri_off[m + 1] - s->mesh_tri_off[m]) return pt_fail(c, PT_ERR_ARGUMENT, "KDMesh leaf triangle out of range");
-                    const uint64_t g = s->mesh_tri_off[m] + (uint64_t)local;
-                    mkd_items[mkd[i].first + k] = (uint32_t)g;
-                    float* ib = &mkd_item_box[6 * (size_t)(mkd[i].first + k)];  // the triangle's padded box, for the walk's pre-cull
-                    for (int r = 0; r < 3; r++) {
-                        const double* v = &tri_v[9 * g];
-                        ib[r] = pt_bvh_detail::round_down(std::min(v[r], std::min(v[3 + r], v[6 + r])) - tri_pad);
-                        ib[3 + r] = pt_bvh_detail::round_up(std::max(v[r], std::max(v[3 + r], v[6 + r])) + tri_pad);
-                    }
-                }
-            }
-            for (size_t vi = visited.size(); vi-- > 0;) {  // children were discovered after their parents: bounds bottom-up
-                const int32_t i = visited[vi];
-                float* b = &mkd_box[6 * (size_t)i];
-                for (int r = 0; r < 3; r++) { b[r] = (float)PT_BOX_LIMIT; b[3 + r] = -(float)PT_BOX_LIMIT; }
-                auto grow = [&](const float* o) { for (int r = 0; r < 3; r++) { b[r] = std::min(b[r], o[r]); b[3 + r] = std::max(b[3 + r], o[3 + r]); } };
-                if (mkd[i].axis >= 0) { grow(&mkd_box[6 * (size_t)mkd[i].front]); grow(&mkd_box[6 * (size_t)mkd[i].back]); }
-                else for (int32_t k = 0; k < mkd[i].count; k++) grow(&mkd_item_box[6 * (size_t)(mkd[i].first + k)]);
-            }
-            PtMeshInfo& mi = meshes[m];
-            mi.kd_root = root;
-            any_kdmesh = true;
-            const double* b = s->mesh_kd_bounds + 6 * (size_t)m;
-            double dx = b[3] - b[0], dy = b[4] - b[1], dz = b[5] - b[2];
-            mi.kd_extent = (dx * dx + dy * dy) + dz * dz;  // bounding_box.rs:95-99
-            for (int r = 0; r < 12; r++) mi.kd_bbox_inv[r] = s->mesh_kd_bounds_invtrans[16 * (size_t)m + r];
-            max_kdm_depth = std::max(max_kdm_depth, s->mesh_kd_depth ? std::max(s->mesh_kd_depth[m], 0) : 24);
-        }
-    }
-    for (uint32_t t = 0; t < s->n_triangles; t++)
-        for (int k = 0; k < 9; k++) {
-            tri_v[9 * (mesh_tris + t) + k] = s->tri_vertices[9 * (size_t)t + k];
-            if (any_normals) tri_n[9 * (mesh_tris + t) + k] = s->tri_normals ? s->tri_normals[9 * (size_t)t + k] : 0.0;
-        }
-
-    // ---- nodes
-    std::vector<double> inv, fwd, nrm;
-    std::vector<uint32_t> info(4 * (size_t)n);
-    PtGraphArrays graph;
-    std::vector<uint32_t> chain_off, chain, dfs_rank;
-    if (traverse == PT_TRAVERSE_HIER && n) {
-        const uint32_t g = s->n_graph_nodes;
-        chain_off.assign(s->node_chain_off, s->node_chain_off + n + 1);
-        if (chain_off[0] != 0) return pt_fail(c, PT_ERR_ARGUMENT, "node_chain_off must start at 0");
-        for (uint32_t i = 0; i < n; i++)
-            if (chain_off[i + 1] <= chain_off[i]) return pt_fail(c, PT_ERR_ARGUMENT, "every flattened node needs a non-empty path (it contains at least itself)");
-        chain.assign(s->node_chain, s->node_chain + chain_off[n]);
-        for (uint32_t id : chain) if (id >= g) return pt_fail(c, PT_ERR_ARGUMENT, "node_chain names a graph node out of range");
-        dfs_rank.assign(s->node_dfs_rank, s->node_dfs_rank + n);
-        pt_pack_graph(n, g, s->graph_trans, s->graph_invtrans, s->graph_normal_trans, chain_off, chain, graph);
-    }
-    pt_pack_node_matrices(n, s->trans, s->invtrans, s->normal_trans, inv, fwd, nrm);
-    std::vector<PtBuildBox> tri_box(s->n_triangles);
-    for (uint32_t t = 0; t < s->n_triangles; t++) pt_triangle_model_box(&tri_v[9 * (mesh_tris + t)], &tri_box[t]);
-    for (uint32_t i = 0; i < n; i++) {
-        int t = s->prim_type[i];
-        uint32_t data = (uint32_t)s->prim_data[i];
-        if (t == PT_PRIM_TRIANGLE) data = (uint32_t)(mesh_tris + data);
-        info[4 * (size_t)i] = (uint32_t)t; info[4 * (size_t)i + 1] = data;
-        info[4 * (size_t)i + 2] = (uint32_t)s->prim_flags[i]; info[4 * (size_t)i + 3] = (uint32_t)s->material[i];
-    }
-    std::vector<PtBuildBox> node_box;
-    pt_node_world_boxes(n, s->trans, info.data(), mesh_box, tri_box, mesh_tris, node_box, c->root_lo, c->root_hi);
-    int tlas_leaf = 1;  // primitive tests (f64, ~200 instructions) cost far more than a node visit: measured best on big-scene
-    if (const char* e = getenv("PORTRAYER_TLAS_LEAF")) tlas_leaf = std::max(1, atoi(e));
-    const bool tlas_direct = tlas_leaf == 1 && n < (1u << 28);
-    // the scene-level tree keeps room for the n - 1 nodes any tree over n leaves can have: pt_scene_update builds its trees into the same place
-    const size_t tlas_first = bvh.size(), tlas_items = items.size(), tlas_cap = n ? n - 1 : 0;
-    PtBvhRef tlas;
-    {
-        std::vector<PtBvhNode> tl_nodes;
-        std::vector<uint32_t> tl_items;
-        tlas = pt_build_scene_tree(node_box, tlas_leaf, tlas_direct, tlas_first, tlas_items, tl_nodes, tl_items);
-        bvh.insert(bvh.end(), tl_nodes.begin(), tl_nodes.end());
-        items.insert(items.end(), tl_items.begin(), tl_items.end());
-        PtBvhNode unused;
-        memset(&unused, 0, sizeof unused);
-        unused.child0 = unused.child1 = PT_REF_EMPTY;
-        bvh.resize(tlas_first + tlas_cap, unused);
-    }
-    const size_t tlas_end = bvh.size();
-
-    // ---- k-d tree (reference structure, KD mode)
-    PtKdArrays kda;
-    int rc;
-    if (traverse == PT_TRAVERSE_KD && (rc = pt_pack_kd(c, kd, n, node_box, kda))) return rc;
-    lap("scene tree");
-    if ((rc = pt_upload(c, c->tri_v, tri_v))) return rc;
-    {   // the edge form of every triangle (pt_triangle_hit_e): corner a, a - b, a - c
-        std::vector<double> tri_e(tri_v.size());
-        for (size_t t = 0; t < total_tris; t++) {
-            const double* v = &tri_v[9 * t];
-            double* e = &tri_e[9 * t];
-            e[0] = v[0]; e[1] = v[1]; e[2] = v[2];
-            e[3] = v[0] - v[3]; e[4] = v[1] - v[4]; e[5] = v[2] - v[5];
-            e[6] = v[0] - v[6]; e[7] = v[1] - v[7]; e[8] = v[2] - v[8];
-        }
-        if ((rc = pt_upload(c, c->tri_e, tri_e))) return rc;
-    }
-    size_t tree_nodes = 0;
-    {   // tree arrays: the host-built part first, then room for the device-built mesh trees
-        size_t n_nodes = bvh.size(), n_items = items.size();
-        for (const DeviceMesh& dm : device_meshes) { n_nodes += PT_DEVICE_TREE_NODES(dm.count); n_items += PT_DEVICE_TREE_ITEMS(dm.count, blas_leaf); }
-        if (n_items >= (1u << 28) || n_nodes >= (1u << 26)) return pt_fail(c, PT_ERR_SCENE, "too many triangles for the 32-bit tree references (a node is addressed by a 32-bit byte offset: 2^26 nodes)");
-        if ((rc = pt_reserve(c, c->bvh, n_nodes * sizeof(PtBvhNode))) || (rc = pt_reserve(c, c->bvh_items, n_items * sizeof(uint32_t)))) return rc;
-        if (!bvh.empty()) PT_HIP(c, hipMemcpy(c->bvh.p, bvh.data(), bvh.size() * sizeof(PtBvhNode), hipMemcpyHostToDevice));
-        if (!items.empty()) PT_HIP(c, hipMemcpy(c->bvh_items.p, items.data(), items.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-        lap("upload triangles + host trees");
-        uint32_t node_base = (uint32_t)bvh.size(), item_base = (uint32_t)items.size();
-        float device_ms = 0.0f;
-        int rounds = 0;
-        for (const DeviceMesh& dm : device_meshes) {
-            PtDeviceBuildResult res;
-            pt_context::Resident::MeshPlace& pl = place[dm.m];
-            pl.node_first = node_base; pl.node_count = PT_DEVICE_TREE_NODES(dm.count); pl.item_first = item_base; pl.item_count = PT_DEVICE_TREE_ITEMS(dm.count, blas_leaf);
-            // entries of the place that the tree will not use name no children (pt_device_tree_parents reads the whole range)
-            PT_HIP(c, hipMemset((PtBvhNode*)c->bvh.p + node_base, 0xFF, (size_t)pl.node_count * sizeof(PtBvhNode)));
-            PT_HIP(c, pt_device_build_mesh_tree((const double*)c->tri_v.p, dm.t0, dm.count, dm.lo, dm.hi, dm.pad, blas_leaf, (PtBvhNode*)c->bvh.p, node_base,
-                                                (uint32_t*)c->bvh_items.p, item_base, nullptr, &res));
-            meshes[dm.m].blas_root = res.root;
-            max_blas_depth = std::max(max_blas_depth, res.depth);
-            pl.depth = res.depth;
-            node_base += PT_DEVICE_TREE_NODES(dm.count); item_base += PT_DEVICE_TREE_ITEMS(dm.count, blas_leaf);
-            device_ms += res.ms; rounds += res.rounds;
-        }
-        if (verbose && !device_meshes.empty()) fprintf(stderr, "[pt_scene_upload] device tree build: %zu mesh(es), %.2f ms, %d clustering rounds, depth %d\n", device_meshes.size(), device_ms, rounds, max_blas_depth);
-        lap("device mesh trees");
-        // the walks read the four-child form of every tree (scene tree and mesh trees alike)
-        if (const char* e = getenv("PORTRAYER_COLLAPSE")) collapse_mode = strcmp(e, "plain") == 0 ? 0 : (strcmp(e, "area") == 0 ? 2 : 1);
-        if ((rc = pt_reserve(c, c->bvh4, std::max<size_t>(n_nodes, 1) * sizeof(PtBvh4Node)))) return rc;
-        if (n_nodes) {
-            hipLaunchKernelGGL(pt_collapse4_kernel, dim3((unsigned)((n_nodes + 255) / 256)), dim3(256), 0, nullptr, (const PtBvhNode*)c->bvh.p, (PtBvh4Node*)c->bvh4.p, (uint32_t)n_nodes, collapse_mode, (uint32_t)tlas_first, (uint32_t)tlas_end, 0u, (uint32_t)n_nodes);
-            PT_HIP(c, hipGetLastError());
-            PT_HIP(c, hipDeviceSynchronize());
-        }
-        tree_nodes = n_nodes;
-        lap("four-child form");
-        if ((rc = pt_reserve(c, c->tri_leaf, std::max<size_t>(n_items, 1) * 80))) return rc;
-        if (n_items && total_tris) {
-            hipLaunchKernelGGL(pt_tri_leaf_kernel, dim3((unsigned)((n_items + 255) / 256)), dim3(256), 0, nullptr, (const uint32_t*)c->bvh_items.p, (uint32_t)n_items, (const double*)c->tri_e.p,
-                               (uint32_t)total_tris, (double*)c->tri_leaf.p);
-            PT_HIP(c, hipGetLastError());
-            PT_HIP(c, hipDeviceSynchronize());
-        }
-        lap("triangle records in leaf order");
-    }
-    for (size_t i = 0; i < mkd.size() && !mkd_box.empty(); i++) for (int r = 0; r < 6; r++) mkd[i].box[r] = mkd_box[6 * i + r];
-    if ((rc = pt_upload(c, c->g_inv, graph.g_inv)) || (rc = pt_upload(c, c->g_fwd, graph.g_fwd)) || (rc = pt_upload(c, c->g_nrm, graph.g_nrm)) ||
-        (rc = pt_upload(c, c->chain_off, chain_off)) || (rc = pt_upload(c, c->chain, chain)) || (rc = pt_upload(c, c->dfs_rank, dfs_rank)) ||
-        (rc = pt_upload(c, c->hier_rec, graph.hier_rec)) || (rc = pt_upload(c, c->own_inv, graph.own_inv)))
-        return rc;
-    if ((rc = pt_upload(c, c->inv, inv)) || (rc = pt_upload(c, c->fwd, fwd)) || (rc = pt_upload(c, c->nrm, nrm)) ||
-        (rc = pt_upload(c, c->info, info)) || (rc = pt_upload(c, c->tri_n, tri_n)) ||
-        (rc = pt_upload(c, c->meshes, meshes)) || (rc = pt_upload(c, c->mkd, mkd)) ||
-        (rc = pt_upload(c, c->mkd_items, mkd_items)) || (rc = pt_upload(c, c->mkd_box, mkd_box)) || (rc = pt_upload(c, c->mkd_item_box, mkd_item_box)))
-        return rc;
-    std::vector<double> mats(s->materials, s->materials + 10 * (size_t)s->n_materials);
-    c->needs_spill = s->n_lights > PT_LIGHT_ROUND;
-    c->spawns = false;
-    for (uint32_t m = 0; m < s->n_materials; m++) if (mats[10 * (size_t)m + 7] > 0.0) c->needs_spill = c->spawns = true;  // material.rs:216: reflectivity > 0 spawns children
-    // The 4-waves-per-SIMD kernel for scenes where the tree walk outweighs the shading: many scene-level nodes or many instanced
-    // triangles, nothing reflective, flat_scene semantics (measured: big-scene +8.7 %, big-soup +6.8 %; macho-cows
-    // with its 23 nodes and 17,500 triangles -8 %; reflective scenes and the k-d walk lose, profiles/r02/notes.md)
-    {
-        uint64_t instanced_tris = 0;
-        for (uint32_t i = 0; i < n; i++)
-            if (s->prim_type[i] == PT_PRIM_MESH || s->prim_type[i] == PT_PRIM_KDMESH) instanced_tris += s->mesh_tri_off[s->prim_data[i] + 1] - s->mesh_tri_off[s->prim_data[i]];
-        // hierarchical semantics (round 3, straight-line kernel): mesh-free scenes with many nodes gain like flat_scene ones (big-scene 25.7 ->
-        // 29.4 Gray/s at 4 waves); with mesh instances the walk carries a second ray and spills at 128 registers (macho-cows 16.4 -> 12.0) unless
-        // the triangle trees dominate (the 1.25 M-triangle soup: equal)
-        // Since the register work of round 3 (arguments re-read, colour parked in LDS, an instantiation of the hierarchical semantics without
-        // the KDMesh walker) scenes with plain Mesh instances of any size gain too (c41: macho-cows 21.4 -> 23.4 Gray/s, hierarchical 18.7 -> 19.7);
-        // with KDMesh trees the kernels still spill 100+ registers at 128 and stay at 3 waves unless the triangle trees dominate.
-        const bool plain_meshes = s->n_meshes > 0 && !any_kdmesh;
-        c->four_waves = !c->spawns && ((traverse == PT_TRAVERSE_FLAT && (n >= 256 || instanced_tris >= 65536)) ||
-                                       (traverse == PT_TRAVERSE_HIER && ((s->n_meshes == 0 && n >= 256) || instanced_tris >= 65536)));
-        c->four_waves_untextured = !c->spawns && plain_meshes && (traverse == PT_TRAVERSE_FLAT || traverse == PT_TRAVERSE_HIER);  // (textured: flat_scene loses 10 % at 4 waves, c45)
-        // The hierarchical semantics without KDMesh trees gain at 4 waves whatever the scene (their leaf tests wait for a path record and a matrix per
-        // level): macho-cows +5 %, fish (textured) +5 %, normal-mapping (11 textured primitives) +12 %, the mirror scene's chain kernel +9 % (c41, c45).
-        c->four_waves_hier = !c->spawns && traverse == PT_TRAVERSE_HIER && !any_kdmesh;
-        // mesh-free scenes go one further: 5 waves per SIMD (96 registers, 17 of the kernel's spilled; big-scene 34.4 -> 37.0, hierarchical
-        // 29.4 -> 32.5 Gray/s; the k-d walk, 50 spilled, loses and stays at 4)
-        c->five_waves = c->four_waves && s->n_meshes == 0 && traverse != PT_TRAVERSE_KD;
-        // ... and so do scenes of very many triangles in plain Mesh instances (round 4, c29: their walks wait for node fetches - 3 -> 4 waves was +18 % -; the 1.25 M-triangle
-        // scenes +3.7 % / +3.2 %, hierarchical +2.6 %, at 96 registers with 57 spilled; macho-cows, 17,500 triangles, loses 15 % and stays at 4)
-        // Round 5 (c47 / c48, after the tree step and the instance walk issue fewer scalar instructions): flat_scene is now FASTER at 4 waves (big-soup 18.96 -> 18.75 ms,
-        // big-mesh 19.16 -> 18.86; 18 spilled registers instead of 69) and takes 4; the hierarchical semantics still gain 1 % at 5 and keep them.
-        c->five_waves_mesh = !c->spawns && plain_meshes && instanced_tris >= 65536 && traverse == PT_TRAVERSE_HIER;
-    }
-    std::vector<double> lights(s->lights, s->lights + 15 * (size_t)s->n_lights);
-    {   // what the materials say about the recursion; the lights have their say in pt_set_light_flags
-        bool draws = false, dielectric = false;
-        for (uint32_t m = 0; m < s->n_materials; m++) {
-            if (mats[10 * (size_t)m + 7] > 0.0 && mats[10 * (size_t)m + 8] > 0.0) draws = true;   // glossy reflection (material.rs:221-239)
-            if (mats[10 * (size_t)m + 7] > 0.0 && mats[10 * (size_t)m + 9] > 0.0) dielectric = true;
-        }
-        c->res.mat_draws = draws; c->res.dielectric = dielectric;
-        pt_set_light_flags(c, lights.data(), s->n_lights);
-    }
-    if ((rc = pt_upload(c, c->materials, mats)) || (rc = pt_upload(c, c->lights, lights))) return rc;
-
-    // ---- textures / normal maps (texture.rs)
-    bool textured = false;
-    for (uint32_t m = 0; m < s->n_materials; m++)
-        if ((s->material_texture && s->material_texture[m] >= 0) || (s->material_normal_map && s->material_normal_map[m] >= 0)) textured = true;
-    std::vector<int32_t> mat_maps;
-    std::vector<double> uv_trans, srgb_lut, tri_uv;
-    std::vector<PtTexInfo> texinfo;
-    std::vector<uint8_t> tex_rgb;
-    if (textured) {
-        if (s->n_textures == 0 || !s->texture_size || !s->texture_offset || !s->texture_rgb) return pt_fail(c, PT_ERR_ARGUMENT, "textured material without texture data");
-        size_t tex_bytes = 0;
-        texinfo.resize(s->n_textures);
-        for (uint32_t t = 0; t < s->n_textures; t++) {
-            texinfo[t].offset = s->texture_offset[t]; texinfo[t].width = s->texture_size[2 * t]; texinfo[t].height = s->texture_size[2 * t + 1];
-            if (texinfo[t].width == 0 || texinfo[t].height == 0) return pt_fail(c, PT_ERR_ARGUMENT, "empty texture");
-            tex_bytes = std::max(tex_bytes, (size_t)texinfo[t].offset + 3 * (size_t)texinfo[t].width * texinfo[t].height);
-        }
-        tex_rgb.assign(s->texture_rgb, s->texture_rgb + tex_bytes);
-        mat_maps.resize(2 * (size_t)s->n_materials);
-        uv_trans.resize(9 * (size_t)s->n_materials);
-        for (uint32_t m = 0; m < s->n_materials; m++) {
-            int32_t a = s->material_texture ? s->material_texture[m] : -1, b = s->material_normal_map ? s->material_normal_map[m] : -1;
-            if (a >= (int32_t)s->n_textures || b >= (int32_t)s->n_textures) return pt_fail(c, PT_ERR_ARGUMENT, "texture index out of range");
-            mat_maps[2 * m] = a < 0 ? -1 : a; mat_maps[2 * m + 1] = b < 0 ? -1 : b;
-            for (int k = 0; k < 9; k++) uv_trans[9 * (size_t)m + k] = s->material_uv_trans ? s->material_uv_trans[9 * (size_t)m + k] : (k % 4 == 0 ? 1.0 : 0.0);
-        }
-        srgb_lut.resize(256);
-        for (int k = 0; k < 256; k++) srgb_lut[k] = std::pow((double)k / 255.0, PT_GAMMA);  // texture.rs:167: c.powf(GAMMA), c = byte / 255
-        tri_uv.assign(total_tris * 6, 0.0);
-        std::vector<uint8_t> tri_has_uv(total_tris, 0);
-        for (uint32_t m = 0; m < s->n_meshes; m++) {
-            if (!(s->mesh_texcoords && s->mesh_has_texcoords && s->mesh_has_texcoords[m])) continue;
-            uint64_t v0 = s->mesh_vert_off[m];
-            for (uint64_t t = s->mesh_tri_off[m]; t < s->mesh_tri_off[m + 1]; t++) {
-                for (int corner = 0; corner < 3; corner++) {
-                    uint64_t vi = v0 + s->mesh_indices[3 * t + corner];
-                    tri_uv[6 * t + 2 * corner] = s->mesh_texcoords[2 * vi]; tri_uv[6 * t + 2 * corner + 1] = s->mesh_texcoords[2 * vi + 1];
-                }
-                tri_has_uv[t] = 1;
-            }
-        }
-        for (uint32_t t = 0; t < s->n_triangles; t++)
-            if (s->tri_texcoords && s->tri_has_texcoords && s->tri_has_texcoords[t]) {
-                for (int k = 0; k < 6; k++) tri_uv[6 * (mesh_tris + t) + k] = s->tri_texcoords[6 * (size_t)t + k];
-                tri_has_uv[mesh_tris + t] = 1;
-            }
-        // material.rs:133 / :141: the reference panics when a mapped material meets a primitive without texture coordinates
-        for (uint32_t i = 0; i < n; i++) {
-            int32_t m = s->material[i];
-            if (mat_maps[2 * m] < 0 && mat_maps[2 * m + 1] < 0) continue;
-            int t = s->prim_type[i];
-            bool ok = t == PT_PRIM_SPHERE || t == PT_PRIM_CUBE || t == PT_PRIM_PLANE;
-            if (t == PT_PRIM_TRIANGLE) ok = tri_has_uv[mesh_tris + (size_t)s->prim_data[i]];
-            if (t == PT_PRIM_MESH || t == PT_PRIM_KDMESH) ok = s->mesh_tri_off[s->prim_data[i] + 1] == s->mesh_tri_off[s->prim_data[i]] || tri_has_uv[s->mesh_tri_off[s->prim_data[i]]];
-            if (!ok) return pt_fail(c, PT_ERR_SCENE, "Texture mapping is not supported for this primitive! (material.rs:133,141)");
-        }
-        if ((rc = pt_upload(c, c->mat_maps, mat_maps)) || (rc = pt_upload(c, c->uv_trans, uv_trans)) || (rc = pt_upload(c, c->tex, texinfo)) ||
-            (rc = pt_upload(c, c->tex_rgb, tex_rgb)) || (rc = pt_upload(c, c->srgb_lut, srgb_lut)) || (rc = pt_upload(c, c->tri_uv, tri_uv)))
-            return rc;
-    }
-
-    PtSceneView& v = c->view;
-    memset(&v, 0, sizeof v);
-    v.n_nodes = n; v.n_lights = s->n_lights;
-    v.inv = (const double*)c->inv.p; v.fwd = (const double*)c->fwd.p; v.nrm = (const double*)c->nrm.p;
-    v.info = (const uint32_t*)c->info.p; v.tri_v = (const double*)c->tri_v.p; v.tri_e = (const double*)c->tri_e.p; v.tri_leaf = (const double*)c->tri_leaf.p; v.tri_n = (const double*)c->tri_n.p;
-    v.meshes = (const PtMeshInfo*)c->meshes.p; v.materials = (const double*)c->materials.p; v.lights = (const double*)c->lights.p;
-    for (int k = 0; k < 3; k++) v.ambient[k] = s->ambient[k];
-    v.bvh = (const PtBvhNode*)c->bvh.p; v.bvh4 = (const PtBvh4Node*)c->bvh4.p; v.bvh_items = (const uint32_t*)c->bvh_items.p;
-    v.tlas_root = tlas.child; v.tlas_direct = tlas_direct ? 1u : 0u;
-    // the octant-sorted slab test inside mesh instances (pt_trace_packet_mesh; round 4, c32: the 1.25 M-triangle scenes +6.0 % / +3.1 %, macho-cows and the
-    // mirror scene +0.6 %; PORTRAYER_MESH_OCT=0 walks every triangle tree with the per-lane form again)
-    v.mesh_oct = 1u;
-    if (const char* e = getenv("PORTRAYER_MESH_OCT")) v.mesh_oct = atoi(e) > 0 ? 1u : 0u;
-    if ((rc = pt_upload_kd(c, kda, traverse == PT_TRAVERSE_KD))) return rc;
-    v.mkd = mkd.empty() ? nullptr : (const PtKdNode*)c->mkd.p; v.mkd_items = (const uint32_t*)c->mkd_items.p;  // (null without KDMesh trees: the k-d walk then keeps no LDS rows for lane stacks)
-    v.mkd_box = mkd_box.empty() || getenv("PORTRAYER_KD_NO_CULL") ? nullptr : (const float*)c->mkd_box.p;
-    v.mkd_item_box = v.mkd_box ? (const float*)c->mkd_item_box.p : nullptr;
-    v.mode = traverse == PT_TRAVERSE_KD ? (s->n_meshes == 0 ? PT_MODE_KD_NOMESH : (any_kdmesh ? PT_MODE_KD : PT_MODE_KD_MESH)) : (s->n_meshes == 0 ? PT_MODE_FLAT_NOMESH : (any_kdmesh ? PT_MODE_FLAT_KDMESH : PT_MODE_FLAT));
-    if (traverse == PT_TRAVERSE_HIER) {  // the general walker (meshes and KDMesh trees compiled in), or its mesh-free instantiation
-        v.mode = s->n_meshes == 0 ? PT_MODE_HIER_NOMESH : (any_kdmesh ? PT_MODE_HIER : PT_MODE_HIER_MESH);
-        v.g_inv = (const double*)c->g_inv.p; v.g_fwd = (const double*)c->g_fwd.p; v.g_nrm = (const double*)c->g_nrm.p;
-        v.chain_off = (const uint32_t*)c->chain_off.p; v.chain = (const uint32_t*)c->chain.p; v.dfs_rank = (const uint32_t*)c->dfs_rank.p;
-        v.hier_rec = (const uint32_t*)c->hier_rec.p; v.own_inv = (const double*)c->own_inv.p;
-    }
-    {   // what pt_scene_update needs later (pt_context::Resident)
-        pt_context::Resident& r = c->res;
-        r.traverse = traverse; r.n_nodes = n; r.n_graph = traverse == PT_TRAVERSE_HIER && n ? s->n_graph_nodes : 0u; r.n_lights = s->n_lights;
-        r.mesh_tris = mesh_tris; r.tlas_first = tlas_first; r.tlas_cap = tlas_cap; r.tlas_items = tlas_items; r.tree_nodes = tree_nodes;
-        r.tlas_leaf = tlas_leaf; r.collapse_mode = collapse_mode;
-        r.last_builder = 0; r.last_rounds = 0;
-        auto wide = [&](int depth2) { return collapse_mode ? 3 * depth2 : 3 * ((depth2 + 1) / 2); };
-        r.below = std::max(wide(max_blas_depth), 3 * (max_kdm_depth + 1));  // deepest walk under a scene leaf: a mesh tree or a KDMesh tree
-        std::vector<double> mb(6 * mesh_box.size());
-        for (size_t m = 0; m < mesh_box.size(); m++) for (int k = 0; k < 3; k++) { mb[6 * m + k] = mesh_box[m].lo[k]; mb[6 * m + 3 + k] = mesh_box[m].hi[k]; }
-        if ((rc = pt_upload(c, c->mesh_box_dev, mb))) return rc;
-        r.info = std::move(info); r.mesh_box = std::move(mesh_box); r.tri_box = std::move(tri_box);
-        r.place = std::move(place); r.meshes = meshes; r.blas_leaf = blas_leaf; r.max_kdm_depth = max_kdm_depth; r.any_normals = any_normals;
-        r.indices.assign(s->mesh_indices, s->mesh_indices + (mesh_tris ? 3 * mesh_tris : 0)); r.indices_resident = false;
-        r.chain_off = std::move(chain_off); r.chain = std::move(chain);
-    }
-    const int cap_rc = pt_set_stack_cap(c, tlas.depth, kda.kd_depth);
-    if (textured) {
-        v.mat_maps = (const int32_t*)c->mat_maps.p; v.uv_trans = (const double*)c->uv_trans.p; v.tex = (const PtTexInfo*)c->tex.p;
-        v.tex_rgb = (const uint8_t*)c->tex_rgb.p; v.srgb_lut = (const double*)c->srgb_lut.p; v.tri_uv = (const double*)c->tri_uv.p;
-        std::vector<PtTexView> tv(1);
-        tv[0].tex = v.tex; tv[0].tex_rgb = v.tex_rgb; tv[0].uv_trans = v.uv_trans; tv[0].tri_v = v.tri_v; tv[0].tri_uv = v.tri_uv;
-        tv[0].mat_maps = v.mat_maps;
-        if ((rc = pt_upload(c, c->texview, tv))) return rc;
-        v.texview = (const PtTexView*)c->texview.p;
-    }
-    lap("upload the rest");
-    if (cap_rc) return cap_rc;
-    c->have_scene = true;
-    return PT_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
-// Scene update: the resident scene with new node matrices, lights and ambient light. Everything under a flattened node lives in model space
-// (triangle records, mesh trees, KDMesh trees, textures) and stays where it is; what depends on the matrices is recomputed by the functions
-// pt_scene_upload uses (above), and the scene-level tree is rebuilt in the place the upload reserved for it - on the host (pt_bvh_build: the
-// upload's tree) or on the device (pt_device_build_scene_tree), by the rule mesh trees follow: PORTRAYER_BUILD = host | device | auto,
-// auto takes the device from PORTRAYER_BUILD_MIN nodes on (default 65536), device from 16 on; PORTRAYER_TLAS_LEAF != 1: always the host.
-// ------------------------------------------------------------------------------------------------
-// What an update computes on the host before its first write (pt_update_prepare) and then writes (pt_update_commit). pt_scene_deform runs the same two
-// steps around its own writes, with the deformed meshes' new boxes.
-struct PtUpdatePlan {
-    std::vector<double> inv, fwd, nrm;
-    PtGraphArrays graph;
-    std::vector<PtBuildBox> node_box;
-    double root_lo[3], root_hi[3];
-    PtKdArrays kda;
-    bool direct = false, on_device = false;
-    std::vector<PtBvhNode> tl_nodes;
-    std::vector<uint32_t> tl_items;
-    PtBvhRef tlas;
-};
-
-// the copies and kernels of an update or a deform are not ordered against the context's non-blocking streams
-static int pt_refuse_in_flight(pt_context* c) {
-    bool in_flight = false;
-    for (const PtPass* v : c->passes) in_flight = in_flight || v->pending;
-    for (const auto& sl : c->slot) in_flight = in_flight || sl.pending;
-    if (in_flight) return pt_fail(c, PT_ERR_ARGUMENT, "a render is in flight: pt_render_finish / pt_aov_finish / pt_rays_finish / pt_radiance_finish first");
-    return PT_OK;
-}
-
-// Every check of pt_scene_update and everything its host side computes. `mesh_box`: the meshes' padded model boxes the moved scene has (the resident ones,
-// or a deform's). Writes nothing to the device; PT_ERR_SCENE leaves the context without a scene, as after a refused upload.
-// On the host-build path it does set view.stack_cap (pt_set_stack_cap) from the mesh depths as they are BEFORE the call: for a deform with rebuild = 1
-// that is half a check - a mesh tree the rebuild makes deeper is only seen by pt_update_commit, which computes the cap again after the writes and then
-// ends with PT_ERR_SCENE and no scene, as the header says.
-static int pt_update_prepare(pt_context* c, const pt_scene_motion* mo, const pt_kdtree* kd, const std::vector<PtBuildBox>& mesh_box, PtUpdatePlan& p) {
-    if (!c || !mo) return PT_ERR_ARGUMENT;
-    if (!c->have_scene) return pt_fail(c, PT_ERR_NO_SCENE, "no scene uploaded");
-    pt_context::Resident& res = c->res;
-    const uint32_t n = res.n_nodes;
-    if (mo->n_nodes != n) return pt_fail(c, PT_ERR_ARGUMENT, "n_nodes differs from the uploaded scene's");
-    if (n && (!mo->trans || !mo->invtrans || !mo->normal_trans)) return pt_fail(c, PT_ERR_ARGUMENT, "null node array");
-    if (mo->n_graph_nodes != res.n_graph) return pt_fail(c, PT_ERR_ARGUMENT, "n_graph_nodes differs from the uploaded scene's (0 unless it was uploaded with PT_TRAVERSE_HIER)");
-    if (res.n_graph && (!mo->graph_trans || !mo->graph_invtrans || !mo->graph_normal_trans))
-        return pt_fail(c, PT_ERR_ARGUMENT, "PT_TRAVERSE_HIER needs the scene graph's matrices (graph_*)");
-    if (mo->lights && mo->n_lights != res.n_lights) return pt_fail(c, PT_ERR_ARGUMENT, "n_lights differs from the uploaded scene's");
-    if (res.traverse == PT_TRAVERSE_KD && !kd) return pt_fail(c, PT_ERR_ARGUMENT, "PT_TRAVERSE_KD needs the host-built k-d tree");
-    if (res.traverse != PT_TRAVERSE_KD && kd) return pt_fail(c, PT_ERR_ARGUMENT, "a k-d tree for a scene that was not uploaded with PT_TRAVERSE_KD");
-    if (int rc = pt_refuse_in_flight(c)) return rc;
-
-    // ---- everything the host computes, before the first write
-    pt_pack_node_matrices(n, mo->trans, mo->invtrans, mo->normal_trans, p.inv, p.fwd, p.nrm);
-    if (res.n_graph) pt_pack_graph(n, res.n_graph, mo->graph_trans, mo->graph_invtrans, mo->graph_normal_trans, res.chain_off, res.chain, p.graph);
-    pt_node_world_boxes(n, mo->trans, res.info.data(), mesh_box, res.tri_box, res.mesh_tris, p.node_box, p.root_lo, p.root_hi);
-    int rc;
-    if (res.traverse == PT_TRAVERSE_KD && (rc = pt_pack_kd(c, kd, n, p.node_box, p.kda))) {
-        if (rc == PT_ERR_SCENE) c->have_scene = false;  // as after a refused upload
-        return rc;
-    }
-    int build_mode = 2;
-    size_t device_build_min = 65536;
-    if (const char* e = getenv("PORTRAYER_BUILD")) build_mode = !strcmp(e, "host") ? 0 : (!strcmp(e, "device") ? 1 : 2);
-    if (const char* e = getenv("PORTRAYER_BUILD_MIN")) device_build_min = (size_t)std::max(16, atoi(e));
-    p.direct = res.tlas_leaf == 1 && n < (1u << 28);
-    p.on_device = p.direct && ((build_mode == 1 && n >= 16) || (build_mode == 2 && n >= device_build_min));
-    p.tlas.child = PT_REF_EMPTY; p.tlas.depth = 0;
-    if (!p.on_device) {
-        p.tlas = pt_build_scene_tree(p.node_box, res.tlas_leaf, p.direct, res.tlas_first, res.tlas_items, p.tl_nodes, p.tl_items);
-        if (p.tl_nodes.size() > res.tlas_cap || p.tl_items.size() > (p.direct ? 0u : n)) return pt_fail(c, PT_ERR_DEVICE, "scene tree larger than its place");  // (a tree over n leaves has at most n - 1 nodes)
-        if ((rc = pt_set_stack_cap(c, p.tlas.depth, p.kda.kd_depth))) { c->have_scene = false; return rc; }
-    }
-    return PT_OK;
-}
-
-// ---- writes
-static int pt_update_commit(pt_context* c, const pt_scene_motion* mo, PtUpdatePlan& p) {
-    pt_context::Resident& res = c->res;
-    const uint32_t n = res.n_nodes;
-    int rc;
-    PT_HIP(c, hipSetDevice(c->device));
-    PT_HIP(c, hipDeviceSynchronize());  // passes whose _finish has been called may still have copies queued
-    c->have_scene = false;              // until every write below has been made
-    if ((rc = pt_upload(c, c->inv, p.inv)) || (rc = pt_upload(c, c->fwd, p.fwd)) || (rc = pt_upload(c, c->nrm, p.nrm))) return rc;
-    if (res.n_graph && ((rc = pt_upload(c, c->g_inv, p.graph.g_inv)) || (rc = pt_upload(c, c->g_fwd, p.graph.g_fwd)) || (rc = pt_upload(c, c->g_nrm, p.graph.g_nrm)) ||
-                        (rc = pt_upload(c, c->hier_rec, p.graph.hier_rec)) || (rc = pt_upload(c, c->own_inv, p.graph.own_inv))))
-        return rc;
-    if (res.traverse == PT_TRAVERSE_KD && (rc = pt_upload_kd(c, p.kda, true))) return rc;
-    for (int k = 0; k < 3; k++) { c->root_lo[k] = p.root_lo[k]; c->root_hi[k] = p.root_hi[k]; }
-    PtSceneView& v = c->view;
-    if (mo->lights) {
-        std::vector<double> lights(mo->lights, mo->lights + 15 * (size_t)mo->n_lights);
-        if ((rc = pt_upload(c, c->lights, lights))) return rc;
-        pt_set_light_flags(c, lights.data(), mo->n_lights);
-    }
-    if (mo->ambient) for (int k = 0; k < 3; k++) v.ambient[k] = mo->ambient[k];
-    PtBvhRef tlas = p.tlas;
-    if (p.on_device) {
-        PtDeviceBuildResult built;
-        PT_HIP(c, pt_device_build_scene_tree(n, (const double*)c->fwd.p, (const uint32_t*)c->info.p, (const double*)c->mesh_box_dev.p, (const double*)c->tri_v.p,
-                                             p.root_lo, p.root_hi, (PtBvhNode*)c->bvh.p, (uint32_t)res.tlas_first, nullptr, &built));
-        tlas.child = built.root; tlas.depth = built.depth;
-        if (getenv("PORTRAYER_VERBOSE")) fprintf(stderr, "[pt_scene_update] device scene tree: %u nodes, %.2f ms, %d clustering rounds, depth %d\n", n, built.ms, built.rounds, built.depth);
-        res.last_builder = 2; res.last_rounds = built.rounds;
-    } else {
-        res.last_builder = 1; res.last_rounds = 0;
-        if (!p.tl_nodes.empty()) PT_HIP(c, hipMemcpy((PtBvhNode*)c->bvh.p + res.tlas_first, p.tl_nodes.data(), p.tl_nodes.size() * sizeof(PtBvhNode), hipMemcpyHostToDevice));
-        if (!p.tl_items.empty()) PT_HIP(c, hipMemcpy((uint32_t*)c->bvh_items.p + res.tlas_items, p.tl_items.data(), p.tl_items.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    }
-    // the stack of the trees as they are now: the scene-level tree just built and (pt_scene_deform) mesh trees a rebuild may have made deeper
-    if ((rc = pt_set_stack_cap(c, tlas.depth, p.kda.kd_depth))) return rc;  // (have_scene stays false)
-    if (res.tlas_cap) {  // the four-child form of the new tree alone, opened as the upload opened it
-        const uint32_t first = (uint32_t)res.tlas_first, end = (uint32_t)(res.tlas_first + res.tlas_cap);
-        hipLaunchKernelGGL(pt_collapse4_kernel, dim3((unsigned)((res.tlas_cap + 255) / 256)), dim3(256), 0, nullptr, (const PtBvhNode*)c->bvh.p, (PtBvh4Node*)c->bvh4.p,
-                           (uint32_t)res.tree_nodes, res.collapse_mode, first, end, first, end);
-        PT_HIP(c, hipGetLastError());
-    }
-    PT_HIP(c, hipDeviceSynchronize());
-    v.tlas_root = tlas.child;
-    c->have_scene = true;
-    return PT_OK;
-}
-
-extern "C" int pt_scene_update(pt_context* c, const pt_scene_motion* mo, const pt_kdtree* kd) {
-    if (!c || !mo) return PT_ERR_ARGUMENT;
-    PtUpdatePlan plan;
-    int rc = pt_update_prepare(c, mo, kd, c->res.mesh_box, plan);
-    if (rc) return rc;
-    return pt_update_commit(c, mo, plan);
-}
-
-// ------------------------------------------------------------------------------------------------
-// Scene deform: new vertices for resident meshes under the topology they were uploaded with, then the update above. Per mesh the host
-// computes the box (the upload's function) and copies the vertices; the device expands the triangle records through the resident indices
-// (pt_device_expand_mesh), refits the mesh's tree in place or rebuilds it there (pt_device_refit_mesh_tree / pt_device_build_mesh_tree) and re-derives
-// the four-child form and the leaf-order records for the mesh's node and item ranges alone. With the vertices already in device memory
-// (pt_scene_deform_device) the box is a reduction on the device (pt_device_vertex_box) and the expand kernel reads the caller's buffer in place.
-// ------------------------------------------------------------------------------------------------
-// One mesh of a deform, wherever its vertices are: pt_mesh_deform's fields with host pointers, pt_mesh_deform_device's with device pointers.
-struct PtDeformItem {
-    uint32_t mesh;
-    const double *positions, *normals, *bounds_invtrans;
-    int32_t rebuild;
-};
-
-// What keeps a caller's mistake from becoming a GPU fault: `p` must be 8-byte aligned device memory of the context's device whose allocation reaches `bytes`
-// beyond it. The context's device is current.
-static int pt_check_device_pointer(pt_context* c, const void* p, uint64_t bytes, const std::string& what) {
-    if ((uintptr_t)p & 7u) return pt_fail(c, PT_ERR_ARGUMENT, what + " is not 8-byte aligned");
-    hipPointerAttribute_t at;
-    memset(&at, 0, sizeof at);
-    if (hipPointerGetAttributes(&at, p) != hipSuccess) {
-        (void)hipGetLastError();  // (pageable host memory: the query itself fails, and leaves its error behind)
-        return pt_fail(c, PT_ERR_ARGUMENT, what + " is not device memory (hipPointerGetAttributes does not know the pointer)");
-    }
-    if (at.type != hipMemoryTypeDevice || at.isManaged)
-        return pt_fail(c, PT_ERR_ARGUMENT, what + " is not device memory (host, pinned or managed memory: copy it to the device, or use pt_scene_deform)");
-    if (at.device != c->device)
-        return pt_fail(c, PT_ERR_ARGUMENT, what + " is memory of device " + std::to_string(at.device) + ", the context is on device " + std::to_string(c->device));
-    hipDeviceptr_t base = nullptr;
-    size_t size = 0;
-    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess || !base) {
-        (void)hipGetLastError();
-        return pt_fail(c, PT_ERR_ARGUMENT, what + ": hipMemGetAddressRange does not know the pointer's allocation");
-    }
-    const uint64_t off = (uint64_t)((const char*)p - (const char*)base);
-    if ((const char*)p < (const char*)base || off > size || bytes > size - off)
-        return pt_fail(c, PT_ERR_ARGUMENT, what + ": the allocation ends " + std::to_string(size - std::min<uint64_t>(off, size)) + " bytes after the pointer, " + std::to_string(bytes) + " are needed (n_vertices x 24)");
-    return PT_OK;
-}
-
-// The box and the count of non-finite coordinates of n x 3 f64 in device memory (pt_device_vertex_box): the pointer has passed pt_check_device_pointer, the
-// context's device is current and synchronised. One copy brings the result back.
-static int pt_vertex_box_on_device(pt_context* c, uint64_t n, const double* d_pos, PtBuildBox* box, uint64_t* non_finite) {
-    int rc = pt_reserve(c, c->vbox, (size_t)pt_vertex_box_partials(c->n_cu) * sizeof(PtVboxPartial));
-    if (rc) return rc;
-    PT_HIP(c, pt_device_vertex_box(d_pos, n, c->n_cu, (PtVboxPartial*)c->vbox.p, nullptr));
-    PtVboxPartial got;
-    PT_HIP(c, hipMemcpy(&got, c->vbox.p, sizeof got, hipMemcpyDeviceToHost));
-    for (int k = 0; k < 3; k++) { box->lo[k] = got.v[k]; box->hi[k] = got.v[3 + k]; }
-    *non_finite = got.non_finite;
-    return PT_OK;
-}
-
-extern "C" int pt_vertex_bounds_device(pt_context* c, uint64_t n_vertices, const double* d_positions, double out[6], uint64_t* non_finite) {
-    if (!c) return PT_ERR_ARGUMENT;
-    if (!out || !non_finite) return pt_fail(c, PT_ERR_ARGUMENT, "out and non_finite are required");
-    if (n_vertices > 0xFFFFFFFFull) return pt_fail(c, PT_ERR_ARGUMENT, "n_vertices must be below 2^32");
-    PtBuildBox box = pt_bvh_detail::empty_box();
-    *non_finite = 0;
-    if (n_vertices) {
-        if (!d_positions) return pt_fail(c, PT_ERR_ARGUMENT, "d_positions is required");
-        PT_HIP(c, hipSetDevice(c->device));
-        int rc = pt_check_device_pointer(c, d_positions, n_vertices * 24, "d_positions");
-        if (rc) return rc;
-        PT_HIP(c, hipDeviceSynchronize());  // behind whatever stream produced the vertices
-        if ((rc = pt_vertex_box_on_device(c, n_vertices, d_positions, &box, non_finite))) return rc;
-    }
-    for (int k = 0; k < 3; k++) { out[k] = box.lo[k]; out[3 + k] = box.hi[k]; }
-    return PT_OK;
-}
-
-// pt_scene_deform and pt_scene_deform_device: the two differ in where a mesh's box comes from (the host loop / the device reduction behind the pointer check)
-// and in which pointer the expand kernel reads (the staging buffer the vertices are copied to / the caller's buffer in place).
-static int pt_deform_meshes(pt_context* c, const std::vector<PtDeformItem>& items, bool on_device, const pt_scene_motion* mo, const pt_kdtree* kd) {
-    if (!c->have_scene) return pt_fail(c, PT_ERR_NO_SCENE, "no scene uploaded");
-    pt_context::Resident& res = c->res;
-    const uint32_t n_deforms = (uint32_t)items.size();
-    struct NewBox { PtBuildBox vertex, padded; double ext; };
-    std::vector<NewBox> nb(n_deforms);
-    std::vector<PtBuildBox> mesh_box = res.mesh_box;
-    {
-        std::vector<uint8_t> named(res.place.size(), 0);
-        bool synchronised = false;
-        for (uint32_t d = 0; d < n_deforms; d++) {
-            const PtDeformItem& df = items[d];
-            const std::string at = "deform " + std::to_string(d) + ": ";
-            if (!df.positions || !df.bounds_invtrans) return pt_fail(c, PT_ERR_ARGUMENT, at + "positions and bounds_invtrans are required");
-            if (df.mesh >= res.place.size()) return pt_fail(c, PT_ERR_ARGUMENT, at + "mesh index out of range");
-            if (named[df.mesh]) return pt_fail(c, PT_ERR_ARGUMENT, at + "the mesh is named twice");
-            named[df.mesh] = 1;
-            const pt_context::Resident::MeshPlace& pl = res.place[df.mesh];
-            if (df.normals && !pl.has_normals) return pt_fail(c, PT_ERR_ARGUMENT, at + "normals for a mesh that was uploaded without normals");
-            if (res.meshes[df.mesh].kd_root >= 0)
-                return pt_fail(c, PT_ERR_ARGUMENT, at + "the mesh has a KDMesh tree, which the host builds from the positions: upload the scene again");
-            if (df.rebuild != 0 && df.rebuild != 1) return pt_fail(c, PT_ERR_ARGUMENT, at + "rebuild must be 0 or 1");
-            if (df.rebuild && !pl.device_built)
-                return pt_fail(c, PT_ERR_ARGUMENT, at + "rebuild = 1 needs a tree the device built at upload (its place has the worst-case size); this one was built on the host");
-            bool finite = true;
-            if (on_device) {
-                nb[d].vertex = pt_bvh_detail::empty_box();
-                if (pl.n_verts) {  // (nothing is launched on an empty mesh, and nothing of it is read)
-                    int rc = pt_refuse_in_flight(c);
-                    if (rc) return rc;
-                    PT_HIP(c, hipSetDevice(c->device));
-                    if ((rc = pt_check_device_pointer(c, df.positions, (uint64_t)pl.n_verts * 24, at + "d_positions"))) return rc;
-                    if (df.normals && (rc = pt_check_device_pointer(c, df.normals, (uint64_t)pl.n_verts * 24, at + "d_normals"))) return rc;
-                    if (!synchronised) PT_HIP(c, hipDeviceSynchronize());  // behind whatever stream produced the vertices
-                    synchronised = true;
-                    uint64_t non_finite = 0;
-                    if ((rc = pt_vertex_box_on_device(c, pl.n_verts, df.positions, &nb[d].vertex, &non_finite))) return rc;
-                    finite = non_finite == 0;
-                }
-                nb[d].ext = pt_box_extent(nb[d].vertex);
-            } else {
-                nb[d].ext = pt_mesh_vertex_box(df.positions, pl.n_verts, &nb[d].vertex);
-                for (uint64_t v = 0; v < 3 * (uint64_t)pl.n_verts; v++) finite = finite && std::isfinite(df.positions[v]);
-            }
-            nb[d].padded = nb[d].vertex;
-            for (int k = 0; k < 3; k++) { nb[d].padded.lo[k] -= 1e-5 * nb[d].ext; nb[d].padded.hi[k] += 1e-5 * nb[d].ext; }
-            for (int k = 0; k < 3; k++) finite = finite && nb[d].padded.lo[k] >= -PT_BOX_LIMIT && nb[d].padded.hi[k] <= PT_BOX_LIMIT;
-            if (!finite) return pt_fail(c, PT_ERR_ARGUMENT, at + "a coordinate is not finite or the mesh's box reaches beyond +-1e18");
-            mesh_box[df.mesh] = nb[d].padded;
-        }
-    }
-    PtUpdatePlan plan;
-    int rc = pt_update_prepare(c, mo, kd, mesh_box, plan);
-    if (rc) return rc;
-    if (n_deforms == 0) return pt_update_commit(c, mo, plan);
-
-    // ---- writes
-    PT_HIP(c, hipSetDevice(c->device));
-    PT_HIP(c, hipDeviceSynchronize());
-    c->have_scene = false;  // until every write has been made (pt_update_commit sets it again)
-    const bool verbose = getenv("PORTRAYER_VERBOSE") != nullptr;
-    if (!res.indices_resident) {
-        if ((rc = pt_upload(c, c->mesh_idx, res.indices))) return rc;
-        res.indices_resident = true;
-    }
-    bool any_refit = false;
-    size_t stage_bytes = 0;
-    for (uint32_t d = 0; d < n_deforms; d++) {
-        any_refit = any_refit || !items[d].rebuild;
-        stage_bytes = std::max(stage_bytes, (size_t)res.place[items[d].mesh].n_verts * 24 * (items[d].normals ? 2 : 1));
-    }
-    if (!on_device && (rc = pt_reserve(c, c->deform_stage, stage_bytes))) return rc;  // (vertices in device memory are read where they are)
-    if (any_refit && ((rc = pt_reserve(c, c->tree_parent, std::max<size_t>(res.tree_nodes, 1) * 4)) || (rc = pt_reserve(c, c->tree_arrive, std::max<size_t>(res.tree_nodes, 1) * 4)))) return rc;
-    const bool write_normals = res.any_normals;  // (tri_n is empty unless a node shades smoothly: the upload then drops the normals it is given, and so does this)
-    for (uint32_t d = 0; d < n_deforms; d++) {
-        const PtDeformItem& df = items[d];
-        pt_context::Resident::MeshPlace& pl = res.place[df.mesh];
-        PtMeshInfo& mi = res.meshes[df.mesh];
-        const size_t pos_bytes = (size_t)pl.n_verts * 24;
-        const double *d_pos = df.positions, *d_nrm = df.normals && write_normals ? df.normals : nullptr;
-        if (!on_device) {
-            PT_HIP(c, hipMemcpy(c->deform_stage.p, df.positions, pos_bytes, hipMemcpyHostToDevice));
-            if (df.normals) PT_HIP(c, hipMemcpy((char*)c->deform_stage.p + pos_bytes, df.normals, pos_bytes, hipMemcpyHostToDevice));
-            d_pos = (const double*)c->deform_stage.p;
-            if (d_nrm) d_nrm = (const double*)((const char*)c->deform_stage.p + pos_bytes);
-        }
-        PT_HIP(c, pt_device_expand_mesh((const uint32_t*)c->mesh_idx.p, mi.tri_first, mi.tri_count, d_pos, d_nrm, pl.n_verts, (double*)c->tri_v.p, (double*)c->tri_e.p,
-                                        d_nrm ? (double*)c->tri_n.p : nullptr, nullptr));
-        const double pad = 1e-7 * nb[d].ext;
-        if (df.rebuild) {
-            PtDeviceBuildResult built;
-            PT_HIP(c, hipMemsetAsync((PtBvhNode*)c->bvh.p + pl.node_first, 0xFF, (size_t)pl.node_count * sizeof(PtBvhNode), nullptr));
-            PT_HIP(c, pt_device_build_mesh_tree((const double*)c->tri_v.p, mi.tri_first, mi.tri_count, nb[d].vertex.lo, nb[d].vertex.hi, pad, res.blas_leaf, (PtBvhNode*)c->bvh.p,
-                                                pl.node_first, (uint32_t*)c->bvh_items.p, pl.item_first, nullptr, &built));
-            mi.blas_root = built.root; pl.depth = built.depth; pl.parents_valid = false;
-            if (verbose) fprintf(stderr, "[pt_scene_deform] mesh %u rebuilt: %u triangles, %.2f ms, %d clustering rounds, depth %d\n", df.mesh, mi.tri_count, built.ms, built.rounds, built.depth);
-        } else if (pl.node_count) {
-            if (!pl.parents_valid) {
-                PT_HIP(c, pt_device_tree_parents((const PtBvhNode*)c->bvh.p, pl.node_first, pl.node_count, (uint32_t*)c->tree_parent.p, nullptr));
-                pl.parents_valid = true;
-            }
-            PT_HIP(c, pt_device_refit_mesh_tree((PtBvhNode*)c->bvh.p, pl.node_first, pl.node_count, (const uint32_t*)c->bvh_items.p, pl.item_first, pl.item_count,
-                                                (const double*)c->tri_v.p, mi.tri_first, mi.tri_count, pad, (const uint32_t*)c->tree_parent.p, (uint32_t*)c->tree_arrive.p, nullptr));
-        }
-        // what the walks read, for the mesh's node and item ranges alone
-        if (pl.node_count) {
-            const uint32_t first = pl.node_first, end = pl.node_first + pl.node_count;
-            hipLaunchKernelGGL(pt_collapse4_kernel, dim3((pl.node_count + 255) / 256), dim3(256), 0, nullptr, (const PtBvhNode*)c->bvh.p, (PtBvh4Node*)c->bvh4.p,
-                               (uint32_t)res.tree_nodes, res.collapse_mode, (uint32_t)res.tlas_first, (uint32_t)(res.tlas_first + res.tlas_cap), first, end);
-            PT_HIP(c, hipGetLastError());
-        }
-        if (pl.item_count) {
-            hipLaunchKernelGGL(pt_tri_leaf_kernel, dim3((pl.item_count + 255) / 256), dim3(256), 0, nullptr, (const uint32_t*)c->bvh_items.p + pl.item_first, pl.item_count,
-                               (const double*)c->tri_e.p, (uint32_t)(res.mesh_tris + res.tri_box.size()), (double*)c->tri_leaf.p + 10 * (size_t)pl.item_first);
-            PT_HIP(c, hipGetLastError());
-        }
-        for (int r = 0; r < 12; r++) mi.bbox_inv[r] = df.bounds_invtrans[r];
-        res.mesh_box[df.mesh] = nb[d].padded;
-        PT_HIP(c, hipStreamSynchronize(nullptr));  // the staging buffer is the next mesh's
-    }
-    {   // the records the walks and the scene-level build read: PtMeshInfo (bbox_inv, blas_root), the padded boxes; the stack under a scene leaf
-        if ((rc = pt_upload(c, c->meshes, res.meshes))) return rc;
-        std::vector<double> mb(6 * res.mesh_box.size());
-        for (size_t m = 0; m < res.mesh_box.size(); m++) for (int k = 0; k < 3; k++) { mb[6 * m + k] = res.mesh_box[m].lo[k]; mb[6 * m + 3 + k] = res.mesh_box[m].hi[k]; }
-        if ((rc = pt_upload(c, c->mesh_box_dev, mb))) return rc;
-        int max_blas_depth = 0;
-        for (const auto& pl : res.place) max_blas_depth = std::max(max_blas_depth, pl.depth);
-        auto wide = [&](int depth2) { return res.collapse_mode ? 3 * depth2 : 3 * ((depth2 + 1) / 2); };
-        res.below = std::max(wide(max_blas_depth), 3 * (res.max_kdm_depth + 1));
-    }
-    return pt_update_commit(c, mo, plan);
-}
-
-extern "C" int pt_scene_deform(pt_context* c, uint32_t n_deforms, const pt_mesh_deform* deforms, const pt_scene_motion* mo, const pt_kdtree* kd) {
-    if (!c || !mo || (n_deforms && !deforms)) return PT_ERR_ARGUMENT;
-    std::vector<PtDeformItem> items(n_deforms);
-    for (uint32_t d = 0; d < n_deforms; d++) items[d] = PtDeformItem{deforms[d].mesh, deforms[d].positions, deforms[d].normals, deforms[d].bounds_invtrans, deforms[d].rebuild};
-    return pt_deform_meshes(c, items, false, mo, kd);
-}
-
-extern "C" int pt_scene_deform_device(pt_context* c, uint32_t n_deforms, const pt_mesh_deform_device* deforms, const pt_scene_motion* mo, const pt_kdtree* kd) {
-    if (!c || !mo || (n_deforms && !deforms)) return PT_ERR_ARGUMENT;
-    std::vector<PtDeformItem> items(n_deforms);
-    for (uint32_t d = 0; d < n_deforms; d++) items[d] = PtDeformItem{deforms[d].mesh, deforms[d].d_positions, deforms[d].d_normals, deforms[d].bounds_invtrans, deforms[d].rebuild};
-    return pt_deform_meshes(c, items, true, mo, kd);
-}
-
-extern "C" int pt_scene_mesh_rebuildable(const pt_context* c, uint32_t mesh) {
-    if (!c) return PT_ERR_ARGUMENT;
-    if (!c->have_scene) return PT_ERR_NO_SCENE;
-    if (mesh >= c->res.place.size()) return PT_ERR_ARGUMENT;
-    return c->res.place[mesh].device_built ? 1 : 0;
-}
-
-// tests: the bytes of device memory the context's scene buffers hold (an update must not make it grow)
-extern "C" uint64_t pt_test_scene_bytes(const pt_context* c) {
-    if (!c) return 0;
-    const PtBuf* bufs[] = {&c->inv, &c->fwd, &c->nrm, &c->info, &c->tri_v, &c->tri_e, &c->tri_leaf, &c->tri_n, &c->meshes, &c->materials, &c->lights, &c->bvh, &c->bvh4,
-                           &c->bvh_items, &c->kd, &c->kd_items, &c->mat_maps, &c->uv_trans, &c->tex, &c->tex_rgb, &c->srgb_lut, &c->tri_uv, &c->texview, &c->mkd, &c->mkd_items,
-                           &c->node_box, &c->kd_box, &c->mkd_box, &c->mkd_item_box, &c->kd_ref, &c->g_inv, &c->g_fwd, &c->g_nrm, &c->chain_off, &c->chain, &c->dfs_rank,
-                           &c->hier_rec, &c->own_inv, &c->mesh_box_dev, &c->mesh_idx, &c->tree_parent, &c->tree_arrive, &c->deform_stage};
-    uint64_t total = 0;
-    for (const PtBuf* b : bufs) total += b->bytes;
-    return total;
-}
-
-extern "C" int pt_test_vertex_box_shape(const pt_context* c, uint64_t out[2]) {
-    if (!c || !out) return PT_ERR_ARGUMENT;
-    out[0] = PT_VBOX_BLOCK; out[1] = pt_vertex_box_partials(c->n_cu);
-    return PT_OK;
-}
-
-// tests: out[0] = stack_cap, out[1] = who built the scene-level tree last (0 the upload, 1 an update on the host, 2 an update on the device),
-// out[2] = the device build's clustering rounds, out[3] = bytes of the tree buffers (bvh, bvh4, bvh_items)
-extern "C" int pt_test_scene_info(const pt_context* c, uint64_t out[4]) {
-    if (!c || !out) return PT_ERR_ARGUMENT;
-    if (!c->have_scene) return PT_ERR_NO_SCENE;
-    out[0] = (uint64_t)c->view.stack_cap; out[1] = (uint64_t)c->res.last_builder; out[2] = (uint64_t)c->res.last_rounds;
-    out[3] = c->bvh.bytes + c->bvh4.bytes + c->bvh_items.bytes;
-    return PT_OK;
-}
 
 // ------------------------------------------------------------------------------------------------
 // Render
@@ -2153,7 +708,7 @@ struct PtInterp { bool tex, park; };
 static PtInterp pt_interp_sizing(const pt_context* c, PtRenderArgs& r) {
     PtInterp k;
     k.tex = r.scene.mat_maps != nullptr;
-    k.park = c->spawns;
+    k.park = pt_spawns(c->traits);
     if (const char* e = getenv("PORTRAYER_PARK")) k.park = k.park && atoi(e) > 0;  // 0: every parked frame in HBM (tests, measurements), as for a render
     r.park_slots = k.park ? 1 : 0;
     const size_t frame_bytes = (size_t)(PT_LDS_FRAME_F64 + r.park_slots * PT_PARK_F64) * PT_BLOCK * 8;
@@ -2162,61 +717,142 @@ static PtInterp pt_interp_sizing(const pt_context* c, PtRenderArgs& r) {
     return k;
 }
 
+// ------------------------------------------------------------------------------------------------
+// Which render kernel a scene runs: PtRenderArgs::run_variant, the waves per SIMD its instantiation is compiled for (PtRenderArgs::four_waves: 0 = three),
+// the parked frames kept in LDS and the LDS a block may take. One rule per kernel family - pt_choose_kernel picks the family, the family's function its
+// wave count - from what the scene says (PtSceneTraits), its mode, whether it is textured, and the PORTRAYER_WAVES, KD_WAVES, CHAIN, CHAIN_WAVES, PARK, FORK and
+// LDS_BUDGET_KB switches, which nothing else reads for this. No context, no HIP call (pt_test_kernel_choice).
+// ------------------------------------------------------------------------------------------------
+struct PtKernelChoice {
+    int run_variant = PT_RUN_LINE3, four_waves = 0, park_slots = 0;
+    size_t block_budget = 0;
+    bool needs_spill = false;  // the lanes keep recursion frames in HBM
+};
+
+// The straight-line kernel, flat_scene / hierarchical semantics.
+// The 4-waves-per-SIMD kernel for scenes where the tree walk outweighs the shading: many scene-level nodes or many instanced
+// triangles, nothing reflective, flat_scene semantics (measured: big-scene +8.7 %, big-soup +6.8 %; macho-cows
+// with its 23 nodes and 17,500 triangles -8 %; reflective scenes and the k-d walk lose, profiles/r02/notes.md)
+static int pt_line_waves(const PtSceneTraits& t, int mode, bool tex) {
+    if (const char* e = getenv("PORTRAYER_WAVES")) {
+        const int wv = atoi(e);
+        if (wv < 4) return 0;
+        if (wv >= 5 && (mode == PT_MODE_FLAT_NOMESH || mode == PT_MODE_HIER_NOMESH)) return PT_LINE_TOP_WAVES;
+        return (wv >= 5 && (mode == PT_MODE_FLAT || mode == PT_MODE_HIER_MESH)) ? PT_MESH_TOP_WAVES : 4;
+    }
+    const bool hier = t.traverse == PT_TRAVERSE_HIER, many_tris = t.instanced_tris >= 65536;
+    // hierarchical semantics (round 3, straight-line kernel): mesh-free scenes with many nodes gain like flat_scene ones (big-scene 25.7 ->
+    // 29.4 Gray/s at 4 waves); with mesh instances the walk carries a second ray and spills at 128 registers (macho-cows 16.4 -> 12.0) unless
+    // the triangle trees dominate (the 1.25 M-triangle soup: equal)
+    // Since the register work of round 3 (arguments re-read, colour parked in LDS, an instantiation of the hierarchical semantics without
+    // the KDMesh walker) scenes with plain Mesh instances of any size gain too (c41: macho-cows 21.4 -> 23.4 Gray/s, hierarchical 18.7 -> 19.7);
+    // with KDMesh trees the kernels still spill 100+ registers at 128 and stay at 3 waves unless the triangle trees dominate.
+    const bool plain_meshes = t.has_meshes && !t.has_kdmesh;
+    // traversal-heavy scene: a kernel compiled for more than 3 waves per SIMD
+    const bool heavy = hier ? ((!t.has_meshes && t.n_nodes >= 256) || many_tris) : (t.n_nodes >= 256 || many_tris);
+    // ... or, while the scene has no texture maps: any scene with plain Mesh instances (textured: flat_scene loses 10 % at 4 waves, c45)
+    // The hierarchical semantics without KDMesh trees gain at 4 waves whatever the scene (their leaf tests wait for a path record and a matrix per
+    // level): macho-cows +5 %, fish (textured) +5 %, normal-mapping (11 textured primitives) +12 %, the mirror scene's chain kernel +9 % (c41, c45).
+    if (!(heavy || (plain_meshes && !tex) || (hier && !t.has_kdmesh))) return 0;
+    // mesh-free scenes go one further: 5 waves per SIMD (96 registers, 17 of the kernel's spilled; big-scene 34.4 -> 37.0, hierarchical
+    // 29.4 -> 32.5 Gray/s; the k-d walk, 50 spilled, loses and stays at 4)
+    if (heavy && !t.has_meshes) return PT_LINE_TOP_WAVES;
+    // ... and so do scenes of very many triangles in plain Mesh instances (round 4, c29: their walks wait for node fetches - 3 -> 4 waves was +18 % -; the 1.25 M-triangle
+    // scenes +3.7 % / +3.2 %, hierarchical +2.6 %, at 96 registers with 57 spilled; macho-cows, 17,500 triangles, loses 15 % and stays at 4)
+    // Round 5 (c47 / c48, after the tree step and the instance walk issue fewer scalar instructions): flat_scene is now FASTER at 4 waves (big-soup 18.96 -> 18.75 ms,
+    // big-mesh 19.16 -> 18.86; 18 spilled registers instead of 69) and takes 4; the hierarchical semantics still gain 1 % at 5 and keep them.
+    return (plain_meshes && many_tris && hier && !tex) ? PT_MESH_TOP_WAVES : 4;
+}
+
+// The straight-line kernel, k-d semantics.
+// The k-d semantics: mesh-free scenes with many nodes take the 4-wave straight-line kernel too (big-scene 35.7 -> 30.7 ms: the per-lane
+// k-d walk waits on its own loads, a fourth wavefront per SIMD hides more of that than the 4 spilled registers cost); with mesh
+// instances the walk needs the registers (167 at 3 waves). PORTRAYER_KD_WAVES=3|4 overrides.
+// Round 4 (one walk per wavefront, pt_trace_packet_kd): mesh-free scenes with many nodes at 5 waves (big-scene 29.2 -> 28.1 ms, c10), scenes with plain
+// Mesh instances (PT_MODE_KD_MESH: no KDMesh walker compiled in) at 4; with KDMesh trees the kernel needs its 168 registers.
+static int pt_line_waves_kd(const PtSceneTraits& t, int mode) {
+    if (const char* e = getenv("PORTRAYER_KD_WAVES")) {
+        const int wv = atoi(e);
+        return (wv < 4 || mode == PT_MODE_KD) ? 0 : ((wv >= 5 && mode == PT_MODE_KD_NOMESH) ? 5 : 4);
+    }
+    return (mode == PT_MODE_KD_NOMESH && t.n_nodes >= 256) ? 5 : (mode == PT_MODE_KD_MESH ? 4 : 0);
+}
+
+// The chain kernel.
+// 4 waves per SIMD in the flat_scene semantics (mirror scene 25.5 -> 26.8 Gray/s, c34: ten bounces per sample leave a lot of latency to hide),
+// 3 in the hierarchical ones (182 spilled registers at 128: 19.3 -> 14.8) and the k-d ones. PORTRAYER_CHAIN_WAVES=3|4 overrides.
+// (Only where that was measured or the compiler's figures are like the measured case's: untextured, no KDMesh trees - those
+// instantiations spill 57 / 142 registers at 128.)
+static int pt_chain_waves(int mode, bool tex) {
+    if (const char* e = getenv("PORTRAYER_CHAIN_WAVES")) return (atoi(e) == 4 && mode != PT_MODE_KD) ? 4 : 0;
+    const bool flat_sem = (mode == PT_MODE_FLAT || mode == PT_MODE_FLAT_NOMESH || mode == PT_MODE_HIER_MESH) && !tex;  // (HIER_MESH: 22.2 -> 24.2, c41)
+    return (flat_sem || (mode == PT_MODE_KD_MESH && !tex)) ? 4 : 0;
+}
+
+static PtKernelChoice pt_choose_kernel(const PtSceneTraits& t, int mode, bool tex) {
+    PtKernelChoice k;
+    k.needs_spill = pt_needs_spill(t);
+    // Scenes whose hits spawn rays need the interpreter kernel (3 waves per SIMD); the others run the straight-line kernel at 3 or
+    // 4 waves per SIMD.
+    if (!pt_spawns(t)) {
+        k.four_waves = pt_kd_semantics(mode) ? pt_line_waves_kd(t, mode) : pt_line_waves(t, mode, tex);
+        k.run_variant = k.four_waves >= 5 ? PT_RUN_LINE5 : (k.four_waves ? PT_RUN_LINE4 : PT_RUN_LINE3);  // (LINE5: the densest instantiation the mode has)
+    } else {
+        // parked recursion frames kept in LDS (pt_shade.h): only scenes that park frames at all have any
+        bool park = true;
+        if (const char* e = getenv("PORTRAYER_PARK")) park = atoi(e) > 0;  // 0: every parked frame in HBM (tests, measurements)
+        // every reflective material is opaque (no index of refraction): a hit spawns at most one ray, the recursion is a chain
+        bool chain = t.reflective_opaque != 0;
+        if (const char* e = getenv("PORTRAYER_CHAIN")) chain = chain && atoi(e) > 0;  // 0: the interpreter kernel also for scenes whose recursion is a chain (A/B runs, tests)
+        if (chain && park) {
+            k.run_variant = PT_RUN_CHAIN;
+            k.park_slots = 0;  // no frame in LDS: the parked colours go straight to the lane's HBM lines
+            k.four_waves = pt_chain_waves(mode, tex);
+        } else {
+            // Fork / join of refracted subtrees (pt_shade.h) is built, parity-green and OFF by default: it fills the idle lanes and still loses
+            // (transmission-refraction 11.4 -> 8.6 Gray/s, profiles/r03/notes.md section 4): the subtrees other lanes walk are other rays, and the
+            // one walk per wavefront pays for the union of their paths. PORTRAYER_FORK=1 switches it on for scenes that qualify.
+            // fork / join of refracted subtrees (pt_shade.h) needs a recursion that draws no random numbers and a dielectric material to be of use:
+            // no hit draws random numbers after the jitter (no area light, no glossy material): refracted subtrees may be walked by other lanes
+            const bool forkable = !t.reflective_opaque && !t.glossy && !t.area_light && t.n_lights <= PT_LIGHT_ROUND;
+            bool fork = false;
+            if (const char* e = getenv("PORTRAYER_FORK")) fork = forkable && park && atoi(e) > 0;
+            k.run_variant = park ? (fork ? PT_RUN_INTERP_FORK : PT_RUN_INTERP_PARK) : PT_RUN_INTERP;
+            k.park_slots = park ? 1 : 0;
+        }
+    }
+    k.block_budget = k.four_waves >= 6 ? 26 * 1024 : (k.four_waves == 5 ? 31 * 1024 : (k.four_waves ? 39 * 1024 : 52 * 1024));  // 3 x 52 KB, 4 x 39 KB, 5 x 31 KB or 6 x 26 KB of the CU's 160 KB
+    if (const char* e = getenv("PORTRAYER_LDS_BUDGET_KB")) k.block_budget = (size_t)std::max(16, std::min(160, atoi(e))) * 1024;  // experiment: 80 = two blocks per CU
+    return k;
+}
+
+// pt_stats.kernel_variant of a choice (without PT_KERNEL_COUNTING, the launch's own)
+static uint32_t pt_choice_variant(const PtKernelChoice& k, bool tex) {
+    const int v = k.run_variant;
+    const bool line = v == PT_RUN_LINE3 || v == PT_RUN_LINE4 || v == PT_RUN_LINE5;
+    return (k.four_waves ? (uint32_t)k.four_waves : 3u) | ((line || v == PT_RUN_CHAIN) ? 0u : PT_KERNEL_INTERPRETER) | (v == PT_RUN_CHAIN ? PT_KERNEL_CHAIN : 0u) |
+           ((v == PT_RUN_INTERP_PARK || v == PT_RUN_INTERP_FORK) ? PT_KERNEL_PARK : 0u) | (v == PT_RUN_INTERP_FORK ? PT_KERNEL_FORK : 0u) | (tex ? PT_KERNEL_TEXTURED : 0u);
+}
+
+extern "C" int pt_test_kernel_choice(const pt_scene_traits* traits, int mode, int textured, uint32_t* kernel_mode, uint32_t* kernel_variant) {
+    if (!traits || !kernel_mode || !kernel_variant) return PT_ERR_ARGUMENT;
+    if (mode < 0) mode = pt_scene_mode(*traits);
+    *kernel_mode = (uint32_t)mode;
+    *kernel_variant = pt_choice_variant(pt_choose_kernel(*traits, mode, textured != 0), textured != 0);
+    return PT_OK;
+}
+
 static int pt_render_common(pt_context* c, PtRenderArgs& a, bool stats, hipStream_t stream, int slot_index = -1) {
     // LDS per block = traversal stack (as much of it as leaves room for three blocks per CU) + the shaded hit's frame (+ a parked one);
     // deeper stack entries live in HBM (PtStackSpill).
     if (getenv("PORTRAYER_NO_TEX")) a.scene.mat_maps = nullptr;  // experiment: the untextured kernel on a textured scene (wrong picture, timing only)
     const bool tex = a.scene.mat_maps != nullptr;
-    // parked recursion frames kept in LDS (pt_shade.h): only scenes that park frames at all have any
-    a.park_slots = 1;
-    if (const char* e = getenv("PORTRAYER_PARK")) a.park_slots = atoi(e) > 0 ? 1 : 0;  // 0: every parked frame in HBM (tests, measurements)
-    if (!c->spawns) a.park_slots = 0;
-    // Scenes whose hits spawn rays need the interpreter kernel (3 waves per SIMD); the others run the straight-line kernel at 3 or
-    // 4 waves per SIMD.
-    const bool kd_sem = pt_kd_semantics(a.scene.mode);
-    a.four_waves = (!c->spawns && (c->four_waves || (c->four_waves_untextured && !tex) || c->four_waves_hier)) ? (c->five_waves ? PT_LINE_TOP_WAVES : ((c->five_waves_mesh && !tex) ? PT_MESH_TOP_WAVES : 4)) : 0;
-    if (const char* e = getenv("PORTRAYER_WAVES")) {
-        const int wv = atoi(e);
-        a.four_waves = (!c->spawns && wv >= 4) ? ((wv >= 5 && (a.scene.mode == PT_MODE_FLAT_NOMESH || a.scene.mode == PT_MODE_HIER_NOMESH)) ? PT_LINE_TOP_WAVES : ((wv >= 5 && (a.scene.mode == PT_MODE_FLAT || a.scene.mode == PT_MODE_HIER_MESH)) ? PT_MESH_TOP_WAVES : 4)) : 0;
-    }
-    if (kd_sem) {
-        // The k-d semantics: mesh-free scenes with many nodes take the 4-wave straight-line kernel too (big-scene 35.7 -> 30.7 ms: the per-lane
-        // k-d walk waits on its own loads, a fourth wavefront per SIMD hides more of that than the 4 spilled registers cost); with mesh
-        // instances the walk needs the registers (167 at 3 waves). PORTRAYER_KD_WAVES=3|4 overrides.
-        // Round 4 (one walk per wavefront, pt_trace_packet_kd): mesh-free scenes with many nodes at 5 waves (big-scene 29.2 -> 28.1 ms, c10), scenes with plain
-        // Mesh instances (PT_MODE_KD_MESH: no KDMesh walker compiled in) at 4; with KDMesh trees the kernel needs its 168 registers.
-        a.four_waves = c->spawns ? 0 : ((a.scene.mode == PT_MODE_KD_NOMESH && a.scene.n_nodes >= 256) ? 5 : (a.scene.mode == PT_MODE_KD_MESH ? 4 : 0));
-        if (const char* e = getenv("PORTRAYER_KD_WAVES")) {
-            const int wv = atoi(e);
-            a.four_waves = (c->spawns || wv < 4 || a.scene.mode == PT_MODE_KD) ? 0 : ((wv >= 5 && a.scene.mode == PT_MODE_KD_NOMESH) ? 5 : 4);
-        }
-    }
-    // Fork / join of refracted subtrees (pt_shade.h) is built, parity-green and OFF by default: it fills the idle lanes and still loses
-    // (transmission-refraction 11.4 -> 8.6 Gray/s, profiles/r03/notes.md section 4): the subtrees other lanes walk are other rays, and the
-    // one walk per wavefront pays for the union of their paths. PORTRAYER_FORK=1 switches it on for scenes that qualify.
-    bool fork = false;
-    if (const char* e = getenv("PORTRAYER_FORK")) fork = c->forkable && a.park_slots && atoi(e) > 0;
+    const PtKernelChoice choice = pt_choose_kernel(c->traits, a.scene.mode, tex);
+    a.run_variant = choice.run_variant; a.four_waves = choice.four_waves; a.park_slots = choice.park_slots;
     if (c->launch_seq == 0) c->launch_seq = (uint32_t)std::chrono::steady_clock::now().time_since_epoch().count() * 2654435761u;  // a different starting point in every context
     a.launch_nonce = ++c->launch_seq;
-    bool chain = c->one_ray;
-    if (const char* e = getenv("PORTRAYER_CHAIN")) chain = chain && atoi(e) > 0;  // 0: the interpreter kernel also for scenes whose recursion is a chain (A/B runs, tests)
-    if (c->spawns) a.run_variant = (chain && a.park_slots) ? PT_RUN_CHAIN : (a.park_slots ? (fork ? PT_RUN_INTERP_FORK : PT_RUN_INTERP_PARK) : PT_RUN_INTERP);
-    else a.run_variant = a.four_waves >= 5 ? PT_RUN_LINE5 : (a.four_waves ? PT_RUN_LINE4 : PT_RUN_LINE3);  // (LINE5: the densest instantiation the mode has)
-    if (a.run_variant == PT_RUN_CHAIN) {
-        a.park_slots = 0;  // no frame in LDS: the parked colours go straight to the lane's HBM lines
-        // 4 waves per SIMD in the flat_scene semantics (mirror scene 25.5 -> 26.8 Gray/s, c34: ten bounces per sample leave a lot of latency to hide),
-        // 3 in the hierarchical ones (182 spilled registers at 128: 19.3 -> 14.8) and the k-d ones. PORTRAYER_CHAIN_WAVES=3|4 overrides.
-        // (Only where that was measured or the compiler's figures are like the measured case's: untextured, no KDMesh trees - those
-        // instantiations spill 57 / 142 registers at 128.)
-        const bool flat_sem = (a.scene.mode == PT_MODE_FLAT || a.scene.mode == PT_MODE_FLAT_NOMESH || a.scene.mode == PT_MODE_HIER_MESH) && !tex;  // (HIER_MESH: 22.2 -> 24.2, c41)
-        a.four_waves = flat_sem ? 4 : 0;
-        if (const char* e = getenv("PORTRAYER_CHAIN_WAVES")) a.four_waves = (atoi(e) == 4 && a.scene.mode != PT_MODE_KD) ? 4 : 0;
-        else if (a.scene.mode == PT_MODE_KD_MESH && !tex) a.four_waves = 4;
-    }
-    size_t block_budget = a.four_waves >= 6 ? 26 * 1024 : (a.four_waves == 5 ? 31 * 1024 : (a.four_waves ? 39 * 1024 : 52 * 1024));  // 3 x 52 KB, 4 x 39 KB, 5 x 31 KB or 6 x 26 KB of the CU's 160 KB
-    if (const char* e = getenv("PORTRAYER_LDS_BUDGET_KB")) block_budget = (size_t)std::max(16, std::min(160, atoi(e))) * 1024;  // experiment: 80 = two blocks per CU
     const size_t frame_bytes = (size_t)(PT_LDS_FRAME_F64 + a.park_slots * PT_PARK_F64) * PT_BLOCK * 8;
-    a.stack_lds_cap = pt_stack_lds_cap(a.scene, block_budget, frame_bytes);
+    a.stack_lds_cap = pt_stack_lds_cap(a.scene, choice.block_budget, frame_bytes);
     a.grid_share = 1;  // (a share of the resident blocks per launch was tried for ranks that share a GPU, round 5 c23: their kernels do not run side by side - 35.5 -> 14.3 Gray/s)
     uint32_t grid = 0;
     PT_HIP(c, pt_dispatch(a, stats, c->n_cu, stream, &grid, false));
@@ -2233,7 +869,7 @@ static int pt_render_common(pt_context* c, PtRenderArgs& a, bool stats, hipStrea
     const uint64_t resident_waves = (uint64_t)grid * (PT_BLOCK / 64);
     const bool long_launch = (uint64_t)a.n_items > 2048ull * std::max<uint64_t>(resident_waves, 1);
     // (round 3's per-lane k-d walk was 1 % better off with batches; the wave-uniform one is not: big-scene +1.1 %, macho-cows +3.2 % with the queues, round 4 c68)
-    a.fine_queues = (c->spawns || !long_launch) ? 16 : 0;  // 8 .. 32 queues measured alike, 64 and 4 about 1 % behind
+    a.fine_queues = (pt_spawns(c->traits) || !long_launch) ? 16 : 0;  // 8 .. 32 queues measured alike, 64 and 4 about 1 % behind
     if (const char* e = getenv("PORTRAYER_FINE_QUEUES")) a.fine_queues = (uint32_t)std::max(0, std::min(PT_FINE_QUEUES, atoi(e)));
     a.item_stride = 1;
     if (const char* e = getenv("PORTRAYER_ITEM_STRIDE")) {  // experiment (batches only): position q -> item (q * stride) mod n; "golden" = 0.618 n
@@ -2247,7 +883,7 @@ static int pt_render_common(pt_context* c, PtRenderArgs& a, bool stats, hipStrea
         slot_index = c->slot_next;
     }
     pt_context::Slot& sl = c->slot[slot_index];  // the launch's work buffers are its slot's: another frame may be in flight on the other slot's
-    const size_t spill_bytes = c->needs_spill ? (size_t)a.n_lanes * PT_SPILL_DEPTHS * PT_SPILL_STRIDE * sizeof(double) : 16;
+    const size_t spill_bytes = choice.needs_spill ?(size_t)a.n_lanes * PT_SPILL_DEPTHS * PT_SPILL_STRIDE * sizeof(double) : 16;
     if ((rc = pt_reserve(c, sl.spill, spill_bytes))) return rc;
     const size_t stack_column = pt_stack_column(a.scene, a.stack_lds_cap);
     if ((rc = pt_reserve(c, sl.stack_spill, (size_t)a.n_lanes * stack_column * 4))) return rc;  // (the k-d walk's saved bounds needed columns behind this until round 5)
@@ -2331,8 +967,7 @@ static int pt_render_common(pt_context* c, PtRenderArgs& a, bool stats, hipStrea
     a.occluders = occ_bytes ? (uint32_t*)((char*)sl.misc.p + misc_head) : nullptr;
     a.occ_row = std::max<uint32_t>(a.div_tiles_x.d / std::max<uint32_t>(a.tile_ranks, 1u), 1u);
     c->last_mode = (uint32_t)a.scene.mode;
-    c->last_variant = (a.four_waves ? (uint32_t)a.four_waves : 3u) | ((a.run_variant == PT_RUN_LINE3 || a.run_variant == PT_RUN_LINE4 || a.run_variant == PT_RUN_LINE5 || a.run_variant == PT_RUN_CHAIN) ? 0u : PT_KERNEL_INTERPRETER) | (a.run_variant == PT_RUN_CHAIN ? PT_KERNEL_CHAIN : 0u) |
-                      ((a.run_variant == PT_RUN_INTERP_PARK || a.run_variant == PT_RUN_INTERP_FORK) ? PT_KERNEL_PARK : 0u) | (a.run_variant == PT_RUN_INTERP_FORK ? PT_KERNEL_FORK : 0u) | (stats ? PT_KERNEL_COUNTING : 0u) | (tex ? PT_KERNEL_TEXTURED : 0u);
+    c->last_variant = pt_choice_variant(choice, tex) | (stats ? PT_KERNEL_COUNTING : 0u);
     PT_HIP(c, hipMemsetAsync(sl.misc.p, 0, misc_head + occ_bytes, stream));
     if (occ_seed) {
         const uint32_t n_occ = (uint32_t)(occ_bytes / 4);

@@ -220,7 +220,7 @@ __global__ void __launch_bounds__(PT_BUILD_BLOCK) pt_ploc_depth(uint32_t n, cons
 // ------------------------------------------------------------------------------------------------
 namespace {
 
-// Conservative world box of every flattened node, with pt_scene_upload's formulas and paddings (pt_api.hip: pt_node_world_boxes): the exact box of
+// Conservative world box of every flattened node, with pt_scene_upload's formulas and paddings (pt_scene.hip: pt_node_world_boxes): the exact box of
 // a sphere, the two discs of a cylinder / cone, the transformed padded model box otherwise, a relative pad of 1e-9 on the result; f64, then
 // rounded outward to f32. The device's f64 may differ from the host's in the last bits (sqrt, the order of min / max): the 1e-4 model-unit
 // padding of every shape dominates that by many orders of magnitude, so the boxes stay conservative and no bit equality with the host's is sought.

@@ -1,7 +1,7 @@
 """Shadow rays at 0 to 65 lights, against the oracle. The kernels branch on the light count where no scene of the other tests reaches:
 the interpreter handles lights in rounds of PT_LIGHT_ROUND = 32 (a 32-bit mask of shadow results per round, the colour parked between
 rounds, the area-light draw counter restarted per round; pt_shade.h), scenes of more than 32 lights keep recursion frames in HBM and get
-one stream for both slots (pt_api.hip: needs_spill, pt_context_stream), fork / join is off above 32 lights, and the occluder table holds
+one stream for both slots (pt_context.h: pt_needs_spill; pt_api.hip: pt_context_stream), fork / join is off above 32 lights, and the occluder table holds
 one word per (tile, light) and is left out above 4 MB. 0, 1, 31, 32, 33, 64 and 65 lights are the round boundaries (65: three rounds, the
 last with one light), in each kernel family - straight-line (nothing reflective, and a 1000-node scene for the 4- to 6-wave
 instantiations), chain (opaque mirrors, one glossy) and interpreter (a dielectric) - x flat / k-d / hierarchical semantics, counting and

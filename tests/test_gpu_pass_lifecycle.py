@@ -1,4 +1,4 @@
-"""What the device passes beside the render share (pt_api.hip: PtPass and the pt_pass_* functions), pinned where the per-pass tests leave it open: the exact
+"""What the device passes beside the render share (pt_context.h: PtPass; pt_api.hip: the pt_pass_* functions), pinned where the per-pass tests leave it open: the exact
 words of every "in flight" refusal and of every _finish with nothing open, each pass's flag apart from the others', a call with nothing to do (n = 0, an
 inverted slice) that queues nothing and reports 0 ms, the film's passes kept as the radiance pass's, and a context destroyed while all three passes are open.
 The `primitives` scene, a 16x16 image, 64 rays: the words and the bookkeeping do not depend on the size."""
