@@ -40,7 +40,7 @@ HIP_OBJS := $(OBJDIR)/pt_api.o $(OBJDIR)/pt_scene.o $(OBJDIR)/pt_build.o $(OBJDI
             $(foreach m,$(RENDER_MODES),$(OBJDIR)/pt_gather_m$(m).o) \
             $(OBJDIR)/pt_film.o $(foreach m,$(RENDER_MODES),$(OBJDIR)/pt_film_m$(m).o) \
             $(OBJDIR)/pt_film_map.o $(foreach m,$(RENDER_MODES),$(OBJDIR)/pt_film_map_m$(m).o) \
-            $(OBJDIR)/pt_denoise.o $(OBJDIR)/pt_denoise_albedo.o
+            $(OBJDIR)/pt_denoise.o $(OBJDIR)/pt_denoise_albedo.o $(OBJDIR)/pt_chart.o
 
 # Every HIP translation unit is built in four steps instead of one `hipcc -c`, so that the device code can be CHECKED and REPAIRED between
 # the compiler and the assembler (tools/check_exec_prologue.py; profiles/r05/notes.md section 1: the AMDGPU backend of this toolchain can put
@@ -76,6 +76,7 @@ $(OBJDIR)/%.o: $(CSRC)/%.hip $(HIP_HDRS) tools/check_exec_prologue.py
 #   radiance  the radiance pass (pt_radiance.h): the interpreter over the caller's rays, <TEX, PARK> instantiations per mode
 #   gather    the gather pass (pt_gather.h): the same interpreter over the ambient-occlusion contract's rays, made in registers (pt_ao.h), summed per point; <TEX, PARK> per mode
 #   film      the film's sampling kernel (pt_film.h): the same interpreter with the camera as its source; its fold and resolve kernels (pt_film.hip): the %.o rule
+#   (chart    the chart pass has no tree walk and no modes: its three kernels and the host replay of its contract, pt_chart.hip, are built by the %.o rule)
 #   film_map  the film's per-pixel budget (pt_film_map.h): the sampling kernel over a list of samples; its plan, fold, error and budget kernels (pt_film_map.hip): the %.o rule
 # Static pattern rules, each over its own nine objects: as a plain pattern, pt_film_m%.o would match pt_film_map.o and pt_film_map_m1.o too.
 PASSES := render aov guides rays segments ao radiance gather film film_map
@@ -144,6 +145,16 @@ sanitize-raypk: build/sanitize/pt_api.o $(HIP_OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -Xarch_host $(SANITIZE) build/sanitize/raypk_sanitize.o build/sanitize/pt_api.o $(filter-out $(OBJDIR)/pt_api.o,$(HIP_OBJS)) -o build/sanitize/raypk_sanitize -ldl
 	build/sanitize/raypk_sanitize
 
+# `make sanitize-chart`: the host code of pt_chart.hip (the contract's host replay pt_test_chart_host) under AddressSanitizer + UBSan, driven by
+# tools/chart_sanitize.cpp as a program of its own on the CPU, built like sanitize-raypk. The program launches nothing.
+build/sanitize/pt_chart.o: $(CSRC)/pt_chart.hip $(HIP_HDRS) tools/check_exec_prologue.py
+	@mkdir -p build/sanitize
+	$(call hip_four_steps,-Xarch_host $(SANITIZE) -Xarch_host -fno-omit-frame-pointer)
+sanitize-chart: build/sanitize/pt_chart.o $(HIP_OBJS)
+	$(LLVM_BIN)/clang++ -O1 -g -std=c++17 $(SANITIZE) -fno-omit-frame-pointer -c tools/chart_sanitize.cpp -o build/sanitize/chart_sanitize.o
+	$(HIPCC) --offload-arch=$(ARCH) -Xarch_host $(SANITIZE) build/sanitize/chart_sanitize.o build/sanitize/pt_chart.o $(filter-out $(OBJDIR)/pt_chart.o,$(HIP_OBJS)) -o build/sanitize/chart_sanitize -ldl
+	build/sanitize/chart_sanitize
+
 clean:
 	rm -f portrayer_amd/*.so $(CSRC)/*.o
 	rm -rf build/asm
@@ -151,4 +162,4 @@ clean:
 	rm -rf build/sanitize
 	rm -rf examples/bin
 	$(MAKE) -C oracle clean
-.PHONY: all oracle clean hipobjs variant verify verify-mi sanitize-raypk switches $(SWITCH_TARGETS)
+.PHONY: all oracle clean hipobjs variant verify verify-mi sanitize-raypk sanitize-chart switches $(SWITCH_TARGETS)

@@ -566,6 +566,45 @@ int pt_gather_device(pt_context *ctx, const pt_gather_params *params, const doub
                      const pt_gather_buffers *device_out, void *hip_stream);
 int pt_gather_finish(pt_context *ctx, double *kernel_ms);
 
+/* ---- Chart: the texels of a mesh's light map as SURFACE POINTS - what pt_ao and pt_gather take (a position and a normal, 48 bytes), made on the device from
+ * what is resident there: the triangle records (kept current by pt_scene_deform and pt_scene_deform_device), the node's composed matrices (kept current by
+ * pt_scene_update) and a UV set. It does for surfaces what pt_aov does for cameras: behind pt_chart_device on the same stream pt_ao_device / pt_gather_device
+ * read position and normal where they are, and a baker moves nothing per texel but the results.
+ * `node` is a flattened node of type PT_PRIM_MESH or PT_PRIM_KDMESH; its mesh has T triangles (pt_chart_triangles). `uv` is T x 6 f64, per triangle the (u, v) of
+ * its corners a, b, c - per CORNER, because a light-map unwrap splits vertices at seams. uv = NULL: the mesh's own texture coordinates, where the scene keeps
+ * them on the device (a scene with a textured material, a mesh with mesh_has_texcoords); PT_ERR_ARGUMENT otherwise.
+ * The points are a CONTRACT, a fixed sequence of correctly rounded f64 operations (portrayer_amd/csrc/pt_chart.h states it in ten steps; pt_test_chart_host
+ * replays it on the host): a corner is (u width, (1 - v) height), rows top to bottom, no wrap; texel (x, y), index q = y width + x, is sampled at its centre; a
+ * triangle with a non-finite corner, one beyond 2^24 texels, or no area owns nothing; the edge functions are evaluated from canonically ordered endpoints, so
+ * two triangles that share an edge leave no texel centre between them, and coverage is inclusive; a texel belongs to the LOWEST triangle index that covers
+ * it, whatever the schedule. Position and normal are interpolated by the weights (the normal: the vertex normals' where the node shades smoothly, else the
+ * face's), taken to world space by the node's COMPOSED matrices in all three traversals, the normal normalised and, with PT_CHART_FLIP_NORMAL, negated.
+ * Outputs, each OPTIONAL (NULL = not wanted), at least one, row-major over the map:
+ *   position  width x height x 3  f64   not owned: +0, +0, +0
+ *   normal    width x height x 3  f64   not owned: +0, +0, +0 - an invalid point for pt_ao and pt_gather: it traces nothing
+ *   tri       width x height      i32   the owner, 0 .. T - 1, or -1
+ *   covered   width x height      u8    1 or 0
+ * The pass runs on pt_aov's pass object, as pt_guides does: ONE aov, guides or chart pass in flight per context (a second is PT_ERR_ARGUMENT), and
+ * pt_chart_device is closed by pt_aov_finish. The owner map (4 bytes per texel) is a buffer of the context's, grown on demand.
+ * Errors, before the first HIP call and in this order: PT_ERR_ARGUMENT (a NULL context / params / buffers; no buffer asked for; unknown flags; width or height
+ * zero, or width x height > PT_AO_MAX), PT_ERR_NO_SCENE, PT_ERR_ARGUMENT (node >= the scene's nodes; a node that is no mesh; uv NULL for a mesh whose texture
+ * coordinates are not on the device; a pass in flight). pt_chart_device then holds every caller pointer to pt_check_device_pointer's rule - device memory of the
+ * context's device, 8-byte aligned, long enough - before any kernel is queued. */
+#define PT_CHART_FLIP_NORMAL 1u
+typedef struct { uint32_t node, width, height, flags; } pt_chart_params;
+typedef struct { double *position; double *normal; int32_t *tri; uint8_t *covered; } pt_chart_buffers;
+/* T of the node's mesh; the errors of pt_chart that concern the node. */
+int pt_chart_triangles(pt_context *ctx, uint32_t node, uint64_t *n_tris);
+/* Host buffers, synchronous: uploads `uv`, copies back the buffers asked for. kernel_ms (optional): device time of the three kernels (HIP events). */
+int pt_chart(pt_context *ctx, const pt_chart_params *params, const double *uv, const pt_chart_buffers *host_out, double *kernel_ms);
+/* The same with the UV set and the results in DEVICE memory, queued on `hip_stream` (a hipStream_t, or NULL for the default stream) without synchronising the
+ * host; closed by pt_aov_finish. */
+int pt_chart_device(pt_context *ctx, const pt_chart_params *params, const double *d_uv, const pt_chart_buffers *device_out, void *hip_stream);
+/* Test hook, no context and no GPU: the contract on the host, by the functions the kernels compile. fwd: the node's 12 doubles, nrm: its 9; tri_v, tri_n: n_tris
+ * 72-byte records (tri_n NULL: the node shades flat); uv n_tris x 6; outputs as above, host memory. */
+int pt_test_chart_host(const double *fwd, const double *nrm, uint64_t n_tris, const double *tri_v, const double *tri_n, const double *uv, uint32_t width,
+                       uint32_t height, uint32_t flags, const pt_chart_buffers *out);
+
 /* ---- Film: a width x height accumulator in DEVICE memory that belongs to a context - a preview that sharpens, a render that can stop when it is good enough,
  * more samples where the image is noisy. Per pixel: `total` (3 f64, the sum of its complete 8-sample chunks), `partial` (3 f64, the sum of the open chunk) and
  * `count` (u32, samples taken so far): 52 bytes, nothing per sample.

@@ -181,6 +181,23 @@ int ph_renderer_gather(ph_renderer *r, const pt_gather_params *params, const dou
 int ph_renderer_gather_camera(ph_renderer *r, const double camera[10], uint32_t width, uint32_t height, const pt_gather_params *params, const double *background,
                               const pt_gather_buffers *out, double *kernel_ms);
 
+/* A mesh's light-map texels as surface points (see pt_chart): `params->node` indexes the flattened nodes, `uv` is T x 6 f64 per corner (ph_renderer_chart_triangles
+ * gives T) or NULL for the mesh's own texture coordinates; host buffers out, width x height entries each, each optional. A renderer spread over a node runs the
+ * pass on rank 0's context. */
+int ph_renderer_chart_triangles(ph_renderer *r, uint32_t node, uint64_t *n_tris);
+/* The mesh under flattened node `node`: counts = {vertices, triangles}; `indices` (optional): cap_tris x 3 vertex indices, cap_tris = the triangle count - what
+ * expands a per-vertex UV set to corners. PH_ERR_ARGUMENT for a node that is out of range or no mesh. Needs no GPU work. */
+int ph_renderer_chart_mesh(ph_renderer *r, uint32_t node, uint64_t counts[2], uint32_t cap_tris, uint32_t *indices);
+int ph_renderer_chart(ph_renderer *r, const pt_chart_params *params, const double *uv, const pt_chart_buffers *out, double *kernel_ms);
+/* Ambient occlusion and gathered radiance at every texel of a mesh's light map, built like ph_renderer_ao_camera / ph_renderer_gather_camera: pt_chart_device
+ * writes position and normal into device memory kept with the renderer, and pt_ao_device / pt_gather_device reads them there on the same stream; point
+ * q = y * width + x. Of `params` samples, pass, seed, radius and bias are read (n = width x height, first_index = 0 and flags = 0 are set here: a chart's normals
+ * are turned by PT_CHART_FLIP_NORMAL, not towards an eye). Host buffers out, each optional: nothing per texel crosses the bus but the results; texels no
+ * triangle owns are invalid points. kernel_ms: the ambient-occlusion / gather pass's. */
+int ph_renderer_ao_chart(ph_renderer *r, const pt_chart_params *chart, const double *uv, const pt_ao_params *params, const pt_ao_buffers *out, double *kernel_ms);
+int ph_renderer_gather_chart(ph_renderer *r, const pt_chart_params *chart, const double *uv, const pt_gather_params *params, const double *background,
+                             const pt_gather_buffers *out, double *kernel_ms);
+
 /* Radiance along rays of the caller's own (see pt_radiance): n x 3 f64 origins and directions in world space, `background` 3 doubles or n x 3
  * (params->background_per_ray), rgb n x 3 f64 out: one linear sample of Ray::color per ray. A renderer spread over a node runs the pass on rank 0's context. */
 int ph_renderer_radiance(ph_renderer *r, const pt_radiance_params *params, const double *origins, const double *directions, const double *background, double *rgb,

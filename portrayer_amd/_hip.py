@@ -163,6 +163,21 @@ class PtGatherBuffers(C.Structure):
 GATHER_BUFFERS = {"sum": (np.float64, 3), "valid": (np.uint8, 1)}
 
 
+class PtChartParams(C.Structure):
+    """pt_chart_params: the flattened mesh node whose light map is charted, the map's size, CHART_FLIP_NORMAL or 0."""
+    _fields_ = [("node", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class PtChartBuffers(C.Structure):
+    """pt_chart_buffers: position and normal (H, W, 3) f64, tri (H, W) i32, covered (H, W) u8; each optional."""
+    _fields_ = [("position", _dp), ("normal", _dp), ("tri", _ip), ("covered", _u8p)]
+
+
+# pt_chart's outputs in the order of pt_chart_buffers: name -> (numpy dtype, components per texel)
+CHART_BUFFERS = {"position": (np.float64, 3), "normal": (np.float64, 3), "tri": (np.int32, 1), "covered": (np.uint8, 1)}
+CHART_FLIP_NORMAL = 1  # PT_CHART_FLIP_NORMAL
+
+
 class PtRadianceParams(C.Structure):
     _fields_ = [("n", C.c_uint64), ("reorder", C.c_int32), ("background_per_ray", C.c_int32), ("seed", C.c_uint64), ("stream_base", C.c_uint64), ("sample", C.c_uint32)]
 
@@ -228,7 +243,8 @@ EXPORTS = ["pt_abi_version", "pt_device_count", "pt_context_create", "pt_context
            "pt_film_denoise", "pt_film_denoise_device", "pt_test_denoise_host",
            "pt_guides", "pt_guides_device", "pt_guides_finish", "pt_film_denoise_albedo", "pt_film_denoise_albedo_device", "pt_test_denoise_albedo_host",
            "pt_ao", "pt_ao_device", "pt_ao_finish", "pt_test_ao_rays_host", "pt_test_ao_tables",
-           "pt_gather", "pt_gather_device", "pt_gather_finish", "pt_test_kernel_choice"]
+           "pt_gather", "pt_gather_device", "pt_gather_finish", "pt_test_kernel_choice",
+           "pt_chart_triangles", "pt_chart", "pt_chart_device", "pt_test_chart_host"]
 
 
 def header_functions():
@@ -401,6 +417,14 @@ def lib() -> C.CDLL:
         l.pt_gather_device.argtypes = [C.c_void_p, C.POINTER(PtGatherParams), C.c_void_p, C.c_void_p, _dp, C.POINTER(PtGatherBuffers), C.c_void_p]
         l.pt_gather_finish.restype = C.c_int
         l.pt_gather_finish.argtypes = [C.c_void_p, _dp]
+        l.pt_chart_triangles.restype = C.c_int
+        l.pt_chart_triangles.argtypes = [C.c_void_p, C.c_uint32, _u64p]
+        l.pt_chart.restype = C.c_int
+        l.pt_chart.argtypes = [C.c_void_p, C.POINTER(PtChartParams), _dp, C.POINTER(PtChartBuffers), _dp]
+        l.pt_chart_device.restype = C.c_int
+        l.pt_chart_device.argtypes = [C.c_void_p, C.POINTER(PtChartParams), C.c_void_p, C.POINTER(PtChartBuffers), C.c_void_p]
+        l.pt_test_chart_host.restype = C.c_int
+        l.pt_test_chart_host.argtypes = [_dp, _dp, C.c_uint64, _dp, _dp, _dp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(PtChartBuffers)]
         l.pt_radiance.restype = C.c_int
         l.pt_radiance.argtypes = [C.c_void_p, C.POINTER(PtRadianceParams), _dp, _dp, _dp, _dp, _dp]
         l.pt_radiance_device.restype = C.c_int

@@ -7,6 +7,7 @@
 #include "pt_context.h"
 #include "pt_aov_inst.h"
 #include "pt_guides_inst.h"
+#include "pt_chart.h"
 #include "pt_rays_inst.h"
 #include "pt_segments_inst.h"
 #include "pt_ao_inst.h"
@@ -1167,8 +1168,9 @@ static hipError_t pt_aov_dispatch(const PtAovArgs& a, int n_cu, hipStream_t stre
     PT_MODE_LAUNCH(pt_aov_launch_mode_, a.r.scene.mode, a, n_cu, stream, grid, launch)
 }
 
-// What refuses a second pass on the pass object pt_aov and pt_guides share: the open one's kind and the call that closes it.
+// What refuses a second pass on the pass object pt_aov, pt_guides and pt_chart share: the open one's kind and the call that closes it.
 static const char* pt_aov_open_words(const pt_context* c) {
+    if (c->aov.chart) return "a pt_chart_device pass is in flight: pt_aov_finish first";
     return c->aov.guides ? "a pt_guides_device pass is in flight: pt_guides_finish first" : "a pt_aov_device pass is in flight: pt_aov_finish first";
 }
 
@@ -1242,7 +1244,7 @@ extern "C" int pt_aov_device(pt_context* c, const pt_camera* cam, const pt_aov_p
     int rc = pt_aov_check(c, cam, p, device_out);
     if (rc) return rc;
     PT_HIP(c, hipSetDevice(c->device));
-    c->aov.guides = false;
+    c->aov.guides = false; c->aov.chart = false;
     return pt_pass_device_tail(c, c->aov.pass, pt_aov_common(c, cam, p, *device_out, (hipStream_t)hip_stream));
 }
 
@@ -1326,12 +1328,131 @@ extern "C" int pt_guides_device(pt_context* c, const pt_camera* cam, const pt_ao
     int rc = pt_guides_check(c, cam, p, device_out);
     if (rc) return rc;
     PT_HIP(c, hipSetDevice(c->device));
-    c->aov.guides = true;
+    c->aov.guides = true; c->aov.chart = false;
     return pt_pass_device_tail(c, c->aov.pass, pt_guides_common(c, cam, p, *device_out, (hipStream_t)hip_stream));
 }
 
 // The pass is pt_aov's: one function closes either.
 extern "C" int pt_guides_finish(pt_context* c, double* kernel_ms) { return pt_aov_finish(c, kernel_ms); }
+
+// ------------------------------------------------------------------------------------------------
+// Chart (pt_chart.h: the contract; pt_chart.hip: the kernels): a mesh's light-map texels as surface points, on the primary-visibility pass's PtPass
+// ------------------------------------------------------------------------------------------------
+// What concerns the node, in the order the header gives; the context has a scene. mesh_out: the node's mesh.
+static int pt_chart_node_check(pt_context* c, uint32_t node, uint32_t* mesh_out) {
+    const pt_context::Resident& res = c->res;
+    if (node >= res.n_nodes) return pt_fail(c, PT_ERR_ARGUMENT, "pt_chart: node " + std::to_string(node) + " of " + std::to_string(res.n_nodes) + " flattened nodes");
+    const uint32_t type = res.info[4 * (size_t)node];
+    if (type != PT_PRIM_MESH && type != PT_PRIM_KDMESH) return pt_fail(c, PT_ERR_ARGUMENT, "pt_chart: node " + std::to_string(node) + " is no mesh (PT_PRIM_MESH, PT_PRIM_KDMESH)");
+    *mesh_out = res.info[4 * (size_t)node + 1];
+    return PT_OK;
+}
+
+// Everything that can be refused without a HIP call, in the order the header gives. (pt_fail takes a NULL context.)
+static int pt_chart_check(pt_context* c, const pt_chart_params* p, const double* uv, const pt_chart_buffers* out, uint32_t* mesh_out) {
+    if (!c || !p || !out) return pt_fail(c, PT_ERR_ARGUMENT, "pt_chart: NULL context, params or buffers");
+    if (!(out->position || out->normal || out->tri || out->covered)) return pt_fail(c, PT_ERR_ARGUMENT, "pt_chart: no output buffer asked for");
+    if (p->flags & ~PT_CHART_FLIP_NORMAL) return pt_fail(c, PT_ERR_ARGUMENT, "pt_chart: unknown flags");
+    if (p->width == 0 || p->height == 0) return pt_fail(c, PT_ERR_ARGUMENT, "pt_chart: width and height must be positive");
+    if ((uint64_t)p->width * p->height > PT_AO_MAX) return pt_fail(c, PT_ERR_ARGUMENT, "pt_chart: more than PT_AO_MAX texels");
+    if (!c->have_scene) return pt_fail(c, PT_ERR_NO_SCENE, "no scene uploaded");
+    if (int rc = pt_chart_node_check(c, p->node, mesh_out)) return rc;
+    if (!uv && !(c->view.tri_uv && c->res.place[*mesh_out].has_uv))
+        return pt_fail(c, PT_ERR_ARGUMENT, c->view.tri_uv ? "pt_chart: uv is NULL and the node's mesh has no texture coordinates of its own (mesh_has_texcoords)"
+                                                          : "pt_chart: uv is NULL and the scene keeps no texture coordinates on the device (no material has a texture or a normal map)");
+    if (c->aov.pass.pending) return pt_fail(c, PT_ERR_ARGUMENT, pt_aov_open_words(c));
+    return PT_OK;
+}
+
+extern "C" int pt_chart_triangles(pt_context* c, uint32_t node, uint64_t* n_tris) {
+    if (!c || !n_tris) return pt_fail(c, PT_ERR_ARGUMENT, "pt_chart_triangles: NULL context or n_tris");
+    if (!c->have_scene) return pt_fail(c, PT_ERR_NO_SCENE, "no scene uploaded");
+    uint32_t mesh = 0;
+    if (int rc = pt_chart_node_check(c, node, &mesh)) return rc;
+    *n_tris = c->res.meshes[mesh].tri_count;
+    return PT_OK;
+}
+
+// Which of the kernels a pass queues: all three. PORTRAYER_CHART_PHASES=1 (seed and own) or 2 (resolve, over the owner map the call before left) lets
+// profiles/chart/measure.py time them apart.
+static int pt_chart_phases() {
+    if (const char* e = getenv("PORTRAYER_CHART_PHASES")) {
+        const int w = atoi(e);
+        if (w == 1 || w == 2) return w;
+    }
+    return 3;
+}
+
+// Queues the pass on `stream` (pt_pass_open ... pt_pass_seal) on pt_aov's PtPass. d_uv null: the mesh's own coordinates in tri_uv. `out` holds DEVICE pointers.
+// No tree is walked: the pass opens with an empty launch (no lanes, no stack columns) for the events and the protocol alone.
+static int pt_chart_common(pt_context* c, const pt_chart_params* p, uint32_t mesh, const double* d_uv, const pt_chart_buffers& out, hipStream_t stream) {
+    PtPass& v = c->aov.pass;
+    int rc = pt_pass_prepare(c, v);
+    if (rc) return rc;
+    if ((rc = pt_reserve(c, c->aov.chart_owner, (size_t)p->width * p->height * 4))) return rc;
+    const PtMeshInfo& mi = c->res.meshes[mesh];
+    const bool smooth = (c->res.info[4 * (size_t)p->node + 2] & 1u) != 0 && c->view.tri_n != nullptr;  // (pt_hit_model's choice; the upload refuses a smooth node without normals)
+    PtChartArgs a;
+    memset(&a, 0, sizeof a);
+    a.width = p->width; a.height = p->height; a.flags = p->flags; a.n_tris = mi.tri_count;
+    a.uv = d_uv ? d_uv : c->view.tri_uv + 6 * (size_t)mi.tri_first;
+    a.tri_v = c->view.tri_v + 9 * (size_t)mi.tri_first;
+    a.tri_n = smooth ? c->view.tri_n + 9 * (size_t)mi.tri_first : nullptr;
+    a.fwd = c->view.fwd + 12 * (size_t)p->node; a.nrm = c->view.nrm + 9 * (size_t)p->node;
+    a.owner = (uint32_t*)c->aov.chart_owner.p;
+    a.position = out.position; a.normal = out.normal; a.tri = out.tri; a.covered = out.covered;
+    PtRenderArgs r;
+    memset(&r, 0, sizeof r);
+    r.scene = c->view;
+    if ((rc = pt_pass_open(c, v, r, 0, false, stream))) return rc;
+    PT_HIP(c, pt_chart_launch(a, pt_chart_phases(), stream));
+    return pt_pass_seal(c, v);
+}
+
+extern "C" int pt_chart(pt_context* c, const pt_chart_params* p, const double* uv, const pt_chart_buffers* host_out, double* kernel_ms) {
+    uint32_t mesh = 0;
+    int rc = pt_chart_check(c, p, uv, host_out, &mesh);
+    if (rc) return rc;
+    PT_HIP(c, hipSetDevice(c->device));
+    const size_t n = (size_t)p->width * p->height, n_tris = c->res.meshes[mesh].tri_count;
+    void* host[4] = {host_out->position, host_out->normal, host_out->tri, host_out->covered};
+    PtBuf* buf[4] = {&c->aov.out[1], &c->aov.out[2], &c->aov.out[3], &c->aov.chart_covered};
+    const size_t elem[4] = {24, 24, 4, 1};  // bytes per texel
+    void* dev[4] = {nullptr, nullptr, nullptr, nullptr};
+    for (int k = 0; k < 4; k++) {
+        if (!host[k]) continue;
+        if ((rc = pt_reserve(c, *buf[k], n * elem[k]))) return rc;
+        dev[k] = buf[k]->p;
+    }
+    const double* d_uv = nullptr;
+    if (uv) {
+        if ((rc = pt_reserve(c, c->aov.chart_uv, n_tris * 48))) return rc;
+        if (n_tris) PT_HIP(c, hipMemcpy(c->aov.chart_uv.p, uv, n_tris * 48, hipMemcpyHostToDevice));
+        d_uv = (const double*)c->aov.chart_uv.p;
+    }
+    pt_chart_buffers d_out;
+    d_out.position = (double*)dev[0]; d_out.normal = (double*)dev[1]; d_out.tri = (int32_t*)dev[2]; d_out.covered = (uint8_t*)dev[3];
+    if ((rc = pt_pass_settle(c, c->aov.pass, pt_chart_common(c, p, mesh, d_uv, d_out, nullptr)))) return rc;
+    for (int k = 0; k < 4; k++)
+        if (host[k]) PT_HIP(c, hipMemcpy(host[k], dev[k], n * elem[k], hipMemcpyDeviceToHost));
+    return pt_pass_result(c, c->aov.pass, kernel_ms);
+}
+
+extern "C" int pt_chart_device(pt_context* c, const pt_chart_params* p, const double* d_uv, const pt_chart_buffers* device_out, void* hip_stream) {
+    uint32_t mesh = 0;
+    int rc = pt_chart_check(c, p, d_uv, device_out, &mesh);
+    if (rc) return rc;
+    PT_HIP(c, hipSetDevice(c->device));
+    // the caller's pointers, before anything is queued: device memory of this device, and long enough
+    const uint64_t n = (uint64_t)p->width * p->height, n_tris = c->res.meshes[mesh].tri_count;
+    if (d_uv && n_tris && (rc = pt_check_device_pointer(c, d_uv, n_tris * 48, "pt_chart_device: d_uv"))) return rc;
+    if (device_out->position && (rc = pt_check_device_pointer(c, device_out->position, n * 24, "pt_chart_device: position"))) return rc;
+    if (device_out->normal && (rc = pt_check_device_pointer(c, device_out->normal, n * 24, "pt_chart_device: normal"))) return rc;
+    if (device_out->tri && (rc = pt_check_device_pointer(c, device_out->tri, n * 4, "pt_chart_device: tri"))) return rc;
+    if (device_out->covered && (rc = pt_check_device_pointer(c, device_out->covered, n, "pt_chart_device: covered"))) return rc;
+    c->aov.guides = false; c->aov.chart = true;
+    return pt_pass_device_tail(c, c->aov.pass, pt_chart_common(c, p, mesh, d_uv, *device_out, (hipStream_t)hip_stream));
+}
 
 // ------------------------------------------------------------------------------------------------
 // Ray queries (pt_rays.h)

@@ -114,6 +114,10 @@ struct pt_context {
         PtBuf out[6];
         PtBuf albedo;
         bool guides = false;  // the pass in flight (pass.pending) is a pt_guides_device one: which words a refusal uses
+        // The chart pass (pt_chart / pt_chart_device) runs on this pass too: its owner map (4 bytes per texel, grown on demand), and the host-buffer path's
+        // device copies of the UV set and of `covered` (position, normal and tri: out[1 .. 3])
+        PtBuf chart_owner, chart_uv, chart_covered;
+        bool chart = false;   // ... or a pt_chart_device one
     } aov;
     // The ray-query pass (pt_rays / pt_segments, their _device forms ... pt_rays_finish): the device copies of the host-buffer path's inputs (in_t_max: pt_segments'
     // third) and seven outputs.
@@ -158,6 +162,7 @@ struct pt_context {
             int depth = 0;                 // of the two-child tree
             bool device_built = false;     // its place has the device builder's worst-case size: it can be rebuilt there
             bool has_normals = false;
+            bool has_uv = false;           // tri_uv holds the mesh's own texture coordinates (a textured scene, mesh_has_texcoords): pt_chart's default UV set
             bool parents_valid = false;    // tree_parent holds this tree's parents (set by the first refit, cleared by a rebuild)
         };
         std::vector<MeshPlace> place;

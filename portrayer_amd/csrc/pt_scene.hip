@@ -789,6 +789,7 @@ static int pt_upload_pack_textures(pt_context* c, PtUploadPlan& p) {
             }
             tri_has_uv[t] = 1;
         }
+        p.res.place[m].has_uv = true;
     }
     for (uint32_t t = 0; t < s->n_triangles; t++)
         if (s->tri_texcoords && s->tri_has_texcoords && s->tri_has_texcoords[t]) {

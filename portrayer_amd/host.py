@@ -19,7 +19,7 @@ _dp, _ip, _up, _u64p, _u8p = H._dp, H._ip, H._up, H._u64p, H._u8p
 
 EXPORTS = ["ph_last_error", "ph_scene_create", "ph_example_scene", "ph_scene_destroy", "ph_scene_counts", "ph_scene_export", "ph_scene_export_textures",
            "ph_scene_flatten", "ph_scene_kdtree", "ph_camera", "ph_obj_load", "ph_renderer_create", "ph_renderer_destroy",
-           "ph_renderer_context", "ph_renderer_ranks", "ph_renderer_node", "ph_renderer_prepare_ms", "ph_renderer_render", "ph_renderer_aov", "ph_renderer_rays", "ph_renderer_segments", "ph_renderer_ao", "ph_renderer_ao_camera", "ph_renderer_gather", "ph_renderer_gather_camera", "ph_renderer_radiance", "ph_renderer_film_create", "ph_renderer_film_destroy", "ph_renderer_film_reset", "ph_renderer_film_add", "ph_renderer_film_resolve", "ph_renderer_film_counts", "ph_renderer_film_create_moments", "ph_renderer_film_add_map", "ph_renderer_film_error", "ph_renderer_film_refine", "ph_renderer_film_denoise", "ph_renderer_guides", "ph_renderer_film_denoise_albedo", "ph_renderer_update", "ph_scene_same_structure", "ph_renderer_deform", "ph_scene_same_topology", "ph_renderer_deform_device", "ph_renderer_mesh_count", "ph_renderer_mesh_vertices", "ph_example_render_to_png", "ph_png_read", "ph_png_write", "ph_image_read", "ph_scene_graph"]
+           "ph_renderer_context", "ph_renderer_ranks", "ph_renderer_node", "ph_renderer_prepare_ms", "ph_renderer_render", "ph_renderer_aov", "ph_renderer_rays", "ph_renderer_segments", "ph_renderer_ao", "ph_renderer_ao_camera", "ph_renderer_gather", "ph_renderer_gather_camera", "ph_renderer_chart_triangles", "ph_renderer_chart_mesh", "ph_renderer_chart", "ph_renderer_ao_chart", "ph_renderer_gather_chart", "ph_renderer_radiance", "ph_renderer_film_create", "ph_renderer_film_destroy", "ph_renderer_film_reset", "ph_renderer_film_add", "ph_renderer_film_resolve", "ph_renderer_film_counts", "ph_renderer_film_create_moments", "ph_renderer_film_add_map", "ph_renderer_film_error", "ph_renderer_film_refine", "ph_renderer_film_denoise", "ph_renderer_guides", "ph_renderer_film_denoise_albedo", "ph_renderer_update", "ph_scene_same_structure", "ph_renderer_deform", "ph_scene_same_topology", "ph_renderer_deform_device", "ph_renderer_mesh_count", "ph_renderer_mesh_vertices", "ph_example_render_to_png", "ph_png_read", "ph_png_write", "ph_image_read", "ph_scene_graph"]
 
 
 class PortrayerHostError(RuntimeError):
@@ -97,6 +97,16 @@ def lib() -> C.CDLL:
         l.ph_renderer_gather.argtypes = [vp, C.POINTER(H.PtGatherParams), _dp, _dp, _dp, C.POINTER(H.PtGatherBuffers), _dp]
         l.ph_renderer_gather_camera.restype = C.c_int
         l.ph_renderer_gather_camera.argtypes = [vp, _dp, C.c_uint32, C.c_uint32, C.POINTER(H.PtGatherParams), _dp, C.POINTER(H.PtGatherBuffers), _dp]
+        l.ph_renderer_chart_triangles.restype = C.c_int
+        l.ph_renderer_chart_triangles.argtypes = [vp, C.c_uint32, _u64p]
+        l.ph_renderer_chart_mesh.restype = C.c_int
+        l.ph_renderer_chart_mesh.argtypes = [vp, C.c_uint32, _u64p, C.c_uint32, _up]
+        l.ph_renderer_chart.restype = C.c_int
+        l.ph_renderer_chart.argtypes = [vp, C.POINTER(H.PtChartParams), _dp, C.POINTER(H.PtChartBuffers), _dp]
+        l.ph_renderer_ao_chart.restype = C.c_int
+        l.ph_renderer_ao_chart.argtypes = [vp, C.POINTER(H.PtChartParams), _dp, C.POINTER(H.PtAoParams), C.POINTER(H.PtAoBuffers), _dp]
+        l.ph_renderer_gather_chart.restype = C.c_int
+        l.ph_renderer_gather_chart.argtypes = [vp, C.POINTER(H.PtChartParams), _dp, C.POINTER(H.PtGatherParams), _dp, C.POINTER(H.PtGatherBuffers), _dp]
         l.ph_renderer_radiance.restype = C.c_int
         l.ph_renderer_radiance.argtypes = [vp, C.POINTER(H.PtRadianceParams), _dp, _dp, _dp, _dp, _dp]
         l.ph_renderer_film_create.restype = C.c_int; l.ph_renderer_film_create.argtypes = [vp, C.c_uint32, C.c_uint32, C.POINTER(vp)]
@@ -915,6 +925,140 @@ class Renderer:
             raise ValueError("cam10 must hold 10 numbers, got shape %r" % (c.shape,))
         ms = C.c_double(0.0)
         _check(lib().ph_renderer_gather_camera(self._h, _p(c, _dp), int(width), int(height), C.byref(p), _p(bg, _dp), C.byref(b), C.byref(ms)), "ph_renderer_gather_camera")
+        return self._gather_result(out, samples, ms)
+
+    def _chart_node(self, node):
+        """chart()'s node check: the flattened node's index, and its mesh's vertex count, triangle count and (T, 3) vertex indices (ph_renderer_chart_mesh)"""
+        if isinstance(node, bool) or not isinstance(node, (int, np.integer)) or not 0 <= int(node) < 1 << 32:
+            raise ValueError("node must index the flattened nodes (Scene.flatten()), got %r" % (node,))
+        counts = np.zeros(2, dtype=np.uint64)
+        rc = lib().ph_renderer_chart_mesh(self._h, int(node), _p(counts, _u64p), 0, None)
+        if rc == H.ERR_ARGUMENT:
+            raise ValueError("node %d: %s" % (int(node), lib().ph_last_error().decode()))
+        _check(rc, "ph_renderer_chart_mesh")
+        n_verts, n_tris = int(counts[0]), int(counts[1])
+        idx = np.zeros((n_tris, 3), dtype=np.uint32)
+        if n_tris:
+            _check(lib().ph_renderer_chart_mesh(self._h, int(node), _p(counts, _u64p), n_tris, _p(idx, _up)), "ph_renderer_chart_mesh")
+        return int(node), n_verts, n_tris, idx
+
+    def _chart_params(self, node, width, height, uv, flip_normal):
+        """chart()'s, ao_chart()'s and gather_chart()'s argument checks: the pt_chart_params, and the UV set as a (T, 6) float64 array per corner, a torch tensor
+        on the renderer's GPU, or None (the mesh's own texture coordinates)"""
+        for name, v in (("width", width), ("height", height)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or int(v) < 1:
+                raise ValueError("%s must be a positive integer, got %r" % (name, v))
+        if int(width) * int(height) > H.AO_MAX:
+            raise ValueError("at most %d texels per map" % H.AO_MAX)
+        if not isinstance(flip_normal, (bool, np.bool_)):
+            raise ValueError("flip_normal must be a bool, got %r" % (flip_normal,))
+        node, n_verts, n_tris, idx = self._chart_node(node)
+        if uv is not None and not isinstance(uv, np.ndarray) and type(uv).__module__.split(".")[0] == "torch":
+            _device_tensor_pointer(uv, tuple(uv.shape) if tuple(uv.shape) in ((n_tris, 6), (n_tris, 3, 2)) else (n_tris, 6), self._device, "uv")
+        elif uv is not None:
+            uv = np.asarray(uv)
+            if uv.dtype != np.float64:
+                raise ValueError("uv must be float64, got %s" % uv.dtype)
+            if uv.shape == (n_tris, 3, 2) or uv.shape == (n_tris, 6):
+                uv = np.ascontiguousarray(uv.reshape(n_tris, 6))
+            elif uv.shape == (n_verts, 2):
+                uv = np.ascontiguousarray(uv[idx.astype(np.int64)].reshape(n_tris, 6))  # per vertex -> per corner, through the mesh's indices
+            else:
+                raise ValueError("uv must be (%d, 3, 2) or (%d, 6) per corner or (%d, 2) per vertex, got %r" % (n_tris, n_tris, n_verts, uv.shape))
+        return H.PtChartParams(node, int(width), int(height), H.CHART_FLIP_NORMAL if flip_normal else 0), uv
+
+    def chart(self, node: int, width: int, height: int, uv=None, flip_normal: bool = False, want=("position", "normal", "tri", "covered"),
+              into: Optional[dict] = None) -> dict:
+        """The texels of a mesh's light map as surface points (pt_chart): `node` indexes Scene.flatten()'s nodes (as g["node"] of aov() does) and must be a mesh;
+        `uv` is its light-map unwrap - (T, 3, 2) or (T, 6) float64 per triangle corner, or (n_verts, 2) per vertex (expanded here through the mesh's indices), or
+        None for the mesh's own texture coordinates (a scene with a textured material only). Texel (x, y) is sampled at its centre, v = 1 at the top row; it
+        belongs to the lowest triangle that covers it. Returns the arrays named in `want` - `position` and `normal` (H, W, 3) float64 in world space, from the
+        vertices and matrices RESIDENT on the device (after deform(), deform_device() and update(): the new ones), `tri` (H, W) int32 (-1: no triangle),
+        `covered` (H, W) uint8 - and `kernel_ms`. Unowned texels hold zeros: invalid points for ao() and gather(). flip_normal negates every normal (the inside
+        of a room). `uv` and the arrays of `into` may be torch tensors on the renderer's GPU (float64 / int32 / uint8, contiguous): the pass is then queued on
+        torch's current stream (pt_chart_device), waited for, and what `into` does not hold comes back as tensors too."""
+        want = tuple(want)
+        unknown = [n for n in want if n not in H.CHART_BUFFERS]
+        if unknown or not want:
+            raise ValueError("want must name some of %s, got %r" % (", ".join(H.CHART_BUFFERS), want))
+        p, uv = self._chart_params(node, width, height, uv, flip_normal)
+        shape = (int(height), int(width))
+        on_device = (uv is not None and not isinstance(uv, np.ndarray)) or (into is not None and any(not isinstance(into[n], np.ndarray) for n in want if n in into))
+        if on_device:
+            return self._chart_on_device(p, uv, want, into, shape)
+        out, b = {}, H.PtChartBuffers()
+        for name in want:
+            dtype, comps = H.CHART_BUFFERS[name]
+            full = shape if comps == 1 else shape + (comps,)
+            a = into[name] if into is not None and name in into else np.zeros(full, dtype=dtype)
+            if not isinstance(a, np.ndarray) or a.shape != full or a.dtype != dtype or not a.flags.c_contiguous:
+                raise ValueError("into[%r] must be a C-contiguous %s array of shape %r" % (name, np.dtype(dtype).name, full))
+            out[name] = a
+            setattr(b, name, _p(a, {np.int32: _ip, np.uint8: _u8p, np.float64: _dp}[dtype]))
+        ms = C.c_double(0.0)
+        _check(lib().ph_renderer_chart(self._h, C.byref(p), _p(uv, _dp) if uv is not None else None, C.byref(b), C.byref(ms)), "ph_renderer_chart")
+        out["kernel_ms"] = ms.value
+        return out
+
+    def _chart_on_device(self, p, uv, want, into, shape):
+        """chart() with tensors: pt_chart_device on torch's current stream, closed by pt_aov_finish before it returns"""
+        import torch
+        dev = torch.device("cuda", self._device)
+        kinds = {np.float64: torch.float64, np.int32: torch.int32, np.uint8: torch.uint8}
+        if isinstance(uv, np.ndarray):
+            uv = torch.from_numpy(uv).to(dev)
+        out, b = {}, H.PtChartBuffers()
+        for name in want:
+            dtype, comps = H.CHART_BUFFERS[name]
+            full = shape if comps == 1 else shape + (comps,)
+            t = into[name] if into is not None and name in into else torch.zeros(full, dtype=kinds[dtype], device=dev)
+            if not isinstance(t, torch.Tensor) or tuple(t.shape) != full or t.dtype != kinds[dtype] or not t.is_contiguous() or t.device != dev:
+                raise ValueError("into[%r] must be a contiguous %s tensor of shape %r on %s (all of `into` numpy arrays, or all tensors)" % (name, kinds[dtype], full, dev))
+            out[name] = t
+            setattr(b, name, C.cast(C.c_void_p(t.data_ptr()), {np.int32: _ip, np.uint8: _u8p, np.float64: _dp}[dtype]))
+        ctx, l = self.context, H.lib()
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        rc = l.pt_chart_device(ctx, C.byref(p), C.c_void_p(uv.data_ptr()) if uv is not None else None, C.byref(b), C.c_void_p(stream))
+        if rc != H.OK:
+            why = l.pt_last_error(ctx).decode()
+            if rc == H.ERR_ARGUMENT:
+                raise ValueError("pt_chart_device: " + why)
+            raise PortrayerHostError("pt_chart_device failed (%d): %s" % (rc, why))
+        ms = C.c_double(0.0)
+        rc = l.pt_aov_finish(ctx, C.byref(ms))
+        if rc != H.OK:
+            raise PortrayerHostError("pt_aov_finish failed (%d): %s" % (rc, l.pt_last_error(ctx).decode()))
+        out["kernel_ms"] = ms.value
+        return out
+
+    def ao_chart(self, node: int, width: int, height: int, uv=None, samples: int = 16, radius: float = float("inf"), bias: float = 0.0, seed: int = 0,
+                 pass_index: int = 0, flip_normal: bool = False, want=("occluded",), into: Optional[dict] = None) -> dict:
+        """Ambient occlusion at every texel of a mesh's light map (pt_chart_device then pt_ao_device on the device): the bits of
+        ao(chart's position, chart's normal, first_index=0, ...), texel (x, y) the stream index y * width + x. Nothing per texel crosses the bus but the results:
+        arrays of shape (H, W) - `bent` (H, W, 3) - as in ao(), with `visibility`; texels no triangle owns are invalid points (valid 0, visibility 1). `node`,
+        `uv` (numpy, or None) and flip_normal as in chart()."""
+        cp, uv = self._chart_params(node, width, height, uv, flip_normal)
+        if uv is not None and not isinstance(uv, np.ndarray):
+            raise ValueError("ao_chart takes uv as a numpy array or None; chart() takes tensors")
+        p = self._ao_params(int(width) * int(height), samples, radius, bias, seed, pass_index, 0, None)
+        out, b = self._ao_buffers(want, into, (int(height), int(width)))
+        ms = C.c_double(0.0)
+        _check(lib().ph_renderer_ao_chart(self._h, C.byref(cp), _p(uv, _dp) if uv is not None else None, C.byref(p), C.byref(b), C.byref(ms)), "ph_renderer_ao_chart")
+        return self._ao_result(out, samples, ms)
+
+    def gather_chart(self, node: int, width: int, height: int, background=(0.0, 0.0, 0.0), uv=None, samples: int = 16, bias: float = 0.0, seed: int = 0,
+                     pass_index: int = 0, flip_normal: bool = False, want=("sum",), into: Optional[dict] = None) -> dict:
+        """Gathered radiance at every texel of a mesh's light map (pt_chart_device then pt_gather_device on the device): the bits of
+        gather(chart's position, chart's normal, background, first_index=0, ...). `sum` and `mean` (H, W, 3), `valid` (H, W), as in gather(); the irradiance
+        estimate is pi x mean; texels no triangle owns are invalid points. `node`, `uv` (numpy, or None) and flip_normal as in chart()."""
+        cp, uv = self._chart_params(node, width, height, uv, flip_normal)
+        if uv is not None and not isinstance(uv, np.ndarray):
+            raise ValueError("gather_chart takes uv as a numpy array or None; chart() takes tensors")
+        p, bg = self._gather_params(int(width) * int(height), background, samples, bias, seed, pass_index, 0, None)
+        out, b = self._gather_buffers(want, into, (int(height), int(width)))
+        ms = C.c_double(0.0)
+        _check(lib().ph_renderer_gather_chart(self._h, C.byref(cp), _p(uv, _dp) if uv is not None else None, C.byref(p), _p(bg, _dp), C.byref(b), C.byref(ms)),
+               "ph_renderer_gather_chart")
         return self._gather_result(out, samples, ms)
 
     def radiance(self, origins, directions, background=(0.0, 0.0, 0.0), seed: int = 0, sample: int = 0, stream_base: int = 0, reorder: bool = False,

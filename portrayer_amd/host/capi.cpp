@@ -19,9 +19,14 @@ struct ph_renderer {
     // first use, grown with the image, freed with the renderer (before its context goes). ph_renderer_gather_camera uses the same five (its sums in the fifth)
     void* d_ao[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     uint64_t ao_points = 0;
+    // ph_renderer_ao_chart / ph_renderer_gather_chart: the same five for the map's texels, and the device copy of the caller's UV set (chart_uv_bytes long)
+    void* d_chart_uv = nullptr;
+    uint64_t chart_uv_bytes = 0;
     void ao_release() {
         for (void*& p : d_ao) { if (p) pt_device_free(r->context(), p); p = nullptr; }
         ao_points = 0;
+        if (d_chart_uv) pt_device_free(r->context(), d_chart_uv);
+        d_chart_uv = nullptr; chart_uv_bytes = 0;
     }
     ~ph_renderer() { if (r) ao_release(); }
 };
@@ -748,6 +753,134 @@ extern "C" int ph_renderer_gather_camera(ph_renderer* r, const double camera[10]
         if (rc) return fail(rc);
         if (out->sum && (rc = pt_copy_from_device(c, out->sum, r->d_ao[4], bytes[4]))) return fail(rc);
         if (out->valid && (rc = pt_copy_from_device(c, out->valid, r->d_ao[3], bytes[3]))) return fail(rc);
+        return PH_OK;
+    });
+}
+
+// A mesh's light-map texels as surface points (pt_chart): host buffers in and out.
+extern "C" int ph_renderer_chart_triangles(ph_renderer* r, uint32_t node, uint64_t* n_tris) {
+    if (!r || !n_tris) return bad("null argument");
+    return guarded([&]() -> int {
+        int rc = pt_chart_triangles(r->r->context(), node, n_tris);
+        if (rc != PT_OK) { g_error = pt_last_error(r->r->context()); return rc == PT_ERR_ARGUMENT ? PH_ERR_ARGUMENT : PH_ERR_RUNTIME; }
+        return PH_OK;
+    });
+}
+
+// The mesh under flattened node `node`, for a caller that expands a per-vertex UV set to corners: counts = {vertices, triangles}; `indices` (optional) gets
+// cap_tris x 3 vertex indices, and cap_tris must then be the triangle count.
+extern "C" int ph_renderer_chart_mesh(ph_renderer* r, uint32_t node, uint64_t counts[2], uint32_t cap_tris, uint32_t* indices) {
+    if (!r || !counts) return bad("null argument");
+    return guarded([&]() -> int {
+        const auto& nodes = r->r->flat().root;
+        if (node >= nodes.size()) return bad("node index out of range");
+        const auto& prim = nodes[node].geometry.primitive;
+        if (prim.kind != primitive::Primitive::MeshK && prim.kind != primitive::Primitive::KDMeshK) return bad("the node is no mesh");
+        counts[0] = prim.mesh->positions().size(); counts[1] = prim.mesh->triangles().size();
+        if (!indices) return PH_OK;
+        if (cap_tris != counts[1]) return bad("cap_tris is not the mesh's triangle count");
+        size_t k = 0;
+        for (const auto& t : prim.mesh->triangles()) { indices[k++] = t[0]; indices[k++] = t[1]; indices[k++] = t[2]; }
+        return PH_OK;
+    });
+}
+
+extern "C" int ph_renderer_chart(ph_renderer* r, const pt_chart_params* p, const double* uv, const pt_chart_buffers* out, double* kernel_ms) {
+    if (!r || !p || !out) return bad("null argument");
+    return guarded([&]() -> int {
+        int rc = pt_chart(r->r->context(), p, uv, out, kernel_ms);  // (a renderer spread over a node: rank 0's context, the whole map)
+        if (rc != PT_OK) { g_error = pt_last_error(r->r->context()); return rc == PT_ERR_ARGUMENT ? PH_ERR_ARGUMENT : PH_ERR_RUNTIME; }
+        return PH_OK;
+    });
+}
+
+// What ph_renderer_ao_chart and ph_renderer_gather_chart share: the renderer's device scratch for width x height texels (ph_renderer_ao_camera's five buffers), the
+// caller's UV set copied beside it (uv NULL: the mesh's own), and pt_chart_device queued on the default stream with position and normal in the first two. The
+// pass is left OPEN: the caller queues its own pass behind it and closes both. Returns a pt_ error code.
+static int chart_points(ph_renderer* r, const pt_chart_params* cp, const double* uv) {
+    pt_context* c = r->r->context();
+    const uint64_t n = (uint64_t)cp->width * cp->height;
+    const size_t bytes[5] = {n * 24, n * 24, n * 4, n * 1, n * 24};
+    int rc = PT_OK;
+    uint64_t n_tris = 0;
+    if ((rc = pt_chart_triangles(c, cp->node, &n_tris))) return rc;
+    if (r->ao_points < n) {
+        r->ao_release();
+        for (int k = 0; k < 5 && rc == PT_OK; k++) rc = pt_device_alloc(c, bytes[k], &r->d_ao[k]);
+        if (rc != PT_OK) { r->ao_release(); return rc; }
+        r->ao_points = n;
+    }
+    if (uv && n_tris) {
+        if (r->chart_uv_bytes < n_tris * 48) {
+            if (r->d_chart_uv) pt_device_free(c, r->d_chart_uv);
+            r->d_chart_uv = nullptr; r->chart_uv_bytes = 0;
+            if ((rc = pt_device_alloc(c, n_tris * 48, &r->d_chart_uv))) return rc;
+            r->chart_uv_bytes = n_tris * 48;
+        }
+        if ((rc = pt_copy_to_device(c, r->d_chart_uv, uv, n_tris * 48))) return rc;
+    }
+    pt_chart_buffers cb = {(double*)r->d_ao[0], (double*)r->d_ao[1], nullptr, nullptr};
+    return pt_chart_device(c, cp, uv && n_tris ? (const double*)r->d_chart_uv : nullptr, &cb, nullptr);
+}
+
+// Ambient occlusion at every texel of a mesh's light map, built like ph_renderer_ao_camera: pt_chart_device writes position and normal into the renderer's device
+// scratch, pt_ao_device behind it on the same stream reads them - point q = y * width + x, first_index 0, no PT_AO_FACE_EYE (a chart's normals face outwards or,
+// with PT_CHART_FLIP_NORMAL, inwards) - and only the results cross the bus. Of `params` samples, pass, seed, radius and bias are read.
+extern "C" int ph_renderer_ao_chart(ph_renderer* r, const pt_chart_params* chart, const double* uv, const pt_ao_params* p, const pt_ao_buffers* out, double* kernel_ms) {
+    if (!r || !chart || !p || !out) return bad("null argument");
+    if (chart->width == 0 || chart->height == 0) return bad("width and height must be positive");
+    if ((uint64_t)chart->width * chart->height > PT_AO_MAX) return bad("more than PT_AO_MAX texels");
+    if (!(out->occluded || out->valid || out->bent)) return bad("no output buffer asked for");
+    return guarded([&]() -> int {
+        pt_context* c = r->r->context();
+        auto fail = [&](int rc) { g_error = pt_last_error(c); return rc == PT_ERR_ARGUMENT ? PH_ERR_ARGUMENT : PH_ERR_RUNTIME; };
+        const uint64_t n = (uint64_t)chart->width * chart->height;
+        const size_t bytes[5] = {n * 24, n * 24, n * 4, n * 1, n * 24};
+        void* host_out[3] = {out->occluded, out->valid, out->bent};
+        int rc = chart_points(r, chart, uv);
+        if (rc) return fail(rc);
+        pt_ao_params q = *p;
+        q.n = n; q.first_index = 0; q.flags = 0;
+        pt_ao_buffers db = {out->occluded ? (uint32_t*)r->d_ao[2] : nullptr, out->valid ? (uint8_t*)r->d_ao[3] : nullptr, out->bent ? (double*)r->d_ao[4] : nullptr};
+        rc = pt_ao_device(c, &q, (const double*)r->d_ao[0], (const double*)r->d_ao[1], &db, nullptr);  // the same (default) stream: behind the chart pass
+        if (rc) { const int shown = fail(rc); pt_aov_finish(c, nullptr); return shown; }
+        const int rc_chart = pt_aov_finish(c, nullptr);
+        if (rc_chart) g_error = pt_last_error(c);
+        rc = pt_ao_finish(c, kernel_ms);
+        if (rc_chart) return PH_ERR_RUNTIME;
+        if (rc) return fail(rc);
+        for (int k = 0; k < 3; k++)
+            if (host_out[k] && (rc = pt_copy_from_device(c, host_out[k], r->d_ao[2 + k], bytes[2 + k]))) return fail(rc);
+        return PH_OK;
+    });
+}
+
+// Gathered radiance at every texel of a mesh's light map: ph_renderer_ao_chart with pt_gather_device behind the chart pass (the sums where that keeps its bent
+// normals, the flags where it keeps its own).
+extern "C" int ph_renderer_gather_chart(ph_renderer* r, const pt_chart_params* chart, const double* uv, const pt_gather_params* p, const double* background,
+                                        const pt_gather_buffers* out, double* kernel_ms) {
+    if (!r || !chart || !p || !background || !out) return bad("null argument");
+    if (chart->width == 0 || chart->height == 0) return bad("width and height must be positive");
+    if ((uint64_t)chart->width * chart->height > PT_AO_MAX) return bad("more than PT_AO_MAX texels");
+    if (!(out->sum || out->valid)) return bad("no output buffer asked for");
+    return guarded([&]() -> int {
+        pt_context* c = r->r->context();
+        auto fail = [&](int rc) { g_error = pt_last_error(c); return rc == PT_ERR_ARGUMENT ? PH_ERR_ARGUMENT : PH_ERR_RUNTIME; };
+        const uint64_t n = (uint64_t)chart->width * chart->height;
+        int rc = chart_points(r, chart, uv);
+        if (rc) return fail(rc);
+        pt_gather_params q = *p;
+        q.n = n; q.first_index = 0; q.flags = 0;
+        pt_gather_buffers db = {out->sum ? (double*)r->d_ao[4] : nullptr, out->valid ? (uint8_t*)r->d_ao[3] : nullptr};
+        rc = pt_gather_device(c, &q, (const double*)r->d_ao[0], (const double*)r->d_ao[1], background, &db, nullptr);  // the same (default) stream: behind the chart pass
+        if (rc) { const int shown = fail(rc); pt_aov_finish(c, nullptr); return shown; }
+        const int rc_chart = pt_aov_finish(c, nullptr);
+        if (rc_chart) g_error = pt_last_error(c);
+        rc = pt_gather_finish(c, kernel_ms);
+        if (rc_chart) return PH_ERR_RUNTIME;
+        if (rc) return fail(rc);
+        if (out->sum && (rc = pt_copy_from_device(c, out->sum, r->d_ao[4], n * 24))) return fail(rc);
+        if (out->valid && (rc = pt_copy_from_device(c, out->valid, r->d_ao[3], n))) return fail(rc);
         return PH_OK;
     });
 }

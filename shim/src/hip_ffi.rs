@@ -125,6 +125,13 @@ pub struct PtGatherParams {                // pt_gather_params: pt_ao_params wit
 pub struct PtGatherBuffers {               // pt_gather_buffers: each optional (null = not wanted), n entries; sum n x 3 = a point's shaded samples added in order
     pub sum: *mut f64, pub valid: *mut u8,
 }
+#[repr(C)]
+pub struct PtChartParams { pub node: u32, pub width: u32, pub height: u32, pub flags: u32 }   // pt_chart_params: a flattened mesh node, its light map's size, 0 or PT_CHART_FLIP_NORMAL
+#[repr(C)]
+pub struct PtChartBuffers {                // pt_chart_buffers: each optional (null = not wanted), width x height entries, row-major; tri = the owning triangle or -1
+    pub position: *mut f64, pub normal: *mut f64, pub tri: *mut i32, pub covered: *mut u8,
+}
+pub const PT_CHART_FLIP_NORMAL: u32 = 1;   // PtChartParams.flags: negate every normal (the inside of a room)
 #[repr(C)] pub struct PtRaysParams { pub n: u64, pub any_hit: i32, pub reorder: i32 }   // pt_rays_params: any_hit 1 = occlusion query, reorder 1 = the device groups like rays first
 #[repr(C)]
 pub struct PtRadianceParams {              // pt_radiance_params: ray i draws from the generator's stream (seed, stream_base + i, sample), draws 2, 3, ...
@@ -226,6 +233,14 @@ extern "C" {
     pub fn pt_gather_device(ctx: *mut PtContext, params: *const PtGatherParams, d_positions: *const f64, d_normals: *const f64, background: *const f64,
                             device_out: *const PtGatherBuffers, hip_stream: *mut c_void) -> c_int;
     pub fn pt_gather_finish(ctx: *mut PtContext, kernel_ms: *mut f64) -> c_int;
+    // a mesh's light-map texels as surface points (position and normal in world space: what pt_ao and pt_gather take), made on the device from the resident
+    // triangle records and matrices by a contract that is checked in every bit (pt_chart.h). uv: T x 6 f64 per triangle corner, T = pt_chart_triangles; null =
+    // the mesh's own texture coordinates where a textured scene keeps them. Runs on pt_aov's pass: pt_chart_device is closed by pt_aov_finish, and behind it
+    // on the same stream pt_ao_device / pt_gather_device read position and normal where they are
+    pub fn pt_chart_triangles(ctx: *mut PtContext, node: u32, n_tris: *mut u64) -> c_int;
+    pub fn pt_chart(ctx: *mut PtContext, params: *const PtChartParams, uv: *const f64, host_out: *const PtChartBuffers, kernel_ms: *mut f64) -> c_int;
+    pub fn pt_chart_device(ctx: *mut PtContext, params: *const PtChartParams, d_uv: *const f64, device_out: *const PtChartBuffers,
+                           hip_stream: *mut c_void) -> c_int;
     // a film: samples accumulate in device memory, add after add; pt_film_add_device is closed by pt_radiance_finish
     pub fn pt_film_create(ctx: *mut PtContext, width: u32, height: u32, out: *mut *mut PtFilm) -> c_int;
     pub fn pt_film_destroy(ctx: *mut PtContext, film: *mut PtFilm) -> c_int;
