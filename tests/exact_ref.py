@@ -354,7 +354,7 @@ def hit_triangle(tr, va, vb, vc, normals, o, dr, lo, hi):
     else:
         n = _cross(_sub(vb, va), _sub(vc, va))
         part = TRI_FLAT
-    return t, _at(o, dr, t), n, 0, part
+    return t, _at(o, dr, t), n, 0, part, (beta, gamma)   # beta and gamma: what triangle.rs:82-138 interpolates texture coordinates with
 
 
 class _Geometry:
@@ -411,7 +411,7 @@ class _Geometry:
         for idx, (ia, ib, ic) in enumerate(tris):
             h = hit_triangle(tr, pos[ia], pos[ib], pos[ic], None if nrm is None else (nrm[ia], nrm[ib], nrm[ic]), o, d, lo, hi)
             if h is not None:
-                found, hi = (h[0], h[1], h[2], idx, h[4]), h[0]
+                found, hi = (h[0], h[1], h[2], idx, h[4], h[5]), h[0]
         return found
 
 
@@ -431,7 +431,7 @@ class _Node:
 
 
 class Hit:
-    __slots__ = ("t", "node", "sub", "part", "point", "normal", "model_point", "kind", "margin", "q1")
+    __slots__ = ("t", "node", "sub", "part", "point", "normal", "model_point", "kind", "margin", "q1", "bary")   # bary: a triangle's (beta, gamma), else None
 
     def __repr__(self):
         return "Hit(t=%s node=%d sub=%d part=%d margin=%g q1=%s)" % (mp.nstr(self.t, 17), self.node, self.sub, self.part, self.margin, self.q1)
@@ -506,7 +506,7 @@ class ExactScene:
             h = node.geometry.hit(tr, lo_, ld, lo, hi, alt)
             if h is not None:
                 hi = h[0]
-                best = (h[0], i, h[3], h[4], _point(t, h[1]), _normal(inv, h[2]), h[1], node.geometry.kind)
+                best = (h[0], i, h[3], h[4], _point(t, h[1]), _normal(inv, h[2]), h[1], node.geometry.kind, h[5] if len(h) > 5 else None)
         return best
 
     # kdtree/node.rs:66-203 over a given tree (the arrays of oracle_lib.kd_scene_dump: the BUILD of the tree is not restated here, its walk is)
@@ -523,7 +523,7 @@ class ExactScene:
                 h = self.flat[i].geometry.hit(tr, _point(inv, o), _direction(inv, d), lo, hi, alt)
                 if h is not None:
                     hi = h[0]
-                    best = (h[0], i, h[3], h[4], _point(tm, h[1]), _normal(inv, h[2]), h[1], self.flat[i].geometry.kind)
+                    best = (h[0], i, h[3], h[4], _point(tm, h[1]), _normal(inv, h[2]), h[1], self.flat[i].geometry.kind, h[5] if len(h) > 5 else None)
             return best
         axis, plane = t["axis"][me], mpf(t["plane"][me])
         t_max = lo + extent
@@ -554,12 +554,12 @@ class ExactScene:
             h = node.geometry.hit(tr, lo_, ld, lo, hi, alt)
             if h is not None:
                 hi = h[0]
-                best = (h[0], node.flat_id, h[3], h[4], _point(t, h[1]), _normal(inv, h[2]), h[1], node.geometry.kind)
+                best = (h[0], node.flat_id, h[3], h[4], _point(t, h[1]), _normal(inv, h[2]), h[1], node.geometry.kind, h[5] if len(h) > 5 else None)
         for c in node.children:
             h = self._cast_hier(tr, c, lo_, ld, lo, hi, alt)
             if h is not None:
                 hi = h[0]
-                best = (h[0], h[1], h[2], h[3], _point(t, h[4]), _normal(inv, h[5]), h[6], h[7])
+                best = (h[0], h[1], h[2], h[3], _point(t, h[4]), _normal(inv, h[5]), h[6], h[7], h[8])
         return best
 
     def cast(self, origin, direction, t_max=math.inf, mode="flat", prec=PREC, alt=False):
@@ -589,7 +589,7 @@ class ExactScene:
             if best is None:
                 return Miss(tr.margin, tr.q1)
             h = Hit()
-            h.t, h.node, h.sub, h.part, h.point, n, h.model_point, h.kind = best
+            h.t, h.node, h.sub, h.part, h.point, n, h.model_point, h.kind, h.bary = best
             s = _dot(n, n)
             if s == 0 or s != s:
                 tr.margin = 0.0

@@ -394,6 +394,7 @@ def batch_tangent(rng, m, trans, prims):
 # ---------------------------------------------------------------- evaluation
 _EX = None
 _RAYS = None
+EXTRA = None   # a generator built on this one (tools/gen_exact_textures.py) sets it: further entries of a ray's row, from its flat 256-bit evaluation
 try:
     from mpmath import mp
 except ImportError:   # the tests' numpy-only half
@@ -444,6 +445,8 @@ def _evaluate(k):
     r.update(hit=f.node >= 0, rgb=f.rgb(), margin=f.margin, node=f.node, branch=f.branch, casts=f.casts, deepest=f.deepest, depth11=f.depth11, events=f.events,
              shadow=[f.shadowed & mask, f.shadowed_beyond & mask, f.lit_front & mask, f.lit_back & mask],
              any_shadow=[f.shadowed & ~f.shadowed_beyond != 0, f.shadowed_beyond != 0, f.lit_front != 0, f.lit_back != 0])
+    if EXTRA is not None:
+        r.update(EXTRA(f))
     r["dev"] = _dev(_run(ex, k, o, d53, bg, "flat", 53), f)
     kd = _run(ex, k, o, d, bg, "kd", exact_shade.PREC)
     hier = _run(ex, k, o, d, bg, "hier", exact_shade.PREC)
