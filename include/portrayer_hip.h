@@ -566,6 +566,73 @@ int pt_gather_device(pt_context *ctx, const pt_gather_params *params, const doub
                      const pt_gather_buffers *device_out, void *hip_stream);
 int pt_gather_finish(pt_context *ctx, double *kernel_ms);
 
+/* ---- Direct light: the light that reaches a point straight from the scene's LIGHTS, the term pt_gather cannot give (its rays sample the hemisphere by cosine and
+ * never meet a point light or a small area light). POINTS in - n positions and n normals, n x 3 f64 in world space, what pt_aov writes per pixel or pt_chart per
+ * texel - and the device makes each point's shadow rays at the resident scene's L lights (15 doubles each: position, colour, falloff c0 c1 c2, area a, area b; kept
+ * current by pt_scene_update) in registers, walks them as occlusion queries and sums what arrives. No ray and no term is ever in memory: 48 bytes per point in, at
+ * most 29 out.
+ * The result is a CONTRACT, a fixed sequence of correctly rounded f64 operations (+, -, *, /, sqrt, fmax; no fused multiply-add; portrayer_amd/csrc/pt_direct.h
+ * states it; pt_test_direct_host replays it on the host). Point i has the stream index q = first_index + i, S = samples, and in this order:
+ *   1. valid      pt_ao's step 1: all six components finite and at most 1e18 in magnitude and the normal not (0, 0, 0). An INVALID point traces nothing, occupies
+ *                 no lane of a walk and reports sum = (0, 0, 0), lit = 0, valid = 0 - so pt_aov's miss pixels and pt_chart's unowned texels are invalid points.
+ *   2. face eye   with PT_AO_FACE_EYE, as pt_ao's step 2: v = P - eye per component; if dot(N, v) > 0 then N = -N. (dot: (x x' + y y') + z z', as everywhere.)
+ *   3. normalise  nrm = N / sqrt(dot(N, N)), a component-wise division, as pt_ao's step 3.
+ *   4. origin     o = P + nrm bias.
+ *   5. light      light li is a POINT light iff a == (0, 0, 0) or b == (0, 0, 0) (light.rs:51-53): lpos = position for every k. Else lpos = position + (a ca + b cb)
+ *                 with ca = 2 rng(seed, q S + k, pass, draw 2 j) - 1 and cb = 2 rng(seed, q S + k, pass, draw 2 j + 1) - 1, the render's counter-based generator;
+ *                 j = the number of area lights with an index below li (the render's rule: an area light consumes two draws, a point light none). q S + k is a
+ *                 64-bit product and sum, reduced modulo 2^64 only.
+ *   6. shadow ray v = lpos - o; dist = sqrt(dot(v, v)); d = v / dist; t_max = +inf: the render's shadow ray (material.rs:149-179), which anything along the ray
+ *                 shadows, also behind the light. With PT_DIRECT_TO_LIGHT t_max = dist: the segment ends at the light - what a baker wants.
+ *   7. cosine     c = fmax(dot(nrm, d), 0). A sample with c == 0 or c NaN (a light at the point) contributes nothing and casts no ray.
+ *   8. occlusion  otherwise occ = what pt_segments with any_hit = 1 answers for (o, d, t_max) in the scene's traversal - that definition taken over whole, with its
+ *                 exceptions for the k-d semantics, KDMesh trees and mesh boxes. A ray that pass would not trace (a component of o beyond 1e18 - a huge bias can do
+ *                 that - or t_max <= EPSILON) contributes nothing.
+ *   9. term       att = (c0 + c1 dist) + (c2 dist) dist (light.rs:31-33); term = (colour c) / att per channel. No material enters: the result is incident light
+ *                 weighted by the cosine, and a caller multiplies by the albedo pt_guides gives.
+ *  10. sum        starting from (0, 0, 0) and lit = 0, for li ascending and inside that k = 0 .. S - 1 ascending: where the sample contributes and occ == 0,
+ *                 sum += term (per channel, left to right) and lit += 1. A point light's sample is the same for every k: it is traced ONCE and added S times, so
+ *                 that sum / S is the estimate whatever mix of lights a scene has. In a scene of point lights only, S = 1 is what to ask for.
+ * Outputs per point, each OPTIONAL (NULL = not wanted), at least one:
+ *   sum    n x 3  f64  step 10
+ *   lit    n      u32  step 10: at most L x S
+ *   valid  n      u8   step 1
+ * A scene without lights gives zeros and step 1's valid, and walks nothing.
+ * Consequences: the bits do not depend on how a batch is cut - a slice [k, k + m) submitted with first_index + k equals that slice of the whole - nor on the work
+ * layout, nor on which rays share a wavefront; and the pass equals pt_test_direct_host's terms, added in step 10's order where pt_segments (any_hit = 1) on that
+ * hook's rays reports no occluder.
+ * The pass IS a ray-query pass, as pt_ao is: it shares pt_rays' work buffers and its one pass in flight - pt_direct_device is closed by pt_direct_finish, which is
+ * pt_rays_finish, and while a pt_rays_device / pt_segments_device / pt_ao_device / pt_direct_device pass is open a second one of any kind is PT_ERR_ARGUMENT.
+ * Errors, before the first HIP call: PT_ERR_ARGUMENT (a NULL context / params / positions / normals / buffers; no buffer asked for; n > PT_AO_MAX; samples not a
+ * power of two <= 64; bias negative or not finite; flags other than PT_AO_FACE_EYE | PT_DIRECT_TO_LIGHT; PT_AO_FACE_EYE with a non-finite eye), PT_ERR_NO_SCENE.
+ * n = 0 is PT_OK: nothing is launched or written. During the pass: PT_ERR_TRAVERSAL as for a render. */
+#define PT_DIRECT_TO_LIGHT 2u             /* pt_direct_params.flags: the shadow segment ends at the light (step 6) */
+typedef struct {
+    uint64_t n;             /* points, <= PT_AO_MAX                                          */
+    uint32_t samples;       /* samples per area light: 1, 2, 4, 8, 16, 32 or 64              */
+    uint32_t pass;          /* the `sample` of the points' streams                           */
+    uint64_t seed;
+    uint64_t first_index;   /* stream index of point 0                                       */
+    double bias;            /* finite, >= 0: the origin is lifted by bias along the normal   */
+    uint32_t flags;         /* any of PT_AO_FACE_EYE | PT_DIRECT_TO_LIGHT                    */
+    double eye[3];          /* read with PT_AO_FACE_EYE only                                 */
+} pt_direct_params;
+typedef struct { double *sum; uint32_t *lit; uint8_t *valid; } pt_direct_buffers;
+/* Host buffers, synchronous: uploads the points, copies back the buffers asked for. kernel_ms (optional): device time of the pass (HIP events). */
+int pt_direct(pt_context *ctx, const pt_direct_params *params, const double *positions, const double *normals, const pt_direct_buffers *host_out, double *kernel_ms);
+/* The same with points and results in DEVICE memory, queued on `hip_stream` (a hipStream_t, or NULL for the default stream) without synchronising the host -
+ * behind a pt_aov_device or pt_chart_device on the same stream it reads that pass's position and normal, and nothing per point crosses the bus but the results.
+ * After the checks above it holds every caller pointer to pt_check_device_pointer's rule - device memory of the context's device, and long enough - before
+ * anything is queued (PT_ERR_ARGUMENT). */
+int pt_direct_device(pt_context *ctx, const pt_direct_params *params, const double *d_positions, const double *d_normals, const pt_direct_buffers *device_out, void *hip_stream);
+int pt_direct_finish(pt_context *ctx, double *kernel_ms);
+/* Test hook, no context and no GPU: steps 1 to 7 and 9 (and step 8's rule for which rays are traced) on the host, by the functions the kernel compiles, against
+ * `lights` (n_lights x 15). origins n x 3; directions and terms n x n_lights x S x 3; t_max n x n_lights x S; valid n. A sample that casts no ray - an invalid
+ * point, c == 0 or NaN, a ray pt_segments would not trace - has direction (0, 0, 0), t_max 0 and term (0, 0, 0): pt_segments does not trace such a ray either, so
+ * the arrays can be handed to it as they are. Checks params as pt_direct does (PT_ERR_ARGUMENT). */
+int pt_test_direct_host(uint64_t n, const pt_direct_params *params, const double *positions, const double *normals, uint32_t n_lights, const double *lights,
+                        double *origins, double *directions, double *t_max, double *terms, uint8_t *valid);
+
 /* ---- Chart: the texels of a mesh's light map as SURFACE POINTS - what pt_ao and pt_gather take (a position and a normal, 48 bytes), made on the device from
  * what is resident there: the triangle records (kept current by pt_scene_deform and pt_scene_deform_device), the node's composed matrices (kept current by
  * pt_scene_update) and a UV set. It does for surfaces what pt_aov does for cameras: behind pt_chart_device on the same stream pt_ao_device / pt_gather_device

@@ -198,6 +198,20 @@ int ph_renderer_ao_chart(ph_renderer *r, const pt_chart_params *chart, const dou
 int ph_renderer_gather_chart(ph_renderer *r, const pt_chart_params *chart, const double *uv, const pt_gather_params *params, const double *background,
                              const pt_gather_buffers *out, double *kernel_ms);
 
+/* Direct light at points of the caller's own (see pt_direct): n x 3 f64 positions and normals in world space, host buffers out, each optional: per point the
+ * sum of the cosine-weighted light that arrives unoccluded from the scene's lights, `samples` samples per area light. A renderer spread over a node runs the
+ * pass on rank 0's context. n = 0 is PH_OK. */
+int ph_renderer_direct(ph_renderer *r, const pt_direct_params *params, const double *positions, const double *normals, const pt_direct_buffers *out, double *kernel_ms);
+/* Direct light under every pixel of a width x height image and at every texel of a mesh's light map, built like ph_renderer_ao_camera / ph_renderer_ao_chart and
+ * on their device scratch: pt_aov_device / pt_chart_device writes position and normal into device memory kept with the renderer, and pt_direct_device reads them
+ * there on the same stream; point q = y * width + x. Of `params` samples, pass, seed, bias and the flag PT_DIRECT_TO_LIGHT are read (n and first_index = 0 are
+ * set here; the camera form runs with PT_AO_FACE_EYE and the camera's eye, the chart form without). Host buffers out, width x height entries each, each
+ * optional: nothing per point crosses the bus but the results. kernel_ms: the direct-light pass's. */
+int ph_renderer_direct_camera(ph_renderer *r, const double camera[10], uint32_t width, uint32_t height, const pt_direct_params *params, const pt_direct_buffers *out,
+                              double *kernel_ms);
+int ph_renderer_direct_chart(ph_renderer *r, const pt_chart_params *chart, const double *uv, const pt_direct_params *params, const pt_direct_buffers *out,
+                             double *kernel_ms);
+
 /* Radiance along rays of the caller's own (see pt_radiance): n x 3 f64 origins and directions in world space, `background` 3 doubles or n x 3
  * (params->background_per_ray), rgb n x 3 f64 out: one linear sample of Ray::color per ray. A renderer spread over a node runs the pass on rank 0's context. */
 int ph_renderer_radiance(ph_renderer *r, const pt_radiance_params *params, const double *origins, const double *directions, const double *background, double *rgb,

@@ -163,6 +163,23 @@ class PtGatherBuffers(C.Structure):
 GATHER_BUFFERS = {"sum": (np.float64, 3), "valid": (np.uint8, 1)}
 
 
+class PtDirectParams(C.Structure):
+    """pt_direct_params: the points of one direct-light call and what fixes their shadow rays - samples per area light, pass, seed, first_index, bias, and the
+    flags AO_FACE_EYE (with the eye every normal is first turned towards) and DIRECT_TO_LIGHT. pt_ao_params without the radius."""
+    _fields_ = [("n", C.c_uint64), ("samples", C.c_uint32), ("pass_index", C.c_uint32), ("seed", C.c_uint64), ("first_index", C.c_uint64), ("bias", C.c_double),
+                ("flags", C.c_uint32), ("eye", C.c_double * 3)]
+
+
+class PtDirectBuffers(C.Structure):
+    """pt_direct_buffers: sum (n, 3) f64, lit (n,) u32, valid (n,) u8; each optional."""
+    _fields_ = [("sum", _dp), ("lit", _up), ("valid", _u8p)]
+
+
+# pt_direct's outputs in the order of pt_direct_buffers: name -> (numpy dtype, components per point)
+DIRECT_BUFFERS = {"sum": (np.float64, 3), "lit": (np.uint32, 1), "valid": (np.uint8, 1)}
+DIRECT_TO_LIGHT = 2  # PT_DIRECT_TO_LIGHT
+
+
 class PtChartParams(C.Structure):
     """pt_chart_params: the flattened mesh node whose light map is charted, the map's size, CHART_FLIP_NORMAL or 0."""
     _fields_ = [("node", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32), ("flags", C.c_uint32)]
@@ -244,7 +261,8 @@ EXPORTS = ["pt_abi_version", "pt_device_count", "pt_context_create", "pt_context
            "pt_guides", "pt_guides_device", "pt_guides_finish", "pt_film_denoise_albedo", "pt_film_denoise_albedo_device", "pt_test_denoise_albedo_host",
            "pt_ao", "pt_ao_device", "pt_ao_finish", "pt_test_ao_rays_host", "pt_test_ao_tables",
            "pt_gather", "pt_gather_device", "pt_gather_finish", "pt_test_kernel_choice",
-           "pt_chart_triangles", "pt_chart", "pt_chart_device", "pt_test_chart_host"]
+           "pt_chart_triangles", "pt_chart", "pt_chart_device", "pt_test_chart_host",
+           "pt_direct", "pt_direct_device", "pt_direct_finish", "pt_test_direct_host"]
 
 
 def header_functions():
@@ -417,6 +435,14 @@ def lib() -> C.CDLL:
         l.pt_gather_device.argtypes = [C.c_void_p, C.POINTER(PtGatherParams), C.c_void_p, C.c_void_p, _dp, C.POINTER(PtGatherBuffers), C.c_void_p]
         l.pt_gather_finish.restype = C.c_int
         l.pt_gather_finish.argtypes = [C.c_void_p, _dp]
+        l.pt_direct.restype = C.c_int
+        l.pt_direct.argtypes = [C.c_void_p, C.POINTER(PtDirectParams), _dp, _dp, C.POINTER(PtDirectBuffers), _dp]
+        l.pt_direct_device.restype = C.c_int
+        l.pt_direct_device.argtypes = [C.c_void_p, C.POINTER(PtDirectParams), C.c_void_p, C.c_void_p, C.POINTER(PtDirectBuffers), C.c_void_p]
+        l.pt_direct_finish.restype = C.c_int
+        l.pt_direct_finish.argtypes = [C.c_void_p, _dp]
+        l.pt_test_direct_host.restype = C.c_int
+        l.pt_test_direct_host.argtypes = [C.c_uint64, C.POINTER(PtDirectParams), _dp, _dp, C.c_uint32, _dp, _dp, _dp, _dp, _dp, _u8p]
         l.pt_chart_triangles.restype = C.c_int
         l.pt_chart_triangles.argtypes = [C.c_void_p, C.c_uint32, _u64p]
         l.pt_chart.restype = C.c_int

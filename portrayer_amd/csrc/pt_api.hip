@@ -11,6 +11,7 @@
 #include "pt_rays_inst.h"
 #include "pt_segments_inst.h"
 #include "pt_ao_inst.h"
+#include "pt_direct_inst.h"
 #include "pt_radiance_inst.h"
 #include "pt_gather_inst.h"
 #include "pt_film_inst.h"
@@ -1735,6 +1736,142 @@ extern "C" int pt_test_ao_tables(double* dirs, double* rot) {
     if (!dirs || !rot) return PT_ERR_ARGUMENT;
     memcpy(dirs, PT_AO_DIRS, sizeof PT_AO_DIRS);
     memcpy(rot, PT_AO_ROT, sizeof PT_AO_ROT);
+    return PT_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Direct light (pt_direct.h: the contract; pt_direct_inst.hip: the kernel): a ray-query pass, on that pass's PtPass, as pt_ao is
+// ------------------------------------------------------------------------------------------------
+static hipError_t pt_direct_dispatch(const PtDirectArgs& a, int n_cu, hipStream_t stream, uint32_t* grid, bool launch) {
+    PT_MODE_LAUNCH(pt_direct_launch_mode_, a.r.scene.mode, a, n_cu, stream, grid, launch)
+}
+
+// What pt_direct refuses of a parameter block, in the order the header gives; null: nothing. (Also pt_test_direct_host's check.)
+static const char* pt_direct_params_error(const pt_direct_params* p) {
+    if (p->n > PT_AO_MAX) return "pt_direct: more than PT_AO_MAX points in one call";
+    if (p->samples == 0 || p->samples > 64 || (p->samples & (p->samples - 1)) != 0) return "pt_direct: samples must be a power of two, 1 .. 64";
+    if (!std::isfinite(p->bias) || p->bias < 0.0) return "pt_direct: bias must be finite and not negative";
+    if (p->flags & ~(PT_AO_FACE_EYE | PT_DIRECT_TO_LIGHT)) return "pt_direct: unknown flags";
+    if ((p->flags & PT_AO_FACE_EYE) && !(std::isfinite(p->eye[0]) && std::isfinite(p->eye[1]) && std::isfinite(p->eye[2]))) return "pt_direct: PT_AO_FACE_EYE needs a finite eye";
+    return nullptr;
+}
+
+static_assert(PT_DIRECT_FLAG_FACE_EYE == PT_AO_FACE_EYE && PT_DIRECT_FLAG_TO_LIGHT == PT_DIRECT_TO_LIGHT, "pt_direct.h restates the header's flags");
+
+static PtDirectSet pt_direct_set(const pt_direct_params* p) {
+    PtDirectSet s;
+    s.seed = p->seed; s.first_index = p->first_index; s.pass = p->pass; s.flags = p->flags; s.samples = p->samples; s.bias = p->bias;
+    s.eye = (p->flags & PT_AO_FACE_EYE) ? pt_v3(p->eye[0], p->eye[1], p->eye[2]) : pt_v3(0.0, 0.0, 0.0);
+    return s;
+}
+
+// Everything that can be refused without a HIP call, in the order the header gives. (pt_fail takes a NULL context.)
+static int pt_direct_check(pt_context* c, const pt_direct_params* p, const double* positions, const double* normals, const pt_direct_buffers* out) {
+    if (!c || !p || !positions || !normals || !out) return pt_fail(c, PT_ERR_ARGUMENT, "pt_direct: NULL context, params, positions, normals or buffers");
+    if (!(out->sum || out->lit || out->valid)) return pt_fail(c, PT_ERR_ARGUMENT, "pt_direct: no output buffer asked for");
+    if (const char* why = pt_direct_params_error(p)) return pt_fail(c, PT_ERR_ARGUMENT, why);
+    if (!c->have_scene) return pt_fail(c, PT_ERR_NO_SCENE, "no scene uploaded");
+    // (the ray queries' words, whichever of the four kinds is open: the pass object is theirs, and pt_rays_finish closes all of them)
+    if (c->rays.pass.pending) return pt_fail(c, PT_ERR_ARGUMENT, "a pt_rays_device / pt_segments_device pass is in flight: pt_rays_finish first");
+    return PT_OK;
+}
+
+// Queues the pass on `stream` (pt_pass_open ... pt_pass_seal), as pt_ao_common does and on its PtPass. Every pointer is a DEVICE pointer; n > 0. The LDS stack
+// area is sized as for the ray queries, less the wavefronts' columns of terms and sums.
+static int pt_direct_common(pt_context* c, const pt_direct_params* p, const double* d_positions, const double* d_normals, const pt_direct_buffers& out, hipStream_t stream) {
+    PtPass& v = c->rays.pass;
+    int rc = pt_pass_prepare(c, v);
+    if (rc) return rc;
+    PtDirectArgs a;
+    memset(&a, 0, sizeof a);
+    a.r.scene = c->view;
+    a.n = p->n; a.positions = d_positions; a.normals = d_normals;
+    a.set = pt_direct_set(p);
+    a.sum = out.sum; a.lit = out.lit; a.valid = out.valid;
+    a.r.n_items = (uint32_t)((p->n + 63u) / 64u);  // (n <= PT_AO_MAX = 2^24)
+    a.r.stack_lds_cap = pt_stack_lds_cap(a.r.scene, pt_direct_waves(a.r.scene.mode) == 3 ? 52 * 1024 : 39 * 1024, pt_direct_frame_bytes());  // (pt_walk_sizing's budgets)
+    a.r.grid_share = 1;
+    uint32_t grid = 0;
+    PT_HIP(c, pt_direct_dispatch(a, c->n_cu, stream, &grid, false));
+    if ((rc = pt_pass_open(c, v, a.r, grid, false, stream))) return rc;
+    PT_HIP(c, pt_direct_dispatch(a, c->n_cu, stream, &grid, true));
+    return pt_pass_seal(c, v);
+}
+
+extern "C" int pt_direct(pt_context* c, const pt_direct_params* p, const double* positions, const double* normals, const pt_direct_buffers* host_out, double* kernel_ms) {
+    int rc = pt_direct_check(c, p, positions, normals, host_out);
+    if (rc) return rc;
+    if (kernel_ms) *kernel_ms = 0.0;
+    if (p->n == 0) return PT_OK;
+    PT_HIP(c, hipSetDevice(c->device));
+    const size_t n = (size_t)p->n;
+    // the ray-query pass's device copies: positions and normals where it keeps origins and directions, the results in three of its output buffers
+    void* host[3] = {host_out->sum, host_out->lit, host_out->valid};
+    PtBuf* buf[3] = {&c->rays.out[1], &c->rays.out[3], &c->rays.out[6]};
+    const size_t elem[3] = {24, 4, 1};  // bytes per point
+    void* dev[3] = {nullptr, nullptr, nullptr};
+    if ((rc = pt_reserve(c, c->rays.in[0], n * 24)) || (rc = pt_reserve(c, c->rays.in[1], n * 24))) return rc;
+    for (int k = 0; k < 3; k++) {
+        if (!host[k]) continue;
+        if ((rc = pt_reserve(c, *buf[k], n * elem[k]))) return rc;
+        dev[k] = buf[k]->p;
+    }
+    PT_HIP(c, hipMemcpy(c->rays.in[0].p, positions, n * 24, hipMemcpyHostToDevice));
+    PT_HIP(c, hipMemcpy(c->rays.in[1].p, normals, n * 24, hipMemcpyHostToDevice));
+    pt_direct_buffers d_out;
+    d_out.sum = (double*)dev[0]; d_out.lit = (uint32_t*)dev[1]; d_out.valid = (uint8_t*)dev[2];
+    rc = pt_direct_common(c, p, (const double*)c->rays.in[0].p, (const double*)c->rays.in[1].p, d_out, nullptr);
+    if ((rc = pt_pass_settle(c, c->rays.pass, rc))) return rc;
+    for (int k = 0; k < 3; k++)
+        if (host[k]) PT_HIP(c, hipMemcpy(host[k], dev[k], n * elem[k], hipMemcpyDeviceToHost));
+    return pt_pass_result(c, c->rays.pass, kernel_ms);
+}
+
+extern "C" int pt_direct_device(pt_context* c, const pt_direct_params* p, const double* d_positions, const double* d_normals, const pt_direct_buffers* device_out, void* hip_stream) {
+    int rc = pt_direct_check(c, p, d_positions, d_normals, device_out);
+    if (rc) return rc;
+    if (p->n == 0) return PT_OK;  // nothing queued, nothing to finish
+    PT_HIP(c, hipSetDevice(c->device));
+    const uint64_t n = p->n;
+    if ((rc = pt_check_device_pointer(c, d_positions, n * 24, "pt_direct_device: d_positions"))) return rc;
+    if ((rc = pt_check_device_pointer(c, d_normals, n * 24, "pt_direct_device: d_normals"))) return rc;
+    if (device_out->sum && (rc = pt_check_device_pointer(c, device_out->sum, n * 24, "pt_direct_device: sum"))) return rc;
+    if (device_out->lit && (rc = pt_check_device_pointer(c, device_out->lit, n * 4, "pt_direct_device: lit"))) return rc;
+    if (device_out->valid && (rc = pt_check_device_pointer(c, device_out->valid, n, "pt_direct_device: valid"))) return rc;
+    return pt_pass_device_tail(c, c->rays.pass, pt_direct_common(c, p, d_positions, d_normals, *device_out, (hipStream_t)hip_stream));
+}
+
+// The pass is the ray queries': one function closes any of them.
+extern "C" int pt_direct_finish(pt_context* c, double* kernel_ms) { return pt_rays_finish(c, kernel_ms); }
+
+// Steps 1 to 7 and 9 of the contract on the host: pt_direct.h's functions as this translation unit's host pass compiles them (-ffp-contract=off).
+extern "C" int pt_test_direct_host(uint64_t n, const pt_direct_params* p, const double* positions, const double* normals, uint32_t n_lights, const double* lights, double* origins,
+                                   double* directions, double* t_max, double* terms, uint8_t* valid) {
+    if (!p || !positions || !normals || (n_lights && !lights) || !origins || !directions || !t_max || !terms || !valid) return PT_ERR_ARGUMENT;
+    if (pt_direct_params_error(p)) return PT_ERR_ARGUMENT;
+    const PtDirectSet set = pt_direct_set(p);
+    const uint64_t S = p->samples;
+    for (uint64_t i = 0; i < n; i++) {
+        const PtVec3 P = pt_v3(positions[3 * i], positions[3 * i + 1], positions[3 * i + 2]), N = pt_v3(normals[3 * i], normals[3 * i + 1], normals[3 * i + 2]);
+        valid[i] = pt_direct_valid(P, N) ? 1 : 0;
+        PtVec3 o = pt_v3(0.0, 0.0, 0.0), nrm = o;
+        if (valid[i]) pt_direct_point(set, P, N, &o, &nrm);
+        origins[3 * i] = o.x; origins[3 * i + 1] = o.y; origins[3 * i + 2] = o.z;
+        uint32_t j = 0;
+        for (uint32_t li = 0; li < n_lights; li++) {
+            const double* light = lights + 15 * (size_t)li;
+            for (uint32_t k = 0; k < p->samples; k++) {
+                PtVec3 d = pt_v3(0.0, 0.0, 0.0), term = d;
+                double tm = 0.0;
+                if (valid[i]) pt_direct_sample(set, o, nrm, pt_direct_light_position(set, light, j, p->first_index + i, k), light, &d, &tm, &term);
+                const uint64_t at = (i * n_lights + li) * S + k;
+                directions[3 * at] = d.x; directions[3 * at + 1] = d.y; directions[3 * at + 2] = d.z;
+                terms[3 * at] = term.x; terms[3 * at + 1] = term.y; terms[3 * at + 2] = term.z;
+                t_max[at] = tm;
+            }
+            if (!pt_direct_is_point_light(light)) j++;
+        }
+    }
     return PT_OK;
 }
 

@@ -19,7 +19,7 @@ _dp, _ip, _up, _u64p, _u8p = H._dp, H._ip, H._up, H._u64p, H._u8p
 
 EXPORTS = ["ph_last_error", "ph_scene_create", "ph_example_scene", "ph_scene_destroy", "ph_scene_counts", "ph_scene_export", "ph_scene_export_textures",
            "ph_scene_flatten", "ph_scene_kdtree", "ph_camera", "ph_obj_load", "ph_renderer_create", "ph_renderer_destroy",
-           "ph_renderer_context", "ph_renderer_ranks", "ph_renderer_node", "ph_renderer_prepare_ms", "ph_renderer_render", "ph_renderer_aov", "ph_renderer_rays", "ph_renderer_segments", "ph_renderer_ao", "ph_renderer_ao_camera", "ph_renderer_gather", "ph_renderer_gather_camera", "ph_renderer_chart_triangles", "ph_renderer_chart_mesh", "ph_renderer_chart", "ph_renderer_ao_chart", "ph_renderer_gather_chart", "ph_renderer_radiance", "ph_renderer_film_create", "ph_renderer_film_destroy", "ph_renderer_film_reset", "ph_renderer_film_add", "ph_renderer_film_resolve", "ph_renderer_film_counts", "ph_renderer_film_create_moments", "ph_renderer_film_add_map", "ph_renderer_film_error", "ph_renderer_film_refine", "ph_renderer_film_denoise", "ph_renderer_guides", "ph_renderer_film_denoise_albedo", "ph_renderer_update", "ph_scene_same_structure", "ph_renderer_deform", "ph_scene_same_topology", "ph_renderer_deform_device", "ph_renderer_mesh_count", "ph_renderer_mesh_vertices", "ph_example_render_to_png", "ph_png_read", "ph_png_write", "ph_image_read", "ph_scene_graph"]
+           "ph_renderer_context", "ph_renderer_ranks", "ph_renderer_node", "ph_renderer_prepare_ms", "ph_renderer_render", "ph_renderer_aov", "ph_renderer_rays", "ph_renderer_segments", "ph_renderer_ao", "ph_renderer_ao_camera", "ph_renderer_gather", "ph_renderer_gather_camera", "ph_renderer_chart_triangles", "ph_renderer_chart_mesh", "ph_renderer_chart", "ph_renderer_ao_chart", "ph_renderer_gather_chart", "ph_renderer_direct", "ph_renderer_direct_camera", "ph_renderer_direct_chart", "ph_renderer_radiance", "ph_renderer_film_create", "ph_renderer_film_destroy", "ph_renderer_film_reset", "ph_renderer_film_add", "ph_renderer_film_resolve", "ph_renderer_film_counts", "ph_renderer_film_create_moments", "ph_renderer_film_add_map", "ph_renderer_film_error", "ph_renderer_film_refine", "ph_renderer_film_denoise", "ph_renderer_guides", "ph_renderer_film_denoise_albedo", "ph_renderer_update", "ph_scene_same_structure", "ph_renderer_deform", "ph_scene_same_topology", "ph_renderer_deform_device", "ph_renderer_mesh_count", "ph_renderer_mesh_vertices", "ph_example_render_to_png", "ph_png_read", "ph_png_write", "ph_image_read", "ph_scene_graph"]
 
 
 class PortrayerHostError(RuntimeError):
@@ -103,6 +103,12 @@ def lib() -> C.CDLL:
         l.ph_renderer_chart_mesh.argtypes = [vp, C.c_uint32, _u64p, C.c_uint32, _up]
         l.ph_renderer_chart.restype = C.c_int
         l.ph_renderer_chart.argtypes = [vp, C.POINTER(H.PtChartParams), _dp, C.POINTER(H.PtChartBuffers), _dp]
+        l.ph_renderer_direct.restype = C.c_int
+        l.ph_renderer_direct.argtypes = [vp, C.POINTER(H.PtDirectParams), _dp, _dp, C.POINTER(H.PtDirectBuffers), _dp]
+        l.ph_renderer_direct_camera.restype = C.c_int
+        l.ph_renderer_direct_camera.argtypes = [vp, _dp, C.c_uint32, C.c_uint32, C.POINTER(H.PtDirectParams), C.POINTER(H.PtDirectBuffers), _dp]
+        l.ph_renderer_direct_chart.restype = C.c_int
+        l.ph_renderer_direct_chart.argtypes = [vp, C.POINTER(H.PtChartParams), _dp, C.POINTER(H.PtDirectParams), C.POINTER(H.PtDirectBuffers), _dp]
         l.ph_renderer_ao_chart.restype = C.c_int
         l.ph_renderer_ao_chart.argtypes = [vp, C.POINTER(H.PtChartParams), _dp, C.POINTER(H.PtAoParams), C.POINTER(H.PtAoBuffers), _dp]
         l.ph_renderer_gather_chart.restype = C.c_int
@@ -1060,6 +1066,96 @@ class Renderer:
         _check(lib().ph_renderer_gather_chart(self._h, C.byref(cp), _p(uv, _dp) if uv is not None else None, C.byref(p), _p(bg, _dp), C.byref(b), C.byref(ms)),
                "ph_renderer_gather_chart")
         return self._gather_result(out, samples, ms)
+
+    @staticmethod
+    def _direct_params(n, samples, bias, seed, pass_index, first_index, eye, to_light):
+        """direct()'s, direct_camera()'s and direct_chart()'s argument checks, and the pt_direct_params they describe"""
+        if not isinstance(to_light, (bool, np.bool_)):
+            raise ValueError("to_light must be a bool, got %r" % (to_light,))
+        a = Renderer._ao_params(n, samples, float("inf"), bias, seed, pass_index, first_index, eye)  # (the same checks; a shadow ray has no radius)
+        return H.PtDirectParams(a.n, a.samples, a.pass_index, a.seed, a.first_index, a.bias, a.flags | (H.DIRECT_TO_LIGHT if to_light else 0), a.eye)
+
+    @staticmethod
+    def _direct_buffers(want, into, shape):
+        want = tuple(want)
+        unknown = [n for n in want if n not in H.DIRECT_BUFFERS]
+        if unknown or not want:
+            raise ValueError("want must name some of %s, got %r" % (", ".join(H.DIRECT_BUFFERS), want))
+        out, b = {}, H.PtDirectBuffers()
+        for name in want:
+            dtype, comps = H.DIRECT_BUFFERS[name]
+            full = shape if comps == 1 else shape + (comps,)
+            a = into[name] if into is not None and name in into else np.zeros(full, dtype=dtype)
+            if not isinstance(a, np.ndarray) or a.shape != full or a.dtype != dtype or not a.flags.c_contiguous:
+                raise ValueError("into[%r] must be a C-contiguous %s array of shape %r" % (name, np.dtype(dtype).name, full))
+            out[name] = a
+            setattr(b, name, _p(a, {np.uint32: _up, np.uint8: _u8p, np.float64: _dp}[dtype]))
+        return out, b
+
+    @staticmethod
+    def _direct_result(out, samples, ms):
+        if "sum" in out:
+            out["mean"] = out["sum"] / float(samples)  # (zeros at invalid points)
+        out["kernel_ms"] = ms.value
+        return out
+
+    def direct(self, points, normals, samples: int = 1, bias: float = 0.0, seed: int = 0, pass_index: int = 0, first_index: int = 0, eye=None,
+               to_light: bool = False, want=("sum",), into: Optional[dict] = None) -> dict:
+        """Direct light at points of the caller's own (pt_direct): `points` and `normals` are (n, 3) float64 in world space - aov()'s or chart()'s position and
+        normal. The device makes each point's shadow rays at the lights RESIDENT on the device (after update(): the new ones) in registers - one at a point
+        light, `samples` (1, 2, 4 .. 64) at an area light, sampled as render() samples it - walks them as occlusion queries and sums per point what arrives:
+        colour x max(cos, 0) / attenuation per light, no material (multiply by guides()'s albedo). The origin is lifted by `bias` along the normal; `eye` (three
+        numbers) first turns every normal towards that point. A shadow ray is render()'s, unbounded: anything along it shadows, also behind the light;
+        to_light=True ends it at the light, which is what a baker wants. Returns the arrays named in `want` - `sum` (n, 3) float64: a point light's term added
+        `samples` times, an area light's samples once each, in order; `lit` (n,) uint32: how many were added; `valid` (n,) uint8 - with `mean` = sum / samples
+        (computed here) where `sum` was asked for, and `kernel_ms`. In a scene of point lights only samples=1 is what to ask for. A point with a non-finite
+        component, one beyond 1e18 or a zero normal is invalid: sum 0, lit 0, valid 0. Point i draws from the streams (seed, (first_index + i) * samples + k,
+        pass_index): a slice [k, k + m) with first_index=k gives that slice of the whole. `into`: a dict of C-contiguous arrays of the right shape and dtype."""
+        P, N = np.asarray(points), np.asarray(normals)
+        if P.ndim != 2 or P.shape[1] != 3 or P.shape != N.shape:
+            raise ValueError("points and normals must both be (n, 3), got %r and %r" % (P.shape, N.shape))
+        if P.dtype != np.float64 or N.dtype != np.float64:
+            raise ValueError("points and normals must be float64, got %s and %s" % (P.dtype, N.dtype))
+        n = P.shape[0]
+        p = self._direct_params(n, samples, bias, seed, pass_index, first_index, eye, to_light)
+        out, b = self._direct_buffers(want, into, (n,))
+        P, N = np.ascontiguousarray(P), np.ascontiguousarray(N)
+        ms = C.c_double(0.0)
+        _check(lib().ph_renderer_direct(self._h, C.byref(p), _p(P, _dp), _p(N, _dp), C.byref(b), C.byref(ms)), "ph_renderer_direct")
+        return self._direct_result(out, samples, ms)
+
+    def direct_camera(self, cam10, width: int, height: int, samples: int = 1, bias: float = 0.0, seed: int = 0, pass_index: int = 0, to_light: bool = False,
+                      want=("sum",), into: Optional[dict] = None) -> dict:
+        """Direct light under every pixel (pt_aov_device then pt_direct_device on the device): the points are what aov() finds at the pixel centres, the normals
+        turned towards the camera's eye, pixel (x, y) the stream index y * width + x - the bits of direct(aov's position, aov's normal, eye=the eye). Nothing
+        per pixel crosses the bus but the results: `sum` and `mean` (H, W, 3), `lit` and `valid` (H, W), as in direct(); pixels that see nothing are invalid
+        points."""
+        for name, v in (("width", width), ("height", height)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or int(v) < 1:
+                raise ValueError("%s must be a positive integer, got %r" % (name, v))
+        p = self._direct_params(int(width) * int(height), samples, bias, seed, pass_index, 0, None, to_light)
+        out, b = self._direct_buffers(want, into, (int(height), int(width)))
+        c = np.ascontiguousarray(cam10, dtype=np.float64)
+        if c.shape != (10,):
+            raise ValueError("cam10 must hold 10 numbers, got shape %r" % (c.shape,))
+        ms = C.c_double(0.0)
+        _check(lib().ph_renderer_direct_camera(self._h, _p(c, _dp), int(width), int(height), C.byref(p), C.byref(b), C.byref(ms)), "ph_renderer_direct_camera")
+        return self._direct_result(out, samples, ms)
+
+    def direct_chart(self, node: int, width: int, height: int, uv=None, samples: int = 1, bias: float = 0.0, seed: int = 0, pass_index: int = 0,
+                     to_light: bool = False, flip_normal: bool = False, want=("sum",), into: Optional[dict] = None) -> dict:
+        """Direct light at every texel of a mesh's light map (pt_chart_device then pt_direct_device on the device): the bits of
+        direct(chart's position, chart's normal, first_index=0, ...), texel (x, y) the stream index y * width + x. `sum` and `mean` (H, W, 3), `lit` and `valid`
+        (H, W), as in direct(); texels no triangle owns are invalid points. `node`, `uv` (numpy, or None) and flip_normal as in chart()."""
+        cp, uv = self._chart_params(node, width, height, uv, flip_normal)
+        if uv is not None and not isinstance(uv, np.ndarray):
+            raise ValueError("direct_chart takes uv as a numpy array or None; chart() takes tensors")
+        p = self._direct_params(int(width) * int(height), samples, bias, seed, pass_index, 0, None, to_light)
+        out, b = self._direct_buffers(want, into, (int(height), int(width)))
+        ms = C.c_double(0.0)
+        _check(lib().ph_renderer_direct_chart(self._h, C.byref(cp), _p(uv, _dp) if uv is not None else None, C.byref(p), C.byref(b), C.byref(ms)),
+               "ph_renderer_direct_chart")
+        return self._direct_result(out, samples, ms)
 
     def radiance(self, origins, directions, background=(0.0, 0.0, 0.0), seed: int = 0, sample: int = 0, stream_base: int = 0, reorder: bool = False,
                  into: Optional[np.ndarray] = None) -> dict:

@@ -885,6 +885,93 @@ extern "C" int ph_renderer_gather_chart(ph_renderer* r, const pt_chart_params* c
     });
 }
 
+// Direct light at points of the caller's own (pt_direct): host buffers in and out.
+extern "C" int ph_renderer_direct(ph_renderer* r, const pt_direct_params* p, const double* positions, const double* normals, const pt_direct_buffers* out, double* kernel_ms) {
+    if (!r || !p || !out) return bad("null argument");
+    if (p->n && (!positions || !normals)) return bad("null argument");
+    if (p->n == 0) { if (kernel_ms) *kernel_ms = 0.0; return PH_OK; }
+    return guarded([&]() -> int {
+        int rc = pt_direct(r->r->context(), p, positions, normals, out, kernel_ms);  // (a renderer spread over a node: rank 0's context, every point)
+        if (rc != PT_OK) { g_error = pt_last_error(r->r->context()); return rc == PT_ERR_ARGUMENT ? PH_ERR_ARGUMENT : PH_ERR_RUNTIME; }
+        return PH_OK;
+    });
+}
+
+// What ph_renderer_direct_camera and ph_renderer_direct_chart share once the points' pass (pt_aov_device or pt_chart_device, left open) has written position and
+// normal into the renderer's device scratch: pt_direct_device behind it on the same (default) stream - the sums where ph_renderer_ao_camera keeps its bent
+// normals, the counts where it keeps its own, the flags likewise - both passes closed, the results asked for copied out.
+static int direct_behind_points(ph_renderer* r, uint64_t n, const pt_direct_params& q, const pt_direct_buffers* out, double* kernel_ms) {
+    pt_context* c = r->r->context();
+    auto fail = [&](int rc) { g_error = pt_last_error(c); return rc == PT_ERR_ARGUMENT ? PH_ERR_ARGUMENT : PH_ERR_RUNTIME; };
+    pt_direct_buffers db = {out->sum ? (double*)r->d_ao[4] : nullptr, out->lit ? (uint32_t*)r->d_ao[2] : nullptr, out->valid ? (uint8_t*)r->d_ao[3] : nullptr};
+    int rc = pt_direct_device(c, &q, (const double*)r->d_ao[0], (const double*)r->d_ao[1], &db, nullptr);
+    if (rc) { const int shown = fail(rc); pt_aov_finish(c, nullptr); return shown; }
+    const int rc_points = pt_aov_finish(c, nullptr);
+    if (rc_points) g_error = pt_last_error(c);
+    rc = pt_direct_finish(c, kernel_ms);
+    if (rc_points) return PH_ERR_RUNTIME;
+    if (rc) return fail(rc);
+    if (out->sum && (rc = pt_copy_from_device(c, out->sum, r->d_ao[4], n * 24))) return fail(rc);
+    if (out->lit && (rc = pt_copy_from_device(c, out->lit, r->d_ao[2], n * 4))) return fail(rc);
+    if (out->valid && (rc = pt_copy_from_device(c, out->valid, r->d_ao[3], n))) return fail(rc);
+    return PH_OK;
+}
+
+// Direct light under every pixel of a width x height image, built like ph_renderer_ao_camera and on its device scratch: pt_aov_device at the pixel centres,
+// pt_direct_device behind it on the same stream with PT_AO_FACE_EYE and the camera's eye - point q = y * width + x, so params->n, eye and first_index are set
+// here, and of its flags PT_DIRECT_TO_LIGHT is kept - and only the results cross the bus.
+extern "C" int ph_renderer_direct_camera(ph_renderer* r, const double camera[10], uint32_t width, uint32_t height, const pt_direct_params* p, const pt_direct_buffers* out,
+                                         double* kernel_ms) {
+    if (!r || !camera || !p || !out) return bad("null argument");
+    if (width == 0 || height == 0) return bad("width and height must be positive");
+    if ((uint64_t)width * height > PT_AO_MAX) return bad("more than PT_AO_MAX pixels");
+    if (!(out->sum || out->lit || out->valid)) return bad("no output buffer asked for");
+    return guarded([&]() -> int {
+        pt_context* c = r->r->context();
+        auto fail = [&](int rc) { g_error = pt_last_error(c); return rc == PT_ERR_ARGUMENT ? PH_ERR_ARGUMENT : PH_ERR_RUNTIME; };
+        const uint64_t n = (uint64_t)width * height;
+        const size_t bytes[5] = {n * 24, n * 24, n * 4, n * 1, n * 24};  // (ph_renderer_ao_camera's five)
+        int rc = PT_OK;
+        if (r->ao_points < n) {
+            r->ao_release();
+            for (int k = 0; k < 5 && rc == PT_OK; k++) rc = pt_device_alloc(c, bytes[k], &r->d_ao[k]);
+            if (rc != PT_OK) { const int shown = fail(rc); r->ao_release(); return shown; }
+            r->ao_points = n;
+        }
+        pt_camera pc = detail::Camera(camera_from(camera), (double)width, (double)height).to_abi();  // the camera a render of this size gets
+        pt_aov_params ap;
+        ap.width = width; ap.height = height;
+        ap.slice.x0 = 0; ap.slice.y0 = 0; ap.slice.x1 = width - 1; ap.slice.y1 = height - 1;
+        ap.offset[0] = 0.5; ap.offset[1] = 0.5;
+        pt_direct_params q = *p;
+        q.n = n; q.first_index = 0; q.flags = PT_AO_FACE_EYE | (p->flags & PT_DIRECT_TO_LIGHT);
+        for (int k = 0; k < 3; k++) q.eye[k] = pc.eye[k];
+        pt_aov_buffers ab = {nullptr, (double*)r->d_ao[0], (double*)r->d_ao[1], nullptr, nullptr, nullptr};
+        if ((rc = pt_aov_device(c, &pc, &ap, &ab, nullptr))) return fail(rc);
+        return direct_behind_points(r, n, q, out, kernel_ms);
+    });
+}
+
+// Direct light at every texel of a mesh's light map, built like ph_renderer_ao_chart: pt_chart_device writes position and normal into the renderer's device
+// scratch, pt_direct_device behind it on the same stream reads them - point q = y * width + x, first_index 0, no PT_AO_FACE_EYE (a chart's normals face outwards
+// or, with PT_CHART_FLIP_NORMAL, inwards) - and only the results cross the bus. Of `params` samples, pass, seed, bias and the flag PT_DIRECT_TO_LIGHT are read.
+extern "C" int ph_renderer_direct_chart(ph_renderer* r, const pt_chart_params* chart, const double* uv, const pt_direct_params* p, const pt_direct_buffers* out,
+                                        double* kernel_ms) {
+    if (!r || !chart || !p || !out) return bad("null argument");
+    if (chart->width == 0 || chart->height == 0) return bad("width and height must be positive");
+    if ((uint64_t)chart->width * chart->height > PT_AO_MAX) return bad("more than PT_AO_MAX texels");
+    if (!(out->sum || out->lit || out->valid)) return bad("no output buffer asked for");
+    return guarded([&]() -> int {
+        pt_context* c = r->r->context();
+        const uint64_t n = (uint64_t)chart->width * chart->height;
+        int rc = chart_points(r, chart, uv);
+        if (rc) { g_error = pt_last_error(c); return rc == PT_ERR_ARGUMENT ? PH_ERR_ARGUMENT : PH_ERR_RUNTIME; }
+        pt_direct_params q = *p;
+        q.n = n; q.first_index = 0; q.flags = p->flags & PT_DIRECT_TO_LIGHT;
+        return direct_behind_points(r, n, q, out, kernel_ms);
+    });
+}
+
 extern "C" int ph_renderer_radiance(ph_renderer* r, const pt_radiance_params* p, const double* origins, const double* directions, const double* background, double* rgb,
                                     double* kernel_ms) {
     if (!r || !p || !background) return bad("null argument");

@@ -126,6 +126,16 @@ pub struct PtGatherBuffers {               // pt_gather_buffers: each optional (
     pub sum: *mut f64, pub valid: *mut u8,
 }
 #[repr(C)]
+pub struct PtDirectParams {                // pt_direct_params: pt_ao_params without the radius; sample k of point i at an area light draws from the stream (seed, (first_index + i) * samples + k, pass)
+    pub n: u64, pub samples: u32, pub pass: u32, pub seed: u64, pub first_index: u64,
+    pub bias: f64, pub flags: u32, pub eye: [f64; 3],
+}
+#[repr(C)]
+pub struct PtDirectBuffers {               // pt_direct_buffers: each optional (null = not wanted), n entries; sum n x 3 = the unoccluded lights' terms added in order, lit = how many
+    pub sum: *mut f64, pub lit: *mut u32, pub valid: *mut u8,
+}
+pub const PT_DIRECT_TO_LIGHT: u32 = 2;     // PtDirectParams.flags (beside PT_AO_FACE_EYE): the shadow segment ends at the light
+#[repr(C)]
 pub struct PtChartParams { pub node: u32, pub width: u32, pub height: u32, pub flags: u32 }   // pt_chart_params: a flattened mesh node, its light map's size, 0 or PT_CHART_FLIP_NORMAL
 #[repr(C)]
 pub struct PtChartBuffers {                // pt_chart_buffers: each optional (null = not wanted), width x height entries, row-major; tri = the owning triangle or -1
@@ -233,6 +243,15 @@ extern "C" {
     pub fn pt_gather_device(ctx: *mut PtContext, params: *const PtGatherParams, d_positions: *const f64, d_normals: *const f64, background: *const f64,
                             device_out: *const PtGatherBuffers, hip_stream: *mut c_void) -> c_int;
     pub fn pt_gather_finish(ctx: *mut PtContext, kernel_ms: *mut f64) -> c_int;
+    // direct light at points of the caller's own: per point the sum of colour x max(cos, 0) / attenuation over the resident scene's lights whose shadow ray
+    // (made in registers, a fixed sequence of f64 operations, pt_direct.h; `samples` per area light) meets nothing. Shares pt_rays' pass as pt_ao does:
+    // pt_direct_device is closed by pt_direct_finish, which is pt_rays_finish; queued behind pt_aov_device / pt_chart_device on the same stream it reads that
+    // pass's position and normal where they are
+    pub fn pt_direct(ctx: *mut PtContext, params: *const PtDirectParams, positions: *const f64, normals: *const f64, host_out: *const PtDirectBuffers,
+                     kernel_ms: *mut f64) -> c_int;
+    pub fn pt_direct_device(ctx: *mut PtContext, params: *const PtDirectParams, d_positions: *const f64, d_normals: *const f64, device_out: *const PtDirectBuffers,
+                            hip_stream: *mut c_void) -> c_int;
+    pub fn pt_direct_finish(ctx: *mut PtContext, kernel_ms: *mut f64) -> c_int;
     // a mesh's light-map texels as surface points (position and normal in world space: what pt_ao and pt_gather take), made on the device from the resident
     // triangle records and matrices by a contract that is checked in every bit (pt_chart.h). uv: T x 6 f64 per triangle corner, T = pt_chart_triangles; null =
     // the mesh's own texture coordinates where a textured scene keeps them. Runs on pt_aov's pass: pt_chart_device is closed by pt_aov_finish, and behind it
