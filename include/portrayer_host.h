@@ -88,6 +88,12 @@ int ph_scene_graph(const ph_scene *scene, uint32_t node_cap, uint32_t chain_cap,
 int ph_scene_kdtree(const ph_scene *scene, int kd_depth, uint32_t node_cap, uint32_t item_cap, int32_t *axis, double *plane,
                     int32_t *front, int32_t *back, int32_t *first, int32_t *count, int32_t *leaf_items, uint32_t *n_items,
                     double root_bounds[6], int32_t *max_depth);
+/* KDMesh::new (kdmesh.rs:37-58) for mesh `mesh` of the scene (meshes are numbered by first use among the flattened nodes, as the
+ * upload numbers them): the tree the upload builds for a KDMesh of that mesh, in the same arrays; items are the mesh's own triangle
+ * indices. kd_mesh_depth < 0: the environment's KD_MESH_DEPTH, else 10. Needs no GPU and uploads nothing. Returns the node count. */
+int ph_scene_kdmesh_tree(const ph_scene *scene, uint32_t mesh, int kd_mesh_depth, uint32_t node_cap, uint32_t item_cap, int32_t *axis, double *plane,
+                         int32_t *front, int32_t *back, int32_t *first, int32_t *count, int32_t *leaf_items, uint32_t *n_items,
+                         double root_bounds[6], int32_t *max_depth);
 /* Camera::new (camera.rs:34-45) */
 int ph_camera(const double camera[10], double width, double height, pt_camera *out);
 /* MeshData::load_obj (mesh.rs:57-61): counts = vertices, triangles, has_normals; then copy out. */

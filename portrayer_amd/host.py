@@ -18,7 +18,7 @@ DEFAULT_ASSETS = os.path.join(REPO_ROOT, "tests", "golden", "assets")
 _dp, _ip, _up, _u64p, _u8p = H._dp, H._ip, H._up, H._u64p, H._u8p
 
 EXPORTS = ["ph_last_error", "ph_scene_create", "ph_example_scene", "ph_scene_destroy", "ph_scene_counts", "ph_scene_export", "ph_scene_export_textures",
-           "ph_scene_flatten", "ph_scene_kdtree", "ph_camera", "ph_obj_load", "ph_renderer_create", "ph_renderer_destroy",
+           "ph_scene_flatten", "ph_scene_kdtree", "ph_scene_kdmesh_tree", "ph_camera", "ph_obj_load", "ph_renderer_create", "ph_renderer_destroy",
            "ph_renderer_context", "ph_renderer_ranks", "ph_renderer_node", "ph_renderer_prepare_ms", "ph_renderer_render", "ph_renderer_aov", "ph_renderer_rays", "ph_renderer_segments", "ph_renderer_ao", "ph_renderer_ao_camera", "ph_renderer_gather", "ph_renderer_gather_camera", "ph_renderer_chart_triangles", "ph_renderer_chart_mesh", "ph_renderer_chart", "ph_renderer_ao_chart", "ph_renderer_gather_chart", "ph_renderer_direct", "ph_renderer_direct_camera", "ph_renderer_direct_chart", "ph_renderer_radiance", "ph_renderer_film_create", "ph_renderer_film_destroy", "ph_renderer_film_reset", "ph_renderer_film_add", "ph_renderer_film_resolve", "ph_renderer_film_counts", "ph_renderer_film_create_moments", "ph_renderer_film_add_map", "ph_renderer_film_error", "ph_renderer_film_refine", "ph_renderer_film_denoise", "ph_renderer_guides", "ph_renderer_film_denoise_albedo", "ph_renderer_update", "ph_scene_same_structure", "ph_renderer_deform", "ph_scene_same_topology", "ph_renderer_deform_device", "ph_renderer_mesh_count", "ph_renderer_mesh_vertices", "ph_example_render_to_png", "ph_png_read", "ph_png_write", "ph_image_read", "ph_scene_graph"]
 
 
@@ -71,6 +71,8 @@ def lib() -> C.CDLL:
         l.ph_scene_flatten.restype = C.c_int; l.ph_scene_flatten.argtypes = [vp, C.c_uint32, _dp, _dp, _dp, _ip, _ip, _dp]
         l.ph_scene_kdtree.restype = C.c_int
         l.ph_scene_kdtree.argtypes = [vp, C.c_int, C.c_uint32, C.c_uint32, _ip, _dp, _ip, _ip, _ip, _ip, _ip, _up, _dp, _ip]
+        l.ph_scene_kdmesh_tree.restype = C.c_int
+        l.ph_scene_kdmesh_tree.argtypes = [vp, C.c_uint32, C.c_int, C.c_uint32, C.c_uint32, _ip, _dp, _ip, _ip, _ip, _ip, _ip, _up, _dp, _ip]
         l.ph_camera.restype = C.c_int; l.ph_camera.argtypes = [_dp, C.c_double, C.c_double, C.POINTER(H.PtCamera)]
         l.ph_obj_load.restype = C.c_int; l.ph_obj_load.argtypes = [C.c_char_p, _u64p, _dp, _dp, _up, C.c_uint64, C.c_uint64]
         l.ph_renderer_create.restype = C.c_int; l.ph_renderer_create.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]
@@ -305,6 +307,17 @@ class Scene:
         n_items = C.c_uint32(0); rb = np.zeros(6); md = C.c_int32(0)
         n = _check(lib().ph_scene_kdtree(self._h, kd_depth, node_cap, item_cap, _p(axis, _ip), _p(plane, _dp), _p(front, _ip), _p(back, _ip),
                                          _p(first, _ip), _p(count, _ip), _p(items, _ip), C.byref(n_items), _p(rb, _dp), C.byref(md)), "ph_scene_kdtree")
+        return dict(axis=axis[:n], plane=plane[:n], front=front[:n], back=back[:n], first=first[:n], count=count[:n],
+                    items=items[:n_items.value], root_bounds=rb, max_depth=md.value)
+
+    def kdmesh_tree(self, mesh: int, kd_mesh_depth: int = -1, node_cap: int = 1 << 16, item_cap: int = 1 << 20) -> dict:
+        """The tree the upload builds for a KDMesh of mesh `mesh` (numbered by first use among the flattened nodes); host logic, no GPU needed."""
+        axis = np.zeros(node_cap, dtype=np.int32); plane = np.zeros(node_cap)
+        front, back, first, count = (np.zeros(node_cap, dtype=np.int32) for _ in range(4))
+        items = np.zeros(item_cap, dtype=np.int32)
+        n_items = C.c_uint32(0); rb = np.zeros(6); md = C.c_int32(0)
+        n = _check(lib().ph_scene_kdmesh_tree(self._h, mesh, kd_mesh_depth, node_cap, item_cap, _p(axis, _ip), _p(plane, _dp), _p(front, _ip), _p(back, _ip),
+                                              _p(first, _ip), _p(count, _ip), _p(items, _ip), C.byref(n_items), _p(rb, _dp), C.byref(md)), "ph_scene_kdmesh_tree")
         return dict(axis=axis[:n], plane=plane[:n], front=front[:n], back=back[:n], first=first[:n], count=count[:n],
                     items=items[:n_items.value], root_bounds=rb, max_depth=md.value)
 

@@ -1,4 +1,5 @@
 // C entry points of the host library (include/portrayer_host.h).
+#include <algorithm>
 #include <cstring>
 #include <map>
 #include <string>
@@ -443,6 +444,28 @@ extern "C" int ph_scene_graph(const ph_scene* s, uint32_t node_cap, uint32_t cha
     });
 }
 
+// a linearised tree into the caller's arrays; returns the node count
+static int emit_kdtree(const detail::KdTree& t, uint32_t node_cap, uint32_t item_cap, int32_t* axis, double* plane, int32_t* front, int32_t* back,
+                       int32_t* first, int32_t* count, int32_t* leaf_items, uint32_t* n_items, double root_bounds[6], int32_t* max_depth) {
+    if (t.axis.size() > node_cap || t.items.size() > item_cap) { g_error = "output capacity too small"; return PH_ERR_SMALL; }
+    for (size_t i = 0; i < t.axis.size(); i++) {
+        if (axis) axis[i] = t.axis[i];
+        if (plane) plane[i] = t.plane[i];
+        if (front) front[i] = t.front[i];
+        if (back) back[i] = t.back[i];
+        if (first) first[i] = t.first[i];
+        if (count) count[i] = t.count[i];
+    }
+    for (size_t i = 0; i < t.items.size(); i++) if (leaf_items) leaf_items[i] = t.items[i];
+    if (n_items) *n_items = (uint32_t)t.items.size();
+    if (root_bounds) {
+        root_bounds[0] = t.root_min.x; root_bounds[1] = t.root_min.y; root_bounds[2] = t.root_min.z;
+        root_bounds[3] = t.root_max.x; root_bounds[4] = t.root_max.y; root_bounds[5] = t.root_max.z;
+    }
+    if (max_depth) *max_depth = t.max_depth;
+    return (int)t.axis.size();
+}
+
 extern "C" int ph_scene_kdtree(const ph_scene* s, int kd_depth, uint32_t node_cap, uint32_t item_cap, int32_t* axis, double* plane,
                                int32_t* front, int32_t* back, int32_t* first, int32_t* count, int32_t* leaf_items, uint32_t* n_items,
                                double root_bounds[6], int32_t* max_depth) {
@@ -450,23 +473,25 @@ extern "C" int ph_scene_kdtree(const ph_scene* s, int kd_depth, uint32_t node_ca
     return guarded([&]() -> int {
         detail::FlatScene flat = detail::FlatScene::from(s->hier);
         detail::KdTree t = detail::kd_scene_tree(flat, kd_depth < 0 ? 10 : (size_t)kd_depth);
-        if (t.axis.size() > node_cap || t.items.size() > item_cap) { g_error = "output capacity too small"; return PH_ERR_SMALL; }
-        for (size_t i = 0; i < t.axis.size(); i++) {
-            if (axis) axis[i] = t.axis[i];
-            if (plane) plane[i] = t.plane[i];
-            if (front) front[i] = t.front[i];
-            if (back) back[i] = t.back[i];
-            if (first) first[i] = t.first[i];
-            if (count) count[i] = t.count[i];
+        return emit_kdtree(t, node_cap, item_cap, axis, plane, front, back, first, count, leaf_items, n_items, root_bounds, max_depth);
+    });
+}
+
+extern "C" int ph_scene_kdmesh_tree(const ph_scene* s, uint32_t mesh, int kd_mesh_depth, uint32_t node_cap, uint32_t item_cap, int32_t* axis, double* plane,
+                                    int32_t* front, int32_t* back, int32_t* first, int32_t* count, int32_t* leaf_items, uint32_t* n_items,
+                                    double root_bounds[6], int32_t* max_depth) {
+    if (!s) return bad("null argument");
+    return guarded([&]() -> int {
+        detail::FlatScene flat = detail::FlatScene::from(s->hier);
+        std::vector<const primitive::MeshData*> meshes;  // numbered by first use, as the upload numbers them
+        for (const auto& fn : flat.root) {
+            const auto& p = fn.geometry.primitive;
+            if (p.kind != primitive::Primitive::MeshK && p.kind != primitive::Primitive::KDMeshK) continue;
+            if (std::find(meshes.begin(), meshes.end(), p.mesh.get()) == meshes.end()) meshes.push_back(p.mesh.get());
         }
-        for (size_t i = 0; i < t.items.size(); i++) if (leaf_items) leaf_items[i] = t.items[i];
-        if (n_items) *n_items = (uint32_t)t.items.size();
-        if (root_bounds) {
-            root_bounds[0] = t.root_min.x; root_bounds[1] = t.root_min.y; root_bounds[2] = t.root_min.z;
-            root_bounds[3] = t.root_max.x; root_bounds[4] = t.root_max.y; root_bounds[5] = t.root_max.z;
-        }
-        if (max_depth) *max_depth = t.max_depth;
-        return (int)t.axis.size();
+        if (mesh >= meshes.size()) return bad("no such mesh");
+        detail::KdTree t = detail::kd_mesh_tree(*meshes[mesh], kd_mesh_depth < 0 ? (size_t)detail::kd_mesh_depth_setting() : (size_t)kd_mesh_depth);
+        return emit_kdtree(t, node_cap, item_cap, axis, plane, front, back, first, count, leaf_items, n_items, root_bounds, max_depth);
     });
 }
 

@@ -72,6 +72,8 @@ struct KdTree {
 // KDLeaf::partitioned (leaf.rs:89-231) over a list of cached bounds (NodeBounds, leaf.rs:16-34)
 KdTree kd_partition(const std::vector<BoundingBox>& bounds, size_t max_depth, PartitionConfig conf);
 KdTree kd_scene_tree(const FlatScene& flat, size_t max_depth);  // KDTreeScene::from, kdscene.rs:19-43
+KdTree kd_mesh_tree(const primitive::MeshData& mesh, size_t max_depth);  // KDMesh::new, kdmesh.rs:37-58: the tree over a mesh's triangles
+long kd_mesh_depth_setting();  // the environment's KD_MESH_DEPTH, else 10 (kdmesh.rs:15, :51-53)
 
 struct Camera {  // camera.rs:17-45
     math::Vec3 eye;

@@ -525,6 +525,23 @@ KdTree kd_scene_tree(const FlatScene& flat, size_t max_depth) {  // kdscene.rs:1
     return kd_partition(bounds, max_depth, PartitionConfig{3, 3, 10});
 }
 
+long kd_mesh_depth_setting() {  // env KD_MESH_DEPTH, kdmesh.rs:51-53
+    long depth = 10;
+    if (const char* e = std::getenv("KD_MESH_DEPTH")) { char* end = nullptr; long v = std::strtol(e, &end, 10); if (end && *end == 0 && v >= 0) depth = v; }
+    return depth;
+}
+
+KdTree kd_mesh_tree(const primitive::MeshData& mesh, size_t max_depth) {  // kdmesh.rs:37-58
+    const auto& pos = mesh.positions();
+    std::vector<BoundingBox> tb;
+    tb.reserve(mesh.triangles().size());
+    for (const auto& t : mesh.triangles()) {  // triangle.rs:29-36
+        Vec3 a = pos[t[0]], b = pos[t[1]], c = pos[t[2]];
+        tb.push_back(BoundingBox::create(Vec3::partial_min(a, Vec3::partial_min(b, c)), Vec3::partial_max(a, Vec3::partial_max(b, c))));
+    }
+    return kd_partition(tb, max_depth, PartitionConfig{3, 3, 10});
+}
+
 Camera::Camera(const camera::CameraSettings& cam, double w, double h) {  // camera.rs:34-45
     eye = cam.eye;
     view_to_world = Mat4::look_at_rh(cam.eye, cam.center, cam.up).inverted();
@@ -698,8 +715,7 @@ Renderer::Renderer(const scene::HierScene& hier, render::Traversal traversal, in
     std::vector<int32_t> kdm_axis, kdm_front, kdm_back, kdm_first, kdm_count, kdm_items;
     std::vector<double> kdm_plane;
     {
-        long kd_mesh_depth = 10;  // env KD_MESH_DEPTH, kdmesh.rs:51-53
-        if (const char* e = std::getenv("KD_MESH_DEPTH")) { char* end = nullptr; long v = std::strtol(e, &end, 10); if (end && *end == 0 && v >= 0) kd_mesh_depth = v; }
+        const long kd_mesh_depth = kd_mesh_depth_setting();
         // PORTRAYER_KDMESH_AS_MESH=1: walk KDMesh primitives like Mesh. The reference's KDMesh classifies the sides of a split
         // with a ray segment of length extent() = the SQUARED diagonal of the mesh's bounds (bounding_box.rs:95-99, "HACK"), so
         // a KDMesh smaller than the distance to the camera loses most of its triangles (the script robot-alarm-clock.rs says
@@ -711,14 +727,7 @@ Renderer::Renderer(const scene::HierScene& hier, render::Traversal traversal, in
             if (p.kind != primitive::Primitive::KDMeshK) continue;
             size_t mi = (size_t)mesh_id[p.mesh.get()];
             if (mesh_kd_root[mi] >= 0) continue;
-            const auto& pos = p.mesh->positions();
-            std::vector<BoundingBox> tb;
-            tb.reserve(p.mesh->triangles().size());
-            for (const auto& t : p.mesh->triangles()) {  // triangle.rs:29-36
-                Vec3 a = pos[t[0]], b = pos[t[1]], c = pos[t[2]];
-                tb.push_back(BoundingBox::create(Vec3::partial_min(a, Vec3::partial_min(b, c)), Vec3::partial_max(a, Vec3::partial_max(b, c))));
-            }
-            KdTree t = kd_partition(tb, (size_t)kd_mesh_depth, PartitionConfig{3, 3, 10});
+            KdTree t = kd_mesh_tree(*p.mesh, (size_t)kd_mesh_depth);
             int32_t base = (int32_t)kdm_axis.size(), ibase = (int32_t)kdm_items.size();
             for (size_t k = 0; k < t.axis.size(); k++) {
                 kdm_axis.push_back(t.axis[k]); kdm_plane.push_back(t.plane[k]);

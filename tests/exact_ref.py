@@ -13,7 +13,14 @@ A triangle's six comparisons are one conjunction (see hit_triangle): a miss take
 
 mode="kd" walks a scene k-d tree as kdtree/node.rs does: the ray segment's end is `start + extent` with extent the squared diagonal (quirk Q3), so with
 directions that are not unit vectors it loses hits the flat walk finds, and the clipped start of a range decides which body root a cone sees (Q1). The
-tree itself is an input (the oracle's dump of its build). KDMesh is out of scope.
+scene's tree is an input (the oracle's dump of its build; tests/exact_kd.py restates the build and tests/test_exact_kdtree.py holds the dump to it).
+
+KDMesh (kdtree/kdmesh.rs:62-74) is the same walk over a tree of triangles in the mesh's model space, behind BoundingBox::test_hit on the tree's root
+bounds. Its tree is NOT an input: it is built by tests/exact_kd.py in plain f64, which equals the reference's tree in every bit (argued there). The
+walk's extent is the squared diagonal of the root bounds, so a KDMesh that is small against its distance from a ray's origin loses hits a Mesh finds
+(Q3 again), and a KDMesh does not answer as a Mesh on purpose. Where the reference would panic (node.rs:146-147, quirk Q4) KdPanic is raised; cast()
+reports such a ray as a miss of margin 0 with `panic` set. ExactScene.mutant names one deliberate misreading of the walk (WALK_MUTANTS), for showing that
+the comparisons can fail.
 """
 from __future__ import annotations
 
@@ -22,7 +29,8 @@ from collections import deque
 
 from mpmath import mp, mpf
 
-from scene_dsl import CONE, CUBE, CYLINDER, MESH, PLANE, SPHERE, TRIANGLE
+import exact_kd
+from scene_dsl import CONE, CUBE, CYLINDER, KDMESH, MESH, PLANE, SPHERE, TRIANGLE
 
 EPS_F64 = 0.00001          # math.rs EPSILON: the f64 nearest to 1e-5, an exact rational here
 FRAGILE = 2.0 ** -30
@@ -31,15 +39,19 @@ PREC = 256
 # parts of a primitive, for coverage
 BODY, CAP_TOP, CAP_BOTTOM = 0, 1, 2   # cylinder: 0, 1, 2; cone: 0 and 2 (its only cap is the bottom one)
 TRI_FLAT, TRI_SMOOTH = 0, 1
+WALK_MUTANTS = ("extent_plain_diagonal", "t_max_without_epsilon", "t_min_without_epsilon", "leaf_range_not_shrinking", "root_box_skipped",
+                "far_side_from_start")
 
 
 class Trace:
     """Smallest margin of the comparisons made for one ray, and whether a Q1 alternative exists."""
-    __slots__ = ("margin", "q1")
+    __slots__ = ("margin", "q1", "far", "mutant")
 
-    def __init__(self):
+    def __init__(self, mutant=None):
         self.margin = math.inf
         self.q1 = False
+        self.far = {}        # per KDMesh geometry: was its last hit found on a pending far side of its tree?
+        self.mutant = mutant
 
     def note(self, m):
         if m != m:
@@ -357,14 +369,57 @@ def hit_triangle(tr, va, vb, vc, normals, o, dr, lo, hi):
     return t, _at(o, dr, t), n, 0, part, (beta, gamma)   # beta and gamma: what triangle.rs:82-138 interpolates texture coordinates with
 
 
+class KdPanic(Exception):
+    pass
+
+
+PANICS = [0]   # how many casts of this process reached the reference's panic
+
+
+def _walk_kd(tr, t, leaf, me, o, d, lo, hi, extent):
+    """kdtree/node.rs:66-203 over the tree `t` (the arrays of exact_kd / the oracle's dump). leaf(items, lo, hi) is `cast_ray` on a leaf's list: the
+    nearest hit of the items in order, the range's end shrinking, as (t, ...) or None. Returns (hit, found on a pending far side)."""
+    if t["kind"][me] == 1:
+        f = t["first"][me]
+        return leaf(t["items"][f:f + t["count"][me]], lo, hi), False
+    mut = tr.mutant
+    axis, plane = t["axis"][me], mpf(t["plane"][me])
+    t_max = lo + extent
+    if not _in_range(tr, t_max, lo, hi):
+        t_max = hi if mut == "t_max_without_epsilon" else hi - mpf(EPS_F64)
+    t_min = lo if mut == "t_min_without_epsilon" else lo + mpf(EPS_F64)
+    # which_side: (p - point) . normal >= 0 is Front; the normal is the positive axis
+    start_front = _le(tr, plane, o[axis] + d[axis] * t_min)
+    end = o[axis] + d[axis] * t_max
+    end_front = False if end != end else _le(tr, plane, end)
+    if start_front == end_front:
+        return _walk_kd(tr, t, leaf, t["front"][me] if start_front else t["back"][me], o, d, lo, hi, extent)
+    plane_t = _div(tr, plane - o[axis], d[axis])
+    if not _in_range(tr, plane_t, lo, hi):
+        raise KdPanic()   # node.rs:146-147: the reference panics here (quirk Q4)
+    first, second = (t["front"][me], t["back"][me]) if start_front else (t["back"][me], t["front"][me])
+    h, far = _walk_kd(tr, t, leaf, first, o, d, lo, plane_t, extent)
+    if h is not None:
+        return h, far
+    h, _ = _walk_kd(tr, t, leaf, second, o, d, lo if mut == "far_side_from_start" else plane_t, hi, extent)
+    return h, h is not None
+
+
+def _extent(tr, rb):
+    """bounding_box.rs:95-99: the SQUARED diagonal (quirk Q3)."""
+    e = sum((rb[3 + q] - rb[q]) ** 2 for q in range(3))
+    return mp.sqrt(e) if tr.mutant == "extent_plain_diagonal" else e
+
+
 class _Geometry:
     """A primitive's data, converted to the working precision on first use."""
+    _trees = {}   # id(MeshData) -> (MeshData, its KDMesh tree): two nodes of one MeshData share one tree, and so do two scenes
 
     def __init__(self, prim):
         self.kind = prim.kind
         self.prim = prim
         self._cache = {}
-        if self.kind not in (SPHERE, TRIANGLE, MESH, PLANE, CUBE, CYLINDER, CONE):
+        if self.kind not in (SPHERE, TRIANGLE, MESH, KDMESH, PLANE, CUBE, CYLINDER, CONE):
             raise ValueError("primitive kind %d is out of scope" % self.kind)
 
     def data(self):
@@ -374,17 +429,28 @@ class _Geometry:
             vec = lambda v: tuple(mpf(float(x)) for x in v)
             if self.kind == TRIANGLE:
                 self._cache[key] = (vec(p.tri[0]), vec(p.tri[1]), vec(p.tri[2]), None if p.tri_normals is None else tuple(vec(n) for n in p.tri_normals))
-            elif self.kind == MESH:
+            elif self.kind in (MESH, KDMESH):
                 pos = [vec(v) for v in p.mesh.positions]
                 nrm = [vec(v) for v in p.mesh.normals] if p.smooth else None
-                mn = tuple(min(v[q] for v in pos) for q in range(3))
-                mx = tuple(max(v[q] for v in pos) for q in range(3))
+                if self.kind == KDMESH:   # kdmesh.rs:26-30: the root node's bounds
+                    rb = [mpf(x) for x in self.tree()["root_bounds"]]
+                    mn, mx = tuple(rb[:3]), tuple(rb[3:])
+                else:
+                    mn = tuple(min(v[q] for v in pos) for q in range(3))
+                    mx = tuple(max(v[q] for v in pos) for q in range(3))
                 size = tuple(max(mx[q] - mn[q], mpf(EPS_F64)) for q in range(3))   # bounding_box.rs:58-64
                 centre = tuple((mn[q] + mx[q]) / 2 for q in range(3))
                 self._cache[key] = (pos, nrm, [tuple(int(x) for x in t) for t in p.mesh.triangles], size, centre)
             else:
                 self._cache[key] = None
         return self._cache[key]
+
+    def tree(self):
+        """KDMesh::new: the tree over the mesh's triangles (exact_kd.mesh_tree, plain f64), built once per MeshData."""
+        m = self.prim.mesh
+        if id(m) not in _Geometry._trees:
+            _Geometry._trees[id(m)] = (m, exact_kd.mesh_tree(m))
+        return _Geometry._trees[id(m)][1]
 
     def hit(self, tr, o, d, lo, hi, alt):
         k = self.kind
@@ -405,13 +471,28 @@ class _Geometry:
         # mesh.rs:152-166 behind bounding_box.rs:100-113: the box is the unit cube under scale(size) then translate(centre)
         bo = tuple((o[q] - centre[q]) / size[q] for q in range(3))
         bd = tuple(d[q] / size[q] for q in range(3))
-        if not _cube_contains(tr, _at(bo, bd, lo)) and hit_cube(tr, bo, bd, lo, hi) is None:
-            return None
-        found = None
-        for idx, (ia, ib, ic) in enumerate(tris):
-            h = hit_triangle(tr, pos[ia], pos[ib], pos[ic], None if nrm is None else (nrm[ia], nrm[ib], nrm[ic]), o, d, lo, hi)
-            if h is not None:
-                found, hi = (h[0], h[1], h[2], idx, h[4], h[5]), h[0]
+        if not (k == KDMESH and tr.mutant == "root_box_skipped"):
+            if not _cube_contains(tr, _at(bo, bd, lo)) and hit_cube(tr, bo, bd, lo, hi) is None:
+                return None
+
+        def nearest(items, lo, hi):   # ray.rs:50-63: [T]::ray_hit, the items in order, the range's end shrinking
+            found = None
+            for idx in items:
+                ia, ib, ic = tris[idx]
+                h = hit_triangle(tr, pos[ia], pos[ib], pos[ic], None if nrm is None else (nrm[ia], nrm[ib], nrm[ic]), o, d, lo, hi)
+                if h is not None:
+                    found = (h[0], h[1], h[2], idx, h[4], h[5])
+                    if tr.mutant != "leaf_range_not_shrinking":
+                        hi = h[0]
+            return found
+
+        if k == MESH:
+            return nearest(range(len(tris)), lo, hi)
+        # kdmesh.rs:72 over node.rs:33-51: the walk of the mesh's own tree; the first leaf with a hit wins
+        tree = self.tree()
+        found, far = _walk_kd(tr, tree, nearest, 0, o, d, lo, hi, _extent(tr, [mpf(x) for x in tree["root_bounds"]]))
+        if found is not None:
+            tr.far[id(self)] = far
         return found
 
 
@@ -431,25 +512,23 @@ class _Node:
 
 
 class Hit:
-    __slots__ = ("t", "node", "sub", "part", "point", "normal", "model_point", "kind", "margin", "q1", "bary")   # bary: a triangle's (beta, gamma), else None
+    __slots__ = ("t", "node", "sub", "part", "point", "normal", "model_point", "kind", "margin", "q1", "bary", "far")   # bary: a triangle's (beta, gamma), else None
+    panic = False
 
     def __repr__(self):
         return "Hit(t=%s node=%d sub=%d part=%d margin=%g q1=%s)" % (mp.nstr(self.t, 17), self.node, self.sub, self.part, self.margin, self.q1)
 
 
 class Miss:
-    __slots__ = ("margin", "q1")
+    __slots__ = ("margin", "q1", "panic")
     t = None
+    far = False
 
-    def __init__(self, margin, q1):
-        self.margin, self.q1 = margin, q1
+    def __init__(self, margin, q1, panic=False):
+        self.margin, self.q1, self.panic = margin, q1, panic
 
     def __bool__(self):
         return False
-
-
-class KdPanic(Exception):
-    pass
 
 
 class ExactScene:
@@ -474,6 +553,7 @@ class ExactScene:
             assert [int(k) for k in prim_type] == [n.geometry.kind for n in self.flat]
         self.flat_trans = flat_trans
         self._fm = {}
+        self.mutant = None   # one of WALK_MUTANTS
 
     def kinds(self):
         return [n.geometry.kind for n in self.flat]
@@ -513,37 +593,20 @@ class ExactScene:
     def set_tree(self, tree):
         self.tree = {k: ([int(x) for x in v] if k != "plane" and k != "root_bounds" else [float(x) for x in v]) for k, v in tree.items()}
 
-    def _cast_kd(self, tr, me, o, d, lo, hi, extent, alt):
-        t = self.tree
-        if t["kind"][me] == 1:   # a leaf: its nodes in order, the range's end shrinking (ray.rs:80-92)
+    def _cast_kd(self, tr, o, d, lo, hi, extent, alt):
+        mats = self.flat_matrices()
+
+        def nearest(items, lo, hi):   # a leaf: its nodes in order, the range's end shrinking (ray.rs:80-92)
             best = None
-            mats = self.flat_matrices()
-            for i in t["items"][t["first"][me]:t["first"][me] + t["count"][me]]:
+            for i in items:
                 tm, inv = mats[i]
                 h = self.flat[i].geometry.hit(tr, _point(inv, o), _direction(inv, d), lo, hi, alt)
                 if h is not None:
-                    hi = h[0]
+                    if tr.mutant != "leaf_range_not_shrinking":
+                        hi = h[0]
                     best = (h[0], i, h[3], h[4], _point(tm, h[1]), _normal(inv, h[2]), h[1], self.flat[i].geometry.kind, h[5] if len(h) > 5 else None)
             return best
-        axis, plane = t["axis"][me], mpf(t["plane"][me])
-        t_max = lo + extent
-        if not _in_range(tr, t_max, lo, hi):
-            t_max = hi - mpf(EPS_F64)
-        t_min = lo + mpf(EPS_F64)
-        # which_side: (p - point) . normal >= 0 is Front; the normal is the positive axis
-        start_front = _le(tr, plane, o[axis] + d[axis] * t_min)
-        end = o[axis] + d[axis] * t_max
-        end_front = False if end != end else _le(tr, plane, end)
-        if start_front == end_front:
-            return self._cast_kd(tr, t["front"][me] if start_front else t["back"][me], o, d, lo, hi, extent, alt)
-        plane_t = _div(tr, plane - o[axis], d[axis])
-        if not _in_range(tr, plane_t, lo, hi):
-            raise KdPanic()   # node.rs:146-147: the reference panics here (quirk Q4)
-        first, second = (t["front"][me], t["back"][me]) if start_front else (t["back"][me], t["front"][me])
-        h = self._cast_kd(tr, first, o, d, lo, plane_t, extent, alt)
-        if h is not None:
-            return h
-        return self._cast_kd(tr, second, o, d, plane_t, hi, extent, alt)
+        return _walk_kd(tr, self.tree, nearest, 0, o, d, lo, hi, extent)[0]
 
     # scene.rs:80-120
     def _cast_hier(self, tr, node, o, d, lo, hi, alt):
@@ -567,27 +630,28 @@ class ExactScene:
         old = mp.prec
         mp.prec = prec
         try:
-            tr = Trace()
+            assert self.mutant is None or self.mutant in WALK_MUTANTS, self.mutant
+            tr = Trace(self.mutant)
+            panic = False
             o = tuple(mpf(float(x)) if not isinstance(x, mpf) else +x for x in origin)
             d = tuple(mpf(float(x)) if not isinstance(x, mpf) else +x for x in direction)
             lo = mpf(EPS_F64)
             hi = t_max if isinstance(t_max, mpf) else (mp.inf if math.isinf(t_max) else mpf(float(t_max)))
-            if mode == "flat":
-                best = self._cast_flat(tr, o, d, lo, hi, alt)
-            elif mode == "hier":
-                best = self._cast_hier(tr, self.root, o, d, lo, hi, alt)
-            elif mode == "kd":
-                rb = [mpf(x) for x in self.tree["root_bounds"]]
-                extent = sum((rb[3 + q] - rb[q]) ** 2 for q in range(3))   # bounding_box.rs:95-99: the SQUARED diagonal (quirk Q3)
-                try:
-                    best = self._cast_kd(tr, 0, o, d, lo, hi, extent, alt)
-                except KdPanic:
-                    best = None
-                    tr.margin = 0.0
-            else:
-                raise ValueError(mode)
+            try:
+                if mode == "flat":
+                    best = self._cast_flat(tr, o, d, lo, hi, alt)
+                elif mode == "hier":
+                    best = self._cast_hier(tr, self.root, o, d, lo, hi, alt)
+                elif mode == "kd":
+                    best = self._cast_kd(tr, o, d, lo, hi, _extent(tr, [mpf(x) for x in self.tree["root_bounds"]]), alt)
+                else:
+                    raise ValueError(mode)
+            except KdPanic:   # in the scene's tree or in a KDMesh's
+                best, panic = None, True
+                PANICS[0] += 1
+                tr.margin = 0.0
             if best is None:
-                return Miss(tr.margin, tr.q1)
+                return Miss(tr.margin, tr.q1, panic)
             h = Hit()
             h.t, h.node, h.sub, h.part, h.point, n, h.model_point, h.kind, h.bary = best
             s = _dot(n, n)
@@ -598,6 +662,7 @@ class ExactScene:
                 r = mp.sqrt(s)
                 h.normal = (n[0] / r, n[1] / r, n[2] / r)
             h.margin, h.q1 = tr.margin, tr.q1
+            h.far = tr.far.get(id(self.flat[h.node].geometry), False)
             return h
         finally:
             mp.prec = old
