@@ -114,6 +114,8 @@ verify-mi:
 # under profiles/ builds - PT_DIAG (diag.sh), PT_CYCLES (cycles.sh), PT_TIMELINE (timeline.sh), PT_OCCLUDER_STATS (occluder_stats.py), PT_PIXEL_LIST_STATS (pixel_list_stats.py), PT_ABLATE
 # (light_slope.py) - and the off switches of shipped optimisations whose gain hangs on this toolchain's register allocation and is measured again after a
 # ROCm update (DESIGN.md names each as its A/B). PT_MIN_WAVES=<n> (profiles/ab.sh) takes a value of the user's and is not listed.
+# PT_PL_DEPTH_FIRST (the list kernel as it was before round 13, for the timing A/B) changes pt_api.hip alone, which `switches` does not compile:
+# `make variant NAME=depthfirst EXTRA_HIPFLAGS=-DPT_PL_DEPTH_FIRST` is its check.
 # `make -j8 switches` compiles each switch alone, device-only, to /dev/null (the pattern of verify-mi, the same HIPFLAGS) for the render modes whose object
 # it changes - MODES_<switch>, all nine where nothing says so: a switch that stops compiling is noticed. Not part of `all`, and no test runs it.
 SWITCHES := PT_DIAG PT_CYCLES PT_TIMELINE PT_OCCLUDER_STATS=1 PT_OCCLUDER_STATS=2 PT_ABLATE=1 PT_ABLATE=2 PT_ABLATE=3 PT_ABLATE=5 PT_ABLATE=6 \

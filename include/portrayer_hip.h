@@ -942,6 +942,16 @@ int pt_test_pixel_beam(uint64_t n, const double *cameras, const uint32_t *pixels
 /* What the last launch of the context left in its per-pixel candidate lists (tests; that launch must be closed). out has 11 entries: [0] the records - 0 where the launch
  * had no lists -, [1] the background ones (empty, nothing left out), [2] those cut at the cap, [3] those marked "take the walk", [4 + n] those with n entries, n = 0 .. 6. */
 int pt_test_pixel_list_summary(pt_context *ctx, uint64_t *out);
+/* pt_test_pixel_beam with a rectangle per case instead of a pixel (rects[4i..]: x, y, nx, ny - the beam of every sample position in [x, x + nx] x [y, y + ny]; the
+ * list kernel opens the tree with the 8 x 8 rectangle of a tile's pixel slots) and the sample's position inside it (offsets[2i..], in [0, nx] x [0, ny]). With
+ * nx = ny = 1 every output is pt_test_pixel_beam's, bit for bit. */
+int pt_test_rect_beam(uint64_t n, const double *cameras, const uint32_t *rects, const double *offsets, const float *box_lo, const float *box_hi,
+                      int32_t *accept, float *bound, int32_t *walk, double *rays);
+/* The raw records of the last launch's per-pixel candidate lists (tests; that launch must be closed). info has 4 entries: [0] the records - 0 where the launch had no
+ * lists -, [1] the 32-bit words of a record, [2] the entries a record holds at most, [3] the scene's flattened nodes. A record: word 0 the number of entries (bit 31: take
+ * the walk), word 1 the tail bound's f32 bits, word 2 + k entry k = the bound's upper 16 bits << 16 | the node. Where out is not NULL and words >= info[0] * info[1], the
+ * records are copied to out; otherwise (words = 0: a query of the sizes) nothing is. */
+int pt_test_pixel_list_records(pt_context *ctx, uint32_t *out, uint64_t words, uint64_t *info);
 /* Host-side run (no GPU, no context) of the film's running sum: `samples` (n x 3) given to one pixel in n_cuts consecutive adds of cuts[k] samples each
  * (their sum must be n), through the functions the film's fold and resolve kernels call. out_sum: what resolve divides by n. */
 int pt_test_film_fold_host(uint32_t n, const double *samples, const uint32_t *cuts, uint32_t n_cuts, double out_sum[3]);

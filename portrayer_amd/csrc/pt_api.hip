@@ -159,14 +159,153 @@ __global__ void __launch_bounds__(256) pt_certain_table_kernel(const uint32_t* _
 }
 
 // The launch's per-pixel candidate lists (pt_pixel_list.h), behind the eye table and the certain-shadow table: a wavefront per 8x8 tile of the launch's own tiles, a lane
-// per pixel slot - pixels of partial tiles outside the slice get a record like any other. The 64 beams of a tile reach nearly the same nodes, so ONE walk of sc.bvh
-// serves them: a node is entered when any lane's beam reaches its box (a lane whose beam missed the box above tests the children all the same: a leaf too many in a list
-// changes nothing), the pending nodes are one list per wavefront in LDS, and a child that is a leaf goes straight into the lists of the lanes that reach it - every item of
-// it with the leaf box's bound. A lane's list is its LDS column, kept sorted (pt_pl_insert). A stack that runs full marks the tile's 64 records "take the walk".
-// cap (PORTRAYER_PIXEL_LIST_CAP, tests only): entries a list may hold, <= PT_PL_K.
+// per pixel slot - pixels of partial tiles outside the slice get a record like any other. Which leaves a pixel's beam reaches does not depend on the order in which the
+// tree is opened, and pt_pl_insert keeps the K smallest entries and the smallest bound turned away whatever the order of arrival: so the wavefront opens sc.bvh up to 64
+// nodes at a time with the TILE's beam (pt_pixel_list.h, 7.: the 8 x 8 rectangle of the tile's slots from lane 0's pixel, whole even where the tile is partial or the launch
+// rank-partitioned; wave-uniform, held in scalar registers), in two interleaved phases:
+//   1. lanes over nodes. The pending inner nodes are one list per wavefront in LDS. A step pops up to 64 from its end; each lane loads its own node's record with vector
+//      loads - all in flight together - and tests both children against the tile's beam. Surviving inner children are appended to the pending list (ballot and lane prefix
+//      count), surviving leaf children go to the wavefront's candidate buffer in LDS as {flattened node index, the leaf box's six planes}, one candidate per item of the
+//      leaf (sc.bvh_items, resolved by the lane that found it). The dependent round trips per tile are about the tree's levels, not the inner nodes reached.
+//   2. lanes over pixels. When the buffer cannot take another step's candidates (PT_PL_STEP_CANDS), or nothing is pending, every lane tests each buffered box - an LDS
+//      broadcast, no global load - with its own pixel's beam and inserts what that reaches with the pixel beam's bound. A lane's list is its LDS column, kept sorted
+//      (pt_pl_insert); flushing in batches cannot change a record.
+// An inner node is pushed once at most, so PT_PL_PENDING words hold any scene of up to 1,024 inner nodes; a pending list that runs full all the same marks the tile's 64
+// records "take the walk".
+// cap (PORTRAYER_PIXEL_LIST_CAP, tests only): entries a list may hold, <= PT_PL_K. pend_cap (PORTRAYER_PIXEL_LIST_PENDING, tests only): the words of the pending list
+// that may be used, 1 .. PT_PL_PENDING - the kernel pops from the end, so on a balanced tree the list stays near 64 x (the levels below the first 64-wide one), a few
+// hundred words at 65,536 nodes: the tests of the marked tiles shrink it.
+// -DPT_PL_DEPTH_FIRST (make variant; the timing A/B): the kernel this one replaced - one depth-first walk per tile, a node per step through the scalar cache, a node
+// entered when any lane's pixel beam reaches it.
+// Block size and buffer by measurement (profiles/r13/notes.md section 4): the kernel waits, so what counts is wavefronts per CU, and LDS sets that - a wavefront per block
+// and the smallest buffer that takes a step, 9.5 KB a wavefront, 16 wavefronts per CU.
+#ifndef PT_PL_DEPTH_FIRST
+#define PT_PL_BLOCK 64
+#define PT_PL_PENDING 1024u    // words of a wavefront's pending list
+#define PT_PL_STEP_CANDS 128u  // the candidates one step can add: 64 nodes x 2 leaf children of one item (direct leaves), or 8 nodes x 2 leaf children x 8 items
+#define PT_PL_CANDS 128u       // a wavefront's candidate buffer, 32 bytes each: flushed in front of a step that might not fit - with this size, whenever it holds anything
+// (what one lane wrote to LDS, seen by the wavefront's other lanes: same wavefront, program order and a fence suffice)
+#define PT_PL_WAVE_SYNC() do { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); } while (0)
+static __device__ __forceinline__ float pt_pl_scalar(float v) { return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v))); }
+static __device__ __forceinline__ uint32_t pt_pl_lanes_below(unsigned long long m) { return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u)); }
+__global__ void __launch_bounds__(PT_PL_BLOCK) pt_pixel_list_kernel(PtRenderArgs a, uint32_t* __restrict__ table, uint32_t cap, uint32_t pend_cap) {
+    __shared__ uint32_t s_list[PT_PL_BLOCK / 64][PT_PL_K][64];
+    __shared__ uint32_t s_pend[PT_PL_BLOCK / 64][PT_PL_PENDING];
+    __shared__ uint4 s_cand[PT_PL_BLOCK / 64][PT_PL_CANDS * 2u];  // {node, lo.x, lo.y, lo.z}, {hi.x, hi.y, hi.z, -}
+    static_assert(PT_PL_CANDS >= PT_PL_STEP_CANDS, "the empty buffer takes a step's candidates");
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    const uint32_t tile_local = PT_UNIFORM_U32(blockIdx.x * (PT_PL_BLOCK / 64) + wave);
+    if (tile_local >= a.n_slots / 64u) return;  // (wave-uniform)
+    const PtSceneView& sc = a.scene;
+    const uint32_t slot = tile_local * 64u + lane;
+    uint32_t x, y, tx, ty;
+    pt_slot_to_pixel(a, slot, &x, &y);
+    pt_slot_to_pixel(a, tile_local * 64u, &tx, &ty);
+    const PtBeam beam = pt_beam_setup(a.cam, (double)x, (double)y);
+    PtBeam tile = pt_beam_setup(a.cam, (double)tx, (double)ty, 8.0, 8.0);
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        PtBeamAxis& t = tile.ax[k];
+        t.neg = __builtin_amdgcn_readfirstlane(t.neg);
+        t.a1 = pt_pl_scalar(t.a1); t.a2 = pt_pl_scalar(t.a2); t.be1 = pt_pl_scalar(t.be1); t.be2 = pt_pl_scalar(t.be2); t.bf1 = pt_pl_scalar(t.bf1); t.bf2 = pt_pl_scalar(t.bf2);
+    }
+    tile.lmin = pt_pl_scalar(tile.lmin);
+    uint32_t* const list = &s_list[wave][0][lane];
+    uint32_t* const pend = s_pend[wave];
+    uint4* const cand = s_cand[wave];
+    uint32_t count = 0, tail = PT_PL_INF_BITS;
+    if (cap > PT_PL_K) cap = PT_PL_K;  // (the host refuses a larger one; a list's LDS column has PT_PL_K rows)
+    if (pend_cap > PT_PL_PENDING) pend_cap = PT_PL_PENDING;
+    bool overflowed = false;
+    uint32_t n_pend = 0, n_cand = 0;  // (wave-uniform)
+    const bool direct = sc.tlas_direct != 0;
+    const uint32_t root = sc.tlas_root;
+    if (sc.n_nodes != 0 && root != PT_REF_EMPTY) {
+        if (root & PT_REF_LEAF) {  // (the walk tests a root leaf without a box test)
+            const uint32_t first = (root & ~PT_REF_LEAF) >> 3, n = direct ? 1u : (root & 7u) + 1u;
+            for (uint32_t i = 0; i < n; i++) pt_pl_insert(list, 64u, cap, &count, &tail, pt_pl_entry(0.0f, direct ? first : sc.bvh_items[first + i]));
+        } else {
+            if (lane == 0) pend[0] = root;
+            n_pend = 1;
+        }
+    }
+    auto flush = [&]() {  // phase 2
+        PT_PL_WAVE_SYNC();
+        for (uint32_t j = 0; j < n_cand; j++) {
+            const uint4 c0 = cand[2u * j], c1 = cand[2u * j + 1u];
+            const float lo[3] = {pt_f32_of(c0.y), pt_f32_of(c0.z), pt_f32_of(c0.w)}, hi[3] = {pt_f32_of(c1.x), pt_f32_of(c1.y), pt_f32_of(c1.z)};
+            float bound = 0.0f;
+            if (pt_beam_box(beam, lo, hi, &bound)) pt_pl_insert(list, 64u, cap, &count, &tail, pt_pl_entry(bound, c0.x));
+        }
+        n_cand = 0;
+    };
+    const uint32_t width = direct ? 64u : PT_PL_STEP_CANDS / 16u;
+    while (n_pend > 0) {
+        if (n_cand > PT_PL_CANDS - PT_PL_STEP_CANDS) flush();
+        PT_PL_WAVE_SYNC();
+        // phase 1: a lane per pending node
+        const uint32_t take = n_pend < width ? n_pend : width;
+        n_pend -= take;
+        uint32_t ref[2] = {PT_REF_EMPTY, PT_REF_EMPTY};
+        uint32_t nd[12] = {};
+        bool reached[2] = {false, false};
+        if (lane < take) {
+            const uint4* const p = reinterpret_cast<const uint4*>(sc.bvh) + 4u * (size_t)pend[n_pend + lane];  // (PtBvhNode as 16 words: lo[axis][child], hi[axis][child], the children)
+            const uint4 q0 = p[0], q1 = p[1], q2 = p[2];
+            const uint2 q3 = *reinterpret_cast<const uint2*>(p + 3);
+            nd[0] = q0.x; nd[1] = q0.y; nd[2] = q0.z; nd[3] = q0.w; nd[4] = q1.x; nd[5] = q1.y; nd[6] = q1.z; nd[7] = q1.w; nd[8] = q2.x; nd[9] = q2.y; nd[10] = q2.z; nd[11] = q2.w;
+            ref[0] = q3.x; ref[1] = q3.y;
+#pragma unroll
+            for (int ch = 0; ch < 2; ch++) {
+                if (ref[ch] == PT_REF_EMPTY) continue;
+                float lo[3], hi[3], bound;
+#pragma unroll
+                for (int k = 0; k < 3; k++) { lo[k] = pt_f32_of(nd[2 * k + ch]); hi[k] = pt_f32_of(nd[6 + 2 * k + ch]); }
+                reached[ch] = pt_beam_box(tile, lo, hi, &bound);
+            }
+        }
+        const bool inner0 = reached[0] && !(ref[0] & PT_REF_LEAF), inner1 = reached[1] && !(ref[1] & PT_REF_LEAF);
+        const unsigned long long m0 = __ballot(inner0), m1 = __ballot(inner1);
+        const uint32_t n0 = (uint32_t)__builtin_popcountll(m0), n1 = (uint32_t)__builtin_popcountll(m1);
+        if (n_pend + n0 + n1 > pend_cap) { overflowed = true; break; }
+        if (inner0) pend[n_pend + pt_pl_lanes_below(m0)] = ref[0];
+        if (inner1) pend[n_pend + n0 + pt_pl_lanes_below(m1)] = ref[1];
+        n_pend += n0 + n1;
+#pragma unroll
+        for (int ch = 0; ch < 2; ch++) {
+            const bool leaf = reached[ch] && (ref[ch] & PT_REF_LEAF);
+            const uint32_t first = (ref[ch] & ~PT_REF_LEAF) >> 3, n = !leaf ? 0u : (direct ? 1u : (ref[ch] & 7u) + 1u);
+            for (uint32_t i = 0; i < 8u; i++) {
+                const bool mine = i < n;
+                const unsigned long long m = __ballot(mine);
+                if (m == 0) break;
+                if (mine) {
+                    const uint32_t at = 2u * (n_cand + pt_pl_lanes_below(m));
+                    cand[at] = make_uint4(direct ? first : sc.bvh_items[first + i], nd[ch], nd[2 + ch], nd[4 + ch]);
+                    cand[at + 1u] = make_uint4(nd[6 + ch], nd[8 + ch], nd[10 + ch], 0u);
+                }
+                n_cand += (uint32_t)__builtin_popcountll(m);
+            }
+        }
+    }
+    if (!overflowed && n_cand) flush();
+    // (each lane its own record, 16-byte stores a record apart: staging the tile's records in LDS and storing them by rows was measured and gained nothing -
+    // profiles/r13/notes.md section 4)
+    uint32_t* rec = table + (size_t)slot * PT_PL_WORDS;
+    uint32_t wds[PT_PL_WORDS];
+    wds[0] = overflowed ? PT_PL_WALK : count;
+    wds[1] = tail;
+#pragma unroll
+    for (uint32_t k = 0; k < PT_PL_K; k++) wds[2 + k] = k < count ? list[k * 64u] : 0u;
+#pragma unroll
+    for (uint32_t k = 2 + PT_PL_K; k < PT_PL_WORDS; k++) wds[k] = 0u;
+#pragma unroll
+    for (uint32_t k = 0; k < PT_PL_WORDS; k += 4) reinterpret_cast<uint4*>(rec)[k / 4] = make_uint4(wds[k], wds[k + 1], wds[k + 2], wds[k + 3]);
+}
+#else
 #define PT_PL_BLOCK 256
 #define PT_PL_STACK 64
-__global__ void __launch_bounds__(PT_PL_BLOCK) pt_pixel_list_kernel(PtRenderArgs a, uint32_t* __restrict__ table, uint32_t cap) {
+__global__ void __launch_bounds__(PT_PL_BLOCK) pt_pixel_list_kernel(PtRenderArgs a, uint32_t* __restrict__ table, uint32_t cap, uint32_t pend_cap) {
     __shared__ uint32_t s_list[PT_PL_BLOCK / 64][PT_PL_K][64];
     __shared__ uint32_t s_stack[PT_PL_BLOCK / 64][PT_PL_STACK];
     const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
@@ -226,6 +365,7 @@ __global__ void __launch_bounds__(PT_PL_BLOCK) pt_pixel_list_kernel(PtRenderArgs
 #pragma unroll
     for (uint32_t k = 0; k < PT_PL_WORDS; k += 4) reinterpret_cast<uint4*>(rec)[k / 4] = make_uint4(wds[k], wds[k + 1], wds[k + 2], wds[k + 3]);
 }
+#endif
 
 // ------------------------------------------------------------------------------------------------
 // The life of a device pass (PtPass), the same for every kind. Queueing: prepare, [the kind's argument block and sizing dispatch], open, [its sort and kernels],
@@ -605,19 +745,20 @@ extern "C" int pt_test_pixel_list_summary(pt_context* c, uint64_t* out) {
 // rejects), walk = what the walk does with the box for that sample's ray and no bound on t (pt_raypk's constants): bit 0 pt_slab_pk2<PT_OCT_MIXED> accepts, bit 1 the form of
 // the ray's own octant accepts (a ray with a switched-off axis has none: bit 1 repeats bit 0); rays (optional, 6 doubles per case): that ray's origin and direction.
 // Tests check that walk != 0 never comes with accept == 0, and that bound never exceeds the exact entry parameter.
-extern "C" int pt_test_pixel_beam(uint64_t n, const double* cameras, const uint32_t* pixels, const double* jitters, const float* box_lo, const float* box_hi,
-                                  int32_t* accept, float* bound, int32_t* walk, double* rays) {
-    if (!cameras || !pixels || !jitters || !box_lo || !box_hi || !accept || !bound || !walk) return PT_ERR_ARGUMENT;
+// (`stride` words per case in `rects`: x, y and, where stride is 4, nx, ny - otherwise the pixel's 1, 1)
+static int pt_test_beam_cases(uint64_t n, const double* cameras, const uint32_t* rects, uint32_t stride, const double* jitters, const float* box_lo, const float* box_hi,
+                              int32_t* accept, float* bound, int32_t* walk, double* rays) {
+    if (!cameras || !rects || !jitters || !box_lo || !box_hi || !accept || !bound || !walk) return PT_ERR_ARGUMENT;
     for (uint64_t i = 0; i < n; i++) {
         PtCamera cam;
         const double* cp = cameras + 19 * i;
         for (int k = 0; k < 3; k++) cam.eye[k] = cp[k];
         for (int k = 0; k < 12; k++) cam.view_to_world[k] = cp[3 + k];
         cam.fov_factor = cp[15]; cam.aspect = cp[16]; cam.width = cp[17]; cam.height = cp[18];
-        const uint32_t x = pixels[2 * i], y = pixels[2 * i + 1];
+        const uint32_t x = rects[stride * i], y = rects[stride * i + 1];
         const float* lo = box_lo + 3 * i;
         const float* hi = box_hi + 3 * i;
-        const PtBeam beam = pt_beam_setup(cam, (double)x, (double)y);
+        const PtBeam beam = stride == 4u ? pt_beam_setup(cam, (double)x, (double)y, (double)rects[4 * i + 2], (double)rects[4 * i + 3]) : pt_beam_setup(cam, (double)x, (double)y);
         float b = 0.0f;
         accept[i] = pt_beam_box(beam, lo, hi, &b) ? 1 : 0;
         bound[i] = accept[i] ? b : 0.0f;
@@ -650,6 +791,35 @@ extern "C" int pt_test_pixel_beam(uint64_t n, const double* cameras, const uint3
         }
         walk[i] = (m0 ? 1 : 0) | (o0 ? 2 : 0);
     }
+    return PT_OK;
+}
+extern "C" int pt_test_pixel_beam(uint64_t n, const double* cameras, const uint32_t* pixels, const double* jitters, const float* box_lo, const float* box_hi,
+                                  int32_t* accept, float* bound, int32_t* walk, double* rays) {
+    return pt_test_beam_cases(n, cameras, pixels, 2u, jitters, box_lo, box_hi, accept, bound, walk, rays);
+}
+// pt_test_pixel_beam with a rectangle per case (rects[4 i ..]: x, y, nx, ny - the beam of the sample positions in [x, x + nx] x [y, y + ny], pt_pixel_list.h 7.; the list
+// kernel's tile beam is nx = ny = 8) and the sample's position inside it (offsets[2 i ..] in [0, nx] x [0, ny]: the ray of pt_camera_ray(x + ox, y + oy)). nx = ny = 1 is
+// pt_test_pixel_beam's case, bit for bit.
+extern "C" int pt_test_rect_beam(uint64_t n, const double* cameras, const uint32_t* rects, const double* offsets, const float* box_lo, const float* box_hi,
+                                 int32_t* accept, float* bound, int32_t* walk, double* rays) {
+    return pt_test_beam_cases(n, cameras, rects, 4u, offsets, box_lo, box_hi, accept, bound, walk, rays);
+}
+
+// The last launch's pixel-list records as the list kernel wrote them (tests; the launch must have been closed, as for pt_test_pixel_list_summary): info[0] the records (0:
+// that launch had no lists), info[1] the words of a record (PT_PL_WORDS), info[2] the entries a record holds at most (PT_PL_K), info[3] the scene's flattened nodes. Where
+// `out` is not NULL and `words` >= info[0] info[1], the records are copied to it; with fewer words (0: a query of the sizes) nothing is copied.
+extern "C" int pt_test_pixel_list_records(pt_context* c, uint32_t* out, uint64_t words, uint64_t* info) {
+    if (!c || !info) return PT_ERR_ARGUMENT;
+    info[0] = 0; info[1] = PT_PL_WORDS; info[2] = PT_PL_K; info[3] = c->pl_nodes;
+    if (c->pl_slot < 0 || c->pl_slots == 0) return PT_OK;
+    info[0] = c->pl_slots;
+    const size_t need = (size_t)c->pl_slots * PT_PL_WORDS;
+    if (!out || words < need) return PT_OK;
+    PT_HIP(c, hipSetDevice(c->device));
+    PT_HIP(c, hipDeviceSynchronize());
+    const pt_context::Slot& sl = c->slot[c->pl_slot];
+    if (sl.eye_tab.bytes < c->pl_off + need * 4) return pt_fail(c, PT_ERR_ARGUMENT, "the slot's buffer no longer holds that launch's lists");
+    PT_HIP(c, hipMemcpy(out, (const char*)sl.eye_tab.p + c->pl_off, need * 4, hipMemcpyDeviceToHost));
     return PT_OK;
 }
 
@@ -932,7 +1102,8 @@ static int pt_render_common(pt_context* c, PtRenderArgs& a, bool stats, hipStrea
     // The per-pixel candidate lists (pt_pixel_list.h; pt_render_simple.h: PIXEL_LISTS) behind both: the launches whose kernel reads them - the plain straight-line kernels of
     // this mode where a wavefront is one pixel - and scenes whose node indices fit an entry's 16 bits. Their 64-byte header is written in every launch that has an eye table
     // (0: no lists). PORTRAYER_PIXEL_LISTS=0: none (the walk's image from the same library); PORTRAYER_PIXEL_LIST_CAP=k (tests only): a list holds k entries at most, so that
-    // small scenes reach the tail bound and the fall-back. -DPT_NO_PIXEL_LISTS: no header, no lists, the kernels as they were (A/B).
+    // small scenes reach the tail bound and the fall-back; PORTRAYER_PIXEL_LIST_PENDING=n (tests only): the list kernel's pending list holds n nodes at most, so that tiles get
+    // marked "take the walk". -DPT_NO_PIXEL_LISTS: no header, no lists, the kernels as they were (A/B).
 #ifndef PT_NO_PIXEL_LISTS
     const bool list_header = eye_table;
 #ifdef PT_PIXEL_LIST_STATS  // the counting build evaluates the lists beside its walk (pt_render_simple.h): it gets them too
@@ -950,9 +1121,16 @@ static int pt_render_common(pt_context* c, PtRenderArgs& a, bool stats, hipStrea
         if (end == e || *end || k > PT_PL_K) return pt_fail(c, PT_ERR_ARGUMENT, std::string("PORTRAYER_PIXEL_LIST_CAP=") + e + ": expected 0 .. " + std::to_string(PT_PL_K));
         list_cap = (uint32_t)k;
     }
+    uint32_t list_pending = 1024u;  // (the kernel's PT_PL_PENDING; the depth-first variant has its own stack and ignores it)
+    if (const char* e = getenv("PORTRAYER_PIXEL_LIST_PENDING"); e && *e) {
+        char* end = nullptr;
+        const unsigned long long k = strtoull(e, &end, 10);
+        if (end == e || *end || k < 1u || k > list_pending) return pt_fail(c, PT_ERR_ARGUMENT, std::string("PORTRAYER_PIXEL_LIST_PENDING=") + e + ": expected 1 .. " + std::to_string(list_pending));
+        list_pending = (uint32_t)k;
+    }
 #else
     const bool list_header = false, pixel_lists = false;
-    const uint32_t list_cap = 0;
+    const uint32_t list_cap = 0, list_pending = 0;
 #endif
     const size_t list_off = pt_pl_header_offset((uint32_t)a.scene.n_nodes);
     a.eye_tab = nullptr;
@@ -995,11 +1173,11 @@ static int pt_render_common(pt_context* c, PtRenderArgs& a, bool stats, hipStrea
             PT_HIP(c, hipMemsetD32Async((hipDeviceptr_t)header, pixel_lists ? 1 : 0, 16, stream));
             if (pixel_lists) {
                 const uint32_t tiles = a.n_slots / 64u;
-                hipLaunchKernelGGL(pt_pixel_list_kernel, dim3((tiles + PT_PL_BLOCK / 64 - 1) / (PT_PL_BLOCK / 64)), dim3(PT_PL_BLOCK), 0, stream, a, header + 16, list_cap);
+                hipLaunchKernelGGL(pt_pixel_list_kernel, dim3((tiles + PT_PL_BLOCK / 64 - 1) / (PT_PL_BLOCK / 64)), dim3(PT_PL_BLOCK), 0, stream, a, header + 16, list_cap, list_pending);
                 PT_HIP(c, hipGetLastError());
             }
         }
-        c->pl_slot = pixel_lists ? slot_index : -1; c->pl_slots = a.n_slots; c->pl_off = list_off + 64;
+        c->pl_slot = pixel_lists ? slot_index : -1; c->pl_slots = a.n_slots; c->pl_off = list_off + 64; c->pl_nodes = (uint32_t)a.scene.n_nodes;
         PT_HIP(c, pt_dispatch(a, stats, c->n_cu, stream, &grid, true));
         hipLaunchKernelGGL(pt_finish_kernel, dim3((a.n_slots + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, stream, a);
         PT_HIP(c, hipGetLastError());

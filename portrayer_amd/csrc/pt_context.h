@@ -104,7 +104,8 @@ struct pt_context {
     uint32_t last_mode = 0, last_variant = 0;
     int pl_slot = -1;          // pt_test_pixel_list_summary: the slot whose eye_tab buffer holds the last launch's pixel lists (-1: that launch had none) ...
     uint32_t pl_slots = 0;     // ... its pixel slots ...
-    size_t pl_off = 0;         // ... and where its records start in the buffer
+    size_t pl_off = 0;         // ... where its records start in the buffer ...
+    uint32_t pl_nodes = 0;     // ... and the scene's flattened nodes (pt_test_pixel_list_records)
     // The three passes beside the render, each with a PtPass of its own: all three may be in flight at once, with two renders. Beside it, what is the kind's.
     // The primary-visibility pass (pt_aov / pt_aov_device ... pt_aov_finish): the device copies of the host-buffer path's six outputs.
     // The guides pass (pt_guides ...) runs on the SAME pass - one of the two in flight, one set of stack columns - and its host-buffer path takes position, normal and

@@ -48,6 +48,13 @@
 //    walk's arithmetic and likewise exactly (E lies below the exact (P - o) / D_a of the entering plane as well), so t_in >= max(E_x, E_y, E_z, 0) L >= Emax Lmin,
 //    Lmin^2 = the sum of the ranges' smallest squared magnitudes. Stored as the f32 below it, of which the record keeps the upper 16 bits (truncation of a positive float
 //    rounds toward zero). A hit of the leaf's primitive lies inside the box at t >= t_in up to f64 rounding (2^-52), five orders of magnitude inside the 2^-19 the bound gave away.
+// 7. Any rectangle. Nothing in 1. to 6. uses the square's size: for sample positions in [px, px + nx] x [py, py + ny] (nx, ny >= 0) the computed D still lies between its
+//    values at the rectangle's four corners (1.: monotone rounding), Lmin and Lmax still come from the ranges, and 2. to 6. speak of one sample's ray against ranges that
+//    contain it. So pt_beam_setup(c, px, py, nx, ny) owes the same: whatever the walk accepts for a sample position inside the rectangle, pt_beam_box accepts, and the bound
+//    lies below every such ray's entry parameter. The pixel's beam is nx = ny = 1 (px + 1.0 as before: the same bits). The list kernel's TILE beam is the 8 x 8 rectangle of
+//    a tile's 64 pixel slots, from lane 0's pixel: a box that any pixel's sample ray reaches in the walk is accepted by it, so every ancestor of a leaf that is hit gets
+//    opened. What does NOT follow, and is not needed: that a box the pixel's beam accepts is accepted by the tile's - the two sets of f32 constants are rounded
+//    independently, so a box that grazes the pixel's beam (and that no ray hits) may be turned away by the tile's.
 #pragma once
 
 #include "pt_scene_view.h"
@@ -111,11 +118,11 @@ PT_HD void pt_beam_corner(const PtCamera& c, double view_x, double view_y, doubl
     D[0] = d.x; D[1] = d.y; D[2] = d.z;
 }
 
-// The beam of pixel (px, py): every sample position in [px, px + 1] x [py, py + 1].
-PT_HD PtBeam pt_beam_setup(const PtCamera& c, double px, double py) {
+// The beam of the sample positions in [px, px + nx] x [py, py + ny] (7.); a pixel's: nx = ny = 1, every sample position in [px, px + 1] x [py, py + 1].
+PT_HD PtBeam pt_beam_setup(const PtCamera& c, double px, double py, double nx = 1.0, double ny = 1.0) {
     double lo[3], hi[3];
     bool finite = true;  // (a NaN or an infinity in a corner: no axis constrains anything)
-    const double vx[2] = {pt_beam_view_x(c, px), pt_beam_view_x(c, px + 1.0)}, vy[2] = {pt_beam_view_y(c, py), pt_beam_view_y(c, py + 1.0)};
+    const double vx[2] = {pt_beam_view_x(c, px), pt_beam_view_x(c, px + nx)}, vy[2] = {pt_beam_view_y(c, py), pt_beam_view_y(c, py + ny)};
     for (int k = 0; k < 4; k++) {
         double D[3];
         pt_beam_corner(c, vx[k & 1], vy[k >> 1], D);

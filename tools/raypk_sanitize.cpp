@@ -66,5 +66,32 @@ int main() {
     if (pt_test_pixel_beam(1, nullptr, pix.data(), jit.data(), lo.data(), hi.data(), accept.data(), bound.data(), walk.data(), nullptr) == 0) { std::printf("cameras = NULL was not refused\n"); return 1; }
     if (pt_test_pixel_beam(0, cams.data(), pix.data(), jit.data(), lo.data(), hi.data(), accept.data(), bound.data(), walk.data(), nullptr) != 0) { std::printf("n = 0 failed\n"); return 1; }
     std::printf("pixel beam ok: %llu cases, %llu listed, %llu accepted by the walk\n", (unsigned long long)n, (unsigned long long)listed, (unsigned long long)walked);
+
+    // The same test with a rectangle per case (pt_test_rect_beam), on the same cameras - the degenerate ones included - and boxes: the list kernel's 8 x 8 tile, rows and
+    // columns, zero-sized rectangles (one sample position, a line of them), huge ones; the sample at a corner of its rectangle or inside. A rectangle of 1 x 1 must repeat
+    // the pixel's verdict and bound.
+    std::vector<uint32_t> rect(4 * n);
+    std::vector<double> off(2 * n);
+    std::vector<int32_t> accept_r(n), walk_r(n);
+    std::vector<float> bound_r(n);
+    const uint32_t sizes[] = {8, 1, 0, 8, 1, 0, 64, 0xFFFFFFFFu};
+    for (uint64_t i = 0; i < n; i++) {
+        rect[4 * i] = pix[2 * i]; rect[4 * i + 1] = pix[2 * i + 1];
+        const bool as_pixel = i % 4 == 0;
+        rect[4 * i + 2] = as_pixel ? 1u : sizes[rng() % 8]; rect[4 * i + 3] = as_pixel ? 1u : sizes[rng() % 8];
+        for (int k = 0; k < 2; k++) off[2 * i + k] = as_pixel ? jit[2 * i + k] : (double)rect[4 * i + 2 + k] * ((rng() % 3 == 0) ? 0.0 : ((rng() % 3 == 0) ? 1.0 : 0.5 + 0.5 * u(rng)));
+    }
+    rc = pt_test_rect_beam(n, cams.data(), rect.data(), off.data(), lo.data(), hi.data(), accept_r.data(), bound_r.data(), walk_r.data(), rays.data());
+    if (rc != 0) { std::printf("pt_test_rect_beam returned %d\n", rc); return 1; }
+    uint64_t listed_r = 0;
+    for (uint64_t i = 0; i < n; i++) {
+        listed_r += (uint64_t)accept_r[i];
+        if (accept_r[i] && !(bound_r[i] >= 0.0f)) { std::printf("rectangle case %llu: a bound that is no number\n", (unsigned long long)i); return 1; }
+        if (i % 4 == 0 && (accept_r[i] != accept[i] || bound_r[i] != bound[i] || walk_r[i] != walk[i])) { std::printf("rectangle case %llu: 1 x 1 differs from the pixel\n", (unsigned long long)i); return 1; }
+    }
+    if (pt_test_rect_beam(n, cams.data(), rect.data(), off.data(), lo.data(), hi.data(), accept_r.data(), bound_r.data(), walk_r.data(), nullptr) != 0) { std::printf("rectangles, rays = NULL failed\n"); return 1; }
+    if (pt_test_rect_beam(1, cams.data(), nullptr, off.data(), lo.data(), hi.data(), accept_r.data(), bound_r.data(), walk_r.data(), nullptr) == 0) { std::printf("rects = NULL was not refused\n"); return 1; }
+    if (pt_test_rect_beam(0, cams.data(), rect.data(), off.data(), lo.data(), hi.data(), accept_r.data(), bound_r.data(), walk_r.data(), nullptr) != 0) { std::printf("rectangles, n = 0 failed\n"); return 1; }
+    std::printf("rectangle beam ok: %llu cases, %llu listed\n", (unsigned long long)n, (unsigned long long)listed_r);
     return 0;
 }
