@@ -932,6 +932,16 @@ int pt_test_raypk(uint64_t n, int body, const double *origins, const double *dir
  * 5 cube have a ball; every other type is never certain) with rows 0..2 of its forward and inverse matrices in fwd[12i..] and inv[12i..], a shaded point P[3i..] and a light position L[3i..].
  * out_certain[i]: the single-precision test says the shadow ray certainly ends in the node; out_exact_hit[i]: the exact test of that node for that ray says so. */
 int pt_test_certain_shadow(uint64_t n, int type, const double *fwd, const double *inv, const double *P, const double *L, int32_t *out_certain, int32_t *out_exact_hit);
+/* Host-side run (no GPU, no context) of the dark-light test: a point light enclosed in a sphere or a cube is dark from everywhere, and the launch finds that once per light.
+ * Case i: a node as for pt_test_certain_shadow, a shaded point P[3i..], a light at L[3i..] with the area vectors area[6i..] (area_a, area_b; NULL: point lights).
+ * out_flagged[i]: the light is found enclosed in the node; out_guard[i]: the single-precision lane guard lets P skip the light (0 where not flagged); out_exact_hit[i]: the
+ * exact test of the node for the shadow ray from P toward L reports a hit. */
+int pt_test_dark_light(uint64_t n, int type, const double *fwd, const double *inv, const double *P, const double *L, const double *area, int32_t *out_flagged, int32_t *out_guard,
+                       int32_t *out_exact_hit);
+/* The dark-light records of the context's last launch (tests; that launch must be closed). info has 2 entries: [0] the lights that launch had records for - 0 where it had
+ * none -, [1] the 32-bit words of a record (8). A record: words 0..2 the light's position as f32 bits, word 3 the guard's ceiling on |L - P|^2 as f32 bits (0: the light is
+ * not dark), word 4 the enclosing node + 1 (0: none), word 5 the guard's floor as f32 bits. Where out is not NULL and words >= info[0] * info[1], the records are copied to out. */
+int pt_test_dark_lights(pt_context *ctx, uint32_t *out, uint64_t words, uint64_t *info);
 /* Host-side run (no GPU, no context) of the beam test behind the primary rays' per-pixel candidate lists, beside the tree walk's own slab test. Case i: a camera
  * (cameras[19i..]: eye, rows 0..2 of view_to_world, fov_factor, aspect_ratio, width, height), a pixel (pixels[2i..]: x, y), a sample position inside it
  * (jitters[2i..], each in [0, 1)) and a box (box_lo[3i..], box_hi[3i..]). accept[i]: some ray through the pixel may reach the box, as the list kernel decides it;

@@ -253,6 +253,7 @@ EXPORTS = ["pt_abi_version", "pt_device_count", "pt_context_create", "pt_context
            "pt_aov", "pt_aov_device", "pt_aov_finish", "pt_rays", "pt_rays_device", "pt_rays_finish", "pt_segments", "pt_segments_device",
            "pt_radiance", "pt_radiance_device", "pt_radiance_finish", "pt_scene_update", "pt_node_scene_update", "pt_scene_deform", "pt_node_scene_deform", "pt_scene_mesh_rebuildable", "pt_test_scene_bytes", "pt_test_scene_info",
            "pt_vertex_bounds_device", "pt_scene_deform_device", "pt_test_vertex_box_shape", "pt_test_raypk", "pt_test_certain_shadow", "pt_test_pixel_beam", "pt_test_pixel_list_summary", "pt_test_rect_beam", "pt_test_pixel_list_records",
+           "pt_test_dark_light", "pt_test_dark_lights",
            "pt_film_create", "pt_film_destroy", "pt_film_reset", "pt_film_add", "pt_film_add_device", "pt_film_resolve", "pt_film_resolve_device", "pt_film_counts",
            "pt_test_film_fold_host",
            "pt_film_create_moments", "pt_film_add_map", "pt_film_add_map_device", "pt_film_error", "pt_film_error_device", "pt_film_budget_device",
@@ -351,6 +352,10 @@ def lib() -> C.CDLL:
         l.pt_test_work_items.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
         l.pt_test_certain_shadow.restype = C.c_int
         l.pt_test_certain_shadow.argtypes = [C.c_uint64, C.c_int, _dp, _dp, _dp, _dp, _ip, _ip]
+        l.pt_test_dark_light.restype = C.c_int
+        l.pt_test_dark_light.argtypes = [C.c_uint64, C.c_int, _dp, _dp, _dp, _dp, _dp, _ip, _ip, _ip]
+        l.pt_test_dark_lights.restype = C.c_int
+        l.pt_test_dark_lights.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.c_uint64, C.POINTER(C.c_uint64)]
         l.pt_test_raypk.restype = C.c_int
         l.pt_test_raypk.argtypes = [C.c_uint64, C.c_int, _dp, _dp, _dp, C.POINTER(C.c_float), C.POINTER(C.c_float), _ip, C.POINTER(C.c_float), C.POINTER(C.c_float)]
         l.pt_test_pixel_list_summary.restype = C.c_int

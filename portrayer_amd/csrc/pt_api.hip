@@ -158,6 +158,30 @@ __global__ void __launch_bounds__(256) pt_certain_table_kernel(const uint32_t* _
     pt_certain_ball(info[4 * (size_t)i], fwd + 12 * (size_t)i, inv + 12 * (size_t)i, tab + 4 * (size_t)i);
 }
 
+#ifndef PT_NO_DARK_LIGHTS
+// The launch's dark-light records (in front of the occluder table, PtRenderArgs::occluders; pt_certain.h 4.-8.), behind pt_certain_table_kernel on the launch's stream: a
+// block per light, its threads over the nodes' balls. Per light PT_DARK_WORDS words: the lane guard's record {f32(L), ceil} of the LOWEST node whose ball encloses the
+// light - all zero where none does - then node + 1 (0: none) and the guard's floor for the tests. Lights x nodes evaluations of a dozen f64 operations each: microseconds
+// for the scenes that have an occluder table. Filled in front of every launch like the tables it reads: pt_scene_update moves lights and nodes.
+__global__ void __launch_bounds__(256) pt_dark_light_kernel(const double* __restrict__ lights, const float* __restrict__ balls, uint32_t* __restrict__ words, uint32_t n_nodes) {
+    __shared__ uint32_t best;
+    const double* const light = lights + 15 * (size_t)blockIdx.x;
+    if (threadIdx.x == 0) best = 0xFFFFFFFFu;
+    __syncthreads();
+    float rec[4];
+    for (uint32_t i = threadIdx.x; i < n_nodes; i += blockDim.x)
+        if (pt_dark_light(light, balls + 4 * (size_t)i, rec)) atomicMin(&best, i);
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    uint32_t* const o = words + PT_DARK_WORDS * (size_t)blockIdx.x;
+    const bool found = best != 0xFFFFFFFFu && pt_dark_light(light, balls + 4 * (size_t)best, rec);
+    for (int k = 0; k < 4; k++) o[k] = found ? __builtin_bit_cast(uint32_t, rec[k]) : 0u;
+    o[4] = found ? best + 1u : 0u;
+    o[5] = found ? __builtin_bit_cast(uint32_t, PT_DARK_D2_MIN) : 0u;
+    o[6] = o[7] = 0u;
+}
+#endif
+
 // The launch's per-pixel candidate lists (pt_pixel_list.h), behind the eye table and the certain-shadow table: a wavefront per 8x8 tile of the launch's own tiles, a lane
 // per pixel slot - pixels of partial tiles outside the slice get a record like any other. Which leaves a pixel's beam reaches does not depend on the order in which the
 // tree is opened, and pt_pl_insert keeps the K smallest entries and the smallest bound turned away whatever the order of arrival: so the wavefront opens sc.bvh up to 64
@@ -846,6 +870,57 @@ extern "C" int pt_test_certain_shadow(uint64_t n, int type, const double* fwd, c
     return PT_OK;
 }
 
+// Host-side run (no GPU involved) of the dark-light test (pt_certain.h 4.-8.): case i is a node of `type` with the records fwd[12 i ..], inv[12 i ..], a shaded point P[3 i ..]
+// and a light at L[3 i ..] with the area vectors area[6 i ..] (area_a, area_b; NULL: point lights). out_flagged[i]: the table routines gave the node a ball and found the light
+// enclosed in it; out_guard[i]: the lane guard, on the floats the kernel would hold, lets P through (0 where not flagged); out_exact_hit[i]: the reference's own test of that
+// node for the shadow ray {P, (L - P) / |L - P|} over [EPSILON, INF), as in pt_test_certain_shadow. Tests check that flagged and guard never come without exact_hit.
+extern "C" int pt_test_dark_light(uint64_t n, int type, const double* fwd, const double* inv, const double* P, const double* L, const double* area, int32_t* out_flagged,
+                                  int32_t* out_guard, int32_t* out_exact_hit) {
+    if (!fwd || !inv || !P || !L || !out_flagged || !out_guard || !out_exact_hit || type < 0 || type > 7) return PT_ERR_ARGUMENT;
+    for (uint64_t i = 0; i < n; i++) {
+        float ball[4], rec[4];
+        pt_certain_ball((uint32_t)type, fwd + 12 * i, inv + 12 * i, ball);
+        double light[15];
+        for (int k = 0; k < 15; k++) light[k] = 0.0;
+        for (int k = 0; k < 3; k++) light[k] = L[3 * i + k];
+        if (area) for (int k = 0; k < 6; k++) light[9 + k] = area[6 * i + k];
+        const PtVec3 p = pt_v3(P[3 * i], P[3 * i + 1], P[3 * i + 2]), l = pt_v3(light[0], light[1], light[2]);
+#ifndef PT_NO_DARK_LIGHTS
+        out_flagged[i] = pt_dark_light(light, ball, rec) ? 1 : 0;
+        out_guard[i] = out_flagged[i] && pt_dark_lane(rec, (float)p.x, (float)p.y, (float)p.z) ? 1 : 0;
+#else
+        (void)rec;
+        out_flagged[i] = out_guard[i] = 0;
+#endif
+        PtRay r;
+        r.o = p;
+        const PtVec3 hit_to_light = l - p;
+        r.d = hit_to_light / pt_length(hit_to_light);
+        const PtRay local = pt_ray_to_local(inv + 12 * i, r);
+        double t;
+        uint32_t part = 0;
+        out_exact_hit[i] = pt_unit_prim_hit((uint32_t)type, local, PT_EPSILON, INFINITY, &t, &part) ? 1 : 0;
+    }
+    return PT_OK;
+}
+
+// The dark-light records of the context's last launch (tests; the launch must have been closed): info[0] the lights that launch had records for (0: none - another mode,
+// no occluder table, -DPT_NO_DARK_LIGHTS), info[1] the words of a record (PT_DARK_WORDS). Where `out` is not NULL and `words` >= info[0] info[1], the records are copied to it.
+extern "C" int pt_test_dark_lights(pt_context* c, uint32_t* out, uint64_t words, uint64_t* info) {
+    if (!c || !info) return PT_ERR_ARGUMENT;
+    info[0] = 0; info[1] = PT_DARK_WORDS;
+    if (c->dark_slot < 0 || c->dark_lights == 0) return PT_OK;
+    info[0] = c->dark_lights;
+    const size_t need = (size_t)c->dark_lights * PT_DARK_WORDS;
+    if (!out || words < need) return PT_OK;
+    PT_HIP(c, hipSetDevice(c->device));
+    PT_HIP(c, hipDeviceSynchronize());
+    const pt_context::Slot& sl = c->slot[c->dark_slot];
+    if (sl.misc.bytes < c->dark_off + need * 4) return pt_fail(c, PT_ERR_ARGUMENT, "the slot's buffer no longer holds that launch's records");
+    PT_HIP(c, hipMemcpy(out, (const char*)sl.misc.p + c->dark_off, need * 4, hipMemcpyDeviceToHost));
+    return PT_OK;
+}
+
 // How a launch's traversal stacks are split between LDS and HBM - one place for the render kernels and every pass beside them, whose
 // kernels lay their LDS out with the same code (pt_trace_wave: pt_wave_rows, pt_kd_layout).
 // pt_stack_lds_cap: entries per lane kept in LDS = what `block_budget` bytes of LDS per block leave beside `frame_bytes` of other per-block data (1 KB a row), at most the
@@ -1083,7 +1158,18 @@ static int pt_render_common(pt_context* c, PtRenderArgs& a, bool stats, hipStrea
         }
         occ_seed = true;
     }
-    if ((rc = pt_reserve(c, sl.misc, misc_head + occ_bytes))) return rc;
+    // The dark-light records (pt_dark_light_kernel; pt_certain.h 4.-8.) lie between the work queues and the occluder table, PT_DARK_WORDS words per light, zeroed with both:
+    // the flat_scene launches that have an occluder table, so that the kernel finds them from PtRenderArgs::occluders alone. PORTRAYER_DARK_LIGHTS=0 (tests, A/B runs
+    // from one library): the records stay zero - no light is skipped. -DPT_NO_DARK_LIGHTS: no records.
+#ifndef PT_NO_DARK_LIGHTS
+    const size_t dark_bytes = (a.scene.mode == PT_MODE_FLAT_NOMESH && occ_bytes != 0) ? (size_t)a.scene.n_lights * PT_DARK_WORDS * 4 : 0;
+    bool dark_lights = dark_bytes != 0 && a.scene.n_nodes > 0;
+    if (const char* e = getenv("PORTRAYER_DARK_LIGHTS")) if (atoi(e) <= 0) dark_lights = false;
+#else
+    const size_t dark_bytes = 0;
+    const bool dark_lights = false;
+#endif
+    if ((rc = pt_reserve(c, sl.misc, misc_head + dark_bytes + occ_bytes))) return rc;
     if ((rc = pt_reserve(c, sl.accum, (size_t)a.n_slots * a.n_chunks * 3 * sizeof(double)))) return rc;
     a.accum = (double*)sl.accum.p;
     // The eye table of the mesh-free flat_scene semantics (pt_render_simple.h: EYE_TABLE): every launch in that mode gets one, whichever kernel runs - the counting,
@@ -1144,11 +1230,11 @@ static int pt_render_common(pt_context* c, PtRenderArgs& a, bool stats, hipStrea
     a.overflow_flag = (unsigned int*)sl.misc.p + 1;
     a.counters = (PtCounters*)((char*)sl.misc.p + 256);
     a.work_queues = (unsigned int*)((char*)sl.misc.p + 256 + sizeof(PtCounters));
-    a.occluders = occ_bytes ? (uint32_t*)((char*)sl.misc.p + misc_head) : nullptr;
+    a.occluders = occ_bytes ? (uint32_t*)((char*)sl.misc.p + misc_head + dark_bytes) : nullptr;
     a.occ_row = std::max<uint32_t>(a.div_tiles_x.d / std::max<uint32_t>(a.tile_ranks, 1u), 1u);
     c->last_mode = (uint32_t)a.scene.mode;
     c->last_variant = pt_choice_variant(choice, tex) | (stats ? PT_KERNEL_COUNTING : 0u);
-    PT_HIP(c, hipMemsetAsync(sl.misc.p, 0, misc_head + occ_bytes, stream));
+    PT_HIP(c, hipMemsetAsync(sl.misc.p, 0, misc_head + dark_bytes + occ_bytes, stream));
     if (occ_seed) {
         const uint32_t n_occ = (uint32_t)(occ_bytes / 4);
         hipLaunchKernelGGL(pt_occ_seed_kernel, dim3((n_occ + 255) / 256), dim3(256), 0, stream, a.occluders, n_occ, occ_hashed ? 1 : 0, occ_seed_value, occ_all, a.scene.n_nodes);
@@ -1168,6 +1254,14 @@ static int pt_render_common(pt_context* c, PtRenderArgs& a, bool stats, hipStrea
                                (uint32_t)a.scene.n_nodes);
             PT_HIP(c, hipGetLastError());
         }
+#ifndef PT_NO_DARK_LIGHTS
+        if (certain_table && dark_lights) {  // (reads the table the kernel above fills)
+            hipLaunchKernelGGL(pt_dark_light_kernel, dim3((uint32_t)a.scene.n_lights), dim3(256), 0, stream, a.scene.lights, (const float*)((const double*)sl.eye_tab.p + 12 * (size_t)a.scene.n_nodes),
+                               (uint32_t*)((char*)sl.misc.p + misc_head), (uint32_t)a.scene.n_nodes);
+            PT_HIP(c, hipGetLastError());
+        }
+        c->dark_slot = dark_bytes ? slot_index : -1; c->dark_lights = (uint32_t)a.scene.n_lights; c->dark_off = misc_head;
+#endif
         if (list_header) {  // behind the eye table's fill, on the launch's stream: the header, then the slot's records
             uint32_t* const header = (uint32_t*)((char*)sl.eye_tab.p + list_off);
             PT_HIP(c, hipMemsetD32Async((hipDeviceptr_t)header, pixel_lists ? 1 : 0, 16, stream));

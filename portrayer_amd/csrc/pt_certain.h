@@ -116,3 +116,62 @@ PT_HD bool pt_certain_lane(const float* rec, float px, float py, float pz, float
     // (& and not &&: five compares and four scalar ands in a straight line, no branch around three fmas)
     return (vw > 0.0f) & (ww > PT_CERTAIN_WW_MIN) & (s < PT_CERTAIN_S_MAX) & (uu < rec[3]) & (__builtin_ldexpf(s * vw, -PT_CERTAIN_REACH2_LOG2) < rec[3]);
 }
+
+// DARK LIGHTS: a light enclosed in a solid, settled once per launch.
+//
+// A shadow ray runs over [EPSILON, INF): nothing bounds it by the light's distance. A point light L that lies inside a closed convex solid is therefore dark everywhere - the
+// ray from ANY origin toward L passes through the solid and leaves it. THE TABLE (pt_dark_light, once per light and launch, behind pt_certain_ball's): the lowest node whose
+// certain ball encloses L with the margin below, and the bounds of THE LANE GUARD (pt_dark_lane): with P~ = f32(P), L~ = f32(L), w = fl(L~ - P~) and d2 = fl(|w|^2),
+//     PT_DARK_D2_MIN <= d2 <= ceil.   Where it holds in every shaded lane, the light is skipped: no occluder entry, no ball record, no direction, no probe, no walk.
+//
+// 4. The margin. The table's record is {c~, rho~^2}, c~ = f32(c), rho~ <= rho (2.: rho^2 is rounded down twice). pt_dark_light flags L where, in f64,
+//        |L - c~|^2 <= rho~^2 (1 - 2^-6)^2 (1 - 2^-40)     (three products, two sums, relative rounding below 2^-50: the 2^-40 pays for them),
+//    so |L - c| <= rho (1 - 2^-6) + 2^-24 |c|, and with r - rho = 2^-5 r + 2^-10 + 2^-20 |c| (2.) the ball B(L, m'), m' = 2^-6 rho + 2^-5 r + 2^-10, lies inside B(c, r), which lies
+//    inside the primitive up to the 2^-20 r of 2. (e). The reference's ray is {P + t d}, h = fl(L - P), d = fl(h / fl|h|). An f64 difference rounds RELATIVE to its result, so
+//    each h_k is (L_k - P_k)(1 + 2^-53) whatever |L| and |P| are; pt_length and the three divisions add relative 2^-51 at most: d is the exact unit direction turned and
+//    scaled by less than 2^-50. The exact ray therefore passes, at t_q = (L - P) . d > 0, a point Q with |Q - L| <= 2^-50 |L - P|. The guard's ceiling gives |L - P| < 2^12 rho
+//    (5.), so |Q - L| < 2^-38 rho, and B(Q, m), m = 2^-10 + 2^-6 r - the ball 2. ends with - lies inside B(L, m'), with 2^-6 rho and half of the 2^-5 r to spare. The same ceiling
+//    gives |c - P| <= |L - P| + |L - c| < (2^12 + 1) rho: 1.'s bound on |v|, which 2. uses for the f64 rounding of the LOCAL ray (|c| <= 2^19 r is the table's). From here 2. and
+//    3. apply as they stand: the ray leaves the primitive at t_x >= t_q + m >= 97 EPSILON, and the reference's own test reports a hit.
+// 5. The ceiling. |L~ - L| <= eps |L|, |P~ - P| <= eps |P| <= eps (|L| + |L - P|), each w_k rounds by eps |w_k|, d2 by 3 eps relative:
+//        |L - P| <= sqrt(d2) (1 + 2^-21) + 2^-22 |L|.   The table stores  ceil = (2^12 rho~ (1 - 2^-10) - 2^-21 |L|)^2  rounded down to f32 (no flag unless the bracket is positive):
+//    d2 <= ceil gives |L - P| < 2^12 rho. An overflowing d2 is +inf and fails; a NaN fails both comparisons as they are written.
+// 6. The floor. P == L gives the reference h = 0, a NaN direction and so a "lit" verdict: such a lane must take the exact path. d2 >= PT_DARK_D2_MIN = 1e-30 means some
+//    |w_k| >= 5.7e-16 (a normal float: no flushed difference decides), so L~_k != P~_k, and as rounding is a function L_k != P_k IN F64, whatever |L| is. One of |L_k|, |P_k| is
+//    then at least 2.8e-16, and two distinct doubles the larger of which is M differ by at least 2^-53 M: |h_k| >= 3e-32, its square is a normal double, fl|h| > 0 and d is
+//    finite. Nothing else is asked of a short h: 4. holds for every |L - P| > 0 (t_q may be as small as 3e-32; the ray still leaves B(L, m') at least m' ahead of L).
+// 7. Every origin. 4. uses nothing about P but the two bounds of the guard. P outside the solid: the ray enters and leaves it. P inside (a second primitive that cuts the solid, a
+//    camera inside it looking at its inner surface) or ON its surface (the solid's own shaded points, the common case): the ray passes L and leaves the solid beyond it - 3.'s
+//    cases "lo < EPSILON: hi is returned" and "the face the ray leaves through". Points of other nodes are no different: the test is an OR over nodes.
+// 8. Types. Cylinder and cone have no ball (3.), so a light inside one is never flagged and takes the exact path. An AREA light (both area vectors non-zero, the kernel's own
+//    criterion, light.rs:51-53) is never flagged either: its position is drawn per sample.
+#define PT_DARK_D2_MIN 1e-30f
+#define PT_DARK_WORDS 8  // per light, in front of the occluder table: {f32(L).xyz, ceil} - what a lane reads; ceil = 0: not dark - then {node + 1, floor, 0, 0} for the tests
+
+// Does the point light of record `light` (15 doubles: position, colour, falloff, area_a, area_b) certainly lie inside the ball `ball` (pt_certain_ball's record)? out[0..3] =
+// the lane guard's record {f32(L), ceil}; all zero where it does not.
+PT_HD bool pt_dark_light(const double* light, const float* ball, float* out) {
+    out[0] = out[1] = out[2] = out[3] = 0.0f;
+    const bool area = !((light[9] == 0.0 && light[10] == 0.0 && light[11] == 0.0) || (light[12] == 0.0 && light[13] == 0.0 && light[14] == 0.0));
+    if (area) return false;
+    const double rho2 = (double)ball[3];
+    if (!(rho2 > 0.0)) return false;
+    const PtVec3 l = pt_v3(light[0], light[1], light[2]);
+    const PtVec3 d = l - pt_v3((double)ball[0], (double)ball[1], (double)ball[2]);
+    if (!(pt_dot(d, d) <= rho2 * ((1.0 - 0x1p-6) * (1.0 - 0x1p-6) * (1.0 - 0x1p-40)))) return false;
+    const double reach = sqrt(rho2) * (4096.0 * (1.0 - 0x1p-10)) - 0x1p-21 * sqrt(pt_dot(l, l));
+    if (!(reach > 0.0)) return false;
+    const double ceil2 = reach * reach;
+    if (!(ceil2 > 1e-30 && ceil2 < 1e37)) return false;
+    float f = (float)ceil2;
+    if ((double)f > ceil2) f = __builtin_bit_cast(float, __builtin_bit_cast(uint32_t, f) - 1u);  // (a positive normal number: the next float towards 0)
+    out[0] = (float)l.x; out[1] = (float)l.y; out[2] = (float)l.z; out[3] = f;
+    return true;
+}
+
+// One lane: rec = a dark light's record, (px, py, pz) = f32(P). (& and not &&, and the comparisons this way round: a NaN fails)
+PT_HD bool pt_dark_lane(const float* rec, float px, float py, float pz) {
+    const float wx = rec[0] - px, wy = rec[1] - py, wz = rec[2] - pz;
+    const float d2 = __builtin_fmaf(wz, wz, __builtin_fmaf(wy, wy, wx * wx));
+    return (d2 >= PT_DARK_D2_MIN) & (d2 <= rec[3]);
+}

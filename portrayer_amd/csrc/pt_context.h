@@ -86,7 +86,7 @@ struct pt_context {
     // wavefronts retire one by one over the duration of its longest work items (the TAIL: 0.13 ms of a 1.3 ms share of the headline frame, 11 %;
     // profiles/r05/notes.md section 2) - and the next frame's wavefronts take the places they free instead of waiting for the last one.
     struct Slot {
-        PtBuf spill, stack_spill, accum, misc;     // misc: work counter + overflow flag (8 B), PtCounters at +256, the work queues behind them
+        PtBuf spill, stack_spill, accum, misc;     // misc: work counter + overflow flag (8 B), PtCounters at +256, the work queues behind them, then the dark-light records and the occluder table
         PtBuf eye_tab;                             // the launch's eye table (pt_eye_table_kernel): n_nodes x 96 bytes, the slot's own - the other slot's frame has another camera;
                                                    // behind it the launch's certain-shadow table (pt_certain_table_kernel): n_nodes x 16 bytes
         hipStream_t stream = nullptr;              // pt_context_stream(ctx, slot): non-blocking, created with the context
@@ -106,6 +106,9 @@ struct pt_context {
     uint32_t pl_slots = 0;     // ... its pixel slots ...
     size_t pl_off = 0;         // ... where its records start in the buffer ...
     uint32_t pl_nodes = 0;     // ... and the scene's flattened nodes (pt_test_pixel_list_records)
+    int dark_slot = -1;        // pt_test_dark_lights: the slot whose misc buffer holds the last launch's dark-light records (-1: that launch had none) ...
+    uint32_t dark_lights = 0;  // ... the scene's lights ...
+    size_t dark_off = 0;       // ... and where the records start in the buffer (in front of the occluder table)
     // The three passes beside the render, each with a PtPass of its own: all three may be in flight at once, with two renders. Beside it, what is the kind's.
     // The primary-visibility pass (pt_aov / pt_aov_device ... pt_aov_finish): the device copies of the host-buffer path's six outputs.
     // The guides pass (pt_guides ...) runs on the SAME pass - one of the two in flight, one set of stack columns - and its host-buffer path takes position, normal and

@@ -526,13 +526,32 @@ __global__ void __launch_bounds__(PT_BLOCK, WAVES) pt_render_simple_kernel(PtRen
                     if (CHAIN) draw += 2;
                 }
                 if (area) udraw += 2;
-                // the occluder table's entry of this item's tile for this light (pt_trace_packet): mesh-free scenes, primary hits only
-                PtOccRef occ{nullptr, 0u, li};
 #ifdef PT_OCCLUDER_STATS
                 constexpr bool OCC = !CHAIN && (MODE == PT_MODE_FLAT_NOMESH || MODE == PT_MODE_HIER_NOMESH);
 #else
                 constexpr bool OCC = !STATS && !CHAIN && (MODE == PT_MODE_FLAT_NOMESH || MODE == PT_MODE_HIER_NOMESH);
 #endif
+                // A light the launch found enclosed in a node's certain ball (pt_dark_light, pt_certain.h 4.-8.; its record lies in front of the occluder table) is dark from
+                // every origin the lane guard lets through: where every shaded lane passes, the light is skipped before anything is read for it - no occluder entry, no ball,
+                // no direction, no probe, no walk. Otherwise today's code for that light, for all lanes. -DPT_NO_DARK_LIGHTS: the code as it was, and no records. The counting
+                // build of -DPT_OCCLUDER_STATS=2 evaluates the guard and hands the outcome to pt_trace_packet's counts, nothing else.
+                [[maybe_unused]] bool dark = false;
+#if !defined(PT_NO_DARK_LIGHTS)
+                if (OCC && MODE == PT_MODE_FLAT_NOMESH && a.occluders) {
+                    const pt_u32x4 dk = pt_sload4(a.occluders - PT_DARK_WORDS * (size_t)(sc.n_lights - li));
+                    if (dk[3] != 0u) {
+                        float drec[4];
+#pragma unroll
+                        for (int k = 0; k < 4; k++) drec[k] = __builtin_bit_cast(float, (uint32_t)dk[k]);
+                        const bool g = shaded & pt_dark_lane(drec, pt_f32_here(sray.o.x), pt_f32_here(sray.o.y), pt_f32_here(sray.o.z));
+                        const unsigned long long want = PT_BALLOT(shaded);
+                        dark = want != 0ull && PT_BALLOT(g) == want;  // (a wavefront without a shaded lane takes today's path)
+                        if (!STATS && dark) { PT_SEC_END(6); continue; }
+                    }
+                }
+#endif
+                // the occluder table's entry of this item's tile for this light (pt_trace_packet): mesh-free scenes, primary hits only
+                PtOccRef occ{nullptr, 0u, li};
                 if (OCC && a.occluders) {
                     const uint32_t tile_local = pt_fastdiv(w >> (a.k_log2 + a.c_log2), a.div_groups);
                     occ.entry = a.occluders + (size_t)tile_local * sc.n_lights + li;
@@ -544,7 +563,7 @@ __global__ void __launch_bounds__(PT_BLOCK, WAVES) pt_render_simple_kernel(PtRen
                 // code as it was, and no table. The counting build of -DPT_OCCLUDER_STATS=2 evaluates the test and hands the outcome to pt_trace_packet's counts,
                 // nothing else.
                 constexpr bool CERTAIN = OCC && MODE == PT_MODE_FLAT_NOMESH;
-                [[maybe_unused]] PtOccHint hint{0u, 0u, 0u, 0u};
+                [[maybe_unused]] PtOccHint hint{0u, 0u, 0u, (STATS && dark) ? 4u : 0u};
                 if (CERTAIN && occ.entry) {  // (a launch of this mode that has an occluder table has the certain-shadow table: pt_render_common)
                     const float* const certain_tab = (const float*)(a.eye_tab + 12 * (size_t)sc.n_nodes);
                     const uint32_t* const entry = (const uint32_t*)pt_uniform_ptr(occ.entry);
@@ -564,22 +583,9 @@ __global__ void __launch_bounds__(PT_BLOCK, WAVES) pt_render_simple_kernel(PtRen
                             const unsigned long long want = PT_BALLOT(shaded), got = PT_BALLOT(c1);
                             bool settled = want != 0ull && got == want;  // (a wavefront without a shaded lane writes no entry, like the probe)
                             if (settled) {
-                                hint.certain = 3u;
+                                hint.certain |= 3u;
                                 if (!STATS && hint.own != cand && lane == (unsigned)(__ffsll((long long)__ballot(1)) - 1)) occ.entry[0] = cand;
                             }
-#if PT_OCCLUDER_STATS + 0 == 2  // (the ball of the tile above for the lanes `own`'s leaves open: counted only - 6 % more walks than the first ball settles, profiles/r09/notes.md - and not built)
-                            else if (hint.own != 0u && hint.up != 0u && hint.up != hint.own) {
-                                const pt_u32x4 rec2 = pt_sload4(certain_tab + 4 * (size_t)(hint.up - 1u));
-                                float ball2[4];
-#pragma unroll
-                                for (int k = 0; k < 4; k++) ball2[k] = __builtin_bit_cast(float, (uint32_t)rec2[k]);
-                                if (ball2[3] > 0.0f) {
-                                    const bool c2 = shaded && !c1 && pt_certain_lane(ball2, pf[0], pf[1], pf[2], lx, ly, lz);
-                                    settled = want != 0ull && (got | PT_BALLOT(c2)) == want;
-                                    if (settled) hint.certain = 2u;
-                                }
-                            }
-#endif
                             if (!STATS && settled) { PT_SEC_END(6); continue; }  // (PT_CYCLES builds count STATS instantiations only, which never get here)
                         }
                     }

@@ -745,7 +745,7 @@ struct PtOccRef {
 };
 
 // What the caller has read of the table already (the certain-shadow test in front of a light's set-up, pt_render_simple_kernel): `loaded` != 0: the two entries
-// (`own`, `up`). `certain` (the -DPT_OCCLUDER_STATS=2 counts only): bit 0 every shaded lane is certain by the candidate's ball, bit 1 by the two entries' balls together.
+// (`own`, `up`). `certain` (the -DPT_OCCLUDER_STATS=2 counts only): bit 0 (and 1) every shaded lane is certain by the candidate's ball, bit 2 the dark-light guard lets every shaded lane through.
 struct PtOccHint {
     uint32_t loaded, own, up, certain;
 };
@@ -797,9 +797,14 @@ PT_HD void pt_trace_packet_occ(const PtSceneView& sc, const PtRay& ray, bool has
         // own tile), diag[7]: walks in which the candidate blocked a lane (low)
         cnt->diag[2 * occ.light] += 1ull | (hit_mask ? 1ull << 32 : 0ull);
         if (hit_mask == rays) cnt->diag[2 * occ.light + 1] += 1ull | (blocked_mask == rays ? 1ull << 32 : 0ull);
-#if PT_OCCLUDER_STATS + 0 == 2  // diag[6]: per light (21 bits each) the walks the candidate alone ends in which its ball settles every lane; diag[7]: the fully blocked walks the two entries' balls settle
+#if PT_OCCLUDER_STATS + 0 == 2  // diag[6]: per light (21 bits each) the walks the candidate alone ends in which its ball settles every lane; diag[7]: the fully blocked walks the dark-light
+        // guard (pt_dark_lane, hint.certain bit 2) settles. A walk it would settle in which some lane is NOT blocked would be a wrong skip: counted in kd_plane_miss, which no
+        // walk of this semantics touches, and must stay 0 (profiles/occluder_stats.py checks it).
         if (hit_mask == rays && blocked_mask == rays && (hint.certain & 1u)) cnt->diag[6] += 1ull << (21 * occ.light);
-        if (hit_mask == rays && (hint.certain & 2u)) cnt->diag[7] += 1ull << (21 * occ.light);
+        if (hint.certain & 4u) {
+            if (hit_mask == rays) cnt->diag[7] += 1ull << (21 * occ.light);
+            else cnt->kd_plane_miss++;
+        }
 #else
         if (cand) cnt->diag[6] += 1ull | (own ? 1ull << 32 : 0ull);
         if (blocked_mask) cnt->diag[7]++;

@@ -8,9 +8,11 @@ usage (GPU box, repo root): python3 profiles/occluder_stats.py build/variants/oc
 With a third argument `certain` the build is one of
   make variant NAME=occstats2 EXTRA_HIPFLAGS=-DPT_OCCLUDER_STATS=2
 whose diag[6] and diag[7] count instead, per light in 21 bits each (so fewer than 2,097,152 walks per light: checked), what the certain-shadow test (pt_certain.h)
-would settle: of the walks the candidate alone ends, those in which its inscribed ball settles every shaded lane; and of ALL fully blocked walks, those the balls
-of the tile's own entry and of the tile above settle together. The counting walk is unchanged there as well (flat only: the hierarchical semantics has no table)."""
-import os, shutil, sys, tempfile, json
+would settle: of the walks the candidate alone ends, those in which its inscribed ball settles every shaded lane; and of ALL fully blocked walks, those the dark-light
+guard (a light the launch found enclosed in a node's ball, pt_certain.h 4.-8.) settles before anything is read for the light. A walk the guard would settle in which some
+lane is NOT blocked would be a wrong skip: the build counts those apart, and this script fails unless there are none. The launch's per-light records are printed too.
+The counting walk is unchanged there as well (flat only: the hierarchical semantics has no table)."""
+import ctypes, os, shutil, sys, tempfile, json
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 tmp = tempfile.mkdtemp()
 shutil.copytree(os.path.join(ROOT, "portrayer_amd"), os.path.join(tmp, "portrayer_amd"), ignore=shutil.ignore_patterns("csrc", "host"))
@@ -24,6 +26,13 @@ sc = host.Scene.example("big-scene", assets=ASSETS)
 r = host.Renderer(sc, H.TRAVERSE_HIER if mode == "hier" else H.TRAVERSE_FLAT)
 w, h = 1920, 1080
 _, _, st = r.render(sc.camera, w, h, default_background(w, h), samples=64, seed=0, sample_mode=H.SAMPLE_RNG, stats=True, want_linear=False)
+dark_nodes = None
+if len(sys.argv) > 3 and sys.argv[3] == "certain":
+    info = (ctypes.c_uint64 * 2)()
+    assert H.lib().pt_test_dark_lights(r.context, None, 0, info) == 0 and info[0] == 3 and info[1] == 8
+    words = (ctypes.c_uint32 * 24)()
+    assert H.lib().pt_test_dark_lights(r.context, words, 24, info) == 0
+    dark_nodes = [int(words[8 * l + 4]) - 1 for l in range(3)]  # the flattened node the light is enclosed in; -1: none
 r.close()
 d = st["diag"]
 lo = lambda x: x & 0xFFFFFFFF
@@ -35,7 +44,12 @@ if len(sys.argv) > 3 and sys.argv[3] == "certain":
     for l in range(3):
         assert out["lights"][l]["walks"] < (1 << 21), "a 21-bit field would overflow"
         out["lights"][l]["candidate_ends_and_its_ball_settles"] = (d[6] >> (21 * l)) & 0x1FFFFF
-        out["lights"][l]["all_occluded_and_two_balls_settle"] = (d[7] >> (21 * l)) & 0x1FFFFF
+        out["lights"][l]["dark_light_guard_settles"] = (d[7] >> (21 * l)) & 0x1FFFFF
+        out["lights"][l]["enclosed_in_node"] = dark_nodes[l]
+        assert out["lights"][l]["dark_light_guard_settles"] <= out["lights"][l]["all_occluded"]
+        assert dark_nodes[l] >= 0 or out["lights"][l]["dark_light_guard_settles"] == 0
+    out["settled_with_a_lane_unblocked"] = st["kd_plane_miss"]
+    assert st["kd_plane_miss"] == 0, "the dark-light guard settled a walk in which some lane is not blocked"
 else:
     out["walks_with_candidate"] = lo(d[6]); out["candidate_from_own_tile"] = hi(d[6]); out["candidate_blocked_a_lane"] = d[7]
 print("OCCSTATS " + json.dumps(out), flush=True)

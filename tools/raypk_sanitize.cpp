@@ -93,5 +93,49 @@ int main() {
     if (pt_test_rect_beam(1, cams.data(), nullptr, off.data(), lo.data(), hi.data(), accept_r.data(), bound_r.data(), walk_r.data(), nullptr) == 0) { std::printf("rects = NULL was not refused\n"); return 1; }
     if (pt_test_rect_beam(0, cams.data(), rect.data(), off.data(), lo.data(), hi.data(), accept_r.data(), bound_r.data(), walk_r.data(), nullptr) != 0) { std::printf("rectangles, n = 0 failed\n"); return 1; }
     std::printf("rectangle beam ok: %llu cases, %llu listed\n", (unsigned long long)n, (unsigned long long)listed_r);
+
+    // The dark-light test (pt_test_dark_light): every type tag, ordinary nodes (a scaled identity at a random centre, the light somewhere in or around it) and degenerate
+    // records - zero radius (a zero matrix), NaN and infinite entries, matrices that are no pair, P and L coincident, NaN / infinite / huge P and L, area vectors zero, tiny and NaN.
+    const uint64_t m = 50000;
+    std::vector<double> fwd(12 * m), inv(12 * m), P(3 * m), L(3 * m), area(6 * m);
+    std::vector<int32_t> flagged(m), guard(m), exact(m);
+    uint64_t n_flagged = 0, n_guard = 0;
+    for (int type = 0; type < 8; type++) {
+        for (uint64_t i = 0; i < m; i++) {
+            const double s = std::pow(10.0, e(rng));
+            for (int k = 0; k < 12; k++) fwd[12 * i + k] = inv[12 * i + k] = 0.0;
+            for (int k = 0; k < 3; k++) {
+                const double c = u(rng) * std::pow(10.0, e(rng));
+                fwd[12 * i + 5 * k] = s; fwd[12 * i + 4 * k + 3] = c;
+                inv[12 * i + 5 * k] = 1.0 / s; inv[12 * i + 4 * k + 3] = -c / s;
+                L[3 * i + k] = c + u(rng) * s * 0.7;
+                P[3 * i + k] = (rng() % 4 == 0) ? L[3 * i + k] : L[3 * i + k] + u(rng) * std::pow(10.0, e(rng));
+            }
+            for (int k = 0; k < 6; k++) area[6 * i + k] = (rng() % 3 == 0) ? u(rng) * std::pow(10.0, -50.0 * std::fabs(u(rng))) : 0.0;
+            switch (rng() % 8) {
+                case 0: for (int k = 0; k < 12; k++) fwd[12 * i + k] = inv[12 * i + k] = 0.0; break;  // zero radius
+                case 1: fwd[12 * i + rng() % 12] = odd[rng() % 7]; break;
+                case 2: inv[12 * i + rng() % 12] = odd[rng() % 7]; break;
+                case 3: L[3 * i + rng() % 3] = odd[rng() % 7]; break;
+                case 4: P[3 * i + rng() % 3] = odd[rng() % 7]; break;
+                case 5: area[6 * i + rng() % 6] = odd[rng() % 7]; break;
+                default: break;
+            }
+        }
+        rc = pt_test_dark_light(m, type, fwd.data(), inv.data(), P.data(), L.data(), (type & 1) ? nullptr : area.data(), flagged.data(), guard.data(), exact.data());
+        if (rc != 0) { std::printf("pt_test_dark_light(type %d) returned %d\n", type, rc); return 1; }
+        for (uint64_t i = 0; i < m; i++) {
+            n_flagged += (uint64_t)flagged[i]; n_guard += (uint64_t)guard[i];
+            if (guard[i] && !flagged[i]) { std::printf("type %d case %llu: the guard without the flag\n", type, (unsigned long long)i); return 1; }
+            if (flagged[i] && type != 0 && type != 5) { std::printf("type %d case %llu: flagged without a ball\n", type, (unsigned long long)i); return 1; }
+            if (guard[i] && P[3 * i] == L[3 * i] && P[3 * i + 1] == L[3 * i + 1] && P[3 * i + 2] == L[3 * i + 2]) { std::printf("type %d case %llu: P == L through the guard\n", type, (unsigned long long)i); return 1; }
+            if (guard[i] && !exact[i]) { std::printf("type %d case %llu: skipped without an exact hit\n", type, (unsigned long long)i); return 1; }
+        }
+    }
+    if (pt_test_dark_light(1, 8, fwd.data(), inv.data(), P.data(), L.data(), nullptr, flagged.data(), guard.data(), exact.data()) == 0) { std::printf("type 8 was not refused\n"); return 1; }
+    if (pt_test_dark_light(1, 0, fwd.data(), inv.data(), P.data(), nullptr, nullptr, flagged.data(), guard.data(), exact.data()) == 0) { std::printf("L = NULL was not refused\n"); return 1; }
+    if (pt_test_dark_light(0, 0, fwd.data(), inv.data(), P.data(), L.data(), nullptr, flagged.data(), guard.data(), exact.data()) != 0) { std::printf("dark light, n = 0 failed\n"); return 1; }
+    if (n_flagged == 0 || n_guard == 0) { std::printf("dark light: nothing flagged\n"); return 1; }
+    std::printf("dark light ok: %llu cases x 8 types, %llu flagged, %llu through the guard\n", (unsigned long long)m, (unsigned long long)n_flagged, (unsigned long long)n_guard);
     return 0;
 }
