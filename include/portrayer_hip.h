@@ -633,6 +633,66 @@ int pt_direct_finish(pt_context *ctx, double *kernel_ms);
 int pt_test_direct_host(uint64_t n, const pt_direct_params *params, const double *positions, const double *normals, uint32_t n_lights, const double *lights,
                         double *origins, double *directions, double *t_max, double *terms, uint8_t *valid);
 
+/* ---- Probe: the light field at a point in FREE SPACE - what lights a character, a prop or a particle that moves through a baked scene - as the nine order-2
+ * spherical-harmonic (SH) sums of `samples` shaded radiance samples over the whole sphere about the point. pt_gather needs a normal and samples one hemisphere by
+ * cosine with at most 64 rays; a caller who wants probes would make the sphere's rays on the host, ship 48 bytes per ray up through pt_radiance, pull 24 back and
+ * project there. This pass does it on the device: PROBES in - n positions, n x 3 f64 in world space, no normals - and per probe 27 sums out. No ray and no
+ * per-ray colour is ever in memory: 24 bytes per probe in, at most 217 out.
+ * The result is a CONTRACT, a fixed sequence of correctly rounded f64 operations (+, -, *, /, sqrt; no fused multiply-add) that portrayer_amd/csrc/pt_probe.h
+ * states as the functions the kernel compiles, over the tables of portrayer_amd/csrc/pt_probe_tables.h (tools/gen_probe_tables.py: every entry the exact value
+ * rounded once) - PT_PROBE_DIRS[1024][3], uniform on the sphere: u = the base-2 radical inverse of k + 1/2048, v = Sobol dimension 2 of k + 1/2048, z = 1 - 2 u,
+ * r = sqrt(1 - z z), the entry (r cos 2 pi v, r sin 2 pi v, z), every power-of-two prefix of 64 .. 1024 entries with equally many points per stratum of u and of
+ * v; PT_PROBE_SH[5], the nearest doubles to 1 / (2 sqrt pi), sqrt(3 / (4 pi)), sqrt(15 / (4 pi)), sqrt(5 / (16 pi)), sqrt(15 / (16 pi)) - and pt_ao's PT_AO_ROT.
+ * Probe i has the stream index q = first_index + i, S = samples, and in this order:
+ *   1. valid      the three components of P finite and at most 1e18 in magnitude. An INVALID probe traces nothing, occupies no lane of a walk and reports zeros
+ *                 and valid = 0.
+ *   2. rotation   j = (uint32)(rng(seed, q, pass, draw 0) * 256), (c, s) = PT_AO_ROT[j]; m = (uint32)(rng(seed, q, pass, draw 1) * 1024), the axis
+ *                 N = PT_PROBE_DIRS[m]: every probe turns the table its own way, so neighbouring probes do not share directions.
+ *   3. direction  sample k takes (x, y, z) = PT_PROBE_DIRS[k], then pt_ao's steps 3, 5, 6 and 7 with that N: n = N / sqrt(dot(N, N)); lx = c x - s y,
+ *                 ly = s x + c y, lz = z; the branch-free frame sg = copysign(1, n.z), a = -1 / (sg + n.z), b = (n.x n.y) a, T = (1 + ((sg n.x) n.x) a, sg b,
+ *                 -(sg n.x)), B = (b, sg + (n.y n.y) a, -n.y); d_k = (T lx + B ly) + n lz per component, NOT renormalised. The origin is P itself: no bias, no
+ *                 face-eye step.
+ *   4. radiance   rgb_k = what pt_radiance answers for the ray (P, d_k) with `background` (3 doubles: what a ray that leaves the scene brings back), the
+ *                 generator's stream (seed, q * S + k, sample = pass), draws 2, 3, ... - that definition taken over whole, as pt_gather takes it. q * S + k is
+ *                 a 64-bit product, reduced modulo 2^64 only.
+ *   5. basis      with d = d_k and c0 .. c4 = PT_PROBE_SH, every product left to right: Y0 = c0, Y1 = c1 d.y, Y2 = c1 d.z, Y3 = c1 d.x, Y4 = (c2 d.x) d.y,
+ *                 Y5 = (c2 d.y) d.z, Y6 = c3 ((3 d.z) d.z - 1), Y7 = (c2 d.x) d.z, Y8 = c4 (d.x d.x - d.y d.y).
+ *   6. sum        for coefficient i and channel c, per round r of 64 samples: the partial sum starts from 0 and adds Y_i(d_k) * rgb_k[c] for k = 64 r ..
+ *                 64 r + 63 ascending; sh[i][c] is round 0's partial plus the later rounds' partials in ascending r, left to right.
+ * Outputs per probe, each OPTIONAL (NULL = not wanted), at least one:
+ *   sh     n x 9 x 3  f64  step 6. The estimate of SH coefficient i of channel c is sh[i][c] x 4 pi / S: that scaling is the caller's.
+ *   valid  n          u8   step 1
+ * Consequences: the bits do not depend on how a batch is cut - a slice [k, k + m) submitted with first_index + k equals that slice of the whole - nor on the
+ * schedule; and the pass equals pt_radiance on pt_test_probe_host's rays, flattened probe-major, with stream_base = first_index * S and sample = pass, weighted
+ * and added in step 6's order. Another `pass` gives other rotations and other draws: a caller sums passes.
+ * The pass runs on the RADIANCE pass object and its work buffers, as pt_gather does: pt_probe_device is closed by pt_probe_finish, which is pt_radiance_finish,
+ * and while a pt_radiance_device / pt_film_add_device / pt_film_add_map_device / pt_gather_device / pt_probe_device pass is open a second one of any kind is
+ * PT_ERR_ARGUMENT. With S > 64 the partial sums of a probe's rounds wait in a scratch of the pass, at most 32 MiB: a call with more probes than that holds runs
+ * as several launches inside the one open pass, which the first consequence makes invisible.
+ * Errors, before the first HIP call: PT_ERR_ARGUMENT (a NULL context / params / positions / background / buffers; no buffer asked for; n > PT_PROBE_MAX; samples
+ * not 64, 128, 256, 512 or 1024), PT_ERR_NO_SCENE. n = 0 is PT_OK: nothing is launched or written. During the pass: PT_ERR_TRAVERSAL as for a render. */
+#define PT_PROBE_MAX (PT_RAYS_MAX / 1024)   /* probes per call (2^20): PT_RAYS_MAX rays at 1024 samples */
+typedef struct {
+    uint64_t n;             /* probes, <= PT_PROBE_MAX                                               */
+    uint32_t samples;       /* rays per probe: 64, 128, 256, 512 or 1024                             */
+    uint32_t pass;          /* which rotation a probe draws, and the `sample` of its streams         */
+    uint64_t seed;
+    uint64_t first_index;   /* stream index of probe 0                                               */
+} pt_probe_params;
+typedef struct { double *sh; uint8_t *valid; } pt_probe_buffers;
+/* Host buffers, synchronous: uploads the positions, copies back the buffers asked for. kernel_ms (optional): device time of the pass (HIP events). */
+int pt_probe(pt_context *ctx, const pt_probe_params *params, const double *positions, const double *background, const pt_probe_buffers *host_out, double *kernel_ms);
+/* The same with positions and results in DEVICE memory, queued on `hip_stream` (a hipStream_t, or NULL for the default stream) without synchronising the host.
+ * `background` stays a HOST pointer to 3 doubles: it is read during the call and travels in the kernel's argument block. */
+int pt_probe_device(pt_context *ctx, const pt_probe_params *params, const double *d_positions, const double *background, const pt_probe_buffers *device_out,
+                    void *hip_stream);
+int pt_probe_finish(pt_context *ctx, double *kernel_ms);
+/* Test hooks, no context and no GPU. pt_test_probe_host: steps 1 to 5 on the host, by the functions the kernel compiles: origins and directions n x samples x 3,
+ * basis n x samples x 9 (Y0 .. Y8), valid n; an invalid probe's rays and basis values are zeros. PT_ERR_ARGUMENT for a NULL pointer or samples the pass refuses.
+ * pt_test_probe_tables: the tables as the library holds them (dirs 1024 x 3, sh 5). */
+int pt_test_probe_host(uint64_t n, const pt_probe_params *params, const double *positions, double *origins, double *directions, double *basis, uint8_t *valid);
+int pt_test_probe_tables(double *dirs, double *sh);
+
 /* ---- Chart: the texels of a mesh's light map as SURFACE POINTS - what pt_ao and pt_gather take (a position and a normal, 48 bytes), made on the device from
  * what is resident there: the triangle records (kept current by pt_scene_deform and pt_scene_deform_device), the node's composed matrices (kept current by
  * pt_scene_update) and a UV set. It does for surfaces what pt_aov does for cameras: behind pt_chart_device on the same stream pt_ao_device / pt_gather_device

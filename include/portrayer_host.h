@@ -218,6 +218,12 @@ int ph_renderer_direct_camera(ph_renderer *r, const double camera[10], uint32_t 
 int ph_renderer_direct_chart(ph_renderer *r, const pt_chart_params *chart, const double *uv, const pt_direct_params *params, const pt_direct_buffers *out,
                              double *kernel_ms);
 
+/* Light probes at points in free space (see pt_probe): n x 3 f64 positions in world space, no normals, `background` 3 doubles, host buffers out, each optional:
+ * per probe the nine order-2 spherical-harmonic sums (9 x 3 f64) of `samples` shaded samples over the whole sphere. A renderer spread over a node runs the pass
+ * on rank 0's context. n = 0 is PH_OK. */
+int ph_renderer_probe(ph_renderer *r, const pt_probe_params *params, const double *positions, const double *background, const pt_probe_buffers *out,
+                      double *kernel_ms);
+
 /* Radiance along rays of the caller's own (see pt_radiance): n x 3 f64 origins and directions in world space, `background` 3 doubles or n x 3
  * (params->background_per_ray), rgb n x 3 f64 out: one linear sample of Ray::color per ray. A renderer spread over a node runs the pass on rank 0's context. */
 int ph_renderer_radiance(ph_renderer *r, const pt_radiance_params *params, const double *origins, const double *directions, const double *background, double *rgb,

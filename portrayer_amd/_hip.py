@@ -163,6 +163,23 @@ class PtGatherBuffers(C.Structure):
 GATHER_BUFFERS = {"sum": (np.float64, 3), "valid": (np.uint8, 1)}
 
 
+class PtProbeParams(C.Structure):
+    """pt_probe_params: the probes of one call and what fixes their rays and draws - samples per probe, pass, seed, first_index. No normal, no bias: a probe is a
+    point in free space and its rays cover the sphere."""
+    _fields_ = [("n", C.c_uint64), ("samples", C.c_uint32), ("pass_index", C.c_uint32), ("seed", C.c_uint64), ("first_index", C.c_uint64)]
+
+
+class PtProbeBuffers(C.Structure):
+    """pt_probe_buffers: sh (n, 9, 3) f64, valid (n,) u8; each optional."""
+    _fields_ = [("sh", _dp), ("valid", _u8p)]
+
+
+# pt_probe's outputs in the order of pt_probe_buffers: name -> (numpy dtype, trailing shape per probe)
+PROBE_BUFFERS = {"sh": (np.float64, (9, 3)), "valid": (np.uint8, ())}
+PROBE_MAX = RAYS_MAX // 1024  # PT_PROBE_MAX
+PROBE_SAMPLES = (64, 128, 256, 512, 1024)
+
+
 class PtDirectParams(C.Structure):
     """pt_direct_params: the points of one direct-light call and what fixes their shadow rays - samples per area light, pass, seed, first_index, bias, and the
     flags AO_FACE_EYE (with the eye every normal is first turned towards) and DIRECT_TO_LIGHT. pt_ao_params without the radius."""
@@ -263,7 +280,8 @@ EXPORTS = ["pt_abi_version", "pt_device_count", "pt_context_create", "pt_context
            "pt_ao", "pt_ao_device", "pt_ao_finish", "pt_test_ao_rays_host", "pt_test_ao_tables",
            "pt_gather", "pt_gather_device", "pt_gather_finish", "pt_test_kernel_choice",
            "pt_chart_triangles", "pt_chart", "pt_chart_device", "pt_test_chart_host",
-           "pt_direct", "pt_direct_device", "pt_direct_finish", "pt_test_direct_host"]
+           "pt_direct", "pt_direct_device", "pt_direct_finish", "pt_test_direct_host",
+           "pt_probe", "pt_probe_device", "pt_probe_finish", "pt_test_probe_host", "pt_test_probe_tables"]
 
 
 def header_functions():
@@ -450,6 +468,16 @@ def lib() -> C.CDLL:
         l.pt_direct_device.argtypes = [C.c_void_p, C.POINTER(PtDirectParams), C.c_void_p, C.c_void_p, C.POINTER(PtDirectBuffers), C.c_void_p]
         l.pt_direct_finish.restype = C.c_int
         l.pt_direct_finish.argtypes = [C.c_void_p, _dp]
+        l.pt_probe.restype = C.c_int
+        l.pt_probe.argtypes = [C.c_void_p, C.POINTER(PtProbeParams), _dp, _dp, C.POINTER(PtProbeBuffers), _dp]
+        l.pt_probe_device.restype = C.c_int
+        l.pt_probe_device.argtypes = [C.c_void_p, C.POINTER(PtProbeParams), C.c_void_p, _dp, C.POINTER(PtProbeBuffers), C.c_void_p]
+        l.pt_probe_finish.restype = C.c_int
+        l.pt_probe_finish.argtypes = [C.c_void_p, _dp]
+        l.pt_test_probe_host.restype = C.c_int
+        l.pt_test_probe_host.argtypes = [C.c_uint64, C.POINTER(PtProbeParams), _dp, _dp, _dp, _dp, _u8p]
+        l.pt_test_probe_tables.restype = C.c_int
+        l.pt_test_probe_tables.argtypes = [_dp, _dp]
         l.pt_test_direct_host.restype = C.c_int
         l.pt_test_direct_host.argtypes = [C.c_uint64, C.POINTER(PtDirectParams), _dp, _dp, C.c_uint32, _dp, _dp, _dp, _dp, _dp, _u8p]
         l.pt_chart_triangles.restype = C.c_int

@@ -14,6 +14,7 @@
 #include "pt_direct_inst.h"
 #include "pt_radiance_inst.h"
 #include "pt_gather_inst.h"
+#include "pt_probe_inst.h"
 #include "pt_film_inst.h"
 #include "pt_film_map_inst.h"
 #include "pt_denoise.h"
@@ -2309,6 +2310,153 @@ extern "C" int pt_gather_device(pt_context* c, const pt_gather_params* p, const 
 
 // The pass is the radiance pass's: one function closes either.
 extern "C" int pt_gather_finish(pt_context* c, double* kernel_ms) { return pt_radiance_finish(c, kernel_ms); }
+
+// ------------------------------------------------------------------------------------------------
+// Probe (pt_probe_inst.hip, pt_probe.hip): the probe contract's rays (pt_probe.h) over a point's whole sphere, shaded, weighted with the order-2 spherical-harmonic
+// basis and summed per probe; a radiance pass for bookkeeping, on that pass's PtPass
+// ------------------------------------------------------------------------------------------------
+static hipError_t pt_probe_dispatch(const PtProbeArgs& a, bool tex, bool park, int n_cu, hipStream_t stream, uint32_t* grid, bool launch) {
+    PT_MODE_LAUNCH(pt_probe_launch_mode_, a.r.scene.mode, a, tex, park, n_cu, stream, grid, launch)
+}
+
+static bool pt_probe_samples_ok(uint32_t s) { return s == 64 || s == 128 || s == 256 || s == 512 || s == 1024; }
+
+// Everything that can be refused without a HIP call, in the order the header gives. (pt_fail takes a NULL context.)
+static int pt_probe_check(pt_context* c, const pt_probe_params* p, const double* positions, const double* background, const pt_probe_buffers* out) {
+    if (!c || !p || !positions || !background || !out) return pt_fail(c, PT_ERR_ARGUMENT, "pt_probe: NULL context, params, positions, background or buffers");
+    if (!(out->sh || out->valid)) return pt_fail(c, PT_ERR_ARGUMENT, "pt_probe: no output buffer asked for");
+    if (p->n > PT_PROBE_MAX) return pt_fail(c, PT_ERR_ARGUMENT, "pt_probe: more than PT_PROBE_MAX probes in one call");
+    if (!pt_probe_samples_ok(p->samples)) return pt_fail(c, PT_ERR_ARGUMENT, "pt_probe: samples must be 64, 128, 256, 512 or 1024");
+    if (!c->have_scene) return pt_fail(c, PT_ERR_NO_SCENE, "no scene uploaded");
+    if (c->radiance.pass.pending)
+        return pt_fail(c, PT_ERR_ARGUMENT, "a pt_radiance_device / pt_film_add_device / pt_gather_device / pt_probe_device pass is in flight: pt_radiance_finish first");
+    return PT_OK;
+}
+
+// The most the pass keeps of partial sums - 216 bytes per (probe, round of 64 samples) - between its kernel and its fold: a call with more runs as several
+// launches. PORTRAYER_PROBE_SCRATCH=<bytes> lowers the bound (tests: a handful of probes across several launches); never below one probe's partials.
+#define PT_PROBE_SCRATCH_BYTES ((size_t)32 << 20)
+static size_t pt_probe_scratch_bound() {
+    size_t bound = PT_PROBE_SCRATCH_BYTES;
+    if (const char* e = getenv("PORTRAYER_PROBE_SCRATCH")) { const long long b = atoll(e); if (b > 0 && (unsigned long long)b < bound) bound = (size_t)b; }
+    return bound;
+}
+
+// Queues the pass on `stream` (pt_pass_open ... pt_pass_seal) as pt_gather_common does and on its PtPass. The position and result pointers are DEVICE pointers,
+// `background` is the caller's HOST colour, copied into the argument block; n > 0. S = 64: one launch, the kernel stores `sh`. S = 64 R, R > 1, with `sh` wanted:
+// per at most `chunk` probes the kernel and the fold of its partials (the queues zeroed again in between; the overflow flag stays: pt_film_add_common) - a
+// launch is a call of its own with first_index moved on, which the contract makes invisible.
+static int pt_probe_common(pt_context* c, const pt_probe_params* p, const double* d_positions, const double* background, const pt_probe_buffers& out, hipStream_t stream) {
+    PtPass& v = c->radiance.pass;
+    int rc = pt_pass_prepare(c, v);
+    if (rc) return rc;
+    PtProbeArgs a;
+    memset(&a, 0, sizeof a);  // (no occluder table, no counters, no work counter: null)
+    a.r.scene = c->view;
+    a.r.seed = p->seed;
+    a.set.seed = p->seed; a.set.pass = p->pass;
+    a.samples = p->samples;
+    while ((64u << a.log2_rounds) < p->samples) a.log2_rounds++;
+    const uint32_t rounds = 1u << a.log2_rounds;
+    for (int k = 0; k < 3; k++) a.background[k] = background[k];
+    const bool fold = rounds > 1 && out.sh;
+    uint64_t chunk = p->n;
+    if (fold) {
+        const size_t per_probe = (size_t)rounds * PT_PROBE_VALUES * sizeof(double);
+        chunk = std::min<uint64_t>(p->n, std::max<size_t>(1, pt_probe_scratch_bound() / per_probe));
+        if ((rc = pt_reserve(c, c->radiance.probe_partial, (size_t)chunk * per_probe))) return rc;
+    }
+    // the buffers are sized for the call's largest launch (its first); the later ones use a prefix of the same lanes
+    auto set_launch = [&](uint64_t first, uint64_t m) {
+        a.n = m;
+        a.positions = d_positions + 3 * first;
+        a.set.first_index = p->first_index + first;  // (modulo 2^64, as the stream index is)
+        a.sh = !fold && out.sh ? out.sh + PT_PROBE_VALUES * first : nullptr;
+        a.partial = fold ? (double*)c->radiance.probe_partial.p : nullptr;
+        a.valid = out.valid ? out.valid + first : nullptr;
+        a.r.n_items = (uint32_t)(m << a.log2_rounds);  // (n <= PT_PROBE_MAX = 2^20, R <= 16: at most 2^24 items)
+    };
+    set_launch(0, chunk);
+    const PtInterp k = pt_interp_sizing(c, a.r);
+    uint32_t grid = 0;
+    PT_HIP(c, pt_probe_dispatch(a, k.tex, k.park, c->n_cu, stream, &grid, false));
+    if ((rc = pt_pass_open(c, v, a.r, grid, true, stream))) return rc;
+    for (uint64_t first = 0; first < p->n; first += chunk) {
+        const uint64_t m = std::min<uint64_t>(chunk, p->n - first);
+        set_launch(first, m);
+        if (first) PT_HIP(c, hipMemsetAsync((char*)v.misc.p + 256, 0, PT_PASS_MISC_BYTES - 256, stream));  // the queues again; the overflow flag stays
+        uint32_t g = 0;
+        PT_HIP(c, pt_probe_dispatch(a, k.tex, k.park, c->n_cu, stream, &g, true));  // (g <= grid: no more items than the launch the buffers were sized for)
+        if (fold) PT_HIP(c, pt_probe_fold_launch(a.partial, out.sh + PT_PROBE_VALUES * first, m, rounds, stream));
+    }
+    return pt_pass_seal(c, v);
+}
+
+extern "C" int pt_probe(pt_context* c, const pt_probe_params* p, const double* positions, const double* background, const pt_probe_buffers* host_out, double* kernel_ms) {
+    int rc = pt_probe_check(c, p, positions, background, host_out);
+    if (rc) return rc;
+    if (kernel_ms) *kernel_ms = 0.0;
+    if (p->n == 0) return PT_OK;
+    PT_HIP(c, hipSetDevice(c->device));
+    pt_context::Radiance& v = c->radiance;
+    const size_t n = (size_t)p->n, sh_bytes = n * PT_PROBE_VALUES * sizeof(double);
+    // the radiance pass's device copies: positions where it keeps origins, the sums in its output, the flags where its background goes
+    if ((rc = pt_reserve(c, v.in[0], n * 24))) return rc;
+    if (host_out->sh && (rc = pt_reserve(c, v.out, sh_bytes))) return rc;
+    if (host_out->valid && (rc = pt_reserve(c, v.in[2], n))) return rc;
+    PT_HIP(c, hipMemcpy(v.in[0].p, positions, n * 24, hipMemcpyHostToDevice));
+    pt_probe_buffers d_out;
+    d_out.sh = host_out->sh ? (double*)v.out.p : nullptr;
+    d_out.valid = host_out->valid ? (uint8_t*)v.in[2].p : nullptr;
+    rc = pt_probe_common(c, p, (const double*)v.in[0].p, background, d_out, nullptr);
+    if ((rc = pt_pass_settle(c, v.pass, rc))) return rc;
+    if (host_out->sh) PT_HIP(c, hipMemcpy(host_out->sh, d_out.sh, sh_bytes, hipMemcpyDeviceToHost));
+    if (host_out->valid) PT_HIP(c, hipMemcpy(host_out->valid, d_out.valid, n, hipMemcpyDeviceToHost));
+    return pt_pass_result(c, v.pass, kernel_ms);
+}
+
+extern "C" int pt_probe_device(pt_context* c, const pt_probe_params* p, const double* d_positions, const double* background, const pt_probe_buffers* device_out,
+                               void* hip_stream) {
+    int rc = pt_probe_check(c, p, d_positions, background, device_out);
+    if (rc) return rc;
+    if (p->n == 0) return PT_OK;  // nothing queued, nothing to finish
+    PT_HIP(c, hipSetDevice(c->device));
+    return pt_pass_device_tail(c, c->radiance.pass, pt_probe_common(c, p, d_positions, background, *device_out, (hipStream_t)hip_stream));
+}
+
+// The pass is the radiance pass's: one function closes either.
+extern "C" int pt_probe_finish(pt_context* c, double* kernel_ms) { return pt_radiance_finish(c, kernel_ms); }
+
+// Steps 1 to 5 of the contract on the host: pt_probe_valid, pt_probe_dir and pt_probe_basis as this translation unit's host pass compiles them
+// (-ffp-contract=off). Zeros for an invalid probe.
+extern "C" int pt_test_probe_host(uint64_t n, const pt_probe_params* p, const double* positions, double* origins, double* directions, double* basis, uint8_t* valid) {
+    if (!p || !positions || !origins || !directions || !basis || !valid) return PT_ERR_ARGUMENT;
+    if (!pt_probe_samples_ok(p->samples)) return PT_ERR_ARGUMENT;
+    PtProbeSet set;
+    set.seed = p->seed; set.first_index = p->first_index; set.pass = p->pass;
+    for (uint64_t i = 0; i < n; i++) {
+        const PtVec3 P = pt_v3(positions[3 * i], positions[3 * i + 1], positions[3 * i + 2]);
+        valid[i] = pt_probe_valid(P) ? 1 : 0;
+        for (uint32_t k = 0; k < p->samples; k++) {
+            PtVec3 o = pt_v3(0.0, 0.0, 0.0), d = o;
+            double Y[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+            if (valid[i]) { o = P; d = pt_probe_dir(set, p->first_index + i, k); pt_probe_basis(d, Y); }
+            double* oo = origins + 3 * (i * p->samples + k);
+            double* dd = directions + 3 * (i * p->samples + k);
+            oo[0] = o.x; oo[1] = o.y; oo[2] = o.z;
+            dd[0] = d.x; dd[1] = d.y; dd[2] = d.z;
+            memcpy(basis + 9 * (i * p->samples + k), Y, sizeof Y);
+        }
+    }
+    return PT_OK;
+}
+
+extern "C" int pt_test_probe_tables(double* dirs, double* sh) {
+    if (!dirs || !sh) return PT_ERR_ARGUMENT;
+    memcpy(dirs, PT_PROBE_DIRS, sizeof PT_PROBE_DIRS);
+    memcpy(sh, PT_PROBE_SH, sizeof PT_PROBE_SH);
+    return PT_OK;
+}
 
 // ------------------------------------------------------------------------------------------------
 // Film: samples accumulate on the device (pt_film.h, pt_film.hip)

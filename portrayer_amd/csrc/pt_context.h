@@ -131,11 +131,12 @@ struct pt_context {
         PtRaySort sort;
     } rays;
     // The radiance pass (pt_radiance / pt_radiance_device ... pt_radiance_finish), which a film's passes share: the device copies of the host-buffer path's three
-    // inputs and its output.
+    // inputs and its output. probe_partial: the probe pass's partial sums between its kernel and its fold (pt_probe_common), at most 32 MiB.
     struct Radiance {
         PtPass pass;
         PtBuf in[3], out;
         PtRaySort sort;
+        PtBuf probe_partial;
     } radiance;
     PtPass* const passes[3] = {&aov.pass, &rays.pass, &radiance.pass};
     // Films (pt_film_create): each owns its device state; a film pass is a radiance pass for bookkeeping (pt_film_add_device), film_open names the film of the

@@ -19,7 +19,7 @@ _dp, _ip, _up, _u64p, _u8p = H._dp, H._ip, H._up, H._u64p, H._u8p
 
 EXPORTS = ["ph_last_error", "ph_scene_create", "ph_example_scene", "ph_scene_destroy", "ph_scene_counts", "ph_scene_export", "ph_scene_export_textures",
            "ph_scene_flatten", "ph_scene_kdtree", "ph_scene_kdmesh_tree", "ph_camera", "ph_obj_load", "ph_renderer_create", "ph_renderer_destroy",
-           "ph_renderer_context", "ph_renderer_ranks", "ph_renderer_node", "ph_renderer_prepare_ms", "ph_renderer_render", "ph_renderer_aov", "ph_renderer_rays", "ph_renderer_segments", "ph_renderer_ao", "ph_renderer_ao_camera", "ph_renderer_gather", "ph_renderer_gather_camera", "ph_renderer_chart_triangles", "ph_renderer_chart_mesh", "ph_renderer_chart", "ph_renderer_ao_chart", "ph_renderer_gather_chart", "ph_renderer_direct", "ph_renderer_direct_camera", "ph_renderer_direct_chart", "ph_renderer_radiance", "ph_renderer_film_create", "ph_renderer_film_destroy", "ph_renderer_film_reset", "ph_renderer_film_add", "ph_renderer_film_resolve", "ph_renderer_film_counts", "ph_renderer_film_create_moments", "ph_renderer_film_add_map", "ph_renderer_film_error", "ph_renderer_film_refine", "ph_renderer_film_denoise", "ph_renderer_guides", "ph_renderer_film_denoise_albedo", "ph_renderer_update", "ph_scene_same_structure", "ph_renderer_deform", "ph_scene_same_topology", "ph_renderer_deform_device", "ph_renderer_mesh_count", "ph_renderer_mesh_vertices", "ph_example_render_to_png", "ph_png_read", "ph_png_write", "ph_image_read", "ph_scene_graph"]
+           "ph_renderer_context", "ph_renderer_ranks", "ph_renderer_node", "ph_renderer_prepare_ms", "ph_renderer_render", "ph_renderer_aov", "ph_renderer_rays", "ph_renderer_segments", "ph_renderer_ao", "ph_renderer_ao_camera", "ph_renderer_gather", "ph_renderer_gather_camera", "ph_renderer_probe", "ph_renderer_chart_triangles", "ph_renderer_chart_mesh", "ph_renderer_chart", "ph_renderer_ao_chart", "ph_renderer_gather_chart", "ph_renderer_direct", "ph_renderer_direct_camera", "ph_renderer_direct_chart", "ph_renderer_radiance", "ph_renderer_film_create", "ph_renderer_film_destroy", "ph_renderer_film_reset", "ph_renderer_film_add", "ph_renderer_film_resolve", "ph_renderer_film_counts", "ph_renderer_film_create_moments", "ph_renderer_film_add_map", "ph_renderer_film_error", "ph_renderer_film_refine", "ph_renderer_film_denoise", "ph_renderer_guides", "ph_renderer_film_denoise_albedo", "ph_renderer_update", "ph_scene_same_structure", "ph_renderer_deform", "ph_scene_same_topology", "ph_renderer_deform_device", "ph_renderer_mesh_count", "ph_renderer_mesh_vertices", "ph_example_render_to_png", "ph_png_read", "ph_png_write", "ph_image_read", "ph_scene_graph"]
 
 
 class PortrayerHostError(RuntimeError):
@@ -105,6 +105,8 @@ def lib() -> C.CDLL:
         l.ph_renderer_chart_mesh.argtypes = [vp, C.c_uint32, _u64p, C.c_uint32, _up]
         l.ph_renderer_chart.restype = C.c_int
         l.ph_renderer_chart.argtypes = [vp, C.POINTER(H.PtChartParams), _dp, C.POINTER(H.PtChartBuffers), _dp]
+        l.ph_renderer_probe.restype = C.c_int
+        l.ph_renderer_probe.argtypes = [vp, C.POINTER(H.PtProbeParams), _dp, _dp, C.POINTER(H.PtProbeBuffers), _dp]
         l.ph_renderer_direct.restype = C.c_int
         l.ph_renderer_direct.argtypes = [vp, C.POINTER(H.PtDirectParams), _dp, _dp, C.POINTER(H.PtDirectBuffers), _dp]
         l.ph_renderer_direct_camera.restype = C.c_int
@@ -336,6 +338,29 @@ def load_obj(path: str):
     pos, nrm, idx = np.zeros((nv, 3)), np.zeros((nv, 3)), np.zeros((nt, 3), dtype=np.uint32)
     _check(lib().ph_obj_load(path.encode(), _p(c, _u64p), _p(pos, _dp), _p(nrm, _dp), _p(idx, _up), nv, nt), "ph_obj_load")
     return pos, (nrm if hn else None), idx
+
+
+def sh_basis(directions) -> np.ndarray:
+    """The nine real spherical harmonics to order 2 at unit `directions` (..., 3), in probe()'s order: 1, y, z, x, xy, yz, 3 z^2 - 1, xz, x^2 - y^2, each with its
+    constant. Plain numpy (the device's own values are the probe contract's: pt_test_probe_host)."""
+    d = np.asarray(directions, dtype=np.float64)
+    if d.ndim < 1 or d.shape[-1] != 3:
+        raise ValueError("directions must be (..., 3), got shape %r" % (d.shape,))
+    x, y, z = d[..., 0], d[..., 1], d[..., 2]
+    c0, c1, c2 = 0.5 / np.sqrt(np.pi), np.sqrt(3.0 / (4.0 * np.pi)), np.sqrt(15.0 / (4.0 * np.pi))
+    c3, c4 = np.sqrt(5.0 / (16.0 * np.pi)), np.sqrt(15.0 / (16.0 * np.pi))
+    return np.stack([np.full_like(x, c0), c1 * y, c1 * z, c1 * x, c2 * x * y, c2 * y * z, c3 * (3.0 * z * z - 1.0), c2 * x * z, c4 * (x * x - y * y)], axis=-1)
+
+
+def sh_irradiance(coeffs, normals) -> np.ndarray:
+    """Irradiance from order-2 SH radiance coefficients - probe()'s `coeffs`, (..., 9, 3) - at unit `normals` (..., 3), the leading shapes broadcast against
+    each other: the coefficients of band l scaled by the cosine lobe's (pi, 2 pi / 3, pi / 4) and the series evaluated at the normal; (..., 3). A constant
+    radiance L has coeffs[0] = 2 sqrt(pi) L and the rest zero, and gives pi L for any normal. Numpy only."""
+    c = np.asarray(coeffs, dtype=np.float64)
+    if c.ndim < 2 or c.shape[-2:] != (9, 3):
+        raise ValueError("coeffs must be (..., 9, 3), got shape %r" % (c.shape,))
+    lobe = np.array([np.pi] + [2.0 * np.pi / 3.0] * 3 + [np.pi / 4.0] * 5)
+    return np.sum((sh_basis(normals) * lobe)[..., :, None] * c, axis=-2)
 
 
 def _device_tensor_pointer(t, shape, device: int, what: str) -> int:
@@ -1169,6 +1194,85 @@ class Renderer:
         _check(lib().ph_renderer_direct_chart(self._h, C.byref(cp), _p(uv, _dp) if uv is not None else None, C.byref(p), C.byref(b), C.byref(ms)),
                "ph_renderer_direct_chart")
         return self._direct_result(out, samples, ms)
+
+    def probe(self, points, background=(0.0, 0.0, 0.0), samples: int = 256, seed: int = 0, pass_index: int = 0, first_index: int = 0, want=("sh",),
+              into: Optional[dict] = None) -> dict:
+        """Light probes at points in free space (pt_probe): `points` is (n, 3) float64 in world space, no normals. The device makes `samples` (64, 128, 256, 512
+        or 1024) rays per probe, uniform over the whole sphere and turned each probe's own way, in registers, shades each as radiance() would - everything
+        render() shades, `background` (three numbers) for a ray that leaves the scene - and sums each colour weighted with the nine order-2 spherical-harmonic
+        basis values of its direction; no ray and no per-ray colour is ever in memory. Returns the arrays named in `want` - `sh` (n, 9, 3) float64: the sums,
+        `valid` (n,) uint8 - with `coeffs` = sh * 4 pi / samples, the estimate of the radiance's SH coefficients (computed here; sh_irradiance(coeffs, normals)
+        lights a surface from them), where `sh` was asked for, and `kernel_ms`. A probe with a non-finite component or one beyond 1e18 is invalid: zeros,
+        valid 0. The bits are those of radiance() on the contract's rays (pt_test_probe_host), flattened probe-major, with stream_base = first_index * samples
+        and sample = pass_index, weighted and summed in the contract's order: a slice [k, k + m) with first_index=k gives that slice of the whole, and another
+        pass_index gives other rays and draws to sum. `into`: a dict of C-contiguous arrays of the right shape and dtype to write into."""
+        P = np.asarray(points)
+        if P.ndim != 2 or P.shape[1] != 3:
+            raise ValueError("points must be (n, 3), got %r" % (P.shape,))
+        if P.dtype != np.float64:
+            raise ValueError("points must be float64, got %s" % (P.dtype,))
+        n = P.shape[0]
+        if isinstance(samples, bool) or not isinstance(samples, (int, np.integer)) or int(samples) not in H.PROBE_SAMPLES:
+            raise ValueError("samples must be one of %r, got %r" % (H.PROBE_SAMPLES, samples))
+        for name, v, top in (("seed", seed, 1 << 64), ("first_index", first_index, 1 << 64), ("pass_index", pass_index, 1 << 32)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) < top:
+                raise ValueError("%s must be an integer in [0, 2^%d), got %r" % (name, top.bit_length() - 1, v))
+        if n > H.PROBE_MAX:
+            raise ValueError("at most %d probes per call" % H.PROBE_MAX)
+        try:
+            bg = np.ascontiguousarray(background, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError("background must be 3 numbers, got %r" % (background,)) from None
+        if bg.shape != (3,):
+            raise ValueError("background must be 3 numbers, got shape %r" % (bg.shape,))
+        if isinstance(want, str):
+            raise ValueError("want must be a sequence of names, got %r" % (want,))
+        want = tuple(want)
+        if not want or [w for w in want if w not in H.PROBE_BUFFERS]:
+            raise ValueError("want must name some of %s, got %r" % (", ".join(H.PROBE_BUFFERS), want))
+        if into is not None and not isinstance(into, dict):
+            raise ValueError("into must be a dict of arrays, got %s" % type(into).__name__)
+        out, b = {}, H.PtProbeBuffers()
+        for name in want:
+            dtype, tail = H.PROBE_BUFFERS[name]
+            full = (n,) + tail
+            a = into[name] if into is not None and name in into else np.zeros(full, dtype=dtype)
+            if not isinstance(a, np.ndarray) or a.shape != full or a.dtype != dtype or not a.flags.c_contiguous:
+                raise ValueError("into[%r] must be a C-contiguous %s array of shape %r" % (name, np.dtype(dtype).name, full))
+            out[name] = a
+            setattr(b, name, _p(a, {np.uint8: _u8p, np.float64: _dp}[dtype]))
+        p = H.PtProbeParams(n, int(samples), int(pass_index), int(seed), int(first_index))
+        P = np.ascontiguousarray(P)
+        ms = C.c_double(0.0)
+        _check(lib().ph_renderer_probe(self._h, C.byref(p), _p(P, _dp), _p(bg, _dp), C.byref(b), C.byref(ms)), "ph_renderer_probe")
+        if "sh" in out:
+            out["coeffs"] = out["sh"] * (4.0 * np.pi / float(samples))  # (zeros at invalid probes)
+        out["kernel_ms"] = ms.value
+        return out
+
+    def probe_grid(self, lo, hi, shape, background=(0.0, 0.0, 0.0), samples: int = 256, seed: int = 0, pass_index: int = 0, first_index: int = 0,
+                   want=("sh",)) -> dict:
+        """Probes on a regular grid: `shape` = (nx, ny, nz) points from corner `lo` to corner `hi` inclusive along each axis (an axis of one point sits at lo),
+        made here in numpy, x slowest and z fastest - probe (i, j, k) has the stream index first_index + (i * ny + j) * nz + k - and handed to probe(). The
+        arrays come back reshaped to shape + (9, 3) (`sh`, `coeffs`) and shape (`valid`), with `points` shape + (3,)."""
+        lo3, hi3 = np.asarray(lo, dtype=np.float64), np.asarray(hi, dtype=np.float64)
+        if lo3.shape != (3,) or hi3.shape != (3,):
+            raise ValueError("lo and hi must be three numbers each, got %r and %r" % (lo, hi))
+        try:
+            dims = tuple(shape)
+        except TypeError:
+            raise ValueError("shape must be three positive integers, got %r" % (shape,)) from None
+        if len(dims) != 3 or any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) or int(v) < 1 for v in dims):
+            raise ValueError("shape must be three positive integers, got %r" % (shape,))
+        dims = tuple(int(v) for v in dims)
+        axes = [np.linspace(lo3[a], hi3[a], dims[a]) if dims[a] > 1 else lo3[a:a + 1] for a in range(3)]  # (both ends exact)
+        pts = np.stack(np.meshgrid(*axes, indexing="ij"), axis=-1)
+        out = self.probe(pts.reshape(-1, 3), background, samples, seed, pass_index, first_index, want)
+        for name in list(out):
+            if name != "kernel_ms":
+                out[name] = out[name].reshape(dims + out[name].shape[1:])
+        out["points"] = pts
+        return out
 
     def radiance(self, origins, directions, background=(0.0, 0.0, 0.0), seed: int = 0, sample: int = 0, stream_base: int = 0, reorder: bool = False,
                  into: Optional[np.ndarray] = None) -> dict:

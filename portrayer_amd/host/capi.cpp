@@ -922,6 +922,18 @@ extern "C" int ph_renderer_direct(ph_renderer* r, const pt_direct_params* p, con
     });
 }
 
+// Light probes at points in free space (pt_probe): host buffers in and out.
+extern "C" int ph_renderer_probe(ph_renderer* r, const pt_probe_params* p, const double* positions, const double* background, const pt_probe_buffers* out, double* kernel_ms) {
+    if (!r || !p || !background || !out) return bad("null argument");
+    if (p->n && !positions) return bad("null argument");
+    if (p->n == 0) { if (kernel_ms) *kernel_ms = 0.0; return PH_OK; }
+    return guarded([&]() -> int {
+        int rc = pt_probe(r->r->context(), p, positions, background, out, kernel_ms);  // (a renderer spread over a node: rank 0's context, every probe)
+        if (rc != PT_OK) { g_error = pt_last_error(r->r->context()); return rc == PT_ERR_ARGUMENT ? PH_ERR_ARGUMENT : PH_ERR_RUNTIME; }
+        return PH_OK;
+    });
+}
+
 // What ph_renderer_direct_camera and ph_renderer_direct_chart share once the points' pass (pt_aov_device or pt_chart_device, left open) has written position and
 // normal into the renderer's device scratch: pt_direct_device behind it on the same (default) stream - the sums where ph_renderer_ao_camera keeps its bent
 // normals, the counts where it keeps its own, the flags likewise - both passes closed, the results asked for copied out.

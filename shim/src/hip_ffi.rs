@@ -142,6 +142,15 @@ pub struct PtChartBuffers {                // pt_chart_buffers: each optional (n
     pub position: *mut f64, pub normal: *mut f64, pub tri: *mut i32, pub covered: *mut u8,
 }
 pub const PT_CHART_FLIP_NORMAL: u32 = 1;   // PtChartParams.flags: negate every normal (the inside of a room)
+#[repr(C)]
+pub struct PtProbeParams {                 // pt_probe_params: a probe has no normal and no bias; ray k of probe i draws from the stream (seed, (first_index + i) * samples + k, pass)
+    pub n: u64, pub samples: u32, pub pass: u32, pub seed: u64, pub first_index: u64,
+}
+#[repr(C)]
+pub struct PtProbeBuffers {                // pt_probe_buffers: each optional (null = not wanted), n entries; sh n x 9 x 3 = a probe's order-2 SH sums, x 4 pi / samples the coefficients
+    pub sh: *mut f64, pub valid: *mut u8,
+}
+pub const PT_PROBE_MAX: u64 = 1 << 20;     // probes per call
 #[repr(C)] pub struct PtRaysParams { pub n: u64, pub any_hit: i32, pub reorder: i32 }   // pt_rays_params: any_hit 1 = occlusion query, reorder 1 = the device groups like rays first
 #[repr(C)]
 pub struct PtRadianceParams {              // pt_radiance_params: ray i draws from the generator's stream (seed, stream_base + i, sample), draws 2, 3, ...
@@ -243,6 +252,14 @@ extern "C" {
     pub fn pt_gather_device(ctx: *mut PtContext, params: *const PtGatherParams, d_positions: *const f64, d_normals: *const f64, background: *const f64,
                             device_out: *const PtGatherBuffers, hip_stream: *mut c_void) -> c_int;
     pub fn pt_gather_finish(ctx: *mut PtContext, kernel_ms: *mut f64) -> c_int;
+    // light probes at points in free space: per probe the nine order-2 spherical-harmonic sums (9 x 3 f64) of `samples` (64 .. 1024) shaded samples - what
+    // pt_radiance answers - over the whole sphere, the rays made in registers; 24 bytes per probe in, background 3 f64 on the HOST in both forms. A radiance
+    // pass for bookkeeping: pt_probe_device is closed by pt_probe_finish, which is pt_radiance_finish
+    pub fn pt_probe(ctx: *mut PtContext, params: *const PtProbeParams, positions: *const f64, background: *const f64,
+                    host_out: *const PtProbeBuffers, kernel_ms: *mut f64) -> c_int;
+    pub fn pt_probe_device(ctx: *mut PtContext, params: *const PtProbeParams, d_positions: *const f64, background: *const f64,
+                           device_out: *const PtProbeBuffers, hip_stream: *mut c_void) -> c_int;
+    pub fn pt_probe_finish(ctx: *mut PtContext, kernel_ms: *mut f64) -> c_int;
     // direct light at points of the caller's own: per point the sum of colour x max(cos, 0) / attenuation over the resident scene's lights whose shadow ray
     // (made in registers, a fixed sequence of f64 operations, pt_direct.h; `samples` per area light) meets nothing. Shares pt_rays' pass as pt_ao does:
     // pt_direct_device is closed by pt_direct_finish, which is pt_rays_finish; queued behind pt_aov_device / pt_chart_device on the same stream it reads that

@@ -5,7 +5,7 @@
 
 Extracts the gfx950 code object from every HIP object of both directories (llvm-objdump --offloading, as tests/test_kernel_resources.py does) and compares
 them byte for byte: the nine per-mode objects of the render kernel and of every pass beside it (pt_<pass>_m1.o .. m9.o) and the single objects (pt_api.o,
-pt_scene.o, pt_build.o, pt_node.o, pt_rays_sort.o, pt_film.o, pt_film_map.o, pt_denoise.o, pt_denoise_albedo.o, pt_chart.o). Only pt_render_m*.o must exist in the other build; an object it lacks (a build
+pt_scene.o, pt_build.o, pt_node.o, pt_rays_sort.o, pt_film.o, pt_film_map.o, pt_denoise.o, pt_denoise_albedo.o, pt_chart.o, pt_probe.o). Only pt_render_m*.o must exist in the other build; an object it lacks (a build
 from before that pass existed) or one that holds no device code in either build is skipped. A change that claims to leave kernels alone (a new pass beside
 them, host code) runs this against a build of its parent commit: identical code objects mean identical behaviour and speed of every kernel, without a GPU.
 Exit status 0: all identical; 1: some differ (named)."""
@@ -20,8 +20,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LLVM = os.environ.get("LLVM_BIN", "/opt/rocm/lib/llvm/bin")
 
 
-PASSES = ("render", "aov", "guides", "rays", "segments", "ao", "radiance", "gather", "direct", "film", "film_map")
-SINGLES = ("pt_api.o", "pt_scene.o", "pt_build.o", "pt_node.o", "pt_rays_sort.o", "pt_film.o", "pt_film_map.o", "pt_denoise.o", "pt_denoise_albedo.o", "pt_chart.o")
+PASSES = ("render", "aov", "guides", "rays", "segments", "ao", "radiance", "gather", "direct", "probe", "film", "film_map")
+SINGLES = ("pt_api.o", "pt_scene.o", "pt_build.o", "pt_node.o", "pt_rays_sort.o", "pt_film.o", "pt_film_map.o", "pt_denoise.o", "pt_denoise_albedo.o", "pt_chart.o", "pt_probe.o")
 
 
 def code_object(obj: str, tmp: str):
