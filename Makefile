@@ -122,9 +122,10 @@ verify-mi:
 # `make -j8 switches` compiles each switch alone, device-only, to /dev/null (the pattern of verify-mi, the same HIPFLAGS) for the render modes whose object
 # it changes - MODES_<switch>, all nine where nothing says so: a switch that stops compiling is noticed. Not part of `all`, and no test runs it.
 SWITCHES := PT_DIAG PT_CYCLES PT_TIMELINE PT_OCCLUDER_STATS=1 PT_OCCLUDER_STATS=2 PT_ABLATE=1 PT_ABLATE=2 PT_ABLATE=3 PT_ABLATE=5 PT_ABLATE=6 \
-            PT_NO_UNIFORM_HIT PT_NO_EYE_TABLE PT_NO_CERTAIN_SHADOW PT_NO_DARK_LIGHTS PT_NO_PIXEL_LISTS PT_PIXEL_LIST_STATS PT_POW_OCML
+            PT_NO_UNIFORM_HIT PT_NO_EYE_TABLE PT_NO_CERTAIN_SHADOW PT_NO_DARK_LIGHTS PT_NO_PIXEL_LISTS PT_NO_BACKGROUND_SKIP PT_PIXEL_LIST_STATS PT_POW_OCML
 MODES_PT_OCCLUDER_STATS := 3 6
 MODES_PT_NO_PIXEL_LISTS := 3
+MODES_PT_NO_BACKGROUND_SKIP := 3
 MODES_PT_PIXEL_LIST_STATS := 3
 MODES_PT_NO_UNIFORM_HIT := 3
 MODES_PT_NO_EYE_TABLE := 3

@@ -1022,6 +1022,14 @@ int pt_test_rect_beam(uint64_t n, const double *cameras, const uint32_t *rects, 
  * the walk), word 1 the tail bound's f32 bits, word 2 + k entry k = the bound's upper 16 bits << 16 | the node. Where out is not NULL and words >= info[0] * info[1], the
  * records are copied to out; otherwise (words = 0: a query of the sizes) nothing is. */
 int pt_test_pixel_list_records(pt_context *ctx, uint32_t *out, uint64_t words, uint64_t *info);
+/* The last launch's queue of the pixels that need the render kernel (tests; that launch must be closed): the pixel slots (local tile << 6 | y * 8 + x inside the tile)
+ * whose record is not {no entry, nothing left out, unmarked} and that lie inside the slice, a tile's together in its Morton order, the tiles in no fixed order. info has
+ * 3 entries: [0] 1 where the launch had a queue (0: every pixel was dealt, PORTRAYER_BACKGROUND_SKIP=0 among the reasons), [1] the queue's length as the device counted
+ * it, [2] the launch's pixel slots. Where out is not NULL and words >= info[1], the ids are copied to out. */
+int pt_test_pixel_list_queue(pt_context *ctx, uint32_t *out, uint64_t words, uint64_t *info);
+/* Host-side run (no GPU, no context) of the sum the finish kernel gives a pixel that was never dealt: `samples` samples of the colour rgb[0..2] under the summation
+ * contract (chunks of 8: a chunk's first sample assigned, the rest added left to right; the first chunk assigned, the rest added in ascending order) -> out[0..2]. */
+int pt_test_background_sum(const double *rgb, uint32_t samples, double *out);
 /* Host-side run (no GPU, no context) of the film's running sum: `samples` (n x 3) given to one pixel in n_cuts consecutive adds of cuts[k] samples each
  * (their sum must be n), through the functions the film's fold and resolve kernels call. out_sum: what resolve divides by n. */
 int pt_test_film_fold_host(uint32_t n, const double *samples, const uint32_t *cuts, uint32_t n_cuts, double out_sum[3]);

@@ -270,6 +270,7 @@ EXPORTS = ["pt_abi_version", "pt_device_count", "pt_context_create", "pt_context
            "pt_aov", "pt_aov_device", "pt_aov_finish", "pt_rays", "pt_rays_device", "pt_rays_finish", "pt_segments", "pt_segments_device",
            "pt_radiance", "pt_radiance_device", "pt_radiance_finish", "pt_scene_update", "pt_node_scene_update", "pt_scene_deform", "pt_node_scene_deform", "pt_scene_mesh_rebuildable", "pt_test_scene_bytes", "pt_test_scene_info",
            "pt_vertex_bounds_device", "pt_scene_deform_device", "pt_test_vertex_box_shape", "pt_test_raypk", "pt_test_certain_shadow", "pt_test_pixel_beam", "pt_test_pixel_list_summary", "pt_test_rect_beam", "pt_test_pixel_list_records",
+           "pt_test_pixel_list_queue", "pt_test_background_sum",
            "pt_test_dark_light", "pt_test_dark_lights",
            "pt_film_create", "pt_film_destroy", "pt_film_reset", "pt_film_add", "pt_film_add_device", "pt_film_resolve", "pt_film_resolve_device", "pt_film_counts",
            "pt_test_film_fold_host",
@@ -384,6 +385,10 @@ def lib() -> C.CDLL:
         l.pt_test_rect_beam.argtypes = l.pt_test_pixel_beam.argtypes
         l.pt_test_pixel_list_records.restype = C.c_int
         l.pt_test_pixel_list_records.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.c_uint64, C.POINTER(C.c_uint64)]
+        l.pt_test_pixel_list_queue.restype = C.c_int
+        l.pt_test_pixel_list_queue.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.c_uint64, C.POINTER(C.c_uint64)]
+        l.pt_test_background_sum.restype = C.c_int
+        l.pt_test_background_sum.argtypes = [_dp, C.c_uint32, _dp]
         l.pt_test_math.restype = C.c_int
         l.pt_test_math.argtypes = [C.c_void_p, C.c_int, C.c_uint64, _dp, _dp, _dp]
         l.pt_node_create.restype = C.c_int

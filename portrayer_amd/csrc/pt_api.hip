@@ -88,16 +88,31 @@ __global__ void __launch_bounds__(256) pt_copy1_kernel(const double2* __restrict
 // bytes; instead the block first adds them up EIGHT THREADS PER PIXEL - thread j of a pixel holds chunk 8 b + j of the b-th block of eight,
 // its seven neighbours' loads next to it, and the pixel's first thread adds the eight values in ascending order (the summation contract: a
 // fixed left-to-right association) - leaves the sums in LDS, and then finishes ONE pixel per thread (the three pows with every lane busy).
-__global__ void __launch_bounds__(PT_BLOCK) pt_finish_kernel(PtRenderArgs a) {
+// has_queue (launches whose list kernel left the masks of the pixels that need the render kernel, pt_pixel_list.h - found through a.eye_tab, 8 bytes per tile of 64
+// pixel slots): a pixel whose bit is clear was never dealt, and nothing wrote its chunk sums. Inside the slice that is a pixel whose record is {no entry, nothing left
+// out, unmarked}: its thread computes the sum from the background alone (pt_background_sum: the same adds in the same order), and the eight-threads-per-pixel loads are
+// skipped for it. (Outside the slice pt_finish_pixel writes nothing, as ever.)
+__global__ void __launch_bounds__(PT_BLOCK) pt_finish_kernel(PtRenderArgs a, uint32_t has_queue) {
     __shared__ double sums[3 * PT_BLOCK];
     const uint32_t base = blockIdx.x * PT_BLOCK, j = threadIdx.x & 7u;
+#ifndef PT_NO_BACKGROUND_SKIP
+    const unsigned long long* masks = nullptr;
+    if (has_queue) masks = pt_pl_masks((uint32_t*)((char*)a.eye_tab + pt_pl_header_offset((uint32_t)a.scene.n_nodes) + 64u), a.n_slots);
+    // slot p was dealt to the render kernel (p < n_slots; has_queue)
+    auto dealt = [&](uint32_t p) { return ((masks[p >> 6] >> pt_pl_slot_to_tile_order(p & 63u)) & 1ull) != 0ull; };
+#endif
     for (uint32_t pass = 0; pass < 8u; pass++) {
         const uint32_t local = pass * (PT_BLOCK / 8u) + (threadIdx.x >> 3), p = base + local;
         PtVec3 sum = pt_v3(0.0, 0.0, 0.0);
+#ifndef PT_NO_BACKGROUND_SKIP
+        const bool skip = has_queue && p < a.n_slots && !dealt(p);
+#else
+        const bool skip = false;
+#endif
         for (uint32_t b = 0; b < a.n_chunks; b += 8u) {  // (wave-uniform trip count)
             const uint32_t k = b + j;
             PtVec3 v = pt_v3(0.0, 0.0, 0.0);
-            if (p < a.n_slots && k < a.n_chunks) { const double* c = a.accum + 3 * ((size_t)p * a.n_chunks + k); v = pt_v3(c[0], c[1], c[2]); }
+            if (p < a.n_slots && k < a.n_chunks && !skip) { const double* c = a.accum + 3 * ((size_t)p * a.n_chunks + k); v = pt_v3(c[0], c[1], c[2]); }
             const uint32_t n = a.n_chunks - b < 8u ? a.n_chunks - b : 8u;
             for (uint32_t i = 0; i < n; i++) {  // chunk b + i of this pixel, from thread i of its eight
                 const int src = (int)((threadIdx.x & 63u & ~7u) + i);
@@ -109,7 +124,16 @@ __global__ void __launch_bounds__(PT_BLOCK) pt_finish_kernel(PtRenderArgs a) {
     }
     __syncthreads();
     const uint32_t p = base + threadIdx.x;
-    if (p < a.n_slots) pt_finish_pixel(a, p, pt_v3(sums[3 * threadIdx.x], sums[3 * threadIdx.x + 1], sums[3 * threadIdx.x + 2]));
+    if (p >= a.n_slots) return;
+    PtVec3 sum = pt_v3(sums[3 * threadIdx.x], sums[3 * threadIdx.x + 1], sums[3 * threadIdx.x + 2]);
+#ifndef PT_NO_BACKGROUND_SKIP
+    if (has_queue && !dealt(p)) {
+        uint32_t x, y;
+        if (!pt_slot_to_pixel(a, p, &x, &y)) return;  // (pt_finish_pixel's own test: a slot outside the slice has no background to read)
+        sum = pt_background_sum(a, x, y);
+    }
+#endif
+    pt_finish_pixel(a, p, sum);
 }
 
 // compact (rank-major, tile-major) -> row-major image
@@ -213,7 +237,7 @@ __global__ void __launch_bounds__(256) pt_dark_light_kernel(const double* __rest
 #define PT_PL_WAVE_SYNC() do { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); } while (0)
 static __device__ __forceinline__ float pt_pl_scalar(float v) { return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v))); }
 static __device__ __forceinline__ uint32_t pt_pl_lanes_below(unsigned long long m) { return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u)); }
-__global__ void __launch_bounds__(PT_PL_BLOCK) pt_pixel_list_kernel(PtRenderArgs a, uint32_t* __restrict__ table, uint32_t cap, uint32_t pend_cap) {
+__global__ void __launch_bounds__(PT_PL_BLOCK) pt_pixel_list_kernel(PtRenderArgs a, uint32_t* __restrict__ table, uint32_t cap, uint32_t pend_cap, uint32_t flags) {
     __shared__ uint32_t s_list[PT_PL_BLOCK / 64][PT_PL_K][64];
     __shared__ uint32_t s_pend[PT_PL_BLOCK / 64][PT_PL_PENDING];
     __shared__ uint4 s_cand[PT_PL_BLOCK / 64][PT_PL_CANDS * 2u];  // {node, lo.x, lo.y, lo.z}, {hi.x, hi.y, hi.z, -}
@@ -224,8 +248,11 @@ __global__ void __launch_bounds__(PT_PL_BLOCK) pt_pixel_list_kernel(PtRenderArgs
     const PtSceneView& sc = a.scene;
     const uint32_t slot = tile_local * 64u + lane;
     uint32_t x, y, tx, ty;
-    pt_slot_to_pixel(a, slot, &x, &y);
+    [[maybe_unused]] const bool inside = pt_slot_to_pixel(a, slot, &x, &y);
     pt_slot_to_pixel(a, tile_local * 64u, &tx, &ty);
+#ifndef PT_NO_BACKGROUND_SKIP
+    if (tile_local == 0u && lane == 0u) table[-16] = flags;  // header word 0 (the host zeroed the header): what follows it
+#endif
     const PtBeam beam = pt_beam_setup(a.cam, (double)x, (double)y);
     PtBeam tile = pt_beam_setup(a.cam, (double)tx, (double)ty, 8.0, 8.0);
 #pragma unroll
@@ -326,16 +353,74 @@ __global__ void __launch_bounds__(PT_PL_BLOCK) pt_pixel_list_kernel(PtRenderArgs
     for (uint32_t k = 2 + PT_PL_K; k < PT_PL_WORDS; k++) wds[k] = 0u;
 #pragma unroll
     for (uint32_t k = 0; k < PT_PL_WORDS; k += 4) reinterpret_cast<uint4*>(rec)[k / 4] = make_uint4(wds[k], wds[k + 1], wds[k + 2], wds[k + 3]);
+#ifndef PT_NO_BACKGROUND_SKIP
+    // The queue (pt_pixel_list.h): the tile's pixels that need the render kernel - inside the slice, and not {no entry, nothing left out, unmarked} - as one 64-bit mask
+    // per tile behind the queue's array, bit L for the pixel the render kernel deals L-th in the tile (pt_tile_order_to_slot). pt_pixel_queue_kernel makes the queue of them.
+    if (flags & PT_PL_QUEUE) {
+        const bool needed = inside && (overflowed || count != 0u || tail != PT_PL_INF_BITS);
+        const bool mine = __shfl((int)needed, (int)pt_tile_order_to_slot(lane)) != 0;
+        const unsigned long long m = __ballot(mine);
+        if (lane == 0) pt_pl_masks(table, a.n_slots)[tile_local] = m;
+    }
+#endif
 }
+
+#ifndef PT_NO_BACKGROUND_SKIP
+// The queue from the tiles' masks, behind the list kernel on the launch's stream: a block per 256 tiles. The tiles' ranges lie in the order of the tiles - the order the
+// items were dealt in before there was a queue, so that a tile is still rendered well behind the one above it, whose occluder-table entries it starts from
+// (pt_trace_packet: PtOccRef::back) - and inside a range the ids go in the tile's Morton order. Every block adds up the masks in front of its own tiles for itself
+// (a 1080p launch has 32,400 of them, 8 bytes each, in the cache): no second launch for a scan, no waiting of block on block. The last block leaves the length in header word 1.
+__global__ void __launch_bounds__(256) pt_pixel_queue_kernel(uint32_t* __restrict__ table, uint32_t n_slots) {
+    __shared__ uint32_t part[256];
+    __shared__ uint32_t offs[256];
+    const uint32_t tiles = n_slots / 64u, first = blockIdx.x * 256u, t = threadIdx.x, lane = t & 63u;
+    const unsigned long long* const masks = pt_pl_masks(table, n_slots);
+    uint32_t* const queue = table + (size_t)n_slots * PT_PL_WORDS;
+    uint32_t before = 0, i = t;
+    for (; i + 7u * 256u < first; i += 8u * 256u) {  // (eight loads in flight: taken one by one, the last block's 126 round trips were most of the kernel's 47 us)
+        unsigned long long v[8];
+#pragma unroll
+        for (uint32_t k = 0; k < 8u; k++) v[k] = masks[i + k * 256u];
+#pragma unroll
+        for (uint32_t k = 0; k < 8u; k++) before += (uint32_t)__builtin_popcountll(v[k]);
+    }
+    for (; i < first; i += 256u) before += (uint32_t)__builtin_popcountll(masks[i]);
+    const unsigned long long mine = first + t < tiles ? masks[first + t] : 0ull;
+    part[t] = before; offs[t] = (uint32_t)__builtin_popcountll(mine);
+    __syncthreads();
+    for (uint32_t s = 128u; s > 0u; s >>= 1) {  // the sum of what lies in front of the block
+        if (t < s) part[t] += part[t + s];
+        __syncthreads();
+    }
+    const uint32_t base = part[0];
+    for (uint32_t s = 1u; s < 256u; s <<= 1) {  // inclusive scan of the block's own counts
+        const uint32_t v = t >= s ? offs[t - s] : 0u;
+        __syncthreads();
+        offs[t] += v;
+        __syncthreads();
+    }
+    if (first + 256u >= tiles && t == 255u) table[-15] = base + offs[255];  // (the tiles behind the launch's last count nothing)
+    for (uint32_t k = 0; k < 64u; k++) {  // a wavefront per tile, 64 tiles each: lane L is the tile's L-th pixel in Morton order
+        const uint32_t i = (t & ~63u) + k, tile = first + i;
+        if (tile >= tiles) break;  // (wave-uniform)
+        const unsigned long long m = (unsigned long long)__shfl((long long)mine, (int)k);  // (thread i of the block read tile i's mask: lane k of this wavefront)
+        const uint32_t at = base + (i ? offs[i - 1u] : 0u) + (uint32_t)__builtin_popcountll(m & ((1ull << lane) - 1ull));
+        if (((m >> lane) & 1ull) && at < n_slots) queue[at] = (tile << 6) | pt_tile_order_to_slot(lane);  // (a slot is queued once at most: the bound always holds)
+    }
+}
+#endif
 #else
 #define PT_PL_BLOCK 256
 #define PT_PL_STACK 64
-__global__ void __launch_bounds__(PT_PL_BLOCK) pt_pixel_list_kernel(PtRenderArgs a, uint32_t* __restrict__ table, uint32_t cap, uint32_t pend_cap) {
+__global__ void __launch_bounds__(PT_PL_BLOCK) pt_pixel_list_kernel(PtRenderArgs a, uint32_t* __restrict__ table, uint32_t cap, uint32_t pend_cap, uint32_t flags) {
     __shared__ uint32_t s_list[PT_PL_BLOCK / 64][PT_PL_K][64];
     __shared__ uint32_t s_stack[PT_PL_BLOCK / 64][PT_PL_STACK];
     const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
     const uint32_t tile_local = blockIdx.x * (PT_PL_BLOCK / 64) + wave;
     if (tile_local >= a.n_slots / 64u) return;  // (wave-uniform)
+#ifndef PT_NO_BACKGROUND_SKIP
+    if (tile_local == 0u && lane == 0u) table[-16] = flags;  // header word 0 (the host never asks this variant for a queue)
+#endif
     const PtSceneView& sc = a.scene;
     const uint32_t slot = tile_local * 64u + lane;
     uint32_t x, y;
@@ -848,6 +933,41 @@ extern "C" int pt_test_pixel_list_records(pt_context* c, uint32_t* out, uint64_t
     return PT_OK;
 }
 
+// The last launch's queue of the pixels that need the render kernel (pt_pixel_list.h) as the list kernel left it (tests; the launch must have been closed): info[0] 1 where
+// that launch had a queue, else 0; info[1] the count in header word 1; info[2] the launch's pixel slots (what the queue can hold). Where `out` is not NULL and `words` >=
+// info[1], the first info[1] slot ids are copied to it.
+extern "C" int pt_test_pixel_list_queue(pt_context* c, uint32_t* out, uint64_t words, uint64_t* info) {
+    if (!c || !info) return PT_ERR_ARGUMENT;
+    info[0] = info[1] = 0; info[2] = c->pl_slots;
+    if (c->pl_slot < 0 || c->pl_slots == 0 || !c->pl_queue) return PT_OK;
+    info[0] = 1;
+    PT_HIP(c, hipSetDevice(c->device));
+    PT_HIP(c, hipDeviceSynchronize());
+    const pt_context::Slot& sl = c->slot[c->pl_slot];
+    const size_t queue_off = c->pl_off + (size_t)c->pl_slots * PT_PL_WORDS * 4;
+    if (sl.eye_tab.bytes < queue_off + (size_t)c->pl_slots * 4) return pt_fail(c, PT_ERR_ARGUMENT, "the slot's buffer no longer holds that launch's queue");
+    uint32_t head[2] = {0u, 0u};
+    PT_HIP(c, hipMemcpy(head, (const char*)sl.eye_tab.p + c->pl_off - 64, sizeof head, hipMemcpyDeviceToHost));
+    if (!(head[0] & PT_PL_QUEUE)) return pt_fail(c, PT_ERR_TRAVERSAL, "the header of a launch with a queue does not say so");
+    info[1] = head[1];
+    if (head[1] > c->pl_slots) return pt_fail(c, PT_ERR_TRAVERSAL, "more pixels queued than the launch has slots");
+    if (!out || words < head[1] || head[1] == 0u) return PT_OK;
+    PT_HIP(c, hipMemcpy(out, (const char*)sl.eye_tab.p + queue_off, (size_t)head[1] * 4, hipMemcpyDeviceToHost));
+    return PT_OK;
+}
+
+// Host-side run (no GPU involved) of pt_background_sum (pt_shade.h): the sum of `samples` samples of the colour rgb[0..2] under the summation contract -> out[0..2].
+extern "C" int pt_test_background_sum(const double* rgb, uint32_t samples, double* out) {
+    if (!rgb || !out || samples == 0u) return PT_ERR_ARGUMENT;
+    PtRenderArgs a;
+    memset(&a, 0, sizeof a);
+    a.background = rgb; a.background_rows = 1; a.width = a.height = 1;
+    a.samples = samples; a.n_chunks = (samples + PT_SAMPLE_CHUNK - 1u) / PT_SAMPLE_CHUNK;
+    const PtVec3 s = pt_background_sum(a, 0u, 0u);
+    out[0] = s.x; out[1] = s.y; out[2] = s.z;
+    return PT_OK;
+}
+
 // Host-side run (no GPU involved) of the certain-shadow test (pt_certain.h): case i is a node of `type` with the records fwd[12 i ..], inv[12 i ..] (rows 0..2 of its two
 // matrices), a shaded point P[3 i ..] and a light position L[3 i ..]. out_certain[i]: the table routine gave the node a ball and the lane test, on the floats the kernel would
 // hold, says "certainly hit"; out_exact_hit[i]: the reference's own test of that node for the shadow ray {P, (L - P) / |L - P|} over [EPSILON, INF) (pt_ray_to_local,
@@ -1219,10 +1339,20 @@ static int pt_render_common(pt_context* c, PtRenderArgs& a, bool stats, hipStrea
     const bool list_header = false, pixel_lists = false;
     const uint32_t list_cap = 0, list_pending = 0;
 #endif
+    // The queue of the pixels that need the render kernel (pt_pixel_list.h), behind the records: every launch that has lists. The render kernel deals only what is queued,
+    // the finish kernel finishes the rest from the background. PORTRAYER_BACKGROUND_SKIP=0 (tests, A/B runs from one library): the lists as before, no queue, every
+    // item dealt. -DPT_NO_BACKGROUND_SKIP: the kernels as they were. The depth-first list kernel (-DPT_PL_DEPTH_FIRST) fills none.
+#if !defined(PT_NO_BACKGROUND_SKIP) && !defined(PT_NO_PIXEL_LISTS) && !defined(PT_PL_DEPTH_FIRST) && !defined(PT_PIXEL_LIST_STATS)
+    bool background_skip = pixel_lists;
+    if (const char* e = getenv("PORTRAYER_BACKGROUND_SKIP")) if (atoi(e) <= 0) background_skip = false;
+#else
+    const bool background_skip = false;
+#endif
+    if (background_skip) a.item_stride = 1;  // (PORTRAYER_ITEM_STRIDE, an experiment: its stride is coprime to n_items, not to the queue's length)
     const size_t list_off = pt_pl_header_offset((uint32_t)a.scene.n_nodes);
     a.eye_tab = nullptr;
     if (eye_table || certain_table) {
-        if ((rc = pt_reserve(c, sl.eye_tab, list_header ? list_off + pt_pl_bytes(pixel_lists ? a.n_slots : 0u) : (size_t)a.scene.n_nodes * (12 * sizeof(double) + 4 * sizeof(float))))) return rc;
+        if ((rc = pt_reserve(c, sl.eye_tab, list_header ? list_off + pt_pl_bytes(pixel_lists ? a.n_slots : 0u, background_skip) : (size_t)a.scene.n_nodes * (12 * sizeof(double) + 4 * sizeof(float))))) return rc;
         a.eye_tab = (const double*)sl.eye_tab.p;
     }
     a.spill = (double*)sl.spill.p;
@@ -1265,16 +1395,27 @@ static int pt_render_common(pt_context* c, PtRenderArgs& a, bool stats, hipStrea
 #endif
         if (list_header) {  // behind the eye table's fill, on the launch's stream: the header, then the slot's records
             uint32_t* const header = (uint32_t*)((char*)sl.eye_tab.p + list_off);
+#ifndef PT_NO_BACKGROUND_SKIP  // all zero: the list kernel writes word 0 (what follows the header) and counts the queue in word 1
+            PT_HIP(c, hipMemsetD32Async((hipDeviceptr_t)header, 0, 16, stream));
+#else
             PT_HIP(c, hipMemsetD32Async((hipDeviceptr_t)header, pixel_lists ? 1 : 0, 16, stream));
+#endif
             if (pixel_lists) {
                 const uint32_t tiles = a.n_slots / 64u;
-                hipLaunchKernelGGL(pt_pixel_list_kernel, dim3((tiles + PT_PL_BLOCK / 64 - 1) / (PT_PL_BLOCK / 64)), dim3(PT_PL_BLOCK), 0, stream, a, header + 16, list_cap, list_pending);
+                hipLaunchKernelGGL(pt_pixel_list_kernel, dim3((tiles + PT_PL_BLOCK / 64 - 1) / (PT_PL_BLOCK / 64)), dim3(PT_PL_BLOCK), 0, stream, a, header + 16, list_cap, list_pending,
+                                   PT_PL_LISTS | (background_skip ? PT_PL_QUEUE : 0u));
                 PT_HIP(c, hipGetLastError());
+#if !defined(PT_NO_BACKGROUND_SKIP) && !defined(PT_PL_DEPTH_FIRST)
+                if (background_skip) {
+                    hipLaunchKernelGGL(pt_pixel_queue_kernel, dim3((tiles + 255u) / 256u), dim3(256), 0, stream, header + 16, a.n_slots);
+                    PT_HIP(c, hipGetLastError());
+                }
+#endif
             }
         }
-        c->pl_slot = pixel_lists ? slot_index : -1; c->pl_slots = a.n_slots; c->pl_off = list_off + 64; c->pl_nodes = (uint32_t)a.scene.n_nodes;
+        c->pl_slot = pixel_lists ? slot_index : -1; c->pl_slots = a.n_slots; c->pl_off = list_off + 64; c->pl_nodes = (uint32_t)a.scene.n_nodes; c->pl_queue = background_skip;
         PT_HIP(c, pt_dispatch(a, stats, c->n_cu, stream, &grid, true));
-        hipLaunchKernelGGL(pt_finish_kernel, dim3((a.n_slots + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, stream, a);
+        hipLaunchKernelGGL(pt_finish_kernel, dim3((a.n_slots + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, stream, a, background_skip ? 1u : 0u);
         PT_HIP(c, hipGetLastError());
     }
     PT_HIP(c, hipEventRecord(sl.ev1, stream));

@@ -106,6 +106,7 @@ struct pt_context {
     uint32_t pl_slots = 0;     // ... its pixel slots ...
     size_t pl_off = 0;         // ... where its records start in the buffer ...
     uint32_t pl_nodes = 0;     // ... and the scene's flattened nodes (pt_test_pixel_list_records)
+    bool pl_queue = false;     // ... and whether the queue of the pixels that need the render kernel lies behind them (pt_test_pixel_list_queue)
     int dark_slot = -1;        // pt_test_dark_lights: the slot whose misc buffer holds the last launch's dark-light records (-1: that launch had none) ...
     uint32_t dark_lights = 0;  // ... the scene's lights ...
     size_t dark_off = 0;       // ... and where the records start in the buffer (in front of the occluder table)

@@ -66,6 +66,12 @@
 //   word 2+k entry k: bound's upper 16 bits << 16 | flattened node index (< 65536: the host leaves the lists out for larger scenes). Ascending as unsigned words, which is
 //            ascending in the bound (non-negative floats order like their bit patterns), then in the index.
 // In front of the records one 64-byte header, behind the launch's eye table and certain-shadow table (pt_pl_header): word 0 != 0: the records follow; 0: no lists, today's walk.
+// Word 0 bit 1 (PT_PL_QUEUE): behind the records the launch's QUEUE follows, one word per pixel slot - the slot ids (local tile << 6 | j) of the pixels that need the render
+// kernel, i.e. the in-slice slots whose record is not {0 entries, infinite tail, unmarked} - and header word 1 holds their number. The host zeroes the header, the list kernel
+// writes word 0 and a 64-bit mask per tile behind the queue, and pt_pixel_queue_kernel (pt_api.hip) makes the queue and word 1 of the masks: the tiles' ranges in the order of
+// the tiles, a tile's ids in the Morton order the render kernel deals a tile's pixels in (pt_tile_order_to_slot) - the order in which the pixels were dealt without a queue,
+// which the occluder table's look at the tile above was measured to need (profiles/r15/notes.md). The render kernel deals only queued pixels; the finish kernel
+// finishes the others from the background alone (pt_background_sum). PORTRAYER_BACKGROUND_SKIP=0, -DPT_NO_BACKGROUND_SKIP: no queue, every pixel dealt.
 #ifndef PT_PL_K  // (-DPT_PL_K=14u with -DPT_PIXEL_LIST_STATS: the build the figures were taken from - 16-word records, so that caps up to 14 can be tried)
 #define PT_PL_K 6u
 #endif
@@ -77,7 +83,16 @@ static_assert(PT_PL_K >= 1u && PT_PL_K <= 14u, "a record is 8 or 16 words: head,
 
 // where the header lies behind an eye table of n_nodes records (96 + 16 bytes each), as a byte offset: the next multiple of 64
 PT_HD size_t pt_pl_header_offset(uint32_t n_nodes) { return ((size_t)n_nodes * (12 * sizeof(double) + 4 * sizeof(float)) + 63u) & ~(size_t)63u; }
-PT_HD size_t pt_pl_bytes(uint32_t n_slots) { return 64u + (size_t)n_slots * (PT_PL_WORDS * 4u); }
+// (with the queue: a word per slot for it, and behind it the 64-bit mask per tile it is made from - n_slots is a multiple of 64, so the masks are 8-byte aligned)
+PT_HD size_t pt_pl_bytes(uint32_t n_slots, bool queue = false) { return 64u + (size_t)n_slots * (PT_PL_WORDS * 4u) + (queue ? (size_t)n_slots * 4u + (size_t)(n_slots / 64u) * 8u : 0u); }
+// the tiles' masks, from the first record's address
+PT_HD unsigned long long* pt_pl_masks(uint32_t* records, uint32_t n_slots) { return reinterpret_cast<unsigned long long*>(records + (size_t)n_slots * (PT_PL_WORDS + 1u)); }
+#define PT_PL_LISTS 1u  // header word 0: the records follow
+#define PT_PL_QUEUE 2u  // header word 0: ... and the queue behind them, its length in header word 1
+// the inverse of pt_tile_order_to_slot: j = y * 8 + x inside the 8x8 tile -> its place in the tile's Morton order
+PT_HD uint32_t pt_pl_slot_to_tile_order(uint32_t j) {
+    return (j & 1u) | ((j >> 2) & 2u) | ((j << 1) & 4u) | ((j >> 1) & 8u) | ((j << 2) & 16u) | (j & 32u);
+}
 
 struct PtBeamAxis {
     int neg;             // 1: every sample's direction is negative on this axis - the box's UPPER plane feeds the entering fmas, the lower one the leaving fmas

@@ -30,6 +30,11 @@
 #if !defined(PT_NO_PIXEL_LISTS) && !defined(PT_NO_EYE_TABLE) && (!defined(PT_INST_MODE) || PT_INST_MODE == 3)
 #define PT_PIXEL_LIST_FORM 1
 #include "pt_pixel_list.h"
+// The queue of the pixels that need the kernel (pt_pixel_list.h: PT_PL_QUEUE): where the launch has one, the instantiations that have PIXEL_LISTS deal its entries instead
+// of every pixel of the launch. -DPT_NO_BACKGROUND_SKIP: the kernels as they were (A/B), and the host asks for no queue.
+#if !defined(PT_NO_BACKGROUND_SKIP)
+#define PT_BACKGROUND_SKIP_FORM 1
+#endif
 // one or two words at a wave-uniform address through the scalar cache
 typedef uint32_t pt_u32x2 __attribute__((ext_vector_type(2)));
 PT_HD uint32_t pt_sload1(const void* p) {
@@ -286,12 +291,26 @@ __global__ void __launch_bounds__(PT_BLOCK, WAVES) pt_render_simple_kernel(PtRen
     const unsigned long long tl_start = wall_clock64();
     unsigned long long tl_item_max = 0, tl_first_item = 0;
 #endif
+#if defined(PT_BACKGROUND_SKIP_FORM)
+    // Where the launch has the queue (header word 0; a launch that has it has lists), the hand-out positions run over its entries x the chunk groups of a pixel: position
+    // q is group q % groups of the pixel slot queue[q / groups]. pl_deal: the items dealt (wave-uniform, read once: the list kernel has finished); 0xFFFFFFFF: no queue.
+    [[maybe_unused]] uint32_t pl_deal = 0xFFFFFFFFu;
+    if constexpr (EYE_TABLE) {
+        if (a.eye_tab && a.k_log2 + a.c_log2 == 6u) {
+            const pt_u32x2 h = pt_sload2((const char*)a.eye_tab + pt_pl_header_offset(a.scene.n_nodes));
+            if (h[0] & PT_PL_QUEUE) pl_deal = h[1] * a.div_groups.d;
+        }
+    }
+#define PT_ITEMS_DEALT ((EYE_TABLE && pl_deal != 0xFFFFFFFFu) ? pl_deal : a.n_items)
+#else
+#define PT_ITEMS_DEALT a.n_items
+#endif
 
     for (;;) {
         unsigned w;
         if (a.fine_queues == 0u) {  // guided batches from one counter (very long launches, the k-d tree semantics)
             if (q_next == q_end) {
-                unsigned remaining = a.n_items > q_seen ? a.n_items - q_seen : 0u;
+                unsigned remaining = PT_ITEMS_DEALT > q_seen ? PT_ITEMS_DEALT - q_seen : 0u;
                 unsigned take = remaining / a.work_div;
                 take = take > a.batch_max ? a.batch_max : (take < 1u ? 1u : take);
                 unsigned base = 0;
@@ -300,15 +319,15 @@ __global__ void __launch_bounds__(PT_BLOCK, WAVES) pt_render_simple_kernel(PtRen
                 q_next = base; q_end = base + take; q_seen = q_end;
             }
             const unsigned q = q_next++;
-            if (q >= a.n_items) break;
-            w = a.item_stride == 1u ? q : (unsigned)(((unsigned long long)q * a.item_stride) % a.n_items);
+            if (q >= PT_ITEMS_DEALT) break;
+            w = a.item_stride == 1u ? q : (unsigned)(((unsigned long long)q * a.item_stride) % a.n_items);  // (a launch with a queue has item_stride 1: pt_render_common)
         } else {  // one item at a time from interleaved queues
             for (;;) {
                 unsigned idx = 0;
                 if (lane == 0) idx = atomicAdd(a.work_queues + q_next * PT_QUEUE_STRIDE, 1u);
                 idx = (unsigned)__builtin_amdgcn_readfirstlane((int)idx);
                 const unsigned long long pos = (unsigned long long)idx * a.fine_queues + q_next;
-                if (pos < a.n_items) { w = (unsigned)pos; q_end = 0; break; }
+                if (pos < PT_ITEMS_DEALT) { w = (unsigned)pos; q_end = 0; break; }
                 q_next = q_next + 1u == a.fine_queues ? 0u : q_next + 1u;
                 if (++q_end == a.fine_queues) { w = 0xFFFFFFFFu; break; }
             }
@@ -342,6 +361,19 @@ __global__ void __launch_bounds__(PT_BLOCK, WAVES) pt_render_simple_kernel(PtRen
         constexpr bool PIXEL_LISTS = EYE_TABLE;
         const uint32_t* pl_rec = nullptr;
         uint32_t pl_head = PT_PL_WALK, pl_tail = 0u;
+#if defined(PT_BACKGROUND_SKIP_FORM)
+        // With the queue, w is still the hand-out position: its pixel slot comes from the queue - one dependent load in place of the header word's, which such a launch
+        // need not read again - and gives the record's address and the item index w that everything below uses, as if every item had been dealt.
+        if (PIXEL_LISTS && pl_deal != 0xFFFFFFFFu) {
+            const uint32_t* const header = (const uint32_t*)((const char*)a.eye_tab + pt_pl_header_offset(sc.n_nodes));
+            const uint32_t pixel = pt_fastdiv(w, a.div_groups), group = w - pixel * a.div_groups.d;
+            const uint32_t slot = pt_sload1(header + 16 + (size_t)a.n_slots * PT_PL_WORDS + pixel);
+            w = ((((slot >> 6) * a.div_groups.d + group) << 6) | pt_pl_slot_to_tile_order(slot & 63u));
+            pl_rec = header + 16 + (size_t)slot * PT_PL_WORDS;
+            const pt_u32x2 h = pt_sload2(pl_rec);
+            pl_head = h[0]; pl_tail = h[1];
+        } else
+#endif
         if constexpr (PIXEL_LISTS) pl_rec = pt_pl_fetch(a, sc.n_nodes, w, &pl_head, &pl_tail);
         // no leaf is reached by any ray through the pixel: background for every sample, without jitter draws, camera ray or walk
         const bool pl_background = PIXEL_LISTS && pl_head == 0u && pl_tail == PT_PL_INF_BITS;
@@ -705,3 +737,4 @@ __global__ void __launch_bounds__(PT_BLOCK, WAVES) pt_render_simple_kernel(PtRen
 #endif
     if (STATS) pt_flush_counters(a.counters, cnt);
 }
+#undef PT_ITEMS_DEALT

@@ -312,6 +312,22 @@ PT_HD PtVec3 pt_background(const PtRenderArgs& a, uint32_t x, uint32_t y) {  // 
     return pt_v3(b[0], b[1], b[2]);
 }
 
+// The sum of a pixel whose every sample is the background (no ray through it reaches anything: pt_pixel_list.h), under the summation contract, as the render kernel's
+// chunk loop and the finish kernel's pass over the chunk sums would have formed it: a chunk's first sample assigned, the rest of its min(8, samples - 8 k) samples added
+// left to right; the pixel's first chunk assigned, the others added in ascending order. The same adds in the same order - no product, no closed form - so that -0.0,
+// an infinity and a NaN come out as they do there.
+PT_HD PtVec3 pt_background_sum(const PtRenderArgs& a, uint32_t x, uint32_t y) {
+    const PtVec3 b = pt_background(a, x, y);
+    PtVec3 sum = b;
+    for (uint32_t k = 0; k < a.n_chunks; k++) {
+        const uint32_t left = a.samples - k * PT_SAMPLE_CHUNK, n = left < (uint32_t)PT_SAMPLE_CHUNK ? left : (uint32_t)PT_SAMPLE_CHUNK;
+        PtVec3 chunk = b;
+        for (uint32_t i = 1; i < n; i++) chunk = chunk + b;
+        sum = k == 0u ? chunk : sum + chunk;
+    }
+    return sum;
+}
+
 PT_HD PtRay pt_camera_ray(const PtCamera& c, double x, double y) {  // camera.rs:48-84
     double ndc_y = y / c.height;
     double view_y = (1.0 - 2.0 * ndc_y) * c.fov_factor;
