@@ -771,6 +771,43 @@ int pt_film_resolve(pt_context *ctx, pt_film *film, uint8_t *rgb, double *linear
 int pt_film_resolve_device(pt_context *ctx, pt_film *film, void *d_rgb, double *d_linear, void *hip_stream);
 int pt_film_counts(pt_context *ctx, pt_film *film, uint32_t *counts);   /* host, width x height: the DEVICE's counts; the host's copy is set to them */
 
+/* ---- Film, behind a lens: depth of field, an orthographic view, a fisheye.
+ *   pt_film_add_lens gives every pixel of `slice` its next samples exactly as pt_film_add does - the same counts, fold, launches and bookkeeping, moments films
+ *     included - and only the PRIMARY ray of sample s of pixel (x, y) differs: it comes from the lens CONTRACT, a fixed sequence of correctly rounded f64
+ *     operations (+ - * / sqrt) that portrayer_amd/csrc/pt_lens.h states in six steps and pt_test_lens_rays_host replays on the host. With
+ *     pixel = y * width + x and (sx, sy) the jittered position as pt_film_add takes it (draws 0 and 1 of (seed, pixel, s), or the centre):
+ *       PT_LENS_THIN    D = pt_render's unnormalised direction through (sx, sy). aperture == 0: pt_film_add's ray itself. Else the lens point (lx, ly) on the
+ *                       unit disc is the xy of pt_ao's direction s & 63 turned by pt_ao's rotation j = (uint32)(draw 0 of (seed, pixel, 0x80000000 | (s >> 6)) *
+ *                       256): 64 consecutive samples are stratified over the disc. R, U = columns 0 and 1 of view_to_world; e = (R lx + U ly) * aperture;
+ *                       origin eye + e, direction normalised(D - e / focus): points at the distance `focus` along the view axis are sharp.
+ *       PT_LENS_ORTHO   vx = (2 sx / W - 1) * aspect * extent, vy = (1 - 2 sy / H) * extent (W, H: the camera's width and height); origin
+ *                       view_to_world (vx, vy, 0), direction normalised(view_to_world (vx, vy, -1) - origin). extent = half the height of the view volume.
+ *       PT_LENS_STEREO  stereographic fisheye: u, v as vx, vy; q = u u + v v; direction normalised(view_to_world (2 u, 2 v, q - 1) - eye), origin eye.
+ *                       extent = tan(fov / 4) for the angle fov across the image height; every pixel has a ray, up to (not including) 360 degrees.
+ *     Behind the primary ray everything is pt_film_add's: the stream y * width + x, sample s, draws 2, 3, ..., the background at the integer pixel.
+ * PROMISE: sample s of pixel p is, to the bit, what pt_radiance answers for the contract's ray with stream_base + i = p, sample = s and the pixel's background,
+ * and the samples are folded as pt_film_add folds them, in all three traversals. The claim covers rays that pt_rays' traced rule accepts; a camera or lens
+ * that makes other rays is the caller's error, as for pt_film_add. A film may mix lens and plain adds: it adds what it is given.
+ * Errors, before the first HIP call and with the film unchanged: all of pt_film_add's, in its order, then PT_ERR_ARGUMENT for a NULL lens; an unknown model;
+ * THIN: aperture not finite or < 0; THIN: focus not finite or <= 0; ORTHO / STEREO: extent not finite or <= 0.
+ * Not covered: pt_film_add_map with a lens, and an equirectangular panorama (it needs sin / cos, which the device does not pin in the last bit). */
+enum { PT_LENS_THIN = 0, PT_LENS_ORTHO = 1, PT_LENS_STEREO = 2 };
+typedef struct {
+    int32_t model;              /* PT_LENS_*                                                                      */
+    double aperture;            /* THIN: lens radius in world units, >= 0                                         */
+    double focus;               /* THIN: distance of the plane of focus along the view axis, > 0                  */
+    double extent;              /* ORTHO: half height of the view volume; STEREO: tan(fov / 4); > 0               */
+} pt_lens;
+/* Host background, synchronous; kernel_ms as for pt_film_add. */
+int pt_film_add_lens(pt_context *ctx, pt_film *film, const pt_camera *camera, const pt_lens *lens, const double *background, const pt_film_params *params, double *kernel_ms);
+/* The background in DEVICE memory, queued on `hip_stream`; closed by pt_radiance_finish like pt_film_add_device, one pass in flight. */
+int pt_film_add_lens_device(pt_context *ctx, pt_film *film, const pt_camera *camera, const pt_lens *lens, const double *d_background, const pt_film_params *params, void *hip_stream);
+/* Test hook, no context and no GPU: the contract on the host, by the functions the kernel compiles. Ray i is sample samples[i] of pixel (pixels_xy[2 i],
+ * pixels_xy[2 i + 1]) of a film width x height; origins and directions n x 3. PT_ERR_ARGUMENT: a NULL pointer, a bad sample_mode, a lens pt_film_add_lens
+ * refuses, a pixel outside the film (nothing is written then). */
+int pt_test_lens_rays_host(const pt_camera *camera, const pt_lens *lens, uint32_t width, uint32_t height, uint64_t seed, int32_t sample_mode, uint64_t n,
+                           const uint32_t *pixels_xy, const uint32_t *samples, double *origins, double *directions);
+
 /* ---- Film, adaptive: a sample budget per pixel, a noise estimate, and the budget a refine pass gives.
  *   pt_film_add_map gives pixel p of `slice` its next m[p] = min(budget[p], max_samples) samples, each taken and folded exactly as pt_film_add does it: the
  *     PROMISE above is unchanged after any mix of pt_film_add and pt_film_add_map. `budget` is width x height u32, row-major like pt_film_counts; only the

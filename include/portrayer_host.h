@@ -238,6 +238,9 @@ int ph_renderer_film_create(ph_renderer *r, uint32_t width, uint32_t height, ph_
 int ph_renderer_film_destroy(ph_renderer *r, ph_film *film);   /* before the renderer; films still alive die with it */
 int ph_renderer_film_reset(ph_renderer *r, ph_film *film);
 int ph_renderer_film_add(ph_renderer *r, ph_film *film, const double camera[10], const double *background, const pt_film_params *params, double *kernel_ms);
+/* The same samples behind a lens (see pt_film_add_lens): a thin lens, an orthographic or a stereographic camera in place of the pinhole. */
+int ph_renderer_film_add_lens(ph_renderer *r, ph_film *film, const double camera[10], const pt_lens *lens, const double *background, const pt_film_params *params,
+                              double *kernel_ms);
 int ph_renderer_film_resolve(ph_renderer *r, ph_film *film, uint8_t *rgb, double *linear);   /* either may be NULL, not both */
 int ph_renderer_film_counts(ph_renderer *r, ph_film *film, uint32_t *counts);
 /* The adaptive film (pt_film_create_moments, pt_film_add_map, pt_film_error, pt_film_budget_device): a film that also keeps the second moment of its samples;

@@ -221,6 +221,14 @@ class PtFilmParams(C.Structure):
     _fields_ = [("slice", PtRect), ("samples", C.c_uint32), ("seed", C.c_uint64), ("sample_mode", C.c_int32), ("background_rows", C.c_int32)]
 
 
+LENS_THIN, LENS_ORTHO, LENS_STEREO = 0, 1, 2  # PT_LENS_*
+
+
+class PtLens(C.Structure):
+    """pt_lens: what stands in for the pinhole in pt_film_add_lens - a thin lens (aperture, focus), an orthographic or a stereographic camera (extent)."""
+    _fields_ = [("model", C.c_int32), ("aperture", C.c_double), ("focus", C.c_double), ("extent", C.c_double)]
+
+
 FILM_MAP_MAX = 4096  # PT_FILM_MAP_MAX
 
 
@@ -282,7 +290,8 @@ EXPORTS = ["pt_abi_version", "pt_device_count", "pt_context_create", "pt_context
            "pt_gather", "pt_gather_device", "pt_gather_finish", "pt_test_kernel_choice",
            "pt_chart_triangles", "pt_chart", "pt_chart_device", "pt_test_chart_host",
            "pt_direct", "pt_direct_device", "pt_direct_finish", "pt_test_direct_host",
-           "pt_probe", "pt_probe_device", "pt_probe_finish", "pt_test_probe_host", "pt_test_probe_tables"]
+           "pt_probe", "pt_probe_device", "pt_probe_finish", "pt_test_probe_host", "pt_test_probe_tables",
+           "pt_film_add_lens", "pt_film_add_lens_device", "pt_test_lens_rays_host"]
 
 
 def header_functions():
@@ -508,6 +517,12 @@ def lib() -> C.CDLL:
         l.pt_film_add.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(PtCamera), _dp, C.POINTER(PtFilmParams), _dp]
         l.pt_film_add_device.restype = C.c_int
         l.pt_film_add_device.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(PtCamera), C.c_void_p, C.POINTER(PtFilmParams), C.c_void_p]
+        l.pt_film_add_lens.restype = C.c_int
+        l.pt_film_add_lens.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(PtCamera), C.POINTER(PtLens), _dp, C.POINTER(PtFilmParams), _dp]
+        l.pt_film_add_lens_device.restype = C.c_int
+        l.pt_film_add_lens_device.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(PtCamera), C.POINTER(PtLens), C.c_void_p, C.POINTER(PtFilmParams), C.c_void_p]
+        l.pt_test_lens_rays_host.restype = C.c_int
+        l.pt_test_lens_rays_host.argtypes = [C.POINTER(PtCamera), C.POINTER(PtLens), C.c_uint32, C.c_uint32, C.c_uint64, C.c_int32, C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _dp, _dp]
         l.pt_film_resolve.restype = C.c_int
         l.pt_film_resolve.argtypes = [C.c_void_p, C.c_void_p, _u8p, _dp]
         l.pt_film_resolve_device.restype = C.c_int

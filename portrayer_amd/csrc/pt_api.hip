@@ -16,6 +16,7 @@
 #include "pt_gather_inst.h"
 #include "pt_probe_inst.h"
 #include "pt_film_inst.h"
+#include "pt_lens_inst.h"
 #include "pt_film_map_inst.h"
 #include "pt_denoise.h"
 #include "pt_render_inst.h"
@@ -2606,6 +2607,10 @@ static hipError_t pt_film_dispatch(const PtFilmArgs& a, bool tex, bool park, int
     PT_MODE_LAUNCH(pt_film_launch_mode_, a.r.scene.mode, a, tex, park, n_cu, stream, grid, launch)
 }
 
+static hipError_t pt_lens_dispatch(const PtLensArgs& a, bool tex, bool park, int n_cu, hipStream_t stream, uint32_t* grid, bool launch) {
+    PT_MODE_LAUNCH(pt_lens_launch_mode_, a.f.r.scene.mode, a, tex, park, n_cu, stream, grid, launch)
+}
+
 #define PT_FILM_COUNT_MAX 0x80000000u  // a pixel holds at most 2^31 samples: count + a launch's lane offset never wraps
 
 // The context's own film, and no pass of its own in flight (`busy`: calls that read or write its state from the host). The handle is looked up, not
@@ -2666,7 +2671,7 @@ extern "C" int pt_film_reset(pt_context* c, pt_film* f) {
 
 // Everything that can be refused without a HIP call, in the order the header gives.
 static int pt_film_add_check(pt_context* c, pt_film* f, const pt_camera* cam, const double* background, const pt_film_params* p) {
-    if (!c || !f || !cam || !background || !p) return pt_fail(c, PT_ERR_ARGUMENT, "pt_film_add: NULL context, film, camera, background or params");
+    if (!c || !f || !cam || !background || !p) return pt_fail(c, PT_ERR_ARGUMENT, "pt_film_add / pt_film_add_lens: NULL context, film, camera, background or params");
     int rc = pt_film_handle(c, f, false, "pt_film_add");
     if (rc) return rc;
     if (p->sample_mode != PT_SAMPLE_CENTRE && p->sample_mode != PT_SAMPLE_RNG) return pt_fail(c, PT_ERR_ARGUMENT, "pt_film_add: bad sample_mode");
@@ -2706,7 +2711,9 @@ static int pt_film_pass_args(pt_context* c, pt_film* f, const pt_camera* cam, co
     return PT_OK;
 }
 
-static int pt_film_add_common(pt_context* c, pt_film* f, const pt_camera* cam, const double* d_background, const pt_film_params* p, hipStream_t stream) {
+// lens: NULL for pt_film_add's pinhole samples (pt_film_kernel); else the lens contract's (pt_lens_kernel, pt_lens_inst.hip), which takes the same block with
+// the lens behind it. Nothing but the launcher differs.
+static int pt_film_add_common(pt_context* c, pt_film* f, const pt_camera* cam, const double* d_background, const pt_film_params* p, const pt_lens* lens, hipStream_t stream) {
     PtPass& v = c->radiance.pass;
     uint32_t lw = PT_FILM_LW;
     if (const char* e = getenv("PORTRAYER_FILM_LW")) { const int w = atoi(e); if (w == 8 || w == 64) lw = (uint32_t)w; }  // measurements (profiles/film)
@@ -2716,6 +2723,13 @@ static int pt_film_add_common(pt_context* c, pt_film* f, const pt_camera* cam, c
     int rc = pt_film_pass_args(c, f, cam, d_background, p->slice, p->seed, p->sample_mode, p->background_rows, lw, a, k);
     if (rc) return rc;
     const uint32_t tiles = a.r.n_slots / 64u;
+    auto dispatch = [&](uint32_t* g, bool launch) {
+        if (!lens) return pt_film_dispatch(a, k.tex, k.park, c->n_cu, stream, g, launch);
+        PtLensArgs la;
+        la.f = a;
+        la.lens.model = lens->model; la.lens.aperture = lens->aperture; la.lens.focus = lens->focus; la.lens.extent = lens->extent;
+        return pt_lens_dispatch(la, k.tex, k.park, c->n_cu, stream, g, launch);
+    };
     // the buffers are sized for the add's largest launch (its first: min(samples, lw) samples per pixel); the later ones use a prefix of the same lanes
     auto set_launch = [&](uint32_t m) {
         a.launch_samples = m;
@@ -2724,7 +2738,7 @@ static int pt_film_add_common(pt_context* c, pt_film* f, const pt_camera* cam, c
     };
     set_launch(std::min(p->samples, lw));
     uint32_t grid = 0;
-    PT_HIP(c, pt_film_dispatch(a, k.tex, k.park, c->n_cu, stream, &grid, false));
+    PT_HIP(c, dispatch(&grid, false));
     if ((rc = pt_reserve(c, f->staging, (size_t)a.r.n_slots * a.lw * 24))) return rc;
     a.staging = (double*)f->staging.p;
     if ((rc = pt_pass_open(c, v, a.r, grid, true, stream))) return rc;
@@ -2733,7 +2747,7 @@ static int pt_film_add_common(pt_context* c, pt_film* f, const pt_camera* cam, c
         set_launch(m);
         if (!first) PT_HIP(c, hipMemsetAsync((char*)v.misc.p + 256, 0, PT_PASS_MISC_BYTES - 256, stream));  // the queues again; the overflow flag stays
         uint32_t g = 0;
-        PT_HIP(c, pt_film_dispatch(a, k.tex, k.park, c->n_cu, stream, &g, true));  // (g <= grid: no more items than the launch the buffers were sized for)
+        PT_HIP(c, dispatch(&g, true));  // (g <= grid: no more items than the launch the buffers were sized for)
         if (f->moments)  // the fold that keeps q as well: a uniform "map" of m, round 0 (pt_film_map.hip)
             PT_HIP(c, pt_film_fold_map_launch(a, nullptr, m, 0u, (double*)f->total.p, (double*)f->partial.p, (uint32_t*)f->count.p, (double*)f->q.p, stream));
         else
@@ -2748,26 +2762,85 @@ static int pt_film_add_common(pt_context* c, pt_film* f, const pt_camera* cam, c
     return PT_OK;
 }
 
-extern "C" int pt_film_add(pt_context* c, pt_film* f, const pt_camera* cam, const double* background, const pt_film_params* p, double* kernel_ms) {
+// What pt_film_add_lens refuses beyond pt_film_add's list, in the header's order. No HIP call.
+static int pt_lens_check(pt_context* c, const pt_lens* l) {
+    if (!l) return pt_fail(c, PT_ERR_ARGUMENT, "pt_film_add_lens: NULL lens");
+    if (l->model != PT_LENS_THIN && l->model != PT_LENS_ORTHO && l->model != PT_LENS_STEREO) return pt_fail(c, PT_ERR_ARGUMENT, "pt_film_add_lens: unknown lens model");
+    if (l->model == PT_LENS_THIN) {
+        if (!std::isfinite(l->aperture) || l->aperture < 0.0) return pt_fail(c, PT_ERR_ARGUMENT, "pt_film_add_lens: aperture must be finite and not negative");
+        if (!std::isfinite(l->focus) || !(l->focus > 0.0)) return pt_fail(c, PT_ERR_ARGUMENT, "pt_film_add_lens: focus must be finite and positive");
+    } else if (!std::isfinite(l->extent) || !(l->extent > 0.0)) {
+        return pt_fail(c, PT_ERR_ARGUMENT, "pt_film_add_lens: extent must be finite and positive");
+    }
+    return PT_OK;
+}
+
+// pt_film_add and pt_film_add_lens (lens_call: the check of `lens` stands behind pt_film_add's own refusals; lens == NULL otherwise)
+static int pt_film_add_host(pt_context* c, pt_film* f, const pt_camera* cam, const pt_lens* lens, bool lens_call, const double* background, const pt_film_params* p, double* kernel_ms) {
     int rc = pt_film_add_check(c, f, cam, background, p);
     if (rc) return rc;
+    if (lens_call && (rc = pt_lens_check(c, lens))) return rc;
     if (kernel_ms) *kernel_ms = 0.0;
     if (pt_film_slice_empty(p)) return PT_OK;
     PT_HIP(c, hipSetDevice(c->device));
     const size_t bg_bytes = (p->background_rows ? (size_t)f->height : (size_t)f->height * f->width) * 24;
     if ((rc = pt_reserve(c, f->bg, bg_bytes))) return rc;
     PT_HIP(c, hipMemcpy(f->bg.p, background, bg_bytes, hipMemcpyHostToDevice));
-    if ((rc = pt_pass_settle(c, c->radiance.pass, pt_film_add_common(c, f, cam, (const double*)f->bg.p, p, nullptr)))) return rc;
+    if ((rc = pt_pass_settle(c, c->radiance.pass, pt_film_add_common(c, f, cam, (const double*)f->bg.p, p, lens, nullptr)))) return rc;
     return pt_pass_result(c, c->radiance.pass, kernel_ms);
 }
 
-extern "C" int pt_film_add_device(pt_context* c, pt_film* f, const pt_camera* cam, const double* d_background, const pt_film_params* p, void* hip_stream) {
+static int pt_film_add_queued(pt_context* c, pt_film* f, const pt_camera* cam, const pt_lens* lens, bool lens_call, const double* d_background, const pt_film_params* p, void* hip_stream) {
     int rc = pt_film_add_check(c, f, cam, d_background, p);
     if (rc) return rc;
+    if (lens_call && (rc = pt_lens_check(c, lens))) return rc;
     if (pt_film_slice_empty(p)) return PT_OK;  // nothing queued, nothing to finish
     PT_HIP(c, hipSetDevice(c->device));
-    if ((rc = pt_pass_device_tail(c, c->radiance.pass, pt_film_add_common(c, f, cam, d_background, p, (hipStream_t)hip_stream)))) return rc;
+    if ((rc = pt_pass_device_tail(c, c->radiance.pass, pt_film_add_common(c, f, cam, d_background, p, lens, (hipStream_t)hip_stream)))) return rc;
     c->film_open = f;
+    return PT_OK;
+}
+
+extern "C" int pt_film_add(pt_context* c, pt_film* f, const pt_camera* cam, const double* background, const pt_film_params* p, double* kernel_ms) {
+    return pt_film_add_host(c, f, cam, nullptr, false, background, p, kernel_ms);
+}
+
+extern "C" int pt_film_add_device(pt_context* c, pt_film* f, const pt_camera* cam, const double* d_background, const pt_film_params* p, void* hip_stream) {
+    return pt_film_add_queued(c, f, cam, nullptr, false, d_background, p, hip_stream);
+}
+
+extern "C" int pt_film_add_lens(pt_context* c, pt_film* f, const pt_camera* cam, const pt_lens* lens, const double* background, const pt_film_params* p, double* kernel_ms) {
+    return pt_film_add_host(c, f, cam, lens, true, background, p, kernel_ms);
+}
+
+extern "C" int pt_film_add_lens_device(pt_context* c, pt_film* f, const pt_camera* cam, const pt_lens* lens, const double* d_background, const pt_film_params* p, void* hip_stream) {
+    return pt_film_add_queued(c, f, cam, lens, true, d_background, p, hip_stream);
+}
+
+// Steps 1 to 6 of the lens contract on the host: pt_lens_jitter and pt_lens_ray as this translation unit's host pass compiles them (-ffp-contract=off). The
+// film's width gives the stream index y width + x; pixels outside width x height, a bad sample mode or a lens pt_film_add_lens refuses: PT_ERR_ARGUMENT.
+extern "C" int pt_test_lens_rays_host(const pt_camera* cam, const pt_lens* lens, uint32_t width, uint32_t height, uint64_t seed, int32_t sample_mode, uint64_t n, const uint32_t* pixels_xy,
+                                      const uint32_t* samples, double* origins, double* directions) {
+    if (!cam || !lens || !pixels_xy || !samples || !origins || !directions) return PT_ERR_ARGUMENT;
+    if (sample_mode != PT_SAMPLE_CENTRE && sample_mode != PT_SAMPLE_RNG) return PT_ERR_ARGUMENT;
+    if (pt_lens_check(nullptr, lens)) return PT_ERR_ARGUMENT;
+    PtCamera pc;
+    for (int k = 0; k < 3; k++) pc.eye[k] = cam->eye[k];
+    for (int k = 0; k < 12; k++) pc.view_to_world[k] = cam->view_to_world[k];
+    pc.fov_factor = cam->fov_factor; pc.aspect = cam->aspect_ratio; pc.width = cam->width; pc.height = cam->height;  // (pt_fill_args)
+    PtLensSet ls;
+    ls.model = lens->model; ls.aperture = lens->aperture; ls.focus = lens->focus; ls.extent = lens->extent;
+    for (uint64_t i = 0; i < n; i++)
+        if (pixels_xy[2 * i] >= width || pixels_xy[2 * i + 1] >= height) return PT_ERR_ARGUMENT;
+    for (uint64_t i = 0; i < n; i++) {
+        const uint32_t x = pixels_xy[2 * i], y = pixels_xy[2 * i + 1], s = samples[i];
+        const uint64_t pixel = (uint64_t)y * width + x;
+        double jx, jy;
+        pt_lens_jitter(seed, sample_mode == PT_SAMPLE_RNG, pixel, s, &jx, &jy);
+        const PtRay r = pt_lens_ray(pc, ls, seed, pixel, s, (double)x + jx, (double)y + jy);
+        origins[3 * i] = r.o.x; origins[3 * i + 1] = r.o.y; origins[3 * i + 2] = r.o.z;
+        directions[3 * i] = r.d.x; directions[3 * i + 1] = r.d.y; directions[3 * i + 2] = r.d.z;
+    }
     return PT_OK;
 }
 

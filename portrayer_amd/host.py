@@ -4,6 +4,7 @@ Image::render) and drives the gfx950 kernels through the C ABI. No CPU fallback 
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 from typing import Optional
 
@@ -19,7 +20,7 @@ _dp, _ip, _up, _u64p, _u8p = H._dp, H._ip, H._up, H._u64p, H._u8p
 
 EXPORTS = ["ph_last_error", "ph_scene_create", "ph_example_scene", "ph_scene_destroy", "ph_scene_counts", "ph_scene_export", "ph_scene_export_textures",
            "ph_scene_flatten", "ph_scene_kdtree", "ph_scene_kdmesh_tree", "ph_camera", "ph_obj_load", "ph_renderer_create", "ph_renderer_destroy",
-           "ph_renderer_context", "ph_renderer_ranks", "ph_renderer_node", "ph_renderer_prepare_ms", "ph_renderer_render", "ph_renderer_aov", "ph_renderer_rays", "ph_renderer_segments", "ph_renderer_ao", "ph_renderer_ao_camera", "ph_renderer_gather", "ph_renderer_gather_camera", "ph_renderer_probe", "ph_renderer_chart_triangles", "ph_renderer_chart_mesh", "ph_renderer_chart", "ph_renderer_ao_chart", "ph_renderer_gather_chart", "ph_renderer_direct", "ph_renderer_direct_camera", "ph_renderer_direct_chart", "ph_renderer_radiance", "ph_renderer_film_create", "ph_renderer_film_destroy", "ph_renderer_film_reset", "ph_renderer_film_add", "ph_renderer_film_resolve", "ph_renderer_film_counts", "ph_renderer_film_create_moments", "ph_renderer_film_add_map", "ph_renderer_film_error", "ph_renderer_film_refine", "ph_renderer_film_denoise", "ph_renderer_guides", "ph_renderer_film_denoise_albedo", "ph_renderer_update", "ph_scene_same_structure", "ph_renderer_deform", "ph_scene_same_topology", "ph_renderer_deform_device", "ph_renderer_mesh_count", "ph_renderer_mesh_vertices", "ph_example_render_to_png", "ph_png_read", "ph_png_write", "ph_image_read", "ph_scene_graph"]
+           "ph_renderer_context", "ph_renderer_ranks", "ph_renderer_node", "ph_renderer_prepare_ms", "ph_renderer_render", "ph_renderer_aov", "ph_renderer_rays", "ph_renderer_segments", "ph_renderer_ao", "ph_renderer_ao_camera", "ph_renderer_gather", "ph_renderer_gather_camera", "ph_renderer_probe", "ph_renderer_chart_triangles", "ph_renderer_chart_mesh", "ph_renderer_chart", "ph_renderer_ao_chart", "ph_renderer_gather_chart", "ph_renderer_direct", "ph_renderer_direct_camera", "ph_renderer_direct_chart", "ph_renderer_radiance", "ph_renderer_film_create", "ph_renderer_film_destroy", "ph_renderer_film_reset", "ph_renderer_film_add", "ph_renderer_film_add_lens", "ph_renderer_film_resolve", "ph_renderer_film_counts", "ph_renderer_film_create_moments", "ph_renderer_film_add_map", "ph_renderer_film_error", "ph_renderer_film_refine", "ph_renderer_film_denoise", "ph_renderer_guides", "ph_renderer_film_denoise_albedo", "ph_renderer_update", "ph_scene_same_structure", "ph_renderer_deform", "ph_scene_same_topology", "ph_renderer_deform_device", "ph_renderer_mesh_count", "ph_renderer_mesh_vertices", "ph_example_render_to_png", "ph_png_read", "ph_png_write", "ph_image_read", "ph_scene_graph"]
 
 
 class PortrayerHostError(RuntimeError):
@@ -123,6 +124,7 @@ def lib() -> C.CDLL:
         l.ph_renderer_film_destroy.restype = C.c_int; l.ph_renderer_film_destroy.argtypes = [vp, vp]
         l.ph_renderer_film_reset.restype = C.c_int; l.ph_renderer_film_reset.argtypes = [vp, vp]
         l.ph_renderer_film_add.restype = C.c_int; l.ph_renderer_film_add.argtypes = [vp, vp, _dp, _dp, C.POINTER(H.PtFilmParams), _dp]
+        l.ph_renderer_film_add_lens.restype = C.c_int; l.ph_renderer_film_add_lens.argtypes = [vp, vp, _dp, C.POINTER(H.PtLens), _dp, C.POINTER(H.PtFilmParams), _dp]
         l.ph_renderer_film_resolve.restype = C.c_int; l.ph_renderer_film_resolve.argtypes = [vp, vp, _u8p, _dp]
         l.ph_renderer_film_counts.restype = C.c_int; l.ph_renderer_film_counts.argtypes = [vp, vp, _up]
         l.ph_renderer_film_create_moments.restype = C.c_int; l.ph_renderer_film_create_moments.argtypes = [vp, C.c_uint32, C.c_uint32, C.POINTER(vp)]
@@ -381,6 +383,50 @@ def _device_tensor_pointer(t, shape, device: int, what: str) -> int:
     return int(t.data_ptr())
 
 
+class Lens:
+    """What stands in for the pinhole when a film takes samples (Film.add(..., lens=)): made by Lens.thin, Lens.ortho or Lens.fisheye. The rays are a contract
+    (pt_film_add_lens): every sample is, to the bit, what Renderer.radiance answers for the ray the contract states."""
+
+    def __init__(self, model: int, aperture: float = 0.0, focus: float = 1.0, extent: float = 1.0):
+        self.model, self.aperture, self.focus, self.extent = model, aperture, focus, extent
+
+    @staticmethod
+    def _number(name, v, positive):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not (0.0 < float(v) if positive else 0.0 <= float(v)) or not float(v) < float("inf"):
+            raise ValueError("%s must be a finite number %s 0, got %r" % (name, ">" if positive else ">=", v))
+        return float(v)
+
+    @classmethod
+    def thin(cls, aperture: float, focus: float) -> "Lens":
+        """A thin lens of radius `aperture` (world units; 0 is the pinhole, bit for bit) that is sharp at the distance `focus` along the view axis. The lens
+        points of 64 consecutive samples of a pixel are stratified over the disc."""
+        return cls(H.LENS_THIN, aperture=cls._number("aperture", aperture, False), focus=cls._number("focus", focus, True))
+
+    @classmethod
+    def ortho(cls, half_height: float) -> "Lens":
+        """An orthographic view: parallel rays along the view axis from a window of height 2 x half_height (world units) through the eye."""
+        return cls(H.LENS_ORTHO, extent=cls._number("half_height", half_height, True))
+
+    @classmethod
+    def fisheye(cls, fov_degrees: float) -> "Lens":
+        """A stereographic fisheye of `fov_degrees` (0 .. 360, exclusive) across the image height."""
+        fov = cls._number("fov_degrees", fov_degrees, True)
+        if not fov < 360.0:
+            raise ValueError("fov_degrees must be below 360, got %r" % (fov_degrees,))
+        return cls(H.LENS_STEREO, extent=math.tan(math.radians(fov) / 4.0))
+
+    def struct(self) -> "H.PtLens":
+        """The pt_lens of this lens, checked as pt_film_add_lens checks it."""
+        if isinstance(self.model, bool) or self.model not in (H.LENS_THIN, H.LENS_ORTHO, H.LENS_STEREO):
+            raise ValueError("lens: unknown model %r" % (self.model,))
+        if self.model == H.LENS_THIN:
+            self._number("aperture", self.aperture, False)
+            self._number("focus", self.focus, True)
+        else:
+            self._number("extent", self.extent, True)
+        return H.PtLens(int(self.model), float(self.aperture), float(self.focus), float(self.extent))
+
+
 class Film:
     """A width x height accumulator in the renderer's device memory (pt_film_*): add() gives pixels their next samples, resolve() gives at every pixel the
     bits of Renderer.render(samples = that pixel's count) - provided every add used the same camera, background, seed and sample mode and the scene did not
@@ -410,9 +456,14 @@ class Film:
         except Exception:
             pass
 
-    def add(self, cam10, background, samples: int = 1, seed: int = 0, sample_mode: int = H.SAMPLE_CENTRE, rect=None) -> float:
+    def add(self, cam10, background, samples: int = 1, seed: int = 0, sample_mode: int = H.SAMPLE_CENTRE, rect=None, lens: Optional[Lens] = None) -> float:
         """`samples` more samples for every pixel of `rect` (x0, y0, x1, y1 inclusive; default: the whole film), each taken as render() takes that sample of
-        that pixel. `background` is (H, 3) or (H, W, 3) as for render(). Returns the device time in ms."""
+        that pixel. `background` is (H, 3) or (H, W, 3) as for render(). Returns the device time in ms.
+        lens: a Lens (Lens.thin for depth of field, Lens.ortho, Lens.fisheye) whose primary rays replace the pinhole's (pt_film_add_lens); everything behind
+        the primary ray, the counts and the fold are the same, and a film may mix lens and plain adds. None is the pinhole."""
+        if lens is not None and not isinstance(lens, Lens):
+            raise ValueError("lens must be a host.Lens or None, got %r" % (lens,))
+        lens_struct = lens.struct() if lens is not None else None
         bg = np.ascontiguousarray(background, dtype=np.float64)
         rows = 1 if bg.shape == (self.height, 3) else 0
         if not rows and bg.shape != (self.height, self.width, 3):
@@ -425,6 +476,9 @@ class Film:
         p = H.PtFilmParams(H.PtRect(x0, y0, x1, y1), int(samples), int(seed), sample_mode, rows)
         c = np.ascontiguousarray(cam10, dtype=np.float64)
         ms = C.c_double(0.0)
+        if lens_struct is not None:
+            _check(lib().ph_renderer_film_add_lens(self._r._h, self._h, _p(c, _dp), C.byref(lens_struct), _p(bg, _dp), C.byref(p), C.byref(ms)), "ph_renderer_film_add_lens")
+            return ms.value
         _check(lib().ph_renderer_film_add(self._r._h, self._h, _p(c, _dp), _p(bg, _dp), C.byref(p), C.byref(ms)), "ph_renderer_film_add")
         return ms.value
 
@@ -521,7 +575,9 @@ class Film:
         variance of r + g + b. Pixels without samples keep what `into` / `linear_into` / `variance_into` hold (zeros when the arrays are made here).
         albedo=True filters DEMODULATED colour (pt_film_denoise_albedo): the diffuse colour under each pixel, from one guides pass on the device that also writes
         the guides, is divided out before the levels and multiplied back after them, so texture detail is not blurred. An (H, W, 3) float64 array is the caller's
-        albedo, as Renderer.guides() returns it, and needs `guides`. False is the plain filter."""
+        albedo, as Renderer.guides() returns it, and needs `guides`. False is the plain filter.
+        The guides made here come from a PINHOLE primary-visibility pass: for a film whose samples came through a lens (add(lens=)) supply your own `guides=`
+        or leave the filter out."""
         iterations = self._integer("iterations", iterations, 1, 8)
         sig = []
         for name, v in (("sigma_color", sigma_color), ("sigma_plane", sigma_plane)):

@@ -1076,6 +1076,15 @@ extern "C" int ph_renderer_film_add(ph_renderer* r, ph_film* film, const double 
     });
 }
 
+// The same behind a lens (pt_film_add_lens): the camera is the one a render of the film's size gets, the lens is the caller's.
+extern "C" int ph_renderer_film_add_lens(ph_renderer* r, ph_film* film, const double camera[10], const pt_lens* lens, const double* background, const pt_film_params* p, double* kernel_ms) {
+    if (!r || !film || !camera || !lens || !background || !p) return bad("null argument");
+    return guarded([&]() -> int {
+        pt_camera pc = detail::Camera(camera_from(camera), (double)film->width, (double)film->height).to_abi();
+        return film_rc(r, pt_film_add_lens(r->r->context(), film->f, &pc, lens, background, p, kernel_ms));
+    });
+}
+
 extern "C" int ph_renderer_film_resolve(ph_renderer* r, ph_film* film, uint8_t* rgb, double* linear) {
     if (!r || !film || (!rgb && !linear)) return bad("null argument");
     return guarded([&]() -> int { return film_rc(r, pt_film_resolve(r->r->context(), film->f, rgb, linear)); });

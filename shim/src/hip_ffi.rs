@@ -161,6 +161,10 @@ pub struct PtFilmParams {                  // pt_film_params: one add to a film 
     pub slice: PtRect, pub samples: u32, pub seed: u64, pub sample_mode: i32, pub background_rows: i32,
 }
 #[repr(C)]
+pub struct PtLens {                        // pt_lens: what stands in for the pinhole in pt_film_add_lens; model 0 thin lens (aperture, focus), 1 orthographic, 2 stereographic (extent)
+    pub model: i32, pub aperture: f64, pub focus: f64, pub extent: f64,
+}
+#[repr(C)]
 pub struct PtFilmMapParams {               // pt_film_map_params: one add with a budget per pixel - pixel p of `slice` gets its next min(budget[p], max_samples) samples
     pub slice: PtRect, pub max_samples: u32, pub seed: u64, pub sample_mode: i32, pub background_rows: i32,
 }
@@ -285,6 +289,12 @@ extern "C" {
                        kernel_ms: *mut f64) -> c_int;
     pub fn pt_film_add_device(ctx: *mut PtContext, film: *mut PtFilm, camera: *const PtCamera, d_background: *const f64, params: *const PtFilmParams,
                               hip_stream: *mut c_void) -> c_int;
+    // the same adds behind a lens (depth of field, an orthographic view, a fisheye): only the primary ray differs, by a contract of f64 operations (pt_lens.h);
+    // counts, fold, bookkeeping and refusals are pt_film_add's, then a NULL lens, an unknown model, a bad aperture / focus / extent
+    pub fn pt_film_add_lens(ctx: *mut PtContext, film: *mut PtFilm, camera: *const PtCamera, lens: *const PtLens, background: *const f64,
+                            params: *const PtFilmParams, kernel_ms: *mut f64) -> c_int;
+    pub fn pt_film_add_lens_device(ctx: *mut PtContext, film: *mut PtFilm, camera: *const PtCamera, lens: *const PtLens, d_background: *const f64,
+                                   params: *const PtFilmParams, hip_stream: *mut c_void) -> c_int;
     pub fn pt_film_resolve(ctx: *mut PtContext, film: *mut PtFilm, rgb: *mut u8, linear: *mut f64) -> c_int;
     pub fn pt_film_resolve_device(ctx: *mut PtContext, film: *mut PtFilm, d_rgb: *mut c_void, d_linear: *mut f64, hip_stream: *mut c_void) -> c_int;
     pub fn pt_film_counts(ctx: *mut PtContext, film: *mut PtFilm, counts: *mut u32) -> c_int;

@@ -20,7 +20,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LLVM = os.environ.get("LLVM_BIN", "/opt/rocm/lib/llvm/bin")
 
 
-PASSES = ("render", "aov", "guides", "rays", "segments", "ao", "radiance", "gather", "direct", "probe", "film", "film_map")
+PASSES = ("render", "aov", "guides", "rays", "segments", "ao", "radiance", "gather", "direct", "probe", "film", "film_map", "lens")
 SINGLES = ("pt_api.o", "pt_scene.o", "pt_build.o", "pt_node.o", "pt_rays_sort.o", "pt_film.o", "pt_film_map.o", "pt_denoise.o", "pt_denoise_albedo.o", "pt_chart.o", "pt_probe.o")
 
 
