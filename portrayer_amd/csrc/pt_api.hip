@@ -561,6 +561,49 @@ static int pt_pass_settle(pt_context* c, PtPass& v, int rc) {
     return rc ? rc : rc_wait;
 }
 
+// The staging of a host-buffer entry point, the same for every kind: a table with a row per array of the caller's and the PtBuf that holds its device copy.
+// A row whose host pointer is null is absent: an output not asked for, an optional input not given.
+struct PtStage {
+    const void* in;  // the caller's array that goes to the device in front of the pass ...
+    void* out;       // ... or the one that comes back behind it
+    PtBuf* buf;
+    size_t bytes;
+    void* dev;       // buf's memory once pt_stage_in has reserved it; null for an absent row
+};
+static PtStage pt_stage_input(const void* host, PtBuf& buf, size_t bytes) { return {host, nullptr, &buf, bytes, nullptr}; }
+static PtStage pt_stage_output(void* host, PtBuf& buf, size_t bytes) { return {nullptr, host, &buf, bytes, nullptr}; }
+
+// In front of the kind's _common: every row's PtBuf reserved, in the table's order, then the inputs copied in.
+template <int N>
+static int pt_stage_in(pt_context* c, PtStage (&rows)[N]) {
+    for (PtStage& s : rows) {
+        if (!s.in && !s.out) continue;
+        if (int rc = pt_reserve(c, *s.buf, s.bytes)) return rc;
+        s.dev = s.buf->p;
+    }
+    for (PtStage& s : rows)
+        if (s.in && s.bytes) PT_HIP(c, hipMemcpy(s.dev, s.in, s.bytes, hipMemcpyHostToDevice));
+    return PT_OK;
+}
+
+// Behind it; rc: what queueing returned. The pass settled (pt_pass_settle), then the outputs copied back, then the pass's result. window (pt_aov, pt_guides):
+// the rows are images of window's size and only its slice's rectangle comes back (the kernel wrote nothing else, and the device copies hold nothing else of
+// value): picking one pixel of a 1920x1080 frame moves 68 bytes, and pixels outside the slice keep the caller's bytes because they are never touched.
+template <int N>
+static int pt_stage_out(pt_context* c, PtPass& v, int rc, PtStage (&rows)[N], double* kernel_ms, const pt_aov_params* window = nullptr) {
+    if ((rc = pt_pass_settle(c, v, rc))) return rc;
+    for (PtStage& s : rows) {
+        if (!s.out) continue;
+        if (!window) { PT_HIP(c, hipMemcpy(s.out, s.dev, s.bytes, hipMemcpyDeviceToHost)); continue; }
+        const pt_rect& sl = window->slice;
+        if (sl.x1 < sl.x0 || sl.y1 < sl.y0) break;
+        const size_t elem = s.bytes / ((size_t)window->width * window->height), cols = (size_t)sl.x1 - sl.x0 + 1, lines = (size_t)sl.y1 - sl.y0 + 1;
+        const size_t pitch = (size_t)window->width * elem, first = ((size_t)sl.y0 * window->width + sl.x0) * elem;
+        PT_HIP(c, hipMemcpy2D((char*)s.out + first, pitch, (const char*)s.dev + first, pitch, cols * elem, lines, hipMemcpyDeviceToHost));
+    }
+    return pt_pass_result(c, v, kernel_ms);
+}
+
 // A _finish entry point (c is not NULL); none: what it says when no _device call of the pass is open.
 static int pt_pass_finish(pt_context* c, PtPass& v, const char* none, double* kernel_ms) {
     if (!v.pending) return pt_fail(c, PT_ERR_ARGUMENT, none);
@@ -1631,29 +1674,12 @@ extern "C" int pt_aov(pt_context* c, const pt_camera* cam, const pt_aov_params* 
     if (rc) return rc;
     PT_HIP(c, hipSetDevice(c->device));
     const size_t px = (size_t)p->width * p->height;
-    void* host[6] = {host_out->depth, host_out->position, host_out->normal, host_out->node, host_out->sub, host_out->material};
-    const size_t elem[6] = {8, 24, 24, 4, 4, 4};  // bytes per pixel
-    void* dev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    for (int k = 0; k < 6; k++) {
-        if (!host[k]) continue;
-        if ((rc = pt_reserve(c, c->aov.out[k], px * elem[k]))) return rc;
-        dev[k] = c->aov.out[k].p;
-    }
-    pt_aov_buffers d_out;
-    d_out.depth = (double*)dev[0]; d_out.position = (double*)dev[1]; d_out.normal = (double*)dev[2];
-    d_out.node = (int32_t*)dev[3]; d_out.sub = (int32_t*)dev[4]; d_out.material = (int32_t*)dev[5];
-    if ((rc = pt_pass_settle(c, c->aov.pass, pt_aov_common(c, cam, p, d_out, nullptr)))) return rc;
-    // Only the slice's rectangle comes back (the kernel wrote nothing else, and the device copies hold nothing else of value): picking one pixel of a
-    // 1920x1080 frame moves 68 bytes, and pixels outside the slice keep the caller's bytes because they are never touched.
-    if (p->slice.x1 >= p->slice.x0 && p->slice.y1 >= p->slice.y0) {
-        const size_t cols = (size_t)p->slice.x1 - p->slice.x0 + 1, rows = (size_t)p->slice.y1 - p->slice.y0 + 1;
-        for (int k = 0; k < 6; k++) {
-            if (!host[k]) continue;
-            const size_t pitch = (size_t)p->width * elem[k], first = ((size_t)p->slice.y0 * p->width + p->slice.x0) * elem[k];
-            PT_HIP(c, hipMemcpy2D((char*)host[k] + first, pitch, (const char*)dev[k] + first, pitch, cols * elem[k], rows, hipMemcpyDeviceToHost));
-        }
-    }
-    return pt_pass_result(c, c->aov.pass, kernel_ms);
+    PtBuf* out = c->aov.out;
+    PtStage s[6] = {pt_stage_output(host_out->depth, out[0], px * 8), pt_stage_output(host_out->position, out[1], px * 24), pt_stage_output(host_out->normal, out[2], px * 24),
+                    pt_stage_output(host_out->node, out[3], px * 4), pt_stage_output(host_out->sub, out[4], px * 4), pt_stage_output(host_out->material, out[5], px * 4)};
+    if ((rc = pt_stage_in(c, s))) return rc;
+    const pt_aov_buffers d_out = {(double*)s[0].dev, (double*)s[1].dev, (double*)s[2].dev, (int32_t*)s[3].dev, (int32_t*)s[4].dev, (int32_t*)s[5].dev};
+    return pt_stage_out(c, c->aov.pass, pt_aov_common(c, cam, p, d_out, nullptr), s, kernel_ms, p);  // (only the slice's rectangle comes back)
 }
 
 extern "C" int pt_aov_device(pt_context* c, const pt_camera* cam, const pt_aov_params* p, const pt_aov_buffers* device_out, void* hip_stream) {
@@ -1716,28 +1742,11 @@ extern "C" int pt_guides(pt_context* c, const pt_camera* cam, const pt_aov_param
     if (rc) return rc;
     PT_HIP(c, hipSetDevice(c->device));
     const size_t px = (size_t)p->width * p->height;
-    void* host[4] = {host_out->albedo, host_out->position, host_out->normal, host_out->node};
-    PtBuf* buf[4] = {&c->aov.albedo, &c->aov.out[1], &c->aov.out[2], &c->aov.out[3]};
-    const size_t elem[4] = {24, 24, 24, 4};  // bytes per pixel
-    void* dev[4] = {nullptr, nullptr, nullptr, nullptr};
-    for (int k = 0; k < 4; k++) {
-        if (!host[k]) continue;
-        if ((rc = pt_reserve(c, *buf[k], px * elem[k]))) return rc;
-        dev[k] = buf[k]->p;
-    }
-    pt_guides_buffers d_out;
-    d_out.albedo = (double*)dev[0]; d_out.position = (double*)dev[1]; d_out.normal = (double*)dev[2]; d_out.node = (int32_t*)dev[3];
-    if ((rc = pt_pass_settle(c, c->aov.pass, pt_guides_common(c, cam, p, d_out, nullptr)))) return rc;
-    // only the slice's rectangle comes back, as in pt_aov: pixels outside it keep the caller's bytes
-    if (p->slice.x1 >= p->slice.x0 && p->slice.y1 >= p->slice.y0) {
-        const size_t cols = (size_t)p->slice.x1 - p->slice.x0 + 1, rows = (size_t)p->slice.y1 - p->slice.y0 + 1;
-        for (int k = 0; k < 4; k++) {
-            if (!host[k]) continue;
-            const size_t pitch = (size_t)p->width * elem[k], first = ((size_t)p->slice.y0 * p->width + p->slice.x0) * elem[k];
-            PT_HIP(c, hipMemcpy2D((char*)host[k] + first, pitch, (const char*)dev[k] + first, pitch, cols * elem[k], rows, hipMemcpyDeviceToHost));
-        }
-    }
-    return pt_pass_result(c, c->aov.pass, kernel_ms);
+    PtStage s[4] = {pt_stage_output(host_out->albedo, c->aov.albedo, px * 24), pt_stage_output(host_out->position, c->aov.out[1], px * 24),
+                    pt_stage_output(host_out->normal, c->aov.out[2], px * 24), pt_stage_output(host_out->node, c->aov.out[3], px * 4)};
+    if ((rc = pt_stage_in(c, s))) return rc;
+    const pt_guides_buffers d_out = {(double*)s[0].dev, (double*)s[1].dev, (double*)s[2].dev, (int32_t*)s[3].dev};
+    return pt_stage_out(c, c->aov.pass, pt_guides_common(c, cam, p, d_out, nullptr), s, kernel_ms, p);  // (only the slice's rectangle comes back, as in pt_aov)
 }
 
 extern "C" int pt_guides_device(pt_context* c, const pt_camera* cam, const pt_aov_params* p, const pt_guides_buffers* device_out, void* hip_stream) {
@@ -1831,27 +1840,12 @@ extern "C" int pt_chart(pt_context* c, const pt_chart_params* p, const double* u
     if (rc) return rc;
     PT_HIP(c, hipSetDevice(c->device));
     const size_t n = (size_t)p->width * p->height, n_tris = c->res.meshes[mesh].tri_count;
-    void* host[4] = {host_out->position, host_out->normal, host_out->tri, host_out->covered};
-    PtBuf* buf[4] = {&c->aov.out[1], &c->aov.out[2], &c->aov.out[3], &c->aov.chart_covered};
-    const size_t elem[4] = {24, 24, 4, 1};  // bytes per texel
-    void* dev[4] = {nullptr, nullptr, nullptr, nullptr};
-    for (int k = 0; k < 4; k++) {
-        if (!host[k]) continue;
-        if ((rc = pt_reserve(c, *buf[k], n * elem[k]))) return rc;
-        dev[k] = buf[k]->p;
-    }
-    const double* d_uv = nullptr;
-    if (uv) {
-        if ((rc = pt_reserve(c, c->aov.chart_uv, n_tris * 48))) return rc;
-        if (n_tris) PT_HIP(c, hipMemcpy(c->aov.chart_uv.p, uv, n_tris * 48, hipMemcpyHostToDevice));
-        d_uv = (const double*)c->aov.chart_uv.p;
-    }
-    pt_chart_buffers d_out;
-    d_out.position = (double*)dev[0]; d_out.normal = (double*)dev[1]; d_out.tri = (int32_t*)dev[2]; d_out.covered = (uint8_t*)dev[3];
-    if ((rc = pt_pass_settle(c, c->aov.pass, pt_chart_common(c, p, mesh, d_uv, d_out, nullptr)))) return rc;
-    for (int k = 0; k < 4; k++)
-        if (host[k]) PT_HIP(c, hipMemcpy(host[k], dev[k], n * elem[k], hipMemcpyDeviceToHost));
-    return pt_pass_result(c, c->aov.pass, kernel_ms);
+    PtStage s[5] = {pt_stage_output(host_out->position, c->aov.out[1], n * 24), pt_stage_output(host_out->normal, c->aov.out[2], n * 24),
+                    pt_stage_output(host_out->tri, c->aov.out[3], n * 4), pt_stage_output(host_out->covered, c->aov.chart_covered, n),
+                    pt_stage_input(uv, c->aov.chart_uv, n_tris * 48)};  // (uv null: the row is absent, and d_uv null)
+    if ((rc = pt_stage_in(c, s))) return rc;
+    const pt_chart_buffers d_out = {(double*)s[0].dev, (double*)s[1].dev, (int32_t*)s[2].dev, (uint8_t*)s[3].dev};
+    return pt_stage_out(c, c->aov.pass, pt_chart_common(c, p, mesh, (const double*)s[4].dev, d_out, nullptr), s, kernel_ms);
 }
 
 extern "C" int pt_chart_device(pt_context* c, const pt_chart_params* p, const double* d_uv, const pt_chart_buffers* device_out, void* hip_stream) {
@@ -1955,28 +1949,14 @@ static int pt_rays_host(pt_context* c, const pt_rays_params* p, const double* or
     if (p->n == 0) return PT_OK;
     PT_HIP(c, hipSetDevice(c->device));
     const size_t n = (size_t)p->n;
-    void* host[7] = {host_out->t, host_out->position, host_out->normal, host_out->node, host_out->sub, host_out->material, host_out->occluded};
-    const size_t elem[7] = {8, 24, 24, 4, 4, 4, 1};  // bytes per ray
-    void* dev[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    int rc;
-    if ((rc = pt_reserve(c, c->rays.in[0], n * 24)) || (rc = pt_reserve(c, c->rays.in[1], n * 24))) return rc;
-    if (t_max && (rc = pt_reserve(c, c->rays.in_t_max, n * 8))) return rc;
-    for (int k = 0; k < 7; k++) {
-        if (!host[k]) continue;
-        if ((rc = pt_reserve(c, c->rays.out[k], n * elem[k]))) return rc;
-        dev[k] = c->rays.out[k].p;
-    }
-    PT_HIP(c, hipMemcpy(c->rays.in[0].p, origins, n * 24, hipMemcpyHostToDevice));
-    PT_HIP(c, hipMemcpy(c->rays.in[1].p, directions, n * 24, hipMemcpyHostToDevice));
-    if (t_max) PT_HIP(c, hipMemcpy(c->rays.in_t_max.p, t_max, n * 8, hipMemcpyHostToDevice));
-    pt_rays_buffers d_out;
-    d_out.t = (double*)dev[0]; d_out.position = (double*)dev[1]; d_out.normal = (double*)dev[2];
-    d_out.node = (int32_t*)dev[3]; d_out.sub = (int32_t*)dev[4]; d_out.material = (int32_t*)dev[5]; d_out.occluded = (uint8_t*)dev[6];
-    rc = pt_rays_common(c, p, (const double*)c->rays.in[0].p, (const double*)c->rays.in[1].p, d_out, nullptr, t_max ? (const double*)c->rays.in_t_max.p : nullptr);
-    if ((rc = pt_pass_settle(c, c->rays.pass, rc))) return rc;
-    for (int k = 0; k < 7; k++)
-        if (host[k]) PT_HIP(c, hipMemcpy(host[k], dev[k], n * elem[k], hipMemcpyDeviceToHost));
-    return pt_pass_result(c, c->rays.pass, kernel_ms);
+    pt_context::Rays& v = c->rays;
+    PtStage s[10] = {pt_stage_input(origins, v.in[0], n * 24), pt_stage_input(directions, v.in[1], n * 24), pt_stage_input(t_max, v.in_t_max, n * 8),  // (pt_rays: no t_max row)
+                     pt_stage_output(host_out->t, v.out[0], n * 8), pt_stage_output(host_out->position, v.out[1], n * 24), pt_stage_output(host_out->normal, v.out[2], n * 24),
+                     pt_stage_output(host_out->node, v.out[3], n * 4), pt_stage_output(host_out->sub, v.out[4], n * 4), pt_stage_output(host_out->material, v.out[5], n * 4),
+                     pt_stage_output(host_out->occluded, v.out[6], n)};
+    if (int rc = pt_stage_in(c, s)) return rc;
+    const pt_rays_buffers d_out = {(double*)s[3].dev, (double*)s[4].dev, (double*)s[5].dev, (int32_t*)s[6].dev, (int32_t*)s[7].dev, (int32_t*)s[8].dev, (uint8_t*)s[9].dev};
+    return pt_stage_out(c, v.pass, pt_rays_common(c, p, (const double*)s[0].dev, (const double*)s[1].dev, d_out, nullptr, (const double*)s[2].dev), s, kernel_ms);
 }
 
 // ... and the device-buffer path of both.
@@ -2033,7 +2013,9 @@ static const char* pt_ao_params_error(const pt_ao_params* p) {
     return nullptr;
 }
 
-static PtAoSet pt_ao_set(const pt_ao_params* p) {
+// What steps 1 to 8 read of a parameter block, pt_ao's or pt_gather's (the eye only with PT_AO_FACE_EYE).
+template <class Params>
+static PtAoSet pt_ao_set(const Params* p) {
     PtAoSet s;
     s.seed = p->seed; s.first_index = p->first_index; s.pass = p->pass; s.flags = p->flags; s.bias = p->bias;
     s.eye = (p->flags & PT_AO_FACE_EYE) ? pt_v3(p->eye[0], p->eye[1], p->eye[2]) : pt_v3(0.0, 0.0, 0.0);
@@ -2095,25 +2077,12 @@ extern "C" int pt_ao(pt_context* c, const pt_ao_params* p, const double* positio
     PT_HIP(c, hipSetDevice(c->device));
     const size_t n = (size_t)p->n;
     // the ray-query pass's device copies: positions and normals where it keeps origins and directions, the results in three of its output buffers
-    void* host[3] = {host_out->occluded, host_out->valid, host_out->bent};
-    PtBuf* buf[3] = {&c->rays.out[3], &c->rays.out[6], &c->rays.out[1]};
-    const size_t elem[3] = {4, 1, 24};  // bytes per point
-    void* dev[3] = {nullptr, nullptr, nullptr};
-    if ((rc = pt_reserve(c, c->rays.in[0], n * 24)) || (rc = pt_reserve(c, c->rays.in[1], n * 24))) return rc;
-    for (int k = 0; k < 3; k++) {
-        if (!host[k]) continue;
-        if ((rc = pt_reserve(c, *buf[k], n * elem[k]))) return rc;
-        dev[k] = buf[k]->p;
-    }
-    PT_HIP(c, hipMemcpy(c->rays.in[0].p, positions, n * 24, hipMemcpyHostToDevice));
-    PT_HIP(c, hipMemcpy(c->rays.in[1].p, normals, n * 24, hipMemcpyHostToDevice));
-    pt_ao_buffers d_out;
-    d_out.occluded = (uint32_t*)dev[0]; d_out.valid = (uint8_t*)dev[1]; d_out.bent = (double*)dev[2];
-    rc = pt_ao_common(c, p, (const double*)c->rays.in[0].p, (const double*)c->rays.in[1].p, d_out, nullptr);
-    if ((rc = pt_pass_settle(c, c->rays.pass, rc))) return rc;
-    for (int k = 0; k < 3; k++)
-        if (host[k]) PT_HIP(c, hipMemcpy(host[k], dev[k], n * elem[k], hipMemcpyDeviceToHost));
-    return pt_pass_result(c, c->rays.pass, kernel_ms);
+    pt_context::Rays& v = c->rays;
+    PtStage s[5] = {pt_stage_input(positions, v.in[0], n * 24), pt_stage_input(normals, v.in[1], n * 24),
+                    pt_stage_output(host_out->occluded, v.out[3], n * 4), pt_stage_output(host_out->valid, v.out[6], n), pt_stage_output(host_out->bent, v.out[1], n * 24)};
+    if ((rc = pt_stage_in(c, s))) return rc;
+    const pt_ao_buffers d_out = {(uint32_t*)s[2].dev, (uint8_t*)s[3].dev, (double*)s[4].dev};
+    return pt_stage_out(c, v.pass, pt_ao_common(c, p, (const double*)s[0].dev, (const double*)s[1].dev, d_out, nullptr), s, kernel_ms);
 }
 
 extern "C" int pt_ao_device(pt_context* c, const pt_ao_params* p, const double* d_positions, const double* d_normals, const pt_ao_buffers* device_out, void* hip_stream) {
@@ -2221,25 +2190,12 @@ extern "C" int pt_direct(pt_context* c, const pt_direct_params* p, const double*
     PT_HIP(c, hipSetDevice(c->device));
     const size_t n = (size_t)p->n;
     // the ray-query pass's device copies: positions and normals where it keeps origins and directions, the results in three of its output buffers
-    void* host[3] = {host_out->sum, host_out->lit, host_out->valid};
-    PtBuf* buf[3] = {&c->rays.out[1], &c->rays.out[3], &c->rays.out[6]};
-    const size_t elem[3] = {24, 4, 1};  // bytes per point
-    void* dev[3] = {nullptr, nullptr, nullptr};
-    if ((rc = pt_reserve(c, c->rays.in[0], n * 24)) || (rc = pt_reserve(c, c->rays.in[1], n * 24))) return rc;
-    for (int k = 0; k < 3; k++) {
-        if (!host[k]) continue;
-        if ((rc = pt_reserve(c, *buf[k], n * elem[k]))) return rc;
-        dev[k] = buf[k]->p;
-    }
-    PT_HIP(c, hipMemcpy(c->rays.in[0].p, positions, n * 24, hipMemcpyHostToDevice));
-    PT_HIP(c, hipMemcpy(c->rays.in[1].p, normals, n * 24, hipMemcpyHostToDevice));
-    pt_direct_buffers d_out;
-    d_out.sum = (double*)dev[0]; d_out.lit = (uint32_t*)dev[1]; d_out.valid = (uint8_t*)dev[2];
-    rc = pt_direct_common(c, p, (const double*)c->rays.in[0].p, (const double*)c->rays.in[1].p, d_out, nullptr);
-    if ((rc = pt_pass_settle(c, c->rays.pass, rc))) return rc;
-    for (int k = 0; k < 3; k++)
-        if (host[k]) PT_HIP(c, hipMemcpy(host[k], dev[k], n * elem[k], hipMemcpyDeviceToHost));
-    return pt_pass_result(c, c->rays.pass, kernel_ms);
+    pt_context::Rays& v = c->rays;
+    PtStage s[5] = {pt_stage_input(positions, v.in[0], n * 24), pt_stage_input(normals, v.in[1], n * 24),
+                    pt_stage_output(host_out->sum, v.out[1], n * 24), pt_stage_output(host_out->lit, v.out[3], n * 4), pt_stage_output(host_out->valid, v.out[6], n)};
+    if ((rc = pt_stage_in(c, s))) return rc;
+    const pt_direct_buffers d_out = {(double*)s[2].dev, (uint32_t*)s[3].dev, (uint8_t*)s[4].dev};
+    return pt_stage_out(c, v.pass, pt_direct_common(c, p, (const double*)s[0].dev, (const double*)s[1].dev, d_out, nullptr), s, kernel_ms);
 }
 
 extern "C" int pt_direct_device(pt_context* c, const pt_direct_params* p, const double* d_positions, const double* d_normals, const pt_direct_buffers* device_out, void* hip_stream) {
@@ -2339,14 +2295,11 @@ extern "C" int pt_radiance(pt_context* c, const pt_radiance_params* p, const dou
     PT_HIP(c, hipSetDevice(c->device));
     pt_context::Radiance& v = c->radiance;
     const size_t n = (size_t)p->n, bg_bytes = p->background_per_ray ? n * 24 : 24;
-    if ((rc = pt_reserve(c, v.in[0], n * 24)) || (rc = pt_reserve(c, v.in[1], n * 24)) || (rc = pt_reserve(c, v.in[2], bg_bytes)) || (rc = pt_reserve(c, v.out, n * 24))) return rc;
-    PT_HIP(c, hipMemcpy(v.in[0].p, origins, n * 24, hipMemcpyHostToDevice));
-    PT_HIP(c, hipMemcpy(v.in[1].p, directions, n * 24, hipMemcpyHostToDevice));
-    PT_HIP(c, hipMemcpy(v.in[2].p, background, bg_bytes, hipMemcpyHostToDevice));
-    rc = pt_radiance_common(c, p, (const double*)v.in[0].p, (const double*)v.in[1].p, (const double*)v.in[2].p, (double*)v.out.p, nullptr);
-    if ((rc = pt_pass_settle(c, v.pass, rc))) return rc;
-    PT_HIP(c, hipMemcpy(rgb, v.out.p, n * 24, hipMemcpyDeviceToHost));
-    return pt_pass_result(c, v.pass, kernel_ms);
+    PtStage s[4] = {pt_stage_input(origins, v.in[0], n * 24), pt_stage_input(directions, v.in[1], n * 24), pt_stage_input(background, v.in[2], bg_bytes),
+                    pt_stage_output(rgb, v.out, n * 24)};
+    if ((rc = pt_stage_in(c, s))) return rc;
+    rc = pt_radiance_common(c, p, (const double*)s[0].dev, (const double*)s[1].dev, (const double*)s[2].dev, (double*)s[3].dev, nullptr);
+    return pt_stage_out(c, v.pass, rc, s, kernel_ms);
 }
 
 extern "C" int pt_radiance_device(pt_context* c, const pt_radiance_params* p, const double* d_origins, const double* d_directions, const double* d_background, double* d_rgb, void* hip_stream) {
@@ -2399,9 +2352,7 @@ static int pt_gather_common(pt_context* c, const pt_gather_params* p, const doub
     a.r.scene = c->view;
     a.r.seed = p->seed;
     a.n = p->n; a.positions = d_positions; a.normals = d_normals;
-    // what steps 1 to 8 read (pt_ao_set: the eye only with PT_AO_FACE_EYE)
-    a.set.seed = p->seed; a.set.first_index = p->first_index; a.set.pass = p->pass; a.set.flags = p->flags; a.set.bias = p->bias;
-    a.set.eye = (p->flags & PT_AO_FACE_EYE) ? pt_v3(p->eye[0], p->eye[1], p->eye[2]) : pt_v3(0.0, 0.0, 0.0);
+    a.set = pt_ao_set(p);
     a.samples = p->samples;
     while ((1u << a.log2_samples) < p->samples) a.log2_samples++;
     for (int k = 0; k < 3; k++) a.background[k] = background[k];
@@ -2426,19 +2377,11 @@ extern "C" int pt_gather(pt_context* c, const pt_gather_params* p, const double*
     pt_context::Radiance& v = c->radiance;
     const size_t n = (size_t)p->n;
     // the radiance pass's device copies: positions and normals where it keeps origins and directions, the sums in its output, the flags where its background goes
-    if ((rc = pt_reserve(c, v.in[0], n * 24)) || (rc = pt_reserve(c, v.in[1], n * 24))) return rc;
-    if (host_out->sum && (rc = pt_reserve(c, v.out, n * 24))) return rc;
-    if (host_out->valid && (rc = pt_reserve(c, v.in[2], n))) return rc;
-    PT_HIP(c, hipMemcpy(v.in[0].p, positions, n * 24, hipMemcpyHostToDevice));
-    PT_HIP(c, hipMemcpy(v.in[1].p, normals, n * 24, hipMemcpyHostToDevice));
-    pt_gather_buffers d_out;
-    d_out.sum = host_out->sum ? (double*)v.out.p : nullptr;
-    d_out.valid = host_out->valid ? (uint8_t*)v.in[2].p : nullptr;
-    rc = pt_gather_common(c, p, (const double*)v.in[0].p, (const double*)v.in[1].p, background, d_out, nullptr);
-    if ((rc = pt_pass_settle(c, v.pass, rc))) return rc;
-    if (host_out->sum) PT_HIP(c, hipMemcpy(host_out->sum, d_out.sum, n * 24, hipMemcpyDeviceToHost));
-    if (host_out->valid) PT_HIP(c, hipMemcpy(host_out->valid, d_out.valid, n, hipMemcpyDeviceToHost));
-    return pt_pass_result(c, v.pass, kernel_ms);
+    PtStage s[4] = {pt_stage_input(positions, v.in[0], n * 24), pt_stage_input(normals, v.in[1], n * 24),
+                    pt_stage_output(host_out->sum, v.out, n * 24), pt_stage_output(host_out->valid, v.in[2], n)};
+    if ((rc = pt_stage_in(c, s))) return rc;
+    const pt_gather_buffers d_out = {(double*)s[2].dev, (uint8_t*)s[3].dev};
+    return pt_stage_out(c, v.pass, pt_gather_common(c, p, (const double*)s[0].dev, (const double*)s[1].dev, background, d_out, nullptr), s, kernel_ms);
 }
 
 extern "C" int pt_gather_device(pt_context* c, const pt_gather_params* p, const double* d_positions, const double* d_normals, const double* background,
@@ -2543,18 +2486,10 @@ extern "C" int pt_probe(pt_context* c, const pt_probe_params* p, const double* p
     pt_context::Radiance& v = c->radiance;
     const size_t n = (size_t)p->n, sh_bytes = n * PT_PROBE_VALUES * sizeof(double);
     // the radiance pass's device copies: positions where it keeps origins, the sums in its output, the flags where its background goes
-    if ((rc = pt_reserve(c, v.in[0], n * 24))) return rc;
-    if (host_out->sh && (rc = pt_reserve(c, v.out, sh_bytes))) return rc;
-    if (host_out->valid && (rc = pt_reserve(c, v.in[2], n))) return rc;
-    PT_HIP(c, hipMemcpy(v.in[0].p, positions, n * 24, hipMemcpyHostToDevice));
-    pt_probe_buffers d_out;
-    d_out.sh = host_out->sh ? (double*)v.out.p : nullptr;
-    d_out.valid = host_out->valid ? (uint8_t*)v.in[2].p : nullptr;
-    rc = pt_probe_common(c, p, (const double*)v.in[0].p, background, d_out, nullptr);
-    if ((rc = pt_pass_settle(c, v.pass, rc))) return rc;
-    if (host_out->sh) PT_HIP(c, hipMemcpy(host_out->sh, d_out.sh, sh_bytes, hipMemcpyDeviceToHost));
-    if (host_out->valid) PT_HIP(c, hipMemcpy(host_out->valid, d_out.valid, n, hipMemcpyDeviceToHost));
-    return pt_pass_result(c, v.pass, kernel_ms);
+    PtStage s[3] = {pt_stage_input(positions, v.in[0], n * 24), pt_stage_output(host_out->sh, v.out, sh_bytes), pt_stage_output(host_out->valid, v.in[2], n)};
+    if ((rc = pt_stage_in(c, s))) return rc;
+    const pt_probe_buffers d_out = {(double*)s[1].dev, (uint8_t*)s[2].dev};
+    return pt_stage_out(c, v.pass, pt_probe_common(c, p, (const double*)s[0].dev, background, d_out, nullptr), s, kernel_ms);
 }
 
 extern "C" int pt_probe_device(pt_context* c, const pt_probe_params* p, const double* d_positions, const double* background, const pt_probe_buffers* device_out,

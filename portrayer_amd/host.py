@@ -383,6 +383,64 @@ def _device_tensor_pointer(t, shape, device: int, what: str) -> int:
     return int(t.data_ptr())
 
 
+_POINTER = {np.float64: _dp, np.int32: _ip, np.uint32: _up, np.uint8: _u8p}
+
+
+def _want_names(table, want) -> tuple:
+    """`want` as a tuple of names of `table`, a pass's *_BUFFERS"""
+    want = tuple(want)
+    unknown = [n for n in want if n not in table]
+    if unknown or not want:
+        raise ValueError("want must name some of %s, got %r" % (", ".join(table), want))
+    return want
+
+
+def _want_buffers(table, struct_type, want, into, shape):
+    """What a pass writes into: for every name of `want` the caller's array in `into`, or zeros - of `shape` and the tail `table` (a pass's *_BUFFERS) gives the
+    name, as components (1: none) or as a tuple. Returns them by name, and the pass's buffer struct pointed at them."""
+    out, b = {}, struct_type()
+    for name in _want_names(table, want):
+        dtype, tail = table[name]
+        if not isinstance(tail, tuple):
+            tail = () if tail == 1 else (tail,)
+        full = shape + tail
+        a = into[name] if into is not None and name in into else np.zeros(full, dtype=dtype)
+        if not isinstance(a, np.ndarray) or a.shape != full or a.dtype != dtype or not a.flags.c_contiguous:
+            raise ValueError("into[%r] must be a C-contiguous %s array of shape %r" % (name, np.dtype(dtype).name, full))
+        out[name] = a
+        setattr(b, name, _p(a, _POINTER[dtype]))
+    return out, b
+
+
+def _points_and_normals(points, normals):
+    """(n, 3) float64 points and normals, C-contiguous"""
+    P, N = np.asarray(points), np.asarray(normals)
+    if P.ndim != 2 or P.shape[1] != 3 or P.shape != N.shape:
+        raise ValueError("points and normals must both be (n, 3), got %r and %r" % (P.shape, N.shape))
+    if P.dtype != np.float64 or N.dtype != np.float64:
+        raise ValueError("points and normals must be float64, got %s and %s" % (P.dtype, N.dtype))
+    return np.ascontiguousarray(P), np.ascontiguousarray(N)
+
+
+def _positive_size(width, height):
+    for name, v in (("width", width), ("height", height)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or int(v) < 1:
+            raise ValueError("%s must be a positive integer, got %r" % (name, v))
+
+
+def _camera_numbers(cam10) -> np.ndarray:
+    c = np.ascontiguousarray(cam10, dtype=np.float64)
+    if c.shape != (10,):
+        raise ValueError("cam10 must hold 10 numbers, got shape %r" % (c.shape,))
+    return c
+
+
+def _uv_on_the_host(method: str, uv):
+    """the forms that chain two passes in the library take the chart's UV set from the host"""
+    if uv is not None and not isinstance(uv, np.ndarray):
+        raise ValueError("%s takes uv as a numpy array or None; chart() takes tensors" % method)
+
+
 class Lens:
     """What stands in for the pinhole when a film takes samples (Film.add(..., lens=)): made by Lens.thin, Lens.ortho or Lens.fisheye. The rays are a contract
     (pt_film_add_lens): every sample is, to the bit, what Renderer.radiance answers for the ray the contract states."""
@@ -769,10 +827,7 @@ class Renderer:
         computed. Pixels outside `rect` are not written: they keep what `into` (a dict of arrays of the right shape and dtype) holds there; without `into` the
         arrays start zero-filled (so outside `rect` depth is 0.0 and the ids are 0, not the miss values). `material` indexes the Renderer's material table: the
         numbering of Scene.flatten()["material"], materials in the order the flattened nodes first use them (not the order of Scene.export()["materials"])."""
-        want = tuple(want)
-        unknown = [n for n in want if n not in H.AOV_BUFFERS]
-        if unknown or not want:
-            raise ValueError("want must name some of %s, got %r" % (", ".join(H.AOV_BUFFERS), want))
+        want = _want_names(H.AOV_BUFFERS, want)
         x0, y0, x1, y1 = rect if rect is not None else (0, 0, width - 1, height - 1)
         p = H.PtAovParams(width, height, H.PtRect(x0, y0, x1, y1), (C.c_double * 2)(float(offset[0]), float(offset[1])))
         out, b = {}, H.PtAovBuffers()
@@ -794,21 +849,10 @@ class Renderer:
         """What a denoiser needs of each pixel (pt_guides), in one trace: aov()'s `position`, `normal` and `node` - the same bits - and `albedo`, (H, W, 3) float64,
         the diffuse colour at the primary hit (the material's, or its texture's texel as the render path reads it; 0 where nothing is hit). `rect`, `offset`,
         `want` and `into` work as in aov(); returns the arrays named in `want` and `kernel_ms`."""
-        want = tuple(want)
-        unknown = [n for n in want if n not in H.GUIDES_BUFFERS]
-        if unknown or not want:
-            raise ValueError("want must name some of %s, got %r" % (", ".join(H.GUIDES_BUFFERS), want))
+        want = _want_names(H.GUIDES_BUFFERS, want)
         x0, y0, x1, y1 = rect if rect is not None else (0, 0, width - 1, height - 1)
         p = H.PtAovParams(width, height, H.PtRect(x0, y0, x1, y1), (C.c_double * 2)(float(offset[0]), float(offset[1])))
-        out, b = {}, H.PtGuidesBuffers()
-        for name in want:
-            dtype, comps = H.GUIDES_BUFFERS[name]
-            shape = (height, width) if comps == 1 else (height, width, comps)
-            a = into[name] if into is not None and name in into else np.zeros(shape, dtype=dtype)
-            if not isinstance(a, np.ndarray) or a.shape != shape or a.dtype != dtype or not a.flags.c_contiguous:
-                raise ValueError("into[%r] must be a C-contiguous %s array of shape %r" % (name, np.dtype(dtype).name, shape))
-            out[name] = a
-            setattr(b, name, _p(a, _dp if dtype is np.float64 else _ip))
+        out, b = _want_buffers(H.GUIDES_BUFFERS, H.PtGuidesBuffers, want, into, (height, width))
         ms = C.c_double(0.0)
         c = np.ascontiguousarray(cam10, dtype=np.float64)
         _check(lib().ph_renderer_guides(self._h, _p(c, _dp), C.byref(p), C.byref(b), C.byref(ms)), "ph_renderer_guides")
@@ -823,10 +867,7 @@ class Renderer:
         Rays with a non-finite component, an all-zero direction or a component beyond 1e18 are not traced and report a miss. `material` is numbered as in aov().
         `t_max` (pt_segments): a scalar or an (n,) float64 array, in units of the direction like t; ray i then answers for the segment [EPSILON, t_max[i]) only -
         the nearest hit inside it, or with any_hit whether there is one - and a bound that is NaN or <= EPSILON reports a miss. None is the unbounded pass."""
-        want = (("occluded",) if any_hit else tuple(H.RAYS_BUFFERS)) if want is None else tuple(want)
-        unknown = [n for n in want if n not in H.RAYS_BUFFERS]
-        if unknown or not want:
-            raise ValueError("want must name some of %s, got %r" % (", ".join(H.RAYS_BUFFERS), want))
+        want = _want_names(H.RAYS_BUFFERS, (("occluded",) if any_hit else tuple(H.RAYS_BUFFERS)) if want is None else want)
         if any_hit and want != ("occluded",):
             raise ValueError("any_hit=True answers only 'occluded', got want=%r" % (want,))
         o, d = np.asarray(origins), np.asarray(directions)
@@ -889,23 +930,6 @@ class Renderer:
         return H.PtAoParams(n, int(samples), int(pass_index), int(seed), int(first_index), float(radius), float(bias), flags, (C.c_double * 3)(*e))
 
     @staticmethod
-    def _ao_buffers(want, into, shape):
-        want = tuple(want)
-        unknown = [n for n in want if n not in H.AO_BUFFERS]
-        if unknown or not want:
-            raise ValueError("want must name some of %s, got %r" % (", ".join(H.AO_BUFFERS), want))
-        out, b = {}, H.PtAoBuffers()
-        for name in want:
-            dtype, comps = H.AO_BUFFERS[name]
-            full = shape if comps == 1 else shape + (comps,)
-            a = into[name] if into is not None and name in into else np.zeros(full, dtype=dtype)
-            if not isinstance(a, np.ndarray) or a.shape != full or a.dtype != dtype or not a.flags.c_contiguous:
-                raise ValueError("into[%r] must be a C-contiguous %s array of shape %r" % (name, np.dtype(dtype).name, full))
-            out[name] = a
-            setattr(b, name, _p(a, {np.uint32: _up, np.uint8: _u8p, np.float64: _dp}[dtype]))
-        return out, b
-
-    @staticmethod
     def _ao_result(out, samples, ms):
         if "occluded" in out:
             out["visibility"] = 1.0 - out["occluded"].astype(np.float64) / float(samples)  # (1.0 at invalid points: they count no occluder)
@@ -922,15 +946,10 @@ class Renderer:
         `kernel_ms`. A point with a non-finite component, one beyond 1e18 or a zero normal is invalid: occluded 0, valid 0, bent 0, visibility 1. Point i draws
         its rotation from the stream (seed, first_index + i, pass_index): a slice [k, k + m) with first_index=k gives that slice of the whole, and another
         pass_index gives other rays to sum. `into`: a dict of C-contiguous arrays of the right shape and dtype to write into."""
-        P, N = np.asarray(points), np.asarray(normals)
-        if P.ndim != 2 or P.shape[1] != 3 or P.shape != N.shape:
-            raise ValueError("points and normals must both be (n, 3), got %r and %r" % (P.shape, N.shape))
-        if P.dtype != np.float64 or N.dtype != np.float64:
-            raise ValueError("points and normals must be float64, got %s and %s" % (P.dtype, N.dtype))
+        P, N = _points_and_normals(points, normals)
         n = P.shape[0]
         p = self._ao_params(n, samples, radius, bias, seed, pass_index, first_index, eye)
-        out, b = self._ao_buffers(want, into, (n,))
-        P, N = np.ascontiguousarray(P), np.ascontiguousarray(N)
+        out, b = _want_buffers(H.AO_BUFFERS, H.PtAoBuffers, want, into, (n,))
         ms = C.c_double(0.0)
         _check(lib().ph_renderer_ao(self._h, C.byref(p), _p(P, _dp), _p(N, _dp), C.byref(b), C.byref(ms)), "ph_renderer_ao")
         return self._ao_result(out, samples, ms)
@@ -940,14 +959,10 @@ class Renderer:
         """Ambient occlusion under every pixel (pt_aov_device then pt_ao_device on the device): the points are what aov() finds at the pixel centres, the normals
         turned towards the camera's eye, pixel (x, y) the stream index y * width + x - the bits of ao(aov's position, aov's normal, eye=the eye). Nothing per
         pixel crosses the bus but the results: arrays of shape (H, W) - `bent` (H, W, 3) - as in ao(); pixels that see nothing are invalid points."""
-        for name, v in (("width", width), ("height", height)):
-            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or int(v) < 1:
-                raise ValueError("%s must be a positive integer, got %r" % (name, v))
+        _positive_size(width, height)
         p = self._ao_params(int(width) * int(height), samples, radius, bias, seed, pass_index, 0, None)
-        out, b = self._ao_buffers(want, into, (int(height), int(width)))
-        c = np.ascontiguousarray(cam10, dtype=np.float64)
-        if c.shape != (10,):
-            raise ValueError("cam10 must hold 10 numbers, got shape %r" % (c.shape,))
+        out, b = _want_buffers(H.AO_BUFFERS, H.PtAoBuffers, want, into, (int(height), int(width)))
+        c = _camera_numbers(cam10)
         ms = C.c_double(0.0)
         _check(lib().ph_renderer_ao_camera(self._h, _p(c, _dp), int(width), int(height), C.byref(p), C.byref(b), C.byref(ms)), "ph_renderer_ao_camera")
         return self._ao_result(out, samples, ms)
@@ -960,23 +975,6 @@ class Renderer:
         if bg.shape != (3,):
             raise ValueError("background must be 3 numbers, got shape %r" % (bg.shape,))
         return H.PtGatherParams(a.n, a.samples, a.pass_index, a.seed, a.first_index, a.bias, a.flags, a.eye), bg
-
-    @staticmethod
-    def _gather_buffers(want, into, shape):
-        want = tuple(want)
-        unknown = [n for n in want if n not in H.GATHER_BUFFERS]
-        if unknown or not want:
-            raise ValueError("want must name some of %s, got %r" % (", ".join(H.GATHER_BUFFERS), want))
-        out, b = {}, H.PtGatherBuffers()
-        for name in want:
-            dtype, comps = H.GATHER_BUFFERS[name]
-            full = shape if comps == 1 else shape + (comps,)
-            a = into[name] if into is not None and name in into else np.zeros(full, dtype=dtype)
-            if not isinstance(a, np.ndarray) or a.shape != full or a.dtype != dtype or not a.flags.c_contiguous:
-                raise ValueError("into[%r] must be a C-contiguous %s array of shape %r" % (name, np.dtype(dtype).name, full))
-            out[name] = a
-            setattr(b, name, _p(a, {np.uint8: _u8p, np.float64: _dp}[dtype]))
-        return out, b
 
     @staticmethod
     def _gather_result(out, samples, ms):
@@ -996,15 +994,10 @@ class Renderer:
         non-finite component, one beyond 1e18 or a zero normal is invalid: sum 0, valid 0. The bits are those of radiance() on ao()'s rays, flattened point-major,
         with stream_base = first_index * samples and sample = pass_index, summed in order: a slice [k, k + m) with first_index=k gives that slice of the whole, and
         another pass_index gives other rays and draws to sum. `into`: a dict of C-contiguous arrays of the right shape and dtype to write into."""
-        P, N = np.asarray(points), np.asarray(normals)
-        if P.ndim != 2 or P.shape[1] != 3 or P.shape != N.shape:
-            raise ValueError("points and normals must both be (n, 3), got %r and %r" % (P.shape, N.shape))
-        if P.dtype != np.float64 or N.dtype != np.float64:
-            raise ValueError("points and normals must be float64, got %s and %s" % (P.dtype, N.dtype))
+        P, N = _points_and_normals(points, normals)
         n = P.shape[0]
         p, bg = self._gather_params(n, background, samples, bias, seed, pass_index, first_index, eye)
-        out, b = self._gather_buffers(want, into, (n,))
-        P, N = np.ascontiguousarray(P), np.ascontiguousarray(N)
+        out, b = _want_buffers(H.GATHER_BUFFERS, H.PtGatherBuffers, want, into, (n,))
         ms = C.c_double(0.0)
         _check(lib().ph_renderer_gather(self._h, C.byref(p), _p(P, _dp), _p(N, _dp), _p(bg, _dp), C.byref(b), C.byref(ms)), "ph_renderer_gather")
         return self._gather_result(out, samples, ms)
@@ -1015,14 +1008,10 @@ class Renderer:
         normals turned towards the camera's eye, pixel (x, y) the stream index y * width + x - the bits of gather(aov's position, aov's normal, eye=the eye).
         Nothing per pixel crosses the bus but the results: `sum` and `mean` (H, W, 3), `valid` (H, W), as in gather(); the irradiance estimate is pi x mean;
         pixels that see nothing are invalid points."""
-        for name, v in (("width", width), ("height", height)):
-            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or int(v) < 1:
-                raise ValueError("%s must be a positive integer, got %r" % (name, v))
+        _positive_size(width, height)
         p, bg = self._gather_params(int(width) * int(height), background, samples, bias, seed, pass_index, 0, None)
-        out, b = self._gather_buffers(want, into, (int(height), int(width)))
-        c = np.ascontiguousarray(cam10, dtype=np.float64)
-        if c.shape != (10,):
-            raise ValueError("cam10 must hold 10 numbers, got shape %r" % (c.shape,))
+        out, b = _want_buffers(H.GATHER_BUFFERS, H.PtGatherBuffers, want, into, (int(height), int(width)))
+        c = _camera_numbers(cam10)
         ms = C.c_double(0.0)
         _check(lib().ph_renderer_gather_camera(self._h, _p(c, _dp), int(width), int(height), C.byref(p), _p(bg, _dp), C.byref(b), C.byref(ms)), "ph_renderer_gather_camera")
         return self._gather_result(out, samples, ms)
@@ -1045,9 +1034,7 @@ class Renderer:
     def _chart_params(self, node, width, height, uv, flip_normal):
         """chart()'s, ao_chart()'s and gather_chart()'s argument checks: the pt_chart_params, and the UV set as a (T, 6) float64 array per corner, a torch tensor
         on the renderer's GPU, or None (the mesh's own texture coordinates)"""
-        for name, v in (("width", width), ("height", height)):
-            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or int(v) < 1:
-                raise ValueError("%s must be a positive integer, got %r" % (name, v))
+        _positive_size(width, height)
         if int(width) * int(height) > H.AO_MAX:
             raise ValueError("at most %d texels per map" % H.AO_MAX)
         if not isinstance(flip_normal, (bool, np.bool_)):
@@ -1077,24 +1064,13 @@ class Renderer:
         `covered` (H, W) uint8 - and `kernel_ms`. Unowned texels hold zeros: invalid points for ao() and gather(). flip_normal negates every normal (the inside
         of a room). `uv` and the arrays of `into` may be torch tensors on the renderer's GPU (float64 / int32 / uint8, contiguous): the pass is then queued on
         torch's current stream (pt_chart_device), waited for, and what `into` does not hold comes back as tensors too."""
-        want = tuple(want)
-        unknown = [n for n in want if n not in H.CHART_BUFFERS]
-        if unknown or not want:
-            raise ValueError("want must name some of %s, got %r" % (", ".join(H.CHART_BUFFERS), want))
+        want = _want_names(H.CHART_BUFFERS, want)
         p, uv = self._chart_params(node, width, height, uv, flip_normal)
         shape = (int(height), int(width))
         on_device = (uv is not None and not isinstance(uv, np.ndarray)) or (into is not None and any(not isinstance(into[n], np.ndarray) for n in want if n in into))
         if on_device:
             return self._chart_on_device(p, uv, want, into, shape)
-        out, b = {}, H.PtChartBuffers()
-        for name in want:
-            dtype, comps = H.CHART_BUFFERS[name]
-            full = shape if comps == 1 else shape + (comps,)
-            a = into[name] if into is not None and name in into else np.zeros(full, dtype=dtype)
-            if not isinstance(a, np.ndarray) or a.shape != full or a.dtype != dtype or not a.flags.c_contiguous:
-                raise ValueError("into[%r] must be a C-contiguous %s array of shape %r" % (name, np.dtype(dtype).name, full))
-            out[name] = a
-            setattr(b, name, _p(a, {np.int32: _ip, np.uint8: _u8p, np.float64: _dp}[dtype]))
+        out, b = _want_buffers(H.CHART_BUFFERS, H.PtChartBuffers, want, into, shape)
         ms = C.c_double(0.0)
         _check(lib().ph_renderer_chart(self._h, C.byref(p), _p(uv, _dp) if uv is not None else None, C.byref(b), C.byref(ms)), "ph_renderer_chart")
         out["kernel_ms"] = ms.value
@@ -1138,10 +1114,9 @@ class Renderer:
         arrays of shape (H, W) - `bent` (H, W, 3) - as in ao(), with `visibility`; texels no triangle owns are invalid points (valid 0, visibility 1). `node`,
         `uv` (numpy, or None) and flip_normal as in chart()."""
         cp, uv = self._chart_params(node, width, height, uv, flip_normal)
-        if uv is not None and not isinstance(uv, np.ndarray):
-            raise ValueError("ao_chart takes uv as a numpy array or None; chart() takes tensors")
+        _uv_on_the_host("ao_chart", uv)
         p = self._ao_params(int(width) * int(height), samples, radius, bias, seed, pass_index, 0, None)
-        out, b = self._ao_buffers(want, into, (int(height), int(width)))
+        out, b = _want_buffers(H.AO_BUFFERS, H.PtAoBuffers, want, into, (int(height), int(width)))
         ms = C.c_double(0.0)
         _check(lib().ph_renderer_ao_chart(self._h, C.byref(cp), _p(uv, _dp) if uv is not None else None, C.byref(p), C.byref(b), C.byref(ms)), "ph_renderer_ao_chart")
         return self._ao_result(out, samples, ms)
@@ -1152,10 +1127,9 @@ class Renderer:
         gather(chart's position, chart's normal, background, first_index=0, ...). `sum` and `mean` (H, W, 3), `valid` (H, W), as in gather(); the irradiance
         estimate is pi x mean; texels no triangle owns are invalid points. `node`, `uv` (numpy, or None) and flip_normal as in chart()."""
         cp, uv = self._chart_params(node, width, height, uv, flip_normal)
-        if uv is not None and not isinstance(uv, np.ndarray):
-            raise ValueError("gather_chart takes uv as a numpy array or None; chart() takes tensors")
+        _uv_on_the_host("gather_chart", uv)
         p, bg = self._gather_params(int(width) * int(height), background, samples, bias, seed, pass_index, 0, None)
-        out, b = self._gather_buffers(want, into, (int(height), int(width)))
+        out, b = _want_buffers(H.GATHER_BUFFERS, H.PtGatherBuffers, want, into, (int(height), int(width)))
         ms = C.c_double(0.0)
         _check(lib().ph_renderer_gather_chart(self._h, C.byref(cp), _p(uv, _dp) if uv is not None else None, C.byref(p), _p(bg, _dp), C.byref(b), C.byref(ms)),
                "ph_renderer_gather_chart")
@@ -1168,23 +1142,6 @@ class Renderer:
             raise ValueError("to_light must be a bool, got %r" % (to_light,))
         a = Renderer._ao_params(n, samples, float("inf"), bias, seed, pass_index, first_index, eye)  # (the same checks; a shadow ray has no radius)
         return H.PtDirectParams(a.n, a.samples, a.pass_index, a.seed, a.first_index, a.bias, a.flags | (H.DIRECT_TO_LIGHT if to_light else 0), a.eye)
-
-    @staticmethod
-    def _direct_buffers(want, into, shape):
-        want = tuple(want)
-        unknown = [n for n in want if n not in H.DIRECT_BUFFERS]
-        if unknown or not want:
-            raise ValueError("want must name some of %s, got %r" % (", ".join(H.DIRECT_BUFFERS), want))
-        out, b = {}, H.PtDirectBuffers()
-        for name in want:
-            dtype, comps = H.DIRECT_BUFFERS[name]
-            full = shape if comps == 1 else shape + (comps,)
-            a = into[name] if into is not None and name in into else np.zeros(full, dtype=dtype)
-            if not isinstance(a, np.ndarray) or a.shape != full or a.dtype != dtype or not a.flags.c_contiguous:
-                raise ValueError("into[%r] must be a C-contiguous %s array of shape %r" % (name, np.dtype(dtype).name, full))
-            out[name] = a
-            setattr(b, name, _p(a, {np.uint32: _up, np.uint8: _u8p, np.float64: _dp}[dtype]))
-        return out, b
 
     @staticmethod
     def _direct_result(out, samples, ms):
@@ -1205,15 +1162,10 @@ class Renderer:
         (computed here) where `sum` was asked for, and `kernel_ms`. In a scene of point lights only samples=1 is what to ask for. A point with a non-finite
         component, one beyond 1e18 or a zero normal is invalid: sum 0, lit 0, valid 0. Point i draws from the streams (seed, (first_index + i) * samples + k,
         pass_index): a slice [k, k + m) with first_index=k gives that slice of the whole. `into`: a dict of C-contiguous arrays of the right shape and dtype."""
-        P, N = np.asarray(points), np.asarray(normals)
-        if P.ndim != 2 or P.shape[1] != 3 or P.shape != N.shape:
-            raise ValueError("points and normals must both be (n, 3), got %r and %r" % (P.shape, N.shape))
-        if P.dtype != np.float64 or N.dtype != np.float64:
-            raise ValueError("points and normals must be float64, got %s and %s" % (P.dtype, N.dtype))
+        P, N = _points_and_normals(points, normals)
         n = P.shape[0]
         p = self._direct_params(n, samples, bias, seed, pass_index, first_index, eye, to_light)
-        out, b = self._direct_buffers(want, into, (n,))
-        P, N = np.ascontiguousarray(P), np.ascontiguousarray(N)
+        out, b = _want_buffers(H.DIRECT_BUFFERS, H.PtDirectBuffers, want, into, (n,))
         ms = C.c_double(0.0)
         _check(lib().ph_renderer_direct(self._h, C.byref(p), _p(P, _dp), _p(N, _dp), C.byref(b), C.byref(ms)), "ph_renderer_direct")
         return self._direct_result(out, samples, ms)
@@ -1224,14 +1176,10 @@ class Renderer:
         turned towards the camera's eye, pixel (x, y) the stream index y * width + x - the bits of direct(aov's position, aov's normal, eye=the eye). Nothing
         per pixel crosses the bus but the results: `sum` and `mean` (H, W, 3), `lit` and `valid` (H, W), as in direct(); pixels that see nothing are invalid
         points."""
-        for name, v in (("width", width), ("height", height)):
-            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or int(v) < 1:
-                raise ValueError("%s must be a positive integer, got %r" % (name, v))
+        _positive_size(width, height)
         p = self._direct_params(int(width) * int(height), samples, bias, seed, pass_index, 0, None, to_light)
-        out, b = self._direct_buffers(want, into, (int(height), int(width)))
-        c = np.ascontiguousarray(cam10, dtype=np.float64)
-        if c.shape != (10,):
-            raise ValueError("cam10 must hold 10 numbers, got shape %r" % (c.shape,))
+        out, b = _want_buffers(H.DIRECT_BUFFERS, H.PtDirectBuffers, want, into, (int(height), int(width)))
+        c = _camera_numbers(cam10)
         ms = C.c_double(0.0)
         _check(lib().ph_renderer_direct_camera(self._h, _p(c, _dp), int(width), int(height), C.byref(p), C.byref(b), C.byref(ms)), "ph_renderer_direct_camera")
         return self._direct_result(out, samples, ms)
@@ -1242,10 +1190,9 @@ class Renderer:
         direct(chart's position, chart's normal, first_index=0, ...), texel (x, y) the stream index y * width + x. `sum` and `mean` (H, W, 3), `lit` and `valid`
         (H, W), as in direct(); texels no triangle owns are invalid points. `node`, `uv` (numpy, or None) and flip_normal as in chart()."""
         cp, uv = self._chart_params(node, width, height, uv, flip_normal)
-        if uv is not None and not isinstance(uv, np.ndarray):
-            raise ValueError("direct_chart takes uv as a numpy array or None; chart() takes tensors")
+        _uv_on_the_host("direct_chart", uv)
         p = self._direct_params(int(width) * int(height), samples, bias, seed, pass_index, 0, None, to_light)
-        out, b = self._direct_buffers(want, into, (int(height), int(width)))
+        out, b = _want_buffers(H.DIRECT_BUFFERS, H.PtDirectBuffers, want, into, (int(height), int(width)))
         ms = C.c_double(0.0)
         _check(lib().ph_renderer_direct_chart(self._h, C.byref(cp), _p(uv, _dp) if uv is not None else None, C.byref(p), C.byref(b), C.byref(ms)),
                "ph_renderer_direct_chart")
@@ -1283,20 +1230,10 @@ class Renderer:
             raise ValueError("background must be 3 numbers, got shape %r" % (bg.shape,))
         if isinstance(want, str):
             raise ValueError("want must be a sequence of names, got %r" % (want,))
-        want = tuple(want)
-        if not want or [w for w in want if w not in H.PROBE_BUFFERS]:
-            raise ValueError("want must name some of %s, got %r" % (", ".join(H.PROBE_BUFFERS), want))
+        want = _want_names(H.PROBE_BUFFERS, want)
         if into is not None and not isinstance(into, dict):
             raise ValueError("into must be a dict of arrays, got %s" % type(into).__name__)
-        out, b = {}, H.PtProbeBuffers()
-        for name in want:
-            dtype, tail = H.PROBE_BUFFERS[name]
-            full = (n,) + tail
-            a = into[name] if into is not None and name in into else np.zeros(full, dtype=dtype)
-            if not isinstance(a, np.ndarray) or a.shape != full or a.dtype != dtype or not a.flags.c_contiguous:
-                raise ValueError("into[%r] must be a C-contiguous %s array of shape %r" % (name, np.dtype(dtype).name, full))
-            out[name] = a
-            setattr(b, name, _p(a, {np.uint8: _u8p, np.float64: _dp}[dtype]))
+        out, b = _want_buffers(H.PROBE_BUFFERS, H.PtProbeBuffers, want, into, (n,))
         p = H.PtProbeParams(n, int(samples), int(pass_index), int(seed), int(first_index))
         P = np.ascontiguousarray(P)
         ms = C.c_double(0.0)

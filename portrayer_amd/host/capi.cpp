@@ -667,60 +667,21 @@ extern "C" int ph_renderer_segments(ph_renderer* r, const pt_rays_params* p, con
     });
 }
 
+// A pt_ return code of the renderer's context as this API shows it: the library's words in g_error, an argument error as one, anything else a runtime error.
+static int shown(pt_context* c, int rc) {
+    if (rc == PT_OK) return PH_OK;
+    g_error = pt_last_error(c);
+    return rc == PT_ERR_ARGUMENT ? PH_ERR_ARGUMENT : PH_ERR_RUNTIME;
+}
+
 // Ambient occlusion at points of the caller's own (pt_ao): host buffers in and out.
 extern "C" int ph_renderer_ao(ph_renderer* r, const pt_ao_params* p, const double* positions, const double* normals, const pt_ao_buffers* out, double* kernel_ms) {
     if (!r || !p || !out) return bad("null argument");
     if (p->n && (!positions || !normals)) return bad("null argument");
     if (p->n == 0) { if (kernel_ms) *kernel_ms = 0.0; return PH_OK; }
     return guarded([&]() -> int {
-        int rc = pt_ao(r->r->context(), p, positions, normals, out, kernel_ms);  // (a renderer spread over a node: rank 0's context, every point)
-        if (rc != PT_OK) { g_error = pt_last_error(r->r->context()); return rc == PT_ERR_ARGUMENT ? PH_ERR_ARGUMENT : PH_ERR_RUNTIME; }
-        return PH_OK;
-    });
-}
-
-// Ambient occlusion under every pixel of a width x height image: pt_aov_device writes position and normal at the pixel centres into device memory kept with the
-// renderer, pt_ao_device behind it on the same stream reads them with PT_AO_FACE_EYE and the camera's eye - point q = y * width + x, so params->n, flags, eye
-// and first_index are set here - and only the results asked for cross the bus.
-extern "C" int ph_renderer_ao_camera(ph_renderer* r, const double camera[10], uint32_t width, uint32_t height, const pt_ao_params* p, const pt_ao_buffers* out, double* kernel_ms) {
-    if (!r || !camera || !p || !out) return bad("null argument");
-    if (width == 0 || height == 0) return bad("width and height must be positive");
-    if ((uint64_t)width * height > PT_AO_MAX) return bad("more than PT_AO_MAX pixels");
-    if (!(out->occluded || out->valid || out->bent)) return bad("no output buffer asked for");
-    return guarded([&]() -> int {
-        pt_context* c = r->r->context();
-        auto fail = [&](int rc) { g_error = pt_last_error(c); return rc == PT_ERR_ARGUMENT ? PH_ERR_ARGUMENT : PH_ERR_RUNTIME; };
-        const uint64_t n = (uint64_t)width * height;
-        const size_t bytes[5] = {n * 24, n * 24, n * 4, n * 1, n * 24};
-        void* host_out[3] = {out->occluded, out->valid, out->bent};
-        int rc = PT_OK;
-        if (r->ao_points < n) {
-            r->ao_release();
-            for (int k = 0; k < 5 && rc == PT_OK; k++) rc = pt_device_alloc(c, bytes[k], &r->d_ao[k]);
-            if (rc != PT_OK) { const int shown = fail(rc); r->ao_release(); return shown; }
-            r->ao_points = n;
-        }
-        pt_camera pc = detail::Camera(camera_from(camera), (double)width, (double)height).to_abi();  // the camera a render of this size gets
-        pt_aov_params ap;
-        ap.width = width; ap.height = height;
-        ap.slice.x0 = 0; ap.slice.y0 = 0; ap.slice.x1 = width - 1; ap.slice.y1 = height - 1;
-        ap.offset[0] = 0.5; ap.offset[1] = 0.5;
-        pt_ao_params q = *p;
-        q.n = n; q.first_index = 0; q.flags = PT_AO_FACE_EYE;
-        for (int k = 0; k < 3; k++) q.eye[k] = pc.eye[k];
-        pt_aov_buffers ab = {nullptr, (double*)r->d_ao[0], (double*)r->d_ao[1], nullptr, nullptr, nullptr};
-        pt_ao_buffers db = {out->occluded ? (uint32_t*)r->d_ao[2] : nullptr, out->valid ? (uint8_t*)r->d_ao[3] : nullptr, out->bent ? (double*)r->d_ao[4] : nullptr};
-        if ((rc = pt_aov_device(c, &pc, &ap, &ab, nullptr))) return fail(rc);
-        rc = pt_ao_device(c, &q, (const double*)r->d_ao[0], (const double*)r->d_ao[1], &db, nullptr);  // the same (default) stream: behind the aov pass
-        if (rc) { const int shown = fail(rc); pt_aov_finish(c, nullptr); return shown; }
-        const int rc_aov = pt_aov_finish(c, nullptr);
-        if (rc_aov) g_error = pt_last_error(c);
-        rc = pt_ao_finish(c, kernel_ms);
-        if (rc_aov) return PH_ERR_RUNTIME;
-        if (rc) return fail(rc);
-        for (int k = 0; k < 3; k++)
-            if (host_out[k] && (rc = pt_copy_from_device(c, host_out[k], r->d_ao[2 + k], bytes[2 + k]))) return fail(rc);
-        return PH_OK;
+        pt_context* c = r->r->context();  // (a renderer spread over a node: rank 0's context, every point)
+        return shown(c, pt_ao(c, p, positions, normals, out, kernel_ms));
     });
 }
 
@@ -731,65 +692,37 @@ extern "C" int ph_renderer_gather(ph_renderer* r, const pt_gather_params* p, con
     if (p->n && (!positions || !normals)) return bad("null argument");
     if (p->n == 0) { if (kernel_ms) *kernel_ms = 0.0; return PH_OK; }
     return guarded([&]() -> int {
-        int rc = pt_gather(r->r->context(), p, positions, normals, background, out, kernel_ms);  // (a renderer spread over a node: rank 0's context, every point)
-        if (rc != PT_OK) { g_error = pt_last_error(r->r->context()); return rc == PT_ERR_ARGUMENT ? PH_ERR_ARGUMENT : PH_ERR_RUNTIME; }
-        return PH_OK;
+        pt_context* c = r->r->context();  // (a renderer spread over a node: rank 0's context, every point)
+        return shown(c, pt_gather(c, p, positions, normals, background, out, kernel_ms));
     });
 }
 
-// Gathered radiance under every pixel of a width x height image, built like ph_renderer_ao_camera and on its device scratch (position, normal; the sums where that
-// pass keeps its bent normals, the flags where it keeps its own): pt_aov_device at the pixel centres, pt_gather_device behind it on the same stream with
-// PT_AO_FACE_EYE and the camera's eye - point q = y * width + x, so params->n, flags, eye and first_index are set here - and only the results cross the bus.
-extern "C" int ph_renderer_gather_camera(ph_renderer* r, const double camera[10], uint32_t width, uint32_t height, const pt_gather_params* p, const double* background,
-                                         const pt_gather_buffers* out, double* kernel_ms) {
-    if (!r || !camera || !p || !background || !out) return bad("null argument");
-    if (width == 0 || height == 0) return bad("width and height must be positive");
-    if ((uint64_t)width * height > PT_AO_MAX) return bad("more than PT_AO_MAX pixels");
-    if (!(out->sum || out->valid)) return bad("no output buffer asked for");
+// Direct light at points of the caller's own (pt_direct): host buffers in and out.
+extern "C" int ph_renderer_direct(ph_renderer* r, const pt_direct_params* p, const double* positions, const double* normals, const pt_direct_buffers* out, double* kernel_ms) {
+    if (!r || !p || !out) return bad("null argument");
+    if (p->n && (!positions || !normals)) return bad("null argument");
+    if (p->n == 0) { if (kernel_ms) *kernel_ms = 0.0; return PH_OK; }
     return guarded([&]() -> int {
-        pt_context* c = r->r->context();
-        auto fail = [&](int rc) { g_error = pt_last_error(c); return rc == PT_ERR_ARGUMENT ? PH_ERR_ARGUMENT : PH_ERR_RUNTIME; };
-        const uint64_t n = (uint64_t)width * height;
-        const size_t bytes[5] = {n * 24, n * 24, n * 4, n * 1, n * 24};  // (ph_renderer_ao_camera's five)
-        int rc = PT_OK;
-        if (r->ao_points < n) {
-            r->ao_release();
-            for (int k = 0; k < 5 && rc == PT_OK; k++) rc = pt_device_alloc(c, bytes[k], &r->d_ao[k]);
-            if (rc != PT_OK) { const int shown = fail(rc); r->ao_release(); return shown; }
-            r->ao_points = n;
-        }
-        pt_camera pc = detail::Camera(camera_from(camera), (double)width, (double)height).to_abi();  // the camera a render of this size gets
-        pt_aov_params ap;
-        ap.width = width; ap.height = height;
-        ap.slice.x0 = 0; ap.slice.y0 = 0; ap.slice.x1 = width - 1; ap.slice.y1 = height - 1;
-        ap.offset[0] = 0.5; ap.offset[1] = 0.5;
-        pt_gather_params q = *p;
-        q.n = n; q.first_index = 0; q.flags = PT_AO_FACE_EYE;
-        for (int k = 0; k < 3; k++) q.eye[k] = pc.eye[k];
-        pt_aov_buffers ab = {nullptr, (double*)r->d_ao[0], (double*)r->d_ao[1], nullptr, nullptr, nullptr};
-        pt_gather_buffers db = {out->sum ? (double*)r->d_ao[4] : nullptr, out->valid ? (uint8_t*)r->d_ao[3] : nullptr};
-        if ((rc = pt_aov_device(c, &pc, &ap, &ab, nullptr))) return fail(rc);
-        rc = pt_gather_device(c, &q, (const double*)r->d_ao[0], (const double*)r->d_ao[1], background, &db, nullptr);  // the same (default) stream: behind the aov pass
-        if (rc) { const int shown = fail(rc); pt_aov_finish(c, nullptr); return shown; }
-        const int rc_aov = pt_aov_finish(c, nullptr);
-        if (rc_aov) g_error = pt_last_error(c);
-        rc = pt_gather_finish(c, kernel_ms);
-        if (rc_aov) return PH_ERR_RUNTIME;
-        if (rc) return fail(rc);
-        if (out->sum && (rc = pt_copy_from_device(c, out->sum, r->d_ao[4], bytes[4]))) return fail(rc);
-        if (out->valid && (rc = pt_copy_from_device(c, out->valid, r->d_ao[3], bytes[3]))) return fail(rc);
-        return PH_OK;
+        pt_context* c = r->r->context();  // (a renderer spread over a node: rank 0's context, every point)
+        return shown(c, pt_direct(c, p, positions, normals, out, kernel_ms));
+    });
+}
+
+// Light probes at points in free space (pt_probe): host buffers in and out.
+extern "C" int ph_renderer_probe(ph_renderer* r, const pt_probe_params* p, const double* positions, const double* background, const pt_probe_buffers* out, double* kernel_ms) {
+    if (!r || !p || !background || !out) return bad("null argument");
+    if (p->n && !positions) return bad("null argument");
+    if (p->n == 0) { if (kernel_ms) *kernel_ms = 0.0; return PH_OK; }
+    return guarded([&]() -> int {
+        pt_context* c = r->r->context();  // (a renderer spread over a node: rank 0's context, every probe)
+        return shown(c, pt_probe(c, p, positions, background, out, kernel_ms));
     });
 }
 
 // A mesh's light-map texels as surface points (pt_chart): host buffers in and out.
 extern "C" int ph_renderer_chart_triangles(ph_renderer* r, uint32_t node, uint64_t* n_tris) {
     if (!r || !n_tris) return bad("null argument");
-    return guarded([&]() -> int {
-        int rc = pt_chart_triangles(r->r->context(), node, n_tris);
-        if (rc != PT_OK) { g_error = pt_last_error(r->r->context()); return rc == PT_ERR_ARGUMENT ? PH_ERR_ARGUMENT : PH_ERR_RUNTIME; }
-        return PH_OK;
-    });
+    return guarded([&]() -> int { return shown(r->r->context(), pt_chart_triangles(r->r->context(), node, n_tris)); });
 }
 
 // The mesh under flattened node `node`, for a caller that expands a per-vertex UV set to corners: counts = {vertices, triangles}; `indices` (optional) gets
@@ -813,199 +746,195 @@ extern "C" int ph_renderer_chart_mesh(ph_renderer* r, uint32_t node, uint64_t co
 extern "C" int ph_renderer_chart(ph_renderer* r, const pt_chart_params* p, const double* uv, const pt_chart_buffers* out, double* kernel_ms) {
     if (!r || !p || !out) return bad("null argument");
     return guarded([&]() -> int {
-        int rc = pt_chart(r->r->context(), p, uv, out, kernel_ms);  // (a renderer spread over a node: rank 0's context, the whole map)
-        if (rc != PT_OK) { g_error = pt_last_error(r->r->context()); return rc == PT_ERR_ARGUMENT ? PH_ERR_ARGUMENT : PH_ERR_RUNTIME; }
-        return PH_OK;
+        pt_context* c = r->r->context();  // (a renderer spread over a node: rank 0's context, the whole map)
+        return shown(c, pt_chart(c, p, uv, out, kernel_ms));
     });
 }
 
-// What ph_renderer_ao_chart and ph_renderer_gather_chart share: the renderer's device scratch for width x height texels (ph_renderer_ao_camera's five buffers), the
-// caller's UV set copied beside it (uv NULL: the mesh's own), and pt_chart_device queued on the default stream with position and normal in the first two. The
-// pass is left OPEN: the caller queues its own pass behind it and closes both. Returns a pt_ error code.
-static int chart_points(ph_renderer* r, const pt_chart_params* cp, const double* uv) {
+// ---- A pass over points that never leave the device: where the points come from (camera_points: a camera's pixels; chart_points: a light map's texels) and what
+// is evaluated there (behind_points: ambient occlusion, gather or direct light). The renderer's point scratch d_ao holds n points: position (0) and normal (1) as
+// the points' pass writes them, and the second pass's results - 4 bytes a point (2: occluded, lit), 1 byte (3: valid) and 24 bytes (4: bent, sum). A new pass over
+// points is a queue step and a list of results for behind_points; a new source of points is a function like the two here.
+
+// The scratch grown to n points. Returns a ph_ code, as everything below does.
+static int points_scratch(ph_renderer* r, uint64_t n) {
+    if (r->ao_points >= n) return PH_OK;
     pt_context* c = r->r->context();
-    const uint64_t n = (uint64_t)cp->width * cp->height;
     const size_t bytes[5] = {n * 24, n * 24, n * 4, n * 1, n * 24};
     int rc = PT_OK;
+    r->ao_release();
+    for (int k = 0; k < 5 && rc == PT_OK; k++) rc = pt_device_alloc(c, bytes[k], &r->d_ao[k]);
+    if (rc != PT_OK) { const int code = shown(c, rc); r->ao_release(); return code; }
+    r->ao_points = n;
+    return PH_OK;
+}
+
+// The points under the pixel centres of a width x height image: the scratch, and pt_aov_device queued on the default stream with position and normal in its first
+// two buffers. The pass is left OPEN: behind_points queues its own pass behind it and closes both. *pc: the camera a render of this size gets, for its eye.
+static int camera_points(ph_renderer* r, const double camera[10], uint32_t width, uint32_t height, pt_camera* pc) {
+    pt_context* c = r->r->context();
+    if (int code = points_scratch(r, (uint64_t)width * height)) return code;
+    *pc = detail::Camera(camera_from(camera), (double)width, (double)height).to_abi();
+    pt_aov_params ap;
+    ap.width = width; ap.height = height;
+    ap.slice.x0 = 0; ap.slice.y0 = 0; ap.slice.x1 = width - 1; ap.slice.y1 = height - 1;
+    ap.offset[0] = 0.5; ap.offset[1] = 0.5;
+    pt_aov_buffers ab = {nullptr, (double*)r->d_ao[0], (double*)r->d_ao[1], nullptr, nullptr, nullptr};
+    return shown(c, pt_aov_device(c, pc, &ap, &ab, nullptr));
+}
+
+// The texels of a mesh's light map: the scratch, the caller's UV set copied beside it (uv NULL: the mesh's own), and pt_chart_device queued on the default
+// stream with position and normal in the scratch's first two buffers. The pass is left OPEN, as camera_points leaves its own.
+static int chart_points(ph_renderer* r, const pt_chart_params* cp, const double* uv) {
+    pt_context* c = r->r->context();
+    int rc = PT_OK;
     uint64_t n_tris = 0;
-    if ((rc = pt_chart_triangles(c, cp->node, &n_tris))) return rc;
-    if (r->ao_points < n) {
-        r->ao_release();
-        for (int k = 0; k < 5 && rc == PT_OK; k++) rc = pt_device_alloc(c, bytes[k], &r->d_ao[k]);
-        if (rc != PT_OK) { r->ao_release(); return rc; }
-        r->ao_points = n;
-    }
+    if ((rc = pt_chart_triangles(c, cp->node, &n_tris))) return shown(c, rc);
+    if (int code = points_scratch(r, (uint64_t)cp->width * cp->height)) return code;
     if (uv && n_tris) {
         if (r->chart_uv_bytes < n_tris * 48) {
             if (r->d_chart_uv) pt_device_free(c, r->d_chart_uv);
             r->d_chart_uv = nullptr; r->chart_uv_bytes = 0;
-            if ((rc = pt_device_alloc(c, n_tris * 48, &r->d_chart_uv))) return rc;
+            if ((rc = pt_device_alloc(c, n_tris * 48, &r->d_chart_uv))) return shown(c, rc);
             r->chart_uv_bytes = n_tris * 48;
         }
-        if ((rc = pt_copy_to_device(c, r->d_chart_uv, uv, n_tris * 48))) return rc;
+        if ((rc = pt_copy_to_device(c, r->d_chart_uv, uv, n_tris * 48))) return shown(c, rc);
     }
     pt_chart_buffers cb = {(double*)r->d_ao[0], (double*)r->d_ao[1], nullptr, nullptr};
-    return pt_chart_device(c, cp, uv && n_tris ? (const double*)r->d_chart_uv : nullptr, &cb, nullptr);
+    return shown(c, pt_chart_device(c, cp, uv && n_tris ? (const double*)r->d_chart_uv : nullptr, &cb, nullptr));
 }
 
-// Ambient occlusion at every texel of a mesh's light map, built like ph_renderer_ao_camera: pt_chart_device writes position and normal into the renderer's device
-// scratch, pt_ao_device behind it on the same stream reads them - point q = y * width + x, first_index 0, no PT_AO_FACE_EYE (a chart's normals face outwards or,
-// with PT_CHART_FLIP_NORMAL, inwards) - and only the results cross the bus. Of `params` samples, pass, seed, radius and bias are read.
-extern "C" int ph_renderer_ao_chart(ph_renderer* r, const pt_chart_params* chart, const double* uv, const pt_ao_params* p, const pt_ao_buffers* out, double* kernel_ms) {
-    if (!r || !chart || !p || !out) return bad("null argument");
-    if (chart->width == 0 || chart->height == 0) return bad("width and height must be positive");
-    if ((uint64_t)chart->width * chart->height > PT_AO_MAX) return bad("more than PT_AO_MAX texels");
-    if (!(out->occluded || out->valid || out->bent)) return bad("no output buffer asked for");
-    return guarded([&]() -> int {
-        pt_context* c = r->r->context();
-        auto fail = [&](int rc) { g_error = pt_last_error(c); return rc == PT_ERR_ARGUMENT ? PH_ERR_ARGUMENT : PH_ERR_RUNTIME; };
-        const uint64_t n = (uint64_t)chart->width * chart->height;
-        const size_t bytes[5] = {n * 24, n * 24, n * 4, n * 1, n * 24};
-        void* host_out[3] = {out->occluded, out->valid, out->bent};
-        int rc = chart_points(r, chart, uv);
-        if (rc) return fail(rc);
-        pt_ao_params q = *p;
-        q.n = n; q.first_index = 0; q.flags = 0;
-        pt_ao_buffers db = {out->occluded ? (uint32_t*)r->d_ao[2] : nullptr, out->valid ? (uint8_t*)r->d_ao[3] : nullptr, out->bent ? (double*)r->d_ao[4] : nullptr};
-        rc = pt_ao_device(c, &q, (const double*)r->d_ao[0], (const double*)r->d_ao[1], &db, nullptr);  // the same (default) stream: behind the chart pass
-        if (rc) { const int shown = fail(rc); pt_aov_finish(c, nullptr); return shown; }
-        const int rc_chart = pt_aov_finish(c, nullptr);
-        if (rc_chart) g_error = pt_last_error(c);
-        rc = pt_ao_finish(c, kernel_ms);
-        if (rc_chart) return PH_ERR_RUNTIME;
-        if (rc) return fail(rc);
-        for (int k = 0; k < 3; k++)
-            if (host_out[k] && (rc = pt_copy_from_device(c, host_out[k], r->d_ao[2 + k], bytes[2 + k]))) return fail(rc);
-        return PH_OK;
-    });
-}
+// One result of the pass behind the points: the caller's array (NULL: not asked for), the scratch buffer it comes back from, its length.
+struct PointsOut { void* host; int slot; size_t bytes; };
+template <class T>
+static T* slot_if(ph_renderer* r, const T* host, int slot) { return host ? (T*)r->d_ao[slot] : nullptr; }
 
-// Gathered radiance at every texel of a mesh's light map: ph_renderer_ao_chart with pt_gather_device behind the chart pass (the sums where that keeps its bent
-// normals, the flags where it keeps its own).
-extern "C" int ph_renderer_gather_chart(ph_renderer* r, const pt_chart_params* chart, const double* uv, const pt_gather_params* p, const double* background,
-                                        const pt_gather_buffers* out, double* kernel_ms) {
-    if (!r || !chart || !p || !background || !out) return bad("null argument");
-    if (chart->width == 0 || chart->height == 0) return bad("width and height must be positive");
-    if ((uint64_t)chart->width * chart->height > PT_AO_MAX) return bad("more than PT_AO_MAX texels");
-    if (!(out->sum || out->valid)) return bad("no output buffer asked for");
-    return guarded([&]() -> int {
-        pt_context* c = r->r->context();
-        auto fail = [&](int rc) { g_error = pt_last_error(c); return rc == PT_ERR_ARGUMENT ? PH_ERR_ARGUMENT : PH_ERR_RUNTIME; };
-        const uint64_t n = (uint64_t)chart->width * chart->height;
-        int rc = chart_points(r, chart, uv);
-        if (rc) return fail(rc);
-        pt_gather_params q = *p;
-        q.n = n; q.first_index = 0; q.flags = 0;
-        pt_gather_buffers db = {out->sum ? (double*)r->d_ao[4] : nullptr, out->valid ? (uint8_t*)r->d_ao[3] : nullptr};
-        rc = pt_gather_device(c, &q, (const double*)r->d_ao[0], (const double*)r->d_ao[1], background, &db, nullptr);  // the same (default) stream: behind the chart pass
-        if (rc) { const int shown = fail(rc); pt_aov_finish(c, nullptr); return shown; }
-        const int rc_chart = pt_aov_finish(c, nullptr);
-        if (rc_chart) g_error = pt_last_error(c);
-        rc = pt_gather_finish(c, kernel_ms);
-        if (rc_chart) return PH_ERR_RUNTIME;
-        if (rc) return fail(rc);
-        if (out->sum && (rc = pt_copy_from_device(c, out->sum, r->d_ao[4], n * 24))) return fail(rc);
-        if (out->valid && (rc = pt_copy_from_device(c, out->valid, r->d_ao[3], n))) return fail(rc);
-        return PH_OK;
-    });
-}
-
-// Direct light at points of the caller's own (pt_direct): host buffers in and out.
-extern "C" int ph_renderer_direct(ph_renderer* r, const pt_direct_params* p, const double* positions, const double* normals, const pt_direct_buffers* out, double* kernel_ms) {
-    if (!r || !p || !out) return bad("null argument");
-    if (p->n && (!positions || !normals)) return bad("null argument");
-    if (p->n == 0) { if (kernel_ms) *kernel_ms = 0.0; return PH_OK; }
-    return guarded([&]() -> int {
-        int rc = pt_direct(r->r->context(), p, positions, normals, out, kernel_ms);  // (a renderer spread over a node: rank 0's context, every point)
-        if (rc != PT_OK) { g_error = pt_last_error(r->r->context()); return rc == PT_ERR_ARGUMENT ? PH_ERR_ARGUMENT : PH_ERR_RUNTIME; }
-        return PH_OK;
-    });
-}
-
-// Light probes at points in free space (pt_probe): host buffers in and out.
-extern "C" int ph_renderer_probe(ph_renderer* r, const pt_probe_params* p, const double* positions, const double* background, const pt_probe_buffers* out, double* kernel_ms) {
-    if (!r || !p || !background || !out) return bad("null argument");
-    if (p->n && !positions) return bad("null argument");
-    if (p->n == 0) { if (kernel_ms) *kernel_ms = 0.0; return PH_OK; }
-    return guarded([&]() -> int {
-        int rc = pt_probe(r->r->context(), p, positions, background, out, kernel_ms);  // (a renderer spread over a node: rank 0's context, every probe)
-        if (rc != PT_OK) { g_error = pt_last_error(r->r->context()); return rc == PT_ERR_ARGUMENT ? PH_ERR_ARGUMENT : PH_ERR_RUNTIME; }
-        return PH_OK;
-    });
-}
-
-// What ph_renderer_direct_camera and ph_renderer_direct_chart share once the points' pass (pt_aov_device or pt_chart_device, left open) has written position and
-// normal into the renderer's device scratch: pt_direct_device behind it on the same (default) stream - the sums where ph_renderer_ao_camera keeps its bent
-// normals, the counts where it keeps its own, the flags likewise - both passes closed, the results asked for copied out.
-static int direct_behind_points(ph_renderer* r, uint64_t n, const pt_direct_params& q, const pt_direct_buffers* out, double* kernel_ms) {
+// Once the points' pass (left open) has position and normal on their way into the scratch: queue(context, d_positions, d_normals) puts a pt_*_device pass behind it
+// on the same (default) stream, both passes are closed - the points' first, and its error is the one reported - and the results asked for are copied out, in
+// `outs`' order.
+template <class Queue, size_t N>
+static int behind_points(ph_renderer* r, Queue&& queue, int (*finish)(pt_context*, double*), const PointsOut (&outs)[N], double* kernel_ms) {
     pt_context* c = r->r->context();
-    auto fail = [&](int rc) { g_error = pt_last_error(c); return rc == PT_ERR_ARGUMENT ? PH_ERR_ARGUMENT : PH_ERR_RUNTIME; };
-    pt_direct_buffers db = {out->sum ? (double*)r->d_ao[4] : nullptr, out->lit ? (uint32_t*)r->d_ao[2] : nullptr, out->valid ? (uint8_t*)r->d_ao[3] : nullptr};
-    int rc = pt_direct_device(c, &q, (const double*)r->d_ao[0], (const double*)r->d_ao[1], &db, nullptr);
-    if (rc) { const int shown = fail(rc); pt_aov_finish(c, nullptr); return shown; }
+    int rc = queue(c, (const double*)r->d_ao[0], (const double*)r->d_ao[1]);
+    if (rc) { const int code = shown(c, rc); pt_aov_finish(c, nullptr); return code; }
     const int rc_points = pt_aov_finish(c, nullptr);
     if (rc_points) g_error = pt_last_error(c);
-    rc = pt_direct_finish(c, kernel_ms);
+    rc = finish(c, kernel_ms);
     if (rc_points) return PH_ERR_RUNTIME;
-    if (rc) return fail(rc);
-    if (out->sum && (rc = pt_copy_from_device(c, out->sum, r->d_ao[4], n * 24))) return fail(rc);
-    if (out->lit && (rc = pt_copy_from_device(c, out->lit, r->d_ao[2], n * 4))) return fail(rc);
-    if (out->valid && (rc = pt_copy_from_device(c, out->valid, r->d_ao[3], n))) return fail(rc);
+    if (rc) return shown(c, rc);
+    for (const PointsOut& o : outs)
+        if (o.host && (rc = pt_copy_from_device(c, o.host, r->d_ao[o.slot], o.bytes))) return shown(c, rc);
     return PH_OK;
 }
 
-// Direct light under every pixel of a width x height image, built like ph_renderer_ao_camera and on its device scratch: pt_aov_device at the pixel centres,
-// pt_direct_device behind it on the same stream with PT_AO_FACE_EYE and the camera's eye - point q = y * width + x, so params->n, eye and first_index are set
-// here, and of its flags PT_DIRECT_TO_LIGHT is kept - and only the results cross the bus.
-extern "C" int ph_renderer_direct_camera(ph_renderer* r, const double camera[10], uint32_t width, uint32_t height, const pt_direct_params* p, const pt_direct_buffers* out,
-                                         double* kernel_ms) {
+// The three passes there are behind points; q: the caller's parameters with n, first_index, flags and eye set for the points' source.
+static int ao_behind_points(ph_renderer* r, const pt_ao_params& q, const pt_ao_buffers* out, double* kernel_ms) {
+    const pt_ao_buffers db = {slot_if(r, out->occluded, 2), slot_if(r, out->valid, 3), slot_if(r, out->bent, 4)};
+    const PointsOut outs[3] = {{out->occluded, 2, q.n * 4}, {out->valid, 3, q.n}, {out->bent, 4, q.n * 24}};
+    return behind_points(r, [&](pt_context* c, const double* P, const double* N) { return pt_ao_device(c, &q, P, N, &db, nullptr); }, pt_ao_finish, outs, kernel_ms);
+}
+static int gather_behind_points(ph_renderer* r, const pt_gather_params& q, const double* background, const pt_gather_buffers* out, double* kernel_ms) {
+    const pt_gather_buffers db = {slot_if(r, out->sum, 4), slot_if(r, out->valid, 3)};
+    const PointsOut outs[2] = {{out->sum, 4, q.n * 24}, {out->valid, 3, q.n}};
+    return behind_points(r, [&](pt_context* c, const double* P, const double* N) { return pt_gather_device(c, &q, P, N, background, &db, nullptr); }, pt_gather_finish, outs,
+                         kernel_ms);
+}
+static int direct_behind_points(ph_renderer* r, const pt_direct_params& q, const pt_direct_buffers* out, double* kernel_ms) {
+    const pt_direct_buffers db = {slot_if(r, out->sum, 4), slot_if(r, out->lit, 2), slot_if(r, out->valid, 3)};
+    const PointsOut outs[3] = {{out->sum, 4, q.n * 24}, {out->lit, 2, q.n * 4}, {out->valid, 3, q.n}};
+    return behind_points(r, [&](pt_context* c, const double* P, const double* N) { return pt_direct_device(c, &q, P, N, &db, nullptr); }, pt_direct_finish, outs, kernel_ms);
+}
+
+// What the camera forms refuse before anything else, and the chart forms; asked: one of the pass's buffers was asked for. NULL: nothing.
+static const char* camera_form_error(uint32_t width, uint32_t height, bool asked) {
+    if (width == 0 || height == 0) return "width and height must be positive";
+    if ((uint64_t)width * height > PT_AO_MAX) return "more than PT_AO_MAX pixels";
+    return asked ? nullptr : "no output buffer asked for";
+}
+static const char* chart_form_error(const pt_chart_params* chart, bool asked) {
+    if (chart->width == 0 || chart->height == 0) return "width and height must be positive";
+    if ((uint64_t)chart->width * chart->height > PT_AO_MAX) return "more than PT_AO_MAX texels";
+    return asked ? nullptr : "no output buffer asked for";
+}
+
+// The point passes under every pixel of a width x height image: point q = y * width + x is what pt_aov finds at the pixel's centre, its normal turned towards the
+// camera's eye - so params->n, first_index, eye and flags (PT_AO_FACE_EYE; of a direct pass's own, PT_DIRECT_TO_LIGHT is kept) are set here - and only the
+// results asked for cross the bus.
+extern "C" int ph_renderer_ao_camera(ph_renderer* r, const double camera[10], uint32_t width, uint32_t height, const pt_ao_params* p, const pt_ao_buffers* out, double* kernel_ms) {
     if (!r || !camera || !p || !out) return bad("null argument");
-    if (width == 0 || height == 0) return bad("width and height must be positive");
-    if ((uint64_t)width * height > PT_AO_MAX) return bad("more than PT_AO_MAX pixels");
-    if (!(out->sum || out->lit || out->valid)) return bad("no output buffer asked for");
+    if (const char* why = camera_form_error(width, height, out->occluded || out->valid || out->bent)) return bad(why);
     return guarded([&]() -> int {
-        pt_context* c = r->r->context();
-        auto fail = [&](int rc) { g_error = pt_last_error(c); return rc == PT_ERR_ARGUMENT ? PH_ERR_ARGUMENT : PH_ERR_RUNTIME; };
-        const uint64_t n = (uint64_t)width * height;
-        const size_t bytes[5] = {n * 24, n * 24, n * 4, n * 1, n * 24};  // (ph_renderer_ao_camera's five)
-        int rc = PT_OK;
-        if (r->ao_points < n) {
-            r->ao_release();
-            for (int k = 0; k < 5 && rc == PT_OK; k++) rc = pt_device_alloc(c, bytes[k], &r->d_ao[k]);
-            if (rc != PT_OK) { const int shown = fail(rc); r->ao_release(); return shown; }
-            r->ao_points = n;
-        }
-        pt_camera pc = detail::Camera(camera_from(camera), (double)width, (double)height).to_abi();  // the camera a render of this size gets
-        pt_aov_params ap;
-        ap.width = width; ap.height = height;
-        ap.slice.x0 = 0; ap.slice.y0 = 0; ap.slice.x1 = width - 1; ap.slice.y1 = height - 1;
-        ap.offset[0] = 0.5; ap.offset[1] = 0.5;
-        pt_direct_params q = *p;
-        q.n = n; q.first_index = 0; q.flags = PT_AO_FACE_EYE | (p->flags & PT_DIRECT_TO_LIGHT);
+        pt_camera pc;
+        if (int code = camera_points(r, camera, width, height, &pc)) return code;
+        pt_ao_params q = *p;
+        q.n = (uint64_t)width * height; q.first_index = 0; q.flags = PT_AO_FACE_EYE;
         for (int k = 0; k < 3; k++) q.eye[k] = pc.eye[k];
-        pt_aov_buffers ab = {nullptr, (double*)r->d_ao[0], (double*)r->d_ao[1], nullptr, nullptr, nullptr};
-        if ((rc = pt_aov_device(c, &pc, &ap, &ab, nullptr))) return fail(rc);
-        return direct_behind_points(r, n, q, out, kernel_ms);
+        return ao_behind_points(r, q, out, kernel_ms);
     });
 }
 
-// Direct light at every texel of a mesh's light map, built like ph_renderer_ao_chart: pt_chart_device writes position and normal into the renderer's device
-// scratch, pt_direct_device behind it on the same stream reads them - point q = y * width + x, first_index 0, no PT_AO_FACE_EYE (a chart's normals face outwards
-// or, with PT_CHART_FLIP_NORMAL, inwards) - and only the results cross the bus. Of `params` samples, pass, seed, bias and the flag PT_DIRECT_TO_LIGHT are read.
+extern "C" int ph_renderer_gather_camera(ph_renderer* r, const double camera[10], uint32_t width, uint32_t height, const pt_gather_params* p, const double* background,
+                                         const pt_gather_buffers* out, double* kernel_ms) {
+    if (!r || !camera || !p || !background || !out) return bad("null argument");
+    if (const char* why = camera_form_error(width, height, out->sum || out->valid)) return bad(why);
+    return guarded([&]() -> int {
+        pt_camera pc;
+        if (int code = camera_points(r, camera, width, height, &pc)) return code;
+        pt_gather_params q = *p;
+        q.n = (uint64_t)width * height; q.first_index = 0; q.flags = PT_AO_FACE_EYE;
+        for (int k = 0; k < 3; k++) q.eye[k] = pc.eye[k];
+        return gather_behind_points(r, q, background, out, kernel_ms);
+    });
+}
+
+extern "C" int ph_renderer_direct_camera(ph_renderer* r, const double camera[10], uint32_t width, uint32_t height, const pt_direct_params* p, const pt_direct_buffers* out,
+                                         double* kernel_ms) {
+    if (!r || !camera || !p || !out) return bad("null argument");
+    if (const char* why = camera_form_error(width, height, out->sum || out->lit || out->valid)) return bad(why);
+    return guarded([&]() -> int {
+        pt_camera pc;
+        if (int code = camera_points(r, camera, width, height, &pc)) return code;
+        pt_direct_params q = *p;
+        q.n = (uint64_t)width * height; q.first_index = 0; q.flags = PT_AO_FACE_EYE | (p->flags & PT_DIRECT_TO_LIGHT);
+        for (int k = 0; k < 3; k++) q.eye[k] = pc.eye[k];
+        return direct_behind_points(r, q, out, kernel_ms);
+    });
+}
+
+// The point passes at every texel of a mesh's light map: point q = y * width + x is pt_chart's, first_index 0, no PT_AO_FACE_EYE (a chart's normals face outwards
+// or, with PT_CHART_FLIP_NORMAL, inwards). Of `params` samples, pass, seed, bias - an ambient-occlusion pass's radius, a direct pass's PT_DIRECT_TO_LIGHT - are read.
+extern "C" int ph_renderer_ao_chart(ph_renderer* r, const pt_chart_params* chart, const double* uv, const pt_ao_params* p, const pt_ao_buffers* out, double* kernel_ms) {
+    if (!r || !chart || !p || !out) return bad("null argument");
+    if (const char* why = chart_form_error(chart, out->occluded || out->valid || out->bent)) return bad(why);
+    return guarded([&]() -> int {
+        if (int code = chart_points(r, chart, uv)) return code;
+        pt_ao_params q = *p;
+        q.n = (uint64_t)chart->width * chart->height; q.first_index = 0; q.flags = 0;
+        return ao_behind_points(r, q, out, kernel_ms);
+    });
+}
+
+extern "C" int ph_renderer_gather_chart(ph_renderer* r, const pt_chart_params* chart, const double* uv, const pt_gather_params* p, const double* background,
+                                        const pt_gather_buffers* out, double* kernel_ms) {
+    if (!r || !chart || !p || !background || !out) return bad("null argument");
+    if (const char* why = chart_form_error(chart, out->sum || out->valid)) return bad(why);
+    return guarded([&]() -> int {
+        if (int code = chart_points(r, chart, uv)) return code;
+        pt_gather_params q = *p;
+        q.n = (uint64_t)chart->width * chart->height; q.first_index = 0; q.flags = 0;
+        return gather_behind_points(r, q, background, out, kernel_ms);
+    });
+}
+
 extern "C" int ph_renderer_direct_chart(ph_renderer* r, const pt_chart_params* chart, const double* uv, const pt_direct_params* p, const pt_direct_buffers* out,
                                         double* kernel_ms) {
     if (!r || !chart || !p || !out) return bad("null argument");
-    if (chart->width == 0 || chart->height == 0) return bad("width and height must be positive");
-    if ((uint64_t)chart->width * chart->height > PT_AO_MAX) return bad("more than PT_AO_MAX texels");
-    if (!(out->sum || out->lit || out->valid)) return bad("no output buffer asked for");
+    if (const char* why = chart_form_error(chart, out->sum || out->lit || out->valid)) return bad(why);
     return guarded([&]() -> int {
-        pt_context* c = r->r->context();
-        const uint64_t n = (uint64_t)chart->width * chart->height;
-        int rc = chart_points(r, chart, uv);
-        if (rc) { g_error = pt_last_error(c); return rc == PT_ERR_ARGUMENT ? PH_ERR_ARGUMENT : PH_ERR_RUNTIME; }
+        if (int code = chart_points(r, chart, uv)) return code;
         pt_direct_params q = *p;
-        q.n = n; q.first_index = 0; q.flags = p->flags & PT_DIRECT_TO_LIGHT;
-        return direct_behind_points(r, n, q, out, kernel_ms);
+        q.n = (uint64_t)chart->width * chart->height; q.first_index = 0; q.flags = p->flags & PT_DIRECT_TO_LIGHT;
+        return direct_behind_points(r, q, out, kernel_ms);
     });
 }
 
