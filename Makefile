@@ -81,10 +81,10 @@ $(OBJDIR)/%.o: $(CSRC)/%.hip $(HIP_HDRS) tools/check_exec_prologue.py
 #   direct    the direct-light pass (pt_direct_inst.hip): a point's shadow rays at the scene's lights made in registers (pt_direct.h), pt_segments' walks, summed per point
 #   probe     the probe pass (pt_probe_inst.hip): the same interpreter over the probe contract's rays, a sphere about a point made in registers (pt_probe.h), weighted with the
 #             order-2 spherical-harmonic basis and summed per probe and round of 64; <TEX, PARK> per mode; the fold over a probe's rounds (pt_probe.hip): the %.o rule
-#   film      the film's sampling kernel (pt_film.h): the same interpreter with the camera as its source; its fold and resolve kernels (pt_film.hip): the %.o rule
-#   lens      the film's sampling kernel behind a lens (pt_lens_inst.hip): pt_film_kernel's frame with the lens contract's primary rays (pt_lens.h); the fold behind it is the film's
+#   film      the film's sampling kernel (pt_film.h): the shading passes' frame (pt_shade_frame.h) with the camera as its source; its fold and resolve kernels (pt_film.hip): the %.o rule
+#   lens      the film's sampling kernel behind a lens (pt_lens_inst.hip): the film's policy on that frame with the lens contract's primary rays (pt_lens.h); the fold behind it is the film's
 #   (chart    the chart pass has no tree walk and no modes: its three kernels and the host replay of its contract, pt_chart.hip, are built by the %.o rule)
-#   film_map  the film's per-pixel budget (pt_film_map.h): the sampling kernel over a list of samples; its plan, fold, error and budget kernels (pt_film_map.hip): the %.o rule
+#   film_map  the film's per-pixel budget (pt_film_map.h): the same frame over a list of samples, its length read on the device; its plan, fold, error and budget kernels (pt_film_map.hip): the %.o rule
 # Static pattern rules, each over its own nine objects: as a plain pattern, pt_film_m%.o would match pt_film_map.o and pt_film_map_m1.o too.
 PASSES := render aov guides rays segments ao radiance gather direct probe film film_map lens
 define mode_rule

@@ -6,8 +6,8 @@
 // starting together. A lane makes its ray in registers when the item starts; lanes of invalid points (pt_ao_valid), lanes past n and rays pt_radiance would not
 // trace (pt_rays_traced: the origin can leave the range through a huge bias) take no part in a walk, the last kind leaving the background in their own column.
 //
-// Nothing of the shading is new: this is pt_film_kernel's frame (pt_film.h) - persistent wavefronts, one item at a time from 16 interleaved queues, the
-// argument block re-read through the kernarg segment, 3 waves per SIMD, LDS as pt_render_lds_bytes lays it out - around pt_source_advance with PtGatherSource
+// Nothing of the shading is new: the kernel's frame is the shading passes' (pt_shade_frame.h holds it for the film's kernels, this kernel keeps its
+// own copy because on the shared frame two of its instantiations spill differently) around pt_source_advance with PtGatherSource
 // (pt_gather_inst.h). When every lane is PT_ST_DONE each lane's sample sits in its own LDS column (PT_L_VALUE); behind a wavefront barrier the first lane of a
 // point's group adds the group's S columns from (0, 0, 0) in ascending k and writes the point's 24 bytes - pt_ao_kernel's pattern for `bent`, and the render
 // kernels' for a chunk's sum - so the pass needs no LDS beyond the frame's.
@@ -15,17 +15,6 @@
 
 #include "pt_radiance.h"
 #include "pt_gather_inst.h"
-
-// The argument block seen again through the kernarg segment (pt_radiance_args_again)
-PT_HD const PtGatherArgs& pt_gather_args_again(const PtGatherArgs& a) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    const __attribute__((address_space(4))) PtGatherArgs* ka = (const __attribute__((address_space(4))) PtGatherArgs*)__builtin_amdgcn_kernarg_segment_ptr();
-    asm volatile("" : "+s"(ka));
-    return *(const PtGatherArgs*)ka;
-#else
-    return a;
-#endif
-}
 
 template <int MODE, bool TEX, int PARK>
 __global__ void __launch_bounds__(PT_BLOCK, pt_gather_waves(MODE)) pt_gather_kernel(PtGatherArgs a0) {
@@ -90,7 +79,7 @@ __global__ void __launch_bounds__(PT_BLOCK, pt_gather_waves(MODE)) pt_gather_ker
             const bool active = L.stage != PT_ST_DONE;
             if (!__any(active)) break;
             // what the interpreter and this pass's walk need of the arguments is fetched now, not kept from the top of the kernel on (pt_render_kernel)
-            const PtGatherArgs& aa = pt_gather_args_again(a0);
+            const PtGatherArgs& aa = pt_args_again(a0);
             const PtRenderArgs& a = aa.r;
             PtGatherSource src;
             src.first_index = aa.set.first_index; src.samples = aa.samples; src.pass = aa.set.pass;
@@ -110,7 +99,7 @@ __global__ void __launch_bounds__(PT_BLOCK, pt_gather_waves(MODE)) pt_gather_ker
 #if defined(__HIP_DEVICE_COMPILE__)
         asm volatile("" : "+s"(w_again));
 #endif
-        const PtGatherArgs& ab = pt_gather_args_again(a0);
+        const PtGatherArgs& ab = pt_args_again(a0);
         const uint64_t p_again = ((uint64_t)w_again << (6u - ab.log2_samples)) + (lane >> ab.log2_samples);
         if (p_again < ab.n && (lane & (ab.samples - 1u)) == 0u) {
             const double* P = ab.positions + 3 * (size_t)p_again;
@@ -129,14 +118,10 @@ __global__ void __launch_bounds__(PT_BLOCK, pt_gather_waves(MODE)) pt_gather_ker
     }
 }
 
-// Launch (or, with launch = false, only size) the pass: the grid is what is resident, by the render kernels' launcher (pt_launch_kernel_args).
-template <int MODE>
-static hipError_t pt_gather_launch(const PtGatherArgs& a, bool tex, bool park, int n_cu, hipStream_t stream, uint32_t* grid_out, bool launch) {
-    const size_t lds = pt_render_lds_bytes(a.r.stack_lds_cap, tex, park ? 1 : 0);
-    if (tex) {
-        if (park) return pt_launch_kernel_args<&pt_gather_kernel<MODE, true, 1>>(lds, a, a.r.n_items, a.r.grid_share, n_cu, stream, grid_out, launch);
-        return pt_launch_kernel_args<&pt_gather_kernel<MODE, true, 0>>(lds, a, a.r.n_items, a.r.grid_share, n_cu, stream, grid_out, launch);
-    }
-    if (park) return pt_launch_kernel_args<&pt_gather_kernel<MODE, false, 1>>(lds, a, a.r.n_items, a.r.grid_share, n_cu, stream, grid_out, launch);
-    return pt_launch_kernel_args<&pt_gather_kernel<MODE, false, 0>>(lds, a, a.r.n_items, a.r.grid_share, n_cu, stream, grid_out, launch);
-}
+// What pt_shade_launch (pt_shade_frame.h) asks of a pass
+struct PtGatherPass {
+    using Args = PtGatherArgs;
+    static PT_HD const PtRenderArgs& render(const PtGatherArgs& a0) { return a0.r; }
+    template <int MODE, bool TEX, int PARK>
+    static constexpr auto kernel() { return &pt_gather_kernel<MODE, TEX, PARK>; }
+};

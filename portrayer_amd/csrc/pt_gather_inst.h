@@ -12,7 +12,7 @@
 
 struct PtGatherArgs {
     PtRenderArgs r;            // scene, seed, recursion frames, stack areas, work queues, overflow flag; n_items = wavefronts' worth of points (64 / S each).
-                               // FIRST: the kernel re-reads the block through the kernarg segment (pt_gather_args_again), and pt_kd_layout & co. take a PtRenderArgs
+                               // FIRST: the kernel re-reads the block through the kernarg segment (pt_args_again), and pt_kd_layout & co. take a PtRenderArgs
     uint64_t n;                // points
     const double* positions;   // n x 3
     const double* normals;     // n x 3

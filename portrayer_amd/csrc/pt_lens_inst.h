@@ -11,14 +11,14 @@
 #include "pt_lens.h"
 
 struct PtLensArgs {
-    PtFilmArgs f;    // what pt_film_kernel takes, unchanged. FIRST: the kernel re-reads the block through the kernarg segment (pt_lens_args_again), and the
+    PtFilmArgs f;    // what pt_film_kernel takes, unchanged. FIRST: the kernel re-reads the block through the kernarg segment (pt_args_again), and the
                      // interpreter and the walks take the PtRenderArgs at its start
     PtLensSet lens;  // model, aperture, focus, extent: the same in every lane
 };
 static_assert(offsetof(PtLensArgs, f) == 0, "the kernel reads PtFilmArgs (and PtRenderArgs) at the start of its argument block");
 
 // The lens film's source (SRC of pt_source_advance / pt_source_light_position): PtFilmSource except for the primary ray. `lens` points into the argument block
-// as the kernarg segment shows it (pt_lens_args_again): the four fields are scalar loads where a sample starts, not registers carried across the walks.
+// as the kernarg segment shows it (pt_args_again): the four fields are scalar loads where a sample starts, not registers carried across the walks.
 struct PtLensSource {
     const PtLensSet* lens;
     PT_HD uint32_t sample(const PtRenderArgs&, const PtLane& L) const { return L.item; }

@@ -12,7 +12,7 @@
 
 struct PtProbeArgs {
     PtRenderArgs r;            // scene, seed, recursion frames, stack areas, work queues, overflow flag; n_items = n x R wavefronts, item w = (probe w / R, round w % R).
-                               // FIRST: the kernel re-reads the block through the kernarg segment (pt_probe_args_again), and pt_kd_layout & co. take a PtRenderArgs
+                               // FIRST: the kernel re-reads the block through the kernarg segment (pt_args_again), and pt_kd_layout & co. take a PtRenderArgs
     uint64_t n;                // probes of this launch
     const double* positions;   // n x 3
     PtProbeSet set;            // seed, first_index (the stream index of this launch's probe 0), pass: what pt_probe_dir reads (set.seed == r.seed)

@@ -9,8 +9,8 @@
 // per probe would not, and the item stays the size of pt_gather_kernel's. A lane makes its ray in registers when the item starts; the lanes of an invalid probe
 // (pt_probe_valid) take no part in a walk.
 //
-// Nothing of the shading is new: this is pt_gather_kernel's frame (pt_gather.h) - persistent wavefronts, one item at a time from 16 interleaved queues, the
-// argument block re-read through the kernarg segment, 3 waves per SIMD, LDS as pt_render_lds_bytes lays it out - around pt_source_advance with PtProbeSource
+// Nothing of the shading is new: the kernel's frame is the shading passes' (pt_shade_frame.h holds it for the film's kernels, this kernel keeps its
+// own copy, as pt_gather_kernel does, because on the shared frame its instantiations spill differently) around pt_source_advance with PtProbeSource
 // (pt_probe_inst.h). When every lane is PT_ST_DONE each lane's sample sits in its own LDS column (PT_L_VALUE) and the column's other seven slots (PT_L_N ..
 // PT_L_TAG) are dead: the lane makes its direction again from the item, writes the basis values Y1 .. Y7 into those seven and keeps Y8 in a register (Y0 is a
 // constant). Behind a wavefront barrier lanes 0 .. 26 each own one (coefficient i, channel c) pair, t = 3 i + c, and add the 64 terms Y_i(d_k) rgb_k[c] from 0 in
@@ -27,17 +27,6 @@
 #define PT_INST_CAT(a, b) PT_INST_CAT2(a, b)
 
 static_assert(PT_L_VALUE == 0 && PT_LDS_FRAME_F64 == 10, "the tail keeps Y1 .. Y7 in slots 3 .. 9 of a finished lane's column, beside its colour in 0 .. 2");
-
-// The argument block seen again through the kernarg segment (pt_radiance_args_again)
-PT_HD const PtProbeArgs& pt_probe_args_again(const PtProbeArgs& a) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    const __attribute__((address_space(4))) PtProbeArgs* ka = (const __attribute__((address_space(4))) PtProbeArgs*)__builtin_amdgcn_kernarg_segment_ptr();
-    asm volatile("" : "+s"(ka));
-    return *(const PtProbeArgs*)ka;
-#else
-    return a;
-#endif
-}
 
 // Lane k's 64 bits, in every lane (k wave-uniform)
 __device__ inline unsigned long long pt_probe_lane_u64(unsigned long long u, unsigned k) {
@@ -113,7 +102,7 @@ __global__ void __launch_bounds__(PT_BLOCK, pt_probe_waves(MODE)) pt_probe_kerne
             const bool active = L.stage != PT_ST_DONE;
             if (!__any(active)) break;
             // what the interpreter and this pass's walk need of the arguments is fetched now, not kept from the top of the kernel on (pt_render_kernel)
-            const PtProbeArgs& aa = pt_probe_args_again(a0);
+            const PtProbeArgs& aa = pt_args_again(a0);
             const PtRenderArgs& a = aa.r;
             PtProbeSource src;
             src.first_index = aa.set.first_index; src.samples = aa.samples; src.pass = aa.set.pass;
@@ -128,7 +117,7 @@ __global__ void __launch_bounds__(PT_BLOCK, pt_probe_waves(MODE)) pt_probe_kerne
 #if defined(__HIP_DEVICE_COMPILE__)
         asm volatile("" : "+s"(w_again));
 #endif
-        const PtProbeArgs& ab = pt_probe_args_again(a0);
+        const PtProbeArgs& ab = pt_args_again(a0);
         const uint32_t p_again = w_again >> ab.log2_rounds;
         const uint32_t r_again = w_again & ((1u << ab.log2_rounds) - 1u);
         const double* P = ab.positions + 3 * (size_t)p_again;
@@ -173,18 +162,14 @@ __global__ void __launch_bounds__(PT_BLOCK, pt_probe_waves(MODE)) pt_probe_kerne
     }
 }
 
-// Launch (or, with launch = false, only size) the pass: the grid is what is resident, by the render kernels' launcher (pt_launch_kernel_args).
-template <int MODE>
-static hipError_t pt_probe_launch(const PtProbeArgs& a, bool tex, bool park, int n_cu, hipStream_t stream, uint32_t* grid_out, bool launch) {
-    const size_t lds = pt_render_lds_bytes(a.r.stack_lds_cap, tex, park ? 1 : 0);
-    if (tex) {
-        if (park) return pt_launch_kernel_args<&pt_probe_kernel<MODE, true, 1>>(lds, a, a.r.n_items, a.r.grid_share, n_cu, stream, grid_out, launch);
-        return pt_launch_kernel_args<&pt_probe_kernel<MODE, true, 0>>(lds, a, a.r.n_items, a.r.grid_share, n_cu, stream, grid_out, launch);
-    }
-    if (park) return pt_launch_kernel_args<&pt_probe_kernel<MODE, false, 1>>(lds, a, a.r.n_items, a.r.grid_share, n_cu, stream, grid_out, launch);
-    return pt_launch_kernel_args<&pt_probe_kernel<MODE, false, 0>>(lds, a, a.r.n_items, a.r.grid_share, n_cu, stream, grid_out, launch);
-}
+// What pt_shade_launch (pt_shade_frame.h) asks of a pass
+struct PtProbePass {
+    using Args = PtProbeArgs;
+    static PT_HD const PtRenderArgs& render(const PtProbeArgs& a0) { return a0.r; }
+    template <int MODE, bool TEX, int PARK>
+    static constexpr auto kernel() { return &pt_probe_kernel<MODE, TEX, PARK>; }
+};
 
 hipError_t PT_INST_CAT(pt_probe_launch_mode_, PT_INST_MODE)(const PtProbeArgs& a, bool tex, bool park, int n_cu, hipStream_t stream, uint32_t* grid, bool launch) {
-    return pt_probe_launch<PT_INST_MODE>(a, tex, park, n_cu, stream, grid, launch);
+    return pt_shade_launch<PT_INST_MODE, PtProbePass>(a, tex, park, n_cu, stream, grid, launch);
 }

@@ -13,22 +13,13 @@
 // No counting variant, no fork / join, no occluder table (that one belongs to a render's tiles).
 //
 // LDS of a block as in pt_render_kernel: the traversal stack area, the hit frame per lane, and (PARK = 1) the youngest parked recursion frame per lane; older
-// frames in the lane's own 128-byte lines in HBM (PtRenderArgs::spill). Persistent wavefronts, one item at a time from 16 interleaved queues.
+// frames in the lane's own 128-byte lines in HBM (PtRenderArgs::spill). Persistent wavefronts, one item at a time from 16 interleaved queues. This is the
+// shading passes' frame: pt_shade_frame.h holds it for the film's kernels, this kernel keeps its own copy because on the shared frame four of
+// its instantiations spill differently. The launcher and the re-read of the argument block are the shared ones.
 #pragma once
 
-#include "pt_render_kernel.h"
+#include "pt_shade_frame.h"
 #include "pt_radiance_inst.h"
-
-// The argument block seen again through the kernarg segment (pt_args_again, pt_render_simple.h): what a pass needs of it is fetched where it is used.
-PT_HD const PtRadianceArgs& pt_radiance_args_again(const PtRadianceArgs& a) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    const __attribute__((address_space(4))) PtRadianceArgs* ka = (const __attribute__((address_space(4))) PtRadianceArgs*)__builtin_amdgcn_kernarg_segment_ptr();
-    asm volatile("" : "+s"(ka));
-    return *(const PtRadianceArgs*)ka;
-#else
-    return a;
-#endif
-}
 
 // ------------------------------------------------------------------------------------------------
 // The interpreter with a SOURCE. pt_source_advance and pt_source_light_position are pt_lane_advance and pt_light_position (pt_shade.h) restated line for
@@ -388,7 +379,7 @@ __global__ void __launch_bounds__(PT_BLOCK, pt_radiance_waves(MODE)) pt_radiance
             const bool active = L.stage != PT_ST_DONE;
             if (!__any(active)) break;
             // what the interpreter and this pass's walk need of the arguments is fetched now, not kept from the top of the kernel on (pt_render_kernel)
-            const PtRadianceArgs& aa = pt_radiance_args_again(a0);
+            const PtRadianceArgs& aa = pt_args_again(a0);
             const PtRenderArgs& a = aa.r;
             PtRaySource src;
             src.bg = aa.background; src.bg_stride = aa.bg_stride; src.sample_index = aa.sample; src.stream_base = aa.stream_base;
@@ -407,14 +398,10 @@ __global__ void __launch_bounds__(PT_BLOCK, pt_radiance_waves(MODE)) pt_radiance
     }
 }
 
-// Launch (or, with launch = false, only size) the pass: the grid is what is resident, by the render kernels' launcher (pt_launch_kernel_args).
-template <int MODE>
-static hipError_t pt_radiance_launch(const PtRadianceArgs& a, bool tex, bool park, int n_cu, hipStream_t stream, uint32_t* grid_out, bool launch) {
-    const size_t lds = pt_render_lds_bytes(a.r.stack_lds_cap, tex, park ? 1 : 0);
-    if (tex) {
-        if (park) return pt_launch_kernel_args<&pt_radiance_kernel<MODE, true, 1>>(lds, a, a.r.n_items, a.r.grid_share, n_cu, stream, grid_out, launch);
-        return pt_launch_kernel_args<&pt_radiance_kernel<MODE, true, 0>>(lds, a, a.r.n_items, a.r.grid_share, n_cu, stream, grid_out, launch);
-    }
-    if (park) return pt_launch_kernel_args<&pt_radiance_kernel<MODE, false, 1>>(lds, a, a.r.n_items, a.r.grid_share, n_cu, stream, grid_out, launch);
-    return pt_launch_kernel_args<&pt_radiance_kernel<MODE, false, 0>>(lds, a, a.r.n_items, a.r.grid_share, n_cu, stream, grid_out, launch);
-}
+// What pt_shade_launch (pt_shade_frame.h) asks of a pass
+struct PtRadiancePass {
+    using Args = PtRadianceArgs;
+    static PT_HD const PtRenderArgs& render(const PtRadianceArgs& a0) { return a0.r; }
+    template <int MODE, bool TEX, int PARK>
+    static constexpr auto kernel() { return &pt_radiance_kernel<MODE, TEX, PARK>; }
+};

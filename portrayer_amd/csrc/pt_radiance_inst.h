@@ -11,7 +11,7 @@
 
 struct PtRadianceArgs {
     PtRenderArgs r;             // scene, seed, recursion frames, stack areas, work queues, overflow flag; n_items = wavefronts' worth of rays (64 each).
-                                // FIRST: the kernel re-reads the block through the kernarg segment (pt_radiance_args_again), and pt_kd_layout & co. take a PtRenderArgs
+                                // FIRST: the kernel re-reads the block through the kernarg segment (pt_args_again), and pt_kd_layout & co. take a PtRenderArgs
     uint64_t n;                 // rays
     const double* origins;      // n x 3
     const double* directions;   // n x 3

@@ -9,5 +9,5 @@
 #define PT_INST_CAT(a, b) PT_INST_CAT2(a, b)
 
 hipError_t PT_INST_CAT(pt_radiance_launch_mode_, PT_INST_MODE)(const PtRadianceArgs& a, bool tex, bool park, int n_cu, hipStream_t stream, uint32_t* grid, bool launch) {
-    return pt_radiance_launch<PT_INST_MODE>(a, tex, park, n_cu, stream, grid, launch);
+    return pt_shade_launch<PT_INST_MODE, PtRadiancePass>(a, tex, park, n_cu, stream, grid, launch);
 }

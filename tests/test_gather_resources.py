@@ -46,7 +46,11 @@ def test_the_wave_count_and_the_lds_are_the_interpreter_passes():
     src = open(os.path.join(CSRC, "pt_gather_inst.h")).read()
     assert re.search(r"constexpr int pt_gather_waves\(int /\*mode\*/\) \{ return 3; \}", src), "pt_gather_waves changed: update BUDGET here knowingly"
     kernel = open(os.path.join(CSRC, "pt_gather.h")).read()
-    assert "__launch_bounds__(PT_BLOCK, pt_gather_waves(MODE))" in kernel and "pt_render_lds_bytes(a.r.stack_lds_cap, tex, park ? 1 : 0)" in kernel
+    assert "__launch_bounds__(PT_BLOCK, pt_gather_waves(MODE))" in kernel
+    # the launcher is the shading passes' (pt_shade_frame.h): the LDS of the PtRenderArgs the pass names, a.r
+    frame = open(os.path.join(CSRC, "pt_shade_frame.h")).read()
+    assert "const PtRenderArgs& r = PASS::render(a);" in frame and "pt_render_lds_bytes(r.stack_lds_cap, tex, park ? 1 : 0)" in frame
+    assert "render(const PtGatherArgs& a0) { return a0.r; }" in kernel and "pt_shade_launch<PT_INST_MODE, PtGatherPass>" in open(os.path.join(CSRC, "pt_gather_inst.hip")).read()
     api = open(os.path.join(CSRC, "pt_api.hip")).read()
     assert "pt_interp_sizing(c, a.r)" in function_body(api, "static int pt_gather_common("), "pt_gather_common sizes its LDS with pt_interp_sizing"
 

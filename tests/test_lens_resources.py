@@ -50,10 +50,18 @@ def test_the_wave_count_the_lds_and_the_frame_are_the_films():
     assert re.search(r"constexpr int pt_lens_waves\(int /\*mode\*/\) \{ return 3; \}", src), "pt_lens_waves changed: update BUDGET here knowingly"
     assert "PtFilmArgs f;" in src and "offsetof(PtLensArgs, f) == 0" in src
     kernel = open(os.path.join(CSRC, "pt_lens_inst.hip")).read()
-    assert "__launch_bounds__(PT_BLOCK, pt_lens_waves(MODE))" in kernel and "pt_render_lds_bytes(a.f.r.stack_lds_cap, tex, park ? 1 : 0)" in kernel
-    assert "__shared__ uint32_t pt_lds[]" in kernel and kernel.count("__shared__") == 1, "no LDS beyond the frame's"
-    assert kernel.count("pt_film_item_slot(") == 2 and "pt_source_advance<TEX, HIER, PARK, PtLensSource>" in kernel, "the film's item-to-slot mapping, the lens' source"
-    assert "src.lens = &aa.lens" in kernel and "pt_lens_args_again(a0)" in kernel, "the lens is read through the kernarg segment where a sample starts"
+    assert "__launch_bounds__(PT_BLOCK, pt_lens_waves(MODE))" in kernel and "pt_shade_frame<MODE, TEX, PARK, PtLensPass>(a0)" in kernel
+    # the frame and the launcher are the shading passes' (pt_shade_frame.h): the LDS of the PtRenderArgs the pass names, a.f.r, and none beyond the frame's
+    frame = open(os.path.join(CSRC, "pt_shade_frame.h")).read()
+    assert "const PtRenderArgs& r = PASS::render(a);" in frame and "pt_render_lds_bytes(r.stack_lds_cap, tex, park ? 1 : 0)" in frame
+    assert "render(const PtLensArgs& a0) { return a0.f.r; }" in kernel and "pt_shade_launch<PT_INST_MODE, PtLensPass>" in kernel
+    assert "__shared__ uint32_t pt_lds[]" in frame and frame.count("__shared__") == 1 and "__shared__" not in kernel, "no LDS beyond the frame's"
+    # the film's item-to-slot mapping (its begin and finish, on the PtFilmArgs at the start of the block), the lens' source
+    film = open(os.path.join(CSRC, "pt_film.h")).read()
+    assert "PtFilmPass::begin(a0.f, " in kernel and "PtFilmPass::finish(a0.f, " in kernel and film.count("pt_film_item_slot(") == 3
+    assert "using Source = PtLensSource;" in kernel and "pt_source_advance<TEX, HIER, PARK, typename PASS::Source>" in frame
+    # the lens is read through the kernarg segment where a sample starts: source() gets the block the frame has just seen again
+    assert "src.lens = &aa.lens" in kernel and "const typename PASS::Args& aa = pt_args_again(a0);" in frame and "PASS::source(aa, src);" in frame
     api = open(os.path.join(CSRC, "pt_api.hip")).read()
     assert "k = pt_interp_sizing(c, a.r)" in function_body(api, "static int pt_film_pass_args("), "the lens add sizes its LDS as the film's add does: the same function"
 

@@ -50,7 +50,11 @@ def test_the_wave_count_and_the_lds_are_the_interpreter_passes():
     src = open(os.path.join(CSRC, "pt_probe_inst.h")).read()
     assert re.search(r"constexpr int pt_probe_waves\(int /\*mode\*/\) \{ return 3; \}", src), "pt_probe_waves changed: update BUDGET here knowingly"
     kernel = open(os.path.join(CSRC, "pt_probe_inst.hip")).read()
-    assert "__launch_bounds__(PT_BLOCK, pt_probe_waves(MODE))" in kernel and "pt_render_lds_bytes(a.r.stack_lds_cap, tex, park ? 1 : 0)" in kernel
+    assert "__launch_bounds__(PT_BLOCK, pt_probe_waves(MODE))" in kernel
+    # the launcher is the shading passes' (pt_shade_frame.h): the LDS of the PtRenderArgs the pass names, a.r
+    frame = open(os.path.join(CSRC, "pt_shade_frame.h")).read()
+    assert "const PtRenderArgs& r = PASS::render(a);" in frame and "pt_render_lds_bytes(r.stack_lds_cap, tex, park ? 1 : 0)" in frame
+    assert "render(const PtProbeArgs& a0) { return a0.r; }" in kernel and "pt_shade_launch<PT_INST_MODE, PtProbePass>" in kernel
     assert "__shared__ uint32_t pt_lds[]" in kernel and kernel.count("__shared__") == 1, "no LDS beyond the frame's"
     api = open(os.path.join(CSRC, "pt_api.hip")).read()
     assert "pt_interp_sizing(c, a.r)" in function_body(api, "static int pt_probe_common("), "pt_probe_common sizes its LDS with pt_interp_sizing"
