@@ -1019,6 +1019,37 @@ typedef struct pt_scene_traits {
  * it - *kernel_mode (PT_KERNEL_MODE_*) and *kernel_variant (PT_KERNEL_*, without PT_KERNEL_COUNTING). mode: the scene's PT_KERNEL_MODE_*, or a negative
  * number for the one that follows from the traits; textured: some material of the scene has a texture or a normal map. */
 int pt_test_kernel_choice(const pt_scene_traits *traits, int mode, int textured, uint32_t *kernel_mode, uint32_t *kernel_variant);
+/* What a render launch depends on besides the PORTRAYER_* switches: the scene's traits, its mode (PT_KERNEL_MODE_*; negative: the one that follows from the traits),
+ * whether it is textured, whether the launch counts (collect_stats), the scene's flattened nodes, lights and traversal-stack entries per lane, the launch's shape - pixel
+ * slots (own tiles x 64), wavefront work items, sample chunks per pixel, log2 of the samples (K) and chunks (C) of a pixel side by side in a wavefront (K C = 64: a
+ * wavefront is one pixel), the slice's tiles per row, the ranks that share the frame's tiles - and the blocks of the chosen kernel resident on the device. */
+typedef struct pt_launch_query {
+    pt_scene_traits traits;
+    int32_t mode, textured, stats;
+    uint32_t n_nodes, n_lights;
+    int32_t stack_cap;
+    uint32_t n_slots, n_items, n_chunks, k_log2, c_log2, tiles_x, tile_ranks;
+    uint32_t grid;
+} pt_launch_query;
+/* The words of a launch's plan (pt_test_launch_plan): the kernel as pt_stats reports it (PT_KERNEL_COUNTING included), its PT_RUN_* number, its waves per SIMD above
+ * three (0: three), parked frames per lane in LDS, LDS bytes a block may take, whether lanes keep recursion frames in HBM, traversal-stack entries per lane in LDS, the
+ * share of the resident blocks; how the work items are dealt; the bytes of the slot's five buffers (EYE_TAB_BYTES 0: the launch has none); in `misc` the dark-light
+ * records and the occluder table, in `eye_tab` (which begins with the eye table) the certain-shadow table, the list header, the records and the queue, as byte offsets
+ * (a region the launch does not have is empty, its offset the next region's); PT_PLAN_HAS_* bits; the entries a list holds at most, the words of the list kernel's
+ * pending list, the occluder table's entries per tile row; PORTRAYER_OCC_SEED's request (0 none, 1 hashed, 2 all:K) and its seed or K; the word the list header is
+ * set to in front of the list kernel. */
+enum { PT_PLAN_KERNEL_MODE, PT_PLAN_KERNEL_VARIANT, PT_PLAN_RUN_VARIANT, PT_PLAN_MORE_WAVES, PT_PLAN_PARK_SLOTS, PT_PLAN_BLOCK_BUDGET, PT_PLAN_NEEDS_SPILL, PT_PLAN_STACK_LDS_CAP,
+       PT_PLAN_GRID_SHARE, PT_PLAN_N_LANES, PT_PLAN_WORK_DIV, PT_PLAN_BATCH_MAX, PT_PLAN_FINE_QUEUES, PT_PLAN_ITEM_STRIDE,
+       PT_PLAN_SPILL_BYTES, PT_PLAN_STACK_SPILL_BYTES, PT_PLAN_MISC_BYTES, PT_PLAN_ACCUM_BYTES, PT_PLAN_EYE_TAB_BYTES,
+       PT_PLAN_DARK_OFF, PT_PLAN_DARK_BYTES, PT_PLAN_OCC_OFF, PT_PLAN_OCC_BYTES, PT_PLAN_CERTAIN_OFF, PT_PLAN_HEADER_OFF, PT_PLAN_RECORDS_OFF, PT_PLAN_QUEUE_OFF,
+       PT_PLAN_HAS, PT_PLAN_LIST_CAP, PT_PLAN_LIST_PENDING, PT_PLAN_OCC_ROW, PT_PLAN_OCC_SEED, PT_PLAN_OCC_SEED_VALUE, PT_PLAN_HEADER_FILL, PT_PLAN_WORDS };
+/* PT_PLAN_HAS: the occluder table; the eye table; the certain-shadow table; the dark-light records (zeroed) and the kernel that fills them; the list header; the
+ * per-pixel lists; the queue of the pixels that need the render kernel (the background skip) */
+enum { PT_PLAN_HAS_OCCLUDERS = 1, PT_PLAN_HAS_EYE_TABLE = 2, PT_PLAN_HAS_CERTAIN_TABLE = 4, PT_PLAN_HAS_DARK_RECORDS = 8, PT_PLAN_HAS_DARK_LIGHTS = 16,
+       PT_PLAN_HAS_LIST_HEADER = 32, PT_PLAN_HAS_PIXEL_LISTS = 64, PT_PLAN_HAS_QUEUE = 128 };
+/* Host-side (no GPU, no context): the plan of a render launch with these inputs under the environment's PORTRAYER_* switches, as PT_PLAN_WORDS words. A malformed
+ * PORTRAYER_OCC_SEED, PORTRAYER_PIXEL_LIST_CAP or PORTRAYER_PIXEL_LIST_PENDING: PT_ERR_ARGUMENT, the words of the refusal in why (optional, why_bytes bytes). */
+int pt_test_launch_plan(const pt_launch_query *query, uint64_t *words, char *why, uint64_t why_bytes);
 /* Host-side run (no GPU, no context) of the tree walks' single-precision slab test. Pair i: the ray origins[3i..], directions[3i..] over [0, t_max[i]]
  * against the box box_lo[3i..], box_hi[3i..]. body 0: the ray constants as the kernels are built, 1: their form with f64 products, 2: their f32 form.
  * Out per pair: the interval the per-lane form computed (t_near, t_far) and verdict - bit 0 the per-lane form accepts the box, bit 1 the wavefront

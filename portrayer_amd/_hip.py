@@ -76,6 +76,31 @@ class PtRenderParams(C.Structure):
                 ("collect_stats", C.c_int32)]
 
 
+class PtSceneTraits(C.Structure):
+    """pt_scene_traits: what an uploaded scene says that the choice of its render kernel depends on."""
+    _fields_ = [("traverse", C.c_int32), ("n_nodes", C.c_uint32), ("n_lights", C.c_uint32), ("has_meshes", C.c_int32), ("has_kdmesh", C.c_int32),
+                ("reflective", C.c_int32), ("reflective_opaque", C.c_int32), ("glossy", C.c_int32), ("area_light", C.c_int32), ("pad", C.c_int32),
+                ("instanced_tris", C.c_uint64)]
+
+
+class PtLaunchQuery(C.Structure):
+    """pt_launch_query: what a render launch's plan depends on besides the PORTRAYER_* switches (pt_test_launch_plan)."""
+    _fields_ = [("traits", PtSceneTraits), ("mode", C.c_int32), ("textured", C.c_int32), ("stats", C.c_int32), ("n_nodes", C.c_uint32), ("n_lights", C.c_uint32),
+                ("stack_cap", C.c_int32), ("n_slots", C.c_uint32), ("n_items", C.c_uint32), ("n_chunks", C.c_uint32), ("k_log2", C.c_uint32), ("c_log2", C.c_uint32),
+                ("tiles_x", C.c_uint32), ("tile_ranks", C.c_uint32), ("grid", C.c_uint32)]
+
+
+# the words of a plan, in the header's order (PT_PLAN_*), and the bits of PLAN_HAS
+PLAN_NAMES = ("KERNEL_MODE", "KERNEL_VARIANT", "RUN_VARIANT", "MORE_WAVES", "PARK_SLOTS", "BLOCK_BUDGET", "NEEDS_SPILL", "STACK_LDS_CAP", "GRID_SHARE", "N_LANES", "WORK_DIV",
+              "BATCH_MAX", "FINE_QUEUES", "ITEM_STRIDE", "SPILL_BYTES", "STACK_SPILL_BYTES", "MISC_BYTES", "ACCUM_BYTES", "EYE_TAB_BYTES", "DARK_OFF", "DARK_BYTES", "OCC_OFF",
+              "OCC_BYTES", "CERTAIN_OFF", "HEADER_OFF", "RECORDS_OFF", "QUEUE_OFF", "HAS", "LIST_CAP", "LIST_PENDING", "OCC_ROW", "OCC_SEED", "OCC_SEED_VALUE", "HEADER_FILL")
+for _k, _name in enumerate(PLAN_NAMES):
+    globals()["PLAN_" + _name] = _k
+PLAN_WORDS = len(PLAN_NAMES)
+(PLAN_HAS_OCCLUDERS, PLAN_HAS_EYE_TABLE, PLAN_HAS_CERTAIN_TABLE, PLAN_HAS_DARK_RECORDS, PLAN_HAS_DARK_LIGHTS, PLAN_HAS_LIST_HEADER, PLAN_HAS_PIXEL_LISTS,
+ PLAN_HAS_QUEUE) = (1 << k for k in range(8))
+
+
 class PtAovParams(C.Structure):
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("slice", PtRect), ("offset", C.c_double * 2)]
 
@@ -287,7 +312,7 @@ EXPORTS = ["pt_abi_version", "pt_device_count", "pt_context_create", "pt_context
            "pt_film_denoise", "pt_film_denoise_device", "pt_test_denoise_host",
            "pt_guides", "pt_guides_device", "pt_guides_finish", "pt_film_denoise_albedo", "pt_film_denoise_albedo_device", "pt_test_denoise_albedo_host",
            "pt_ao", "pt_ao_device", "pt_ao_finish", "pt_test_ao_rays_host", "pt_test_ao_tables",
-           "pt_gather", "pt_gather_device", "pt_gather_finish", "pt_test_kernel_choice",
+           "pt_gather", "pt_gather_device", "pt_gather_finish", "pt_test_kernel_choice", "pt_test_launch_plan",
            "pt_chart_triangles", "pt_chart", "pt_chart_device", "pt_test_chart_host",
            "pt_direct", "pt_direct_device", "pt_direct_finish", "pt_test_direct_host",
            "pt_probe", "pt_probe_device", "pt_probe_finish", "pt_test_probe_host", "pt_test_probe_tables",
@@ -386,6 +411,8 @@ def lib() -> C.CDLL:
         l.pt_test_dark_lights.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.c_uint64, C.POINTER(C.c_uint64)]
         l.pt_test_raypk.restype = C.c_int
         l.pt_test_raypk.argtypes = [C.c_uint64, C.c_int, _dp, _dp, _dp, C.POINTER(C.c_float), C.POINTER(C.c_float), _ip, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+        l.pt_test_launch_plan.restype = C.c_int
+        l.pt_test_launch_plan.argtypes = [C.POINTER(PtLaunchQuery), _u64p, C.c_char_p, C.c_uint64]
         l.pt_test_pixel_list_summary.restype = C.c_int
         l.pt_test_pixel_list_summary.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
         l.pt_test_pixel_beam.restype = C.c_int

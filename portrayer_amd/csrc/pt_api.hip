@@ -151,7 +151,7 @@ __global__ void pt_untile_kernel(PtRenderArgs a, uint32_t slots_per_rank, const 
     d[0] = s[0]; d[1] = s[1]; d[2] = s[2];
 }
 
-// PORTRAYER_OCC_SEED (tests only, pt_render_common): the occluder table filled with hints the test chooses instead of zeros - every entry
+// PORTRAYER_OCC_SEED (tests only, pt_plan_launch): the occluder table filled with hints the test chooses instead of zeros - every entry
 // `all` + 1, or entry i = hash(seed, i) mod (n_nodes + 1) (0: none). The table's test is exact whatever an entry holds (pt_trace_packet).
 __global__ void __launch_bounds__(256) pt_occ_seed_kernel(uint32_t* __restrict__ occ, uint32_t n, int hashed, uint64_t seed, uint32_t all, uint32_t n_nodes) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -498,7 +498,7 @@ static int pt_pass_prepare(pt_context* c, PtPass& v) {
 
 // The work buffers for a launch of `grid` blocks (the sizing dispatch's figure, with r.stack_lds_cap set) and `r` pointed into them; then misc zeroed and the first
 // event on `stream`. frames: the kernels keep recursion frames (the interpreter's). The items come one at a time from 16 interleaved queues, as a render of this
-// size has them (pt_render_common).
+// size has them (pt_plan_launch).
 static int pt_pass_open(pt_context* c, PtPass& v, PtRenderArgs& r, uint32_t grid, bool frames, hipStream_t stream) {
     r.n_lanes = grid * PT_BLOCK;
     int rc;
@@ -684,8 +684,7 @@ extern "C" const char* pt_last_error(const pt_context* c) { return c ? c->err.c_
 // PORTRAYER_TWO_STREAMS=0 / 1 forces one / two.
 extern "C" void* pt_context_stream(pt_context* c, int slot) {
     if (!c) return nullptr;
-    bool two = !(c->have_scene && pt_needs_spill(c->traits));
-    if (const char* e = getenv("PORTRAYER_TWO_STREAMS")) two = atoi(e) > 0;
+    const bool two = pt_env_on("PORTRAYER_TWO_STREAMS", !(c->have_scene && pt_needs_spill(c->traits)));
     return (void*)c->slot[two ? (slot & 1) : 0].stream;
 }
 extern "C" int pt_context_next_slot(const pt_context* c) { return c ? c->slot_next : 0; }
@@ -873,15 +872,16 @@ extern "C" int pt_test_raypk(uint64_t n, int body, const double* origins, const 
 extern "C" int pt_test_pixel_list_summary(pt_context* c, uint64_t* out) {
     if (!c || !out) return PT_ERR_ARGUMENT;
     for (uint32_t k = 0; k < 5u + PT_PL_K; k++) out[k] = 0;
-    if (c->pl_slot < 0 || c->pl_slots == 0) return PT_OK;
+    const PtLaunchPlan& p = c->last.plan;
+    if (!p.pixel_lists) return PT_OK;
     PT_HIP(c, hipSetDevice(c->device));
     PT_HIP(c, hipDeviceSynchronize());
-    std::vector<uint32_t> rec((size_t)c->pl_slots * PT_PL_WORDS);
-    const pt_context::Slot& sl = c->slot[c->pl_slot];
-    if (sl.eye_tab.bytes < c->pl_off + rec.size() * 4) return pt_fail(c, PT_ERR_ARGUMENT, "the slot's buffer no longer holds that launch's lists");
-    PT_HIP(c, hipMemcpy(rec.data(), (const char*)sl.eye_tab.p + c->pl_off, rec.size() * 4, hipMemcpyDeviceToHost));
-    out[0] = c->pl_slots;
-    for (uint32_t i = 0; i < c->pl_slots; i++) {
+    std::vector<uint32_t> rec((size_t)p.n_slots * PT_PL_WORDS);
+    const pt_context::Slot& sl = c->slot[c->last.slot];
+    if (sl.eye_tab.bytes < p.queue_off) return pt_fail(c, PT_ERR_ARGUMENT, "the slot's buffer no longer holds that launch's lists");
+    PT_HIP(c, hipMemcpy(rec.data(), (const char*)sl.eye_tab.p + p.records_off, rec.size() * 4, hipMemcpyDeviceToHost));
+    out[0] = p.n_slots;
+    for (uint32_t i = 0; i < p.n_slots; i++) {
         const uint32_t head = rec[(size_t)i * PT_PL_WORDS], tail = rec[(size_t)i * PT_PL_WORDS + 1];
         if (head & PT_PL_WALK) { out[3]++; continue; }
         const uint32_t n = head & 255u;
@@ -964,16 +964,17 @@ extern "C" int pt_test_rect_beam(uint64_t n, const double* cameras, const uint32
 // `out` is not NULL and `words` >= info[0] info[1], the records are copied to it; with fewer words (0: a query of the sizes) nothing is copied.
 extern "C" int pt_test_pixel_list_records(pt_context* c, uint32_t* out, uint64_t words, uint64_t* info) {
     if (!c || !info) return PT_ERR_ARGUMENT;
-    info[0] = 0; info[1] = PT_PL_WORDS; info[2] = PT_PL_K; info[3] = c->pl_nodes;
-    if (c->pl_slot < 0 || c->pl_slots == 0) return PT_OK;
-    info[0] = c->pl_slots;
-    const size_t need = (size_t)c->pl_slots * PT_PL_WORDS;
+    const PtLaunchPlan& p = c->last.plan;
+    info[0] = 0; info[1] = PT_PL_WORDS; info[2] = PT_PL_K; info[3] = p.n_nodes;
+    if (!p.pixel_lists) return PT_OK;
+    info[0] = p.n_slots;
+    const size_t need = (size_t)p.n_slots * PT_PL_WORDS;
     if (!out || words < need) return PT_OK;
     PT_HIP(c, hipSetDevice(c->device));
     PT_HIP(c, hipDeviceSynchronize());
-    const pt_context::Slot& sl = c->slot[c->pl_slot];
-    if (sl.eye_tab.bytes < c->pl_off + need * 4) return pt_fail(c, PT_ERR_ARGUMENT, "the slot's buffer no longer holds that launch's lists");
-    PT_HIP(c, hipMemcpy(out, (const char*)sl.eye_tab.p + c->pl_off, need * 4, hipMemcpyDeviceToHost));
+    const pt_context::Slot& sl = c->slot[c->last.slot];
+    if (sl.eye_tab.bytes < p.queue_off) return pt_fail(c, PT_ERR_ARGUMENT, "the slot's buffer no longer holds that launch's lists");
+    PT_HIP(c, hipMemcpy(out, (const char*)sl.eye_tab.p + p.records_off, need * 4, hipMemcpyDeviceToHost));
     return PT_OK;
 }
 
@@ -982,21 +983,21 @@ extern "C" int pt_test_pixel_list_records(pt_context* c, uint32_t* out, uint64_t
 // info[1], the first info[1] slot ids are copied to it.
 extern "C" int pt_test_pixel_list_queue(pt_context* c, uint32_t* out, uint64_t words, uint64_t* info) {
     if (!c || !info) return PT_ERR_ARGUMENT;
-    info[0] = info[1] = 0; info[2] = c->pl_slots;
-    if (c->pl_slot < 0 || c->pl_slots == 0 || !c->pl_queue) return PT_OK;
+    const PtLaunchPlan& p = c->last.plan;
+    info[0] = info[1] = 0; info[2] = p.n_slots;
+    if (!p.background_skip) return PT_OK;
     info[0] = 1;
     PT_HIP(c, hipSetDevice(c->device));
     PT_HIP(c, hipDeviceSynchronize());
-    const pt_context::Slot& sl = c->slot[c->pl_slot];
-    const size_t queue_off = c->pl_off + (size_t)c->pl_slots * PT_PL_WORDS * 4;
-    if (sl.eye_tab.bytes < queue_off + (size_t)c->pl_slots * 4) return pt_fail(c, PT_ERR_ARGUMENT, "the slot's buffer no longer holds that launch's queue");
+    const pt_context::Slot& sl = c->slot[c->last.slot];
+    if (sl.eye_tab.bytes < p.queue_off + (size_t)p.n_slots * 4) return pt_fail(c, PT_ERR_ARGUMENT, "the slot's buffer no longer holds that launch's queue");
     uint32_t head[2] = {0u, 0u};
-    PT_HIP(c, hipMemcpy(head, (const char*)sl.eye_tab.p + c->pl_off - 64, sizeof head, hipMemcpyDeviceToHost));
+    PT_HIP(c, hipMemcpy(head, (const char*)sl.eye_tab.p + p.header_off, sizeof head, hipMemcpyDeviceToHost));
     if (!(head[0] & PT_PL_QUEUE)) return pt_fail(c, PT_ERR_TRAVERSAL, "the header of a launch with a queue does not say so");
     info[1] = head[1];
-    if (head[1] > c->pl_slots) return pt_fail(c, PT_ERR_TRAVERSAL, "more pixels queued than the launch has slots");
+    if (head[1] > p.n_slots) return pt_fail(c, PT_ERR_TRAVERSAL, "more pixels queued than the launch has slots");
     if (!out || words < head[1] || head[1] == 0u) return PT_OK;
-    PT_HIP(c, hipMemcpy(out, (const char*)sl.eye_tab.p + queue_off, (size_t)head[1] * 4, hipMemcpyDeviceToHost));
+    PT_HIP(c, hipMemcpy(out, (const char*)sl.eye_tab.p + p.queue_off, (size_t)head[1] * 4, hipMemcpyDeviceToHost));
     return PT_OK;
 }
 
@@ -1074,15 +1075,16 @@ extern "C" int pt_test_dark_light(uint64_t n, int type, const double* fwd, const
 extern "C" int pt_test_dark_lights(pt_context* c, uint32_t* out, uint64_t words, uint64_t* info) {
     if (!c || !info) return PT_ERR_ARGUMENT;
     info[0] = 0; info[1] = PT_DARK_WORDS;
-    if (c->dark_slot < 0 || c->dark_lights == 0) return PT_OK;
-    info[0] = c->dark_lights;
-    const size_t need = (size_t)c->dark_lights * PT_DARK_WORDS;
+    const PtLaunchPlan& p = c->last.plan;
+    if (p.dark_bytes == 0) return PT_OK;
+    info[0] = p.n_lights;
+    const size_t need = p.dark_bytes / 4;
     if (!out || words < need) return PT_OK;
     PT_HIP(c, hipSetDevice(c->device));
     PT_HIP(c, hipDeviceSynchronize());
-    const pt_context::Slot& sl = c->slot[c->dark_slot];
-    if (sl.misc.bytes < c->dark_off + need * 4) return pt_fail(c, PT_ERR_ARGUMENT, "the slot's buffer no longer holds that launch's records");
-    PT_HIP(c, hipMemcpy(out, (const char*)sl.misc.p + c->dark_off, need * 4, hipMemcpyDeviceToHost));
+    const pt_context::Slot& sl = c->slot[c->last.slot];
+    if (sl.misc.bytes < p.occ_off) return pt_fail(c, PT_ERR_ARGUMENT, "the slot's buffer no longer holds that launch's records");
+    PT_HIP(c, hipMemcpy(out, (const char*)sl.misc.p + p.dark_off, p.dark_bytes, hipMemcpyDeviceToHost));
     return PT_OK;
 }
 
@@ -1092,26 +1094,27 @@ extern "C" int pt_test_dark_lights(pt_context* c, uint32_t* out, uint64_t words,
 // scene's whole stack. The k-d walk keeps no saved bounds in HBM (round 5): its wavefront rows must hold the stack and, where the stack's slack is too small for it, the two
 // rows of the path table (pt_kd_layout, PtKdSav) - also under PORTRAYER_LDS_STACK=1 (experiments / tests of the overflow path), which then only shrinks the LANES' stacks.
 static bool pt_kd_semantics(int mode) { return mode == PT_MODE_KD || mode == PT_MODE_KD_NOMESH || mode == PT_MODE_KD_MESH; }
-static int pt_stack_lds_cap(const PtSceneView& sc, size_t block_budget, size_t frame_bytes) {
+static int pt_stack_lds_cap(int mode, int stack_cap, size_t block_budget, size_t frame_bytes) {
     int lds_cap = block_budget > frame_bytes ? (int)((block_budget - frame_bytes) / (PT_BLOCK * 4)) : 0;
-    lds_cap = std::max(lds_cap, 2);
-    if (const char* e = getenv("PORTRAYER_LDS_STACK")) lds_cap = std::max(1, atoi(e));
-    int cap = std::min(lds_cap, sc.stack_cap);
-    if (pt_kd_semantics(sc.mode)) cap = std::max(cap, (sc.stack_cap + 63) / 64 + 2);
+    lds_cap = pt_env_clamped("PORTRAYER_LDS_STACK", std::max(lds_cap, 2), 1, INT_MAX);
+    int cap = std::min(lds_cap, stack_cap);
+    if (pt_kd_semantics(mode)) cap = std::max(cap, (stack_cap + 63) / 64 + 2);
     return cap;
 }
+static int pt_stack_lds_cap(const PtSceneView& sc, size_t block_budget, size_t frame_bytes) { return pt_stack_lds_cap(sc.mode, sc.stack_cap, block_budget, frame_bytes); }
 // pt_stack_column: entries of a lane's HBM stack column (PtStackSpill::gbase). + wave_rows: the wavefront's own stack takes LDS rows from the lanes' stacks (pt_wave_rows,
 // pt_render_simple.h): eight, or what a deep tree needs; and at least everything a lane's own stack can reach (pt_trace_wave gives the lanes fewer LDS rows in the k-d semantics).
-static size_t pt_stack_column(const PtSceneView& sc, int stack_lds_cap) {
-    const int wave_rows = std::min(std::max(8, (sc.stack_cap + 63) / 64), std::max(stack_lds_cap, 8));  // (pt_wave_rows: at most this many)
-    const int stack_spill_entries = std::max(sc.stack_cap - stack_lds_cap + wave_rows, 0);
-    return (size_t)std::max(stack_spill_entries, sc.stack_cap);
+static size_t pt_stack_column(int stack_cap, int stack_lds_cap) {
+    const int wave_rows = std::min(std::max(8, (stack_cap + 63) / 64), std::max(stack_lds_cap, 8));  // (pt_wave_rows: at most this many)
+    const int stack_spill_entries = std::max(stack_cap - stack_lds_cap + wave_rows, 0);
+    return (size_t)std::max(stack_spill_entries, stack_cap);
 }
+static size_t pt_stack_column(const PtSceneView& sc, int stack_lds_cap) { return pt_stack_column(sc.stack_cap, stack_lds_cap); }
 
 // What a pass's sizing dispatch reads of the host-side fields. The passes that only walk (primary visibility, ray queries): the LDS stack area is sized like a
 // render's for the waves per SIMD the mode's instantiation is compiled for, with no hit frame beside the stacks.
 static void pt_walk_sizing(PtRenderArgs& r, int waves) {
-    r.stack_lds_cap = pt_stack_lds_cap(r.scene, waves == 3 ? 52 * 1024 : 39 * 1024, 0);  // 3 x 52 KB or 4 x 39 KB of the CU's 160 KB
+    r.stack_lds_cap = pt_stack_lds_cap(r.scene, pt_block_budget(waves), 0);
     r.grid_share = 1;
 }
 // The interpreter passes (radiance, the film's): LDS per block as a render's interpreter kernel has it - three blocks per CU, the stack area beside the hit
@@ -1120,11 +1123,10 @@ struct PtInterp { bool tex, park; };
 static PtInterp pt_interp_sizing(const pt_context* c, PtRenderArgs& r) {
     PtInterp k;
     k.tex = r.scene.mat_maps != nullptr;
-    k.park = pt_spawns(c->traits);
-    if (const char* e = getenv("PORTRAYER_PARK")) k.park = k.park && atoi(e) > 0;  // 0: every parked frame in HBM (tests, measurements), as for a render
+    k.park = pt_spawns(c->traits) && pt_env_park();  // (as for a render)
     r.park_slots = k.park ? 1 : 0;
     const size_t frame_bytes = (size_t)(PT_LDS_FRAME_F64 + r.park_slots * PT_PARK_F64) * PT_BLOCK * 8;
-    r.stack_lds_cap = pt_stack_lds_cap(r.scene, 52 * 1024, frame_bytes);  // 3 x 52 KB of the CU's 160 KB (pt_radiance_waves, pt_film_waves)
+    r.stack_lds_cap = pt_stack_lds_cap(r.scene, pt_block_budget(3), frame_bytes);  // (pt_radiance_waves, pt_film_waves)
     r.grid_share = 1;
     return k;
 }
@@ -1135,19 +1137,12 @@ static PtInterp pt_interp_sizing(const pt_context* c, PtRenderArgs& r) {
 // wave count - from what the scene says (PtSceneTraits), its mode, whether it is textured, and the PORTRAYER_WAVES, KD_WAVES, CHAIN, CHAIN_WAVES, PARK, FORK and
 // LDS_BUDGET_KB switches, which nothing else reads for this. No context, no HIP call (pt_test_kernel_choice).
 // ------------------------------------------------------------------------------------------------
-struct PtKernelChoice {
-    int run_variant = PT_RUN_LINE3, four_waves = 0, park_slots = 0;
-    size_t block_budget = 0;
-    bool needs_spill = false;  // the lanes keep recursion frames in HBM
-};
-
 // The straight-line kernel, flat_scene / hierarchical semantics.
 // The 4-waves-per-SIMD kernel for scenes where the tree walk outweighs the shading: many scene-level nodes or many instanced
 // triangles, nothing reflective, flat_scene semantics (measured: big-scene +8.7 %, big-soup +6.8 %; macho-cows
 // with its 23 nodes and 17,500 triangles -8 %; reflective scenes and the k-d walk lose, profiles/r02/notes.md)
 static int pt_line_waves(const PtSceneTraits& t, int mode, bool tex) {
-    if (const char* e = getenv("PORTRAYER_WAVES")) {
-        const int wv = atoi(e);
+    if (const int wv = pt_env_clamped("PORTRAYER_WAVES", -1, 0, 6); wv >= 0) {
         if (wv < 4) return 0;
         if (wv >= 5 && (mode == PT_MODE_FLAT_NOMESH || mode == PT_MODE_HIER_NOMESH)) return PT_LINE_TOP_WAVES;
         return (wv >= 5 && (mode == PT_MODE_FLAT || mode == PT_MODE_HIER_MESH)) ? PT_MESH_TOP_WAVES : 4;
@@ -1183,8 +1178,7 @@ static int pt_line_waves(const PtSceneTraits& t, int mode, bool tex) {
 // Round 4 (one walk per wavefront, pt_trace_packet_kd): mesh-free scenes with many nodes at 5 waves (big-scene 29.2 -> 28.1 ms, c10), scenes with plain
 // Mesh instances (PT_MODE_KD_MESH: no KDMesh walker compiled in) at 4; with KDMesh trees the kernel needs its 168 registers.
 static int pt_line_waves_kd(const PtSceneTraits& t, int mode) {
-    if (const char* e = getenv("PORTRAYER_KD_WAVES")) {
-        const int wv = atoi(e);
+    if (const int wv = pt_env_clamped("PORTRAYER_KD_WAVES", -1, 0, 6); wv >= 0) {
         return (wv < 4 || mode == PT_MODE_KD) ? 0 : ((wv >= 5 && mode == PT_MODE_KD_NOMESH) ? 5 : 4);
     }
     return (mode == PT_MODE_KD_NOMESH && t.n_nodes >= 256) ? 5 : (mode == PT_MODE_KD_MESH ? 4 : 0);
@@ -1196,7 +1190,7 @@ static int pt_line_waves_kd(const PtSceneTraits& t, int mode) {
 // (Only where that was measured or the compiler's figures are like the measured case's: untextured, no KDMesh trees - those
 // instantiations spill 57 / 142 registers at 128.)
 static int pt_chain_waves(int mode, bool tex) {
-    if (const char* e = getenv("PORTRAYER_CHAIN_WAVES")) return (atoi(e) == 4 && mode != PT_MODE_KD) ? 4 : 0;
+    if (const int wv = pt_env_clamped("PORTRAYER_CHAIN_WAVES", -1, 0, 6); wv >= 0) return (wv == 4 && mode != PT_MODE_KD) ? 4 : 0;
     const bool flat_sem = (mode == PT_MODE_FLAT || mode == PT_MODE_FLAT_NOMESH || mode == PT_MODE_HIER_MESH) && !tex;  // (HIER_MESH: 22.2 -> 24.2, c41)
     return (flat_sem || (mode == PT_MODE_KD_MESH && !tex)) ? 4 : 0;
 }
@@ -1211,11 +1205,9 @@ static PtKernelChoice pt_choose_kernel(const PtSceneTraits& t, int mode, bool te
         k.run_variant = k.four_waves >= 5 ? PT_RUN_LINE5 : (k.four_waves ? PT_RUN_LINE4 : PT_RUN_LINE3);  // (LINE5: the densest instantiation the mode has)
     } else {
         // parked recursion frames kept in LDS (pt_shade.h): only scenes that park frames at all have any
-        bool park = true;
-        if (const char* e = getenv("PORTRAYER_PARK")) park = atoi(e) > 0;  // 0: every parked frame in HBM (tests, measurements)
+        const bool park = pt_env_park();
         // every reflective material is opaque (no index of refraction): a hit spawns at most one ray, the recursion is a chain
-        bool chain = t.reflective_opaque != 0;
-        if (const char* e = getenv("PORTRAYER_CHAIN")) chain = chain && atoi(e) > 0;  // 0: the interpreter kernel also for scenes whose recursion is a chain (A/B runs, tests)
+        const bool chain = t.reflective_opaque != 0 && pt_env_on("PORTRAYER_CHAIN", true);  // 0: the interpreter kernel also for scenes whose recursion is a chain (A/B runs, tests)
         if (chain && park) {
             k.run_variant = PT_RUN_CHAIN;
             k.park_slots = 0;  // no frame in LDS: the parked colours go straight to the lane's HBM lines
@@ -1227,14 +1219,13 @@ static PtKernelChoice pt_choose_kernel(const PtSceneTraits& t, int mode, bool te
             // fork / join of refracted subtrees (pt_shade.h) needs a recursion that draws no random numbers and a dielectric material to be of use:
             // no hit draws random numbers after the jitter (no area light, no glossy material): refracted subtrees may be walked by other lanes
             const bool forkable = !t.reflective_opaque && !t.glossy && !t.area_light && t.n_lights <= PT_LIGHT_ROUND;
-            bool fork = false;
-            if (const char* e = getenv("PORTRAYER_FORK")) fork = forkable && park && atoi(e) > 0;
+            const bool fork = forkable && park && pt_env_on("PORTRAYER_FORK", false);
             k.run_variant = park ? (fork ? PT_RUN_INTERP_FORK : PT_RUN_INTERP_PARK) : PT_RUN_INTERP;
             k.park_slots = park ? 1 : 0;
         }
     }
-    k.block_budget = k.four_waves >= 6 ? 26 * 1024 : (k.four_waves == 5 ? 31 * 1024 : (k.four_waves ? 39 * 1024 : 52 * 1024));  // 3 x 52 KB, 4 x 39 KB, 5 x 31 KB or 6 x 26 KB of the CU's 160 KB
-    if (const char* e = getenv("PORTRAYER_LDS_BUDGET_KB")) k.block_budget = (size_t)std::max(16, std::min(160, atoi(e))) * 1024;  // experiment: 80 = two blocks per CU
+    k.block_budget = pt_block_budget(k.four_waves ? k.four_waves : 3);
+    if (const int kb = pt_env_clamped("PORTRAYER_LDS_BUDGET_KB", 0, 16, 160)) k.block_budget = (size_t)kb * 1024;  // experiment: 80 = two blocks per CU
     return k;
 }
 
@@ -1254,217 +1245,259 @@ extern "C" int pt_test_kernel_choice(const pt_scene_traits* traits, int mode, in
     return PT_OK;
 }
 
-static int pt_render_common(pt_context* c, PtRenderArgs& a, bool stats, hipStream_t stream, int slot_index = -1) {
-    // LDS per block = traversal stack (as much of it as leaves room for three blocks per CU) + the shaded hit's frame (+ a parked one);
-    // deeper stack entries live in HBM (PtStackSpill).
-    if (getenv("PORTRAYER_NO_TEX")) a.scene.mat_maps = nullptr;  // experiment: the untextured kernel on a textured scene (wrong picture, timing only)
-    const bool tex = a.scene.mat_maps != nullptr;
-    const PtKernelChoice choice = pt_choose_kernel(c->traits, a.scene.mode, tex);
-    a.run_variant = choice.run_variant; a.four_waves = choice.four_waves; a.park_slots = choice.park_slots;
-    if (c->launch_seq == 0) c->launch_seq = (uint32_t)std::chrono::steady_clock::now().time_since_epoch().count() * 2654435761u;  // a different starting point in every context
-    a.launch_nonce = ++c->launch_seq;
-    const size_t frame_bytes = (size_t)(PT_LDS_FRAME_F64 + a.park_slots * PT_PARK_F64) * PT_BLOCK * 8;
-    a.stack_lds_cap = pt_stack_lds_cap(a.scene, choice.block_budget, frame_bytes);
-    a.grid_share = 1;  // (a share of the resident blocks per launch was tried for ranks that share a GPU, round 5 c23: their kernels do not run side by side - 35.5 -> 14.3 Gray/s)
-    uint32_t grid = 0;
-    PT_HIP(c, pt_dispatch(a, stats, c->n_cu, stream, &grid, false));
-    a.n_lanes = grid * PT_BLOCK;
-    a.work_div = std::max<uint32_t>(grid * (PT_BLOCK / 64) * 8u, 1u);  // batch = remaining items / (8 x resident wavefronts)
+// ------------------------------------------------------------------------------------------------
+// A render launch, planned (PtLaunchPlan, pt_context.h): how the work is dealt, the bytes of the slot's five buffers, where each table and list lies in
+// `misc` and `eye_tab`, and which of them this launch has - from the scene's traits, the launch's shape (pt_launch_query, the fields of PtRenderArgs a launch depends
+// on), the resident grid and the PORTRAYER_* switches. No context, no HIP call (pt_test_launch_plan). Two steps, because the size query needs the kernel and the
+// plan needs the grid: pt_plan_kernel, pt_dispatch(launch = false), pt_plan_launch; pt_render_common commits the result.
+// ------------------------------------------------------------------------------------------------
+// What the build compiled in (EXTRA_HIPFLAGS / make variant; the Makefile's SWITCHES), asked here and nowhere else in the host code. (A macro that is not defined
+// stringifies to its own name.)
+#define PT_STRINGIFY_(x) #x
+#define PT_STRINGIFY(x) PT_STRINGIFY_(x)
+constexpr bool pt_same_text(const char* a, const char* b) { return *a == *b && (*a == 0 || pt_same_text(a + 1, b + 1)); }
+#define PT_BUILT_WITH(flag) (!pt_same_text(#flag, PT_STRINGIFY(flag)))
+constexpr bool PT_EYE_TABLE = !PT_BUILT_WITH(PT_NO_EYE_TABLE), PT_CERTAIN_SHADOW = !PT_BUILT_WITH(PT_NO_CERTAIN_SHADOW), PT_DARK_LIGHTS = !PT_BUILT_WITH(PT_NO_DARK_LIGHTS),
+               PT_PIXEL_LISTS = !PT_BUILT_WITH(PT_NO_PIXEL_LISTS), PT_BACKGROUND_SKIP = !PT_BUILT_WITH(PT_NO_BACKGROUND_SKIP),
+               PT_LIST_STATS = PT_BUILT_WITH(PT_PIXEL_LIST_STATS),  // the counting build evaluates the lists beside its walk (pt_render_simple.h): it gets them too
+               PT_DEPTH_FIRST = PT_BUILT_WITH(PT_PL_DEPTH_FIRST);   // the list kernel as it was before round 13: it fills no queue
+
+typedef pt_launch_query PtLaunchQuery;
+static bool pt_parse_decimal(const char* text, unsigned long long* v) {
+    char* end = nullptr;
+    *v = strtoull(text, &end, 10);
+    return end != text && !*end;
+}
+
+// Step 1: the kernel, its variant word and the LDS split of its traversal stacks - what the size query (pt_dispatch) reads.
+// LDS per block = traversal stack (as much of it as leaves room for the kernel's blocks per CU) + the shaded hit's frame (+ a parked one); deeper stack entries live in
+// HBM (PtStackSpill).
+static void pt_plan_kernel(const PtLaunchQuery& q, PtLaunchPlan* plan) {
+    PtLaunchPlan& p = *plan;
+    p.choice = pt_choose_kernel(q.traits, q.mode, q.textured != 0);
+    p.kernel_mode = (uint32_t)q.mode;
+    p.kernel_variant = pt_choice_variant(p.choice, q.textured != 0) | (q.stats ? PT_KERNEL_COUNTING : 0u);
+    const size_t frame_bytes = (size_t)(PT_LDS_FRAME_F64 + p.choice.park_slots * PT_PARK_F64) * PT_BLOCK * 8;
+    p.stack_lds_cap = pt_stack_lds_cap(q.mode, q.stack_cap, p.choice.block_budget, frame_bytes);
+    p.grid_share = 1;  // (a share of the resident blocks per launch was tried for ranks that share a GPU, round 5 c23: their kernels do not run side by side - 35.5 -> 14.3 Gray/s)
+}
+
+// Step 2, with q.grid = the resident blocks pt_dispatch answered. PT_ERR_ARGUMENT and *why for a malformed PORTRAYER_OCC_SEED, PIXEL_LIST_CAP or PIXEL_LIST_PENDING.
+static int pt_plan_launch(const PtLaunchQuery& q, PtLaunchPlan* plan, std::string* why) {
+    PtLaunchPlan& p = *plan;
+    const bool flat_nomesh = q.mode == PT_MODE_FLAT_NOMESH, stats = q.stats != 0;
+    p.n_slots = q.n_slots; p.n_nodes = q.n_nodes; p.n_lights = q.n_lights;
+
     // How the work items are handed out (pt_render_kernel): batches of consecutive items from one counter, or - scenes whose
     // hits can spawn rays, where an item in the glass costs hundreds of times its neighbour - one item at a time from
     // interleaved queues. transmission-refraction: wavefronts resident 47 % of the launch and 5.2 Gray/s with batches, 11+ without.
-    a.batch_max = PT_WORK_BATCH_MAX;
-    if (const char* e = getenv("PORTRAYER_BATCH_MAX")) a.batch_max = (uint32_t)std::max(1, atoi(e));
+    const uint64_t resident_waves = (uint64_t)q.grid * (PT_BLOCK / 64);
+    p.n_lanes = q.grid * PT_BLOCK;
+    p.work_div = std::max<uint32_t>((uint32_t)resident_waves * 8u, 1u);  // batch = remaining items / (8 x resident wavefronts)
+    p.batch_max = (uint32_t)pt_env_clamped("PORTRAYER_BATCH_MAX", PT_WORK_BATCH_MAX, 1, INT_MAX);
     // The queues also win wherever a wavefront gets few items (a small frame, one GPU's share of a frame: big-scene's 1/8 share +8 %,
     // macho-cows +13 %) and on the mesh-heavy scenes (+3-7 %); very long launches (> 2048 items per resident wavefront: 3840x2160x256)
     // are 1 % better off with batches.
-    const uint64_t resident_waves = (uint64_t)grid * (PT_BLOCK / 64);
-    const bool long_launch = (uint64_t)a.n_items > 2048ull * std::max<uint64_t>(resident_waves, 1);
     // (round 3's per-lane k-d walk was 1 % better off with batches; the wave-uniform one is not: big-scene +1.1 %, macho-cows +3.2 % with the queues, round 4 c68)
-    a.fine_queues = (pt_spawns(c->traits) || !long_launch) ? 16 : 0;  // 8 .. 32 queues measured alike, 64 and 4 about 1 % behind
-    if (const char* e = getenv("PORTRAYER_FINE_QUEUES")) a.fine_queues = (uint32_t)std::max(0, std::min(PT_FINE_QUEUES, atoi(e)));
-    a.item_stride = 1;
+    const bool long_launch = (uint64_t)q.n_items > 2048ull * std::max<uint64_t>(resident_waves, 1);
+    p.fine_queues = (uint32_t)pt_env_clamped("PORTRAYER_FINE_QUEUES", (pt_spawns(q.traits) || !long_launch) ? 16 : 0, 0, PT_FINE_QUEUES);  // 8 .. 32 queues measured alike, 64 and 4 about 1 % behind
+    p.item_stride = 1;
     if (const char* e = getenv("PORTRAYER_ITEM_STRIDE")) {  // experiment (batches only): position q -> item (q * stride) mod n; "golden" = 0.618 n
-        uint64_t st = strcmp(e, "golden") == 0 ? (uint64_t)((double)a.n_items * 0.6180339887498949) : (uint64_t)atoll(e);
+        uint64_t st = strcmp(e, "golden") == 0 ? (uint64_t)((double)q.n_items * 0.6180339887498949) : (uint64_t)atoll(e);
         auto gcd = [](uint64_t x, uint64_t y) { while (y) { uint64_t t = x % y; x = y; y = t; } return x; };
-        if (a.n_items > 2 && st != 1) { st = st % a.n_items; if (st < 1) st = 1; while (gcd(st, a.n_items) != 1) st++; a.item_stride = (uint32_t)st; }
+        if (q.n_items > 2 && st != 1) { st = st % q.n_items; if (st < 1) st = 1; while (gcd(st, q.n_items) != 1) st++; p.item_stride = (uint32_t)st; }
     }
-    int rc;
-    if (slot_index < 0) {  // the host-buffer path (pt_render): one frame at a time
-        if (c->slot[c->slot_oldest].pending) return pt_fail(c, PT_ERR_ARGUMENT, "a render is in flight: pt_render_finish first");
-        slot_index = c->slot_next;
-    }
-    pt_context::Slot& sl = c->slot[slot_index];  // the launch's work buffers are its slot's: another frame may be in flight on the other slot's
-    const size_t spill_bytes = choice.needs_spill ?(size_t)a.n_lanes * PT_SPILL_DEPTHS * PT_SPILL_STRIDE * sizeof(double) : 16;
-    if ((rc = pt_reserve(c, sl.spill, spill_bytes))) return rc;
-    const size_t stack_column = pt_stack_column(a.scene, a.stack_lds_cap);
-    if ((rc = pt_reserve(c, sl.stack_spill, (size_t)a.n_lanes * stack_column * 4))) return rc;  // (the k-d walk's saved bounds needed columns behind this until round 5)
-    // The occluder table of the mesh-free walks' shadow rays (pt_trace_packet): one word per (own 8x8 tile, light), behind the work
-    // queues, zeroed with them before every launch - what it remembers comes from the frame being rendered, never from an earlier one.
-    // PORTRAYER_SHADOW_CACHE=0 leaves it out (A/B runs); so does a table of more than 4 MB (many lights: zeroing it would cost more).
-    const size_t misc_head = 256 + sizeof(PtCounters) + PT_FINE_QUEUES * PT_QUEUE_STRIDE * 4;
-    size_t occ_bytes = (size_t)(a.n_slots / 64) * a.scene.n_lights * 4;
-    if (!(a.scene.mode == PT_MODE_FLAT_NOMESH || a.scene.mode == PT_MODE_HIER_NOMESH) || occ_bytes > ((size_t)4 << 20)) occ_bytes = 0;
-    if (const char* e = getenv("PORTRAYER_SHADOW_CACHE")) if (atoi(e) <= 0) occ_bytes = 0;
+
+    p.spill = p.choice.needs_spill ? (size_t)p.n_lanes * PT_SPILL_DEPTHS * PT_SPILL_STRIDE * sizeof(double) : 16;
+    p.stack_spill = (size_t)p.n_lanes * pt_stack_column(q.stack_cap, p.stack_lds_cap) * 4;  // (the k-d walk's saved bounds needed columns behind this until round 5)
+    p.accum = (size_t)q.n_slots * q.n_chunks * 3 * sizeof(double);
+
+    // `misc`. The occluder table of the mesh-free walks' shadow rays (pt_trace_packet): one word per (own 8x8 tile, light), behind the work queues, zeroed with them
+    // before every launch - what it remembers comes from the frame being rendered, never from an earlier one. PORTRAYER_SHADOW_CACHE=0 leaves it out (A/B runs); so does
+    // a table of more than 4 MB (many lights: zeroing it would cost more).
+    p.occ_bytes = (size_t)(q.n_slots / 64) * q.n_lights * 4;
+    if (!(flat_nomesh || q.mode == PT_MODE_HIER_NOMESH) || p.occ_bytes > ((size_t)4 << 20) || !pt_env_on("PORTRAYER_SHADOW_CACHE", true)) p.occ_bytes = 0;
+    p.occ_row = std::max<uint32_t>(q.tiles_x / std::max<uint32_t>(q.tile_ranks, 1u), 1u);
     // PORTRAYER_OCC_SEED=all:K | <seed> (tests only): the table starts with hints the test chose (pt_occ_seed_kernel), not with zeros
-    bool occ_seed = false, occ_hashed = false;
-    uint64_t occ_seed_value = 0;
-    uint32_t occ_all = 0;
-    if (const char* e = getenv("PORTRAYER_OCC_SEED"); e && *e && occ_bytes) {
-        char* end = nullptr;
+    if (const char* e = getenv("PORTRAYER_OCC_SEED"); e && *e && p.occ_bytes) {
+        unsigned long long v = 0;
         if (strncmp(e, "all:", 4) == 0) {
-            const unsigned long long k = strtoull(e + 4, &end, 10);
-            if (end == e + 4 || *end || k >= a.scene.n_nodes) return pt_fail(c, PT_ERR_ARGUMENT, std::string("PORTRAYER_OCC_SEED=") + e + ": K must be a node index below " + std::to_string(a.scene.n_nodes));
-            occ_all = (uint32_t)k;
+            if (!pt_parse_decimal(e + 4, &v) || v >= q.n_nodes) { *why = std::string("PORTRAYER_OCC_SEED=") + e + ": K must be a node index below " + std::to_string(q.n_nodes); return PT_ERR_ARGUMENT; }
+            p.occ_seed = PT_OCC_SEED_ALL; p.occ_all = (uint32_t)v;
         } else {
-            occ_seed_value = strtoull(e, &end, 10);
-            if (end == e || *end) return pt_fail(c, PT_ERR_ARGUMENT, std::string("PORTRAYER_OCC_SEED=") + e + ": expected all:<node> or a decimal seed");
-            occ_hashed = true;
+            if (!pt_parse_decimal(e, &v)) { *why = std::string("PORTRAYER_OCC_SEED=") + e + ": expected all:<node> or a decimal seed"; return PT_ERR_ARGUMENT; }
+            p.occ_seed = PT_OCC_SEED_HASHED; p.occ_seed_value = v;
         }
-        occ_seed = true;
     }
     // The dark-light records (pt_dark_light_kernel; pt_certain.h 4.-8.) lie between the work queues and the occluder table, PT_DARK_WORDS words per light, zeroed with both:
-    // the flat_scene launches that have an occluder table, so that the kernel finds them from PtRenderArgs::occluders alone. PORTRAYER_DARK_LIGHTS=0 (tests, A/B runs
-    // from one library): the records stay zero - no light is skipped. -DPT_NO_DARK_LIGHTS: no records.
-#ifndef PT_NO_DARK_LIGHTS
-    const size_t dark_bytes = (a.scene.mode == PT_MODE_FLAT_NOMESH && occ_bytes != 0) ? (size_t)a.scene.n_lights * PT_DARK_WORDS * 4 : 0;
-    bool dark_lights = dark_bytes != 0 && a.scene.n_nodes > 0;
-    if (const char* e = getenv("PORTRAYER_DARK_LIGHTS")) if (atoi(e) <= 0) dark_lights = false;
-#else
-    const size_t dark_bytes = 0;
-    const bool dark_lights = false;
-#endif
-    if ((rc = pt_reserve(c, sl.misc, misc_head + dark_bytes + occ_bytes))) return rc;
-    if ((rc = pt_reserve(c, sl.accum, (size_t)a.n_slots * a.n_chunks * 3 * sizeof(double)))) return rc;
-    a.accum = (double*)sl.accum.p;
-    // The eye table of the mesh-free flat_scene semantics (pt_render_simple.h: EYE_TABLE): every launch in that mode gets one, whichever kernel runs - the counting,
-    // chain and interpreter kernels do not read it, and a launch's choice of kernel must never leave a kernel that does without
-#ifndef PT_NO_EYE_TABLE
-    const bool eye_table = a.scene.mode == PT_MODE_FLAT_NOMESH && a.scene.n_nodes > 0;
-#else
-    const bool eye_table = false;
-#endif
-    // The certain-shadow table (pt_render_simple.h: CERTAIN) behind it: the flat_scene launches that have an occluder table, whichever kernel runs
-#ifndef PT_NO_CERTAIN_SHADOW
-    const bool certain_table = a.scene.mode == PT_MODE_FLAT_NOMESH && a.scene.n_nodes > 0 && occ_bytes != 0;
-#else
-    const bool certain_table = false;
-#endif
+    // the flat_scene launches that have an occluder table, so that the kernel finds them from PtRenderArgs::occluders alone. -DPT_NO_DARK_LIGHTS: no records.
+    p.dark_bytes = (PT_DARK_LIGHTS && flat_nomesh && p.occ_bytes != 0) ? (size_t)q.n_lights * PT_DARK_WORDS * 4 : 0;
+    p.dark_off = 256 + sizeof(PtCounters) + PT_FINE_QUEUES * PT_QUEUE_STRIDE * 4;
+    p.occ_off = p.dark_off + p.dark_bytes;
+    p.misc = p.occ_off + p.occ_bytes;
+
+    // `eye_tab`. The eye table of the mesh-free flat_scene semantics (pt_render_simple.h: EYE_TABLE): every launch in that mode gets one, whichever kernel runs - the
+    // counting, chain and interpreter kernels do not read it, and a launch's choice of kernel must never leave a kernel that does without.
+    p.eye_table = PT_EYE_TABLE && flat_nomesh && q.n_nodes > 0;
+    // The certain-shadow table (pt_render_simple.h: CERTAIN) behind it: the flat_scene launches that have an occluder table, whichever kernel runs.
+    p.certain_table = PT_CERTAIN_SHADOW && flat_nomesh && q.n_nodes > 0 && p.occ_bytes != 0;
+    // The kernel that fills the dark-light records reads the certain-shadow table. PORTRAYER_DARK_LIGHTS=0 (tests, A/B runs from one library): the records stay zero - no
+    // light is skipped.
+    p.dark_lights = p.certain_table && p.dark_bytes != 0 && pt_env_on("PORTRAYER_DARK_LIGHTS", true);
     // The per-pixel candidate lists (pt_pixel_list.h; pt_render_simple.h: PIXEL_LISTS) behind both: the launches whose kernel reads them - the plain straight-line kernels of
     // this mode where a wavefront is one pixel - and scenes whose node indices fit an entry's 16 bits. Their 64-byte header is written in every launch that has an eye table
     // (0: no lists). PORTRAYER_PIXEL_LISTS=0: none (the walk's image from the same library); PORTRAYER_PIXEL_LIST_CAP=k (tests only): a list holds k entries at most, so that
     // small scenes reach the tail bound and the fall-back; PORTRAYER_PIXEL_LIST_PENDING=n (tests only): the list kernel's pending list holds n nodes at most, so that tiles get
     // marked "take the walk". -DPT_NO_PIXEL_LISTS: no header, no lists, the kernels as they were (A/B).
-#ifndef PT_NO_PIXEL_LISTS
-    const bool list_header = eye_table;
-#ifdef PT_PIXEL_LIST_STATS  // the counting build evaluates the lists beside its walk (pt_render_simple.h): it gets them too
-    const bool list_reader = true;
-#else
-    const bool list_reader = !stats;
-#endif
-    bool pixel_lists = eye_table && list_reader && (a.run_variant == PT_RUN_LINE3 || a.run_variant == PT_RUN_LINE4 || a.run_variant == PT_RUN_LINE5) && a.k_log2 + a.c_log2 == 6u &&
-                       a.scene.n_nodes <= PT_PL_MAX_NODES && a.n_slots != 0;
-    if (const char* e = getenv("PORTRAYER_PIXEL_LISTS")) if (atoi(e) <= 0) pixel_lists = false;
-    uint32_t list_cap = PT_PL_K;
-    if (const char* e = getenv("PORTRAYER_PIXEL_LIST_CAP"); e && *e) {
-        char* end = nullptr;
-        const unsigned long long k = strtoull(e, &end, 10);
-        if (end == e || *end || k > PT_PL_K) return pt_fail(c, PT_ERR_ARGUMENT, std::string("PORTRAYER_PIXEL_LIST_CAP=") + e + ": expected 0 .. " + std::to_string(PT_PL_K));
-        list_cap = (uint32_t)k;
-    }
-    uint32_t list_pending = 1024u;  // (the kernel's PT_PL_PENDING; the depth-first variant has its own stack and ignores it)
-    if (const char* e = getenv("PORTRAYER_PIXEL_LIST_PENDING"); e && *e) {
-        char* end = nullptr;
-        const unsigned long long k = strtoull(e, &end, 10);
-        if (end == e || *end || k < 1u || k > list_pending) return pt_fail(c, PT_ERR_ARGUMENT, std::string("PORTRAYER_PIXEL_LIST_PENDING=") + e + ": expected 1 .. " + std::to_string(list_pending));
-        list_pending = (uint32_t)k;
-    }
-#else
-    const bool list_header = false, pixel_lists = false;
-    const uint32_t list_cap = 0, list_pending = 0;
-#endif
+    const int v = p.choice.run_variant;
+    p.list_header = PT_PIXEL_LISTS && p.eye_table;
+    p.pixel_lists = p.list_header && (PT_LIST_STATS || !stats) && (v == PT_RUN_LINE3 || v == PT_RUN_LINE4 || v == PT_RUN_LINE5) && q.k_log2 + q.c_log2 == 6u &&
+                    q.n_nodes <= PT_PL_MAX_NODES && q.n_slots != 0 && pt_env_on("PORTRAYER_PIXEL_LISTS", true);
+    p.list_cap = PT_PIXEL_LISTS ? PT_PL_K : 0u;
+    p.list_pending = PT_PIXEL_LISTS ? 1024u : 0u;  // (the kernel's PT_PL_PENDING; the depth-first variant has its own stack and ignores it)
+    if (PT_PIXEL_LISTS && !(pt_env_strict("PORTRAYER_PIXEL_LIST_CAP", 0, PT_PL_K, &p.list_cap, why) && pt_env_strict("PORTRAYER_PIXEL_LIST_PENDING", 1, p.list_pending, &p.list_pending, why)))
+        return PT_ERR_ARGUMENT;
     // The queue of the pixels that need the render kernel (pt_pixel_list.h), behind the records: every launch that has lists. The render kernel deals only what is queued,
     // the finish kernel finishes the rest from the background. PORTRAYER_BACKGROUND_SKIP=0 (tests, A/B runs from one library): the lists as before, no queue, every
-    // item dealt. -DPT_NO_BACKGROUND_SKIP: the kernels as they were. The depth-first list kernel (-DPT_PL_DEPTH_FIRST) fills none.
-#if !defined(PT_NO_BACKGROUND_SKIP) && !defined(PT_NO_PIXEL_LISTS) && !defined(PT_PL_DEPTH_FIRST) && !defined(PT_PIXEL_LIST_STATS)
-    bool background_skip = pixel_lists;
-    if (const char* e = getenv("PORTRAYER_BACKGROUND_SKIP")) if (atoi(e) <= 0) background_skip = false;
-#else
-    const bool background_skip = false;
-#endif
-    if (background_skip) a.item_stride = 1;  // (PORTRAYER_ITEM_STRIDE, an experiment: its stride is coprime to n_items, not to the queue's length)
-    const size_t list_off = pt_pl_header_offset((uint32_t)a.scene.n_nodes);
-    a.eye_tab = nullptr;
-    if (eye_table || certain_table) {
-        if ((rc = pt_reserve(c, sl.eye_tab, list_header ? list_off + pt_pl_bytes(pixel_lists ? a.n_slots : 0u, background_skip) : (size_t)a.scene.n_nodes * (12 * sizeof(double) + 4 * sizeof(float))))) return rc;
-        a.eye_tab = (const double*)sl.eye_tab.p;
+    // item dealt. -DPT_NO_BACKGROUND_SKIP: the kernels as they were, and the header's words say whether lists follow.
+    p.background_skip = PT_BACKGROUND_SKIP && !PT_DEPTH_FIRST && !PT_LIST_STATS && p.pixel_lists && pt_env_on("PORTRAYER_BACKGROUND_SKIP", true);
+    if (p.background_skip) p.item_stride = 1;  // (PORTRAYER_ITEM_STRIDE, an experiment: its stride is coprime to n_items, not to the queue's length)
+    p.header_fill = (!PT_BACKGROUND_SKIP && p.pixel_lists) ? 1u : 0u;  // (all zero: the list kernel writes word 0 - what follows the header - and counts the queue in word 1)
+    const uint32_t listed = p.pixel_lists ? q.n_slots : 0u;
+    p.certain_off = (size_t)q.n_nodes * 12 * sizeof(double);
+    p.header_off = p.list_header ? pt_pl_header_offset(q.n_nodes) : p.certain_off + (size_t)q.n_nodes * 4 * sizeof(float);
+    p.records_off = p.header_off + (p.list_header ? 64u : 0u);
+    p.queue_off = p.list_header ? p.header_off + pt_pl_bytes(listed, false) : p.records_off;
+    p.eye_tab = !(p.eye_table || p.certain_table) ? 0 : (p.list_header ? p.header_off + pt_pl_bytes(listed, p.background_skip) : p.header_off);
+    return PT_OK;
+}
+
+extern "C" int pt_test_launch_plan(const pt_launch_query* query, uint64_t* words, char* why, uint64_t why_bytes) {
+    if (!query || !words) return PT_ERR_ARGUMENT;
+    PtLaunchQuery q = *query;
+    if (q.mode < 0) q.mode = pt_scene_mode(q.traits);
+    PtLaunchPlan p;
+    std::string err;
+    pt_plan_kernel(q, &p);
+    const int rc = pt_plan_launch(q, &p, &err);
+    if (why && why_bytes) snprintf(why, (size_t)why_bytes, "%s", err.c_str());
+    if (rc) return rc;
+    const uint64_t w[PT_PLAN_WORDS] = {
+        p.kernel_mode, p.kernel_variant, (uint64_t)p.choice.run_variant, (uint64_t)p.choice.four_waves, (uint64_t)p.choice.park_slots, p.choice.block_budget, p.choice.needs_spill,
+        (uint64_t)p.stack_lds_cap, p.grid_share, p.n_lanes, p.work_div, p.batch_max, p.fine_queues, p.item_stride, p.spill, p.stack_spill, p.misc, p.accum, p.eye_tab,
+        p.dark_off, p.dark_bytes, p.occ_off, p.occ_bytes, p.certain_off, p.header_off, p.records_off, p.queue_off,
+        (p.occ_bytes ? PT_PLAN_HAS_OCCLUDERS : 0u) | (p.eye_table ? PT_PLAN_HAS_EYE_TABLE : 0u) | (p.certain_table ? PT_PLAN_HAS_CERTAIN_TABLE : 0u) |
+            (p.dark_bytes ? PT_PLAN_HAS_DARK_RECORDS : 0u) | (p.dark_lights ? PT_PLAN_HAS_DARK_LIGHTS : 0u) | (p.list_header ? PT_PLAN_HAS_LIST_HEADER : 0u) |
+            (p.pixel_lists ? PT_PLAN_HAS_PIXEL_LISTS : 0u) | (p.background_skip ? PT_PLAN_HAS_QUEUE : 0u),
+        p.list_cap, p.list_pending, p.occ_row, (uint64_t)p.occ_seed, p.occ_seed == PT_OCC_SEED_ALL ? p.occ_all : p.occ_seed_value, p.header_fill};
+    memcpy(words, w, sizeof w);
+    return PT_OK;
+}
+
+// The fields of a launch's arguments that its plan depends on. PORTRAYER_NO_TEX: an experiment - the untextured kernel on a textured scene (wrong picture, timing only).
+static PtLaunchQuery pt_launch_query_of(const PtSceneTraits& traits, PtRenderArgs& a, bool stats) {
+    if (pt_env_set("PORTRAYER_NO_TEX")) a.scene.mat_maps = nullptr;
+    PtLaunchQuery q = {};
+    q.traits = traits; q.mode = a.scene.mode; q.textured = a.scene.mat_maps != nullptr; q.stats = stats;
+    q.n_nodes = a.scene.n_nodes; q.n_lights = a.scene.n_lights; q.stack_cap = a.scene.stack_cap;
+    q.n_slots = a.n_slots; q.n_items = a.n_items; q.n_chunks = a.n_chunks; q.k_log2 = a.k_log2; q.c_log2 = a.c_log2;
+    q.tiles_x = a.div_tiles_x.d; q.tile_ranks = a.tile_ranks;
+    return q;
+}
+
+static void pt_report_occ_seed(uint32_t n_occ) {
+    if (pt_env_set("PORTRAYER_VERBOSE")) fprintf(stderr, "[pt_render] occluder table: %u entries seeded (PORTRAYER_OCC_SEED=%s)\n", n_occ, getenv("PORTRAYER_OCC_SEED"));
+}
+
+// Commits a planned launch to slot `slot_index` (< 0: the host-buffer path, pt_render, one frame at a time) on `stream`: the slot's buffers reserved, `a` pointed into
+// them at the plan's offsets, `misc` zeroed, [the occluder table seeded,] ev0, the launch's tables and lists, the render kernel, the finish kernel, ev1, the copy of the
+// flag and the counters. What the launch has and where it lies is the plan's to say, never this function's.
+static int pt_render_common(pt_context* c, PtRenderArgs& a, bool stats, hipStream_t stream, int slot_index = -1) {
+    if (slot_index < 0) {
+        if (c->slot[c->slot_oldest].pending) return pt_fail(c, PT_ERR_ARGUMENT, "a render is in flight: pt_render_finish first");
+        slot_index = c->slot_next;
     }
+    PtLaunchQuery q = pt_launch_query_of(c->traits, a, stats);
+    PtLaunchPlan plan;
+    pt_plan_kernel(q, &plan);
+    a.run_variant = plan.choice.run_variant; a.four_waves = plan.choice.four_waves; a.park_slots = plan.choice.park_slots;
+    a.stack_lds_cap = plan.stack_lds_cap;
+    a.grid_share = plan.grid_share;
+    PT_HIP(c, pt_dispatch(a, stats, c->n_cu, stream, &q.grid, false));
+    std::string why;
+    if (int rc = pt_plan_launch(q, &plan, &why)) return pt_fail(c, rc, why);
+    if (c->launch_seq == 0) c->launch_seq = (uint32_t)std::chrono::steady_clock::now().time_since_epoch().count() * 2654435761u;  // a different starting point in every context
+    a.launch_nonce = ++c->launch_seq;
+    a.n_lanes = plan.n_lanes; a.work_div = plan.work_div; a.batch_max = plan.batch_max; a.fine_queues = plan.fine_queues; a.item_stride = plan.item_stride;
+    a.occ_row = plan.occ_row;
+
+    pt_context::Slot& sl = c->slot[slot_index];  // the launch's work buffers are its slot's: another frame may be in flight on the other slot's
+    int rc;
+    if ((rc = pt_reserve(c, sl.spill, plan.spill)) || (rc = pt_reserve(c, sl.stack_spill, plan.stack_spill)) || (rc = pt_reserve(c, sl.misc, plan.misc)) ||
+        (rc = pt_reserve(c, sl.accum, plan.accum)) || (plan.eye_tab && (rc = pt_reserve(c, sl.eye_tab, plan.eye_tab))))
+        return rc;
+    char* const misc = (char*)sl.misc.p;
+    char* const tab = plan.eye_tab ? (char*)sl.eye_tab.p : nullptr;
+    a.accum = (double*)sl.accum.p;
+    a.eye_tab = (const double*)tab;
     a.spill = (double*)sl.spill.p;
     a.stack_spill = (uint32_t*)sl.stack_spill.p;
-    a.work_counter = (unsigned int*)sl.misc.p;
-    a.overflow_flag = (unsigned int*)sl.misc.p + 1;
-    a.counters = (PtCounters*)((char*)sl.misc.p + 256);
-    a.work_queues = (unsigned int*)((char*)sl.misc.p + 256 + sizeof(PtCounters));
-    a.occluders = occ_bytes ? (uint32_t*)((char*)sl.misc.p + misc_head + dark_bytes) : nullptr;
-    a.occ_row = std::max<uint32_t>(a.div_tiles_x.d / std::max<uint32_t>(a.tile_ranks, 1u), 1u);
-    c->last_mode = (uint32_t)a.scene.mode;
-    c->last_variant = pt_choice_variant(choice, tex) | (stats ? PT_KERNEL_COUNTING : 0u);
-    PT_HIP(c, hipMemsetAsync(sl.misc.p, 0, misc_head + dark_bytes + occ_bytes, stream));
-    if (occ_seed) {
-        const uint32_t n_occ = (uint32_t)(occ_bytes / 4);
-        hipLaunchKernelGGL(pt_occ_seed_kernel, dim3((n_occ + 255) / 256), dim3(256), 0, stream, a.occluders, n_occ, occ_hashed ? 1 : 0, occ_seed_value, occ_all, a.scene.n_nodes);
+    a.work_counter = (unsigned int*)misc;
+    a.overflow_flag = (unsigned int*)misc + 1;
+    a.counters = (PtCounters*)(misc + 256);
+    a.work_queues = (unsigned int*)(misc + 256 + sizeof(PtCounters));
+    a.occluders = plan.occ_bytes ? (uint32_t*)(misc + plan.occ_off) : nullptr;
+    PT_HIP(c, hipMemsetAsync(misc, 0, plan.misc, stream));
+    if (plan.occ_seed != PT_OCC_SEED_NONE) {
+        const uint32_t n_occ = (uint32_t)(plan.occ_bytes / 4);
+        hipLaunchKernelGGL(pt_occ_seed_kernel, dim3((n_occ + 255) / 256), dim3(256), 0, stream, a.occluders, n_occ, plan.occ_seed == PT_OCC_SEED_HASHED ? 1 : 0, plan.occ_seed_value, plan.occ_all,
+                           a.scene.n_nodes);
         PT_HIP(c, hipGetLastError());
-        if (getenv("PORTRAYER_VERBOSE")) fprintf(stderr, "[pt_render] occluder table: %u entries seeded (PORTRAYER_OCC_SEED=%s)\n", n_occ, getenv("PORTRAYER_OCC_SEED"));
+        pt_report_occ_seed(n_occ);
     }
-    sl.mode = c->last_mode; sl.variant = c->last_variant; sl.counted = stats;
+    sl.mode = plan.kernel_mode; sl.variant = plan.kernel_variant; sl.counted = stats;
     PT_HIP(c, hipEventRecord(sl.ev0, stream));
     if (a.n_items) {
-        if (eye_table) {  // (behind ev0: pt_stats.kernel_ms pays for it)
-            hipLaunchKernelGGL(pt_eye_table_kernel, dim3((a.scene.n_nodes + 255) / 256), dim3(256), 0, stream, a.scene.inv, (double*)sl.eye_tab.p, (uint32_t)a.scene.n_nodes,
-                               a.cam.eye[0], a.cam.eye[1], a.cam.eye[2]);
+        const uint32_t n_nodes = (uint32_t)a.scene.n_nodes, node_blocks = (n_nodes + 255) / 256;
+        float* const certain = tab ? (float*)(tab + plan.certain_off) : nullptr;
+        if (plan.eye_table) {  // (behind ev0: pt_stats.kernel_ms pays for it)
+            hipLaunchKernelGGL(pt_eye_table_kernel, dim3(node_blocks), dim3(256), 0, stream, a.scene.inv, (double*)tab, n_nodes, a.cam.eye[0], a.cam.eye[1], a.cam.eye[2]);
             PT_HIP(c, hipGetLastError());
         }
-        if (certain_table) {
-            hipLaunchKernelGGL(pt_certain_table_kernel, dim3((a.scene.n_nodes + 255) / 256), dim3(256), 0, stream, a.scene.info, a.scene.fwd, a.scene.inv, (float*)((double*)sl.eye_tab.p + 12 * (size_t)a.scene.n_nodes),
-                               (uint32_t)a.scene.n_nodes);
+        if (plan.certain_table) {
+            hipLaunchKernelGGL(pt_certain_table_kernel, dim3(node_blocks), dim3(256), 0, stream, a.scene.info, a.scene.fwd, a.scene.inv, certain, n_nodes);
             PT_HIP(c, hipGetLastError());
         }
-#ifndef PT_NO_DARK_LIGHTS
-        if (certain_table && dark_lights) {  // (reads the table the kernel above fills)
-            hipLaunchKernelGGL(pt_dark_light_kernel, dim3((uint32_t)a.scene.n_lights), dim3(256), 0, stream, a.scene.lights, (const float*)((const double*)sl.eye_tab.p + 12 * (size_t)a.scene.n_nodes),
-                               (uint32_t*)((char*)sl.misc.p + misc_head), (uint32_t)a.scene.n_nodes);
+#ifndef PT_NO_DARK_LIGHTS  // (a build without the kernel plans no launch of it)
+        if (plan.dark_lights) {  // (reads the table the kernel above fills)
+            hipLaunchKernelGGL(pt_dark_light_kernel, dim3((uint32_t)a.scene.n_lights), dim3(256), 0, stream, a.scene.lights, (const float*)certain, (uint32_t*)(misc + plan.dark_off), n_nodes);
             PT_HIP(c, hipGetLastError());
         }
-        c->dark_slot = dark_bytes ? slot_index : -1; c->dark_lights = (uint32_t)a.scene.n_lights; c->dark_off = misc_head;
 #endif
-        if (list_header) {  // behind the eye table's fill, on the launch's stream: the header, then the slot's records
-            uint32_t* const header = (uint32_t*)((char*)sl.eye_tab.p + list_off);
-#ifndef PT_NO_BACKGROUND_SKIP  // all zero: the list kernel writes word 0 (what follows the header) and counts the queue in word 1
-            PT_HIP(c, hipMemsetD32Async((hipDeviceptr_t)header, 0, 16, stream));
-#else
-            PT_HIP(c, hipMemsetD32Async((hipDeviceptr_t)header, pixel_lists ? 1 : 0, 16, stream));
-#endif
-            if (pixel_lists) {
+        if (plan.list_header) {  // behind the eye table's fill, on the launch's stream: the header, then the slot's records
+            uint32_t* const records = (uint32_t*)(tab + plan.records_off);
+            PT_HIP(c, hipMemsetD32Async((hipDeviceptr_t)(tab + plan.header_off), (int)plan.header_fill, 16, stream));
+            if (plan.pixel_lists) {
                 const uint32_t tiles = a.n_slots / 64u;
-                hipLaunchKernelGGL(pt_pixel_list_kernel, dim3((tiles + PT_PL_BLOCK / 64 - 1) / (PT_PL_BLOCK / 64)), dim3(PT_PL_BLOCK), 0, stream, a, header + 16, list_cap, list_pending,
-                                   PT_PL_LISTS | (background_skip ? PT_PL_QUEUE : 0u));
+                hipLaunchKernelGGL(pt_pixel_list_kernel, dim3((tiles + PT_PL_BLOCK / 64 - 1) / (PT_PL_BLOCK / 64)), dim3(PT_PL_BLOCK), 0, stream, a, records, plan.list_cap, plan.list_pending,
+                                   PT_PL_LISTS | (plan.background_skip ? PT_PL_QUEUE : 0u));
                 PT_HIP(c, hipGetLastError());
-#if !defined(PT_NO_BACKGROUND_SKIP) && !defined(PT_PL_DEPTH_FIRST)
-                if (background_skip) {
-                    hipLaunchKernelGGL(pt_pixel_queue_kernel, dim3((tiles + 255u) / 256u), dim3(256), 0, stream, header + 16, a.n_slots);
+#if !defined(PT_NO_BACKGROUND_SKIP) && !defined(PT_PL_DEPTH_FIRST)  // (likewise)
+                if (plan.background_skip) {
+                    hipLaunchKernelGGL(pt_pixel_queue_kernel, dim3((tiles + 255u) / 256u), dim3(256), 0, stream, records, a.n_slots);
                     PT_HIP(c, hipGetLastError());
                 }
 #endif
             }
         }
-        c->pl_slot = pixel_lists ? slot_index : -1; c->pl_slots = a.n_slots; c->pl_off = list_off + 64; c->pl_nodes = (uint32_t)a.scene.n_nodes; c->pl_queue = background_skip;
-        PT_HIP(c, pt_dispatch(a, stats, c->n_cu, stream, &grid, true));
-        hipLaunchKernelGGL(pt_finish_kernel, dim3((a.n_slots + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, stream, a, background_skip ? 1u : 0u);
+        c->last.slot = slot_index; c->last.plan = plan;
+        PT_HIP(c, pt_dispatch(a, stats, c->n_cu, stream, &q.grid, true));
+        hipLaunchKernelGGL(pt_finish_kernel, dim3((a.n_slots + PT_BLOCK - 1) / PT_BLOCK), dim3(PT_BLOCK), 0, stream, a, plan.background_skip ? 1u : 0u);
         PT_HIP(c, hipGetLastError());
     }
     PT_HIP(c, hipEventRecord(sl.ev1, stream));
     // the overflow flag (always) and the counters (counting build) follow the kernels into the slot's pinned page
-    PT_HIP(c, hipMemcpyAsync(sl.host, sl.misc.p, stats ? PT_SLOT_BYTES : 8, hipMemcpyDeviceToHost, stream));
+    PT_HIP(c, hipMemcpyAsync(sl.host, misc, stats ? PT_SLOT_BYTES : 8, hipMemcpyDeviceToHost, stream));
     PT_HIP(c, hipEventRecord(sl.copy_done, stream));
     return PT_OK;
 }
@@ -2060,7 +2093,7 @@ static int pt_ao_common(pt_context* c, const pt_ao_params* p, const double* d_po
     a.occluded = out.occluded; a.valid = out.valid; a.bent = out.bent;
     const uint64_t per_item = layout == PT_AO_POINT_MAJOR ? 64u >> a.log2_samples : 64u;  // points of a wavefront
     a.r.n_items = (uint32_t)((p->n + per_item - 1) / per_item);                          // (n <= PT_AO_MAX = 2^24: at most 2^24 items)
-    a.r.stack_lds_cap = pt_stack_lds_cap(a.r.scene, pt_ao_waves(a.r.scene.mode) == 3 ? 52 * 1024 : 39 * 1024, pt_ao_frame_bytes(layout));  // (pt_walk_sizing's budgets)
+    a.r.stack_lds_cap = pt_stack_lds_cap(a.r.scene, pt_block_budget(pt_ao_waves(a.r.scene.mode)), pt_ao_frame_bytes(layout));  // (as pt_walk_sizing)
     a.r.grid_share = 1;
     uint32_t grid = 0;
     PT_HIP(c, pt_ao_dispatch(a, layout, c->n_cu, stream, &grid, false));
@@ -2173,7 +2206,7 @@ static int pt_direct_common(pt_context* c, const pt_direct_params* p, const doub
     a.set = pt_direct_set(p);
     a.sum = out.sum; a.lit = out.lit; a.valid = out.valid;
     a.r.n_items = (uint32_t)((p->n + 63u) / 64u);  // (n <= PT_AO_MAX = 2^24)
-    a.r.stack_lds_cap = pt_stack_lds_cap(a.r.scene, pt_direct_waves(a.r.scene.mode) == 3 ? 52 * 1024 : 39 * 1024, pt_direct_frame_bytes());  // (pt_walk_sizing's budgets)
+    a.r.stack_lds_cap = pt_stack_lds_cap(a.r.scene, pt_block_budget(pt_direct_waves(a.r.scene.mode)), pt_direct_frame_bytes());  // (as pt_walk_sizing)
     a.r.grid_share = 1;
     uint32_t grid = 0;
     PT_HIP(c, pt_direct_dispatch(a, c->n_cu, stream, &grid, false));
@@ -2996,8 +3029,7 @@ static int pt_film_denoise_queue(pt_context* c, pt_film* f, const pt_denoise_par
     const size_t n = f->counts.size();
     int rc;
     if ((rc = pt_reserve(c, f->dn_work[0], n * 32)) || (rc = pt_reserve(c, f->dn_work[1], n * 32))) return rc;
-    bool tiled = true;  // the LDS-tiled form, the faster one at 5 levels by more than three spreads (profiles/denoise/notes.md), unless the switch says otherwise
-    if (const char* e = getenv("PORTRAYER_DENOISE_TILE")) tiled = atoi(e) > 0;
+    const bool tiled = pt_env_on("PORTRAYER_DENOISE_TILE", true);  // the LDS-tiled form, the faster one at 5 levels by more than three spreads (profiles/denoise/notes.md), unless the switch says otherwise
     const uint32_t* count = (const uint32_t*)f->count.p;
     const double* q = f->moments ? (const double*)f->q.p : nullptr;
     if (d_albedo) PT_HIP(c, pt_denoise_albedo_seed_launch(f->width, f->height, (const double*)f->total.p, (const double*)f->partial.p, count, q, g.node, d_albedo, (double*)f->dn_work[0].p, stream));
@@ -3198,7 +3230,7 @@ extern "C" int pt_measure_copy_bandwidth(pt_context* c, uint64_t bytes, int iter
         PT_HIP(c, hipEventElapsedTime(&ms, c->slot[0].ev0, c->slot[0].ev1));
         if (i > 0 && ms > 0.f) {
             const double rate = 2.0 * (double)(n * 16) / (ms * 1e-3) / 1e9;
-            if (getenv("PORTRAYER_VERBOSE")) fprintf(stderr, "[pt_measure_copy_bandwidth] form %d: %.0f GB/s\n", form, rate);
+            if (pt_env_set("PORTRAYER_VERBOSE")) fprintf(stderr, "[pt_measure_copy_bandwidth] form %d: %.0f GB/s\n", form, rate);
             best = std::max(best, rate);
         }
     }

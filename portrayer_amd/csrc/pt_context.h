@@ -63,6 +63,82 @@ static int pt_scene_mode(const PtSceneTraits& t) {
     return !t.has_meshes ? PT_MODE_FLAT_NOMESH : (t.has_kdmesh ? PT_MODE_FLAT_KDMESH : PT_MODE_FLAT);
 }
 
+// ------------------------------------------------------------------------------------------------
+// Environment switches (PORTRAYER_*), read at every launch - tests flip them between launches of one process - in three forms.
+// ------------------------------------------------------------------------------------------------
+// Set at all, whatever to (experiments, PORTRAYER_VERBOSE).
+static bool pt_env_set(const char* name) { return getenv(name) != nullptr; }
+// On / off: unset -> `unset`; set -> on exactly where atoi() of it is positive ("0", "", words: off).
+static bool pt_env_on(const char* name, bool unset) {
+    const char* e = getenv(name);
+    return e ? atoi(e) > 0 : unset;
+}
+// A lenient integer: unset -> `unset`; set -> atoi() of it, clamped to lo .. hi.
+static int pt_env_clamped(const char* name, int unset, int lo, int hi) {
+    const char* e = getenv(name);
+    return e ? std::max(lo, std::min(hi, atoi(e))) : unset;
+}
+// A strict unsigned integer: unset or empty -> true, *value untouched; all of it a decimal number in lo .. hi -> true, *value set; anything else -> false and
+// *why = "NAME=text: expected lo .. hi".
+static bool pt_env_strict(const char* name, unsigned long long lo, unsigned long long hi, uint32_t* value, std::string* why) {
+    const char* e = getenv(name);
+    if (!e || !*e) return true;
+    char* end = nullptr;
+    const unsigned long long v = strtoull(e, &end, 10);
+    if (end == e || *end || v < lo || v > hi) {
+        *why = std::string(name) + "=" + e + ": expected " + std::to_string(lo) + " .. " + std::to_string(hi);
+        return false;
+    }
+    *value = (uint32_t)v;
+    return true;
+}
+// PORTRAYER_PARK=0: every parked recursion frame in HBM (tests, measurements) - the render's interpreter kernels and the interpreter passes alike
+static bool pt_env_park() { return pt_env_on("PORTRAYER_PARK", true); }
+
+// The LDS a block may take where `waves` wavefronts per SIMD are to be resident: a CU has 160 KB, a block is four wavefronts, one per SIMD - 3 x 52 KB, 4 x 39 KB,
+// 5 x 31 KB or 6 x 26 KB.
+static size_t pt_block_budget(int waves) { return (size_t)(waves >= 6 ? 26 : (waves == 5 ? 31 : (waves == 4 ? 39 : 52))) * 1024; }
+
+// ------------------------------------------------------------------------------------------------
+// A render launch as planned (pt_api.hip: pt_choose_kernel, pt_plan_launch) - what pt_render_common commits.
+// ------------------------------------------------------------------------------------------------
+// Which render kernel a scene runs: PtRenderArgs::run_variant, the waves per SIMD its instantiation is compiled for (PtRenderArgs::four_waves: 0 = three),
+// the parked frames kept in LDS and the LDS a block may take.
+struct PtKernelChoice {
+    int run_variant = PT_RUN_LINE3, four_waves = 0, park_slots = 0;
+    size_t block_budget = 0;
+    bool needs_spill = false;  // the lanes keep recursion frames in HBM
+};
+enum PtOccSeed { PT_OCC_SEED_NONE = 0, PT_OCC_SEED_HASHED = 1, PT_OCC_SEED_ALL = 2 };  // PORTRAYER_OCC_SEED: unset, <seed>, all:K
+struct PtLaunchPlan {
+    PtKernelChoice choice;
+    uint32_t kernel_mode = 0, kernel_variant = 0;  // pt_stats' words, PT_KERNEL_COUNTING included
+    int stack_lds_cap = 0;
+    uint32_t grid_share = 1;
+    // how the work items are dealt
+    uint32_t n_lanes = 0, work_div = 1, batch_max = 0, fine_queues = 0, item_stride = 1;
+    // the slot's buffers, in bytes
+    size_t spill = 0, stack_spill = 0, misc = 0, accum = 0, eye_tab = 0;
+    //   misc:    [0 work counter, overflow flag | 256 PtCounters | work queues | dark_off: dark-light records | occ_off: occluder table | misc)
+    //   eye_tab: [0 eye table | certain_off: certain-shadow table | header_off: list header, 64 bytes | records_off: records | queue_off: queue, tile masks | eye_tab)
+    // A region the launch does not have is empty and its offset the next region's.
+    size_t dark_off = 0, dark_bytes = 0, occ_off = 0, occ_bytes = 0;
+    size_t certain_off = 0, header_off = 0, records_off = 0, queue_off = 0;
+    // what the launch has (dark_lights: the kernel that fills the records runs - they are zeroed in any case)
+    bool eye_table = false, certain_table = false, dark_lights = false, list_header = false, pixel_lists = false, background_skip = false;
+    uint32_t list_cap = 0, list_pending = 0, occ_row = 1;
+    uint32_t header_fill = 0;         // the word the list header's 16 are set to in front of the list kernel
+    int occ_seed = PT_OCC_SEED_NONE;  // PtOccSeed ...
+    uint64_t occ_seed_value = 0;      // ... hashed: the seed ...
+    uint32_t occ_all = 0;             // ... all:K: K
+    uint32_t n_slots = 0, n_nodes = 0, n_lights = 0;  // what the regions are sized by
+};
+// What the context's last render launch left behind, for the pt_test_* hooks: its slot (-1: no launch with work items yet) and its plan.
+struct PtLastLaunch {
+    int slot = -1;
+    PtLaunchPlan plan;
+};
+
 struct pt_film;
 struct pt_context {
     int device = 0;
@@ -101,15 +177,7 @@ struct pt_context {
     Slot slot[PT_SLOTS];
     int slot_next = 0;     // the slot the next launch takes
     int slot_oldest = 0;   // the oldest launch not yet closed (== slot_next: none, unless every slot is pending)
-    uint32_t last_mode = 0, last_variant = 0;
-    int pl_slot = -1;          // pt_test_pixel_list_summary: the slot whose eye_tab buffer holds the last launch's pixel lists (-1: that launch had none) ...
-    uint32_t pl_slots = 0;     // ... its pixel slots ...
-    size_t pl_off = 0;         // ... where its records start in the buffer ...
-    uint32_t pl_nodes = 0;     // ... and the scene's flattened nodes (pt_test_pixel_list_records)
-    bool pl_queue = false;     // ... and whether the queue of the pixels that need the render kernel lies behind them (pt_test_pixel_list_queue)
-    int dark_slot = -1;        // pt_test_dark_lights: the slot whose misc buffer holds the last launch's dark-light records (-1: that launch had none) ...
-    uint32_t dark_lights = 0;  // ... the scene's lights ...
-    size_t dark_off = 0;       // ... and where the records start in the buffer (in front of the occluder table)
+    PtLastLaunch last;     // what the last render launch left behind (the pt_test_* hooks)
     // The three passes beside the render, each with a PtPass of its own: all three may be in flight at once, with two renders. Beside it, what is the kind's.
     // The primary-visibility pass (pt_aov / pt_aov_device ... pt_aov_finish): the device copies of the host-buffer path's six outputs.
     // The guides pass (pt_guides ...) runs on the SAME pass - one of the two in flight, one set of stack columns - and its host-buffer path takes position, normal and

@@ -342,7 +342,7 @@ static hipError_t pt_launch_kernel(size_t lds, const PtRenderArgs& a, int n_cu, 
     return pt_launch_kernel_args<KERNEL>(lds, a, a.n_items, a.grid_share, n_cu, stream, grid_out, launch);
 }
 
-// Which kernel runs (`variant`, chosen in pt_render_common):
+// Which kernel runs (`variant`, chosen by pt_choose_kernel):
 //   PT_RUN_INTERP / PT_RUN_INTERP_PARK   the interpreter kernel (scenes with reflective materials: hits spawn rays), every parked
 //                                        recursion frame in HBM / the youngest in LDS; 3 waves per SIMD
 //   PT_RUN_INTERP_FORK                   PT_RUN_INTERP_PARK + fork / join: idle lanes take the refracted subtrees busy lanes offer (pt_shade.h)

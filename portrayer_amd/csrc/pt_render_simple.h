@@ -153,7 +153,7 @@ PT_HD PtKdLayout pt_kd_layout(const PtRenderArgs& a) {
         l.lane_rows = r < 0 ? 0 : r;
     }
     l.wrows = cap - l.lane_rows;  // >= 1
-    if (l.wrows < l.srows + 2 && 3 * a.scene.kd_levels > l.srows * 64 - a.scene.stack_cap) {  // room for the path table comes first (pt_render_common keeps cap >= srows + 2 in these semantics)
+    if (l.wrows < l.srows + 2 && 3 * a.scene.kd_levels > l.srows * 64 - a.scene.stack_cap) {  // room for the path table comes first (pt_stack_lds_cap keeps cap >= srows + 2 in these semantics)
         l.wrows = cap < l.srows + 2 ? cap : l.srows + 2;
         l.lane_rows = cap - l.wrows;
     }
@@ -320,7 +320,7 @@ __global__ void __launch_bounds__(PT_BLOCK, WAVES) pt_render_simple_kernel(PtRen
             }
             const unsigned q = q_next++;
             if (q >= PT_ITEMS_DEALT) break;
-            w = a.item_stride == 1u ? q : (unsigned)(((unsigned long long)q * a.item_stride) % a.n_items);  // (a launch with a queue has item_stride 1: pt_render_common)
+            w = a.item_stride == 1u ? q : (unsigned)(((unsigned long long)q * a.item_stride) % a.n_items);  // (a launch with a queue has item_stride 1: pt_plan_launch)
         } else {  // one item at a time from interleaved queues
             for (;;) {
                 unsigned idx = 0;
@@ -596,7 +596,7 @@ __global__ void __launch_bounds__(PT_BLOCK, WAVES) pt_render_simple_kernel(PtRen
                 // nothing else.
                 constexpr bool CERTAIN = OCC && MODE == PT_MODE_FLAT_NOMESH;
                 [[maybe_unused]] PtOccHint hint{0u, 0u, 0u, (STATS && dark) ? 4u : 0u};
-                if (CERTAIN && occ.entry) {  // (a launch of this mode that has an occluder table has the certain-shadow table: pt_render_common)
+                if (CERTAIN && occ.entry) {  // (a launch of this mode that has an occluder table has the certain-shadow table: pt_plan_launch)
                     const float* const certain_tab = (const float*)(a.eye_tab + 12 * (size_t)sc.n_nodes);
                     const uint32_t* const entry = (const uint32_t*)pt_uniform_ptr(occ.entry);
                     hint.own = PT_UNIFORM_U32(entry[0]);

@@ -141,7 +141,7 @@ struct PtRenderArgs {
     uint32_t grid_share;             // host side only: the launch gets 1 / grid_share of the device's resident blocks (pt_node: ranks that share a GPU; 0 or 1 = all of them)
     int32_t park_slots;              // parked recursion frames per lane kept in LDS (0 or 1; selects the PARK instantiation); older ones in `spill`
     int32_t four_waves;              // the instantiation compiled for more than 3 waves per SIMD (scenes without reflective materials only): 0, or 4 / 5 = the waves
-    int32_t run_variant;             // PT_RUN_* (pt_render_kernel.h): which kernel pt_render_common launches
+    int32_t run_variant;             // PT_RUN_* (pt_render_kernel.h): which kernel the launch runs (pt_choose_kernel)
     uint32_t launch_nonce;           // differs from launch to launch of a context (24 bits): mailbox tickets of an earlier launch never match
     unsigned int* work_counter;
     unsigned int* overflow_flag;     // set to 1 by any lane that runs out of traversal stack

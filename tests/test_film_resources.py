@@ -66,9 +66,10 @@ def test_the_wave_count_is_the_one_the_source_states():
     # the LDS budget stands once, in the sizing the interpreter passes share; the film's argument block calls it, and both of its queueing functions build that block
     api = open(os.path.join(CSRC, "pt_api.hip")).read()
     sizing = function_body(api, "static PtInterp pt_interp_sizing(")
-    assert re.search(r"r\.stack_lds_cap = pt_stack_lds_cap\(r\.scene, 52 \* 1024, frame_bytes\);\s*// 3 x 52 KB of the CU's 160 KB \(pt_radiance_waves, pt_film_waves\)", sizing), \
-        "the film sizes its LDS for three blocks per CU"
-    assert "pt_kd_semantics(sc.mode)" in function_body(api, "static int pt_stack_lds_cap(const PtSceneView& sc, size_t block_budget, size_t frame_bytes)")
+    assert re.search(r"r\.stack_lds_cap = pt_stack_lds_cap\(r\.scene, pt_block_budget\(3\), frame_bytes\);", sizing), "the film sizes its LDS for three blocks per CU"
+    budget = open(os.path.join(CSRC, "pt_context.h")).read()  # ... where pt_block_budget(3) is 52 KB: 3 x 52 KB of the CU's 160 KB
+    assert re.search(r"static size_t pt_block_budget\(int waves\) \{ return \(size_t\)\(waves >= 6 \? 26 : \(waves == 5 \? 31 : \(waves == 4 \? 39 : 52\)\)\) \* 1024; \}", budget), "three blocks per CU: 52 KB each"
+    assert "pt_kd_semantics(mode)" in function_body(api, "static int pt_stack_lds_cap(int mode, int stack_cap, size_t block_budget, size_t frame_bytes)")
     assert "k = pt_interp_sizing(c, a.r)" in function_body(api, "static int pt_film_pass_args(")
     for queue in ("static int pt_film_add_common(", "static int pt_film_add_map_common("):
         assert "pt_film_pass_args(c, f, cam, d_background, " in function_body(api, queue), queue

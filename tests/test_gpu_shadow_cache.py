@@ -110,7 +110,7 @@ def test_shadowed_scenes_against_the_oracle(host, H, oracle, monkeypatch, mode, 
 
 
 # ---------------------------------------------------------------------------------------------------
-# Hints the test chooses (PORTRAYER_OCC_SEED, pt_render_common): the table's test must give the same image whatever an entry holds -
+# Hints the test chooses (PORTRAYER_OCC_SEED, pt_plan_launch): the table's test must give the same image whatever an entry holds -
 # the surface being shaded, a node behind the shading point, a node under a transformed or shared group, a node the walk's f32 box
 # test would have culled, none. Only the plain instantiations read the table: seeded renders are compared as plain images and f64 means.
 # ---------------------------------------------------------------------------------------------------

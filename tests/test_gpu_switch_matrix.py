@@ -1,7 +1,7 @@
 """The kernel instantiations only an environment switch reaches, against the oracle - inside the GPU suite (round 4 ran this matrix by hand,
 profiles/r04/calls/c55.sh, and it was the matrix that found the one wrong instantiation, pt_render_kernel<2, true, *, 0> under PORTRAYER_PARK=0).
 
-Every switch of pt_render_common (csrc/pt_api.hip) x four scenes that between them reach every kernel family - dielectric recursion (interpreter, parked
+Every switch of pt_choose_kernel and pt_plan_launch (csrc/pt_api.hip) x four scenes that between them reach every kernel family - dielectric recursion (interpreter, parked
 frame / fork), opaque mirrors (chain kernel), a mesh-free scene (straight-line kernels at 3 - 6 waves per SIMD), meshes (walks inside instances; the host's
 and the device's tree builder) - x the crate's three traversal semantics, counting AND plain instantiation each: u8 pixels, f64 means and ray counts."""
 import numpy as np

@@ -1,10 +1,12 @@
-// Stand-alone driver for a sanitizer run of the slab-test hook (pt_api.hip: pt_test_raypk) on the CPU: `make sanitize-raypk` compiles pt_api.hip's host
+// Stand-alone driver for a sanitizer run of the host-side hooks of pt_api.hip (pt_test_raypk, the beam tests, pt_test_dark_light, pt_test_launch_plan) on the CPU: `make sanitize-raypk` compiles pt_api.hip's host
 // code and this file with -fsanitize=address,undefined, links them with the library's other objects and runs the result. No GPU is touched.
 // Rays and boxes of every kind tests/test_raypk_conservative.py draws: ordinary ones, zero / denormal / huge direction components, boxes at the limit
 // of +-1e18, a face through the origin, infinite and tiny ranges; every body of the constants.
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
+#include <cstring>
 #include <limits>
 #include <random>
 #include <vector>
@@ -137,5 +139,43 @@ int main() {
     if (pt_test_dark_light(0, 0, fwd.data(), inv.data(), P.data(), L.data(), nullptr, flagged.data(), guard.data(), exact.data()) != 0) { std::printf("dark light, n = 0 failed\n"); return 1; }
     if (n_flagged == 0 || n_guard == 0) { std::printf("dark light: nothing flagged\n"); return 1; }
     std::printf("dark light ok: %llu cases x 8 types, %llu flagged, %llu through the guard\n", (unsigned long long)m, (unsigned long long)n_flagged, (unsigned long long)n_guard);
+
+    // The launch planner (pt_test_launch_plan): every mode, plain and counting, with sizes at the ends of their ranges - no nodes, no lights, no slots, the most of each, a
+    // grid of one block and a huge one - under the switches at hostile values; a malformed switch must be refused with its words cut to the caller's buffer.
+    const char* const envs[][2] = {{"PORTRAYER_OCC_SEED", "18446744073709551615"}, {"PORTRAYER_OCC_SEED", "all:0"}, {"PORTRAYER_PIXEL_LIST_CAP", "0"}, {"PORTRAYER_PIXEL_LIST_PENDING", "1"},
+                                   {"PORTRAYER_FINE_QUEUES", "2147483647"}, {"PORTRAYER_BATCH_MAX", "-2147483648"}, {"PORTRAYER_ITEM_STRIDE", "golden"}, {"PORTRAYER_ITEM_STRIDE", "-7"},
+                                   {"PORTRAYER_LDS_STACK", "0"}, {"PORTRAYER_LDS_BUDGET_KB", "999"}};
+    const uint32_t ends[] = {0u, 1u, 64u, 65536u, 65537u, 0xFFFFFFC0u};
+    uint64_t plans = 0, lists = 0;
+    for (int env = -1; env < 10; env++) {
+        if (env >= 0) setenv(envs[env][0], envs[env][1], 1);
+        for (int k = 0; k < 54; k++) {
+            pt_launch_query q = {};
+            q.traits.traverse = 1 + k % 3; q.traits.n_nodes = ends[(k / 5) % 6]; q.traits.n_lights = ends[(k / 2) % 4]; q.traits.reflective = k % 5 == 0; q.traits.reflective_opaque = k % 2;
+            q.mode = k % 10 == 0 ? -1 : 1 + k % 9; q.textured = k % 4 == 0; q.stats = k % 3 == 0;
+            q.n_nodes = q.traits.n_nodes; q.n_lights = q.traits.n_lights; q.stack_cap = (int32_t)(1 + ends[k % 5] % 4096u);
+            q.n_slots = ends[(k / 3) % 6]; q.n_chunks = 1 + k % 13; q.k_log2 = 3; q.c_log2 = 2 + k % 2; q.n_items = ends[(k / 3) % 6] / 64u * 64u;
+            q.tiles_x = ends[k % 6]; q.tile_ranks = ends[(k / 6) % 3]; q.grid = (k % 7 == 0) ? 1u : ((k % 7 == 1) ? 0xFFFFFFu : 768u);
+            uint64_t words[PT_PLAN_WORDS];
+            char why[16];
+            rc = pt_test_launch_plan(&q, words, why, sizeof why);
+            if (rc != 0 && !(env == 1 && q.n_nodes == 0)) { std::printf("pt_test_launch_plan (switch %d, case %d) returned %d: %s\n", env, k, rc, why); return 1; }
+            if (rc == 0) { plans++; lists += (words[PT_PLAN_HAS] & PT_PLAN_HAS_PIXEL_LISTS) != 0; }
+            if (rc == 0 && words[PT_PLAN_MISC_BYTES] != words[PT_PLAN_OCC_OFF] + words[PT_PLAN_OCC_BYTES]) { std::printf("switch %d, case %d: misc does not end with the occluder table\n", env, k); return 1; }
+        }
+        if (env >= 0) unsetenv(envs[env][0]);
+    }
+    pt_launch_query q = {};
+    q.traits.traverse = 1; q.traits.n_nodes = q.n_nodes = 5; q.traits.n_lights = q.n_lights = 2; q.traits.reflective_opaque = 1; q.mode = -1; q.stack_cap = 16;
+    q.n_slots = 256; q.n_items = 16384; q.n_chunks = 8; q.k_log2 = q.c_log2 = 3; q.tiles_x = 2; q.tile_ranks = 1; q.grid = 768;
+    uint64_t words[PT_PLAN_WORDS];
+    char why[24];
+    setenv("PORTRAYER_PIXEL_LIST_CAP", "a value far longer than the buffer its refusal is copied to", 1);
+    if (pt_test_launch_plan(&q, words, why, sizeof why) != -1 || std::strlen(why) != sizeof why - 1) { std::printf("a malformed list cap was not refused\n"); return 1; }
+    if (pt_test_launch_plan(&q, words, nullptr, 0) != -1 || pt_test_launch_plan(&q, nullptr, why, sizeof why) != -1 || pt_test_launch_plan(nullptr, words, why, sizeof why) != -1) { std::printf("NULL arguments\n"); return 1; }
+    unsetenv("PORTRAYER_PIXEL_LIST_CAP");
+    if (pt_test_launch_plan(&q, words, why, sizeof why) != 0 || !(words[PT_PLAN_HAS] & PT_PLAN_HAS_QUEUE)) { std::printf("the five-node launch has no queue\n"); return 1; }
+    if (lists == 0) { std::printf("launch plan: no case had lists\n"); return 1; }
+    std::printf("launch plan ok: %llu plans, %llu with lists\n", (unsigned long long)plans, (unsigned long long)lists);
     return 0;
 }
